@@ -12,10 +12,19 @@ resident in HBM (weights resident, H2D/D2H excluded).
            semantics (tile_pad 32, hat_model.py:40-108), one tile per rank, one RCCL all-gather of
            the output cores per step  ->  "strong" scaling.  (`--mode frames` instead gives every
            rank its own full frame, no collective: "weak" scaling.)
-Prints ONE JSON line on rank 0.  `roofline` describes the dominant kernel (largest share of the
-step), timed live with HIP events on the launch stream; `cpu_baseline` is the CPU oracle (a
-restatement of the reference forward, pinned to reference-generated goldens) timed on the host
-cores on a bounded crop of the same workload.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the `--steps` steps and
+prints the headline (`value`, `ms_per_step`); `roofline`, `kernels` and `cpu_baseline` are null.
+With `--full` it also measures what takes runs of its own: `roofline` describes the dominant kernel
+(largest share of the step), timed live with HIP events on the launch stream; `path_f32` times the
+exact-fp32 path; `cpu_baseline` is the CPU oracle (a restatement of the reference forward, pinned
+to reference-generated goldens) timed on the host cores on a bounded crop of the same workload.
+
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR
+
+`--dump-outputs DIR` writes, on rank 0, what the last timed step returned (the SR frame, cropped
+to H*s x W*s) as float32 / float64 .npy files: see `dump_outputs`.  Inputs and weights are seeded,
+so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import json
@@ -102,6 +111,37 @@ def f32_path(args, cfg, x, dev, fl_frame):
             "frac_of_f32_mfma_peak": round(tf / MFMA_PEAK_TFLOPS["f32"], 4), "peak_tflops": MFMA_PEAK_TFLOPS["f32"]}
 
 
+DUMP_SEED = 20240601
+DUMP_SAMPLE = 4 << 20   # float32 elements of the seeded sample: 16 MB
+
+
+def dump_outputs(y, out_dir):
+    """What the timed path returned in its last step, within 64 MB: the whole frame is 176 MB at 720p x4.
+      sr_output_sample.npy        float32 [min(numel, DUMP_SAMPLE)]: the frame at DUMP_SEED-chosen flat indices (ascending)
+      sr_output_crop_corner.npy   float32 [C, 256, 256]: the top-left corner crop at full resolution
+      sr_output_crop_centre.npy   float32 [C, 256, 256]: the centre crop
+      sr_output_stats.npy         float64 [C, 5]: per channel mean, std, min, max, sum of |y| over the whole frame
+    (smaller frames give smaller crops).  Only the output shape decides the sample, not the data."""
+    import numpy as np
+    a = y.detach().float().cpu().numpy()[0]   # [C, H, W]; B == 1 here
+    os.makedirs(out_dir, exist_ok=True)
+    flat = a.reshape(-1)
+    k = min(flat.size, DUMP_SAMPLE)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.size, size=k, replace=False))
+    C, Ho, Wo = a.shape
+    c = min(256, Ho, Wo)
+    r0, c0 = (Ho - c) // 2, (Wo - c) // 2
+    d = a.astype(np.float64).reshape(C, -1)
+    files = {
+        "sr_output_sample": np.ascontiguousarray(flat[idx], dtype=np.float32),
+        "sr_output_crop_corner": np.ascontiguousarray(a[:, :c, :c], dtype=np.float32),
+        "sr_output_crop_centre": np.ascontiguousarray(a[:, r0:r0 + c, c0:c0 + c], dtype=np.float32),
+        "sr_output_stats": np.stack([d.mean(1), d.std(1), d.min(1), d.max(1), np.abs(d).sum(1)], axis=1),
+    }
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -116,10 +156,17 @@ def main():
                     help="N>1: one frame cut in independent tiles (reference tile semantics), one frame per rank, or one frame "
                          "sharded EXACTLY into row bands that exchange halo rows and pool sums (SURVEY §8 f4)")
     ap.add_argument("--tile-pad", type=int, default=32)
-    ap.add_argument("--cpu-crop", type=int, default=256, help="side of the crop timed on the CPU (0 disables the baseline)")
-    ap.add_argument("--no-kernel-profile", action="store_true")
-    ap.add_argument("--no-f32-path", action="store_true", help="skip the exact-fp32 path timing reported beside the bf16 headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the per-kernel roofline, the exact-fp32 path and the CPU baseline "
+                         "(a plain run does only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/*.npy (rank 0; see dump_outputs)")
+    ap.add_argument("--cpu-crop", type=int, default=256, help="--full: side of the crop timed on the CPU (0 disables the baseline)")
+    ap.add_argument("--no-kernel-profile", action="store_true", help="--full: skip the per-kernel timing")
+    ap.add_argument("--no-f32-path", action="store_true", help="--full: skip the exact-fp32 path timing reported beside the bf16 headline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as children, BEFORE anything in
@@ -206,9 +253,11 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        y = step()
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(y[..., :H * s, :W * s], args.dump_outputs)   # before anything else can reuse the output's buffer
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -219,7 +268,7 @@ def main():
 
     # ---- per-kernel timing with HIP events on the launch stream (rank 0) -------------------------
     roofline, kernels = None, None
-    if rank == 0 and not args.no_kernel_profile:
+    if rank == 0 and args.full and not args.no_kernel_profile:
         agg, layers = {}, {}
         reps = 2
         for _ in range(reps):
@@ -302,9 +351,9 @@ def main():
             "roofline": roofline,
             "kernels": kernels,
         }
-        if world == 1 and args.dtype == "bf16" and not args.no_f32_path:
+        if world == 1 and args.full and args.dtype == "bf16" and not args.no_f32_path:
             res["path_f32"] = f32_path(args, cfg, x, dev, fl_frame)
-        if world == 1 and args.cpu_crop > 0:
+        if world == 1 and args.full and args.cpu_crop > 0:
             # the GPU box gives one GPU a share of 16 host cores; more threads than that only oversubscribe
             cores = min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
             res["cpu_baseline"] = cpu_baseline(args.model, s, args.cpu_crop, cores)

@@ -1,6 +1,6 @@
 """CPU-side checks of the PRODUCT package (no kernels run): the `HAT` module's state-dict surface against the one recorded
 from the reference itself (tests/golden/state_dict_surface.json), the weights-version bookkeeping that decides when the
-packed engine is rebuilt, the dataset GT crop, and bench.py's self-launch of its ranks."""
+packed engine is rebuilt, the dataset GT crop, bench.py's self-launch of its ranks and its output dump."""
 import json
 import os
 import subprocess
@@ -116,6 +116,34 @@ def test_bench_self_launches_its_ranks():
     assert r.returncode != 0
     assert r.stderr.count("bench.py needs an MI355X") >= 2, r.stderr[-2000:]
     assert "WORLD_SIZE=1" not in r.stderr
+
+
+def test_bench_dump_outputs_is_bounded_and_seeded(tmp_path):
+    """bench.py --dump-outputs on a frame of the headline's output size (3x2880x5120): float32 / float64 files only, at
+    most 64 MB in all, the same sample positions on every call, and values that are the frame's own."""
+    import bench
+    y = torch.rand(1, 3, 2880, 5120, generator=torch.Generator().manual_seed(3))
+    bench.dump_outputs(y, str(tmp_path / "a"))
+    bench.dump_outputs(y.clone(), str(tmp_path / "b"))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["sr_output_crop_centre.npy", "sr_output_crop_corner.npy", "sr_output_sample.npy", "sr_output_stats.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    f = y[0].numpy()
+    assert np.array_equal(np.load(tmp_path / "a" / "sr_output_crop_corner.npy"), f[:, :256, :256])
+    assert np.array_equal(np.load(tmp_path / "a" / "sr_output_crop_centre.npy"), f[:, 1312:1568, 2432:2688])
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(f.size, size=bench.DUMP_SAMPLE, replace=False))
+    assert np.array_equal(np.load(tmp_path / "a" / "sr_output_sample.npy"), f.reshape(-1)[idx])
+    st = np.load(tmp_path / "a" / "sr_output_stats.npy")
+    assert st.shape == (3, 5) and np.allclose(st[:, 0], f.reshape(3, -1).astype(np.float64).mean(1))
+
+
+def test_bench_has_full_and_dump_options():
+    """A plain run does only the headline; `--full` adds the per-kernel roofline, the fp32 path and the CPU baseline."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
 
 
 def test_pack_cab_w2f_is_the_expand_weight_in_fragment_order():

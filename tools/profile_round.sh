@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 cd /tmp
 O=$R/gpurun_out
 rm -rf $O/prof_fin $O/pmcS_fin $O/pmcI_fin $O/pmcF_fin $O/pmcW_fin
-( cd $R && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_fin -- python3 bench.py --steps 5 --warmup 2 --cpu-crop 0 --no-f32-path > $O/prof_fin_bench.json 2> $O/prof_fin.err ) || { tail -5 $O/prof_fin.err; exit 1; }
+( cd $R && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_fin -- python3 bench.py --full --steps 5 --warmup 2 --cpu-crop 0 --no-f32-path > $O/prof_fin_bench.json 2> $O/prof_fin.err ) || { tail -5 $O/prof_fin.err; exit 1; }
 echo "kernel trace done"
 ( cd $R && timeout -k 10 400 rocprofv3 --pmc SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAVES SQ_WAVE_CYCLES --output-format csv -d $O/pmcS_fin -- python3 tools/run_forward.py > $O/pmcS_fin.log 2>&1 ) || { tail -5 $O/pmcS_fin.log; exit 1; }
 echo "pmc S done"

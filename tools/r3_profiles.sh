@@ -17,7 +17,7 @@ done
 unset HAT_TAIL_V2
 echo "L2 passes done"
 rm -rf $O/prof_hatl
-( cd $R && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_hatl -- python3 bench.py --model HAT-L --height 512 --width 512 --steps 5 --warmup 2 --cpu-crop 0 --no-f32-path > $O/r03_final/r03_hatl_bench_under_rocprof.json 2> $O/prof_hatl.err ) || { tail -5 $O/prof_hatl.err; exit 1; }
+( cd $R && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_hatl -- python3 bench.py --full --model HAT-L --height 512 --width 512 --steps 5 --warmup 2 --cpu-crop 0 --no-f32-path > $O/r03_final/r03_hatl_bench_under_rocprof.json 2> $O/prof_hatl.err ) || { tail -5 $O/prof_hatl.err; exit 1; }
 cp $(ls $O/prof_hatl/*/*kernel_stats.csv | head -1) $O/r03_final/r03_hatl_kernel_stats.csv
 find $O/prof_hatl -name "*kernel_trace.csv" -delete
 echo "HAT-L stats done"
@@ -25,4 +25,4 @@ cd $R
 tools/gap_trace.sh > $O/r03_final/r03_gap_trace.txt 2>&1 || { tail -5 $O/r03_final/r03_gap_trace.txt; exit 1; }
 cat $O/r03_final/r03_gap_trace.txt | head -30
 timeout -k 10 400 python tools/bench_configs.py > $O/r03_final/r03_bench_configs.txt 2>&1; cat $O/r03_final/r03_bench_configs.txt
-timeout -k 10 400 python bench.py > $O/r03_final/r03_final_bench_default.json 2> $O/r03_bench_default.err; head -c 400 $O/r03_final/r03_final_bench_default.json
+timeout -k 10 400 python bench.py --full > $O/r03_final/r03_final_bench_default.json 2> $O/r03_bench_default.err; head -c 400 $O/r03_final/r03_final_bench_default.json
