@@ -62,7 +62,7 @@ typedef struct HatConvDesc {
     const void* w;        /* packed weights (T) */
     const float* bias;    /* [n_slices*nt*16] fp32, zero padded */
     void* out;
-    const float* r1;      /* optional fp32 residual, NHWC stride ldr1 */
+    const float* r1;      /* optional fp32 residual, NHWC stride ldr1 (FP16 rows when reserved0 bit 0 is set) */
     const void* r2;       /* optional T residual, NHWC stride ldr2, scaled per channel by r2scale */
     const float* r2scale; /* [B][r2scale_bstride] fp32 */
     float* colsum;        /* optional [B][tiles][n_slices*nt*16] per-tile column sums */
@@ -96,6 +96,13 @@ typedef struct HatConvDesc {
     float* gap_out;
     void* n16_out;
     int32_t gap_c;
+    /* The residual stream as FP16 rows (B,H,W,C) instead of fp32 ones: bit 0 = r1 is FP16 rows (8-byte aligned), bit 1 = the
+     * HAT_O_NHWC_F32 output is stored as FP16 rows (16-byte aligned, ldo % 8 == 0; round to nearest, clamped to +-65504).
+     * Conversion on load is exact.  The fused LayerNorm, its GAP partials and n16_out are computed from the UNROUNDED fp32
+     * result, as hat_hab_tail3 does with an FP16 t_out.  Accepted by hat_conv for bf16, nt == 9, one slice, n_store == 144,
+     * ksize > 1, no colsum (the group conv of the embed_dim-144 models; r1 == out in place works as with fp32), and by
+     * hat_linear for bf16, nt == 9, Cin <= 160, fp32 output with r1 only, one slice, ln_ones == 0 (the OCAB projection,
+     * with or without its fused LayerNorm).  HAT_EINVAL elsewhere; 0 = both fp32. */
     int32_t reserved0;
 } HatConvDesc;
 
@@ -233,7 +240,8 @@ int hat_dwconv_gate(const void* u, const float* wdw, const float* bdw, void* out
  * (the bf16 path's approximation of hat_linear), for embed_dim 144, hidden 288, bf16 (HAT_EUNSUPPORTED otherwise: run the two
  * hat_linear launches).  The hidden tensor stays in registers.
  *   x    (B,H,W,ldx) T: LayerNorm2 output;  r1 (B,H,W,ldr1) fp32: the residual stream;
- *   out  (B,H,W,ldo): fp32 when out_f32 (may alias r1), else T rows (16-byte aligned, ldo % 8 == 0);
+ *   out  (B,H,W,ldo): fp32 when out_f32 == 1 (may alias r1), else T rows (16-byte aligned, ldo % 8 == 0);
+ *   out_f32 == 2: T rows out and r1 is FP16 rows (8-byte aligned; the 16-bit residual stream, converted exactly); 3 is HAT_EINVAL;
  *   w1f  fc1 as MFMA A fragments [18 n-tiles][4 k-steps][64 lanes][8] bf16 (rows = hidden unit 16 nt + (lane & 15), k = 32 ks +
  *        8 (lane >> 4) + j), followed by the 16-deep tail [18][64 lanes][4] (k = 128 + 4 (lane >> 4) + j);  b1 [288] fp32;
  *   w2f  fc2 as A fragments [9 n-tiles][9 k-steps][64 lanes][8] bf16, rows = output channel, k-slot (g = lane >> 4, j) of k-step kk =

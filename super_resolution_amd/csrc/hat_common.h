@@ -174,6 +174,24 @@ __device__ __forceinline__ void store_pair_f16_if(_Float16* row, int n0, int g, 
     if (pred) *reinterpret_cast<u32x4*>(row + n) = v;
 }
 
+// Four channels of an FP16 row as raw bits (8 bytes).  Loads of the FP16 residual stream keep their results in an INTEGER
+// array until use: parked in float registers through a bit_cast, hipcc once merged the two dwords.
+typedef unsigned h4raw __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ h4raw load_h4raw(const void* p) { return *reinterpret_cast<const h4raw*>(p); }
+__device__ __forceinline__ float h16bits_to_f(unsigned bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
+// exact.  Scalar shifts, no <2 x half> view of the dwords: through such a view hipcc (in the group conv's epilogue) again
+// converted the first dword twice and never read the second.
+__device__ __forceinline__ f32x4 h4raw_to_f32(h4raw r) {
+    const unsigned a = r[0], b = r[1];
+    return f32x4{h16bits_to_f(a & 0xffffu), h16bits_to_f(a >> 16), h16bits_to_f(b & 0xffffu), h16bits_to_f(b >> 16)};
+}
+// four channels -> FP16 (round to nearest even, clamped to the finite range), one 8-byte store
+__device__ __forceinline__ void store_h4(_Float16* p, f32x4 v) {
+    typedef _Float16 v4 __attribute__((ext_vector_type(4)));
+    auto c = [](float x) { return (_Float16)__builtin_amdgcn_fmed3f(x, -65504.0f, 65504.0f); };
+    *reinterpret_cast<v4*>(p) = v4{c(v[0]), c(v[1]), c(v[2]), c(v[3])};
+}
+
 // LDS row stride (in elements) for rows of `n` elements of size `es`, for MFMA operand images read by ds_read_b128
 // with lane (c16, g) -> row base + c16, 16-byte slot k0 + g (bf16) or k0 + 2g (+1) (f32).  The instruction is serviced
 // in the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, {32-35,...}: rows 0-3 and 12-15 of lane group g together

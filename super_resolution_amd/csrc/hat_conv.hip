@@ -61,7 +61,9 @@ __host__ inline bool conv_pick(const HatConvDesc& d, TileCfg* out, size_t* lds) 
     return false;
 }
 
-template <typename T, int WAVES, int PT, int NT>
+// TH: the residual stream's type in the epilogue (hat_conv's reserved0 flags; bf16 group conv only) — bit 0: r1 is FP16 rows,
+// bit 1: the HAT_O_NHWC_F32 output is stored as FP16 rows (round to nearest, clamped to +-65504).  Else fp32.
+template <typename T, int WAVES, int PT, int NT, int TH = 0>
 __global__ __launch_bounds__(WAVES * 64) void conv_kernel(const HatConvDesc d) {
     using M = MT<T>;
     constexpr int NTHR = WAVES * 64;
@@ -370,7 +372,10 @@ __global__ __launch_bounds__(WAVES * 64) void conv_kernel(const HatConvDesc d) {
         };
 #pragma unroll
         for (int ng = 0; ng < NT; ng += NG) {
-            f32x4 r1v[NG][PT], scv[NG], biasv[NG];
+            // (FP16 residual rows wait as raw bits, converted where they are added)
+        using r1_t = std::conditional_t<(TH & 1) != 0, h4raw, f32x4>;
+        r1_t r1v[NG][PT];
+        f32x4 scv[NG], biasv[NG];
             typename Vec4<T>::raw_t r2v[NG][PT];
 #pragma unroll
             for (int i = 0; i < NG; ++i) {
@@ -381,7 +386,10 @@ __global__ __launch_bounds__(WAVES * 64) void conv_kernel(const HatConvDesc d) {
 #pragma unroll
                 for (int pt = 0; pt < PT; ++pt) {
                     const size_t pixc = ((size_t)b * H + min(y0 + wave * PT + pt, H - 1)) * W + min(x0 + c16, W - 1);
-                    if (has_r1) r1v[i][pt] = *reinterpret_cast<const f32x4*>(d.r1 + pixc * d.ldr1 + nc);
+                    if (has_r1) {
+                        if constexpr ((TH & 1) != 0) r1v[i][pt] = load_h4raw(reinterpret_cast<const _Float16*>(d.r1) + pixc * d.ldr1 + nc);
+                        else r1v[i][pt] = *reinterpret_cast<const f32x4*>(d.r1 + pixc * d.ldr1 + nc);
+                    }
                     if (has_r2) r2v[i][pt] = Vec4<T>::load_raw(reinterpret_cast<const T*>(d.r2) + pixc * d.ldr2 + nc);
                 }
             }
@@ -399,7 +407,10 @@ __global__ __launch_bounds__(WAVES * 64) void conv_kernel(const HatConvDesc d) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = v[r] >= 0.f ? v[r] : 0.01f * v[r];
                     }
-                    if (has_r1) v += r1v[i][pt];
+                    if (has_r1) {
+                        if constexpr ((TH & 1) != 0) v += h4raw_to_f32(r1v[i][pt]);
+                        else v += r1v[i][pt];
+                    }
                     if (has_r2) v += scv[i] * Vec4<T>::cvt(r2v[i][pt]);
                     acc[nt][pt] = v;   // (pass B and the fused LayerNorm below need the finished pixel)
                     if constexpr (!TWO_PASS) put(nt, pt, v, csum);
@@ -411,7 +422,22 @@ __global__ __launch_bounds__(WAVES * 64) void conv_kernel(const HatConvDesc d) {
             if (tid < NT * 16) { lnt[tid] = lpg; lnt[NT * 16 + tid] = lpb; }
             lds_barrier();
         }
-        if constexpr (TWO_PASS) {
+        if constexpr ((TH & 2) != 0) {
+            // FP16 rows (host checks: one slice, every channel stored, no column sums, 16-byte rows): n-tile pairs leave as one
+            // 16-byte store per lane, the odd last tile as an 8-byte one.  The fused LayerNorm below reads the unrounded fp32
+            // values, as hat_hab_tail3 does with its FP16 t_out.
+#pragma unroll
+            for (int pt = 0; pt < PT; ++pt) {
+                const int y = y0 + wave * PT + pt, x = x0 + c16;
+                const bool valid = (y < H) && (x < W);
+                _Float16* orow = reinterpret_cast<_Float16*>(d.out) + (((size_t)b * H + min(y, H - 1)) * W + min(x, W - 1)) * d.ldo;
+#pragma unroll
+                for (int nt = 0; nt + 1 < NT; nt += 2) store_pair_f16_if(orow, nt * 16, g, acc[nt][pt], acc[nt + 1][pt], valid);
+                if constexpr ((NT & 1) != 0) {
+                    if (valid) store_h4(orow + (NT - 1) * 16 + 4 * g, acc[NT - 1][pt]);
+                }
+            }
+        } else if constexpr (TWO_PASS) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 f32x4 csum = {0.f, 0.f, 0.f, 0.f};
@@ -505,9 +531,9 @@ __global__ __launch_bounds__(WAVES * 64) void conv_kernel(const HatConvDesc d) {
 
 int* g_occ_query = nullptr;   // hat_conv_occupancy: when set, launch_conv reports workgroups per CU instead of launching
 
-template <typename T, int WAVES, int PT, int NT>
+template <typename T, int WAVES, int PT, int NT, int TH = 0>
 int launch_conv(const HatConvDesc& d, size_t lds, hipStream_t stream) {
-    auto kern = conv_kernel<T, WAVES, PT, NT>;
+    auto kern = conv_kernel<T, WAVES, PT, NT, TH>;
     if (g_occ_query != nullptr) {
         if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(g_occ_query, kern, WAVES * 64, lds);
@@ -531,7 +557,16 @@ int dispatch_nt(const HatConvDesc& d, size_t lds, hipStream_t s) {
         case 1: return launch_conv<T, WAVES, PT, 1>(d, lds, s);
         case 4: return launch_conv<T, WAVES, PT, 4>(d, lds, s);
         case 8: return launch_conv<T, WAVES, PT, 8>(d, lds, s);   // 256 outputs = 2 x 8 tiles exactly (the upsampler convs)
-        case 9: return launch_conv<T, WAVES, PT, 9>(d, lds, s);
+        case 9:
+            if constexpr (sizeof(T) == 2) {   // the group conv of the embed_dim-144 models: FP16 residual stream (reserved0)
+                switch (d.reserved0) {
+                    case 1: return launch_conv<T, WAVES, PT, 9, 1>(d, lds, s);
+                    case 2: return launch_conv<T, WAVES, PT, 9, 2>(d, lds, s);
+                    case 3: return launch_conv<T, WAVES, PT, 9, 3>(d, lds, s);
+                    default: break;
+                }
+            }
+            return launch_conv<T, WAVES, PT, 9>(d, lds, s);
         case 12: return launch_conv<T, WAVES, PT, 12>(d, lds, s);
         default: return HAT_EINVAL;
     }
@@ -546,6 +581,12 @@ int dispatch_tile(const HatConvDesc& d, TileCfg tc, size_t lds, hipStream_t s) {
 
 int conv_validate(const HatConvDesc& d) {
     if (!d.x || !d.w || !d.bias || !d.out) return HAT_EINVAL;
+    if (d.reserved0 & ~3) return HAT_EINVAL;
+    if (d.reserved0) {   // FP16 residual stream: the bf16 group conv only (one slice of nine n-tiles, every channel stored)
+        if (d.dtype != HAT_BF16 || d.nt != 9 || d.n_slices != 1 || d.n_store != 144 || d.colsum || d.ksize == 1) return HAT_EINVAL;
+        if ((d.reserved0 & 1) && (!d.r1 || reinterpret_cast<uintptr_t>(d.r1) % 8)) return HAT_EINVAL;
+        if ((d.reserved0 & 2) && (d.out_mode != HAT_O_NHWC_F32 || d.ldo % 8 || reinterpret_cast<uintptr_t>(d.out) % 16)) return HAT_EINVAL;
+    }
     if (d.B < 1 || d.H < 1 || d.W < 1 || d.Cin < 1) return HAT_EINVAL;
     if (d.ksize < 1 || (d.ksize & 1) == 0 || d.ksize > 17) return HAT_EINVAL;   // (17: the OCAB-ESC kernel of the HATX training config)
     if (d.dtype != HAT_F32 && d.dtype != HAT_BF16) return HAT_EINVAL;

@@ -13,6 +13,7 @@
 // (j < 4) or of tile 2kk + 1 (j >= 4) — ops.pack_ocab_mlp orders fc2's fragments that way (the trick of the attention
 // kernel's P fragment and of hat_ffn2's gate).
 #include <cstdlib>
+#include <type_traits>
 
 #include "hat_common.h"
 
@@ -46,7 +47,8 @@ constexpr int ML_W2F = (ML_NT2 * ML_KK - ML_NREG) * 1024;   // 78848
 constexpr int ML_OFF_W1H = ML_W1F, ML_OFF_W2 = ML_W1F + ML_W1H, ML_OFF_B1 = ML_OFF_W2 + ML_W2F, ML_OFF_B2 = ML_OFF_B1 + ML_HID * 4;
 constexpr int ML_LDS = ML_OFF_B2 + ML_C * 4;       // 163520 <= 163840
 
-template <bool OUTF32, int WAVES>
+// R16: r1 is FP16 rows (the 16-bit residual stream), loaded as raw bits and converted (exactly) where it is added
+template <bool OUTF32, int WAVES, bool R16 = false>
 __global__ __launch_bounds__(WAVES * 64) void ocab_mlp_kernel(const HatMlpDesc d, long npix, long tiles) {
     constexpr int ML_NTHR = WAVES * 64, ML_WAVES = WAVES;
     using M = MT<bf16_t>;
@@ -87,17 +89,21 @@ __global__ __launch_bounds__(WAVES * 64) void ocab_mlp_kernel(const HatMlpDesc d
         for (int ks = 0; ks < 4; ++ks) xb.f[ks] = M::load(row + ks * 32 + 8 * g);
         xb.h = *reinterpret_cast<const s16x4*>(row + 128 + 4 * g);
     };
-    auto load_r = [&](long tile, f32x4 (&r)[ML_NT2]) {
+    using r1_t = std::conditional_t<R16, h4raw, f32x4>;
+    auto load_r = [&](long tile, r1_t (&r)[ML_NT2]) {
         long p = tile * 16 + c16;
         p = p < npix ? p : npix - 1;
 #pragma unroll
-        for (int nt = 0; nt < ML_NT2; ++nt) r[nt] = *reinterpret_cast<const f32x4*>(d.r1 + p * d.ldr1 + nt * 16 + 4 * g);
+        for (int nt = 0; nt < ML_NT2; ++nt) {
+            if constexpr (R16) r[nt] = load_h4raw(reinterpret_cast<const _Float16*>(d.r1) + p * d.ldr1 + nt * 16 + 4 * g);
+            else r[nt] = *reinterpret_cast<const f32x4*>(d.r1 + p * d.ldr1 + nt * 16 + 4 * g);
+        }
     };
 
     const long stride = (long)gridDim.x * ML_WAVES;
     long tile = (long)blockIdx.x * ML_WAVES + wave;
     XB xcur, xnxt;
-    f32x4 r1v[ML_NT2];
+    r1_t r1v[ML_NT2];
     load_x(tile, xcur);
     load_x(tile + stride, xnxt);
     load_r(tile, r1v);
@@ -161,7 +167,8 @@ __global__ __launch_bounds__(WAVES * 64) void ocab_mlp_kernel(const HatMlpDesc d
             for (int f = 0; f < AD; ++f) rd2(f);
 #pragma unroll
             for (int nt = 0; nt < ML_NT2; ++nt) {
-                acc[nt] = *reinterpret_cast<const f32x4*>(b2l + nt * 16 + 4 * g) + r1v[nt];
+                if constexpr (R16) acc[nt] = *reinterpret_cast<const f32x4*>(b2l + nt * 16 + 4 * g) + h4raw_to_f32(r1v[nt]);
+                else acc[nt] = *reinterpret_cast<const f32x4*>(b2l + nt * 16 + 4 * g) + r1v[nt];
 #pragma unroll
                 for (int kk = 0; kk < ML_KK; ++kk) {
                     const int f = nt * ML_KK + kk;
@@ -303,15 +310,20 @@ extern "C" int hat_ocab_mlp(const HatMlpDesc* dp, void* stream) {
     if (d.B < 1 || d.H < 1 || d.W < 1) return HAT_EINVAL;
     if (d.C != ML_C || d.hidden != ML_HID || d.dtype != HAT_BF16) return HAT_EUNSUPPORTED;
     if (d.ldx < ML_C || d.ldx % 8 || d.ldr1 < ML_C || d.ldr1 % 4 || d.ldo < ML_C) return HAT_EINVAL;
-    if (d.out_f32 ? d.ldo % 4 : (d.ldo % 8 || reinterpret_cast<uintptr_t>(d.out) % 16)) return HAT_EINVAL;
+    // out_f32: bit 0 — fp32 output (else T rows); bit 1 — r1 is FP16 rows (the 16-bit residual stream), T-row output only
+    if ((d.out_f32 & ~3) != 0 || d.out_f32 == 3) return HAT_EINVAL;
+    const bool out_f32 = (d.out_f32 & 1) != 0, r16 = (d.out_f32 & 2) != 0;
+    if (r16 && reinterpret_cast<uintptr_t>(d.r1) % 8) return HAT_EINVAL;
+    if (out_f32 ? d.ldo % 4 : (d.ldo % 8 || reinterpret_cast<uintptr_t>(d.out) % 16)) return HAT_EINVAL;
     const long npix = (long)d.B * d.H * d.W, tiles = (npix + 15) / 16;
     static const int waves = getenv("HAT_MLP_WAVES") ? atoi(getenv("HAT_MLP_WAVES")) : 8;    // (A/B switch; 16 waves spill at 128 registers and measured slower)
     const int nw = waves == 8 ? 8 : 16;
     int gx = 256;
     if ((long)gx * nw > tiles) gx = (int)((tiles + nw - 1) / nw);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    void (*kern)(const HatMlpDesc, long, long) = d.out_f32 ? (nw == 8 ? ocab_mlp_kernel<true, 8> : ocab_mlp_kernel<true, 16>)
-                                                            : (nw == 8 ? ocab_mlp_kernel<false, 8> : ocab_mlp_kernel<false, 16>);
+    void (*kern)(const HatMlpDesc, long, long) = out_f32 ? (nw == 8 ? ocab_mlp_kernel<true, 8> : ocab_mlp_kernel<true, 16>)
+                                               : r16 ? (nw == 8 ? ocab_mlp_kernel<false, 8, true> : ocab_mlp_kernel<false, 16, true>)
+                                                     : (nw == 8 ? ocab_mlp_kernel<false, 8> : ocab_mlp_kernel<false, 16>);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, ML_LDS);
     if (e != hipSuccess) return (int)e;
     HAT_LAUNCH(kern, dim3(gx), dim3(nw * 64), ML_LDS, s, d, npix, tiles);

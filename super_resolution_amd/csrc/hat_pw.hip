@@ -12,6 +12,8 @@
 //     so waves free-run and 12-16 of them per CU keep HBM requests in flight;
 //   * the epilogue (bias, GELU, fp32 residual, scaled T residual) is applied on the accumulators: a lane owns
 //     4 consecutive channels of one pixel.
+#include <type_traits>
+
 #include "hat_common.h"
 
 namespace {
@@ -22,7 +24,10 @@ template <bool SPEC_, bool R1_, bool R2_, bool OUTF32_, bool LN_, bool PAIR_ = f
 };
 
 // RES: the launch has residual operands (r1 and/or r2): their loads are batched ahead of the MFMAs (+54 registers)
-template <typename T, int NT, int KS, int WAVES, int MINW, bool RES>
+// TH (RES only; hat_linear's reserved0 flags): bit 0 — r1 is FP16 rows, bit 1 — the HAT_O_NHWC_F32 output is stored as FP16
+// rows (round to nearest, clamped to +-65504; the fused LayerNorm reads the unrounded fp32 values, like hat_hab_tail3).  Only
+// the specialised copies of an fp32-output, r1-only launch (the OCAB projection) are instantiated with TH != 0.
+template <typename T, int NT, int KS, int WAVES, int MINW, bool RES, int TH = 0>
 __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc d, long npix_total, int tiles, int scale_in_lds) {
     using M = MT<T>;
     using frag_t = typename M::frag_t;
@@ -122,7 +127,9 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc 
         // everything issued so far"; the loop therefore issues its loads LAST (B operands of the tile after next, residual
         // operands of the next tile) and consumes them only after the next tile's MFMAs: by then they, and the stores
         // issued just before them, have had a whole MFMA phase to complete.
-        auto load_r = [&](long t, f32x4 (&r1v)[RES ? NT : 1], typename Vec4<T>::raw_t (&r2v)[RES ? NT : 1]) {
+        // (FP16 residual rows wait as raw bits — half the registers — and are converted where they are added)
+        using r1_t = std::conditional_t<(TH & 1) != 0, h4raw, f32x4>;
+        auto load_r = [&](long t, r1_t (&r1v)[RES ? NT : 1], typename Vec4<T>::raw_t (&r2v)[RES ? NT : 1]) {
             if constexpr (RES) {
                 long pp = t * 16 + c16;
                 pp = pp < npix_total ? pp : npix_total - 1;
@@ -130,7 +137,10 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc 
                 for (int nt = 0; nt < NT; ++nt) {
                     const int n = SPEC ? (nt == NT - 1 && NT > 1 && !lastok ? (nt - 1) * 16 + 4 * g : nt * 16 + 4 * g)
                                        : min(nbase + nt * 16 + 4 * g, d.n_store - 4);
-                    if (has_r1) r1v[nt] = *reinterpret_cast<const f32x4*>(d.r1 + pp * d.ldr1 + n);
+                    if (has_r1) {
+                        if constexpr ((TH & 1) != 0) r1v[nt] = load_h4raw(reinterpret_cast<const _Float16*>(d.r1) + pp * d.ldr1 + n);
+                        else r1v[nt] = *reinterpret_cast<const f32x4*>(d.r1 + pp * d.ldr1 + n);
+                    }
                     if (has_r2) r2v[nt] = Vec4<T>::load_raw(reinterpret_cast<const T*>(d.r2) + pp * d.ldr2 + n);
                 }
             }
@@ -138,7 +148,7 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc 
         // (without residual registers and with a short K there is room for a third set: B operands two tiles ahead)
         constexpr bool DEEP = !RES && KS <= 5;
         frag_t bcur[KSMAX], bnxt[KSMAX], bnx2[DEEP ? KSMAX : 1];
-        f32x4 r1v[RES ? NT : 1];
+        r1_t r1v[RES ? NT : 1];
         typename Vec4<T>::raw_t r2v[RES ? NT : 1];
         load_b(tile, bcur);
         load_b(tile + stride, bnxt);
@@ -176,7 +186,10 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc 
                     for (int r = 0; r < 4; ++r) v[r] = v[r] >= 0.f ? v[r] : 0.01f * v[r];
                 }
                 if constexpr (RES) {
-                    if (has_r1) v += r1v[nt];
+                    if (has_r1) {
+                        if constexpr ((TH & 1) != 0) v += h4raw_to_f32(r1v[nt]);
+                        else v += r1v[nt];
+                    }
                     if (has_r2) {
                         const int n = min(nbase + nt * 16 + 4 * g, d.n_store - 4);
                         const f32x4 sc = sc_lds ? *reinterpret_cast<const f32x4*>(sct + bidx * (NT * 16) + nt * 16 + 4 * g)
@@ -197,6 +210,12 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc 
 #pragma unroll
                 for (int nt = 0; nt + 1 < NT; nt += 2) store_pair_bf16(orow, nt * 16, g, acc[nt], acc[nt + 1]);
                 if constexpr (NT & 1) Vec4<T>::store(reinterpret_cast<T*>(d.out) + pc * d.ldo + (NT - 1) * 16 + 4 * g, acc[NT - 1]);
+            } else if constexpr (SPEC && Tag::outf32 && (TH & 2) != 0 && Tag::pair) {
+                // full tiles, FP16 rows of the fp32 result: n-tile pairs, 16 bytes per lane (store_pair_f16_if)
+                _Float16* orow = reinterpret_cast<_Float16*>(d.out) + pc * d.ldo;
+#pragma unroll
+                for (int nt = 0; nt + 1 < NT; nt += 2) store_pair_f16_if(orow, nt * 16, g, acc[nt], acc[nt + 1], true);
+                if constexpr (NT & 1) store_h4(orow + (NT - 1) * 16 + 4 * g, acc[NT - 1]);
             } else if (SPEC || p < npix_total) {
                 const long ps = SPEC ? pc : p;
 #pragma unroll
@@ -212,6 +231,7 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc 
                     }
                     if (SPEC || n < d.n_store) {
                         if (!out_f32) Vec4<T>::store(reinterpret_cast<T*>(d.out) + ps * d.ldo + n, v);
+                        else if constexpr ((TH & 2) != 0) store_h4(reinterpret_cast<_Float16*>(d.out) + ps * d.ldo + n, v);
                         else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(d.out) + ps * d.ldo + n) = v;
                     }
                 }
@@ -301,7 +321,11 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc 
     // T-typed rows leave the specialised copies in 16-byte pieces (store_pair_bf16)
     const bool out16 = d.ldo % 8 == 0 && reinterpret_cast<uintptr_t>(d.out) % 16 == 0;
     const bool ln16 = d.ld_ln % 8 == 0 && reinterpret_cast<uintptr_t>(d.ln_out) % 16 == 0;
-    if constexpr (RES) {
+    if constexpr (RES && TH != 0) {   // (hat_linear checked: fp32 output, r1 only, one slice, partial last tile at most)
+        if (full && emit_ln && !d.ln_ones && ln16) tile_loop(PwTag<true, true, false, true, true, true>{});
+        else if (tail_ok && emit_ln && !d.ln_ones) tile_loop(PwTag<true, true, false, true, true, false>{});
+        else if (tail_ok && !emit_ln) tile_loop(PwTag<true, true, false, true, false>{});
+    } else if constexpr (RES) {
         const bool f32o = d.out_mode == HAT_O_NHWC_F32;
         if (tail_ok && f32o && d.r1 && d.r2 && scale_in_lds && !emit_ln) tile_loop(PwTag<true, true, true, true, false>{});
         else if (full && f32o && d.r1 && !d.r2 && emit_ln && !d.ln_ones && ln16) tile_loop(PwTag<true, true, false, true, true, true>{});
@@ -317,13 +341,13 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc 
     }
 }
 
-template <typename T, int NT, int KS, int WAVES, int MINW, bool RES>
+template <typename T, int NT, int KS, int WAVES, int MINW, bool RES, int TH = 0>
 int launch_pw_cfg(const HatConvDesc& d, hipStream_t s, size_t lds, int wgs_per_cu, int scale_in_lds) {
     const long npix = (long)d.B * d.H * d.W;
     const int tiles = (int)((npix + 15) / 16);
     int gx = 256 * wgs_per_cu;
     if (gx > (tiles + WAVES - 1) / WAVES) gx = (tiles + WAVES - 1) / WAVES;
-    auto kern = pw_kernel<T, NT, KS, WAVES, MINW, RES>;
+    auto kern = pw_kernel<T, NT, KS, WAVES, MINW, RES, TH>;
     if (lds > 65536) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
@@ -351,6 +375,17 @@ int launch_pw(const HatConvDesc& d, hipStream_t s) {
     // waves per SIMD the register allocation is sized for: 3 workgroups x 4 waves -> 3, 2 x 4 -> 2, 1 x 8 -> 2; the
     // residual variant keeps a tile's residual operands in registers and is sized for 2
     wgs_per_cu = wgs_per_cu > (res ? 2 : 3) ? (res ? 2 : 3) : wgs_per_cu;
+    if constexpr (NT == 9 && KS == 5 && sizeof(T) == 2) {   // FP16 residual stream (reserved0; the OCAB projection at C = 144)
+        if (d.reserved0 != 0 && wgs_per_cu == 2) {
+            switch (d.reserved0) {
+                case 1: return launch_pw_cfg<T, NT, KS, 4, 2, true, 1>(d, s, lds, 2, scale_in_lds);
+                case 2: return launch_pw_cfg<T, NT, KS, 4, 2, true, 2>(d, s, lds, 2, scale_in_lds);
+                case 3: return launch_pw_cfg<T, NT, KS, 4, 2, true, 3>(d, s, lds, 2, scale_in_lds);
+                default: return HAT_EINVAL;
+            }
+        }
+    }
+    if (d.reserved0 != 0) return HAT_EINVAL;
     if (wgs_per_cu < 2) return res ? launch_pw_cfg<T, NT, KS, 8, 2, true>(d, s, lds, 1, scale_in_lds) : launch_pw_cfg<T, NT, KS, 8, 2, false>(d, s, lds, 1, 0);
     if (wgs_per_cu == 2) return res ? launch_pw_cfg<T, NT, KS, 4, 2, true>(d, s, lds, 2, scale_in_lds) : launch_pw_cfg<T, NT, KS, 4, 2, false>(d, s, lds, 2, 0);
     return launch_pw_cfg<T, NT, KS, 4, 3, false>(d, s, lds, 3, 0);
@@ -521,6 +556,13 @@ extern "C" int hat_linear(const HatConvDesc* dp, void* stream) {
     const int vec = d.dtype == HAT_BF16 ? 8 : 4;
     if (d.ldx % vec || d.Cin % 4 || (d.x0 && (d.ldx0 % vec || d.c_split % vec || d.c_split > d.Cin))) return HAT_EINVAL;
     if ((d.r1 && d.ldr1 % 4) || (d.r2 && (d.ldr2 % 4 || !d.r2scale))) return HAT_EINVAL;
+    if (d.reserved0 & ~3) return HAT_EINVAL;
+    if (d.reserved0) {   // FP16 residual stream: an fp32-output launch with r1 only, one slice, at most the last n-tile partial
+        if (d.dtype != HAT_BF16 || !d.r1 || d.r2 || d.out_mode != HAT_O_NHWC_F32 || d.n_slices != 1 || d.ln_ones) return HAT_EINVAL;
+        if (d.nt < 2 || d.n_store <= (d.nt - 1) * 16) return HAT_EINVAL;
+        if ((d.reserved0 & 1) && reinterpret_cast<uintptr_t>(d.r1) % 8) return HAT_EINVAL;
+        if ((d.reserved0 & 2) && (d.ldo % 8 || reinterpret_cast<uintptr_t>(d.out) % 16)) return HAT_EINVAL;
+    }
     if (d.ln_out && (!d.ln_g || !d.ln_b || d.n_slices != 1 || d.ld_ln % 4 || d.ld_ln < d.n_store + (d.ln_ones ? 4 : 0))) return HAT_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int ks = (d.Cin + 31) / 32;

@@ -311,7 +311,9 @@ class HATEngine:
         yw = max([16] + [e.npad for e in escs])      # channels of the ESC conv output / floats per GAP partial block
         w = {
             "f0": z(B, N, C, dtype=f), "tA": z(B, N, C, dtype=f), "tB": z(B, N, C, dtype=f), "tC": z(B, N, C, dtype=f),
-            # the residual stream BETWEEN the fused tails of a group as FP16 rows (hat_hab_tail3 reads and writes it in both types)
+            # the residual stream as FP16 rows: hA = a group's input (written by the previous group conv), hB / hC = between its
+            # fused tails and through its OCAB (see _stream16_plan)
+            "hA": (z(B, N, C, dtype=torch.float16) if self.t16 else None),
             "hB": (z(B, N, C, dtype=torch.float16) if self.t16 else None), "hC": (z(B, N, C, dtype=torch.float16) if self.t16 else None),
             "n": z(B, N, _r8(C)), "n2b": z(B, N, _r8(C)), "c1": z(B, N, _r8(mid)), "c2": z(B, N, _r8(C)), "m2": z(B, N, ops.ffn_m_ld(C)),
             "y16": z(B, N, yw), "n16": z(B, N, 16), "u": z(B, N, _r8(max(hid2, 2 * C))), "g": z(B, N, _r8(max(hid2 // 2, 2 * C))),
@@ -384,6 +386,53 @@ class HATEngine:
         """ESC large-kernel + dynamic depthwise conv on the first pdim channels of `n` -> w['y16']."""
         self._esc_w(esc, w, B, H, W, nblk)
         self._esc_conv(esc, w, n, B, H, W)
+
+    def _to_conv(self, L) -> bool:
+        """The OCAB's last layer hands its result to the group's 3x3 conv as T rows (run_ocab's as_conv_input)."""
+        return bool(L["conv"] is not None and self.dtype == ops.HAT_BF16 and _r8(self.C) == self.C and L["ocab"]["mlp2"].frag
+                    and not os.environ.get("HAT_NO_BF16_CONV_IN"))
+
+    def _conv_ln_next(self, gi):
+        """(gamma, beta), gap_c of the LayerNorm the group conv of group gi emits from its epilogue, or None when it does not."""
+        L = self.layers[gi]
+        cv = L["conv"]
+        if cv is None or self.dtype != ops.HAT_BF16 or os.environ.get("HAT_NO_CONV_LN") or cv.n_slices != 1 or cv.nout != cv.nt * 16:
+            return None
+        if gi + 1 < len(self.layers):
+            nh = self.layers[gi + 1]["habs"]
+            nxt, gap_c = (nh[0]["n1"], nh[0]["esc"].pdim) if nh else (None, 0)
+        else:
+            nxt, gap_c = (self.norm, 0) if self.conv_after_body is not None else (None, 0)
+        return (nxt, gap_c) if nxt is not None and gap_c in (0, 4, 8, 12, 16) else None
+
+    def _stream16_plan(self):
+        """Where the residual stream is handed over as FP16 rows (bf16 path at embed_dim 144, HAT_NO_T16=1: nowhere).
+        A hand-over is FP16 only when EVERY reader of that buffer takes FP16 rows: hat_hab_tail3 (t_in / t_out), the OCAB
+        projection (hat_linear: r1 and its output, in place), hat_ocab_mlp (r1) and the group conv (hat_conv: r1 and its
+        output, in place).  hat_layernorm, hat_add_f32, the unfused OCAB / conv-LN fallbacks and the embed_dim-180 tail read
+        fp32.  Returns (in16, ocab16): in16[g] — group g's input (the previous group conv's output; in16[len] the stream after
+        the last group) is FP16; ocab16[g] — group g's last tail, its OCAB projection and MLP carry FP16 rows."""
+        ng = len(self.layers)
+        in16, ocab16 = [False] * (ng + 1), [False] * ng
+        if not self.t16:
+            return in16, ocab16
+        tail16 = lambda hb: bool("fold" in hb and hb.get("tail") and "ffn3" in hb and hb["ffn3"].C == 144)
+        conv16 = lambda L: bool(L["conv"] is not None and not L["conv"].frag and L["conv"].ksize > 1 and L["conv"].nt == 9
+                                and L["conv"].n_slices == 1 and L["conv"].nout == 144)
+        for g, L in enumerate(self.layers):
+            oc = L["ocab"]
+            ocab16[g] = bool(L["habs"] and tail16(L["habs"][-1]) and self._to_conv(L) and oc["mlpf"] is not None
+                             and oc["proj"].frag and oc["proj"].nt == 9 and getattr(oc["proj"], "ksplit", None) is None
+                             and "esc" not in oc)
+        for g, L in enumerate(self.layers):
+            if not conv16(L) or self._conv_ln_next(g) is None:   # (without the fused LayerNorm, hat_layernorm reads the output)
+                continue
+            if g + 1 < ng:
+                nL = self.layers[g + 1]
+                in16[g + 1] = bool(nL["habs"] and tail16(nL["habs"][0]) and conv16(nL))
+            else:
+                in16[ng] = self.conv_after_body is not None     # (the stream itself is not read after the last group)
+        return in16, ocab16
 
     def _side_stream(self):
         if os.environ.get("HAT_ONE_STREAM") == "1":
@@ -497,7 +546,7 @@ class HATEngine:
             else:
                 ops.ocab_attention(qbuf, kvbuf, oc["bias_rot"], w["ao"], B=B, H=H, W=W, C_=C, heads=L["heads"], ws=ws,
                                    wse=self.wse, ldq=ldq, ldkv=ldkv, ldo=ldc, dtype=dt, q_log2=oc["qlog2"])
-            tout = tB if t is tA else t  # never write the RHAG input buffer
+            tout = tB if t is tA else t  # never write the RHAG input buffer (an FP16 t is hB / hC: proj and MLP take it in place)
             if oc["proj"].frag:  # norm2 (:306) rides on the projection's epilogue
                 self._run_lin(oc["proj"], w["ao"], tout, **geo, ldx=ldc, ldo=C, out_mode=O_NHWC_F32, r1=t, ldr1=C,
                               ln=oc["n2"], ln_out=w["n"], ld_ln=ldc)
@@ -533,11 +582,13 @@ class HATEngine:
                                    f"pixels (ape=True fixes the input size to img_size, hat_arch.py:699-702)")
             ops.add_f32(tA, self.ape, tA, B=B, n=N * C, c_bstride=0)
         # the group conv's epilogue emits the LayerNorm its consumer starts with (the next group's first norm1, or HAT.norm)
-        conv_ln = dt == ops.HAT_BF16 and not os.environ.get("HAT_NO_CONV_LN")
         grp_n = grp_n16 = False   # ... so w["n"] (and w["n16"]) are already valid when a group starts
         grp_nblk = LNB
+        in16, ocab16 = self._stream16_plan()
+        gin = tA
         for gi, L in enumerate(self.layers):
-            t = tA            # current value of the residual stream (tA must survive until the RHAG tail)
+            # gin: the group's input — hA (FP16 rows) when the previous group conv wrote them there, else tA
+            t = gin           # current value of the residual stream (the group input must survive until the RHAG tail)
             have_n = grp_n    # w["n"] already holds the next LayerNorm of t (emitted by the fused FFN / the group conv)
             have_n16 = grp_n16  # ... and w["n16"] a compact copy of its first 16 channels
             nblk = grp_nblk   # number of GAP partial blocks currently in w["gap"]
@@ -626,12 +677,11 @@ class HATEngine:
                             nxt, gap_c = L["habs"][i + 1]["n1"], L["habs"][i + 1]["esc"].pdim
                         else:
                             nxt, gap_c = oc["n1"], (oc["esc"].pdim if "esc" in oc else 0)
-                        # Between two fused tails of a group the stream is FP16 rows (only this kernel reads and writes it there:
-                        # 4C of a pixel's 12.3C bytes less, 43.7 -> 43.6 dB at 720p by emulation); the group's first
-                        # tail reads fp32 (group conv / first LayerNorm), its last one writes fp32 (the OCAB's linears).
+                        # The stream leaves as FP16 rows when its reader takes them: the next fused tail, or, after the last
+                        # block, the OCAB projection and MLP (_stream16_plan; 43.7 -> 43.6 dB at 720p by emulation).
                         nh = L["habs"][i + 1] if i + 1 < len(L["habs"]) else None
-                        out16 = bool(self.t16 and "ffn3" in hb and hb["ffn3"].C == 144 and nh is not None and nh.get("tail")
-                                     and "ffn3" in nh and nh["ffn3"].C == 144)
+                        out16 = bool(self.t16 and "ffn3" in hb and hb["ffn3"].C == 144
+                                     and (ocab16[gi] if nh is None else (nh.get("tail") and "ffn3" in nh and nh["ffn3"].C == 144)))
                         if out16:
                             tout = w["hB"] if t is not w["hB"] else w["hC"]
                         else:
@@ -720,8 +770,7 @@ class HATEngine:
                                         ldo=w["g"].shape[2], dtype=dt)
                     self._run_lin(hb["fc2"], w["g"], tB, **geo, ldx=w["g"].shape[2], ldo=C, out_mode=O_NHWC_F32, r1=tB, ldr1=C)
                     t, have_n, have_n16 = tB, False, False
-            to_conv = (L["conv"] is not None and dt == ops.HAT_BF16 and ldc == C and L["ocab"]["mlp2"].frag
-                       and not os.environ.get("HAT_NO_BF16_CONV_IN"))
+            to_conv = self._to_conv(L)
             tout = yield from run_ocab(L, t, have_n, nblk, as_conv_input=to_conv)
             if bd is not None and L["conv"] is not None:   # the group's 3x3 conv reads one row beyond the band's own
                 yield ("halo", [(tout, 1)])
@@ -730,22 +779,23 @@ class HATEngine:
                 ops.add_f32(tout, tA, tA, B=B, n=N * C)
             else:
                 lnkw = {}
-                if conv_ln and L["conv"].n_slices == 1 and L["conv"].nout == L["conv"].nt * 16 and tout is not w["n"]:
-                    if gi + 1 < len(self.layers):
-                        nh = self.layers[gi + 1]["habs"]
-                        nxt, gap_c = (nh[0]["n1"], nh[0]["esc"].pdim) if nh else (None, 0)
-                    else:
-                        nxt, gap_c = (self.norm, 0) if self.conv_after_body is not None else (None, 0)
-                    if nxt is not None and gap_c in (0, 4, 8, 12, 16):
-                        lnkw = dict(ln=nxt, ln_out=w["n"], ld_ln=ldc, gap_out=w["gap"], gap_c=gap_c,
-                                    n16_out=(w["n16"] if self.use_n16 and gap_c else None))
-                        grp_n, grp_n16, grp_nblk = True, bool(self.use_n16 and gap_c), ops.conv_tiles(L["conv"], H, W, dt)
+                cln = self._conv_ln_next(gi) if tout is not w["n"] else None
+                if cln is not None:
+                    nxt, gap_c = cln
+                    lnkw = dict(ln=nxt, ln_out=w["n"], ld_ln=ldc, gap_out=w["gap"], gap_c=gap_c,
+                                n16_out=(w["n16"] if self.use_n16 and gap_c else None))
+                    grp_n, grp_n16, grp_nblk = True, bool(self.use_n16 and gap_c), ops.conv_tiles(L["conv"], H, W, dt)
+                # written over the group input when both have the same type; else into the other type's buffer
+                gout = w["hA"] if in16[gi + 1] and cln is not None else tA
                 if to_conv:
-                    ops.conv(L["conv"], tout, tA, **geo, ldx=ldc, ldo=C, x_mode=X_NHWC_T, out_mode=O_NHWC_F32, r1=tA, ldr1=C, **lnkw)
+                    ops.conv(L["conv"], tout, gout, **geo, ldx=ldc, ldo=C, x_mode=X_NHWC_T, out_mode=O_NHWC_F32, r1=gin, ldr1=C, **lnkw)
                 else:
-                    ops.conv(L["conv"], tout, tA, **geo, ldx=C, ldo=C, x_mode=X_NHWC_F32, out_mode=O_NHWC_F32, r1=tA, ldr1=C, **lnkw)
+                    ops.conv(L["conv"], tout, gout, **geo, ldx=C, ldo=C, x_mode=X_NHWC_F32, out_mode=O_NHWC_F32, r1=gin, ldr1=C, **lnkw)
+                gin = gout
                 if _EMU_T16 is not None:
                     tA.copy_(tA.to(_EMU_T16).to(torch.float32))
+        if gin is not tA and not (grp_n and self.conv_after_body is not None):
+            raise RuntimeError("the FP16 residual stream reached a reader that takes fp32 only")   # (_stream16_plan rules it out)
         # final LN; conv_after_body + f0 ; conv_before_upsample + LeakyReLU                :844, :854-855
         if self.conv_after_body is None:   # nn.Identity: LN(t) + f0 in fp32, read as such by the next conv      :748
             ln(tA, tB, self.norm, out_f32=True)

@@ -127,6 +127,15 @@ def pack_conv_weight(weight: torch.Tensor, bias: Optional[torch.Tensor], dtype: 
     return PackedConv(wp.to(TORCH_DTYPE[dtype]).to(device).contiguous(), bp.to(device), kh, i, kpad, nt, n_slices, o)
 
 
+def _stream16(r1, out, out_mode: int) -> int:
+    """HatConvDesc.reserved0 from the tensors' dtypes: bit 0 = r1, bit 1 = the fp32 (O_NHWC_F32) output are FP16 rows (the
+    16-bit residual stream; hat_conv / hat_linear accept it on the group conv and the OCAB projection only)."""
+    h = 1 if r1 is not None and r1.dtype == torch.float16 else 0
+    if out_mode == O_NHWC_F32 and out.dtype == torch.float16:
+        h |= 2
+    return h
+
+
 def conv(pw: PackedConv, x: torch.Tensor, out: torch.Tensor, *, B: int, H: int, W: int, dtype: int, ldx: int, ldo: int,
          x_mode: int = X_NHWC_T, out_mode: int = O_NHWC_T, act: int = ACT_NONE, n_store: Optional[int] = None,
          x0: Optional[torch.Tensor] = None, c_split: int = 0, ldx0: int = 0,
@@ -158,6 +167,7 @@ def conv(pw: PackedConv, x: torch.Tensor, out: torch.Tensor, *, B: int, H: int, 
     for i in range(4):
         d.mean[i] = float(mean[i]) if i < len(mean) else 0.0
     d.dtype = dtype
+    d.reserved0 = _stream16(r1, out, out_mode)
     name, flops = "conv_kernel", 0.0
     if _prof is not None:
         wv, pt, tl, lds = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
@@ -338,14 +348,18 @@ def ocab_qkv(pm: PackedMlp, x, out, *, B: int, H: int, W: int, ldx: int, ldo: in
 
 
 def ocab_mlp(pm: PackedMlp, x, r1, out, *, B: int, H: int, W: int, ldx: int, ldr1: int, ldo: int, out_f32: bool, dtype: int):
-    """out = r1 + fc2(GELU(fc1(x))) in one launch (hat_ocab_mlp): the 288-wide hidden tensor never reaches HBM."""
+    """out = r1 + fc2(GELU(fc1(x))) in one launch (hat_ocab_mlp): the 288-wide hidden tensor never reaches HBM.
+    r1 may be FP16 rows (the 16-bit residual stream) when out is T rows."""
     lib = _lib.load()
     d = HatMlpDesc()
     d.x, d.w1f, d.b1, d.w2f, d.b2, d.r1, d.out = _ptr(x), _ptr(pm.w1f), _ptr(pm.b1), _ptr(pm.w2f), _ptr(pm.b2), _ptr(r1), _ptr(out)
-    d.B, d.H, d.W, d.C, d.hidden, d.ldx, d.ldr1, d.ldo, d.out_f32, d.dtype = B, H, W, pm.C, pm.hidden, ldx, ldr1, ldo, int(out_f32), dtype
+    r16 = r1.dtype == torch.float16
+    d.B, d.H, d.W, d.C, d.hidden, d.ldx, d.ldr1, d.ldo, d.dtype = B, H, W, pm.C, pm.hidden, ldx, ldr1, ldo, dtype
+    d.out_f32 = int(out_f32) | (2 if r16 else 0)
     _timed(f"ocab_mlp_kernel<{'true' if out_f32 else 'false'}>", 2.0 * 2 * pm.C * pm.hidden * B * H * W,
            lambda: _lib.check(lib.hat_ocab_mlp(C.byref(d), _stream()), "hat_ocab_mlp"),
-           tag=f"mlp {pm.C}->{pm.hidden}->{pm.C} {H}x{W}", nbytes=float(B * H * W) * (2 * ldx + 4 * pm.C + (4 if out_f32 else 2) * pm.C))
+           tag=f"mlp {pm.C}->{pm.hidden}->{pm.C} {H}x{W}",
+           nbytes=float(B * H * W) * (2 * ldx + (2 if r16 else 4) * pm.C + (4 if out_f32 else 2) * pm.C))
 
 
 def sgfn_gate(u, wdw, bdw, out, *, B: int, H: int, W: int, half: int, ldu: int, ldo: int, dtype: int):
@@ -813,6 +827,7 @@ def linear(pw: PackedConv, x: torch.Tensor, out: torch.Tensor, *, B: int, H: int
     d.c_split, d.ldx0, d.ksize, d.Kpad, d.nt, d.n_slices = c_split, ldx0, 1, pw.kpad, pw.nt, pw.n_slices
     d.n_store = pw.nout if n_store is None else n_store
     d.ldo, d.out_mode, d.act, d.ldr1, d.ldr2, d.r2scale_bstride, d.dtype = ldo, out_mode, act, ldr1, ldr2, r2scale_bstride, dtype
+    d.reserved0 = _stream16(r1, out, out_mode)
     flops = 2.0 * B * H * W * pw.cin * pw.nout
     _timed(f"pw_kernel<{_TNAME[dtype]}, {pw.nt}, {pw.kpad // 32}>", flops,
            lambda: _lib.check(lib.hat_linear(C.byref(d), _stream()), f"hat_linear(Cin={pw.cin}, N={pw.nout})"),
