@@ -354,7 +354,10 @@ class HAT(nn.Module):
 
     def forward_bands(self, x, n_bands: int):
         """`forward(x)` computed as n_bands row bands on this GPU that exchange halo rows and pool sums: equal to the
-        unsharded forward up to the summation order of the two global pools (band_parallel.forward_bands_local)."""
+        unsharded forward up to the summation order of the global pools (band_parallel.forward_bands_local).  Every variant:
+        HAT and HATX (SGFN, focus bias, top-k, odd key windows), OCAB-ESC, ape, resi_connection '1conv' / 'identity',
+        patch_norm on / off.  Raises RuntimeError when a band would need ghost rows its neighbours do not own (the network's
+        deepest refresh, HATEngine.band_halo(): 8 rows for HAT, up to 13 for HATX's live config)."""
         from .. import band_parallel
         self._check_band_input(x)
         with torch.no_grad():
@@ -363,7 +366,8 @@ class HAT(nn.Module):
     def forward_band_parallel(self, x, group=None):
         """`forward(x)` with one row band per rank of `group` (torch.distributed; RCCL send / recv of halo rows between
         neighbours, one small all-reduce per pool, one all-gather of the output rows): every rank passes the same x and
-        receives the full output frame (band_parallel.forward_band_distributed)."""
+        receives the full output frame (band_parallel.forward_band_distributed).  The variants and the geometry limit of
+        forward_bands apply."""
         from .. import band_parallel
         self._check_band_input(x)
         with torch.no_grad():

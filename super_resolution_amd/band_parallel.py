@@ -10,11 +10,16 @@ and the bands together compute exactly the unsharded forward:
     tiles of the fused HAB tail stay aligned); every kernel runs on the whole extended band, as if it were a frame;
   * before a layer reads across the band border, the ghost rows it will read are REFRESHED from the neighbour that owns them
     (`("halo", [(tensor, depth)...])`): per HAB one row of the fp32 residual stream (depthwise 3x3 of the FFN), three rows of
-    LayerNorm1's output (CAB squeeze conv under the folded expand conv) and seven rows of its first 16 channels (13x13 conv
-    under the aggregation's halo row) = 2.1 MB per side at 720p; per group four rows for the OCAB's key windows and one for
-    the group conv; eight rows once before the five convs that end the network;
-  * the two global pools become sums over the band's OWN rows (`hat_rect_sum`) added over the bands
-    (`("reduce", [(local, glob, n) ...])`): 16 + 72 floats per HAB in ONE reduce (fp32 / embed_dim-180 path: 16 + C).
+    LayerNorm1's output (CAB squeeze conv under the folded expand conv) and ksize // 2 + 1 rows of its first pdim channels
+    (the ESC conv under the aggregation's halo row: 7 for 13x13, 8 for HATX's 15x15) = 2.1 MB per side at 720p (HAT-S); per
+    group ceil((wse - ws) / 2) rows for the OCAB's key windows (4 for HAT-S, 3 / 5 for HATX's 13 / 25-wide ceil-padded
+    windows), plus ocab_esc_kernel // 2 with OCAB-ESC (the ESC conv under the keys: 11 rows for the hatx_live_x2 shapes, 13
+    for the live HATX config), and one for the group conv; eight rows once before the convs that end the network (either
+    resi_connection).  HATEngine.band_halo() is the deepest of them: make_bands(..., halo=) checks that the neighbours OWN
+    every row a refresh asks for, and the drivers clamp each refresh to the rows the frame has;
+  * the global pools become sums over the band's OWN rows (`hat_rect_sum`) added over the bands
+    (`("reduce", [(local, glob, n) ...])`): 16 + 72 floats per HAB in ONE reduce (fp32 / embed_dim-180 / HATX path: pdim + C),
+    and with OCAB-ESC one more reduce of ocab_esc_pdim floats per group (the OCAB's ESC pool).
 
 `HATEngine._forward_gen(x_band, band=...)` is the per-band forward as a generator that yields those two requests; this
 module holds the two drivers that answer them:
@@ -56,12 +61,16 @@ class Band(NamedTuple):
         return self.e1 - self.r1
 
 
-def make_bands(H: int, n: int, window: int = 16, ghost: int = GHOST) -> List[Band]:
-    """n row bands of a frame of H rows: heights are multiples of `window`, as equal as possible."""
+def make_bands(H: int, n: int, window: int = 16, ghost: int = GHOST, halo: int = 8) -> List[Band]:
+    """n row bands of a frame of H rows: heights are multiples of `window`, as equal as possible.  halo: the deepest ghost-row
+    refresh the band network asks for (HATEngine.band_halo()): the rows [r0 - halo, r0) and [r1, r1 + halo) that exist in the
+    frame must lie in the neighbours' OWN rows, so that one exchange with the two neighbours refreshes them."""
     if H % window:
         raise RuntimeError(f"frame height {H} is not a multiple of window_size {window} (pad it first, hat_model.py:16-26)")
     if ghost % window or ghost < 8:
         raise ValueError("ghost must be a multiple of the window size and cover the 8 rows of the last refresh")
+    if halo > ghost:
+        raise RuntimeError(f"a halo of {halo} rows does not fit the {ghost} ghost rows of a band")
     units = H // window
     if n < 1 or n > units:
         raise RuntimeError(f"cannot cut {H} rows into {n} bands of whole {window}-row windows")
@@ -73,7 +82,22 @@ def make_bands(H: int, n: int, window: int = 16, ghost: int = GHOST) -> List[Ban
         r += h
     if n > 1 and min(b.own for b in out) < 8:
         raise RuntimeError("bands thinner than the deepest halo (8 rows)")
+    over = [(b, max(b.r0 - halo, 0), b.r0) for a, b in zip(out[:-1], out[1:]) if max(b.r0 - halo, 0) < a.r0]
+    over += [(a, a.r1, min(a.r1 + halo, H)) for a, b in zip(out[:-1], out[1:]) if min(a.r1 + halo, H) > b.r1]
+    if over:
+        b, g0, g1 = over[0]
+        raise RuntimeError(f"a halo of {halo} rows does not fit {n} bands of {H} rows: band {b.idx} (rows [{b.r0}, {b.r1})) needs "
+                           f"rows [{g0}, {g1}), beyond its neighbour's own rows; use fewer bands")
     return out
+
+
+def _depths(depth: int, band: Band, bands: Sequence[Band]):
+    """Ghost rows a refresh of `depth` rows fills above and below this band, clamped to the rows the frame has (a ghost region
+    ends at the frame edge), each checked against the neighbour that owns them."""
+    up, dn = min(depth, band.lo), min(depth, band.hi)
+    if (band.idx > 0 and up > bands[band.idx - 1].own) or (band.idx + 1 < band.n and dn > bands[band.idx + 1].own):
+        raise RuntimeError(f"a halo of {depth} rows reaches beyond the neighbours of band {band.idx} (make_bands(..., halo=) rules this out)")
+    return up, dn
 
 
 def _pairs(req):
@@ -116,12 +140,13 @@ def run_lockstep(gens: Sequence[Generator], bands: Sequence[Band], B: int, add: 
                         raise RuntimeError("band generators ask for different halo depths")
                     views.append(_rows(t, B, b.e1 - b.e0))
                 for i, b in enumerate(bands):
-                    if i > 0:          # rows [r0 - depth, r0) live at the bottom of the upper neighbour's owned rows
+                    du, dd = _depths(depth, b, bands)
+                    if i > 0:          # rows [r0 - du, r0) live at the bottom of the upper neighbour's owned rows
                         u = bands[i - 1]
-                        views[i][:, b.lo - depth:b.lo].copy_(views[i - 1][:, u.lo + u.own - depth:u.lo + u.own])
-                    if i + 1 < n:      # rows [r1, r1 + depth) live at the top of the lower neighbour's owned rows
+                        views[i][:, b.lo - du:b.lo].copy_(views[i - 1][:, u.lo + u.own - du:u.lo + u.own])
+                    if i + 1 < n:      # rows [r1, r1 + dd) live at the top of the lower neighbour's owned rows
                         l = bands[i + 1]
-                        views[i][:, b.lo + b.own:b.lo + b.own + depth].copy_(views[i + 1][:, l.lo:l.lo + depth])
+                        views[i][:, b.lo + b.own:b.lo + b.own + dd].copy_(views[i + 1][:, l.lo:l.lo + dd])
         elif kind == "reduce":
             for k in range(len(_pairs(reqs[0]))):
                 loc0, glob0, m = _pairs(reqs[0])[k]
@@ -144,7 +169,7 @@ def forward_bands_local(engine, x: torch.Tensor, n: int) -> torch.Tensor:
     """The exact full-frame forward of `x` (B,3,H,W) computed as n row bands on the engine's GPU (stage 1 of §8 f4)."""
     from . import ops
     B, _, H, W = x.shape
-    bands = make_bands(H, n, engine.ws)
+    bands = make_bands(H, n, engine.ws, halo=engine.band_halo())
     s = engine.scale
 
     def add(a, c, out, m):
@@ -185,20 +210,23 @@ def run_distributed(gen: Generator, band: Band, bands: Sequence[Band], B: int, g
             ops_, recvs = [], []
             for t, depth in req[1]:
                 v = _rows(t, B, hb)
+                du, dd = _depths(depth, band, bands)     # rows I receive; a neighbour receives its own clamp of depth from me
                 if up is not None:
-                    send = v[:, band.lo:band.lo + depth].contiguous()                # my top rows -> the upper rank's bottom ghost
-                    recv = torch.empty_like(v[:, band.lo - depth:band.lo])
+                    su = _depths(depth, up, bands)[1]
+                    send = v[:, band.lo:band.lo + su].contiguous()                   # my top rows -> the upper rank's bottom ghost
+                    recv = torch.empty_like(v[:, band.lo - du:band.lo])
                     if stage_on_host:
                         send, recv = send.cpu(), recv.cpu()
                     ops_ += [dist.P2POp(dist.isend, send, peer(rank - 1), group), dist.P2POp(dist.irecv, recv, peer(rank - 1), group)]
-                    recvs.append((v, band.lo - depth, band.lo, recv))
+                    recvs.append((v, band.lo - du, band.lo, recv))
                 if down is not None:
-                    send = v[:, band.lo + band.own - depth:band.lo + band.own].contiguous()
-                    recv = torch.empty_like(v[:, band.lo + band.own:band.lo + band.own + depth])
+                    sd = _depths(depth, down, bands)[0]
+                    send = v[:, band.lo + band.own - sd:band.lo + band.own].contiguous()
+                    recv = torch.empty_like(v[:, band.lo + band.own:band.lo + band.own + dd])
                     if stage_on_host:
                         send, recv = send.cpu(), recv.cpu()
                     ops_ += [dist.P2POp(dist.isend, send, peer(rank + 1), group), dist.P2POp(dist.irecv, recv, peer(rank + 1), group)]
-                    recvs.append((v, band.lo + band.own, band.lo + band.own + depth, recv))
+                    recvs.append((v, band.lo + band.own, band.lo + band.own + dd, recv))
             if ops_:
                 for w in dist.batch_isend_irecv(ops_):
                     w.wait()
@@ -230,7 +258,7 @@ def forward_band_distributed(engine, x: torch.Tensor, group=None, stage_on_host:
     if stage_on_host is None:
         stage_on_host = dist.get_backend(group) == "gloo" and x.is_cuda
     B, Cin, H, W = x.shape
-    bands = make_bands(H, world, engine.ws)
+    bands = make_bands(H, world, engine.ws, halo=engine.band_halo())
     band, s = bands[rank], engine.scale
     with engine._lock, torch.cuda.device(engine.dev):
         gen = engine._forward_gen(x.to(torch.float32)[:, :, band.e0:band.e1].contiguous(), band=band)

@@ -387,6 +387,28 @@ class HATEngine:
         self._esc_w(esc, w, B, H, W, nblk)
         self._esc_conv(esc, w, n, B, H, W)
 
+    @staticmethod
+    def _hab_halo(esc: _ESC) -> int:
+        """Ghost rows a HAB reads beyond the band's own ones: LayerNorm1's output three rows (the two CAB convs under the FFN's
+        depthwise 3x3), its first pdim channels ksize // 2 + 1 rows (the ESC conv under the same row)."""
+        return max(3, esc.ksize // 2 + 1)
+
+    def _ocab_halo(self, oc) -> int:
+        """Ghost rows an OCAB reads: its key windows reach pad = ceil((wse - ws) / 2) rows beyond the query window (HATX's
+        ceil padding, hatx_arch.py:315-321: pad above, pad - 1 below); with OCAB-ESC the keys are ESC(LN(x)), whose conv reads
+        ksize // 2 rows further."""
+        pad = (self.wse - self.ws + 1) // 2
+        return pad + (oc["esc"].ksize // 2 if "esc" in oc else 0)
+
+    def band_halo(self) -> int:
+        """The deepest ghost-row refresh the band-sharded forward of this network requests (band_parallel.make_bands checks
+        the band geometry against it): the largest of the HAB and OCAB refreshes and the 8 rows before the network's last
+        convs.  HAT-S / HAT: 8; hatx_live_x2 shapes (ESC 15, OCAB-ESC 17, 13x13 key windows): 11; the live HATX config: 13."""
+        d = 8
+        for L in self.layers:
+            d = max([d, self._ocab_halo(L["ocab"])] + [self._hab_halo(hb["esc"]) for hb in L["habs"]])
+        return d
+
     def _to_conv(self, L) -> bool:
         """The OCAB's last layer hands its result to the group's 3x3 conv as T rows (run_ocab's as_conv_input)."""
         return bool(L["conv"] is not None and self.dtype == ops.HAT_BF16 and _r8(self.C) == self.C and L["ocab"]["mlp2"].frag
@@ -484,14 +506,19 @@ class HATEngine:
         bd = band
         w = dict(self._workspace(B, H, W, tag=(None if bd is None else ("band", bd.idx, bd.n))))   # (a shallow copy: the forward swaps the two LayerNorm-output buffers locally)
         if bd is not None:
-            if (self.hatx or self.identity or self.ape is not None or self.pe_norm is None or self.conv_after_body is None
-                    or any("esc" in L["ocab"] for L in self.layers) or (bd.e1 - bd.e0) != H):
-                raise NotImplementedError("band-sharded forward: plain HAT with resi_connection='1conv', patch_norm, no ape, no OCAB-ESC")
+            if (bd.e1 - bd.e0) != H:
+                raise RuntimeError(f"band {bd.idx} holds frame rows [{bd.e0}, {bd.e1}) but the input has {H} rows")
             lo, own, npix_full = bd.lo, bd.own, bd.Hfull * W
 
             def pooled(src, ld, C_, dst, off=0, r0=None, r1=None, c0=0, c1=None):
                 ops.rect_sum(src, dst, w["rs_tmp"], w["rs_cnt"], B=B, W=W, ld=ld, C_=C_, r0=(lo if r0 is None else r0),
                              r1=(lo + own if r1 is None else r1), c0=c0, c1=c1, out_off=off)
+
+            def gstat(esc):
+                """(local, global) ESC pool vectors as (B, 16) views, (B, 32) for pdim > 16: hat_esc_weights reads one block
+                of that many floats per sample, whatever width the workspace gives the buffers (yw)."""
+                gs = 32 if esc.pdim > 16 else 16
+                return tuple(w[k].view(-1)[:B * gs].view(B, gs) for k in ("gstat_l", "gstat_g"))
         s = self.scale
         y = torch.empty(B, cfg["in_chans"], H * s, W * s, dtype=torch.float32, device=self.dev)
         mean = RGB_MEAN if cfg["in_chans"] == 3 else (0.0,) * 4
@@ -512,13 +539,24 @@ class HATEngine:
             oc = L["ocab"]
             esc = oc.get("esc")  # OCAB                                                    :326-393
             if bd is not None:   # key / value windows reach (wse - ws) / 2 rows into the neighbours' bands             :359-360
-                yield ("halo", [((w["n"] if have_n else t), (self.wse - ws + 1) // 2)])
+                # (+ the ESC conv under them with OCAB-ESC).  HATX's focus bias and top-k need nothing more: the saliency head is
+                # 1x1 and keys are ranked per window.  A window with owned query rows has its whole key window inside the buffer
+                # (ghost 16 >= pad), and the first / last band have the frame edge at their buffer edge, so the padded keys and
+                # the lowest-index tie rule are the frame's.
+                yield ("halo", [((w["n"] if have_n else t), self._ocab_halo(oc))])
             if not have_n:
                 ln(t, w["n"], oc["n1"], gap_c=(esc.pdim if esc else 0))
                 nblk = LNB
             kv_src = w["n"]
             if esc is not None:  # K/V from ESC(LN(x))                                     :336-344
-                self._esc_lk(esc, w, w["n"], B, H, W, nblk)
+                if bd is not None:   # the ESC pool over the whole FRAME: this band's rows, then ONE more reduce per group
+                    gl, gg = gstat(esc)
+                    pooled(w["n"], ldc, esc.pdim, gl)
+                    yield ("reduce", [(gl, gg, esc.pdim)])
+                    self._esc_w(esc, w, B, bd.Hfull, W, 1, gap=gg)
+                    self._esc_conv(esc, w, w["n"], B, H, W)
+                else:
+                    self._esc_lk(esc, w, w["n"], B, H, W, nblk)
                 self._run_lin(esc.aggr, w["n"], w["yesc"], **geo, ldx=ldc, ldo=ldc, x0=w["y16"], c_split=esc.pdim, ldx0=w["y16"].shape[2])
                 kv_src = w["yesc"]
             qbuf, kvbuf, ldq, ldkv = w["q"], w["kv"], ldc, w["kv"].shape[2]
@@ -576,7 +614,12 @@ class HATEngine:
             ln(w["f0"], tA, self.pe_norm, out_f32=True)
         else:
             tA.copy_(w["f0"])        # device-to-device copy on the current stream
-        if self.ape is not None:      # x + absolute_pos_embed (1, num_patches, C)          :837-838
+        if self.ape is not None and bd is not None:   # a band adds ITS rows [e0, e1) of the frame's position table
+            if self.ape.numel() != npix_full * C:
+                raise RuntimeError(f"absolute_pos_embed holds {self.ape.numel() // C} positions but the frame has {npix_full} "
+                                   f"pixels (ape=True fixes the input size to img_size, hat_arch.py:699-702)")
+            ops.add_f32(tA, self.ape[bd.e0 * W * C:bd.e1 * W * C], tA, B=B, n=N * C, c_bstride=0)
+        elif self.ape is not None:      # x + absolute_pos_embed (1, num_patches, C)          :837-838
             if self.ape.numel() != N * C:
                 raise RuntimeError(f"absolute_pos_embed holds {self.ape.numel() // C} positions but the input has {N} "
                                    f"pixels (ape=True fixes the input size to img_size, hat_arch.py:699-702)")
@@ -596,8 +639,8 @@ class HATEngine:
             oc = L["ocab"]
             for i, hb in enumerate(L["habs"]):  # HAB                                     :217-238
                 esc = hb["esc"]
-                if bd is not None and not have_n:
-                    yield ("halo", [(t, 7)])          # (LayerNorm1 is recomputed on the ghost rows from the refreshed stream)
+                if bd is not None and not have_n:   # (LayerNorm1 is recomputed on the ghost rows from the refreshed stream)
+                    yield ("halo", [(t, self._hab_halo(esc))])
                 if not have_n:
                     ln(t, w["n"], hb["n1"], gap_c=esc.pdim)
                     nblk, have_n16 = LNB, False
@@ -606,14 +649,14 @@ class HATEngine:
                     # output three rows (the two CAB convs under it) and its first pdim channels ksize / 2 + 1 = seven rows
                     # (13x13 conv under the FFN's halo row)
                     er = esc.ksize // 2 + 1
-                    yield ("halo", [(t, 1)] + ([(w["n"], 3), (w["n16"], er)] if have_n16 else [(w["n"], max(3, er))]))
+                    yield ("halo", [(t, 1)] + ([(w["n"], 3), (w["n16"], er)] if have_n16 else [(w["n"], self._hab_halo(esc))]))
                 gapb = None
                 if bd is not None:   # the ESC pool (esc_arch.py:96,121) over the whole FRAME: this band's share, then the sum
+                    gstl, gapb = gstat(esc)   # (gapb: summed over the bands together with the CAB pool below: ONE reduce per HAB)
                     if have_n16:
-                        pooled(w["n16"], 16, esc.pdim, w["gstat_l"])
+                        pooled(w["n16"], 16, esc.pdim, gstl)
                     else:
-                        pooled(w["n"], ldc, esc.pdim, w["gstat_l"])
-                    gapb = w["gstat_g"]    # (summed over the bands together with the CAB pool below: ONE reduce per HAB)
+                        pooled(w["n"], ldc, esc.pdim, gstl)
                 mid = hb["cab0"].nout
                 if "fold" in hb:
                     # c2 = conv3x3(c1) never exists: its ECA pooling follows from the sums of c1 (hat_cab_fold) and the
@@ -652,7 +695,7 @@ class HATEngine:
                             pooled(w["c1"], 8, 8, st, 16, r0=lo + own - 1, r1=lo + own)
                             pooled(w["c1"], 8, 8, st, 56, r0=lo + own - 1, r1=lo + own, c0=0, c1=1)
                             pooled(w["c1"], 8, 8, st, 64, r0=lo + own - 1, r1=lo + own, c0=W - 1, c1=W)
-                        yield ("reduce", [(w["gstat_l"], w["gstat_g"], esc.pdim), (st, w["cstat_g"], 72)])
+                        yield ("reduce", [(gstl, gapb, esc.pdim), (st, w["cstat_g"], 72)])
                         ops.cab_fold(None, None, 1, hb["cab0"].npad, fo["w2"], fo["b2"], hb["eca_w"], hb["eca_w"].numel(), fo["ba"],
                                      float(cfg["conv_scale"]), w["scale"], w["wf"], w["bias_b"], None, B=B, H=bd.Hfull, W=W, C_=C,
                                      mid=mid, dtype=dt, stats=w["cstat_g"], w2f=fo["w2f"])
@@ -713,7 +756,7 @@ class HATEngine:
                         npd = hb["cab2"].npad
                         el, eg = (w[k].view(-1)[:B * npd].view(B, npd) for k in ("estat_l", "estat_g"))
                         pooled(w["c2"], ldc, C, el)
-                        yield ("reduce", [(w["gstat_l"], w["gstat_g"], esc.pdim), (el, eg, _r4(C))])
+                        yield ("reduce", [(gstl, gapb, esc.pdim), (el, eg, _r4(C))])
                         ops.eca_scale(eg, 1, npd, npix_full, hb["eca_w"], hb["eca_w"].numel(),
                                       float(cfg["conv_scale"]), w["eca_tmp"], w["scale"], B=B, C_=C)
                         self._esc_w(esc, w, B, bd.Hfull, W, 1, gap=gapb)
@@ -798,6 +841,8 @@ class HATEngine:
             raise RuntimeError("the FP16 residual stream reached a reader that takes fp32 only")   # (_stream16_plan rules it out)
         # final LN; conv_after_body + f0 ; conv_before_upsample + LeakyReLU                :844, :854-855
         if self.conv_after_body is None:   # nn.Identity: LN(t) + f0 in fp32, read as such by the next conv      :748
+            if bd is not None:   # the same one refresh as below: LN + f0 and the four 3x3 convs that end the network read < 4 rows
+                yield ("halo", [(tA, 8)])
             ln(tA, tB, self.norm, out_f32=True)
             ops.add_f32(tB, w["f0"], tB, B=B, n=N * C)
             ops.conv(self.conv_before_up, tB, w["fb"], **geo, ldx=C, ldo=64, x_mode=X_NHWC_F32, act=ACT_LRELU)

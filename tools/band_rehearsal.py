@@ -1,6 +1,7 @@
 """SURVEY §8 f4, stage 2 rehearsal on a ONE-GPU box: world_size ranks share cuda:0 and talk over gloo (payloads staged through
 host memory) — exercises band_parallel.forward_band_distributed end to end: halo rows by batched send / recv between neighbouring
-ranks, pool sums by all-reduce, output rows by all-gather.  On an 8-GPU node the same call runs one rank per GPU over RCCL.
+ranks, pool sums by all-reduce, output rows by all-gather — for plain HAT, OCAB-ESC and the shapes of the HATX live config
+(11-row halos).  On an 8-GPU node the same call runs one rank per GPU over RCCL.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 tools/band_rehearsal.py"""
 import os
 import sys
@@ -21,11 +22,20 @@ def main():
     rank, world = dist.get_rank(), dist.get_world_size()
     from oracle import hat_oracle as O
     from super_resolution_amd import synth
+    from super_resolution_amd.registry import build_network
     from test_gpu_model import build_net
-    from helpers import X_SEED
+    from helpers import META, W_SEED, X_SEED
     res = []
-    for name, dtype, shape in (("tiny_x2", "f32", (2, 3, 64, 24)), ("hats_1g_x4", "bf16", (1, 3, 96, 64)), ("HAT-S_x4", "bf16", (1, 3, 720, 1280))):
-        net = build_net(name, dtype, dev)
+
+    def hatx_net(name, dtype):
+        net = build_network(dict(type="HATX", compute_dtype=dtype, **META["cfgs"][name])).eval()
+        net.load_state_dict(synth.synth_state_dict(net.state_dict(), W_SEED), strict=True)
+        return net.to(dev)
+    for name, dtype, shape in (("tiny_x2", "f32", (2, 3, 64, 24)), ("tiny_ocabesc_x2", "f32", (2, 3, 64, 24)),
+                               ("tiny_ocabesc_x2", "bf16", (1, 3, 64, 40)), ("hatx_live_x2", "f32", (1, 3, 64, 40)),
+                               ("hatx_live_x2", "bf16", (2, 3, 48, 24)), ("hats_1g_x4", "bf16", (1, 3, 96, 64)),
+                               ("HAT-S_x4", "bf16", (1, 3, 720, 1280))):
+        net = hatx_net(name, dtype) if name.startswith("hatx") else build_net(name, dtype, dev)
         x = synth.synth_input(X_SEED, shape).to(dev)
         y0 = net(x).float()
         torch.cuda.synchronize()
