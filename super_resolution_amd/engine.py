@@ -5,6 +5,7 @@ kernel sequence of `HAT.forward` (reference: hat/archs/hat_arch.py:848-859 and t
 calls; op-by-op map in SURVEY.md App. A) on the current stream.  Nothing here computes on the
 CPU or through torch ops: torch only allocates device buffers and packs weights at load time.
 
+Which kernel runs where is decided once, at pack time (_Hab, _Ocab, _Group); the forward is a driver over stage steps.
 Data layout in HBM (B = batch, N = H*W pixels, C = embed_dim):
   residual stream      tA, tB : fp32 (B, N, C)  two buffers: tA = RHAG input/output, tB = working copy
   shallow feature      f0     : fp32 (B, N, C)
@@ -16,6 +17,7 @@ T = bf16 (performance path) or fp32 (exact-fp32 parity path).
 from __future__ import annotations
 
 import collections
+import dataclasses
 import math
 import os
 import threading
@@ -24,8 +26,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .ops import (ACT_GELU, ACT_LRELU, ACT_NONE, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T, X_NCHW_F32_MEAN,
-                  X_NHWC_F32, X_NHWC_T)
+from .ops import (ACT_GELU, ACT_LRELU, ACT_NONE, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T, X_NCHW_F32_MEAN, X_NHWC_F32, X_NHWC_T)
 
 RGB_MEAN = (0.4488, 0.4371, 0.4040)  # hat_arch.py:659
 
@@ -38,9 +39,57 @@ def _r4(x: int) -> int:
     return (x + 3) // 4 * 4
 
 
-# HAT_EMU_T16=fp16|bf16: round the fp32 residual stream to that type after every HAB tail and group conv (a torch copy:
-# slower, NOT a product path) — the parity cost of a 16-bit residual stream, measured before anyone builds it.
-_EMU_T16 = {"fp16": torch.float16, "bf16": torch.bfloat16}.get(os.environ.get("HAT_EMU_T16", ""))
+@dataclasses.dataclass(frozen=True)
+class Options:
+    """The engine's environment switches, read once per process: HATEngine reads them when it is built (a switch changed later
+    takes effect in the next engine built).  None is needed in production: each selects an older kernel SEQUENCE of the same
+    arithmetic, for A/B runs and diagnosis.  "=1" switches take exactly "1", the others any non-empty value.
+      HAT_NO_N16=1           no compact 16-channel copy of the LayerNorm rows for the 13x13 ESC conv
+      HAT_NO_T16=1           the residual stream in fp32 everywhere (default on the bf16 path at embed_dim 144: FP16 rows wherever
+                             every reader takes them: group conv, fused HAB tails, OCAB projection / MLP)
+      HAT_EMU_T16=fp16|bf16  measurement only: round the fp32 residual stream to that type after every fused HAB tail and group
+                             conv (a torch copy, not a product path; tools/residual16_psnr.py)
+      HAT_NO_FUSED_FFN=1     the FFN as fc1 -> dw + gate -> fc2 instead of hat_ffn / hat_ffn2
+      HAT_FFN_V1=1           hat_ffn (bf16 hidden tensor) instead of hat_ffn2
+      HAT_NO_HAB_TAIL=1      no fused HAB tail: the aggregation (hat_aggr_cab / hat_linear), then the fused FFN
+      HAT_TAIL_V2=1          round 2's hat_hab_tail instead of hat_hab_tail3 (embed_dim 180: no fused tail)
+      HAT_NO_CAB_FOLD        CAB expand conv + ECA as their own launches instead of folded into the aggregation
+      HAT_NO_CAB_SWEEP       CAB squeeze conv and conv_last on hat_conv instead of the row-sweep kernels
+      HAT_NO_ESC13=1         the 13x13 ESC conv on hat_conv instead of hat_esc_conv13
+      HAT_ESC_SIDE=1         the 13x13 conv (not the CAB squeeze chain) on the side stream: round 2's arrangement
+      HAT_ONE_STREAM=1       no side stream: a HAB's two short chains and the q / kv projections run one after the other (what
+                             hat_plan_forward replays; HATEngine.forward(x, one_stream=...) overrides it per call)
+      HAT_NO_ATTN_LOG2=1     hat_ocab_attention instead of hat_ocab_attention_log2
+      HAT_NO_OCAB_MLP        the OCAB MLP as two hat_linear launches instead of hat_ocab_mlp
+      HAT_NO_OCAB_QKV        the OCAB q and kv projections as two hat_linear launches on two streams instead of hat_ocab_qkv
+      HAT_NO_BF16_CONV_IN    fp32 rows into the group conv instead of the OCAB MLP's bf16 rows
+      HAT_NO_CONV_LN         the LayerNorm after the group conv as its own launch instead of the conv's epilogue"""
+    no_n16: bool = False
+    no_t16: bool = False
+    emu_t16: Optional[torch.dtype] = None
+    no_fused_ffn: bool = False
+    ffn_v1: bool = False
+    no_hab_tail: bool = False
+    tail_v2: bool = False
+    no_cab_fold: bool = False
+    no_cab_sweep: bool = False
+    no_esc13: bool = False
+    esc_side: bool = False
+    one_stream: bool = False
+    no_attn_log2: bool = False
+    no_ocab_mlp: bool = False
+    no_ocab_qkv: bool = False
+    no_bf16_conv_in: bool = False
+    no_conv_ln: bool = False
+
+    @classmethod
+    def from_env(cls, env=None) -> "Options":
+        """Field f is the variable HAT_<F>."""
+        env = os.environ if env is None else env
+        get = lambda name: env.get("HAT_" + name.upper(), "")
+        any_value = ("no_cab_fold", "no_cab_sweep", "no_ocab_mlp", "no_ocab_qkv", "no_bf16_conv_in", "no_conv_ln")
+        kw = {k.name: (get(k.name) != "" if k.name in any_value else get(k.name) == "1") for k in dataclasses.fields(cls)}
+        return cls(**dict(kw, emu_t16={"fp16": torch.float16, "bf16": torch.bfloat16}.get(get("emu_t16"))))
 
 
 class _ESC:
@@ -65,6 +114,80 @@ class _ESC:
         self.zero_bias = torch.zeros(self.npad, **f32)
         self.aggr = None  # packed by the engine (hat_linear when the shape is instantiated)
         self.aggr_keys = (core + ".aggr.weight", core + ".aggr.bias")
+        self.conv13 = False   # set by the engine: the conv runs on hat_esc_conv13 (else on hat_conv)
+
+
+class _Packed:
+    """Read access by key as well as by attribute, so callers that read the packed layers as dicts (L["habs"], hb["ffn"]) keep working."""
+
+    def __getitem__(self, key):
+        try:
+            return getattr(self, key)
+        except AttributeError:
+            raise KeyError(key) from None
+
+
+class _Hab(_Packed):
+    """One HAB (hat_arch.py:217-238): packed weights and the launches chosen for it at pack time.
+    fold: the CAB expand conv + ECA folded into the aggregation (hat_cab_fold / hat_aggr_cab), else None (plain CAB convs).
+    tail: "fused144" (hat_hab_tail3, or hat_hab_tail under HAT_TAIL_V2) | "fused180" (hat_hab_tail3 with c2 as a map) |
+          "aggr_cab" (after a fold) or "aggr" (hat_linear) followed by the FFN: fused (ffn) or fc1 / gate / fc2 (ffn None).
+    next_ln: (gamma, beta), gap_c of the LayerNorm its consumer (the next HAB or the OCAB) starts with.
+    out16: the fused tail hands the residual stream on as FP16 rows."""
+    fold = ffn = ffn3 = fc1 = fc2 = bias256 = None
+    tail = "aggr"
+    next_ln = None
+    out16 = False
+
+
+class _Ocab(_Packed):
+    """One OCAB (hat_arch.py:326-393): packed weights; qkvf / mlpf are the fused launches where they are built (else None),
+    esc the OCAB-ESC on the key / value path (None without one), fh0 / fh2 HATX's saliency head."""
+    qkvf = mlpf = esc = fh0 = fh2 = None
+
+
+class _Group(_Packed):
+    """One residual group (RHAG): its HABs, OCAB and 3x3 conv (None for resi_connection 'identity'), and the group-level routes:
+    to_conv: the OCAB hands its result to the group conv as T rows;  conv_ln: (gamma, beta), gap_c of the LayerNorm the
+    group conv emits from its epilogue, or None;  ocab16: the last tail, the OCAB projection and MLP carry FP16 rows;
+    out16: the group conv writes its output as FP16 rows (hA)."""
+    to_conv = ocab16 = out16 = False
+    conv_ln = None
+
+    def __init__(self, heads, habs, ocab, conv):
+        self.heads, self.habs, self.ocab, self.conv = heads, habs, ocab, conv
+
+
+class _Fwd:
+    """The state of one forward, handed to every stage step: geometry, the workspace (a shallow copy: the steps swap the two
+    LayerNorm-output buffers in it), the band, and what one step leaves for the next — t, the residual stream; gin, the
+    current group's input; have_n, w["n"] already holds the next LayerNorm of t; have_n16, w["n16"] a compact copy of its
+    first 16 channels; nblk, the number of GAP partial blocks in w["gap"]."""
+
+    def __init__(self, eng, w, B, H, W, band, one_stream):
+        self.B, self.H, self.W, self.N = B, H, W, H * W
+        self.C, self.dt, self.ldc = eng.C, eng.dtype, _r8(eng.C)
+        self.geo = dict(B=B, H=H, W=W, dtype=eng.dtype)
+        self.w, self.band, self.one_stream = w, band, one_stream
+        self.t = self.gin = w["tA"]
+        self.have_n = self.have_n16 = False
+        self.nblk = ops.layernorm_blocks()
+
+    def ln(self, src, dst, gb, out_f32=False, gap_c=0):
+        ops.layernorm(src, dst, gb[0], gb[1], B=self.B, npix=self.N, C_=self.C, ldy=(self.C if out_f32 else self.ldc),
+                      out_f32=out_f32, dtype=self.dt, gap=(self.w["gap"] if gap_c else None), gap_c=gap_c)
+
+    def pooled(self, src, ld, C_, dst, off=0, r0=None, r1=None, c0=0, c1=None):
+        """dst[:, off:off + C_] = sums of src over this band's own rows (or rows [r0, r1)) x columns [c0, c1)."""
+        bd, w = self.band, self.w
+        ops.rect_sum(src, dst, w["rs_tmp"], w["rs_cnt"], B=self.B, W=self.W, ld=ld, C_=C_, r0=(bd.lo if r0 is None else r0),
+                     r1=(bd.lo + bd.own if r1 is None else r1), c0=c0, c1=c1, out_off=off)
+
+    def gstat(self, esc):
+        """(local, global) ESC pool vectors as (B, 16) views, (B, 32) for pdim > 16: hat_esc_weights reads one block
+        of that many floats per sample, whatever width the workspace gives the buffers (yw)."""
+        gs = 32 if esc.pdim > 16 else 16
+        return tuple(self.w[k].view(-1)[:self.B * gs].view(self.B, gs) for k in ("gstat_l", "gstat_g"))
 
 
 class HATEngine:
@@ -74,6 +197,7 @@ class HATEngine:
         if cfg.get("resi_connection", "1conv") not in ("1conv", "identity"):
             raise ValueError(f"Unknown resi_connection: {cfg.get('resi_connection')}")   # hat_arch.py:547-548, :750-751
         self.cfg = cfg
+        self.opt = Options.from_env()
         self.identity = cfg.get("resi_connection", "1conv") == "identity"
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
@@ -89,22 +213,22 @@ class HATEngine:
         self._ws_cache = collections.OrderedDict()
         self._ws_max = int(os.environ.get("HAT_WS_CACHE", "12"))
         self._ws_max_bytes = int(float(os.environ.get("HAT_WS_CACHE_GIB", "96")) * 2 ** 30)
-        self.use_n16 = os.environ.get("HAT_NO_N16") != "1"
+        self.ws_allocations = self.fp16_fallbacks = 0
+        self.use_n16 = not self.opt.no_n16
         # FP16 residual rows between the fused HAB tails of a residual group (bf16 path, embed_dim 144; HAT_NO_T16=1: fp32 everywhere)
-        self.t16 = os.environ.get("HAT_NO_T16") != "1" and _EMU_T16 is None and self.dtype == ops.HAT_BF16 and self.C == 144
+        self.t16 = not self.opt.no_t16 and self.opt.emu_t16 is None and self.dtype == ops.HAT_BF16 and self.C == 144
         self._lock = threading.Lock()   # one forward at a time per engine: the workspace and side stream are shared state
+        self._s1 = None
         ops._lib.load()
-        # fused FFN kernel (hat_ffn) for the shapes it is instantiated for; HAT_NO_FUSED_FFN=1 forces the
-        # unfused kernel sequence (fc1 -> dw+gate -> fc2), kept for A/B validation of the fusion
+        # HATX (hatx_arch.py): the SGFN runs as fc1 -> hat_sgfn_gate -> fc2; odd window overlaps are padded with
+        # ceil((wse - ws) / 2) (hatx_arch.py:303-305) and run on the generic attention kernel (key windows 25 and 13)
         self.hatx = cfg.get("variant", "hat") == "hatx"
-        if self.hatx:
-            # HATX (hatx_arch.py): the SGFN runs as fc1 -> hat_sgfn_gate -> fc2; odd window overlaps are padded with
-            # ceil((wse - ws) / 2) (hatx_arch.py:303-305) and run on the generic attention kernel (key windows 25 and 13)
-            pass
         self.topk = float(cfg.get("kv_topk_ratio", 1.0)) if self.hatx else 1.0
         self.focus = bool(cfg.get("use_focus_bias", False)) if self.hatx else False
-        self.fuse_ffn = not self.hatx and ops.ffn_supported(self.C) and os.environ.get("HAT_NO_FUSED_FFN", "0") != "1"
+        # fused FFN kernel (hat_ffn) for the shapes it is instantiated for, else the unfused fc1 -> dw+gate -> fc2
+        self.fuse_ffn = not self.hatx and ops.ffn_supported(self.C) and not self.opt.no_fused_ffn
         self._pack(state_dict)
+        self._resolve()
 
     # ------------------------------------------------------------------------------------------
     def _lin(self, sd, wkey, bkey, scale=1.0):
@@ -139,6 +263,12 @@ class HATEngine:
             return ops.pack_linear_weight(w, sd[bkey], self.dtype, self.dev)
         return ops.pack_conv_weight(w, sd[bkey], self.dtype, self.dev)
 
+    def _esc(self, sd, core, plk_key, pdim, ksize):
+        esc = _ESC(sd, core, plk_key, pdim, ksize, self.C, self.dtype, self.dev)
+        esc.aggr = self._lin(sd, *esc.aggr_keys)
+        esc.conv13 = ops.esc_conv13_supported(pdim, ksize, self.dtype) and not self.opt.no_esc13
+        return esc
+
     def _run_lin(self, pw, x, out, **kw):
         h2 = getattr(pw, "ksplit", None)
         if h2 is not None:   # out = W[:, :K/2] x[:, :K/2] + b (+ r1), then out += W[:, K/2:] x[:, K/2:]   (fp32 output only)
@@ -150,121 +280,18 @@ class HATEngine:
         (ops.linear if pw.frag else ops.conv)(pw, x, out, **kw)
 
     def _pack(self, sd):
-        cfg, dt, dev, C = self.cfg, self.dtype, self.dev, self.C
+        cfg, dev = self.cfg, self.dev
         f32 = dict(dtype=torch.float32, device=dev)
-        P = lambda w, b=None, **kw: ops.pack_conv_weight(sd[w], None if b is None else sd[b], dt, dev, **kw)
+        P = lambda w, b=None, **kw: ops.pack_conv_weight(sd[w], None if b is None else sd[b], self.dtype, dev, **kw)
         vec = lambda k: sd[k].detach().to(**f32).contiguous()
         self.conv_first = P("conv_first.weight", "conv_first.bias")
         self.pe_norm = (vec("patch_embed.norm.weight"), vec("patch_embed.norm.bias")) if cfg.get("patch_norm", True) else None
         self.ape = vec("absolute_pos_embed").reshape(-1) if cfg.get("ape", False) else None   # (num_patches * C,)  :699-702
         self.layers = []
-        ws, wse = self.ws, self.wse
-        M = ws + wse - 1
-        shift = (ws - wse + 1 - (ws - 1)) * (M + 1)  # rotated index i' -> reference index rpi = i' + shift (may be < 0)
-        rot = (torch.arange(M * M) + shift) % (M * M)  # negative-index wraparound of hat_arch.py:378
         for g, (depth, heads) in enumerate(zip(cfg["depths"], cfg["num_heads"])):
-            L = {"heads": heads, "habs": []}
-            for i in range(depth):
-                p = f"layers.{g}.residual_group.blocks.{i}"
-                hb = {
-                    "n1": (vec(p + ".norm1.weight"), vec(p + ".norm1.bias")),
-                    "n2": (vec(p + ".norm2.weight"), vec(p + ".norm2.bias")),
-                    "esc": _ESC(sd, p + ".esc_attn.core", p + ".esc_attn.plk_filter", cfg["esc_pdim"], cfg["esc_kernel"], C, dt, dev),
-                    "cab0": self._c3(sd, p + ".conv_block.cab.0.weight", p + ".conv_block.cab.0.bias"),
-                    "cab2": self._c3(sd, p + ".conv_block.cab.2.weight", p + ".conv_block.cab.2.bias"),
-                    "eca_w": vec(p + ".conv_block.cab.3.conv.weight").reshape(-1),
-                }
-                hb["esc"].aggr = self._lin(sd, *hb["esc"].aggr_keys)
-                w2raw = sd[p + ".conv_block.cab.2.weight"]
-                # CAB expand conv + ECA folded into the aggregation (hat_cab_fold / hat_aggr_cab): squeeze width <= 8 only
-                if (hb["esc"].aggr.frag and not hb["cab0"].frag and ops.aggr_cab_supported(C, w2raw.shape[1], dt)
-                        and not os.environ.get("HAT_NO_CAB_FOLD")):
-                    hb["fold"] = {"w2": w2raw.detach().to(**f32).contiguous(), "b2": vec(p + ".conv_block.cab.2.bias"),
-                                  "ba": vec(hb["esc"].aggr_keys[1]), "w2f": ops.pack_cab_w2f(w2raw, dev)}
-                    # squeeze conv on the row-sweep kernel (no LDS operand traffic) where it is instantiated
-                    if ops.cab_squeeze_supported(C, w2raw.shape[1], 16, dt) and not os.environ.get("HAT_NO_CAB_SWEEP"):
-                        hb["fold"]["sq"] = ops.pack_cab_squeeze(sd[p + ".conv_block.cab.0.weight"], sd[p + ".conv_block.cab.0.bias"], dev)
-                if not self.fuse_ffn:
-                    hb["fc1"] = self._lin(sd, p + ".mlp.fc1.weight", p + ".mlp.fc1.bias")
-                    hb["fc2"] = self._lin(sd, p + ".mlp.fc2.weight", p + ".mlp.fc2.bias")
-                hid2 = sd[p + ".mlp.dw.weight"].shape[0]     # (HATX: the first half of the SGFN's hidden width)
-                hb["dw_w"] = sd[p + ".mlp.dw.weight"].detach().to(**f32).reshape(hid2, 9).t().contiguous()  # [9][2*hid]
-                hb["dw_b"] = vec(p + ".mlp.dw.bias")
-                if self.fuse_ffn:
-                    fw = [sd[p + k] for k in (".mlp.fc1.weight", ".mlp.fc1.bias", ".mlp.dw.weight", ".mlp.dw.bias",
-                                              ".mlp.fc2.weight", ".mlp.fc2.bias")]
-                    # hat_ffn2 (fp16 hidden tensor, depthwise conv on the packed-fp16 VALU) where it is built; HAT_FFN_V1=1
-                    # keeps the first-generation kernel for A/B runs
-                    # ... unless this block's weights could drive its FP16 hidden tensor past the FP16 range for SOME input
-                    # (pack-time worst-case bound, ops.ffn_fp16_range_bound): then the bf16-hidden kernel stays
-                    fp16_ok = ops.ffn_fp16_range_bound(fw[0], fw[1], fw[2], fw[3], *hb["n2"]) < ops.FP16_SAFE
-                    if not fp16_ok:
-                        self.fp16_fallbacks = getattr(self, "fp16_fallbacks", 0) + 1
-                    if ops.ffn2_supported(C, hid2 // 2, dt) and os.environ.get("HAT_FFN_V1") != "1" and fp16_ok:
-                        hb["ffn"] = ops.pack_ffn2(*fw, dev)
-                    else:
-                        hb["ffn"] = ops.pack_ffn(*fw, dt, dev)
-                    hb["tail"] = ("fold" in hb and hb["esc"].pdim == 16 and ops.hab_tail_supported(hb["ffn"], hb["esc"].aggr, w2raw.shape[1], dt)
-                                  and os.environ.get("HAT_NO_HAB_TAIL") != "1")
-                    # third-generation tail (activation-stationary fc1, weights shared through LDS): its own packing;
-                    # HAT_TAIL_V2=1 keeps hat_hab_tail for A/B runs
-                    if hb["tail"] and hb["ffn"].khalf == "v2" and os.environ.get("HAT_TAIL_V2") != "1":
-                        hb["ffn3"] = ops.pack_ffn3(*fw, *hb["n2"], dev)
-                    # embed_dim 180 (HAT / HAT-L): hat_hab_tail3 with the CAB's c2 as a map (their squeeze is 60 wide: no fold)
-                    if ("fold" not in hb and C == 180 and fp16_ok and ops.tail3_supported(C, hid2 // 2, dt) and hb["esc"].pdim == 16
-                            and hb["esc"].aggr.frag and os.environ.get("HAT_NO_HAB_TAIL") != "1" and os.environ.get("HAT_TAIL_V2") != "1"):
-                        f3 = ops.pack_ffn3(*fw, *hb["n2"], dev)
-                        if ops.hab_tail_supported(f3, hb["esc"].aggr, w2raw.shape[1], dt):
-                            hb["ffn3"], hb["tail180"] = f3, True
-                            b256 = torch.zeros(256, **f32)
-                            b256[:C] = vec(hb["esc"].aggr_keys[1])
-                            hb["bias256"] = b256
-                L["habs"].append(hb)
-            p = f"layers.{g}.residual_group.overlap_attn"
-            d = C // heads
-            qscale = cfg.get("qk_scale") or d ** -0.5
-            # the tuned OCAB kernel of the embed_dim-144 models takes its queries in log2 units: fold log2(e) into the q
-            # projection too (before the weights are rounded), not into the kernel (HAT_NO_ATTN_LOG2=1: the round-2 kernel)
-            qlog2 = (ops.ocab_attention_log2_supported(C, heads, self.ws, self.wse, dt) and not (self.focus or self.topk < 1.0)
-                     and os.environ.get("HAT_NO_ATTN_LOG2") != "1" and d % 2 == 0 and _r8(C) == C)
-            if qlog2:
-                qscale = qscale * ops.LOG2E
-            table = sd[p + ".relative_position_bias_table"].detach().to(torch.float32).cpu()  # (M*M, heads)
-            oc = {
-                "n1": (vec(p + ".norm1.weight"), vec(p + ".norm1.bias")),
-                "n2": (vec(p + ".norm2.weight"), vec(p + ".norm2.bias")),
-                # q * scale (hat_arch.py:375) is folded into the projection
-                "q": self._lin(sd, p + ".q_proj.weight", p + ".q_proj.bias", scale=qscale),
-                "kv": self._lin(sd, p + ".kv_proj.weight", p + ".kv_proj.bias"),
-                "proj": self._lin(sd, p + ".proj.weight", p + ".proj.bias"),
-                "mlp0": self._lin(sd, p + ".mlp.0.weight", p + ".mlp.0.bias"),
-                "mlp2": self._lin(sd, p + ".mlp.2.weight", p + ".mlp.2.bias"),
-                # both MLP layers in one launch where hat_ocab_mlp is built (HAT_NO_OCAB_MLP=1: the two hat_linear launches)
-                "mlpf": (ops.pack_ocab_mlp(sd[p + ".mlp.0.weight"], sd[p + ".mlp.0.bias"], sd[p + ".mlp.2.weight"], sd[p + ".mlp.2.bias"], dev)
-                         if ops.ocab_mlp_supported(C, sd[p + ".mlp.0.weight"].shape[0], dt) and _r8(C) == C
-                         and not os.environ.get("HAT_NO_OCAB_MLP") else None),
-                "bias_rot": table[rot].t().contiguous().to(dev),  # [heads][M*M]
-                "qlog2": qlog2,
-            }
-            # q and kv projections in one launch (both read LayerNorm1's output) where hat_ocab_qkv is built and the OCAB has
-            # no ESC on its key / value path (HAT_NO_OCAB_QKV=1: two hat_linear launches on two streams)
-            oc["qkvf"] = (ops.pack_ocab_qkv(sd[p + ".q_proj.weight"], sd.get(p + ".q_proj.bias"), sd[p + ".kv_proj.weight"],
-                                            sd.get(p + ".kv_proj.bias"), qscale, dev)
-                          if C == 144 and dt == ops.HAT_BF16 and not cfg.get("ocab_esc_enable", False)
-                          and not os.environ.get("HAT_NO_OCAB_QKV") else None)
-            if cfg.get("ocab_esc_enable", False):
-                oc["esc"] = _ESC(sd, p + ".esc_core", p + ".esc_plk", cfg["ocab_esc_pdim"], cfg["ocab_esc_kernel"], C, dt, dev)
-                oc["esc"].aggr = self._lin(sd, *oc["esc"].aggr_keys)
-            if self.focus:  # saliency head: 1x1 C -> C/4, GELU, 1x1 -> 1                     hatx_arch.py:357-361
-                oc["fh0"] = ops.pack_conv_weight(sd[p + ".focus_head.0.weight"], sd[p + ".focus_head.0.bias"], dt, dev)
-                oc["fh2"] = ops.pack_conv_weight(sd[p + ".focus_head.2.weight"], sd[p + ".focus_head.2.bias"], dt, dev)
-            L["ocab"] = oc
-            L["conv"] = None if self.identity else P(f"layers.{g}.conv.weight", f"layers.{g}.conv.bias")
-            self.layers.append(L)
-        if any(e.npad > 16 for L in self.layers for e in [hb["esc"] for hb in L["habs"]] + ([L["ocab"]["esc"]] if "esc" in L["ocab"] else [])):
-            for L in self.layers:       # the fused tail reads the ESC conv output as 16-channel rows
-                for hb in L["habs"]:
-                    hb["tail"] = False
+            habs = [self._pack_hab(sd, f"layers.{g}.residual_group.blocks.{i}") for i in range(depth)]
+            ocab = self._pack_ocab(sd, f"layers.{g}.residual_group.overlap_attn", heads)
+            self.layers.append(_Group(heads, habs, ocab, None if self.identity else P(f"layers.{g}.conv.weight", f"layers.{g}.conv.bias")))
         self.norm = (vec("norm.weight"), vec("norm.bias"))
         self.conv_after_body = None if self.identity else P("conv_after_body.weight", "conv_after_body.bias")
         self.conv_before_up = P("conv_before_upsample.0.weight", "conv_before_upsample.0.bias")
@@ -280,8 +307,105 @@ class HATEngine:
         self.conv_last = P("conv_last.weight", "conv_last.bias")
         wl = sd["conv_last.weight"]
         self.conv_last_sweep = None   # row-sweep kernel (no LDS) for the 64 -> 3 conv at output resolution
-        if ops.conv3x3_to_planes_supported(wl.shape[0], wl.shape[1], 16, dt) and not os.environ.get("HAT_NO_CAB_SWEEP"):
+        if ops.conv3x3_to_planes_supported(wl.shape[0], wl.shape[1], 16, self.dtype) and not self.opt.no_cab_sweep:
             self.conv_last_sweep = ops.pack_cab_squeeze(wl, sd["conv_last.bias"], dev) + (wl.shape[0],)
+
+    def _pack_hab(self, sd, p):
+        """Packs one HAB.  Sets tail144_ok / tail180_ok; _resolve turns them into the tail route once the whole net is packed."""
+        cfg, dt, dev, C, opt = self.cfg, self.dtype, self.dev, self.C, self.opt
+        f32 = dict(dtype=torch.float32, device=dev)
+        vec = lambda k: sd[k].detach().to(**f32).contiguous()
+        hb = _Hab()
+        hb.n1 = (vec(p + ".norm1.weight"), vec(p + ".norm1.bias"))
+        hb.n2 = (vec(p + ".norm2.weight"), vec(p + ".norm2.bias"))
+        hb.esc = self._esc(sd, p + ".esc_attn.core", p + ".esc_attn.plk_filter", cfg["esc_pdim"], cfg["esc_kernel"])
+        hb.cab0 = self._c3(sd, p + ".conv_block.cab.0.weight", p + ".conv_block.cab.0.bias")
+        hb.cab2 = self._c3(sd, p + ".conv_block.cab.2.weight", p + ".conv_block.cab.2.bias")
+        hb.eca_w = vec(p + ".conv_block.cab.3.conv.weight").reshape(-1)
+        w2raw = sd[p + ".conv_block.cab.2.weight"]
+        # CAB expand conv + ECA folded into the aggregation (hat_cab_fold / hat_aggr_cab): squeeze width <= 8 only
+        if hb.esc.aggr.frag and not hb.cab0.frag and ops.aggr_cab_supported(C, w2raw.shape[1], dt) and not opt.no_cab_fold:
+            hb.fold = {"w2": w2raw.detach().to(**f32).contiguous(), "b2": vec(p + ".conv_block.cab.2.bias"),
+                       "ba": vec(hb.esc.aggr_keys[1]), "w2f": ops.pack_cab_w2f(w2raw, dev)}
+            # squeeze conv on the row-sweep kernel (no LDS operand traffic) where it is instantiated
+            if ops.cab_squeeze_supported(C, w2raw.shape[1], 16, dt) and not opt.no_cab_sweep:
+                hb.fold["sq"] = ops.pack_cab_squeeze(sd[p + ".conv_block.cab.0.weight"], sd[p + ".conv_block.cab.0.bias"], dev)
+        if not self.fuse_ffn:
+            hb.fc1 = self._lin(sd, p + ".mlp.fc1.weight", p + ".mlp.fc1.bias")
+            hb.fc2 = self._lin(sd, p + ".mlp.fc2.weight", p + ".mlp.fc2.bias")
+        hid2 = sd[p + ".mlp.dw.weight"].shape[0]     # (HATX: the first half of the SGFN's hidden width)
+        hb.dw_w = sd[p + ".mlp.dw.weight"].detach().to(**f32).reshape(hid2, 9).t().contiguous()  # [9][2*hid]
+        hb.dw_b = vec(p + ".mlp.dw.bias")
+        hb.tail144_ok = hb.tail180_ok = False
+        if not self.fuse_ffn:
+            return hb
+        fw = [sd[p + k] for k in (".mlp.fc1.weight", ".mlp.fc1.bias", ".mlp.dw.weight", ".mlp.dw.bias", ".mlp.fc2.weight", ".mlp.fc2.bias")]
+        # hat_ffn2 (fp16 hidden tensor, depthwise conv on the packed-fp16 VALU) where it is built; HAT_FFN_V1=1 keeps the
+        # first-generation kernel for A/B runs ... unless this block's weights could drive its FP16 hidden tensor past the FP16
+        # range for SOME input (pack-time worst-case bound, ops.ffn_fp16_range_bound): then the bf16-hidden kernel stays
+        fp16_ok = ops.ffn_fp16_range_bound(fw[0], fw[1], fw[2], fw[3], *hb.n2) < ops.FP16_SAFE
+        if not fp16_ok:
+            self.fp16_fallbacks += 1
+        if ops.ffn2_supported(C, hid2 // 2, dt) and not opt.ffn_v1 and fp16_ok:
+            hb.ffn = ops.pack_ffn2(*fw, dev)
+        else:
+            hb.ffn = ops.pack_ffn(*fw, dt, dev)
+        hb.tail144_ok = (hb.fold is not None and hb.esc.pdim == 16 and ops.hab_tail_supported(hb.ffn, hb.esc.aggr, w2raw.shape[1], dt)
+                         and not opt.no_hab_tail)
+        # third-generation tail (activation-stationary fc1, weights shared through LDS): its own packing;
+        # HAT_TAIL_V2=1 keeps hat_hab_tail for A/B runs
+        if hb.tail144_ok and hb.ffn.khalf == "v2" and not opt.tail_v2:
+            hb.ffn3 = ops.pack_ffn3(*fw, *hb.n2, dev)
+        # embed_dim 180 (HAT / HAT-L): hat_hab_tail3 with the CAB's c2 as a map (their squeeze is 60 wide: no fold)
+        if (hb.fold is None and C == 180 and fp16_ok and ops.tail3_supported(C, hid2 // 2, dt) and hb.esc.pdim == 16
+                and hb.esc.aggr.frag and not opt.no_hab_tail and not opt.tail_v2):
+            f3 = ops.pack_ffn3(*fw, *hb.n2, dev)
+            if ops.hab_tail_supported(f3, hb.esc.aggr, w2raw.shape[1], dt):
+                hb.ffn3, hb.tail180_ok = f3, True
+                hb.bias256 = torch.zeros(256, **f32)
+                hb.bias256[:C] = vec(hb.esc.aggr_keys[1])
+        return hb
+
+    def _pack_ocab(self, sd, p, heads):
+        cfg, dt, dev, C = self.cfg, self.dtype, self.dev, self.C
+        vec = lambda k: sd[k].detach().to(dtype=torch.float32, device=dev).contiguous()
+        ws, wse = self.ws, self.wse
+        M = ws + wse - 1
+        shift = (ws - wse + 1 - (ws - 1)) * (M + 1)  # rotated index i' -> reference index rpi = i' + shift (may be < 0)
+        rot = (torch.arange(M * M) + shift) % (M * M)  # negative-index wraparound of hat_arch.py:378 (SURVEY F10)
+        d = C // heads
+        qscale = cfg.get("qk_scale") or d ** -0.5
+        # the tuned OCAB kernel of the embed_dim-144 models takes its queries in log2 units: fold log2(e) into the q
+        # projection too (before the weights are rounded), not into the kernel (HAT_NO_ATTN_LOG2=1: the round-2 kernel)
+        qlog2 = (ops.ocab_attention_log2_supported(C, heads, ws, wse, dt) and not (self.focus or self.topk < 1.0)
+                 and not self.opt.no_attn_log2 and d % 2 == 0 and _r8(C) == C)
+        if qlog2:
+            qscale = qscale * ops.LOG2E
+        table = sd[p + ".relative_position_bias_table"].detach().to(torch.float32).cpu()  # (M*M, heads)
+        oc = _Ocab()
+        oc.n1 = (vec(p + ".norm1.weight"), vec(p + ".norm1.bias"))
+        oc.n2 = (vec(p + ".norm2.weight"), vec(p + ".norm2.bias"))
+        oc.q = self._lin(sd, p + ".q_proj.weight", p + ".q_proj.bias", scale=qscale)   # q * scale (hat_arch.py:375) folded in
+        oc.kv = self._lin(sd, p + ".kv_proj.weight", p + ".kv_proj.bias")
+        oc.proj = self._lin(sd, p + ".proj.weight", p + ".proj.bias")
+        oc.mlp0 = self._lin(sd, p + ".mlp.0.weight", p + ".mlp.0.bias")
+        oc.mlp2 = self._lin(sd, p + ".mlp.2.weight", p + ".mlp.2.bias")
+        # both MLP layers in one launch where hat_ocab_mlp is built (HAT_NO_OCAB_MLP=1: the two hat_linear launches)
+        if ops.ocab_mlp_supported(C, sd[p + ".mlp.0.weight"].shape[0], dt) and _r8(C) == C and not self.opt.no_ocab_mlp:
+            oc.mlpf = ops.pack_ocab_mlp(sd[p + ".mlp.0.weight"], sd[p + ".mlp.0.bias"], sd[p + ".mlp.2.weight"], sd[p + ".mlp.2.bias"], dev)
+        oc.bias_rot = table[rot].t().contiguous().to(dev)  # [heads][M*M]
+        oc.qlog2 = qlog2
+        # q and kv projections in one launch (both read LayerNorm1's output) where hat_ocab_qkv is built and the OCAB has
+        # no ESC on its key / value path (HAT_NO_OCAB_QKV=1: two hat_linear launches on two streams)
+        if C == 144 and dt == ops.HAT_BF16 and not cfg.get("ocab_esc_enable", False) and not self.opt.no_ocab_qkv:
+            oc.qkvf = ops.pack_ocab_qkv(sd[p + ".q_proj.weight"], sd.get(p + ".q_proj.bias"), sd[p + ".kv_proj.weight"],
+                                        sd.get(p + ".kv_proj.bias"), qscale, dev)
+        if cfg.get("ocab_esc_enable", False):
+            oc.esc = self._esc(sd, p + ".esc_core", p + ".esc_plk", cfg["ocab_esc_pdim"], cfg["ocab_esc_kernel"])
+        if self.focus:  # saliency head: 1x1 C -> C/4, GELU, 1x1 -> 1                     hatx_arch.py:357-361
+            oc.fh0 = ops.pack_conv_weight(sd[p + ".focus_head.0.weight"], sd[p + ".focus_head.0.bias"], dt, dev)
+            oc.fh2 = ops.pack_conv_weight(sd[p + ".focus_head.2.weight"], sd[p + ".focus_head.2.bias"], dt, dev)
+        return oc
 
     def _pack_ps(self, sd, key, r):
         """Conv feeding nn.PixelShuffle(r) (hat_arch.py:598-602): output channel c*r^2 + i*r + j is stored
@@ -293,6 +417,67 @@ class HATEngine:
         perm = (n % cps) * (r * r) + n // cps  # packed row n' = ij*cps + c  <-  original channel c*r^2 + ij
         return ops.pack_conv_weight(w, sd[key + ".bias"], self.dtype, self.dev, out_perm=perm)
 
+    def _resolve(self):
+        """Every launch route that does not depend on the input shape, decided once for the packed network."""
+        layers, dt, C = self.layers, self.dtype, self.C
+        escs = [hb.esc for G in layers for hb in G.habs] + [G.ocab.esc for G in layers if G.ocab.esc is not None]
+        wide = any(e.npad > 16 for e in escs)   # the 144 tail reads the ESC conv output as 16-channel rows
+        for gi, G in enumerate(layers):
+            oc = G.ocab
+            for i, hb in enumerate(G.habs):
+                nh = G.habs[i + 1] if i + 1 < len(G.habs) else None
+                hb.next_ln = (nh.n1, nh.esc.pdim) if nh is not None else (oc.n1, oc.esc.pdim if oc.esc is not None else 0)
+                # (the 144 tail is ruled out network-wide by any wide ESC, the 180 tail only by its consumer's: kept as found)
+                if hb.fold is not None:
+                    hb.tail = "fused144" if hb.tail144_ok and not wide else "aggr_cab"
+                else:
+                    hb.tail = "fused180" if hb.tail180_ok and hb.next_ln[1] <= 16 else "aggr"
+            # the OCAB's last layer hands its result to the group's 3x3 conv as T rows
+            G.to_conv = bool(G.conv is not None and dt == ops.HAT_BF16 and _r8(C) == C and oc.mlp2.frag and not self.opt.no_bf16_conv_in)
+            cv = G.conv
+            if cv is not None and dt == ops.HAT_BF16 and not self.opt.no_conv_ln and cv.n_slices == 1 and cv.nout == cv.nt * 16:
+                if gi + 1 < len(layers):
+                    nhs = layers[gi + 1].habs
+                    nxt, gap_c = (nhs[0].n1, nhs[0].esc.pdim) if nhs else (None, 0)
+                else:
+                    nxt, gap_c = (self.norm, 0) if self.conv_after_body is not None else (None, 0)
+                G.conv_ln = (nxt, gap_c) if nxt is not None and gap_c in (0, 4, 8, 12, 16) else None
+        self._resolve_stream16()
+        # what every workspace is sized by
+        hab0 = layers[0].habs[0] if layers and layers[0].habs else None
+        self._hab0 = hab0
+        self._yw = max([16] + [e.npad for e in escs])      # channels of the ESC conv output / floats per GAP partial block
+        self._kpad = max([hab0.esc.kpad if hab0 else 0] + [G.ocab.esc.kpad for G in layers if G.ocab.esc is not None])
+
+    def _resolve_stream16(self):
+        """Where the residual stream is handed over as FP16 rows (bf16 path at embed_dim 144, HAT_NO_T16=1: nowhere).
+        A hand-over is FP16 only when EVERY reader of that buffer takes FP16 rows: hat_hab_tail3 (t_in / t_out), the OCAB
+        projection (hat_linear: r1 and its output, in place), hat_ocab_mlp (r1) and the group conv (hat_conv: r1 and its
+        output, in place).  hat_layernorm, hat_add_f32, the unfused OCAB / conv-LN fallbacks and the embed_dim-180 tail read
+        fp32.  Sets G.ocab16, G.out16 (group input of the next group, or the stream after the last group) and hb.out16."""
+        if not self.t16:
+            return
+        layers = self.layers
+        tail16 = lambda hb: hb.tail == "fused144" and hb.ffn3 is not None and hb.ffn3.C == 144
+        conv16 = lambda G: bool(G.conv is not None and not G.conv.frag and G.conv.ksize > 1 and G.conv.nt == 9
+                                and G.conv.n_slices == 1 and G.conv.nout == 144)
+        for G in layers:
+            oc = G.ocab
+            G.ocab16 = bool(G.habs and tail16(G.habs[-1]) and G.to_conv and oc.mlpf is not None and oc.proj.frag
+                            and oc.proj.nt == 9 and getattr(oc.proj, "ksplit", None) is None and oc.esc is None)
+            for i, hb in enumerate(G.habs):
+                # the stream leaves as FP16 rows when its reader takes them: the next fused tail, or, after the last block,
+                # the OCAB projection and MLP (43.7 -> 43.6 dB at 720p by emulation, DESIGN 4.2)
+                hb.out16 = tail16(hb) and (G.ocab16 if i + 1 == len(G.habs) else tail16(G.habs[i + 1]))
+        for gi, G in enumerate(layers):
+            if not conv16(G) or G.conv_ln is None:   # (without the fused LayerNorm, hat_layernorm reads the output)
+                continue
+            if gi + 1 < len(layers):
+                nG = layers[gi + 1]
+                G.out16 = bool(nG.habs and tail16(nG.habs[0]) and conv16(nG))
+            else:
+                G.out16 = self.conv_after_body is not None     # (the stream itself is not read after the last group)
+
     # ------------------------------------------------------------------------------------------
     def _workspace(self, B, H, W, tag=None):
         """tag: a row band of a sharded frame gets a workspace of its own (two bands of one shape must not share buffers)."""
@@ -301,18 +486,16 @@ class HATEngine:
         if ws is not None:
             self._ws_cache.move_to_end(key)
             return ws
-        C, dev, T = self.C, self.dev, self.tdt
+        C, dev, T, hab0, yw = self.C, self.dev, self.tdt, self._hab0, self._yw
         N = H * W
-        mid = self.layers[0]["habs"][0]["cab0"].nout if self.layers and self.layers[0]["habs"] else 8
+        mid = hab0.cab0.nout if hab0 is not None else 8
         hid2 = 2 * int(C * self.cfg["mlp_ratio"])  # fc1 width of GatedDconvFFN (hat_arch.py:99-100)
         z = lambda *shape, dtype=T: torch.zeros(*shape, dtype=dtype, device=dev)
         f = torch.float32
-        escs = [hb["esc"] for L in self.layers for hb in L["habs"]] + [L["ocab"]["esc"] for L in self.layers if "esc" in L["ocab"]]
-        yw = max([16] + [e.npad for e in escs])      # channels of the ESC conv output / floats per GAP partial block
         w = {
             "f0": z(B, N, C, dtype=f), "tA": z(B, N, C, dtype=f), "tB": z(B, N, C, dtype=f), "tC": z(B, N, C, dtype=f),
             # the residual stream as FP16 rows: hA = a group's input (written by the previous group conv), hB / hC = between its
-            # fused tails and through its OCAB (see _stream16_plan)
+            # fused tails and through its OCAB (see _resolve_stream16)
             "hA": (z(B, N, C, dtype=torch.float16) if self.t16 else None),
             "hB": (z(B, N, C, dtype=torch.float16) if self.t16 else None), "hC": (z(B, N, C, dtype=torch.float16) if self.t16 else None),
             "n": z(B, N, _r8(C)), "n2b": z(B, N, _r8(C)), "c1": z(B, N, _r8(mid)), "c2": z(B, N, _r8(C)), "m2": z(B, N, ops.ffn_m_ld(C)),
@@ -322,30 +505,27 @@ class HATEngine:
             "gap": z(B, max(ops.layernorm_blocks(), -(-H // 4) * -(-W // 16)), yw, dtype=f),
             "scale": z(B, 256, dtype=f), "eca_tmp": z(B, 32, 256, dtype=f),
         }
-        if any(L["ocab"].get("qkvf") is not None for L in self.layers):
+        if any(G.ocab.qkvf is not None for G in self.layers):
             w["qkv"] = z(B, N, 432)      # [q | k | v] rows of the fused projection
-        esc0 = self.layers[0]["habs"][0]["esc"] if self.layers and self.layers[0]["habs"] else None
-        kpad = max([esc0.kpad if esc0 else 0] + [L["ocab"]["esc"].kpad for L in self.layers if "esc" in L["ocab"]])
-        w["weff"] = z(B, yw, max(kpad, 64))
-        if any("esc" in L["ocab"] for L in self.layers):
+        w["weff"] = z(B, yw, max(self._kpad, 64))
+        if any(G.ocab.esc is not None for G in self.layers):
             w["yesc"] = z(B, N, _r8(C))
         if self.focus:
             w["fh"], w["sal"] = z(B, N, _r8(C // 4)), z(B, N, 8, dtype=f)   # (the saliency map stays fp32: the keys are ranked on it)
         if self.focus or self.topk < 1.0:
             w["kb"] = z(B, (H // self.ws) * (W // self.ws), -(-(self.wse * self.wse) // 16) * 16, dtype=f)   # rows of whole key tiles
-        cab2 = self.layers[0]["habs"][0]["cab2"] if self.layers and self.layers[0]["habs"] else None
-        if cab2 is not None:
+        if hab0 is not None:
+            cab2 = hab0.cab2
             tiles = ops.conv3x3_small_groups(cab2, B, H, W, self.dtype) if cab2.frag else ops.conv_tiles(cab2, H, W, self.dtype)
             w["tiles"] = tiles
             w["colsum"] = z(B, tiles, cab2.npad, dtype=f)
-        hab0 = self.layers[0]["habs"][0] if self.layers and self.layers[0]["habs"] else None
-        if hab0 is not None and "fold" in hab0:
-            cab0 = hab0["cab0"]
-            w["sweep"] = "sq" in hab0["fold"] and W % 16 == 0 and cab0.npad == 16
+        if hab0 is not None and hab0.fold is not None:
+            cab0 = hab0.cab0
+            w["sweep"] = "sq" in hab0.fold and W % 16 == 0 and cab0.npad == 16
             w["tiles1"] = ops.cab_squeeze_units(H, W) if w["sweep"] else ops.conv_tiles(cab0, H, W, self.dtype)
             w["colsum1"] = z(B, w["tiles1"], cab0.npad, dtype=f)
-            w["wf"] = z(B, hab0["esc"].aggr.nt * 3 * 512)
-            w["bias_b"] = z(B, hab0["esc"].aggr.npad, dtype=f)
+            w["wf"] = z(B, hab0.esc.aggr.nt * 3 * 512)
+            w["bias_b"] = z(B, hab0.esc.aggr.npad, dtype=f)
         if tag is not None:   # pooled sums of this band's own rows (local) and of the whole frame (global): SURVEY §8 f4
             w["gstat_l"], w["gstat_g"] = z(B, yw, dtype=f), z(B, yw, dtype=f)
             w["cstat_l"], w["cstat_g"] = z(B, 72, dtype=f), z(B, 72, dtype=f)
@@ -359,7 +539,7 @@ class HATEngine:
         w["bytes"] = sum(t.numel() * t.element_size() for v in w.values() for t in (v if isinstance(v, list) else [v])
                          if isinstance(t, torch.Tensor))
         self._ws_cache[key] = w
-        self.ws_allocations = getattr(self, "ws_allocations", 0) + 1
+        self.ws_allocations += 1
         while len(self._ws_cache) > 1 and (len(self._ws_cache) > self._ws_max
                                            or sum(v["bytes"] for v in self._ws_cache.values()) > self._ws_max_bytes):
             self._ws_cache.popitem(last=False)   # graphs captured on an evicted workspace keep their own reference
@@ -374,7 +554,7 @@ class HATEngine:
 
     def _esc_conv(self, esc: _ESC, w, n, B, H, W, n16=None):
         """n16: a compact (B,N,16) copy of n's first 16 channels when the producer wrote one (the fused HAB tail does)."""
-        if ops.esc_conv13_supported(esc.pdim, esc.ksize, self.dtype) and os.environ.get("HAT_NO_ESC13") != "1":
+        if esc.conv13:
             src, ldx = (n16, 16) if n16 is not None else (n, _r8(self.C))
             ops.esc_conv13(src, w["weff"], w["y16"], B=B, H=H, W=W, ldx=ldx, kpad=esc.kpad, dtype=self.dtype)
             return
@@ -393,77 +573,32 @@ class HATEngine:
         depthwise 3x3), its first pdim channels ksize // 2 + 1 rows (the ESC conv under the same row)."""
         return max(3, esc.ksize // 2 + 1)
 
-    def _ocab_halo(self, oc) -> int:
+    def _ocab_halo(self, oc: _Ocab) -> int:
         """Ghost rows an OCAB reads: its key windows reach pad = ceil((wse - ws) / 2) rows beyond the query window (HATX's
         ceil padding, hatx_arch.py:315-321: pad above, pad - 1 below); with OCAB-ESC the keys are ESC(LN(x)), whose conv reads
         ksize // 2 rows further."""
         pad = (self.wse - self.ws + 1) // 2
-        return pad + (oc["esc"].ksize // 2 if "esc" in oc else 0)
+        return pad + (oc.esc.ksize // 2 if oc.esc is not None else 0)
 
     def band_halo(self) -> int:
         """The deepest ghost-row refresh the band-sharded forward of this network requests (band_parallel.make_bands checks
         the band geometry against it): the largest of the HAB and OCAB refreshes and the 8 rows before the network's last
         convs.  HAT-S / HAT: 8; hatx_live_x2 shapes (ESC 15, OCAB-ESC 17, 13x13 key windows): 11; the live HATX config: 13."""
         d = 8
-        for L in self.layers:
-            d = max([d, self._ocab_halo(L["ocab"])] + [self._hab_halo(hb["esc"]) for hb in L["habs"]])
+        for G in self.layers:
+            d = max([d, self._ocab_halo(G.ocab)] + [self._hab_halo(hb.esc) for hb in G.habs])
         return d
 
-    def _to_conv(self, L) -> bool:
-        """The OCAB's last layer hands its result to the group's 3x3 conv as T rows (run_ocab's as_conv_input)."""
-        return bool(L["conv"] is not None and self.dtype == ops.HAT_BF16 and _r8(self.C) == self.C and L["ocab"]["mlp2"].frag
-                    and not os.environ.get("HAT_NO_BF16_CONV_IN"))
-
-    def _conv_ln_next(self, gi):
-        """(gamma, beta), gap_c of the LayerNorm the group conv of group gi emits from its epilogue, or None when it does not."""
-        L = self.layers[gi]
-        cv = L["conv"]
-        if cv is None or self.dtype != ops.HAT_BF16 or os.environ.get("HAT_NO_CONV_LN") or cv.n_slices != 1 or cv.nout != cv.nt * 16:
-            return None
-        if gi + 1 < len(self.layers):
-            nh = self.layers[gi + 1]["habs"]
-            nxt, gap_c = (nh[0]["n1"], nh[0]["esc"].pdim) if nh else (None, 0)
-        else:
-            nxt, gap_c = (self.norm, 0) if self.conv_after_body is not None else (None, 0)
-        return (nxt, gap_c) if nxt is not None and gap_c in (0, 4, 8, 12, 16) else None
-
-    def _stream16_plan(self):
-        """Where the residual stream is handed over as FP16 rows (bf16 path at embed_dim 144, HAT_NO_T16=1: nowhere).
-        A hand-over is FP16 only when EVERY reader of that buffer takes FP16 rows: hat_hab_tail3 (t_in / t_out), the OCAB
-        projection (hat_linear: r1 and its output, in place), hat_ocab_mlp (r1) and the group conv (hat_conv: r1 and its
-        output, in place).  hat_layernorm, hat_add_f32, the unfused OCAB / conv-LN fallbacks and the embed_dim-180 tail read
-        fp32.  Returns (in16, ocab16): in16[g] — group g's input (the previous group conv's output; in16[len] the stream after
-        the last group) is FP16; ocab16[g] — group g's last tail, its OCAB projection and MLP carry FP16 rows."""
-        ng = len(self.layers)
-        in16, ocab16 = [False] * (ng + 1), [False] * ng
-        if not self.t16:
-            return in16, ocab16
-        tail16 = lambda hb: bool("fold" in hb and hb.get("tail") and "ffn3" in hb and hb["ffn3"].C == 144)
-        conv16 = lambda L: bool(L["conv"] is not None and not L["conv"].frag and L["conv"].ksize > 1 and L["conv"].nt == 9
-                                and L["conv"].n_slices == 1 and L["conv"].nout == 144)
-        for g, L in enumerate(self.layers):
-            oc = L["ocab"]
-            ocab16[g] = bool(L["habs"] and tail16(L["habs"][-1]) and self._to_conv(L) and oc["mlpf"] is not None
-                             and oc["proj"].frag and oc["proj"].nt == 9 and getattr(oc["proj"], "ksplit", None) is None
-                             and "esc" not in oc)
-        for g, L in enumerate(self.layers):
-            if not conv16(L) or self._conv_ln_next(g) is None:   # (without the fused LayerNorm, hat_layernorm reads the output)
-                continue
-            if g + 1 < ng:
-                nL = self.layers[g + 1]
-                in16[g + 1] = bool(nL["habs"] and tail16(nL["habs"][0]) and conv16(nL))
-            else:
-                in16[ng] = self.conv_after_body is not None     # (the stream itself is not read after the last group)
-        return in16, ocab16
-
-    def _side_stream(self):
-        if os.environ.get("HAT_ONE_STREAM") == "1":
+    def _side_stream(self, f: _Fwd):
+        """The stream the short independent chains go to: the current one for a band or with one_stream."""
+        if f.band is not None or f.one_stream:
             return torch.cuda.current_stream(self.dev)
-        if getattr(self, "_s1", None) is None:
+        if self._s1 is None:
             self._s1 = torch.cuda.Stream(device=self.dev)
         return self._s1
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, *, one_stream: Optional[bool] = None) -> torch.Tensor:
+        """one_stream: overrides HAT_ONE_STREAM for this call (plan export records the one-stream order)."""
         if not x.is_cuda:
             raise RuntimeError("HAT forward needs a device tensor: the HIP path is the only path")
         if x.device != self.dev:
@@ -471,7 +606,7 @@ class HATEngine:
         # kernels are enqueued on the CURRENT stream of the engine's device: make that device current for the launches
         # (the C side never switches devices), and serialise callers: workspace and side stream are per-engine state
         with self._lock, torch.cuda.device(self.dev):
-            return self._forward(x)
+            return self._forward(x, one_stream=one_stream)
 
     def ocab_only(self, t: torch.Tensor, group: int, H: int, W: int) -> torch.Tensor:
         """Run only the OCAB of residual group `group` on tokens t (B, H*W, C) fp32 -> (B, H*W, C) fp32 (used by the tests)."""
@@ -479,15 +614,15 @@ class HATEngine:
         with self._lock, torch.cuda.device(self.dev):
             return self._forward(x, only_ocab=(t.to(self.dev, torch.float32).contiguous(), group))
 
-    def _forward(self, x: torch.Tensor, only_ocab=None) -> torch.Tensor:
-        gen = self._forward_gen(x, only_ocab=only_ocab)
+    def _forward(self, x: torch.Tensor, only_ocab=None, one_stream=None) -> torch.Tensor:
+        gen = self._forward_gen(x, only_ocab=only_ocab, one_stream=one_stream)
         try:
             req = next(gen)
         except StopIteration as done:
             return done.value
         raise RuntimeError(f"the unsharded forward must not reach an exchange point (got {req[0]!r})")
 
-    def _forward_gen(self, x: torch.Tensor, only_ocab=None, band=None):
+    def _forward_gen(self, x: torch.Tensor, only_ocab=None, band=None, one_stream=None):
         """The forward as a generator.  Unsharded (band=None) it never yields and returns the output.  For one ROW BAND of a
         sharded frame (band: tile_parallel.Band, x = the band's rows + ghost rows of the LR frame) it yields at
         every point where bands must exchange: ("halo", [(tensor, depth) ...]) — refresh `depth` ghost rows above and below
@@ -497,374 +632,377 @@ class HATEngine:
         if x.dim() != 4 or x.shape[1] != self.cfg["in_chans"]:
             raise RuntimeError(f"expected (B,{self.cfg['in_chans']},H,W), got {tuple(x.shape)}")
         B, _, H, W = x.shape
-        ws = self.ws
-        if H % ws or W % ws:  # the reference raises from calculate_mask's view (hat_arch.py:815), SURVEY F4
-            raise RuntimeError(f"input size ({H},{W}) is not a multiple of window_size {ws}")
+        if H % self.ws or W % self.ws:  # the reference raises from calculate_mask's view (hat_arch.py:815), SURVEY F4
+            raise RuntimeError(f"input size ({H},{W}) is not a multiple of window_size {self.ws}")
         x = x.to(torch.float32).contiguous()
-        cfg, dt, C = self.cfg, self.dtype, self.C
-        N, ldc = H * W, _r8(C)
-        bd = band
-        w = dict(self._workspace(B, H, W, tag=(None if bd is None else ("band", bd.idx, bd.n))))   # (a shallow copy: the forward swaps the two LayerNorm-output buffers locally)
-        if bd is not None:
-            if (bd.e1 - bd.e0) != H:
-                raise RuntimeError(f"band {bd.idx} holds frame rows [{bd.e0}, {bd.e1}) but the input has {H} rows")
-            lo, own, npix_full = bd.lo, bd.own, bd.Hfull * W
-
-            def pooled(src, ld, C_, dst, off=0, r0=None, r1=None, c0=0, c1=None):
-                ops.rect_sum(src, dst, w["rs_tmp"], w["rs_cnt"], B=B, W=W, ld=ld, C_=C_, r0=(lo if r0 is None else r0),
-                             r1=(lo + own if r1 is None else r1), c0=c0, c1=c1, out_off=off)
-
-            def gstat(esc):
-                """(local, global) ESC pool vectors as (B, 16) views, (B, 32) for pdim > 16: hat_esc_weights reads one block
-                of that many floats per sample, whatever width the workspace gives the buffers (yw)."""
-                gs = 32 if esc.pdim > 16 else 16
-                return tuple(w[k].view(-1)[:B * gs].view(B, gs) for k in ("gstat_l", "gstat_g"))
-        s = self.scale
-        y = torch.empty(B, cfg["in_chans"], H * s, W * s, dtype=torch.float32, device=self.dev)
-        mean = RGB_MEAN if cfg["in_chans"] == 3 else (0.0,) * 4
-        r = float(cfg.get("img_range", 1.0))
-        geo = dict(B=B, H=H, W=W, dtype=dt)
-        ln = lambda src, dst, gb, out_f32=False, gap_c=0: ops.layernorm(
-            src, dst, gb[0], gb[1], B=B, npix=N, C_=C, ldy=(C if out_f32 else ldc), out_f32=out_f32, dtype=dt,
-            gap=(w["gap"] if gap_c else None), gap_c=gap_c)
-
-        tA, tB, tC = w["tA"], w["tB"], w["tC"]
-        LNB = ops.layernorm_blocks()
-
-        def run_ocab(L, t, have_n, nblk, as_conv_input=False):
-            """OCAB of residual group L on the residual stream t -> the buffer holding the result   hat_arch.py:326-393
-            as_conv_input: the only consumer is the group's 3x3 conv, which reads its input as T (bf16) rows anyway: the last
-            linear then stores its fp32 result (+ residual) as T rows into w["ao"] and the fp32 stream is not written at all
-            (same values as the conv's own staging conversion; 650 B/px less traffic per group)."""
-            oc = L["ocab"]
-            esc = oc.get("esc")  # OCAB                                                    :326-393
-            if bd is not None:   # key / value windows reach (wse - ws) / 2 rows into the neighbours' bands             :359-360
-                # (+ the ESC conv under them with OCAB-ESC).  HATX's focus bias and top-k need nothing more: the saliency head is
-                # 1x1 and keys are ranked per window.  A window with owned query rows has its whole key window inside the buffer
-                # (ghost 16 >= pad), and the first / last band have the frame edge at their buffer edge, so the padded keys and
-                # the lowest-index tie rule are the frame's.
-                yield ("halo", [((w["n"] if have_n else t), self._ocab_halo(oc))])
-            if not have_n:
-                ln(t, w["n"], oc["n1"], gap_c=(esc.pdim if esc else 0))
-                nblk = LNB
-            kv_src = w["n"]
-            if esc is not None:  # K/V from ESC(LN(x))                                     :336-344
-                if bd is not None:   # the ESC pool over the whole FRAME: this band's rows, then ONE more reduce per group
-                    gl, gg = gstat(esc)
-                    pooled(w["n"], ldc, esc.pdim, gl)
-                    yield ("reduce", [(gl, gg, esc.pdim)])
-                    self._esc_w(esc, w, B, bd.Hfull, W, 1, gap=gg)
-                    self._esc_conv(esc, w, w["n"], B, H, W)
-                else:
-                    self._esc_lk(esc, w, w["n"], B, H, W, nblk)
-                self._run_lin(esc.aggr, w["n"], w["yesc"], **geo, ldx=ldc, ldo=ldc, x0=w["y16"], c_split=esc.pdim, ldx0=w["y16"].shape[2])
-                kv_src = w["yesc"]
-            qbuf, kvbuf, ldq, ldkv = w["q"], w["kv"], ldc, w["kv"].shape[2]
-            if oc.get("qkvf") is not None and esc is None:
-                ops.ocab_qkv(oc["qkvf"], w["n"], w["qkv"], B=B, H=H, W=W, ldx=ldc, ldo=432, dtype=dt)
-                qbuf, kvbuf, ldq, ldkv = w["qkv"], w["qkv"].view(-1)[144:], 432, 432
-            else:
-                s0 = torch.cuda.current_stream(self.dev)   # q and kv projections are independent
-                s1 = s0 if bd is not None else self._side_stream()
-                s1.wait_stream(s0)
-                with torch.cuda.stream(s1):
-                    self._run_lin(oc["q"], w["n"], w["q"], **geo, ldx=ldc, ldo=ldc)
-                self._run_lin(oc["kv"], kv_src, w["kv"], **geo, ldx=ldc, ldo=w["kv"].shape[2])
-                s0.wait_stream(s1)
-            if self.focus or self.topk < 1.0:   # HATX: focus bias on the logits and / or top-k key pruning   hatx_arch.py:421-449
-                nk, pad = self.wse * self.wse, (self.wse - ws + 1) // 2
-                if self.focus:
-                    ops.conv(oc["fh0"], kv_src, w["fh"], **geo, ldx=ldc, ldo=w["fh"].shape[2], act=ACT_GELU, n_store=_r4(C // 4))
-                    ops.conv(oc["fh2"], w["fh"], w["sal"], **geo, ldx=w["fh"].shape[2], ldo=8, n_store=4, out_mode=O_NHWC_F32)
-                k_keep = max(1, int(self.topk * nk)) if self.topk < 1.0 else nk
-                ops.ocab_keybias(w["sal"] if self.focus else None, kvbuf, w["kb"], B=B, H=H, W=W, C_=C, ws=ws, wse=self.wse, pad=pad,
-                                 k_keep=k_keep, ldsal=(-8 if dt == ops.HAT_BF16 else 8), ldkv=ldkv, dtype=dt)
-                ops.ocab_attention_kb(qbuf, kvbuf, oc["bias_rot"], w["kb"], w["ao"], B=B, H=H, W=W, C_=C, heads=L["heads"], ws=ws,
-                                      wse=self.wse, pad=pad, ldq=ldq, ldkv=ldkv, ldo=ldc, dtype=dt)
-            else:
-                ops.ocab_attention(qbuf, kvbuf, oc["bias_rot"], w["ao"], B=B, H=H, W=W, C_=C, heads=L["heads"], ws=ws,
-                                   wse=self.wse, ldq=ldq, ldkv=ldkv, ldo=ldc, dtype=dt, q_log2=oc["qlog2"])
-            tout = tB if t is tA else t  # never write the RHAG input buffer (an FP16 t is hB / hC: proj and MLP take it in place)
-            if oc["proj"].frag:  # norm2 (:306) rides on the projection's epilogue
-                self._run_lin(oc["proj"], w["ao"], tout, **geo, ldx=ldc, ldo=C, out_mode=O_NHWC_F32, r1=t, ldr1=C,
-                              ln=oc["n2"], ln_out=w["n"], ld_ln=ldc)
-            else:
-                self._run_lin(oc["proj"], w["ao"], tout, **geo, ldx=ldc, ldo=C, out_mode=O_NHWC_F32, r1=t, ldr1=C)
-                ln(tout, w["n"], oc["n2"])
-            if oc["mlpf"] is not None:   # fc1 + GELU + fc2 + residual fused: the hidden tensor never reaches HBM
-                dst = w["ao"] if as_conv_input else tout
-                ops.ocab_mlp(oc["mlpf"], w["n"], tout, dst, B=B, H=H, W=W, ldx=ldc, ldr1=C, ldo=(ldc if as_conv_input else C),
-                             out_f32=not as_conv_input, dtype=dt)
-                return dst
-            self._run_lin(oc["mlp0"], w["n"], w["g"], **geo, ldx=ldc, ldo=w["g"].shape[2], act=ACT_GELU)
-            if as_conv_input:
-                self._run_lin(oc["mlp2"], w["g"], w["ao"], **geo, ldx=w["g"].shape[2], ldo=ldc, out_mode=O_NHWC_T, r1=tout, ldr1=C)
-                return w["ao"]
-            self._run_lin(oc["mlp2"], w["g"], tout, **geo, ldx=w["g"].shape[2], ldo=C, out_mode=O_NHWC_F32, r1=tout, ldr1=C)
-            return tout
-
+        w = dict(self._workspace(B, H, W, tag=(None if band is None else ("band", band.idx, band.n))))
+        if band is not None and band.e1 - band.e0 != H:
+            raise RuntimeError(f"band {band.idx} holds frame rows [{band.e0}, {band.e1}) but the input has {H} rows")
+        f = _Fwd(self, w, B, H, W, band, self.opt.one_stream if one_stream is None else one_stream)
         if only_ocab is not None:   # test hook: one OCAB on a given residual stream (block-level parity against reference goldens)
             t_in, gidx = only_ocab
-            w["tB"].copy_(t_in.reshape(B, N, C))
-            return (yield from run_ocab(self.layers[gidx], w["tB"], False, ops.layernorm_blocks())).clone()
-        # (x - mean) * img_range ; conv_first                                           :849-853
-        ops.conv(self.conv_first, x, w["f0"], **geo, ldx=0, ldo=C, x_mode=X_NCHW_F32_MEAN, out_mode=O_NHWC_F32,
-                 in_scale=r, mean=mean)
-        if self.pe_norm is not None:  # patch_embed + LN                                 :836
-            ln(w["f0"], tA, self.pe_norm, out_f32=True)
+            w["tB"].copy_(t_in.reshape(B, H * W, self.C))
+            f.t = w["tB"]
+            return (yield from self._ocab(f, self.layers[gidx], as_conv_input=False)).clone()
+        y = torch.empty(B, self.cfg["in_chans"], H * self.scale, W * self.scale, dtype=torch.float32, device=self.dev)
+        self._head(f, x)
+        for G in self.layers:
+            for hb in G.habs:   # HAB                                                            :217-238
+                yield from self._hab_prologue(f, hb)
+                getattr(self, "_tail_" + hb.tail)(f, hb)
+            tout = yield from self._ocab(f, G, as_conv_input=G.to_conv)
+            yield from self._group_end(f, G, tout)
+        yield from self._body_end(f)
+        self._upsample(f, y)
+        return y
+
+    # ------------------------------------------------------------------------------------------ stage steps
+    def _head(self, f: _Fwd, x):
+        """(x - mean) * img_range ; conv_first ; patch_embed LN ; + absolute_pos_embed     :836-838, :849-853"""
+        w, tA, C = f.w, f.w["tA"], self.C
+        r = float(self.cfg.get("img_range", 1.0))
+        ops.conv(self.conv_first, x, w["f0"], **f.geo, ldx=0, ldo=C, x_mode=X_NCHW_F32_MEAN, out_mode=O_NHWC_F32,
+                 in_scale=r, mean=self._mean())
+        if self.pe_norm is not None:
+            f.ln(w["f0"], tA, self.pe_norm, out_f32=True)
         else:
             tA.copy_(w["f0"])        # device-to-device copy on the current stream
-        if self.ape is not None and bd is not None:   # a band adds ITS rows [e0, e1) of the frame's position table
-            if self.ape.numel() != npix_full * C:
-                raise RuntimeError(f"absolute_pos_embed holds {self.ape.numel() // C} positions but the frame has {npix_full} "
-                                   f"pixels (ape=True fixes the input size to img_size, hat_arch.py:699-702)")
-            ops.add_f32(tA, self.ape[bd.e0 * W * C:bd.e1 * W * C], tA, B=B, n=N * C, c_bstride=0)
-        elif self.ape is not None:      # x + absolute_pos_embed (1, num_patches, C)          :837-838
-            if self.ape.numel() != N * C:
-                raise RuntimeError(f"absolute_pos_embed holds {self.ape.numel() // C} positions but the input has {N} "
-                                   f"pixels (ape=True fixes the input size to img_size, hat_arch.py:699-702)")
-            ops.add_f32(tA, self.ape, tA, B=B, n=N * C, c_bstride=0)
-        # the group conv's epilogue emits the LayerNorm its consumer starts with (the next group's first norm1, or HAT.norm)
-        grp_n = grp_n16 = False   # ... so w["n"] (and w["n16"]) are already valid when a group starts
-        grp_nblk = LNB
-        in16, ocab16 = self._stream16_plan()
-        gin = tA
-        for gi, L in enumerate(self.layers):
-            # gin: the group's input — hA (FP16 rows) when the previous group conv wrote them there, else tA
-            t = gin           # current value of the residual stream (the group input must survive until the RHAG tail)
-            have_n = grp_n    # w["n"] already holds the next LayerNorm of t (emitted by the fused FFN / the group conv)
-            have_n16 = grp_n16  # ... and w["n16"] a compact copy of its first 16 channels
-            nblk = grp_nblk   # number of GAP partial blocks currently in w["gap"]
-            grp_n = grp_n16 = False
-            oc = L["ocab"]
-            for i, hb in enumerate(L["habs"]):  # HAB                                     :217-238
-                esc = hb["esc"]
-                if bd is not None and not have_n:   # (LayerNorm1 is recomputed on the ghost rows from the refreshed stream)
-                    yield ("halo", [(t, self._hab_halo(esc))])
-                if not have_n:
-                    ln(t, w["n"], hb["n1"], gap_c=esc.pdim)
-                    nblk, have_n16 = LNB, False
-                elif bd is not None:
-                    # what this block reads beyond the band's own rows: t one row (depthwise 3x3 of the FFN), LayerNorm1's
-                    # output three rows (the two CAB convs under it) and its first pdim channels ksize / 2 + 1 = seven rows
-                    # (13x13 conv under the FFN's halo row)
-                    er = esc.ksize // 2 + 1
-                    yield ("halo", [(t, 1)] + ([(w["n"], 3), (w["n16"], er)] if have_n16 else [(w["n"], self._hab_halo(esc))]))
-                gapb = None
-                if bd is not None:   # the ESC pool (esc_arch.py:96,121) over the whole FRAME: this band's share, then the sum
-                    gstl, gapb = gstat(esc)   # (gapb: summed over the bands together with the CAB pool below: ONE reduce per HAB)
-                    if have_n16:
-                        pooled(w["n16"], 16, esc.pdim, gstl)
-                    else:
-                        pooled(w["n"], ldc, esc.pdim, gstl)
-                mid = hb["cab0"].nout
-                if "fold" in hb:
-                    # c2 = conv3x3(c1) never exists: its ECA pooling follows from the sums of c1 (hat_cab_fold) and the
-                    # scaled expand conv is three more k-steps of the aggregation GEMM (hat_aggr_cab).
-                    # The two tiny per-sample kernels (one workgroup each, latency-bound) run on a side stream next to the
-                    # convs they do not depend on: esc_weights beside the CAB squeeze conv, cab_fold beside the 13x13 conv.
-                    fo = hb["fold"]
-                    s0 = torch.cuda.current_stream(self.dev)
-                    s1 = s0 if bd is not None else self._side_stream()
-                    # The critical chain — ESC weight kernel -> 13x13 conv -> tail — stays on ONE stream: every hop between
-                    # streams costs an event wait of ~12 us on this runtime (kernel trace: 2 hops per block = 0.9 ms per
-                    # frame when the 13x13 conv sat on the side stream).  The CAB squeeze conv and its fold are shorter and
-                    # go to the side stream (HAT_ESC_SIDE=1: the round-2 arrangement, for A/B).
-                    def squeeze_chain():
-                        if w["sweep"]:
-                            ops.cab_squeeze(w["n"], fo["sq"][0], fo["sq"][1], w["c1"], w["colsum1"], B=B, H=H, W=W, C_=C, ldx=ldc, dtype=dt)
-                        else:
-                            ops.conv(hb["cab0"], w["n"], w["c1"], **geo, ldx=ldc, ldo=8, act=ACT_GELU, n_store=8, colsum=w["colsum1"])
-                        if bd is None:
-                            ops.cab_fold(w["c1"], w["colsum1"], w["tiles1"], hb["cab0"].npad, fo["w2"], fo["b2"], hb["eca_w"],
-                                         hb["eca_w"].numel(), fo["ba"], float(cfg["conv_scale"]), w["scale"], w["wf"], w["bias_b"],
-                                         w["eca_tmp"], B=B, H=H, W=W, C_=C, mid=mid, dtype=dt, w2f=fo["w2f"])
-                    if bd is not None:
-                        # band-sharded: the sums hat_cab_fold takes from c1 (hat_arch.py:73 via the linearity of the expand conv)
-                        # are this band's share of [total | first row | last row | first column | last column | 4 corners]
-                        squeeze_chain()
-                        st = w["cstat_l"]
-                        pooled(w["c1"], 8, 8, st, 0)
-                        pooled(w["c1"], 8, 8, st, 24, c0=0, c1=1)
-                        pooled(w["c1"], 8, 8, st, 32, c0=W - 1, c1=W)
-                        if bd.r0 == 0:
-                            pooled(w["c1"], 8, 8, st, 8, r0=lo, r1=lo + 1)
-                            pooled(w["c1"], 8, 8, st, 40, r0=lo, r1=lo + 1, c0=0, c1=1)
-                            pooled(w["c1"], 8, 8, st, 48, r0=lo, r1=lo + 1, c0=W - 1, c1=W)
-                        if bd.r1 == bd.Hfull:
-                            pooled(w["c1"], 8, 8, st, 16, r0=lo + own - 1, r1=lo + own)
-                            pooled(w["c1"], 8, 8, st, 56, r0=lo + own - 1, r1=lo + own, c0=0, c1=1)
-                            pooled(w["c1"], 8, 8, st, 64, r0=lo + own - 1, r1=lo + own, c0=W - 1, c1=W)
-                        yield ("reduce", [(gstl, gapb, esc.pdim), (st, w["cstat_g"], 72)])
-                        ops.cab_fold(None, None, 1, hb["cab0"].npad, fo["w2"], fo["b2"], hb["eca_w"], hb["eca_w"].numel(), fo["ba"],
-                                     float(cfg["conv_scale"]), w["scale"], w["wf"], w["bias_b"], None, B=B, H=bd.Hfull, W=W, C_=C,
-                                     mid=mid, dtype=dt, stats=w["cstat_g"], w2f=fo["w2f"])
-                        self._esc_w(esc, w, B, bd.Hfull, W, 1, gap=gapb)
-                        self._esc_conv(esc, w, w["n"], B, H, W, n16=(w["n16"] if have_n16 else None))
-                    elif os.environ.get("HAT_ESC_SIDE") == "1":
-                        self._esc_w(esc, w, B, H, W, nblk)
-                        s1.wait_stream(s0)                              # n and the 13x13 weights are ready
-                        with torch.cuda.stream(s1):                     # chain 2: 13x13 conv
-                            self._esc_conv(esc, w, w["n"], B, H, W, n16=(w["n16"] if have_n16 else None))
-                        squeeze_chain()
-                    else:
-                        s1.wait_stream(s0)                              # n is ready
-                        with torch.cuda.stream(s1):
-                            squeeze_chain()
-                        self._esc_w(esc, w, B, H, W, nblk)
-                        self._esc_conv(esc, w, w["n"], B, H, W, n16=(w["n16"] if have_n16 else None))
-                    s0.wait_stream(s1)                              # both chains are done
-                    if hb.get("tail"):   # (also the faster choice on small frames: 64x64 HAT-S 3.97 vs 6.19 ms per forward)
-                        # aggregation + folded CAB + residuals + the whole FFN in ONE launch: tB never exists in HBM
-                        if i + 1 < len(L["habs"]):
-                            nxt, gap_c = L["habs"][i + 1]["n1"], L["habs"][i + 1]["esc"].pdim
-                        else:
-                            nxt, gap_c = oc["n1"], (oc["esc"].pdim if "esc" in oc else 0)
-                        # The stream leaves as FP16 rows when its reader takes them: the next fused tail, or, after the last
-                        # block, the OCAB projection and MLP (_stream16_plan; 43.7 -> 43.6 dB at 720p by emulation, DESIGN 4.2).
-                        nh = L["habs"][i + 1] if i + 1 < len(L["habs"]) else None
-                        out16 = bool(self.t16 and "ffn3" in hb and hb["ffn3"].C == 144
-                                     and (ocab16[gi] if nh is None else (nh.get("tail") and "ffn3" in nh and nh["ffn3"].C == 144)))
-                        if out16:
-                            tout = w["hB"] if t is not w["hB"] else w["hC"]
-                        else:
-                            tout = tB if t is not tB else tC
-                        ops.hab_tail(hb.get("ffn3", hb["ffn"]), esc.aggr, t, tout, hb["n2"][0], hb["n2"][1], n=w["n"], ldn_in=ldc, y16=w["y16"],
-                                     c1=w["c1"], wf=w["wf"], bias_b=w["bias_b"], B=B, H=H, W=W, dtype=dt, ln1=nxt, n_out=w["n2b"],
-                                     ldn=ldc, gap_out=w["gap"], gap_c=gap_c, n16_out=(w["n16"] if self.use_n16 else None))
-                        w["n"], w["n2b"] = w["n2b"], w["n"]      # the kernel reads n with a halo: its output n' is another buffer
-                        if _EMU_T16 is not None and not out16:   # measurement only (tools/residual16_psnr.py): what a 16-bit residual stream would cost
-                            tout.copy_(tout.to(_EMU_T16).to(torch.float32))
-                        t, have_n, nblk = tout, True, ops.ffn_tiles(hb["ffn"], H, W, dt)
-                        have_n16 = self.use_n16
-                        continue
-                    ops.aggr_cab(esc.aggr, w["n"], tB, w["c1"], w["wf"], w["bias_b"], **geo, ldx=ldc, ldo=C, x0=w["y16"],
-                                 c_split=esc.pdim, ldx0=w["y16"].shape[2], r1=t, ldr1=C)
-                    pre_ln = False
-                else:
-                    c3 = ops.conv3x3_small if hb["cab0"].frag else ops.conv
-                    c3(hb["cab0"], w["n"], w["c1"], **geo, ldx=ldc, ldo=_r8(mid), act=ACT_GELU, n_store=_r4(mid))
-                    c3 = ops.conv3x3_small if hb["cab2"].frag else ops.conv
-                    c3(hb["cab2"], w["c1"], w["c2"], **geo, ldx=_r8(mid), ldo=ldc, colsum=w["colsum"])
-                    if bd is None:
-                        ops.eca_scale(w["colsum"], w["tiles"], hb["cab2"].npad, N, hb["eca_w"], hb["eca_w"].numel(),
-                                      float(cfg["conv_scale"]), w["eca_tmp"], w["scale"], B=B, C_=C)
-                        self._esc_lk(esc, w, w["n"], B, H, W, nblk)
-                    else:   # ECA pool of c2 (hat_arch.py:73) over the whole frame: this band's rows, then the sum over the bands
-                        # (rows of npad floats, like the per-tile column sums: hat_eca_scale writes `scale` with that stride and
-                        # the aggregation reads it so)
-                        npd = hb["cab2"].npad
-                        el, eg = (w[k].view(-1)[:B * npd].view(B, npd) for k in ("estat_l", "estat_g"))
-                        pooled(w["c2"], ldc, C, el)
-                        yield ("reduce", [(gstl, gapb, esc.pdim), (el, eg, _r4(C))])
-                        ops.eca_scale(eg, 1, npd, npix_full, hb["eca_w"], hb["eca_w"].numel(),
-                                      float(cfg["conv_scale"]), w["eca_tmp"], w["scale"], B=B, C_=C)
-                        self._esc_w(esc, w, B, bd.Hfull, W, 1, gap=gapb)
-                        self._esc_conv(esc, w, w["n"], B, H, W)
-                    if hb.get("tail180") and not any(e.npad > 16 for e in [esc]):
-                        # embed_dim 180: aggregation + scaled c2 + residuals + the whole FFN in one launch (hat_hab_tail3)
-                        if i + 1 < len(L["habs"]):
-                            nxt, gap_c = L["habs"][i + 1]["n1"], L["habs"][i + 1]["esc"].pdim
-                        else:
-                            nxt, gap_c = oc["n1"], (oc["esc"].pdim if "esc" in oc else 0)
-                        if gap_c <= 16:
-                            tout = tB if t is not tB else tC
-                            ops.hab_tail(hb["ffn3"], esc.aggr, t, tout, hb["n2"][0], hb["n2"][1], n=w["n"], ldn_in=ldc, y16=w["y16"],
-                                         bias_b=hb["bias256"], B=B, H=H, W=W, dtype=dt, ln1=nxt, n_out=w["n2b"], ldn=ldc, gap_out=w["gap"],
-                                         gap_c=gap_c, n16_out=(w["n16"] if self.use_n16 else None), r2=w["c2"], ldr2=ldc,
-                                         r2scale=w["scale"], r2scale_bstride=hb["cab2"].npad)
-                            w["n"], w["n2b"] = w["n2b"], w["n"]
-                            t, have_n, nblk = tout, True, -(-H // 8) * -(-W // 16)
-                            have_n16 = self.use_n16
-                            continue
-                    # t = t + aggr(cat(y16, n[pdim:])) + conv_scale * eca * c2                :236
-                    # hat_linear can emit LayerNorm2 of its result as hat_ffn's m_in, turning the FFN's stage 0 into a copy.
-                    # Measured at 720p HAT-S: FFN -0.034 ms, aggr +0.070 ms per block (320 more bytes per pixel to write,
-                    # and the FFN's stage 0 was already hidden behind its other workgroup) — a net loss, so it stays off.
-                    pre_ln = False and "ffn" in hb and esc.aggr.frag
-                    lnkw = dict(ln=hb["n2"], ln_out=w["m2"], ld_ln=w["m2"].shape[2], ln_ones=True) if pre_ln else {}
-                    self._run_lin(esc.aggr, w["n"], tB, **geo, ldx=ldc, ldo=C, out_mode=O_NHWC_F32, x0=w["y16"],
-                                  c_split=esc.pdim, ldx0=w["y16"].shape[2], r1=t, ldr1=C, r2=w["c2"], ldr2=ldc, r2scale=w["scale"],
-                                  r2scale_bstride=hb["cab2"].npad, **lnkw)
-                if "ffn" in hb:  # fused LN2 + fc1 + dw3x3 + gate + fc2 + residual (+ the next block's LayerNorm)
-                    if i + 1 < len(L["habs"]):
-                        nxt, gap_c = L["habs"][i + 1]["n1"], L["habs"][i + 1]["esc"].pdim
-                    else:
-                        nxt, gap_c = oc["n1"], (oc["esc"].pdim if "esc" in oc else 0)
-                    mkw = dict(m_in=w["m2"], ldm_in=w["m2"].shape[2]) if pre_ln else {}
-                    if gap_c > 16:   # (the fused kernels pool at most 16 channels: a wider ESC gets its LayerNorm + pool from hat_layernorm)
-                        ops.ffn(hb["ffn"], tB, tC, hb["n2"][0], hb["n2"][1], B=B, H=H, W=W, dtype=dt, **mkw)
-                        t, have_n, have_n16 = tC, False, False
-                    else:
-                        ops.ffn(hb["ffn"], tB, tC, hb["n2"][0], hb["n2"][1], B=B, H=H, W=W, dtype=dt, ln1=nxt, n_out=w["n"],
-                                ldn=ldc, gap_out=w["gap"], gap_c=gap_c, **mkw)
-                        # (hat_ffn / hat_ffn2 emit the LayerNorm rows only: w["n16"] still holds an OLDER block's compact copy —
-                        # the group conv's or a fused tail's — and must not be handed to the next 13x13 conv)
-                        t, have_n, have_n16, nblk = tC, True, False, ops.ffn_tiles(hb["ffn"], H, W, dt)
-                else:
-                    ln(tB, w["n"], hb["n2"])
-                    hid2 = hb["fc1"].nout
-                    self._run_lin(hb["fc1"], w["n"], w["u"], **geo, ldx=ldc, ldo=w["u"].shape[2])
-                    if self.hatx:   # SGFN: [dw(a) * silu(b) | b], hid2 channels in and out            hatx_arch.py:165-177
-                        ops.sgfn_gate(w["u"], hb["dw_w"], hb["dw_b"], w["g"], B=B, H=H, W=W, half=hid2 // 2, ldu=w["u"].shape[2],
-                                      ldo=w["g"].shape[2], dtype=dt)
-                    else:
-                        ops.dwconv_gate(w["u"], hb["dw_w"], hb["dw_b"], w["g"], B=B, H=H, W=W, hid=hid2 // 2, ldu=w["u"].shape[2],
-                                        ldo=w["g"].shape[2], dtype=dt)
-                    self._run_lin(hb["fc2"], w["g"], tB, **geo, ldx=w["g"].shape[2], ldo=C, out_mode=O_NHWC_F32, r1=tB, ldr1=C)
-                    t, have_n, have_n16 = tB, False, False
-            to_conv = self._to_conv(L)
-            tout = yield from run_ocab(L, t, have_n, nblk, as_conv_input=to_conv)
-            if bd is not None and L["conv"] is not None:   # the group's 3x3 conv reads one row beyond the band's own
-                yield ("halo", [(tout, 1)])
-            # RHAG tail: conv3x3 + group residual, written over the group input             :556
-            if L["conv"] is None:  # resi_connection == 'identity': group(x) + x                 :545-546
-                ops.add_f32(tout, tA, tA, B=B, n=N * C)
+        if self.ape is not None:   # (1, num_patches, C); a band adds ITS rows [e0, e1) of the frame's position table
+            npix, off = (f.band.Hfull * f.W, f.band.e0 * f.W * C) if f.band is not None else (f.N, 0)
+            if self.ape.numel() != npix * C:
+                raise RuntimeError(f"absolute_pos_embed holds {self.ape.numel() // C} positions but the "
+                                   f"{'frame' if f.band is not None else 'input'} has {npix} pixels (ape=True fixes the input "
+                                   f"size to img_size, hat_arch.py:699-702)")
+            ops.add_f32(tA, self.ape[off:off + f.N * C], tA, B=f.B, n=f.N * C, c_bstride=0)
+
+    def _mean(self):
+        return RGB_MEAN if self.cfg["in_chans"] == 3 else (0.0,) * 4
+
+    def _hab_prologue(self, f: _Fwd, hb: _Hab):
+        """LayerNorm1 (unless its producer emitted it), then the ESC branch and the CAB up to what the tail reads."""
+        w, esc, bd = f.w, hb.esc, f.band
+        if bd is not None and not f.have_n:   # (LayerNorm1 is recomputed on the ghost rows from the refreshed stream)
+            yield ("halo", [(f.t, self._hab_halo(esc))])
+        if not f.have_n:
+            f.ln(f.t, w["n"], hb.n1, gap_c=esc.pdim)
+            f.nblk, f.have_n16 = ops.layernorm_blocks(), False
+        elif bd is not None:
+            # what this block reads beyond the band's own rows: t one row (depthwise 3x3 of the FFN), LayerNorm1's
+            # output three rows (the two CAB convs under it) and its first pdim channels ksize / 2 + 1 = seven rows
+            # (13x13 conv under the FFN's halo row)
+            er = esc.ksize // 2 + 1
+            yield ("halo", [(f.t, 1)] + ([(w["n"], 3), (w["n16"], er)] if f.have_n16 else [(w["n"], self._hab_halo(esc))]))
+        gst = None
+        if bd is not None:   # the ESC pool (esc_arch.py:96,121) over the whole FRAME: this band's share, then the sum
+            gst = f.gstat(esc)   # (summed over the bands together with the CAB pool: ONE reduce per HAB)
+            if f.have_n16:
+                f.pooled(w["n16"], 16, esc.pdim, gst[0])
             else:
-                lnkw = {}
-                cln = self._conv_ln_next(gi) if tout is not w["n"] else None
-                if cln is not None:
-                    nxt, gap_c = cln
-                    lnkw = dict(ln=nxt, ln_out=w["n"], ld_ln=ldc, gap_out=w["gap"], gap_c=gap_c,
-                                n16_out=(w["n16"] if self.use_n16 and gap_c else None))
-                    grp_n, grp_n16, grp_nblk = True, bool(self.use_n16 and gap_c), ops.conv_tiles(L["conv"], H, W, dt)
-                # written over the group input when both have the same type; else into the other type's buffer
-                gout = w["hA"] if in16[gi + 1] and cln is not None else tA
-                if to_conv:
-                    ops.conv(L["conv"], tout, gout, **geo, ldx=ldc, ldo=C, x_mode=X_NHWC_T, out_mode=O_NHWC_F32, r1=gin, ldr1=C, **lnkw)
-                else:
-                    ops.conv(L["conv"], tout, gout, **geo, ldx=C, ldo=C, x_mode=X_NHWC_F32, out_mode=O_NHWC_F32, r1=gin, ldr1=C, **lnkw)
-                gin = gout
-                if _EMU_T16 is not None:
-                    tA.copy_(tA.to(_EMU_T16).to(torch.float32))
-        if gin is not tA and not (grp_n and self.conv_after_body is not None):
-            raise RuntimeError("the FP16 residual stream reached a reader that takes fp32 only")   # (_stream16_plan rules it out)
-        # final LN; conv_after_body + f0 ; conv_before_upsample + LeakyReLU                :844, :854-855
-        if self.conv_after_body is None:   # nn.Identity: LN(t) + f0 in fp32, read as such by the next conv      :748
-            if bd is not None:   # the same one refresh as below: LN + f0 and the four 3x3 convs that end the network read < 4 rows
-                yield ("halo", [(tA, 8)])
-            ln(tA, tB, self.norm, out_f32=True)
-            ops.add_f32(tB, w["f0"], tB, B=B, n=N * C)
-            ops.conv(self.conv_before_up, tB, w["fb"], **geo, ldx=C, ldo=64, x_mode=X_NHWC_F32, act=ACT_LRELU)
+                f.pooled(w["n"], f.ldc, esc.pdim, gst[0])
+        if hb.fold is not None:
+            yield from self._prologue_fold(f, hb, gst)
         else:
-            if bd is not None:
-                # conv_after_body, conv_before_upsample, the Upsample convs and conv_last are five 3x3 convs, the last two at
-                # 2x / 4x resolution: their receptive field is < 4 LR rows.  ONE refresh of 8 rows here, then the band computes
-                # its ghost rows redundantly (f0 = conv_first(x) is exact there: the band's x carries the ghost rows).
-                yield ("halo", [((w["n"] if grp_n else tA), 8)])
-            if not grp_n:
-                ln(tA, w["n"], self.norm)
-            ops.conv(self.conv_after_body, w["n"], w["c2"], **geo, ldx=ldc, ldo=ldc, r1=w["f0"], ldr1=C)
-            ops.conv(self.conv_before_up, w["c2"], w["fb"], **geo, ldx=ldc, ldo=64, act=ACT_LRELU)
-        src, h, wd = w["fb"], H, W
-        for (pw, rr), dst in zip(self.ups, w["ups"]):  # conv + PixelShuffle                :593-605
-            ops.conv(pw, src, dst, B=B, H=h, W=wd, dtype=dt, ldx=64, ldo=64, out_mode=O_PIXSHUF_T, ps_r=rr)
+            yield from self._prologue_plain(f, hb, gst)
+
+    def _squeeze_chain(self, f: _Fwd, hb: _Hab):
+        """CAB squeeze conv -> c1 (+ its column sums), then hat_cab_fold (unsharded: a band folds after its reduce)."""
+        w, fo = f.w, hb.fold
+        if w["sweep"]:
+            ops.cab_squeeze(w["n"], fo["sq"][0], fo["sq"][1], w["c1"], w["colsum1"], B=f.B, H=f.H, W=f.W, C_=self.C, ldx=f.ldc, dtype=f.dt)
+        else:
+            ops.conv(hb.cab0, w["n"], w["c1"], **f.geo, ldx=f.ldc, ldo=8, act=ACT_GELU, n_store=8, colsum=w["colsum1"])
+        if f.band is None:
+            ops.cab_fold(w["c1"], w["colsum1"], w["tiles1"], hb.cab0.npad, fo["w2"], fo["b2"], hb.eca_w, hb.eca_w.numel(),
+                         fo["ba"], float(self.cfg["conv_scale"]), w["scale"], w["wf"], w["bias_b"], w["eca_tmp"], B=f.B, H=f.H,
+                         W=f.W, C_=self.C, mid=hb.cab0.nout, dtype=f.dt, w2f=fo["w2f"])
+
+    def _prologue_fold(self, f: _Fwd, hb: _Hab, gst):
+        """c2 = conv3x3(c1) never exists: its ECA pooling follows from the sums of c1 (hat_cab_fold) and the scaled expand conv
+        is three more k-steps of the aggregation GEMM (hat_aggr_cab).
+        The two tiny per-sample kernels (one workgroup each, latency-bound) run on a side stream next to the convs they do not
+        depend on: esc_weights beside the CAB squeeze conv, cab_fold beside the 13x13 conv.  The critical chain — ESC weight
+        kernel -> 13x13 conv -> tail — stays on ONE stream: every hop between streams costs an event wait of ~12 us on this
+        runtime (kernel trace: 2 hops per block = 0.9 ms per frame when the 13x13 conv sat on the side stream).  The CAB
+        squeeze conv and its fold are shorter and go to the side stream (HAT_ESC_SIDE=1: the round-2 arrangement, for A/B)."""
+        w, esc, B, H, W = f.w, hb.esc, f.B, f.H, f.W
+        n16 = w["n16"] if f.have_n16 else None
+        s0 = torch.cuda.current_stream(self.dev)
+        s1 = self._side_stream(f)
+        if f.band is not None:
+            yield from self._fold_band(f, hb, gst)
+            self._esc_w(esc, w, B, f.band.Hfull, W, 1, gap=gst[1])
+            self._esc_conv(esc, w, w["n"], B, H, W, n16=n16)
+        elif self.opt.esc_side:
+            self._esc_w(esc, w, B, H, W, f.nblk)
+            s1.wait_stream(s0)                              # n and the 13x13 weights are ready
+            with torch.cuda.stream(s1):                     # chain 2: 13x13 conv
+                self._esc_conv(esc, w, w["n"], B, H, W, n16=n16)
+            self._squeeze_chain(f, hb)
+        else:
+            s1.wait_stream(s0)                              # n is ready
+            with torch.cuda.stream(s1):
+                self._squeeze_chain(f, hb)
+            self._esc_w(esc, w, B, H, W, f.nblk)
+            self._esc_conv(esc, w, w["n"], B, H, W, n16=n16)
+        s0.wait_stream(s1)                                  # both chains are done
+
+    def _fold_band(self, f: _Fwd, hb: _Hab, gst):
+        """The band-sharded fold: the sums hat_cab_fold takes from c1 (hat_arch.py:73 via the linearity of the expand conv) are
+        this band's share of [total | first row | last row | first column | last column | 4 corners], summed over the bands."""
+        w, bd, W, fo = f.w, f.band, f.W, hb.fold
+        self._squeeze_chain(f, hb)
+        st, c1, lo, own = w["cstat_l"], w["c1"], bd.lo, bd.own
+        f.pooled(c1, 8, 8, st, 0)
+        f.pooled(c1, 8, 8, st, 24, c0=0, c1=1)
+        f.pooled(c1, 8, 8, st, 32, c0=W - 1, c1=W)
+        if bd.r0 == 0:
+            f.pooled(c1, 8, 8, st, 8, r0=lo, r1=lo + 1)
+            f.pooled(c1, 8, 8, st, 40, r0=lo, r1=lo + 1, c0=0, c1=1)
+            f.pooled(c1, 8, 8, st, 48, r0=lo, r1=lo + 1, c0=W - 1, c1=W)
+        if bd.r1 == bd.Hfull:
+            f.pooled(c1, 8, 8, st, 16, r0=lo + own - 1, r1=lo + own)
+            f.pooled(c1, 8, 8, st, 56, r0=lo + own - 1, r1=lo + own, c0=0, c1=1)
+            f.pooled(c1, 8, 8, st, 64, r0=lo + own - 1, r1=lo + own, c0=W - 1, c1=W)
+        yield ("reduce", [(gst[0], gst[1], hb.esc.pdim), (st, w["cstat_g"], 72)])
+        ops.cab_fold(None, None, 1, hb.cab0.npad, fo["w2"], fo["b2"], hb.eca_w, hb.eca_w.numel(), fo["ba"],
+                     float(self.cfg["conv_scale"]), w["scale"], w["wf"], w["bias_b"], None, B=f.B, H=bd.Hfull, W=W, C_=self.C,
+                     mid=hb.cab0.nout, dtype=f.dt, stats=w["cstat_g"], w2f=fo["w2f"])
+
+    def _prologue_plain(self, f: _Fwd, hb: _Hab, gst):
+        """CAB squeeze and expand convs (c2), the ECA scale of c2, and the ESC conv."""
+        w, esc, bd, B, H, W, C, ldc = f.w, hb.esc, f.band, f.B, f.H, f.W, self.C, f.ldc
+        mid = hb.cab0.nout
+        c3 = ops.conv3x3_small if hb.cab0.frag else ops.conv
+        c3(hb.cab0, w["n"], w["c1"], **f.geo, ldx=ldc, ldo=_r8(mid), act=ACT_GELU, n_store=_r4(mid))
+        c3 = ops.conv3x3_small if hb.cab2.frag else ops.conv
+        c3(hb.cab2, w["c1"], w["c2"], **f.geo, ldx=_r8(mid), ldo=ldc, colsum=w["colsum"])
+        if bd is None:
+            ops.eca_scale(w["colsum"], w["tiles"], hb.cab2.npad, f.N, hb.eca_w, hb.eca_w.numel(),
+                          float(self.cfg["conv_scale"]), w["eca_tmp"], w["scale"], B=B, C_=C)
+            self._esc_lk(esc, w, w["n"], B, H, W, f.nblk)
+            return
+        # ECA pool of c2 (hat_arch.py:73) over the whole frame: this band's rows, then the sum over the bands (rows of npad
+        # floats, like the per-tile column sums: hat_eca_scale writes `scale` with that stride and the aggregation reads it so)
+        npd = hb.cab2.npad
+        el, eg = (w[k].view(-1)[:B * npd].view(B, npd) for k in ("estat_l", "estat_g"))
+        f.pooled(w["c2"], ldc, C, el)
+        yield ("reduce", [(gst[0], gst[1], esc.pdim), (el, eg, _r4(C))])
+        ops.eca_scale(eg, 1, npd, bd.Hfull * W, hb.eca_w, hb.eca_w.numel(), float(self.cfg["conv_scale"]), w["eca_tmp"],
+                      w["scale"], B=B, C_=C)
+        self._esc_w(esc, w, B, bd.Hfull, W, 1, gap=gst[1])
+        self._esc_conv(esc, w, w["n"], B, H, W)
+
+    def _tail_fused144(self, f: _Fwd, hb: _Hab):
+        """Aggregation + folded CAB + residuals + the whole FFN in ONE launch: tB never exists in HBM (also the faster choice on
+        small frames: 64x64 HAT-S 3.97 vs 6.19 ms per forward)."""
+        w, t = f.w, f.t
+        if hb.out16:
+            tout = w["hB"] if t is not w["hB"] else w["hC"]
+        else:
+            tout = w["tB"] if t is not w["tB"] else w["tC"]
+        nxt, gap_c = hb.next_ln
+        ops.hab_tail(hb.ffn3 if hb.ffn3 is not None else hb.ffn, hb.esc.aggr, t, tout, hb.n2[0], hb.n2[1], n=w["n"], ldn_in=f.ldc,
+                     y16=w["y16"], c1=w["c1"], wf=w["wf"], bias_b=w["bias_b"], B=f.B, H=f.H, W=f.W, dtype=f.dt, ln1=nxt,
+                     n_out=w["n2b"], ldn=f.ldc, gap_out=w["gap"], gap_c=gap_c, n16_out=(w["n16"] if self.use_n16 else None))
+        w["n"], w["n2b"] = w["n2b"], w["n"]      # the kernel reads n with a halo: its output n' is another buffer
+        if self.opt.emu_t16 is not None:   # measurement only (tools/residual16_psnr.py): what a 16-bit residual stream would cost
+            tout.copy_(tout.to(self.opt.emu_t16).to(torch.float32))
+        f.t, f.have_n, f.have_n16, f.nblk = tout, True, self.use_n16, ops.ffn_tiles(hb.ffn, f.H, f.W, f.dt)
+
+    def _tail_fused180(self, f: _Fwd, hb: _Hab):
+        """embed_dim 180: aggregation + scaled c2 + residuals + the whole FFN in one launch (hat_hab_tail3)."""
+        w, t = f.w, f.t
+        tout = w["tB"] if t is not w["tB"] else w["tC"]
+        nxt, gap_c = hb.next_ln
+        ops.hab_tail(hb.ffn3, hb.esc.aggr, t, tout, hb.n2[0], hb.n2[1], n=w["n"], ldn_in=f.ldc, y16=w["y16"], bias_b=hb.bias256,
+                     B=f.B, H=f.H, W=f.W, dtype=f.dt, ln1=nxt, n_out=w["n2b"], ldn=f.ldc, gap_out=w["gap"], gap_c=gap_c,
+                     n16_out=(w["n16"] if self.use_n16 else None), r2=w["c2"], ldr2=f.ldc, r2scale=w["scale"],
+                     r2scale_bstride=hb.cab2.npad)
+        w["n"], w["n2b"] = w["n2b"], w["n"]
+        f.t, f.have_n, f.have_n16, f.nblk = tout, True, self.use_n16, -(-f.H // 8) * -(-f.W // 16)
+
+    def _tail_aggr_cab(self, f: _Fwd, hb: _Hab):
+        """tB = t + aggr(cat(y16, n[pdim:])) + the folded CAB (hat_aggr_cab), then the FFN."""
+        w = f.w
+        ops.aggr_cab(hb.esc.aggr, w["n"], w["tB"], w["c1"], w["wf"], w["bias_b"], **f.geo, ldx=f.ldc, ldo=self.C, x0=w["y16"],
+                     c_split=hb.esc.pdim, ldx0=w["y16"].shape[2], r1=f.t, ldr1=self.C)
+        self._ffn(f, hb)
+
+    def _tail_aggr(self, f: _Fwd, hb: _Hab):
+        """tB = t + aggr(cat(y16, n[pdim:])) + conv_scale * eca * c2 (hat_linear), then the FFN                  :236"""
+        w = f.w
+        self._run_lin(hb.esc.aggr, w["n"], w["tB"], **f.geo, ldx=f.ldc, ldo=self.C, out_mode=O_NHWC_F32, x0=w["y16"],
+                      c_split=hb.esc.pdim, ldx0=w["y16"].shape[2], r1=f.t, ldr1=self.C, r2=w["c2"], ldr2=f.ldc,
+                      r2scale=w["scale"], r2scale_bstride=hb.cab2.npad)
+        self._ffn(f, hb)
+
+    def _ffn(self, f: _Fwd, hb: _Hab):
+        """The FFN on tB: fused LN2 + fc1 + dw3x3 + gate + fc2 + residual (+ the next block's LayerNorm) -> tC, or the
+        unfused LN2, fc1, gate (HATX: SGFN), fc2 in place on tB."""
+        w, C, ldc = f.w, self.C, f.ldc
+        tB, tC = w["tB"], w["tC"]
+        if hb.ffn is not None:
+            nxt, gap_c = hb.next_ln
+            if gap_c > 16:   # (the fused kernels pool at most 16 channels: a wider ESC gets its LayerNorm + pool from hat_layernorm)
+                ops.ffn(hb.ffn, tB, tC, hb.n2[0], hb.n2[1], B=f.B, H=f.H, W=f.W, dtype=f.dt)
+                f.t, f.have_n, f.have_n16 = tC, False, False
+            else:
+                ops.ffn(hb.ffn, tB, tC, hb.n2[0], hb.n2[1], B=f.B, H=f.H, W=f.W, dtype=f.dt, ln1=nxt, n_out=w["n"], ldn=ldc,
+                        gap_out=w["gap"], gap_c=gap_c)
+                # (hat_ffn / hat_ffn2 emit the LayerNorm rows only: w["n16"] still holds an OLDER block's compact copy —
+                # the group conv's or a fused tail's — and must not be handed to the next 13x13 conv)
+                f.t, f.have_n, f.have_n16, f.nblk = tC, True, False, ops.ffn_tiles(hb.ffn, f.H, f.W, f.dt)
+            return
+        f.ln(tB, w["n"], hb.n2)
+        hid2 = hb.fc1.nout
+        self._run_lin(hb.fc1, w["n"], w["u"], **f.geo, ldx=ldc, ldo=w["u"].shape[2])
+        if self.hatx:   # SGFN: [dw(a) * silu(b) | b], hid2 channels in and out            hatx_arch.py:165-177
+            ops.sgfn_gate(w["u"], hb.dw_w, hb.dw_b, w["g"], B=f.B, H=f.H, W=f.W, half=hid2 // 2, ldu=w["u"].shape[2],
+                          ldo=w["g"].shape[2], dtype=f.dt)
+        else:
+            ops.dwconv_gate(w["u"], hb.dw_w, hb.dw_b, w["g"], B=f.B, H=f.H, W=f.W, hid=hid2 // 2, ldu=w["u"].shape[2],
+                            ldo=w["g"].shape[2], dtype=f.dt)
+        self._run_lin(hb.fc2, w["g"], tB, **f.geo, ldx=w["g"].shape[2], ldo=C, out_mode=O_NHWC_F32, r1=tB, ldr1=C)
+        f.t, f.have_n, f.have_n16 = tB, False, False
+
+    def _ocab(self, f: _Fwd, G: _Group, as_conv_input):
+        """OCAB of residual group G on the residual stream f.t -> the buffer holding the result   hat_arch.py:326-393
+        as_conv_input: the only consumer is the group's 3x3 conv, which reads its input as T (bf16) rows anyway: the last
+        linear then stores its fp32 result (+ residual) as T rows into w["ao"] and the fp32 stream is not written at all
+        (same values as the conv's own staging conversion; 650 B/px less traffic per group)."""
+        w, oc, esc, bd, t, C, ldc, geo = f.w, G.ocab, G.ocab.esc, f.band, f.t, self.C, f.ldc, f.geo
+        nblk = f.nblk
+        if bd is not None:   # key / value windows reach (wse - ws) / 2 rows into the neighbours' bands             :359-360
+            # (+ the ESC conv under them with OCAB-ESC).  HATX's focus bias and top-k need nothing more: the saliency head is
+            # 1x1 and keys are ranked per window.  A window with owned query rows has its whole key window inside the buffer
+            # (ghost 16 >= pad), and the first / last band have the frame edge at their buffer edge, so the padded keys and
+            # the lowest-index tie rule are the frame's.
+            yield ("halo", [((w["n"] if f.have_n else t), self._ocab_halo(oc))])
+        if not f.have_n:
+            f.ln(t, w["n"], oc.n1, gap_c=(esc.pdim if esc else 0))
+            nblk = ops.layernorm_blocks()
+        kv_src = w["n"]
+        if esc is not None:  # K/V from ESC(LN(x))                                     :336-344
+            if bd is not None:   # the ESC pool over the whole FRAME: this band's rows, then ONE more reduce per group
+                gl, gg = f.gstat(esc)
+                f.pooled(w["n"], ldc, esc.pdim, gl)
+                yield ("reduce", [(gl, gg, esc.pdim)])
+                self._esc_w(esc, w, f.B, bd.Hfull, f.W, 1, gap=gg)
+                self._esc_conv(esc, w, w["n"], f.B, f.H, f.W)
+            else:
+                self._esc_lk(esc, w, w["n"], f.B, f.H, f.W, nblk)
+            self._run_lin(esc.aggr, w["n"], w["yesc"], **geo, ldx=ldc, ldo=ldc, x0=w["y16"], c_split=esc.pdim, ldx0=w["y16"].shape[2])
+            kv_src = w["yesc"]
+        if oc.qkvf is not None:
+            ops.ocab_qkv(oc.qkvf, w["n"], w["qkv"], **geo, ldx=ldc, ldo=432)
+            qbuf, kvbuf, ldq, ldkv = w["qkv"], w["qkv"].view(-1)[144:], 432, 432
+        else:
+            qbuf, kvbuf, ldq, ldkv = w["q"], w["kv"], ldc, w["kv"].shape[2]
+            s0 = torch.cuda.current_stream(self.dev)   # q and kv projections are independent
+            s1 = self._side_stream(f)
+            s1.wait_stream(s0)
+            with torch.cuda.stream(s1):
+                self._run_lin(oc.q, w["n"], w["q"], **geo, ldx=ldc, ldo=ldc)
+            self._run_lin(oc.kv, kv_src, w["kv"], **geo, ldx=ldc, ldo=w["kv"].shape[2])
+            s0.wait_stream(s1)
+        self._ocab_attention(f, G, kv_src, qbuf, kvbuf, ldq, ldkv)
+        tout = w["tB"] if t is w["tA"] else t  # never write the RHAG input buffer (an FP16 t is hB / hC: proj and MLP take it in place)
+        if oc.proj.frag:  # norm2 (:306) rides on the projection's epilogue
+            self._run_lin(oc.proj, w["ao"], tout, **geo, ldx=ldc, ldo=C, out_mode=O_NHWC_F32, r1=t, ldr1=C,
+                          ln=oc.n2, ln_out=w["n"], ld_ln=ldc)
+        else:
+            self._run_lin(oc.proj, w["ao"], tout, **geo, ldx=ldc, ldo=C, out_mode=O_NHWC_F32, r1=t, ldr1=C)
+            f.ln(tout, w["n"], oc.n2)
+        if oc.mlpf is not None:   # fc1 + GELU + fc2 + residual fused: the hidden tensor never reaches HBM
+            dst = w["ao"] if as_conv_input else tout
+            ops.ocab_mlp(oc.mlpf, w["n"], tout, dst, B=f.B, H=f.H, W=f.W, ldx=ldc, ldr1=C, ldo=(ldc if as_conv_input else C),
+                         out_f32=not as_conv_input, dtype=f.dt)
+            return dst
+        self._run_lin(oc.mlp0, w["n"], w["g"], **geo, ldx=ldc, ldo=w["g"].shape[2], act=ACT_GELU)
+        if as_conv_input:
+            self._run_lin(oc.mlp2, w["g"], w["ao"], **geo, ldx=w["g"].shape[2], ldo=ldc, out_mode=O_NHWC_T, r1=tout, ldr1=C)
+            return w["ao"]
+        self._run_lin(oc.mlp2, w["g"], tout, **geo, ldx=w["g"].shape[2], ldo=C, out_mode=O_NHWC_F32, r1=tout, ldr1=C)
+        return tout
+
+    def _ocab_attention(self, f: _Fwd, G: _Group, kv_src, qbuf, kvbuf, ldq, ldkv):
+        """Overlapping cross-attention -> w["ao"]; HATX: focus bias on the logits and / or top-k key pruning   hatx_arch.py:421-449"""
+        w, oc, C, ldc, ws, wse = f.w, G.ocab, self.C, f.ldc, self.ws, self.wse
+        if not (self.focus or self.topk < 1.0):
+            ops.ocab_attention(qbuf, kvbuf, oc.bias_rot, w["ao"], B=f.B, H=f.H, W=f.W, C_=C, heads=G.heads, ws=ws, wse=wse,
+                               ldq=ldq, ldkv=ldkv, ldo=ldc, dtype=f.dt, q_log2=oc.qlog2)
+            return
+        nk, pad = wse * wse, (wse - ws + 1) // 2
+        if self.focus:
+            ops.conv(oc.fh0, kv_src, w["fh"], **f.geo, ldx=ldc, ldo=w["fh"].shape[2], act=ACT_GELU, n_store=_r4(C // 4))
+            ops.conv(oc.fh2, w["fh"], w["sal"], **f.geo, ldx=w["fh"].shape[2], ldo=8, n_store=4, out_mode=O_NHWC_F32)
+        k_keep = max(1, int(self.topk * nk)) if self.topk < 1.0 else nk
+        ops.ocab_keybias(w["sal"] if self.focus else None, kvbuf, w["kb"], B=f.B, H=f.H, W=f.W, C_=C, ws=ws, wse=wse, pad=pad,
+                         k_keep=k_keep, ldsal=(-8 if f.dt == ops.HAT_BF16 else 8), ldkv=ldkv, dtype=f.dt)
+        ops.ocab_attention_kb(qbuf, kvbuf, oc.bias_rot, w["kb"], w["ao"], B=f.B, H=f.H, W=f.W, C_=C, heads=G.heads, ws=ws,
+                              wse=wse, pad=pad, ldq=ldq, ldkv=ldkv, ldo=ldc, dtype=f.dt)
+
+    def _group_end(self, f: _Fwd, G: _Group, tout):
+        """RHAG tail: conv3x3 + group residual, written over the group input (or the identity add)           :545-546, :556"""
+        w, tA, C = f.w, f.w["tA"], self.C
+        if f.band is not None and G.conv is not None:   # the group's 3x3 conv reads one row beyond the band's own
+            yield ("halo", [(tout, 1)])
+        if G.conv is None:  # resi_connection == 'identity': group(x) + x
+            ops.add_f32(tout, tA, tA, B=f.B, n=f.N * C)
+            f.t = f.gin = tA
+            f.have_n = f.have_n16 = False
+            return
+        # the epilogue emits the LayerNorm its consumer starts with (the next group's first norm1, or HAT.norm): w["n"] (and
+        # w["n16"]) are then already valid when the next step starts
+        lnkw = {}
+        if G.conv_ln is not None:
+            nxt, gap_c = G.conv_ln
+            lnkw = dict(ln=nxt, ln_out=w["n"], ld_ln=f.ldc, gap_out=w["gap"], gap_c=gap_c, n16_out=(w["n16"] if self.use_n16 and gap_c else None))
+            f.nblk = ops.conv_tiles(G.conv, f.H, f.W, f.dt)
+        f.have_n = G.conv_ln is not None
+        f.have_n16 = bool(f.have_n and self.use_n16 and G.conv_ln[1])
+        gout = w["hA"] if G.out16 else tA   # written over the group input when both have the same type, else into hA
+        if G.to_conv:
+            ops.conv(G.conv, tout, gout, **f.geo, ldx=f.ldc, ldo=C, x_mode=X_NHWC_T, out_mode=O_NHWC_F32, r1=f.gin, ldr1=C, **lnkw)
+        else:
+            ops.conv(G.conv, tout, gout, **f.geo, ldx=C, ldo=C, x_mode=X_NHWC_F32, out_mode=O_NHWC_F32, r1=f.gin, ldr1=C, **lnkw)
+        f.t = f.gin = gout
+        if self.opt.emu_t16 is not None:
+            tA.copy_(tA.to(self.opt.emu_t16).to(torch.float32))
+
+    def _body_end(self, f: _Fwd):
+        """final LN; conv_after_body + f0 ; conv_before_upsample + LeakyReLU               :844, :854-855"""
+        w, tA, C, ldc = f.w, f.w["tA"], self.C, f.ldc
+        if f.gin is not tA and not (f.have_n and self.conv_after_body is not None):
+            raise RuntimeError("the FP16 residual stream reached a reader that takes fp32 only")   # (_resolve_stream16 rules it out)
+        if self.conv_after_body is None:   # nn.Identity: LN(t) + f0 in fp32, read as such by the next conv      :748
+            if f.band is not None:   # the same one refresh as below: LN + f0 and the four 3x3 convs that end the network read < 4 rows
+                yield ("halo", [(tA, 8)])
+            f.ln(tA, w["tB"], self.norm, out_f32=True)
+            ops.add_f32(w["tB"], w["f0"], w["tB"], B=f.B, n=f.N * C)
+            ops.conv(self.conv_before_up, w["tB"], w["fb"], **f.geo, ldx=C, ldo=64, x_mode=X_NHWC_F32, act=ACT_LRELU)
+            return
+        if f.band is not None:
+            # conv_after_body, conv_before_upsample, the Upsample convs and conv_last are five 3x3 convs, the last two at
+            # 2x / 4x resolution: their receptive field is < 4 LR rows.  ONE refresh of 8 rows here, then the band computes
+            # its ghost rows redundantly (f0 = conv_first(x) is exact there: the band's x carries the ghost rows).
+            yield ("halo", [((w["n"] if f.have_n else tA), 8)])
+        if not f.have_n:
+            f.ln(tA, w["n"], self.norm)
+        ops.conv(self.conv_after_body, w["n"], w["c2"], **f.geo, ldx=ldc, ldo=ldc, r1=w["f0"], ldr1=C)
+        ops.conv(self.conv_before_up, w["c2"], w["fb"], **f.geo, ldx=ldc, ldo=64, act=ACT_LRELU)
+
+    def _upsample(self, f: _Fwd, y):
+        """conv + PixelShuffle per stage; conv_last ; / img_range + mean                     :593-605, :856-858"""
+        src, h, wd, dt = f.w["fb"], f.H, f.W, f.dt
+        for (pw, rr), dst in zip(self.ups, f.w["ups"]):
+            ops.conv(pw, src, dst, B=f.B, H=h, W=wd, dtype=dt, ldx=64, ldo=64, out_mode=O_PIXSHUF_T, ps_r=rr)
             src, h, wd = dst, h * rr, wd * rr
-        # conv_last ; / img_range + mean                                                   :856-858
+        r = float(self.cfg.get("img_range", 1.0))
         if self.conv_last_sweep is not None and wd % 16 == 0:
             wpk, b8, nout = self.conv_last_sweep
-            ops.conv3x3_to_planes(src, wpk, b8, y, B=B, H=h, W=wd, C_=64, ldx=64, n_out=nout, out_scale=1.0 / r, mean=mean, dtype=dt)
+            ops.conv3x3_to_planes(src, wpk, b8, y, B=f.B, H=h, W=wd, C_=64, ldx=64, n_out=nout, out_scale=1.0 / r, mean=self._mean(),
+                                  dtype=dt)
         else:
-            ops.conv(self.conv_last, src, y, B=B, H=h, W=wd, dtype=dt, ldx=64, ldo=0, out_mode=O_NCHW_F32,
-                     out_scale=1.0 / r, mean=mean)
-        return y
+            ops.conv(self.conv_last, src, y, B=f.B, H=h, W=wd, dtype=dt, ldx=64, ldo=0, out_mode=O_NCHW_F32,
+                     out_scale=1.0 / r, mean=self._mean())

@@ -21,7 +21,6 @@ from __future__ import annotations
 import argparse
 import bisect
 import ctypes as C
-import os
 import struct
 import threading
 from typing import List, Tuple
@@ -110,21 +109,14 @@ def export_plan(net, x_shape: Tuple[int, int, int, int], path: str) -> dict:
     x = torch.zeros(x_shape, dtype=torch.float32, device=dev)
     real = _lib.load()
     rec = _Recorder(real)
-    prev_one = os.environ.get("HAT_ONE_STREAM")
-    os.environ["HAT_ONE_STREAM"] = "1"          # the plan replays on one stream: record the launches in that order
-    _EXPORT_LOCK.acquire()                     # one export at a time: the recorder stands in for the process-wide library handle
-    _lib._lib = rec
-    try:
-        with torch.no_grad():
-            y = eng.forward(x)
-        torch.cuda.synchronize(dev)
-    finally:
-        _lib._lib = real
-        _EXPORT_LOCK.release()
-        if prev_one is None:
-            os.environ.pop("HAT_ONE_STREAM", None)
-        else:
-            os.environ["HAT_ONE_STREAM"] = prev_one
+    with _EXPORT_LOCK:                         # one export at a time: the recorder stands in for the process-wide library handle
+        _lib._lib = rec
+        try:
+            with torch.no_grad():
+                y = eng.forward(x, one_stream=True)   # the plan replays on one stream: record the launches in that order
+            torch.cuda.synchronize(dev)
+        finally:
+            _lib._lib = real
     ws = eng._workspace(B, H, W)
     consts, scratch = [], []
     _tensors_of({k: v for k, v in eng.__dict__.items() if k != "_ws_cache"}, set(), consts)

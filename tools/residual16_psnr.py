@@ -1,7 +1,7 @@
 """What would a 16-bit residual stream cost in parity?  Runs the 720p headline frame three times in separate processes' worth of
 engines (HAT_EMU_T16 unset / fp16 / bf16: the engine then rounds the fp32 residual stream after every HAB tail and group conv)
 and reports PSNR and max-abs against the REFERENCE's crops (tests/golden/big_headline_HAT-S_x4_720p.npz).
-    PYTHONPATH=. python tools/residual16_psnr.py <mode>      (mode: none | fp16 | bf16; one mode per process: the flag is read at import)"""
+    PYTHONPATH=. python tools/residual16_psnr.py <mode>      (mode: none | fp16 | bf16; the engine reads the flag when it is built)"""
 import os, sys
 mode = sys.argv[1] if len(sys.argv) > 1 else "none"
 if mode != "none":
