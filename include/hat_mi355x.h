@@ -356,6 +356,35 @@ int hat_conv3x3_to_planes(const void* x, const void* wpk, const float* bias, flo
                           void* stream);
 
 /*
+ * The 8-bit frame boundary: interleaved uint8 frames in, interleaved uint8 frames out, with the reference's conversions
+ * (basicsr utils/img_util.py:9-35, :131 in; hat/models/hat_model.py:16-26 pad, :110-112 crop; img_util.py:66-91 out).
+ *
+ * hat_u8_to_planes   src: (B,h,w,3) uint8, rows src_pitch bytes apart (>= 3 w), samples src_bstride bytes apart (ignored for
+ *                    B == 1) -> dst: (B,3,Hp,Wp) fp32 planes, dst[b][c][y][x] = float(src[b][y'][x'][bgr ? 2 - c : c]) / 255.0f
+ *                    exactly (a 256-entry table of correctly rounded quotients), y' = y for y < h else 2 (h - 1) - y and
+ *                    likewise x': rows and columns past the frame are its reflection without the edge (F.pad 'reflect'
+ *                    on the bottom and the right).  Hp >= h, Wp >= w; Hp - h >= h or Wp - w >= w (no row / column to
+ *                    reflect) is HAT_EINVAL.
+ * hat_planes_to_u8   src: (B,3,Hs,Ws) fp32 planes -> dst: (B,h_out,w_out,3) uint8 with dst_pitch >= 3 w_out bytes per row
+ *                    and dst_bstride bytes per sample: the top-left h_out x w_out pixels (h_out <= Hs, w_out <= Ws),
+ *                    each value clamped to [0, 1], multiplied by 255 in fp32, rounded half to even; plane c goes to
+ *                    byte (bgr ? 2 - c : c) of its pixel.  The general output path: any width, any engine dtype.
+ * hat_conv3x3_to_u8  conv_last with that conversion as its epilogue: hat_conv3x3_to_planes' kernel, arguments and fp32
+ *                    value (conv3x3(x, 64 -> 3) + bias) * out_scale + mean[ch], stored as hat_planes_to_u8 stores it
+ *                    (rows >= h_out and columns >= w_out are skipped; h_out <= H, w_out <= W), so the fp32 image is never
+ *                    written.  Bit-identical to hat_planes_to_u8 of hat_conv3x3_to_planes.  x: (B,H,W,ldx) bf16,
+ *                    W % 16 == 0, C == 64, wpk / bias packed for n_out = 3; dtype must be HAT_BF16.
+ * All three check their arguments before they touch the device; none allocates or synchronises.
+ */
+int hat_u8_to_planes(const uint8_t* src, int64_t src_pitch, int64_t src_bstride, float* dst, int32_t B, int32_t h, int32_t w,
+                     int32_t Hp, int32_t Wp, int32_t bgr, void* stream);
+int hat_planes_to_u8(const float* src, int32_t B, int32_t Hs, int32_t Ws, uint8_t* dst, int64_t dst_pitch, int64_t dst_bstride,
+                     int32_t h_out, int32_t w_out, int32_t bgr, void* stream);
+int hat_conv3x3_to_u8(const void* x, const void* wpk, const float* bias, uint8_t* dst, int64_t dst_pitch, int64_t dst_bstride,
+                      int32_t B, int32_t H, int32_t W, int32_t C, int32_t ldx, int32_t h_out, int32_t w_out, float out_scale,
+                      const float* mean4, int32_t bgr, int32_t dtype, void* stream);
+
+/*
  * (Shifted-)window self-attention, (S)W-MSA — SURVEY §8 row f2.  Replaces, for one attention branch of a Swin / upstream-HAT
  * block, ESC/basicsr/archs/swinir_arch.py:291-317 (torch.roll by -shift, window_partition, WindowAttention core :147-168
  * with the relative-position bias :153-156 and the shift mask of calculate_mask :262-280, window_reverse, torch.roll by
@@ -498,12 +527,26 @@ int hat_hab_tail3(const HatHabTailDesc* d, void* stream);
  *                     are bit-identical to the Python engine's for the same weights.  Not re-entrant per plan (the
  *                     workspace is the plan's): one forward at a time.
  *   hat_plan_free     releases everything.
+ *   hat_plan_forward_u8  the same forward from and to 8-bit frames, for a plan with Cin = Cout = 3.  src: (B,h,w,3) uint8
+ *                     device memory, rows src_pitch bytes apart, samples h * src_pitch apart; any h <= H, w <= W with
+ *                     H - h < h and W - w < w: the frame is reflect-padded to the plan's (H, W) by hat_u8_to_planes.
+ *                     dst: (B, scale*h, scale*w, 3) uint8 device memory, rows dst_pitch bytes apart, samples
+ *                     scale*h * dst_pitch apart.  flags bit 0: the bytes of a pixel are B, G, R on both sides.  The
+ *                     plan keeps an fp32 input staging buffer (B*3*H*W floats) and, unless its last launch is
+ *                     hat_conv3x3_to_planes into the output (then hat_conv3x3_to_u8 is issued with the recorded
+ *                     arguments and no fp32 image exists), an fp32 output one: the FIRST u8 call allocates them
+ *                     (hipMalloc: it synchronises the device once); later calls allocate nothing.  Results are
+ *                     bit-identical to HAT.forward_u8 on a frame that pads to (H, W).  hat_plan_forward is unaffected.
+ *                     Returns 0, a negative HAT_E* for a refused argument, or — as hat_plan_load does — the positive
+ *                     hipError_t of a failed hipMalloc / launch.
  */
 typedef struct hat_plan hat_plan;
 int hat_plan_load(const char* path, hat_plan** out);
 int hat_plan_info(const hat_plan* plan, int32_t* dims8, int64_t* n_calls, int64_t* device_bytes);
 int hat_plan_forward(const hat_plan* plan, const float* x, float* y, void* stream);
 void hat_plan_free(hat_plan* plan);
+int hat_plan_forward_u8(const hat_plan* plan, const uint8_t* src, int64_t src_pitch, int32_t h, int32_t w, uint8_t* dst,
+                        int64_t dst_pitch, int32_t flags, void* stream);
 
 /*
  * Per-channel sums of a channel-last map over the pixel rectangle rows [r0, r1) x columns [c0, c1):

@@ -344,6 +344,40 @@ class HAT(nn.Module):
                 return self._forward_graph(x)
             return self.engine(x.device).forward(x).to(x.dtype)
 
+    # ---- the 8-bit frame boundary (no counterpart in the reference's module: its caller converts on the host,
+    # basicsr utils/img_util.py:9-35, :66-91, :131 and hat/models/hat_model.py:16-26, :110-112) ----
+    def _check_u8_input(self, t):
+        if self.training:
+            raise RuntimeError("this HAT implements the inference forward pass only: call .eval() first")
+        if not t.is_cuda:
+            raise RuntimeError("HAT.forward needs a GPU tensor: the MI355X HIP path is the only path (no CPU fallback)")
+        if self.cfg["in_chans"] != 3:
+            raise RuntimeError(f"8-bit frames are three-channel images: in_chans={self.cfg['in_chans']} has no uint8 path")
+
+    def forward_to_u8(self, x, *, bgr: bool = False, out=None):
+        """`forward(x)` handed over as an 8-bit image: (B,3,H,W) float in [0,1], H and W window multiples as for `forward`
+        -> (B,sH,sW,3) uint8 on the device, equal to the reference's `tensor2img` of `forward(x)` (clamp to [0,1], x255 in
+        fp32, round half to even, CHW -> HWC; bgr=True: B,G,R byte order).  On the bf16 path conv_last converts in its
+        epilogue and the fp32 image is never written.  out: a (B,sH,sW,3) uint8 device tensor to fill instead of a fresh one.
+        Runs eagerly also with use_graph=True (the 8-bit path is not captured)."""
+        self._check_u8_input(x)
+        with torch.no_grad():
+            return self.engine(x.device).forward_to_u8(x, bgr=bgr, out=out)
+
+    def forward_u8(self, frame, *, bgr: bool = False, out=None):
+        """8-bit frames in, 8-bit frames out, all on the device: `frame` is an (h,w,3) or (B,h,w,3) uint8 device tensor of ANY
+        size whose reflect-padding to the next window multiple is defined (padding smaller than the frame); returns
+        (B,s*h,s*w,3) uint8.  Equal to the reference's pipeline float32(u8)/255 -> HATModel.pre_process (reflect-pad bottom /
+        right) -> forward -> post_process (crop) -> tensor2img, bit for bit against this build's `forward`.  bgr=True: the
+        bytes are B,G,R on both sides (OpenCV's order); out: a (B,s*h,s*w,3) uint8 device tensor to fill instead of a fresh
+        one (with it the call allocates nothing where conv_last converts in its epilogue).  The padded fp32 input lives in the engine's per-shape workspace.
+        Runs eagerly also with use_graph=True (the 8-bit path is not captured)."""
+        self._check_u8_input(frame)
+        if frame.dim() == 3:
+            frame = frame.unsqueeze(0)
+        with torch.no_grad():
+            return self.engine(frame.device).forward_u8(frame, bgr=bgr, out=out)
+
     # ---- exact full-frame sharding into row bands (SURVEY §8 f4; no counterpart in the reference, whose tile loop
     # hat_model.py:40-108 gives a DIFFERENT result than the full frame: SURVEY F6) ----
     def _check_band_input(self, x):

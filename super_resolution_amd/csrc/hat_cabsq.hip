@@ -23,13 +23,18 @@ namespace {
 
 // KS = k-steps (C padded to 32 KS).  NCHW = false: bias + GELU -> (B,H,W,8) bf16 + per-unit channel sums (CAB squeeze);
 // NCHW = true: (acc + bias) * out_scale + mean[ch] -> (B,nst,H,W) fp32 planes (conv_last, hat_arch.py:856-858).
+// Epi = SweepEpiU8 (with NCHW): that same fp32 value, by the same expression, converted as tensor2img converts it and
+// stored as interleaved bytes (B,h_out,w_out,3) with a row pitch; rows and columns outside the crop are not stored.
 struct SweepEpi { float out_scale; float mean[4]; int nst; };
+struct SweepEpiU8 { float out_scale; float mean[4]; int h_out, w_out, bgr; long long pitch, bstride; };
 
-template <int KS, bool NCHW>
+template <int KS, bool NCHW, typename Epi = SweepEpi>
 __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wpk,
                                                              const float* __restrict__ bias, void* __restrict__ outv,
                                                              float* __restrict__ colsum, int H, int W, int C, int ldx,
-                                                             int rows, int strips, int units, SweepEpi epi) {
+                                                             int rows, int strips, int units, Epi epi) {
+    constexpr bool U8 = std::is_same<Epi, SweepEpiU8>::value;
+    static_assert(!U8 || NCHW, "the byte epilogue converts the conv_last value");
     using M = MT<bf16_t>;
     using frag_t = M::frag_t;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, c16 = lane & 15;
@@ -40,7 +45,10 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
     const int x0 = strip * 14 - 1, y0 = band * rows, y1 = min(y0 + rows, H);   // x0: the pixel column of lane c16 = 0 (a halo column)
     const bf16_t* xb = x + (size_t)b * H * W * ldx;
     bf16_t* ob = reinterpret_cast<bf16_t*>(outv) + (size_t)b * H * W * 8;
-    float* of = reinterpret_cast<float*>(outv) + (size_t)b * epi.nst * H * W;
+    float* of = nullptr;
+    uint8_t* o8 = nullptr;
+    if constexpr (U8) o8 = reinterpret_cast<uint8_t*>(outv) + (size_t)b * epi.bstride;
+    else of = reinterpret_cast<float*>(outv) + (size_t)b * epi.nst * H * W;
 
     frag_t A[6][KS];   // [2 * kx + (0: T1, 1: T2)][k-step], fragment-packed on the host: one coalesced 1 KB load each
 #pragma unroll
@@ -111,7 +119,15 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
         for (int i = 0; i < 4; ++i) v[i] = S2[i] + __shfl_xor(S0[i], 32);
         if (y >= y0 && y < y1 && g < 2 && oin) {
             v += bs;
-            if constexpr (NCHW) {
+            if constexpr (U8) {
+                // lane group g = 0 holds R, G, B of pixel (y, xx): a strip row is 42 bytes from byte 42 strip of the image
+                // row, so three byte stores per lane, each instruction covering the strip's 42-byte span (DESIGN: frame path)
+                if (g == 0 && y < epi.h_out && xx < epi.w_out) {
+                    uint8_t* p = o8 + (size_t)y * epi.pitch + (size_t)xx * 3;
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) p[epi.bgr ? 2 - i : i] = (uint8_t)hat_unit_to_u8(v[i] * epi.out_scale + epi.mean[i]);
+                }
+            } else if constexpr (NCHW) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     if (4 * g + i < epi.nst) of[((size_t)(4 * g + i) * H + y) * W + xx] = v[i] * epi.out_scale + epi.mean[(4 * g + i) & 3];
@@ -196,5 +212,23 @@ extern "C" int hat_conv3x3_to_planes(const void* x, const void* wpk, const float
     HAT_LAUNCH((cab_squeeze_kernel<2, true>), dim3((units + 3) / 4, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(wpk), bias, out, nullptr, H, W, C, ldx, rows,
                (W + 13) / 14, units, SweepEpi{out_scale, {mean4[0], mean4[1], mean4[2], mean4[3]}, n_out});
+    return hat_check_launch();
+}
+
+extern "C" int hat_conv3x3_to_u8(const void* x, const void* wpk, const float* bias, uint8_t* dst, int64_t dst_pitch, int64_t dst_bstride,
+                                 int32_t B, int32_t H, int32_t W, int32_t C, int32_t ldx, int32_t h_out, int32_t w_out, float out_scale,
+                                 const float* mean4, int32_t bgr, int32_t dtype, void* stream) {
+    if (!x || !wpk || !bias || !dst || !mean4 || B < 1 || H < 1 || W < 16 || W % 16 || h_out < 1 || w_out < 1 || h_out > H || w_out > W)
+        return HAT_EINVAL;
+    if (dst_pitch < 3 * (int64_t)w_out || (B > 1 && dst_bstride < dst_pitch * (int64_t)(h_out - 1) + 3 * (int64_t)w_out)) return HAT_EINVAL;
+    if (dtype != HAT_BF16) return HAT_EUNSUPPORTED;
+    if (C != 64 || ldx < C || ldx % 8) return HAT_EUNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpk)) % 16) return HAT_EINVAL;
+    int rows = 0, units = 0;
+    sweep_units(H, W, 3072, &rows, &units);                 // the launch geometry of hat_conv3x3_to_planes
+    HAT_LAUNCH((cab_squeeze_kernel<2, true, SweepEpiU8>), dim3((units + 3) / 4, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+               reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(wpk), bias, dst, nullptr, H, W, C, ldx, rows, (W + 13) / 14, units,
+               SweepEpiU8{out_scale, {mean4[0], mean4[1], mean4[2], mean4[3]}, h_out, w_out, bgr ? 1 : 0, (long long)dst_pitch,
+                          (long long)dst_bstride});
     return hat_check_launch();
 }

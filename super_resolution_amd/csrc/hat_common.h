@@ -240,6 +240,13 @@ template <typename T> __device__ __forceinline__ float gelu_act(float x) {
 
 // Launch status.  Every launch site first drains hipGetLastError(): the value is per-thread state that
 // other libraries in the process (e.g. a failed probe inside the framework) may have left set.
+// tensor2img of the reference (basicsr utils/img_util.py:66-91): clamp to [0, 1], x255 in fp32, round half to even
+// (v_rndne_f32).  The one conversion every 8-bit output path shares (hat_planes_to_u8, hat_conv3x3_to_u8).
+__device__ __forceinline__ unsigned hat_unit_to_u8(float v) {
+    v = fminf(fmaxf(v, 0.f), 1.f);
+    return (unsigned)(int)__builtin_rintf(v * 255.0f);
+}
+
 #define HAT_LAUNCH(...)                      \
     do {                                     \
         (void)hipGetLastError();             \

@@ -42,6 +42,10 @@ struct hat_plan {
     std::vector<Buf> bufs;
     std::vector<Call> calls;
     int device = -1;   // the device the buffers were allocated on (hat_plan_forward refuses to launch on another one)
+    // hat_plan_forward_u8's fp32 staging (allocated by its first call, freed with the plan; `mutable`: the C API hands plans
+    // out as const, and like the workspace these belong to the one forward that may run at a time)
+    mutable float* stage_in = nullptr;
+    mutable float* stage_out = nullptr;
 };
 
 namespace {
@@ -165,6 +169,8 @@ extern "C" void hat_plan_free(hat_plan* p) {
     if (!p) return;
     for (Buf& b : p->bufs)
         if (b.dev) (void)hipFree(b.dev);
+    if (p->stage_in) (void)hipFree(p->stage_in);
+    if (p->stage_out) (void)hipFree(p->stage_out);
     delete p;
 }
 
@@ -297,4 +303,61 @@ extern "C" int hat_plan_forward(const hat_plan* p, const float* x, float* y, voi
         if (rc) return rc;
     }
     return 0;
+}
+
+namespace {
+constexpr uint32_t FN_CONV3X3_TO_PLANES = 16;   // index of "hat_conv3x3_to_planes" in FN_NAMES
+
+bool addresses_output(const hat_plan* p, const Call& c) {
+    for (const Arg& a : c.args) {
+        if (a.tag == ARG_PTR && a.buf != NULL_BUF && p->bufs[a.buf].kind == BUF_OUTPUT) return true;
+        for (const Fix& fx : a.fix)
+            if (fx.buf != NULL_BUF && p->bufs[fx.buf].kind == BUF_OUTPUT) return true;
+    }
+    return false;
+}
+
+// The recorded forward ends with hat_conv3x3_to_planes writing three planes to the start of the output buffer and no earlier
+// launch touches that buffer: the fp32 image can be skipped (the earlier launches are then replayed without an output).
+bool ends_in_planes(const hat_plan* p) {
+    if (p->calls.empty() || strcmp(FN_NAMES[FN_CONV3X3_TO_PLANES], "hat_conv3x3_to_planes") != 0) return false;
+    const Call& c = p->calls.back();
+    if (c.fn != FN_CONV3X3_TO_PLANES || c.args.size() != 14 || c.args[3].tag != ARG_PTR || c.args[3].buf >= p->bufs.size()) return false;
+    if (p->bufs[c.args[3].buf].kind != BUF_OUTPUT || c.args[3].off != 0 || c.args[9].i != 3) return false;
+    for (size_t k = 0; k + 1 < p->calls.size(); ++k)
+        if (addresses_output(p, p->calls[k])) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" int hat_plan_forward_u8(const hat_plan* p, const uint8_t* src, int64_t src_pitch, int32_t h, int32_t w, uint8_t* dst,
+                                   int64_t dst_pitch, int32_t flags, void* stream) {
+    if (!p || !src || !dst || h < 1 || w < 1 || src_pitch < 3 * (int64_t)w) return HAT_EINVAL;
+    const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4];
+    if (p->dims[1] != 3 || p->dims[5] != 3) return HAT_EUNSUPPORTED;   // 8-bit frames are three-channel
+    if (h > H || w > W || H - h >= h || W - w >= w || dst_pitch < 3 * (int64_t)s * w) return HAT_EINVAL;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != p->device) return HAT_EINVAL;
+    const bool fused = ends_in_planes(p);
+    if (!p->stage_in) {
+        const hipError_t e = hipMalloc((void**)&p->stage_in, (size_t)B * 3 * H * W * sizeof(float));
+        if (e != hipSuccess) { p->stage_in = nullptr; return (int)e; }
+    }
+    if (!fused && !p->stage_out) {
+        const hipError_t e = hipMalloc((void**)&p->stage_out, (size_t)B * 3 * s * H * s * W * sizeof(float));
+        if (e != hipSuccess) { p->stage_out = nullptr; return (int)e; }
+    }
+    const int bgr = flags & 1, ho = s * h, wo = s * w;
+    int rc = hat_u8_to_planes(src, src_pitch, src_pitch * h, p->stage_in, B, h, w, H, W, bgr, stream);
+    if (rc) return rc;
+    const size_t n = p->calls.size() - (fused ? 1 : 0);
+    for (size_t k = 0; k < n; ++k) {
+        Resolved r{p, &p->calls[k], p->stage_in, p->stage_out, stream, {}};
+        rc = dispatch(r);
+        if (rc) return rc;
+    }
+    if (!fused) return hat_planes_to_u8(p->stage_out, B, s * H, s * W, dst, dst_pitch, dst_pitch * ho, ho, wo, bgr, stream);
+    Resolved r{p, &p->calls.back(), p->stage_in, nullptr, stream, {}};
+    return hat_conv3x3_to_u8(r.P(0), r.P(1), (const float*)r.P(2), dst, dst_pitch, dst_pitch * ho, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8),
+                             ho, wo, r.F(10), (const float*)r.P(11), bgr, r.I(12), stream);
 }

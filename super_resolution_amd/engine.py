@@ -214,6 +214,7 @@ class HATEngine:
         self._ws_max = int(os.environ.get("HAT_WS_CACHE", "12"))
         self._ws_max_bytes = int(float(os.environ.get("HAT_WS_CACHE_GIB", "96")) * 2 ** 30)
         self.ws_allocations = self.fp16_fallbacks = 0
+        self.u8_fused_calls = self.u8_planes_calls = 0   # 8-bit forwards that ended in hat_conv3x3_to_u8 / in hat_planes_to_u8
         self.use_n16 = not self.opt.no_n16
         # FP16 residual rows between the fused HAB tails of a residual group (bf16 path, embed_dim 144; HAT_NO_T16=1: fp32 everywhere)
         self.t16 = not self.opt.no_t16 and self.opt.emu_t16 is None and self.dtype == ops.HAT_BF16 and self.C == 144
@@ -443,6 +444,10 @@ class HATEngine:
                     nxt, gap_c = (self.norm, 0) if self.conv_after_body is not None else (None, 0)
                 G.conv_ln = (nxt, gap_c) if nxt is not None and gap_c in (0, 4, 8, 12, 16) else None
         self._resolve_stream16()
+        # 8-bit output (forward_to_u8 / forward_u8): conv_last's row-sweep kernel converts in its epilogue when it is packed for
+        # three output channels (the width condition, W % 16, is the one _upsample already checks per shape); otherwise
+        # conv_last writes fp32 planes and hat_planes_to_u8 converts them
+        self.u8_fused = self.conv_last_sweep is not None and self.conv_last_sweep[2] == 3
         # what every workspace is sized by
         hab0 = layers[0].habs[0] if layers and layers[0].habs else None
         self._hab0 = hab0
@@ -608,27 +613,82 @@ class HATEngine:
         with self._lock, torch.cuda.device(self.dev):
             return self._forward(x, one_stream=one_stream)
 
+    def _check_u8(self):
+        if self.cfg["in_chans"] != 3:
+            raise RuntimeError(f"8-bit frames are three-channel images: in_chans={self.cfg['in_chans']} has no uint8 path "
+                               f"(use forward() and convert the planes yourself)")
+
+    def _u8_out(self, out, shape):
+        """The (B,h_out,w_out,3) uint8 result: the caller's `out` (rows may be pitched) or a fresh tensor."""
+        if out is None:
+            return torch.empty(shape, dtype=torch.uint8, device=self.dev)
+        if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device != self.dev or out.stride(3) != 1 or out.stride(2) != 3:
+            raise RuntimeError(f"out must be a {tuple(shape)} uint8 tensor on {self.dev} with interleaved pixels, got "
+                               f"{tuple(out.shape)} {out.dtype} on {out.device}")
+        return out
+
+    def forward_to_u8(self, x: torch.Tensor, *, crop=None, bgr: bool = False, out=None, one_stream: Optional[bool] = None) -> torch.Tensor:
+        """forward(x) converted on the device as the reference's tensor2img converts it: (B,3,H,W) float in ->
+        (B,h_out,w_out,3) uint8 out, crop = (h_out, w_out) the top-left pixels kept (default: all of (sH, sW)), bgr: bytes in
+        B, G, R order, out: write into this tensor instead of a fresh one (then the call allocates nothing on the fused path).
+        The fp32 image is not written where conv_last converts in its epilogue (u8_fused_calls counts those)."""
+        self._check_u8()
+        if not x.is_cuda or x.device != self.dev:
+            raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
+        ho, wo = (x.shape[2] * self.scale, x.shape[3] * self.scale) if crop is None else (int(crop[0]), int(crop[1]))
+        if not (1 <= ho <= x.shape[2] * self.scale and 1 <= wo <= x.shape[3] * self.scale):
+            raise RuntimeError(f"crop {(ho, wo)} does not lie inside the output {(x.shape[2] * self.scale, x.shape[3] * self.scale)}")
+        with self._lock, torch.cuda.device(self.dev):
+            return self._forward(x, one_stream=one_stream, u8=(ho, wo, bool(bgr), self._u8_out(out, (x.shape[0], ho, wo, 3))))
+
+    def forward_u8(self, frame: torch.Tensor, *, bgr: bool = False, out=None) -> torch.Tensor:
+        """(B,h,w,3) uint8 device frames of any size the reflection allows -> (B,s*h,s*w,3) uint8: float(v) / 255, the
+        reflect-pad to the next window multiple (hat_u8_to_planes, into this shape's workspace), the forward, the crop and
+        tensor2img's conversion (in conv_last's epilogue or hat_planes_to_u8).  bgr: the bytes are B, G, R on both sides;
+        out: the caller's (B,s*h,s*w,3) uint8 result tensor (default: a fresh one)."""
+        self._check_u8()
+        if frame.dim() != 4 or frame.shape[3] != 3 or frame.dtype != torch.uint8:
+            raise RuntimeError(f"expected (B,h,w,3) uint8 frames, got {tuple(frame.shape)} {frame.dtype}")
+        if not frame.is_cuda or frame.device != self.dev:
+            raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
+        B, h, w, _ = frame.shape
+        Hp, Wp = -(-h // self.ws) * self.ws, -(-w // self.ws) * self.ws
+        if Hp - h >= h or Wp - w >= w:
+            raise RuntimeError(f"a {h}x{w} frame cannot be reflect-padded to {Hp}x{Wp} (window_size {self.ws}): the padding must be "
+                               f"smaller than the frame")
+        if frame.stride(3) != 1 or frame.stride(2) != 3:
+            frame = frame.contiguous()
+        with self._lock, torch.cuda.device(self.dev):
+            ws = self._workspace(B, Hp, Wp)
+            if "x_u8" not in ws:     # the padded fp32 input of this shape: allocated once, with the workspace
+                ws["x_u8"] = torch.zeros(B, 3, Hp, Wp, dtype=torch.float32, device=self.dev)
+                ws["bytes"] += ws["x_u8"].numel() * 4
+            ops.u8_to_planes(frame, ws["x_u8"], bgr=bgr)
+            ho, wo = h * self.scale, w * self.scale
+            return self._forward(ws["x_u8"], u8=(ho, wo, bool(bgr), self._u8_out(out, (B, ho, wo, 3))))
+
     def ocab_only(self, t: torch.Tensor, group: int, H: int, W: int) -> torch.Tensor:
         """Run only the OCAB of residual group `group` on tokens t (B, H*W, C) fp32 -> (B, H*W, C) fp32 (used by the tests)."""
         x = torch.zeros(t.shape[0], self.cfg["in_chans"], H, W, device=self.dev)
         with self._lock, torch.cuda.device(self.dev):
             return self._forward(x, only_ocab=(t.to(self.dev, torch.float32).contiguous(), group))
 
-    def _forward(self, x: torch.Tensor, only_ocab=None, one_stream=None) -> torch.Tensor:
-        gen = self._forward_gen(x, only_ocab=only_ocab, one_stream=one_stream)
+    def _forward(self, x: torch.Tensor, only_ocab=None, one_stream=None, u8=None) -> torch.Tensor:
+        gen = self._forward_gen(x, only_ocab=only_ocab, one_stream=one_stream, u8=u8)
         try:
             req = next(gen)
         except StopIteration as done:
             return done.value
         raise RuntimeError(f"the unsharded forward must not reach an exchange point (got {req[0]!r})")
 
-    def _forward_gen(self, x: torch.Tensor, only_ocab=None, band=None, one_stream=None):
+    def _forward_gen(self, x: torch.Tensor, only_ocab=None, band=None, one_stream=None, u8=None):
         """The forward as a generator.  Unsharded (band=None) it never yields and returns the output.  For one ROW BAND of a
         sharded frame (band: tile_parallel.Band, x = the band's rows + ghost rows of the LR frame) it yields at
         every point where bands must exchange: ("halo", [(tensor, depth) ...]) — refresh `depth` ghost rows above and below
         from the neighbours that own them — and ("reduce", local, glob, n) — glob[:, :n] = sum over bands of local[:, :n] (the
         global average pools of ECA, hat_arch.py:69-73, and of the ESC dynamic kernel, esc_arch.py:96,121) — and returns the
-        band's output rows (ghost rows included; the driver keeps the owned ones)."""
+        band's output rows (ghost rows included; the driver keeps the owned ones).
+        u8 = (h_out, w_out, bgr, out): the unsharded forward fills and returns out, (B,h_out,w_out,3) uint8 (forward_to_u8)."""
         if x.dim() != 4 or x.shape[1] != self.cfg["in_chans"]:
             raise RuntimeError(f"expected (B,{self.cfg['in_chans']},H,W), got {tuple(x.shape)}")
         B, _, H, W = x.shape
@@ -644,7 +704,12 @@ class HATEngine:
             w["tB"].copy_(t_in.reshape(B, H * W, self.C))
             f.t = w["tB"]
             return (yield from self._ocab(f, self.layers[gidx], as_conv_input=False)).clone()
-        y = torch.empty(B, self.cfg["in_chans"], H * self.scale, W * self.scale, dtype=torch.float32, device=self.dev)
+        if u8 is None:
+            y = torch.empty(B, self.cfg["in_chans"], H * self.scale, W * self.scale, dtype=torch.float32, device=self.dev)
+        else:
+            if band is not None:
+                raise RuntimeError("a row band hands its rows over as fp32: the 8-bit output is the unsharded forward's")
+            y = u8[3]
         self._head(f, x)
         for G in self.layers:
             for hb in G.habs:   # HAB                                                            :217-238
@@ -653,7 +718,7 @@ class HATEngine:
             tout = yield from self._ocab(f, G, as_conv_input=G.to_conv)
             yield from self._group_end(f, G, tout)
         yield from self._body_end(f)
-        self._upsample(f, y)
+        self._upsample(f, y, u8)
         return y
 
     # ------------------------------------------------------------------------------------------ stage steps
@@ -992,13 +1057,23 @@ class HATEngine:
         ops.conv(self.conv_after_body, w["n"], w["c2"], **f.geo, ldx=ldc, ldo=ldc, r1=w["f0"], ldr1=C)
         ops.conv(self.conv_before_up, w["c2"], w["fb"], **f.geo, ldx=ldc, ldo=64, act=ACT_LRELU)
 
-    def _upsample(self, f: _Fwd, y):
-        """conv + PixelShuffle per stage; conv_last ; / img_range + mean                     :593-605, :856-858"""
+    def _upsample(self, f: _Fwd, y, u8=None):
+        """conv + PixelShuffle per stage; conv_last ; / img_range + mean                     :593-605, :856-858
+        u8 = (h_out, w_out, bgr, y): y is (B,h_out,w_out,3) uint8 — conv_last converts in its epilogue (hat_conv3x3_to_u8) where
+        the row-sweep kernel runs, else it writes fp32 planes as always and hat_planes_to_u8 converts and crops them."""
         src, h, wd, dt = f.w["fb"], f.H, f.W, f.dt
         for (pw, rr), dst in zip(self.ups, f.w["ups"]):
             ops.conv(pw, src, dst, B=f.B, H=h, W=wd, dtype=dt, ldx=64, ldo=64, out_mode=O_PIXSHUF_T, ps_r=rr)
             src, h, wd = dst, h * rr, wd * rr
         r = float(self.cfg.get("img_range", 1.0))
+        if u8 is not None:
+            if self.u8_fused and wd % 16 == 0:
+                wpk, b8, _ = self.conv_last_sweep
+                ops.conv3x3_to_u8(src, wpk, b8, y, B=f.B, H=h, W=wd, C_=64, ldx=64, h_out=u8[0], w_out=u8[1], out_scale=1.0 / r,
+                                  mean=self._mean(), bgr=u8[2], dtype=dt)
+                self.u8_fused_calls += 1
+                return
+            y8, y = y, torch.empty(f.B, 3, h, wd, dtype=torch.float32, device=self.dev)
         if self.conv_last_sweep is not None and wd % 16 == 0:
             wpk, b8, nout = self.conv_last_sweep
             ops.conv3x3_to_planes(src, wpk, b8, y, B=f.B, H=h, W=wd, C_=64, ldx=64, n_out=nout, out_scale=1.0 / r, mean=self._mean(),
@@ -1006,3 +1081,6 @@ class HATEngine:
         else:
             ops.conv(self.conv_last, src, y, B=f.B, H=h, W=wd, dtype=dt, ldx=64, ldo=0, out_mode=O_NCHW_F32,
                      out_scale=1.0 / r, mean=self._mean())
+        if u8 is not None:
+            ops.planes_to_u8(y, y8, bgr=u8[2])
+            self.u8_planes_calls += 1

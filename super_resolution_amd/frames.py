@@ -1,0 +1,88 @@
+"""Frame sequences: 8-bit host frames in, 8-bit host frames out, with the copies hidden behind the compute.
+
+    for out in frames.upscale_frames(net, reader, bgr=True):   # reader yields (h,w,3) uint8 arrays of one size
+        writer.write(out)
+
+Two pinned input and two pinned output buffers, two device buffers on each side, and ONE extra stream for the copies of
+both directions: while frame n computes on the current stream, frame n+1 uploads and frame n-1 downloads on the copy
+stream; HIP events order the two streams.  No threads, no second process.  With the engine's own side stream the process
+uses three streams, within the four hardware queues a process gets by default.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+
+def upscale_frames(net, frames, *, bgr: bool = False):
+    """Generator: for every (h,w,3) uint8 array of `frames` (all of one size) yield the (s*h,s*w,3) uint8 array that
+    `net.forward_u8` computes for it, in order.  `net`: a HAT / HATX module on a GPU, in eval mode.  The yielded array is
+    the caller's own (copied out of the pinned buffer).  An empty sequence yields nothing."""
+    dev = next(net.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError("upscale_frames needs the network on a GPU: the MI355X HIP path is the only path")
+    it = iter(frames)
+    first = next(it, None)
+    if first is None:
+        return
+    first = np.ascontiguousarray(first)
+    if first.ndim != 3 or first.shape[2] != 3 or first.dtype != np.uint8:
+        raise RuntimeError(f"expected (h,w,3) uint8 frames, got {first.shape} {first.dtype}")
+    h, w, _ = first.shape
+    s = net.upscale
+    # Nothing of the device state stays entered across a yield: the buffers and the copy stream are made once, and every step
+    # enters the device and takes the stream that is current THEN, so a caller may switch device or stream between frames.
+    with torch.cuda.device(dev):
+        copy = torch.cuda.Stream(device=dev)
+        hin = [torch.empty(h, w, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        hout = [torch.empty(s * h, s * w, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        din = [torch.empty(1, h, w, 3, dtype=torch.uint8, device=dev) for _ in range(2)]
+        dout = [torch.empty(1, s * h, s * w, 3, dtype=torch.uint8, device=dev) for _ in range(2)]
+        ev = lambda: torch.cuda.Event()
+        up, done, down = [ev(), ev()], [ev(), ev()], [ev(), ev()]
+
+    def upload(k, a):
+        """frame -> pinned slot k -> device slot k, on the copy stream (after the compute that last read the slot)."""
+        a = np.ascontiguousarray(a)
+        if a.shape != (h, w, 3) or a.dtype != np.uint8:
+            raise RuntimeError(f"all frames of a sequence must be ({h},{w},3) uint8, got {a.shape} {a.dtype}")
+        up[k].synchronize()                    # the previous upload out of this pinned buffer has finished
+        hin[k].numpy()[...] = a
+        with torch.cuda.device(dev), torch.cuda.stream(copy):
+            copy.wait_event(done[k])           # the forward that last read din[k] (frame n-2) has finished
+            din[k].copy_(hin[k].unsqueeze(0), non_blocking=True)
+            up[k].record(copy)
+
+    def compute(k):
+        """forward of slot k on the stream that is current now, then its download on the copy stream."""
+        with torch.cuda.device(dev):
+            comp = torch.cuda.current_stream(dev)
+            comp.wait_event(up[k])
+            comp.wait_event(down[k])           # dout[k] was last read by the download of frame n-2
+            comp.wait_event(done[k ^ 1])       # the engine's workspace is shared: after frame n-1's forward, whatever stream it ran on
+            net.forward_u8(din[k], bgr=bgr, out=dout[k])
+            done[k].record(comp)               # din[k] is free again and dout[k] is complete
+            with torch.cuda.stream(copy):
+                copy.wait_event(done[k])
+                hout[k].copy_(dout[k][0], non_blocking=True)
+                down[k].record(copy)
+
+    def collect(k):
+        down[k].synchronize()
+        return hout[k].numpy().copy()
+
+    n = 0
+    upload(0, first)
+    nxt = next(it, None)
+    while True:
+        k = n & 1
+        if nxt is not None:
+            upload(k ^ 1, nxt)                 # frame n+1 goes up while frame n computes
+        compute(k)
+        if n >= 1:
+            yield collect(k ^ 1)               # frame n-1 (its download ran beside frame n's launches)
+        n += 1
+        if nxt is None:
+            break
+        nxt = next(it, None)
+    yield collect((n - 1) & 1)

@@ -96,11 +96,61 @@ class HATModel:
             self.process()
         self.post_process()
 
+    def test_u8(self, lq: torch.Tensor):
+        """`val.u8_on_device`: the same result as test() + tensor2img, with the conversions on the device.  The LQ image goes up
+        as uint8 and only the uint8 result comes back: without `tile`, HAT.forward_u8 pads, runs, crops and converts; with
+        `tile`, hat_u8_to_planes builds the padded input (pre_process_u8), tile_process runs as always and hat_planes_to_u8
+        crops and converts the assembled fp32 output.  lq: the
+        dataset's (1,3,h,w) float image, which must hold 8-bit values (v / 255, what data.read_image produces)."""
+        from .. import ops
+        u8 = torch.round(lq * 255.0).clamp(0, 255).to(torch.uint8)
+        if not torch.equal(u8.to(torch.float32) / 255.0, lq.to(torch.float32)):
+            raise RuntimeError("val.u8_on_device needs 8-bit input images (every value k / 255): this one is not")
+        frame = u8.permute(0, 2, 3, 1).contiguous().to(self.device)
+        if "tile" not in self.opt:
+            with torch.no_grad():
+                out = self.get_bare_model(self.net_g).forward_u8(frame)
+        else:
+            self.pre_process_u8(frame)
+            self.tile_process()
+            b, _, h, w = self.output.shape
+            out = torch.empty(b, h - self.mod_pad_h * self.scale, w - self.mod_pad_w * self.scale, 3, dtype=torch.uint8, device=self.device)
+            ops.planes_to_u8(self.output.to(torch.float32).contiguous(), out)
+            del self.img, self.output
+        return out[0].cpu().numpy()
+
+    def pre_process_u8(self, frame: torch.Tensor):
+        """pre_process for a (B,h,w,3) uint8 device frame: self.img = the reflect-padded float32(v) / 255 planes, bit for bit
+        what pre_process makes of data.read_image's tensor.  hat_u8_to_planes divides exactly and pads; a torch division on the
+        device would not do (it multiplies by the reciprocal, which is off by an ulp for about half of the byte values)."""
+        from .. import ops
+        window_size = self.opt["network_g"]["window_size"]
+        self.scale = self.opt.get("scale", 1)
+        b, h, w, _ = frame.shape
+        self.mod_pad_h = (window_size - h % window_size) % window_size
+        self.mod_pad_w = (window_size - w % window_size) % window_size
+        if self.mod_pad_h >= h or self.mod_pad_w >= w:
+            raise RuntimeError(f"a {h}x{w} image cannot be reflect-padded to a multiple of window_size {window_size}")
+        self.img = torch.empty(b, 3, h + self.mod_pad_h, w + self.mod_pad_w, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            ops.u8_to_planes(frame, self.img)
+
     def get_current_visuals(self):
         out = {"lq": self.lq.detach().cpu(), "result": self.output.detach().cpu()}
         if hasattr(self, "gt"):
             out["gt"] = self.gt.detach().cpu()
         return out
+
+    def _test_float(self, val_data):
+        self.feed_data(val_data)
+        self.test()
+        visuals = self.get_current_visuals()
+        data = {"img": tensor2img(visuals["result"])}
+        if "gt" in visuals:
+            data["img2"] = tensor2img(visuals["gt"])
+            del self.gt
+        del self.lq, self.output
+        return data
 
     def nondist_validation(self, dataset, save_img: bool = True):  # hat_model.py:114-185
         dataset_name = dataset.opt["name"]
@@ -111,15 +161,13 @@ class HATModel:
         n = 0
         for val_data in dataset:
             img_name = osp.splitext(osp.basename(val_data["lq_path"][0]))[0]
-            self.feed_data(val_data)
-            self.test()
-            visuals = self.get_current_visuals()
-            sr_img = tensor2img(visuals["result"])
-            data = {"img": sr_img}
-            if "gt" in visuals:
-                data["img2"] = tensor2img(visuals["gt"])
-                del self.gt
-            del self.lq, self.output
+            if val.get("u8_on_device"):
+                data = {"img": self.test_u8(val_data["lq"])}
+                if "gt" in val_data:
+                    data["img2"] = tensor2img(val_data["gt"])
+            else:
+                data = self._test_float(val_data)
+            sr_img = data["img"]
             if save_img:
                 suffix = val.get("suffix") or self.opt["name"]
                 root = (self.opt.get("path") or {}).get("visualization") or osp.join("results", self.opt["name"], "visualization")

@@ -429,6 +429,49 @@ def conv3x3_to_planes(x, wpk, bias8, out, *, B: int, H: int, W: int, C_: int, ld
                                   _stream()), "hat_conv3x3_to_planes"), tag=f"k3 {C_}->{n_out} {H}x{W} row sweep planes")
 
 
+def conv3x3_to_u8(x, wpk, bias8, out, *, B: int, H: int, W: int, C_: int, ldx: int, h_out: int, w_out: int, out_scale: float, mean,
+                  bgr: bool, dtype: int):
+    """conv_last with the 8-bit conversion as its epilogue: out (B, h_out, w_out, 3) uint8 = tensor2img of what
+    conv3x3_to_planes writes, cropped to the top-left h_out x w_out pixels; no fp32 image is written."""
+    lib = _lib.load()
+    m4 = (C.c_float * 4)(*[float(mean[i]) if i < len(mean) else 0.0 for i in range(4)])
+    if out.dtype != torch.uint8 or not out.is_cuda or tuple(out.shape) != (B, h_out, w_out, 3) or out.stride(-1) != 1 or out.stride(-2) != 3:
+        raise RuntimeError("conv3x3_to_u8 needs a (B,h_out,w_out,3) uint8 device destination with interleaved pixels")
+    _timed("cab_squeeze_kernel<2, u8>", 2.0 * B * H * W * 9 * C_ * 3, lambda: _lib.check(
+        lib.hat_conv3x3_to_u8(_ptr(x), _ptr(wpk), _ptr(bias8), out.data_ptr(), out.stride(1), out.stride(0), B, H, W, C_, ldx, h_out, w_out,
+                              out_scale, m4, int(bgr), dtype, _stream()), "hat_conv3x3_to_u8"), tag=f"k3 {C_}->3 {H}x{W} row sweep u8")
+
+
+def u8_to_planes(src, dst, *, bgr: bool = False):
+    """src (B, h, w, 3) uint8 (rows may be pitched: stride(-3) >= 3 w) -> dst (B, 3, Hp, Wp) fp32 = float(src) / 255 as
+    planes, the rows and columns past (h, w) filled by reflection (hat_u8_to_planes)."""
+    lib = _lib.load()
+    B, h, w, c = src.shape
+    if c != 3 or src.dtype != torch.uint8 or src.stride(-1) != 1 or src.stride(-2) != 3 or dst.dtype != torch.float32:
+        raise RuntimeError("u8_to_planes needs (B,h,w,3) uint8 with interleaved pixels and an fp32 destination")
+    if not src.is_cuda:
+        raise RuntimeError("HAT HIP ops need device tensors (no CPU path exists)")
+    if dst.dim() != 4 or dst.shape[0] != B or dst.shape[1] != 3 or dst.shape[2] < h or dst.shape[3] < w or dst.device != src.device:
+        raise RuntimeError(f"u8_to_planes needs a (B,3,Hp>=h,Wp>=w) destination on {src.device}, got {tuple(dst.shape)} on {dst.device} "
+                           f"for frames {tuple(src.shape)}")
+    _timed("u8_to_planes_kernel", 0.0, lambda: _lib.check(
+        lib.hat_u8_to_planes(src.data_ptr(), src.stride(1), src.stride(0), _ptr(dst), B, h, w, dst.shape[2], dst.shape[3], int(bgr),
+                             _stream()), "hat_u8_to_planes"), tag=f"u8 {h}x{w} -> planes {dst.shape[2]}x{dst.shape[3]}")
+
+
+def planes_to_u8(src, dst, *, bgr: bool = False):
+    """src (B, 3, Hs, Ws) fp32 planes -> dst (B, h_out, w_out, 3) uint8 (rows may be pitched), the top-left crop, converted as
+    the reference's tensor2img converts: clamp to [0, 1], x255 in fp32, round half to even (hat_planes_to_u8)."""
+    lib = _lib.load()
+    B, c, Hs, Ws = src.shape
+    if c != 3 or src.dtype != torch.float32 or dst.dtype != torch.uint8 or dst.shape[0] != B or dst.shape[3] != 3 or dst.stride(-1) != 1 \
+            or dst.stride(-2) != 3 or not dst.is_cuda:
+        raise RuntimeError("planes_to_u8 needs (B,3,Hs,Ws) fp32 planes and a (B,h,w,3) uint8 device destination with interleaved pixels")
+    _timed("planes_to_u8_kernel", 0.0, lambda: _lib.check(
+        lib.hat_planes_to_u8(_ptr(src), B, Hs, Ws, dst.data_ptr(), dst.stride(1), dst.stride(0), dst.shape[1], dst.shape[2], int(bgr),
+                             _stream()), "hat_planes_to_u8"), tag=f"planes {Hs}x{Ws} -> u8 {dst.shape[1]}x{dst.shape[2]}")
+
+
 def cab_squeeze_units(H: int, W: int) -> int:
     lib = _lib.load()
     rows, units = C.c_int32(0), C.c_int32(0)

@@ -211,6 +211,20 @@ class Plan:
     def forward(self, x: torch.Tensor, y: torch.Tensor, stream: int = 0):
         _lib.check(self._lib.hat_plan_forward(self._h, x.data_ptr(), y.data_ptr(), stream), "hat_plan_forward")
 
+    def forward_u8(self, src: torch.Tensor, dst: torch.Tensor, *, bgr: bool = False, stream: int = 0):
+        """hat_plan_forward_u8: src (B,h,w,3) uint8 device frames with h <= H, w <= W of the plan (reflect-padded to (H, W) on
+        the device) -> dst (B,s*h,s*w,3) uint8.  Rows may be pitched; samples must lie h (s*h) rows apart.  The first call
+        allocates the plan's fp32 staging buffers."""
+        for t, rows in ((src, src.shape[1]), (dst, dst.shape[1])):
+            if not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.stride(3) != 1 or t.stride(2) != 3 \
+                    or (t.shape[0] > 1 and t.stride(0) != rows * t.stride(1)):
+                raise RuntimeError("forward_u8 needs (B,h,w,3) uint8 device tensors with interleaved pixels and samples h rows apart")
+        s, (h, w) = self.dims[4], src.shape[1:3]
+        if src.shape[0] != self.dims[0] or tuple(dst.shape) != (self.dims[0], s * h, s * w, 3):
+            raise RuntimeError(f"forward_u8: src {tuple(src.shape)} / dst {tuple(dst.shape)} do not match a plan of batch {self.dims[0]}, scale {s}")
+        _lib.check(self._lib.hat_plan_forward_u8(self._h, src.data_ptr(), src.stride(1), h, w, dst.data_ptr(), dst.stride(1), int(bgr), stream),
+                   "hat_plan_forward_u8")
+
     def close(self):
         if self._h:
             self._lib.hat_plan_free(self._h)

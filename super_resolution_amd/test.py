@@ -12,9 +12,12 @@ from .data import FolderDataset
 from .models import HATModel
 
 
-def parse_options(path: str) -> dict:
+def parse_options(path: str, u8: bool = False) -> dict:
+    """u8 (the --u8 flag): set val.u8_on_device; without it the options are exactly what the YAML says."""
     with open(path) as f:
         opt = yaml.safe_load(f)
+    if u8:
+        opt["val"] = dict(opt.get("val") or {}, u8_on_device=True)
     opt["is_train"] = False
     for phase, d in (opt.get("datasets") or {}).items():
         d["phase"] = phase.split("_")[0]
@@ -27,8 +30,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("-opt", type=str, required=True, help="Path to option YAML file.")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--u8", action="store_true", help="8-bit frames on the device (sets val.u8_on_device): upload uint8, download uint8")
     args = ap.parse_args(argv)
-    opt = parse_options(args.opt)
+    opt = parse_options(args.opt, u8=args.u8)
     model = HATModel(opt, device=args.device)
     results = {}
     for _, dopt in sorted((opt.get("datasets") or {}).items()):
