@@ -385,6 +385,36 @@ int hat_conv3x3_to_u8(const void* x, const void* wpk, const float* bias, uint8_t
                       const float* mean4, int32_t bgr, int32_t dtype, void* stream);
 
 /*
+ * PSNR / SSIM of two 8-bit frames on the device, with the definitions of the reference's validation loop (basicsr
+ * metrics/psnr_ssim.py calculate_psnr / calculate_ssim / _ssim, metrics/metric_util.py to_y_channel).  a, b: (B,h,w,3) uint8
+ * with row pitches >= 3 w bytes and sample strides in bytes (ignored for B == 1), as hat_u8_to_planes takes them.
+ * crop_border pixels come off every side first (0 crops nothing).  flags: HAT_METRICS_PSNR and / or HAT_METRICS_SSIM select
+ * what is produced (at least one); HAT_METRICS_Y scores the BT.601 Y value of each pixel (float32(v) / 255 per channel,
+ * y = 65.481 r + 128.553 g + 24.966 b + 16 in fp64, float32(y / 255) * 255 in fp32, not rounded to a level), with
+ * HAT_METRICS_BGR naming the byte order of BOTH frames; without HAT_METRICS_Y the three byte values are scored as they are
+ * (byte order does not matter then: the flag is ignored).
+ *
+ * sums: [B][4] doubles in device memory.  sums[b][0] = the sum of squared differences over the cropped frame (all three
+ * channels without HAT_METRICS_Y; exact there: accumulated in 64-bit integers), sums[b][1 + c] = the sum of the SSIM map of
+ * channel c over its (h - 2 crop - 10) x (w - 2 crop - 10) positions (VALID 11x11 Gaussian window, sigma 1.5, C1 = (0.01 *
+ * 255)^2, C2 = (0.03 * 255)^2; only c = 0 with HAT_METRICS_Y).  Entries that are not produced are written as 0.  The caller
+ * divides and takes the logarithm: PSNR = 10 log10(255^2 n / sums[0]), SSIM = mean over channels of sums[1 + c] / positions.
+ * All SSIM arithmetic is fp64 (sigma^2 = blur(a^2) - mu^2 cancels; fp32 is 4e-4 off on a nearly flat image).  The sums are
+ * reproducible bit for bit: per-workgroup partials in `workspace`, added in a fixed order by a second small launch; no
+ * floating-point atomics.
+ *
+ * hat_u8_metrics_workspace_bytes is a pure host query: the size `workspace` must have (8-byte aligned device memory; its
+ * content before the call does not matter).  Both functions return HAT_EINVAL for B, h or w < 1, a negative crop_border,
+ * unknown flag bits, neither metric selected, a cropped frame without pixels, a cropped frame smaller than 11x11 with
+ * HAT_METRICS_SSIM, and more than 65535 sample-channels; hat_u8_metrics also for null pointers, a pitch below 3 w and
+ * overlapping samples.  The checks come before anything touches the device; neither function allocates or synchronises.
+ */
+enum { HAT_METRICS_Y = 1, HAT_METRICS_BGR = 2, HAT_METRICS_PSNR = 4, HAT_METRICS_SSIM = 8 };
+int hat_u8_metrics_workspace_bytes(int32_t B, int32_t h, int32_t w, int32_t crop_border, int32_t flags, int64_t* bytes);
+int hat_u8_metrics(const uint8_t* a, int64_t a_pitch, int64_t a_bstride, const uint8_t* b, int64_t b_pitch, int64_t b_bstride,
+                   int32_t B, int32_t h, int32_t w, int32_t crop_border, int32_t flags, double* sums, void* workspace, void* stream);
+
+/*
  * (Shifted-)window self-attention, (S)W-MSA — SURVEY §8 row f2.  Replaces, for one attention branch of a Swin / upstream-HAT
  * block, ESC/basicsr/archs/swinir_arch.py:291-317 (torch.roll by -shift, window_partition, WindowAttention core :147-168
  * with the relative-position bias :153-156 and the shift mask of calculate_mask :262-280, window_reverse, torch.roll by

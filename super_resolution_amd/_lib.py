@@ -17,6 +17,7 @@ HAT_F32, HAT_BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_LRELU = 0, 1, 2
 X_NHWC_T, X_NHWC_F32, X_NCHW_F32_MEAN = 0, 1, 2
 O_NHWC_T, O_NHWC_F32, O_PIXSHUF_T, O_NCHW_F32 = 0, 1, 2, 3
+METRICS_Y, METRICS_BGR, METRICS_PSNR, METRICS_SSIM = 1, 2, 4, 8   # flags of hat_u8_metrics
 
 _ERRORS = {-1: "HAT_EINVAL (bad argument)", -2: "HAT_ELDS (tile does not fit in 160 KiB LDS)",
            -3: "HAT_EUNSUPPORTED (shape not instantiated)"}
@@ -154,6 +155,9 @@ SIGNATURES = {
                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "hat_plan_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                       C.c_void_p]),
+    "hat_u8_metrics_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "hat_u8_metrics": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                 C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hat_window_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_void_p]),

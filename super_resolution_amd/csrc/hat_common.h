@@ -247,6 +247,17 @@ __device__ __forceinline__ unsigned hat_unit_to_u8(float v) {
     return (unsigned)(int)__builtin_rintf(v * 255.0f);
 }
 
+// float(v) / 255.0f for every byte value, correctly rounded: built by the compiler's constant evaluator (IEEE), so a
+// kernel does not depend on how the device divides (a reciprocal multiply is not exact for every byte value).  The 8-bit
+// input side (hat_u8_to_planes) and the Y value of the metrics (hat_u8_metrics) read the same table.
+struct HatU8Table {
+    float v[256];
+    constexpr HatU8Table() : v() {
+        for (int i = 0; i < 256; ++i) v[i] = (float)i / 255.0f;
+    }
+};
+static __device__ const HatU8Table hat_u8_unit{};
+
 #define HAT_LAUNCH(...)                      \
     do {                                     \
         (void)hipGetLastError();             \

@@ -6,16 +6,6 @@
 
 namespace {
 
-// float(v) / 255.0f for every byte value, correctly rounded: built by the compiler's constant evaluator (IEEE), so the
-// kernel does not depend on how the device divides (a reciprocal multiply is not exact for every byte value).
-struct U8Table {
-    float v[256];
-    constexpr U8Table() : v() {
-        for (int i = 0; i < 256; ++i) v[i] = (float)i / 255.0f;
-    }
-};
-__device__ const U8Table hat_u8_unit{};
-
 // one thread = one pixel of the padded plane row: three byte loads (the row's bytes stay in L1 / L2 across the 3 reads of
 // a lane and the neighbouring lanes), three plane stores coalesced over the lanes.  Reflection (F.pad 'reflect', no edge
 // repeat): padded row y >= h reads row 2 (h - 1) - y, likewise in x.

@@ -96,17 +96,23 @@ class HATModel:
             self.process()
         self.post_process()
 
-    def test_u8(self, lq: torch.Tensor):
+    def _u8_frame(self, img: torch.Tensor, option: str, what: str) -> torch.Tensor:
+        """The dataset's (1,3,h,w) float image, which must hold 8-bit values (v / 255, what data.read_image produces) -> the
+        (1,h,w,3) uint8 frame on the device."""
+        u8 = torch.round(img * 255.0).clamp(0, 255).to(torch.uint8)
+        if not torch.equal(u8.to(torch.float32) / 255.0, img.to(torch.float32)):
+            raise RuntimeError(f"{option} needs 8-bit {what} images (every value k / 255): this one is not")
+        return u8.permute(0, 2, 3, 1).contiguous().to(self.device)
+
+    def test_u8(self, lq: torch.Tensor, on_device: bool = False):
         """`val.u8_on_device`: the same result as test() + tensor2img, with the conversions on the device.  The LQ image goes up
         as uint8 and only the uint8 result comes back: without `tile`, HAT.forward_u8 pads, runs, crops and converts; with
         `tile`, hat_u8_to_planes builds the padded input (pre_process_u8), tile_process runs as always and hat_planes_to_u8
         crops and converts the assembled fp32 output.  lq: the
-        dataset's (1,3,h,w) float image, which must hold 8-bit values (v / 255, what data.read_image produces)."""
+        dataset's (1,3,h,w) float image, which must hold 8-bit values (v / 255, what data.read_image produces).
+        on_device (`val.metrics_on_device`): return the (h,w,3) uint8 device tensor instead of downloading it."""
         from .. import ops
-        u8 = torch.round(lq * 255.0).clamp(0, 255).to(torch.uint8)
-        if not torch.equal(u8.to(torch.float32) / 255.0, lq.to(torch.float32)):
-            raise RuntimeError("val.u8_on_device needs 8-bit input images (every value k / 255): this one is not")
-        frame = u8.permute(0, 2, 3, 1).contiguous().to(self.device)
+        frame = self._u8_frame(lq, "val.u8_on_device", "input")
         if "tile" not in self.opt:
             with torch.no_grad():
                 out = self.get_bare_model(self.net_g).forward_u8(frame)
@@ -117,7 +123,7 @@ class HATModel:
             out = torch.empty(b, h - self.mod_pad_h * self.scale, w - self.mod_pad_w * self.scale, 3, dtype=torch.uint8, device=self.device)
             ops.planes_to_u8(self.output.to(torch.float32).contiguous(), out)
             del self.img, self.output
-        return out[0].cpu().numpy()
+        return out[0] if on_device else out[0].cpu().numpy()
 
     def pre_process_u8(self, frame: torch.Tensor):
         """pre_process for a (B,h,w,3) uint8 device frame: self.img = the reflect-padded float32(v) / 255 planes, bit for bit
@@ -152,6 +158,26 @@ class HATModel:
         del self.lq, self.output
         return data
 
+    def _test_metrics_on_device(self, val_data, metrics, save_img):
+        """`val.metrics_on_device`: test_u8 leaves its result on the device, the ground truth goes up as uint8 and the metrics
+        of type calculate_psnr / calculate_ssim come from hat_u8_metrics (metrics_device.calculate_metrics_u8).  The result is
+        downloaded only when it is saved or a metric of another type needs it; that metric is computed on the host as ever.
+        Returns (data for the host side: 'img' / 'img2' where they exist there, {name: value} of the device metrics)."""
+        from ..metrics_device import DEVICE_METRICS, calculate_metrics_u8
+        out = self.test_u8(val_data["lq"], on_device=True)
+        has_gt = "gt" in val_data
+        scored = {}
+        if metrics and has_gt:
+            gt = self._u8_frame(val_data["gt"], "val.metrics_on_device", "ground-truth")[0]
+            scored = calculate_metrics_u8(out, gt, metrics)
+        host_metrics = bool(metrics) and has_gt and any(m.get("type") not in DEVICE_METRICS for m in metrics.values())
+        data = {}
+        if save_img or host_metrics:
+            data["img"] = out.cpu().numpy()
+        if host_metrics:
+            data["img2"] = tensor2img(val_data["gt"])
+        return data, scored
+
     def nondist_validation(self, dataset, save_img: bool = True):  # hat_model.py:114-185
         dataset_name = dataset.opt["name"]
         val = self.opt.get("val") or {}
@@ -159,23 +185,27 @@ class HATModel:
         self.metric_results = {m: 0.0 for m in (metrics or {})}
         per_image = []
         n = 0
+        on_device = bool(val.get("metrics_on_device"))   # implies u8_on_device; the known metrics are scored where the result is
         for val_data in dataset:
             img_name = osp.splitext(osp.basename(val_data["lq_path"][0]))[0]
-            if val.get("u8_on_device"):
+            device_metrics = {}
+            if on_device:
+                data, device_metrics = self._test_metrics_on_device(val_data, metrics, save_img)
+            elif val.get("u8_on_device"):
                 data = {"img": self.test_u8(val_data["lq"])}
                 if "gt" in val_data:
                     data["img2"] = tensor2img(val_data["gt"])
             else:
                 data = self._test_float(val_data)
-            sr_img = data["img"]
+            sr_img = data.get("img")
             if save_img:
                 suffix = val.get("suffix") or self.opt["name"]
                 root = (self.opt.get("path") or {}).get("visualization") or osp.join("results", self.opt["name"], "visualization")
                 write_image(sr_img, osp.join(root, dataset_name, f"{img_name}_{suffix}.png"))
             row = {"name": img_name}
-            if metrics and "img2" in data:
+            if metrics and ("img2" in data or device_metrics):
                 for name, mopt in metrics.items():
-                    v = calculate_metric(data, mopt)
+                    v = device_metrics[name] if name in device_metrics else calculate_metric(data, mopt)
                     self.metric_results[name] += v
                     row[name] = v
             per_image.append(row)

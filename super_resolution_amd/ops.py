@@ -472,6 +472,50 @@ def planes_to_u8(src, dst, *, bgr: bool = False):
                              _stream()), "hat_planes_to_u8"), tag=f"planes {Hs}x{Ws} -> u8 {dst.shape[1]}x{dst.shape[2]}")
 
 
+def u8_metrics_flags(*, y_channel: bool, bgr: bool, psnr: bool, ssim: bool) -> int:
+    return (_lib.METRICS_Y if y_channel else 0) | (_lib.METRICS_BGR if bgr else 0) | (_lib.METRICS_PSNR if psnr else 0) \
+        | (_lib.METRICS_SSIM if ssim else 0)
+
+
+def u8_metrics_workspace_bytes(B: int, h: int, w: int, *, crop_border: int, y_channel: bool, bgr: bool = False, psnr: bool = True,
+                               ssim: bool = True) -> int:
+    """Bytes of workspace hat_u8_metrics needs for (B,h,w,3) frames; raises for sizes it refuses (a pure host query)."""
+    lib = _lib.load()
+    n = C.c_int64(0)
+    _lib.check(lib.hat_u8_metrics_workspace_bytes(B, h, w, crop_border, u8_metrics_flags(y_channel=y_channel, bgr=bgr, psnr=psnr, ssim=ssim),
+                                                  C.byref(n)), "hat_u8_metrics_workspace_bytes")
+    return n.value
+
+
+def u8_metrics(a, b, sums, workspace, *, crop_border: int, y_channel: bool, bgr: bool = False, psnr: bool = True, ssim: bool = True):
+    """a, b (B, h, w, 3) uint8 (rows may be pitched) -> sums (B, 4) float64: the sum of squared differences and the SSIM-map
+    sums of channel 0, 1, 2 (hat_u8_metrics; metrics_device.finalize turns them into PSNR / SSIM).  workspace: a uint8
+    device tensor of at least u8_metrics_workspace_bytes(...) bytes."""
+    lib = _lib.load()
+    for t in (a, b):
+        if t.dim() != 4 or t.shape[3] != 3 or t.dtype != torch.uint8 or t.stride(-1) != 1 or t.stride(-2) != 3:
+            raise RuntimeError("u8_metrics needs (B,h,w,3) uint8 frames with interleaved pixels")
+        if not t.is_cuda:
+            raise RuntimeError("HAT HIP ops need device tensors (no CPU path exists)")
+    if a.shape != b.shape or a.device != b.device:
+        raise RuntimeError(f"u8_metrics needs two frames of one shape on one device, got {tuple(a.shape)} on {a.device} and "
+                           f"{tuple(b.shape)} on {b.device}")
+    B, h, w, _ = a.shape
+    if sums.dtype != torch.float64 or tuple(sums.shape) != (B, 4) or sums.device != a.device or workspace.device != a.device:
+        raise RuntimeError(f"u8_metrics needs a (B,4) float64 destination and a workspace on {a.device}")
+    need = u8_metrics_workspace_bytes(B, h, w, crop_border=crop_border, y_channel=y_channel, bgr=bgr, psnr=psnr, ssim=ssim)
+    if workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.data_ptr() % 8:
+        raise RuntimeError(f"u8_metrics needs an 8-byte aligned uint8 workspace of at least {need} bytes")
+    flags = u8_metrics_flags(y_channel=y_channel, bgr=bgr, psnr=psnr, ssim=ssim)
+    nch = 1 if y_channel else 3
+    hc, wc = h - 2 * crop_border, w - 2 * crop_border
+    flops = 2.0 * B * nch * (hc - 10) * (wc - 10) * 5 * 22 if ssim else 0.0
+    _timed(f"u8_metrics_kernel<{'y' if y_channel else 'rgb'}>", flops, lambda: _lib.check(
+        lib.hat_u8_metrics(a.data_ptr(), a.stride(1), a.stride(0), b.data_ptr(), b.stride(1), b.stride(0), B, h, w, crop_border, flags,
+                           _ptr(sums), _ptr(workspace), _stream()), "hat_u8_metrics"),
+        tag=f"u8 metrics {h}x{w} crop {crop_border}{' psnr' if psnr else ''}{' ssim' if ssim else ''}", nbytes=2.0 * B * h * w * 3)
+
+
 def cab_squeeze_units(H: int, W: int) -> int:
     lib = _lib.load()
     rows, units = C.c_int32(0), C.c_int32(0)
