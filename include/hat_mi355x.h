@@ -281,6 +281,10 @@ int hat_ocab_qkv(const HatMlpDesc* d, void* stream);
  *                         place of the logit where kb = -inf; `pad` = ceil((wse - ws) / 2), HATX's unfold padding.
  * ldsal < 0 (dtype HAT_BF16 only): `sal` is an FP32 map of row stride -ldsal — the saliency head's last conv writes its fp32
  * accumulators (HAT_O_NHWC_F32) so that the keys are ranked on unrounded scores; kv stays bf16.
+ * hat_ocab_keybias writes 0 into the dead tail [wse*wse, round_up(wse*wse, 16)) of a row; hat_ocab_attention_kb ignores what
+ * is there.  A key's rank is the number of keys that compare greater (or equal, at a lower index), so a NaN score — a NaN in
+ * the saliency map or in k — compares with nothing, ranks 0 and is kept (with kb = NaN under a focus head), and more than k_keep keys of that window
+ * survive: the maps must be finite (the engine's are; nothing here checks).
  */
 int hat_ocab_keybias(const void* sal, int32_t ldsal, const void* kv, int32_t ldkv, float* kb, int32_t B, int32_t H, int32_t W,
                      int32_t C, int32_t ws, int32_t wse, int32_t pad, int32_t k_keep, int32_t dtype, void* stream);
@@ -306,8 +310,9 @@ int hat_sgfn_gate(const void* u, const float* wdw, const float* bdw, void* out, 
  * negative-index wraparound, hat_arch.py:378, is applied when the table is packed).
  * out: (B,H,W,ldo) T in window_reverse order (:387-388).
  * Key windows: wse = 24 and 12 (window 16 / 8, overlap 0.5; padding (wse - ws) / 2 on every side) and the odd 25 and 13
- * (HATX: overlap 0.6 / 0.7, padding ceil((wse - ws) / 2), hatx_arch.py:303-305); HAT_EUNSUPPORTED for others, HAT_ELDS when
- * K and V of one key window do not fit the LDS (fp32, wse 25, head_dim 30).
+ * (HATX: overlap 0.6 / 0.7, padding ceil((wse - ws) / 2), hatx_arch.py:303-305); HAT_EUNSUPPORTED for others.  When
+ * K and V of one key window do not fit the LDS (fp32, wse 25, head_dim 30) a 16 x 16 window streams its keys through the LDS
+ * in chunks (same arithmetic, same key order); HAT_ELDS for other window sizes in that case.
  */
 int hat_ocab_attention(const void* q, const void* kv, const float* bias_rot, void* out, int32_t B, int32_t H,
                        int32_t W, int32_t C, int32_t heads, int32_t ws, int32_t wse, int32_t ldq,

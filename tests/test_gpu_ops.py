@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 from oracle import hat_oracle as O
 from super_resolution_amd import synth
+from helpers import _r8, check, q, rnd, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -27,40 +28,6 @@ def _dev():
 def _ops():
     from super_resolution_amd import ops
     return ops
-
-
-def _r8(x):
-    return (x + 7) // 8 * 8
-
-
-def to_dev(x_bhwc: torch.Tensor, ld: int, tdt, dev):
-    """(B,H,W,C) float -> device (B, H*W, ld) of dtype tdt with zero pad channels."""
-    b, h, w, c = x_bhwc.shape
-    out = torch.zeros(b, h * w, ld, dtype=tdt, device=dev)
-    out[:, :, :c] = x_bhwc.reshape(b, h * w, c).to(dev).to(tdt)
-    return out
-
-
-def check(got: torch.Tensor, ref: torch.Tensor, dtype: str, what: str, f32_tol=2e-5):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert torch.isfinite(got).all(), what + ": non-finite output"
-    scale = max(float(ref.abs().max()), 1e-6)
-    err = float((got - ref).abs().max())
-    rel = float((got - ref).norm() / max(float(ref.norm()), 1e-12))
-    if dtype == "f32":
-        assert err <= f32_tol * max(scale, 1.0), f"{what}: max-abs {err:.3e} (scale {scale:.3g}, rel {rel:.3e})"
-    else:
-        assert rel <= 1.2e-2 and err <= 6e-2 * max(scale, 1.0), f"{what}: rel {rel:.3e} max-abs {err:.3e} (scale {scale:.3g})"
-
-
-def rnd(key, shape, std=1.0):
-    return synth.normal(11, key, shape, std=std)
-
-
-def q(x, dtype):
-    """Round inputs the way the kernel's storage type does, so the oracle sees the same operands."""
-    return x.to(torch.bfloat16).to(torch.float32) if dtype == "bf16" else x
 
 
 # ------------------------------------------------------------------------------------------------
