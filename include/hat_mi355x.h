@@ -390,6 +390,49 @@ int hat_conv3x3_to_u8(const void* x, const void* wpk, const float* bias, uint8_t
                       const float* mean4, int32_t bgr, int32_t dtype, void* stream);
 
 /*
+ * The 4:2:0 frame boundary: 8-bit YCbCr frames as decoders and encoders exchange them (NV12, NV21, I420) in and out.  The
+ * definition, operation by operation, is super_resolution_amd/yuv.py; the results equal it bit for bit (every product and
+ * sum is rounded to fp32 on its own: no fused multiply-add).  A frame block is
+ *     y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride
+ * — the Y plane (h rows of w bytes, rows y_pitch >= w bytes apart, samples y_bstride bytes apart) and the (h/2, w/2) Cb and
+ * Cr samples behind two pointers, rows c_pitch bytes apart, samples of a row c_step bytes apart, samples of the batch
+ * c_bstride apart: c_step = 1 for planar chroma (I420), c_step = 2 for interleaved chroma (NV12: cr = cb + 1; NV21: cb = cr +
+ * 1), c_pitch >= c_step * w / 2.  The b-strides are ignored for B == 1.  h and w must be even.
+ * to_rgb12 / from_rgb12: HOST pointers to 12 floats, a row-major 3 x 4 matrix passed to the kernel by value
+ * (super_resolution_amd.yuv.csc(matrix, full_range) makes the pairs for BT.601 / BT.709, limited / full range):
+ *     to_rgb    rows R, G, B; columns Y, Cb - 128, Cr - 128, offset   (byte units in, [0, 1] out; the luma offset is part of
+ *               the offset column, which is added last)
+ *     from_rgb  rows Y, Cb, Cr; columns R, G, B, offset               ([0, 1] in, byte units out)
+ *
+ * hat_yuv420_to_planes   -> dst: (B,3,Hp,Wp) fp32 RGB planes.  Pixel (y, x) reads source pixel (y', x') by hat_u8_to_planes'
+ *                    reflection rule and the chroma sample (y' >> 1, x' >> 1) (nearest: a chroma sample covers its 2 x 2
+ *                    block); dst = min(max(((m0 Y + m1 (Cb - 128)) + m2 (Cr - 128)) + m3, 0), 1) per row of to_rgb.
+ *                    Refuses what hat_u8_to_planes refuses, odd h or w, short pitches and c_step outside {1, 2}.
+ * hat_planes_to_yuv420   src: (B,3,Hs,Ws) fp32 planes -> the top-left h_out x w_out pixels (even, <= Hs, Ws) as a frame
+ *                    block.  r, g, b are clamped to [0, 1]; Y = ((k00 r + k01 g) + k02 b) + k03 per pixel; cb = (k10 r + k11
+ *                    g) + k12 b per pixel and Cb = ((cb00 + cb01) + (cb10 + cb11)) * 0.25 + k13 per 2 x 2 block (box), Cr
+ *                    likewise; a byte is the value clamped to [0, 255] and rounded half to even.  The general output
+ *                    path: any width, any engine dtype.
+ * hat_conv3x3_to_yuv420  conv_last with that conversion as its epilogue: hat_conv3x3_to_u8's arguments with the destination
+ *                    replaced by a frame block, the same kernel and fp32 value; neither the fp32 image nor an RGB byte
+ *                    image is written.  Bit-identical to hat_planes_to_yuv420 of hat_conv3x3_to_planes.  Its row bands
+ *                    are an even number of rows high (a 2 x 2 block never straddles two bands).
+ * Centre-sited chroma (JPEG, MPEG-1, Y4M C420jpeg) is what nearest-up / box-down means; left-sited sources (MPEG-2, H.264)
+ * are accepted and treated the same.  All three check their arguments before they touch the device; none allocates or
+ * synchronises.
+ */
+int hat_yuv420_to_planes(const uint8_t* y, int64_t y_pitch, int64_t y_bstride, const uint8_t* cb, const uint8_t* cr, int64_t c_pitch,
+                         int32_t c_step, int64_t c_bstride, float* dst, int32_t B, int32_t h, int32_t w, int32_t Hp, int32_t Wp,
+                         const float* to_rgb12, void* stream);
+int hat_planes_to_yuv420(const float* src, int32_t B, int32_t Hs, int32_t Ws, uint8_t* y, int64_t y_pitch, int64_t y_bstride,
+                         uint8_t* cb, uint8_t* cr, int64_t c_pitch, int32_t c_step, int64_t c_bstride, int32_t h_out, int32_t w_out,
+                         const float* from_rgb12, void* stream);
+int hat_conv3x3_to_yuv420(const void* x, const void* wpk, const float* bias, uint8_t* y, int64_t y_pitch, int64_t y_bstride, uint8_t* cb,
+                          uint8_t* cr, int64_t c_pitch, int32_t c_step, int64_t c_bstride, int32_t B, int32_t H, int32_t W, int32_t C,
+                          int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, const float* mean4, const float* from_rgb12,
+                          int32_t dtype, void* stream);
+
+/*
  * PSNR / SSIM of two 8-bit frames on the device, with the definitions of the reference's validation loop (basicsr
  * metrics/psnr_ssim.py calculate_psnr / calculate_ssim / _ssim, metrics/metric_util.py to_y_channel).  a, b: (B,h,w,3) uint8
  * with row pitches >= 3 w bytes and sample strides in bytes (ignored for B == 1), as hat_u8_to_planes takes them.
@@ -574,6 +617,12 @@ int hat_hab_tail3(const HatHabTailDesc* d, void* stream);
  *                     bit-identical to HAT.forward_u8 on a frame that pads to (H, W).  hat_plan_forward is unaffected.
  *                     Returns 0, a negative HAT_E* for a refused argument, or — as hat_plan_load does — the positive
  *                     hipError_t of a failed hipMalloc / launch.
+ *   hat_plan_forward_yuv420  the same forward from and to 4:2:0 frames: a source frame block of (B, h, w) and a destination
+ *                     frame block of (B, scale*h, scale*w) (see "The 4:2:0 frame boundary"), h and w even, with the size rules
+ *                     of hat_plan_forward_u8.  It stages with hat_yuv420_to_planes, replays, and ends in
+ *                     hat_conv3x3_to_yuv420 (recorded arguments) or, where the plan does not end in hat_conv3x3_to_planes,
+ *                     in hat_planes_to_yuv420 of an fp32 staging image.  The staging buffers are the ones
+ *                     hat_plan_forward_u8 uses.  Bit-identical to HAT.forward_yuv420; same return values.
  */
 typedef struct hat_plan hat_plan;
 int hat_plan_load(const char* path, hat_plan** out);
@@ -582,6 +631,10 @@ int hat_plan_forward(const hat_plan* plan, const float* x, float* y, void* strea
 void hat_plan_free(hat_plan* plan);
 int hat_plan_forward_u8(const hat_plan* plan, const uint8_t* src, int64_t src_pitch, int32_t h, int32_t w, uint8_t* dst,
                         int64_t dst_pitch, int32_t flags, void* stream);
+int hat_plan_forward_yuv420(const hat_plan* plan, const uint8_t* src_y, int64_t src_y_pitch, int64_t src_y_bstride, const uint8_t* src_cb,
+                            const uint8_t* src_cr, int64_t src_c_pitch, int32_t src_c_step, int64_t src_c_bstride, int32_t h, int32_t w,
+                            uint8_t* dst_y, int64_t dst_y_pitch, int64_t dst_y_bstride, uint8_t* dst_cb, uint8_t* dst_cr, int64_t dst_c_pitch,
+                            int32_t dst_c_step, int64_t dst_c_bstride, const float* to_rgb12, const float* from_rgb12, void* stream);
 
 /*
  * Per-channel sums of a channel-last map over the pixel rectangle rows [r0, r1) x columns [c0, c1):

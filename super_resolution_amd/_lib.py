@@ -94,6 +94,8 @@ class HatAggrCabDesc(C.Structure):
     _fields_ = [("lin", HatConvDesc), ("c1", C.c_void_p), ("wf", C.c_void_p), ("bias_b", C.c_void_p)]
 
 
+_YUV_BLOCK = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]   # a 4:2:0 frame block
+
 # name -> (restype, argtypes); every symbol declared in include/hat_mi355x.h
 SIGNATURES = {
     "hat_abi_version": (C.c_int, []),
@@ -155,6 +157,12 @@ SIGNATURES = {
                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "hat_plan_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                       C.c_void_p]),
+    # frame block: y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride
+    "hat_yuv420_to_planes": (C.c_int, _YUV_BLOCK + [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "hat_planes_to_yuv420": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + _YUV_BLOCK + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "hat_conv3x3_to_yuv420": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + _YUV_BLOCK + [C.c_int32] * 7 + [C.c_float, C.c_void_p, C.c_void_p,
+                                                                                                      C.c_int32, C.c_void_p]),
+    "hat_plan_forward_yuv420": (C.c_int, [C.c_void_p] + _YUV_BLOCK + [C.c_int32, C.c_int32] + _YUV_BLOCK + [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hat_u8_metrics_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "hat_u8_metrics": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "hat_common.h"
+#include "hat_yuv_check.h"
 
 __device__ __attribute__((aligned(16))) unsigned hat_cabsq_zero_page[80] = {};   // 160 bf16 channels of zeros
 
@@ -25,8 +26,14 @@ namespace {
 // NCHW = true: (acc + bias) * out_scale + mean[ch] -> (B,nst,H,W) fp32 planes (conv_last, hat_arch.py:856-858).
 // Epi = SweepEpiU8 (with NCHW): that same fp32 value, by the same expression, converted as tensor2img converts it and
 // stored as interleaved bytes (B,h_out,w_out,3) with a row pitch; rows and columns outside the crop are not stored.
+// Epi = SweepEpiYUV (with NCHW): that same fp32 value converted to 4:2:0 YCbCr (hat_rgb_to_ycc): a Y byte per pixel into outv,
+// a Cb and a Cr byte per 2 x 2 block into cb / cr.  The bands of this instantiation start on even rows.
 struct SweepEpi { float out_scale; float mean[4]; int nst; };
 struct SweepEpiU8 { float out_scale; float mean[4]; int h_out, w_out, bgr; long long pitch, bstride; };
+struct SweepEpiYUV {
+    float out_scale; float mean[4]; int h_out, w_out, c_step; long long pitch, bstride, c_pitch, c_bstride;
+    uint8_t* cb; uint8_t* cr; HatCsc k;
+};
 
 template <int KS, bool NCHW, typename Epi = SweepEpi>
 __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wpk,
@@ -34,7 +41,8 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
                                                              float* __restrict__ colsum, int H, int W, int C, int ldx,
                                                              int rows, int strips, int units, Epi epi) {
     constexpr bool U8 = std::is_same<Epi, SweepEpiU8>::value;
-    static_assert(!U8 || NCHW, "the byte epilogue converts the conv_last value");
+    constexpr bool YUV = std::is_same<Epi, SweepEpiYUV>::value;
+    static_assert((!U8 && !YUV) || NCHW, "the byte epilogues convert the conv_last value");
     using M = MT<bf16_t>;
     using frag_t = M::frag_t;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, c16 = lane & 15;
@@ -47,8 +55,10 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
     bf16_t* ob = reinterpret_cast<bf16_t*>(outv) + (size_t)b * H * W * 8;
     float* of = nullptr;
     uint8_t* o8 = nullptr;
-    if constexpr (U8) o8 = reinterpret_cast<uint8_t*>(outv) + (size_t)b * epi.bstride;
+    if constexpr (U8 || YUV) o8 = reinterpret_cast<uint8_t*>(outv) + (size_t)b * epi.bstride;
     else of = reinterpret_cast<float*>(outv) + (size_t)b * epi.nst * H * W;
+    // yuv epilogue: cb00 + cb01 and cr00 + cr01 of the even row wait here for the odd row (the lane of the even column)
+    [[maybe_unused]] float ctop_b = 0.f, ctop_r = 0.f;
 
     frag_t A[6][KS];   // [2 * kx + (0: T1, 1: T2)][k-step], fragment-packed on the host: one coalesced 1 KB load each
 #pragma unroll
@@ -117,7 +127,29 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
         f32x4 v;
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = S2[i] + __shfl_xor(S0[i], 32);
-        if (y >= y0 && y < y1 && g < 2 && oin) {
+        if constexpr (YUV) {
+            // Lane group g = 0 holds R, G, B of pixel (y, xx).  A strip starts at the even column 14 strip = lane c16 = 1, so the
+            // pixels of a 2 x 2 block's row sit in lanes (c16, c16 + 1), c16 odd: one row_shl:1 move per chroma component brings
+            // the right pixel's term to the left pixel's lane.  Every lane runs the arithmetic (the move is not under the store's
+            // condition); only lanes that own a pixel inside the crop store.  Y: one byte per lane and row, a 14-byte span per
+            // strip; Cb, Cr: on odd rows, the lane of the even column, 7 samples per strip.
+            const f32x4 vb = v + bs;
+            float Yv, cbv, crv;
+            hat_rgb_to_ycc(epi.k, vb[0] * epi.out_scale + epi.mean[0], vb[1] * epi.out_scale + epi.mean[1], vb[2] * epi.out_scale + epi.mean[2],
+                           Yv, cbv, crv);
+            const float cbn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cbv), 0x101, 0xf, 0xf, false));
+            const float crn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, crv), 0x101, 0xf, 0xf, false));
+            const float cbs = hat_add_rn(cbv, cbn), crs = hat_add_rn(crv, crn);
+            if (y >= y0 && y < y1 && g == 0 && oin && y < epi.h_out && xx < epi.w_out) {
+                o8[(size_t)y * epi.pitch + xx] = (uint8_t)hat_ycc_byte(Yv);
+                if ((y & 1) && !(xx & 1)) {
+                    const size_t co = (size_t)b * epi.c_bstride + (size_t)(y >> 1) * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
+                    epi.cb[co] = (uint8_t)hat_chroma_byte(ctop_b, cbs, epi.k.m[7]);
+                    epi.cr[co] = (uint8_t)hat_chroma_byte(ctop_r, crs, epi.k.m[11]);
+                }
+            }
+            if (!(y & 1)) { ctop_b = cbs; ctop_r = crs; }
+        } else if (y >= y0 && y < y1 && g < 2 && oin) {
             v += bs;
             if constexpr (U8) {
                 // lane group g = 0 holds R, G, B of pixel (y, xx): a strip row is 42 bytes from byte 42 strip of the image
@@ -164,13 +196,14 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
 
 }  // namespace
 
-static int sweep_units(int H, int W, int slots, int* rows_out, int* units_out) {
+static int sweep_units(int H, int W, int slots, int* rows_out, int* units_out, bool even_rows = false) {
     const int strips = (W + 13) / 14;   // a strip is 16 loaded columns = 14 output columns + one halo column each side
     // one round of wave units on the chip's wave slots when the frame allows it; never fewer than 8 rows per band (2 halo rows each)
     int bands = slots / strips;
     bands = bands < 1 ? 1 : bands;
     int rows = (H + bands - 1) / bands;
     rows = rows < 8 ? 8 : rows;
+    if (even_rows) rows += rows & 1;    // the yuv epilogue pairs rows (y, y + 1), y even, inside one band
     *rows_out = rows;
     *units_out = strips * ((H + rows - 1) / rows);
     return 0;
@@ -230,5 +263,25 @@ extern "C" int hat_conv3x3_to_u8(const void* x, const void* wpk, const float* bi
                reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(wpk), bias, dst, nullptr, H, W, C, ldx, rows, (W + 13) / 14, units,
                SweepEpiU8{out_scale, {mean4[0], mean4[1], mean4[2], mean4[3]}, h_out, w_out, bgr ? 1 : 0, (long long)dst_pitch,
                           (long long)dst_bstride});
+    return hat_check_launch();
+}
+
+extern "C" int hat_conv3x3_to_yuv420(const void* x, const void* wpk, const float* bias, uint8_t* y, int64_t y_pitch, int64_t y_bstride,
+                                     uint8_t* cb, uint8_t* cr, int64_t c_pitch, int32_t c_step, int64_t c_bstride, int32_t B, int32_t H,
+                                     int32_t W, int32_t C, int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, const float* mean4,
+                                     const float* from_rgb12, int32_t dtype, void* stream) {
+    if (!x || !wpk || !bias || !y || !cb || !cr || !mean4 || !from_rgb12 || H < 1 || W < 16 || W % 16 || h_out > H || w_out > W) return HAT_EINVAL;
+    if (!hat_yuv_block_ok(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out)) return HAT_EINVAL;
+    if (dtype != HAT_BF16) return HAT_EUNSUPPORTED;
+    if (C != 64 || ldx < C || ldx % 8) return HAT_EUNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpk)) % 16) return HAT_EINVAL;
+    int rows = 0, units = 0;
+    sweep_units(H, W, 3072, &rows, &units, true);           // hat_conv3x3_to_planes' geometry with the band height rounded up to even
+    SweepEpiYUV epi{out_scale, {mean4[0], mean4[1], mean4[2], mean4[3]}, h_out, w_out, c_step, (long long)y_pitch, (long long)y_bstride,
+                    (long long)c_pitch, (long long)c_bstride, cb, cr, {}};
+    for (int i = 0; i < 12; ++i) epi.k.m[i] = from_rgb12[i];
+    HAT_LAUNCH((cab_squeeze_kernel<2, true, SweepEpiYUV>), dim3((units + 3) / 4, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+               reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(wpk), bias, y, nullptr, H, W, C, ldx, rows, (W + 13) / 14, units,
+               epi);
     return hat_check_launch();
 }

@@ -258,6 +258,50 @@ struct HatU8Table {
 };
 static __device__ const HatU8Table hat_u8_unit{};
 
+// 4:2:0 YCbCr <-> RGB (definition: super_resolution_amd/yuv.py).  A 3 x 4 matrix travels by value in the kernel arguments.
+// Every product and sum is rounded to fp32 on its own — contraction is off inside these functions — so that numpy float32
+// arithmetic reproduces them bit for bit; every route (hat_yuv.hip's two kernels, conv_last's yuv epilogue) calls these.
+struct HatCsc { float m[12]; };
+
+// bytes Y, Cb, Cr -> r, g, b in [0, 1]: rows R, G, B; columns Y, Cb - 128, Cr - 128, offset (added last)
+__device__ __forceinline__ void hat_ycc_to_rgb(const HatCsc& k, unsigned Y, unsigned Cb, unsigned Cr, float (&rgb)[3]) {
+#pragma clang fp contract(off)
+    const float y = (float)Y, cb = (float)Cb - 128.0f, cr = (float)Cr - 128.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float v = ((k.m[4 * c] * y + k.m[4 * c + 1] * cb) + k.m[4 * c + 2] * cr) + k.m[4 * c + 3];
+        rgb[c] = fminf(fmaxf(v, 0.f), 1.f);
+    }
+}
+
+// the float path's r, g, b of one pixel -> Y (with its offset) and the pixel's cb, cr terms (without: the offset joins
+// after the 2 x 2 average); rows Y, Cb, Cr; columns R, G, B, offset
+__device__ __forceinline__ void hat_rgb_to_ycc(const HatCsc& k, float r, float g, float b, float& Y, float& cb, float& cr) {
+#pragma clang fp contract(off)
+    r = fminf(fmaxf(r, 0.f), 1.f);
+    g = fminf(fmaxf(g, 0.f), 1.f);
+    b = fminf(fmaxf(b, 0.f), 1.f);
+    Y = ((k.m[0] * r + k.m[1] * g) + k.m[2] * b) + k.m[3];
+    cb = (k.m[4] * r + k.m[5] * g) + k.m[6] * b;
+    cr = (k.m[8] * r + k.m[9] * g) + k.m[10] * b;
+}
+
+// a value in byte units -> the byte: clamp to [0, 255], round half to even
+__device__ __forceinline__ unsigned hat_ycc_byte(float v) { return (unsigned)(int)__builtin_rintf(fminf(fmaxf(v, 0.f), 255.f)); }
+
+// the chroma byte of a 2 x 2 block from its two row sums (left + right each): (top + bottom) * 0.25 + offset
+__device__ __forceinline__ unsigned hat_chroma_byte(float top, float bottom, float offset) {
+#pragma clang fp contract(off)
+    const float s = top + bottom;
+    const float q = s * 0.25f;
+    return hat_ycc_byte(q + offset);
+}
+
+__device__ __forceinline__ float hat_add_rn(float a, float b) {   // a sum that stays a sum whatever surrounds the call
+#pragma clang fp contract(off)
+    return a + b;
+}
+
 #define HAT_LAUNCH(...)                      \
     do {                                     \
         (void)hipGetLastError();             \

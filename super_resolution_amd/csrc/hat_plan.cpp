@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/hat_mi355x.h"
+#include "hat_yuv_check.h"
 
 namespace {
 
@@ -360,4 +361,45 @@ extern "C" int hat_plan_forward_u8(const hat_plan* p, const uint8_t* src, int64_
     Resolved r{p, &p->calls.back(), p->stage_in, nullptr, stream, {}};
     return hat_conv3x3_to_u8(r.P(0), r.P(1), (const float*)r.P(2), dst, dst_pitch, dst_pitch * ho, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8),
                              ho, wo, r.F(10), (const float*)r.P(11), bgr, r.I(12), stream);
+}
+
+extern "C" int hat_plan_forward_yuv420(const hat_plan* p, const uint8_t* sy, int64_t sy_pitch, int64_t sy_bstride, const uint8_t* scb,
+                                       const uint8_t* scr, int64_t sc_pitch, int32_t sc_step, int64_t sc_bstride, int32_t h, int32_t w,
+                                       uint8_t* dy, int64_t dy_pitch, int64_t dy_bstride, uint8_t* dcb, uint8_t* dcr, int64_t dc_pitch,
+                                       int32_t dc_step, int64_t dc_bstride, const float* to_rgb12, const float* from_rgb12, void* stream) {
+    if (!p || !sy || !scb || !scr || !dy || !dcb || !dcr || !to_rgb12 || !from_rgb12 || h < 2 || w < 2 || (h & 1) || (w & 1)) return HAT_EINVAL;
+    if ((sc_step != 1 && sc_step != 2) || (dc_step != 1 && dc_step != 2) || sy_pitch < w || sc_pitch < (int64_t)sc_step * (w / 2)) return HAT_EINVAL;
+    const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4];
+    if (p->dims[1] != 3 || p->dims[5] != 3) return HAT_EUNSUPPORTED;   // 4:2:0 frames become three-channel images
+    if (h > H || w > W || H - h >= h || W - w >= w) return HAT_EINVAL;
+    // both blocks in full before anything is enqueued (the kernels' own checks would refuse the destination only after the replay)
+    if (!hat_yuv_block_ok(sy_pitch, sy_bstride, sc_pitch, sc_step, sc_bstride, B, h, w) ||
+        !hat_yuv_block_ok(dy_pitch, dy_bstride, dc_pitch, dc_step, dc_bstride, B, (int64_t)s * h, (int64_t)s * w))
+        return HAT_EINVAL;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != p->device) return HAT_EINVAL;
+    const bool fused = ends_in_planes(p);
+    if (!p->stage_in) {
+        const hipError_t e = hipMalloc((void**)&p->stage_in, (size_t)B * 3 * H * W * sizeof(float));
+        if (e != hipSuccess) { p->stage_in = nullptr; return (int)e; }
+    }
+    if (!fused && !p->stage_out) {
+        const hipError_t e = hipMalloc((void**)&p->stage_out, (size_t)B * 3 * s * H * s * W * sizeof(float));
+        if (e != hipSuccess) { p->stage_out = nullptr; return (int)e; }
+    }
+    const int ho = s * h, wo = s * w;
+    int rc = hat_yuv420_to_planes(sy, sy_pitch, sy_bstride, scb, scr, sc_pitch, sc_step, sc_bstride, p->stage_in, B, h, w, H, W, to_rgb12, stream);
+    if (rc) return rc;
+    const size_t n = p->calls.size() - (fused ? 1 : 0);
+    for (size_t k = 0; k < n; ++k) {
+        Resolved r{p, &p->calls[k], p->stage_in, p->stage_out, stream, {}};
+        rc = dispatch(r);
+        if (rc) return rc;
+    }
+    if (!fused)
+        return hat_planes_to_yuv420(p->stage_out, B, s * H, s * W, dy, dy_pitch, dy_bstride, dcb, dcr, dc_pitch, dc_step, dc_bstride, ho, wo,
+                                    from_rgb12, stream);
+    Resolved r{p, &p->calls.back(), p->stage_in, nullptr, stream, {}};
+    return hat_conv3x3_to_yuv420(r.P(0), r.P(1), (const float*)r.P(2), dy, dy_pitch, dy_bstride, dcb, dcr, dc_pitch, dc_step, dc_bstride, r.I(4),
+                                 r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10), (const float*)r.P(11), from_rgb12, r.I(12), stream);
 }

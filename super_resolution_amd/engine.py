@@ -215,6 +215,7 @@ class HATEngine:
         self._ws_max_bytes = int(float(os.environ.get("HAT_WS_CACHE_GIB", "96")) * 2 ** 30)
         self.ws_allocations = self.fp16_fallbacks = 0
         self.u8_fused_calls = self.u8_planes_calls = 0   # 8-bit forwards that ended in hat_conv3x3_to_u8 / in hat_planes_to_u8
+        self.yuv_fused_calls = self.yuv_planes_calls = 0   # 4:2:0 forwards that ended in hat_conv3x3_to_yuv420 / in hat_planes_to_yuv420
         self.use_n16 = not self.opt.no_n16
         # FP16 residual rows between the fused HAB tails of a residual group (bf16 path, embed_dim 144; HAT_NO_T16=1: fp32 everywhere)
         self.t16 = not self.opt.no_t16 and self.opt.emu_t16 is None and self.dtype == ops.HAT_BF16 and self.C == 144
@@ -667,28 +668,66 @@ class HATEngine:
             ho, wo = h * self.scale, w * self.scale
             return self._forward(ws["x_u8"], u8=(ho, wo, bool(bgr), self._u8_out(out, (B, ho, wo, 3))))
 
+    def forward_yuv420(self, frame: torch.Tensor, *, fmt: str = "nv12", to_rgb, from_rgb, out=None) -> torch.Tensor:
+        """(B,3h/2,w) uint8 device frames in the layout `fmt` (yuv.py), any even size the reflection allows -> (B,3sh/2,sw) uint8
+        in the same layout: hat_yuv420_to_planes into this shape's workspace, the forward, the crop and the conversion back (in
+        conv_last's epilogue or hat_planes_to_yuv420).  to_rgb / from_rgb: yuv.csc's matrices.  out: the caller's result tensor."""
+        self._check_u8()
+        if not isinstance(frame, torch.Tensor) or frame.dtype != torch.uint8:
+            raise TypeError(f"expected (B,3h/2,w) uint8 frames, got {getattr(frame, 'dtype', type(frame))}")
+        if frame.dim() != 3:
+            raise RuntimeError(f"expected (B,3h/2,w) uint8 frames, got {tuple(frame.shape)}")
+        if not frame.is_cuda or frame.device != self.dev:
+            raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
+        from . import yuv as _yuv
+        h, w = _yuv.frame_size(frame.shape)
+        B, s = frame.shape[0], self.scale
+        Hp, Wp = -(-h // self.ws) * self.ws, -(-w // self.ws) * self.ws
+        if Hp - h >= h or Wp - w >= w:
+            raise RuntimeError(f"a {h}x{w} frame cannot be reflect-padded to {Hp}x{Wp} (window_size {self.ws}): the padding must be "
+                               f"smaller than the frame")
+        if frame.stride(2) != 1 or frame.stride(1) != w:
+            frame = frame.contiguous()
+        shape = (B,) + _yuv.frame_shape(s * h, s * w)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.dev)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != self.dev \
+                or out.stride(2) != 1 or out.stride(1) != s * w:
+            raise RuntimeError(f"out must be a {shape} uint8 tensor on {self.dev} with packed rows, got "
+                               f"{tuple(out.shape)} {out.dtype} on {out.device}")
+        src, dst = ops.yuv420_views(frame, fmt), ops.yuv420_views(out, fmt)
+        with self._lock, torch.cuda.device(self.dev):
+            ws = self._workspace(B, Hp, Wp)
+            if "x_u8" not in ws:     # the padded fp32 input of this shape, shared with forward_u8
+                ws["x_u8"] = torch.zeros(B, 3, Hp, Wp, dtype=torch.float32, device=self.dev)
+                ws["bytes"] += ws["x_u8"].numel() * 4
+            ops.yuv420_to_planes(*src, ws["x_u8"], to_rgb)
+            self._forward(ws["x_u8"], yuv=(dst, from_rgb, out))
+        return out
+
     def ocab_only(self, t: torch.Tensor, group: int, H: int, W: int) -> torch.Tensor:
         """Run only the OCAB of residual group `group` on tokens t (B, H*W, C) fp32 -> (B, H*W, C) fp32 (used by the tests)."""
         x = torch.zeros(t.shape[0], self.cfg["in_chans"], H, W, device=self.dev)
         with self._lock, torch.cuda.device(self.dev):
             return self._forward(x, only_ocab=(t.to(self.dev, torch.float32).contiguous(), group))
 
-    def _forward(self, x: torch.Tensor, only_ocab=None, one_stream=None, u8=None) -> torch.Tensor:
-        gen = self._forward_gen(x, only_ocab=only_ocab, one_stream=one_stream, u8=u8)
+    def _forward(self, x: torch.Tensor, only_ocab=None, one_stream=None, u8=None, yuv=None) -> torch.Tensor:
+        gen = self._forward_gen(x, only_ocab=only_ocab, one_stream=one_stream, u8=u8, yuv=yuv)
         try:
             req = next(gen)
         except StopIteration as done:
             return done.value
         raise RuntimeError(f"the unsharded forward must not reach an exchange point (got {req[0]!r})")
 
-    def _forward_gen(self, x: torch.Tensor, only_ocab=None, band=None, one_stream=None, u8=None):
+    def _forward_gen(self, x: torch.Tensor, only_ocab=None, band=None, one_stream=None, u8=None, yuv=None):
         """The forward as a generator.  Unsharded (band=None) it never yields and returns the output.  For one ROW BAND of a
         sharded frame (band: tile_parallel.Band, x = the band's rows + ghost rows of the LR frame) it yields at
         every point where bands must exchange: ("halo", [(tensor, depth) ...]) — refresh `depth` ghost rows above and below
         from the neighbours that own them — and ("reduce", local, glob, n) — glob[:, :n] = sum over bands of local[:, :n] (the
         global average pools of ECA, hat_arch.py:69-73, and of the ESC dynamic kernel, esc_arch.py:96,121) — and returns the
         band's output rows (ghost rows included; the driver keeps the owned ones).
-        u8 = (h_out, w_out, bgr, out): the unsharded forward fills and returns out, (B,h_out,w_out,3) uint8 (forward_to_u8)."""
+        u8 = (h_out, w_out, bgr, out): the unsharded forward fills and returns out, (B,h_out,w_out,3) uint8 (forward_to_u8).
+        yuv = ((y, cb, cr) views, from_rgb, out): it fills the views of a 4:2:0 frame and returns out (forward_yuv420)."""
         if x.dim() != 4 or x.shape[1] != self.cfg["in_chans"]:
             raise RuntimeError(f"expected (B,{self.cfg['in_chans']},H,W), got {tuple(x.shape)}")
         B, _, H, W = x.shape
@@ -704,7 +743,11 @@ class HATEngine:
             w["tB"].copy_(t_in.reshape(B, H * W, self.C))
             f.t = w["tB"]
             return (yield from self._ocab(f, self.layers[gidx], as_conv_input=False)).clone()
-        if u8 is None:
+        if yuv is not None:
+            if band is not None or u8 is not None:
+                raise RuntimeError("the 4:2:0 output is the unsharded forward's, and it is one target of three")
+            y = yuv[2]
+        elif u8 is None:
             y = torch.empty(B, self.cfg["in_chans"], H * self.scale, W * self.scale, dtype=torch.float32, device=self.dev)
         else:
             if band is not None:
@@ -718,7 +761,7 @@ class HATEngine:
             tout = yield from self._ocab(f, G, as_conv_input=G.to_conv)
             yield from self._group_end(f, G, tout)
         yield from self._body_end(f)
-        self._upsample(f, y, u8)
+        self._upsample(f, y, u8, yuv)
         return y
 
     # ------------------------------------------------------------------------------------------ stage steps
@@ -1057,10 +1100,12 @@ class HATEngine:
         ops.conv(self.conv_after_body, w["n"], w["c2"], **f.geo, ldx=ldc, ldo=ldc, r1=w["f0"], ldr1=C)
         ops.conv(self.conv_before_up, w["c2"], w["fb"], **f.geo, ldx=ldc, ldo=64, act=ACT_LRELU)
 
-    def _upsample(self, f: _Fwd, y, u8=None):
+    def _upsample(self, f: _Fwd, y, u8=None, yuv=None):
         """conv + PixelShuffle per stage; conv_last ; / img_range + mean                     :593-605, :856-858
         u8 = (h_out, w_out, bgr, y): y is (B,h_out,w_out,3) uint8 — conv_last converts in its epilogue (hat_conv3x3_to_u8) where
-        the row-sweep kernel runs, else it writes fp32 planes as always and hat_planes_to_u8 converts and crops them."""
+        the row-sweep kernel runs, else it writes fp32 planes as always and hat_planes_to_u8 converts and crops them.
+        yuv = ((y, cb, cr), from_rgb, out): the third target, 4:2:0 views of `out`, by the same rule: hat_conv3x3_to_yuv420 where
+        the row-sweep kernel runs, else fp32 planes and hat_planes_to_yuv420."""
         src, h, wd, dt = f.w["fb"], f.H, f.W, f.dt
         for (pw, rr), dst in zip(self.ups, f.w["ups"]):
             ops.conv(pw, src, dst, B=f.B, H=h, W=wd, dtype=dt, ldx=64, ldo=64, out_mode=O_PIXSHUF_T, ps_r=rr)
@@ -1074,6 +1119,14 @@ class HATEngine:
                 self.u8_fused_calls += 1
                 return
             y8, y = y, torch.empty(f.B, 3, h, wd, dtype=torch.float32, device=self.dev)
+        if yuv is not None:
+            if self.u8_fused and wd % 16 == 0:
+                wpk, b8, _ = self.conv_last_sweep
+                ops.conv3x3_to_yuv420(src, wpk, b8, *yuv[0], B=f.B, H=h, W=wd, C_=64, ldx=64, out_scale=1.0 / r, mean=self._mean(),
+                                      from_rgb=yuv[1], dtype=dt)
+                self.yuv_fused_calls += 1
+                return
+            y = torch.empty(f.B, 3, h, wd, dtype=torch.float32, device=self.dev)
         if self.conv_last_sweep is not None and wd % 16 == 0:
             wpk, b8, nout = self.conv_last_sweep
             ops.conv3x3_to_planes(src, wpk, b8, y, B=f.B, H=h, W=wd, C_=64, ldx=64, n_out=nout, out_scale=1.0 / r, mean=self._mean(),
@@ -1084,3 +1137,6 @@ class HATEngine:
         if u8 is not None:
             ops.planes_to_u8(y, y8, bgr=u8[2])
             self.u8_planes_calls += 1
+        if yuv is not None:
+            ops.planes_to_yuv420(y, *yuv[0], yuv[1])
+            self.yuv_planes_calls += 1

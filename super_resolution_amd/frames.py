@@ -14,10 +14,19 @@ import numpy as np
 import torch
 
 
-def upscale_frames(net, frames, *, bgr: bool = False):
+PIXFMTS = ("rgb24", "nv12", "nv21", "i420")
+
+
+def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", matrix: str = "bt601", full_range: bool = False):
     """Generator: for every (h,w,3) uint8 array of `frames` (all of one size) yield the (s*h,s*w,3) uint8 array that
     `net.forward_u8` computes for it, in order.  `net`: a HAT / HATX module on a GPU, in eval mode.  The yielded array is
-    the caller's own (copied out of the pinned buffer).  An empty sequence yields nothing."""
+    the caller's own (copied out of the pinned buffer).  An empty sequence yields nothing.
+    pixfmt 'nv12' / 'nv21' / 'i420': the frames are (3h/2, w) uint8 arrays in that 4:2:0 layout (yuv.py), the yielded arrays
+    (3sh/2, sw) ones, computed by `net.forward_yuv420` with `matrix` and `full_range` (bgr does not apply).  Same slots,
+    same copy stream, same events: only the buffer shapes and the forward differ."""
+    if pixfmt not in PIXFMTS:
+        raise RuntimeError(f"unknown pixfmt {pixfmt!r}: one of {PIXFMTS}")
+    yuv420 = pixfmt != "rgb24"
     dev = next(net.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("upscale_frames needs the network on a GPU: the MI355X HIP path is the only path")
@@ -26,26 +35,36 @@ def upscale_frames(net, frames, *, bgr: bool = False):
     if first is None:
         return
     first = np.ascontiguousarray(first)
-    if first.ndim != 3 or first.shape[2] != 3 or first.dtype != np.uint8:
-        raise RuntimeError(f"expected (h,w,3) uint8 frames, got {first.shape} {first.dtype}")
-    h, w, _ = first.shape
     s = net.upscale
+    if yuv420:
+        from . import yuv as _yuv
+        if first.ndim != 2 or first.dtype != np.uint8:
+            raise RuntimeError(f"expected (3h/2,w) uint8 {pixfmt} frames, got {first.shape} {first.dtype}")
+        h, w = _yuv.frame_size(first.shape)
+        in_shape, out_shape, shape_text = first.shape, _yuv.frame_shape(s * h, s * w), f"({3 * h // 2},{w})"
+        forward = lambda src, dst: net.forward_yuv420(src, fmt=pixfmt, matrix=matrix, full_range=full_range, out=dst)
+    else:
+        if first.ndim != 3 or first.shape[2] != 3 or first.dtype != np.uint8:
+            raise RuntimeError(f"expected (h,w,3) uint8 frames, got {first.shape} {first.dtype}")
+        h, w, _ = first.shape
+        in_shape, out_shape, shape_text = (h, w, 3), (s * h, s * w, 3), f"({h},{w},3)"
+        forward = lambda src, dst: net.forward_u8(src, bgr=bgr, out=dst)
     # Nothing of the device state stays entered across a yield: the buffers and the copy stream are made once, and every step
     # enters the device and takes the stream that is current THEN, so a caller may switch device or stream between frames.
     with torch.cuda.device(dev):
         copy = torch.cuda.Stream(device=dev)
-        hin = [torch.empty(h, w, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        hout = [torch.empty(s * h, s * w, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        din = [torch.empty(1, h, w, 3, dtype=torch.uint8, device=dev) for _ in range(2)]
-        dout = [torch.empty(1, s * h, s * w, 3, dtype=torch.uint8, device=dev) for _ in range(2)]
+        hin = [torch.empty(in_shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        hout = [torch.empty(out_shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        din = [torch.empty((1,) + tuple(in_shape), dtype=torch.uint8, device=dev) for _ in range(2)]
+        dout = [torch.empty((1,) + tuple(out_shape), dtype=torch.uint8, device=dev) for _ in range(2)]
         ev = lambda: torch.cuda.Event()
         up, done, down = [ev(), ev()], [ev(), ev()], [ev(), ev()]
 
     def upload(k, a):
         """frame -> pinned slot k -> device slot k, on the copy stream (after the compute that last read the slot)."""
         a = np.ascontiguousarray(a)
-        if a.shape != (h, w, 3) or a.dtype != np.uint8:
-            raise RuntimeError(f"all frames of a sequence must be ({h},{w},3) uint8, got {a.shape} {a.dtype}")
+        if a.shape != tuple(in_shape) or a.dtype != np.uint8:
+            raise RuntimeError(f"all frames of a sequence must be {shape_text} uint8, got {a.shape} {a.dtype}")
         up[k].synchronize()                    # the previous upload out of this pinned buffer has finished
         hin[k].numpy()[...] = a
         with torch.cuda.device(dev), torch.cuda.stream(copy):
@@ -60,7 +79,7 @@ def upscale_frames(net, frames, *, bgr: bool = False):
             comp.wait_event(up[k])
             comp.wait_event(down[k])           # dout[k] was last read by the download of frame n-2
             comp.wait_event(done[k ^ 1])       # the engine's workspace is shared: after frame n-1's forward, whatever stream it ran on
-            net.forward_u8(din[k], bgr=bgr, out=dout[k])
+            forward(din[k], dout[k])
             done[k].record(comp)               # din[k] is free again and dout[k] is complete
             with torch.cuda.stream(copy):
                 copy.wait_event(done[k])

@@ -225,6 +225,22 @@ class Plan:
         _lib.check(self._lib.hat_plan_forward_u8(self._h, src.data_ptr(), src.stride(1), h, w, dst.data_ptr(), dst.stride(1), int(bgr), stream),
                    "hat_plan_forward_u8")
 
+    def forward_yuv420(self, src: torch.Tensor, dst: torch.Tensor, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False,
+                       stream: int = 0):
+        """hat_plan_forward_yuv420: src (B,3h/2,w) uint8 device frames in the layout `fmt` with h <= H, w <= W of the plan
+        (reflect-padded to (H, W) on the device) -> dst (B,3sh/2,sw) uint8 in the same layout.  The first byte-path call
+        allocates the plan's fp32 staging buffers."""
+        from . import ops, yuv
+        to_rgb, from_rgb = yuv.csc(matrix, full_range)
+        h, w = yuv.frame_size(src.shape)
+        s = self.dims[4]
+        if src.shape[0] != self.dims[0] or tuple(dst.shape) != (self.dims[0],) + yuv.frame_shape(s * h, s * w):
+            raise RuntimeError(f"forward_yuv420: src {tuple(src.shape)} / dst {tuple(dst.shape)} do not match a plan of batch {self.dims[0]}, scale {s}")
+        sb = ops._yuv_block(*ops.yuv420_views(src, fmt), "forward_yuv420")
+        db = ops._yuv_block(*ops.yuv420_views(dst, fmt), "forward_yuv420")
+        _lib.check(self._lib.hat_plan_forward_yuv420(self._h, *sb, h, w, *db, ops._f12(to_rgb), ops._f12(from_rgb), stream),
+                   "hat_plan_forward_yuv420")
+
     def close(self):
         if self._h:
             self._lib.hat_plan_free(self._h)

@@ -1,0 +1,51 @@
+"""Upscale a YUV4MPEG2 file on the device: 4:2:0 frames up, 4:2:0 frames down, no colour conversion on the host.
+
+    python -m super_resolution_amd.video -opt options/test/HAT-S_SRx4.yml -i in.y4m -o out.y4m [--matrix bt709] [--full-range]
+
+y4m.Reader -> frames.upscale_frames(pixfmt='i420') -> y4m.Writer.  W and H of the header are multiplied by the network's
+scale; every other header token (frame rate, interlacing, aspect, colour space, X comments) is copied.  Decoding and
+encoding compressed video is somebody else's job: `ffmpeg -i in.mp4 -pix_fmt yuv420p in.y4m` and back.
+"""
+from __future__ import annotations
+
+import argparse
+
+from . import y4m
+
+
+def upscale_file(net, src: str, dst: str, *, matrix: str = "bt601", full_range: bool = False) -> dict:
+    """Every frame of the .y4m file `src` through `net` into `dst`; returns {'frames', 'in', 'out'} (sizes as (w, h))."""
+    from . import frames
+    n = 0
+    with y4m.Reader(src) as rd:
+        hdr = y4m.scaled_header(rd.header, net.upscale)
+        with y4m.Writer(dst, hdr) as wr:
+            for out in frames.upscale_frames(net, rd, pixfmt="i420", matrix=matrix, full_range=full_range):
+                wr.write(out)
+                n += 1
+    return {"frames": n, "in": (rd.w, rd.h), "out": (hdr["W"], hdr["H"])}
+
+
+def parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description="upscale a YUV4MPEG2 (.y4m) file of 8-bit 4:2:0 video on the device")
+    ap.add_argument("-opt", required=True, help="test YAML (network_g, path.pretrain_network_g ...), as for super_resolution_amd.test")
+    ap.add_argument("-i", "--input", required=True)
+    ap.add_argument("-o", "--output", required=True)
+    ap.add_argument("--matrix", default="bt601", choices=["bt601", "bt709"], help="YCbCr matrix of the stream (default: bt601, the reference's)")
+    ap.add_argument("--full-range", action="store_true", help="the stream is full range (0-255) instead of 16-235 / 16-240")
+    ap.add_argument("--device", default="cuda:0")
+    return ap
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
+    from .models import HATModel
+    from .test import parse_options
+    model = HATModel(parse_options(args.opt), device=args.device)
+    info = upscale_file(model.get_bare_model(model.net_g), args.input, args.output, matrix=args.matrix, full_range=args.full_range)
+    print(info)
+    return info
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,185 @@
+"""4:2:0 YCbCr frames <-> the network's fp32 RGB planes: the DEFINITION, in numpy on the host.
+
+What a decoder hands over and an encoder takes back is 8-bit 4:2:0 YCbCr (NV12, NV21, I420), not packed RGB.  This
+module says, operation by operation, what the device kernels (csrc/hat_yuv.hip, the yuv epilogue of csrc/hat_cabsq.hip)
+compute: every product and every sum below is rounded to fp32 on its own (numpy float32 arithmetic does exactly that; the
+kernels compile the shared conversion with floating-point contraction off), so the device results EQUAL these, bit for
+bit, and the tests compare with array_equal.
+
+Colour matrices.  csc(matrix, full_range) -> (to_rgb, from_rgb), two float32[12] arrays, row-major 3 x 4:
+  to_rgb    rows R, G, B; columns Y, Cb, Cr, offset.  Byte units in, [0, 1] out.
+  from_rgb  rows Y, Cb, Cr; columns R, G, B, offset.  [0, 1] in, byte units out.
+'bt601' limited range (the default everywhere) is the reference's basicsr/utils/color_util.py: from_rgb holds
+rgb2ycbcr's literals, to_rgb holds ycbcr2rgb's constants folded once in fp64.  The reference's inverse constants are
+rounded to six digits: its offsets are not exactly -(16 m[c][0] + 128 m[c][1] + 128 m[c][2]) but 1e-6 .. 3e-6 off, more
+than the 2e-6 this module is pinned to the reference with, so the offset is kept as a number of its own.  The chroma
+samples are centred on 128 (every matrix has that centre); the luma offset is part of to_rgb's offset column, which is
+added last, so the twelve floats are the whole conversion and the C entry points need no range flag.  'bt709' and
+full_range=True are derived in fp64 from Kr / Kb (0.299 / 0.114 and 0.2126 / 0.0722), offset -16 / 219 or 0.
+
+Input, per pixel (y, x) of the reflect-padded plane: the source pixel is (sy, sx) = (y < h ? y : 2 (h - 1) - y, likewise x)
+— hat_u8_to_planes' rule — and its chroma sample is (sy >> 1, sx >> 1): every chroma sample covers its 2 x 2 luma block
+(nearest).  With Cb' = float(Cb) - 128, Cr' = float(Cr) - 128 (exact in fp32)
+    plane_c = min(max((((m[c][0] * float(Y) + m[c][1] * Cb') + m[c][2] * Cr') + m[c][3]), 0), 1).
+
+Output, from the fp32 value v the float path would have stored: r, g, b = min(max(v, 0), 1);
+    Y  = ((k[0][0] r + k[0][1] g) + k[0][2] b) + k[0][3]                       per pixel
+    cb = (k[1][0] r + k[1][1] g) + k[1][2] b          (no offset), cr likewise  per pixel
+    Cb = ((cb00 + cb01) + (cb10 + cb11)) * 0.25 + k[1][3]                       per 2 x 2 block: left + right, then top + bottom
+and a byte is rint(min(max(., 0), 255)), round half to even.
+
+Chroma siting: nearest up, box down is centre-sited chroma (JPEG, MPEG-1, Y4M C420jpeg).  Left-sited sources (MPEG-2,
+H.264) are accepted and treated the same: a quarter-pixel chroma shift at the output scale.  Other chroma filters, 4:2:2,
+4:4:4 and more than 8 bits are out of scope.
+
+Layouts of one frame, a (3 h / 2, w) uint8 array, h and w even:
+  nv12  h rows of Y, then h / 2 rows of interleaved Cb, Cr
+  nv21  h rows of Y, then h / 2 rows of interleaved Cr, Cb
+  i420  h rows of Y, then the (h / 2, w / 2) Cb plane, then the Cr plane (each stored contiguously in h / 4 rows' worth of bytes)
+"""
+from __future__ import annotations
+
+import numpy as np
+
+FORMATS = ("nv12", "nv21", "i420")
+MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}   # Kr, Kb
+_F = np.float32
+
+
+def check_fmt(fmt: str) -> str:
+    if fmt not in FORMATS:
+        raise RuntimeError(f"unknown 4:2:0 format {fmt!r}: one of {FORMATS}")
+    return fmt
+
+
+def csc(matrix: str = "bt601", full_range: bool = False):
+    """(to_rgb, from_rgb): float32[12] each, see the module docstring."""
+    if matrix not in MATRICES:
+        raise RuntimeError(f"unknown colour matrix {matrix!r}: one of {tuple(MATRICES)}")
+    if matrix == "bt601" and not full_range:
+        fr = np.array([[65.481, 128.553, 24.966, 16.0], [-37.797, -74.203, 112.0, 128.0], [112.0, -93.786, -18.214, 128.0]])
+        # ycbcr2rgb: rgb255 = (ycc_bytes @ M) * 255 + off  ->  rgb = ycc_bytes @ M + off / 255
+        M = np.array([[0.00456621, 0.00456621, 0.00456621], [0.0, -0.00153632, 0.00791071], [0.00625893, -0.00318811, 0.0]])
+        off = np.array([-222.921, 135.576, -276.836]) / 255.0
+        to = np.empty((3, 4))
+        to[:, :3] = M.T
+        to[:, 3] = 128.0 * M[1] + 128.0 * M[2] + off                    # the chroma centre moves into Cb', Cr'
+        return to.astype(_F).reshape(12), fr.astype(_F).reshape(12)
+    kr, kb = MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    ys, cs, oy = (255.0, 255.0, 0.0) if full_range else (219.0, 224.0, 16.0)
+    fr = np.array([[ys * kr, ys * kg, ys * kb, oy],
+                   [-cs * kr / (2 * (1 - kb)), -cs * kg / (2 * (1 - kb)), cs * 0.5, 128.0],
+                   [cs * 0.5, -cs * kg / (2 * (1 - kr)), -cs * kb / (2 * (1 - kr)), 128.0]])
+    to = np.array([[1 / ys, 0.0, 2 * (1 - kr) / cs, -oy / ys],
+                   [1 / ys, -2 * kb * (1 - kb) / (kg * cs), -2 * kr * (1 - kr) / (kg * cs), -oy / ys],
+                   [1 / ys, 2 * (1 - kb) / cs, 0.0, -oy / ys]])
+    return to.astype(_F).reshape(12), fr.astype(_F).reshape(12)
+
+
+# ------------------------------------------------------------------------------------------------ layouts
+def frame_shape(h: int, w: int):
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise RuntimeError(f"4:2:0 frames need even sizes, got {h}x{w}")
+    return (3 * h // 2, w)
+
+
+def frame_size(shape):
+    """(h, w) of a (3 h / 2, w) 4:2:0 frame array."""
+    hh, w = int(shape[-2]), int(shape[-1])
+    if hh < 3 or hh % 3 or w < 2 or w % 2:
+        raise RuntimeError(f"a 4:2:0 frame is a (3h/2, w) array with even h and w, got {tuple(shape)}")
+    return 2 * hh // 3, w
+
+
+def split(frame: np.ndarray, fmt: str = "nv12"):
+    """frame (..., 3h/2, w) uint8 -> views Y (..., h, w), Cb, Cr (..., h/2, w/2)."""
+    check_fmt(fmt)
+    h, w = frame_size(frame.shape)
+    lead = frame.shape[:-2]
+    Y = frame[..., :h, :]
+    c = frame[..., h:, :]
+    if fmt == "i420":
+        c = c.reshape(lead + (2, h // 2, w // 2))
+        return Y, c[..., 0, :, :], c[..., 1, :, :]
+    c = c.reshape(lead + (h // 2, w // 2, 2))
+    return (Y, c[..., 0], c[..., 1]) if fmt == "nv12" else (Y, c[..., 1], c[..., 0])
+
+
+def join(Y: np.ndarray, Cb: np.ndarray, Cr: np.ndarray, fmt: str = "nv12") -> np.ndarray:
+    check_fmt(fmt)
+    h, w = Y.shape[-2:]
+    out = np.empty(Y.shape[:-2] + frame_shape(h, w), dtype=np.uint8)
+    oy, ocb, ocr = split(out, fmt)
+    oy[...], ocb[...], ocr[...] = Y, Cb, Cr
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the two directions
+def _reflect_index(n: int, n_pad: int) -> np.ndarray:
+    i = np.arange(n_pad)
+    return np.where(i < n, i, 2 * (n - 1) - i)
+
+
+def ycc_to_rgb(Y, Cb, Cr, to_rgb) -> np.ndarray:
+    """Per-sample input expression: uint8 arrays of one shape -> float32 (3,) + shape, clamped to [0, 1]."""
+    m = np.asarray(to_rgb, dtype=_F).reshape(3, 4)
+    y = Y.astype(_F)
+    cb = Cb.astype(_F) - _F(128.0)
+    cr = Cr.astype(_F) - _F(128.0)
+    out = np.empty((3,) + y.shape, dtype=_F)
+    for c in range(3):
+        v = ((m[c, 0] * y + m[c, 1] * cb) + m[c, 2] * cr) + m[c, 3]
+        out[c] = np.minimum(np.maximum(v, _F(0.0)), _F(1.0))
+    return out
+
+
+def yuv420_to_planes(frame: np.ndarray, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False, pad=(0, 0)) -> np.ndarray:
+    """frame (3h/2, w) or (B, 3h/2, w) uint8 -> (B, 3, h + pad[0], w + pad[1]) float32 RGB planes, reflect-padded bottom / right."""
+    frame = np.asarray(frame)
+    if frame.dtype != np.uint8 or frame.ndim not in (2, 3):
+        raise RuntimeError(f"expected a (3h/2, w) or (B, 3h/2, w) uint8 frame, got {frame.shape} {frame.dtype}")
+    if frame.ndim == 2:
+        frame = frame[None]
+    h, w = frame_size(frame.shape)
+    if pad[0] >= h or pad[1] >= w or pad[0] < 0 or pad[1] < 0:
+        raise RuntimeError(f"a {h}x{w} frame cannot be reflect-padded by {tuple(pad)}: the padding must be smaller than the frame")
+    to_rgb, _ = csc(matrix, full_range)
+    Y, Cb, Cr = split(frame, fmt)
+    sy, sx = _reflect_index(h, h + pad[0]), _reflect_index(w, w + pad[1])
+    Yp = Y[:, sy][:, :, sx]
+    Cbp = Cb[:, sy >> 1][:, :, sx >> 1]
+    Crp = Cr[:, sy >> 1][:, :, sx >> 1]
+    return np.ascontiguousarray(ycc_to_rgb(Yp, Cbp, Crp, to_rgb).transpose(1, 0, 2, 3))
+
+
+def _byte(v: np.ndarray) -> np.ndarray:
+    return np.rint(np.minimum(np.maximum(v, _F(0.0)), _F(255.0))).astype(np.uint8)
+
+
+def rgb_to_ycc_float(planes: np.ndarray, from_rgb):
+    """planes (..., 3, H, W) float32 -> per-pixel float32 Y (with offset), cb, cr (WITHOUT offset), before any rounding to bytes."""
+    k = np.asarray(from_rgb, dtype=_F).reshape(3, 4)
+    with np.errstate(invalid="ignore"):
+        p = np.minimum(np.maximum(np.asarray(planes, dtype=_F), _F(0.0)), _F(1.0))
+    r, g, b = p[..., 0, :, :], p[..., 1, :, :], p[..., 2, :, :]
+    Y = ((k[0, 0] * r + k[0, 1] * g) + k[0, 2] * b) + k[0, 3]
+    cb = (k[1, 0] * r + k[1, 1] * g) + k[1, 2] * b
+    cr = (k[2, 0] * r + k[2, 1] * g) + k[2, 2] * b
+    return Y, cb, cr
+
+
+def planes_to_yuv420(planes: np.ndarray, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False, crop=None) -> np.ndarray:
+    """planes (B, 3, Hs, Ws) float32 -> (B, 3 h_out / 2, w_out) uint8 in layout `fmt`; crop = (h_out, w_out), even, the
+    top-left pixels kept (default: all)."""
+    planes = np.asarray(planes, dtype=_F)
+    if planes.ndim != 4 or planes.shape[1] != 3:
+        raise RuntimeError(f"expected (B,3,Hs,Ws) float32 planes, got {planes.shape}")
+    ho, wo = (planes.shape[2], planes.shape[3]) if crop is None else (int(crop[0]), int(crop[1]))
+    frame_shape(ho, wo)
+    if ho > planes.shape[2] or wo > planes.shape[3]:
+        raise RuntimeError(f"crop {(ho, wo)} does not lie inside the planes {planes.shape[2:]}")
+    _, k = csc(matrix, full_range)
+    Y, cb, cr = rgb_to_ycc_float(planes[:, :, :ho, :wo], k)
+    box = lambda c, off: ((c[:, 0::2, 0::2] + c[:, 0::2, 1::2]) + (c[:, 1::2, 0::2] + c[:, 1::2, 1::2])) * _F(0.25) + off
+    return join(_byte(Y), _byte(box(cb, k[7])), _byte(box(cr, k[11])), fmt)
