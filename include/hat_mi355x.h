@@ -433,6 +433,44 @@ int hat_conv3x3_to_yuv420(const void* x, const void* wpk, const float* bias, uin
                           int32_t dtype, void* stream);
 
 /*
+ * MATLAB-style bicubic imresize (basicsr utils/matlab_functions.py:16-178): the resize the reference makes its low-resolution
+ * input with (hat/data/imagenet_paired_dataset.py:59).  The definition, operation by operation, is
+ * super_resolution_amd/resize.py; the results equal it bit for bit.
+ *
+ * Tables.  The CALLER builds them on the host (resize.weights_indices reproduces the reference's fp32 arithmetic bit for bit;
+ * the device's linspace, division and floor need not round alike) and passes DEVICE pointers: per axis w[out_len][P] fp32
+ * weights and src[out_len][P] int32 source indices, row-major, out_len = ceil(in_len * scale).  src holds indices into the
+ * source itself, 0 <= src < in_len: the reference's symmetric copy in front of and behind the image is folded in (position s
+ * before the image reads -s - 1, behind it 2 in_len - 1 - s).  The library cannot look into device tables: an index outside
+ * the source is the caller's error.  n_table = out_len * P, the number of entries of each table, is checked against the sizes.
+ * Accumulation.  out1[c][i][x] = sum_k w_h[i][k] * img[c][src_h[i][k]][x] and out[c][i][j] = sum_k w_w[j][k] *
+ * out1[c][i][src_w[j][k]]: the H pass first, k ascending from a zero accumulator, every product and every sum rounded to fp32
+ * on its own (no fused multiply-add).  No clamp and no rounding on the fp32 results: a bicubic overshoots [0, 1].
+ *
+ * hat_imresize_rows            the H pass.  src_u8 != 0: src is (B,h,w,3) uint8 with src_pitch >= 3 w bytes per row and
+ *                    src_bstride bytes per sample (ignored for B == 1), value float(byte) / 255.0f exactly (hat_u8_to_planes'
+ *                    table), plane c = byte (bgr ? 2 - c : c).  src_u8 == 0: src is (B,3,h,w) contiguous fp32 planes (pitch,
+ *                    bstride and bgr ignored).  -> mid: (B,3,oh,w) fp32, the caller's workspace.
+ * hat_imresize_cols_to_planes  the W pass from mid (B,3,oh,w) -> dst (B,3,Hp,Wp) fp32 planes, reflect-padded by
+ *                    hat_u8_to_planes' rule applied to OUTPUT coordinates: plane pixel (y, x) is resized pixel (y', x'), y' = y
+ *                    for y < oh else 2 (oh - 1) - y, likewise x'.  Hp - oh >= oh or Wp - ow >= ow is HAT_EINVAL; Hp = oh, Wp = ow:
+ *                    no padding.
+ * hat_imresize_cols_to_u8      the W pass -> dst (B,oh,ow,3) uint8 with dst_pitch >= 3 ow and dst_bstride: each value clamped to
+ *                    [0, 1], x255, rounded half to even (hat_planes_to_u8's conversion); plane c to byte (bgr ? 2 - c : c).
+ * All three check their arguments before they touch the device (sizes against n_table, pitches, the reflect condition); none
+ * allocates or synchronises.  No plan records these calls.
+ */
+int hat_imresize_rows(const void* src, int32_t src_u8, int64_t src_pitch, int64_t src_bstride, int32_t bgr, float* mid, int32_t B,
+                      int32_t h, int32_t w, int32_t oh, const float* w_h, const int32_t* src_h, int32_t P_h, int64_t n_table,
+                      void* stream);
+int hat_imresize_cols_to_planes(const float* mid, int32_t B, int32_t oh, int32_t w, int32_t ow, const float* w_w, const int32_t* src_w,
+                                int32_t P_w, int64_t n_table, float* dst, int32_t Hp, int32_t Wp, void* stream);
+int hat_imresize_cols_to_u8(const float* mid, int32_t B, int32_t oh, int32_t w, int32_t ow, const float* w_w, const int32_t* src_w,
+                            int32_t P_w, int64_t n_table, uint8_t* dst, int64_t dst_pitch, int64_t dst_bstride, int32_t bgr,
+                            void* stream);
+
+
+/*
  * PSNR / SSIM of two 8-bit frames on the device, with the definitions of the reference's validation loop (basicsr
  * metrics/psnr_ssim.py calculate_psnr / calculate_ssim / _ssim, metrics/metric_util.py to_y_channel).  a, b: (B,h,w,3) uint8
  * with row pitches >= 3 w bytes and sample strides in bytes (ignored for B == 1), as hat_u8_to_planes takes them.

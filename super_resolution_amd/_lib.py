@@ -163,6 +163,12 @@ SIGNATURES = {
     "hat_conv3x3_to_yuv420": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + _YUV_BLOCK + [C.c_int32] * 7 + [C.c_float, C.c_void_p, C.c_void_p,
                                                                                                       C.c_int32, C.c_void_p]),
     "hat_plan_forward_yuv420": (C.c_int, [C.c_void_p] + _YUV_BLOCK + [C.c_int32, C.c_int32] + _YUV_BLOCK + [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hat_imresize_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "hat_imresize_cols_to_planes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "hat_imresize_cols_to_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
     "hat_u8_metrics_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "hat_u8_metrics": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -378,6 +378,20 @@ class HAT(nn.Module):
         with torch.no_grad():
             return self.engine(frame.device).forward_u8(frame, bgr=bgr, out=out)
 
+    def forward_gt_u8(self, gt, *, bgr: bool = False, out=None):
+        """Ground-truth frames in, the super-resolution of their own bicubic low-resolution image out, all on the device: `gt`
+        is an (H,W,3) or (B,H,W,3) uint8 device tensor; it is mod-cropped to multiples of `upscale` (a view), resized at
+        1 / upscale by the reference's MATLAB-style `imresize` (super_resolution_amd/resize.py, bit for bit; float, unrounded,
+        as hat/data/imagenet_paired_dataset.py:59 makes its LQ) into the reflect-padded input, and run as forward_u8 runs:
+        returns (B, H - H % s, W - W % s, 3) uint8, to be scored against the same mod-cropped `gt`.  bgr, out: as forward_u8."""
+        if not isinstance(gt, torch.Tensor) or gt.dtype != torch.uint8:
+            raise RuntimeError(f"forward_gt_u8 needs a uint8 device tensor, got {getattr(gt, 'dtype', type(gt).__name__)}")
+        self._check_u8_input(gt)
+        if gt.dim() == 3:
+            gt = gt.unsqueeze(0)
+        with torch.no_grad():
+            return self.engine(gt.device).forward_gt_u8(gt, bgr=bgr, out=out)
+
     def forward_yuv420(self, frame, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False, out=None):
         """4:2:0 YCbCr frames in, 4:2:0 frames out, all on the device: `frame` is a (3h/2, w) or (B, 3h/2, w) uint8 device tensor in
         the standard contiguous layout of `fmt` ('nv12', 'nv21', 'i420': super_resolution_amd/yuv.py), h and w even and of ANY

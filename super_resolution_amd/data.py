@@ -30,10 +30,18 @@ def _scan(folder: str):
 
 class FolderDataset:
     """opt: {name, type: PairedImageDataset|SingleImageDataset, dataroot_lq, [dataroot_gt], [filename_tmpl]}.
-    Paired: every LQ file must have a GT file of the same basename (paired_paths_from_folder semantics)."""
+    Paired: every LQ file must have a GT file of the same basename (paired_paths_from_folder semantics).
+    type: ImageNetPairedDataset takes {name, dataroot_gt, scale, [gt_size]} only and makes each LQ image from its GT image."""
 
     def __init__(self, opt: dict):
         self.opt = opt
+        self.gt_only = opt.get("type") == "ImageNetPairedDataset"
+        # GT-only datasets: False leaves `lq` out of the items (no host imresize).  HATModel.nondist_validation clears it for
+        # the time of a `val.lq_on_device` run, which makes the LQ image on the device from `gt`.
+        self.make_lq = True
+        if self.gt_only:
+            self._init_gt_only(opt)
+            return
         self.lq = _scan(opt["dataroot_lq"])
         self.gt = None
         if opt.get("type", "SingleImageDataset") == "PairedImageDataset" or opt.get("dataroot_gt"):
@@ -51,10 +59,46 @@ class FolderDataset:
             self.lq = [m for m, _ in self.gt]
             self.gt = [g for _, g in self.gt]
 
+    # ---- type: ImageNetPairedDataset (hat/data/imagenet_paired_dataset.py), test phase: a folder of ground-truth images
+    # only; the LQ image is made from each GT image by the reference's MATLAB-style imresize (resize.py) ----
+    def _init_gt_only(self, opt: dict):
+        if opt.get("phase", "test") == "train":
+            raise NotImplementedError("ImageNetPairedDataset: only the test-phase branch is built (no random crop, no augmentation)")
+        if (opt.get("io_backend") or {}).get("type", "disk") != "disk":
+            raise NotImplementedError("ImageNetPairedDataset: io_backend lmdb is not supported, only disk")
+        for key, what in (("meta_info_file", "a meta_info_file"), ("mean", "mean / std normalisation"), ("std", "mean / std normalisation")):
+            if opt.get(key) is not None:
+                raise NotImplementedError(f"ImageNetPairedDataset: {what} is not supported")
+        if opt.get("color") == "y":
+            raise NotImplementedError("ImageNetPairedDataset: color: y is not supported")
+        if not int(opt.get("scale", 0) or 0) > 0:
+            raise ValueError(f"{opt.get('name')}: ImageNetPairedDataset needs `scale`: the LQ image is made from the GT image at 1 / scale")
+        self.gt = _scan(opt["dataroot_gt"])
+        self.lq = self.gt            # the outputs are named after lq_path
+
+    def _getitem_gt_only(self, i):
+        from . import resize
+        s = int(self.opt["scale"])
+        gt = read_image(self.gt[i]).numpy()                                   # (3,H,W) float32 RGB
+        H, W = resize.mod_crop(gt.shape[1], gt.shape[2], s)                   # imagenet_paired_dataset.py:49-53
+        gt_size = int(self.opt.get("gt_size", 0) or 0)
+        if H < gt_size or W < gt_size:                                        # :56-58 enlarges with cv2.resize: out of scope
+            raise RuntimeError(f"{self.gt[i]}: {H}x{W} after mod-crop is smaller than gt_size {gt_size}; enlarging is not supported")
+        gt = np.ascontiguousarray(gt[:, :H, :W])
+        d = {"gt_path": [self.gt[i]], "lq_path": [self.gt[i]]}
+        if self.make_lq:
+            lq = resize.imresize(gt, 1 / s)                                    # :59, float, unrounded
+            d["lq"] = torch.from_numpy(lq).unsqueeze(0)
+            gt = gt[:, :lq.shape[1] * s, :lq.shape[2] * s]                     # :79-80; a no-op after the mod-crop: ceil(H / s) s = H
+        d["gt"] = torch.from_numpy(np.ascontiguousarray(gt)).unsqueeze(0)
+        return d
+
     def __len__(self):
         return len(self.lq)
 
     def __getitem__(self, i):
+        if self.gt_only:
+            return self._getitem_gt_only(i)
         d = {"lq": read_image(self.lq[i]).unsqueeze(0), "lq_path": [self.lq[i]]}
         if self.gt is not None:
             gt = read_image(self.gt[i]).unsqueeze(0)

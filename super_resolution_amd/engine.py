@@ -668,6 +668,38 @@ class HATEngine:
             ho, wo = h * self.scale, w * self.scale
             return self._forward(ws["x_u8"], u8=(ho, wo, bool(bgr), self._u8_out(out, (B, ho, wo, 3))))
 
+    def forward_gt_u8(self, gt: torch.Tensor, *, bgr: bool = False, out=None) -> torch.Tensor:
+        """(B,H,W,3) uint8 device GROUND-TRUTH frames -> the (B, H - H % s, W - W % s, 3) uint8 super-resolution of their own
+        bicubic low-resolution image, as the reference's GT-only dataset makes it (hat/data/imagenet_paired_dataset.py:49-59):
+        mod-crop to multiples of the upscale s (a view, no copy), resize.imresize_u8 at 1 / s (ops.imresize: float,
+        unrounded, with its overshoot) written reflect-padded into this shape's workspace, the forward, the crop and
+        tensor2img's conversion as in forward_u8.  bgr, out: as in forward_u8."""
+        self._check_u8()
+        if not isinstance(gt, torch.Tensor) or gt.dtype != torch.uint8 or gt.dim() != 4 or gt.shape[3] != 3:
+            raise RuntimeError(f"expected (B,H,W,3) uint8 ground-truth frames, got {tuple(getattr(gt, 'shape', ()))} {getattr(gt, 'dtype', type(gt))}")
+        if not gt.is_cuda or gt.device != self.dev:
+            raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
+        s = self.scale
+        if s not in (2, 3, 4):
+            raise RuntimeError(f"forward_gt_u8 makes the low-resolution image at 1/2, 1/3 or 1/4: upscale {s} has no such path")
+        B, H, W, _ = gt.shape
+        if gt.stride(3) != 1 or gt.stride(2) != 3:
+            gt = gt.contiguous()
+        gt = gt[:, :H - H % s, :W - W % s]
+        h, w = gt.shape[1] // s, gt.shape[2] // s
+        Hp, Wp = -(-h // self.ws) * self.ws, -(-w // self.ws) * self.ws
+        if h < 1 or w < 1 or Hp - h >= h or Wp - w >= w:
+            raise RuntimeError(f"the {h}x{w} low-resolution image of a {H}x{W} frame cannot be reflect-padded to {Hp}x{Wp} (window_size "
+                               f"{self.ws}): the padding must be smaller than the image")
+        with self._lock, torch.cuda.device(self.dev):
+            ws = self._workspace(B, Hp, Wp)
+            if "x_u8" not in ws:     # the padded fp32 input of this shape, shared with forward_u8
+                ws["x_u8"] = torch.zeros(B, 3, Hp, Wp, dtype=torch.float32, device=self.dev)
+                ws["bytes"] += ws["x_u8"].numel() * 4
+            ops.imresize(gt, 1.0 / s, dst=ws["x_u8"], pad_to=(Hp, Wp), bgr=bgr)
+            ho, wo = h * s, w * s
+            return self._forward(ws["x_u8"], u8=(ho, wo, bool(bgr), self._u8_out(out, (B, ho, wo, 3))))
+
     def forward_yuv420(self, frame: torch.Tensor, *, fmt: str = "nv12", to_rgb, from_rgb, out=None) -> torch.Tensor:
         """(B,3h/2,w) uint8 device frames in the layout `fmt` (yuv.py), any even size the reflection allows -> (B,3sh/2,sw) uint8
         in the same layout: hat_yuv420_to_planes into this shape's workspace, the forward, the crop and the conversion back (in

@@ -178,6 +178,65 @@ class HATModel:
             data["img2"] = tensor2img(val_data["gt"])
         return data, scored
 
+    def test_gt_u8(self, gt: torch.Tensor):
+        """`val.lq_on_device`: the (1,H,W,3) uint8 device ground truth -> the (h,w,3) uint8 device result of its own bicubic
+        low-resolution image (resize.py's imresize at 1 / scale, made on the device: the float LQ never exists on the host).
+        Without `tile`, HAT.forward_gt_u8 does it all; with `tile`, ops.imresize writes the padded planes, tile_process runs
+        as always and hat_planes_to_u8 crops and converts, as test_u8 does."""
+        from .. import ops
+        if "tile" not in self.opt:
+            with torch.no_grad():
+                return self.get_bare_model(self.net_g).forward_gt_u8(gt)[0]
+        window_size = self.opt["network_g"]["window_size"]
+        s = self.scale = self.opt.get("scale", 1)
+        b, H, W, _ = gt.shape
+        gt = gt[:, :H - H % s, :W - W % s]
+        h, w = gt.shape[1] // s, gt.shape[2] // s
+        self.mod_pad_h = (window_size - h % window_size) % window_size
+        self.mod_pad_w = (window_size - w % window_size) % window_size
+        if h < 1 or w < 1 or self.mod_pad_h >= h or self.mod_pad_w >= w:
+            raise RuntimeError(f"a {h}x{w} image cannot be reflect-padded to a multiple of window_size {window_size}")
+        with torch.cuda.device(self.device):
+            self.img = ops.imresize(gt, 1.0 / s, pad_to=(h + self.mod_pad_h, w + self.mod_pad_w))
+        self.tile_process()
+        out = torch.empty(b, h * s, w * s, 3, dtype=torch.uint8, device=self.device)
+        ops.planes_to_u8(self.output.to(torch.float32).contiguous(), out)
+        del self.img, self.output
+        return out[0]
+
+    def _test_lq_on_device(self, val_data, metrics, save_img, on_device_metrics):
+        """`val.lq_on_device`: the ground truth goes up once as uint8, test_gt_u8 makes the LQ image and runs, and the result is
+        scored against the same device buffer (its mod-cropped view).  Returns what _test_metrics_on_device returns."""
+        from ..metrics_device import DEVICE_METRICS, calculate_metrics_u8
+        if "gt" not in val_data:
+            raise RuntimeError("val.lq_on_device makes the LQ image from the ground truth: it needs a dataset that delivers `gt` "
+                               "(type: ImageNetPairedDataset or PairedImageDataset)")
+        gt = self._u8_frame(val_data["gt"], "val.lq_on_device", "ground-truth")
+        out = self.test_gt_u8(gt)
+        gtc = gt[0, :out.shape[0], :out.shape[1]]
+        scored = calculate_metrics_u8(out, gtc, metrics) if (metrics and on_device_metrics) else {}
+        host_metrics = bool(metrics) and any(m.get("type") not in DEVICE_METRICS or not on_device_metrics for m in metrics.values())
+        data = {}
+        if save_img or host_metrics:
+            data["img"] = out.cpu().numpy()
+        if host_metrics:
+            data["img2"] = gtc.cpu().numpy()
+        return data, scored
+
+    @staticmethod
+    def _items(dataset, lq_on_device: bool):
+        """The dataset's items.  Under `val.lq_on_device` a GT-only dataset is told not to make `lq` (data.FolderDataset.make_lq):
+        its host imresize is the very step the device takes over, and nothing would read the result."""
+        skip = lq_on_device and getattr(dataset, "gt_only", False)
+        if not skip:
+            yield from dataset
+            return
+        before, dataset.make_lq = dataset.make_lq, False
+        try:
+            yield from dataset
+        finally:
+            dataset.make_lq = before
+
     def nondist_validation(self, dataset, save_img: bool = True):  # hat_model.py:114-185
         dataset_name = dataset.opt["name"]
         val = self.opt.get("val") or {}
@@ -186,10 +245,12 @@ class HATModel:
         per_image = []
         n = 0
         on_device = bool(val.get("metrics_on_device"))   # implies u8_on_device; the known metrics are scored where the result is
-        for val_data in dataset:
+        for val_data in self._items(dataset, bool(val.get("lq_on_device"))):
             img_name = osp.splitext(osp.basename(val_data["lq_path"][0]))[0]
             device_metrics = {}
-            if on_device:
+            if val.get("lq_on_device"):   # implies u8_on_device; the LQ image is made on the device from the uploaded GT
+                data, device_metrics = self._test_lq_on_device(val_data, metrics, save_img, on_device)
+            elif on_device:
                 data, device_metrics = self._test_metrics_on_device(val_data, metrics, save_img)
             elif val.get("u8_on_device"):
                 data = {"img": self.test_u8(val_data["lq"])}

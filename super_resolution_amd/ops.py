@@ -4,6 +4,7 @@ anything on the hot path.  Every wrapper raises if the library is missing or a c
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 from typing import Optional
 
@@ -470,6 +471,106 @@ def planes_to_u8(src, dst, *, bgr: bool = False):
     _timed("planes_to_u8_kernel", 0.0, lambda: _lib.check(
         lib.hat_planes_to_u8(_ptr(src), B, Hs, Ws, dst.data_ptr(), dst.stride(1), dst.stride(0), dst.shape[1], dst.shape[2], int(bgr),
                              _stream()), "hat_planes_to_u8"), tag=f"planes {Hs}x{Ws} -> u8 {dst.shape[1]}x{dst.shape[2]}")
+
+
+# ---- MATLAB bicubic imresize (definition: resize.py; kernels: csrc/hat_resize.hip) ----
+resize_calls = 0            # imresize calls = hat_imresize_rows + hat_imresize_cols_* pairs
+_RESIZE_TABLES_KEPT = 32    # axes; a folder of images of many sizes must not pile tables up
+_resize_tables = collections.OrderedDict()   # (device, in_len, out_len, scale, antialiasing) -> the axis' uploaded tables, least recent first
+_resize_mid = {}            # (device, stream) -> ONE flat fp32 buffer, the general route's intermediate: it only grows
+
+
+def _resize_workspace(dev, B: int, oh: int, w: int):
+    """The (B,3,oh,w) fp32 intermediate as a view of the device's and stream's one grow-only buffer: launches on one stream are
+    ordered, so they may share it; another stream gets its own.  A buffer that is outgrown goes back to torch's allocator, which
+    hands it out again in stream order."""
+    key, n = (str(dev), _stream()), B * 3 * oh * w
+    buf = _resize_mid.get(key)
+    if buf is None or buf.numel() < n:
+        _resize_mid.pop(key, None)
+        buf = _resize_mid[key] = torch.empty(n, dtype=torch.float32, device=dev)
+    return buf[:n].view(B, 3, oh, w)
+
+
+def _resize_axis(dev, in_len: int, scale: float, antialiasing: bool) -> dict:
+    """One axis' tables on `dev`, built on the host by resize.tables and cached: w, src (device tensors), P, out."""
+    import numpy as np
+
+    from . import resize as _rz
+    out_len = _rz.out_length(in_len, scale)
+    key = (str(dev), int(in_len), out_len, float(scale), bool(antialiasing))
+    t = _resize_tables.get(key)
+    if t is not None:
+        _resize_tables.move_to_end(key)
+    else:
+        try:
+            w, s, _, _ = _rz.tables(in_len, out_len, scale, antialiasing)
+        except ValueError as e:
+            raise RuntimeError(str(e)) from e
+        t = {"w": torch.from_numpy(w).to(dev).contiguous(), "src": torch.from_numpy(_rz.mirror(s, in_len).astype(np.int32)).to(dev).contiguous(),
+             "P": w.shape[1], "out": out_len}
+        _resize_tables[key] = t
+        while len(_resize_tables) > _RESIZE_TABLES_KEPT:
+            _resize_tables.popitem(last=False)
+    return t
+
+
+def imresize(src, scale: float, *, antialiasing: bool = True, dst=None, to: str = "planes", pad_to=None, bgr: bool = False):
+    """resize.imresize on the device, bit for bit.  src: (B,h,w,3) uint8 frames (rows may be pitched; value float(v) / 255) or
+    (B,3,h,w) fp32 planes.  to='planes': -> (B,3,Hp,Wp) fp32, (Hp, Wp) = pad_to (default: the resized size), the rows and
+    columns past the resized image filled by reflection as hat_u8_to_planes fills them; to='u8': -> (B,oh,ow,3) uint8 by
+    tensor2img's conversion.  bgr: the bytes of a uint8 side are B, G, R.  dst: the caller's destination (default: a fresh
+    one; with it a second call of the same shape allocates nothing: the last 32 axes' tables are kept, and the intermediate is one
+    grow-only buffer per device and stream).  Two launches, any scale, either direction."""
+    global resize_calls
+    lib = _lib.load()
+    if to not in ("planes", "u8"):
+        raise RuntimeError(f"imresize: to is 'planes' or 'u8', got {to!r}")
+    if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dim() != 4:
+        raise RuntimeError("imresize needs a (B,h,w,3) uint8 or (B,3,h,w) fp32 device tensor (no CPU path exists: resize.imresize is the host definition)")
+    u8 = src.dtype == torch.uint8
+    if u8:
+        B, h, w, c = src.shape
+        if c != 3 or src.stride(3) != 1 or src.stride(2) != 3:
+            raise RuntimeError(f"imresize needs (B,h,w,3) uint8 frames with interleaved pixels, got {tuple(src.shape)}")
+    else:
+        B, c, h, w = src.shape
+        if c != 3 or src.dtype != torch.float32 or not src.is_contiguous():
+            raise RuntimeError(f"imresize needs contiguous (B,3,h,w) fp32 planes, got {tuple(src.shape)} {src.dtype}")
+    dev = src.device
+    th, tw = _resize_axis(dev, h, scale, antialiasing), _resize_axis(dev, w, scale, antialiasing)
+    oh, ow = th["out"], tw["out"]
+    if to == "planes":
+        Hp, Wp = (oh, ow) if pad_to is None else (int(pad_to[0]), int(pad_to[1]))
+        if Hp < oh or Wp < ow or Hp - oh >= oh or Wp - ow >= ow:
+            raise RuntimeError(f"a {oh}x{ow} image cannot be reflect-padded to {Hp}x{Wp}: the padding must be smaller than the image")
+        shape, dtype = (B, 3, Hp, Wp), torch.float32
+    else:
+        if pad_to is not None:
+            raise RuntimeError("imresize: pad_to goes with to='planes'")
+        shape, dtype = (B, oh, ow, 3), torch.uint8
+    if dst is None:
+        dst = torch.empty(shape, dtype=dtype, device=dev)
+    elif tuple(dst.shape) != shape or dst.dtype != dtype or dst.device != dev or (to == "planes" and not dst.is_contiguous()) \
+            or (to == "u8" and (dst.stride(3) != 1 or dst.stride(2) != 3)):
+        raise RuntimeError(f"imresize: dst must be a {shape} {dtype} tensor on {dev}, got {tuple(dst.shape)} {dst.dtype} on {dst.device}")
+    mid = _resize_workspace(dev, B, oh, w)
+    _timed(f"resize_rows_kernel<{'u8' if u8 else 'f32'}>", 2.0 * B * 3 * oh * w * th["P"], lambda: _lib.check(
+        lib.hat_imresize_rows(src.data_ptr(), int(u8), src.stride(1) if u8 else 0, src.stride(0) if u8 else 0, int(bgr and u8), _ptr(mid),
+                              B, h, w, oh, _ptr(th["w"]), _ptr(th["src"]), th["P"], th["w"].numel(), _stream()), "hat_imresize_rows"),
+        tag=f"imresize rows {h}x{w} -> {oh}x{w}", nbytes=B * 3.0 * (h * w * (1 if u8 else 4) + 4.0 * oh * w))
+    if to == "planes":
+        _timed("resize_cols_kernel<planes>", 2.0 * B * 3 * Hp * Wp * tw["P"], lambda: _lib.check(
+            lib.hat_imresize_cols_to_planes(_ptr(mid), B, oh, w, ow, _ptr(tw["w"]), _ptr(tw["src"]), tw["P"], tw["w"].numel(), _ptr(dst),
+                                            Hp, Wp, _stream()), "hat_imresize_cols_to_planes"),
+            tag=f"imresize cols {oh}x{w} -> planes {Hp}x{Wp}", nbytes=B * 3.0 * 4.0 * (oh * w + Hp * Wp))
+    else:
+        _timed("resize_cols_kernel<u8>", 2.0 * B * 3 * oh * ow * tw["P"], lambda: _lib.check(
+            lib.hat_imresize_cols_to_u8(_ptr(mid), B, oh, w, ow, _ptr(tw["w"]), _ptr(tw["src"]), tw["P"], tw["w"].numel(), dst.data_ptr(),
+                                        dst.stride(1), dst.stride(0), int(bgr), _stream()), "hat_imresize_cols_to_u8"),
+            tag=f"imresize cols {oh}x{w} -> u8 {oh}x{ow}", nbytes=B * 3.0 * (4.0 * oh * w + oh * ow))
+    resize_calls += 1
+    return dst
 
 
 def yuv420_views(frame, fmt: str = "nv12"):

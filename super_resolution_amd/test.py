@@ -12,11 +12,14 @@ from .data import FolderDataset
 from .models import HATModel
 
 
-def parse_options(path: str, u8: bool = False, metrics_on_device: bool = False) -> dict:
+def parse_options(path: str, u8: bool = False, metrics_on_device: bool = False, lq_on_device: bool = False) -> dict:
     """u8 (the --u8 flag): set val.u8_on_device; metrics_on_device (--metrics-on-device): set val.metrics_on_device and, since
-    it implies it, val.u8_on_device; without the flags the options are exactly what the YAML says."""
+    it implies it, val.u8_on_device; lq_on_device (--lq-on-device): set val.lq_on_device (and val.u8_on_device); without the
+    flags the options are exactly what the YAML says."""
     with open(path) as f:
         opt = yaml.safe_load(f)
+    if lq_on_device:
+        opt["val"] = dict(opt.get("val") or {}, u8_on_device=True, lq_on_device=True)
     if u8:
         opt["val"] = dict(opt.get("val") or {}, u8_on_device=True)
     if metrics_on_device:
@@ -36,8 +39,10 @@ def main(argv=None):
     ap.add_argument("--u8", action="store_true", help="8-bit frames on the device (sets val.u8_on_device): upload uint8, download uint8")
     ap.add_argument("--metrics-on-device", action="store_true",
                     help="PSNR / SSIM from 8-bit frames on the device (sets val.metrics_on_device and val.u8_on_device)")
+    ap.add_argument("--lq-on-device", action="store_true",
+                    help="make the bicubic LQ image on the device from the uploaded 8-bit ground truth (sets val.lq_on_device)")
     args = ap.parse_args(argv)
-    opt = parse_options(args.opt, u8=args.u8, metrics_on_device=args.metrics_on_device)
+    opt = parse_options(args.opt, u8=args.u8, metrics_on_device=args.metrics_on_device, lq_on_device=args.lq_on_device)
     model = HATModel(opt, device=args.device)
     results = {}
     for _, dopt in sorted((opt.get("datasets") or {}).items()):
