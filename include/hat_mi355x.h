@@ -390,9 +390,9 @@ int hat_conv3x3_to_u8(const void* x, const void* wpk, const float* bias, uint8_t
                       const float* mean4, int32_t bgr, int32_t dtype, void* stream);
 
 /*
- * The 4:2:0 frame boundary: 8-bit YCbCr frames as decoders and encoders exchange them (NV12, NV21, I420) in and out.  The
- * definition, operation by operation, is super_resolution_amd/yuv.py; the results equal it bit for bit (every product and
- * sum is rounded to fp32 on its own: no fused multiply-add).  A frame block is
+ * The 4:2:0 frame boundary: YCbCr frames as decoders and encoders exchange them (NV12, NV21, I420) in and out; first with
+ * 8-bit samples.  The definition, operation by operation, is super_resolution_amd/yuv.py; the results equal it bit for bit
+ * (every product and sum is rounded to fp32 on its own: no fused multiply-add).  A frame block is
  *     y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride
  * — the Y plane (h rows of w bytes, rows y_pitch >= w bytes apart, samples y_bstride bytes apart) and the (h/2, w/2) Cb and
  * Cr samples behind two pointers, rows c_pitch bytes apart, samples of a row c_step bytes apart, samples of the batch
@@ -431,6 +431,33 @@ int hat_conv3x3_to_yuv420(const void* x, const void* wpk, const float* bias, uin
                           uint8_t* cr, int64_t c_pitch, int32_t c_step, int64_t c_bstride, int32_t B, int32_t H, int32_t W, int32_t C,
                           int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, const float* mean4, const float* from_rgb12,
                           int32_t dtype, void* stream);
+
+/*
+ * The same boundary for 10-, 12- and 16-bit video (HEVC Main10, AV1, VP9 profile 2): a sample is a little-endian 16-bit word
+ * that holds an n-bit code, n = depth in {10, 12, 16}.  msb = 1: MSB-aligned words (P010 / P012 / P016, what VCN, VA-API and
+ * D3D surfaces hold): code = word >> (16 - n), the low bits are ignored, and word = code << (16 - n) on output.  msb = 0:
+ * LSB-aligned words (yuv420p10le / p12le, Y4M C420p10 / C420p12): code = min(word, 2^n - 1) — a word above the range saturates —
+ * and word = code.  At n = 16 the two are the same.  With k = n - 8 the input is s = float(code) * 2^-k (exact) and then the
+ * byte expression above on s, Cb' = s_cb - 128, Cr' = s_cr - 128; the output value v (byte units, computed exactly as above)
+ * becomes code = rint(min(max(v * 2^k, 0), 2^n - 1)), half to even.  The matrices are in BYTE units at every depth
+ * (super_resolution_amd.yuv.csc(matrix, full_range, depth); limited-range matrices do not depend on the depth).  No
+ * transfer function is applied: the network sees the source's own transfer (gamma, PQ, HLG).
+ * The three entries take the 8-bit entries' argument lists with uint16_t blocks, then depth and msb.  Pitches, strides and
+ * c_step stay in BYTES (decoder surfaces report bytes) and must be even; c_step is 2 (planar) or 4 (interleaved); the pointers
+ * are 2-byte aligned.  They refuse all that the 8-bit entries refuse, odd pitches / strides / pointers, a depth outside {10,
+ * 12, 16} and an msb outside {0, 1}, before they touch the device; none allocates or synchronises.  4:2:2, 4:4:4, other
+ * chroma filters and tone mapping are out of scope.
+ */
+int hat_yuv420p16_to_planes(const uint16_t* y, int64_t y_pitch, int64_t y_bstride, const uint16_t* cb, const uint16_t* cr, int64_t c_pitch,
+                            int32_t c_step, int64_t c_bstride, float* dst, int32_t B, int32_t h, int32_t w, int32_t Hp, int32_t Wp,
+                            const float* to_rgb12, int32_t depth, int32_t msb, void* stream);
+int hat_planes_to_yuv420p16(const float* src, int32_t B, int32_t Hs, int32_t Ws, uint16_t* y, int64_t y_pitch, int64_t y_bstride,
+                            uint16_t* cb, uint16_t* cr, int64_t c_pitch, int32_t c_step, int64_t c_bstride, int32_t h_out, int32_t w_out,
+                            const float* from_rgb12, int32_t depth, int32_t msb, void* stream);
+int hat_conv3x3_to_yuv420p16(const void* x, const void* wpk, const float* bias, uint16_t* y, int64_t y_pitch, int64_t y_bstride, uint16_t* cb,
+                             uint16_t* cr, int64_t c_pitch, int32_t c_step, int64_t c_bstride, int32_t B, int32_t H, int32_t W, int32_t C,
+                             int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, const float* mean4, const float* from_rgb12,
+                             int32_t dtype, int32_t depth, int32_t msb, void* stream);
 
 /*
  * MATLAB-style bicubic imresize (basicsr utils/matlab_functions.py:16-178): the resize the reference makes its low-resolution
@@ -661,6 +688,12 @@ int hat_hab_tail3(const HatHabTailDesc* d, void* stream);
  *                     hat_conv3x3_to_yuv420 (recorded arguments) or, where the plan does not end in hat_conv3x3_to_planes,
  *                     in hat_planes_to_yuv420 of an fp32 staging image.  The staging buffers are the ones
  *                     hat_plan_forward_u8 uses.  Bit-identical to HAT.forward_yuv420; same return values.
+ *   hat_plan_forward_yuv420_deep  hat_plan_forward_yuv420 with a sample width on either side: after each block its depth (8:
+ *                     bytes, then pitches are what hat_plan_forward_yuv420 takes and msb is not used; 10 / 12 / 16: 16-bit
+ *                     words, see the deep 4:2:0 entries) and msb (0 / 1).  8 -> 10 and 10 -> 8 are this one entry.  It
+ *                     replays from the recorded conv_last arguments in the same way (hat_conv3x3_to_yuv420p16 for a deep
+ *                     destination), stages only in hat_plan_forward_u8's buffers, and needs no new plan file content.
+ *                     Bit-identical to HAT.forward_yuv420(depth=, out_depth=); same return values.
  */
 typedef struct hat_plan hat_plan;
 int hat_plan_load(const char* path, hat_plan** out);
@@ -673,6 +706,11 @@ int hat_plan_forward_yuv420(const hat_plan* plan, const uint8_t* src_y, int64_t 
                             const uint8_t* src_cr, int64_t src_c_pitch, int32_t src_c_step, int64_t src_c_bstride, int32_t h, int32_t w,
                             uint8_t* dst_y, int64_t dst_y_pitch, int64_t dst_y_bstride, uint8_t* dst_cb, uint8_t* dst_cr, int64_t dst_c_pitch,
                             int32_t dst_c_step, int64_t dst_c_bstride, const float* to_rgb12, const float* from_rgb12, void* stream);
+int hat_plan_forward_yuv420_deep(const hat_plan* plan, const void* src_y, int64_t src_y_pitch, int64_t src_y_bstride, const void* src_cb,
+                                 const void* src_cr, int64_t src_c_pitch, int32_t src_c_step, int64_t src_c_bstride, int32_t src_depth,
+                                 int32_t src_msb, int32_t h, int32_t w, void* dst_y, int64_t dst_y_pitch, int64_t dst_y_bstride, void* dst_cb,
+                                 void* dst_cr, int64_t dst_c_pitch, int32_t dst_c_step, int64_t dst_c_bstride, int32_t dst_depth,
+                                 int32_t dst_msb, const float* to_rgb12, const float* from_rgb12, void* stream);
 
 /*
  * Per-channel sums of a channel-last map over the pixel rectangle rows [r0, r1) x columns [c0, c1):

@@ -163,6 +163,15 @@ SIGNATURES = {
     "hat_conv3x3_to_yuv420": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + _YUV_BLOCK + [C.c_int32] * 7 + [C.c_float, C.c_void_p, C.c_void_p,
                                                                                                       C.c_int32, C.c_void_p]),
     "hat_plan_forward_yuv420": (C.c_int, [C.c_void_p] + _YUV_BLOCK + [C.c_int32, C.c_int32] + _YUV_BLOCK + [C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the deep forms: the same lists with 16-bit blocks, then depth, msb
+    "hat_yuv420p16_to_planes": (C.c_int, _YUV_BLOCK + [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                                       C.c_int32, C.c_void_p]),
+    "hat_planes_to_yuv420p16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + _YUV_BLOCK + [C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                                                                                     C.c_int32, C.c_void_p]),
+    "hat_conv3x3_to_yuv420p16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + _YUV_BLOCK + [C.c_int32] * 7 + [C.c_float, C.c_void_p, C.c_void_p,
+                                                                                                         C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "hat_plan_forward_yuv420_deep": (C.c_int, [C.c_void_p] + _YUV_BLOCK + [C.c_int32] * 4 + _YUV_BLOCK + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                                                                     C.c_void_p]),
     "hat_imresize_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     "hat_imresize_cols_to_planes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,

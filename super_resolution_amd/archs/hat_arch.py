@@ -392,26 +392,34 @@ class HAT(nn.Module):
         with torch.no_grad():
             return self.engine(gt.device).forward_gt_u8(gt, bgr=bgr, out=out)
 
-    def forward_yuv420(self, frame, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False, out=None):
+    def forward_yuv420(self, frame, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False, depth: int = 8, out_depth=None,
+                       msb=None, out=None):
         """4:2:0 YCbCr frames in, 4:2:0 frames out, all on the device: `frame` is a (3h/2, w) or (B, 3h/2, w) uint8 device tensor in
         the standard contiguous layout of `fmt` ('nv12', 'nv21', 'i420': super_resolution_amd/yuv.py), h and w even and of ANY
         size whose reflect-padding to the next window multiple is defined; returns (B, 3sh/2, sw) uint8 in the same layout.
-        Equal, bit for bit, to yuv.yuv420_to_planes (nearest chroma, `matrix` 'bt601' / 'bt709', limited or full range) ->
-        reflect-pad -> this build's `forward` -> crop -> yuv.planes_to_yuv420 (2 x 2 box chroma).  out: a (B, 3sh/2, sw) uint8
-        device tensor to fill instead of a fresh one (with it the call allocates nothing where conv_last converts in its
-        epilogue).  Runs eagerly also with use_graph=True (the byte paths are not captured)."""
+        Equal, bit for bit, to yuv.yuv420_to_planes (nearest chroma, `matrix` 'bt601' / 'bt709' / 'bt2020nc', limited or full
+        range) -> reflect-pad -> this build's `forward` -> crop -> yuv.planes_to_yuv420 (2 x 2 box chroma).  out: a (B, 3sh/2,
+        sw) device tensor to fill instead of a fresh one (with it the call allocates nothing where conv_last converts in its
+        epilogue).  depth 10 / 12 / 16: the frame is a uint16 tensor of n-bit codes (P010 / P012 / P016 for nv12 / nv21,
+        yuv420p10le ... for i420; msb=True / False overrides the alignment); out_depth (default: depth) is the width of the
+        result, uint8 for 8 and uint16 otherwise, so 8 -> 10 writes ten bits from an 8-bit source.  The input dtype must agree
+        with `depth`.  No transfer function is applied.  Runs eagerly also with use_graph=True (the byte paths are not captured)."""
         if not isinstance(frame, torch.Tensor):
             raise TypeError(f"forward_yuv420 needs a uint8 device tensor, got {type(frame).__name__}")
-        if frame.dtype != torch.uint8:
-            raise TypeError(f"forward_yuv420 needs a uint8 tensor, got {frame.dtype}")
+        if frame.dtype not in (torch.uint8, torch.uint16):
+            raise TypeError(f"forward_yuv420 needs a uint8 tensor (uint16 with depth 10, 12 or 16), got {frame.dtype}")
         self._check_u8_input(frame)
         from .. import yuv
         yuv.check_fmt(fmt)
-        to_rgb, from_rgb = yuv.csc(matrix, full_range)
+        out_depth = depth if out_depth is None else out_depth
+        to_rgb, from_rgb = yuv.csc(matrix, full_range, depth)[0], yuv.csc(matrix, full_range, out_depth)[1]
+        if frame.dtype != (torch.uint8 if depth == 8 else torch.uint16):
+            raise TypeError(f"forward_yuv420: depth={depth} needs a {'uint8' if depth == 8 else 'uint16'} tensor, got {frame.dtype}")
         if frame.dim() == 2:
             frame = frame.unsqueeze(0)
         with torch.no_grad():
-            return self.engine(frame.device).forward_yuv420(frame, fmt=fmt, to_rgb=to_rgb, from_rgb=from_rgb, out=out)
+            return self.engine(frame.device).forward_yuv420(frame, fmt=fmt, to_rgb=to_rgb, from_rgb=from_rgb, out=out, depth=depth,
+                                                            out_depth=out_depth, msb=msb)
 
     # ---- exact full-frame sharding into row bands (SURVEY §8 f4; no counterpart in the reference, whose tile loop
     # hat_model.py:40-108 gives a DIFFERENT result than the full frame: SURVEY F6) ----

@@ -28,11 +28,16 @@ namespace {
 // stored as interleaved bytes (B,h_out,w_out,3) with a row pitch; rows and columns outside the crop are not stored.
 // Epi = SweepEpiYUV (with NCHW): that same fp32 value converted to 4:2:0 YCbCr (hat_rgb_to_ycc): a Y byte per pixel into outv,
 // a Cb and a Cr byte per 2 x 2 block into cb / cr.  The bands of this instantiation start on even rows.
+// Epi = SweepEpiYUV16 (with NCHW): SweepEpiYUV with 16-bit words for bytes: the n-bit code hat_ycc_code(., scale, maxcode) << shift.
 struct SweepEpi { float out_scale; float mean[4]; int nst; };
 struct SweepEpiU8 { float out_scale; float mean[4]; int h_out, w_out, bgr; long long pitch, bstride; };
 struct SweepEpiYUV {
     float out_scale; float mean[4]; int h_out, w_out, c_step; long long pitch, bstride, c_pitch, c_bstride;
     uint8_t* cb; uint8_t* cr; HatCsc k;
+};
+struct SweepEpiYUV16 {   // pitches, strides and c_step in bytes, as everywhere
+    float out_scale; float mean[4]; int h_out, w_out, c_step; long long pitch, bstride, c_pitch, c_bstride;
+    uint8_t* cb; uint8_t* cr; HatCsc k; int shift; float scale, maxcode;
 };
 
 template <int KS, bool NCHW, typename Epi = SweepEpi>
@@ -41,7 +46,8 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
                                                              float* __restrict__ colsum, int H, int W, int C, int ldx,
                                                              int rows, int strips, int units, Epi epi) {
     constexpr bool U8 = std::is_same<Epi, SweepEpiU8>::value;
-    constexpr bool YUV = std::is_same<Epi, SweepEpiYUV>::value;
+    constexpr bool YUV16 = std::is_same<Epi, SweepEpiYUV16>::value;
+    constexpr bool YUV = std::is_same<Epi, SweepEpiYUV>::value || YUV16;
     static_assert((!U8 && !YUV) || NCHW, "the byte epilogues convert the conv_last value");
     using M = MT<bf16_t>;
     using frag_t = M::frag_t;
@@ -141,11 +147,21 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
             const float crn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, crv), 0x101, 0xf, 0xf, false));
             const float cbs = hat_add_rn(cbv, cbn), crs = hat_add_rn(crv, crn);
             if (y >= y0 && y < y1 && g == 0 && oin && y < epi.h_out && xx < epi.w_out) {
-                o8[(size_t)y * epi.pitch + xx] = (uint8_t)hat_ycc_byte(Yv);
-                if ((y & 1) && !(xx & 1)) {
-                    const size_t co = (size_t)b * epi.c_bstride + (size_t)(y >> 1) * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
-                    epi.cb[co] = (uint8_t)hat_chroma_byte(ctop_b, cbs, epi.k.m[7]);
-                    epi.cr[co] = (uint8_t)hat_chroma_byte(ctop_r, crs, epi.k.m[11]);
+                if constexpr (YUV16) {
+                    // the same lanes, 16-bit stores: a 28-byte Y span per strip and row, 7 + 7 chroma words on odd rows
+                    *reinterpret_cast<uint16_t*>(o8 + (size_t)y * epi.pitch + 2 * (size_t)xx) = (uint16_t)(hat_ycc_code(Yv, epi.scale, epi.maxcode) << epi.shift);
+                    if ((y & 1) && !(xx & 1)) {
+                        const size_t co = (size_t)b * epi.c_bstride + (size_t)(y >> 1) * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
+                        *reinterpret_cast<uint16_t*>(epi.cb + co) = (uint16_t)(hat_ycc_code(hat_chroma_value(ctop_b, cbs, epi.k.m[7]), epi.scale, epi.maxcode) << epi.shift);
+                        *reinterpret_cast<uint16_t*>(epi.cr + co) = (uint16_t)(hat_ycc_code(hat_chroma_value(ctop_r, crs, epi.k.m[11]), epi.scale, epi.maxcode) << epi.shift);
+                    }
+                } else {
+                    o8[(size_t)y * epi.pitch + xx] = (uint8_t)hat_ycc_byte(Yv);
+                    if ((y & 1) && !(xx & 1)) {
+                        const size_t co = (size_t)b * epi.c_bstride + (size_t)(y >> 1) * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
+                        epi.cb[co] = (uint8_t)hat_chroma_byte(ctop_b, cbs, epi.k.m[7]);
+                        epi.cr[co] = (uint8_t)hat_chroma_byte(ctop_r, crs, epi.k.m[11]);
+                    }
                 }
             }
             if (!(y & 1)) { ctop_b = cbs; ctop_r = crs; }
@@ -281,6 +297,28 @@ extern "C" int hat_conv3x3_to_yuv420(const void* x, const void* wpk, const float
                     (long long)c_pitch, (long long)c_bstride, cb, cr, {}};
     for (int i = 0; i < 12; ++i) epi.k.m[i] = from_rgb12[i];
     HAT_LAUNCH((cab_squeeze_kernel<2, true, SweepEpiYUV>), dim3((units + 3) / 4, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+               reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(wpk), bias, y, nullptr, H, W, C, ldx, rows, (W + 13) / 14, units,
+               epi);
+    return hat_check_launch();
+}
+
+extern "C" int hat_conv3x3_to_yuv420p16(const void* x, const void* wpk, const float* bias, uint16_t* y, int64_t y_pitch, int64_t y_bstride,
+                                        uint16_t* cb, uint16_t* cr, int64_t c_pitch, int32_t c_step, int64_t c_bstride, int32_t B, int32_t H,
+                                        int32_t W, int32_t C, int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, const float* mean4,
+                                        const float* from_rgb12, int32_t dtype, int32_t depth, int32_t msb, void* stream) {
+    if (!x || !wpk || !bias || !y || !cb || !cr || !mean4 || !from_rgb12 || H < 1 || W < 16 || W % 16 || h_out > H || w_out > W) return HAT_EINVAL;
+    if (!hat_yuv_depth_ok(depth, msb) || ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(cb) | reinterpret_cast<uintptr_t>(cr)) & 1)) return HAT_EINVAL;
+    if (!hat_yuv_block_ok_n(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out, 2)) return HAT_EINVAL;
+    if (dtype != HAT_BF16) return HAT_EUNSUPPORTED;
+    if (C != 64 || ldx < C || ldx % 8) return HAT_EUNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpk)) % 16) return HAT_EINVAL;
+    int rows = 0, units = 0;
+    sweep_units(H, W, 3072, &rows, &units, true);           // hat_conv3x3_to_yuv420's geometry: even band heights
+    SweepEpiYUV16 epi{out_scale, {mean4[0], mean4[1], mean4[2], mean4[3]}, h_out, w_out, c_step, (long long)y_pitch, (long long)y_bstride,
+                      (long long)c_pitch, (long long)c_bstride, reinterpret_cast<uint8_t*>(cb), reinterpret_cast<uint8_t*>(cr), {},
+                      msb ? 16 - depth : 0, (float)(1 << (depth - 8)), (float)((1u << depth) - 1u)};
+    for (int i = 0; i < 12; ++i) epi.k.m[i] = from_rgb12[i];
+    HAT_LAUNCH((cab_squeeze_kernel<2, true, SweepEpiYUV16>), dim3((units + 3) / 4, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(wpk), bias, y, nullptr, H, W, C, ldx, rows, (W + 13) / 14, units,
                epi);
     return hat_check_launch();

@@ -260,18 +260,33 @@ static __device__ const HatU8Table hat_u8_unit{};
 
 // 4:2:0 YCbCr <-> RGB (definition: super_resolution_amd/yuv.py).  A 3 x 4 matrix travels by value in the kernel arguments.
 // Every product and sum is rounded to fp32 on its own — contraction is off inside these functions — so that numpy float32
-// arithmetic reproduces them bit for bit; every route (hat_yuv.hip's two kernels, conv_last's yuv epilogue) calls these.
+// arithmetic reproduces them bit for bit; every route (hat_yuv.hip's kernels, conv_last's yuv epilogues) calls these.
 struct HatCsc { float m[12]; };
 
-// bytes Y, Cb, Cr -> r, g, b in [0, 1]: rows R, G, B; columns Y, Cb - 128, Cr - 128, offset (added last)
-__device__ __forceinline__ void hat_ycc_to_rgb(const HatCsc& k, unsigned Y, unsigned Cb, unsigned Cr, float (&rgb)[3]) {
+// Y, Cb - 128, Cr - 128 in byte units (any sample width: an n-bit code times 2^(8 - n)) -> r, g, b in [0, 1]: rows R, G, B;
+// columns Y, Cb', Cr', offset (added last).  The one expression of the byte and the deep path.
+__device__ __forceinline__ void hat_ycc_to_rgb_f(const HatCsc& k, float y, float cb, float cr, float (&rgb)[3]) {
 #pragma clang fp contract(off)
-    const float y = (float)Y, cb = (float)Cb - 128.0f, cr = (float)Cr - 128.0f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float v = ((k.m[4 * c] * y + k.m[4 * c + 1] * cb) + k.m[4 * c + 2] * cr) + k.m[4 * c + 3];
         rgb[c] = fminf(fmaxf(v, 0.f), 1.f);
     }
+}
+
+// bytes Y, Cb, Cr -> r, g, b in [0, 1]
+__device__ __forceinline__ void hat_ycc_to_rgb(const HatCsc& k, unsigned Y, unsigned Cb, unsigned Cr, float (&rgb)[3]) {
+#pragma clang fp contract(off)
+    const float y = (float)Y, cb = (float)Cb - 128.0f, cr = (float)Cr - 128.0f;
+    hat_ycc_to_rgb_f(k, y, cb, cr, rgb);
+}
+
+// n-bit codes Y, Cb, Cr -> r, g, b in [0, 1]; inv = 2^(8 - n): the products with it and the centring are exact
+__device__ __forceinline__ void hat_ycc_to_rgb(const HatCsc& k, unsigned Y, unsigned Cb, unsigned Cr, float inv, float (&rgb)[3]) {
+#pragma clang fp contract(off)
+    const float y = (float)Y * inv, sb = (float)Cb * inv, sr = (float)Cr * inv;
+    const float cb = sb - 128.0f, cr = sr - 128.0f;
+    hat_ycc_to_rgb_f(k, y, cb, cr, rgb);
 }
 
 // the float path's r, g, b of one pixel -> Y (with its offset) and the pixel's cb, cr terms (without: the offset joins
@@ -289,13 +304,22 @@ __device__ __forceinline__ void hat_rgb_to_ycc(const HatCsc& k, float r, float g
 // a value in byte units -> the byte: clamp to [0, 255], round half to even
 __device__ __forceinline__ unsigned hat_ycc_byte(float v) { return (unsigned)(int)__builtin_rintf(fminf(fmaxf(v, 0.f), 255.f)); }
 
-// the chroma byte of a 2 x 2 block from its two row sums (left + right each): (top + bottom) * 0.25 + offset
-__device__ __forceinline__ unsigned hat_chroma_byte(float top, float bottom, float offset) {
+// a value in byte units -> the n-bit code: scale = 2^(n - 8) (the product is exact), clamp to [0, maxcode = 2^n - 1], round
+// half to even.  scale = 1, maxcode = 255 is hat_ycc_byte.
+__device__ __forceinline__ unsigned hat_ycc_code(float v, float scale, float maxcode) {
+#pragma clang fp contract(off)
+    const float s = v * scale;
+    return (unsigned)(int)__builtin_rintf(fminf(fmaxf(s, 0.f), maxcode));
+}
+
+// the chroma value (byte units) of a 2 x 2 block from its two row sums (left + right each): (top + bottom) * 0.25 + offset
+__device__ __forceinline__ float hat_chroma_value(float top, float bottom, float offset) {
 #pragma clang fp contract(off)
     const float s = top + bottom;
     const float q = s * 0.25f;
-    return hat_ycc_byte(q + offset);
+    return q + offset;
 }
+__device__ __forceinline__ unsigned hat_chroma_byte(float top, float bottom, float offset) { return hat_ycc_byte(hat_chroma_value(top, bottom, offset)); }
 
 __device__ __forceinline__ float hat_add_rn(float a, float b) {   // a sum that stays a sum whatever surrounds the call
 #pragma clang fp contract(off)

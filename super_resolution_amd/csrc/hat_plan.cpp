@@ -403,3 +403,63 @@ extern "C" int hat_plan_forward_yuv420(const hat_plan* p, const uint8_t* sy, int
     return hat_conv3x3_to_yuv420(r.P(0), r.P(1), (const float*)r.P(2), dy, dy_pitch, dy_bstride, dcb, dcr, dc_pitch, dc_step, dc_bstride, r.I(4),
                                  r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10), (const float*)r.P(11), from_rgb12, r.I(12), stream);
 }
+
+// The same forward with a sample width on either side: 8 (bytes, the msb flag is not used) or 10 / 12 / 16 (16-bit words).
+extern "C" int hat_plan_forward_yuv420_deep(const hat_plan* p, const void* sy, int64_t sy_pitch, int64_t sy_bstride, const void* scb,
+                                            const void* scr, int64_t sc_pitch, int32_t sc_step, int64_t sc_bstride, int32_t src_depth,
+                                            int32_t src_msb, int32_t h, int32_t w, void* dy, int64_t dy_pitch, int64_t dy_bstride, void* dcb,
+                                            void* dcr, int64_t dc_pitch, int32_t dc_step, int64_t dc_bstride, int32_t dst_depth, int32_t dst_msb,
+                                            const float* to_rgb12, const float* from_rgb12, void* stream) {
+    if (!p || !sy || !scb || !scr || !dy || !dcb || !dcr || !to_rgb12 || !from_rgb12 || h < 2 || w < 2 || (h & 1) || (w & 1)) return HAT_EINVAL;
+    if ((src_depth != 8 && !hat_yuv_depth_ok(src_depth, 0)) || (dst_depth != 8 && !hat_yuv_depth_ok(dst_depth, 0))) return HAT_EINVAL;
+    if ((src_msb != 0 && src_msb != 1) || (dst_msb != 0 && dst_msb != 1)) return HAT_EINVAL;
+    const int32_t sb = src_depth == 8 ? 1 : 2, db = dst_depth == 8 ? 1 : 2;
+    auto odd = [](const void* a, const void* b, const void* c) { return ((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 1; };
+    if ((sb == 2 && odd(sy, scb, scr)) || (db == 2 && odd(dy, dcb, dcr))) return HAT_EINVAL;
+    // what needs no plan first (a B of 1 stands in: the batch strides are checked against the plan's B below)
+    if (!hat_yuv_block_ok_n(sy_pitch, 0, sc_pitch, sc_step, 0, 1, h, w, sb) || (dc_step != db && dc_step != 2 * db)) return HAT_EINVAL;
+    const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4];
+    if (p->dims[1] != 3 || p->dims[5] != 3) return HAT_EUNSUPPORTED;   // 4:2:0 frames become three-channel images
+    if (h > H || w > W || H - h >= h || W - w >= w) return HAT_EINVAL;
+    if (!hat_yuv_block_ok_n(sy_pitch, sy_bstride, sc_pitch, sc_step, sc_bstride, B, h, w, sb) ||
+        !hat_yuv_block_ok_n(dy_pitch, dy_bstride, dc_pitch, dc_step, dc_bstride, B, (int64_t)s * h, (int64_t)s * w, db))
+        return HAT_EINVAL;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != p->device) return HAT_EINVAL;
+    const bool fused = ends_in_planes(p);
+    if (!p->stage_in) {
+        const hipError_t e = hipMalloc((void**)&p->stage_in, (size_t)B * 3 * H * W * sizeof(float));
+        if (e != hipSuccess) { p->stage_in = nullptr; return (int)e; }
+    }
+    if (!fused && !p->stage_out) {
+        const hipError_t e = hipMalloc((void**)&p->stage_out, (size_t)B * 3 * s * H * s * W * sizeof(float));
+        if (e != hipSuccess) { p->stage_out = nullptr; return (int)e; }
+    }
+    const int ho = s * h, wo = s * w;
+    int rc = sb == 1 ? hat_yuv420_to_planes((const uint8_t*)sy, sy_pitch, sy_bstride, (const uint8_t*)scb, (const uint8_t*)scr, sc_pitch, sc_step,
+                                            sc_bstride, p->stage_in, B, h, w, H, W, to_rgb12, stream)
+                     : hat_yuv420p16_to_planes((const uint16_t*)sy, sy_pitch, sy_bstride, (const uint16_t*)scb, (const uint16_t*)scr, sc_pitch,
+                                               sc_step, sc_bstride, p->stage_in, B, h, w, H, W, to_rgb12, src_depth, src_msb, stream);
+    if (rc) return rc;
+    const size_t n = p->calls.size() - (fused ? 1 : 0);
+    for (size_t k = 0; k < n; ++k) {
+        Resolved r{p, &p->calls[k], p->stage_in, p->stage_out, stream, {}};
+        rc = dispatch(r);
+        if (rc) return rc;
+    }
+    if (!fused) {
+        if (db == 1)
+            return hat_planes_to_yuv420(p->stage_out, B, s * H, s * W, (uint8_t*)dy, dy_pitch, dy_bstride, (uint8_t*)dcb, (uint8_t*)dcr, dc_pitch,
+                                        dc_step, dc_bstride, ho, wo, from_rgb12, stream);
+        return hat_planes_to_yuv420p16(p->stage_out, B, s * H, s * W, (uint16_t*)dy, dy_pitch, dy_bstride, (uint16_t*)dcb, (uint16_t*)dcr, dc_pitch,
+                                       dc_step, dc_bstride, ho, wo, from_rgb12, dst_depth, dst_msb, stream);
+    }
+    Resolved r{p, &p->calls.back(), p->stage_in, nullptr, stream, {}};
+    if (db == 1)
+        return hat_conv3x3_to_yuv420(r.P(0), r.P(1), (const float*)r.P(2), (uint8_t*)dy, dy_pitch, dy_bstride, (uint8_t*)dcb, (uint8_t*)dcr, dc_pitch,
+                                     dc_step, dc_bstride, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10), (const float*)r.P(11), from_rgb12,
+                                     r.I(12), stream);
+    return hat_conv3x3_to_yuv420p16(r.P(0), r.P(1), (const float*)r.P(2), (uint16_t*)dy, dy_pitch, dy_bstride, (uint16_t*)dcb, (uint16_t*)dcr,
+                                    dc_pitch, dc_step, dc_bstride, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10), (const float*)r.P(11),
+                                    from_rgb12, r.I(12), dst_depth, dst_msb, stream);
+}

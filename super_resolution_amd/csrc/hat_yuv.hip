@@ -1,26 +1,58 @@
-// hat_yuv.hip — the 4:2:0 frame boundary: 8-bit YCbCr frames (NV12 / NV21 / I420) <-> the network's fp32 RGB planes.
-// Contract: include/hat_mi355x.h (hat_yuv420_to_planes, hat_planes_to_yuv420); definition: super_resolution_amd/yuv.py;
+// hat_yuv.hip — the 4:2:0 frame boundary: YCbCr frames (NV12 / NV21 / I420, bytes; P010 / P012 / P016 / yuv420p1xle, 16-bit
+// words) <-> the network's fp32 RGB planes.  Contract: include/hat_mi355x.h (hat_yuv420_to_planes, hat_planes_to_yuv420 and
+// their p16 forms); definition: super_resolution_amd/yuv.py;
 // colour conversion: basicsr utils/color_util.py (rgb2ycbcr, ycbcr2rgb: BT.601, 16-235), shared with conv_last's yuv epilogue
 // through hat_common.h (hat_ycc_to_rgb, hat_rgb_to_ycc).  cb and cr are separate pointers with a byte step between the
 // samples of a row (1: planar, 2: interleaved), so one kernel serves all three layouts.
+#include <type_traits>
+
 #include "hat_common.h"
 #include "hat_yuv_check.h"
 
 namespace {
 
-// one thread = one pixel of the padded plane row (hat_u8_to_planes' shape): a Y byte, the Cb and Cr bytes of its 2 x 2 block
-// (the four pixels of a block read the same two bytes: L1), three plane stores coalesced over the lanes.  Reflection as in
+// What differs between the sample types T.  uint8_t: nothing travels.  uint16_t: an n-bit code in a 16-bit word —
+// shift = 16 - n for MSB-aligned words (else 0), maxcode = 2^n - 1, inv = 2^(8 - n), scale = 2^(n - 8).
+template <typename T> struct HatSample;
+template <> struct HatSample<uint8_t> {
+    __device__ __forceinline__ void to_rgb(const HatCsc& k, unsigned Y, unsigned Cb, unsigned Cr, float (&rgb)[3]) const { hat_ycc_to_rgb(k, Y, Cb, Cr, rgb); }
+    __device__ __forceinline__ unsigned luma(float v) const { return hat_ycc_byte(v); }
+    __device__ __forceinline__ unsigned chroma(float top, float bottom, float offset) const { return hat_chroma_byte(top, bottom, offset); }
+};
+template <> struct HatSample<uint16_t> {
+    int shift;
+    unsigned maxcode;
+    float inv, scale;
+    __device__ __forceinline__ unsigned code(unsigned word) const { return min(word >> shift, maxcode); }   // LSB words above the range saturate
+    __device__ __forceinline__ void to_rgb(const HatCsc& k, unsigned Y, unsigned Cb, unsigned Cr, float (&rgb)[3]) const {
+        hat_ycc_to_rgb(k, code(Y), code(Cb), code(Cr), inv, rgb);
+    }
+    __device__ __forceinline__ unsigned luma(float v) const { return hat_ycc_code(v, scale, (float)maxcode) << shift; }
+    __device__ __forceinline__ unsigned chroma(float top, float bottom, float offset) const {
+        return hat_ycc_code(hat_chroma_value(top, bottom, offset), scale, (float)maxcode) << shift;
+    }
+};
+
+// sample i of a row that starts at byte address p (pitches, strides and the chroma step are in bytes for every T)
+template <typename T> __device__ __forceinline__ T& sample_at(T* base, size_t bytes) {
+    using byte_t = typename std::conditional<std::is_const<T>::value, const char, char>::type;
+    return *reinterpret_cast<T*>(reinterpret_cast<byte_t*>(base) + bytes);
+}
+
+// one thread = one pixel of the padded plane row (hat_u8_to_planes' shape): a Y sample, the Cb and Cr samples of its 2 x 2 block
+// (the four pixels of a block read the same two samples: L1), three plane stores coalesced over the lanes.  Reflection as in
 // u8_to_planes_kernel; the chroma sample of source pixel (sy, sx) is (sy >> 1, sx >> 1).
-__global__ __launch_bounds__(256) void yuv420_to_planes_kernel(const uint8_t* __restrict__ yp, long long y_pitch, long long y_bstride,
-                                                               const uint8_t* __restrict__ cbp, const uint8_t* __restrict__ crp,
+template <typename T>
+__global__ __launch_bounds__(256) void yuv420_to_planes_kernel(const T* __restrict__ yp, long long y_pitch, long long y_bstride,
+                                                               const T* __restrict__ cbp, const T* __restrict__ crp,
                                                                long long c_pitch, int c_step, long long c_bstride, float* __restrict__ dst,
-                                                               int h, int w, int Hp, int Wp, HatCsc k) {
+                                                               int h, int w, int Hp, int Wp, HatCsc k, HatSample<T> q) {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
     if (x >= Wp) return;
     const int sy = y < h ? y : 2 * (h - 1) - y, sx = x < w ? x : 2 * (w - 1) - x;
     const size_t co = (size_t)b * c_bstride + (size_t)(sy >> 1) * c_pitch + (size_t)(sx >> 1) * c_step;
     float rgb[3];
-    hat_ycc_to_rgb(k, yp[(size_t)b * y_bstride + (size_t)sy * y_pitch + sx], cbp[co], crp[co], rgb);
+    q.to_rgb(k, sample_at(yp, (size_t)b * y_bstride + (size_t)sy * y_pitch + (size_t)sx * sizeof(T)), sample_at(cbp, co), sample_at(crp, co), rgb);
     float* o = dst + ((size_t)b * 3 * Hp + y) * Wp + x;
     const size_t plane = (size_t)Hp * Wp;
 #pragma unroll
@@ -28,19 +60,21 @@ __global__ __launch_bounds__(256) void yuv420_to_planes_kernel(const uint8_t* __
 }
 
 // one thread = two rows x four columns = two 2 x 2 blocks: rows are not independent here.  Per row and plane 16 contiguous
-// bytes are loaded; the Y bytes of a row go out as one dword where the segment is whole and 4-byte aligned, as single bytes
-// otherwise; the two Cb and two Cr bytes are single byte stores (planar or interleaved: the step decides).
-__global__ __launch_bounds__(256) void planes_to_yuv420_kernel(const float* __restrict__ src, int Hs, int Ws, uint8_t* __restrict__ yp,
-                                                               long long y_pitch, long long y_bstride, uint8_t* __restrict__ cbp,
-                                                               uint8_t* __restrict__ crp, long long c_pitch, int c_step, long long c_bstride,
-                                                               int w_out, HatCsc k) {
+// bytes are loaded; the four Y samples of a row go out as one store (a dword of bytes, 8 bytes of words) where the segment is
+// whole and aligned to that store, as single samples otherwise; the two Cb and two Cr samples are single stores (planar or
+// interleaved: the step decides).
+template <typename T>
+__global__ __launch_bounds__(256) void planes_to_yuv420_kernel(const float* __restrict__ src, int Hs, int Ws, T* __restrict__ yp,
+                                                               long long y_pitch, long long y_bstride, T* __restrict__ cbp,
+                                                               T* __restrict__ crp, long long c_pitch, int c_step, long long c_bstride,
+                                                               int w_out, HatCsc k, HatSample<T> q) {
     const int x = (blockIdx.x * 256 + threadIdx.x) * 4, y = blockIdx.y * 2, b = blockIdx.z;
     if (x >= w_out) return;
     const size_t plane = (size_t)Hs * Ws;
     const float* s = src + (size_t)b * 3 * plane + (size_t)y * Ws + x;
     const int n = min(4, w_out - x);          // 2 or 4: w_out is even
     float cb[2][4], cr[2][4];
-    unsigned q[2][4];
+    unsigned v[2][4];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -48,23 +82,28 @@ __global__ __launch_bounds__(256) void planes_to_yuv420_kernel(const float* __re
             float Y = 0.f;
             cb[j][i] = cr[j][i] = 0.f;
             if (i < n) hat_rgb_to_ycc(k, s[(size_t)j * Ws + i], s[plane + (size_t)j * Ws + i], s[2 * plane + (size_t)j * Ws + i], Y, cb[j][i], cr[j][i]);
-            q[j][i] = hat_ycc_byte(Y);
+            v[j][i] = q.luma(Y);
         }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        uint8_t* o = yp + (size_t)b * y_bstride + (size_t)(y + j) * y_pitch + x;
-        if (n == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
-            *reinterpret_cast<unsigned*>(o) = q[j][0] | (q[j][1] << 8) | (q[j][2] << 16) | (q[j][3] << 24);
+        T* o = &sample_at(yp, (size_t)b * y_bstride + (size_t)(y + j) * y_pitch + (size_t)x * sizeof(T));
+        if (n == 4 && (reinterpret_cast<uintptr_t>(o) & (4 * sizeof(T) - 1)) == 0) {
+            if constexpr (sizeof(T) == 1) {
+                *reinterpret_cast<unsigned*>(o) = v[j][0] | (v[j][1] << 8) | (v[j][2] << 16) | (v[j][3] << 24);
+            } else {
+                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+                *reinterpret_cast<u32x2*>(o) = u32x2{v[j][0] | (v[j][1] << 16), v[j][2] | (v[j][3] << 16)};
+            }
         } else {
-            for (int i = 0; i < n; ++i) o[i] = (uint8_t)q[j][i];
+            for (int i = 0; i < n; ++i) o[i] = (T)v[j][i];
         }
     }
     const size_t co = (size_t)b * c_bstride + (size_t)(y >> 1) * c_pitch + (size_t)(x >> 1) * c_step;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         if (2 * i < n) {
-            cbp[co + (size_t)i * c_step] = (uint8_t)hat_chroma_byte(hat_add_rn(cb[0][2 * i], cb[0][2 * i + 1]), hat_add_rn(cb[1][2 * i], cb[1][2 * i + 1]), k.m[7]);
-            crp[co + (size_t)i * c_step] = (uint8_t)hat_chroma_byte(hat_add_rn(cr[0][2 * i], cr[0][2 * i + 1]), hat_add_rn(cr[1][2 * i], cr[1][2 * i + 1]), k.m[11]);
+            sample_at(cbp, co + (size_t)i * c_step) = (T)q.chroma(hat_add_rn(cb[0][2 * i], cb[0][2 * i + 1]), hat_add_rn(cb[1][2 * i], cb[1][2 * i + 1]), k.m[7]);
+            sample_at(crp, co + (size_t)i * c_step) = (T)q.chroma(hat_add_rn(cr[0][2 * i], cr[0][2 * i + 1]), hat_add_rn(cr[1][2 * i], cr[1][2 * i + 1]), k.m[11]);
         }
     }
 }
@@ -75,6 +114,14 @@ HatCsc load_csc(const float* m12) {
     return k;
 }
 
+HatSample<uint16_t> deep_sample(int depth, int msb) {
+    return HatSample<uint16_t>{msb ? 16 - depth : 0, (1u << depth) - 1u, 1.0f / (float)(1 << (depth - 8)), (float)(1 << (depth - 8))};
+}
+
+bool even_ptrs(const void* a, const void* b, const void* c) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 1) == 0;
+}
+
 }  // namespace
 
 extern "C" int hat_yuv420_to_planes(const uint8_t* y, int64_t y_pitch, int64_t y_bstride, const uint8_t* cb, const uint8_t* cr,
@@ -83,9 +130,9 @@ extern "C" int hat_yuv420_to_planes(const uint8_t* y, int64_t y_pitch, int64_t y
     if (!y || !cb || !cr || !dst || !to_rgb12 || !hat_yuv_block_ok(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h, w)) return HAT_EINVAL;
     if (Hp < h || Wp < w || B > 65535 || Hp > 65535) return HAT_EINVAL;
     if (Hp - h >= h || Wp - w >= w) return HAT_EINVAL;   // the reflection needs a source row / column: pad < size
-    HAT_LAUNCH(yuv420_to_planes_kernel, dim3((Wp + 255) / 256, Hp, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y,
+    HAT_LAUNCH(yuv420_to_planes_kernel<uint8_t>, dim3((Wp + 255) / 256, Hp, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y,
                (long long)y_pitch, (long long)y_bstride, cb, cr, (long long)c_pitch, (int)c_step, (long long)c_bstride, dst, h, w, Hp, Wp,
-               load_csc(to_rgb12));
+               load_csc(to_rgb12), HatSample<uint8_t>{});
     return hat_check_launch();
 }
 
@@ -95,8 +142,36 @@ extern "C" int hat_planes_to_yuv420(const float* src, int32_t B, int32_t Hs, int
     if (!src || !y || !cb || !cr || !from_rgb12 || Hs < 1 || Ws < 1 || !hat_yuv_block_ok(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out))
         return HAT_EINVAL;
     if (h_out > Hs || w_out > Ws || B > 65535 || h_out / 2 > 65535) return HAT_EINVAL;
-    HAT_LAUNCH(planes_to_yuv420_kernel, dim3((w_out + 1023) / 1024, h_out / 2, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src,
+    HAT_LAUNCH(planes_to_yuv420_kernel<uint8_t>, dim3((w_out + 1023) / 1024, h_out / 2, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src,
                Hs, Ws, y, (long long)y_pitch, (long long)y_bstride, cb, cr, (long long)c_pitch, (int)c_step, (long long)c_bstride, w_out,
-               load_csc(from_rgb12));
+               load_csc(from_rgb12), HatSample<uint8_t>{});
+    return hat_check_launch();
+}
+
+// The deep forms: the same kernels on 16-bit words.  Pitches, strides and c_step are in bytes and even.
+extern "C" int hat_yuv420p16_to_planes(const uint16_t* y, int64_t y_pitch, int64_t y_bstride, const uint16_t* cb, const uint16_t* cr,
+                                       int64_t c_pitch, int32_t c_step, int64_t c_bstride, float* dst, int32_t B, int32_t h, int32_t w,
+                                       int32_t Hp, int32_t Wp, const float* to_rgb12, int32_t depth, int32_t msb, void* stream) {
+    if (!y || !cb || !cr || !dst || !to_rgb12 || !hat_yuv_depth_ok(depth, msb) || !even_ptrs(y, cb, cr) ||
+        !hat_yuv_block_ok_n(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h, w, 2))
+        return HAT_EINVAL;
+    if (Hp < h || Wp < w || B > 65535 || Hp > 65535) return HAT_EINVAL;
+    if (Hp - h >= h || Wp - w >= w) return HAT_EINVAL;
+    HAT_LAUNCH(yuv420_to_planes_kernel<uint16_t>, dim3((Wp + 255) / 256, Hp, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y,
+               (long long)y_pitch, (long long)y_bstride, cb, cr, (long long)c_pitch, (int)c_step, (long long)c_bstride, dst, h, w, Hp, Wp,
+               load_csc(to_rgb12), deep_sample(depth, msb));
+    return hat_check_launch();
+}
+
+extern "C" int hat_planes_to_yuv420p16(const float* src, int32_t B, int32_t Hs, int32_t Ws, uint16_t* y, int64_t y_pitch, int64_t y_bstride,
+                                       uint16_t* cb, uint16_t* cr, int64_t c_pitch, int32_t c_step, int64_t c_bstride, int32_t h_out,
+                                       int32_t w_out, const float* from_rgb12, int32_t depth, int32_t msb, void* stream) {
+    if (!src || !y || !cb || !cr || !from_rgb12 || Hs < 1 || Ws < 1 || !hat_yuv_depth_ok(depth, msb) || !even_ptrs(y, cb, cr) ||
+        !hat_yuv_block_ok_n(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out, 2))
+        return HAT_EINVAL;
+    if (h_out > Hs || w_out > Ws || B > 65535 || h_out / 2 > 65535) return HAT_EINVAL;
+    HAT_LAUNCH(planes_to_yuv420_kernel<uint16_t>, dim3((w_out + 1023) / 1024, h_out / 2, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+               src, Hs, Ws, y, (long long)y_pitch, (long long)y_bstride, cb, cr, (long long)c_pitch, (int)c_step, (long long)c_bstride, w_out,
+               load_csc(from_rgb12), deep_sample(depth, msb));
     return hat_check_launch();
 }

@@ -12,3 +12,18 @@ static inline bool hat_yuv_block_ok(int64_t y_pitch, int64_t y_bstride, int64_t 
     if (y_pitch < w || c_pitch < crow) return false;
     return B == 1 || (y_bstride >= y_pitch * (h - 1) + w && c_bstride >= c_pitch * (h / 2 - 1) + crow);
 }
+
+// the same for samples of bps bytes (1: bytes, 2: 16-bit words).  Pitches, strides and c_step stay in BYTES (decoder surfaces
+// report bytes): c_step is bps (planar) or 2 bps (interleaved), and with words every pitch and stride that is used is even
+static inline bool hat_yuv_block_ok_n(int64_t y_pitch, int64_t y_bstride, int64_t c_pitch, int32_t c_step, int64_t c_bstride, int32_t B,
+                                      int64_t h, int64_t w, int32_t bps) {
+    if (bps == 1) return hat_yuv_block_ok(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h, w);
+    if (bps != 2 || B < 1 || h < 2 || w < 2 || (h & 1) || (w & 1) || (c_step != 2 && c_step != 4)) return false;
+    const int64_t yrow = 2 * w, crow = (int64_t)c_step * (w / 2);
+    if (y_pitch < yrow || c_pitch < crow || (y_pitch & 1) || (c_pitch & 1)) return false;
+    return B == 1 || (!(y_bstride & 1) && !(c_bstride & 1) && y_bstride >= y_pitch * (h - 1) + yrow && c_bstride >= c_pitch * (h / 2 - 1) + crow);
+}
+
+// sample widths of the deep entries: an n-bit code in a 16-bit little-endian word, MSB-aligned (msb = 1: P010 / P012 / P016) or
+// LSB-aligned (msb = 0: yuv420p10le ...); at 16 bits the two are the same
+static inline bool hat_yuv_depth_ok(int32_t depth, int32_t msb) { return (depth == 10 || depth == 12 || depth == 16) && (msb == 0 || msb == 1); }

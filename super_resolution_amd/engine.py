@@ -700,18 +700,26 @@ class HATEngine:
             ho, wo = h * s, w * s
             return self._forward(ws["x_u8"], u8=(ho, wo, bool(bgr), self._u8_out(out, (B, ho, wo, 3))))
 
-    def forward_yuv420(self, frame: torch.Tensor, *, fmt: str = "nv12", to_rgb, from_rgb, out=None) -> torch.Tensor:
+    def forward_yuv420(self, frame: torch.Tensor, *, fmt: str = "nv12", to_rgb, from_rgb, out=None, depth: int = 8, out_depth=None,
+                       msb=None) -> torch.Tensor:
         """(B,3h/2,w) uint8 device frames in the layout `fmt` (yuv.py), any even size the reflection allows -> (B,3sh/2,sw) uint8
         in the same layout: hat_yuv420_to_planes into this shape's workspace, the forward, the crop and the conversion back (in
-        conv_last's epilogue or hat_planes_to_yuv420).  to_rgb / from_rgb: yuv.csc's matrices.  out: the caller's result tensor."""
+        conv_last's epilogue or hat_planes_to_yuv420).  to_rgb / from_rgb: yuv.csc's matrices (of `depth` / `out_depth`).  out: the
+        caller's result tensor.  depth / out_depth 10, 12, 16: uint16 frames on that side (yuv.py, "Deep samples"; out_depth
+        defaults to depth); msb: MSB-aligned words (default: by the layout)."""
         self._check_u8()
-        if not isinstance(frame, torch.Tensor) or frame.dtype != torch.uint8:
+        from . import yuv as _yuv
+        out_depth = depth if out_depth is None else out_depth
+        in_msb, out_msb = bool(_yuv.container(depth, fmt, msb)[3]), bool(_yuv.container(out_depth, fmt, msb)[3])   # (checks depths and fmt)
+        in_dt, out_dt = (torch.uint8 if d == 8 else torch.uint16 for d in (depth, out_depth))
+        if not isinstance(frame, torch.Tensor) or frame.dtype not in (torch.uint8, torch.uint16):
             raise TypeError(f"expected (B,3h/2,w) uint8 frames, got {getattr(frame, 'dtype', type(frame))}")
+        if frame.dtype != in_dt:
+            raise TypeError(f"{depth}-bit frames are {in_dt} tensors (uint8 holds 8-bit samples, uint16 deeper ones), got {frame.dtype}")
         if frame.dim() != 3:
             raise RuntimeError(f"expected (B,3h/2,w) uint8 frames, got {tuple(frame.shape)}")
         if not frame.is_cuda or frame.device != self.dev:
             raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
-        from . import yuv as _yuv
         h, w = _yuv.frame_size(frame.shape)
         B, s = frame.shape[0], self.scale
         Hp, Wp = -(-h // self.ws) * self.ws, -(-w // self.ws) * self.ws
@@ -719,13 +727,13 @@ class HATEngine:
             raise RuntimeError(f"a {h}x{w} frame cannot be reflect-padded to {Hp}x{Wp} (window_size {self.ws}): the padding must be "
                                f"smaller than the frame")
         if frame.stride(2) != 1 or frame.stride(1) != w:
-            frame = frame.contiguous()
+            frame = frame.contiguous() if in_dt is torch.uint8 else frame.view(torch.int16).contiguous().view(torch.uint16)
         shape = (B,) + _yuv.frame_shape(s * h, s * w)
         if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=self.dev)
-        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != self.dev \
+            out = torch.empty(shape, dtype=out_dt, device=self.dev)
+        elif not isinstance(out, torch.Tensor) or out.dtype != out_dt or tuple(out.shape) != shape or out.device != self.dev \
                 or out.stride(2) != 1 or out.stride(1) != s * w:
-            raise RuntimeError(f"out must be a {shape} uint8 tensor on {self.dev} with packed rows, got "
+            raise RuntimeError(f"out must be a {shape} {str(out_dt)[6:]} tensor on {self.dev} with packed rows, got "
                                f"{tuple(out.shape)} {out.dtype} on {out.device}")
         src, dst = ops.yuv420_views(frame, fmt), ops.yuv420_views(out, fmt)
         with self._lock, torch.cuda.device(self.dev):
@@ -733,8 +741,8 @@ class HATEngine:
             if "x_u8" not in ws:     # the padded fp32 input of this shape, shared with forward_u8
                 ws["x_u8"] = torch.zeros(B, 3, Hp, Wp, dtype=torch.float32, device=self.dev)
                 ws["bytes"] += ws["x_u8"].numel() * 4
-            ops.yuv420_to_planes(*src, ws["x_u8"], to_rgb)
-            self._forward(ws["x_u8"], yuv=(dst, from_rgb, out))
+            ops.yuv420_to_planes(*src, ws["x_u8"], to_rgb, depth=depth, msb=in_msb)
+            self._forward(ws["x_u8"], yuv=(dst, from_rgb, out, out_depth, out_msb))
         return out
 
     def ocab_only(self, t: torch.Tensor, group: int, H: int, W: int) -> torch.Tensor:
@@ -759,7 +767,7 @@ class HATEngine:
         global average pools of ECA, hat_arch.py:69-73, and of the ESC dynamic kernel, esc_arch.py:96,121) — and returns the
         band's output rows (ghost rows included; the driver keeps the owned ones).
         u8 = (h_out, w_out, bgr, out): the unsharded forward fills and returns out, (B,h_out,w_out,3) uint8 (forward_to_u8).
-        yuv = ((y, cb, cr) views, from_rgb, out): it fills the views of a 4:2:0 frame and returns out (forward_yuv420)."""
+        yuv = ((y, cb, cr) views, from_rgb, out, depth, msb): it fills the views of a 4:2:0 frame and returns out (forward_yuv420)."""
         if x.dim() != 4 or x.shape[1] != self.cfg["in_chans"]:
             raise RuntimeError(f"expected (B,{self.cfg['in_chans']},H,W), got {tuple(x.shape)}")
         B, _, H, W = x.shape
@@ -1136,8 +1144,10 @@ class HATEngine:
         """conv + PixelShuffle per stage; conv_last ; / img_range + mean                     :593-605, :856-858
         u8 = (h_out, w_out, bgr, y): y is (B,h_out,w_out,3) uint8 — conv_last converts in its epilogue (hat_conv3x3_to_u8) where
         the row-sweep kernel runs, else it writes fp32 planes as always and hat_planes_to_u8 converts and crops them.
-        yuv = ((y, cb, cr), from_rgb, out): the third target, 4:2:0 views of `out`, by the same rule: hat_conv3x3_to_yuv420 where
-        the row-sweep kernel runs, else fp32 planes and hat_planes_to_yuv420."""
+        yuv = ((y, cb, cr), from_rgb, out, depth, msb): the third target, 4:2:0 views of `out`, by the same rule:
+        hat_conv3x3_to_yuv420 where the row-sweep kernel runs, else fp32 planes and hat_planes_to_yuv420.  With uint16 views
+        (depth 10 / 12 / 16) it is the fourth target, by the same rule again: hat_conv3x3_to_yuv420p16, else fp32 planes and
+        hat_planes_to_yuv420p16; the two yuv counters count both widths."""
         src, h, wd, dt = f.w["fb"], f.H, f.W, f.dt
         for (pw, rr), dst in zip(self.ups, f.w["ups"]):
             ops.conv(pw, src, dst, B=f.B, H=h, W=wd, dtype=dt, ldx=64, ldo=64, out_mode=O_PIXSHUF_T, ps_r=rr)
@@ -1155,7 +1165,7 @@ class HATEngine:
             if self.u8_fused and wd % 16 == 0:
                 wpk, b8, _ = self.conv_last_sweep
                 ops.conv3x3_to_yuv420(src, wpk, b8, *yuv[0], B=f.B, H=h, W=wd, C_=64, ldx=64, out_scale=1.0 / r, mean=self._mean(),
-                                      from_rgb=yuv[1], dtype=dt)
+                                      from_rgb=yuv[1], dtype=dt, depth=yuv[3], msb=yuv[4])
                 self.yuv_fused_calls += 1
                 return
             y = torch.empty(f.B, 3, h, wd, dtype=torch.float32, device=self.dev)
@@ -1170,5 +1180,5 @@ class HATEngine:
             ops.planes_to_u8(y, y8, bgr=u8[2])
             self.u8_planes_calls += 1
         if yuv is not None:
-            ops.planes_to_yuv420(y, *yuv[0], yuv[1])
+            ops.planes_to_yuv420(y, *yuv[0], yuv[1], depth=yuv[3], msb=yuv[4])
             self.yuv_planes_calls += 1

@@ -17,13 +17,20 @@ import torch
 PIXFMTS = ("rgb24", "nv12", "nv21", "i420")
 
 
-def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", matrix: str = "bt601", full_range: bool = False):
+def _raw(t):
+    """A uint16 tensor as int16 (the same words): torch's copy kernels are complete for the signed type."""
+    return t.view(torch.int16) if t.dtype == torch.uint16 else t
+
+
+def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", matrix: str = "bt601", full_range: bool = False, depth: int = 8,
+                   out_depth=None, msb=None):
     """Generator: for every (h,w,3) uint8 array of `frames` (all of one size) yield the (s*h,s*w,3) uint8 array that
     `net.forward_u8` computes for it, in order.  `net`: a HAT / HATX module on a GPU, in eval mode.  The yielded array is
     the caller's own (copied out of the pinned buffer).  An empty sequence yields nothing.
     pixfmt 'nv12' / 'nv21' / 'i420': the frames are (3h/2, w) uint8 arrays in that 4:2:0 layout (yuv.py), the yielded arrays
     (3sh/2, sw) ones, computed by `net.forward_yuv420` with `matrix` and `full_range` (bgr does not apply).  Same slots,
-    same copy stream, same events: only the buffer shapes and the forward differ."""
+    same copy stream, same events: only the buffer shapes and the forward differ.  depth / out_depth / msb (4:2:0 only): as
+    HAT.forward_yuv420 takes them; a deep side's frames are uint16 arrays, and so are its pinned and device buffers."""
     if pixfmt not in PIXFMTS:
         raise RuntimeError(f"unknown pixfmt {pixfmt!r}: one of {PIXFMTS}")
     yuv420 = pixfmt != "rgb24"
@@ -36,14 +43,22 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
         return
     first = np.ascontiguousarray(first)
     s = net.upscale
+    in_np, in_dt, out_dt = np.uint8, torch.uint8, torch.uint8
     if yuv420:
         from . import yuv as _yuv
-        if first.ndim != 2 or first.dtype != np.uint8:
-            raise RuntimeError(f"expected (3h/2,w) uint8 {pixfmt} frames, got {first.shape} {first.dtype}")
+        out_depth = depth if out_depth is None else out_depth
+        in_np = _yuv.container(depth, pixfmt, msb)[0]
+        _yuv.container(out_depth, pixfmt, msb)
+        in_dt, out_dt = (torch.uint8 if d == 8 else torch.uint16 for d in (depth, out_depth))
+        if first.ndim != 2 or first.dtype != in_np:
+            raise RuntimeError(f"expected (3h/2,w) {np.dtype(in_np).name} {pixfmt} frames, got {first.shape} {first.dtype}")
         h, w = _yuv.frame_size(first.shape)
         in_shape, out_shape, shape_text = first.shape, _yuv.frame_shape(s * h, s * w), f"({3 * h // 2},{w})"
-        forward = lambda src, dst: net.forward_yuv420(src, fmt=pixfmt, matrix=matrix, full_range=full_range, out=dst)
+        forward = lambda src, dst: net.forward_yuv420(src, fmt=pixfmt, matrix=matrix, full_range=full_range, out=dst, depth=depth,
+                                                      out_depth=out_depth, msb=msb)
     else:
+        if depth != 8 or out_depth not in (None, 8):
+            raise RuntimeError("rgb24 frames are 8-bit: depth and out_depth belong to the 4:2:0 pixel formats")
         if first.ndim != 3 or first.shape[2] != 3 or first.dtype != np.uint8:
             raise RuntimeError(f"expected (h,w,3) uint8 frames, got {first.shape} {first.dtype}")
         h, w, _ = first.shape
@@ -53,23 +68,23 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
     # enters the device and takes the stream that is current THEN, so a caller may switch device or stream between frames.
     with torch.cuda.device(dev):
         copy = torch.cuda.Stream(device=dev)
-        hin = [torch.empty(in_shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        hout = [torch.empty(out_shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        din = [torch.empty((1,) + tuple(in_shape), dtype=torch.uint8, device=dev) for _ in range(2)]
-        dout = [torch.empty((1,) + tuple(out_shape), dtype=torch.uint8, device=dev) for _ in range(2)]
+        hin = [torch.empty(in_shape, dtype=in_dt).pin_memory() for _ in range(2)]
+        hout = [torch.empty(out_shape, dtype=out_dt).pin_memory() for _ in range(2)]
+        din = [torch.empty((1,) + tuple(in_shape), dtype=in_dt, device=dev) for _ in range(2)]
+        dout = [torch.empty((1,) + tuple(out_shape), dtype=out_dt, device=dev) for _ in range(2)]
         ev = lambda: torch.cuda.Event()
         up, done, down = [ev(), ev()], [ev(), ev()], [ev(), ev()]
 
     def upload(k, a):
         """frame -> pinned slot k -> device slot k, on the copy stream (after the compute that last read the slot)."""
         a = np.ascontiguousarray(a)
-        if a.shape != tuple(in_shape) or a.dtype != np.uint8:
-            raise RuntimeError(f"all frames of a sequence must be {shape_text} uint8, got {a.shape} {a.dtype}")
+        if a.shape != tuple(in_shape) or a.dtype != in_np:
+            raise RuntimeError(f"all frames of a sequence must be {shape_text} {np.dtype(in_np).name}, got {a.shape} {a.dtype}")
         up[k].synchronize()                    # the previous upload out of this pinned buffer has finished
         hin[k].numpy()[...] = a
         with torch.cuda.device(dev), torch.cuda.stream(copy):
             copy.wait_event(done[k])           # the forward that last read din[k] (frame n-2) has finished
-            din[k].copy_(hin[k].unsqueeze(0), non_blocking=True)
+            _raw(din[k]).copy_(_raw(hin[k]).unsqueeze(0), non_blocking=True)
             up[k].record(copy)
 
     def compute(k):
@@ -83,7 +98,7 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
             done[k].record(comp)               # din[k] is free again and dout[k] is complete
             with torch.cuda.stream(copy):
                 copy.wait_event(done[k])
-                hout[k].copy_(dout[k][0], non_blocking=True)
+                _raw(hout[k]).copy_(_raw(dout[k])[0], non_blocking=True)
                 down[k].record(copy)
 
     def collect(k):

@@ -574,11 +574,11 @@ def imresize(src, scale: float, *, antialiasing: bool = True, dst=None, to: str 
 
 
 def yuv420_views(frame, fmt: str = "nv12"):
-    """frame (B, 3h/2, w) uint8 in the standard layout of `fmt` (rows w bytes apart, samples anywhere) -> views y (B,h,w), cb, cr
-    (B,h/2,w/2): the torch twin of yuv.split.  The chroma views step 2 bytes for nv12 / nv21 and 1 byte for i420."""
+    """frame (B, 3h/2, w) uint8 (uint16: deep samples) in the standard layout of `fmt` (rows w samples apart, samples anywhere) ->
+    views y (B,h,w), cb, cr (B,h/2,w/2): the torch twin of yuv.split.  The chroma views step 2 samples for nv12 / nv21 and 1 for i420."""
     from . import yuv as _yuv
     _yuv.check_fmt(fmt)
-    if frame.dim() != 3 or frame.dtype != torch.uint8 or frame.stride(2) != 1 or frame.stride(1) != frame.shape[2]:
+    if frame.dim() != 3 or frame.dtype not in (torch.uint8, torch.uint16) or frame.stride(2) != 1 or frame.stride(1) != frame.shape[2]:
         raise RuntimeError(f"expected (B,3h/2,w) uint8 frames with packed rows, got {tuple(frame.shape)} {frame.dtype} strides {frame.stride()}")
     h, w = _yuv.frame_size(frame.shape)
     B, y, c = frame.shape[0], frame[:, :h], frame[:, h:]
@@ -590,9 +590,10 @@ def yuv420_views(frame, fmt: str = "nv12"):
 
 
 def _yuv_block(y, cb, cr, what: str):
-    """The C frame block (y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride) of three uint8 device views."""
-    if y.dim() != 3 or y.dtype != torch.uint8 or cb.dtype != torch.uint8 or cr.dtype != torch.uint8:
-        raise TypeError(f"{what} needs uint8 (B,h,w) / (B,h/2,w/2) views, got {y.dtype} {tuple(y.shape)}")
+    """The C frame block (y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride) of three uint8 device views, or of three
+    uint16 ones (deep samples): pitches, strides and the step are in BYTES either way."""
+    if y.dim() != 3 or y.dtype not in (torch.uint8, torch.uint16) or cb.dtype != y.dtype or cr.dtype != y.dtype:
+        raise TypeError(f"{what} needs uint8 (or uint16) (B,h,w) / (B,h/2,w/2) views, got {y.dtype} {tuple(y.shape)}")
     if not (y.is_cuda and cb.is_cuda and cr.is_cuda):
         raise RuntimeError("HAT HIP ops need device tensors (no CPU path exists)")
     B, h, w = y.shape
@@ -600,8 +601,20 @@ def _yuv_block(y, cb, cr, what: str):
         raise RuntimeError(f"{what}: 4:2:0 frames need even sizes, got {h}x{w}")
     if tuple(cb.shape) != (B, h // 2, w // 2) or tuple(cr.shape) != tuple(cb.shape) or cb.stride() != cr.stride() or y.stride(2) != 1 \
             or cb.stride(2) not in (1, 2):
-        raise RuntimeError(f"{what} needs Y (B,h,w) with unit step and Cb, Cr (B,h/2,w/2) of one pitch with a step of 1 or 2 bytes")
-    return [y.data_ptr(), y.stride(1), y.stride(0), cb.data_ptr(), cr.data_ptr(), cb.stride(1), cb.stride(2), cb.stride(0)]
+        raise RuntimeError(f"{what} needs Y (B,h,w) with unit step and Cb, Cr (B,h/2,w/2) of one pitch with a step of 1 or 2 samples")
+    n = y.element_size()
+    return [y.data_ptr(), n * y.stride(1), n * y.stride(0), cb.data_ptr(), cr.data_ptr(), n * cb.stride(1), n * cb.stride(2), n * cb.stride(0)]
+
+
+def _deep_args(y, depth, msb, what: str):
+    """() for byte views, (depth, msb) for uint16 views: the width must agree with the dtype."""
+    if y.dtype == torch.uint8:
+        if depth not in (None, 8):
+            raise TypeError(f"{what}: uint8 views hold 8-bit samples, not depth {depth}")
+        return ()
+    if depth not in (10, 12, 16):
+        raise TypeError(f"{what}: uint16 views need depth 10, 12 or 16 (uint8 views hold 8-bit samples), got {depth}")
+    return (int(depth), int(bool(msb)))
 
 
 def _f12(m):
@@ -611,45 +624,66 @@ def _f12(m):
     return (C.c_float * 12)(*m)
 
 
-def yuv420_to_planes(y, cb, cr, dst, to_rgb):
+def yuv420_to_planes(y, cb, cr, dst, to_rgb, *, depth=None, msb=False):
     """Y (B,h,w), Cb, Cr (B,h/2,w/2) uint8 views (yuv420_views; rows may be pitched) -> dst (B,3,Hp,Wp) fp32 RGB planes, rows and
-    columns past (h, w) filled by reflection; the conversion is yuv.yuv420_to_planes' (hat_yuv420_to_planes)."""
+    columns past (h, w) filled by reflection; the conversion is yuv.yuv420_to_planes' (hat_yuv420_to_planes).  uint16 views with
+    depth 10 / 12 / 16 and msb (MSB-aligned words): hat_yuv420p16_to_planes."""
     lib = _lib.load()
     blk = _yuv_block(y, cb, cr, "yuv420_to_planes")
+    deep = _deep_args(y, depth, msb, "yuv420_to_planes")
     B, h, w = y.shape
     if dst.dtype != torch.float32 or dst.dim() != 4 or dst.shape[0] != B or dst.shape[1] != 3 or dst.shape[2] < h or dst.shape[3] < w \
             or dst.device != y.device:
         raise RuntimeError(f"yuv420_to_planes needs a (B,3,Hp>=h,Wp>=w) fp32 destination on {y.device}, got {tuple(dst.shape)} {dst.dtype} on "
                            f"{dst.device} for frames {tuple(y.shape)}")
     m = _f12(to_rgb)
+    if deep:
+        _timed("yuv420_to_planes_kernel<u16>", 0.0, lambda: _lib.check(
+            lib.hat_yuv420p16_to_planes(*blk, _ptr(dst), B, h, w, dst.shape[2], dst.shape[3], m, *deep, _stream()), "hat_yuv420p16_to_planes"),
+            tag=f"yuv420p{deep[0]} {h}x{w} -> planes {dst.shape[2]}x{dst.shape[3]}")
+        return
     _timed("yuv420_to_planes_kernel", 0.0, lambda: _lib.check(
         lib.hat_yuv420_to_planes(*blk, _ptr(dst), B, h, w, dst.shape[2], dst.shape[3], m, _stream()), "hat_yuv420_to_planes"),
         tag=f"yuv420 {h}x{w} -> planes {dst.shape[2]}x{dst.shape[3]}")
 
 
-def planes_to_yuv420(src, y, cb, cr, from_rgb):
+def planes_to_yuv420(src, y, cb, cr, from_rgb, *, depth=None, msb=False):
     """src (B,3,Hs,Ws) fp32 planes -> the top-left h x w pixels as Y (B,h,w), Cb, Cr (B,h/2,w/2) uint8 views, converted as
-    yuv.planes_to_yuv420 converts (hat_planes_to_yuv420)."""
+    yuv.planes_to_yuv420 converts (hat_planes_to_yuv420).  uint16 views with depth / msb: hat_planes_to_yuv420p16."""
     lib = _lib.load()
     blk = _yuv_block(y, cb, cr, "planes_to_yuv420")
+    deep = _deep_args(y, depth, msb, "planes_to_yuv420")
     B, h, w = y.shape
     if src.dim() != 4 or src.shape[0] != B or src.shape[1] != 3 or src.dtype != torch.float32 or src.device != y.device:
         raise RuntimeError(f"planes_to_yuv420 needs (B,3,Hs,Ws) fp32 planes on {y.device}, got {tuple(src.shape)} {src.dtype} on {src.device}")
     m = _f12(from_rgb)
+    if deep:
+        _timed("planes_to_yuv420_kernel<u16>", 0.0, lambda: _lib.check(
+            lib.hat_planes_to_yuv420p16(_ptr(src), B, src.shape[2], src.shape[3], *blk, h, w, m, *deep, _stream()), "hat_planes_to_yuv420p16"),
+            tag=f"planes {src.shape[2]}x{src.shape[3]} -> yuv420p{deep[0]} {h}x{w}")
+        return
     _timed("planes_to_yuv420_kernel", 0.0, lambda: _lib.check(
         lib.hat_planes_to_yuv420(_ptr(src), B, src.shape[2], src.shape[3], *blk, h, w, m, _stream()), "hat_planes_to_yuv420"),
         tag=f"planes {src.shape[2]}x{src.shape[3]} -> yuv420 {h}x{w}")
 
 
-def conv3x3_to_yuv420(x, wpk, bias8, y, cb, cr, *, B: int, H: int, W: int, C_: int, ldx: int, out_scale: float, mean, from_rgb, dtype: int):
+def conv3x3_to_yuv420(x, wpk, bias8, y, cb, cr, *, B: int, H: int, W: int, C_: int, ldx: int, out_scale: float, mean, from_rgb, dtype: int,
+                      depth=None, msb=False):
     """conv_last with the 4:2:0 conversion as its epilogue: Y (B,h,w), Cb, Cr (B,h/2,w/2) = planes_to_yuv420 of what
-    conv3x3_to_planes writes, cropped to the top-left h x w pixels; neither an fp32 nor an RGB byte image is written."""
+    conv3x3_to_planes writes, cropped to the top-left h x w pixels; neither an fp32 nor an RGB byte image is written.
+    uint16 views with depth / msb: hat_conv3x3_to_yuv420p16."""
     lib = _lib.load()
     blk = _yuv_block(y, cb, cr, "conv3x3_to_yuv420")
+    deep = _deep_args(y, depth, msb, "conv3x3_to_yuv420")
     if y.shape[0] != B:
         raise RuntimeError(f"conv3x3_to_yuv420: destination batch {y.shape[0]} != {B}")
     m4 = (C.c_float * 4)(*[float(mean[i]) if i < len(mean) else 0.0 for i in range(4)])
     m = _f12(from_rgb)
+    if deep:
+        _timed("cab_squeeze_kernel<2, yuv420p16>", 2.0 * B * H * W * 9 * C_ * 3, lambda: _lib.check(
+            lib.hat_conv3x3_to_yuv420p16(_ptr(x), _ptr(wpk), _ptr(bias8), *blk, B, H, W, C_, ldx, y.shape[1], y.shape[2], out_scale, m4, m, dtype,
+                                         *deep, _stream()), "hat_conv3x3_to_yuv420p16"), tag=f"k3 {C_}->3 {H}x{W} row sweep yuv420p{deep[0]}")
+        return
     _timed("cab_squeeze_kernel<2, yuv420>", 2.0 * B * H * W * 9 * C_ * 3, lambda: _lib.check(
         lib.hat_conv3x3_to_yuv420(_ptr(x), _ptr(wpk), _ptr(bias8), *blk, B, H, W, C_, ldx, y.shape[1], y.shape[2], out_scale, m4, m, dtype,
                                   _stream()), "hat_conv3x3_to_yuv420"), tag=f"k3 {C_}->3 {H}x{W} row sweep yuv420")

@@ -226,20 +226,32 @@ class Plan:
                    "hat_plan_forward_u8")
 
     def forward_yuv420(self, src: torch.Tensor, dst: torch.Tensor, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False,
-                       stream: int = 0):
+                       depth: int = 8, out_depth=None, msb=None, stream: int = 0):
         """hat_plan_forward_yuv420: src (B,3h/2,w) uint8 device frames in the layout `fmt` with h <= H, w <= W of the plan
         (reflect-padded to (H, W) on the device) -> dst (B,3sh/2,sw) uint8 in the same layout.  The first byte-path call
-        allocates the plan's fp32 staging buffers."""
+        allocates the plan's fp32 staging buffers.  depth / out_depth / msb as HAT.forward_yuv420 takes them (uint16 tensors on a
+        deep side): hat_plan_forward_yuv420_deep."""
         from . import ops, yuv
-        to_rgb, from_rgb = yuv.csc(matrix, full_range)
+        out_depth = depth if out_depth is None else out_depth
+        to_rgb, from_rgb = yuv.csc(matrix, full_range, depth)[0], yuv.csc(matrix, full_range, out_depth)[1]
         h, w = yuv.frame_size(src.shape)
         s = self.dims[4]
         if src.shape[0] != self.dims[0] or tuple(dst.shape) != (self.dims[0],) + yuv.frame_shape(s * h, s * w):
             raise RuntimeError(f"forward_yuv420: src {tuple(src.shape)} / dst {tuple(dst.shape)} do not match a plan of batch {self.dims[0]}, scale {s}")
         sb = ops._yuv_block(*ops.yuv420_views(src, fmt), "forward_yuv420")
         db = ops._yuv_block(*ops.yuv420_views(dst, fmt), "forward_yuv420")
-        _lib.check(self._lib.hat_plan_forward_yuv420(self._h, *sb, h, w, *db, ops._f12(to_rgb), ops._f12(from_rgb), stream),
-                   "hat_plan_forward_yuv420")
+        if depth == 8 and out_depth == 8:
+            if src.dtype != torch.uint8 or dst.dtype != torch.uint8:
+                raise TypeError(f"forward_yuv420: 8-bit frames are uint8 tensors, got {src.dtype} / {dst.dtype}")
+            _lib.check(self._lib.hat_plan_forward_yuv420(self._h, *sb, h, w, *db, ops._f12(to_rgb), ops._f12(from_rgb), stream),
+                       "hat_plan_forward_yuv420")
+            return
+        for t, d in ((src, depth), (dst, out_depth)):
+            if t.dtype != (torch.uint8 if d == 8 else torch.uint16):
+                raise TypeError(f"forward_yuv420: depth {d} needs a {'uint8' if d == 8 else 'uint16'} tensor, got {t.dtype}")
+        sm, dm = int(bool(yuv.container(depth, fmt, msb)[3])), int(bool(yuv.container(out_depth, fmt, msb)[3]))
+        _lib.check(self._lib.hat_plan_forward_yuv420_deep(self._h, *sb, depth, sm, h, w, *db, out_depth, dm, ops._f12(to_rgb), ops._f12(from_rgb),
+                                                          stream), "hat_plan_forward_yuv420_deep")
 
     def close(self):
         if self._h:

@@ -1,10 +1,14 @@
 """Upscale a YUV4MPEG2 file on the device: 4:2:0 frames up, 4:2:0 frames down, no colour conversion on the host.
 
     python -m super_resolution_amd.video -opt options/test/HAT-S_SRx4.yml -i in.y4m -o out.y4m [--matrix bt709] [--full-range]
+                                         [--out-depth 10]
 
 y4m.Reader -> frames.upscale_frames(pixfmt='i420') -> y4m.Writer.  W and H of the header are multiplied by the network's
 scale; every other header token (frame rate, interlacing, aspect, colour space, X comments) is copied.  Decoding and
 encoding compressed video is somebody else's job: `ffmpeg -i in.mp4 -pix_fmt yuv420p in.y4m` and back.
+10-, 12- and 16-bit streams (C420p10 / C420p12 / C420p16, `-pix_fmt yuv420p10le -strict -1`) are read as they are: the input
+depth comes from the header; --out-depth sets the output's (default: the input's) and with it the output's C token, so
+`--out-depth 10` on an 8-bit file writes the network's result with ten bits.  No transfer function is applied.
 """
 from __future__ import annotations
 
@@ -13,25 +17,32 @@ import argparse
 from . import y4m
 
 
-def upscale_file(net, src: str, dst: str, *, matrix: str = "bt601", full_range: bool = False) -> dict:
-    """Every frame of the .y4m file `src` through `net` into `dst`; returns {'frames', 'in', 'out'} (sizes as (w, h))."""
+def upscale_file(net, src: str, dst: str, *, matrix: str = "bt601", full_range: bool = False, out_depth=None) -> dict:
+    """Every frame of the .y4m file `src` through `net` into `dst`; returns {'frames', 'in', 'out'} (sizes as (w, h)), and for
+    streams that are not 8-bit on both sides also 'depth' and 'out_depth'."""
     from . import frames
     n = 0
-    with y4m.Reader(src) as rd:
-        hdr = y4m.scaled_header(rd.header, net.upscale)
-        with y4m.Writer(dst, hdr) as wr:
-            for out in frames.upscale_frames(net, rd, pixfmt="i420", matrix=matrix, full_range=full_range):
+    with y4m.Reader(src, deep=True) as rd:
+        depth = rd.depth
+        out_depth = depth if out_depth is None else out_depth
+        hdr = y4m.with_depth(y4m.scaled_header(rd.header, net.upscale), out_depth)
+        kw = {} if depth == 8 and out_depth == 8 else {"depth": depth, "out_depth": out_depth}
+        with y4m.Writer(dst, hdr, deep=True) as wr:
+            for out in frames.upscale_frames(net, rd, pixfmt="i420", matrix=matrix, full_range=full_range, **kw):
                 wr.write(out)
                 n += 1
-    return {"frames": n, "in": (rd.w, rd.h), "out": (hdr["W"], hdr["H"])}
+    return dict({"frames": n, "in": (rd.w, rd.h), "out": (hdr["W"], hdr["H"])}, **kw)
 
 
 def parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(description="upscale a YUV4MPEG2 (.y4m) file of 8-bit 4:2:0 video on the device")
+    ap = argparse.ArgumentParser(description="upscale a YUV4MPEG2 (.y4m) file of 4:2:0 video (8, 10, 12 or 16 bits) on the device")
     ap.add_argument("-opt", required=True, help="test YAML (network_g, path.pretrain_network_g ...), as for super_resolution_amd.test")
     ap.add_argument("-i", "--input", required=True)
     ap.add_argument("-o", "--output", required=True)
-    ap.add_argument("--matrix", default="bt601", choices=["bt601", "bt709"], help="YCbCr matrix of the stream (default: bt601, the reference's)")
+    ap.add_argument("--matrix", default="bt601", choices=["bt601", "bt709", "bt2020nc"],
+                    help="YCbCr matrix of the stream (default: bt601, the reference's)")
+    ap.add_argument("--out-depth", type=int, default=None, choices=[8, 10, 12, 16],
+                    help="bits per sample of the output stream (default: the input's, which the header names)")
     ap.add_argument("--full-range", action="store_true", help="the stream is full range (0-255) instead of 16-235 / 16-240")
     ap.add_argument("--device", default="cuda:0")
     return ap
@@ -42,7 +53,8 @@ def main(argv=None):
     from .models import HATModel
     from .test import parse_options
     model = HATModel(parse_options(args.opt), device=args.device)
-    info = upscale_file(model.get_bare_model(model.net_g), args.input, args.output, matrix=args.matrix, full_range=args.full_range)
+    info = upscale_file(model.get_bare_model(model.net_g), args.input, args.output, matrix=args.matrix, full_range=args.full_range,
+                        out_depth=args.out_depth)
     print(info)
     return info
 

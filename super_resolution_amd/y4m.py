@@ -1,10 +1,14 @@
-"""YUV4MPEG2 (.y4m) files of 8-bit 4:2:0 video: a reader and a writer, nothing else.
+"""YUV4MPEG2 (.y4m) files of 4:2:0 video, 8-bit and (with deep=True) 10 / 12 / 16-bit: a reader and a writer, nothing else.
 
 A stream is one header line `YUV4MPEG2 W<w> H<h> F<num>:<den> I<p|t|b|m> A<n>:<d> C<colour space> [X...]` and, per frame,
 a line `FRAME[ params]` followed by the planes Y (h x w), Cb, Cr (h/2 x w/2 each): that is the 'i420' layout of yuv.py,
 so a frame is a (3h/2, w) uint8 array.  Accepted colour spaces: C420 (the default when the token is absent), C420jpeg,
 C420mpeg2, C420paldv — they differ in chroma siting only, which this project treats alike (yuv.py).  Every other colour
 space (C444, C422, Cmono ...), more than 8 bits (C420p10 ...) and odd sizes are refused by name.
+
+deep=True (parse_header, Reader, Writer) also accepts C420p10, C420p12 and C420p16: every sample is a little-endian 16-bit word
+holding the code LSB-aligned (yuv.py, "Deep samples"), a frame is a (3h/2, w) uint16 array and its record is 3 w h bytes long.
+depth(hdr) is 8, 10, 12 or 16.  Without deep=True these streams are refused as before.
 """
 from __future__ import annotations
 
@@ -12,6 +16,7 @@ import numpy as np
 
 MAGIC = b"YUV4MPEG2"
 COLOUR_SPACES = ("420", "420jpeg", "420mpeg2", "420paldv")
+DEEP_COLOUR_SPACES = {"420p10": 10, "420p12": 12, "420p16": 16}
 TOKENS = "WHFIAC"
 
 
@@ -19,7 +24,21 @@ class Y4MError(RuntimeError):
     pass
 
 
-def parse_header(line: bytes) -> dict:
+def depth(hdr: dict) -> int:
+    """Bits per sample of a stream with this header: 8, or 10 / 12 / 16 for C420p10 / C420p12 / C420p16."""
+    return DEEP_COLOUR_SPACES.get(hdr.get("C", "420"), 8)
+
+
+def with_depth(hdr: dict, bits: int) -> dict:
+    """The header with its C token set for `bits` per sample: an 8-bit token is kept, a change of width writes C420 / C420p<bits>."""
+    if bits not in (8, 10, 12, 16):
+        raise Y4MError(f"a 4:2:0 stream has 8, 10, 12 or 16 bits per sample, got {bits}")
+    if bits == depth(hdr):
+        return dict(hdr)
+    return dict(hdr, C="420" if bits == 8 else f"420p{bits}")
+
+
+def parse_header(line: bytes, deep: bool = False) -> dict:
     """The header line (without its newline) -> {'W': int, 'H': int, 'F': str, 'I': str, 'A': str, 'C': str, 'X': [str ...]};
     tokens that are absent are absent (C defaults to '420' for the reader's purposes)."""
     parts = line.split(b" ")
@@ -44,7 +63,7 @@ def parse_header(line: bytes) -> dict:
     if "W" not in hdr or "H" not in hdr:
         raise Y4MError("the header names no W / H")
     c = hdr.get("C", "420")
-    if c not in COLOUR_SPACES:
+    if c not in COLOUR_SPACES and not (deep and c in DEEP_COLOUR_SPACES):
         if c.startswith("420p"):
             raise Y4MError(f"colour space C{c} has more than 8 bits per sample: only 8-bit 4:2:0 is supported")
         raise Y4MError(f"colour space C{c} is not supported: only 8-bit 4:2:0 (C420, C420jpeg, C420mpeg2, C420paldv)")
@@ -53,9 +72,9 @@ def parse_header(line: bytes) -> dict:
     return hdr
 
 
-def format_header(hdr: dict) -> bytes:
+def format_header(hdr: dict, deep: bool = False) -> bytes:
     """The header line for W, H and whichever of F, I, A, C, X are present, in that order, with its newline."""
-    parse_header(b" ".join([MAGIC, b"W%d" % hdr["W"], b"H%d" % hdr["H"]] + ([b"C" + hdr["C"].encode()] if "C" in hdr else [])))
+    parse_header(b" ".join([MAGIC, b"W%d" % hdr["W"], b"H%d" % hdr["H"]] + ([b"C" + hdr["C"].encode()] if "C" in hdr else [])), deep)
     out = [MAGIC, b"W%d" % hdr["W"], b"H%d" % hdr["H"]]
     out += [k.encode() + str(hdr[k]).encode() for k in "FIAC" if k in hdr]
     out += [b"X" + x.encode() for x in hdr.get("X", [])]
@@ -75,9 +94,10 @@ def _readline(f, limit: int = 4096) -> bytes:
 
 
 class Reader:
-    """Iterates the frames of a .y4m file as (3h/2, w) uint8 arrays (layout 'i420'); .header is the parsed header."""
+    """Iterates the frames of a .y4m file as (3h/2, w) uint8 arrays (layout 'i420'); .header is the parsed header.  deep=True:
+    C420p10 / p12 / p16 streams are read too, as uint16 arrays (.depth says which)."""
 
-    def __init__(self, path_or_file):
+    def __init__(self, path_or_file, deep: bool = False):
         self._own = isinstance(path_or_file, (str, bytes)) or hasattr(path_or_file, "__fspath__")
         self._f = open(path_or_file, "rb") if self._own else path_or_file
         line = _readline(self._f)
@@ -85,11 +105,13 @@ class Reader:
             self.close()
             raise Y4MError("the stream ends inside its header")
         try:
-            self.header = parse_header(line[:-1])
+            self.header = parse_header(line[:-1], deep)
         except Y4MError:
             self.close()
             raise
         self.w, self.h = self.header["W"], self.header["H"]
+        self.depth = depth(self.header)
+        self._dtype = np.dtype(np.uint8) if self.depth == 8 else np.dtype("<u2")
 
     def __iter__(self):
         return self
@@ -100,11 +122,11 @@ class Reader:
             raise StopIteration
         if not line.endswith(b"\n") or not (line == b"FRAME\n" or line.startswith(b"FRAME ")):
             raise Y4MError(f"expected a FRAME record, got {line[:16]!r}")
-        n = self.w * self.h * 3 // 2
+        n = self.w * self.h * 3 // 2 * self._dtype.itemsize
         raw = self._f.read(n)
         if len(raw) != n:
             raise Y4MError(f"truncated frame: {len(raw)} of {n} bytes")
-        return np.frombuffer(raw, dtype=np.uint8).reshape(3 * self.h // 2, self.w)
+        return np.frombuffer(raw, dtype=self._dtype).reshape(3 * self.h // 2, self.w)
 
     def close(self):
         if self._own and self._f:
@@ -119,11 +141,13 @@ class Reader:
 
 
 class Writer:
-    """Writes (3h/2, w) uint8 'i420' frames as a .y4m file with the given header (a dict as parse_header returns)."""
+    """Writes (3h/2, w) uint8 'i420' frames as a .y4m file with the given header (a dict as parse_header returns).  deep=True:
+    a C420p10 / p12 / p16 header is accepted and its frames are uint16 arrays, written as little-endian words."""
 
-    def __init__(self, path_or_file, header: dict):
+    def __init__(self, path_or_file, header: dict, deep: bool = False):
         self.header = dict(header)
-        head = format_header(self.header)
+        head = format_header(self.header, deep)
+        self._dtype = np.dtype(np.uint8) if depth(self.header) == 8 else np.dtype(np.uint16)
         self._own = isinstance(path_or_file, (str, bytes)) or hasattr(path_or_file, "__fspath__")
         self._f = open(path_or_file, "wb") if self._own else path_or_file
         self._shape = (3 * header["H"] // 2, header["W"])
@@ -131,10 +155,10 @@ class Writer:
 
     def write(self, frame: np.ndarray):
         frame = np.ascontiguousarray(frame)
-        if frame.shape != self._shape or frame.dtype != np.uint8:
-            raise Y4MError(f"a frame of this stream is a {self._shape} uint8 array, got {frame.shape} {frame.dtype}")
+        if frame.shape != self._shape or frame.dtype != self._dtype:
+            raise Y4MError(f"a frame of this stream is a {self._shape} {self._dtype.name} array, got {frame.shape} {frame.dtype}")
         self._f.write(b"FRAME\n")
-        self._f.write(frame.tobytes())
+        self._f.write(frame.tobytes() if self._dtype.itemsize == 1 else frame.astype("<u2", copy=False).tobytes())
 
     def close(self):
         if self._f:

@@ -1,6 +1,7 @@
 """4:2:0 YCbCr frames <-> the network's fp32 RGB planes: the DEFINITION, in numpy on the host.
 
-What a decoder hands over and an encoder takes back is 8-bit 4:2:0 YCbCr (NV12, NV21, I420), not packed RGB.  This
+What a decoder hands over and an encoder takes back is 4:2:0 YCbCr (NV12, NV21, I420; 8, 10, 12 or 16 bits per sample), not
+packed RGB.  The 8-bit case is described first; "Deep samples" below adds the sample width as one more parameter.  This
 module says, operation by operation, what the device kernels (csrc/hat_yuv.hip, the yuv epilogue of csrc/hat_cabsq.hip)
 compute: every product and every sum below is rounded to fp32 on its own (numpy float32 arithmetic does exactly that; the
 kernels compile the shared conversion with floating-point contraction off), so the device results EQUAL these, bit for
@@ -30,9 +31,23 @@ and a byte is rint(min(max(., 0), 255)), round half to even.
 
 Chroma siting: nearest up, box down is centre-sited chroma (JPEG, MPEG-1, Y4M C420jpeg).  Left-sited sources (MPEG-2,
 H.264) are accepted and treated the same: a quarter-pixel chroma shift at the output scale.  Other chroma filters, 4:2:2,
-4:4:4 and more than 8 bits are out of scope.
+4:4:4 and tone mapping are out of scope.
 
-Layouts of one frame, a (3 h / 2, w) uint8 array, h and w even:
+Deep samples (HEVC Main10, AV1, VP9 profile 2).  A deep sample is a little-endian 16-bit word that holds an n-bit code, n =
+depth in {10, 12, 16}; k = n - 8, maxcode = 2^n - 1, shift = 16 - n for an MSB-aligned container, else 0.
+  MSB-aligned (P010 / P012 / P016: VCN, VA-API, D3D surfaces)    code = word >> shift (the low bits are ignored); word = code << shift
+  LSB-aligned (yuv420p10le / p12le, Y4M C420p10 / C420p12)       code = min(word, maxcode) (saturates, never wraps); word = code
+The default alignment is MSB for 'nv12' / 'nv21' and LSB for 'i420'; msb=True / False overrides it; at n = 16 both are the same.
+Input: s = float32(code) * 2^-k (exact), Cb' = s_cb - 128, Cr' = s_cr - 128 (exact: at most 16 significant bits), then the
+expression above on s.  Output: Y, the cb / cr terms and the box are computed exactly as above, in byte units, and then
+    code = rint(min(max(v * 2^k, 0), maxcode)), half to even (the product is exact; k = 0 is the byte rule).
+csc(matrix, full_range, depth): the matrices stay in BYTE units.  Limited range: an n-bit code is the 8-bit code times 2^k
+(H.273), so the twelve floats do not depend on the depth (the reference's BT.601 literals included).  Full range: the code is
+(2^n - 1) E' with chroma centre 2^(n-1) = 128 in s units, so (2^n - 1) / 2^k (255.75 at 10 bits) takes the place of 255.
+'bt2020nc' is BT.2020 non-constant luminance (Kr 0.2627, Kb 0.0593; ffmpeg's name).  NO transfer function is applied anywhere:
+the network sees the source's own transfer (gamma, PQ, HLG) and its output carries the same one.
+
+Layouts of one frame, a (3 h / 2, w) uint8 array (uint16 for deep samples), h and w even:
   nv12  h rows of Y, then h / 2 rows of interleaved Cb, Cr
   nv21  h rows of Y, then h / 2 rows of interleaved Cr, Cb
   i420  h rows of Y, then the (h / 2, w / 2) Cb plane, then the Cr plane (each stored contiguously in h / 4 rows' worth of bytes)
@@ -42,7 +57,8 @@ from __future__ import annotations
 import numpy as np
 
 FORMATS = ("nv12", "nv21", "i420")
-MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}   # Kr, Kb
+MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020nc": (0.2627, 0.0593)}   # Kr, Kb
+DEPTHS = (8, 10, 12, 16)
 _F = np.float32
 
 
@@ -52,10 +68,27 @@ def check_fmt(fmt: str) -> str:
     return fmt
 
 
-def csc(matrix: str = "bt601", full_range: bool = False):
-    """(to_rgb, from_rgb): float32[12] each, see the module docstring."""
+def check_depth(depth) -> int:
+    if isinstance(depth, bool) or depth not in DEPTHS:
+        raise RuntimeError(f"unsupported sample depth {depth!r}: one of {DEPTHS}")
+    return int(depth)
+
+
+def container(depth: int, fmt: str = "nv12", msb=None):
+    """(dtype, k, maxcode, shift) of a sample of `depth` bits in layout `fmt`: see "Deep samples" in the module docstring."""
+    depth = check_depth(depth)
+    check_fmt(fmt)
+    if depth == 8:
+        return np.uint8, 0, 255, 0
+    msb = (fmt != "i420") if msb is None else bool(msb)
+    return np.uint16, depth - 8, (1 << depth) - 1, (16 - depth) if msb else 0
+
+
+def csc(matrix: str = "bt601", full_range: bool = False, depth: int = 8):
+    """(to_rgb, from_rgb): float32[12] each, in byte units at every depth, see the module docstring."""
     if matrix not in MATRICES:
         raise RuntimeError(f"unknown colour matrix {matrix!r}: one of {tuple(MATRICES)}")
+    depth = check_depth(depth)
     if matrix == "bt601" and not full_range:
         fr = np.array([[65.481, 128.553, 24.966, 16.0], [-37.797, -74.203, 112.0, 128.0], [112.0, -93.786, -18.214, 128.0]])
         # ycbcr2rgb: rgb255 = (ycc_bytes @ M) * 255 + off  ->  rgb = ycc_bytes @ M + off / 255
@@ -67,7 +100,8 @@ def csc(matrix: str = "bt601", full_range: bool = False):
         return to.astype(_F).reshape(12), fr.astype(_F).reshape(12)
     kr, kb = MATRICES[matrix]
     kg = 1.0 - kr - kb
-    ys, cs, oy = (255.0, 255.0, 0.0) if full_range else (219.0, 224.0, 16.0)
+    top = ((1 << depth) - 1) / float(1 << (depth - 8))          # the full-range code of E' = 1 in byte units: 255, 255.75, ...
+    ys, cs, oy = (top, top, 0.0) if full_range else (219.0, 224.0, 16.0)
     fr = np.array([[ys * kr, ys * kg, ys * kb, oy],
                    [-cs * kr / (2 * (1 - kb)), -cs * kg / (2 * (1 - kb)), cs * 0.5, 128.0],
                    [cs * 0.5, -cs * kg / (2 * (1 - kr)), -cs * kb / (2 * (1 - kr)), 128.0]])
@@ -92,9 +126,12 @@ def frame_size(shape):
     return 2 * hh // 3, w
 
 
-def split(frame: np.ndarray, fmt: str = "nv12"):
-    """frame (..., 3h/2, w) uint8 -> views Y (..., h, w), Cb, Cr (..., h/2, w/2)."""
+def split(frame: np.ndarray, fmt: str = "nv12", depth=None, msb=None):
+    """frame (..., 3h/2, w) uint8 (uint16: deep) -> views Y (..., h, w), Cb, Cr (..., h/2, w/2) of the samples AS STORED (words, not
+    codes: decode / encode translate).  depth, if given, must agree with the dtype; msb does not change a view."""
     check_fmt(fmt)
+    if depth is not None and frame.dtype != container(depth, fmt, msb)[0]:
+        raise RuntimeError(f"a {depth}-bit frame is a {np.dtype(container(depth, fmt, msb)[0]).name} array, got {frame.dtype}")
     h, w = frame_size(frame.shape)
     lead = frame.shape[:-2]
     Y = frame[..., :h, :]
@@ -106,13 +143,29 @@ def split(frame: np.ndarray, fmt: str = "nv12"):
     return (Y, c[..., 0], c[..., 1]) if fmt == "nv12" else (Y, c[..., 1], c[..., 0])
 
 
-def join(Y: np.ndarray, Cb: np.ndarray, Cr: np.ndarray, fmt: str = "nv12") -> np.ndarray:
+def join(Y: np.ndarray, Cb: np.ndarray, Cr: np.ndarray, fmt: str = "nv12", depth: int = 8, msb=None) -> np.ndarray:
+    """The frame of the stored samples Y, Cb, Cr (bytes, or words for a deep frame: the inverse of split)."""
     check_fmt(fmt)
     h, w = Y.shape[-2:]
-    out = np.empty(Y.shape[:-2] + frame_shape(h, w), dtype=np.uint8)
+    out = np.empty(Y.shape[:-2] + frame_shape(h, w), dtype=container(depth, fmt, msb)[0])
     oy, ocb, ocr = split(out, fmt)
     oy[...], ocb[...], ocr[...] = Y, Cb, Cr
     return out
+
+
+def decode(words: np.ndarray, depth: int, fmt: str = "nv12", msb=None) -> np.ndarray:
+    """stored samples -> codes (uint16): word >> shift (MSB-aligned) or min(word, maxcode) (LSB-aligned)."""
+    dt, _, maxcode, shift = container(depth, fmt, msb)
+    words = np.asarray(words)
+    if words.dtype != dt:
+        raise RuntimeError(f"a {depth}-bit sample is a {np.dtype(dt).name}, got {words.dtype}")
+    return np.minimum(words >> shift, maxcode).astype(np.uint16) if depth > 8 else words
+
+
+def encode(codes: np.ndarray, depth: int, fmt: str = "nv12", msb=None) -> np.ndarray:
+    """codes -> stored samples: code << shift."""
+    dt, _, _, shift = container(depth, fmt, msb)
+    return (np.asarray(codes).astype(dt) << shift).astype(dt) if depth > 8 else np.asarray(codes).astype(dt)
 
 
 # ------------------------------------------------------------------------------------------------ the two directions
@@ -134,23 +187,43 @@ def ycc_to_rgb(Y, Cb, Cr, to_rgb) -> np.ndarray:
     return out
 
 
-def yuv420_to_planes(frame: np.ndarray, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False, pad=(0, 0)) -> np.ndarray:
-    """frame (3h/2, w) or (B, 3h/2, w) uint8 -> (B, 3, h + pad[0], w + pad[1]) float32 RGB planes, reflect-padded bottom / right."""
+def ycc_to_rgb_deep(Y, Cb, Cr, to_rgb, depth: int) -> np.ndarray:
+    """The same for n-bit CODES (uint16 arrays of one shape): s = float32(code) * 2^-k, then ycc_to_rgb's expression on s."""
+    m = np.asarray(to_rgb, dtype=_F).reshape(3, 4)
+    inv = _F(1.0 / (1 << (check_depth(depth) - 8)))
+    y = Y.astype(_F) * inv
+    cb = Cb.astype(_F) * inv - _F(128.0)
+    cr = Cr.astype(_F) * inv - _F(128.0)
+    out = np.empty((3,) + y.shape, dtype=_F)
+    for c in range(3):
+        v = ((m[c, 0] * y + m[c, 1] * cb) + m[c, 2] * cr) + m[c, 3]
+        out[c] = np.minimum(np.maximum(v, _F(0.0)), _F(1.0))
+    return out
+
+
+def yuv420_to_planes(frame: np.ndarray, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False, pad=(0, 0), depth: int = 8,
+                     msb=None) -> np.ndarray:
+    """frame (3h/2, w) or (B, 3h/2, w) uint8 (uint16 with depth 10 / 12 / 16) -> (B, 3, h + pad[0], w + pad[1]) float32 RGB planes,
+    reflect-padded bottom / right."""
     frame = np.asarray(frame)
-    if frame.dtype != np.uint8 or frame.ndim not in (2, 3):
-        raise RuntimeError(f"expected a (3h/2, w) or (B, 3h/2, w) uint8 frame, got {frame.shape} {frame.dtype}")
+    dt = container(depth, fmt, msb)[0]
+    if frame.dtype != dt or frame.ndim not in (2, 3):
+        raise RuntimeError(f"expected a (3h/2, w) or (B, 3h/2, w) {np.dtype(dt).name} frame, got {frame.shape} {frame.dtype}")
     if frame.ndim == 2:
         frame = frame[None]
     h, w = frame_size(frame.shape)
     if pad[0] >= h or pad[1] >= w or pad[0] < 0 or pad[1] < 0:
         raise RuntimeError(f"a {h}x{w} frame cannot be reflect-padded by {tuple(pad)}: the padding must be smaller than the frame")
-    to_rgb, _ = csc(matrix, full_range)
+    to_rgb, _ = csc(matrix, full_range, depth)
     Y, Cb, Cr = split(frame, fmt)
     sy, sx = _reflect_index(h, h + pad[0]), _reflect_index(w, w + pad[1])
     Yp = Y[:, sy][:, :, sx]
     Cbp = Cb[:, sy >> 1][:, :, sx >> 1]
     Crp = Cr[:, sy >> 1][:, :, sx >> 1]
-    return np.ascontiguousarray(ycc_to_rgb(Yp, Cbp, Crp, to_rgb).transpose(1, 0, 2, 3))
+    if depth == 8:
+        return np.ascontiguousarray(ycc_to_rgb(Yp, Cbp, Crp, to_rgb).transpose(1, 0, 2, 3))
+    Yp, Cbp, Crp = (decode(a, depth, fmt, msb) for a in (Yp, Cbp, Crp))
+    return np.ascontiguousarray(ycc_to_rgb_deep(Yp, Cbp, Crp, to_rgb, depth).transpose(1, 0, 2, 3))
 
 
 def _byte(v: np.ndarray) -> np.ndarray:
@@ -169,9 +242,14 @@ def rgb_to_ycc_float(planes: np.ndarray, from_rgb):
     return Y, cb, cr
 
 
-def planes_to_yuv420(planes: np.ndarray, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False, crop=None) -> np.ndarray:
-    """planes (B, 3, Hs, Ws) float32 -> (B, 3 h_out / 2, w_out) uint8 in layout `fmt`; crop = (h_out, w_out), even, the
-    top-left pixels kept (default: all)."""
+def _code(v: np.ndarray, k: int, maxcode: int) -> np.ndarray:
+    return np.rint(np.minimum(np.maximum(v * _F(1 << k), _F(0.0)), _F(maxcode))).astype(np.uint16)
+
+
+def planes_to_yuv420(planes: np.ndarray, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False, crop=None, out_depth: int = 8,
+                     msb=None) -> np.ndarray:
+    """planes (B, 3, Hs, Ws) float32 -> (B, 3 h_out / 2, w_out) uint8 (uint16 with out_depth 10 / 12 / 16) in layout `fmt`;
+    crop = (h_out, w_out), even, the top-left pixels kept (default: all)."""
     planes = np.asarray(planes, dtype=_F)
     if planes.ndim != 4 or planes.shape[1] != 3:
         raise RuntimeError(f"expected (B,3,Hs,Ws) float32 planes, got {planes.shape}")
@@ -179,7 +257,11 @@ def planes_to_yuv420(planes: np.ndarray, *, fmt: str = "nv12", matrix: str = "bt
     frame_shape(ho, wo)
     if ho > planes.shape[2] or wo > planes.shape[3]:
         raise RuntimeError(f"crop {(ho, wo)} does not lie inside the planes {planes.shape[2:]}")
-    _, k = csc(matrix, full_range)
+    _, kk, maxcode, _ = container(out_depth, fmt, msb)
+    _, k = csc(matrix, full_range, out_depth)
     Y, cb, cr = rgb_to_ycc_float(planes[:, :, :ho, :wo], k)
     box = lambda c, off: ((c[:, 0::2, 0::2] + c[:, 0::2, 1::2]) + (c[:, 1::2, 0::2] + c[:, 1::2, 1::2])) * _F(0.25) + off
-    return join(_byte(Y), _byte(box(cb, k[7])), _byte(box(cr, k[11])), fmt)
+    if out_depth == 8:
+        return join(_byte(Y), _byte(box(cb, k[7])), _byte(box(cr, k[11])), fmt)
+    q = lambda v: encode(_code(v, kk, maxcode), out_depth, fmt, msb)
+    return join(q(Y), q(box(cb, k[7])), q(box(cr, k[11])), fmt, out_depth, msb)
