@@ -57,15 +57,7 @@ class WindowAttention(nn.Module):
         dt = ops.DTYPE_CODE[self.compute_dtype]
         C = self.dim
 
-        def lin(w, b):
-            if ops.linear_supported(w.shape[0], w.shape[1], dt):
-                pw = ops.pack_linear_weight(w, b, dt, dev)
-                pw.frag = True
-            else:
-                pw = ops.pack_conv_weight(w, b, dt, dev)
-                pw.frag = False
-            return pw
-
+        lin = lambda w, b: ops.pack_pointwise(w, b, dt, dev)
         w = self.qkv.weight.detach().float().clone()
         b = (self.qkv.bias.detach().float().clone() if self.qkv.bias is not None else torch.zeros(3 * C, device=w.device))
         w[:C] *= self.scale   # q * scale (swinir_arch.py:149) folded into the projection

@@ -239,14 +239,7 @@ class HATEngine:
         b = sd.get(bkey) if bkey else None
         o, i = w.shape[0], w.reshape(w.shape[0], -1).shape[1]
 
-        def pack(wm, bias):
-            if ops.linear_supported(wm.shape[0], wm.shape[1], self.dtype):
-                pw = ops.pack_linear_weight(wm, bias, self.dtype, self.dev, scale=scale)
-                pw.frag = True
-                return pw
-            pw = ops.pack_conv_weight(wm, bias, self.dtype, self.dev, scale=scale)
-            pw.frag = False
-            return pw
+        pack = lambda wm, bias: ops.pack_pointwise(wm, bias, self.dtype, self.dev, scale=scale)
         w2 = w.reshape(o, -1)
         if w2.shape[1] == i and i > 512 and i % 16 == 0 and not ops.linear_supported(o, i, self.dtype):
             # K too wide for any tiling (HATX's SGFN fc2 at embed_dim 180: 720 -> 180; its fp32 rows do not fit a hat_conv tile):
@@ -356,7 +349,7 @@ class HATEngine:
                          and not opt.no_hab_tail)
         # third-generation tail (activation-stationary fc1, weights shared through LDS): its own packing;
         # HAT_TAIL_V2=1 keeps hat_hab_tail for A/B runs
-        if hb.tail144_ok and hb.ffn.khalf == "v2" and not opt.tail_v2:
+        if hb.tail144_ok and hb.ffn.layout == "ffn2" and not opt.tail_v2:
             hb.ffn3 = ops.pack_ffn3(*fw, *hb.n2, dev)
         # embed_dim 180 (HAT / HAT-L): hat_hab_tail3 with the CAB's c2 as a map (their squeeze is 60 wide: no fold)
         if (hb.fold is None and C == 180 and fp16_ok and ops.tail3_supported(C, hid2 // 2, dt) and hb.esc.pdim == 16

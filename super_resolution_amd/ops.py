@@ -13,10 +13,12 @@ import torch
 from . import _lib
 from ._lib import (ACT_GELU, ACT_LRELU, ACT_NONE, HAT_BF16, HAT_F32, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T,
                    X_NCHW_F32_MEAN, X_NHWC_F32, X_NHWC_T, HatAggrCabDesc, HatCabFoldDesc, HatConvDesc, HatFfnDesc, HatHabTailDesc, HatMlpDesc)
+# host-side weight packing lives in packing.py; ops.pack_* / ops.Packed* stay the names the engine, the tools and the tests use
+from .packing import (FP16_SAFE, KC, TORCH_DTYPE, PackedConv, PackedFFN, PackedMlp, choose_nt, choose_nt_linear,  # noqa: F401
+                      ffn_fp16_range_bound, pack_cab_squeeze, pack_cab_w2f, pack_conv_weight, pack_ffn, pack_ffn2, pack_ffn3,
+                      pack_linear_weight, pack_ocab_mlp, pack_ocab_qkv, pack_pointwise)
 
-TORCH_DTYPE = {HAT_F32: torch.float32, HAT_BF16: torch.bfloat16}
 DTYPE_CODE = {"f32": HAT_F32, "fp32": HAT_F32, "float32": HAT_F32, "bf16": HAT_BF16, "bfloat16": HAT_BF16}
-KC = {HAT_F32: 32, HAT_BF16: 64}
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -71,61 +73,8 @@ def _timed(name, flops, fn, tag="", nbytes=0.0):
 _TNAME = {HAT_F32: "float", HAT_BF16: "__bf16"}
 
 
-class PackedConv:
-    """Packed weights of one conv/linear layer (see HatConvDesc in include/hat_mi355x.h)."""
-    __slots__ = ("w", "bias", "ksize", "cin", "kpad", "nt", "n_slices", "nout", "w_bstride", "frag", "ksplit")
-
-    def __init__(self, w, bias, ksize, cin, kpad, nt, n_slices, nout, w_bstride=0, frag=False):
-        self.w, self.bias, self.ksize, self.cin, self.kpad = w, bias, ksize, cin, kpad
-        self.nt, self.n_slices, self.nout, self.w_bstride = nt, n_slices, nout, w_bstride
-        self.frag = frag  # True: MFMA-fragment order for hat_linear; False: [Npad][Kpad] rows for hat_conv
-        self.ksplit = None  # second half of a layer whose K is split over two launches (engine._lin)
-
-    @property
-    def npad(self):
-        return self.nt * 16 * self.n_slices
-
-
-def choose_nt(nout: int):
-    """n-tiles per slice in {12, 9, 8, 4, 1}: least padded work, weighted by LDS fragment reads per MFMA."""
-    best = None
-    for nt in (12, 9, 8, 4, 1):
-        npad = -(-nout // (16 * nt)) * 16 * nt
-        cost = npad * (nt + 2) / nt
-        if best is None or cost < best[0]:
-            best = (cost, nt, npad // (16 * nt))
-    return best[1], best[2]
-
-
-def pack_conv_weight(weight: torch.Tensor, bias: Optional[torch.Tensor], dtype: int, device, out_perm=None,
-                     scale: float = 1.0, nt: Optional[int] = None) -> PackedConv:
-    """weight (O, I, k, k) [or (O, I) for nn.Linear] -> [Npad][Kpad] with K = tap * Cin_p + ci."""
-    w = weight.detach().to(torch.float32).cpu()
-    if w.dim() == 2:
-        w = w[:, :, None, None]
-    o, i, kh, kw = w.shape
-    assert kh == kw
-    b = torch.zeros(o) if bias is None else bias.detach().to(torch.float32).cpu()
-    if scale != 1.0:
-        w, b = w * scale, b * scale
-    if out_perm is not None:
-        w, b = w[out_perm], b[out_perm]
-    cin_p = (i + 7) // 8 * 8
-    k = kh * kw * cin_p
-    if nt is None:
-        nt, n_slices = choose_nt(o)
-    else:
-        n_slices = -(-o // (16 * nt))
-    kc = KC[dtype] * (3 if nt == 1 else (2 if nt <= 4 else 1))  # weight chunk length of hat_conv.hip: longer for few n-tiles
-    kpad = -(-k // kc) * kc
-    npad = nt * 16 * n_slices
-    wp = torch.zeros(npad, kpad, dtype=torch.float32)
-    wt = torch.zeros(o, kh * kw, cin_p)
-    wt[:, :, :i] = w.permute(0, 2, 3, 1).reshape(o, kh * kw, i)
-    wp[:o, :k] = wt.reshape(o, k)
-    bp = torch.zeros(npad, dtype=torch.float32)
-    bp[:o] = b
-    return PackedConv(wp.to(TORCH_DTYPE[dtype]).to(device).contiguous(), bp.to(device), kh, i, kpad, nt, n_slices, o)
+def _mean4(mean):
+    return (C.c_float * 4)(*[float(mean[i]) if i < len(mean) else 0.0 for i in range(4)])
 
 
 def _stream16(r1, out, out_mode: int) -> int:
@@ -165,8 +114,7 @@ def conv(pw: PackedConv, x: torch.Tensor, out: torch.Tensor, *, B: int, H: int, 
     d.ldo, d.out_mode, d.act = ldo, out_mode, act
     d.ldr1, d.ldr2, d.r2scale_bstride, d.ps_r = ldr1, ldr2, r2scale_bstride, ps_r
     d.in_scale, d.out_scale = in_scale, out_scale
-    for i in range(4):
-        d.mean[i] = float(mean[i]) if i < len(mean) else 0.0
+    d.mean = _mean4(mean)
     d.dtype = dtype
     d.reserved0 = _stream16(r1, out, out_mode)
     name, flops = "conv_kernel", 0.0
@@ -273,69 +221,8 @@ def ocab_attention_kb(q, kv, bias_rot, kb, out, *, B: int, H: int, W: int, C_: i
                                   dtype, _stream()), "hat_ocab_attention_kb"))
 
 
-class PackedMlp:
-    """fc1 / fc2 of the OCAB's MLP in hat_ocab_mlp's fragment layouts (include/hat_mi355x.h)."""
-    __slots__ = ("w1f", "b1", "w2f", "b2", "C", "hidden")
-
-
 def ocab_mlp_supported(C_: int, hidden: int, dtype: int) -> bool:
     return C_ == 144 and hidden == 288 and dtype == HAT_BF16
-
-
-def pack_ocab_mlp(fc1_w, fc1_b, fc2_w, fc2_b, device) -> PackedMlp:
-    f = lambda t: t.detach().to(torch.float32).cpu()
-    W1, b1, W2, b2 = f(fc1_w), f(fc1_b), f(fc2_w), f(fc2_b)
-    hid, C_ = W1.shape
-    assert (C_, hid) == (144, 288) and W2.shape == (C_, hid)
-    lane = torch.arange(64)
-    n16, g4 = lane & 15, lane >> 4
-    # fc1: full fragments [nt][ks][lane][j] = W1[16 nt + n16][32 ks + 8 g + j], then the 16-deep tail [nt][lane][j] = W1[..][128 + 4 g + j]
-    r = (torch.arange(18)[:, None, None, None] * 16 + n16[None, None, :, None]).expand(18, 4, 64, 8)
-    c = (torch.arange(4)[None, :, None, None] * 32 + 8 * g4[None, None, :, None] + torch.arange(8)[None, None, None, :]).expand(18, 4, 64, 8)
-    full = W1[r, c]
-    rh = (torch.arange(18)[:, None, None] * 16 + n16[None, :, None]).expand(18, 64, 4)
-    ch = (128 + 4 * g4[None, :, None] + torch.arange(4)[None, None, :]).expand(18, 64, 4)
-    half = W1[rh, ch]
-    w1f = torch.cat([full.reshape(-1), half.reshape(-1)])
-    # fc2: [nt2][kk][lane][j] = W2[16 nt2 + n16][unit], unit = 32 kk + 4 g + j (j < 4) | 32 kk + 16 + 4 g + j - 4
-    j8 = torch.arange(8)
-    unit = (torch.arange(9)[:, None, None] * 32 + torch.where(j8[None, None, :] < 4, 4 * g4[None, :, None] + j8[None, None, :],
-                                                               16 + 4 * g4[None, :, None] + j8[None, None, :] - 4))   # (kk, lane, j)
-    r2 = (torch.arange(9)[:, None, None, None] * 16 + n16[None, None, :, None]).expand(9, 9, 64, 8)
-    w2f = W2[r2, unit[None].expand(9, 9, 64, 8)]
-    p = PackedMlp()
-    p.w1f = w1f.to(torch.bfloat16).contiguous().to(device)
-    p.w2f = w2f.to(torch.bfloat16).contiguous().to(device)
-    p.b1, p.b2, p.C, p.hidden = b1.contiguous().to(device), b2.contiguous().to(device), C_, hid
-    return p
-
-
-def _pack_fc1_frags(W1: torch.Tensor) -> torch.Tensor:
-    """(16 nt, 144) fp32 -> hat_ocab_mlp's fc1 layout: [nt][4][64 lanes][8] full k-steps then [nt][64][4] the 16-deep tail."""
-    nt_ = W1.shape[0] // 16
-    lane = torch.arange(64)
-    n16, g4 = lane & 15, lane >> 4
-    r = (torch.arange(nt_)[:, None, None, None] * 16 + n16[None, None, :, None]).expand(nt_, 4, 64, 8)
-    c = (torch.arange(4)[None, :, None, None] * 32 + 8 * g4[None, None, :, None] + torch.arange(8)[None, None, None, :]).expand(nt_, 4, 64, 8)
-    rh = (torch.arange(nt_)[:, None, None] * 16 + n16[None, :, None]).expand(nt_, 64, 4)
-    ch = (128 + 4 * g4[None, :, None] + torch.arange(4)[None, None, :]).expand(nt_, 64, 4)
-    return torch.cat([W1[r, c].reshape(-1), W1[rh, ch].reshape(-1)])
-
-
-def pack_ocab_qkv(q_w, q_b, kv_w, kv_b, qscale: float, device) -> PackedMlp:
-    """Stacked [q_proj * qscale ; kv_proj] (432 x 144) for hat_ocab_qkv."""
-    f = lambda t: t.detach().to(torch.float32).cpu()
-    Wq, Wkv = f(q_w) * qscale, f(kv_w)
-    bq = (torch.zeros(Wq.shape[0]) if q_b is None else f(q_b)) * qscale
-    bkv = torch.zeros(Wkv.shape[0]) if kv_b is None else f(kv_b)
-    W = torch.cat([Wq, Wkv], 0)
-    assert W.shape == (432, 144)
-    p = PackedMlp()
-    p.w1f = _pack_fc1_frags(W).to(torch.bfloat16).contiguous().to(device)
-    p.b1 = torch.cat([bq, bkv]).contiguous().to(device)
-    p.w2f = p.b2 = None
-    p.C, p.hidden = 144, 432
-    return p
 
 
 def ocab_qkv(pm: PackedMlp, x, out, *, B: int, H: int, W: int, ldx: int, ldo: int, dtype: int):
@@ -394,28 +281,6 @@ def cab_squeeze_supported(C_: int, mid: int, W: int, dtype: int) -> bool:
     return dtype == HAT_BF16 and 128 < C_ <= 160 and C_ % 8 == 0 and mid <= 8 and W % 16 == 0
 
 
-def pack_cab_squeeze(weight: torch.Tensor, bias: torch.Tensor, device):
-    """3x3 weight (mid <= 8, C, 3, 3) -> the 6 x ceil(C/32) MFMA A fragments the row-sweep kernel keeps in registers
-    (hat_cab_squeeze / hat_conv3x3_to_planes), + 8 bias floats."""
-    w = weight.detach().to(torch.float32).cpu()
-    mid, cin = w.shape[0], w.shape[1]
-    ks = -(-cin // 32)
-    A = torch.zeros(6, 16, 32 * ks)                  # [tile][row][k]
-    for kx in range(3):
-        A[2 * kx, 0:mid, :cin] = w[:, :, 0, kx]      # ky = 0 -> output row r + 1
-        A[2 * kx, 8:8 + mid, :cin] = w[:, :, 1, kx]  # ky = 1 -> output row r
-        A[2 * kx + 1, 0:mid, :cin] = w[:, :, 2, kx]  # ky = 2 -> output row r - 1
-    lane = torch.arange(64)
-    shape = (6, ks, 64, 8)
-    row = (lane & 15)[None, None, :, None].expand(shape)
-    col = (torch.arange(ks)[None, :, None, None] * 32 + 8 * (lane >> 4)[None, None, :, None] + torch.arange(8)[None, None, None, :]).expand(shape)
-    tile = torch.arange(6)[:, None, None, None].expand(shape)
-    wpk = A[tile, row, col].to(torch.bfloat16).contiguous().to(device)
-    b8 = torch.zeros(8)
-    b8[:mid] = bias.detach().to(torch.float32).cpu()
-    return wpk, b8.to(device)
-
-
 def conv3x3_to_planes_supported(nout: int, cin: int, W: int, dtype: int) -> bool:
     return dtype == HAT_BF16 and cin == 64 and nout <= 8 and W % 16 == 0
 
@@ -424,7 +289,7 @@ def conv3x3_to_planes(x, wpk, bias8, out, *, B: int, H: int, W: int, C_: int, ld
                       dtype: int):
     """conv_last on the row-sweep kernel: (conv3x3 + bias) * out_scale + mean -> (B, n_out, H, W) fp32."""
     lib = _lib.load()
-    m4 = (C.c_float * 4)(*[float(mean[i]) if i < len(mean) else 0.0 for i in range(4)])
+    m4 = _mean4(mean)
     _timed("cab_squeeze_kernel<2, planes>", 2.0 * B * H * W * 9 * C_ * n_out, lambda: _lib.check(
         lib.hat_conv3x3_to_planes(_ptr(x), _ptr(wpk), _ptr(bias8), _ptr(out), B, H, W, C_, ldx, n_out, out_scale, m4, dtype,
                                   _stream()), "hat_conv3x3_to_planes"), tag=f"k3 {C_}->{n_out} {H}x{W} row sweep planes")
@@ -435,7 +300,7 @@ def conv3x3_to_u8(x, wpk, bias8, out, *, B: int, H: int, W: int, C_: int, ldx: i
     """conv_last with the 8-bit conversion as its epilogue: out (B, h_out, w_out, 3) uint8 = tensor2img of what
     conv3x3_to_planes writes, cropped to the top-left h_out x w_out pixels; no fp32 image is written."""
     lib = _lib.load()
-    m4 = (C.c_float * 4)(*[float(mean[i]) if i < len(mean) else 0.0 for i in range(4)])
+    m4 = _mean4(mean)
     if out.dtype != torch.uint8 or not out.is_cuda or tuple(out.shape) != (B, h_out, w_out, 3) or out.stride(-1) != 1 or out.stride(-2) != 3:
         raise RuntimeError("conv3x3_to_u8 needs a (B,h_out,w_out,3) uint8 device destination with interleaved pixels")
     _timed("cab_squeeze_kernel<2, u8>", 2.0 * B * H * W * 9 * C_ * 3, lambda: _lib.check(
@@ -617,6 +482,11 @@ def _deep_args(y, depth, msb, what: str):
     return (int(depth), int(bool(msb)))
 
 
+def _deep_entry(entry: str, deep):
+    """(C entry point, record-name suffix, tag suffix) of the 8-bit (deep == ()) or the deep-sample twin of a 4:2:0 launch."""
+    return (entry.format("p16"), "<u16>", f"p{deep[0]}") if deep else (entry.format(""), "", "")
+
+
 def _f12(m):
     m = [float(v) for v in m]
     if len(m) != 12:
@@ -637,14 +507,10 @@ def yuv420_to_planes(y, cb, cr, dst, to_rgb, *, depth=None, msb=False):
         raise RuntimeError(f"yuv420_to_planes needs a (B,3,Hp>=h,Wp>=w) fp32 destination on {y.device}, got {tuple(dst.shape)} {dst.dtype} on "
                            f"{dst.device} for frames {tuple(y.shape)}")
     m = _f12(to_rgb)
-    if deep:
-        _timed("yuv420_to_planes_kernel<u16>", 0.0, lambda: _lib.check(
-            lib.hat_yuv420p16_to_planes(*blk, _ptr(dst), B, h, w, dst.shape[2], dst.shape[3], m, *deep, _stream()), "hat_yuv420p16_to_planes"),
-            tag=f"yuv420p{deep[0]} {h}x{w} -> planes {dst.shape[2]}x{dst.shape[3]}")
-        return
-    _timed("yuv420_to_planes_kernel", 0.0, lambda: _lib.check(
-        lib.hat_yuv420_to_planes(*blk, _ptr(dst), B, h, w, dst.shape[2], dst.shape[3], m, _stream()), "hat_yuv420_to_planes"),
-        tag=f"yuv420 {h}x{w} -> planes {dst.shape[2]}x{dst.shape[3]}")
+    entry, u16, p = _deep_entry("hat_yuv420{}_to_planes", deep)
+    _timed("yuv420_to_planes_kernel" + u16, 0.0, lambda: _lib.check(
+        getattr(lib, entry)(*blk, _ptr(dst), B, h, w, dst.shape[2], dst.shape[3], m, *deep, _stream()), entry),
+        tag=f"yuv420{p} {h}x{w} -> planes {dst.shape[2]}x{dst.shape[3]}")
 
 
 def planes_to_yuv420(src, y, cb, cr, from_rgb, *, depth=None, msb=False):
@@ -657,14 +523,10 @@ def planes_to_yuv420(src, y, cb, cr, from_rgb, *, depth=None, msb=False):
     if src.dim() != 4 or src.shape[0] != B or src.shape[1] != 3 or src.dtype != torch.float32 or src.device != y.device:
         raise RuntimeError(f"planes_to_yuv420 needs (B,3,Hs,Ws) fp32 planes on {y.device}, got {tuple(src.shape)} {src.dtype} on {src.device}")
     m = _f12(from_rgb)
-    if deep:
-        _timed("planes_to_yuv420_kernel<u16>", 0.0, lambda: _lib.check(
-            lib.hat_planes_to_yuv420p16(_ptr(src), B, src.shape[2], src.shape[3], *blk, h, w, m, *deep, _stream()), "hat_planes_to_yuv420p16"),
-            tag=f"planes {src.shape[2]}x{src.shape[3]} -> yuv420p{deep[0]} {h}x{w}")
-        return
-    _timed("planes_to_yuv420_kernel", 0.0, lambda: _lib.check(
-        lib.hat_planes_to_yuv420(_ptr(src), B, src.shape[2], src.shape[3], *blk, h, w, m, _stream()), "hat_planes_to_yuv420"),
-        tag=f"planes {src.shape[2]}x{src.shape[3]} -> yuv420 {h}x{w}")
+    entry, u16, p = _deep_entry("hat_planes_to_yuv420{}", deep)
+    _timed("planes_to_yuv420_kernel" + u16, 0.0, lambda: _lib.check(
+        getattr(lib, entry)(_ptr(src), B, src.shape[2], src.shape[3], *blk, h, w, m, *deep, _stream()), entry),
+        tag=f"planes {src.shape[2]}x{src.shape[3]} -> yuv420{p} {h}x{w}")
 
 
 def conv3x3_to_yuv420(x, wpk, bias8, y, cb, cr, *, B: int, H: int, W: int, C_: int, ldx: int, out_scale: float, mean, from_rgb, dtype: int,
@@ -677,16 +539,12 @@ def conv3x3_to_yuv420(x, wpk, bias8, y, cb, cr, *, B: int, H: int, W: int, C_: i
     deep = _deep_args(y, depth, msb, "conv3x3_to_yuv420")
     if y.shape[0] != B:
         raise RuntimeError(f"conv3x3_to_yuv420: destination batch {y.shape[0]} != {B}")
-    m4 = (C.c_float * 4)(*[float(mean[i]) if i < len(mean) else 0.0 for i in range(4)])
+    m4 = _mean4(mean)
     m = _f12(from_rgb)
-    if deep:
-        _timed("cab_squeeze_kernel<2, yuv420p16>", 2.0 * B * H * W * 9 * C_ * 3, lambda: _lib.check(
-            lib.hat_conv3x3_to_yuv420p16(_ptr(x), _ptr(wpk), _ptr(bias8), *blk, B, H, W, C_, ldx, y.shape[1], y.shape[2], out_scale, m4, m, dtype,
-                                         *deep, _stream()), "hat_conv3x3_to_yuv420p16"), tag=f"k3 {C_}->3 {H}x{W} row sweep yuv420p{deep[0]}")
-        return
-    _timed("cab_squeeze_kernel<2, yuv420>", 2.0 * B * H * W * 9 * C_ * 3, lambda: _lib.check(
-        lib.hat_conv3x3_to_yuv420(_ptr(x), _ptr(wpk), _ptr(bias8), *blk, B, H, W, C_, ldx, y.shape[1], y.shape[2], out_scale, m4, m, dtype,
-                                  _stream()), "hat_conv3x3_to_yuv420"), tag=f"k3 {C_}->3 {H}x{W} row sweep yuv420")
+    entry, _, p = _deep_entry("hat_conv3x3_to_yuv420{}", deep)
+    _timed(f"cab_squeeze_kernel<2, yuv420{'p16' if deep else ''}>", 2.0 * B * H * W * 9 * C_ * 3, lambda: _lib.check(
+        getattr(lib, entry)(_ptr(x), _ptr(wpk), _ptr(bias8), *blk, B, H, W, C_, ldx, y.shape[1], y.shape[2], out_scale, m4, m, dtype,
+                            *deep, _stream()), entry), tag=f"k3 {C_}->3 {H}x{W} row sweep yuv420{p}")
 
 
 def u8_metrics_flags(*, y_channel: bool, bgr: bool, psnr: bool, ssim: bool) -> int:
@@ -759,83 +617,9 @@ def window_attention(q, kv, bias_flip, out, *, B: int, H: int, W: int, C_: int, 
 # ------------------------------------------------------------------------------------------------
 # fused feed-forward half of the HAB (hat_ffn)
 # ------------------------------------------------------------------------------------------------
-class PackedFFN:
-    __slots__ = ("w1f", "b1", "dww", "dwb", "w2f", "b2", "chunks", "C", "hid", "nt", "ks", "khalf")
-
-
 def ffn_supported(C_: int) -> bool:
     """Shapes hat_ffn is instantiated for (anything else uses the unfused kernels)."""
     return C_ in (144, 180) or (C_ <= 32 and C_ % 32 != 16 and C_ >= 8)
-
-
-def pack_ffn(fc1_w, fc1_b, dw_w, dw_b, fc2_w, fc2_b, dtype: int, device) -> PackedFFN:
-    """Fragment-pack GatedDconvFFN weights (hat_arch.py:99-104) for hat_ffn; layouts in include/hat_mi355x.h."""
-    f = lambda t: t.detach().to(torch.float32).cpu()
-    W1, b1, Wd, bd, W2, b2 = f(fc1_w), f(fc1_b), f(dw_w).reshape(-1, 9), f(dw_b), f(fc2_w), f(fc2_b)
-    C_, hid = W2.shape
-    assert W1.shape == (2 * hid, C_) and Wd.shape[0] == 2 * hid
-    chunks = -(-hid // 32)
-    hid_p = 32 * chunks
-    khalf = False
-    ks = -(-(C_ + 1) // 32)          # K padded to a multiple of 32 with room for the bias column at k = C
-    nt = 9 if C_ == 144 else (12 if C_ == 180 else 2)
-    tdt = TORCH_DTYPE[dtype]
-    lane = torch.arange(64)
-    n16, g4 = lane & 15, lane >> 4
-    j8 = torch.arange(8)
-    # ---- fc1: w1f[chunk][nt4][ks][lane][8]; column C of the padded weight matrix is the fc1 bias (the kernel
-    # keeps a constant 1 in column C of the LayerNorm'ed activations)
-    W1p = torch.zeros(2 * hid_p, ks * 32)
-    W1p[:hid, :C_] = W1[:hid]
-    W1p[hid_p:hid_p + hid, :C_] = W1[hid:]
-    W1p[:hid, C_] = b1[:hid]
-    W1p[hid_p:hid_p + hid, C_] = b1[hid:]
-    c_i = torch.arange(chunks)[:, None, None, None, None]
-    nt_i = torch.arange(4)[None, :, None, None, None]
-    ks_i = torch.arange(ks)[None, None, :, None, None]
-    nl = nt_i * 16 + n16[None, None, None, :, None]                       # chunk-local channel 0..63
-    row = torch.where(nl < 32, c_i * 32 + nl, hid_p + c_i * 32 + (nl - 32)).expand(chunks, 4, ks, 64, 8)
-    col = (ks_i * 32 + 8 * g4[None, None, None, :, None] + j8[None, None, None, None, :]).expand(chunks, 4, ks, 64, 8)
-    w1f = W1p[row, col]
-    # ---- fc2: w2f[chunk][nt][lane][8]; the k order inside the 32-deep chunk is the accumulator order of the
-    # depthwise stage: element (g, j<4) <-> channel 4g+j of a-group 0, (g, j>=4) <-> channel 16+4g+(j-4)
-    W2p = torch.zeros(nt * 16, hid_p)
-    W2p[:C_, :hid] = W2
-    n_i = (torch.arange(nt)[:, None] * 16 + n16[None, :])                  # (nt, 64)
-    kloc = torch.where(j8[None, :] < 4, 4 * g4[:, None] + j8[None, :], 16 + 4 * g4[:, None] + (j8[None, :] - 4))  # (64, 8)
-    k_i = torch.arange(chunks)[:, None, None] * 32 + kloc[None]            # (chunks, 64, 8)
-    w2f = W2p[n_i[None, :, :, None].expand(chunks, nt, 64, 8), k_i[:, None].expand(chunks, nt, 64, 8)]
-    # ---- biases
-    b1p = torch.zeros(2 * hid_p)
-    b1p[:hid], b1p[hid_p:hid_p + hid] = b1[:hid], b1[hid:]
-    dwb = torch.zeros(2 * hid_p)
-    dwb[:hid], dwb[hid_p:hid_p + hid] = bd[:hid], bd[hid:]
-    b2p = torch.zeros(nt * 16)
-    b2p[:C_] = b2
-    # ---- depthwise weights, one value per (chunk, lane, group of 16 channels, tap pair): lane (n = l&15, g = l>>4)
-    # owns channel n of the group and tap 2*pair + (g>>1) (tap 9 = the depthwise BIAS, multiplied by a constant 1 in
-    # the kernel); non-zero only in the lanes whose 8-wide k group holds channel n (n>>3 == g&1), so the kernel
-    # builds its diagonal A fragment from this single value.  bf16: stored duplicated in both halves of a dword.
-    Wd_a, Wd_g = torch.zeros(hid_p, 10), torch.zeros(hid_p, 10)
-    Wd_a[:hid, :9], Wd_g[:hid, :9] = Wd[:hid], Wd[hid:]
-    Wd_a[:hid, 9], Wd_g[:hid, 9] = bd[:hid], bd[hid:]
-    Wdp = torch.stack([Wd_a.reshape(chunks, 2, 16, 10)[:, 0], Wd_a.reshape(chunks, 2, 16, 10)[:, 1],
-                       Wd_g.reshape(chunks, 2, 16, 10)[:, 0], Wd_g.reshape(chunks, 2, 16, 10)[:, 1]])  # [group][chunk][ch][tap]
-    tap = 2 * torch.arange(5)[None, :] + (g4[:, None] >> 1)                  # (64, 5)
-    active = ((n16 >> 3) == (g4 & 1)).to(torch.float32)                      # (64,)
-    dww = torch.zeros(chunks, 64, 4, 5)
-    for gi in range(4):
-        dww[:, :, gi, :] = Wdp[gi][:, n16[:, None].expand(64, 5), tap] * active[None, :, None]
-    dww = dww.reshape(chunks, 64, 20)
-    if dtype == HAT_BF16:
-        bits = dww.to(torch.bfloat16).view(torch.int16).to(torch.int32) & 0xFFFF
-        dww = (bits | (bits << 16)).to(torch.int32)
-    p = PackedFFN()
-    p.w1f, p.w2f = w1f.to(tdt).contiguous().to(device), w2f.to(tdt).contiguous().to(device)
-    p.b1, p.dwb, p.b2 = b1p.to(device), dwb.to(device), b2p.to(device)
-    p.dww = dww.contiguous().to(device)
-    p.chunks, p.C, p.hid, p.nt, p.ks, p.khalf = chunks, C_, hid, nt, ks, khalf
-    return p
 
 
 def ffn2_supported(C_: int, hid: int, dtype: int) -> bool:
@@ -843,131 +627,9 @@ def ffn2_supported(C_: int, hid: int, dtype: int) -> bool:
     return C_ == 144 and hid % 32 == 0 and dtype == HAT_BF16
 
 
-FP16_SAFE = 6.0e4   # below _Float16's largest finite value, 65504
-
-
-def ffn_fp16_range_bound(fc1_w, fc1_b, dw_w, dw_b, ln_g, ln_b) -> float:
-    """Worst-case magnitude of anything hat_ffn2 / hat_hab_tail3 hold in FP16 — the hidden tensor u = fc1(LayerNorm2(x)), the
-    depthwise conv's outputs a and g, and the gated product a * g * sigmoid(g) — for ANY input: LayerNorm's normalised row
-    has Euclidean norm <= sqrt(C), so |u_j| <= sqrt(C) * ||W1[j] * gamma||_2 + |W1[j] . beta + b1[j]| =: U_j (Cauchy-Schwarz),
-    |a_j| <= sum_taps |wd[j, tap]| * U_j + |bd_j|, likewise g, and |a * g * sigmoid(g)| <= |a| * |g|.
-    The kernels convert to FP16 with round-toward-zero (a value past the range saturates at 65504 instead of becoming an
-    infinity) but the packed-FP16 products behind that conversion can still overflow, so the engine uses these kernels only
-    while this bound stays below FP16_SAFE and otherwise keeps hat_ffn (hidden tensor in bf16, fp32 range).  The bound is loose
-    by design (a trained HAT-S sits orders of magnitude below it: unit-variance rows, weights of norm ~1 give U ~ 12, a * g ~ 10^3)."""
-    f = lambda t: t.detach().to(torch.float64).cpu()
-    W1, b1, Wd, bd, g_, b_ = f(fc1_w), f(fc1_b), f(dw_w).reshape(-1, 9), f(dw_b), f(ln_g), f(ln_b)
-    C_ = W1.shape[1]
-    hid = W1.shape[0] // 2
-    U = (C_ ** 0.5) * (W1 * g_[None, :]).norm(dim=1) + (W1 @ b_ + b1).abs()
-    A = Wd.abs().sum(1) * U + bd.abs()
-    return float(max(U.max(), A.max(), (A[:hid] * A[hid:]).max()))
-
-
-def pack_ffn2(fc1_w, fc1_b, dw_w, dw_b, fc2_w, fc2_b, device) -> PackedFFN:
-    """GatedDconvFFN weights (hat_arch.py:99-104) in hat_ffn2's layouts (include/hat_mi355x.h)."""
-    f = lambda t: t.detach().to(torch.float32).cpu()
-    W1, b1, Wd, bd, W2, b2 = f(fc1_w), f(fc1_b), f(dw_w).reshape(-1, 9), f(dw_b), f(fc2_w), f(fc2_b)
-    C_, hid = W2.shape
-    assert W1.shape == (2 * hid, C_) and Wd.shape[0] == 2 * hid and hid % 32 == 0 and C_ == 144
-    chunks, ks, nt = hid // 32, 5, 9
-    lane = torch.arange(64)
-    n16, g4, j8 = lane & 15, lane >> 4, torch.arange(8)
-    # fc1 output row nl = tile * 16 + n16 of a chunk (tiles 0, 1: a half; 2, 3: gate half) computes hidden unit
-    # q = 8 g + 4 ii + r of its half (ii = tile & 1, n16 = 4 g + r): a lane's 4 + 4 results of the two tiles are then 16
-    # contiguous bytes of the U row, unit order natural (one conflict-free-enough ds_write_b128, hat_ffn2.hip `ust`)
-    nl = torch.arange(64)
-    q = 8 * ((nl & 15) >> 2) + 4 * ((nl >> 4) & 1) + (nl & 3)
-    rows = (nl[None, :] >> 5) * hid + torch.arange(chunks)[:, None] * 32 + q[None, :]            # (chunks, 64)
-    W1p = torch.zeros(2 * hid, ks * 32)
-    W1p[:, :C_] = W1
-    r = rows.reshape(chunks, 4, 16)[:, :, None, n16, None].expand(chunks, 4, ks, 64, 8)
-    col = (torch.arange(ks)[None, None, :, None, None] * 32 + 8 * g4[None, None, None, :, None] + j8).expand(chunks, 4, ks, 64, 8)
-    w1f = W1p[r, col]
-    b1c = b1[rows]                                                                               # (chunks, 64)
-    # depthwise: [chunk][g][tap 0..8, bias][a-units 8g..8g+7 | gate-units 8g..8g+7]
-    Wd10 = torch.cat([Wd, bd[:, None]], dim=1)                                                    # (2*hid, 10)
-    unit = (torch.arange(chunks)[:, None, None] * 32 + 8 * torch.arange(4)[None, :, None] + j8[None, None, :])   # (chunks, 4, 8)
-    dww = torch.cat([Wd10[unit].permute(0, 1, 3, 2), Wd10[hid + unit].permute(0, 1, 3, 2)], dim=-1)  # (chunks, 4, 10, 16)
-    W2p = torch.zeros(nt * 16, hid)
-    W2p[:C_] = W2
-    n_i = torch.arange(nt)[:, None] * 16 + n16[None, :]                                           # (nt, 64)
-    k_i = torch.arange(chunks)[:, None, None] * 32 + (8 * g4[:, None] + j8[None, :])[None]        # (chunks, 64, 8)
-    w2f = W2p[n_i[None, :, :, None].expand(chunks, nt, 64, 8), k_i[:, None].expand(chunks, nt, 64, 8)]
-    b2p = torch.zeros(nt * 16)
-    b2p[:C_] = b2
-    p = PackedFFN()
-    p.w1f = w1f.to(torch.bfloat16).contiguous().to(device)
-    p.w2f = w2f.to(torch.float16).contiguous().to(device)
-    p.dww = dww.to(torch.float16).contiguous().to(device)
-    p.b1, p.dwb, p.b2 = b1c.contiguous().to(device), bd.to(device), b2p.to(device)
-    p.chunks, p.C, p.hid, p.nt, p.ks, p.khalf = chunks, C_, hid, nt, ks, "v2"
-    return p
-
-
 def tail3_supported(C_: int, hid: int, dtype: int) -> bool:
     """Shapes hat_hab_tail3 is built for: embed_dim 144 (hidden 288, folded CAB) and 180 (hidden 360 padded to 384, c2 as a map)."""
     return dtype == HAT_BF16 and ((C_ == 144 and hid % 32 == 0) or (C_ == 180 and hid == 360))
-
-
-def pack_ffn3(fc1_w, fc1_b, dw_w, dw_b, fc2_w, fc2_b, ln_g, ln_b, device) -> PackedFFN:
-    """GatedDconvFFN weights (hat_arch.py:99-104) + the affine part of the LayerNorm in front of them (norm2, hat_arch.py:237)
-    in hat_hab_tail3's layouts (include/hat_mi355x.h), embed_dim 144 or 180:
-      * LayerNorm2's gamma folded into the fc1 columns and W1 . beta into the fc1 bias (fc1(xhat * gamma + beta) =
-        (W1 diag(gamma)) xhat + (W1 beta + b1), exact in real arithmetic): the kernel normalises without an affine step;
-      * the fc1 bias as column k = C of the fc1 fragments (K = C + 1 padded to a multiple of 32);
-      * the hidden width padded to a multiple of 32 with zero units (embed_dim 180: 360 -> 384);
-      * fc1 output row (tile, n16) of a chunk computes hidden unit 8 (n16 >> 2) + 4 (tile & 1) + (n16 & 3) of its half, so that a
-        lane's 4 + 4 results of the two tiles are 16 contiguous bytes of the U row (as pack_ffn2);
-      * the depthwise record of a chunk zero padded to 2 KiB and the fc2 bias to 1 KiB (every record the kernel copies is then
-        a whole number of 1 KiB LDS-DMA pieces)."""
-    f = lambda t: t.detach().to(torch.float32).cpu()
-    W1, b1, gam, bet = f(fc1_w), f(fc1_b), f(ln_g), f(ln_b)
-    Wd, bd, W2, b2 = f(dw_w).reshape(-1, 9), f(dw_b), f(fc2_w), f(fc2_b)
-    C_, hid = W2.shape
-    assert W1.shape == (2 * hid, C_) and C_ in (144, 180)
-    b1 = b1 + W1 @ bet
-    W1 = W1 * gam[None, :]
-    ks, nt = (C_ + 1 + 31) // 32, (C_ + 15) // 16
-    chunks = -(-hid // 32)
-    hid_p = 32 * chunks
-    z2 = lambda m, rows: torch.cat([m, torch.zeros(rows - m.shape[0], *m.shape[1:])]) if rows > m.shape[0] else m
-    W1a, W1g = z2(W1[:hid], hid_p), z2(W1[hid:], hid_p)             # (hid_p, C) each
-    b1a, b1g = z2(b1[:hid], hid_p), z2(b1[hid:], hid_p)
-    Wd10 = torch.cat([Wd, bd[:, None]], dim=1)                      # (2*hid, 10): taps 0..8 + the depthwise bias as "tap 9"
-    Wda, Wdg = z2(Wd10[:hid], hid_p), z2(Wd10[hid:], hid_p)
-    lane = torch.arange(64)
-    n16, g4, j8 = lane & 15, lane >> 4, torch.arange(8)
-    nl = torch.arange(64)                                           # fc1 output row of a chunk: tiles 0, 1 = a half; 2, 3 = gate half
-    q = 8 * ((nl & 15) >> 2) + 4 * ((nl >> 4) & 1) + (nl & 3)       # hidden unit of its half, chunk-local
-    unit = torch.arange(chunks)[:, None] * 32 + q[None, :]          # (chunks, 64)
-    half = (nl >> 5)[None, :].expand(chunks, 64)
-    Wp = torch.zeros(2, hid_p, ks * 32)
-    Wp[0, :, :C_], Wp[1, :, :C_] = W1a, W1g
-    Wp[0, :, C_], Wp[1, :, C_] = b1a, b1g                           # the bias column (the kernel keeps 1.0 in k-slot C)
-    rows = Wp[half, unit]                                           # (chunks, 64, ks*32)
-    r = rows.reshape(chunks, 4, 16, ks * 32)[:, :, n16]             # (chunks, 4, 64 lanes, K)
-    col = (torch.arange(ks)[:, None, None] * 32 + 8 * g4[None, :, None] + j8[None, None, :])   # (ks, 64, 8)
-    w1f = torch.stack([r[:, :, lane[:, None], col[k]] for k in range(ks)], dim=2)                   # (chunks, 4, ks, 64, 8)
-    # depthwise: [chunk][g][tap 0..8, bias][a-units 8g..8g+7 | gate-units 8g..8g+7], padded to 1024 elements per chunk
-    u8 = (torch.arange(chunks)[:, None, None] * 32 + 8 * torch.arange(4)[None, :, None] + j8[None, None, :])   # (chunks, 4, 8)
-    dww = torch.cat([Wda[u8].permute(0, 1, 3, 2), Wdg[u8].permute(0, 1, 3, 2)], dim=-1)         # (chunks, 4, 10, 16)
-    dw = torch.zeros(chunks, 1024)
-    dw[:, :640] = dww.reshape(chunks, 640)
-    W2p = torch.zeros(nt * 16, hid_p)
-    W2p[:C_, :hid] = W2
-    n_i = torch.arange(nt)[:, None] * 16 + n16[None, :]
-    k_i = torch.arange(chunks)[:, None, None] * 32 + (8 * g4[:, None] + j8[None, :])[None]
-    w2f = W2p[n_i[None, :, :, None].expand(chunks, nt, 64, 8), k_i[:, None].expand(chunks, nt, 64, 8)]
-    b2p = torch.zeros(256)
-    b2p[:C_] = b2
-    p = PackedFFN()
-    p.w1f = w1f.to(torch.bfloat16).contiguous().to(device)
-    p.w2f = w2f.to(torch.float16).contiguous().to(device)
-    p.dww = dw.to(torch.float16).contiguous().to(device)
-    p.b1, p.dwb, p.b2 = torch.zeros(4, device=device), torch.zeros(4, device=device), b2p.to(device)
-    p.chunks, p.C, p.hid, p.nt, p.ks, p.khalf = chunks, C_, hid, nt, ks, "v3"
-    return p
 
 
 def _ffn_desc(pf: PackedFFN, B, H, W, dtype):
@@ -1012,9 +674,9 @@ def ffn(pf: PackedFFN, t_in, t_out, ln_g, ln_b, *, B: int, H: int, W: int, dtype
     # (with m_in, LayerNorm2(t_in) arrives pre-computed as T rows: it replaces the haloed fp32 read; t_in is still read
     # once for the residual)
     nbytes = B * H * W * (4.0 * pf.C + 4.0 * pf.C + (es * ldn if ln1 is not None else 0) + (es * ldm_in if m_in is not None else 0))
-    if pf.khalf == "v3":
+    if pf.layout == "tail3":
         raise RuntimeError("a hat_hab_tail3-packed FFN has no stand-alone launch: pack with pack_ffn2 for hat_ffn2")
-    if pf.khalf == "v2":
+    if pf.layout == "ffn2":
         _timed("ffn2_kernel", flops, lambda: _lib.check(lib.hat_ffn2(C.byref(d), _stream()), "hat_ffn2"), nbytes=nbytes)
         return
     _timed(f"ffn_kernel<{_TNAME[dtype]}>", flops, lambda: _lib.check(lib.hat_ffn(C.byref(d), _stream()), "hat_ffn"),
@@ -1023,8 +685,8 @@ def ffn(pf: PackedFFN, t_in, t_out, ln_g, ln_b, *, B: int, H: int, W: int, dtype
 
 def hab_tail_supported(pf: PackedFFN, aggr: PackedConv, mid: int, dtype: int) -> bool:
     if pf.C == 180:   # hat_hab_tail3 with the CAB's c2 as a map (no fold: mid is 60)
-        return pf.khalf == "v3" and aggr.frag and aggr.nt == 12 and aggr.n_slices == 1 and aggr.kpad == 192 and dtype == HAT_BF16
-    return pf.khalf in ("v2", "v3") and aggr.frag and aggr.nt == 9 and aggr.n_slices == 1 and aggr.kpad == 160 and mid <= 8 and dtype == HAT_BF16
+        return pf.layout == "tail3" and aggr.frag and aggr.nt == 12 and aggr.n_slices == 1 and aggr.kpad == 192 and dtype == HAT_BF16
+    return pf.layout in ("ffn2", "tail3") and aggr.frag and aggr.nt == 9 and aggr.n_slices == 1 and aggr.kpad == 160 and mid <= 8 and dtype == HAT_BF16
 
 
 def hab_tail(pf: PackedFFN, aggr: PackedConv, t_in, t_out, ln_g, ln_b, *, n, ldn_in: int, y16, c1=None, wf=None, bias_b, B: int, H: int,
@@ -1040,7 +702,7 @@ def hab_tail(pf: PackedFFN, aggr: PackedConv, t_in, t_out, ln_g, ln_b, *, n, ldn
     h.n, h.y16, h.c1, h.w_aggr, h.wf, h.bias_b, h.ldn_in = _ptr(n), _ptr(y16), _ptr(c1), _ptr(aggr.w), _ptr(wf), _ptr(bias_b), ldn_in
     h.r2, h.ldr2, h.r2scale, h.r2scale_bstride = _ptr(r2), ldr2, _ptr(r2scale), r2scale_bstride
     in_half, out_half = t_in.dtype == torch.float16, t_out.dtype == torch.float16
-    if (in_half or out_half) and not (pf.C == 144 and pf.khalf == "v3"):
+    if (in_half or out_half) and not (pf.C == 144 and pf.layout == "tail3"):
         raise RuntimeError("an FP16 residual stream is only instantiated for hat_hab_tail3 at embed_dim 144")
     if (not in_half and t_in.dtype != torch.float32) or (not out_half and t_out.dtype != torch.float32):
         raise RuntimeError("hab_tail: t_in / t_out must be fp32 or FP16 rows")
@@ -1054,7 +716,7 @@ def hab_tail(pf: PackedFFN, aggr: PackedConv, t_in, t_out, ln_g, ln_b, *, n, ldn
     # algorithmic HBM bytes per pixel: n (T), y16 (T x 16), c1 (T x 8), t (fp32) read once; t_out (fp32) and the next
     # block's LayerNorm output (T) written
     nbytes = B * H * W * (2.0 * ldn_in + 32 + 16 + (2.0 if in_half else 4.0) * pf.C + (2.0 if out_half else 4.0) * pf.C + (2 * ldn if ln1 is not None else 0))
-    if pf.khalf == "v3":
+    if pf.layout == "tail3":
         _timed("tail3_kernel", flops, lambda: _lib.check(lib.hat_hab_tail3(C.byref(h), _stream()), "hat_hab_tail3"), nbytes=nbytes)
         return
     _timed("ffn2_kernel<aggr>", flops, lambda: _lib.check(lib.hat_hab_tail(C.byref(h), _stream()), "hat_hab_tail"), nbytes=nbytes)
@@ -1066,52 +728,11 @@ def hab_tail(pf: PackedFFN, aggr: PackedConv, t_in, t_out, ln_g, ln_b, *, n, ldn
 _PW_SHAPES = {(9, 5), (18, 5), (9, 9), (12, 6), (23, 6), (12, 12), (4, 1), (4, 2)}  # (nt, ceil(Cin/32)) instantiated in hat_pw.hip
 
 
-def choose_nt_linear(nout: int, cin: int, dtype: int):
-    """hat_linear's n-tiling: like choose_nt, except that a 288-wide output over 144 inputs (OCAB kv and MLP fc1 of the
-    embed_dim-144 models) is ONE slice of 18 n-tiles in bf16 (90 KB of weights in LDS): every slice re-reads the input,
-    and these layers are HBM-bound."""
-    if nout == 288 and -(-cin // 32) == 5 and dtype == HAT_BF16:
-        return 18, 1
-    if nout == 360 and -(-cin // 32) == 6 and dtype == HAT_BF16:   # the same layers of the embed_dim-180 models: 23 n-tiles, 138 KB
-        return 23, 1
-    return choose_nt(nout)
-
-
 def linear_supported(nout: int, cin: int, dtype: int) -> bool:
     nt, _ = choose_nt_linear(nout, cin, dtype)
     ks = -(-cin // 32)
     lds = nt * ks * 64 * 8 * (2 if dtype == HAT_BF16 else 4)
     return (nt, ks) in _PW_SHAPES and lds <= 163840 and cin % 4 == 0
-
-
-def pack_linear_weight(weight: torch.Tensor, bias: Optional[torch.Tensor], dtype: int, device, scale: float = 1.0) -> PackedConv:
-    """weight (O, I) -> MFMA A-fragment order [n_slices][nt][ceil(I/32)][64 lanes][8] for hat_linear.
-    A conv weight (O, I, k, k) is first flattened to K = tap * Cin_p + ci (hat_conv3x3_small)."""
-    w = weight.detach().to(torch.float32).cpu()
-    ksize, cin = 1, None
-    if w.dim() == 4 and w.shape[-1] > 1:
-        o_, i_, ksize, _ = w.shape
-        cin, cin_p = i_, (i_ + 7) // 8 * 8
-        wt = torch.zeros(o_, ksize * ksize, cin_p)
-        wt[:, :, :i_] = w.permute(0, 2, 3, 1).reshape(o_, ksize * ksize, i_)
-        w = wt.reshape(o_, -1)
-    w = w.reshape(w.shape[0], -1) * scale
-    o, i = w.shape
-    b = (torch.zeros(o) if bias is None else bias.detach().to(torch.float32).cpu()) * scale
-    nt, n_slices = choose_nt_linear(o, i, dtype) if ksize == 1 else choose_nt(o)
-    ks = -(-i // 32)
-    npad = nt * 16 * n_slices
-    wp = torch.zeros(npad, ks * 32)
-    wp[:o, :i] = w
-    lane = torch.arange(64)
-    row = (torch.arange(n_slices)[:, None, None, None, None] * nt * 16 + torch.arange(nt)[None, :, None, None, None] * 16
-           + (lane & 15)[None, None, None, :, None]).expand(n_slices, nt, ks, 64, 8)
-    col = (torch.arange(ks)[None, None, :, None, None] * 32 + 8 * (lane >> 4)[None, None, None, :, None]
-           + torch.arange(8)[None, None, None, None, :]).expand(n_slices, nt, ks, 64, 8)
-    wf = wp[row, col].to(TORCH_DTYPE[dtype]).contiguous().to(device)
-    bp = torch.zeros(npad)
-    bp[:o] = b
-    return PackedConv(wf, bp.to(device), ksize, (i if cin is None else cin), ks * 32, nt, n_slices, o, frag=True)
 
 
 def linear(pw: PackedConv, x: torch.Tensor, out: torch.Tensor, *, B: int, H: int, W: int, dtype: int, ldx: int, ldo: int,
@@ -1181,22 +802,6 @@ def conv3x3_small(pw: PackedConv, x, out, *, B: int, H: int, W: int, dtype: int,
 # ------------------------------------------------------------------------------------------------
 def aggr_cab_supported(C_: int, mid: int, dtype: int) -> bool:
     return C_ == 144 and mid <= 8 and dtype == HAT_BF16
-
-
-def pack_cab_w2f(w2: torch.Tensor, device) -> torch.Tensor:
-    """(C, mid <= 8, 3, 3) expand-conv weight -> fp32 [nt][3][64][8] in the order of hat_cab_fold's output `wf` (HatCabFoldDesc.w2f)."""
-    w = w2.detach().to(torch.float32).cpu()
-    C_, mid = w.shape[0], w.shape[1]
-    nt = -(-C_ // 16)
-    full = torch.zeros(nt * 16, 12, 8)                     # [co][tap 0..11][ci 0..7]
-    full[:C_, :9, :mid] = w.reshape(C_, mid, 9).permute(0, 2, 1)
-    lane = torch.arange(64)
-    t = torch.arange(nt)[:, None, None, None]
-    ks = torch.arange(3)[None, :, None, None]
-    co = (t * 16 + (lane & 15)[None, None, :, None]).expand(nt, 3, 64, 8)
-    tap = (4 * ks + (lane >> 4)[None, None, :, None]).expand(nt, 3, 64, 8)
-    ci = torch.arange(8)[None, None, None, :].expand(nt, 3, 64, 8)
-    return full[co, tap, ci].contiguous().to(device)
 
 
 def cab_fold(c1, c1_colsum, tiles: int, ldcs: int, w2, b2, wk, k: int, bias_in, conv_scale: float, scale, wf, bias_out, tmp, *,

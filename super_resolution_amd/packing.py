@@ -1,0 +1,363 @@
+"""Host-side weight packing: state-dict tensors -> the layouts the kernels read (include/hat_mi355x.h).  Pure index
+gathering on CPU tensors; nothing here loads the library or touches the GPU (`device` is only where the result is put).
+
+Every MFMA A-fragment layout goes through `frags`; a packer builds the padded matrix (bias column, zero hidden units),
+reorders its rows where the layout has a row permutation, calls `frags`, and reshapes to the documented dimension order.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from ._lib import HAT_BF16, HAT_F32
+
+TORCH_DTYPE = {HAT_F32: torch.float32, HAT_BF16: torch.bfloat16}
+KC = {HAT_F32: 32, HAT_BF16: 64}
+
+
+class PackedConv:
+    """Packed weights of one conv/linear layer (see HatConvDesc in include/hat_mi355x.h)."""
+    __slots__ = ("w", "bias", "ksize", "cin", "kpad", "nt", "n_slices", "nout", "w_bstride", "frag", "ksplit")
+
+    def __init__(self, w, bias, ksize, cin, kpad, nt, n_slices, nout, w_bstride=0, frag=False):
+        self.w, self.bias, self.ksize, self.cin, self.kpad = w, bias, ksize, cin, kpad
+        self.nt, self.n_slices, self.nout, self.w_bstride = nt, n_slices, nout, w_bstride
+        self.frag = frag  # True: MFMA-fragment order for hat_linear; False: [Npad][Kpad] rows for hat_conv
+        self.ksplit = None  # second half of a layer whose K is split over two launches (engine._lin)
+
+    @property
+    def npad(self):
+        return self.nt * 16 * self.n_slices
+
+
+class PackedMlp:
+    """fc1 / fc2 of the OCAB's MLP in hat_ocab_mlp's fragment layouts (include/hat_mi355x.h)."""
+    __slots__ = ("w1f", "b1", "w2f", "b2", "C", "hidden")
+
+
+class PackedFFN:
+    """GatedDconvFFN weights; `layout` names the kernel generation they are packed for: "ffn" (hat_ffn), "ffn2" (hat_ffn2 /
+    hat_hab_tail) or "tail3" (hat_hab_tail3)."""
+    __slots__ = ("w1f", "b1", "dww", "dwb", "w2f", "b2", "chunks", "C", "hid", "nt", "ks", "layout")
+
+
+def choose_nt(nout: int):
+    """n-tiles per slice in {12, 9, 8, 4, 1}: least padded work, weighted by LDS fragment reads per MFMA."""
+    best = None
+    for nt in (12, 9, 8, 4, 1):
+        npad = -(-nout // (16 * nt)) * 16 * nt
+        cost = npad * (nt + 2) / nt
+        if best is None or cost < best[0]:
+            best = (cost, nt, npad // (16 * nt))
+    return best[1], best[2]
+
+
+def choose_nt_linear(nout: int, cin: int, dtype: int):
+    """hat_linear's n-tiling: like choose_nt, except that a 288-wide output over 144 inputs (OCAB kv and MLP fc1 of the
+    embed_dim-144 models) is ONE slice of 18 n-tiles in bf16 (90 KB of weights in LDS): every slice re-reads the input,
+    and these layers are HBM-bound."""
+    if nout == 288 and -(-cin // 32) == 5 and dtype == HAT_BF16:
+        return 18, 1
+    if nout == 360 and -(-cin // 32) == 6 and dtype == HAT_BF16:   # the same layers of the embed_dim-180 models: 23 n-tiles, 138 KB
+        return 23, 1
+    return choose_nt(nout)
+
+
+# ------------------------------------------------------------------------------------------------
+# helpers
+# ------------------------------------------------------------------------------------------------
+def _f32(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().to(torch.float32).cpu()
+
+
+def _pad(m: torch.Tensor, rows: int, cols: Optional[int] = None) -> torch.Tensor:
+    """m (a vector or a matrix) zero padded to `rows` rows (and `cols` columns)."""
+    if m.dim() == 1:
+        out = torch.zeros(rows)
+        out[:m.shape[0]] = m
+    else:
+        out = torch.zeros(rows, m.shape[1] if cols is None else cols)
+        out[:m.shape[0], :m.shape[1]] = m
+    return out
+
+
+def frags(M: torch.Tensor, order: str = "natural", jn: int = 8) -> torch.Tensor:
+    """MFMA A fragments of a 2-D fp32 matrix (rows a multiple of 16, columns a multiple of 4 jn): [rows/16][cols/(4 jn)][64][jn]
+    with element (t, ks, lane, j) = M[16 t + (lane & 15)][4 jn ks + k(lane >> 4, j)], k(g, j) = jn g + j ("natural": the 32-deep
+    k-step with jn = 8, the 16-deep half step with jn = 4) or j < 4 ? 4 g + j : 16 + 4 g + j - 4 ("acc": the accumulator order
+    of the stage that produced the operand, jn = 8).  A view: callers convert and make it contiguous."""
+    assert M.dim() == 2 and M.shape[0] % 16 == 0 and M.shape[1] % (4 * jn) == 0 and (order == "natural" or (order, jn) == ("acc", 8))
+    lane, j = torch.arange(64)[:, None], torch.arange(jn)[None, :]
+    g = lane >> 4
+    k = jn * g + j if order == "natural" else torch.where(j < 4, 4 * g + j, 16 + 4 * g + j - 4)
+    return M.reshape(M.shape[0] // 16, 16, M.shape[1] // (4 * jn), 4 * jn)[:, lane & 15, :, k].permute(2, 3, 0, 1)
+
+
+def _tap_major(w: torch.Tensor) -> torch.Tensor:
+    """(O, I, k, k) -> (O, k*k*Cin_p) with K = tap * Cin_p + ci, Cin_p = I rounded up to 8 (zero channels)."""
+    o, i, kh, kw = w.shape
+    assert kh == kw
+    wt = torch.zeros(o, kh * kw, (i + 7) // 8 * 8)
+    wt[:, :, :i] = w.permute(0, 2, 3, 1).reshape(o, kh * kw, i)
+    return wt.reshape(o, -1)
+
+
+# ------------------------------------------------------------------------------------------------
+# hat_conv / hat_linear / hat_conv3x3_small
+# ------------------------------------------------------------------------------------------------
+def pack_conv_weight(weight: torch.Tensor, bias: Optional[torch.Tensor], dtype: int, device, out_perm=None,
+                     scale: float = 1.0, nt: Optional[int] = None) -> PackedConv:
+    """weight (O, I, k, k) [or (O, I) for nn.Linear] -> [Npad][Kpad] with K = tap * Cin_p + ci."""
+    w = _f32(weight)
+    if w.dim() == 2:
+        w = w[:, :, None, None]
+    o, i, kh, _ = w.shape
+    b = torch.zeros(o) if bias is None else _f32(bias)
+    if scale != 1.0:
+        w, b = w * scale, b * scale
+    if out_perm is not None:
+        w, b = w[out_perm], b[out_perm]
+    w = _tap_major(w)
+    if nt is None:
+        nt, n_slices = choose_nt(o)
+    else:
+        n_slices = -(-o // (16 * nt))
+    kc = KC[dtype] * (3 if nt == 1 else (2 if nt <= 4 else 1))  # weight chunk length of hat_conv.hip: longer for few n-tiles
+    kpad = -(-w.shape[1] // kc) * kc
+    npad = nt * 16 * n_slices
+    return PackedConv(_pad(w, npad, kpad).to(TORCH_DTYPE[dtype]).to(device).contiguous(), _pad(b, npad).to(device), kh, i, kpad, nt, n_slices, o)
+
+
+def pack_linear_weight(weight: torch.Tensor, bias: Optional[torch.Tensor], dtype: int, device, scale: float = 1.0) -> PackedConv:
+    """weight (O, I) -> MFMA A-fragment order [n_slices][nt][ceil(I/32)][64 lanes][8] for hat_linear (include/hat_mi355x.h:
+    element (lane l, j) = W[slice*nt*16 + t*16 + (l & 15)][32*ks + 8*(l >> 4) + j], zero beyond Cin / n).
+    A conv weight (O, I, k, k) is first flattened to K = tap * Cin_p + ci (hat_conv3x3_small)."""
+    w = _f32(weight)
+    ksize, cin = 1, None
+    if w.dim() == 4 and w.shape[-1] > 1:
+        cin, ksize = w.shape[1], w.shape[2]
+        w = _tap_major(w)
+    w = w.reshape(w.shape[0], -1) * scale
+    o, i = w.shape
+    b = (torch.zeros(o) if bias is None else _f32(bias)) * scale
+    nt, n_slices = choose_nt_linear(o, i, dtype) if ksize == 1 else choose_nt(o)
+    ks = -(-i // 32)
+    npad = nt * 16 * n_slices
+    wf = frags(_pad(w, npad, ks * 32)).reshape(n_slices, nt, ks, 64, 8)
+    return PackedConv(wf.to(TORCH_DTYPE[dtype]).contiguous().to(device), _pad(b, npad).to(device), ksize, (i if cin is None else cin),
+                      ks * 32, nt, n_slices, o, frag=True)
+
+
+def pack_pointwise(weight: torch.Tensor, bias: Optional[torch.Tensor], dtype: int, device, scale: float = 1.0) -> PackedConv:
+    """A pointwise layer for hat_linear when its shape is instantiated (PackedConv.frag), else for hat_conv (ksize 1)."""
+    from .ops import linear_supported   # which kernels exist is the launch wrappers' knowledge
+    if linear_supported(weight.shape[0], weight.shape[1], dtype):
+        return pack_linear_weight(weight, bias, dtype, device, scale=scale)
+    return pack_conv_weight(weight, bias, dtype, device, scale=scale)
+
+
+# ------------------------------------------------------------------------------------------------
+# hat_ocab_mlp / hat_ocab_qkv
+# ------------------------------------------------------------------------------------------------
+def _pack_fc1_frags(W1: torch.Tensor) -> torch.Tensor:
+    """(16 nt, 144) fp32 -> hat_ocab_mlp's fc1 layout: [nt][4][64 lanes][8] full k-steps (k = 32 ks + 8 g + j) then
+    [nt][64][4] the 16-deep tail (k = 128 + 4 g + j)."""
+    return torch.cat([frags(W1[:, :128]).reshape(-1), frags(W1[:, 128:], jn=4).reshape(-1)])
+
+
+def pack_ocab_mlp(fc1_w, fc1_b, fc2_w, fc2_b, device) -> PackedMlp:
+    """HatMlpDesc (include/hat_mi355x.h): w1f = fc1 as A fragments [18][4][64][8] + the 16-deep tail [18][64][4];
+    w2f = fc2 as A fragments [9 n-tiles][9 k-steps][64][8], k-slot (g, j) of k-step kk = hidden unit 32 kk + 4 g + j (j < 4) or
+    32 kk + 16 + 4 g + j - 4 (the accumulator order of fc1's results)."""
+    W1, b1, W2, b2 = _f32(fc1_w), _f32(fc1_b), _f32(fc2_w), _f32(fc2_b)
+    hid, C_ = W1.shape
+    assert (C_, hid) == (144, 288) and W2.shape == (C_, hid)
+    p = PackedMlp()
+    p.w1f = _pack_fc1_frags(W1).to(torch.bfloat16).contiguous().to(device)
+    p.w2f = frags(W2, "acc").to(torch.bfloat16).contiguous().to(device)
+    p.b1, p.b2, p.C, p.hidden = b1.contiguous().to(device), b2.contiguous().to(device), C_, hid
+    return p
+
+
+def pack_ocab_qkv(q_w, q_b, kv_w, kv_b, qscale: float, device) -> PackedMlp:
+    """Stacked [q_proj * qscale ; kv_proj] (432 x 144) for hat_ocab_qkv, in hat_ocab_mlp's fc1 layout ([27][4][64][8] + [27][64][4])."""
+    Wq, Wkv = _f32(q_w) * qscale, _f32(kv_w)
+    bq = (torch.zeros(Wq.shape[0]) if q_b is None else _f32(q_b)) * qscale
+    bkv = torch.zeros(Wkv.shape[0]) if kv_b is None else _f32(kv_b)
+    W = torch.cat([Wq, Wkv], 0)
+    assert W.shape == (432, 144)
+    p = PackedMlp()
+    p.w1f = _pack_fc1_frags(W).to(torch.bfloat16).contiguous().to(device)
+    p.b1 = torch.cat([bq, bkv]).contiguous().to(device)
+    p.w2f = p.b2 = None
+    p.C, p.hidden = 144, 432
+    return p
+
+
+# ------------------------------------------------------------------------------------------------
+# CAB: the row-sweep squeeze conv (hat_cab_squeeze / hat_conv3x3_to_*) and hat_cab_fold's w2f
+# ------------------------------------------------------------------------------------------------
+def pack_cab_squeeze(weight: torch.Tensor, bias: torch.Tensor, device):
+    """3x3 weight (mid <= 8, C, 3, 3) -> the 6 x ceil(C/32) MFMA A fragments the row-sweep kernel keeps in registers
+    (hat_cab_squeeze / hat_conv3x3_to_planes: wpk [tile = 2 kx + j][kstep][64 lanes][8] bf16, j = 0: rows 0-7 = ky 0,
+    rows 8-15 = ky 1; j = 1: rows 0-7 = ky 2, rest zero), + 8 bias floats."""
+    w = _f32(weight)
+    mid, cin = w.shape[0], w.shape[1]
+    A = torch.zeros(6, 16, 32 * -(-cin // 32))       # [tile][row][k]
+    for kx in range(3):
+        A[2 * kx, 0:mid, :cin] = w[:, :, 0, kx]      # ky = 0 -> output row r + 1
+        A[2 * kx, 8:8 + mid, :cin] = w[:, :, 1, kx]  # ky = 1 -> output row r
+        A[2 * kx + 1, 0:mid, :cin] = w[:, :, 2, kx]  # ky = 2 -> output row r - 1
+    return frags(A.reshape(96, -1)).to(torch.bfloat16).contiguous().to(device), _pad(_f32(bias), 8).to(device)
+
+
+def pack_cab_w2f(w2: torch.Tensor, device) -> torch.Tensor:
+    """(C, mid <= 8, 3, 3) expand-conv weight -> fp32 [nt][3][64][8] in the order of hat_cab_fold's output `wf` (HatCabFoldDesc.w2f):
+    element (t, ks, lane, j) = W2[16 t + (lane & 15)][ci = j][tap = 4 ks + (lane >> 4)], the fragments of the [co][tap * 8 + ci] matrix."""
+    w = _f32(w2)
+    C_, mid = w.shape[0], w.shape[1]
+    full = torch.zeros(-(-C_ // 16) * 16, 12, 8)           # [co][tap 0..11][ci 0..7]
+    full[:C_, :9, :mid] = w.reshape(C_, mid, 9).permute(0, 2, 1)
+    return frags(full.reshape(-1, 96)).contiguous().to(device)
+
+
+# ------------------------------------------------------------------------------------------------
+# the gated depthwise FFN: hat_ffn, hat_ffn2 / hat_hab_tail, hat_hab_tail3
+# ------------------------------------------------------------------------------------------------
+FP16_SAFE = 6.0e4   # below _Float16's largest finite value, 65504
+
+
+def ffn_fp16_range_bound(fc1_w, fc1_b, dw_w, dw_b, ln_g, ln_b) -> float:
+    """Worst-case magnitude of anything hat_ffn2 / hat_hab_tail3 hold in FP16 — the hidden tensor u = fc1(LayerNorm2(x)), the
+    depthwise conv's outputs a and g, and the gated product a * g * sigmoid(g) — for ANY input: LayerNorm's normalised row
+    has Euclidean norm <= sqrt(C), so |u_j| <= sqrt(C) * ||W1[j] * gamma||_2 + |W1[j] . beta + b1[j]| =: U_j (Cauchy-Schwarz),
+    |a_j| <= sum_taps |wd[j, tap]| * U_j + |bd_j|, likewise g, and |a * g * sigmoid(g)| <= |a| * |g|.
+    The kernels convert to FP16 with round-toward-zero (a value past the range saturates at 65504 instead of becoming an
+    infinity) but the packed-FP16 products behind that conversion can still overflow, so the engine uses these kernels only
+    while this bound stays below FP16_SAFE and otherwise keeps hat_ffn (hidden tensor in bf16, fp32 range).  The bound is loose
+    by design (a trained HAT-S sits orders of magnitude below it: unit-variance rows, weights of norm ~1 give U ~ 12, a * g ~ 10^3)."""
+    f = lambda t: t.detach().to(torch.float64).cpu()
+    W1, b1, Wd, bd, g_, b_ = f(fc1_w), f(fc1_b), f(dw_w).reshape(-1, 9), f(dw_b), f(ln_g), f(ln_b)
+    C_ = W1.shape[1]
+    hid = W1.shape[0] // 2
+    U = (C_ ** 0.5) * (W1 * g_[None, :]).norm(dim=1) + (W1 @ b_ + b1).abs()
+    A = Wd.abs().sum(1) * U + bd.abs()
+    return float(max(U.max(), A.max(), (A[:hid] * A[hid:]).max()))
+
+
+def _halves(m: torch.Tensor, hid_p: int) -> torch.Tensor:
+    """[a half ; gate half] (2 hid rows) with each half zero padded to hid_p rows (zero hidden units)."""
+    hid = m.shape[0] // 2
+    return torch.cat([_pad(m[:hid], hid_p), _pad(m[hid:], hid_p)])
+
+
+def _ffn_rows(chunks: int, unit_order: bool) -> torch.Tensor:
+    """Row of the [a ; gate] matrix (hid_p = 32 chunks rows per half) that fc1 output row nl = 16 tile + n16 of chunk c computes
+    (tiles 0, 1: a half; 2, 3: gate half): (chunks, 64).  Plain order: unit 32 c + (nl & 31) of its half (hat_ffn).  Unit order:
+    unit 32 c + 8 (n16 >> 2) + 4 (tile & 1) + (n16 & 3), so that a lane's 4 + 4 results of the two tiles are 16 contiguous bytes of
+    the U row, unit order natural (one ds_write_b128, hat_ffn2.hip `ust`)."""
+    nl = torch.arange(64)
+    q = 8 * ((nl & 15) >> 2) + 4 * ((nl >> 4) & 1) + (nl & 3) if unit_order else nl & 31
+    return (nl >> 5)[None, :] * (32 * chunks) + torch.arange(chunks)[:, None] * 32 + q[None, :]
+
+
+def _ffn_fc1(W1, b1, chunks: int, ks: int, unit_order: bool) -> torch.Tensor:
+    """w1f [chunk][4][ks][64 lanes][8]: the fragments of the chunk's 64 fc1 rows (_ffn_rows), K zero padded to 32 ks, with the
+    fc1 bias as column k = C where b1 is given (the kernel keeps a constant 1 in k-slot C of the normalised activations)."""
+    M = _pad(_halves(W1, 32 * chunks), 64 * chunks, 32 * ks)
+    if b1 is not None:
+        M[:, W1.shape[1]] = _halves(b1, 32 * chunks)
+    return frags(M[_ffn_rows(chunks, unit_order).reshape(-1)]).reshape(chunks, 4, ks, 64, 8)
+
+
+def _ffn_fc2(W2, nt: int, chunks: int, order: str) -> torch.Tensor:
+    """w2f [chunk][nt][64 lanes][8]: fc2 columns 32 c .. 32 c + 31 of output-channel tile nt, in `order` (frags)."""
+    return frags(_pad(W2, 16 * nt, 32 * chunks), order).permute(1, 0, 2, 3)
+
+
+def _ffn_dw_record(Wd, bd, chunks: int) -> torch.Tensor:
+    """[chunk][g][tap 0..8, the depthwise bias as "tap 9"][a-units 32 c + 8 g .. + 7 | gate-units 32 c + 8 g .. + 7] (hat_ffn2's dww)."""
+    Wd10 = _halves(torch.cat([Wd, bd[:, None]], dim=1), 32 * chunks)        # (2 hid_p, 10)
+    return Wd10.reshape(2, chunks, 4, 8, 10).permute(1, 2, 4, 0, 3).reshape(chunks, 4, 10, 16)
+
+
+def _ffn_args(fc1_w, fc1_b, dw_w, dw_b, fc2_w, fc2_b):
+    W1, b1, Wd, bd, W2, b2 = _f32(fc1_w), _f32(fc1_b), _f32(dw_w).reshape(-1, 9), _f32(dw_b), _f32(fc2_w), _f32(fc2_b)
+    C_, hid = W2.shape
+    assert W1.shape == (2 * hid, C_) and Wd.shape[0] == 2 * hid
+    return W1, b1, Wd, bd, W2, b2, C_, hid, -(-hid // 32)
+
+
+def _packed_ffn(layout, w1f, w2f, dww, b1, dwb, b2, chunks, C_, hid, nt, ks, device) -> PackedFFN:
+    p = PackedFFN()
+    p.w1f, p.w2f, p.dww = w1f.contiguous().to(device), w2f.contiguous().to(device), dww.contiguous().to(device)
+    p.b1, p.dwb, p.b2 = b1.contiguous().to(device), dwb.to(device), b2.to(device)
+    p.chunks, p.C, p.hid, p.nt, p.ks, p.layout = chunks, C_, hid, nt, ks, layout
+    return p
+
+
+def pack_ffn(fc1_w, fc1_b, dw_w, dw_b, fc2_w, fc2_b, dtype: int, device) -> PackedFFN:
+    """Fragment-pack GatedDconvFFN weights (hat_arch.py:99-104) for hat_ffn; layouts in include/hat_mi355x.h (HatFfnDesc):
+      w1f [chunk][4][ks][64][8]: fc1 rows {a: 32c..32c+31, g: hid_p+32c..} of chunk c, K = round_up(C + 1, 32) with the fc1
+          bias as column k = C;
+      w2f [chunk][nt][64][8]: fc2 columns 32c..32c+31, k in the accumulator order of the depthwise stage: element (g, j<4) <->
+          channel 4g+j of a-group 0, (g, j>=4) <-> channel 16+4g+(j-4);
+      dww [chunk][64 lanes][4 groups x 5 tap pairs]: one value per (chunk, lane, group of 16 channels {a0, a1, g0, g1}, tap pair):
+          lane (n = l & 15, g = l >> 4) owns channel n of the group and tap 2*pair + (g >> 1) (tap 9 = the depthwise BIAS,
+          multiplied by a constant 1 in the kernel); non-zero only in the lanes whose 8-wide k group holds channel n
+          (n >> 3 == g & 1), so the kernel builds its diagonal A fragment from this single value.  bf16: stored duplicated in
+          both halves of a dword;
+      b1, dwb [2 hid_p], b2 [16 nt]: zero padded fp32."""
+    W1, b1, Wd, bd, W2, b2, C_, hid, chunks = _ffn_args(fc1_w, fc1_b, dw_w, dw_b, fc2_w, fc2_b)
+    hid_p = 32 * chunks
+    ks = -(-(C_ + 1) // 32)          # K padded to a multiple of 32 with room for the bias column at k = C
+    nt = 9 if C_ == 144 else (12 if C_ == 180 else 2)
+    tdt = TORCH_DTYPE[dtype]
+    lane = torch.arange(64)
+    n16, g4 = lane & 15, lane >> 4
+    Wd10 = _halves(torch.cat([Wd, bd[:, None]], dim=1), hid_p).reshape(2, chunks, 2, 16, 10)   # [a | gate][chunk][16-group][ch][tap]
+    tap = 2 * torch.arange(5)[None, :] + (g4[:, None] >> 1)                  # (64, 5)
+    active = ((n16 >> 3) == (g4 & 1)).to(torch.float32)                      # (64,)
+    dww = Wd10[:, :, :, n16[:, None], tap] * active[:, None]                 # (2, chunks, 2, 64, 5)
+    dww = dww.permute(1, 3, 0, 2, 4).reshape(chunks, 64, 20)
+    if dtype == HAT_BF16:
+        bits = dww.to(torch.bfloat16).view(torch.int16).to(torch.int32) & 0xFFFF
+        dww = (bits | (bits << 16)).to(torch.int32)
+    return _packed_ffn("ffn", _ffn_fc1(W1, b1, chunks, ks, False).to(tdt), _ffn_fc2(W2, nt, chunks, "acc").to(tdt), dww,
+                       _halves(b1, hid_p), _halves(bd, hid_p), _pad(b2, nt * 16), chunks, C_, hid, nt, ks, device)
+
+
+def pack_ffn2(fc1_w, fc1_b, dw_w, dw_b, fc2_w, fc2_b, device) -> PackedFFN:
+    """GatedDconvFFN weights (hat_arch.py:99-104) in hat_ffn2's layouts (include/hat_mi355x.h):
+      w1f [chunk][4][5][64][8] bf16: fc1 rows of chunk c in unit order (_ffn_rows), K = 144 zero padded to 160, NO bias column;
+      b1 [chunk][64] fp32: the fc1 bias of the chunk's rows in the same order;
+      dww [chunk][4][10][16] fp16 (_ffn_dw_record);  w2f [chunk][9][64][8] fp16, natural k order;  b2 [144] fp32."""
+    W1, b1, Wd, bd, W2, b2, C_, hid, chunks = _ffn_args(fc1_w, fc1_b, dw_w, dw_b, fc2_w, fc2_b)
+    assert hid % 32 == 0 and C_ == 144
+    ks, nt = 5, 9
+    return _packed_ffn("ffn2", _ffn_fc1(W1, None, chunks, ks, True).to(torch.bfloat16), _ffn_fc2(W2, nt, chunks, "natural").to(torch.float16),
+                       _ffn_dw_record(Wd, bd, chunks).to(torch.float16), b1[_ffn_rows(chunks, True)], bd, _pad(b2, nt * 16),
+                       chunks, C_, hid, nt, ks, device)
+
+
+def pack_ffn3(fc1_w, fc1_b, dw_w, dw_b, fc2_w, fc2_b, ln_g, ln_b, device) -> PackedFFN:
+    """GatedDconvFFN weights (hat_arch.py:99-104) + the affine part of the LayerNorm in front of them (norm2, hat_arch.py:237)
+    in hat_hab_tail3's layouts (include/hat_mi355x.h), embed_dim 144 or 180:
+      * LayerNorm2's gamma folded into the fc1 columns and W1 . beta into the fc1 bias (fc1(xhat * gamma + beta) =
+        (W1 diag(gamma)) xhat + (W1 beta + b1), exact in real arithmetic): the kernel normalises without an affine step;
+      * the fc1 bias as column k = C of the fc1 fragments (K = C + 1 padded to a multiple of 32);
+      * the hidden width padded to a multiple of 32 with zero units (embed_dim 180: 360 -> 384);
+      * fc1 output row (tile, n16) of a chunk computes hidden unit 8 (n16 >> 2) + 4 (tile & 1) + (n16 & 3) of its half, so that a
+        lane's 4 + 4 results of the two tiles are 16 contiguous bytes of the U row (as pack_ffn2);
+      * the depthwise record of a chunk zero padded to 2 KiB and the fc2 bias to 1 KiB (every record the kernel copies is then
+        a whole number of 1 KiB LDS-DMA pieces)."""
+    W1, b1, Wd, bd, W2, b2, C_, hid, chunks = _ffn_args(fc1_w, fc1_b, dw_w, dw_b, fc2_w, fc2_b)
+    gam, bet = _f32(ln_g), _f32(ln_b)
+    assert C_ in (144, 180)
+    b1 = b1 + W1 @ bet
+    W1 = W1 * gam[None, :]
+    ks, nt = (C_ + 1 + 31) // 32, (C_ + 15) // 16
+    dww = _pad(_ffn_dw_record(Wd, bd, chunks).reshape(chunks, 640), chunks, 1024)
+    return _packed_ffn("tail3", _ffn_fc1(W1, b1, chunks, ks, True).to(torch.bfloat16), _ffn_fc2(W2, nt, chunks, "natural").to(torch.float16),
+                       dww.to(torch.float16), torch.zeros(4), torch.zeros(4), _pad(b2, 256), chunks, C_, hid, nt, ks, device)

@@ -1100,8 +1100,8 @@ def test_fp16_range_bound_switches_the_engine_to_the_bf16_hidden_kernel():
     torch.cuda.synchronize()
     eng = net.engine()
     assert getattr(eng, "fp16_fallbacks", 0) == 1
-    kinds = [hb["ffn"].khalf for hb in eng.layers[0]["habs"]]
-    assert kinds[1] not in ("v2", "v3") and all(k == "v2" for i, k in enumerate(kinds) if i != 1), kinds
+    kinds = [hb["ffn"].layout for hb in eng.layers[0]["habs"]]
+    assert kinds[1] == "ffn" and all(k == "ffn2" for i, k in enumerate(kinds) if i != 1), kinds
     assert torch.isfinite(y).all()
     assert O.psnr_float(y, ref) >= 40.0 and max_abs(y, ref) <= 0.08, (O.psnr_float(y, ref), max_abs(y, ref))
 
