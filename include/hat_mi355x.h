@@ -725,6 +725,24 @@ int hat_plan_forward_yuv420_deep(const hat_plan* plan, const void* src_y, int64_
 int hat_rect_sum(const void* x, int32_t dtype, int32_t ld, int32_t C, int32_t W, int32_t r0, int32_t r1, int32_t c0, int32_t c1,
                  int64_t bstride, int32_t B, float* out, int32_t ldo, float* tmp, uint32_t* counter, void* stream);
 
+/*
+ * The eight flips / transposes of fp32 planes (the dihedral group of the rectangle), with a scale and an optional accumulate:
+ * the data movement of the geometric self-ensemble (basicsr models/sr_model.py:132-178; HATEngine.forward_ensemble).
+ *     src: (planes, H, W) fp32, contiguous.   dst: (planes, H', W') fp32, contiguous.
+ *     dst[p][T(y, x)] = (accumulate ? dst[p][T(y, x)] : 0) + alpha * src[p][y][x]
+ * op = v | h << 1 | t << 2 names the member T_op = t^b2 o h^b1 o v^b0: v reverses the last axis (W), h reverses H, t swaps H and
+ * W, applied in that order (member i of the reference's list of eight).  With inverse != 0, T is T_op^-1 (t undone first, then
+ * h, then v): ops 5 and 6 (the quarter turns) are each other's inverses, every other member is its own.  (H', W') = (W, H) when
+ * the transform contains t, else (H, W); `inverse` does not change that, H and W always describe src.
+ * The product and the sum are each rounded to fp32 (no fused multiply-add); no atomics: the result is deterministic, and every
+ * element of dst is written exactly once per call.  One launch covers all planes.  Any H, W >= 1 (ragged tiles are handled
+ * inside).  HAT_EINVAL before any launch for: a null pointer, op outside 0..7, planes, H or W < 1, planes > 65535, H or W >
+ * 65535 * 64 (the grid), and src / dst byte ranges [p, p + 4 planes H W) that overlap (in place is not supported).
+ * A C host gets the self-ensemble of a network by putting this call around two plans, one per orientation.
+ */
+int hat_dihedral_f32(const float* src, float* dst, int32_t planes, int32_t H, int32_t W, int32_t op, int32_t inverse, float alpha,
+                     int32_t accumulate, void* stream);
+
 int hat_abi_version(void);
 /* name of the architecture the code objects in this library were compiled for ("gfx950") */
 const char* hat_target_arch(void);

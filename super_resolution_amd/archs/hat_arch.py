@@ -344,6 +344,24 @@ class HAT(nn.Module):
                 return self._forward_graph(x)
             return self.engine(x.device).forward(x).to(x.dtype)
 
+    def forward_ensemble(self, x, n: int = 8):
+        """The geometric self-ensemble of `forward` (the "+" of SR evaluation; the reference's SRModel.test_selfensemble, basicsr
+        models/sr_model.py:132-178, without its host round trips): the network on the first n of the eight flips / transposes of
+        x, every output transformed back, the mean of the n — all on the device (hat_dihedral_f32).  n in {1, 2, 4, 8}
+        (ValueError otherwise); member i = v | h << 1 | t << 2 with v: reverse W, h: reverse H, t: swap H and W, applied in that
+        order, so n = 4 runs no transposed shape and n = 1 is forward(x) bit for bit.  fp32 accumulation in member order, acc +=
+        (1 / n) * T_i^-1(y_i).  Input, output and refusals are forward's.  Runs eagerly also with use_graph=True (the ensemble
+        is not captured)."""
+        from .. import ops
+        n = ops.ensemble_members(n)
+        if self.training:
+            raise RuntimeError("this HAT implements the inference forward pass only: call .eval() first "
+                               "(training is out of scope, SURVEY §2)")
+        if not x.is_cuda:
+            raise RuntimeError("HAT.forward needs a GPU tensor: the MI355X HIP path is the only path (no CPU fallback)")
+        with torch.no_grad():
+            return self.engine(x.device).forward_ensemble(x, n).to(x.dtype)
+
     # ---- the 8-bit frame boundary (no counterpart in the reference's module: its caller converts on the host,
     # basicsr utils/img_util.py:9-35, :66-91, :131 and hat/models/hat_model.py:16-26, :110-112) ----
     def _check_u8_input(self, t):
@@ -354,46 +372,51 @@ class HAT(nn.Module):
         if self.cfg["in_chans"] != 3:
             raise RuntimeError(f"8-bit frames are three-channel images: in_chans={self.cfg['in_chans']} has no uint8 path")
 
-    def forward_to_u8(self, x, *, bgr: bool = False, out=None):
+    def forward_to_u8(self, x, *, bgr: bool = False, out=None, ensemble: int = 1):
         """`forward(x)` handed over as an 8-bit image: (B,3,H,W) float in [0,1], H and W window multiples as for `forward`
         -> (B,sH,sW,3) uint8 on the device, equal to the reference's `tensor2img` of `forward(x)` (clamp to [0,1], x255 in
         fp32, round half to even, CHW -> HWC; bgr=True: B,G,R byte order).  On the bf16 path conv_last converts in its
         epilogue and the fp32 image is never written.  out: a (B,sH,sW,3) uint8 device tensor to fill instead of a fresh one.
-        Runs eagerly also with use_graph=True (the 8-bit path is not captured)."""
+        Runs eagerly also with use_graph=True (the 8-bit path is not captured).
+        ensemble 2 / 4 / 8: `forward_ensemble(x, ensemble)` handed over in the same way (hat_planes_to_u8 converts its fp32 image);
+        ensemble=1 is the call as it always was."""
         self._check_u8_input(x)
         with torch.no_grad():
-            return self.engine(x.device).forward_to_u8(x, bgr=bgr, out=out)
+            return self.engine(x.device).forward_to_u8(x, bgr=bgr, out=out, ensemble=ensemble)
 
-    def forward_u8(self, frame, *, bgr: bool = False, out=None):
+    def forward_u8(self, frame, *, bgr: bool = False, out=None, ensemble: int = 1):
         """8-bit frames in, 8-bit frames out, all on the device: `frame` is an (h,w,3) or (B,h,w,3) uint8 device tensor of ANY
         size whose reflect-padding to the next window multiple is defined (padding smaller than the frame); returns
         (B,s*h,s*w,3) uint8.  Equal to the reference's pipeline float32(u8)/255 -> HATModel.pre_process (reflect-pad bottom /
         right) -> forward -> post_process (crop) -> tensor2img, bit for bit against this build's `forward`.  bgr=True: the
         bytes are B,G,R on both sides (OpenCV's order); out: a (B,s*h,s*w,3) uint8 device tensor to fill instead of a fresh
         one (with it the call allocates nothing where conv_last converts in its epilogue).  The padded fp32 input lives in the engine's per-shape workspace.
-        Runs eagerly also with use_graph=True (the 8-bit path is not captured)."""
+        Runs eagerly also with use_graph=True (the 8-bit path is not captured).
+        ensemble 2 / 4 / 8: pad -> `forward_ensemble` of the padded planes -> crop -> hat_planes_to_u8 (the reference's order of
+        pre_process / process / post_process); ensemble=1 is the call as it always was."""
         self._check_u8_input(frame)
         if frame.dim() == 3:
             frame = frame.unsqueeze(0)
         with torch.no_grad():
-            return self.engine(frame.device).forward_u8(frame, bgr=bgr, out=out)
+            return self.engine(frame.device).forward_u8(frame, bgr=bgr, out=out, ensemble=ensemble)
 
-    def forward_gt_u8(self, gt, *, bgr: bool = False, out=None):
+    def forward_gt_u8(self, gt, *, bgr: bool = False, out=None, ensemble: int = 1):
         """Ground-truth frames in, the super-resolution of their own bicubic low-resolution image out, all on the device: `gt`
         is an (H,W,3) or (B,H,W,3) uint8 device tensor; it is mod-cropped to multiples of `upscale` (a view), resized at
         1 / upscale by the reference's MATLAB-style `imresize` (super_resolution_amd/resize.py, bit for bit; float, unrounded,
         as hat/data/imagenet_paired_dataset.py:59 makes its LQ) into the reflect-padded input, and run as forward_u8 runs:
-        returns (B, H - H % s, W - W % s, 3) uint8, to be scored against the same mod-cropped `gt`.  bgr, out: as forward_u8."""
+        returns (B, H - H % s, W - W % s, 3) uint8, to be scored against the same mod-cropped `gt`.  bgr, out, ensemble: as
+        forward_u8."""
         if not isinstance(gt, torch.Tensor) or gt.dtype != torch.uint8:
             raise RuntimeError(f"forward_gt_u8 needs a uint8 device tensor, got {getattr(gt, 'dtype', type(gt).__name__)}")
         self._check_u8_input(gt)
         if gt.dim() == 3:
             gt = gt.unsqueeze(0)
         with torch.no_grad():
-            return self.engine(gt.device).forward_gt_u8(gt, bgr=bgr, out=out)
+            return self.engine(gt.device).forward_gt_u8(gt, bgr=bgr, out=out, ensemble=ensemble)
 
     def forward_yuv420(self, frame, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False, depth: int = 8, out_depth=None,
-                       msb=None, out=None):
+                       msb=None, out=None, ensemble: int = 1):
         """4:2:0 YCbCr frames in, 4:2:0 frames out, all on the device: `frame` is a (3h/2, w) or (B, 3h/2, w) uint8 device tensor in
         the standard contiguous layout of `fmt` ('nv12', 'nv21', 'i420': super_resolution_amd/yuv.py), h and w even and of ANY
         size whose reflect-padding to the next window multiple is defined; returns (B, 3sh/2, sw) uint8 in the same layout.
@@ -403,7 +426,9 @@ class HAT(nn.Module):
         epilogue).  depth 10 / 12 / 16: the frame is a uint16 tensor of n-bit codes (P010 / P012 / P016 for nv12 / nv21,
         yuv420p10le ... for i420; msb=True / False overrides the alignment); out_depth (default: depth) is the width of the
         result, uint8 for 8 and uint16 otherwise, so 8 -> 10 writes ten bits from an 8-bit source.  The input dtype must agree
-        with `depth`.  No transfer function is applied.  Runs eagerly also with use_graph=True (the byte paths are not captured)."""
+        with `depth`.  No transfer function is applied.  Runs eagerly also with use_graph=True (the byte paths are not captured).
+        ensemble 2 / 4 / 8: the padded RGB planes go through `forward_ensemble`, then crop and yuv.planes_to_yuv420
+        (hat_planes_to_yuv420); ensemble=1 is the call as it always was."""
         if not isinstance(frame, torch.Tensor):
             raise TypeError(f"forward_yuv420 needs a uint8 device tensor, got {type(frame).__name__}")
         if frame.dtype not in (torch.uint8, torch.uint16):
@@ -419,7 +444,7 @@ class HAT(nn.Module):
             frame = frame.unsqueeze(0)
         with torch.no_grad():
             return self.engine(frame.device).forward_yuv420(frame, fmt=fmt, to_rgb=to_rgb, from_rgb=from_rgb, out=out, depth=depth,
-                                                            out_depth=out_depth, msb=msb)
+                                                            out_depth=out_depth, msb=msb, ensemble=ensemble)
 
     # ---- exact full-frame sharding into row bands (no counterpart in the reference, whose tile loop
     # hat_model.py:40-108 gives a DIFFERENT result than the full frame: SURVEY F6) ----

@@ -607,6 +607,62 @@ class HATEngine:
         with self._lock, torch.cuda.device(self.dev):
             return self._forward(x, one_stream=one_stream)
 
+    def forward_ensemble(self, x: torch.Tensor, n: int = 8, *, one_stream: Optional[bool] = None) -> torch.Tensor:
+        """The geometric self-ensemble ("+" mode; basicsr models/sr_model.py:132-178): the mean over the first n of the eight flips /
+        transposes T_i of x of T_i^-1(forward(T_i x)), n in {1, 2, 4, 8} (ValueError otherwise).  Member i = v | h << 1 | t << 2
+        (v: reverse W, h: reverse H, t: swap H and W, applied in that order).  Accumulated in fp32 in member order, acc += (1 / n) *
+        T_i^-1(y_i); n = 1 is forward(x).  Shapes and refusals are forward's.  hat_dihedral_f32 makes every transformed input (into
+        the workspace of the member's shape: the transposed members run a (B, W, H) workspace) and undoes, scales and adds every
+        output in one pass; no torch op computes."""
+        n = ops.ensemble_members(n)
+        if not x.is_cuda:
+            raise RuntimeError("HAT forward needs a device tensor: the HIP path is the only path")
+        if x.device != self.dev:
+            raise RuntimeError(f"input is on {x.device} but this engine's weights and workspace live on {self.dev}")
+        with self._lock, torch.cuda.device(self.dev):
+            if n == 1:
+                return self._forward(x, one_stream=one_stream)
+            self._check_input(x)
+            # the result is the caller's, as forward's is: it is the accumulator (the byte paths, whose fp32 image never leaves
+            # the engine, keep theirs in the workspace: _ens_acc)
+            acc = torch.empty(x.shape[0], x.shape[1], x.shape[2] * self.scale, x.shape[3] * self.scale, dtype=torch.float32, device=self.dev)
+            return self._ensemble(x, n, acc, one_stream=one_stream)
+
+    def _check_input(self, x):
+        """The shapes every forward refuses (_forward_gen calls it; an ensemble calls it before it allocates or launches)."""
+        if x.dim() != 4 or x.shape[1] != self.cfg["in_chans"]:
+            raise RuntimeError(f"expected (B,{self.cfg['in_chans']},H,W), got {tuple(x.shape)}")
+        if x.shape[2] % self.ws or x.shape[3] % self.ws:  # the reference raises from calculate_mask's view (hat_arch.py:815), SURVEY F4
+            raise RuntimeError(f"input size ({x.shape[2]},{x.shape[3]}) is not a multiple of window_size {self.ws}")
+
+    def _ws_buffer(self, ws, key, shape):
+        """An fp32 buffer that lives in the per-shape workspace `ws`, allocated with its first use (as x_u8 is)."""
+        t = ws.get(key)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = ws[key] = torch.zeros(shape, dtype=torch.float32, device=self.dev)
+            ws["bytes"] += t.numel() * 4
+        return t
+
+    def _ens_acc(self, ws, B, Hp, Wp):
+        """The byte paths' fp32 accumulator of the (B, Hp, Wp) workspace: the ensembled image before the crop and the conversion."""
+        return self._ws_buffer(ws, "ens_acc", (B, 3, Hp * self.scale, Wp * self.scale))
+
+    def _ensemble(self, x, n, acc, one_stream=None):
+        """acc (B, C, sH, sW) fp32 = sum over i < n of (1 / n) * T_i^-1(forward(T_i x)), in member order; returns acc.  Called under
+        the lock.  x must not be the buffer a member's input is written to (it is not: that is ens_x, this method's own)."""
+        x = x.to(torch.float32).contiguous()
+        B, C_, H, W = x.shape
+        for i in range(n):
+            if i == 0:
+                xi = x
+            else:
+                Hi, Wi = (W, H) if i & 4 else (H, W)
+                xi = self._ws_buffer(self._workspace(B, Hi, Wi), "ens_x", (B, C_, Hi, Wi))
+                ops.dihedral(x, xi, op=i)
+            y = self._forward(xi, one_stream=one_stream)
+            ops.dihedral(y, acc, op=i, inverse=True, alpha=1.0 / n, accumulate=i > 0)
+        return acc
+
     def _check_u8(self):
         if self.cfg["in_chans"] != 3:
             raise RuntimeError(f"8-bit frames are three-channel images: in_chans={self.cfg['in_chans']} has no uint8 path "
@@ -621,26 +677,43 @@ class HATEngine:
                                f"{tuple(out.shape)} {out.dtype} on {out.device}")
         return out
 
-    def forward_to_u8(self, x: torch.Tensor, *, crop=None, bgr: bool = False, out=None, one_stream: Optional[bool] = None) -> torch.Tensor:
+    def forward_to_u8(self, x: torch.Tensor, *, crop=None, bgr: bool = False, out=None, one_stream: Optional[bool] = None,
+                      ensemble: int = 1) -> torch.Tensor:
         """forward(x) converted on the device as the reference's tensor2img converts it: (B,3,H,W) float in ->
         (B,h_out,w_out,3) uint8 out, crop = (h_out, w_out) the top-left pixels kept (default: all of (sH, sW)), bgr: bytes in
         B, G, R order, out: write into this tensor instead of a fresh one (then the call allocates nothing on the fused path).
-        The fp32 image is not written where conv_last converts in its epilogue (u8_fused_calls counts those)."""
+        The fp32 image is not written where conv_last converts in its epilogue (u8_fused_calls counts those).
+        ensemble 2 / 4 / 8: forward_ensemble's fp32 image (in the workspace), then hat_planes_to_u8 with the crop."""
         self._check_u8()
+        ensemble = ops.ensemble_members(ensemble)
         if not x.is_cuda or x.device != self.dev:
             raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
         ho, wo = (x.shape[2] * self.scale, x.shape[3] * self.scale) if crop is None else (int(crop[0]), int(crop[1]))
         if not (1 <= ho <= x.shape[2] * self.scale and 1 <= wo <= x.shape[3] * self.scale):
             raise RuntimeError(f"crop {(ho, wo)} does not lie inside the output {(x.shape[2] * self.scale, x.shape[3] * self.scale)}")
         with self._lock, torch.cuda.device(self.dev):
+            if ensemble > 1:
+                self._check_input(x)
+                out = self._u8_out(out, (x.shape[0], ho, wo, 3))
+                return self._ensemble_to_u8(x, ensemble, out, bgr, one_stream=one_stream)
             return self._forward(x, one_stream=one_stream, u8=(ho, wo, bool(bgr), self._u8_out(out, (x.shape[0], ho, wo, 3))))
 
-    def forward_u8(self, frame: torch.Tensor, *, bgr: bool = False, out=None) -> torch.Tensor:
+    def _ensemble_to_u8(self, x, n, out, bgr, one_stream=None):
+        """The ensembled fp32 image of the padded planes x -> out (B,h_out,w_out,3) uint8, its top-left crop (hat_planes_to_u8)."""
+        B, _, Hp, Wp = x.shape
+        acc = self._ensemble(x, n, self._ens_acc(self._workspace(B, Hp, Wp), B, Hp, Wp), one_stream=one_stream)
+        ops.planes_to_u8(acc, out, bgr=bool(bgr))
+        self.u8_planes_calls += 1
+        return out
+
+    def forward_u8(self, frame: torch.Tensor, *, bgr: bool = False, out=None, ensemble: int = 1) -> torch.Tensor:
         """(B,h,w,3) uint8 device frames of any size the reflection allows -> (B,s*h,s*w,3) uint8: float(v) / 255, the
         reflect-pad to the next window multiple (hat_u8_to_planes, into this shape's workspace), the forward, the crop and
         tensor2img's conversion (in conv_last's epilogue or hat_planes_to_u8).  bgr: the bytes are B, G, R on both sides;
-        out: the caller's (B,s*h,s*w,3) uint8 result tensor (default: a fresh one)."""
+        out: the caller's (B,s*h,s*w,3) uint8 result tensor (default: a fresh one).  ensemble 2 / 4 / 8: the padded planes go
+        through forward_ensemble (pad first, ensemble the padded image, crop last), then hat_planes_to_u8."""
         self._check_u8()
+        ensemble = ops.ensemble_members(ensemble)
         if frame.dim() != 4 or frame.shape[3] != 3 or frame.dtype != torch.uint8:
             raise RuntimeError(f"expected (B,h,w,3) uint8 frames, got {tuple(frame.shape)} {frame.dtype}")
         if not frame.is_cuda or frame.device != self.dev:
@@ -659,15 +732,18 @@ class HATEngine:
                 ws["bytes"] += ws["x_u8"].numel() * 4
             ops.u8_to_planes(frame, ws["x_u8"], bgr=bgr)
             ho, wo = h * self.scale, w * self.scale
+            if ensemble > 1:
+                return self._ensemble_to_u8(ws["x_u8"], ensemble, self._u8_out(out, (B, ho, wo, 3)), bgr)
             return self._forward(ws["x_u8"], u8=(ho, wo, bool(bgr), self._u8_out(out, (B, ho, wo, 3))))
 
-    def forward_gt_u8(self, gt: torch.Tensor, *, bgr: bool = False, out=None) -> torch.Tensor:
+    def forward_gt_u8(self, gt: torch.Tensor, *, bgr: bool = False, out=None, ensemble: int = 1) -> torch.Tensor:
         """(B,H,W,3) uint8 device GROUND-TRUTH frames -> the (B, H - H % s, W - W % s, 3) uint8 super-resolution of their own
         bicubic low-resolution image, as the reference's GT-only dataset makes it (hat/data/imagenet_paired_dataset.py:49-59):
         mod-crop to multiples of the upscale s (a view, no copy), resize.imresize_u8 at 1 / s (ops.imresize: float,
         unrounded, with its overshoot) written reflect-padded into this shape's workspace, the forward, the crop and
-        tensor2img's conversion as in forward_u8.  bgr, out: as in forward_u8."""
+        tensor2img's conversion as in forward_u8.  bgr, out, ensemble: as in forward_u8."""
         self._check_u8()
+        ensemble = ops.ensemble_members(ensemble)
         if not isinstance(gt, torch.Tensor) or gt.dtype != torch.uint8 or gt.dim() != 4 or gt.shape[3] != 3:
             raise RuntimeError(f"expected (B,H,W,3) uint8 ground-truth frames, got {tuple(getattr(gt, 'shape', ()))} {getattr(gt, 'dtype', type(gt))}")
         if not gt.is_cuda or gt.device != self.dev:
@@ -691,16 +767,20 @@ class HATEngine:
                 ws["bytes"] += ws["x_u8"].numel() * 4
             ops.imresize(gt, 1.0 / s, dst=ws["x_u8"], pad_to=(Hp, Wp), bgr=bgr)
             ho, wo = h * s, w * s
+            if ensemble > 1:
+                return self._ensemble_to_u8(ws["x_u8"], ensemble, self._u8_out(out, (B, ho, wo, 3)), bgr)
             return self._forward(ws["x_u8"], u8=(ho, wo, bool(bgr), self._u8_out(out, (B, ho, wo, 3))))
 
     def forward_yuv420(self, frame: torch.Tensor, *, fmt: str = "nv12", to_rgb, from_rgb, out=None, depth: int = 8, out_depth=None,
-                       msb=None) -> torch.Tensor:
+                       msb=None, ensemble: int = 1) -> torch.Tensor:
         """(B,3h/2,w) uint8 device frames in the layout `fmt` (yuv.py), any even size the reflection allows -> (B,3sh/2,sw) uint8
         in the same layout: hat_yuv420_to_planes into this shape's workspace, the forward, the crop and the conversion back (in
         conv_last's epilogue or hat_planes_to_yuv420).  to_rgb / from_rgb: yuv.csc's matrices (of `depth` / `out_depth`).  out: the
         caller's result tensor.  depth / out_depth 10, 12, 16: uint16 frames on that side (yuv.py, "Deep samples"; out_depth
-        defaults to depth); msb: MSB-aligned words (default: by the layout)."""
+        defaults to depth); msb: MSB-aligned words (default: by the layout).  ensemble 2 / 4 / 8: the padded RGB planes go through
+        forward_ensemble, then hat_planes_to_yuv420 with the crop."""
         self._check_u8()
+        ensemble = ops.ensemble_members(ensemble)
         from . import yuv as _yuv
         out_depth = depth if out_depth is None else out_depth
         in_msb, out_msb = bool(_yuv.container(depth, fmt, msb)[3]), bool(_yuv.container(out_depth, fmt, msb)[3])   # (checks depths and fmt)
@@ -735,6 +815,11 @@ class HATEngine:
                 ws["x_u8"] = torch.zeros(B, 3, Hp, Wp, dtype=torch.float32, device=self.dev)
                 ws["bytes"] += ws["x_u8"].numel() * 4
             ops.yuv420_to_planes(*src, ws["x_u8"], to_rgb, depth=depth, msb=in_msb)
+            if ensemble > 1:
+                acc = self._ensemble(ws["x_u8"], ensemble, self._ens_acc(ws, B, Hp, Wp))
+                ops.planes_to_yuv420(acc, *dst, from_rgb, depth=out_depth, msb=out_msb)
+                self.yuv_planes_calls += 1
+                return out
             self._forward(ws["x_u8"], yuv=(dst, from_rgb, out, out_depth, out_msb))
         return out
 
@@ -761,11 +846,8 @@ class HATEngine:
         band's output rows (ghost rows included; the driver keeps the owned ones).
         u8 = (h_out, w_out, bgr, out): the unsharded forward fills and returns out, (B,h_out,w_out,3) uint8 (forward_to_u8).
         yuv = ((y, cb, cr) views, from_rgb, out, depth, msb): it fills the views of a 4:2:0 frame and returns out (forward_yuv420)."""
-        if x.dim() != 4 or x.shape[1] != self.cfg["in_chans"]:
-            raise RuntimeError(f"expected (B,{self.cfg['in_chans']},H,W), got {tuple(x.shape)}")
+        self._check_input(x)
         B, _, H, W = x.shape
-        if H % self.ws or W % self.ws:  # the reference raises from calculate_mask's view (hat_arch.py:815), SURVEY F4
-            raise RuntimeError(f"input size ({H},{W}) is not a multiple of window_size {self.ws}")
         x = x.to(torch.float32).contiguous()
         w = dict(self._workspace(B, H, W, tag=(None if band is None else ("band", band.idx, band.n))))
         if band is not None and band.e1 - band.e0 != H:

@@ -23,14 +23,17 @@ def _raw(t):
 
 
 def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", matrix: str = "bt601", full_range: bool = False, depth: int = 8,
-                   out_depth=None, msb=None):
+                   out_depth=None, msb=None, ensemble: int = 1):
     """Generator: for every (h,w,3) uint8 array of `frames` (all of one size) yield the (s*h,s*w,3) uint8 array that
     `net.forward_u8` computes for it, in order.  `net`: a HAT / HATX module on a GPU, in eval mode.  The yielded array is
     the caller's own (copied out of the pinned buffer).  An empty sequence yields nothing.
     pixfmt 'nv12' / 'nv21' / 'i420': the frames are (3h/2, w) uint8 arrays in that 4:2:0 layout (yuv.py), the yielded arrays
     (3sh/2, sw) ones, computed by `net.forward_yuv420` with `matrix` and `full_range` (bgr does not apply).  Same slots,
     same copy stream, same events: only the buffer shapes and the forward differ.  depth / out_depth / msb (4:2:0 only): as
-    HAT.forward_yuv420 takes them; a deep side's frames are uint16 arrays, and so are its pinned and device buffers."""
+    HAT.forward_yuv420 takes them; a deep side's frames are uint16 arrays, and so are its pinned and device buffers.
+    ensemble 2 / 4 / 8: every frame through the geometric self-ensemble (HAT.forward_ensemble) of that many members."""
+    from .ops import ensemble_members
+    ensemble = ensemble_members(ensemble)
     if pixfmt not in PIXFMTS:
         raise RuntimeError(f"unknown pixfmt {pixfmt!r}: one of {PIXFMTS}")
     yuv420 = pixfmt != "rgb24"
@@ -55,7 +58,7 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
         h, w = _yuv.frame_size(first.shape)
         in_shape, out_shape, shape_text = first.shape, _yuv.frame_shape(s * h, s * w), f"({3 * h // 2},{w})"
         forward = lambda src, dst: net.forward_yuv420(src, fmt=pixfmt, matrix=matrix, full_range=full_range, out=dst, depth=depth,
-                                                      out_depth=out_depth, msb=msb)
+                                                      out_depth=out_depth, msb=msb, ensemble=ensemble)
     else:
         if depth != 8 or out_depth not in (None, 8):
             raise RuntimeError("rgb24 frames are 8-bit: depth and out_depth belong to the 4:2:0 pixel formats")
@@ -63,7 +66,7 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
             raise RuntimeError(f"expected (h,w,3) uint8 frames, got {first.shape} {first.dtype}")
         h, w, _ = first.shape
         in_shape, out_shape, shape_text = (h, w, 3), (s * h, s * w, 3), f"({h},{w},3)"
-        forward = lambda src, dst: net.forward_u8(src, bgr=bgr, out=dst)
+        forward = lambda src, dst: net.forward_u8(src, bgr=bgr, out=dst, ensemble=ensemble)
     # Nothing of the device state stays entered across a yield: the buffers and the copy stream are made once, and every step
     # enters the device and takes the stream that is current THEN, so a caller may switch device or stream between frames.
     with torch.cuda.device(dev):

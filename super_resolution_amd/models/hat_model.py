@@ -2,6 +2,8 @@
 basicsr SRModel/BaseModel): pad to a window multiple, run the network whole or tile by tile, crop, convert to uint8,
 save, score.  Same option dictionary as the reference's test YAMLs (`network_g`, `path.pretrain_network_g`,
 `path.param_key_g`, `path.strict_load_g`, `tile.{tile_size,tile_pad}`, `val.{save_img,suffix,metrics}`).
+`val.self_ensemble: true | 2 | 4 | 8` (no counterpart in the reference's YAMLs; its SRModel.test_selfensemble is never called) runs
+every forward of every validation branch as the geometric self-ensemble of that many members (`true`: 8), whole or per tile.
 
 Deviations (documented in INTEGRATION.md): a tile that fails raises instead of being printed and skipped
 (hat_model.py:89-90); images are read/written with PIL; `num_gpu: 0` (CPU) is not supported by the MI355X path.
@@ -33,6 +35,34 @@ class HATModel:
         self.net_g = self.model_to_device(self.net_g)
         self.scale = opt.get("scale", 1)
         self.metric_results = {}
+
+    @staticmethod
+    def self_ensemble_members(value) -> int:
+        """`val.self_ensemble` -> the number of ensemble members: absent / None / false -> 1 (no ensemble), true -> 8, the
+        integers 2, 4, 8 -> themselves; anything else (1, 3, "8", 8.0 ...) is a ValueError: the option is never guessed at."""
+        if value is None or value is False:
+            return 1
+        if value is True:
+            return 8
+        if isinstance(value, int) and value in (2, 4, 8):
+            return value
+        raise ValueError(f"val.self_ensemble is true, 2, 4 or 8 (members of the geometric self-ensemble), got {value!r}")
+
+    @property
+    def ensemble(self) -> int:
+        return self.self_ensemble_members((self.opt.get("val") or {}).get("self_ensemble"))
+
+    def _forward_fn(self):
+        """The callable process / tile_process hand the (padded) image or a tile to: the network, or with val.self_ensemble its
+        forward_ensemble — so a tiled frame keeps the reference's tile grid and every tile is ensembled on its own.
+        forward_ensemble is a method of the bare module, so with `num_gpu > 1` the ensemble does not go through the
+        nn.DataParallel wrapper: it runs on this model's device.  Validation feeds one image at a time, which DataParallel
+        would hand to one device anyway (model_to_device: tile_parallel / band_parallel are the multi-GPU paths)."""
+        n = self.ensemble
+        if n == 1:
+            return self.net_g
+        bare = self.get_bare_model(self.net_g)
+        return lambda t: bare.forward_ensemble(t, n)
 
     def model_to_device(self, net):
         """basicsr BaseModel.model_to_device (base_model.py:91-104): `num_gpu > 1` wraps the network in nn.DataParallel, as the
@@ -76,13 +106,13 @@ class HATModel:
 
     def process(self):  # hat_model.py:28-38
         with torch.no_grad():
-            self.output = self.net_g(self.img)
+            self.output = self._forward_fn()(self.img)
 
     def tile_process(self):  # hat_model.py:40-108
         _, _, h, w = self.img.shape
         tiles = tp.reference_tiles(h, w, self.opt["tile"]["tile_size"], self.opt["tile"]["tile_pad"])
         with torch.no_grad():
-            self.output = tp.tile_forward(self.img, self.net_g, self.scale, tiles)
+            self.output = tp.tile_forward(self.img, self._forward_fn(), self.scale, tiles)
 
     def post_process(self):  # hat_model.py:110-112
         _, _, h, w = self.output.size()
@@ -110,12 +140,13 @@ class HATModel:
         `tile`, hat_u8_to_planes builds the padded input (pre_process_u8), tile_process runs as always and hat_planes_to_u8
         crops and converts the assembled fp32 output.  lq: the
         dataset's (1,3,h,w) float image, which must hold 8-bit values (v / 255, what data.read_image produces).
-        on_device (`val.metrics_on_device`): return the (h,w,3) uint8 device tensor instead of downloading it."""
+        on_device (`val.metrics_on_device`): return the (h,w,3) uint8 device tensor instead of downloading it.
+        `val.self_ensemble`: forward_u8(ensemble=n) without `tile`; with `tile`, tile_process ensembles every tile."""
         from .. import ops
         frame = self._u8_frame(lq, "val.u8_on_device", "input")
         if "tile" not in self.opt:
             with torch.no_grad():
-                out = self.get_bare_model(self.net_g).forward_u8(frame)
+                out = self.get_bare_model(self.net_g).forward_u8(frame, **self._ensemble_kw())
         else:
             self.pre_process_u8(frame)
             self.tile_process()
@@ -124,6 +155,11 @@ class HATModel:
             ops.planes_to_u8(self.output.to(torch.float32).contiguous(), out)
             del self.img, self.output
         return out[0] if on_device else out[0].cpu().numpy()
+
+    def _ensemble_kw(self) -> dict:
+        """ensemble=n for the byte forwards under val.self_ensemble; nothing without it (the call is then today's call)."""
+        n = self.ensemble
+        return {"ensemble": n} if n > 1 else {}
 
     def pre_process_u8(self, frame: torch.Tensor):
         """pre_process for a (B,h,w,3) uint8 device frame: self.img = the reflect-padded float32(v) / 255 planes, bit for bit
@@ -182,11 +218,11 @@ class HATModel:
         """`val.lq_on_device`: the (1,H,W,3) uint8 device ground truth -> the (h,w,3) uint8 device result of its own bicubic
         low-resolution image (resize.py's imresize at 1 / scale, made on the device: the float LQ never exists on the host).
         Without `tile`, HAT.forward_gt_u8 does it all; with `tile`, ops.imresize writes the padded planes, tile_process runs
-        as always and hat_planes_to_u8 crops and converts, as test_u8 does."""
+        as always and hat_planes_to_u8 crops and converts, as test_u8 does.  `val.self_ensemble`: as in test_u8."""
         from .. import ops
         if "tile" not in self.opt:
             with torch.no_grad():
-                return self.get_bare_model(self.net_g).forward_gt_u8(gt)[0]
+                return self.get_bare_model(self.net_g).forward_gt_u8(gt, **self._ensemble_kw())[0]
         window_size = self.opt["network_g"]["window_size"]
         s = self.scale = self.opt.get("scale", 1)
         b, H, W, _ = gt.shape
@@ -242,6 +278,7 @@ class HATModel:
         val = self.opt.get("val") or {}
         metrics = val.get("metrics")
         self.metric_results = {m: 0.0 for m in (metrics or {})}
+        self.ensemble   # a val.self_ensemble that is not true / 2 / 4 / 8 raises here, before the first image
         per_image = []
         n = 0
         on_device = bool(val.get("metrics_on_device"))   # implies u8_on_device; the known metrics are scored where the result is

@@ -338,6 +338,35 @@ def planes_to_u8(src, dst, *, bgr: bool = False):
                              _stream()), "hat_planes_to_u8"), tag=f"planes {Hs}x{Ws} -> u8 {dst.shape[1]}x{dst.shape[2]}")
 
 
+ENSEMBLE_SIZES = (1, 2, 4, 8)   # members of the geometric self-ensemble: the first n of the eight (HATEngine.forward_ensemble)
+
+
+def ensemble_members(n) -> int:
+    """The member count a caller asked for: 1, 2, 4 or 8 as an int (a bool is not a count); anything else is a ValueError."""
+    if isinstance(n, bool) or not isinstance(n, int) or n not in ENSEMBLE_SIZES:
+        raise ValueError(f"the self-ensemble runs the first 1, 2, 4 or 8 of the eight flips / transposes, got {n!r}")
+    return n
+
+
+def dihedral(src, dst, *, op: int, inverse: bool = False, alpha: float = 1.0, accumulate: bool = False):
+    """src (..., H, W) fp32 -> dst (..., H', W') fp32, the leading axes are planes: dst[T(y, x)] = (accumulate ? dst : 0) + alpha *
+    src[y, x] with T member `op` = v | h << 1 | t << 2 of the eight flips / transposes (v: reverse W, h: reverse H, t: swap H and W,
+    in that order) or, with inverse, its inverse; (H', W') = (W, H) when op contains t (hat_dihedral_f32)."""
+    lib = _lib.load()
+    if src.dtype != torch.float32 or dst.dtype != torch.float32 or src.dim() < 2 or src.device != dst.device:
+        raise RuntimeError(f"dihedral needs fp32 planes on one device, got {src.dtype} on {src.device} and {dst.dtype} on {dst.device}")
+    if not 0 <= int(op) <= 7:
+        raise RuntimeError(f"dihedral: op is one of the eight members 0..7, got {op}")
+    H, W = src.shape[-2:]
+    want = tuple(src.shape[:-2]) + ((W, H) if op & 4 else (H, W))
+    if tuple(dst.shape) != want:
+        raise RuntimeError(f"dihedral: member {op} of {tuple(src.shape)} planes needs a {want} destination, got {tuple(dst.shape)}")
+    planes = src.numel() // (H * W)
+    _timed("dihedral_transpose_kernel" if op & 4 else "dihedral_flip_kernel", 0.0, lambda: _lib.check(
+        lib.hat_dihedral_f32(_ptr(src), _ptr(dst), planes, H, W, int(op), int(bool(inverse)), float(alpha), int(bool(accumulate)), _stream()),
+        "hat_dihedral_f32"), tag=f"dihedral op {op}{' inv' if inverse else ''} {planes}x{H}x{W}", nbytes=4.0 * src.numel() * (3 if accumulate else 2))
+
+
 # ---- MATLAB bicubic imresize (definition: resize.py; kernels: csrc/hat_resize.hip) ----
 resize_calls = 0            # imresize calls = hat_imresize_rows + hat_imresize_cols_* pairs
 _RESIZE_TABLES_KEPT = 32    # axes; a folder of images of many sizes must not pile tables up

@@ -12,8 +12,9 @@ from .data import FolderDataset
 from .models import HATModel
 
 
-def parse_options(path: str, u8: bool = False, metrics_on_device: bool = False, lq_on_device: bool = False) -> dict:
-    """u8 (the --u8 flag): set val.u8_on_device; metrics_on_device (--metrics-on-device): set val.metrics_on_device and, since
+def parse_options(path: str, u8: bool = False, metrics_on_device: bool = False, lq_on_device: bool = False, self_ensemble=None) -> dict:
+    """self_ensemble (--self-ensemble [N]): set val.self_ensemble to N (2, 4 or 8);
+    u8 (the --u8 flag): set val.u8_on_device; metrics_on_device (--metrics-on-device): set val.metrics_on_device and, since
     it implies it, val.u8_on_device; lq_on_device (--lq-on-device): set val.lq_on_device (and val.u8_on_device); without the
     flags the options are exactly what the YAML says."""
     with open(path) as f:
@@ -24,6 +25,8 @@ def parse_options(path: str, u8: bool = False, metrics_on_device: bool = False, 
         opt["val"] = dict(opt.get("val") or {}, u8_on_device=True)
     if metrics_on_device:
         opt["val"] = dict(opt.get("val") or {}, u8_on_device=True, metrics_on_device=True)
+    if self_ensemble is not None:
+        opt["val"] = dict(opt.get("val") or {}, self_ensemble=self_ensemble)
     opt["is_train"] = False
     for phase, d in (opt.get("datasets") or {}).items():
         d["phase"] = phase.split("_")[0]
@@ -41,8 +44,12 @@ def main(argv=None):
                     help="PSNR / SSIM from 8-bit frames on the device (sets val.metrics_on_device and val.u8_on_device)")
     ap.add_argument("--lq-on-device", action="store_true",
                     help="make the bicubic LQ image on the device from the uploaded 8-bit ground truth (sets val.lq_on_device)")
+    ap.add_argument("--self-ensemble", nargs="?", type=int, const=8, default=None, choices=[2, 4, 8], metavar="N",
+                    help="geometric self-ensemble over the first N = 2, 4 or 8 (default when N is left out) flips / transposes of "
+                         "every image (sets val.self_ensemble)")
     args = ap.parse_args(argv)
-    opt = parse_options(args.opt, u8=args.u8, metrics_on_device=args.metrics_on_device, lq_on_device=args.lq_on_device)
+    opt = parse_options(args.opt, u8=args.u8, metrics_on_device=args.metrics_on_device, lq_on_device=args.lq_on_device,
+                        self_ensemble=args.self_ensemble)
     model = HATModel(opt, device=args.device)
     results = {}
     for _, dopt in sorted((opt.get("datasets") or {}).items()):
