@@ -173,7 +173,7 @@ int hat_conv64r_launch(const HatConvDesc& d, hipStream_t s) {
     int m = 32 / nsl;                       // groups of 8 workgroups per slice: 256 workgroups for 4 slices
     if (m < 1) m = 1;
     while (m > 1 && 8 * (m - 1) >= ntiles) --m;   // (small frames: no idle workgroups)
-    const int nwps = 8 * m;
+    const int nwps = 8 * m;   // tests/test_gpu_multitrip.py: conv64r_trip_tiles(nsl, ntiles) restates m and nwps
     HAT_LAUNCH(kern, dim3(8 * nsl * m), dim3(R_NTHR), R_LDS, s, d, nsl, nwps, tiles_x, tiles_y);
     return hat_check_launch();
 }

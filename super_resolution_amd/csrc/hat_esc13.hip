@@ -155,7 +155,7 @@ extern "C" int hat_esc_conv13(const void* x, int32_t ldx, const void* wp, int32_
     if (!x || !wp || !y16 || B < 1 || H < 1 || W < 1 || ldx < 16 || ldx % 8 || Kpad < 169 * 16 || Kpad % 8) return HAT_EINVAL;
     if (dtype != HAT_BF16) return HAT_EUNSUPPORTED;
     const int tiles_x = (W + E_TC - 1) / E_TC, tiles_y = (H + E_TR - 1) / E_TR, ntiles = tiles_x * tiles_y;
-    int gx = 256 / (B < 2 ? 1 : (B < 4 ? 2 : 4));
+    int gx = 256 / (B < 2 ? 1 : (B < 4 ? 2 : 4));   // tests/test_gpu_multitrip.py: ESC13_TRIP_TILES[B] 32 x 32 tiles per sample
     if (gx > ntiles) gx = ntiles;
     static const int rw = [] { const char* e = getenv("HAT_ESC13_RW"); return e && atoi(e) == 2 ? 2 : 4; }();   // 2: round 2's sixteen-wave shape (A/B)
     auto launch = [&](auto kern, int waves) -> int {

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void ln_kernel(const float* __restrict__ x, Ou
 template <typename OutT>
 int launch_ln(const float* x, void* y, const float* gamma, const float* beta, float* gap, int B, long npix, int C,
               int ldy, int gap_c, hipStream_t s) {
-    dim3 grid(LN_BLOCKS, B), block(256);
+    dim3 grid(LN_BLOCKS, B), block(256);   // tests/test_gpu_multitrip.py: LN_TRIP_PIXELS = LN_BLOCKS * 16 per sample
     const int nv = (C + 63) / 64;
     OutT* yo = reinterpret_cast<OutT*>(y);
     switch (nv) {
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(1024) void esc_weights_kernel(const float* __restri
         // FOUR iterations' loads (32) are issued before the first add: a 720p frame has 7200 partial blocks = 15 iterations,
         // each one round trip to wherever the tail's workgroups left them (other XCDs' L2 / HBM): 4 round trips instead of 15.
         // The adds keep the order of the one-iteration-at-a-time loop (same bits).
-        for (int k0 = pp; k0 < nblk; k0 += np * 8 * 4) {
+        for (int k0 = pp; k0 < nblk; k0 += np * 8 * 4) {   // tests/test_gpu_multitrip.py: ESCW_TRIP_BLOCKS = np * 32 (2048 or 1024)
             float v[4][8];
 #pragma unroll
             for (int it = 0; it < 4; ++it)

@@ -294,7 +294,7 @@ extern "C" int hat_ocab_qkv(const HatMlpDesc* dp, void* stream) {
     const long npix = (long)d.B * d.H * d.W, tiles = (npix + 15) / 16;
     static const int waves = getenv("HAT_QKV_WAVES") ? atoi(getenv("HAT_QKV_WAVES")) : 8;    // (A/B switch: 8 or 16 waves per workgroup; no difference measured)
     const int nw = waves == 8 ? 8 : 16;
-    int gx = 256;
+    int gx = 256;   // tests/test_gpu_multitrip.py: QKV_TRIP_TILES = 256 * nw
     if ((long)gx * nw > tiles) gx = (int)((tiles + nw - 1) / nw);
     auto kern = nw == 8 ? ocab_qkv_kernel<8> : ocab_qkv_kernel<16>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, QK_LDS);
@@ -318,7 +318,7 @@ extern "C" int hat_ocab_mlp(const HatMlpDesc* dp, void* stream) {
     const long npix = (long)d.B * d.H * d.W, tiles = (npix + 15) / 16;
     static const int waves = getenv("HAT_MLP_WAVES") ? atoi(getenv("HAT_MLP_WAVES")) : 8;    // (A/B switch; 16 waves spill at 128 registers and measured slower)
     const int nw = waves == 8 ? 8 : 16;
-    int gx = 256;
+    int gx = 256;   // tests/test_gpu_multitrip.py: MLP_TRIP_TILES = 256 * nw
     if ((long)gx * nw > tiles) gx = (int)((tiles + nw - 1) / nw);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     void (*kern)(const HatMlpDesc, long, long) = out_f32 ? (nw == 8 ? ocab_mlp_kernel<true, 8> : ocab_mlp_kernel<true, 16>)

@@ -345,7 +345,7 @@ template <typename T, int NT, int KS, int WAVES, int MINW, bool RES, int TH = 0>
 int launch_pw_cfg(const HatConvDesc& d, hipStream_t s, size_t lds, int wgs_per_cu, int scale_in_lds) {
     const long npix = (long)d.B * d.H * d.W;
     const int tiles = (int)((npix + 15) / 16);
-    int gx = 256 * wgs_per_cu;
+    int gx = 256 * wgs_per_cu;   // tests/test_gpu_multitrip.py: PW_TRIP_TILES = 256 * wgs_per_cu * WAVES (2048 or 3072)
     if (gx > (tiles + WAVES - 1) / WAVES) gx = (tiles + WAVES - 1) / WAVES;
     auto kern = pw_kernel<T, NT, KS, WAVES, MINW, RES, TH>;
     if (lds > 65536) {
@@ -514,7 +514,7 @@ int launch_tap3(const HatConvDesc& d, hipStream_t s, int32_t* groups_out) {
     const long hw = (long)d.H * d.W;
     const int tiles = (int)((hw + 15) / 16);
     const int wgs_per_cu = (int)(HAT_LDS_MAX / lds) >= 3 ? 3 : 2;
-    int gx = 256 * wgs_per_cu;
+    int gx = 256 * wgs_per_cu;   // tests/test_gpu_multitrip.py: TAP3_WAVES * groups tiles per sample and trip (hat_conv3x3_small_groups)
     if (gx > (tiles + 3) / 4) gx = (tiles + 3) / 4;
     if (groups_out) { *groups_out = gx; return 0; }
     dim3 grid(gx, 1, d.B);
@@ -710,7 +710,7 @@ extern "C" int hat_aggr_cab(const HatAggrCabDesc* dp, void* stream) {
     const size_t lds = (size_t)9 * (5 + 3) * 512 * sizeof(bf16_t) + (size_t)9 * 16 * sizeof(float);
     const long HW = (long)d.H * d.W;
     const int tiles = (int)((HW + 15) / 16);
-    int gx = 512 / (d.B < 2 ? 1 : 2);
+    int gx = 512 / (d.B < 2 ? 1 : 2);   // tests/test_gpu_multitrip.py: AGGR_CAB_TRIP_TILES = gx * 4 waves per sample
     if (gx > (tiles + 3) / 4) gx = (tiles + 3) / 4;
     auto kern = aggr_cab_kernel<bf16_t>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

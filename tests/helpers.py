@@ -1,5 +1,7 @@
 """Shared helpers for the tests: golden loading, oracle nets with synthetic weights, the per-kernel GPU tests' input / tolerance
-helpers, and plain fp64 restatements of the HATX attention options and the SGFN gate that take the kernels' own inputs."""
+helpers, plain fp64 restatements of the HATX attention options and the SGFN gate that take the kernels' own inputs, and the
+builders / references of the multi-trip tests (test_gpu_multitrip.py): device-drawn activations, a banded fp64 convolution,
+the chunked re-run of a pointwise launch."""
 import json
 import os
 
@@ -62,7 +64,9 @@ def to_dev(x_bhwc: torch.Tensor, ld: int, tdt, dev):
 
 
 def check(got: torch.Tensor, ref: torch.Tensor, dtype: str, what: str, f32_tol=2e-5):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
+    got, ref = got.detach().double(), ref.detach().double()
+    if got.device != ref.device:      # (two tensors of one device are judged there: the multi-trip tests' maps are 0.2 Mpx)
+        got, ref = got.cpu(), ref.cpu()
     assert got.shape == ref.shape, (what, got.shape, ref.shape)
     assert torch.isfinite(got).all(), what + ": non-finite output"
     scale = max(float(ref.abs().max()), 1e-6)
@@ -152,3 +156,84 @@ def ref_sgfn_gate(u, wdw, bdw, half: int):
     a = F.conv2d(u[..., :half].permute(0, 3, 1, 2), wdw.double(), bdw.double(), padding=1, groups=half).permute(0, 2, 3, 1)
     g = u[..., half:]
     return torch.cat([a * (g / (1.0 + torch.exp(-g))), g], dim=-1)
+
+
+# ------------------------------------------------------------------------------------------------
+# multi-trip tests (test_gpu_multitrip.py): frames of 0.1 - 0.5 Mpx, so activations are drawn on the device (synth.normal is host
+# numpy in float64) and the references run in fp64 where the operands already are
+# ------------------------------------------------------------------------------------------------
+def dev_randn(key: str, shape, dev, std=1.0, mean=0.0):
+    """fp32 N(mean, std^2) of `shape` drawn on `dev` from a generator seeded by `key` (the same tensor for the same key within a
+    run: the big launch, its chunked re-run and the reference all read one buffer)."""
+    g = torch.Generator(device=dev)
+    g.manual_seed(synth._fnv1a64(key) & 0x7FFFFFFFFFFF)
+    return torch.randn(tuple(shape), generator=g, device=dev) * std + mean
+
+
+def dev_rows(key: str, B: int, N: int, C_: int, ld: int, tdt, dev, std=1.0, mean=0.0):
+    """(B, N, ld) rows of dtype tdt on the device: N(mean, std^2) in the first C_ channels, zero pad channels (to_dev's layout)."""
+    out = torch.zeros(B, N, ld, dtype=tdt, device=dev)
+    out[:, :, :C_] = dev_randn(key, (B, N, C_), dev, std, mean).to(tdt)
+    return out
+
+
+def conv_ref_banded(x: torch.Tensor, w: torch.Tensor, bias=None, band: int = 64):
+    """fp64 'same' convolution (stride 1, zero padding) of a channel-last map, on x's device: x (B, H, W, Cin); w (Cout, Cin, k, k)
+    or per-sample (B, Cout, Cin, k, k); -> (B, H, W, Cout) fp64.  Row bands of `band` rows with a k // 2 halo, one matmul per tap:
+    only a band of the map exists in fp64 next to the result, and no convolution library is involved."""
+    b, h, wd, cin = x.shape
+    k, pad, cout = w.shape[-1], w.shape[-1] // 2, w.shape[-4]
+    w = w.double().to(x.device)
+    out = torch.empty(b, h, wd, cout, dtype=torch.float64, device=x.device)
+    for y0 in range(0, h, band):
+        y1 = min(y0 + band, h)
+        lo, hi = max(y0 - pad, 0), min(y1 + pad, h)
+        xb = F.pad(x[:, lo:hi].double(), (0, 0, pad, pad, pad - (y0 - lo), pad - (hi - y1)))     # (B, rows + 2 pad, W + 2 pad, Cin)
+        acc = torch.zeros(b, (y1 - y0) * wd, cout, dtype=torch.float64, device=x.device)
+        for dy in range(k):
+            for dx in range(k):
+                acc += xb[:, dy:dy + (y1 - y0), dx:dx + wd].reshape(b, -1, cin) @ w[..., dy, dx].transpose(-1, -2)
+        out[:, y0:y1] = acc.reshape(b, y1 - y0, wd, cout)
+    return out if bias is None else out + bias.double().to(x.device)
+
+
+def run_chunked(launch, rows: dict, B: int, N: int, chunk: int):
+    """Re-run a pointwise launch over consecutive chunks of at most `chunk` pixels that never cross a sample: launch(views, b) gets
+    the (1, n, ld) views of every per-pixel tensor in `rows` ((B, N, ld), contiguous) and the sample index, and launches
+    B = 1, H = 1, W = n on them."""
+    for b in range(B):
+        for p0 in range(0, N, chunk):
+            p1 = min(p0 + chunk, N)
+            launch({key: t[b:b + 1, p0:p1] for key, t in rows.items()}, b)
+
+
+def esc_weights_case(ops, dev, dtype: str, pdim: int, ks: int, nblk: int, B: int = 2, N: int = 777):
+    """hat_esc_weights on seeded GAP partials of `nblk` blocks -> (the kernel's weights un-packed to (B, pdim, pdim, ks, ks) on
+    the host, their fp64 restatement, the raw (B, npad, kpad) output pre-filled with 7.0, npad)."""
+    dt = ops.DTYPE_CODE[dtype]
+    tdt = ops.TORCH_DTYPE[dt]
+    npad = 16 if pdim <= 16 else 32   # weight rows per sample and floats per GAP block
+    gap = rnd("gp", (B, nblk, npad), std=1.0)
+    gap[:, :, pdim:] = 0
+    w1, b1 = rnd("w1", (pdim // 2, pdim), std=0.3), rnd("b1", (pdim // 2,), std=0.1)
+    w2, b2 = rnd("w2", (pdim * 9, pdim // 2), std=0.3), rnd("b2", (pdim * 9,), std=0.1)
+    plk = rnd("plk", (pdim, pdim, ks, ks), std=0.05)
+    p = gap.double().sum(1)[:, :pdim] / N
+    h = F.gelu(p @ w1.double().t() + b1.double())
+    dk = (h @ w2.double().t() + b2.double()).reshape(B, pdim, 3, 3)
+    weff = plk.double()[None].repeat(B, 1, 1, 1, 1)
+    c = ks // 2
+    for i in range(pdim):
+        weff[:, i, i, c - 1:c + 2, c - 1:c + 2] += dk[:, i]
+    lk = ops.pack_conv_weight(plk, None, ops.HAT_F32, dev, nt=1)
+    kc = ops.KC[dt] * 3
+    kpad = -(-(ks * ks * _r8(pdim)) // kc) * kc
+    plkp = torch.zeros(npad, kpad, device=dev)
+    plkp[:lk.w.shape[0], :min(kpad, lk.kpad)] = lk.w[:npad, :min(kpad, lk.kpad)]
+    wout = torch.full((B, npad, kpad), 7.0, dtype=tdt, device=dev)
+    ops.esc_weights(gap.to(dev), nblk, N, w1.to(dev), b1.to(dev), w2.to(dev), b2.to(dev), plkp, wout, B=B, pdim=pdim, ksize=ks,
+                    kpad=kpad, dtype=dt)
+    torch.cuda.synchronize()
+    cin_p = _r8(pdim)
+    got = wout.float().cpu()[:, :pdim, :ks * ks * cin_p].reshape(B, pdim, ks, ks, cin_p)[..., :pdim].permute(0, 1, 4, 2, 3)
+    return got, weff, wout, npad

@@ -12,7 +12,7 @@ import torch.nn.functional as F
 
 from oracle import hat_oracle as O
 from super_resolution_amd import synth
-from helpers import _r8, check, q, rnd, to_dev
+from helpers import _r8, check, esc_weights_case, q, rnd, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -357,31 +357,8 @@ def test_esc_weights_and_eca(dtype, pdim, ks):
     dev, ops = _dev(), _ops()
     dt = ops.DTYPE_CODE[dtype]
     tdt = ops.TORCH_DTYPE[dt]
-    B, N, nblk = 2, 777, ops.layernorm_blocks()
-    npad = 16 if pdim <= 16 else 32   # weight rows per sample and floats per GAP block
-    gap = rnd("gp", (B, nblk, npad), std=1.0)
-    gap[:, :, pdim:] = 0
-    w1, b1 = rnd("w1", (pdim // 2, pdim), std=0.3), rnd("b1", (pdim // 2,), std=0.1)
-    w2, b2 = rnd("w2", (pdim * 9, pdim // 2), std=0.3), rnd("b2", (pdim * 9,), std=0.1)
-    plk = rnd("plk", (pdim, pdim, ks, ks), std=0.05)
-    p = gap.double().sum(1)[:, :pdim] / N
-    h = F.gelu(p @ w1.double().t() + b1.double())
-    dk = (h @ w2.double().t() + b2.double()).reshape(B, pdim, 3, 3)
-    weff = plk.double()[None].repeat(B, 1, 1, 1, 1)
-    c = ks // 2
-    for i in range(pdim):
-        weff[:, i, i, c - 1:c + 2, c - 1:c + 2] += dk[:, i]
-    lk = ops.pack_conv_weight(plk, None, ops.HAT_F32, dev, nt=1)
-    kc = ops.KC[dt] * 3
-    kpad = -(-(ks * ks * _r8(pdim)) // kc) * kc
-    plkp = torch.zeros(npad, kpad, device=dev)
-    plkp[:lk.w.shape[0], :min(kpad, lk.kpad)] = lk.w[:npad, :min(kpad, lk.kpad)]
-    wout = torch.full((B, npad, kpad), 7.0, dtype=tdt, device=dev)
-    ops.esc_weights(gap.to(dev), nblk, N, w1.to(dev), b1.to(dev), w2.to(dev), b2.to(dev), plkp, wout, B=B, pdim=pdim, ksize=ks,
-                    kpad=kpad, dtype=dt)
-    torch.cuda.synchronize()
-    cin_p = _r8(pdim)
-    got = wout.float().cpu()[:, :pdim, :ks * ks * cin_p].reshape(B, pdim, ks, ks, cin_p)[..., :pdim].permute(0, 1, 4, 2, 3)
+    B, N = 2, 777
+    got, weff, wout, npad = esc_weights_case(ops, dev, dtype, pdim, ks, ops.layernorm_blocks(), B=B, N=N)
     check(got, weff, dtype, "esc weights", f32_tol=1e-5)
     assert float(wout[:, pdim:].float().abs().max()) == 0.0 if pdim < npad else True
     # ECA
@@ -654,7 +631,9 @@ def test_aggr_with_folded_cab(geom):
 def test_esc_conv13_resident(geom):
     """hat_esc_conv13 (the ESC large-kernel conv with all weights and the haloed tile resident in LDS, esc_arch.py:121-123)
     against conv2d in fp64 with per-sample weights in hat_esc_weights' [B][16][Kpad] layout, and against hat_conv (ksize 13),
-    the path it replaces: several tiles per workgroup, frames smaller than a tile, ragged edges, B = 2."""
+    the path it replaces: frames smaller than a tile, ragged edges, B = 2.  Every case here is ONE 32 x 32 tile per workgroup
+    (the grid is capped at the tile count: at most 6 tiles); a workgroup that walks several tiles, with the next tile's fetch
+    under the K loop, is test_gpu_multitrip.py::test_esc_conv13_multitrip."""
     B, H, W = geom
     dev, ops = _dev(), _ops()
     dt = ops.DTYPE_CODE["bf16"]
