@@ -747,6 +747,47 @@ int hat_abi_version(void);
 /* name of the architecture the code objects in this library were compiled for ("gfx950") */
 const char* hat_target_arch(void);
 
+/*
+ * NIQE on the device (basicsr metrics/niqe.py calculate_niqe, convert_to 'y'): the no-reference score of GT-less test sets.
+ * The device delivers, per 96 x 96 block and scale, the 25 sums the AGGD fits need; the fits, the mean / covariance over the
+ * blocks and the 36 x 36 pseudo-inverse are tiny and stay with the caller in fp64 (super_resolution_amd/niqe.py:
+ * features_from_stats, score).  The reference runs in float32 and the kernels follow it step by step (niqe.py's docstring).
+ *
+ * hat_niqe_workspace_bytes  a pure host query: H96, W96 = the size of the plane after crop_border pixels come off every side
+ *     and the rest is cropped to whole 96 x 96 blocks; bytes = room for the four fp32 buffers of one score: the plane and its
+ *     / 255 copy (B,H96,W96 each), the resize intermediate (B,H96/2,W96) and the half-size plane (B,H96/2,W96/2).
+ * hat_niqe_y_u8  src: (B,h,w,3) uint8 with pitch >= 3 w bytes per row and bstride bytes per sample (ignored for B == 1), as
+ *     hat_u8_metrics takes them; bgr: the bytes are B, G, R.  plane (B,H96,W96) fp32 = the BT.601 Y value hat_u8_metrics
+ *     forms under HAT_METRICS_Y, ROUNDED half to even (niqe.py:195).  unit: null, or (B,H96,W96) fp32 = float32(plane) / 255,
+ *     correctly rounded: what the half-size resize reads.
+ * hat_imresize_plane_rows / hat_imresize_plane_cols  the two passes of hat_imresize_* for ONE fp32 plane per sample:
+ *     src (B,h,w) -> mid (B,oh,w) -> dst (B,oh,ow), tables as resize.weights_indices makes them, every product and sum
+ *     rounded to fp32 on its own, k ascending; dst = the resized value * out_scale (one more fp32 rounding; 1 changes
+ *     nothing).  NIQE's second scale is rows(unit), cols(out_scale = 255).
+ * hat_niqe_block_stats  plane: (B,h,w) fp32, h and w multiples of block (96, or 48 for the second scale).  window: 49
+ *     doubles in HOST memory, the 7 x 7 Gaussian (niqe.gaussian_window()), read before the call returns.  stats:
+ *     (B, h / block, w / block, 25) doubles in device memory; entry 5 m + q: map m = n, n roll(n,(0,1)), n roll(n,(1,0)),
+ *     n roll(n,(1,1)), n roll(n,(1,-1)) with the roll wrapping inside the block; q = count of negative values, count of positive
+ *     values, sum of squares over the negative, over the positive values (each square an fp32), sum of absolute values.
+ *     n = (img - mu) / (sigma + 1), mu = conv7x7(img), sigma = sqrt(|conv7x7(img^2) - mu^2|), borders `nearest` at the IMAGE
+ *     edge: the 49 taps accumulate in fp64 in raster order, mu and conv(img^2) are rounded to fp32, the rest is fp32; the
+ *     sums are fp64.  One workgroup per block, the block resident in LDS; no intermediate plane is written; no atomics, so
+ *     the sums are reproducible bit for bit.
+ * All return HAT_EINVAL, before anything touches the device, for null pointers (unit excepted), B, h or w < 1, B > 65535, a
+ * negative crop_border, fewer than 96 rows or columns after cropping, a pitch below 3 w or overlapping samples, a table length
+ * that is not out_len * P, a block other than 96 or 48, h or w that is no multiple of block, and more than 65535 rows of
+ * blocks / output rows (the grid).  None allocates or synchronises.
+ */
+int hat_niqe_workspace_bytes(int32_t B, int32_t h, int32_t w, int32_t crop_border, int32_t* H96, int32_t* W96, int64_t* bytes);
+int hat_niqe_y_u8(const uint8_t* src, int64_t pitch, int64_t bstride, int32_t B, int32_t h, int32_t w, int32_t crop_border, int32_t bgr,
+                  float* plane, float* unit, void* stream);
+int hat_imresize_plane_rows(const float* src, float* mid, int32_t B, int32_t h, int32_t w, int32_t oh, const float* w_h,
+                            const int32_t* src_h, int32_t P_h, int64_t n_table, void* stream);
+int hat_imresize_plane_cols(const float* mid, int32_t B, int32_t oh, int32_t w, int32_t ow, const float* w_w, const int32_t* src_w,
+                            int32_t P_w, int64_t n_table, float out_scale, float* dst, void* stream);
+int hat_niqe_block_stats(const float* plane, int32_t B, int32_t h, int32_t w, int32_t block, const double* window, double* stats,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

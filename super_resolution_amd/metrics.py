@@ -82,11 +82,22 @@ def calculate_ssim(img, img2, crop_border, test_y_channel=False, **_):
     return float(np.mean([_ssim(a[..., i], b[..., i]) for i in range(a.shape[2])]))
 
 
-METRICS = {"calculate_psnr": calculate_psnr, "calculate_ssim": calculate_ssim}
+def calculate_niqe(img, crop_border, input_order="HWC", convert_to="y", **kw):
+    """basicsr.metrics.calculate_niqe for RGB arrays: niqe.calculate_niqe (imported on use: niqe.py imports this module)."""
+    from .niqe import calculate_niqe as fn
+    return fn(img, crop_border, input_order=input_order, convert_to=convert_to, **kw)
+
+
+METRICS = {"calculate_psnr": calculate_psnr, "calculate_ssim": calculate_ssim, "calculate_niqe": calculate_niqe}
+NO_REFERENCE = ("calculate_niqe",)   # the types that score `img` alone
 
 
 def calculate_metric(data: dict, opt: dict) -> float:
-    """basicsr.metrics.calculate_metric: opt = {type: calculate_psnr|calculate_ssim, crop_border, test_y_channel}."""
+    """basicsr.metrics.calculate_metric: opt = {type: calculate_psnr|calculate_ssim, crop_border, test_y_channel} or
+    {type: calculate_niqe, crop_border[, input_order, convert_to, pris_params]}, which needs no data['img2']."""
     opt = dict(opt)
-    fn = METRICS[opt.pop("type")]
+    kind = opt.pop("type")
+    fn = METRICS[kind]
+    if kind in NO_REFERENCE:
+        return fn(data["img"], **opt)
     return fn(data["img"], data["img2"], **opt)

@@ -1,6 +1,8 @@
 """PSNR / SSIM of 8-bit frames that are already on the device (`val.metrics_on_device`): hat_u8_metrics delivers the sum of
 squared differences and the per-channel SSIM-map sums, `finalize` turns them into the numbers `metrics.calculate_psnr` /
 `metrics.calculate_ssim` return for the same uint8 arrays.  Only the sums (32 bytes per sample) come back to the host.
+NIQE (`calculate_niqe`, which needs no second frame): ops.niqe_stats delivers 25 sums per block and scale (2 x nblocks x 200
+bytes per sample), niqe.features_from_stats / niqe.score finish on the host in fp64.
 """
 from __future__ import annotations
 
@@ -9,7 +11,8 @@ import torch
 
 from . import ops
 
-DEVICE_METRICS = ("calculate_psnr", "calculate_ssim")   # the `type`s computed here; any other stays with metrics.calculate_metric
+DEVICE_METRICS = ("calculate_psnr", "calculate_ssim", "calculate_niqe")   # the `type`s computed here; any other stays with metrics.calculate_metric
+PAIRED_METRICS = ("calculate_psnr", "calculate_ssim")                      # those of them that need the second frame
 
 _buffers = {}   # (device, B, h, w, crop_border, y_channel, psnr, ssim) -> (sums, workspace)
 
@@ -35,21 +38,52 @@ def _buffers_for(dev, B, h, w, crop_border, y_channel, bgr, psnr, ssim):
     return buf
 
 
-def calculate_metrics_u8(a: torch.Tensor, b: torch.Tensor, metrics_opt: dict, *, bgr: bool = False) -> dict:
+def calculate_niqe_u8(a: torch.Tensor, opt: dict, *, bgr: bool = False):
+    """a: (h,w,3) or (B,h,w,3) uint8 device tensor; opt: one metric entry of type calculate_niqe ({crop_border[, input_order,
+    convert_to, pris_params]}) -> metrics.calculate_niqe of the same uint8 array (a float; a list for B > 1).  Only the block
+    sums are downloaded."""
+    from . import niqe
+    if opt.get("input_order", "HWC") != "HWC":
+        raise RuntimeError(f"calculate_niqe on the device scores (h,w,3) frames: input_order {opt['input_order']!r} is not 'HWC'")
+    convert_to = opt.get("convert_to", "y")
+    if convert_to == "gray":
+        raise NotImplementedError("calculate_niqe: convert_to 'gray' is cv2.cvtColor's BGR2GRAY in the reference, whose float "
+                                  "arithmetic cannot be pinned without OpenCV; use convert_to 'y'")
+    if convert_to != "y":
+        raise ValueError(f"calculate_niqe: convert_to is 'y' (or 'gray', unsupported), got {convert_to!r}")
+    pris = niqe.pris_params(opt.get("pris_params"))   # before any launch: a missing model is an error of the configuration
+    with torch.cuda.device(a.device):
+        s96, s48 = ops.niqe_stats(a, crop_border=int(opt["crop_border"]), bgr=bgr)
+    h96, h48 = s96.cpu().numpy(), s48.cpu().numpy()
+    vals = [niqe.score(niqe.features_from_stats(h96[i], niqe.BLOCK), niqe.features_from_stats(h48[i], niqe.BLOCK // 2), pris)
+            for i in range(h96.shape[0])]
+    return vals[0] if len(vals) == 1 else vals
+
+
+def calculate_metrics_u8(a: torch.Tensor, b, metrics_opt: dict, *, bgr: bool = False, niqe: bool = False) -> dict:
     """a, b: (h,w,3) or (B,h,w,3) uint8 device tensors; metrics_opt: the YAML's `val.metrics` ({name: {type, crop_border,
     test_y_channel}}).  Returns {name: value} for every entry of type calculate_psnr / calculate_ssim (a float; a list of
     floats, one per sample, for B > 1); entries of another type are left out.  Entries that share (crop_border,
-    test_y_channel) are one launch.  The sums and the kernel's workspace are kept per shape, so a repeated shape allocates
-    nothing on the device."""
+    test_y_channel) are one launch.  niqe=True (HATModel passes it) also scores the entries of type calculate_niqe, each on
+    `a` alone (calculate_niqe_u8); b may then be None when there is no PSNR / SSIM entry.  Without it they are left out like any
+    other type, as before NIQE existed here.  The sums and the kernels' workspaces are kept per shape, so a repeated shape
+    allocates nothing on the device."""
+    paired = any(m.get("type") in PAIRED_METRICS for m in (metrics_opt or {}).values())
+    if b is None:
+        if paired:
+            raise RuntimeError("calculate_metrics_u8: PSNR / SSIM entries need the second frame")
+        b = a
     if tuple(a.shape) != tuple(b.shape):
         raise AssertionError(f"Image shapes are different: {tuple(a.shape)}, {tuple(b.shape)}.")
     a4, b4 = (a, b) if a.dim() == 4 else (a.unsqueeze(0), b.unsqueeze(0))
     B, h, w, _ = a4.shape
     groups = {}
-    for name, mopt in (metrics_opt or {}).items():
-        if mopt.get("type") in DEVICE_METRICS:
-            groups.setdefault((int(mopt["crop_border"]), bool(mopt.get("test_y_channel", False))), []).append((name, mopt["type"]))
     out = {}
+    for name, mopt in (metrics_opt or {}).items():
+        if mopt.get("type") in PAIRED_METRICS:
+            groups.setdefault((int(mopt["crop_border"]), bool(mopt.get("test_y_channel", False))), []).append((name, mopt["type"]))
+        elif niqe and mopt.get("type") == "calculate_niqe":
+            out[name] = calculate_niqe_u8(a4, mopt, bgr=bgr)
     for (crop, y), entries in groups.items():
         psnr = any(t == "calculate_psnr" for _, t in entries)
         ssim = any(t == "calculate_ssim" for _, t in entries)

@@ -196,8 +196,10 @@ class HATModel:
 
     def _test_metrics_on_device(self, val_data, metrics, save_img):
         """`val.metrics_on_device`: test_u8 leaves its result on the device, the ground truth goes up as uint8 and the metrics
-        of type calculate_psnr / calculate_ssim come from hat_u8_metrics (metrics_device.calculate_metrics_u8).  The result is
-        downloaded only when it is saved or a metric of another type needs it; that metric is computed on the host as ever.
+        of type calculate_psnr / calculate_ssim come from hat_u8_metrics, those of type calculate_niqe from the NIQE block sums
+        (metrics_device.calculate_metrics_u8).  A dataset without `gt` is scored when every entry is NIQE, which needs none.
+        The result is downloaded only when it is saved or a metric of another type needs it; that metric is computed on the
+        host as ever.
         Returns (data for the host side: 'img' / 'img2' where they exist there, {name: value} of the device metrics)."""
         from ..metrics_device import DEVICE_METRICS, calculate_metrics_u8
         out = self.test_u8(val_data["lq"], on_device=True)
@@ -205,7 +207,9 @@ class HATModel:
         scored = {}
         if metrics and has_gt:
             gt = self._u8_frame(val_data["gt"], "val.metrics_on_device", "ground-truth")[0]
-            scored = calculate_metrics_u8(out, gt, metrics)
+            scored = calculate_metrics_u8(out, gt, metrics, niqe=True)
+        elif self._no_reference(metrics):
+            scored = calculate_metrics_u8(out, None, metrics, niqe=True)
         host_metrics = bool(metrics) and has_gt and any(m.get("type") not in DEVICE_METRICS for m in metrics.values())
         data = {}
         if save_img or host_metrics:
@@ -250,7 +254,7 @@ class HATModel:
         gt = self._u8_frame(val_data["gt"], "val.lq_on_device", "ground-truth")
         out = self.test_gt_u8(gt)
         gtc = gt[0, :out.shape[0], :out.shape[1]]
-        scored = calculate_metrics_u8(out, gtc, metrics) if (metrics and on_device_metrics) else {}
+        scored = calculate_metrics_u8(out, gtc, metrics, niqe=True) if (metrics and on_device_metrics) else {}
         host_metrics = bool(metrics) and any(m.get("type") not in DEVICE_METRICS or not on_device_metrics for m in metrics.values())
         data = {}
         if save_img or host_metrics:
@@ -258,6 +262,12 @@ class HATModel:
         if host_metrics:
             data["img2"] = gtc.cpu().numpy()
         return data, scored
+
+    @staticmethod
+    def _no_reference(metrics) -> bool:
+        """Every entry scores the result alone (NIQE): such a set of metrics runs on a dataset without `gt`."""
+        from ..metrics import NO_REFERENCE
+        return bool(metrics) and all(m.get("type") in NO_REFERENCE for m in metrics.values())
 
     @staticmethod
     def _items(dataset, lq_on_device: bool):
@@ -301,7 +311,7 @@ class HATModel:
                 root = (self.opt.get("path") or {}).get("visualization") or osp.join("results", self.opt["name"], "visualization")
                 write_image(sr_img, osp.join(root, dataset_name, f"{img_name}_{suffix}.png"))
             row = {"name": img_name}
-            if metrics and ("img2" in data or device_metrics):
+            if metrics and ("img2" in data or device_metrics or self._no_reference(metrics)):
                 for name, mopt in metrics.items():
                     v = device_metrics[name] if name in device_metrics else calculate_metric(data, mopt)
                     self.metric_results[name] += v

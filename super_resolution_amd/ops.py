@@ -620,6 +620,82 @@ def u8_metrics(a, b, sums, workspace, *, crop_border: int, y_channel: bool, bgr:
         tag=f"u8 metrics {h}x{w} crop {crop_border}{' psnr' if psnr else ''}{' ssim' if ssim else ''}", nbytes=2.0 * B * h * w * 3)
 
 
+# ---- NIQE block sums (definition: niqe.py; kernels: csrc/hat_niqe.hip) ----
+_niqe_buffers = {}   # (device, B, h, w, crop_border) -> the workspace's four views, the two stats tensors, the window
+
+
+def niqe_workspace(B: int, h: int, w: int, *, crop_border: int):
+    """(H96, W96, bytes) of hat_niqe_workspace_bytes for (B,h,w,3) frames; raises for sizes it refuses (a pure host query)."""
+    lib = _lib.load()
+    H, W, n = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    _lib.check(lib.hat_niqe_workspace_bytes(B, h, w, crop_border, C.byref(H), C.byref(W), C.byref(n)), "hat_niqe_workspace_bytes")
+    return H.value, W.value, n.value
+
+
+def _niqe_buffers_for(dev, B, h, w, crop_border):
+    import numpy as np
+
+    from . import niqe as _nq
+    key = (str(dev), B, h, w, crop_border)
+    buf = _niqe_buffers.get(key)
+    if buf is None:
+        H, W, nbytes = niqe_workspace(B, h, w, crop_border=crop_border)
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        px, views, o = B * H * W, [], 0
+        for shape in ((B, H, W), (B, H, W), (B, H // 2, W), (B, H // 2, W // 2)):
+            n = shape[0] * shape[1] * shape[2]
+            views.append(ws[o:o + n].view(shape))
+            o += n
+        assert o * 4 == nbytes and px == views[0].numel()
+        win = np.ascontiguousarray(_nq.gaussian_window(), dtype=np.float64)
+        buf = _niqe_buffers[key] = {"plane": views[0], "unit": views[1], "mid": views[2], "half": views[3], "window": win,
+                                    "stats96": torch.zeros(B, H // 96, W // 96, 25, dtype=torch.float64, device=dev),
+                                    "stats48": torch.zeros(B, H // 96, W // 96, 25, dtype=torch.float64, device=dev)}
+    return buf
+
+
+def niqe_stats(frame_u8, *, crop_border: int, bgr: bool = False):
+    """frame_u8: (h,w,3) or (B,h,w,3) uint8 device frames (rows may be pitched) -> (stats96, stats48): (B, H96 / 96, W96 / 96, 25)
+    float64 device tensors, niqe.stats_of(niqe.y_plane(frame, crop_border), acc=float64) per sample.  Five launches (Y, the two
+    resize passes, the two block kernels); the buffers are kept per shape and the tensors returned are those buffers: the next
+    call of the same shape overwrites them."""
+    lib = _lib.load()
+    f = frame_u8
+    if not isinstance(f, torch.Tensor) or not f.is_cuda:
+        raise RuntimeError("niqe_stats needs a uint8 device tensor (no CPU path exists: niqe.stats_of is the host definition)")
+    if f.dim() == 3:
+        f = f.unsqueeze(0)
+    if f.dim() != 4 or f.shape[3] != 3 or f.dtype != torch.uint8 or f.stride(3) != 1 or f.stride(2) != 3:
+        raise RuntimeError(f"niqe_stats needs (B,h,w,3) uint8 frames with interleaved pixels, got {tuple(frame_u8.shape)} {frame_u8.dtype}")
+    B, h, w, _ = f.shape
+    crop_border = int(crop_border)
+    dev = f.device
+    buf = _niqe_buffers_for(dev, B, h, w, crop_border)
+    plane, unit, mid, half = buf["plane"], buf["unit"], buf["mid"], buf["half"]
+    H, W = plane.shape[1], plane.shape[2]
+    th, tw = _resize_axis(dev, H, 0.5, True), _resize_axis(dev, W, 0.5, True)
+    if th["out"] != H // 2 or tw["out"] != W // 2:
+        raise RuntimeError(f"niqe_stats: the half size of {H}x{W} came out as {th['out']}x{tw['out']}")
+    win = buf["window"].ctypes.data_as(C.POINTER(C.c_double))
+    st = _stream()
+    _timed("niqe_y_kernel", 0.0, lambda: _lib.check(
+        lib.hat_niqe_y_u8(f.data_ptr(), f.stride(1), f.stride(0), B, h, w, crop_border, int(bgr), _ptr(plane), _ptr(unit), st), "hat_niqe_y_u8"),
+        tag=f"niqe Y {h}x{w} crop {crop_border} -> {H}x{W}", nbytes=B * (3.0 * H * W + 8.0 * H * W))
+    _timed("plane_rows_kernel", 2.0 * B * (H // 2) * W * th["P"], lambda: _lib.check(
+        lib.hat_imresize_plane_rows(_ptr(unit), _ptr(mid), B, H, W, H // 2, _ptr(th["w"]), _ptr(th["src"]), th["P"], th["w"].numel(), st),
+        "hat_imresize_plane_rows"), tag=f"niqe half rows {H}x{W}", nbytes=B * 4.0 * (H * W + H // 2 * W))
+    _timed("plane_cols_kernel", 2.0 * B * (H // 2) * (W // 2) * tw["P"], lambda: _lib.check(
+        lib.hat_imresize_plane_cols(_ptr(mid), B, H // 2, W, W // 2, _ptr(tw["w"]), _ptr(tw["src"]), tw["P"], tw["w"].numel(), 255.0,
+                                    _ptr(half), st), "hat_imresize_plane_cols"),
+        tag=f"niqe half cols {H // 2}x{W}", nbytes=B * 4.0 * (H // 2 * W + H // 2 * (W // 2)))
+    for src, block, out in ((plane, 96, buf["stats96"]), (half, 48, buf["stats48"])):
+        hh, ww = src.shape[1], src.shape[2]
+        _timed(f"niqe_block_kernel<{block}>", 4.0 * 49 * 2 * B * hh * ww, lambda: _lib.check(
+            lib.hat_niqe_block_stats(_ptr(src), B, hh, ww, block, win, _ptr(out), st), "hat_niqe_block_stats"),
+            tag=f"niqe blocks {block} {hh}x{ww}", nbytes=B * (4.0 * hh * ww + 200.0 * (hh // block) * (ww // block)))
+    return buf["stats96"], buf["stats48"]
+
+
 def cab_squeeze_units(H: int, W: int) -> int:
     lib = _lib.load()
     rows, units = C.c_int32(0), C.c_int32(0)
