@@ -94,6 +94,13 @@ class HatAggrCabDesc(C.Structure):
     _fields_ = [("lin", HatConvDesc), ("c1", C.c_void_p), ("wf", C.c_void_p), ("bias_b", C.c_void_p)]
 
 
+class HatYuvSurface(C.Structure):
+    """Mirror of `HatYuvSurface` (include/hat_mi355x.h): one frame surface of any subsampling; bytes everywhere, cb = cr = None: grey."""
+    _fields_ = [("y", C.c_void_p), ("y_pitch", C.c_int64), ("y_bstride", C.c_int64), ("cb", C.c_void_p), ("cr", C.c_void_p),
+                ("c_pitch", C.c_int64), ("c_step", C.c_int32), ("c_bstride", C.c_int64),
+                ("sub_x", C.c_int32), ("sub_y", C.c_int32), ("depth", C.c_int32), ("msb", C.c_int32)]
+
+
 _YUV_BLOCK = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]   # a 4:2:0 frame block
 
 # name -> (restype, argtypes); every symbol declared in include/hat_mi355x.h
@@ -172,6 +179,14 @@ SIGNATURES = {
                                                                                                          C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "hat_plan_forward_yuv420_deep": (C.c_int, [C.c_void_p] + _YUV_BLOCK + [C.c_int32] * 4 + _YUV_BLOCK + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                                                                      C.c_void_p]),
+    # any subsampling: one HatYuvSurface per side
+    "hat_yuv_to_planes": (C.c_int, [C.POINTER(HatYuvSurface), C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
+    "hat_planes_to_yuv": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HatYuvSurface), C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_void_p]),
+    "hat_conv3x3_to_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HatYuvSurface)] + [C.c_int32] * 7 + [C.c_float, C.c_void_p,
+                                                                                                        C.c_void_p, C.c_int32, C.c_void_p]),
+    "hat_plan_forward_yuv": (C.c_int, [C.c_void_p, C.POINTER(HatYuvSurface), C.POINTER(HatYuvSurface), C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
     "hat_imresize_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     "hat_imresize_cols_to_planes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,

@@ -446,6 +446,35 @@ class HAT(nn.Module):
             return self.engine(frame.device).forward_yuv420(frame, fmt=fmt, to_rgb=to_rgb, from_rgb=from_rgb, out=out, depth=depth,
                                                             out_depth=out_depth, msb=msb, ensemble=ensemble)
 
+    def forward_yuv(self, frame, *, fmt: str, out_fmt=None, matrix: str = "bt601", full_range: bool = False, depth: int = 8, out_depth=None,
+                    msb=None, out_msb=None, out=None, ensemble: int = 1):
+        """YCbCr frames of any chroma subsampling in, any out, all on the device: `frame` is a (rows, w) or (B, rows, w) uint8
+        (uint16 with depth 10 / 12 / 16) device tensor in the standard contiguous layout of `fmt`, one of yuv.ALL_FORMATS —
+        'nv12' 'nv21' 'i420' (4:2:0), 'i422' 'nv16' (4:2:2), 'i444' 'nv24' (4:4:4), 'gray' — and the result is the s-times larger
+        frame in the layout `out_fmt` (default: fmt): nv12 -> i444 keeps all of the network's chroma, i444 -> gray keeps none,
+        gray -> i420 writes neutral-born chroma.  w is even where the layout subsamples horizontally and h where vertically;
+        every other size >= 1 whose reflect-padding to the next window multiple is defined is a frame.  Equal, bit for bit, to
+        yuv.yuv_to_planes -> reflect-pad -> this build's `forward` -> crop -> yuv.planes_to_yuv.  depth / out_depth, matrix,
+        full_range, out, ensemble: as forward_yuv420; msb / out_msb: the word alignment of each deep side (default: by the layout).
+        forward_yuv420 is this call with out_fmt = fmt for the three 4:2:0 layouts."""
+        if not isinstance(frame, torch.Tensor):
+            raise TypeError(f"forward_yuv needs a uint8 device tensor, got {type(frame).__name__}")
+        if frame.dtype not in (torch.uint8, torch.uint16):
+            raise TypeError(f"forward_yuv needs a uint8 tensor (uint16 with depth 10, 12 or 16), got {frame.dtype}")
+        self._check_u8_input(frame)
+        from .. import yuv
+        yuv.check_layout(fmt)
+        yuv.check_layout(fmt if out_fmt is None else out_fmt)
+        out_depth = depth if out_depth is None else out_depth
+        to_rgb, from_rgb = yuv.csc(matrix, full_range, depth)[0], yuv.csc(matrix, full_range, out_depth)[1]
+        if frame.dtype != (torch.uint8 if depth == 8 else torch.uint16):
+            raise TypeError(f"forward_yuv: depth={depth} needs a {'uint8' if depth == 8 else 'uint16'} tensor, got {frame.dtype}")
+        if frame.dim() == 2:
+            frame = frame.unsqueeze(0)
+        with torch.no_grad():
+            return self.engine(frame.device).forward_yuv(frame, fmt=fmt, out_fmt=out_fmt, to_rgb=to_rgb, from_rgb=from_rgb, out=out,
+                                                         depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, ensemble=ensemble)
+
     # ---- exact full-frame sharding into row bands (SURVEY §8 f4; no counterpart in the reference, whose tile loop
     # hat_model.py:40-108 gives a DIFFERENT result than the full frame: SURVEY F6) ----
     def _check_band_input(self, x):

@@ -29,15 +29,27 @@ namespace {
 // Epi = SweepEpiYUV (with NCHW): that same fp32 value converted to 4:2:0 YCbCr (hat_rgb_to_ycc): a Y byte per pixel into outv,
 // a Cb and a Cr byte per 2 x 2 block into cb / cr.  The bands of this instantiation start on even rows.
 // Epi = SweepEpiYUV16 (with NCHW): SweepEpiYUV with 16-bit words for bytes: the n-bit code hat_ycc_code(., scale, maxcode) << shift.
+// Both carry the chroma subsampling of the destination as template parameters (SX, SY; GREY: no chroma): (1,1) is 4:2:0 as
+// described; (1,0) 4:2:2 stores chroma on every row from the even column's lane (the same row_shl:1 move, no carry between
+// rows); (0,0) 4:4:4 stores per lane with no move; GREY stores Y only.  Only (1,1) needs bands that start on even rows.
 struct SweepEpi { float out_scale; float mean[4]; int nst; };
 struct SweepEpiU8 { float out_scale; float mean[4]; int h_out, w_out, bgr; long long pitch, bstride; };
-struct SweepEpiYUV {
+template <int SX, int SY, bool GREY> struct SweepEpiYUVT {
     float out_scale; float mean[4]; int h_out, w_out, c_step; long long pitch, bstride, c_pitch, c_bstride;
     uint8_t* cb; uint8_t* cr; HatCsc k;
 };
-struct SweepEpiYUV16 {   // pitches, strides and c_step in bytes, as everywhere
+template <int SX, int SY, bool GREY> struct SweepEpiYUV16T {   // pitches, strides and c_step in bytes, as everywhere
     float out_scale; float mean[4]; int h_out, w_out, c_step; long long pitch, bstride, c_pitch, c_bstride;
     uint8_t* cb; uint8_t* cr; HatCsc k; int shift; float scale, maxcode;
+};
+using SweepEpiYUV = SweepEpiYUVT<1, 1, false>;
+using SweepEpiYUV16 = SweepEpiYUV16T<1, 1, false>;
+template <typename E> struct SweepYuvTraits { static constexpr bool yuv = false, deep = false, grey = false; static constexpr int sx = 1, sy = 1; };
+template <int SX, int SY, bool G> struct SweepYuvTraits<SweepEpiYUVT<SX, SY, G>> {
+    static constexpr bool yuv = true, deep = false, grey = G; static constexpr int sx = SX, sy = SY;
+};
+template <int SX, int SY, bool G> struct SweepYuvTraits<SweepEpiYUV16T<SX, SY, G>> {
+    static constexpr bool yuv = true, deep = true, grey = G; static constexpr int sx = SX, sy = SY;
 };
 
 template <int KS, bool NCHW, typename Epi = SweepEpi>
@@ -46,8 +58,10 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
                                                              float* __restrict__ colsum, int H, int W, int C, int ldx,
                                                              int rows, int strips, int units, Epi epi) {
     constexpr bool U8 = std::is_same<Epi, SweepEpiU8>::value;
-    constexpr bool YUV16 = std::is_same<Epi, SweepEpiYUV16>::value;
-    constexpr bool YUV = std::is_same<Epi, SweepEpiYUV>::value || YUV16;
+    using YT = SweepYuvTraits<Epi>;
+    constexpr bool YUV16 = YT::deep, YUV = YT::yuv;
+    constexpr bool C420 = YUV && !YT::grey && YT::sx == 1 && YT::sy == 1, C422 = YUV && !YT::grey && YT::sx == 1 && YT::sy == 0;
+    constexpr bool C444 = YUV && !YT::grey && YT::sx == 0;
     static_assert((!U8 && !YUV) || NCHW, "the byte epilogues convert the conv_last value");
     using M = MT<bf16_t>;
     using frag_t = M::frag_t;
@@ -143,28 +157,58 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
             float Yv, cbv, crv;
             hat_rgb_to_ycc(epi.k, vb[0] * epi.out_scale + epi.mean[0], vb[1] * epi.out_scale + epi.mean[1], vb[2] * epi.out_scale + epi.mean[2],
                            Yv, cbv, crv);
-            const float cbn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cbv), 0x101, 0xf, 0xf, false));
-            const float crn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, crv), 0x101, 0xf, 0xf, false));
-            const float cbs = hat_add_rn(cbv, cbn), crs = hat_add_rn(crv, crn);
+            [[maybe_unused]] float cbs = cbv, crs = crv;
+            if constexpr (C420 || C422) {
+                const float cbn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cbv), 0x101, 0xf, 0xf, false));
+                const float crn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, crv), 0x101, 0xf, 0xf, false));
+                cbs = hat_add_rn(cbv, cbn);
+                crs = hat_add_rn(crv, crn);
+            }
             if (y >= y0 && y < y1 && g == 0 && oin && y < epi.h_out && xx < epi.w_out) {
                 if constexpr (YUV16) {
                     // the same lanes, 16-bit stores: a 28-byte Y span per strip and row, 7 + 7 chroma words on odd rows
                     *reinterpret_cast<uint16_t*>(o8 + (size_t)y * epi.pitch + 2 * (size_t)xx) = (uint16_t)(hat_ycc_code(Yv, epi.scale, epi.maxcode) << epi.shift);
-                    if ((y & 1) && !(xx & 1)) {
-                        const size_t co = (size_t)b * epi.c_bstride + (size_t)(y >> 1) * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
-                        *reinterpret_cast<uint16_t*>(epi.cb + co) = (uint16_t)(hat_ycc_code(hat_chroma_value(ctop_b, cbs, epi.k.m[7]), epi.scale, epi.maxcode) << epi.shift);
-                        *reinterpret_cast<uint16_t*>(epi.cr + co) = (uint16_t)(hat_ycc_code(hat_chroma_value(ctop_r, crs, epi.k.m[11]), epi.scale, epi.maxcode) << epi.shift);
+                    if constexpr (C420) {
+                        if ((y & 1) && !(xx & 1)) {
+                            const size_t co = (size_t)b * epi.c_bstride + (size_t)(y >> 1) * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
+                            *reinterpret_cast<uint16_t*>(epi.cb + co) = (uint16_t)(hat_ycc_code(hat_chroma_value(ctop_b, cbs, epi.k.m[7]), epi.scale, epi.maxcode) << epi.shift);
+                            *reinterpret_cast<uint16_t*>(epi.cr + co) = (uint16_t)(hat_ycc_code(hat_chroma_value(ctop_r, crs, epi.k.m[11]), epi.scale, epi.maxcode) << epi.shift);
+                        }
+                    } else if constexpr (C422) {   // every row, the lane of the even column: 7 + 7 chroma words per strip and row
+                        if (!(xx & 1)) {
+                            const size_t co = (size_t)b * epi.c_bstride + (size_t)y * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
+                            *reinterpret_cast<uint16_t*>(epi.cb + co) = (uint16_t)(hat_ycc_code(hat_chroma_value_h(cbs, epi.k.m[7]), epi.scale, epi.maxcode) << epi.shift);
+                            *reinterpret_cast<uint16_t*>(epi.cr + co) = (uint16_t)(hat_ycc_code(hat_chroma_value_h(crs, epi.k.m[11]), epi.scale, epi.maxcode) << epi.shift);
+                        }
+                    } else if constexpr (C444) {   // every lane: 14 + 14 chroma words per strip and row
+                        const size_t co = (size_t)b * epi.c_bstride + (size_t)y * epi.c_pitch + (size_t)xx * epi.c_step;
+                        *reinterpret_cast<uint16_t*>(epi.cb + co) = (uint16_t)(hat_ycc_code(hat_add_rn(cbv, epi.k.m[7]), epi.scale, epi.maxcode) << epi.shift);
+                        *reinterpret_cast<uint16_t*>(epi.cr + co) = (uint16_t)(hat_ycc_code(hat_add_rn(crv, epi.k.m[11]), epi.scale, epi.maxcode) << epi.shift);
                     }
                 } else {
                     o8[(size_t)y * epi.pitch + xx] = (uint8_t)hat_ycc_byte(Yv);
-                    if ((y & 1) && !(xx & 1)) {
-                        const size_t co = (size_t)b * epi.c_bstride + (size_t)(y >> 1) * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
-                        epi.cb[co] = (uint8_t)hat_chroma_byte(ctop_b, cbs, epi.k.m[7]);
-                        epi.cr[co] = (uint8_t)hat_chroma_byte(ctop_r, crs, epi.k.m[11]);
+                    if constexpr (C420) {
+                        if ((y & 1) && !(xx & 1)) {
+                            const size_t co = (size_t)b * epi.c_bstride + (size_t)(y >> 1) * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
+                            epi.cb[co] = (uint8_t)hat_chroma_byte(ctop_b, cbs, epi.k.m[7]);
+                            epi.cr[co] = (uint8_t)hat_chroma_byte(ctop_r, crs, epi.k.m[11]);
+                        }
+                    } else if constexpr (C422) {
+                        if (!(xx & 1)) {
+                            const size_t co = (size_t)b * epi.c_bstride + (size_t)y * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
+                            epi.cb[co] = (uint8_t)hat_ycc_byte(hat_chroma_value_h(cbs, epi.k.m[7]));
+                            epi.cr[co] = (uint8_t)hat_ycc_byte(hat_chroma_value_h(crs, epi.k.m[11]));
+                        }
+                    } else if constexpr (C444) {
+                        const size_t co = (size_t)b * epi.c_bstride + (size_t)y * epi.c_pitch + (size_t)xx * epi.c_step;
+                        epi.cb[co] = (uint8_t)hat_ycc_byte(hat_add_rn(cbv, epi.k.m[7]));
+                        epi.cr[co] = (uint8_t)hat_ycc_byte(hat_add_rn(crv, epi.k.m[11]));
                     }
                 }
             }
-            if (!(y & 1)) { ctop_b = cbs; ctop_r = crs; }
+            if constexpr (C420) {
+                if (!(y & 1)) { ctop_b = cbs; ctop_r = crs; }
+            }
         } else if (y >= y0 && y < y1 && g < 2 && oin) {
             v += bs;
             if constexpr (U8) {
@@ -321,5 +365,54 @@ extern "C" int hat_conv3x3_to_yuv420p16(const void* x, const void* wpk, const fl
     HAT_LAUNCH((cab_squeeze_kernel<2, true, SweepEpiYUV16>), dim3((units + 3) / 4, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(wpk), bias, y, nullptr, H, W, C, ldx, rows, (W + 13) / 14, units,
                epi);
+    return hat_check_launch();
+}
+
+// hat_conv3x3_to_yuv420 / p16 with the destination described once: the instance by the surface's depth and subsampling
+namespace {
+template <typename Epi>
+void launch_sweep_yuv(const void* x, const void* wpk, const float* bias, const HatYuvSurface& d, int B, int H, int W, int C, int ldx, int h_out,
+                      int w_out, float out_scale, const float* mean4, const float* from_rgb12, bool even_rows, hipStream_t st) {
+    int rows = 0, units = 0;
+    sweep_units(H, W, 3072, &rows, &units, even_rows);      // hat_conv3x3_to_planes' geometry; even band heights for 4:2:0 only
+    Epi epi{};
+    epi.out_scale = out_scale;
+    for (int i = 0; i < 4; ++i) epi.mean[i] = mean4[i];
+    epi.h_out = h_out, epi.w_out = w_out, epi.c_step = d.c_step;
+    epi.pitch = d.y_pitch, epi.bstride = d.y_bstride, epi.c_pitch = d.c_pitch, epi.c_bstride = d.c_bstride;
+    epi.cb = reinterpret_cast<uint8_t*>(d.cb), epi.cr = reinterpret_cast<uint8_t*>(d.cr);
+    for (int i = 0; i < 12; ++i) epi.k.m[i] = from_rgb12[i];
+    if constexpr (SweepYuvTraits<Epi>::deep) {
+        epi.shift = d.msb ? 16 - d.depth : 0;
+        epi.scale = (float)(1 << (d.depth - 8));
+        epi.maxcode = (float)((1u << d.depth) - 1u);
+    }
+    HAT_LAUNCH((cab_squeeze_kernel<2, true, Epi>), dim3((units + 3) / 4, B), dim3(256), 0, st, reinterpret_cast<const bf16_t*>(x),
+               reinterpret_cast<const bf16_t*>(wpk), bias, d.y, nullptr, H, W, C, ldx, rows, (W + 13) / 14, units, epi);
+}
+}  // namespace
+
+extern "C" int hat_conv3x3_to_yuv(const void* x, const void* wpk, const float* bias, const HatYuvSurface* dst, int32_t B, int32_t H, int32_t W,
+                                  int32_t C, int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, const float* mean4,
+                                  const float* from_rgb12, int32_t dtype, void* stream) {
+    if (!x || !wpk || !bias || !mean4 || !from_rgb12 || H < 1 || W < 16 || W % 16 || h_out > H || w_out > W) return HAT_EINVAL;
+    if (!hat_yuv_surface_ok(dst, B, h_out, w_out)) return HAT_EINVAL;
+    if (dtype != HAT_BF16) return HAT_EUNSUPPORTED;
+    if (C != 64 || ldx < C || ldx % 8) return HAT_EUNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpk)) % 16) return HAT_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define HAT_SWEEP_YUV(E, even) launch_sweep_yuv<E>(x, wpk, bias, *dst, B, H, W, C, ldx, h_out, w_out, out_scale, mean4, from_rgb12, even, st)
+    using Grey8 = SweepEpiYUVT<0, 0, true>;
+    using Grey16 = SweepEpiYUV16T<0, 0, true>;
+    using C422x8 = SweepEpiYUVT<1, 0, false>;
+    using C422x16 = SweepEpiYUV16T<1, 0, false>;
+    using C444x8 = SweepEpiYUVT<0, 0, false>;
+    using C444x16 = SweepEpiYUV16T<0, 0, false>;
+    const bool deep = dst->depth != 8;
+    if (!dst->cb) { if (deep) HAT_SWEEP_YUV(Grey16, false); else HAT_SWEEP_YUV(Grey8, false); }
+    else if (dst->sub_y) { if (deep) HAT_SWEEP_YUV(SweepEpiYUV16, true); else HAT_SWEEP_YUV(SweepEpiYUV, true); }
+    else if (dst->sub_x) { if (deep) HAT_SWEEP_YUV(C422x16, false); else HAT_SWEEP_YUV(C422x8, false); }
+    else { if (deep) HAT_SWEEP_YUV(C444x16, false); else HAT_SWEEP_YUV(C444x8, false); }
+#undef HAT_SWEEP_YUV
     return hat_check_launch();
 }

@@ -321,6 +321,13 @@ __device__ __forceinline__ float hat_chroma_value(float top, float bottom, float
 }
 __device__ __forceinline__ unsigned hat_chroma_byte(float top, float bottom, float offset) { return hat_ycc_byte(hat_chroma_value(top, bottom, offset)); }
 
+// the chroma value of a 4:2:2 pair from its sum (left + right): sum * 0.5 + offset; a 4:4:4 sample is hat_add_rn(c, offset)
+__device__ __forceinline__ float hat_chroma_value_h(float sum, float offset) {
+#pragma clang fp contract(off)
+    const float q = sum * 0.5f;
+    return q + offset;
+}
+
 __device__ __forceinline__ float hat_add_rn(float a, float b) {   // a sum that stays a sum whatever surrounds the call
 #pragma clang fp contract(off)
     return a + b;

@@ -463,3 +463,40 @@ extern "C" int hat_plan_forward_yuv420_deep(const hat_plan* p, const void* sy, i
                                     dc_pitch, dc_step, dc_bstride, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10), (const float*)r.P(11),
                                     from_rgb12, r.I(12), dst_depth, dst_msb, stream);
 }
+
+// The same forward between two surface descriptions: any subsampling and depth in, any out.
+extern "C" int hat_plan_forward_yuv(const hat_plan* p, const HatYuvSurface* src, const HatYuvSurface* dst, int32_t h, int32_t w,
+                                    const float* to_rgb12, const float* from_rgb12, void* stream) {
+    if (!p || !src || !dst || !to_rgb12 || !from_rgb12 || h < 1 || w < 1) return HAT_EINVAL;
+    // what needs no plan first (a B of 1 stands in: the batch strides are checked against the plan's B below)
+    if (!hat_yuv_surface_ok(src, 1, h, w)) return HAT_EINVAL;
+    const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4];
+    if (p->dims[1] != 3 || p->dims[5] != 3) return HAT_EUNSUPPORTED;   // frames become three-channel images
+    if (h > H || w > W || H - h >= h || W - w >= w) return HAT_EINVAL;
+    // both surfaces in full before anything is enqueued
+    if (!hat_yuv_surface_ok(src, B, h, w) || !hat_yuv_surface_ok(dst, B, (int64_t)s * h, (int64_t)s * w)) return HAT_EINVAL;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != p->device) return HAT_EINVAL;
+    const bool fused = ends_in_planes(p);
+    if (!p->stage_in) {
+        const hipError_t e = hipMalloc((void**)&p->stage_in, (size_t)B * 3 * H * W * sizeof(float));
+        if (e != hipSuccess) { p->stage_in = nullptr; return (int)e; }
+    }
+    if (!fused && !p->stage_out) {
+        const hipError_t e = hipMalloc((void**)&p->stage_out, (size_t)B * 3 * s * H * s * W * sizeof(float));
+        if (e != hipSuccess) { p->stage_out = nullptr; return (int)e; }
+    }
+    const int ho = s * h, wo = s * w;
+    int rc = hat_yuv_to_planes(src, p->stage_in, B, h, w, H, W, to_rgb12, stream);
+    if (rc) return rc;
+    const size_t n = p->calls.size() - (fused ? 1 : 0);
+    for (size_t k = 0; k < n; ++k) {
+        Resolved r{p, &p->calls[k], p->stage_in, p->stage_out, stream, {}};
+        rc = dispatch(r);
+        if (rc) return rc;
+    }
+    if (!fused) return hat_planes_to_yuv(p->stage_out, B, s * H, s * W, dst, ho, wo, from_rgb12, stream);
+    Resolved r{p, &p->calls.back(), p->stage_in, nullptr, stream, {}};
+    return hat_conv3x3_to_yuv(r.P(0), r.P(1), (const float*)r.P(2), dst, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10),
+                              (const float*)r.P(11), from_rgb12, r.I(12), stream);
+}

@@ -3,7 +3,9 @@
 // their p16 forms); definition: super_resolution_amd/yuv.py;
 // colour conversion: basicsr utils/color_util.py (rgb2ycbcr, ycbcr2rgb: BT.601, 16-235), shared with conv_last's yuv epilogue
 // through hat_common.h (hat_ycc_to_rgb, hat_rgb_to_ycc).  cb and cr are separate pointers with a byte step between the
-// samples of a row (1: planar, 2: interleaved), so one kernel serves all three layouts.
+// samples of a row (1: planar, 2: interleaved), so one kernel serves all three layouts.  The chroma subsampling (SUB_X, SUB_Y) and
+// grey (no chroma) are template parameters of the same two kernels: (1,1) is 4:2:0, (1,0) 4:2:2, (0,0) 4:4:4; the surface
+// entries (hat_yuv_to_planes, hat_planes_to_yuv) pick the instance.
 #include <type_traits>
 
 #include "hat_common.h"
@@ -18,6 +20,7 @@ template <> struct HatSample<uint8_t> {
     __device__ __forceinline__ void to_rgb(const HatCsc& k, unsigned Y, unsigned Cb, unsigned Cr, float (&rgb)[3]) const { hat_ycc_to_rgb(k, Y, Cb, Cr, rgb); }
     __device__ __forceinline__ unsigned luma(float v) const { return hat_ycc_byte(v); }
     __device__ __forceinline__ unsigned chroma(float top, float bottom, float offset) const { return hat_chroma_byte(top, bottom, offset); }
+    __device__ __forceinline__ unsigned neutral() const { return 128u; }   // the chroma sample of a grey frame: Cb' = Cr' = 0
 };
 template <> struct HatSample<uint16_t> {
     int shift;
@@ -31,6 +34,7 @@ template <> struct HatSample<uint16_t> {
     __device__ __forceinline__ unsigned chroma(float top, float bottom, float offset) const {
         return hat_ycc_code(hat_chroma_value(top, bottom, offset), scale, (float)maxcode) << shift;
     }
+    __device__ __forceinline__ unsigned neutral() const { return (128u * (unsigned)scale) << shift; }
 };
 
 // sample i of a row that starts at byte address p (pitches, strides and the chroma step are in bytes for every T)
@@ -41,8 +45,9 @@ template <typename T> __device__ __forceinline__ T& sample_at(T* base, size_t by
 
 // one thread = one pixel of the padded plane row (hat_u8_to_planes' shape): a Y sample, the Cb and Cr samples of its 2 x 2 block
 // (the four pixels of a block read the same two samples: L1), three plane stores coalesced over the lanes.  Reflection as in
-// u8_to_planes_kernel; the chroma sample of source pixel (sy, sx) is (sy >> 1, sx >> 1).
-template <typename T>
+// u8_to_planes_kernel; the chroma sample of source pixel (sy, sx) is (sy >> SUB_Y, sx >> SUB_X).  GREY: no chroma is read, both
+// samples are the neutral one.
+template <typename T, int SUB_X, int SUB_Y, bool GREY>
 __global__ __launch_bounds__(256) void yuv420_to_planes_kernel(const T* __restrict__ yp, long long y_pitch, long long y_bstride,
                                                                const T* __restrict__ cbp, const T* __restrict__ crp,
                                                                long long c_pitch, int c_step, long long c_bstride, float* __restrict__ dst,
@@ -50,33 +55,54 @@ __global__ __launch_bounds__(256) void yuv420_to_planes_kernel(const T* __restri
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
     if (x >= Wp) return;
     const int sy = y < h ? y : 2 * (h - 1) - y, sx = x < w ? x : 2 * (w - 1) - x;
-    const size_t co = (size_t)b * c_bstride + (size_t)(sy >> 1) * c_pitch + (size_t)(sx >> 1) * c_step;
     float rgb[3];
-    q.to_rgb(k, sample_at(yp, (size_t)b * y_bstride + (size_t)sy * y_pitch + (size_t)sx * sizeof(T)), sample_at(cbp, co), sample_at(crp, co), rgb);
+    const unsigned Yw = sample_at(yp, (size_t)b * y_bstride + (size_t)sy * y_pitch + (size_t)sx * sizeof(T));
+    if constexpr (GREY) {
+        q.to_rgb(k, Yw, q.neutral(), q.neutral(), rgb);
+    } else {
+        const size_t co = (size_t)b * c_bstride + (size_t)(sy >> SUB_Y) * c_pitch + (size_t)(sx >> SUB_X) * c_step;
+        q.to_rgb(k, Yw, sample_at(cbp, co), sample_at(crp, co), rgb);
+    }
     float* o = dst + ((size_t)b * 3 * Hp + y) * Wp + x;
     const size_t plane = (size_t)Hp * Wp;
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c * plane] = rgb[c];
 }
 
-// one thread = two rows x four columns = two 2 x 2 blocks: rows are not independent here.  Per row and plane 16 contiguous
-// bytes are loaded; the four Y samples of a row go out as one store (a dword of bytes, 8 bytes of words) where the segment is
-// whole and aligned to that store, as single samples otherwise; the two Cb and two Cr samples are single stores (planar or
-// interleaved: the step decides).
-template <typename T>
+// four samples of one row from o: one store (a dword of bytes, 8 bytes of words) where all four are there and o is aligned to
+// that store, single samples otherwise
+template <typename T> __device__ __forceinline__ void store_row4(T* o, const unsigned (&v)[4], int n) {
+    if (n == 4 && (reinterpret_cast<uintptr_t>(o) & (4 * sizeof(T) - 1)) == 0) {
+        if constexpr (sizeof(T) == 1) {
+            *reinterpret_cast<unsigned*>(o) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+        } else {
+            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+            *reinterpret_cast<u32x2*>(o) = u32x2{v[0] | (v[1] << 16), v[2] | (v[3] << 16)};
+        }
+    } else {
+        for (int i = 0; i < n; ++i) o[i] = (T)v[i];
+    }
+}
+
+// one thread = (1 + SUB_Y) rows x four columns (4:2:0: two 2 x 2 blocks, rows are not independent there).  Per row and plane 16
+// contiguous bytes are loaded; the four Y samples of a row go out through store_row4.  4:2:0 and 4:2:2: the two Cb and two Cr
+// samples are single stores (planar or interleaved: the step decides); 4:4:4: four samples a row, through store_row4 when planar.
+// Widths that are no multiple of 4 leave a tail of n = 1, 2 or 3 columns (odd only without horizontal subsampling).
+template <typename T, int SUB_X, int SUB_Y, bool GREY>
 __global__ __launch_bounds__(256) void planes_to_yuv420_kernel(const float* __restrict__ src, int Hs, int Ws, T* __restrict__ yp,
                                                                long long y_pitch, long long y_bstride, T* __restrict__ cbp,
                                                                T* __restrict__ crp, long long c_pitch, int c_step, long long c_bstride,
                                                                int w_out, HatCsc k, HatSample<T> q) {
-    const int x = (blockIdx.x * 256 + threadIdx.x) * 4, y = blockIdx.y * 2, b = blockIdx.z;
+    constexpr int R = 1 + SUB_Y;
+    const int x = (blockIdx.x * 256 + threadIdx.x) * 4, y = blockIdx.y * R, b = blockIdx.z;
     if (x >= w_out) return;
     const size_t plane = (size_t)Hs * Ws;
     const float* s = src + (size_t)b * 3 * plane + (size_t)y * Ws + x;
-    const int n = min(4, w_out - x);          // 2 or 4: w_out is even
-    float cb[2][4], cr[2][4];
-    unsigned v[2][4];
+    const int n = min(4, w_out - x);
+    float cb[R][4], cr[R][4];
+    unsigned v[R][4];
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < R; ++j)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float Y = 0.f;
@@ -85,25 +111,42 @@ __global__ __launch_bounds__(256) void planes_to_yuv420_kernel(const float* __re
             v[j][i] = q.luma(Y);
         }
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        T* o = &sample_at(yp, (size_t)b * y_bstride + (size_t)(y + j) * y_pitch + (size_t)x * sizeof(T));
-        if (n == 4 && (reinterpret_cast<uintptr_t>(o) & (4 * sizeof(T) - 1)) == 0) {
-            if constexpr (sizeof(T) == 1) {
-                *reinterpret_cast<unsigned*>(o) = v[j][0] | (v[j][1] << 8) | (v[j][2] << 16) | (v[j][3] << 24);
-            } else {
-                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-                *reinterpret_cast<u32x2*>(o) = u32x2{v[j][0] | (v[j][1] << 16), v[j][2] | (v[j][3] << 16)};
+    for (int j = 0; j < R; ++j)
+        store_row4(&sample_at(yp, (size_t)b * y_bstride + (size_t)(y + j) * y_pitch + (size_t)x * sizeof(T)), v[j], n);
+    if constexpr (!GREY) {
+        const size_t co = (size_t)b * c_bstride + (size_t)(y >> SUB_Y) * c_pitch + (size_t)(x >> SUB_X) * c_step;
+        if constexpr (SUB_X == 1 && SUB_Y == 1) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                if (2 * i < n) {
+                    sample_at(cbp, co + (size_t)i * c_step) = (T)q.chroma(hat_add_rn(cb[0][2 * i], cb[0][2 * i + 1]), hat_add_rn(cb[1][2 * i], cb[1][2 * i + 1]), k.m[7]);
+                    sample_at(crp, co + (size_t)i * c_step) = (T)q.chroma(hat_add_rn(cr[0][2 * i], cr[0][2 * i + 1]), hat_add_rn(cr[1][2 * i], cr[1][2 * i + 1]), k.m[11]);
+                }
+            }
+        } else if constexpr (SUB_X == 1) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                if (2 * i < n) {
+                    sample_at(cbp, co + (size_t)i * c_step) = (T)q.luma(hat_chroma_value_h(hat_add_rn(cb[0][2 * i], cb[0][2 * i + 1]), k.m[7]));
+                    sample_at(crp, co + (size_t)i * c_step) = (T)q.luma(hat_chroma_value_h(hat_add_rn(cr[0][2 * i], cr[0][2 * i + 1]), k.m[11]));
+                }
             }
         } else {
-            for (int i = 0; i < n; ++i) o[i] = (T)v[j][i];
-        }
-    }
-    const size_t co = (size_t)b * c_bstride + (size_t)(y >> 1) * c_pitch + (size_t)(x >> 1) * c_step;
+            unsigned vb[4], vr[4];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        if (2 * i < n) {
-            sample_at(cbp, co + (size_t)i * c_step) = (T)q.chroma(hat_add_rn(cb[0][2 * i], cb[0][2 * i + 1]), hat_add_rn(cb[1][2 * i], cb[1][2 * i + 1]), k.m[7]);
-            sample_at(crp, co + (size_t)i * c_step) = (T)q.chroma(hat_add_rn(cr[0][2 * i], cr[0][2 * i + 1]), hat_add_rn(cr[1][2 * i], cr[1][2 * i + 1]), k.m[11]);
+            for (int i = 0; i < 4; ++i) {
+                vb[i] = q.luma(hat_add_rn(cb[0][i], k.m[7]));
+                vr[i] = q.luma(hat_add_rn(cr[0][i], k.m[11]));
+            }
+            if (c_step == (int)sizeof(T)) {
+                store_row4(&sample_at(cbp, co), vb, n);
+                store_row4(&sample_at(crp, co), vr, n);
+            } else {
+                for (int i = 0; i < n; ++i) {
+                    sample_at(cbp, co + (size_t)i * c_step) = (T)vb[i];
+                    sample_at(crp, co + (size_t)i * c_step) = (T)vr[i];
+                }
+            }
         }
     }
 }
@@ -122,7 +165,59 @@ bool even_ptrs(const void* a, const void* b, const void* c) {
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 1) == 0;
 }
 
+// the surface entries: one launch each, the instance chosen by the surface's subsampling (grey: no chroma pointers)
+template <typename T, int SX, int SY, bool GREY>
+void launch_to_planes(const HatYuvSurface& s, float* dst, int B, int h, int w, int Hp, int Wp, const HatCsc& k, HatSample<T> q, hipStream_t st) {
+    HAT_LAUNCH((yuv420_to_planes_kernel<T, SX, SY, GREY>), dim3((Wp + 255) / 256, Hp, B), dim3(256), 0, st, reinterpret_cast<const T*>(s.y),
+               (long long)s.y_pitch, (long long)s.y_bstride, reinterpret_cast<const T*>(s.cb), reinterpret_cast<const T*>(s.cr),
+               (long long)s.c_pitch, (int)s.c_step, (long long)s.c_bstride, dst, h, w, Hp, Wp, k, q);
+}
+
+template <typename T, int SX, int SY, bool GREY>
+void launch_from_planes(const float* src, int B, int Hs, int Ws, const HatYuvSurface& s, int h_out, int w_out, const HatCsc& k, HatSample<T> q,
+                        hipStream_t st) {
+    HAT_LAUNCH((planes_to_yuv420_kernel<T, SX, SY, GREY>), dim3((w_out + 1023) / 1024, h_out >> SY, B), dim3(256), 0, st, src, Hs, Ws,
+               reinterpret_cast<T*>(s.y), (long long)s.y_pitch, (long long)s.y_bstride, reinterpret_cast<T*>(s.cb), reinterpret_cast<T*>(s.cr),
+               (long long)s.c_pitch, (int)s.c_step, (long long)s.c_bstride, w_out, k, q);
+}
+
+template <typename T>
+void surface_to_planes(const HatYuvSurface& s, float* dst, int B, int h, int w, int Hp, int Wp, const HatCsc& k, HatSample<T> q, hipStream_t st) {
+    if (!s.cb) launch_to_planes<T, 0, 0, true>(s, dst, B, h, w, Hp, Wp, k, q, st);
+    else if (s.sub_y) launch_to_planes<T, 1, 1, false>(s, dst, B, h, w, Hp, Wp, k, q, st);
+    else if (s.sub_x) launch_to_planes<T, 1, 0, false>(s, dst, B, h, w, Hp, Wp, k, q, st);
+    else launch_to_planes<T, 0, 0, false>(s, dst, B, h, w, Hp, Wp, k, q, st);
+}
+
+template <typename T>
+void surface_from_planes(const float* src, int B, int Hs, int Ws, const HatYuvSurface& s, int h_out, int w_out, const HatCsc& k, HatSample<T> q,
+                         hipStream_t st) {
+    if (!s.cb) launch_from_planes<T, 0, 0, true>(src, B, Hs, Ws, s, h_out, w_out, k, q, st);
+    else if (s.sub_y) launch_from_planes<T, 1, 1, false>(src, B, Hs, Ws, s, h_out, w_out, k, q, st);
+    else if (s.sub_x) launch_from_planes<T, 1, 0, false>(src, B, Hs, Ws, s, h_out, w_out, k, q, st);
+    else launch_from_planes<T, 0, 0, false>(src, B, Hs, Ws, s, h_out, w_out, k, q, st);
+}
+
 }  // namespace
+
+extern "C" int hat_yuv_to_planes(const HatYuvSurface* src, float* dst, int32_t B, int32_t h, int32_t w, int32_t Hp, int32_t Wp,
+                                 const float* to_rgb12, void* stream) {
+    if (!dst || !to_rgb12 || !hat_yuv_surface_ok(src, B, h, w)) return HAT_EINVAL;
+    if (Hp < h || Wp < w || B > 65535 || Hp > 65535) return HAT_EINVAL;
+    if (Hp - h >= h || Wp - w >= w) return HAT_EINVAL;   // the reflection needs a source row / column: pad < size
+    if (src->depth == 8) surface_to_planes<uint8_t>(*src, dst, B, h, w, Hp, Wp, load_csc(to_rgb12), HatSample<uint8_t>{}, reinterpret_cast<hipStream_t>(stream));
+    else surface_to_planes<uint16_t>(*src, dst, B, h, w, Hp, Wp, load_csc(to_rgb12), deep_sample(src->depth, src->msb), reinterpret_cast<hipStream_t>(stream));
+    return hat_check_launch();
+}
+
+extern "C" int hat_planes_to_yuv(const float* src, int32_t B, int32_t Hs, int32_t Ws, const HatYuvSurface* dst, int32_t h_out, int32_t w_out,
+                                 const float* from_rgb12, void* stream) {
+    if (!src || !from_rgb12 || Hs < 1 || Ws < 1 || !hat_yuv_surface_ok(dst, B, h_out, w_out)) return HAT_EINVAL;
+    if (h_out > Hs || w_out > Ws || B > 65535 || h_out > 65535) return HAT_EINVAL;
+    if (dst->depth == 8) surface_from_planes<uint8_t>(src, B, Hs, Ws, *dst, h_out, w_out, load_csc(from_rgb12), HatSample<uint8_t>{}, reinterpret_cast<hipStream_t>(stream));
+    else surface_from_planes<uint16_t>(src, B, Hs, Ws, *dst, h_out, w_out, load_csc(from_rgb12), deep_sample(dst->depth, dst->msb), reinterpret_cast<hipStream_t>(stream));
+    return hat_check_launch();
+}
 
 extern "C" int hat_yuv420_to_planes(const uint8_t* y, int64_t y_pitch, int64_t y_bstride, const uint8_t* cb, const uint8_t* cr,
                                     int64_t c_pitch, int32_t c_step, int64_t c_bstride, float* dst, int32_t B, int32_t h, int32_t w,
@@ -130,7 +225,7 @@ extern "C" int hat_yuv420_to_planes(const uint8_t* y, int64_t y_pitch, int64_t y
     if (!y || !cb || !cr || !dst || !to_rgb12 || !hat_yuv_block_ok(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h, w)) return HAT_EINVAL;
     if (Hp < h || Wp < w || B > 65535 || Hp > 65535) return HAT_EINVAL;
     if (Hp - h >= h || Wp - w >= w) return HAT_EINVAL;   // the reflection needs a source row / column: pad < size
-    HAT_LAUNCH(yuv420_to_planes_kernel<uint8_t>, dim3((Wp + 255) / 256, Hp, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y,
+    HAT_LAUNCH((yuv420_to_planes_kernel<uint8_t, 1, 1, false>), dim3((Wp + 255) / 256, Hp, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y,
                (long long)y_pitch, (long long)y_bstride, cb, cr, (long long)c_pitch, (int)c_step, (long long)c_bstride, dst, h, w, Hp, Wp,
                load_csc(to_rgb12), HatSample<uint8_t>{});
     return hat_check_launch();
@@ -142,7 +237,7 @@ extern "C" int hat_planes_to_yuv420(const float* src, int32_t B, int32_t Hs, int
     if (!src || !y || !cb || !cr || !from_rgb12 || Hs < 1 || Ws < 1 || !hat_yuv_block_ok(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out))
         return HAT_EINVAL;
     if (h_out > Hs || w_out > Ws || B > 65535 || h_out / 2 > 65535) return HAT_EINVAL;
-    HAT_LAUNCH(planes_to_yuv420_kernel<uint8_t>, dim3((w_out + 1023) / 1024, h_out / 2, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src,
+    HAT_LAUNCH((planes_to_yuv420_kernel<uint8_t, 1, 1, false>), dim3((w_out + 1023) / 1024, h_out / 2, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src,
                Hs, Ws, y, (long long)y_pitch, (long long)y_bstride, cb, cr, (long long)c_pitch, (int)c_step, (long long)c_bstride, w_out,
                load_csc(from_rgb12), HatSample<uint8_t>{});
     return hat_check_launch();
@@ -157,7 +252,7 @@ extern "C" int hat_yuv420p16_to_planes(const uint16_t* y, int64_t y_pitch, int64
         return HAT_EINVAL;
     if (Hp < h || Wp < w || B > 65535 || Hp > 65535) return HAT_EINVAL;
     if (Hp - h >= h || Wp - w >= w) return HAT_EINVAL;
-    HAT_LAUNCH(yuv420_to_planes_kernel<uint16_t>, dim3((Wp + 255) / 256, Hp, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y,
+    HAT_LAUNCH((yuv420_to_planes_kernel<uint16_t, 1, 1, false>), dim3((Wp + 255) / 256, Hp, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y,
                (long long)y_pitch, (long long)y_bstride, cb, cr, (long long)c_pitch, (int)c_step, (long long)c_bstride, dst, h, w, Hp, Wp,
                load_csc(to_rgb12), deep_sample(depth, msb));
     return hat_check_launch();
@@ -170,7 +265,7 @@ extern "C" int hat_planes_to_yuv420p16(const float* src, int32_t B, int32_t Hs, 
         !hat_yuv_block_ok_n(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out, 2))
         return HAT_EINVAL;
     if (h_out > Hs || w_out > Ws || B > 65535 || h_out / 2 > 65535) return HAT_EINVAL;
-    HAT_LAUNCH(planes_to_yuv420_kernel<uint16_t>, dim3((w_out + 1023) / 1024, h_out / 2, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    HAT_LAUNCH((planes_to_yuv420_kernel<uint16_t, 1, 1, false>), dim3((w_out + 1023) / 1024, h_out / 2, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                src, Hs, Ws, y, (long long)y_pitch, (long long)y_bstride, cb, cr, (long long)c_pitch, (int)c_step, (long long)c_bstride, w_out,
                load_csc(from_rgb12), deep_sample(depth, msb));
     return hat_check_launch();

@@ -1,7 +1,9 @@
-// hat_yuv_check.h — the one host-side check of a 4:2:0 frame block (include/hat_mi355x.h, "The 4:2:0 frame boundary"), shared by
+// hat_yuv_check.h — the host-side checks of a frame block (4:2:0: the first two; any subsampling: hat_yuv_surface_ok) (include/hat_mi355x.h, "The 4:2:0 frame boundary"), shared by
 // hat_yuv.hip, hat_cabsq.hip and hat_plan.cpp.  Plain C++ (hat_plan.cpp is not a HIP source and cannot include hat_common.h).
 #pragma once
 #include <stdint.h>
+
+#include "../../include/hat_mi355x.h"
 
 // sizes, chroma step, pitches and batch strides (bytes) of a (B, h, w) block: even sizes, rows fit their pitch, samples of
 // the batch do not overlap (the b-strides are ignored for B == 1); the pointers are the caller's to check
@@ -27,3 +29,26 @@ static inline bool hat_yuv_block_ok_n(int64_t y_pitch, int64_t y_bstride, int64_
 // sample widths of the deep entries: an n-bit code in a 16-bit little-endian word, MSB-aligned (msb = 1: P010 / P012 / P016) or
 // LSB-aligned (msb = 0: yuv420p10le ...); at 16 bits the two are the same
 static inline bool hat_yuv_depth_ok(int32_t depth, int32_t msb) { return (depth == 10 || depth == 12 || depth == 16) && (msb == 0 || msb == 1); }
+
+// one HatYuvSurface holding a (B, h, w) block, any subsampling: the sample width, the pointers (cb = cr = NULL: grey, then
+// sub_x / sub_y and the chroma fields are not read; one of them NULL is an error; words are 2-byte aligned), the sizes (w even
+// where sub_x = 1, h even where sub_y = 1; (sub_x, sub_y) is (1,1), (1,0) or (0,0)), c_step = bps (planar) or 2 bps
+// (interleaved), rows that fit their pitch, samples of the batch that do not overlap (the b-strides are ignored for B == 1), and
+// with words even pitches and strides
+static inline bool hat_yuv_surface_ok(const HatYuvSurface* s, int32_t B, int64_t h, int64_t w) {
+    if (!s || !s->y || B < 1 || h < 1 || w < 1 || (s->msb != 0 && s->msb != 1)) return false;
+    if (s->depth != 8 && !hat_yuv_depth_ok(s->depth, s->msb)) return false;
+    const int64_t bps = s->depth == 8 ? 1 : 2, yrow = bps * w;
+    if (!s->cb != !s->cr) return false;
+    const bool grey = !s->cb;
+    if (bps == 2 && (((uintptr_t)s->y | (uintptr_t)s->cb | (uintptr_t)s->cr) & 1)) return false;
+    if (s->y_pitch < yrow || (bps == 2 && (s->y_pitch & 1))) return false;
+    if (B > 1 && (s->y_bstride < s->y_pitch * (h - 1) + yrow || (bps == 2 && (s->y_bstride & 1)))) return false;
+    if (grey) return true;
+    if ((s->sub_x != 0 && s->sub_x != 1) || (s->sub_y != 0 && s->sub_y != 1) || s->sub_y > s->sub_x) return false;   // 4:4:0: out of scope
+    if ((s->sub_x && (w & 1)) || (s->sub_y && (h & 1))) return false;
+    if (s->c_step != bps && s->c_step != 2 * bps) return false;
+    const int64_t crow = (int64_t)s->c_step * (w >> s->sub_x), ch = h >> s->sub_y;
+    if (s->c_pitch < crow || (bps == 2 && (s->c_pitch & 1))) return false;
+    return B == 1 || (s->c_bstride >= s->c_pitch * (ch - 1) + crow && !(bps == 2 && (s->c_bstride & 1)));
+}

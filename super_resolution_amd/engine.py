@@ -823,6 +823,59 @@ class HATEngine:
             self._forward(ws["x_u8"], yuv=(dst, from_rgb, out, out_depth, out_msb))
         return out
 
+    def forward_yuv(self, frame: torch.Tensor, *, fmt: str, out_fmt=None, to_rgb, from_rgb, out=None, depth: int = 8, out_depth=None,
+                    msb=None, out_msb=None, ensemble: int = 1) -> torch.Tensor:
+        """forward_yuv420 for every layout of yuv.LAYOUTS on either side: (B,rows,w) device frames in the layout `fmt` -> the frames
+        of the s-times larger image in the layout `out_fmt` (default: fmt), any subsampling or grey to any other:
+        hat_yuv_to_planes into this shape's workspace, the forward, the crop and the conversion back (in conv_last's epilogue,
+        hat_conv3x3_to_yuv, or hat_planes_to_yuv).  msb / out_msb: the alignment of deep words on each side (default: by the
+        layout); every other keyword as forward_yuv420 takes it."""
+        self._check_u8()
+        ensemble = ops.ensemble_members(ensemble)
+        from . import yuv as _yuv
+        out_fmt = fmt if out_fmt is None else out_fmt
+        out_depth = depth if out_depth is None else out_depth
+        in_msb, out_msb = bool(_yuv.container(depth, fmt, msb)[3]), bool(_yuv.container(out_depth, out_fmt, out_msb)[3])
+        in_dt, out_dt = (torch.uint8 if d == 8 else torch.uint16 for d in (depth, out_depth))
+        if not isinstance(frame, torch.Tensor) or frame.dtype not in (torch.uint8, torch.uint16):
+            raise TypeError(f"expected (B,rows,w) uint8 frames, got {getattr(frame, 'dtype', type(frame))}")
+        if frame.dtype != in_dt:
+            raise TypeError(f"{depth}-bit frames are {in_dt} tensors (uint8 holds 8-bit samples, uint16 deeper ones), got {frame.dtype}")
+        if frame.dim() != 3:
+            raise RuntimeError(f"expected (B,rows,w) {fmt} frames, got {tuple(frame.shape)}")
+        if not frame.is_cuda or frame.device != self.dev:
+            raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
+        h, w = _yuv.frame_size_fmt(frame.shape, fmt)
+        B, s = frame.shape[0], self.scale
+        Hp, Wp = -(-h // self.ws) * self.ws, -(-w // self.ws) * self.ws
+        if Hp - h >= h or Wp - w >= w:
+            raise RuntimeError(f"a {h}x{w} frame cannot be reflect-padded to {Hp}x{Wp} (window_size {self.ws}): the padding must be "
+                               f"smaller than the frame")
+        if frame.stride(2) != 1 or frame.stride(1) != w:
+            frame = frame.contiguous() if in_dt is torch.uint8 else frame.view(torch.int16).contiguous().view(torch.uint16)
+        shape = (B,) + _yuv.frame_shape_fmt(s * h, s * w, out_fmt)
+        if out is None:
+            out = torch.empty(shape, dtype=out_dt, device=self.dev)
+        elif not isinstance(out, torch.Tensor) or out.dtype != out_dt or tuple(out.shape) != shape or out.device != self.dev \
+                or out.stride(2) != 1 or out.stride(1) != s * w:
+            raise RuntimeError(f"out must be a {shape} {str(out_dt)[6:]} tensor on {self.dev} with packed rows, got "
+                               f"{tuple(out.shape)} {out.dtype} on {out.device}")
+        sub = lambda f: None if _yuv.LAYOUTS[f][0] is None else _yuv.LAYOUTS[f][:2]
+        src, dst = ops.yuv_views(frame, fmt), ops.yuv_views(out, out_fmt)
+        with self._lock, torch.cuda.device(self.dev):
+            ws = self._workspace(B, Hp, Wp)
+            if "x_u8" not in ws:     # the padded fp32 input of this shape, shared with forward_u8
+                ws["x_u8"] = torch.zeros(B, 3, Hp, Wp, dtype=torch.float32, device=self.dev)
+                ws["bytes"] += ws["x_u8"].numel() * 4
+            ops.yuv_to_planes(*src, ws["x_u8"], to_rgb, sub=sub(fmt), depth=depth, msb=in_msb)
+            if ensemble > 1:
+                acc = self._ensemble(ws["x_u8"], ensemble, self._ens_acc(ws, B, Hp, Wp))
+                ops.planes_to_yuv(acc, *dst, from_rgb, sub=sub(out_fmt), depth=out_depth, msb=out_msb)
+                self.yuv_planes_calls += 1
+                return out
+            self._forward(ws["x_u8"], yuv=(dst, from_rgb, out, out_depth, out_msb, sub(out_fmt)))
+        return out
+
     def ocab_only(self, t: torch.Tensor, group: int, H: int, W: int) -> torch.Tensor:
         """Run only the OCAB of residual group `group` on tokens t (B, H*W, C) fp32 -> (B, H*W, C) fp32 (used by the tests)."""
         x = torch.zeros(t.shape[0], self.cfg["in_chans"], H, W, device=self.dev)
@@ -845,7 +898,8 @@ class HATEngine:
         global average pools of ECA, hat_arch.py:69-73, and of the ESC dynamic kernel, esc_arch.py:96,121) — and returns the
         band's output rows (ghost rows included; the driver keeps the owned ones).
         u8 = (h_out, w_out, bgr, out): the unsharded forward fills and returns out, (B,h_out,w_out,3) uint8 (forward_to_u8).
-        yuv = ((y, cb, cr) views, from_rgb, out, depth, msb): it fills the views of a 4:2:0 frame and returns out (forward_yuv420)."""
+        yuv = ((y, cb, cr) views, from_rgb, out, depth, msb): it fills the views of a 4:2:0 frame and returns out (forward_yuv420);
+        with a sixth item, the subsampling (sub_x, sub_y) or None for grey, the views are that surface's (forward_yuv)."""
         self._check_input(x)
         B, _, H, W = x.shape
         x = x.to(torch.float32).contiguous()
@@ -1222,7 +1276,8 @@ class HATEngine:
         yuv = ((y, cb, cr), from_rgb, out, depth, msb): the third target, 4:2:0 views of `out`, by the same rule:
         hat_conv3x3_to_yuv420 where the row-sweep kernel runs, else fp32 planes and hat_planes_to_yuv420.  With uint16 views
         (depth 10 / 12 / 16) it is the fourth target, by the same rule again: hat_conv3x3_to_yuv420p16, else fp32 planes and
-        hat_planes_to_yuv420p16; the two yuv counters count both widths."""
+        hat_planes_to_yuv420p16; the two yuv counters count both widths.  yuv with a sixth item (the output surface's subsampling,
+        None: grey): the same rule with hat_conv3x3_to_yuv / hat_planes_to_yuv, for every output format, on the same counters."""
         src, h, wd, dt = f.w["fb"], f.H, f.W, f.dt
         for (pw, rr), dst in zip(self.ups, f.w["ups"]):
             ops.conv(pw, src, dst, B=f.B, H=h, W=wd, dtype=dt, ldx=64, ldo=64, out_mode=O_PIXSHUF_T, ps_r=rr)
@@ -1239,8 +1294,12 @@ class HATEngine:
         if yuv is not None:
             if self.u8_fused and wd % 16 == 0:
                 wpk, b8, _ = self.conv_last_sweep
-                ops.conv3x3_to_yuv420(src, wpk, b8, *yuv[0], B=f.B, H=h, W=wd, C_=64, ldx=64, out_scale=1.0 / r, mean=self._mean(),
-                                      from_rgb=yuv[1], dtype=dt, depth=yuv[3], msb=yuv[4])
+                if len(yuv) > 5:
+                    ops.conv3x3_to_yuv(src, wpk, b8, *yuv[0], sub=yuv[5], B=f.B, H=h, W=wd, C_=64, ldx=64, out_scale=1.0 / r, mean=self._mean(),
+                                       from_rgb=yuv[1], dtype=dt, depth=yuv[3], msb=yuv[4])
+                else:
+                    ops.conv3x3_to_yuv420(src, wpk, b8, *yuv[0], B=f.B, H=h, W=wd, C_=64, ldx=64, out_scale=1.0 / r, mean=self._mean(),
+                                          from_rgb=yuv[1], dtype=dt, depth=yuv[3], msb=yuv[4])
                 self.yuv_fused_calls += 1
                 return
             y = torch.empty(f.B, 3, h, wd, dtype=torch.float32, device=self.dev)
@@ -1255,5 +1314,8 @@ class HATEngine:
             ops.planes_to_u8(y, y8, bgr=u8[2])
             self.u8_planes_calls += 1
         if yuv is not None:
-            ops.planes_to_yuv420(y, *yuv[0], yuv[1], depth=yuv[3], msb=yuv[4])
+            if len(yuv) > 5:
+                ops.planes_to_yuv(y, *yuv[0], yuv[1], sub=yuv[5], depth=yuv[3], msb=yuv[4])
+            else:
+                ops.planes_to_yuv420(y, *yuv[0], yuv[1], depth=yuv[3], msb=yuv[4])
             self.yuv_planes_calls += 1

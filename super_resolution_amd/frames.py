@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 
-PIXFMTS = ("rgb24", "nv12", "nv21", "i420")
+PIXFMTS = ("rgb24", "nv12", "nv21", "i420", "i422", "nv16", "i444", "nv24", "gray")
 
 
 def _raw(t):
@@ -23,7 +23,7 @@ def _raw(t):
 
 
 def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", matrix: str = "bt601", full_range: bool = False, depth: int = 8,
-                   out_depth=None, msb=None, ensemble: int = 1):
+                   out_depth=None, msb=None, ensemble: int = 1, out_pixfmt=None, out_msb=None):
     """Generator: for every (h,w,3) uint8 array of `frames` (all of one size) yield the (s*h,s*w,3) uint8 array that
     `net.forward_u8` computes for it, in order.  `net`: a HAT / HATX module on a GPU, in eval mode.  The yielded array is
     the caller's own (copied out of the pinned buffer).  An empty sequence yields nothing.
@@ -31,12 +31,20 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
     (3sh/2, sw) ones, computed by `net.forward_yuv420` with `matrix` and `full_range` (bgr does not apply).  Same slots,
     same copy stream, same events: only the buffer shapes and the forward differ.  depth / out_depth / msb (4:2:0 only): as
     HAT.forward_yuv420 takes them; a deep side's frames are uint16 arrays, and so are its pinned and device buffers.
+    pixfmt 'i422' / 'nv16' / 'i444' / 'nv24' / 'gray', or out_pixfmt (any layout of yuv.LAYOUTS; default: pixfmt) different from
+    pixfmt: the frames are arrays of yuv.frame_shape_fmt in that layout and every frame goes through `net.forward_yuv` (any
+    subsampling in, any out; out_msb: the output words' alignment), in the same two-slot pipeline.
     ensemble 2 / 4 / 8: every frame through the geometric self-ensemble (HAT.forward_ensemble) of that many members."""
     from .ops import ensemble_members
     ensemble = ensemble_members(ensemble)
     if pixfmt not in PIXFMTS:
         raise RuntimeError(f"unknown pixfmt {pixfmt!r}: one of {PIXFMTS}")
-    yuv420 = pixfmt != "rgb24"
+    if out_pixfmt is not None and (out_pixfmt not in PIXFMTS or (out_pixfmt == "rgb24") != (pixfmt == "rgb24")):
+        raise RuntimeError(f"out_pixfmt {out_pixfmt!r}: one of {PIXFMTS[1:]} for a YCbCr pixfmt (rgb24 frames stay rgb24)")
+    if out_msb is not None and pixfmt == "rgb24":
+        raise RuntimeError("out_msb belongs to the YCbCr pixel formats")
+    general = pixfmt != "rgb24" and (pixfmt not in PIXFMTS[1:4] or out_pixfmt not in (None, pixfmt) or out_msb is not None)
+    yuv420 = pixfmt != "rgb24" and not general
     dev = next(net.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("upscale_frames needs the network on a GPU: the MI355X HIP path is the only path")
@@ -47,7 +55,20 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
     first = np.ascontiguousarray(first)
     s = net.upscale
     in_np, in_dt, out_dt = np.uint8, torch.uint8, torch.uint8
-    if yuv420:
+    if general:
+        from . import yuv as _yuv
+        out_pixfmt = pixfmt if out_pixfmt is None else out_pixfmt
+        out_depth = depth if out_depth is None else out_depth
+        in_np = _yuv.container(depth, pixfmt, msb)[0]
+        _yuv.container(out_depth, out_pixfmt, out_msb)
+        in_dt, out_dt = (torch.uint8 if d == 8 else torch.uint16 for d in (depth, out_depth))
+        if first.ndim != 2 or first.dtype != in_np:
+            raise RuntimeError(f"expected (rows,w) {np.dtype(in_np).name} {pixfmt} frames, got {first.shape} {first.dtype}")
+        h, w = _yuv.frame_size_fmt(first.shape, pixfmt)
+        in_shape, out_shape, shape_text = first.shape, _yuv.frame_shape_fmt(s * h, s * w, out_pixfmt), str(tuple(first.shape)).replace(" ", "")
+        forward = lambda src, dst: net.forward_yuv(src, fmt=pixfmt, out_fmt=out_pixfmt, matrix=matrix, full_range=full_range, out=dst,
+                                                   depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, ensemble=ensemble)
+    elif yuv420:
         from . import yuv as _yuv
         out_depth = depth if out_depth is None else out_depth
         in_np = _yuv.container(depth, pixfmt, msb)[0]

@@ -576,6 +576,97 @@ def conv3x3_to_yuv420(x, wpk, bias8, y, cb, cr, *, B: int, H: int, W: int, C_: i
                             *deep, _stream()), entry), tag=f"k3 {C_}->3 {H}x{W} row sweep yuv420{p}")
 
 
+def yuv_views(frame, fmt: str):
+    """frame (B, rows, w) uint8 (uint16: deep samples) in the standard layout of any `fmt` of yuv.LAYOUTS (rows w samples apart) ->
+    views y (B,h,w), cb, cr (B, h >> sub_y, w >> sub_x): the torch twin of yuv.split_fmt; cb = cr = None for 'gray'."""
+    from . import yuv as _yuv
+    sub_x, sub_y, kind = _yuv.check_layout(fmt)
+    if frame.dim() != 3 or frame.dtype not in (torch.uint8, torch.uint16) or frame.stride(2) != 1 or frame.stride(1) != frame.shape[2]:
+        raise RuntimeError(f"expected (B,rows,w) uint8 frames with packed rows, got {tuple(frame.shape)} {frame.dtype} strides {frame.stride()}")
+    h, w = _yuv.frame_size_fmt(frame.shape, fmt)
+    if kind == "gray":
+        return frame, None, None
+    B, ch, cw, off = frame.shape[0], h >> sub_y, w >> sub_x, frame.storage_offset() + h * w
+    if kind == "planar":
+        st, o_cb, o_cr = (frame.stride(0), cw, 1), off, off + ch * cw
+    else:
+        st, o_cb, o_cr = (frame.stride(0), 2 * cw, 2), off + (kind == "semi_vu"), off + (kind == "semi")
+    return frame[:, :h], frame.as_strided((B, ch, cw), st, o_cb), frame.as_strided((B, ch, cw), st, o_cr)
+
+
+def yuv_surface(y, cb, cr, *, sub, depth: int = 8, msb=False, what: str = "yuv_surface"):
+    """The HatYuvSurface of three device views (cb = cr = None and sub = None: grey): pitches, strides and the step in BYTES;
+    sub = (sub_x, sub_y).  The struct holds raw pointers: keep the views alive while it is used."""
+    if y.dim() != 3 or y.dtype not in (torch.uint8, torch.uint16):
+        raise TypeError(f"{what} needs uint8 (or uint16) (B,h,w) views, got {y.dtype} {tuple(y.shape)}")
+    if (y.dtype == torch.uint8) != (depth == 8) or depth not in (8, 10, 12, 16):
+        raise TypeError(f"{what}: depth {depth} does not go with {y.dtype} views (uint8 holds 8-bit samples, uint16 10, 12 or 16 bits)")
+    if (cb is None) != (cr is None) or (cb is None) != (sub is None):
+        raise RuntimeError(f"{what}: a grey surface has neither Cb nor Cr nor a subsampling; every other one has all three")
+    if not y.is_cuda or y.stride(2) != 1:
+        raise RuntimeError("HAT HIP ops need device tensors with unit-step rows (no CPU path exists)")
+    n, (B, h, w) = y.element_size(), y.shape
+    s = _lib.HatYuvSurface(y=y.data_ptr(), y_pitch=n * y.stride(1), y_bstride=n * y.stride(0), depth=int(depth), msb=int(bool(msb)))
+    if cb is not None:
+        sx, sy = int(sub[0]), int(sub[1])
+        if (sx, sy) not in ((1, 1), (1, 0), (0, 0)) or (sx and w % 2) or (sy and h % 2):
+            raise RuntimeError(f"{what}: a {h}x{w} frame has no chroma subsampling {(sx, sy)} (w even where sub_x = 1, h where sub_y = 1)")
+        if cb.dtype != y.dtype or cr.dtype != y.dtype or not (cb.is_cuda and cr.is_cuda) or tuple(cb.shape) != (B, h >> sy, w >> sx) \
+                or tuple(cr.shape) != tuple(cb.shape) or cb.stride() != cr.stride() or cb.stride(2) not in (1, 2):
+            raise RuntimeError(f"{what} needs Cb, Cr ({B},{h >> sy},{w >> sx}) views of Y's dtype and one pitch with a step of 1 or 2 samples")
+        s.cb, s.cr, s.c_pitch, s.c_step, s.c_bstride, s.sub_x, s.sub_y = cb.data_ptr(), cr.data_ptr(), n * cb.stride(1), n * cb.stride(2), \
+            n * cb.stride(0), sx, sy
+    return s
+
+
+def _sub_name(sub, depth):
+    return ("gray" if sub is None else {(1, 1): "yuv420", (1, 0): "yuv422", (0, 0): "yuv444"}[tuple(sub)]) + ("" if depth == 8 else f"p{depth}")
+
+
+def yuv_to_planes(y, cb, cr, dst, to_rgb, *, sub, depth: int = 8, msb=False):
+    """Y (B,h,w), Cb, Cr (B, h >> sub_y, w >> sub_x) views (yuv_views; None, None and sub=None: grey) -> dst (B,3,Hp,Wp) fp32 RGB
+    planes, rows and columns past (h, w) filled by reflection: yuv.yuv_to_planes' conversion (hat_yuv_to_planes)."""
+    lib = _lib.load()
+    surf = yuv_surface(y, cb, cr, sub=sub, depth=depth, msb=msb, what="yuv_to_planes")
+    B, h, w = y.shape
+    if dst.dtype != torch.float32 or dst.dim() != 4 or dst.shape[0] != B or dst.shape[1] != 3 or dst.shape[2] < h or dst.shape[3] < w \
+            or dst.device != y.device or not dst.is_contiguous():
+        raise RuntimeError(f"yuv_to_planes needs a contiguous (B,3,Hp>=h,Wp>=w) fp32 destination on {y.device}, got {tuple(dst.shape)} "
+                           f"{dst.dtype} on {dst.device} for frames {tuple(y.shape)}")
+    m, name = _f12(to_rgb), _sub_name(sub, depth)
+    _timed(f"yuv_to_planes_kernel<{name}>", 0.0, lambda: _lib.check(
+        lib.hat_yuv_to_planes(C.byref(surf), _ptr(dst), B, h, w, dst.shape[2], dst.shape[3], m, _stream()), "hat_yuv_to_planes"),
+        tag=f"{name} {h}x{w} -> planes {dst.shape[2]}x{dst.shape[3]}")
+
+
+def planes_to_yuv(src, y, cb, cr, from_rgb, *, sub, depth: int = 8, msb=False):
+    """src (B,3,Hs,Ws) fp32 planes -> the top-left h x w pixels as Y (B,h,w), Cb, Cr views of any subsampling (or grey), converted
+    as yuv.planes_to_yuv converts (hat_planes_to_yuv)."""
+    lib = _lib.load()
+    surf = yuv_surface(y, cb, cr, sub=sub, depth=depth, msb=msb, what="planes_to_yuv")
+    B, h, w = y.shape
+    if src.dim() != 4 or src.shape[0] != B or src.shape[1] != 3 or src.dtype != torch.float32 or src.device != y.device or not src.is_contiguous():
+        raise RuntimeError(f"planes_to_yuv needs contiguous (B,3,Hs,Ws) fp32 planes on {y.device}, got {tuple(src.shape)} {src.dtype} on {src.device}")
+    m, name = _f12(from_rgb), _sub_name(sub, depth)
+    _timed(f"planes_to_yuv_kernel<{name}>", 0.0, lambda: _lib.check(
+        lib.hat_planes_to_yuv(_ptr(src), B, src.shape[2], src.shape[3], C.byref(surf), h, w, m, _stream()), "hat_planes_to_yuv"),
+        tag=f"planes {src.shape[2]}x{src.shape[3]} -> {name} {h}x{w}")
+
+
+def conv3x3_to_yuv(x, wpk, bias8, y, cb, cr, *, sub, B: int, H: int, W: int, C_: int, ldx: int, out_scale: float, mean, from_rgb, dtype: int,
+                   depth: int = 8, msb=False):
+    """conv_last with the YCbCr conversion of any subsampling (or grey) as its epilogue: planes_to_yuv of what conv3x3_to_planes
+    writes, cropped to the top-left h x w pixels of the views; no fp32 image is written (hat_conv3x3_to_yuv)."""
+    lib = _lib.load()
+    surf = yuv_surface(y, cb, cr, sub=sub, depth=depth, msb=msb, what="conv3x3_to_yuv")
+    if y.shape[0] != B:
+        raise RuntimeError(f"conv3x3_to_yuv: destination batch {y.shape[0]} != {B}")
+    m4, m, name = _mean4(mean), _f12(from_rgb), _sub_name(sub, depth)
+    _timed(f"cab_squeeze_kernel<2, {name}>", 2.0 * B * H * W * 9 * C_ * 3, lambda: _lib.check(
+        lib.hat_conv3x3_to_yuv(_ptr(x), _ptr(wpk), _ptr(bias8), C.byref(surf), B, H, W, C_, ldx, y.shape[1], y.shape[2], out_scale, m4, m, dtype,
+                               _stream()), "hat_conv3x3_to_yuv"), tag=f"k3 {C_}->3 {H}x{W} row sweep {name}")
+
+
 def u8_metrics_flags(*, y_channel: bool, bgr: bool, psnr: bool, ssim: bool) -> int:
     return (_lib.METRICS_Y if y_channel else 0) | (_lib.METRICS_BGR if bgr else 0) | (_lib.METRICS_PSNR if psnr else 0) \
         | (_lib.METRICS_SSIM if ssim else 0)

@@ -253,6 +253,25 @@ class Plan:
         _lib.check(self._lib.hat_plan_forward_yuv420_deep(self._h, *sb, depth, sm, h, w, *db, out_depth, dm, ops._f12(to_rgb), ops._f12(from_rgb),
                                                           stream), "hat_plan_forward_yuv420_deep")
 
+    def forward_yuv(self, src: torch.Tensor, dst: torch.Tensor, *, fmt: str, out_fmt=None, matrix: str = "bt601", full_range: bool = False,
+                    depth: int = 8, out_depth=None, msb=None, out_msb=None, stream: int = 0):
+        """hat_plan_forward_yuv: src (B,rows,w) device frames in any layout `fmt` of yuv.LAYOUTS with h <= H, w <= W of the plan ->
+        dst, the frames of the s-times larger image in the layout `out_fmt` (default: fmt).  Keywords as HAT.forward_yuv takes them."""
+        from . import ops, yuv
+        out_fmt = fmt if out_fmt is None else out_fmt
+        out_depth = depth if out_depth is None else out_depth
+        to_rgb, from_rgb = yuv.csc(matrix, full_range, depth)[0], yuv.csc(matrix, full_range, out_depth)[1]
+        h, w = yuv.frame_size_fmt(src.shape, fmt)
+        s = self.dims[4]
+        if src.shape[0] != self.dims[0] or tuple(dst.shape) != (self.dims[0],) + yuv.frame_shape_fmt(s * h, s * w, out_fmt):
+            raise RuntimeError(f"forward_yuv: src {tuple(src.shape)} / dst {tuple(dst.shape)} do not match a plan of batch {self.dims[0]}, scale {s}")
+        sub = lambda f: None if yuv.LAYOUTS[f][0] is None else yuv.LAYOUTS[f][:2]
+        sv, dv = ops.yuv_views(src, fmt), ops.yuv_views(dst, out_fmt)     # (kept alive: the surfaces hold raw pointers)
+        ss = ops.yuv_surface(*sv, sub=sub(fmt), depth=depth, msb=yuv.container(depth, fmt, msb)[3], what="forward_yuv")
+        ds = ops.yuv_surface(*dv, sub=sub(out_fmt), depth=out_depth, msb=yuv.container(out_depth, out_fmt, out_msb)[3], what="forward_yuv")
+        _lib.check(self._lib.hat_plan_forward_yuv(self._h, C.byref(ss), C.byref(ds), h, w, ops._f12(to_rgb), ops._f12(from_rgb), stream),
+                   "hat_plan_forward_yuv")
+
     def close(self):
         if self._h:
             self._lib.hat_plan_free(self._h)

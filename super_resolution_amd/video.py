@@ -1,7 +1,7 @@
 """Upscale a YUV4MPEG2 file on the device: 4:2:0 frames up, 4:2:0 frames down, no colour conversion on the host.
 
     python -m super_resolution_amd.video -opt options/test/HAT-S_SRx4.yml -i in.y4m -o out.y4m [--matrix bt709] [--full-range]
-                                         [--out-depth 10] [--self-ensemble [N]]
+                                         [--out-depth 10] [--out-chroma 444] [--self-ensemble [N]]
 
 y4m.Reader -> frames.upscale_frames(pixfmt='i420') -> y4m.Writer.  W and H of the header are multiplied by the network's
 scale; every other header token (frame rate, interlacing, aspect, colour space, X comments) is copied.  Decoding and
@@ -9,6 +9,9 @@ encoding compressed video is somebody else's job: `ffmpeg -i in.mp4 -pix_fmt yuv
 10-, 12- and 16-bit streams (C420p10 / C420p12 / C420p16, `-pix_fmt yuv420p10le -strict -1`) are read as they are: the input
 depth comes from the header; --out-depth sets the output's (default: the input's) and with it the output's C token, so
 `--out-depth 10` on an 8-bit file writes the network's result with ten bits.  No transfer function is applied.
+4:2:2, 4:4:4 and grey streams (C422 / C444 / Cmono and their deep forms) are read as they are; --out-chroma 420|422|444|mono
+sets the output's subsampling (default: the input's) and with it the C token: `--out-chroma 444` on a 4:2:0 file keeps all of the
+network's chroma.
 --self-ensemble [N] runs every frame through the geometric self-ensemble of N = 2, 4 or 8 (the default) members.
 """
 from __future__ import annotations
@@ -18,26 +21,32 @@ import argparse
 from . import y4m
 
 
-def upscale_file(net, src: str, dst: str, *, matrix: str = "bt601", full_range: bool = False, out_depth=None, ensemble: int = 1) -> dict:
+def upscale_file(net, src: str, dst: str, *, matrix: str = "bt601", full_range: bool = False, out_depth=None, ensemble: int = 1,
+                 out_chroma=None) -> dict:
     """Every frame of the .y4m file `src` through `net` into `dst`; returns {'frames', 'in', 'out'} (sizes as (w, h)), and for
     streams that are not 8-bit on both sides also 'depth' and 'out_depth'; with ensemble 2 / 4 / 8 (the self-ensemble of every
-    frame, frames.upscale_frames) also 'ensemble'."""
+    frame, frames.upscale_frames) also 'ensemble'; for streams that are not 4:2:0 on both sides also 'chroma' and 'out_chroma'
+    (out_chroma '420' / '422' / '444' / 'mono'; default: the input's)."""
     from . import frames
     from .ops import ensemble_members
     ensemble = ensemble_members(ensemble)
     n = 0
-    with y4m.Reader(src, deep=True) as rd:
+    with y4m.Reader(src, chroma=True) as rd:
         depth = rd.depth
         out_depth = depth if out_depth is None else out_depth
-        hdr = y4m.with_depth(y4m.scaled_header(rd.header, net.upscale), out_depth)
+        chroma = y4m.chroma(rd.header)
+        out_chroma = chroma if out_chroma is None else out_chroma
+        hdr = y4m.with_chroma(y4m.with_depth(y4m.scaled_header(rd.header, net.upscale), out_depth), out_chroma)
         kw = {} if depth == 8 and out_depth == 8 else {"depth": depth, "out_depth": out_depth}
         if ensemble > 1:
             kw["ensemble"] = ensemble
-        with y4m.Writer(dst, hdr, deep=True) as wr:
-            for out in frames.upscale_frames(net, rd, pixfmt="i420", matrix=matrix, full_range=full_range, **kw):
+        info = {} if chroma == "420" and out_chroma == "420" else {"chroma": chroma, "out_chroma": out_chroma}
+        fkw = {"out_pixfmt": y4m.CHROMAS[out_chroma]} if info else {}
+        with y4m.Writer(dst, hdr, chroma=True) as wr:
+            for out in frames.upscale_frames(net, rd, pixfmt=rd.fmt, matrix=matrix, full_range=full_range, **kw, **fkw):
                 wr.write(out)
                 n += 1
-    return dict({"frames": n, "in": (rd.w, rd.h), "out": (hdr["W"], hdr["H"])}, **kw)
+    return dict({"frames": n, "in": (rd.w, rd.h), "out": (hdr["W"], hdr["H"])}, **kw, **info)
 
 
 def parser() -> argparse.ArgumentParser:
@@ -49,6 +58,8 @@ def parser() -> argparse.ArgumentParser:
                     help="YCbCr matrix of the stream (default: bt601, the reference's)")
     ap.add_argument("--out-depth", type=int, default=None, choices=[8, 10, 12, 16],
                     help="bits per sample of the output stream (default: the input's, which the header names)")
+    ap.add_argument("--out-chroma", default=None, choices=["420", "422", "444", "mono"],
+                    help="chroma subsampling of the output stream (default: the input's, which the header names)")
     ap.add_argument("--full-range", action="store_true", help="the stream is full range (0-255) instead of 16-235 / 16-240")
     ap.add_argument("--self-ensemble", nargs="?", type=int, const=8, default=None, choices=[2, 4, 8], metavar="N",
                     help="geometric self-ensemble of every frame over the first N = 2, 4 or 8 (default when N is left out) flips / transposes")
@@ -62,7 +73,7 @@ def main(argv=None):
     from .test import parse_options
     model = HATModel(parse_options(args.opt), device=args.device)
     info = upscale_file(model.get_bare_model(model.net_g), args.input, args.output, matrix=args.matrix, full_range=args.full_range,
-                        out_depth=args.out_depth, ensemble=args.self_ensemble or 1)
+                        out_depth=args.out_depth, ensemble=args.self_ensemble or 1, out_chroma=args.out_chroma)
     print(info)
     return info
 

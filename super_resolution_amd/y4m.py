@@ -9,6 +9,13 @@ space (C444, C422, Cmono ...), more than 8 bits (C420p10 ...) and odd sizes are 
 deep=True (parse_header, Reader, Writer) also accepts C420p10, C420p12 and C420p16: every sample is a little-endian 16-bit word
 holding the code LSB-aligned (yuv.py, "Deep samples"), a frame is a (3h/2, w) uint16 array and its record is 3 w h bytes long.
 depth(hdr) is 8, 10, 12 or 16.  Without deep=True these streams are refused as before.
+
+chroma=True (parse_header, format_header, Reader, Writer; it includes deep=True) also accepts C422, C444 and Cmono and their deep
+forms C422p10 / p12 / p16, C444p10 / p12 / p16, Cmono10 / Cmono12 / Cmono16.  Reader.fmt / Writer.fmt names the layout of yuv.py
+('i420', 'i422', 'i444' or 'gray'), a frame is an array of yuv.frame_shape_fmt(h, w, fmt) and its record holds 3/2, 2, 3 or 1
+times w h samples; only the subsampled directions need even sizes.  chroma(hdr) is '420', '422', '444' or 'mono';
+with_chroma(hdr, c) rewrites the C token.  C444alpha and everything else is still refused by name.  Without chroma=True the
+behaviour is what it was.
 """
 from __future__ import annotations
 
@@ -18,6 +25,15 @@ MAGIC = b"YUV4MPEG2"
 COLOUR_SPACES = ("420", "420jpeg", "420mpeg2", "420paldv")
 DEEP_COLOUR_SPACES = {"420p10": 10, "420p12": 12, "420p16": 16}
 TOKENS = "WHFIAC"
+CHROMAS = {"420": "i420", "422": "i422", "444": "i444", "mono": "gray"}   # chroma(hdr) -> layout of yuv.py
+_CHROMA_SPACES = {}   # C token (chroma=True) -> (chroma, bits)
+for _c in ("422", "444"):
+    _CHROMA_SPACES[_c] = (_c, 8)
+    for _b in (10, 12, 16):
+        _CHROMA_SPACES[f"{_c}p{_b}"] = (_c, _b)
+_CHROMA_SPACES["mono"] = ("mono", 8)
+for _b in (10, 12, 16):
+    _CHROMA_SPACES[f"mono{_b}"] = ("mono", _b)
 
 
 class Y4MError(RuntimeError):
@@ -26,7 +42,30 @@ class Y4MError(RuntimeError):
 
 def depth(hdr: dict) -> int:
     """Bits per sample of a stream with this header: 8, or 10 / 12 / 16 for C420p10 / C420p12 / C420p16."""
-    return DEEP_COLOUR_SPACES.get(hdr.get("C", "420"), 8)
+    c = hdr.get("C", "420")
+    return _CHROMA_SPACES[c][1] if c in _CHROMA_SPACES else DEEP_COLOUR_SPACES.get(c, 8)
+
+
+def chroma(hdr: dict) -> str:
+    """'420', '422', '444' or 'mono': the subsampling the header's C token names (CHROMAS maps it to a layout of yuv.py)."""
+    c = hdr.get("C", "420")
+    return _CHROMA_SPACES[c][0] if c in _CHROMA_SPACES else "420"
+
+
+_chroma_of = chroma    # (parse_header, Reader and Writer take a keyword of this name)
+
+
+def with_chroma(hdr: dict, c: str, bits=None) -> dict:
+    """The header with its C token set for subsampling `c` ('420', '422', '444', 'mono') at `bits` per sample (default: the
+    header's); a token that already says so is kept (C420jpeg stays C420jpeg)."""
+    if c not in CHROMAS:
+        raise Y4MError(f"unknown chroma subsampling {c!r}: one of {tuple(CHROMAS)}")
+    bits = depth(hdr) if bits is None else bits
+    if bits not in (8, 10, 12, 16):
+        raise Y4MError(f"a stream has 8, 10, 12 or 16 bits per sample, got {bits}")
+    if c == chroma(hdr) and bits == depth(hdr):
+        return dict(hdr)
+    return dict(hdr, C=c if bits == 8 else (f"mono{bits}" if c == "mono" else f"{c}p{bits}"))
 
 
 def with_depth(hdr: dict, bits: int) -> dict:
@@ -35,10 +74,12 @@ def with_depth(hdr: dict, bits: int) -> dict:
         raise Y4MError(f"a 4:2:0 stream has 8, 10, 12 or 16 bits per sample, got {bits}")
     if bits == depth(hdr):
         return dict(hdr)
+    if chroma(hdr) != "420":
+        return with_chroma(hdr, chroma(hdr), bits)
     return dict(hdr, C="420" if bits == 8 else f"420p{bits}")
 
 
-def parse_header(line: bytes, deep: bool = False) -> dict:
+def parse_header(line: bytes, deep: bool = False, chroma: bool = False) -> dict:
     """The header line (without its newline) -> {'W': int, 'H': int, 'F': str, 'I': str, 'A': str, 'C': str, 'X': [str ...]};
     tokens that are absent are absent (C defaults to '420' for the reader's purposes)."""
     parts = line.split(b" ")
@@ -63,6 +104,15 @@ def parse_header(line: bytes, deep: bool = False) -> dict:
     if "W" not in hdr or "H" not in hdr:
         raise Y4MError("the header names no W / H")
     c = hdr.get("C", "420")
+    if chroma:
+        if c in _CHROMA_SPACES:
+            sub = _CHROMA_SPACES[c][0]
+            if sub == "422" and hdr["W"] % 2:
+                raise Y4MError(f"4:2:2 frames need an even width, got W{hdr['W']} H{hdr['H']}")
+            return hdr
+        if c not in COLOUR_SPACES and c not in DEEP_COLOUR_SPACES:
+            raise Y4MError(f"colour space C{c} is not supported: C420 (jpeg, mpeg2, paldv), C422, C444, Cmono and their 10 / 12 / 16-bit forms")
+        deep = True
     if c not in COLOUR_SPACES and not (deep and c in DEEP_COLOUR_SPACES):
         if c.startswith("420p"):
             raise Y4MError(f"colour space C{c} has more than 8 bits per sample: only 8-bit 4:2:0 is supported")
@@ -72,9 +122,9 @@ def parse_header(line: bytes, deep: bool = False) -> dict:
     return hdr
 
 
-def format_header(hdr: dict, deep: bool = False) -> bytes:
+def format_header(hdr: dict, deep: bool = False, chroma: bool = False) -> bytes:
     """The header line for W, H and whichever of F, I, A, C, X are present, in that order, with its newline."""
-    parse_header(b" ".join([MAGIC, b"W%d" % hdr["W"], b"H%d" % hdr["H"]] + ([b"C" + hdr["C"].encode()] if "C" in hdr else [])), deep)
+    parse_header(b" ".join([MAGIC, b"W%d" % hdr["W"], b"H%d" % hdr["H"]] + ([b"C" + hdr["C"].encode()] if "C" in hdr else [])), deep, chroma)
     out = [MAGIC, b"W%d" % hdr["W"], b"H%d" % hdr["H"]]
     out += [k.encode() + str(hdr[k]).encode() for k in "FIAC" if k in hdr]
     out += [b"X" + x.encode() for x in hdr.get("X", [])]
@@ -93,11 +143,15 @@ def _readline(f, limit: int = 4096) -> bytes:
     return line
 
 
+def _frame_shape(h: int, w: int, fmt: str):
+    return {"i420": (3 * h // 2, w), "i422": (2 * h, w), "i444": (3 * h, w), "gray": (h, w)}[fmt]
+
+
 class Reader:
     """Iterates the frames of a .y4m file as (3h/2, w) uint8 arrays (layout 'i420'); .header is the parsed header.  deep=True:
     C420p10 / p12 / p16 streams are read too, as uint16 arrays (.depth says which)."""
 
-    def __init__(self, path_or_file, deep: bool = False):
+    def __init__(self, path_or_file, deep: bool = False, chroma: bool = False):
         self._own = isinstance(path_or_file, (str, bytes)) or hasattr(path_or_file, "__fspath__")
         self._f = open(path_or_file, "rb") if self._own else path_or_file
         line = _readline(self._f)
@@ -105,13 +159,15 @@ class Reader:
             self.close()
             raise Y4MError("the stream ends inside its header")
         try:
-            self.header = parse_header(line[:-1], deep)
+            self.header = parse_header(line[:-1], deep, chroma)
         except Y4MError:
             self.close()
             raise
         self.w, self.h = self.header["W"], self.header["H"]
         self.depth = depth(self.header)
         self._dtype = np.dtype(np.uint8) if self.depth == 8 else np.dtype("<u2")
+        self.fmt = CHROMAS[_chroma_of(self.header)]      # 'i420' unless chroma=True let another colour space in
+        self._shape = _frame_shape(self.h, self.w, self.fmt)
 
     def __iter__(self):
         return self
@@ -122,11 +178,11 @@ class Reader:
             raise StopIteration
         if not line.endswith(b"\n") or not (line == b"FRAME\n" or line.startswith(b"FRAME ")):
             raise Y4MError(f"expected a FRAME record, got {line[:16]!r}")
-        n = self.w * self.h * 3 // 2 * self._dtype.itemsize
+        n = self._shape[0] * self._shape[1] * self._dtype.itemsize
         raw = self._f.read(n)
         if len(raw) != n:
             raise Y4MError(f"truncated frame: {len(raw)} of {n} bytes")
-        return np.frombuffer(raw, dtype=self._dtype).reshape(3 * self.h // 2, self.w)
+        return np.frombuffer(raw, dtype=self._dtype).reshape(self._shape)
 
     def close(self):
         if self._own and self._f:
@@ -144,13 +200,14 @@ class Writer:
     """Writes (3h/2, w) uint8 'i420' frames as a .y4m file with the given header (a dict as parse_header returns).  deep=True:
     a C420p10 / p12 / p16 header is accepted and its frames are uint16 arrays, written as little-endian words."""
 
-    def __init__(self, path_or_file, header: dict, deep: bool = False):
+    def __init__(self, path_or_file, header: dict, deep: bool = False, chroma: bool = False):
         self.header = dict(header)
-        head = format_header(self.header, deep)
+        head = format_header(self.header, deep, chroma)
+        self.fmt = CHROMAS[_chroma_of(self.header)]
         self._dtype = np.dtype(np.uint8) if depth(self.header) == 8 else np.dtype(np.uint16)
         self._own = isinstance(path_or_file, (str, bytes)) or hasattr(path_or_file, "__fspath__")
         self._f = open(path_or_file, "wb") if self._own else path_or_file
-        self._shape = (3 * header["H"] // 2, header["W"])
+        self._shape = _frame_shape(header["H"], header["W"], self.fmt)
         self._f.write(head)
 
     def write(self, frame: np.ndarray):

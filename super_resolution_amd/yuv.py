@@ -30,8 +30,8 @@ Output, from the fp32 value v the float path would have stored: r, g, b = min(ma
 and a byte is rint(min(max(., 0), 255)), round half to even.
 
 Chroma siting: nearest up, box down is centre-sited chroma (JPEG, MPEG-1, Y4M C420jpeg).  Left-sited sources (MPEG-2,
-H.264) are accepted and treated the same: a quarter-pixel chroma shift at the output scale.  Other chroma filters, 4:2:2,
-4:4:4 and tone mapping are out of scope.
+H.264) are accepted and treated the same: a quarter-pixel chroma shift at the output scale.  Other chroma filters and tone
+mapping are out of scope; 4:2:2, 4:4:4 and grey are "Other subsamplings" below.
 
 Deep samples (HEVC Main10, AV1, VP9 profile 2).  A deep sample is a little-endian 16-bit word that holds an n-bit code, n =
 depth in {10, 12, 16}; k = n - 8, maxcode = 2^n - 1, shift = 16 - n for an MSB-aligned container, else 0.
@@ -51,12 +51,34 @@ Layouts of one frame, a (3 h / 2, w) uint8 array (uint16 for deep samples), h an
   nv12  h rows of Y, then h / 2 rows of interleaved Cb, Cr
   nv21  h rows of Y, then h / 2 rows of interleaved Cr, Cb
   i420  h rows of Y, then the (h / 2, w / 2) Cb plane, then the Cr plane (each stored contiguously in h / 4 rows' worth of bytes)
+
+Other subsamplings (the general functions: yuv_to_planes, planes_to_yuv, split_fmt, join_fmt, frame_shape_fmt, frame_size_fmt).
+LAYOUTS maps every layout name to (sub_x, sub_y, kind): the chroma sample of source pixel (sy, sx) is (sy >> sub_y, sx >> sub_x).
+  name              sub   one frame array                                                         deep default
+  i420 nv12 nv21    1,1   (3h/2, w), as above                                                     as above
+  i422              1,0   (2h, w): Y, then the (h, w/2) Cb plane, then Cr (Y4M C422, yuv422p[10le])  LSB
+  nv16              1,0   (2h, w): Y, then h rows of interleaved Cb, Cr (P210 / P216)               MSB
+  i444              0,0   (3h, w): the Y, Cb, Cr planes (Y4M C444, yuv444p[10le])                   LSB
+  nv24              0,0   (3h, w): Y, then h rows of 2w interleaved samples Cb, Cr (P410 / P416)    MSB
+  gray              none  (h, w): Y only (Y4M Cmono, gray[10le])                                    LSB
+w is even where sub_x = 1 and h where sub_y = 1; every other size >= 1 is a frame (the reflection still needs pad < size).
+Depths, container, decode / encode and csc apply unchanged.  In: as above with the layout's shifts; for 'gray' Cb' = Cr' = 0
+exactly and the same expression follows.  Out: Y and the per-pixel cb, cr terms as above, then
+    4:2:0  as above        4:2:2  C = (c0 + c1) * 0.5 + k[c][3], left + right        4:4:4  C = c + k[c][3]        gray  Y only
+and the byte / code rule is unchanged.  For nv12 / nv21 / i420 the general functions return what the 4:2:0 pair returns.
+Packed 4:2:2 (YUY2 / UYVY / Y210 / v210), 4:1:1, 4:4:0, alpha planes, chroma siting or filters other than nearest / box, and
+tone mapping are out of scope.
 """
 from __future__ import annotations
 
 import numpy as np
 
 FORMATS = ("nv12", "nv21", "i420")
+# name -> (sub_x, sub_y, kind); kind 'planar': Cb plane then Cr plane, 'semi': interleaved Cb, Cr, 'semi_vu': interleaved Cr, Cb,
+# 'gray': no chroma (sub_x = sub_y = None)
+LAYOUTS = {"nv12": (1, 1, "semi"), "nv21": (1, 1, "semi_vu"), "i420": (1, 1, "planar"), "i422": (1, 0, "planar"), "nv16": (1, 0, "semi"),
+           "i444": (0, 0, "planar"), "nv24": (0, 0, "semi"), "gray": (None, None, "gray")}
+ALL_FORMATS = tuple(LAYOUTS)
 MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020nc": (0.2627, 0.0593)}   # Kr, Kb
 DEPTHS = (8, 10, 12, 16)
 _F = np.float32
@@ -68,6 +90,13 @@ def check_fmt(fmt: str) -> str:
     return fmt
 
 
+def check_layout(fmt: str):
+    """(sub_x, sub_y, kind) of any layout of LAYOUTS."""
+    if fmt not in LAYOUTS:
+        raise RuntimeError(f"unknown frame format {fmt!r}: one of {ALL_FORMATS}")
+    return LAYOUTS[fmt]
+
+
 def check_depth(depth) -> int:
     if isinstance(depth, bool) or depth not in DEPTHS:
         raise RuntimeError(f"unsupported sample depth {depth!r}: one of {DEPTHS}")
@@ -77,10 +106,10 @@ def check_depth(depth) -> int:
 def container(depth: int, fmt: str = "nv12", msb=None):
     """(dtype, k, maxcode, shift) of a sample of `depth` bits in layout `fmt`: see "Deep samples" in the module docstring."""
     depth = check_depth(depth)
-    check_fmt(fmt)
+    kind = check_layout(fmt)[2]
     if depth == 8:
         return np.uint8, 0, 255, 0
-    msb = (fmt != "i420") if msb is None else bool(msb)
+    msb = kind.startswith("semi") if msb is None else bool(msb)
     return np.uint16, depth - 8, (1 << depth) - 1, (16 - depth) if msb else 0
 
 
@@ -265,3 +294,128 @@ def planes_to_yuv420(planes: np.ndarray, *, fmt: str = "nv12", matrix: str = "bt
         return join(_byte(Y), _byte(box(cb, k[7])), _byte(box(cr, k[11])), fmt)
     q = lambda v: encode(_code(v, kk, maxcode), out_depth, fmt, msb)
     return join(q(Y), q(box(cb, k[7])), q(box(cr, k[11])), fmt, out_depth, msb)
+
+
+# ------------------------------------------------------------------------------------------------ every subsampling
+def check_size(h: int, w: int, fmt: str):
+    """(h, w) if an h x w frame exists in layout `fmt`: w even where sub_x = 1, h even where sub_y = 1, both >= 1."""
+    sub_x, sub_y, _ = check_layout(fmt)
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise RuntimeError(f"a frame has at least one row and one column, got {h}x{w}")
+    if sub_x == 1 and w % 2:
+        raise RuntimeError(f"{fmt} frames (horizontally subsampled chroma) need an even width, got {h}x{w}")
+    if sub_y == 1 and h % 2:
+        raise RuntimeError(f"{fmt} frames (vertically subsampled chroma) need an even height, got {h}x{w}")
+    return h, w
+
+
+def _rows(fmt: str):
+    """(numerator, denominator) of frame rows per luma row: 3/2, 2, 3 or 1."""
+    sub_x, sub_y, _ = check_layout(fmt)
+    if sub_x is None:
+        return 1, 1
+    return {(1, 1): (3, 2), (1, 0): (2, 1), (0, 0): (3, 1)}[(sub_x, sub_y)]
+
+
+def frame_shape_fmt(h: int, w: int, fmt: str):
+    """Shape of the array that holds one h x w frame in layout `fmt`."""
+    h, w = check_size(h, w, fmt)
+    n, d = _rows(fmt)
+    return (n * h // d, w)
+
+
+def frame_size_fmt(shape, fmt: str):
+    """(h, w) of a frame array of layout `fmt` (the shape alone does not name the layout)."""
+    n, d = _rows(fmt)
+    hh, w = int(shape[-2]), int(shape[-1])
+    if hh < 1 or hh % n:
+        raise RuntimeError(f"a {fmt} frame is a ({n}h{'/' + str(d) if d > 1 else ''}, w) array, got {tuple(shape)}")
+    return check_size(d * hh // n, w, fmt)
+
+
+def split_fmt(frame: np.ndarray, fmt: str, depth=None, msb=None):
+    """frame (..., rows, w) in layout `fmt` -> views Y (..., h, w), Cb, Cr (..., h >> sub_y, w >> sub_x) of the samples as stored;
+    Cb and Cr are None for 'gray'."""
+    sub_x, sub_y, kind = check_layout(fmt)
+    if depth is not None and frame.dtype != container(depth, fmt, msb)[0]:
+        raise RuntimeError(f"a {depth}-bit frame is a {np.dtype(container(depth, fmt, msb)[0]).name} array, got {frame.dtype}")
+    h, w = frame_size_fmt(frame.shape, fmt)
+    if kind == "gray":
+        return frame, None, None
+    lead, ch, cw = frame.shape[:-2], h >> sub_y, w >> sub_x
+    Y, c = frame[..., :h, :], frame[..., h:, :]
+    if kind == "planar":
+        c = c.reshape(lead + (2, ch, cw))
+        return Y, c[..., 0, :, :], c[..., 1, :, :]
+    c = c.reshape(lead + (ch, cw, 2))
+    return (Y, c[..., 0], c[..., 1]) if kind == "semi" else (Y, c[..., 1], c[..., 0])
+
+
+def join_fmt(Y: np.ndarray, Cb, Cr, fmt: str, depth: int = 8, msb=None) -> np.ndarray:
+    """The frame of the stored samples Y, Cb, Cr in layout `fmt` (the inverse of split_fmt; Cb = Cr = None for 'gray')."""
+    h, w = Y.shape[-2:]
+    out = np.empty(Y.shape[:-2] + frame_shape_fmt(h, w, fmt), dtype=container(depth, fmt, msb)[0])
+    oy, ocb, ocr = split_fmt(out, fmt)
+    oy[...] = Y
+    if ocb is not None:
+        ocb[...], ocr[...] = Cb, Cr
+    return out
+
+
+def yuv_to_planes(frame: np.ndarray, *, fmt: str, matrix: str = "bt601", full_range: bool = False, pad=(0, 0), depth: int = 8,
+                  msb=None) -> np.ndarray:
+    """frame (rows, w) or (B, rows, w) in any layout of LAYOUTS -> (B, 3, h + pad[0], w + pad[1]) float32 RGB planes, reflect-padded
+    bottom / right.  yuv420_to_planes for the three 4:2:0 layouts."""
+    frame = np.asarray(frame)
+    sub_x, sub_y, kind = check_layout(fmt)
+    dt = container(depth, fmt, msb)[0]
+    if frame.dtype != dt or frame.ndim not in (2, 3):
+        raise RuntimeError(f"expected a (rows, w) or (B, rows, w) {np.dtype(dt).name} {fmt} frame, got {frame.shape} {frame.dtype}")
+    if frame.ndim == 2:
+        frame = frame[None]
+    h, w = frame_size_fmt(frame.shape, fmt)
+    if pad[0] >= h or pad[1] >= w or pad[0] < 0 or pad[1] < 0:
+        raise RuntimeError(f"a {h}x{w} frame cannot be reflect-padded by {tuple(pad)}: the padding must be smaller than the frame")
+    to_rgb, _ = csc(matrix, full_range, depth)
+    Y, Cb, Cr = split_fmt(frame, fmt)
+    sy, sx = _reflect_index(h, h + pad[0]), _reflect_index(w, w + pad[1])
+    Yp = Y[:, sy][:, :, sx]
+    if kind == "gray":       # Cb' = Cr' = 0: the neutral sample, 128 in byte units at every depth
+        Cbp = Crp = np.full(Yp.shape, 128 << (depth - 8), dtype=np.uint16 if depth > 8 else np.uint8)
+    else:
+        Cbp = Cb[:, sy >> sub_y][:, :, sx >> sub_x]
+        Crp = Cr[:, sy >> sub_y][:, :, sx >> sub_x]
+    if depth == 8:
+        return np.ascontiguousarray(ycc_to_rgb(Yp, Cbp, Crp, to_rgb).transpose(1, 0, 2, 3))
+    Yp = decode(Yp, depth, fmt, msb)
+    if kind != "gray":
+        Cbp, Crp = decode(Cbp, depth, fmt, msb), decode(Crp, depth, fmt, msb)
+    return np.ascontiguousarray(ycc_to_rgb_deep(Yp, Cbp, Crp, to_rgb, depth).transpose(1, 0, 2, 3))
+
+
+def planes_to_yuv(planes: np.ndarray, *, fmt: str, matrix: str = "bt601", full_range: bool = False, crop=None, out_depth: int = 8,
+                  msb=None) -> np.ndarray:
+    """planes (B, 3, Hs, Ws) float32 -> (B,) + frame_shape_fmt(h_out, w_out, fmt) frames in any layout of LAYOUTS; crop = (h_out,
+    w_out), the top-left pixels kept (default: all).  planes_to_yuv420 for the three 4:2:0 layouts."""
+    planes = np.asarray(planes, dtype=_F)
+    sub_x, sub_y, kind = check_layout(fmt)
+    if planes.ndim != 4 or planes.shape[1] != 3:
+        raise RuntimeError(f"expected (B,3,Hs,Ws) float32 planes, got {planes.shape}")
+    ho, wo = (planes.shape[2], planes.shape[3]) if crop is None else (int(crop[0]), int(crop[1]))
+    check_size(ho, wo, fmt)
+    if ho > planes.shape[2] or wo > planes.shape[3]:
+        raise RuntimeError(f"crop {(ho, wo)} does not lie inside the planes {planes.shape[2:]}")
+    _, kk, maxcode, _ = container(out_depth, fmt, msb)
+    _, k = csc(matrix, full_range, out_depth)
+    Y, cb, cr = rgb_to_ycc_float(planes[:, :, :ho, :wo], k)
+    if (sub_x, sub_y) == (1, 1):
+        down = lambda c, off: ((c[:, 0::2, 0::2] + c[:, 0::2, 1::2]) + (c[:, 1::2, 0::2] + c[:, 1::2, 1::2])) * _F(0.25) + off
+    elif (sub_x, sub_y) == (1, 0):
+        down = lambda c, off: (c[:, :, 0::2] + c[:, :, 1::2]) * _F(0.5) + off
+    else:
+        down = lambda c, off: c + off
+    q = _byte if out_depth == 8 else (lambda v: encode(_code(v, kk, maxcode), out_depth, fmt, msb))
+    if kind == "gray":
+        return join_fmt(q(Y), None, None, fmt, out_depth, msb)
+    return join_fmt(q(Y), q(down(cb, k[7])), q(down(cr, k[11])), fmt, out_depth, msb)
