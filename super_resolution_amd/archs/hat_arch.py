@@ -436,15 +436,14 @@ class HAT(nn.Module):
         self._check_u8_input(frame)
         from .. import yuv
         yuv.check_fmt(fmt)
-        out_depth = depth if out_depth is None else out_depth
-        to_rgb, from_rgb = yuv.csc(matrix, full_range, depth)[0], yuv.csc(matrix, full_range, out_depth)[1]
+        yuv.csc(matrix, full_range, depth), yuv.csc(matrix, full_range, depth if out_depth is None else out_depth)   # (refused in this order)
         if frame.dtype != (torch.uint8 if depth == 8 else torch.uint16):
             raise TypeError(f"forward_yuv420: depth={depth} needs a {'uint8' if depth == 8 else 'uint16'} tensor, got {frame.dtype}")
         if frame.dim() == 2:
             frame = frame.unsqueeze(0)
-        with torch.no_grad():
-            return self.engine(frame.device).forward_yuv420(frame, fmt=fmt, to_rgb=to_rgb, from_rgb=from_rgb, out=out, depth=depth,
-                                                            out_depth=out_depth, msb=msb, ensemble=ensemble)
+        yuv.frame_size(frame.shape)   # (what is no 4:2:0 frame is refused in those words)
+        return self.forward_yuv(frame, fmt=fmt, out_fmt=fmt, matrix=matrix, full_range=full_range, depth=depth, out_depth=out_depth, msb=msb,
+                                out_msb=msb, out=out, ensemble=ensemble)
 
     def forward_yuv(self, frame, *, fmt: str, out_fmt=None, matrix: str = "bt601", full_range: bool = False, depth: int = 8, out_depth=None,
                     msb=None, out_msb=None, out=None, ensemble: int = 1):

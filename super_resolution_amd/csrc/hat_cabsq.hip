@@ -326,50 +326,15 @@ extern "C" int hat_conv3x3_to_u8(const void* x, const void* wpk, const float* bi
     return hat_check_launch();
 }
 
-extern "C" int hat_conv3x3_to_yuv420(const void* x, const void* wpk, const float* bias, uint8_t* y, int64_t y_pitch, int64_t y_bstride,
-                                     uint8_t* cb, uint8_t* cr, int64_t c_pitch, int32_t c_step, int64_t c_bstride, int32_t B, int32_t H,
-                                     int32_t W, int32_t C, int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, const float* mean4,
-                                     const float* from_rgb12, int32_t dtype, void* stream) {
-    if (!x || !wpk || !bias || !y || !cb || !cr || !mean4 || !from_rgb12 || H < 1 || W < 16 || W % 16 || h_out > H || w_out > W) return HAT_EINVAL;
-    if (!hat_yuv_block_ok(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out)) return HAT_EINVAL;
-    if (dtype != HAT_BF16) return HAT_EUNSUPPORTED;
-    if (C != 64 || ldx < C || ldx % 8) return HAT_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpk)) % 16) return HAT_EINVAL;
-    int rows = 0, units = 0;
-    sweep_units(H, W, 3072, &rows, &units, true);           // hat_conv3x3_to_planes' geometry with the band height rounded up to even
-    SweepEpiYUV epi{out_scale, {mean4[0], mean4[1], mean4[2], mean4[3]}, h_out, w_out, c_step, (long long)y_pitch, (long long)y_bstride,
-                    (long long)c_pitch, (long long)c_bstride, cb, cr, {}};
-    for (int i = 0; i < 12; ++i) epi.k.m[i] = from_rgb12[i];
-    HAT_LAUNCH((cab_squeeze_kernel<2, true, SweepEpiYUV>), dim3((units + 3) / 4, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-               reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(wpk), bias, y, nullptr, H, W, C, ldx, rows, (W + 13) / 14, units,
-               epi);
-    return hat_check_launch();
-}
-
-extern "C" int hat_conv3x3_to_yuv420p16(const void* x, const void* wpk, const float* bias, uint16_t* y, int64_t y_pitch, int64_t y_bstride,
-                                        uint16_t* cb, uint16_t* cr, int64_t c_pitch, int32_t c_step, int64_t c_bstride, int32_t B, int32_t H,
-                                        int32_t W, int32_t C, int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, const float* mean4,
-                                        const float* from_rgb12, int32_t dtype, int32_t depth, int32_t msb, void* stream) {
-    if (!x || !wpk || !bias || !y || !cb || !cr || !mean4 || !from_rgb12 || H < 1 || W < 16 || W % 16 || h_out > H || w_out > W) return HAT_EINVAL;
-    if (!hat_yuv_depth_ok(depth, msb) || ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(cb) | reinterpret_cast<uintptr_t>(cr)) & 1)) return HAT_EINVAL;
-    if (!hat_yuv_block_ok_n(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out, 2)) return HAT_EINVAL;
-    if (dtype != HAT_BF16) return HAT_EUNSUPPORTED;
-    if (C != 64 || ldx < C || ldx % 8) return HAT_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpk)) % 16) return HAT_EINVAL;
-    int rows = 0, units = 0;
-    sweep_units(H, W, 3072, &rows, &units, true);           // hat_conv3x3_to_yuv420's geometry: even band heights
-    SweepEpiYUV16 epi{out_scale, {mean4[0], mean4[1], mean4[2], mean4[3]}, h_out, w_out, c_step, (long long)y_pitch, (long long)y_bstride,
-                      (long long)c_pitch, (long long)c_bstride, reinterpret_cast<uint8_t*>(cb), reinterpret_cast<uint8_t*>(cr), {},
-                      msb ? 16 - depth : 0, (float)(1 << (depth - 8)), (float)((1u << depth) - 1u)};
-    for (int i = 0; i < 12; ++i) epi.k.m[i] = from_rgb12[i];
-    HAT_LAUNCH((cab_squeeze_kernel<2, true, SweepEpiYUV16>), dim3((units + 3) / 4, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-               reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(wpk), bias, y, nullptr, H, W, C, ldx, rows, (W + 13) / 14, units,
-               epi);
-    return hat_check_launch();
-}
-
-// hat_conv3x3_to_yuv420 / p16 with the destination described once: the instance by the surface's depth and subsampling
+// conv_last into a YCbCr surface: what the yuv entries share.  The conv they accept (after their own checks of the destination)
+// and the launch, the instance by the epilogue type
 namespace {
+int sweep_conv_last_ok(const void* x, const void* wpk, int C, int ldx, int dtype) {
+    if (dtype != HAT_BF16) return HAT_EUNSUPPORTED;
+    if (C != 64 || ldx < C || ldx % 8) return HAT_EUNSUPPORTED;   // conv_last: num_feat = 64
+    return (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpk)) % 16 ? HAT_EINVAL : 0;
+}
+
 template <typename Epi>
 void launch_sweep_yuv(const void* x, const void* wpk, const float* bias, const HatYuvSurface& d, int B, int H, int W, int C, int ldx, int h_out,
                       int w_out, float out_scale, const float* mean4, const float* from_rgb12, bool even_rows, hipStream_t st) {
@@ -392,14 +357,39 @@ void launch_sweep_yuv(const void* x, const void* wpk, const float* bias, const H
 }
 }  // namespace
 
+// The 4:2:0 entries: their own argument lists and checks, then the (1,1) surface of their block into the same launch
+extern "C" int hat_conv3x3_to_yuv420(const void* x, const void* wpk, const float* bias, uint8_t* y, int64_t y_pitch, int64_t y_bstride,
+                                     uint8_t* cb, uint8_t* cr, int64_t c_pitch, int32_t c_step, int64_t c_bstride, int32_t B, int32_t H,
+                                     int32_t W, int32_t C, int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, const float* mean4,
+                                     const float* from_rgb12, int32_t dtype, void* stream) {
+    if (!x || !wpk || !bias || !y || !cb || !cr || !mean4 || !from_rgb12 || H < 1 || W < 16 || W % 16 || h_out > H || w_out > W) return HAT_EINVAL;
+    if (!hat_yuv_block_ok(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out)) return HAT_EINVAL;
+    if (const int rc = sweep_conv_last_ok(x, wpk, C, ldx, dtype)) return rc;
+    launch_sweep_yuv<SweepEpiYUV>(x, wpk, bias, hat_yuv420_surface(y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride, 8, 0), B, H, W, C, ldx,
+                                  h_out, w_out, out_scale, mean4, from_rgb12, true, reinterpret_cast<hipStream_t>(stream));
+    return hat_check_launch();
+}
+
+extern "C" int hat_conv3x3_to_yuv420p16(const void* x, const void* wpk, const float* bias, uint16_t* y, int64_t y_pitch, int64_t y_bstride,
+                                        uint16_t* cb, uint16_t* cr, int64_t c_pitch, int32_t c_step, int64_t c_bstride, int32_t B, int32_t H,
+                                        int32_t W, int32_t C, int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, const float* mean4,
+                                        const float* from_rgb12, int32_t dtype, int32_t depth, int32_t msb, void* stream) {
+    if (!x || !wpk || !bias || !y || !cb || !cr || !mean4 || !from_rgb12 || H < 1 || W < 16 || W % 16 || h_out > H || w_out > W) return HAT_EINVAL;
+    if (!hat_yuv_depth_ok(depth, msb) || ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(cb) | reinterpret_cast<uintptr_t>(cr)) & 1)) return HAT_EINVAL;
+    if (!hat_yuv_block_ok_n(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out, 2)) return HAT_EINVAL;
+    if (const int rc = sweep_conv_last_ok(x, wpk, C, ldx, dtype)) return rc;
+    launch_sweep_yuv<SweepEpiYUV16>(x, wpk, bias, hat_yuv420_surface(y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride, depth, msb), B, H, W, C,
+                                    ldx, h_out, w_out, out_scale, mean4, from_rgb12, true, reinterpret_cast<hipStream_t>(stream));
+    return hat_check_launch();
+}
+
+// the destination described once: the instance by the surface's depth and subsampling
 extern "C" int hat_conv3x3_to_yuv(const void* x, const void* wpk, const float* bias, const HatYuvSurface* dst, int32_t B, int32_t H, int32_t W,
                                   int32_t C, int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, const float* mean4,
                                   const float* from_rgb12, int32_t dtype, void* stream) {
     if (!x || !wpk || !bias || !mean4 || !from_rgb12 || H < 1 || W < 16 || W % 16 || h_out > H || w_out > W) return HAT_EINVAL;
     if (!hat_yuv_surface_ok(dst, B, h_out, w_out)) return HAT_EINVAL;
-    if (dtype != HAT_BF16) return HAT_EUNSUPPORTED;
-    if (C != 64 || ldx < C || ldx % 8) return HAT_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpk)) % 16) return HAT_EINVAL;
+    if (const int rc = sweep_conv_last_ok(x, wpk, C, ldx, dtype)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 #define HAT_SWEEP_YUV(E, even) launch_sweep_yuv<E>(x, wpk, bias, *dst, B, H, W, C, ldx, h_out, w_out, out_scale, mean4, from_rgb12, even, st)
     using Grey8 = SweepEpiYUVT<0, 0, true>;

@@ -329,14 +329,13 @@ bool ends_in_planes(const hat_plan* p) {
         if (addresses_output(p, p->calls[k])) return false;
     return true;
 }
-}  // namespace
 
-extern "C" int hat_plan_forward_u8(const hat_plan* p, const uint8_t* src, int64_t src_pitch, int32_t h, int32_t w, uint8_t* dst,
-                                   int64_t dst_pitch, int32_t flags, void* stream) {
-    if (!p || !src || !dst || h < 1 || w < 1 || src_pitch < 3 * (int64_t)w) return HAT_EINVAL;
+// What the frame entries share once their own checks have passed: the device check, the fp32 staging (allocated by the first
+// call), source(stage_in), the replay of all but a final hat_conv3x3_to_planes, and the ending: fused(r), the conv_last
+// epilogue on the recorded arguments r of that last call, or planes(stage_out, Hs, Ws) after a replay of every call.
+template <typename Source, typename Fused, typename Planes>
+int forward_frames(const hat_plan* p, void* stream, Source source, Fused fused_sink, Planes planes_sink) {
     const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4];
-    if (p->dims[1] != 3 || p->dims[5] != 3) return HAT_EUNSUPPORTED;   // 8-bit frames are three-channel
-    if (h > H || w > W || H - h >= h || W - w >= w || dst_pitch < 3 * (int64_t)s * w) return HAT_EINVAL;
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != p->device) return HAT_EINVAL;
     const bool fused = ends_in_planes(p);
@@ -348,8 +347,7 @@ extern "C" int hat_plan_forward_u8(const hat_plan* p, const uint8_t* src, int64_
         const hipError_t e = hipMalloc((void**)&p->stage_out, (size_t)B * 3 * s * H * s * W * sizeof(float));
         if (e != hipSuccess) { p->stage_out = nullptr; return (int)e; }
     }
-    const int bgr = flags & 1, ho = s * h, wo = s * w;
-    int rc = hat_u8_to_planes(src, src_pitch, src_pitch * h, p->stage_in, B, h, w, H, W, bgr, stream);
+    int rc = source(p->stage_in);
     if (rc) return rc;
     const size_t n = p->calls.size() - (fused ? 1 : 0);
     for (size_t k = 0; k < n; ++k) {
@@ -357,10 +355,60 @@ extern "C" int hat_plan_forward_u8(const hat_plan* p, const uint8_t* src, int64_
         rc = dispatch(r);
         if (rc) return rc;
     }
-    if (!fused) return hat_planes_to_u8(p->stage_out, B, s * H, s * W, dst, dst_pitch, dst_pitch * ho, ho, wo, bgr, stream);
+    if (!fused) return planes_sink(p->stage_out, s * H, s * W);
     Resolved r{p, &p->calls.back(), p->stage_in, nullptr, stream, {}};
-    return hat_conv3x3_to_u8(r.P(0), r.P(1), (const float*)r.P(2), dst, dst_pitch, dst_pitch * ho, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8),
-                             ho, wo, r.F(10), (const float*)r.P(11), bgr, r.I(12), stream);
+    return fused_sink(r);
+}
+
+// a three-channel plan whose (H, W) the (h, w) frame reflect-pads to
+int frame_fits(const hat_plan* p, int32_t h, int32_t w) {
+    const int32_t H = p->dims[2], W = p->dims[3];
+    if (p->dims[1] != 3 || p->dims[5] != 3) return HAT_EUNSUPPORTED;   // frames become three-channel images
+    return h > H || w > W || H - h >= h || W - w >= w ? HAT_EINVAL : 0;
+}
+
+// hat_plan_forward_yuv after its NULL checks.  The 4:2:0 entries come here with the (1,1) surfaces of their blocks and their own
+// from-planes entry (planes420: its grid takes frames twice as tall as hat_planes_to_yuv's).
+int forward_yuv(const hat_plan* p, const HatYuvSurface* src, const HatYuvSurface* dst, int32_t h, int32_t w, const float* to_rgb12,
+                const float* from_rgb12, void* stream, bool planes420) {
+    // what needs no plan first (a B of 1 stands in: the batch strides are checked against the plan's B below)
+    if (!hat_yuv_surface_ok(src, 1, h, w)) return HAT_EINVAL;
+    if (const int rc = frame_fits(p, h, w)) return rc;
+    const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4], ho = s * h, wo = s * w;
+    // both surfaces in full before anything is enqueued (the kernels' own checks would refuse the destination only after the replay)
+    if (!hat_yuv_surface_ok(src, B, h, w) || !hat_yuv_surface_ok(dst, B, (int64_t)s * h, (int64_t)s * w)) return HAT_EINVAL;
+    return forward_frames(
+        p, stream, [&](float* in) { return hat_yuv_to_planes(src, in, B, h, w, H, W, to_rgb12, stream); },
+        [&](Resolved& r) {
+            return hat_conv3x3_to_yuv(r.P(0), r.P(1), (const float*)r.P(2), dst, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10),
+                                      (const float*)r.P(11), from_rgb12, r.I(12), stream);
+        },
+        [&](const float* out, int32_t Hs, int32_t Ws) {
+            const HatYuvSurface& d = *dst;
+            if (!planes420) return hat_planes_to_yuv(out, B, Hs, Ws, dst, ho, wo, from_rgb12, stream);
+            if (d.depth == 8)
+                return hat_planes_to_yuv420(out, B, Hs, Ws, (uint8_t*)d.y, d.y_pitch, d.y_bstride, (uint8_t*)d.cb, (uint8_t*)d.cr, d.c_pitch, d.c_step,
+                                            d.c_bstride, ho, wo, from_rgb12, stream);
+            return hat_planes_to_yuv420p16(out, B, Hs, Ws, (uint16_t*)d.y, d.y_pitch, d.y_bstride, (uint16_t*)d.cb, (uint16_t*)d.cr, d.c_pitch, d.c_step,
+                                           d.c_bstride, ho, wo, from_rgb12, d.depth, d.msb, stream);
+        });
+}
+}  // namespace
+
+extern "C" int hat_plan_forward_u8(const hat_plan* p, const uint8_t* src, int64_t src_pitch, int32_t h, int32_t w, uint8_t* dst,
+                                   int64_t dst_pitch, int32_t flags, void* stream) {
+    if (!p || !src || !dst || h < 1 || w < 1 || src_pitch < 3 * (int64_t)w) return HAT_EINVAL;
+    if (const int rc = frame_fits(p, h, w)) return rc;
+    const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4];
+    if (dst_pitch < 3 * (int64_t)s * w) return HAT_EINVAL;
+    const int bgr = flags & 1, ho = s * h, wo = s * w;
+    return forward_frames(
+        p, stream, [&](float* in) { return hat_u8_to_planes(src, src_pitch, src_pitch * h, in, B, h, w, H, W, bgr, stream); },
+        [&](Resolved& r) {
+            return hat_conv3x3_to_u8(r.P(0), r.P(1), (const float*)r.P(2), dst, dst_pitch, dst_pitch * ho, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8),
+                                     ho, wo, r.F(10), (const float*)r.P(11), bgr, r.I(12), stream);
+        },
+        [&](const float* out, int32_t Hs, int32_t Ws) { return hat_planes_to_u8(out, B, Hs, Ws, dst, dst_pitch, dst_pitch * ho, ho, wo, bgr, stream); });
 }
 
 extern "C" int hat_plan_forward_yuv420(const hat_plan* p, const uint8_t* sy, int64_t sy_pitch, int64_t sy_bstride, const uint8_t* scb,
@@ -369,39 +417,9 @@ extern "C" int hat_plan_forward_yuv420(const hat_plan* p, const uint8_t* sy, int
                                        int32_t dc_step, int64_t dc_bstride, const float* to_rgb12, const float* from_rgb12, void* stream) {
     if (!p || !sy || !scb || !scr || !dy || !dcb || !dcr || !to_rgb12 || !from_rgb12 || h < 2 || w < 2 || (h & 1) || (w & 1)) return HAT_EINVAL;
     if ((sc_step != 1 && sc_step != 2) || (dc_step != 1 && dc_step != 2) || sy_pitch < w || sc_pitch < (int64_t)sc_step * (w / 2)) return HAT_EINVAL;
-    const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4];
-    if (p->dims[1] != 3 || p->dims[5] != 3) return HAT_EUNSUPPORTED;   // 4:2:0 frames become three-channel images
-    if (h > H || w > W || H - h >= h || W - w >= w) return HAT_EINVAL;
-    // both blocks in full before anything is enqueued (the kernels' own checks would refuse the destination only after the replay)
-    if (!hat_yuv_block_ok(sy_pitch, sy_bstride, sc_pitch, sc_step, sc_bstride, B, h, w) ||
-        !hat_yuv_block_ok(dy_pitch, dy_bstride, dc_pitch, dc_step, dc_bstride, B, (int64_t)s * h, (int64_t)s * w))
-        return HAT_EINVAL;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != p->device) return HAT_EINVAL;
-    const bool fused = ends_in_planes(p);
-    if (!p->stage_in) {
-        const hipError_t e = hipMalloc((void**)&p->stage_in, (size_t)B * 3 * H * W * sizeof(float));
-        if (e != hipSuccess) { p->stage_in = nullptr; return (int)e; }
-    }
-    if (!fused && !p->stage_out) {
-        const hipError_t e = hipMalloc((void**)&p->stage_out, (size_t)B * 3 * s * H * s * W * sizeof(float));
-        if (e != hipSuccess) { p->stage_out = nullptr; return (int)e; }
-    }
-    const int ho = s * h, wo = s * w;
-    int rc = hat_yuv420_to_planes(sy, sy_pitch, sy_bstride, scb, scr, sc_pitch, sc_step, sc_bstride, p->stage_in, B, h, w, H, W, to_rgb12, stream);
-    if (rc) return rc;
-    const size_t n = p->calls.size() - (fused ? 1 : 0);
-    for (size_t k = 0; k < n; ++k) {
-        Resolved r{p, &p->calls[k], p->stage_in, p->stage_out, stream, {}};
-        rc = dispatch(r);
-        if (rc) return rc;
-    }
-    if (!fused)
-        return hat_planes_to_yuv420(p->stage_out, B, s * H, s * W, dy, dy_pitch, dy_bstride, dcb, dcr, dc_pitch, dc_step, dc_bstride, ho, wo,
-                                    from_rgb12, stream);
-    Resolved r{p, &p->calls.back(), p->stage_in, nullptr, stream, {}};
-    return hat_conv3x3_to_yuv420(r.P(0), r.P(1), (const float*)r.P(2), dy, dy_pitch, dy_bstride, dcb, dcr, dc_pitch, dc_step, dc_bstride, r.I(4),
-                                 r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10), (const float*)r.P(11), from_rgb12, r.I(12), stream);
+    const HatYuvSurface src = hat_yuv420_surface(sy, sy_pitch, sy_bstride, scb, scr, sc_pitch, sc_step, sc_bstride, 8, 0);
+    const HatYuvSurface dst = hat_yuv420_surface(dy, dy_pitch, dy_bstride, dcb, dcr, dc_pitch, dc_step, dc_bstride, 8, 0);
+    return forward_yuv(p, &src, &dst, h, w, to_rgb12, from_rgb12, stream, true);
 }
 
 // The same forward with a sample width on either side: 8 (bytes, the msb flag is not used) or 10 / 12 / 16 (16-bit words).
@@ -413,90 +431,17 @@ extern "C" int hat_plan_forward_yuv420_deep(const hat_plan* p, const void* sy, i
     if (!p || !sy || !scb || !scr || !dy || !dcb || !dcr || !to_rgb12 || !from_rgb12 || h < 2 || w < 2 || (h & 1) || (w & 1)) return HAT_EINVAL;
     if ((src_depth != 8 && !hat_yuv_depth_ok(src_depth, 0)) || (dst_depth != 8 && !hat_yuv_depth_ok(dst_depth, 0))) return HAT_EINVAL;
     if ((src_msb != 0 && src_msb != 1) || (dst_msb != 0 && dst_msb != 1)) return HAT_EINVAL;
-    const int32_t sb = src_depth == 8 ? 1 : 2, db = dst_depth == 8 ? 1 : 2;
-    auto odd = [](const void* a, const void* b, const void* c) { return ((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 1; };
-    if ((sb == 2 && odd(sy, scb, scr)) || (db == 2 && odd(dy, dcb, dcr))) return HAT_EINVAL;
-    // what needs no plan first (a B of 1 stands in: the batch strides are checked against the plan's B below)
-    if (!hat_yuv_block_ok_n(sy_pitch, 0, sc_pitch, sc_step, 0, 1, h, w, sb) || (dc_step != db && dc_step != 2 * db)) return HAT_EINVAL;
-    const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4];
-    if (p->dims[1] != 3 || p->dims[5] != 3) return HAT_EUNSUPPORTED;   // 4:2:0 frames become three-channel images
-    if (h > H || w > W || H - h >= h || W - w >= w) return HAT_EINVAL;
-    if (!hat_yuv_block_ok_n(sy_pitch, sy_bstride, sc_pitch, sc_step, sc_bstride, B, h, w, sb) ||
-        !hat_yuv_block_ok_n(dy_pitch, dy_bstride, dc_pitch, dc_step, dc_bstride, B, (int64_t)s * h, (int64_t)s * w, db))
-        return HAT_EINVAL;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != p->device) return HAT_EINVAL;
-    const bool fused = ends_in_planes(p);
-    if (!p->stage_in) {
-        const hipError_t e = hipMalloc((void**)&p->stage_in, (size_t)B * 3 * H * W * sizeof(float));
-        if (e != hipSuccess) { p->stage_in = nullptr; return (int)e; }
-    }
-    if (!fused && !p->stage_out) {
-        const hipError_t e = hipMalloc((void**)&p->stage_out, (size_t)B * 3 * s * H * s * W * sizeof(float));
-        if (e != hipSuccess) { p->stage_out = nullptr; return (int)e; }
-    }
-    const int ho = s * h, wo = s * w;
-    int rc = sb == 1 ? hat_yuv420_to_planes((const uint8_t*)sy, sy_pitch, sy_bstride, (const uint8_t*)scb, (const uint8_t*)scr, sc_pitch, sc_step,
-                                            sc_bstride, p->stage_in, B, h, w, H, W, to_rgb12, stream)
-                     : hat_yuv420p16_to_planes((const uint16_t*)sy, sy_pitch, sy_bstride, (const uint16_t*)scb, (const uint16_t*)scr, sc_pitch,
-                                               sc_step, sc_bstride, p->stage_in, B, h, w, H, W, to_rgb12, src_depth, src_msb, stream);
-    if (rc) return rc;
-    const size_t n = p->calls.size() - (fused ? 1 : 0);
-    for (size_t k = 0; k < n; ++k) {
-        Resolved r{p, &p->calls[k], p->stage_in, p->stage_out, stream, {}};
-        rc = dispatch(r);
-        if (rc) return rc;
-    }
-    if (!fused) {
-        if (db == 1)
-            return hat_planes_to_yuv420(p->stage_out, B, s * H, s * W, (uint8_t*)dy, dy_pitch, dy_bstride, (uint8_t*)dcb, (uint8_t*)dcr, dc_pitch,
-                                        dc_step, dc_bstride, ho, wo, from_rgb12, stream);
-        return hat_planes_to_yuv420p16(p->stage_out, B, s * H, s * W, (uint16_t*)dy, dy_pitch, dy_bstride, (uint16_t*)dcb, (uint16_t*)dcr, dc_pitch,
-                                       dc_step, dc_bstride, ho, wo, from_rgb12, dst_depth, dst_msb, stream);
-    }
-    Resolved r{p, &p->calls.back(), p->stage_in, nullptr, stream, {}};
-    if (db == 1)
-        return hat_conv3x3_to_yuv420(r.P(0), r.P(1), (const float*)r.P(2), (uint8_t*)dy, dy_pitch, dy_bstride, (uint8_t*)dcb, (uint8_t*)dcr, dc_pitch,
-                                     dc_step, dc_bstride, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10), (const float*)r.P(11), from_rgb12,
-                                     r.I(12), stream);
-    return hat_conv3x3_to_yuv420p16(r.P(0), r.P(1), (const float*)r.P(2), (uint16_t*)dy, dy_pitch, dy_bstride, (uint16_t*)dcb, (uint16_t*)dcr,
-                                    dc_pitch, dc_step, dc_bstride, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10), (const float*)r.P(11),
-                                    from_rgb12, r.I(12), dst_depth, dst_msb, stream);
+    const int32_t db = dst_depth == 8 ? 1 : 2;
+    // before the plan is read: the source block (forward_yuv refuses it, odd pointers included), odd destination pointers and dc_step
+    if ((db == 2 && (((uintptr_t)dy | (uintptr_t)dcb | (uintptr_t)dcr) & 1)) || (dc_step != db && dc_step != 2 * db)) return HAT_EINVAL;
+    const HatYuvSurface src = hat_yuv420_surface(sy, sy_pitch, sy_bstride, scb, scr, sc_pitch, sc_step, sc_bstride, src_depth, src_msb);
+    const HatYuvSurface dst = hat_yuv420_surface(dy, dy_pitch, dy_bstride, dcb, dcr, dc_pitch, dc_step, dc_bstride, dst_depth, dst_msb);
+    return forward_yuv(p, &src, &dst, h, w, to_rgb12, from_rgb12, stream, true);
 }
 
 // The same forward between two surface descriptions: any subsampling and depth in, any out.
 extern "C" int hat_plan_forward_yuv(const hat_plan* p, const HatYuvSurface* src, const HatYuvSurface* dst, int32_t h, int32_t w,
                                     const float* to_rgb12, const float* from_rgb12, void* stream) {
     if (!p || !src || !dst || !to_rgb12 || !from_rgb12 || h < 1 || w < 1) return HAT_EINVAL;
-    // what needs no plan first (a B of 1 stands in: the batch strides are checked against the plan's B below)
-    if (!hat_yuv_surface_ok(src, 1, h, w)) return HAT_EINVAL;
-    const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4];
-    if (p->dims[1] != 3 || p->dims[5] != 3) return HAT_EUNSUPPORTED;   // frames become three-channel images
-    if (h > H || w > W || H - h >= h || W - w >= w) return HAT_EINVAL;
-    // both surfaces in full before anything is enqueued
-    if (!hat_yuv_surface_ok(src, B, h, w) || !hat_yuv_surface_ok(dst, B, (int64_t)s * h, (int64_t)s * w)) return HAT_EINVAL;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != p->device) return HAT_EINVAL;
-    const bool fused = ends_in_planes(p);
-    if (!p->stage_in) {
-        const hipError_t e = hipMalloc((void**)&p->stage_in, (size_t)B * 3 * H * W * sizeof(float));
-        if (e != hipSuccess) { p->stage_in = nullptr; return (int)e; }
-    }
-    if (!fused && !p->stage_out) {
-        const hipError_t e = hipMalloc((void**)&p->stage_out, (size_t)B * 3 * s * H * s * W * sizeof(float));
-        if (e != hipSuccess) { p->stage_out = nullptr; return (int)e; }
-    }
-    const int ho = s * h, wo = s * w;
-    int rc = hat_yuv_to_planes(src, p->stage_in, B, h, w, H, W, to_rgb12, stream);
-    if (rc) return rc;
-    const size_t n = p->calls.size() - (fused ? 1 : 0);
-    for (size_t k = 0; k < n; ++k) {
-        Resolved r{p, &p->calls[k], p->stage_in, p->stage_out, stream, {}};
-        rc = dispatch(r);
-        if (rc) return rc;
-    }
-    if (!fused) return hat_planes_to_yuv(p->stage_out, B, s * H, s * W, dst, ho, wo, from_rgb12, stream);
-    Resolved r{p, &p->calls.back(), p->stage_in, nullptr, stream, {}};
-    return hat_conv3x3_to_yuv(r.P(0), r.P(1), (const float*)r.P(2), dst, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10),
-                              (const float*)r.P(11), from_rgb12, r.I(12), stream);
+    return forward_yuv(p, src, dst, h, w, to_rgb12, from_rgb12, stream, false);
 }

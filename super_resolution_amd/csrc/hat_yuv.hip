@@ -165,7 +165,7 @@ bool even_ptrs(const void* a, const void* b, const void* c) {
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 1) == 0;
 }
 
-// the surface entries: one launch each, the instance chosen by the surface's subsampling (grey: no chroma pointers)
+// every entry: one launch, the instance chosen by the surface's subsampling (grey: no chroma pointers)
 template <typename T, int SX, int SY, bool GREY>
 void launch_to_planes(const HatYuvSurface& s, float* dst, int B, int h, int w, int Hp, int Wp, const HatCsc& k, HatSample<T> q, hipStream_t st) {
     HAT_LAUNCH((yuv420_to_planes_kernel<T, SX, SY, GREY>), dim3((Wp + 255) / 256, Hp, B), dim3(256), 0, st, reinterpret_cast<const T*>(s.y),
@@ -198,37 +198,47 @@ void surface_from_planes(const float* src, int B, int Hs, int Ws, const HatYuvSu
     else launch_from_planes<T, 0, 0, false>(src, B, Hs, Ws, s, h_out, w_out, k, q, st);
 }
 
+// what every to-planes / from-planes entry ends in once its own checks have passed: the instance by the surface's depth
+int to_planes(const HatYuvSurface& s, float* dst, int B, int h, int w, int Hp, int Wp, const float* to_rgb12, void* stream) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (s.depth == 8) surface_to_planes<uint8_t>(s, dst, B, h, w, Hp, Wp, load_csc(to_rgb12), HatSample<uint8_t>{}, st);
+    else surface_to_planes<uint16_t>(s, dst, B, h, w, Hp, Wp, load_csc(to_rgb12), deep_sample(s.depth, s.msb), st);
+    return hat_check_launch();
+}
+
+int from_planes(const float* src, int B, int Hs, int Ws, const HatYuvSurface& s, int h_out, int w_out, const float* from_rgb12, void* stream) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (s.depth == 8) surface_from_planes<uint8_t>(src, B, Hs, Ws, s, h_out, w_out, load_csc(from_rgb12), HatSample<uint8_t>{}, st);
+    else surface_from_planes<uint16_t>(src, B, Hs, Ws, s, h_out, w_out, load_csc(from_rgb12), deep_sample(s.depth, s.msb), st);
+    return hat_check_launch();
+}
+
+// the padded planes hold the frame, fit the grid, and the reflection has a source row / column: pad < size
+bool padded_ok(int B, int h, int w, int Hp, int Wp) { return Hp >= h && Wp >= w && B <= 65535 && Hp <= 65535 && Hp - h < h && Wp - w < w; }
+
 }  // namespace
 
 extern "C" int hat_yuv_to_planes(const HatYuvSurface* src, float* dst, int32_t B, int32_t h, int32_t w, int32_t Hp, int32_t Wp,
                                  const float* to_rgb12, void* stream) {
-    if (!dst || !to_rgb12 || !hat_yuv_surface_ok(src, B, h, w)) return HAT_EINVAL;
-    if (Hp < h || Wp < w || B > 65535 || Hp > 65535) return HAT_EINVAL;
-    if (Hp - h >= h || Wp - w >= w) return HAT_EINVAL;   // the reflection needs a source row / column: pad < size
-    if (src->depth == 8) surface_to_planes<uint8_t>(*src, dst, B, h, w, Hp, Wp, load_csc(to_rgb12), HatSample<uint8_t>{}, reinterpret_cast<hipStream_t>(stream));
-    else surface_to_planes<uint16_t>(*src, dst, B, h, w, Hp, Wp, load_csc(to_rgb12), deep_sample(src->depth, src->msb), reinterpret_cast<hipStream_t>(stream));
-    return hat_check_launch();
+    if (!dst || !to_rgb12 || !hat_yuv_surface_ok(src, B, h, w) || !padded_ok(B, h, w, Hp, Wp)) return HAT_EINVAL;
+    return to_planes(*src, dst, B, h, w, Hp, Wp, to_rgb12, stream);
 }
 
 extern "C" int hat_planes_to_yuv(const float* src, int32_t B, int32_t Hs, int32_t Ws, const HatYuvSurface* dst, int32_t h_out, int32_t w_out,
                                  const float* from_rgb12, void* stream) {
     if (!src || !from_rgb12 || Hs < 1 || Ws < 1 || !hat_yuv_surface_ok(dst, B, h_out, w_out)) return HAT_EINVAL;
     if (h_out > Hs || w_out > Ws || B > 65535 || h_out > 65535) return HAT_EINVAL;
-    if (dst->depth == 8) surface_from_planes<uint8_t>(src, B, Hs, Ws, *dst, h_out, w_out, load_csc(from_rgb12), HatSample<uint8_t>{}, reinterpret_cast<hipStream_t>(stream));
-    else surface_from_planes<uint16_t>(src, B, Hs, Ws, *dst, h_out, w_out, load_csc(from_rgb12), deep_sample(dst->depth, dst->msb), reinterpret_cast<hipStream_t>(stream));
-    return hat_check_launch();
+    return from_planes(src, B, Hs, Ws, *dst, h_out, w_out, from_rgb12, stream);
 }
 
+// The 4:2:0 entries: their own argument lists and checks, then the (1,1) surface of their block through the same two functions
+// (the grid of a 4:2:0 from-planes launch has h_out / 2 rows, so these two take frames twice as tall as hat_planes_to_yuv does).
 extern "C" int hat_yuv420_to_planes(const uint8_t* y, int64_t y_pitch, int64_t y_bstride, const uint8_t* cb, const uint8_t* cr,
                                     int64_t c_pitch, int32_t c_step, int64_t c_bstride, float* dst, int32_t B, int32_t h, int32_t w,
                                     int32_t Hp, int32_t Wp, const float* to_rgb12, void* stream) {
     if (!y || !cb || !cr || !dst || !to_rgb12 || !hat_yuv_block_ok(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h, w)) return HAT_EINVAL;
-    if (Hp < h || Wp < w || B > 65535 || Hp > 65535) return HAT_EINVAL;
-    if (Hp - h >= h || Wp - w >= w) return HAT_EINVAL;   // the reflection needs a source row / column: pad < size
-    HAT_LAUNCH((yuv420_to_planes_kernel<uint8_t, 1, 1, false>), dim3((Wp + 255) / 256, Hp, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y,
-               (long long)y_pitch, (long long)y_bstride, cb, cr, (long long)c_pitch, (int)c_step, (long long)c_bstride, dst, h, w, Hp, Wp,
-               load_csc(to_rgb12), HatSample<uint8_t>{});
-    return hat_check_launch();
+    if (!padded_ok(B, h, w, Hp, Wp)) return HAT_EINVAL;
+    return to_planes(hat_yuv420_surface(y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride, 8, 0), dst, B, h, w, Hp, Wp, to_rgb12, stream);
 }
 
 extern "C" int hat_planes_to_yuv420(const float* src, int32_t B, int32_t Hs, int32_t Ws, uint8_t* y, int64_t y_pitch, int64_t y_bstride,
@@ -237,25 +247,18 @@ extern "C" int hat_planes_to_yuv420(const float* src, int32_t B, int32_t Hs, int
     if (!src || !y || !cb || !cr || !from_rgb12 || Hs < 1 || Ws < 1 || !hat_yuv_block_ok(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out))
         return HAT_EINVAL;
     if (h_out > Hs || w_out > Ws || B > 65535 || h_out / 2 > 65535) return HAT_EINVAL;
-    HAT_LAUNCH((planes_to_yuv420_kernel<uint8_t, 1, 1, false>), dim3((w_out + 1023) / 1024, h_out / 2, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src,
-               Hs, Ws, y, (long long)y_pitch, (long long)y_bstride, cb, cr, (long long)c_pitch, (int)c_step, (long long)c_bstride, w_out,
-               load_csc(from_rgb12), HatSample<uint8_t>{});
-    return hat_check_launch();
+    return from_planes(src, B, Hs, Ws, hat_yuv420_surface(y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride, 8, 0), h_out, w_out, from_rgb12, stream);
 }
 
-// The deep forms: the same kernels on 16-bit words.  Pitches, strides and c_step are in bytes and even.
+// The deep forms: the same on 16-bit words.  Pitches, strides and c_step are in bytes and even.
 extern "C" int hat_yuv420p16_to_planes(const uint16_t* y, int64_t y_pitch, int64_t y_bstride, const uint16_t* cb, const uint16_t* cr,
                                        int64_t c_pitch, int32_t c_step, int64_t c_bstride, float* dst, int32_t B, int32_t h, int32_t w,
                                        int32_t Hp, int32_t Wp, const float* to_rgb12, int32_t depth, int32_t msb, void* stream) {
     if (!y || !cb || !cr || !dst || !to_rgb12 || !hat_yuv_depth_ok(depth, msb) || !even_ptrs(y, cb, cr) ||
         !hat_yuv_block_ok_n(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h, w, 2))
         return HAT_EINVAL;
-    if (Hp < h || Wp < w || B > 65535 || Hp > 65535) return HAT_EINVAL;
-    if (Hp - h >= h || Wp - w >= w) return HAT_EINVAL;
-    HAT_LAUNCH((yuv420_to_planes_kernel<uint16_t, 1, 1, false>), dim3((Wp + 255) / 256, Hp, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y,
-               (long long)y_pitch, (long long)y_bstride, cb, cr, (long long)c_pitch, (int)c_step, (long long)c_bstride, dst, h, w, Hp, Wp,
-               load_csc(to_rgb12), deep_sample(depth, msb));
-    return hat_check_launch();
+    if (!padded_ok(B, h, w, Hp, Wp)) return HAT_EINVAL;
+    return to_planes(hat_yuv420_surface(y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride, depth, msb), dst, B, h, w, Hp, Wp, to_rgb12, stream);
 }
 
 extern "C" int hat_planes_to_yuv420p16(const float* src, int32_t B, int32_t Hs, int32_t Ws, uint16_t* y, int64_t y_pitch, int64_t y_bstride,
@@ -265,8 +268,5 @@ extern "C" int hat_planes_to_yuv420p16(const float* src, int32_t B, int32_t Hs, 
         !hat_yuv_block_ok_n(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out, 2))
         return HAT_EINVAL;
     if (h_out > Hs || w_out > Ws || B > 65535 || h_out / 2 > 65535) return HAT_EINVAL;
-    HAT_LAUNCH((planes_to_yuv420_kernel<uint16_t, 1, 1, false>), dim3((w_out + 1023) / 1024, h_out / 2, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-               src, Hs, Ws, y, (long long)y_pitch, (long long)y_bstride, cb, cr, (long long)c_pitch, (int)c_step, (long long)c_bstride, w_out,
-               load_csc(from_rgb12), deep_sample(depth, msb));
-    return hat_check_launch();
+    return from_planes(src, B, Hs, Ws, hat_yuv420_surface(y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride, depth, msb), h_out, w_out, from_rgb12, stream);
 }

@@ -52,3 +52,9 @@ static inline bool hat_yuv_surface_ok(const HatYuvSurface* s, int32_t B, int64_t
     if (s->c_pitch < crow || (bps == 2 && (s->c_pitch & 1))) return false;
     return B == 1 || (s->c_bstride >= s->c_pitch * (ch - 1) + crow && !(bps == 2 && (s->c_bstride & 1)));
 }
+
+// the frame block of a 4:2:0 entry as the surface it is: sub_x = sub_y = 1 (the 8-bit entries pass depth 8, msb 0)
+static inline HatYuvSurface hat_yuv420_surface(const void* y, int64_t y_pitch, int64_t y_bstride, const void* cb, const void* cr, int64_t c_pitch,
+                                               int32_t c_step, int64_t c_bstride, int32_t depth, int32_t msb) {
+    return HatYuvSurface{const_cast<void*>(y), y_pitch, y_bstride, const_cast<void*>(cb), const_cast<void*>(cr), c_pitch, c_step, c_bstride, 1, 1, depth, msb};
+}

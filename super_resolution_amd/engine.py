@@ -190,6 +190,56 @@ class _Fwd:
         return tuple(self.w[k].view(-1)[:self.B * gs].view(self.B, gs) for k in ("gstat_l", "gstat_g"))
 
 
+class _Sink:
+    """Where a byte-frame forward ends instead of in fp32 planes: `out`, the caller's result tensor of the (h_out, w_out) top-left
+    pixels, and the two ways to fill it — fused(src, wpk, b8, conv_last's geometry ...), conv_last's row sweep with the conversion
+    as its epilogue (no fp32 image exists), or from_planes(y) of an fp32 image.  Each bumps its engine counter, `kind`_fused_calls
+    or `kind`_planes_calls.  band_refusal: why a row band, which hands its rows over as fp32, cannot end in this sink."""
+    kind = band_refusal = None
+
+    def __init__(self, eng, out, size):
+        self.eng, self.out, self.size = eng, out, size
+
+    def _count(self, how):
+        name = f"{self.kind}_{how}_calls"
+        setattr(self.eng, name, getattr(self.eng, name) + 1)
+
+
+class _U8Sink(_Sink):
+    """out (B,h_out,w_out,3) uint8 by tensor2img's conversion: hat_conv3x3_to_u8 / hat_planes_to_u8."""
+    kind, band_refusal = "u8", "a row band hands its rows over as fp32: the 8-bit output is the unsharded forward's"
+
+    def __init__(self, eng, out, bgr):
+        super().__init__(eng, out, tuple(out.shape[1:3]))
+        self.bgr = bool(bgr)
+
+    def fused(self, src, wpk, b8, **conv):
+        ops.conv3x3_to_u8(src, wpk, b8, self.out, h_out=self.size[0], w_out=self.size[1], bgr=self.bgr, **conv)
+        self._count("fused")
+
+    def from_planes(self, y):
+        ops.planes_to_u8(y, self.out, bgr=self.bgr)
+        self._count("planes")
+
+
+class _YuvSink(_Sink):
+    """out in a layout of yuv.LAYOUTS as its (y, cb, cr) views (ops.yuv_views; sub = (sub_x, sub_y), None: grey), `depth` bits a
+    sample: hat_conv3x3_to_yuv / hat_planes_to_yuv, for the 4:2:0 layouts as for every other."""
+    kind, band_refusal = "yuv", "the 4:2:0 output is the unsharded forward's, and it is one target of three"
+
+    def __init__(self, eng, out, views, from_rgb, *, sub, depth, msb):
+        super().__init__(eng, out, tuple(views[0].shape[1:3]))
+        self.views, self.from_rgb, self.surface = views, from_rgb, dict(sub=sub, depth=depth, msb=msb)
+
+    def fused(self, src, wpk, b8, **conv):
+        ops.conv3x3_to_yuv(src, wpk, b8, *self.views, from_rgb=self.from_rgb, **self.surface, **conv)
+        self._count("fused")
+
+    def from_planes(self, y):
+        ops.planes_to_yuv(y, *self.views, self.from_rgb, **self.surface)
+        self._count("planes")
+
+
 class HATEngine:
     def __init__(self, cfg: dict, state_dict: Dict[str, torch.Tensor], device, dtype: str = "bf16"):
         if cfg.get("upsampler") != "pixelshuffle":
@@ -215,7 +265,7 @@ class HATEngine:
         self._ws_max_bytes = int(float(os.environ.get("HAT_WS_CACHE_GIB", "96")) * 2 ** 30)
         self.ws_allocations = self.fp16_fallbacks = 0
         self.u8_fused_calls = self.u8_planes_calls = 0   # 8-bit forwards that ended in hat_conv3x3_to_u8 / in hat_planes_to_u8
-        self.yuv_fused_calls = self.yuv_planes_calls = 0   # 4:2:0 forwards that ended in hat_conv3x3_to_yuv420 / in hat_planes_to_yuv420
+        self.yuv_fused_calls = self.yuv_planes_calls = 0   # YCbCr forwards that ended in hat_conv3x3_to_yuv / in hat_planes_to_yuv
         self.use_n16 = not self.opt.no_n16
         # FP16 residual rows between the fused HAB tails of a residual group (bf16 path, embed_dim 144; HAT_NO_T16=1: fp32 everywhere)
         self.t16 = not self.opt.no_t16 and self.opt.emu_t16 is None and self.dtype == ops.HAT_BF16 and self.C == 144
@@ -677,6 +727,29 @@ class HATEngine:
                                f"{tuple(out.shape)} {out.dtype} on {out.device}")
         return out
 
+    def _to_sink(self, x, sink, ensemble, one_stream=None):
+        """The forward of the planes x into `sink`, or their ensemble's (2 / 4 / 8: forward_ensemble's fp32 image in the workspace,
+        then sink.from_planes).  Called under the lock; returns sink.out."""
+        if ensemble > 1:
+            B, _, Hp, Wp = x.shape
+            sink.from_planes(self._ensemble(x, ensemble, self._ens_acc(self._workspace(B, Hp, Wp), B, Hp, Wp), one_stream=one_stream))
+            return sink.out
+        return self._forward(x, one_stream=one_stream, sink=sink)
+
+    def _frame_forward(self, B, h, w, fill, make_sink, ensemble, what=None, of="frame"):
+        """What the frame entry points share: (B, h, w) frames reflect-pad to the next window multiple (Hp, Wp) or are refused;
+        fill(x) writes the padded fp32 planes x = ws["x_u8"], the one staging buffer of this shape's workspace; make_sink() checks
+        the caller's `out` and returns the sink; then the forward (or its ensemble) into it."""
+        Hp, Wp = -(-h // self.ws) * self.ws, -(-w // self.ws) * self.ws
+        if Hp - h >= h or Wp - w >= w:
+            raise RuntimeError(f"{what or f'a {h}x{w} frame'} cannot be reflect-padded to {Hp}x{Wp} (window_size {self.ws}): the padding must be "
+                               f"smaller than the {of}")
+        sink = make_sink()
+        with self._lock, torch.cuda.device(self.dev):
+            x = self._ws_buffer(self._workspace(B, Hp, Wp), "x_u8", (B, 3, Hp, Wp))
+            fill(x)
+            return self._to_sink(x, sink, ensemble)
+
     def forward_to_u8(self, x: torch.Tensor, *, crop=None, bgr: bool = False, out=None, one_stream: Optional[bool] = None,
                       ensemble: int = 1) -> torch.Tensor:
         """forward(x) converted on the device as the reference's tensor2img converts it: (B,3,H,W) float in ->
@@ -694,17 +767,7 @@ class HATEngine:
         with self._lock, torch.cuda.device(self.dev):
             if ensemble > 1:
                 self._check_input(x)
-                out = self._u8_out(out, (x.shape[0], ho, wo, 3))
-                return self._ensemble_to_u8(x, ensemble, out, bgr, one_stream=one_stream)
-            return self._forward(x, one_stream=one_stream, u8=(ho, wo, bool(bgr), self._u8_out(out, (x.shape[0], ho, wo, 3))))
-
-    def _ensemble_to_u8(self, x, n, out, bgr, one_stream=None):
-        """The ensembled fp32 image of the padded planes x -> out (B,h_out,w_out,3) uint8, its top-left crop (hat_planes_to_u8)."""
-        B, _, Hp, Wp = x.shape
-        acc = self._ensemble(x, n, self._ens_acc(self._workspace(B, Hp, Wp), B, Hp, Wp), one_stream=one_stream)
-        ops.planes_to_u8(acc, out, bgr=bool(bgr))
-        self.u8_planes_calls += 1
-        return out
+            return self._to_sink(x, _U8Sink(self, self._u8_out(out, (x.shape[0], ho, wo, 3)), bgr), ensemble, one_stream)
 
     def forward_u8(self, frame: torch.Tensor, *, bgr: bool = False, out=None, ensemble: int = 1) -> torch.Tensor:
         """(B,h,w,3) uint8 device frames of any size the reflection allows -> (B,s*h,s*w,3) uint8: float(v) / 255, the
@@ -719,22 +782,10 @@ class HATEngine:
         if not frame.is_cuda or frame.device != self.dev:
             raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
         B, h, w, _ = frame.shape
-        Hp, Wp = -(-h // self.ws) * self.ws, -(-w // self.ws) * self.ws
-        if Hp - h >= h or Wp - w >= w:
-            raise RuntimeError(f"a {h}x{w} frame cannot be reflect-padded to {Hp}x{Wp} (window_size {self.ws}): the padding must be "
-                               f"smaller than the frame")
         if frame.stride(3) != 1 or frame.stride(2) != 3:
             frame = frame.contiguous()
-        with self._lock, torch.cuda.device(self.dev):
-            ws = self._workspace(B, Hp, Wp)
-            if "x_u8" not in ws:     # the padded fp32 input of this shape: allocated once, with the workspace
-                ws["x_u8"] = torch.zeros(B, 3, Hp, Wp, dtype=torch.float32, device=self.dev)
-                ws["bytes"] += ws["x_u8"].numel() * 4
-            ops.u8_to_planes(frame, ws["x_u8"], bgr=bgr)
-            ho, wo = h * self.scale, w * self.scale
-            if ensemble > 1:
-                return self._ensemble_to_u8(ws["x_u8"], ensemble, self._u8_out(out, (B, ho, wo, 3)), bgr)
-            return self._forward(ws["x_u8"], u8=(ho, wo, bool(bgr), self._u8_out(out, (B, ho, wo, 3))))
+        return self._frame_forward(B, h, w, lambda x: ops.u8_to_planes(frame, x, bgr=bgr),
+                                   lambda: _U8Sink(self, self._u8_out(out, (B, h * self.scale, w * self.scale, 3)), bgr), ensemble)
 
     def forward_gt_u8(self, gt: torch.Tensor, *, bgr: bool = False, out=None, ensemble: int = 1) -> torch.Tensor:
         """(B,H,W,3) uint8 device GROUND-TRUTH frames -> the (B, H - H % s, W - W % s, 3) uint8 super-resolution of their own
@@ -756,35 +807,22 @@ class HATEngine:
             gt = gt.contiguous()
         gt = gt[:, :H - H % s, :W - W % s]
         h, w = gt.shape[1] // s, gt.shape[2] // s
-        Hp, Wp = -(-h // self.ws) * self.ws, -(-w // self.ws) * self.ws
-        if h < 1 or w < 1 or Hp - h >= h or Wp - w >= w:
-            raise RuntimeError(f"the {h}x{w} low-resolution image of a {H}x{W} frame cannot be reflect-padded to {Hp}x{Wp} (window_size "
-                               f"{self.ws}): the padding must be smaller than the image")
-        with self._lock, torch.cuda.device(self.dev):
-            ws = self._workspace(B, Hp, Wp)
-            if "x_u8" not in ws:     # the padded fp32 input of this shape, shared with forward_u8
-                ws["x_u8"] = torch.zeros(B, 3, Hp, Wp, dtype=torch.float32, device=self.dev)
-                ws["bytes"] += ws["x_u8"].numel() * 4
-            ops.imresize(gt, 1.0 / s, dst=ws["x_u8"], pad_to=(Hp, Wp), bgr=bgr)
-            ho, wo = h * s, w * s
-            if ensemble > 1:
-                return self._ensemble_to_u8(ws["x_u8"], ensemble, self._u8_out(out, (B, ho, wo, 3)), bgr)
-            return self._forward(ws["x_u8"], u8=(ho, wo, bool(bgr), self._u8_out(out, (B, ho, wo, 3))))
+        return self._frame_forward(B, h, w, lambda x: ops.imresize(gt, 1.0 / s, dst=x, pad_to=tuple(x.shape[2:]), bgr=bgr),
+                                   lambda: _U8Sink(self, self._u8_out(out, (B, h * s, w * s, 3)), bgr), ensemble,
+                                   what=f"the {h}x{w} low-resolution image of a {H}x{W} frame", of="image")
 
     def forward_yuv420(self, frame: torch.Tensor, *, fmt: str = "nv12", to_rgb, from_rgb, out=None, depth: int = 8, out_depth=None,
                        msb=None, ensemble: int = 1) -> torch.Tensor:
-        """(B,3h/2,w) uint8 device frames in the layout `fmt` (yuv.py), any even size the reflection allows -> (B,3sh/2,sw) uint8
-        in the same layout: hat_yuv420_to_planes into this shape's workspace, the forward, the crop and the conversion back (in
-        conv_last's epilogue or hat_planes_to_yuv420).  to_rgb / from_rgb: yuv.csc's matrices (of `depth` / `out_depth`).  out: the
-        caller's result tensor.  depth / out_depth 10, 12, 16: uint16 frames on that side (yuv.py, "Deep samples"; out_depth
-        defaults to depth); msb: MSB-aligned words (default: by the layout).  ensemble 2 / 4 / 8: the padded RGB planes go through
-        forward_ensemble, then hat_planes_to_yuv420 with the crop."""
+        """forward_yuv for the three 4:2:0 layouts of yuv.FORMATS, the same one on both sides: (B,3h/2,w) device frames in the
+        layout `fmt`, h and w even -> (B,3sh/2,sw) in the same layout; msb: the alignment of deep words on both sides (default: by
+        the layout).  It refuses what is no 4:2:0 frame in its own words; everything else is forward_yuv's."""
         self._check_u8()
         ensemble = ops.ensemble_members(ensemble)
         from . import yuv as _yuv
+        _yuv.check_fmt(fmt)
         out_depth = depth if out_depth is None else out_depth
-        in_msb, out_msb = bool(_yuv.container(depth, fmt, msb)[3]), bool(_yuv.container(out_depth, fmt, msb)[3])   # (checks depths and fmt)
-        in_dt, out_dt = (torch.uint8 if d == 8 else torch.uint16 for d in (depth, out_depth))
+        _yuv.container(depth, fmt, msb), _yuv.container(out_depth, fmt, msb)   # (checks the depths)
+        in_dt = torch.uint8 if depth == 8 else torch.uint16
         if not isinstance(frame, torch.Tensor) or frame.dtype not in (torch.uint8, torch.uint16):
             raise TypeError(f"expected (B,3h/2,w) uint8 frames, got {getattr(frame, 'dtype', type(frame))}")
         if frame.dtype != in_dt:
@@ -793,43 +831,19 @@ class HATEngine:
             raise RuntimeError(f"expected (B,3h/2,w) uint8 frames, got {tuple(frame.shape)}")
         if not frame.is_cuda or frame.device != self.dev:
             raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
-        h, w = _yuv.frame_size(frame.shape)
-        B, s = frame.shape[0], self.scale
-        Hp, Wp = -(-h // self.ws) * self.ws, -(-w // self.ws) * self.ws
-        if Hp - h >= h or Wp - w >= w:
-            raise RuntimeError(f"a {h}x{w} frame cannot be reflect-padded to {Hp}x{Wp} (window_size {self.ws}): the padding must be "
-                               f"smaller than the frame")
-        if frame.stride(2) != 1 or frame.stride(1) != w:
-            frame = frame.contiguous() if in_dt is torch.uint8 else frame.view(torch.int16).contiguous().view(torch.uint16)
-        shape = (B,) + _yuv.frame_shape(s * h, s * w)
-        if out is None:
-            out = torch.empty(shape, dtype=out_dt, device=self.dev)
-        elif not isinstance(out, torch.Tensor) or out.dtype != out_dt or tuple(out.shape) != shape or out.device != self.dev \
-                or out.stride(2) != 1 or out.stride(1) != s * w:
-            raise RuntimeError(f"out must be a {shape} {str(out_dt)[6:]} tensor on {self.dev} with packed rows, got "
-                               f"{tuple(out.shape)} {out.dtype} on {out.device}")
-        src, dst = ops.yuv420_views(frame, fmt), ops.yuv420_views(out, fmt)
-        with self._lock, torch.cuda.device(self.dev):
-            ws = self._workspace(B, Hp, Wp)
-            if "x_u8" not in ws:     # the padded fp32 input of this shape, shared with forward_u8
-                ws["x_u8"] = torch.zeros(B, 3, Hp, Wp, dtype=torch.float32, device=self.dev)
-                ws["bytes"] += ws["x_u8"].numel() * 4
-            ops.yuv420_to_planes(*src, ws["x_u8"], to_rgb, depth=depth, msb=in_msb)
-            if ensemble > 1:
-                acc = self._ensemble(ws["x_u8"], ensemble, self._ens_acc(ws, B, Hp, Wp))
-                ops.planes_to_yuv420(acc, *dst, from_rgb, depth=out_depth, msb=out_msb)
-                self.yuv_planes_calls += 1
-                return out
-            self._forward(ws["x_u8"], yuv=(dst, from_rgb, out, out_depth, out_msb))
-        return out
+        _yuv.frame_size(frame.shape)
+        return self.forward_yuv(frame, fmt=fmt, out_fmt=fmt, to_rgb=to_rgb, from_rgb=from_rgb, out=out, depth=depth, out_depth=out_depth,
+                                msb=msb, out_msb=msb, ensemble=ensemble)
 
     def forward_yuv(self, frame: torch.Tensor, *, fmt: str, out_fmt=None, to_rgb, from_rgb, out=None, depth: int = 8, out_depth=None,
                     msb=None, out_msb=None, ensemble: int = 1) -> torch.Tensor:
-        """forward_yuv420 for every layout of yuv.LAYOUTS on either side: (B,rows,w) device frames in the layout `fmt` -> the frames
+        """(B,rows,w) device frames in the layout `fmt` of yuv.LAYOUTS, any size the layout and the reflection allow -> the frames
         of the s-times larger image in the layout `out_fmt` (default: fmt), any subsampling or grey to any other:
         hat_yuv_to_planes into this shape's workspace, the forward, the crop and the conversion back (in conv_last's epilogue,
-        hat_conv3x3_to_yuv, or hat_planes_to_yuv).  msb / out_msb: the alignment of deep words on each side (default: by the
-        layout); every other keyword as forward_yuv420 takes it."""
+        hat_conv3x3_to_yuv, or hat_planes_to_yuv).  to_rgb / from_rgb: yuv.csc's matrices (of `depth` / `out_depth`).  out: the
+        caller's result tensor.  depth / out_depth 10, 12, 16: uint16 frames on that side (yuv.py, "Deep samples"; out_depth
+        defaults to depth); msb / out_msb: MSB-aligned words on that side (default: by the layout).  ensemble 2 / 4 / 8: the
+        padded RGB planes go through forward_ensemble, then hat_planes_to_yuv with the crop."""
         self._check_u8()
         ensemble = ops.ensemble_members(ensemble)
         from . import yuv as _yuv
@@ -847,34 +861,25 @@ class HATEngine:
             raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
         h, w = _yuv.frame_size_fmt(frame.shape, fmt)
         B, s = frame.shape[0], self.scale
-        Hp, Wp = -(-h // self.ws) * self.ws, -(-w // self.ws) * self.ws
-        if Hp - h >= h or Wp - w >= w:
-            raise RuntimeError(f"a {h}x{w} frame cannot be reflect-padded to {Hp}x{Wp} (window_size {self.ws}): the padding must be "
-                               f"smaller than the frame")
-        if frame.stride(2) != 1 or frame.stride(1) != w:
-            frame = frame.contiguous() if in_dt is torch.uint8 else frame.view(torch.int16).contiguous().view(torch.uint16)
-        shape = (B,) + _yuv.frame_shape_fmt(s * h, s * w, out_fmt)
-        if out is None:
-            out = torch.empty(shape, dtype=out_dt, device=self.dev)
-        elif not isinstance(out, torch.Tensor) or out.dtype != out_dt or tuple(out.shape) != shape or out.device != self.dev \
-                or out.stride(2) != 1 or out.stride(1) != s * w:
-            raise RuntimeError(f"out must be a {shape} {str(out_dt)[6:]} tensor on {self.dev} with packed rows, got "
-                               f"{tuple(out.shape)} {out.dtype} on {out.device}")
         sub = lambda f: None if _yuv.LAYOUTS[f][0] is None else _yuv.LAYOUTS[f][:2]
-        src, dst = ops.yuv_views(frame, fmt), ops.yuv_views(out, out_fmt)
-        with self._lock, torch.cuda.device(self.dev):
-            ws = self._workspace(B, Hp, Wp)
-            if "x_u8" not in ws:     # the padded fp32 input of this shape, shared with forward_u8
-                ws["x_u8"] = torch.zeros(B, 3, Hp, Wp, dtype=torch.float32, device=self.dev)
-                ws["bytes"] += ws["x_u8"].numel() * 4
-            ops.yuv_to_planes(*src, ws["x_u8"], to_rgb, sub=sub(fmt), depth=depth, msb=in_msb)
-            if ensemble > 1:
-                acc = self._ensemble(ws["x_u8"], ensemble, self._ens_acc(ws, B, Hp, Wp))
-                ops.planes_to_yuv(acc, *dst, from_rgb, sub=sub(out_fmt), depth=out_depth, msb=out_msb)
-                self.yuv_planes_calls += 1
-                return out
-            self._forward(ws["x_u8"], yuv=(dst, from_rgb, out, out_depth, out_msb, sub(out_fmt)))
-        return out
+
+        def fill(x):
+            f = frame
+            if f.stride(2) != 1 or f.stride(1) != w:
+                f = f.contiguous() if in_dt is torch.uint8 else f.view(torch.int16).contiguous().view(torch.uint16)
+            ops.yuv_to_planes(*ops.yuv_views(f, fmt), x, to_rgb, sub=sub(fmt), depth=depth, msb=in_msb)
+
+        def make_sink():
+            shape, dst = (B,) + _yuv.frame_shape_fmt(s * h, s * w, out_fmt), out
+            if dst is None:
+                dst = torch.empty(shape, dtype=out_dt, device=self.dev)
+            elif not isinstance(dst, torch.Tensor) or dst.dtype != out_dt or tuple(dst.shape) != shape or dst.device != self.dev \
+                    or dst.stride(2) != 1 or dst.stride(1) != s * w:
+                raise RuntimeError(f"out must be a {shape} {str(out_dt)[6:]} tensor on {self.dev} with packed rows, got "
+                                   f"{tuple(dst.shape)} {dst.dtype} on {dst.device}")
+            return _YuvSink(self, dst, ops.yuv_views(dst, out_fmt), from_rgb, sub=sub(out_fmt), depth=out_depth, msb=out_msb)
+
+        return self._frame_forward(B, h, w, fill, make_sink, ensemble)
 
     def ocab_only(self, t: torch.Tensor, group: int, H: int, W: int) -> torch.Tensor:
         """Run only the OCAB of residual group `group` on tokens t (B, H*W, C) fp32 -> (B, H*W, C) fp32 (used by the tests)."""
@@ -882,24 +887,22 @@ class HATEngine:
         with self._lock, torch.cuda.device(self.dev):
             return self._forward(x, only_ocab=(t.to(self.dev, torch.float32).contiguous(), group))
 
-    def _forward(self, x: torch.Tensor, only_ocab=None, one_stream=None, u8=None, yuv=None) -> torch.Tensor:
-        gen = self._forward_gen(x, only_ocab=only_ocab, one_stream=one_stream, u8=u8, yuv=yuv)
+    def _forward(self, x: torch.Tensor, only_ocab=None, one_stream=None, sink=None) -> torch.Tensor:
+        gen = self._forward_gen(x, only_ocab=only_ocab, one_stream=one_stream, sink=sink)
         try:
             req = next(gen)
         except StopIteration as done:
             return done.value
         raise RuntimeError(f"the unsharded forward must not reach an exchange point (got {req[0]!r})")
 
-    def _forward_gen(self, x: torch.Tensor, only_ocab=None, band=None, one_stream=None, u8=None, yuv=None):
+    def _forward_gen(self, x: torch.Tensor, only_ocab=None, band=None, one_stream=None, sink=None):
         """The forward as a generator.  Unsharded (band=None) it never yields and returns the output.  For one ROW BAND of a
         sharded frame (band: tile_parallel.Band, x = the band's rows + ghost rows of the LR frame) it yields at
         every point where bands must exchange: ("halo", [(tensor, depth) ...]) — refresh `depth` ghost rows above and below
         from the neighbours that own them — and ("reduce", local, glob, n) — glob[:, :n] = sum over bands of local[:, :n] (the
         global average pools of ECA, hat_arch.py:69-73, and of the ESC dynamic kernel, esc_arch.py:96,121) — and returns the
         band's output rows (ghost rows included; the driver keeps the owned ones).
-        u8 = (h_out, w_out, bgr, out): the unsharded forward fills and returns out, (B,h_out,w_out,3) uint8 (forward_to_u8).
-        yuv = ((y, cb, cr) views, from_rgb, out, depth, msb): it fills the views of a 4:2:0 frame and returns out (forward_yuv420);
-        with a sixth item, the subsampling (sub_x, sub_y) or None for grey, the views are that surface's (forward_yuv)."""
+        sink (a _Sink; the unsharded forward only): the forward fills and returns sink.out, bytes, instead of fp32 planes."""
         self._check_input(x)
         B, _, H, W = x.shape
         x = x.to(torch.float32).contiguous()
@@ -912,16 +915,12 @@ class HATEngine:
             w["tB"].copy_(t_in.reshape(B, H * W, self.C))
             f.t = w["tB"]
             return (yield from self._ocab(f, self.layers[gidx], as_conv_input=False)).clone()
-        if yuv is not None:
-            if band is not None or u8 is not None:
-                raise RuntimeError("the 4:2:0 output is the unsharded forward's, and it is one target of three")
-            y = yuv[2]
-        elif u8 is None:
+        if sink is None:
             y = torch.empty(B, self.cfg["in_chans"], H * self.scale, W * self.scale, dtype=torch.float32, device=self.dev)
+        elif band is not None:
+            raise RuntimeError(sink.band_refusal)
         else:
-            if band is not None:
-                raise RuntimeError("a row band hands its rows over as fp32: the 8-bit output is the unsharded forward's")
-            y = u8[3]
+            y = sink.out
         self._head(f, x)
         for G in self.layers:
             for hb in G.habs:   # HAB                                                            :217-238
@@ -930,7 +929,7 @@ class HATEngine:
             tout = yield from self._ocab(f, G, as_conv_input=G.to_conv)
             yield from self._group_end(f, G, tout)
         yield from self._body_end(f)
-        self._upsample(f, y, u8, yuv)
+        self._upsample(f, y, sink)
         return y
 
     # ------------------------------------------------------------------------------------------ stage steps
@@ -1269,38 +1268,20 @@ class HATEngine:
         ops.conv(self.conv_after_body, w["n"], w["c2"], **f.geo, ldx=ldc, ldo=ldc, r1=w["f0"], ldr1=C)
         ops.conv(self.conv_before_up, w["c2"], w["fb"], **f.geo, ldx=ldc, ldo=64, act=ACT_LRELU)
 
-    def _upsample(self, f: _Fwd, y, u8=None, yuv=None):
+    def _upsample(self, f: _Fwd, y, sink=None):
         """conv + PixelShuffle per stage; conv_last ; / img_range + mean                     :593-605, :856-858
-        u8 = (h_out, w_out, bgr, y): y is (B,h_out,w_out,3) uint8 — conv_last converts in its epilogue (hat_conv3x3_to_u8) where
-        the row-sweep kernel runs, else it writes fp32 planes as always and hat_planes_to_u8 converts and crops them.
-        yuv = ((y, cb, cr), from_rgb, out, depth, msb): the third target, 4:2:0 views of `out`, by the same rule:
-        hat_conv3x3_to_yuv420 where the row-sweep kernel runs, else fp32 planes and hat_planes_to_yuv420.  With uint16 views
-        (depth 10 / 12 / 16) it is the fourth target, by the same rule again: hat_conv3x3_to_yuv420p16, else fp32 planes and
-        hat_planes_to_yuv420p16; the two yuv counters count both widths.  yuv with a sixth item (the output surface's subsampling,
-        None: grey): the same rule with hat_conv3x3_to_yuv / hat_planes_to_yuv, for every output format, on the same counters."""
+        Without a sink conv_last writes the fp32 planes y.  With one (then y is sink.out) it converts in its epilogue, sink.fused,
+        where the row-sweep kernel runs with three output channels; else it writes fp32 planes of its own as always and
+        sink.from_planes converts and crops them."""
         src, h, wd, dt = f.w["fb"], f.H, f.W, f.dt
         for (pw, rr), dst in zip(self.ups, f.w["ups"]):
             ops.conv(pw, src, dst, B=f.B, H=h, W=wd, dtype=dt, ldx=64, ldo=64, out_mode=O_PIXSHUF_T, ps_r=rr)
             src, h, wd = dst, h * rr, wd * rr
         r = float(self.cfg.get("img_range", 1.0))
-        if u8 is not None:
+        if sink is not None:
             if self.u8_fused and wd % 16 == 0:
                 wpk, b8, _ = self.conv_last_sweep
-                ops.conv3x3_to_u8(src, wpk, b8, y, B=f.B, H=h, W=wd, C_=64, ldx=64, h_out=u8[0], w_out=u8[1], out_scale=1.0 / r,
-                                  mean=self._mean(), bgr=u8[2], dtype=dt)
-                self.u8_fused_calls += 1
-                return
-            y8, y = y, torch.empty(f.B, 3, h, wd, dtype=torch.float32, device=self.dev)
-        if yuv is not None:
-            if self.u8_fused and wd % 16 == 0:
-                wpk, b8, _ = self.conv_last_sweep
-                if len(yuv) > 5:
-                    ops.conv3x3_to_yuv(src, wpk, b8, *yuv[0], sub=yuv[5], B=f.B, H=h, W=wd, C_=64, ldx=64, out_scale=1.0 / r, mean=self._mean(),
-                                       from_rgb=yuv[1], dtype=dt, depth=yuv[3], msb=yuv[4])
-                else:
-                    ops.conv3x3_to_yuv420(src, wpk, b8, *yuv[0], B=f.B, H=h, W=wd, C_=64, ldx=64, out_scale=1.0 / r, mean=self._mean(),
-                                          from_rgb=yuv[1], dtype=dt, depth=yuv[3], msb=yuv[4])
-                self.yuv_fused_calls += 1
+                sink.fused(src, wpk, b8, B=f.B, H=h, W=wd, C_=64, ldx=64, out_scale=1.0 / r, mean=self._mean(), dtype=dt)
                 return
             y = torch.empty(f.B, 3, h, wd, dtype=torch.float32, device=self.dev)
         if self.conv_last_sweep is not None and wd % 16 == 0:
@@ -1310,12 +1291,5 @@ class HATEngine:
         else:
             ops.conv(self.conv_last, src, y, B=f.B, H=h, W=wd, dtype=dt, ldx=64, ldo=0, out_mode=O_NCHW_F32,
                      out_scale=1.0 / r, mean=self._mean())
-        if u8 is not None:
-            ops.planes_to_u8(y, y8, bgr=u8[2])
-            self.u8_planes_calls += 1
-        if yuv is not None:
-            if len(yuv) > 5:
-                ops.planes_to_yuv(y, *yuv[0], yuv[1], sub=yuv[5], depth=yuv[3], msb=yuv[4])
-            else:
-                ops.planes_to_yuv420(y, *yuv[0], yuv[1], depth=yuv[3], msb=yuv[4])
-            self.yuv_planes_calls += 1
+        if sink is not None:
+            sink.from_planes(y)

@@ -468,19 +468,10 @@ def imresize(src, scale: float, *, antialiasing: bool = True, dst=None, to: str 
 
 
 def yuv420_views(frame, fmt: str = "nv12"):
-    """frame (B, 3h/2, w) uint8 (uint16: deep samples) in the standard layout of `fmt` (rows w samples apart, samples anywhere) ->
-    views y (B,h,w), cb, cr (B,h/2,w/2): the torch twin of yuv.split.  The chroma views step 2 samples for nv12 / nv21 and 1 for i420."""
+    """yuv_views for the three 4:2:0 layouts of yuv.FORMATS: frame (B, 3h/2, w) -> views y (B,h,w), cb, cr (B,h/2,w/2), the torch
+    twin of yuv.split.  The chroma views step 2 samples for nv12 / nv21 and 1 for i420."""
     from . import yuv as _yuv
-    _yuv.check_fmt(fmt)
-    if frame.dim() != 3 or frame.dtype not in (torch.uint8, torch.uint16) or frame.stride(2) != 1 or frame.stride(1) != frame.shape[2]:
-        raise RuntimeError(f"expected (B,3h/2,w) uint8 frames with packed rows, got {tuple(frame.shape)} {frame.dtype} strides {frame.stride()}")
-    h, w = _yuv.frame_size(frame.shape)
-    B, y, c = frame.shape[0], frame[:, :h], frame[:, h:]
-    if fmt == "i420":
-        off, n = frame.storage_offset() + h * w, (h // 2) * (w // 2)
-        return y, frame.as_strided((B, h // 2, w // 2), (frame.stride(0), w // 2, 1), off), \
-            frame.as_strided((B, h // 2, w // 2), (frame.stride(0), w // 2, 1), off + n)
-    return (y, c[:, :, 0::2], c[:, :, 1::2]) if fmt == "nv12" else (y, c[:, :, 1::2], c[:, :, 0::2])
+    return yuv_views(frame, _yuv.check_fmt(fmt))
 
 
 def _yuv_block(y, cb, cr, what: str):
@@ -516,6 +507,23 @@ def _deep_entry(entry: str, deep):
     return (entry.format("p16"), "<u16>", f"p{deep[0]}") if deep else (entry.format(""), "", "")
 
 
+def _planes_dst(what: str, dst, y, contiguous: bool = False):
+    """dst holds the padded fp32 RGB planes of the frames whose Y view is y (B,h,w)."""
+    B, h, w = y.shape
+    if dst.dtype != torch.float32 or dst.dim() != 4 or dst.shape[0] != B or dst.shape[1] != 3 or dst.shape[2] < h or dst.shape[3] < w \
+            or dst.device != y.device or (contiguous and not dst.is_contiguous()):
+        raise RuntimeError(f"{what} needs a {'contiguous ' if contiguous else ''}(B,3,Hp>=h,Wp>=w) fp32 destination on {y.device}, got "
+                           f"{tuple(dst.shape)} {dst.dtype} on {dst.device} for frames {tuple(y.shape)}")
+
+
+def _planes_src(what: str, src, y, contiguous: bool = False):
+    """src holds fp32 RGB planes for the frames whose Y view is y (the kernel's own checks see that they are large enough)."""
+    if src.dim() != 4 or src.shape[0] != y.shape[0] or src.shape[1] != 3 or src.dtype != torch.float32 or src.device != y.device \
+            or (contiguous and not src.is_contiguous()):
+        raise RuntimeError(f"{what} needs {'contiguous ' if contiguous else ''}(B,3,Hs,Ws) fp32 planes on {y.device}, got {tuple(src.shape)} "
+                           f"{src.dtype} on {src.device}")
+
+
 def _f12(m):
     m = [float(v) for v in m]
     if len(m) != 12:
@@ -531,10 +539,7 @@ def yuv420_to_planes(y, cb, cr, dst, to_rgb, *, depth=None, msb=False):
     blk = _yuv_block(y, cb, cr, "yuv420_to_planes")
     deep = _deep_args(y, depth, msb, "yuv420_to_planes")
     B, h, w = y.shape
-    if dst.dtype != torch.float32 or dst.dim() != 4 or dst.shape[0] != B or dst.shape[1] != 3 or dst.shape[2] < h or dst.shape[3] < w \
-            or dst.device != y.device:
-        raise RuntimeError(f"yuv420_to_planes needs a (B,3,Hp>=h,Wp>=w) fp32 destination on {y.device}, got {tuple(dst.shape)} {dst.dtype} on "
-                           f"{dst.device} for frames {tuple(y.shape)}")
+    _planes_dst("yuv420_to_planes", dst, y)
     m = _f12(to_rgb)
     entry, u16, p = _deep_entry("hat_yuv420{}_to_planes", deep)
     _timed("yuv420_to_planes_kernel" + u16, 0.0, lambda: _lib.check(
@@ -549,8 +554,7 @@ def planes_to_yuv420(src, y, cb, cr, from_rgb, *, depth=None, msb=False):
     blk = _yuv_block(y, cb, cr, "planes_to_yuv420")
     deep = _deep_args(y, depth, msb, "planes_to_yuv420")
     B, h, w = y.shape
-    if src.dim() != 4 or src.shape[0] != B or src.shape[1] != 3 or src.dtype != torch.float32 or src.device != y.device:
-        raise RuntimeError(f"planes_to_yuv420 needs (B,3,Hs,Ws) fp32 planes on {y.device}, got {tuple(src.shape)} {src.dtype} on {src.device}")
+    _planes_src("planes_to_yuv420", src, y)
     m = _f12(from_rgb)
     entry, u16, p = _deep_entry("hat_planes_to_yuv420{}", deep)
     _timed("planes_to_yuv420_kernel" + u16, 0.0, lambda: _lib.check(
@@ -629,10 +633,7 @@ def yuv_to_planes(y, cb, cr, dst, to_rgb, *, sub, depth: int = 8, msb=False):
     lib = _lib.load()
     surf = yuv_surface(y, cb, cr, sub=sub, depth=depth, msb=msb, what="yuv_to_planes")
     B, h, w = y.shape
-    if dst.dtype != torch.float32 or dst.dim() != 4 or dst.shape[0] != B or dst.shape[1] != 3 or dst.shape[2] < h or dst.shape[3] < w \
-            or dst.device != y.device or not dst.is_contiguous():
-        raise RuntimeError(f"yuv_to_planes needs a contiguous (B,3,Hp>=h,Wp>=w) fp32 destination on {y.device}, got {tuple(dst.shape)} "
-                           f"{dst.dtype} on {dst.device} for frames {tuple(y.shape)}")
+    _planes_dst("yuv_to_planes", dst, y, contiguous=True)
     m, name = _f12(to_rgb), _sub_name(sub, depth)
     _timed(f"yuv_to_planes_kernel<{name}>", 0.0, lambda: _lib.check(
         lib.hat_yuv_to_planes(C.byref(surf), _ptr(dst), B, h, w, dst.shape[2], dst.shape[3], m, _stream()), "hat_yuv_to_planes"),
@@ -645,8 +646,7 @@ def planes_to_yuv(src, y, cb, cr, from_rgb, *, sub, depth: int = 8, msb=False):
     lib = _lib.load()
     surf = yuv_surface(y, cb, cr, sub=sub, depth=depth, msb=msb, what="planes_to_yuv")
     B, h, w = y.shape
-    if src.dim() != 4 or src.shape[0] != B or src.shape[1] != 3 or src.dtype != torch.float32 or src.device != y.device or not src.is_contiguous():
-        raise RuntimeError(f"planes_to_yuv needs contiguous (B,3,Hs,Ws) fp32 planes on {y.device}, got {tuple(src.shape)} {src.dtype} on {src.device}")
+    _planes_src("planes_to_yuv", src, y, contiguous=True)
     m, name = _f12(from_rgb), _sub_name(sub, depth)
     _timed(f"planes_to_yuv_kernel<{name}>", 0.0, lambda: _lib.check(
         lib.hat_planes_to_yuv(_ptr(src), B, src.shape[2], src.shape[3], C.byref(surf), h, w, m, _stream()), "hat_planes_to_yuv"),

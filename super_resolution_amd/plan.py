@@ -225,6 +225,17 @@ class Plan:
         _lib.check(self._lib.hat_plan_forward_u8(self._h, src.data_ptr(), src.stride(1), h, w, dst.data_ptr(), dst.stride(1), int(bgr), stream),
                    "hat_plan_forward_u8")
 
+    def _yuv_args(self, what, src, dst, size, shape, matrix, full_range, depth, out_depth):
+        """What the YCbCr forwards start with: (h, w) = size(src.shape) of the source frames, the refusal of a dst that is not
+        shape(s h, s w) frames of the plan's batch, and the two colour matrices of the depths as the C side takes them."""
+        from . import ops, yuv
+        to_rgb, from_rgb = yuv.csc(matrix, full_range, depth)[0], yuv.csc(matrix, full_range, out_depth)[1]
+        h, w = size(src.shape)
+        s = self.dims[4]
+        if src.shape[0] != self.dims[0] or tuple(dst.shape) != (self.dims[0],) + shape(s * h, s * w):
+            raise RuntimeError(f"{what}: src {tuple(src.shape)} / dst {tuple(dst.shape)} do not match a plan of batch {self.dims[0]}, scale {s}")
+        return h, w, ops._f12(to_rgb), ops._f12(from_rgb)
+
     def forward_yuv420(self, src: torch.Tensor, dst: torch.Tensor, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False,
                        depth: int = 8, out_depth=None, msb=None, stream: int = 0):
         """hat_plan_forward_yuv420: src (B,3h/2,w) uint8 device frames in the layout `fmt` with h <= H, w <= W of the plan
@@ -233,25 +244,20 @@ class Plan:
         deep side): hat_plan_forward_yuv420_deep."""
         from . import ops, yuv
         out_depth = depth if out_depth is None else out_depth
-        to_rgb, from_rgb = yuv.csc(matrix, full_range, depth)[0], yuv.csc(matrix, full_range, out_depth)[1]
-        h, w = yuv.frame_size(src.shape)
-        s = self.dims[4]
-        if src.shape[0] != self.dims[0] or tuple(dst.shape) != (self.dims[0],) + yuv.frame_shape(s * h, s * w):
-            raise RuntimeError(f"forward_yuv420: src {tuple(src.shape)} / dst {tuple(dst.shape)} do not match a plan of batch {self.dims[0]}, scale {s}")
+        h, w, to_rgb, from_rgb = self._yuv_args("forward_yuv420", src, dst, yuv.frame_size, yuv.frame_shape, matrix, full_range, depth, out_depth)
         sb = ops._yuv_block(*ops.yuv420_views(src, fmt), "forward_yuv420")
         db = ops._yuv_block(*ops.yuv420_views(dst, fmt), "forward_yuv420")
         if depth == 8 and out_depth == 8:
             if src.dtype != torch.uint8 or dst.dtype != torch.uint8:
                 raise TypeError(f"forward_yuv420: 8-bit frames are uint8 tensors, got {src.dtype} / {dst.dtype}")
-            _lib.check(self._lib.hat_plan_forward_yuv420(self._h, *sb, h, w, *db, ops._f12(to_rgb), ops._f12(from_rgb), stream),
-                       "hat_plan_forward_yuv420")
+            _lib.check(self._lib.hat_plan_forward_yuv420(self._h, *sb, h, w, *db, to_rgb, from_rgb, stream), "hat_plan_forward_yuv420")
             return
         for t, d in ((src, depth), (dst, out_depth)):
             if t.dtype != (torch.uint8 if d == 8 else torch.uint16):
                 raise TypeError(f"forward_yuv420: depth {d} needs a {'uint8' if d == 8 else 'uint16'} tensor, got {t.dtype}")
         sm, dm = int(bool(yuv.container(depth, fmt, msb)[3])), int(bool(yuv.container(out_depth, fmt, msb)[3]))
-        _lib.check(self._lib.hat_plan_forward_yuv420_deep(self._h, *sb, depth, sm, h, w, *db, out_depth, dm, ops._f12(to_rgb), ops._f12(from_rgb),
-                                                          stream), "hat_plan_forward_yuv420_deep")
+        _lib.check(self._lib.hat_plan_forward_yuv420_deep(self._h, *sb, depth, sm, h, w, *db, out_depth, dm, to_rgb, from_rgb, stream),
+                   "hat_plan_forward_yuv420_deep")
 
     def forward_yuv(self, src: torch.Tensor, dst: torch.Tensor, *, fmt: str, out_fmt=None, matrix: str = "bt601", full_range: bool = False,
                     depth: int = 8, out_depth=None, msb=None, out_msb=None, stream: int = 0):
@@ -260,17 +266,13 @@ class Plan:
         from . import ops, yuv
         out_fmt = fmt if out_fmt is None else out_fmt
         out_depth = depth if out_depth is None else out_depth
-        to_rgb, from_rgb = yuv.csc(matrix, full_range, depth)[0], yuv.csc(matrix, full_range, out_depth)[1]
-        h, w = yuv.frame_size_fmt(src.shape, fmt)
-        s = self.dims[4]
-        if src.shape[0] != self.dims[0] or tuple(dst.shape) != (self.dims[0],) + yuv.frame_shape_fmt(s * h, s * w, out_fmt):
-            raise RuntimeError(f"forward_yuv: src {tuple(src.shape)} / dst {tuple(dst.shape)} do not match a plan of batch {self.dims[0]}, scale {s}")
+        h, w, to_rgb, from_rgb = self._yuv_args("forward_yuv", src, dst, lambda shape: yuv.frame_size_fmt(shape, fmt),
+                                                lambda ho, wo: yuv.frame_shape_fmt(ho, wo, out_fmt), matrix, full_range, depth, out_depth)
         sub = lambda f: None if yuv.LAYOUTS[f][0] is None else yuv.LAYOUTS[f][:2]
         sv, dv = ops.yuv_views(src, fmt), ops.yuv_views(dst, out_fmt)     # (kept alive: the surfaces hold raw pointers)
         ss = ops.yuv_surface(*sv, sub=sub(fmt), depth=depth, msb=yuv.container(depth, fmt, msb)[3], what="forward_yuv")
         ds = ops.yuv_surface(*dv, sub=sub(out_fmt), depth=out_depth, msb=yuv.container(out_depth, out_fmt, out_msb)[3], what="forward_yuv")
-        _lib.check(self._lib.hat_plan_forward_yuv(self._h, C.byref(ss), C.byref(ds), h, w, ops._f12(to_rgb), ops._f12(from_rgb), stream),
-                   "hat_plan_forward_yuv")
+        _lib.check(self._lib.hat_plan_forward_yuv(self._h, C.byref(ss), C.byref(ds), h, w, to_rgb, from_rgb, stream), "hat_plan_forward_yuv")
 
     def close(self):
         if self._h:

@@ -318,3 +318,23 @@ def test_c_example_compiles_and_links(lib, tmp_path):
                        capture_output=True, text=True)
     assert r.returncode == 0 and "warning" not in r.stderr, r.stderr[-2000:]
     assert exe.exists()
+
+
+@pytest.mark.parametrize("dtype", ["uint8", "uint16"])
+@pytest.mark.parametrize("fmt", yuv.FORMATS)
+def test_yuv420_views_are_yuv_views(fmt, dtype):
+    """ops.yuv420_views is ops.yuv_views for the 4:2:0 layouts: the same pointers, shapes and strides (a batch stride larger than a
+    frame and a storage offset included); it still refuses every other layout."""
+    import torch
+    from super_resolution_amd import ops
+    B, h, w = 2, 6, 10
+    rows = yuv.frame_shape(h, w)[0]
+    f = torch.zeros(B, rows + 3, w, dtype=torch.uint8) if dtype == "uint8" else torch.zeros(B, rows + 3, w, dtype=torch.int16).view(torch.uint16)
+    f = f[:, 1:1 + rows]
+    a, b = ops.yuv420_views(f, fmt), ops.yuv_views(f, fmt)
+    step = 1 if fmt == "i420" else 2
+    for va, vb, shape in zip(a, b, ((B, h, w), (B, h // 2, w // 2), (B, h // 2, w // 2))):
+        assert va.data_ptr() == vb.data_ptr() and tuple(va.shape) == tuple(vb.shape) == shape and va.stride() == vb.stride()
+    assert a[1].stride(2) == a[2].stride(2) == step and a[1].data_ptr() != a[2].data_ptr()
+    with pytest.raises(RuntimeError, match="format"):
+        ops.yuv420_views(f, "i444")
