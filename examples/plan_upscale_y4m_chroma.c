@@ -4,12 +4,15 @@
  *   python -m super_resolution_amd.plan -opt options/test/HAT-S_SRx4.yml --shape 1 720 1280 -o hats_720p.hatplan   (once)
  *   gcc examples/plan_upscale_y4m_chroma.c -Iinclude -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -Lsuper_resolution_amd -lhat_mi355x \
  *       -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$PWD/super_resolution_amd -o plan_upscale_y4m_chroma
- *   ./plan_upscale_y4m_chroma hats_720p.hatplan in.y4m out.y4m [420|422|444|mono [out_depth]]
+ *   ./plan_upscale_y4m_chroma hats_720p.hatplan in.y4m out.y4m [420|422|444|mono [out_depth]] [--chroma-loc center|left|topleft]
  *
  * Input: C420 (jpeg, mpeg2, paldv, or no C token), C422, C444, Cmono and their deep forms C420p10 / C422p12 / C444p16 / Cmono10 ...
  * (little-endian 16-bit words, the code LSB-aligned).  The third argument is the output's subsampling (default: the input's), the
  * fourth its sample width (default: the input's): `444` on a 4:2:0 file keeps all of the network's chroma.  One HatYuvSurface
  * describes each side and hat_plan_forward_yuv converts on the device with the BT.601 limited-range matrices below.  The frames
+ * --chroma-loc names the chroma siting of both sides (include/hat_mi355x.h, "Chroma siting"): center, the default, is this example as
+ * it always was; left (MPEG-2, H.264, HEVC, AV1; all standard 4:2:2) and topleft (BT.2020) go through hat_plan_forward_yuv_sited,
+ * and an 8-bit 4:2:0 output then says C420mpeg2 / C420paldv.  The frames
  * may be smaller than the plan's shape (down to just over half of it on each side).  The plan must be recorded for batch 1.  Only
  * the C ABI of include/hat_mi355x.h and the HIP runtime are used.
  */
@@ -66,7 +69,20 @@ static HatYuvSurface surface(uint8_t* base, int sub, int depth, long h, long w) 
 }
 
 int main(int argc, char** argv) {
-    if (argc < 4) { fprintf(stderr, "usage: %s net.hatplan in.y4m out.y4m [420|422|444|mono [out_depth]]\n", argv[0]); return 2; }
+    static const char* const LOCS[3] = {"center", "left", "topleft"};
+    static const char* const LOC_TOKENS[3] = {"C420jpeg", "C420mpeg2", "C420paldv"};
+    int siting = HAT_SITING_CENTER;
+    for (int i = 1; i < argc; ++i) {   /* --chroma-loc <name> may stand anywhere; it is taken out of the positional arguments */
+        if (strcmp(argv[i], "--chroma-loc")) continue;
+        for (siting = 0; i + 1 < argc && siting < 3 && strcmp(argv[i + 1], LOCS[siting]); ++siting) {}
+        if (i + 1 >= argc || siting == 3) { fprintf(stderr, "--chroma-loc is center, left or topleft\n"); return 2; }
+        for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+        argc -= 2, --i;
+    }
+    if (argc < 4) {
+        fprintf(stderr, "usage: %s net.hatplan in.y4m out.y4m [420|422|444|mono [out_depth]] [--chroma-loc center|left|topleft]\n", argv[0]);
+        return 2;
+    }
     FILE* f = fopen(argv[2], "rb");
     if (!f) { fprintf(stderr, "cannot open %s\n", argv[2]); return 1; }
     char head[4096], rest[4096] = "", in_c[32] = "";
@@ -101,6 +117,7 @@ int main(int argc, char** argv) {
     if (out_sub == sub && out_depth == depth) strcpy(out_c, in_c);
     else if (out_depth == 8) sprintf(out_c, "C%s", NAMES[out_sub]);
     else sprintf(out_c, out_sub == CMONO ? "C%s%d" : "C%sp%d", NAMES[out_sub], out_depth % 100);
+    if (siting != HAT_SITING_CENTER && out_sub == C420 && out_depth == 8) strcpy(out_c, LOC_TOKENS[siting]);   /* the header says what is written */
 
     hat_plan* plan = NULL;
     int rc = hat_plan_load(argv[1], &plan);
@@ -125,7 +142,8 @@ int main(int argc, char** argv) {
         if (strncmp(line, "FRAME", 5) != 0 || !strchr(line, '\n')) { fprintf(stderr, "frame %ld: expected a FRAME record\n", frames); return 1; }
         if (fread(hin, 1, nin, f) != nin) { fprintf(stderr, "frame %ld is truncated\n", frames); return 1; }
         if (hipMemcpy(din, hin, nin, hipMemcpyHostToDevice)) return 1;
-        rc = hat_plan_forward_yuv(plan, &src, &dst, (int32_t)h, (int32_t)w, TO_RGB, FROM_RGB, NULL);
+        rc = siting == HAT_SITING_CENTER ? hat_plan_forward_yuv(plan, &src, &dst, (int32_t)h, (int32_t)w, TO_RGB, FROM_RGB, NULL)
+                                         : hat_plan_forward_yuv_sited(plan, &src, siting, &dst, siting, (int32_t)h, (int32_t)w, TO_RGB, FROM_RGB, NULL);
         if (rc) { fprintf(stderr, "hat_plan_forward_yuv failed: %d (plan shape %dx%d, frame %ldx%ld)\n", rc, d[2], d[3], h, w); return 1; }
         if (hipDeviceSynchronize() || hipMemcpy(hout, dout, nout, hipMemcpyDeviceToHost)) return 1;
         if (fputs("FRAME\n", g) < 0 || fwrite(hout, 1, nout, g) != nout) { fprintf(stderr, "write to %s failed\n", argv[3]); return 1; }

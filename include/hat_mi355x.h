@@ -417,9 +417,9 @@ int hat_conv3x3_to_u8(const void* x, const void* wpk, const float* bias, uint8_t
  *                    replaced by a frame block, the same kernel and fp32 value; neither the fp32 image nor an RGB byte
  *                    image is written.  Bit-identical to hat_planes_to_yuv420 of hat_conv3x3_to_planes.  Its row bands
  *                    are an even number of rows high (a 2 x 2 block never straddles two bands).
- * Centre-sited chroma (JPEG, MPEG-1, Y4M C420jpeg) is what nearest-up / box-down means; left-sited sources (MPEG-2, H.264)
- * are accepted and treated the same.  All three check their arguments before they touch the device; none allocates or
- * synchronises.
+ * Centre-sited chroma (JPEG, MPEG-1, Y4M C420jpeg) is what nearest-up / box-down means, and it is what these entries compute;
+ * left- and top-left-sited chroma (MPEG-2, H.264, HEVC, AV1; BT.2020) is "Chroma siting" below.  All three check their
+ * arguments before they touch the device; none allocates or synchronises.
  */
 int hat_yuv420_to_planes(const uint8_t* y, int64_t y_pitch, int64_t y_bstride, const uint8_t* cb, const uint8_t* cr, int64_t c_pitch,
                          int32_t c_step, int64_t c_bstride, float* dst, int32_t B, int32_t h, int32_t w, int32_t Hp, int32_t Wp,
@@ -477,7 +477,8 @@ int hat_conv3x3_to_yuv420p16(const void* x, const void* wpk, const float* bias, 
  * and write the same samples.  hat_conv3x3_to_yuv takes hat_conv3x3_to_yuv420's conv arguments.  A bad surface (odd w with
  * sub_x = 1, one chroma pointer NULL, c_step not bps / 2 bps, an odd pitch for words, overlapping batch strides, sub_y >
  * sub_x ...) returns HAT_EINVAL before anything touches the device; none allocates or synchronises.  Packed 4:2:2 (YUY2 / UYVY /
- * Y210 / v210), 4:1:1, 4:4:0, alpha planes, chroma siting or filters other than nearest / box, and tone mapping are out of scope.
+ * Y210 / v210), 4:1:1, 4:4:0, alpha planes and tone mapping are out of scope.  These entries are centre-sited chroma; see
+ * "Chroma siting" below for the rest.
  */
 typedef struct {
     void* y; int64_t y_pitch, y_bstride; void* cb; void* cr; int64_t c_pitch; int32_t c_step; int64_t c_bstride;
@@ -490,6 +491,39 @@ int hat_planes_to_yuv(const float* src, int32_t B, int32_t Hs, int32_t Ws, const
 int hat_conv3x3_to_yuv(const void* x, const void* wpk, const float* bias, const HatYuvSurface* dst, int32_t B, int32_t H, int32_t W, int32_t C,
                        int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, const float* mean4, const float* from_rgb12,
                        int32_t dtype, void* stream);
+
+/*
+ * Chroma siting.  HatYuvSurface keeps its layout (HAT_ABI_VERSION stays 2): the siting travels beside the surface, as a code
+ *     HAT_SITING_CENTER 0   chroma in the middle of its luma block: JPEG, MPEG-1, Y4M C420jpeg — every entry above
+ *     HAT_SITING_LEFT 1     on the even luma columns, between the rows: MPEG-2, H.264, HEVC, AV1 4:2:0; all standard 4:2:2
+ *     HAT_SITING_TOPLEFT 2  on the even luma columns and rows: BT.2020 / UHD HEVC
+ * An axis is CO-SITED where it is subsampled and the siting puts chroma on the even luma sample: x where sub_x = 1 and the
+ * siting is 1 or 2, y where sub_y = 1 and the siting is 2.  Every other axis keeps the centre rule, so on a 4:2:2 surface 2 is
+ * 1, and on 4:4:4 and grey surfaces every siting is 0: accepted, not refused.  The definition is super_resolution_amd/yuv.py
+ * ("Chroma siting": chroma_up, chroma_down), and the results equal it bit for bit.
+ *   In.  Source pixel (y', x') after the reflection, s[.][.] the chroma samples in byte units, (ch, cw) the chroma plane's size:
+ *     j = x' >> sub_x, j1 = min(j + (x' & 1), cw - 1) if x is co-sited, else j;  i, i1 likewise from y', sub_y, ch;
+ *     c = ((s[i][j] + s[i][j1]) + (s[i1][j] + s[i1][j1])) * 0.25 (exact), Cb' = c - 128, then the per-pixel expression.
+ *   Out.  From the per-pixel cb / cr terms c of the cropped h_out x w_out pixels, every + rounded to fp32 on its own:
+ *     co-sited x: t_r[j] = (c[r][max(2j - 1, 0)] + c[r][2j + 1]) + 2 c[r][2j];  centred x: t_r[j] = c[r][2j] + c[r][2j + 1]
+ *     4:2:2, siting 1 / 2:  C = t_r[j] * 0.25 + k[c][3]
+ *     4:2:0, siting 1:      C = (t_2i[j] + t_2i+1[j]) * 0.125 + k[c][3]
+ *     4:2:0, siting 2:      C = ((t_max(2i-1,0)[j] + t_2i+1[j]) + 2 t_2i[j]) * 0.0625 + k[c][3]
+ *     Left and top edges replicate; no tap reads past the crop; the byte / code rule is unchanged.
+ * hat_yuv_to_planes_sited / hat_planes_to_yuv_sited take hat_yuv_to_planes' / hat_planes_to_yuv's arguments with the siting
+ * after the surface.  They refuse everything those refuse, and a siting outside {0, 1, 2}, with HAT_EINVAL before anything
+ * touches the device.  Where the surface makes the siting 0 they forward to the unsited entry: the same launch, the same
+ * samples.  conv_last's fused epilogue (hat_conv3x3_to_yuv) has no sited form — its bands and lanes would need a halo column and
+ * row — so a sited output is hat_conv3x3_to_planes followed by hat_planes_to_yuv_sited.  Other filters (Lanczos, 3/4 - 1/4
+ * vertical linear for centred axes), PAL-DV's alternating-line siting, packed 4:2:2 and transfer functions are out of scope.
+ */
+#define HAT_SITING_CENTER 0
+#define HAT_SITING_LEFT 1
+#define HAT_SITING_TOPLEFT 2
+int hat_yuv_to_planes_sited(const HatYuvSurface* src, int32_t siting, float* dst, int32_t B, int32_t h, int32_t w, int32_t Hp, int32_t Wp,
+                            const float* to_rgb12, void* stream);
+int hat_planes_to_yuv_sited(const float* src, int32_t B, int32_t Hs, int32_t Ws, const HatYuvSurface* dst, int32_t siting, int32_t h_out,
+                            int32_t w_out, const float* from_rgb12, void* stream);
 
 /*
  * MATLAB-style bicubic imresize (basicsr utils/matlab_functions.py:16-178): the resize the reference makes its low-resolution
@@ -731,6 +765,13 @@ int hat_hab_tail3(const HatHabTailDesc* d, void* stream);
  *                     grey -> grey, I444 -> grey ...).  Both surfaces are checked in full before anything is enqueued.  It stages
  *                     with hat_yuv_to_planes, replays, and ends in hat_conv3x3_to_yuv or hat_planes_to_yuv by the rule of
  *                     hat_plan_forward_yuv420, in the same staging buffers.  Bit-identical to HAT.forward_yuv.
+ *   hat_plan_forward_yuv_sited  hat_plan_forward_yuv with a chroma siting beside each surface (see "Chroma siting").  It
+ *                     refuses what hat_plan_forward_yuv refuses and a siting outside {0, 1, 2}; two sitings that the surfaces
+ *                     make 0 ARE hat_plan_forward_yuv.  It stages with hat_yuv_to_planes_sited.  Where the destination is
+ *                     co-sited, a plan that ends in hat_conv3x3_to_planes replays that launch too, into its fp32 output
+ *                     staging image (allocated on the first such call, as under hat_plan_forward_u8), and ends in
+ *                     hat_planes_to_yuv_sited; a centre destination ends by the rule of hat_plan_forward_yuv420.  No new plan
+ *                     file content.  Bit-identical to HAT.forward_yuv(siting=, out_siting=).
  */
 typedef struct hat_plan hat_plan;
 int hat_plan_load(const char* path, hat_plan** out);
@@ -750,6 +791,8 @@ int hat_plan_forward_yuv420_deep(const hat_plan* plan, const void* src_y, int64_
                                  int32_t dst_msb, const float* to_rgb12, const float* from_rgb12, void* stream);
 int hat_plan_forward_yuv(const hat_plan* plan, const HatYuvSurface* src, const HatYuvSurface* dst, int32_t h, int32_t w,
                          const float* to_rgb12, const float* from_rgb12, void* stream);
+int hat_plan_forward_yuv_sited(const hat_plan* plan, const HatYuvSurface* src, int32_t src_siting, const HatYuvSurface* dst,
+                               int32_t dst_siting, int32_t h, int32_t w, const float* to_rgb12, const float* from_rgb12, void* stream);
 
 /*
  * Per-channel sums of a channel-last map over the pixel rectangle rows [r0, r1) x columns [c0, c1):

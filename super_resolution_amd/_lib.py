@@ -187,6 +187,12 @@ SIGNATURES = {
                                                                                                         C.c_void_p, C.c_int32, C.c_void_p]),
     "hat_plan_forward_yuv": (C.c_int, [C.c_void_p, C.POINTER(HatYuvSurface), C.POINTER(HatYuvSurface), C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
+    # chroma siting: the surface entries with a siting code (0 centre, 1 left, 2 top-left) beside each surface
+    "hat_yuv_to_planes_sited": (C.c_int, [C.POINTER(HatYuvSurface), C.c_int32, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
+    "hat_planes_to_yuv_sited": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HatYuvSurface), C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p]),
+    "hat_plan_forward_yuv_sited": (C.c_int, [C.c_void_p, C.POINTER(HatYuvSurface), C.c_int32, C.POINTER(HatYuvSurface), C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hat_imresize_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     "hat_imresize_cols_to_planes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,

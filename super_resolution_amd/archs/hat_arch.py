@@ -416,7 +416,7 @@ class HAT(nn.Module):
             return self.engine(gt.device).forward_gt_u8(gt, bgr=bgr, out=out, ensemble=ensemble)
 
     def forward_yuv420(self, frame, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False, depth: int = 8, out_depth=None,
-                       msb=None, out=None, ensemble: int = 1):
+                       msb=None, out=None, ensemble: int = 1, siting: str = "center", out_siting=None):
         """4:2:0 YCbCr frames in, 4:2:0 frames out, all on the device: `frame` is a (3h/2, w) or (B, 3h/2, w) uint8 device tensor in
         the standard contiguous layout of `fmt` ('nv12', 'nv21', 'i420': super_resolution_amd/yuv.py), h and w even and of ANY
         size whose reflect-padding to the next window multiple is defined; returns (B, 3sh/2, sw) uint8 in the same layout.
@@ -428,7 +428,8 @@ class HAT(nn.Module):
         result, uint8 for 8 and uint16 otherwise, so 8 -> 10 writes ten bits from an 8-bit source.  The input dtype must agree
         with `depth`.  No transfer function is applied.  Runs eagerly also with use_graph=True (the byte paths are not captured).
         ensemble 2 / 4 / 8: the padded RGB planes go through `forward_ensemble`, then crop and yuv.planes_to_yuv420
-        (hat_planes_to_yuv420); ensemble=1 is the call as it always was."""
+        (hat_planes_to_yuv420); ensemble=1 is the call as it always was.  siting / out_siting: as forward_yuv takes them;
+        siting="center" is the call as it always was."""
         if not isinstance(frame, torch.Tensor):
             raise TypeError(f"forward_yuv420 needs a uint8 device tensor, got {type(frame).__name__}")
         if frame.dtype not in (torch.uint8, torch.uint16):
@@ -443,10 +444,10 @@ class HAT(nn.Module):
             frame = frame.unsqueeze(0)
         yuv.frame_size(frame.shape)   # (what is no 4:2:0 frame is refused in those words)
         return self.forward_yuv(frame, fmt=fmt, out_fmt=fmt, matrix=matrix, full_range=full_range, depth=depth, out_depth=out_depth, msb=msb,
-                                out_msb=msb, out=out, ensemble=ensemble)
+                                out_msb=msb, out=out, ensemble=ensemble, siting=siting, out_siting=out_siting)
 
     def forward_yuv(self, frame, *, fmt: str, out_fmt=None, matrix: str = "bt601", full_range: bool = False, depth: int = 8, out_depth=None,
-                    msb=None, out_msb=None, out=None, ensemble: int = 1):
+                    msb=None, out_msb=None, out=None, ensemble: int = 1, siting: str = "center", out_siting=None):
         """YCbCr frames of any chroma subsampling in, any out, all on the device: `frame` is a (rows, w) or (B, rows, w) uint8
         (uint16 with depth 10 / 12 / 16) device tensor in the standard contiguous layout of `fmt`, one of yuv.ALL_FORMATS —
         'nv12' 'nv21' 'i420' (4:2:0), 'i422' 'nv16' (4:2:2), 'i444' 'nv24' (4:4:4), 'gray' — and the result is the s-times larger
@@ -455,7 +456,12 @@ class HAT(nn.Module):
         every other size >= 1 whose reflect-padding to the next window multiple is defined is a frame.  Equal, bit for bit, to
         yuv.yuv_to_planes -> reflect-pad -> this build's `forward` -> crop -> yuv.planes_to_yuv.  depth / out_depth, matrix,
         full_range, out, ensemble: as forward_yuv420; msb / out_msb: the word alignment of each deep side (default: by the layout).
-        forward_yuv420 is this call with out_fmt = fmt for the three 4:2:0 layouts."""
+        forward_yuv420 is this call with out_fmt = fmt for the three 4:2:0 layouts.
+        siting: where the source's chroma samples lie (yuv.SITINGS, yuv.py "Chroma siting"): 'center' (JPEG, MPEG-1; nearest up,
+        box down: the call as it always was), 'left' (MPEG-2, H.264, HEVC, AV1 4:2:0 and all standard 4:2:2) or 'topleft'
+        (BT.2020); out_siting: the result's (None: the input's).  A siting applies to the subsampled axes only, so it is
+        ignored by 4:4:4 and grey.  The call stays bit-equal to the composition with the same siting= on both yuv.py functions;
+        an output with a co-sited axis is written from fp32 planes (hat_planes_to_yuv_sited), not in conv_last's epilogue."""
         if not isinstance(frame, torch.Tensor):
             raise TypeError(f"forward_yuv needs a uint8 device tensor, got {type(frame).__name__}")
         if frame.dtype not in (torch.uint8, torch.uint16):
@@ -464,6 +470,8 @@ class HAT(nn.Module):
         from .. import yuv
         yuv.check_layout(fmt)
         yuv.check_layout(fmt if out_fmt is None else out_fmt)
+        yuv.check_siting(siting)
+        out_siting = siting if out_siting is None else yuv.check_siting(out_siting)
         out_depth = depth if out_depth is None else out_depth
         to_rgb, from_rgb = yuv.csc(matrix, full_range, depth)[0], yuv.csc(matrix, full_range, out_depth)[1]
         if frame.dtype != (torch.uint8 if depth == 8 else torch.uint16):
@@ -472,7 +480,8 @@ class HAT(nn.Module):
             frame = frame.unsqueeze(0)
         with torch.no_grad():
             return self.engine(frame.device).forward_yuv(frame, fmt=fmt, out_fmt=out_fmt, to_rgb=to_rgb, from_rgb=from_rgb, out=out,
-                                                         depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, ensemble=ensemble)
+                                                         depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, ensemble=ensemble,
+                                                         siting=siting, out_siting=out_siting)
 
     # ---- exact full-frame sharding into row bands (no counterpart in the reference, whose tile loop
     # hat_model.py:40-108 gives a DIFFERENT result than the full frame: SURVEY F6) ----

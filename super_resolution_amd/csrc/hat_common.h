@@ -333,6 +333,27 @@ __device__ __forceinline__ float hat_add_rn(float a, float b) {   // a sum that 
     return a + b;
 }
 
+// Chroma siting (yuv.py, "Chroma siting").  In: the chroma of one source pixel from the (up to) four samples around it, in byte
+// units, centred on 128: every step is exact.  Out: the [1 2 1] tap of a co-sited axis from (left, centre, right) or (above,
+// row, below), and value = tap sum * scale + offset with scale a power of two.
+__device__ __forceinline__ float hat_chroma_up4(float s00, float s01, float s10, float s11) {
+#pragma clang fp contract(off)
+    const float top = s00 + s01, bottom = s10 + s11;
+    const float q = (top + bottom) * 0.25f;
+    return q - 128.0f;
+}
+__device__ __forceinline__ float hat_chroma_tap121(float before, float centre, float after) {
+#pragma clang fp contract(off)
+    const float outer = before + after;
+    const float mid = 2.0f * centre;
+    return outer + mid;
+}
+__device__ __forceinline__ float hat_chroma_value_s(float sum, float scale, float offset) {
+#pragma clang fp contract(off)
+    const float q = sum * scale;
+    return q + offset;
+}
+
 #define HAT_LAUNCH(...)                      \
     do {                                     \
         (void)hipGetLastError();             \

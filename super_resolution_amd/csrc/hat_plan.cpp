@@ -333,12 +333,14 @@ bool ends_in_planes(const hat_plan* p) {
 // What the frame entries share once their own checks have passed: the device check, the fp32 staging (allocated by the first
 // call), source(stage_in), the replay of all but a final hat_conv3x3_to_planes, and the ending: fused(r), the conv_last
 // epilogue on the recorded arguments r of that last call, or planes(stage_out, Hs, Ws) after a replay of every call.
+// may_fuse = false: the ending has no epilogue form (a co-sited YCbCr destination), so a final hat_conv3x3_to_planes is replayed
+// like every other call, into the output staging image.
 template <typename Source, typename Fused, typename Planes>
-int forward_frames(const hat_plan* p, void* stream, Source source, Fused fused_sink, Planes planes_sink) {
+int forward_frames(const hat_plan* p, void* stream, Source source, Fused fused_sink, Planes planes_sink, bool may_fuse = true) {
     const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4];
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != p->device) return HAT_EINVAL;
-    const bool fused = ends_in_planes(p);
+    const bool fused = may_fuse && ends_in_planes(p);
     if (!p->stage_in) {
         const hipError_t e = hipMalloc((void**)&p->stage_in, (size_t)B * 3 * H * W * sizeof(float));
         if (e != hipSuccess) { p->stage_in = nullptr; return (int)e; }
@@ -370,28 +372,36 @@ int frame_fits(const hat_plan* p, int32_t h, int32_t w) {
 // hat_plan_forward_yuv after its NULL checks.  The 4:2:0 entries come here with the (1,1) surfaces of their blocks and their own
 // from-planes entry (planes420: its grid takes frames twice as tall as hat_planes_to_yuv's).
 int forward_yuv(const hat_plan* p, const HatYuvSurface* src, const HatYuvSurface* dst, int32_t h, int32_t w, const float* to_rgb12,
-                const float* from_rgb12, void* stream, bool planes420) {
+                const float* from_rgb12, void* stream, bool planes420, int32_t src_siting = HAT_SITING_CENTER,
+                int32_t dst_siting = HAT_SITING_CENTER) {
     // what needs no plan first (a B of 1 stands in: the batch strides are checked against the plan's B below)
     if (!hat_yuv_surface_ok(src, 1, h, w)) return HAT_EINVAL;
     if (const int rc = frame_fits(p, h, w)) return rc;
     const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4], ho = s * h, wo = s * w;
     // both surfaces in full before anything is enqueued (the kernels' own checks would refuse the destination only after the replay)
     if (!hat_yuv_surface_ok(src, B, h, w) || !hat_yuv_surface_ok(dst, B, (int64_t)s * h, (int64_t)s * w)) return HAT_EINVAL;
+    const bool sited_out = hat_siting_of(dst, dst_siting) != HAT_SITING_CENTER;   // (a sited entry: never planes420)
     return forward_frames(
-        p, stream, [&](float* in) { return hat_yuv_to_planes(src, in, B, h, w, H, W, to_rgb12, stream); },
+        p, stream,
+        [&](float* in) {
+            if (hat_siting_of(src, src_siting) == HAT_SITING_CENTER) return hat_yuv_to_planes(src, in, B, h, w, H, W, to_rgb12, stream);
+            return hat_yuv_to_planes_sited(src, src_siting, in, B, h, w, H, W, to_rgb12, stream);
+        },
         [&](Resolved& r) {
             return hat_conv3x3_to_yuv(r.P(0), r.P(1), (const float*)r.P(2), dst, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10),
                                       (const float*)r.P(11), from_rgb12, r.I(12), stream);
         },
         [&](const float* out, int32_t Hs, int32_t Ws) {
             const HatYuvSurface& d = *dst;
+            if (sited_out) return hat_planes_to_yuv_sited(out, B, Hs, Ws, dst, dst_siting, ho, wo, from_rgb12, stream);
             if (!planes420) return hat_planes_to_yuv(out, B, Hs, Ws, dst, ho, wo, from_rgb12, stream);
             if (d.depth == 8)
                 return hat_planes_to_yuv420(out, B, Hs, Ws, (uint8_t*)d.y, d.y_pitch, d.y_bstride, (uint8_t*)d.cb, (uint8_t*)d.cr, d.c_pitch, d.c_step,
                                             d.c_bstride, ho, wo, from_rgb12, stream);
             return hat_planes_to_yuv420p16(out, B, Hs, Ws, (uint16_t*)d.y, d.y_pitch, d.y_bstride, (uint16_t*)d.cb, (uint16_t*)d.cr, d.c_pitch, d.c_step,
                                            d.c_bstride, ho, wo, from_rgb12, d.depth, d.msb, stream);
-        });
+        },
+        !sited_out);
 }
 }  // namespace
 
@@ -444,4 +454,13 @@ extern "C" int hat_plan_forward_yuv(const hat_plan* p, const HatYuvSurface* src,
                                     const float* to_rgb12, const float* from_rgb12, void* stream) {
     if (!p || !src || !dst || !to_rgb12 || !from_rgb12 || h < 1 || w < 1) return HAT_EINVAL;
     return forward_yuv(p, src, dst, h, w, to_rgb12, from_rgb12, stream, false);
+}
+
+// The same forward with a chroma siting beside each surface; two centre sitings are hat_plan_forward_yuv.
+extern "C" int hat_plan_forward_yuv_sited(const hat_plan* p, const HatYuvSurface* src, int32_t src_siting, const HatYuvSurface* dst,
+                                          int32_t dst_siting, int32_t h, int32_t w, const float* to_rgb12, const float* from_rgb12,
+                                          void* stream) {
+    if (!p || !src || !dst || !to_rgb12 || !from_rgb12 || h < 1 || w < 1 || !hat_siting_ok(src_siting) || !hat_siting_ok(dst_siting))
+        return HAT_EINVAL;
+    return forward_yuv(p, src, dst, h, w, to_rgb12, from_rgb12, stream, false, src_siting, dst_siting);
 }

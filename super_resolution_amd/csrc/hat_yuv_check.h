@@ -58,3 +58,12 @@ static inline HatYuvSurface hat_yuv420_surface(const void* y, int64_t y_pitch, i
                                                int32_t c_step, int64_t c_bstride, int32_t depth, int32_t msb) {
     return HatYuvSurface{const_cast<void*>(y), y_pitch, y_bstride, const_cast<void*>(cb), const_cast<void*>(cr), c_pitch, c_step, c_bstride, 1, 1, depth, msb};
 }
+
+// chroma siting (include/hat_mi355x.h, "Chroma siting"): a code of HAT_SITING_*, and what a checked surface makes of it — an axis
+// is co-sited only where it is subsampled, so 4:4:4 and grey are centre under every siting and 4:2:2 'topleft' is 'left'
+static inline bool hat_siting_ok(int32_t siting) { return siting == HAT_SITING_CENTER || siting == HAT_SITING_LEFT || siting == HAT_SITING_TOPLEFT; }
+
+static inline int32_t hat_siting_of(const HatYuvSurface* s, int32_t siting) {
+    if (!s->cb || !s->sub_x || siting == HAT_SITING_CENTER) return HAT_SITING_CENTER;
+    return siting == HAT_SITING_TOPLEFT && s->sub_y ? HAT_SITING_TOPLEFT : HAT_SITING_LEFT;
+}

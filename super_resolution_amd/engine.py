@@ -196,6 +196,7 @@ class _Sink:
     as its epilogue (no fp32 image exists), or from_planes(y) of an fp32 image.  Each bumps its engine counter, `kind`_fused_calls
     or `kind`_planes_calls.  band_refusal: why a row band, which hands its rows over as fp32, cannot end in this sink."""
     kind = band_refusal = None
+    fusable = True   # False: conv_last has no epilogue for this sink; it always ends in from_planes
 
     def __init__(self, eng, out, size):
         self.eng, self.out, self.size = eng, out, size
@@ -224,19 +225,23 @@ class _U8Sink(_Sink):
 
 class _YuvSink(_Sink):
     """out in a layout of yuv.LAYOUTS as its (y, cb, cr) views (ops.yuv_views; sub = (sub_x, sub_y), None: grey), `depth` bits a
-    sample: hat_conv3x3_to_yuv / hat_planes_to_yuv, for the 4:2:0 layouts as for every other."""
+    sample: hat_conv3x3_to_yuv / hat_planes_to_yuv, for the 4:2:0 layouts as for every other.  siting: the output's chroma siting
+    (yuv.SITINGS).  Where the layout leaves an axis co-sited the sink is not fusable — conv_last's epilogue has no halo column or
+    row — and ends in hat_planes_to_yuv_sited; every other siting is the centre sink."""
     kind, band_refusal = "yuv", "the 4:2:0 output is the unsharded forward's, and it is one target of three"
 
-    def __init__(self, eng, out, views, from_rgb, *, sub, depth, msb):
+    def __init__(self, eng, out, views, from_rgb, *, sub, depth, msb, siting="center"):
         super().__init__(eng, out, tuple(views[0].shape[1:3]))
         self.views, self.from_rgb, self.surface = views, from_rgb, dict(sub=sub, depth=depth, msb=msb)
+        self.siting = ops._siting(sub, siting)[0]
+        self.fusable = self.siting == "center"
 
     def fused(self, src, wpk, b8, **conv):
         ops.conv3x3_to_yuv(src, wpk, b8, *self.views, from_rgb=self.from_rgb, **self.surface, **conv)
         self._count("fused")
 
     def from_planes(self, y):
-        ops.planes_to_yuv(y, *self.views, self.from_rgb, **self.surface)
+        ops.planes_to_yuv(y, *self.views, self.from_rgb, siting=self.siting, **self.surface)
         self._count("planes")
 
 
@@ -812,7 +817,7 @@ class HATEngine:
                                    what=f"the {h}x{w} low-resolution image of a {H}x{W} frame", of="image")
 
     def forward_yuv420(self, frame: torch.Tensor, *, fmt: str = "nv12", to_rgb, from_rgb, out=None, depth: int = 8, out_depth=None,
-                       msb=None, ensemble: int = 1) -> torch.Tensor:
+                       msb=None, ensemble: int = 1, siting: str = "center", out_siting=None) -> torch.Tensor:
         """forward_yuv for the three 4:2:0 layouts of yuv.FORMATS, the same one on both sides: (B,3h/2,w) device frames in the
         layout `fmt`, h and w even -> (B,3sh/2,sw) in the same layout; msb: the alignment of deep words on both sides (default: by
         the layout).  It refuses what is no 4:2:0 frame in its own words; everything else is forward_yuv's."""
@@ -833,20 +838,24 @@ class HATEngine:
             raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
         _yuv.frame_size(frame.shape)
         return self.forward_yuv(frame, fmt=fmt, out_fmt=fmt, to_rgb=to_rgb, from_rgb=from_rgb, out=out, depth=depth, out_depth=out_depth,
-                                msb=msb, out_msb=msb, ensemble=ensemble)
+                                msb=msb, out_msb=msb, ensemble=ensemble, siting=siting, out_siting=out_siting)
 
     def forward_yuv(self, frame: torch.Tensor, *, fmt: str, out_fmt=None, to_rgb, from_rgb, out=None, depth: int = 8, out_depth=None,
-                    msb=None, out_msb=None, ensemble: int = 1) -> torch.Tensor:
+                    msb=None, out_msb=None, ensemble: int = 1, siting: str = "center", out_siting=None) -> torch.Tensor:
         """(B,rows,w) device frames in the layout `fmt` of yuv.LAYOUTS, any size the layout and the reflection allow -> the frames
         of the s-times larger image in the layout `out_fmt` (default: fmt), any subsampling or grey to any other:
         hat_yuv_to_planes into this shape's workspace, the forward, the crop and the conversion back (in conv_last's epilogue,
         hat_conv3x3_to_yuv, or hat_planes_to_yuv).  to_rgb / from_rgb: yuv.csc's matrices (of `depth` / `out_depth`).  out: the
         caller's result tensor.  depth / out_depth 10, 12, 16: uint16 frames on that side (yuv.py, "Deep samples"; out_depth
         defaults to depth); msb / out_msb: MSB-aligned words on that side (default: by the layout).  ensemble 2 / 4 / 8: the
-        padded RGB planes go through forward_ensemble, then hat_planes_to_yuv with the crop."""
+        padded RGB planes go through forward_ensemble, then hat_planes_to_yuv with the crop.  siting / out_siting (yuv.SITINGS;
+        out_siting defaults to siting): the chroma siting of each side; a co-sited output ends in hat_conv3x3_to_planes and
+        hat_planes_to_yuv_sited (yuv_planes_calls counts it), never in conv_last's epilogue."""
         self._check_u8()
         ensemble = ops.ensemble_members(ensemble)
         from . import yuv as _yuv
+        siting = _yuv.check_siting(siting)
+        out_siting = siting if out_siting is None else _yuv.check_siting(out_siting)
         out_fmt = fmt if out_fmt is None else out_fmt
         out_depth = depth if out_depth is None else out_depth
         in_msb, out_msb = bool(_yuv.container(depth, fmt, msb)[3]), bool(_yuv.container(out_depth, out_fmt, out_msb)[3])
@@ -867,7 +876,7 @@ class HATEngine:
             f = frame
             if f.stride(2) != 1 or f.stride(1) != w:
                 f = f.contiguous() if in_dt is torch.uint8 else f.view(torch.int16).contiguous().view(torch.uint16)
-            ops.yuv_to_planes(*ops.yuv_views(f, fmt), x, to_rgb, sub=sub(fmt), depth=depth, msb=in_msb)
+            ops.yuv_to_planes(*ops.yuv_views(f, fmt), x, to_rgb, sub=sub(fmt), depth=depth, msb=in_msb, siting=siting)
 
         def make_sink():
             shape, dst = (B,) + _yuv.frame_shape_fmt(s * h, s * w, out_fmt), out
@@ -877,7 +886,7 @@ class HATEngine:
                     or dst.stride(2) != 1 or dst.stride(1) != s * w:
                 raise RuntimeError(f"out must be a {shape} {str(out_dt)[6:]} tensor on {self.dev} with packed rows, got "
                                    f"{tuple(dst.shape)} {dst.dtype} on {dst.device}")
-            return _YuvSink(self, dst, ops.yuv_views(dst, out_fmt), from_rgb, sub=sub(out_fmt), depth=out_depth, msb=out_msb)
+            return _YuvSink(self, dst, ops.yuv_views(dst, out_fmt), from_rgb, sub=sub(out_fmt), depth=out_depth, msb=out_msb, siting=out_siting)
 
         return self._frame_forward(B, h, w, fill, make_sink, ensemble)
 
@@ -1279,7 +1288,7 @@ class HATEngine:
             src, h, wd = dst, h * rr, wd * rr
         r = float(self.cfg.get("img_range", 1.0))
         if sink is not None:
-            if self.u8_fused and wd % 16 == 0:
+            if self.u8_fused and wd % 16 == 0 and sink.fusable:
                 wpk, b8, _ = self.conv_last_sweep
                 sink.fused(src, wpk, b8, B=f.B, H=h, W=wd, C_=64, ldx=64, out_scale=1.0 / r, mean=self._mean(), dtype=dt)
                 return

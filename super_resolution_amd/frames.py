@@ -23,7 +23,7 @@ def _raw(t):
 
 
 def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", matrix: str = "bt601", full_range: bool = False, depth: int = 8,
-                   out_depth=None, msb=None, ensemble: int = 1, out_pixfmt=None, out_msb=None):
+                   out_depth=None, msb=None, ensemble: int = 1, out_pixfmt=None, out_msb=None, siting: str = "center", out_siting=None):
     """Generator: for every (h,w,3) uint8 array of `frames` (all of one size) yield the (s*h,s*w,3) uint8 array that
     `net.forward_u8` computes for it, in order.  `net`: a HAT / HATX module on a GPU, in eval mode.  The yielded array is
     the caller's own (copied out of the pinned buffer).  An empty sequence yields nothing.
@@ -34,7 +34,9 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
     pixfmt 'i422' / 'nv16' / 'i444' / 'nv24' / 'gray', or out_pixfmt (any layout of yuv.LAYOUTS; default: pixfmt) different from
     pixfmt: the frames are arrays of yuv.frame_shape_fmt in that layout and every frame goes through `net.forward_yuv` (any
     subsampling in, any out; out_msb: the output words' alignment), in the same two-slot pipeline.
-    ensemble 2 / 4 / 8: every frame through the geometric self-ensemble (HAT.forward_ensemble) of that many members."""
+    ensemble 2 / 4 / 8: every frame through the geometric self-ensemble (HAT.forward_ensemble) of that many members.
+    siting / out_siting (YCbCr pixel formats; yuv.SITINGS): the chroma siting of the frames and of the yielded frames (default:
+    the input's), as HAT.forward_yuv takes them; 'center' is the sequence as it always was."""
     from .ops import ensemble_members
     ensemble = ensemble_members(ensemble)
     if pixfmt not in PIXFMTS:
@@ -43,6 +45,11 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
         raise RuntimeError(f"out_pixfmt {out_pixfmt!r}: one of {PIXFMTS[1:]} for a YCbCr pixfmt (rgb24 frames stay rgb24)")
     if out_msb is not None and pixfmt == "rgb24":
         raise RuntimeError("out_msb belongs to the YCbCr pixel formats")
+    from . import yuv as _yuv
+    out_siting = _yuv.check_siting(siting) if out_siting is None else _yuv.check_siting(out_siting)
+    skw = {} if (siting, out_siting) == ("center", "center") else {"siting": siting, "out_siting": out_siting}
+    if skw and pixfmt == "rgb24":
+        raise RuntimeError("siting and out_siting belong to the YCbCr pixel formats")
     general = pixfmt != "rgb24" and (pixfmt not in PIXFMTS[1:4] or out_pixfmt not in (None, pixfmt) or out_msb is not None)
     yuv420 = pixfmt != "rgb24" and not general
     dev = next(net.parameters()).device
@@ -67,7 +74,7 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
         h, w = _yuv.frame_size_fmt(first.shape, pixfmt)
         in_shape, out_shape, shape_text = first.shape, _yuv.frame_shape_fmt(s * h, s * w, out_pixfmt), str(tuple(first.shape)).replace(" ", "")
         forward = lambda src, dst: net.forward_yuv(src, fmt=pixfmt, out_fmt=out_pixfmt, matrix=matrix, full_range=full_range, out=dst,
-                                                   depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, ensemble=ensemble)
+                                                   depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, ensemble=ensemble, **skw)
     elif yuv420:
         from . import yuv as _yuv
         out_depth = depth if out_depth is None else out_depth
@@ -79,7 +86,7 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
         h, w = _yuv.frame_size(first.shape)
         in_shape, out_shape, shape_text = first.shape, _yuv.frame_shape(s * h, s * w), f"({3 * h // 2},{w})"
         forward = lambda src, dst: net.forward_yuv420(src, fmt=pixfmt, matrix=matrix, full_range=full_range, out=dst, depth=depth,
-                                                      out_depth=out_depth, msb=msb, ensemble=ensemble)
+                                                      out_depth=out_depth, msb=msb, ensemble=ensemble, **skw)
     else:
         if depth != 8 or out_depth not in (None, 8):
             raise RuntimeError("rgb24 frames are 8-bit: depth and out_depth belong to the 4:2:0 pixel formats")

@@ -627,27 +627,48 @@ def _sub_name(sub, depth):
     return ("gray" if sub is None else {(1, 1): "yuv420", (1, 0): "yuv422", (0, 0): "yuv444"}[tuple(sub)]) + ("" if depth == 8 else f"p{depth}")
 
 
-def yuv_to_planes(y, cb, cr, dst, to_rgb, *, sub, depth: int = 8, msb=False):
+def _siting(sub, siting):
+    """The siting the layout makes of `siting` (yuv.effective_siting: 'center' on 4:4:4 and grey, 'left' for 'topleft' on 4:2:2)
+    and its C code; an unknown siting is refused naming yuv.SITINGS."""
+    from . import yuv as _yuv
+    eff = _yuv.effective_siting(sub, siting)
+    return eff, _yuv.SITINGS.index(eff)
+
+
+def yuv_to_planes(y, cb, cr, dst, to_rgb, *, sub, depth: int = 8, msb=False, siting: str = "center"):
     """Y (B,h,w), Cb, Cr (B, h >> sub_y, w >> sub_x) views (yuv_views; None, None and sub=None: grey) -> dst (B,3,Hp,Wp) fp32 RGB
-    planes, rows and columns past (h, w) filled by reflection: yuv.yuv_to_planes' conversion (hat_yuv_to_planes)."""
+    planes, rows and columns past (h, w) filled by reflection: yuv.yuv_to_planes' conversion (hat_yuv_to_planes; with a siting
+    that leaves an axis co-sited, hat_yuv_to_planes_sited)."""
     lib = _lib.load()
+    eff, code = _siting(sub, siting)
     surf = yuv_surface(y, cb, cr, sub=sub, depth=depth, msb=msb, what="yuv_to_planes")
     B, h, w = y.shape
     _planes_dst("yuv_to_planes", dst, y, contiguous=True)
     m, name = _f12(to_rgb), _sub_name(sub, depth)
+    if code:
+        _timed(f"yuv_to_planes_sited_kernel<{name}, {eff}>", 0.0, lambda: _lib.check(
+            lib.hat_yuv_to_planes_sited(C.byref(surf), code, _ptr(dst), B, h, w, dst.shape[2], dst.shape[3], m, _stream()),
+            "hat_yuv_to_planes_sited"), tag=f"{name} {eff} {h}x{w} -> planes {dst.shape[2]}x{dst.shape[3]}")
+        return
     _timed(f"yuv_to_planes_kernel<{name}>", 0.0, lambda: _lib.check(
         lib.hat_yuv_to_planes(C.byref(surf), _ptr(dst), B, h, w, dst.shape[2], dst.shape[3], m, _stream()), "hat_yuv_to_planes"),
         tag=f"{name} {h}x{w} -> planes {dst.shape[2]}x{dst.shape[3]}")
 
 
-def planes_to_yuv(src, y, cb, cr, from_rgb, *, sub, depth: int = 8, msb=False):
+def planes_to_yuv(src, y, cb, cr, from_rgb, *, sub, depth: int = 8, msb=False, siting: str = "center"):
     """src (B,3,Hs,Ws) fp32 planes -> the top-left h x w pixels as Y (B,h,w), Cb, Cr views of any subsampling (or grey), converted
-    as yuv.planes_to_yuv converts (hat_planes_to_yuv)."""
+    as yuv.planes_to_yuv converts (hat_planes_to_yuv; with a siting that leaves an axis co-sited, hat_planes_to_yuv_sited)."""
     lib = _lib.load()
+    eff, code = _siting(sub, siting)
     surf = yuv_surface(y, cb, cr, sub=sub, depth=depth, msb=msb, what="planes_to_yuv")
     B, h, w = y.shape
     _planes_src("planes_to_yuv", src, y, contiguous=True)
     m, name = _f12(from_rgb), _sub_name(sub, depth)
+    if code:
+        _timed(f"planes_to_yuv_sited_kernel<{name}, {eff}>", 0.0, lambda: _lib.check(
+            lib.hat_planes_to_yuv_sited(_ptr(src), B, src.shape[2], src.shape[3], C.byref(surf), code, h, w, m, _stream()),
+            "hat_planes_to_yuv_sited"), tag=f"planes {src.shape[2]}x{src.shape[3]} -> {name} {eff} {h}x{w}")
+        return
     _timed(f"planes_to_yuv_kernel<{name}>", 0.0, lambda: _lib.check(
         lib.hat_planes_to_yuv(_ptr(src), B, src.shape[2], src.shape[3], C.byref(surf), h, w, m, _stream()), "hat_planes_to_yuv"),
         tag=f"planes {src.shape[2]}x{src.shape[3]} -> {name} {h}x{w}")

@@ -237,12 +237,18 @@ class Plan:
         return h, w, ops._f12(to_rgb), ops._f12(from_rgb)
 
     def forward_yuv420(self, src: torch.Tensor, dst: torch.Tensor, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False,
-                       depth: int = 8, out_depth=None, msb=None, stream: int = 0):
+                       depth: int = 8, out_depth=None, msb=None, stream: int = 0, siting: str = "center", out_siting=None):
         """hat_plan_forward_yuv420: src (B,3h/2,w) uint8 device frames in the layout `fmt` with h <= H, w <= W of the plan
         (reflect-padded to (H, W) on the device) -> dst (B,3sh/2,sw) uint8 in the same layout.  The first byte-path call
         allocates the plan's fp32 staging buffers.  depth / out_depth / msb as HAT.forward_yuv420 takes them (uint16 tensors on a
-        deep side): hat_plan_forward_yuv420_deep."""
+        deep side): hat_plan_forward_yuv420_deep.  siting / out_siting other than 'center': forward_yuv's route
+        (hat_plan_forward_yuv_sited) for the same frames."""
         from . import ops, yuv
+        out_siting = yuv.check_siting(siting) if out_siting is None else yuv.check_siting(out_siting)
+        if (siting, out_siting) != ("center", "center"):
+            yuv.check_fmt(fmt), yuv.frame_size(src.shape)
+            return self.forward_yuv(src, dst, fmt=fmt, out_fmt=fmt, matrix=matrix, full_range=full_range, depth=depth, out_depth=out_depth,
+                                    msb=msb, out_msb=msb, stream=stream, siting=siting, out_siting=out_siting)
         out_depth = depth if out_depth is None else out_depth
         h, w, to_rgb, from_rgb = self._yuv_args("forward_yuv420", src, dst, yuv.frame_size, yuv.frame_shape, matrix, full_range, depth, out_depth)
         sb = ops._yuv_block(*ops.yuv420_views(src, fmt), "forward_yuv420")
@@ -260,10 +266,12 @@ class Plan:
                    "hat_plan_forward_yuv420_deep")
 
     def forward_yuv(self, src: torch.Tensor, dst: torch.Tensor, *, fmt: str, out_fmt=None, matrix: str = "bt601", full_range: bool = False,
-                    depth: int = 8, out_depth=None, msb=None, out_msb=None, stream: int = 0):
+                    depth: int = 8, out_depth=None, msb=None, out_msb=None, stream: int = 0, siting: str = "center", out_siting=None):
         """hat_plan_forward_yuv: src (B,rows,w) device frames in any layout `fmt` of yuv.LAYOUTS with h <= H, w <= W of the plan ->
-        dst, the frames of the s-times larger image in the layout `out_fmt` (default: fmt).  Keywords as HAT.forward_yuv takes them."""
+        dst, the frames of the s-times larger image in the layout `out_fmt` (default: fmt).  Keywords as HAT.forward_yuv takes them;
+        a siting or out_siting other than 'center' goes through hat_plan_forward_yuv_sited."""
         from . import ops, yuv
+        out_siting = yuv.check_siting(siting) if out_siting is None else yuv.check_siting(out_siting)
         out_fmt = fmt if out_fmt is None else out_fmt
         out_depth = depth if out_depth is None else out_depth
         h, w, to_rgb, from_rgb = self._yuv_args("forward_yuv", src, dst, lambda shape: yuv.frame_size_fmt(shape, fmt),
@@ -272,6 +280,11 @@ class Plan:
         sv, dv = ops.yuv_views(src, fmt), ops.yuv_views(dst, out_fmt)     # (kept alive: the surfaces hold raw pointers)
         ss = ops.yuv_surface(*sv, sub=sub(fmt), depth=depth, msb=yuv.container(depth, fmt, msb)[3], what="forward_yuv")
         ds = ops.yuv_surface(*dv, sub=sub(out_fmt), depth=out_depth, msb=yuv.container(out_depth, out_fmt, out_msb)[3], what="forward_yuv")
+        if (siting, out_siting) != ("center", "center"):
+            _lib.check(self._lib.hat_plan_forward_yuv_sited(self._h, C.byref(ss), yuv.SITINGS.index(siting), C.byref(ds),
+                                                            yuv.SITINGS.index(out_siting), h, w, to_rgb, from_rgb, stream),
+                       "hat_plan_forward_yuv_sited")
+            return
         _lib.check(self._lib.hat_plan_forward_yuv(self._h, C.byref(ss), C.byref(ds), h, w, to_rgb, from_rgb, stream), "hat_plan_forward_yuv")
 
     def close(self):

@@ -2,6 +2,7 @@
 
     python -m super_resolution_amd.video -opt options/test/HAT-S_SRx4.yml -i in.y4m -o out.y4m [--matrix bt709] [--full-range]
                                          [--out-depth 10] [--out-chroma 444] [--self-ensemble [N]]
+                                         [--chroma-loc auto|center|left|topleft] [--out-chroma-loc ...]
 
 y4m.Reader -> frames.upscale_frames(pixfmt='i420') -> y4m.Writer.  W and H of the header are multiplied by the network's
 scale; every other header token (frame rate, interlacing, aspect, colour space, X comments) is copied.  Decoding and
@@ -12,6 +13,10 @@ depth comes from the header; --out-depth sets the output's (default: the input's
 4:2:2, 4:4:4 and grey streams (C422 / C444 / Cmono and their deep forms) are read as they are; --out-chroma 420|422|444|mono
 sets the output's subsampling (default: the input's) and with it the C token: `--out-chroma 444` on a 4:2:0 file keeps all of the
 network's chroma.
+--chroma-loc auto|center|left|topleft names the chroma siting of the input (yuv.py, "Chroma siting"); the default, center, treats
+every stream as this tool always did.  auto takes it from the header (y4m.siting_of: C420mpeg2 is left, C420paldv top-left; a
+4:2:2 header cannot say, so ask for left).  --out-chroma-loc sets the output's (default: the input's), and the written header
+says what was written.
 --self-ensemble [N] runs every frame through the geometric self-ensemble of N = 2, 4 or 8 (the default) members.
 """
 from __future__ import annotations
@@ -22,11 +27,14 @@ from . import y4m
 
 
 def upscale_file(net, src: str, dst: str, *, matrix: str = "bt601", full_range: bool = False, out_depth=None, ensemble: int = 1,
-                 out_chroma=None) -> dict:
+                 out_chroma=None, chroma_loc: str = "center", out_chroma_loc=None) -> dict:
     """Every frame of the .y4m file `src` through `net` into `dst`; returns {'frames', 'in', 'out'} (sizes as (w, h)), and for
     streams that are not 8-bit on both sides also 'depth' and 'out_depth'; with ensemble 2 / 4 / 8 (the self-ensemble of every
     frame, frames.upscale_frames) also 'ensemble'; for streams that are not 4:2:0 on both sides also 'chroma' and 'out_chroma'
-    (out_chroma '420' / '422' / '444' / 'mono'; default: the input's)."""
+    (out_chroma '420' / '422' / '444' / 'mono'; default: the input's).  chroma_loc 'auto' / 'center' / 'left' / 'topleft': the
+    input's chroma siting ('auto': y4m.siting_of the header); out_chroma_loc: the output's (default: the input's).  Unless both
+    are 'center' — then the header is copied as always — the result also holds 'chroma_loc' and 'out_chroma_loc' and the output
+    header names the output's siting (y4m.with_siting)."""
     from . import frames
     from .ops import ensemble_members
     ensemble = ensemble_members(ensemble)
@@ -37,16 +45,34 @@ def upscale_file(net, src: str, dst: str, *, matrix: str = "bt601", full_range: 
         chroma = y4m.chroma(rd.header)
         out_chroma = chroma if out_chroma is None else out_chroma
         hdr = y4m.with_chroma(y4m.with_depth(y4m.scaled_header(rd.header, net.upscale), out_depth), out_chroma)
+        siting, out_siting = resolve_chroma_loc(rd.header, chroma_loc, out_chroma_loc)
+        skw = {} if (siting, out_siting) == ("center", "center") else {"siting": siting, "out_siting": out_siting}
+        if skw:
+            hdr = y4m.with_siting(hdr, out_siting)
         kw = {} if depth == 8 and out_depth == 8 else {"depth": depth, "out_depth": out_depth}
         if ensemble > 1:
             kw["ensemble"] = ensemble
         info = {} if chroma == "420" and out_chroma == "420" else {"chroma": chroma, "out_chroma": out_chroma}
         fkw = {"out_pixfmt": y4m.CHROMAS[out_chroma]} if info else {}
         with y4m.Writer(dst, hdr, chroma=True) as wr:
-            for out in frames.upscale_frames(net, rd, pixfmt=rd.fmt, matrix=matrix, full_range=full_range, **kw, **fkw):
+            for out in frames.upscale_frames(net, rd, pixfmt=rd.fmt, matrix=matrix, full_range=full_range, **kw, **fkw, **skw):
                 wr.write(out)
                 n += 1
-    return dict({"frames": n, "in": (rd.w, rd.h), "out": (hdr["W"], hdr["H"])}, **kw, **info)
+    loc = {"chroma_loc": siting, "out_chroma_loc": out_siting} if skw else {}
+    return dict({"frames": n, "in": (rd.w, rd.h), "out": (hdr["W"], hdr["H"])}, **kw, **info, **loc)
+
+
+CHROMA_LOCS = ("auto", "center", "left", "topleft")
+
+
+def resolve_chroma_loc(header: dict, chroma_loc: str = "center", out_chroma_loc=None):
+    """(siting, out_siting) of a run on a stream with this header: 'auto' is y4m.siting_of(header), None the input's."""
+    for v in (chroma_loc, out_chroma_loc):
+        if v is not None and v not in CHROMA_LOCS:
+            raise RuntimeError(f"unknown chroma location {v!r}: one of {CHROMA_LOCS}")
+    siting = y4m.siting_of(header) if chroma_loc == "auto" else chroma_loc
+    out_siting = siting if out_chroma_loc is None else y4m.siting_of(header) if out_chroma_loc == "auto" else out_chroma_loc
+    return siting, out_siting
 
 
 def parser() -> argparse.ArgumentParser:
@@ -60,6 +86,11 @@ def parser() -> argparse.ArgumentParser:
                     help="bits per sample of the output stream (default: the input's, which the header names)")
     ap.add_argument("--out-chroma", default=None, choices=["420", "422", "444", "mono"],
                     help="chroma subsampling of the output stream (default: the input's, which the header names)")
+    ap.add_argument("--chroma-loc", default="center", choices=list(CHROMA_LOCS),
+                    help="chroma siting of the input: center (default: JPEG / MPEG-1, every stream as before), left (MPEG-2, H.264, HEVC, "
+                         "AV1; all 4:2:2), topleft (BT.2020), or auto: what the header says (C420mpeg2 left, C420paldv topleft)")
+    ap.add_argument("--out-chroma-loc", default=None, choices=list(CHROMA_LOCS),
+                    help="chroma siting of the output stream (default: the input's); the output header names it")
     ap.add_argument("--full-range", action="store_true", help="the stream is full range (0-255) instead of 16-235 / 16-240")
     ap.add_argument("--self-ensemble", nargs="?", type=int, const=8, default=None, choices=[2, 4, 8], metavar="N",
                     help="geometric self-ensemble of every frame over the first N = 2, 4 or 8 (default when N is left out) flips / transposes")
@@ -73,7 +104,8 @@ def main(argv=None):
     from .test import parse_options
     model = HATModel(parse_options(args.opt), device=args.device)
     info = upscale_file(model.get_bare_model(model.net_g), args.input, args.output, matrix=args.matrix, full_range=args.full_range,
-                        out_depth=args.out_depth, ensemble=args.self_ensemble or 1, out_chroma=args.out_chroma)
+                        out_depth=args.out_depth, ensemble=args.self_ensemble or 1, out_chroma=args.out_chroma, chroma_loc=args.chroma_loc,
+                        out_chroma_loc=args.out_chroma_loc)
     print(info)
     return info
 

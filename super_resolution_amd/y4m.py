@@ -3,7 +3,8 @@
 A stream is one header line `YUV4MPEG2 W<w> H<h> F<num>:<den> I<p|t|b|m> A<n>:<d> C<colour space> [X...]` and, per frame,
 a line `FRAME[ params]` followed by the planes Y (h x w), Cb, Cr (h/2 x w/2 each): that is the 'i420' layout of yuv.py,
 so a frame is a (3h/2, w) uint8 array.  Accepted colour spaces: C420 (the default when the token is absent), C420jpeg,
-C420mpeg2, C420paldv — they differ in chroma siting only, which this project treats alike (yuv.py).  Every other colour
+C420mpeg2, C420paldv — they differ in chroma siting only: the reader hands over the same arrays, siting_of(hdr) names the
+siting ('center', 'left', 'topleft': yuv.py, "Chroma siting") and with_siting(hdr, siting) writes it back.  Every other colour
 space (C444, C422, Cmono ...), more than 8 bits (C420p10 ...) and odd sizes are refused by name.
 
 deep=True (parse_header, Reader, Writer) also accepts C420p10, C420p12 and C420p16: every sample is a little-endian 16-bit word
@@ -38,6 +39,40 @@ for _b in (10, 12, 16):
 
 class Y4MError(RuntimeError):
     pass
+
+
+_SITING_OF_TOKEN = {"420jpeg": "center", "420mpeg2": "left", "420paldv": "topleft"}
+_TOKEN_OF_SITING = {v: k for k, v in _SITING_OF_TOKEN.items()}
+_XYSCSS = "YSCSS="     # the X comment `XYSCSS=<name>` as parse_header keeps it (without its X): ffmpeg / mjpegtools' extension
+
+
+def siting_of(hdr: dict) -> str:
+    """The chroma siting (yuv.SITINGS) a header names: C420mpeg2 -> 'left', C420paldv -> 'topleft' (its alternating-line detail
+    is out of scope), C420jpeg -> 'center'.  A bare C420 and every token without a siting (C420p10, C422*, C444*, Cmono*) is
+    'center' unless an XYSCSS=420MPEG2 | 420PALDV | 420JPEG comment says otherwise (the last such comment counts).  A 4:2:2 header
+    cannot say: standard 4:2:2 is 'left', and the caller asks for it."""
+    c = hdr.get("C", "420")
+    if c in ("420mpeg2", "420paldv"):
+        return _SITING_OF_TOKEN[c]
+    for x in reversed(hdr.get("X", [])):
+        if x.startswith(_XYSCSS) and x[len(_XYSCSS):].lower() in _SITING_OF_TOKEN:
+            return _SITING_OF_TOKEN[x[len(_XYSCSS):].lower()]
+    return "center"
+
+
+def with_siting(hdr: dict, siting: str) -> dict:
+    """The header saying `siting`: an 8-bit 4:2:0 C token becomes C420jpeg / C420mpeg2 / C420paldv (a bare C420 stays bare for
+    'center'), and an XYSCSS=420* comment that is there is rewritten to agree.  Tokens that cannot carry a siting (deep 4:2:0
+    without an XYSCSS comment, 4:2:2, 4:4:4, mono) are left alone."""
+    if siting not in _TOKEN_OF_SITING:
+        raise Y4MError(f"unknown chroma siting {siting!r}: one of {tuple(_TOKEN_OF_SITING)}")
+    out = dict(hdr, X=list(hdr.get("X", [])))
+    c = hdr.get("C", "420")
+    if c in _SITING_OF_TOKEN or (c == "420" and siting != "center"):
+        out["C"] = _TOKEN_OF_SITING[siting]
+    if chroma(hdr) == "420":
+        out["X"] = [_XYSCSS + _TOKEN_OF_SITING[siting].upper() if x.startswith(_XYSCSS + "420") else x for x in out["X"]]
+    return out
 
 
 def depth(hdr: dict) -> int:

@@ -29,9 +29,10 @@ Output, from the fp32 value v the float path would have stored: r, g, b = min(ma
     Cb = ((cb00 + cb01) + (cb10 + cb11)) * 0.25 + k[1][3]                       per 2 x 2 block: left + right, then top + bottom
 and a byte is rint(min(max(., 0), 255)), round half to even.
 
-Chroma siting: nearest up, box down is centre-sited chroma (JPEG, MPEG-1, Y4M C420jpeg).  Left-sited sources (MPEG-2,
-H.264) are accepted and treated the same: a quarter-pixel chroma shift at the output scale.  Other chroma filters and tone
-mapping are out of scope; 4:2:2, 4:4:4 and grey are "Other subsamplings" below.
+Chroma siting: nearest up, box down is CENTRE-sited chroma (JPEG, MPEG-1, Y4M C420jpeg), and it is what every function computes
+by default (siting="center").  "Chroma siting" below defines 'left' (MPEG-2, H.264, HEVC, AV1 4:2:0; all standard 4:2:2) and
+'topleft' (BT.2020 / UHD HEVC).  Other chroma filters and tone mapping are out of scope; 4:2:2, 4:4:4 and grey are "Other
+subsamplings" below.
 
 Deep samples (HEVC Main10, AV1, VP9 profile 2).  A deep sample is a little-endian 16-bit word that holds an n-bit code, n =
 depth in {10, 12, 16}; k = n - 8, maxcode = 2^n - 1, shift = 16 - n for an MSB-aligned container, else 0.
@@ -66,8 +67,27 @@ Depths, container, decode / encode and csc apply unchanged.  In: as above with t
 exactly and the same expression follows.  Out: Y and the per-pixel cb, cr terms as above, then
     4:2:0  as above        4:2:2  C = (c0 + c1) * 0.5 + k[c][3], left + right        4:4:4  C = c + k[c][3]        gray  Y only
 and the byte / code rule is unchanged.  For nv12 / nv21 / i420 the general functions return what the 4:2:0 pair returns.
-Packed 4:2:2 (YUY2 / UYVY / Y210 / v210), 4:1:1, 4:4:0, alpha planes, chroma siting or filters other than nearest / box, and
-tone mapping are out of scope.
+Packed 4:2:2 (YUY2 / UYVY / Y210 / v210), 4:1:1, 4:4:0, alpha planes and tone mapping are out of scope.
+
+Chroma siting (siting= / out_siting=; SITINGS = 'center', 'left', 'topleft', C codes 0, 1, 2).  An axis is CO-SITED when it is
+subsampled and the siting puts the chroma sample on the even luma sample: x where sub_x = 1 and the siting is 'left' or 'topleft',
+y where sub_y = 1 and the siting is 'topleft'.  Every other axis keeps the centre rule above, so on 4:2:2 'topleft' is 'left', and
+on 4:4:4 and grey every siting is 'center' (accepted, not refused).  siting="center" takes exactly the code path above.
+In (chroma_up).  Source pixel (sy, sx), after the reflection; s[.][.] the chroma samples as float32(code) * 2^-k; (ch, cw) the
+chroma plane's size:
+    j = sx >> sub_x, j1 = min(j + (sx & 1), cw - 1) if x is co-sited, else j;      i, i1 likewise from sy, sub_y, ch
+    c = ((s[i][j] + s[i][j1]) + (s[i1][j] + s[i1][j1])) * 0.25,     Cb' = c - 128 (Cr' likewise), then the per-pixel expression.
+Every step is exact in fp32 (four integers of at most 16 bits, a power of two), so one formula is nearest, horizontal-linear
+and bilinear: an even luma sample takes its chroma sample, an odd one the mean of its two neighbours; right and bottom edges clamp.
+Out (chroma_down).  The per-pixel cb / cr terms c (no offset) of the cropped h_out x w_out pixels as above; every + rounds to fp32
+on its own, 2 * and the power-of-two scales are exact.  Row tap of chroma column j in pixel row r:
+    co-sited x   t_r[j] = (c[r][max(2j - 1, 0)] + c[r][2j + 1]) + 2 c[r][2j]          centred x   t_r[j] = c[r][2j] + c[r][2j + 1]
+    4:2:2 'left' / 'topleft'   C = t_r[j] * 0.25 + k[c][3]
+    4:2:0 'left'               C = (t_2i[j] + t_2i+1[j]) * 0.125 + k[c][3]
+    4:2:0 'topleft'            C = ((t_max(2i-1,0)[j] + t_2i+1[j]) + 2 t_2i[j]) * 0.0625 + k[c][3]
+(the [1 2 1] / 4 filter centred on the even sample).  Left and top edges replicate, no tap reads past the crop, and the byte /
+code rule is unchanged.  Other filters (Lanczos, 3/4 - 1/4 vertical linear for centred axes), PAL-DV's alternating-line siting and
+transfer functions are out of scope.
 """
 from __future__ import annotations
 
@@ -81,6 +101,7 @@ LAYOUTS = {"nv12": (1, 1, "semi"), "nv21": (1, 1, "semi_vu"), "i420": (1, 1, "pl
 ALL_FORMATS = tuple(LAYOUTS)
 MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020nc": (0.2627, 0.0593)}   # Kr, Kb
 DEPTHS = (8, 10, 12, 16)
+SITINGS = ("center", "left", "topleft")   # the index is the C code (include/hat_mi355x.h, HAT_SITING_*)
 _F = np.float32
 
 
@@ -95,6 +116,26 @@ def check_layout(fmt: str):
     if fmt not in LAYOUTS:
         raise RuntimeError(f"unknown frame format {fmt!r}: one of {ALL_FORMATS}")
     return LAYOUTS[fmt]
+
+
+def check_siting(siting) -> str:
+    if not isinstance(siting, str) or siting not in SITINGS:
+        raise RuntimeError(f"unknown chroma siting {siting!r}: one of SITINGS = {SITINGS}")
+    return siting
+
+
+def cosited(sub, siting):
+    """(x, y): which axes of a layout with sub = (sub_x, sub_y) (None or (None, None): grey) are co-sited under `siting`."""
+    siting = check_siting(siting)
+    if sub is None or sub[0] is None:
+        return False, False
+    return bool(sub[0] == 1 and siting != "center"), bool(sub[1] == 1 and siting == "topleft")
+
+
+def effective_siting(sub, siting) -> str:
+    """The siting that a layout makes of `siting`: 'center' on 4:4:4 and grey, 'left' for 'topleft' on 4:2:2."""
+    cx, cy = cosited(sub, siting)
+    return "topleft" if cy else "left" if cx else "center"
 
 
 def check_depth(depth) -> int:
@@ -230,10 +271,63 @@ def ycc_to_rgb_deep(Y, Cb, Cr, to_rgb, depth: int) -> np.ndarray:
     return out
 
 
+def ycc_to_rgb_sited(y, cb, cr, to_rgb) -> np.ndarray:
+    """The same expression on float32 SAMPLES in byte units (float32(code) * 2^-k; cb, cr interpolated by chroma_up, not yet centred)."""
+    m = np.asarray(to_rgb, dtype=_F).reshape(3, 4)
+    cb, cr = cb - _F(128.0), cr - _F(128.0)
+    out = np.empty((3,) + y.shape, dtype=_F)
+    for c in range(3):
+        v = ((m[c, 0] * y + m[c, 1] * cb) + m[c, 2] * cr) + m[c, 3]
+        out[c] = np.minimum(np.maximum(v, _F(0.0)), _F(1.0))
+    return out
+
+
+def chroma_up(C, h: int, w: int, sub, siting: str) -> np.ndarray:
+    """Chroma samples C (..., h >> sub_y, w >> sub_x), float32 in byte units, -> the chroma of every source pixel, (..., h, w)
+    float32: "Chroma siting, In" of the module docstring.  A centred axis repeats its sample, a co-sited one interpolates."""
+    C = np.asarray(C, dtype=_F)
+    sub_x, sub_y = sub
+    cx, cy = cosited(sub, siting)
+    ch, cw = C.shape[-2:]
+    if (ch, cw) != (h >> sub_y, w >> sub_x):
+        raise RuntimeError(f"a {h}x{w} frame with subsampling {tuple(sub)} has {(h >> sub_y, w >> sub_x)} chroma samples, got {(ch, cw)}")
+    sy, sx = np.arange(h), np.arange(w)
+    i, j = sy >> sub_y, sx >> sub_x
+    i1 = np.minimum(i + (sy & 1), ch - 1) if cy else i
+    j1 = np.minimum(j + (sx & 1), cw - 1) if cx else j
+    g = lambda a, b: C[..., a, :][..., b]
+    return ((g(i, j) + g(i, j1)) + (g(i1, j) + g(i1, j1))) * _F(0.25)
+
+
+def chroma_down(c, sub, siting: str, offset=0.0) -> np.ndarray:
+    """Per-pixel chroma terms c (..., h, w) float32 -> the chroma plane (..., h >> sub_y, w >> sub_x) float32 with `offset` added
+    last: "Chroma siting, Out" of the module docstring; the centre rules (box, pair, copy) where no axis is co-sited."""
+    c = np.asarray(c, dtype=_F)
+    sub_x, sub_y = sub
+    cx, cy = cosited(sub, siting)
+    off = _F(offset)
+    if not sub_x:
+        return c + off
+    if cx:
+        left = np.concatenate([c[..., :, 0:1], c[..., :, 1:-1:2]], axis=-1)              # c[max(2j - 1, 0)]
+        t, n = (left + c[..., :, 1::2]) + _F(2.0) * c[..., :, 0::2], 4
+    else:
+        t, n = c[..., :, 0::2] + c[..., :, 1::2], 2
+    if not sub_y:
+        return t * _F(1.0 / n) + off
+    if cy:
+        up = np.concatenate([t[..., 0:1, :], t[..., 1:-1:2, :]], axis=-2)                # t of row max(2i - 1, 0)
+        return ((up + t[..., 1::2, :]) + _F(2.0) * t[..., 0::2, :]) * _F(0.25 / n) + off
+    return (t[..., 0::2, :] + t[..., 1::2, :]) * _F(0.5 / n) + off
+
+
 def yuv420_to_planes(frame: np.ndarray, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False, pad=(0, 0), depth: int = 8,
-                     msb=None) -> np.ndarray:
+                     msb=None, siting: str = "center") -> np.ndarray:
     """frame (3h/2, w) or (B, 3h/2, w) uint8 (uint16 with depth 10 / 12 / 16) -> (B, 3, h + pad[0], w + pad[1]) float32 RGB planes,
-    reflect-padded bottom / right."""
+    reflect-padded bottom / right.  siting: "Chroma siting" of the module docstring."""
+    if check_siting(siting) != "center":
+        check_fmt(fmt)
+        return yuv_to_planes(frame, fmt=fmt, matrix=matrix, full_range=full_range, pad=pad, depth=depth, msb=msb, siting=siting)
     frame = np.asarray(frame)
     dt = container(depth, fmt, msb)[0]
     if frame.dtype != dt or frame.ndim not in (2, 3):
@@ -276,9 +370,14 @@ def _code(v: np.ndarray, k: int, maxcode: int) -> np.ndarray:
 
 
 def planes_to_yuv420(planes: np.ndarray, *, fmt: str = "nv12", matrix: str = "bt601", full_range: bool = False, crop=None, out_depth: int = 8,
-                     msb=None) -> np.ndarray:
+                     msb=None, siting: str = "center") -> np.ndarray:
     """planes (B, 3, Hs, Ws) float32 -> (B, 3 h_out / 2, w_out) uint8 (uint16 with out_depth 10 / 12 / 16) in layout `fmt`;
-    crop = (h_out, w_out), even, the top-left pixels kept (default: all)."""
+    crop = (h_out, w_out), even, the top-left pixels kept (default: all).  siting: "Chroma siting" of the module docstring."""
+    if check_siting(siting) != "center":
+        check_fmt(fmt)
+        if crop is not None:
+            frame_shape(int(crop[0]), int(crop[1]))
+        return planes_to_yuv(planes, fmt=fmt, matrix=matrix, full_range=full_range, crop=crop, out_depth=out_depth, msb=msb, siting=siting)
     planes = np.asarray(planes, dtype=_F)
     if planes.ndim != 4 or planes.shape[1] != 3:
         raise RuntimeError(f"expected (B,3,Hs,Ws) float32 planes, got {planes.shape}")
@@ -364,11 +463,12 @@ def join_fmt(Y: np.ndarray, Cb, Cr, fmt: str, depth: int = 8, msb=None) -> np.nd
 
 
 def yuv_to_planes(frame: np.ndarray, *, fmt: str, matrix: str = "bt601", full_range: bool = False, pad=(0, 0), depth: int = 8,
-                  msb=None) -> np.ndarray:
+                  msb=None, siting: str = "center") -> np.ndarray:
     """frame (rows, w) or (B, rows, w) in any layout of LAYOUTS -> (B, 3, h + pad[0], w + pad[1]) float32 RGB planes, reflect-padded
-    bottom / right.  yuv420_to_planes for the three 4:2:0 layouts."""
+    bottom / right.  yuv420_to_planes for the three 4:2:0 layouts.  siting: "Chroma siting" of the module docstring."""
     frame = np.asarray(frame)
     sub_x, sub_y, kind = check_layout(fmt)
+    sited = effective_siting((sub_x, sub_y), siting) != "center"
     dt = container(depth, fmt, msb)[0]
     if frame.dtype != dt or frame.ndim not in (2, 3):
         raise RuntimeError(f"expected a (rows, w) or (B, rows, w) {np.dtype(dt).name} {fmt} frame, got {frame.shape} {frame.dtype}")
@@ -381,6 +481,11 @@ def yuv_to_planes(frame: np.ndarray, *, fmt: str, matrix: str = "bt601", full_ra
     Y, Cb, Cr = split_fmt(frame, fmt)
     sy, sx = _reflect_index(h, h + pad[0]), _reflect_index(w, w + pad[1])
     Yp = Y[:, sy][:, :, sx]
+    if sited:                # samples in byte units, interpolated per source pixel, then the reflection picks its source pixel
+        inv = _F(1.0 / (1 << (depth - 8)))
+        val = lambda a: decode(a, depth, fmt, msb).astype(_F) * inv
+        Cbp, Crp = (chroma_up(val(a), h, w, (sub_x, sub_y), siting)[:, sy][:, :, sx] for a in (Cb, Cr))
+        return np.ascontiguousarray(ycc_to_rgb_sited(val(Yp), Cbp, Crp, to_rgb).transpose(1, 0, 2, 3))
     if kind == "gray":       # Cb' = Cr' = 0: the neutral sample, 128 in byte units at every depth
         Cbp = Crp = np.full(Yp.shape, 128 << (depth - 8), dtype=np.uint16 if depth > 8 else np.uint8)
     else:
@@ -395,11 +500,13 @@ def yuv_to_planes(frame: np.ndarray, *, fmt: str, matrix: str = "bt601", full_ra
 
 
 def planes_to_yuv(planes: np.ndarray, *, fmt: str, matrix: str = "bt601", full_range: bool = False, crop=None, out_depth: int = 8,
-                  msb=None) -> np.ndarray:
+                  msb=None, siting: str = "center") -> np.ndarray:
     """planes (B, 3, Hs, Ws) float32 -> (B,) + frame_shape_fmt(h_out, w_out, fmt) frames in any layout of LAYOUTS; crop = (h_out,
-    w_out), the top-left pixels kept (default: all).  planes_to_yuv420 for the three 4:2:0 layouts."""
+    w_out), the top-left pixels kept (default: all).  planes_to_yuv420 for the three 4:2:0 layouts.  siting: "Chroma siting" of the
+    module docstring."""
     planes = np.asarray(planes, dtype=_F)
     sub_x, sub_y, kind = check_layout(fmt)
+    sited = effective_siting((sub_x, sub_y), siting) != "center"
     if planes.ndim != 4 or planes.shape[1] != 3:
         raise RuntimeError(f"expected (B,3,Hs,Ws) float32 planes, got {planes.shape}")
     ho, wo = (planes.shape[2], planes.shape[3]) if crop is None else (int(crop[0]), int(crop[1]))
@@ -409,7 +516,9 @@ def planes_to_yuv(planes: np.ndarray, *, fmt: str, matrix: str = "bt601", full_r
     _, kk, maxcode, _ = container(out_depth, fmt, msb)
     _, k = csc(matrix, full_range, out_depth)
     Y, cb, cr = rgb_to_ycc_float(planes[:, :, :ho, :wo], k)
-    if (sub_x, sub_y) == (1, 1):
+    if sited:
+        down = lambda c, off: chroma_down(c, (sub_x, sub_y), siting, off)
+    elif (sub_x, sub_y) == (1, 1):
         down = lambda c, off: ((c[:, 0::2, 0::2] + c[:, 0::2, 1::2]) + (c[:, 1::2, 0::2] + c[:, 1::2, 1::2])) * _F(0.25) + off
     elif (sub_x, sub_y) == (1, 0):
         down = lambda c, off: (c[:, :, 0::2] + c[:, :, 1::2]) * _F(0.5) + off
