@@ -870,6 +870,76 @@ int hat_imresize_plane_cols(const float* mid, int32_t B, int32_t oh, int32_t w, 
 int hat_niqe_block_stats(const float* plane, int32_t B, int32_t h, int32_t w, int32_t block, const double* window, double* stats,
                          void* stream);
 
+/*
+ * NAF stem: the NAFNet-style blocks in front of HATX in HybridHATNAF (hybrid_hat_naf_arch.py:16-82), c = 64 or 32 channels
+ * (HAT_EUNSUPPORTED otherwise), fp32 or bf16 storage.  One NAFBlock is
+ *     u = pw1(x); v = dw3x3(u); g = v[:c] * v[c:]; s = sca(mean_HW(g)); y = x + beta * pw2(g * s)
+ *     u2 = ffn1(y); v2 = ffn_dw(u2); g2 = v2[:c] * v2[c:]; out = y + gamma * ffn2(g2)
+ * The global pool cuts it into two halves of one shape, 1x1 c -> 2c, depthwise 3x3 (+ bias), gate: hat_naf_half is one half.
+ * The depthwise conv zero-pads u: outside the image u is 0, not the 1x1 conv's bias.
+ *
+ * hat_naf_half  works on tiles of 8 x 16 pixels with a 1-pixel halo, one workgroup per tile (hat_naf_half_tiles(H, W) per
+ *   sample).  It first takes the fp32 residual-stream row of every halo pixel
+ *     form (a), gprev == NULL:  r = r_in
+ *     form (b), gprev != NULL:  r = r_in + Wf . gprev + bf, written to r_out for the tile's own pixels (halo pixels are
+ *                               recomputed, not written: r_out must not be r_in)
+ *   then u = W1 . r + b1 on the MFMA units (r rounded to T, fp32 accumulation), the depthwise conv and the gate in fp32, and
+ *   stores g as T.  w1 == NULL (form (b) only) stops after r_out: the projection that ends the stem.
+ *     r_in, r_out  (B,H,W,ldr) fp32, ldr >= C, ldr % 4 == 0; channels >= C are neither read nor written
+ *     gprev        (B,H,W,ldg) T, ldg >= C and a multiple of 16 bytes; must not be g_out
+ *     wf           T fragments [C/16][C/32][64 lanes][8]: element (t, ks, l, j) = Wf[16 t + (l & 15)][32 ks + 8 (l >> 4) + j];
+ *                  sample b reads wf + b * wf_bstride elements (0: one matrix for all; a multiple of 16 bytes)
+ *     bf           fp32 [C], sample b reads bf + b * bf_bstride (0 or a multiple of 4)
+ *     w1           T fragments [2C/16][C/32][64][8] of the (2C, C) matrix, same element order;  b1 fp32 [2C]
+ *     dww          fp32 [9][2C], tap = 3 ky + kx;  dwb fp32 [2C]
+ *     g_out        (B,H,W,ldo) T, ldo >= C and a multiple of 16 bytes; channels >= C keep what they held
+ *     partials     optional fp32 [B][tiles][C]: slot (b, tile) = the sums of g over the tile's own pixels inside the image,
+ *                  taken from the fp32 values before rounding, in a fixed order (no atomics: two runs agree bit for bit).
+ *                  Every slot is written.  Needs w1.
+ *   All pointers that are read or written as vectors are 16-byte aligned.  HAT_EINVAL, before any launch, for a null or
+ *   misaligned pointer the chosen form needs, bad leading dimensions, B, H or W < 1, B > 65535, r_out == r_in,
+ *   g_out == gprev, form (a) without w1, partials without w1.
+ *
+ * hat_naf_fold  one workgroup per sample: mean = sum of the `tiles` partial slots / npix; s = wsca . mean + bsca;
+ *   wf[b] = T(beta[o] * w2[o][i] * s[i]) in hat_naf_half's fragment order ([B][C * C] T); bf[b][o] = beta[o] * b2[o]
+ *   ([B][C] fp32).  wsca, w2: fp32 [C][C] row major (out, in); bsca, b2, beta: fp32 [C].  The static second fold of a block
+ *   (gamma * ffn2) is made by the host packer.  HAT_EINVAL for a null pointer, wf / bf not 16-byte aligned, B, tiles or
+ *   npix < 1.
+ */
+typedef struct HatNafHalfDesc {
+    const float* r_in;
+    const void* gprev;
+    const void* wf;
+    const float* bf;
+    float* r_out;
+    const void* w1;
+    const float* b1;
+    const float* dww;
+    const float* dwb;
+    void* g_out;
+    float* partials;
+    int64_t wf_bstride;
+    int32_t bf_bstride;
+    int32_t B, H, W, C, ldr, ldg, ldo, dtype;
+    int32_t reserved0;
+} HatNafHalfDesc;
+int hat_naf_half_tiles(int32_t H, int32_t W);
+int hat_naf_half(const HatNafHalfDesc* d, void* stream);
+
+typedef struct HatNafFoldDesc {
+    const float* partials;
+    const float* wsca;
+    const float* bsca;
+    const float* w2;
+    const float* b2;
+    const float* beta;
+    void* wf;
+    float* bf;
+    int64_t npix;
+    int32_t B, tiles, C, dtype;
+} HatNafFoldDesc;
+int hat_naf_fold(const HatNafFoldDesc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

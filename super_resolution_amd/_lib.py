@@ -101,6 +101,22 @@ class HatYuvSurface(C.Structure):
                 ("sub_x", C.c_int32), ("sub_y", C.c_int32), ("depth", C.c_int32), ("msb", C.c_int32)]
 
 
+class HatNafHalfDesc(C.Structure):
+    """Mirror of `struct HatNafHalfDesc` (include/hat_mi355x.h)."""
+    _fields_ = [("r_in", C.c_void_p), ("gprev", C.c_void_p), ("wf", C.c_void_p), ("bf", C.c_void_p), ("r_out", C.c_void_p),
+                ("w1", C.c_void_p), ("b1", C.c_void_p), ("dww", C.c_void_p), ("dwb", C.c_void_p), ("g_out", C.c_void_p),
+                ("partials", C.c_void_p), ("wf_bstride", C.c_int64), ("bf_bstride", C.c_int32),
+                ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("ldr", C.c_int32), ("ldg", C.c_int32),
+                ("ldo", C.c_int32), ("dtype", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class HatNafFoldDesc(C.Structure):
+    """Mirror of `struct HatNafFoldDesc` (include/hat_mi355x.h)."""
+    _fields_ = [("partials", C.c_void_p), ("wsca", C.c_void_p), ("bsca", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
+                ("beta", C.c_void_p), ("wf", C.c_void_p), ("bf", C.c_void_p), ("npix", C.c_int64),
+                ("B", C.c_int32), ("tiles", C.c_int32), ("C", C.c_int32), ("dtype", C.c_int32)]
+
+
 _YUV_BLOCK = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]   # a 4:2:0 frame block
 
 # name -> (restype, argtypes); every symbol declared in include/hat_mi355x.h
@@ -217,6 +233,9 @@ SIGNATURES = {
                                           C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "hat_niqe_block_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p,
                                        C.c_void_p]),
+    "hat_naf_half_tiles": (C.c_int, [C.c_int32, C.c_int32]),
+    "hat_naf_half": (C.c_int, [C.POINTER(HatNafHalfDesc), C.c_void_p]),
+    "hat_naf_fold": (C.c_int, [C.POINTER(HatNafFoldDesc), C.c_void_p]),
 }
 
 _lib = None

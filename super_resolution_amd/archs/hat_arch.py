@@ -248,15 +248,27 @@ class HAT(nn.Module):
             self.upsample = _Upsample(upscale, num_feat)
             self.conv_last = nn.Conv2d(num_feat, in_chans, 3, 1, 1)
         self.apply(self._init_weights)
+        self._init_runtime(bool(kwargs.get("use_graph", False)))
+
+    def _init_runtime(self, use_graph: bool):
+        """What the device forward keeps beside the parameters: the packed engine, the weight-change tracking, the graph cache."""
         self._engine = None
         self._engine_key = None
         self._wver = 0   # bumped whenever the parameters may have changed (load_state_dict, .to()/.cuda()/..., explicit)
         self._plist = None
         self.register_load_state_dict_post_hook(HAT._post_load_hook)
         # extra (non-reference) switch: replay the forward as a HIP graph (also HAT_GRAPH=1 in the environment)
-        self.use_graph = bool(kwargs.get("use_graph", False)) or os.environ.get("HAT_GRAPH") == "1"
+        self.use_graph = use_graph or os.environ.get("HAT_GRAPH") == "1"
         self._graphs, self._graph_engine = collections.OrderedDict(), None
         self._graph_max = int(os.environ.get("HAT_GRAPH_CACHE", "4"))
+
+    def _anchor(self) -> torch.Tensor:
+        """The parameter whose device is the module's."""
+        return self.conv_first.weight
+
+    def _engine_args(self):
+        """(cfg, state dict) the engine packs."""
+        return self.cfg, self.state_dict()
 
     def _init_weights(self, m):  # hat_arch.py:761-768
         if isinstance(m, nn.Linear):
@@ -320,15 +332,15 @@ class HAT(nn.Module):
     def engine(self, device=None):
         """The packed-weight engine for the current parameters (re-packed when they change)."""
         from ..engine import HATEngine
-        device = torch.device(device) if device is not None else self.conv_first.weight.device
+        device = torch.device(device) if device is not None else self._anchor().device
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         key = self._weights_key(device)
         if self._engine is None or self._engine_key != key:
-            if self.conv_first.weight.device != device:
-                raise RuntimeError(f"input is on {device} but the parameters are on {self.conv_first.weight.device}: "
+            if self._anchor().device != device:
+                raise RuntimeError(f"input is on {device} but the parameters are on {self._anchor().device}: "
                                    f"move the module first (net.to('{device}'))")
-            self._engine = HATEngine(self.cfg, self.state_dict(), device, self.compute_dtype)
+            self._engine = HATEngine(*self._engine_args(), device, self.compute_dtype)
             self._engine_key = key
         return self._engine
 

@@ -146,6 +146,14 @@ class _Ocab(_Packed):
     qkvf = mlpf = esc = fh0 = fh2 = None
 
 
+class _Naf(_Packed):
+    """The NAF stem of HybridHATNAF (hybrid_hat_naf_arch.py:69-82): head / tail 3x3 convs packed for hat_conv, the blocks for
+    hat_naf_half / hat_naf_fold (packing.PackedNafBlock), c = naf_width."""
+
+    def __init__(self, c, head, blocks, tail):
+        self.c, self.head, self.blocks, self.tail = c, head, blocks, tail
+
+
 class _Group(_Packed):
     """One residual group (RHAG): its HABs, OCAB and 3x3 conv (None for resi_connection 'identity'), and the group-level routes:
     to_conv: the OCAB hands its result to the group conv as T rows;  conv_ln: (gamma, beta), gap_c of the LayerNorm the
@@ -334,6 +342,7 @@ class HATEngine:
         f32 = dict(dtype=torch.float32, device=dev)
         P = lambda w, b=None, **kw: ops.pack_conv_weight(sd[w], None if b is None else sd[b], self.dtype, dev, **kw)
         vec = lambda k: sd[k].detach().to(**f32).contiguous()
+        self.naf = self._pack_naf(sd) if cfg.get("naf") else None
         self.conv_first = P("conv_first.weight", "conv_first.bias")
         self.pe_norm = (vec("patch_embed.norm.weight"), vec("patch_embed.norm.bias")) if cfg.get("patch_norm", True) else None
         self.ape = vec("absolute_pos_embed").reshape(-1) if cfg.get("ape", False) else None   # (num_patches * C,)  :699-702
@@ -359,6 +368,17 @@ class HATEngine:
         self.conv_last_sweep = None   # row-sweep kernel (no LDS) for the 64 -> 3 conv at output resolution
         if ops.conv3x3_to_planes_supported(wl.shape[0], wl.shape[1], 16, self.dtype) and not self.opt.no_cab_sweep:
             self.conv_last_sweep = ops.pack_cab_squeeze(wl, sd["conv_last.bias"], dev) + (wl.shape[0],)
+
+    def _pack_naf(self, sd):
+        """cfg["naf"] = {width, blocks}: the stem in front of the network, parameters under "naf." (the rest of sd is HATX's own
+        surface).  Widths hat_naf_half is not built for and an in_chans other than 3 are refused here: there is no other path."""
+        c, nb = int(self.cfg["naf"]["width"]), int(self.cfg["naf"]["blocks"])
+        if c not in ops.NAF_WIDTHS:
+            raise ValueError(f"naf_width {c} is not supported: hat_naf_half is built for {' and '.join(map(str, ops.NAF_WIDTHS))} channels")
+        if self.cfg["in_chans"] != 3:
+            raise ValueError(f"the NAF stem's head and tail convs are packed for in_chans 3, got {self.cfg['in_chans']}")
+        P = lambda k: ops.pack_conv_weight(sd[f"naf.{k}.weight"], sd[f"naf.{k}.bias"], self.dtype, self.dev)
+        return _Naf(c, P("head"), [ops.pack_naf_block(sd, f"naf.body.{i}", self.dtype, self.dev) for i in range(nb)], P("tail"))
 
     def _pack_hab(self, sd, p):
         """Packs one HAB.  Sets tail144_ok / tail180_ok; _resolve turns them into the tail route once the whole net is packed."""
@@ -585,6 +605,11 @@ class HATEngine:
             w["cstat_l"], w["cstat_g"] = z(B, 72, dtype=f), z(B, 72, dtype=f)
             w["estat_l"], w["estat_g"] = z(B, 256, dtype=f), z(B, 256, dtype=f)
             w["rs_tmp"], w["rs_cnt"] = z(B, 64, 256, dtype=f), torch.zeros(B, dtype=torch.int32, device=dev)
+        if self.naf is not None:   # the stem's two fp32 streams, two gated maps, pool partials, per-sample fold and result
+            c = self.naf.c
+            w["naf_sA"], w["naf_sB"], w["naf_gA"], w["naf_gB"] = z(B, N, c, dtype=f), z(B, N, c, dtype=f), z(B, N, c), z(B, N, c)
+            w["naf_part"], w["naf_wf"], w["naf_bf"] = z(B, ops.naf_tiles(H, W), c, dtype=f), z(B, c * c), z(B, c, dtype=f)
+            w["x_naf"] = z(B, self.cfg["in_chans"], H, W, dtype=f)
         h, wd = H, W
         w["ups"] = []
         for _, r in self.ups:
@@ -913,6 +938,9 @@ class HATEngine:
         band's output rows (ghost rows included; the driver keeps the owned ones).
         sink (a _Sink; the unsharded forward only): the forward fills and returns sink.out, bytes, instead of fp32 planes."""
         self._check_input(x)
+        if band is not None and self.naf is not None:
+            raise NotImplementedError("a row band of a HybridHATNAF frame is not implemented: the stem's SCA pool needs one more "
+                                      "reduce exchange and two more halo rows per NAF block")
         B, _, H, W = x.shape
         x = x.to(torch.float32).contiguous()
         w = dict(self._workspace(B, H, W, tag=(None if band is None else ("band", band.idx, band.n))))
@@ -930,6 +958,8 @@ class HATEngine:
             raise RuntimeError(sink.band_refusal)
         else:
             y = sink.out
+        if self.naf is not None:
+            x = self._naf_stem(f, x)
         self._head(f, x)
         for G in self.layers:
             for hb in G.habs:   # HAB                                                            :217-238
@@ -942,6 +972,38 @@ class HATEngine:
         return y
 
     # ------------------------------------------------------------------------------------------ stage steps
+    def _naf_stem(self, f: _Fwd, x):
+        """x + tail(body(head(x))) -> w["x_naf"], fp32 planes as _head reads them           hybrid_hat_naf_arch.py:77-82, :130-131
+        head: hat_conv 3 -> c into the fp32 stream.  Per block: half (pw1, dw, gate; pool partials), hat_naf_fold (SCA into pw2),
+        half (+ beta pw2 as its form (b); ffn1, ffn_dw, gate).  The block's last 1x1, gamma * ffn2, is the form (b) of the NEXT
+        half; after the last block one projection-only launch.  The stream and the gated map alternate between two buffers
+        each: a half reads its neighbours' halo pixels of both while it writes."""
+        st, w, c = self.naf, f.w, self.naf.c
+        kw = dict(B=f.B, H=f.H, W=f.W, C_=c, dtype=f.dt)
+        s_in, s_out, g_in, g_out = w["naf_sA"], w["naf_sB"], w["naf_gA"], w["naf_gB"]
+        ops.conv(st.head, x, s_in, **f.geo, ldx=0, ldo=c, x_mode=X_NCHW_F32_MEAN, out_mode=O_NHWC_F32)
+        fold = None   # (wf, bf) of the previous block's gamma * ffn2
+        for blk in st.blocks:
+            if fold is None:
+                ops.naf_half(s_in, g_out, blk.w1, blk.b1, blk.dww, blk.dwb, partials=w["naf_part"], **kw)
+            else:
+                ops.naf_half(s_in, g_out, blk.w1, blk.b1, blk.dww, blk.dwb, gprev=g_in, wf=fold[0], bf=fold[1], r_out=s_out,
+                             partials=w["naf_part"], **kw)
+                s_in, s_out = s_out, s_in
+            g_in, g_out = g_out, g_in
+            ops.naf_fold(w["naf_part"], blk, w["naf_wf"], w["naf_bf"], **kw)
+            ops.naf_half(s_in, g_out, blk.w1f, blk.b1f, blk.dwwf, blk.dwbf, gprev=g_in, wf=w["naf_wf"], wf_bstride=c * c,
+                         bf=w["naf_bf"], bf_bstride=c, r_out=s_out, **kw)
+            s_in, s_out = s_out, s_in
+            g_in, g_out = g_out, g_in
+            fold = (blk.wf2, blk.bf2)
+        if fold is not None:
+            ops.naf_half(s_in, None, None, None, None, None, gprev=g_in, wf=fold[0], bf=fold[1], r_out=s_out, **kw)
+            s_in = s_out
+        ops.conv(st.tail, s_in, w["x_naf"], **f.geo, ldx=c, ldo=0, x_mode=X_NHWC_F32, out_mode=O_NCHW_F32)
+        ops.add_f32(w["x_naf"], x, w["x_naf"], B=f.B, n=x.shape[1] * f.N)
+        return w["x_naf"]
+
     def _head(self, f: _Fwd, x):
         """(x - mean) * img_range ; conv_first ; patch_embed LN ; + absolute_pos_embed     :836-838, :849-853"""
         w, tA, C = f.w, f.w["tA"], self.C

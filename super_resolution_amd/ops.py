@@ -12,9 +12,11 @@ import torch
 
 from . import _lib
 from ._lib import (ACT_GELU, ACT_LRELU, ACT_NONE, HAT_BF16, HAT_F32, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T,
-                   X_NCHW_F32_MEAN, X_NHWC_F32, X_NHWC_T, HatAggrCabDesc, HatCabFoldDesc, HatConvDesc, HatFfnDesc, HatHabTailDesc, HatMlpDesc)
+                   X_NCHW_F32_MEAN, X_NHWC_F32, X_NHWC_T, HatAggrCabDesc, HatCabFoldDesc, HatConvDesc, HatFfnDesc, HatHabTailDesc, HatMlpDesc, HatNafFoldDesc,
+                   HatNafHalfDesc)
 # host-side weight packing lives in packing.py; ops.pack_* / ops.Packed* stay the names the engine, the tools and the tests use
-from .packing import (FP16_SAFE, KC, TORCH_DTYPE, PackedConv, PackedFFN, PackedMlp, choose_nt, choose_nt_linear,  # noqa: F401
+from .packing import (FP16_SAFE, KC, NAF_WIDTHS, TORCH_DTYPE, PackedConv, PackedFFN, PackedMlp, PackedNafBlock, choose_nt,  # noqa: F401
+                      choose_nt_linear, naf_ffn_fold, naf_frags, pack_naf_block,
                       ffn_fp16_range_bound, pack_cab_squeeze, pack_cab_w2f, pack_conv_weight, pack_ffn, pack_ffn2, pack_ffn3,
                       pack_linear_weight, pack_ocab_mlp, pack_ocab_qkv, pack_pointwise)
 
@@ -255,6 +257,46 @@ def sgfn_gate(u, wdw, bdw, out, *, B: int, H: int, W: int, half: int, ldu: int, 
     lib = _lib.load()
     _timed(f"sgfn_gate_kernel<{_TNAME[dtype]}>", 2.0 * 9 * half * B * H * W, lambda: _lib.check(
         lib.hat_sgfn_gate(_ptr(u), _ptr(wdw), _ptr(bdw), _ptr(out), B, H, W, half, ldu, ldo, dtype, _stream()), "hat_sgfn_gate"))
+
+
+# ------------------------------------------------------------------------------------------------
+# the NAF stem of HybridHATNAF (hat_naf_half / hat_naf_fold)
+# ------------------------------------------------------------------------------------------------
+def naf_tiles(H: int, W: int) -> int:
+    """Tiles per sample of hat_naf_half = slots per sample of its pool partials."""
+    n = _lib.load().hat_naf_half_tiles(H, W)
+    _lib.check(min(n, 0), "hat_naf_half_tiles")
+    return n
+
+
+def naf_half(r_in, g_out, w1, b1, dww, dwb, *, B: int, H: int, W: int, C_: int, dtype: int, ldr: Optional[int] = None, ldo: Optional[int] = None,
+             gprev=None, ldg: Optional[int] = None, wf=None, wf_bstride: int = 0, bf=None, bf_bstride: int = 0, r_out=None, partials=None):
+    """One half of a NAFBlock (hat_naf_half): g_out = gate(dw3x3(W1 r + b1)) with r = r_in (form a) or, with gprev / wf / bf /
+    r_out, r = r_in + Wf gprev + bf, also written to r_out (form b).  w1 None (form b): only r_out, the stem's last projection.
+    partials: the (B, naf_tiles, C_) fp32 pool partials of g_out."""
+    lib = _lib.load()
+    d = HatNafHalfDesc()
+    d.r_in, d.gprev, d.wf, d.bf, d.r_out = _ptr(r_in), _ptr(gprev), _ptr(wf), _ptr(bf), _ptr(r_out)
+    d.w1, d.b1, d.dww, d.dwb, d.g_out, d.partials = _ptr(w1), _ptr(b1), _ptr(dww), _ptr(dwb), _ptr(g_out), _ptr(partials)
+    d.wf_bstride, d.bf_bstride = wf_bstride, bf_bstride
+    d.B, d.H, d.W, d.C, d.dtype = B, H, W, C_, dtype
+    d.ldr, d.ldg, d.ldo = (C_ if ldr is None else ldr), (C_ if ldg is None else ldg), (C_ if ldo is None else ldo)
+    form = "a" if gprev is None else ("b" if w1 is not None else "proj")
+    es, npx = (2 if dtype == HAT_BF16 else 4), float(B * H * W)
+    flops = 2.0 * npx * C_ * ((2 * C_ if w1 is not None else 0) + (C_ if gprev is not None else 0)) + (2.0 * 9 * 2 * C_ * npx if w1 is not None else 0.0)
+    nbytes = npx * C_ * (4 + (4 + es if gprev is not None else 0) + (es if w1 is not None else 0))
+    _timed(f"naf_half_kernel<{_TNAME[dtype]}, {C_}>", flops, lambda: _lib.check(lib.hat_naf_half(C.byref(d), _stream()), f"hat_naf_half(c={C_}, form {form})"),
+           tag=f"naf {form} c{C_} {H}x{W}{' pool' if partials is not None else ''}", nbytes=nbytes)
+
+
+def naf_fold(partials, blk: PackedNafBlock, wf, bf, *, B: int, H: int, W: int, C_: int, dtype: int):
+    """The SCA of a NAFBlock folded into its pw2 (hat_naf_fold): wf (B, C_ * C_) T fragments, bf (B, C_) fp32 for naf_half."""
+    lib = _lib.load()
+    d = HatNafFoldDesc()
+    d.partials, d.wsca, d.bsca, d.w2, d.b2, d.beta = _ptr(partials), _ptr(blk.wsca), _ptr(blk.bsca), _ptr(blk.w2), _ptr(blk.b2), _ptr(blk.beta)
+    d.wf, d.bf, d.npix, d.B, d.tiles, d.C, d.dtype = _ptr(wf), _ptr(bf), H * W, B, naf_tiles(H, W), C_, dtype
+    _timed(f"naf_fold_kernel<{_TNAME[dtype]}, {C_}>", 0.0, lambda: _lib.check(lib.hat_naf_fold(C.byref(d), _stream()), f"hat_naf_fold(c={C_})"),
+           tag=f"naf fold c{C_} {H}x{W}")
 
 
 LOG2E = 1.4426950408889634

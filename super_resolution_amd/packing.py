@@ -361,3 +361,47 @@ def pack_ffn3(fc1_w, fc1_b, dw_w, dw_b, fc2_w, fc2_b, ln_g, ln_b, device) -> Pac
     dww = _pad(_ffn_dw_record(Wd, bd, chunks).reshape(chunks, 640), chunks, 1024)
     return _packed_ffn("tail3", _ffn_fc1(W1, b1, chunks, ks, True).to(torch.bfloat16), _ffn_fc2(W2, nt, chunks, "natural").to(torch.float16),
                        dww.to(torch.float16), torch.zeros(4), torch.zeros(4), _pad(b2, 256), chunks, C_, hid, nt, ks, device)
+
+
+# ------------------------------------------------------------------------------------------------
+# the NAF stem of HybridHATNAF: hat_naf_half / hat_naf_fold (hybrid_hat_naf_arch.py:16-82)
+# ------------------------------------------------------------------------------------------------
+NAF_WIDTHS = (64, 32)   # channel counts hat_naf_half is instantiated for
+
+
+class PackedNafBlock:
+    """One NAFBlock in hat_naf_half's / hat_naf_fold's operand layouts (include/hat_mi355x.h "NAF stem"): per half the (2c, c)
+    1x1 as A fragments [2c/16][c/32][64][8] T (w1), its bias [2c], the depthwise taps [9][2c] and bias [2c], all fp32; the
+    attention half's fold inputs wsca, w2 [c][c], bsca, b2, beta [c] fp32 (hat_naf_fold makes Wf per sample); the FFN half's
+    static fold wf2 = T fragments of gamma * ffn2.weight [c/16][c/32][64][8], bf2 = gamma * ffn2.bias [c] fp32."""
+    __slots__ = ("w1", "b1", "dww", "dwb", "wsca", "bsca", "w2", "b2", "beta", "w1f", "b1f", "dwwf", "dwbf", "wf2", "bf2")
+
+
+def naf_frags(M: torch.Tensor, dtype: int, device) -> torch.Tensor:
+    """A (rows, c) matrix of a NAF 1x1 conv -> hat_naf_half's A fragments [rows/16][c/32][64][8] of type T."""
+    return frags(M).to(TORCH_DTYPE[dtype]).contiguous().to(device)
+
+
+def naf_ffn_fold(gamma: torch.Tensor, ffn2_w: torch.Tensor, ffn2_b: torch.Tensor):
+    """out = y + gamma * ffn2(g2) as y + Wf . g2 + bf: Wf = gamma[o] * W[o][i], bf = gamma * b (fp32, host)."""
+    gam = _f32(gamma).reshape(-1)
+    W = _f32(ffn2_w).reshape(gam.shape[0], -1)
+    return gam[:, None] * W, gam * _f32(ffn2_b)
+
+
+def pack_naf_block(sd, p: str, dtype: int, device) -> PackedNafBlock:
+    """sd[p + '.pw1.weight'] ... of one NAFBlock (state-dict names of hybrid_hat_naf_arch.py:27-46) -> PackedNafBlock."""
+    c = sd[p + ".beta"].numel()
+    if c not in NAF_WIDTHS:
+        raise ValueError(f"naf_width {c} is not supported: hat_naf_half is built for {' and '.join(map(str, NAF_WIDTHS))} channels")
+    vec = lambda k: _f32(sd[p + k]).reshape(-1).contiguous().to(device)
+    mat = lambda k: _f32(sd[p + k]).reshape(sd[p + k].shape[0], -1)
+    taps = lambda k: _f32(sd[p + k]).reshape(2 * c, 9).t().contiguous().to(device)
+    b = PackedNafBlock()
+    b.w1, b.b1, b.dww, b.dwb = naf_frags(mat(".pw1.weight"), dtype, device), vec(".pw1.bias"), taps(".dw.weight"), vec(".dw.bias")
+    b.wsca, b.bsca = mat(".sca.1.weight").contiguous().to(device), vec(".sca.1.bias")
+    b.w2, b.b2, b.beta = mat(".pw2.weight").contiguous().to(device), vec(".pw2.bias"), vec(".beta")
+    b.w1f, b.b1f, b.dwwf, b.dwbf = naf_frags(mat(".ffn1.weight"), dtype, device), vec(".ffn1.bias"), taps(".ffn_dw.weight"), vec(".ffn_dw.bias")
+    wf2, bf2 = naf_ffn_fold(sd[p + ".gamma"], sd[p + ".ffn2.weight"], sd[p + ".ffn2.bias"])
+    b.wf2, b.bf2 = naf_frags(wf2, dtype, device), bf2.contiguous().to(device)
+    return b

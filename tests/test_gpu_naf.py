@@ -1,0 +1,309 @@
+"""HybridHATNAF on the device: hat_naf_half and hat_naf_fold against the fp64 restatement (tests/naf_ref.py) on the kernels' own
+rounded operands, the stem and the whole model against the reference's goldens, and the equalities between the paths that end
+in the same forward.  hat_naf_half runs one workgroup per tile (no persistent loop), so there is no multi-trip case to add."""
+import numpy as np
+import pytest
+import torch
+
+import ensemble_ref as E
+import naf_ref as R
+from helpers import check, golden, max_abs, q, rnd
+from oracle import hat_oracle as O
+from super_resolution_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+WIDTHS = [64, 32]
+#          5x3: smaller than a tile, every pixel is border;  20x37: ragged in both axes;  33x64, B = 2: a tile row of one pixel row
+SHAPES = [(1, 5, 3), (1, 20, 37), (2, 33, 64)]
+
+
+def _dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    return torch.device("cuda:0")
+
+
+def _rows(x_bhwc, ld, tdt, dev, fill):
+    """(B,H,W,C) -> device (B, H*W, ld) rows of dtype tdt whose pad channels hold `fill` (nothing may read them)."""
+    b, h, w, c = x_bhwc.shape
+    out = torch.full((b, h * w, ld), fill, dtype=tdt, device=dev)
+    out[:, :, :c] = x_bhwc.reshape(b, h * w, c).to(dev).to(tdt)
+    return out
+
+
+def _unfrag(wf, rows, cols):
+    wf = wf.float().cpu().reshape(rows // 16, cols // 32, 64, 8)
+    M = torch.zeros(rows, cols)
+    for lane in range(64):
+        for j in range(8):
+            M[(lane & 15)::16, 8 * (lane >> 4) + j::32] = wf[:, :, lane, j]
+    return M
+
+
+def _half(dtype, c, form, pool, B, H, W, dev, b1=None, dw=None):
+    """Runs hat_naf_half once; returns (g (B,H,W,c) as stored, g_ref fp64, r_out / r_ref or None, partials or None, raw buffers)."""
+    from super_resolution_amd import ops
+    dt = ops.DTYPE_CODE[dtype]
+    tdt = ops.TORCH_DTYPE[dt]
+    key = f"{c}{form}{B}{H}{W}"
+    w1 = q(rnd("w1" + key, (2 * c, c), std=c ** -0.5), dtype)
+    b1 = rnd("b1" + key, (2 * c,), std=0.1) if b1 is None else b1
+    dw = rnd("dw" + key, (2 * c, 1, 3, 3), std=1.0 / 3) if dw is None else dw
+    db = rnd("db" + key, (2 * c,), std=0.1)
+    r = rnd("r" + key, (B, H, W, c))
+    ldr, ldg, ldo = c + 4, c + 8, c + 8
+    kw = {}
+    if form == "a":
+        r = q(r, dtype)                       # the stored stream is the MFMA operand
+        r_ref = r.double()
+    else:
+        gp = q(rnd("gp" + key, (B, H, W, c)), dtype)
+        Wf, bf = q(rnd("wf" + key, (B, c, c), std=c ** -0.5), dtype), rnd("bf" + key, (B, c), std=0.1)
+        r_ref = r.double() + torch.einsum("boi,bhwi->bhwo", Wf.double(), gp.double()) + bf.double()[:, None, None, :]
+        wf = torch.stack([ops.naf_frags(Wf[b], dt, dev) for b in range(B)]).reshape(B, c * c)
+        kw = dict(gprev=_rows(gp, ldg, tdt, dev, 1e30), ldg=ldg, wf=wf, wf_bstride=c * c, bf=bf.to(dev), bf_bstride=c,
+                  r_out=torch.full((B, H * W, ldr), float("nan"), device=dev))
+    g_out = torch.full((B, H * W, ldo), float("nan"), dtype=tdt, device=dev)
+    part = torch.full((B, ops.naf_tiles(H, W), c), float("nan"), device=dev) if pool else None
+    ops.naf_half(_rows(r, ldr, torch.float32, dev, float("nan")), g_out, ops.naf_frags(w1, dt, dev), b1.to(dev),
+                 dw.reshape(2 * c, 9).t().contiguous().to(dev), db.to(dev), B=B, H=H, W=W, C_=c, dtype=dt, ldr=ldr, ldo=ldo, partials=part, **kw)
+    torch.cuda.synchronize()
+    g_ref = R.gate_half(r_ref.permute(0, 3, 1, 2), w1, b1, dw, db).permute(0, 2, 3, 1)
+    return g_out, g_ref, kw.get("r_out"), r_ref, part
+
+
+@pytest.mark.parametrize("pool", [True, False], ids=["pool", "nopool"])
+@pytest.mark.parametrize("form", ["a", "b"])
+@pytest.mark.parametrize("c", WIDTHS)
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_naf_half(dtype, c, form, pool):
+    dev = _dev()
+    for B, H, W in SHAPES:
+        g_out, g_ref, r_out, r_ref, part = _half(dtype, c, form, pool, B, H, W, dev)
+        what = f"naf_half {dtype} c{c} {form} {B}x{H}x{W}"
+        g = g_out[:, :, :c].float().cpu().reshape(B, H, W, c)
+        check(g, g_ref, dtype, what)                                   # (asserts that everything written is finite)
+        assert torch.isnan(g_out[:, :, c:].float()).all(), what + ": pad channels of g_out were written"
+        if form == "b":
+            check(r_out[:, :, :c].cpu().reshape(B, H, W, c), r_ref, "f32" if dtype == "f32" else "bf16", what + " r_out")
+            assert torch.isnan(r_out[:, :, c:]).all(), what + ": pad channels of r_out were written"
+            if dtype == "bf16":   # the stream itself is fp32: only its Wf . gprev term carries bf16 operands, exact products, fp32 sums
+                assert max_abs(r_out[:, :, :c].cpu().reshape(B, H, W, c), r_ref) <= 2e-5 * max(1.0, float(r_ref.abs().max())), what
+        if pool:
+            assert torch.isfinite(part).all(), what + ": a partials slot was not written"
+            got, stored = part.double().sum(1).cpu(), g.double().sum(dim=(1, 2))
+            mass = g.double().abs().sum(dim=(1, 2))
+            if dtype == "f32":
+                assert float((got - stored).abs().max() / stored.abs().max()) <= 1e-5, what
+            else:   # the stored map is rounded to bf16, the pool is not: at most half an ulp (2^-9 relative) per term, x2 for the fp32 sums
+                assert bool(((got - stored).abs() <= mass * 2.0 ** -8).all()), what
+
+
+@pytest.mark.parametrize("c", WIDTHS)
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_naf_half_zero_pads_u_not_x(dtype, c):
+    """pw1.bias = 0.5 and dw.weight = 1: with the wrong rule (u = bias outside the image) every border pixel is off by O(bias)."""
+    dev = _dev()
+    B, H, W = 1, 9, 17
+    b1, dw = torch.full((2 * c,), 0.5), torch.ones(2 * c, 1, 3, 3)
+    g_out, g_ref, _, r_ref, _ = _half(dtype, c, "a", False, B, H, W, dev, b1=b1, dw=dw)
+    g = g_out[:, :, :c].float().cpu().reshape(B, H, W, c)
+    border = torch.ones(H, W, dtype=torch.bool)
+    border[1:-1, 1:-1] = False
+    check(g[:, border], g_ref[:, border], dtype, f"naf_half border {dtype} c{c}")
+    check(g, g_ref, dtype, f"naf_half zero-pad {dtype} c{c}")
+    key = f"{c}a{B}{H}{W}"
+    wrong = R.gate_half(r_ref.permute(0, 3, 1, 2), q(rnd("w1" + key, (2 * c, c), std=c ** -0.5), dtype), b1, dw, rnd("db" + key, (2 * c,), std=0.1),
+                        zero_pad_u=False).permute(0, 2, 3, 1)
+    with pytest.raises(AssertionError):      # the test can tell the two rules apart
+        check(g[:, border], wrong[:, border], dtype, "wrong rule")
+
+
+@pytest.mark.parametrize("c", WIDTHS)
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_naf_fold(dtype, c):
+    dev = _dev()
+    from super_resolution_amd import ops
+    dt = ops.DTYPE_CODE[dtype]
+    B, H, W = 2, 20, 37
+    tiles = ops.naf_tiles(H, W)
+    part = rnd(f"part{c}", (B, tiles, c), std=3.0)
+    blk = ops.PackedNafBlock()
+    blk.wsca, blk.bsca = rnd("wsca", (c, c), std=c ** -0.5).to(dev), rnd("bsca", (c,), std=0.1).to(dev)
+    blk.w2, blk.b2, blk.beta = rnd("w2", (c, c), std=c ** -0.5).to(dev), rnd("b2", (c,), std=0.1).to(dev), rnd("beta", (c,), std=0.5).to(dev)
+    wf = torch.full((B, c * c), float("nan"), dtype=ops.TORCH_DTYPE[dt], device=dev)
+    bf = torch.full((B, c), float("nan"), device=dev)
+    ops.naf_fold(part.to(dev), blk, wf, bf, B=B, H=H, W=W, C_=c, dtype=dt)
+    ops.naf_fold(part.to(dev), blk, wf2 := torch.empty_like(wf), bf2 := torch.empty_like(bf), B=B, H=H, W=W, C_=c, dtype=dt)
+    torch.cuda.synchronize()
+    Wf, bfr = R.fold(part.double().sum(1) / (H * W), blk.wsca.cpu(), blk.bsca.cpu(), blk.w2.cpu(), blk.b2.cpu(), blk.beta.cpu())
+    got = torch.stack([_unfrag(wf[b], c, c) for b in range(B)])
+    check(got, Wf, dtype, f"naf_fold wf {dtype} c{c}", f32_tol=2e-5)        # (bf16: the stored type's bars; fp32: the issue's 2e-5)
+    check(bf.cpu(), bfr[None].expand(B, c), "f32", f"naf_fold bf c{c}", f32_tol=2e-5)
+    assert torch.equal(wf, wf2) and torch.equal(bf, bf2), "two runs agree bit for bit"
+
+
+def test_naf_half_is_deterministic():
+    dev = _dev()
+    a = _half("bf16", 64, "b", True, 2, 33, 64, dev)
+    b = _half("bf16", 64, "b", True, 2, 33, 64, dev)
+    assert torch.equal(a[0][:, :, :64], b[0][:, :, :64]) and torch.equal(a[4], b[4]) and torch.equal(a[2][:, :, :64], b[2][:, :, :64])
+
+
+# ---------------------------------------------------------------------------------------------- model level
+def _net(c, dtype, dev, **kw):
+    from super_resolution_amd.registry import build_network
+    name = R.NAMES[c]
+    net = build_network(dict(type="HybridHATNAF", compute_dtype=dtype, **R.net_kwargs(name), **kw)).eval()
+    net.load_state_dict(R.synth_sd(name), strict=True)
+    return net.to(dev)
+
+
+def _gold(c):
+    gold = golden(f"whole_{R.NAMES[c]}.npz")
+    return gold, synth.synth_input(R.X_SEED, tuple(int(v) for v in gold["x_shape"]))
+
+
+@pytest.mark.parametrize("c", WIDTHS)
+def test_stem_and_model_fp32_vs_reference(c):
+    dev = _dev()
+    gold, x = _gold(c)
+    net = _net(c, "f32", dev)
+    y = net(x.to(dev))
+    torch.cuda.synchronize()
+    x_naf = net.engine()._workspace(1, x.shape[2], x.shape[3])["x_naf"].cpu()
+    e_stem, e_y = max_abs(x_naf, gold["x_naf"]), max_abs(y.cpu(), gold["y"])
+    print(f"NAF-GOLDEN w{c}/f32: x_naf max-abs {e_stem:.3e}  y max-abs {e_y:.3e}")
+    assert e_stem <= 1e-4, e_stem
+    assert y.shape == gold["y"].shape and e_y <= 1e-4, e_y
+
+
+@pytest.mark.parametrize("c", WIDTHS)
+def test_model_bf16_vs_reference(c):
+    """The project's HAT / HATX bar: >= 40 dB and max-abs <= 0.08 against the reference's fp32 output."""
+    dev = _dev()
+    gold, x = _gold(c)
+    net = _net(c, "bf16", dev)
+    y = net(x.to(dev)).cpu()
+    x_naf = net.engine()._workspace(1, x.shape[2], x.shape[3])["x_naf"].cpu()
+    ref = torch.from_numpy(gold["y"])
+    err, psnr = max_abs(y, ref), O.psnr_float(y, ref)
+    print(f"NAF-GOLDEN w{c}/bf16: x_naf max-abs {max_abs(x_naf, gold['x_naf']):.3e}  y max-abs {err:.3e} PSNR {psnr:.2f} dB")
+    assert psnr >= 40.0 and err <= 0.08, (psnr, err)
+
+
+def test_graph_replay_equals_eager():
+    dev = _dev()
+    _, x = _gold(32)
+    x = x.to(dev)
+    eager = _net(32, "f32", dev)(x)
+    g = _net(32, "f32", dev, use_graph=True)
+    y1, y2 = g(x), g(x)
+    torch.cuda.synchronize()
+    assert torch.equal(y1, eager) and torch.equal(y2, eager)
+
+
+def test_plan_replay_equals_forward(tmp_path):
+    dev = _dev()
+    from super_resolution_amd import plan
+    shape = (1, 3, 16, 24)
+    net = _net(32, "f32", dev)
+    path = str(tmp_path / "hybrid.hatplan")
+    info = plan.export_plan(net, shape, path)
+    x = synth.synth_input(R.X_SEED + 1, shape).to(dev)
+    ref = net(x).clone()
+    p = plan.Plan(path)
+    assert p.dims[:4] == list(shape) and p.launches == info["launches"]
+    for fill in (5.0, 0.0):       # (the second forward reuses the plan's workspace)
+        y = torch.full((1, 3, 32, 48), fill, device=dev)
+        p.forward(x, y, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert torch.equal(y, ref)
+    p.close()
+
+
+def test_forward_u8_is_forward_then_the_reference_rounding():
+    dev = _dev()
+    from super_resolution_amd import ops
+    net = _net(32, "f32", dev)
+    frame = torch.from_numpy(np.random.default_rng(5).integers(0, 256, (1, 16, 24, 3), dtype=np.uint8)).to(dev)
+    x = torch.empty(1, 3, 16, 24, device=dev)
+    ops.u8_to_planes(frame, x)
+    y = net(x)
+    ref = torch.round(y.clamp(0.0, 1.0) * 255.0).to(torch.uint8).permute(0, 2, 3, 1).contiguous()    # tensor2img: round half to even
+    got = net.forward_u8(frame)
+    torch.cuda.synchronize()
+    assert got.dtype == torch.uint8 and torch.equal(got, ref)
+    assert torch.equal(net.forward_to_u8(x), ref)
+
+
+def test_forward_ensemble():
+    dev = _dev()
+    _, x = _gold(32)
+    x = x.to(dev)
+    net = _net(32, "f32", dev)
+    plain = net(x)
+    one, eight = net.forward_ensemble(x, 1), net.forward_ensemble(x, 8)
+    ref = E.ensemble(net, x, 8)
+    torch.cuda.synchronize()
+    assert torch.equal(one, plain)
+    assert torch.equal(eight, ref) and not torch.equal(eight, plain)      # (the existing ensemble tolerance: bit for bit)
+
+
+def test_in_place_edit_of_a_stem_parameter_repacks():
+    dev = _dev()
+    _, x = _gold(32)
+    x = x.to(dev)
+    net = _net(32, "f32", dev)
+    y1 = net(x).clone()
+    eng = net.engine()
+    with torch.no_grad():
+        net.naf.body[0].beta.mul_(2.0)
+    y2 = net(x)
+    torch.cuda.synchronize()
+    assert net.engine() is not eng and not torch.equal(y1, y2)
+    with torch.no_grad():
+        net.naf.body[0].beta.mul_(0.5)
+    assert torch.equal(net(x), y1)
+
+
+def test_band_and_width_refusals_on_the_device():
+    dev = _dev()
+    net = _net(32, "f32", dev)
+    with pytest.raises(NotImplementedError, match="SCA pool"):
+        net.forward_bands(torch.zeros(1, 3, 64, 16, device=dev), 2)
+    from super_resolution_amd.registry import build_network
+    bad = build_network(dict(type="HybridHATNAF", naf_width=48, naf_blocks=1, hat_kwargs=R.net_kwargs(R.NAMES[32])["hat_kwargs"])).eval().to(dev)
+    with pytest.raises(ValueError, match="naf_width 48"):
+        bad(torch.zeros(1, 3, 16, 16, device=dev))
+
+
+def test_yaml_reaches_the_network_through_test_and_plan(tmp_path):
+    """`python -m super_resolution_amd.test -opt x.yml` and `python -m super_resolution_amd.plan` with network_g.type HybridHATNAF
+    on synthesized weights (as in the reference, HATModel reads network_g.window_size: the YAML sets it at top level)."""
+    dev = _dev()
+    import yaml
+    from super_resolution_amd import data as D, metrics as M, plan, test as T
+    name = R.NAMES[32]
+    sd = R.synth_sd(name)
+    torch.save({"params": sd}, tmp_path / "net.pth")
+    D.write_image(M.tensor2img(synth.synth_input(30, (1, 3, 21, 19))), str(tmp_path / "lq" / "im0.png"))
+    D.write_image(M.tensor2img(synth.synth_input(40, (1, 3, 42, 38))), str(tmp_path / "gt" / "im0.png"))
+    opt = {"name": "toy", "model_type": "HATModel", "scale": 2, "num_gpu": 1,
+           "datasets": {"test_1": {"name": "Toy", "type": "PairedImageDataset", "dataroot_gt": str(tmp_path / "gt"),
+                                   "dataroot_lq": str(tmp_path / "lq"), "io_backend": {"type": "disk"}}},
+           "network_g": dict(type="HybridHATNAF", window_size=8, compute_dtype="f32", **R.net_kwargs(name)),
+           "path": {"pretrain_network_g": str(tmp_path / "net.pth"), "strict_load_g": True, "param_key_g": "params",
+                    "visualization": str(tmp_path / "vis")},
+           "val": {"save_img": True, "suffix": None, "metrics": {"psnr": {"type": "calculate_psnr", "crop_border": 2, "test_y_channel": True}}}}
+    (tmp_path / "opt.yml").write_text(yaml.safe_dump(opt))
+    res = T.main(["-opt", str(tmp_path / "opt.yml")])
+    net = _net(32, "f32", dev)
+    lq = D.read_image(str(tmp_path / "lq" / "im0.png")).unsqueeze(0).to(dev)
+    y = net(torch.nn.functional.pad(lq, (0, 5, 0, 3), "reflect"))[:, :, :42, :38]
+    gt8 = M.tensor2img(D.read_image(str(tmp_path / "gt" / "im0.png")))
+    want = M.calculate_metric({"img": M.tensor2img(y.cpu()), "img2": gt8}, opt["val"]["metrics"]["psnr"])
+    assert res["Toy"]["images"][0]["psnr"] == pytest.approx(want, abs=1e-3)
+    info = plan.main(["-opt", str(tmp_path / "opt.yml"), "--shape", "1", "16", "24", "-o", str(tmp_path / "net.hatplan")])
+    assert info["launches"] > 20 and (tmp_path / "net.hatplan").stat().st_size == info["file_bytes"]
