@@ -940,6 +940,73 @@ typedef struct HatNafFoldDesc {
 } HatNafFoldDesc;
 int hat_naf_fold(const HatNafFoldDesc* d, void* stream);
 
+/*
+ * ESC: what the ESC network (esc_arch.py:256-386) needs beyond hat_conv / hat_linear / hat_esc_weights / hat_esc_conv13.
+ * dim = 64 channels, fp32 or bf16 storage (the fp32 instantiations are the parity path).
+ *
+ * hat_esc_convffn  ConvFFN (esc_arch.py:148-159) in one launch, on tiles of 8 x 12 pixels with a 1-pixel halo, one workgroup
+ *   per tile (hat_esc_convffn_tiles(H, W) per sample):
+ *       n = ln_g ? LayerNorm(x; ln_g, ln_b, ln_eps) : x;  h = gelu(W1 n + b1);  h2 = gelu(dw3x3(h) + dwb) + h;
+ *       out = W2 h2 + b2 (+ r)
+ *   GELU is the erf form.  The depthwise conv zero-pads h: outside the image h is 0, not gelu(b1).  Both 1x1 convs run on the
+ *   MFMA units with their operand rounded to T and fp32 accumulation; the depthwise taps are fp32.
+ *     x          (B,H,W,ldx) fp32, ldx >= 64, ldx % 4 == 0
+ *     ln_g, ln_b fp32 [64], both or neither; ln_eps > 0
+ *     hid_p      the hidden width padded to a multiple of 32: 96 (int(64 * 1.25) = 80) or 128; HAT_EUNSUPPORTED otherwise.
+ *                Pad units have zero weights and biases everywhere and contribute 0.
+ *     w1         T fragments [hid_p/16][2][64 lanes][8]: element (t, ks, l, j) = W1[16 t + (l & 15)][32 ks + 8 (l >> 4) + j]
+ *     b1, dwb    fp32 [hid_p];  dww fp32 [9][hid_p], tap = 3 ky + kx
+ *     w2         T fragments [4][hid_p/32][64][8] of the (64, hid_p) matrix, same element order;  b2 fp32 [64]
+ *     r          optional (B,H,W,ldr) fp32 residual, ldr >= 64, ldr % 4 == 0
+ *     out        (B,H,W,ldo): fp32 rows when out_f32 != 0, else T rows (ldo a multiple of 16 bytes); must not be x
+ *     partials   optional fp32 [B][tiles][16]: slot (b, tile) = the sums of out's channels 0..15, as stored, over the tile's
+ *                pixels inside the image, in a fixed order (no atomics: two runs agree bit for bit) — the block layout
+ *                hat_esc_weights reduces (nblk = tiles).  Every slot is written.
+ *   Vector-accessed pointers are 16-byte aligned.  HAT_EINVAL, before any launch, for a null or misaligned pointer, bad
+ *   leading dimensions, B, H or W < 1, B > 65535, out == x.
+ *
+ * hat_window_attention_r  window self-attention with 32 x 32 windows whose edge windows read reflected pixels
+ *   (esc_arch.py:205-250): the frame (h, w) is taken as reflect-padded on the right and the bottom to multiples of 32; a
+ *   window position past the frame reads q, k and v at the pixel it mirrors (the 1x1 to_qkv commutes with the pad), takes
+ *   part in the softmax over all 1024 keys as in the reference, and its own output is dropped.  q, kv, out, head layout and
+ *   q's pre-multiplication by head_dim^-0.5 as for hat_window_attention; bias: [heads][63 * 63] fp32, the reference's
+ *   relative_position_bias as it is, indexed (ky - qy + 31) * 63 + (kx - qx + 31).  ws == 32 and C == 16 heads
+ *   (HAT_EUNSUPPORTED otherwise); no shift.  K, V^T and one head's bias table stay in LDS (fp32: 144 KiB, bf16: 80 KiB).
+ *   HAT_EINVAL when a pad would not be smaller than the frame side (32 ceil(h / 32) - h > h - 1), as reflect padding requires.
+ *
+ * hat_esc_layernorm  y = LayerNorm(x) over 64 channels with `eps` as an argument (esc_arch.py:68-86 uses 1e-6; hat_layernorm
+ *   is fixed at 1e-5): x (npix, ldx) fp32 -> y (npix, ldy) T.
+ *
+ * hat_esc_shuffle_add  y[b][c][s yy + i][s xx + j] = rows[b][yy][xx][c s^2 + s i + j] + x[b][c][yy][xx]: the pixel shuffle of
+ *   to_img's rows (B,H,W,ld) fp32 plus the repeat_interleave base image (esc_arch.py:384-385) -> (B,3,sH,sW) fp32 planes.
+ */
+typedef struct HatEscConvFfnDesc {
+    const float* x;
+    const float* ln_g;
+    const float* ln_b;
+    const void* w1;
+    const float* b1;
+    const float* dww;
+    const float* dwb;
+    const void* w2;
+    const float* b2;
+    const float* r;
+    void* out;
+    float* partials;
+    float ln_eps;
+    int32_t B, H, W, hid_p, ldx, ldr, ldo, out_f32, dtype;
+    int32_t reserved0;
+} HatEscConvFfnDesc;
+int hat_esc_convffn_tiles(int32_t H, int32_t W);
+int hat_esc_convffn(const HatEscConvFfnDesc* d, void* stream);
+int hat_window_attention_r(const void* q, const void* kv, const float* bias, void* out, int32_t B, int32_t h, int32_t w,
+                           int32_t C, int32_t heads, int32_t ws, int32_t ldq, int32_t ldkv, int32_t ldo, int32_t dtype,
+                           void* stream);
+int hat_esc_layernorm(const float* x, void* y, const float* gamma, const float* beta, float eps, int64_t npix, int32_t ldx,
+                      int32_t ldy, int32_t dtype, void* stream);
+int hat_esc_shuffle_add(const float* rows, const float* x, float* y, int32_t B, int32_t H, int32_t W, int32_t s, int32_t ld,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,15 @@ class HatNafFoldDesc(C.Structure):
                 ("B", C.c_int32), ("tiles", C.c_int32), ("C", C.c_int32), ("dtype", C.c_int32)]
 
 
+class HatEscConvFfnDesc(C.Structure):
+    """Mirror of `struct HatEscConvFfnDesc` (include/hat_mi355x.h)."""
+    _fields_ = [("x", C.c_void_p), ("ln_g", C.c_void_p), ("ln_b", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p),
+                ("dww", C.c_void_p), ("dwb", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("r", C.c_void_p),
+                ("out", C.c_void_p), ("partials", C.c_void_p), ("ln_eps", C.c_float),
+                ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("hid_p", C.c_int32), ("ldx", C.c_int32), ("ldr", C.c_int32),
+                ("ldo", C.c_int32), ("out_f32", C.c_int32), ("dtype", C.c_int32), ("reserved0", C.c_int32)]
+
+
 _YUV_BLOCK = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]   # a 4:2:0 frame block
 
 # name -> (restype, argtypes); every symbol declared in include/hat_mi355x.h
@@ -236,6 +245,11 @@ SIGNATURES = {
     "hat_naf_half_tiles": (C.c_int, [C.c_int32, C.c_int32]),
     "hat_naf_half": (C.c_int, [C.POINTER(HatNafHalfDesc), C.c_void_p]),
     "hat_naf_fold": (C.c_int, [C.POINTER(HatNafFoldDesc), C.c_void_p]),
+    "hat_esc_convffn_tiles": (C.c_int, [C.c_int32, C.c_int32]),
+    "hat_esc_convffn": (C.c_int, [C.POINTER(HatEscConvFfnDesc), C.c_void_p]),
+    "hat_window_attention_r": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 10 + [C.c_void_p]),
+    "hat_esc_layernorm": (C.c_int, [C.c_void_p] * 4 + [C.c_float, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "hat_esc_shuffle_add": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p]),
 }
 
 _lib = None

@@ -1,4 +1,5 @@
-"""Importing this package registers `HAT`, `HATX` and `HybridHATNAF` under their names (hat/archs/__init__.py:8-11 does the
+"""Importing this package registers `HAT`, `HATX`, `HybridHATNAF` and `ESC` under their names (hat/archs/__init__.py:8-11 does the
 same by scanning `*_arch.py`)."""
 from .hat_arch import HAT  # noqa: F401
 from .hybrid_hat_naf_arch import HybridHATNAF  # noqa: F401
+from .esc_arch import ESC  # noqa: F401

@@ -1,0 +1,153 @@
+"""`ESCEngine` — the ESC network (esc_arch.py:301-386) as a launch sequence on the MI355X: packed weights, a workspace per
+input shape, no torch op on the hot path.  DESIGN.md §4.14 has the launch list.
+
+The residual stream is fp32 rows (B, H*W, 64); what a 1x1 / 3x3 / 13x13 conv reads is T rows (T = the compute dtype).  Per Block:
+    hat_esc_convffn (LN + ConvFFN)  ->  hat_esc_layernorm, to_qkv, hat_window_attention_r, to_out (+ x)
+    conv_blocks x [ hat_esc_convffn (+ pool partials), hat_esc_weights, 13x13 conv, aggr (+ x) ]  ->  hat_esc_layernorm, conv_out (+ skip)
+"""
+from __future__ import annotations
+
+import collections
+
+import torch
+
+from . import ops
+from .engine import _ESC
+from .ops import O_NHWC_F32, O_NHWC_T, X_NCHW_F32_MEAN, X_NHWC_F32
+
+LN_EPS = 1e-6   # esc_arch.py:69
+SUPPORTED = dict(dim=64, pdim=16, kernel_size=13, window_size=32, num_heads=4)
+
+
+def _r4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
+class _Block:
+    pass
+
+
+class ESCEngine:
+    def __init__(self, cfg: dict, sd: dict, device, compute_dtype: str = "bf16"):
+        for k, v in SUPPORTED.items():
+            if int(cfg[k]) != v:
+                raise ValueError(f"ESC with {k}={cfg[k]} is not supported: the device path is built for "
+                                 + ", ".join(f"{a}={b}" for a, b in SUPPORTED.items()) + " (ESC, ESC-light, ESCReal's body)")
+        if int(cfg["dim"] * cfg["exp_ratio"]) not in ops.ESC_HID_PAD:
+            raise ValueError(f"ESC with exp_ratio={cfg['exp_ratio']} is not supported: hat_esc_convffn is built for exp_ratio 1.25 and 2")
+        if compute_dtype not in ops.DTYPE_CODE:
+            raise ValueError(f"compute_dtype {compute_dtype!r}: expected 'bf16' or 'fp32'")
+        self.cfg, self.dev = dict(cfg), torch.device(device)
+        self.dtype = dt = ops.DTYPE_CODE[compute_dtype]
+        self.tdt = ops.TORCH_DTYPE[dt]
+        self.C, self.scale, self.heads, self.ws = 64, int(cfg["upscaling_factor"]), int(cfg["num_heads"]), int(cfg["window_size"])
+        dev, C = self.dev, self.C
+        vec = lambda k: sd[k].detach().to(dtype=torch.float32, device=dev).contiguous()
+        # the geometric re-parameterisation of the one large-kernel filter, once, unless convert() has baked it in already
+        plk = sd["plk_filter"].detach().to(torch.float32).cpu()
+        sd = dict(sd, _plk=plk if cfg.get("converted", False) else ops.esc_geo_ensemble(plk))
+        self.proj = ops.pack_conv_weight(sd["proj.weight"], sd["proj.bias"], dt, dev)
+        self.blocks = []
+        for i in range(int(cfg["n_blocks"])):
+            p, b = f"blocks.{i}", _Block()
+            b.ln_proj = (vec(p + ".ln_proj.weight"), vec(p + ".ln_proj.bias"))
+            b.proj = ops.pack_esc_convffn(sd, p + ".proj", dt, dev)
+            b.ln_attn = (vec(p + ".ln_attn.weight"), vec(p + ".ln_attn.bias"))
+            # head_dim^-0.5 = 1/4 folded into the q rows of to_qkv: a power of two, so exact
+            qs = torch.cat([torch.full((C,), (C // self.heads) ** -0.5), torch.ones(2 * C)])
+            wq = sd[p + ".attn.to_qkv.weight"].detach().to(torch.float32).cpu().reshape(3 * C, C) * qs[:, None]
+            bq = sd[p + ".attn.to_qkv.bias"].detach().to(torch.float32).cpu() * qs
+            b.to_qkv = ops.pack_pointwise(wq, bq, dt, dev)
+            b.to_out = ops.pack_pointwise(sd[p + ".attn.to_out.weight"].detach().reshape(C, C), sd[p + ".attn.to_out.bias"], dt, dev)
+            b.rpb = vec(p + ".attn.relative_position_bias")
+            b.convs = []
+            for j in range(int(cfg["conv_blocks"])):
+                ln = (vec(f"{p}.lns.{j}.weight"), vec(f"{p}.lns.{j}.bias")) if cfg.get("use_ln", False) else None
+                esc = _ESC(sd, f"{p}.pconvs.{j}", "_plk", 16, 13, C, dt, dev)
+                esc.aggr = ops.pack_pointwise(sd[esc.aggr_keys[0]].detach().reshape(C, C), sd[esc.aggr_keys[1]], dt, dev)
+                esc.conv13 = ops.esc_conv13_supported(16, 13, dt)
+                b.convs.append((ln, ops.pack_esc_convffn(sd, f"{p}.convffns.{j}", dt, dev), esc))
+            b.ln_out = (vec(p + ".ln_out.weight"), vec(p + ".ln_out.bias"))
+            b.conv_out = ops.pack_conv_weight(sd[p + ".conv_out.weight"], sd[p + ".conv_out.bias"], dt, dev)
+            self.blocks.append(b)
+        self.last = ops.pack_conv_weight(sd["last.weight"], sd["last.bias"], dt, dev)
+        self.to_img = ops.pack_conv_weight(sd["to_img.weight"], sd["to_img.bias"], dt, dev)
+        self._kpad = self.blocks[0].convs[0][2].kpad if self.blocks and self.blocks[0].convs else 0
+        self._ws_cache = collections.OrderedDict()
+
+    # ------------------------------------------------------------------------------------------
+    def _workspace(self, B: int, H: int, W: int):
+        key = (B, H, W)
+        w = self._ws_cache.get(key)
+        if w is not None:
+            self._ws_cache.move_to_end(key)
+            return w
+        dev, N, C, s = self.dev, H * W, self.C, self.scale
+        f = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        t = lambda *shape: torch.zeros(*shape, dtype=self.tdt, device=dev)
+        w = {"feat0": f(B, N, C), "s": [f(B, N, C) for _ in range(3)], "n": t(B, N, C), "qkv": t(B, N, 3 * C), "att": t(B, N, C),
+             "z": t(B, N, C), "y16": t(B, N, 16), "gap": f(B, ops.esc_convffn_tiles(H, W), 16), "weff": t(B, 16, max(self._kpad, 1)),
+             "rows": f(B, N, _r4(3 * s * s)), "y": f(B, 3, H * s, W * s)}
+        self._ws_cache[key] = w
+        while len(self._ws_cache) > 4:
+            self._ws_cache.popitem(last=False)
+        return w
+
+    def _lin(self, pw, x, out, *, geo, ldx, ldo, out_mode=O_NHWC_T, **kw):
+        if pw.frag:
+            ops.linear(pw, x, out, **geo, dtype=self.dtype, ldx=ldx, ldo=ldo, out_mode=out_mode, **kw)
+        else:
+            ops.conv(pw, x, out, **geo, dtype=self.dtype, ldx=ldx, ldo=ldo, out_mode=out_mode, **kw)
+
+    def forward(self, x: torch.Tensor, taps: dict = None) -> torch.Tensor:
+        """x (1, 3, h, w) fp32 -> (1, 3, s h, s w) fp32 (the workspace's output buffer: copy it before the next forward of the shape).
+        taps: a dict that receives clones of the stream after the first ConvFFN, the attention and the first conv block."""
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise RuntimeError(f"ESC expects (B,3,h,w) input, got {tuple(x.shape)}")
+        B, _, H, W = x.shape
+        if B != 1:
+            raise RuntimeError("ESC's eval path takes one frame at a time (esc_arch.py:121: the dynamic kernel of a batch cannot be "
+                               f"reshaped to (pdim,1,3,3)), got a batch of {B}")
+        ws = self.ws
+        if (-H) % ws > H - 1 or (-W) % ws > W - 1:
+            raise RuntimeError(f"a {H}x{W} frame cannot be reflect-padded to a multiple of window_size {ws}: the padding must be smaller than the frame")
+        x = x.to(torch.float32).contiguous()
+        w, C, dt, N = self._workspace(B, H, W), self.C, self.dtype, H * W
+        geo = dict(B=B, H=H, W=W)
+        tiles = w["gap"].shape[1]
+        ops.conv(self.proj, x, w["feat0"], **geo, dtype=dt, ldx=0, ldo=C, x_mode=X_NCHW_F32_MEAN, out_mode=O_NHWC_F32)
+        cur = w["feat0"]
+        for bi, b in enumerate(self.blocks):
+            xa, xb = [s for s in w["s"] if s is not cur][:2]
+            ops.esc_convffn(b.proj, cur, xa, **geo, dtype=dt, ln=b.ln_proj, eps=LN_EPS)
+            if taps is not None and bi == 0:
+                taps["ffn0"] = xa.clone()
+            ops.esc_layernorm(xa, w["n"], *b.ln_attn, npix=B * N, dtype=dt, eps=LN_EPS)
+            self._lin(b.to_qkv, w["n"], w["qkv"], geo=geo, ldx=C, ldo=3 * C)
+            ops.window_attention_r(w["qkv"], w["qkv"].view(-1)[C:], b.rpb, w["att"], B=B, h=H, w=W, C_=C, heads=self.heads, ws=ws,
+                                   ldq=3 * C, ldkv=3 * C, ldo=C, dtype=dt)
+            self._lin(b.to_out, w["att"], xb, geo=geo, ldx=C, ldo=C, out_mode=O_NHWC_F32, r1=xa, ldr1=C)
+            xa, xb = xb, xa
+            if taps is not None and bi == 0:
+                taps["attn0"] = xa.clone()
+            for ci, (ln, ffn, esc) in enumerate(b.convs):
+                ops.esc_convffn(ffn, xa, w["z"], **geo, dtype=dt, ln=ln, eps=LN_EPS, partials=w["gap"])
+                ops.esc_weights(w["gap"], tiles, N, esc.w1, esc.b1, esc.w2, esc.b2, esc.plk, w["weff"], B=B, pdim=16, ksize=13,
+                                kpad=esc.kpad, dtype=dt)
+                if esc.conv13:
+                    ops.esc_conv13(w["z"], w["weff"], w["y16"], **geo, ldx=C, kpad=esc.kpad, dtype=dt)
+                else:
+                    pw = ops.PackedConv(w["weff"], esc.zero_bias, 13, 16, esc.kpad, 1, 1, 16, w_bstride=16 * esc.kpad)
+                    ops.conv(pw, w["z"], w["y16"], **geo, dtype=dt, ldx=C, ldo=16, n_store=16)
+                self._lin(esc.aggr, w["z"], xb, geo=geo, ldx=C, ldo=C, out_mode=O_NHWC_F32, x0=w["y16"], c_split=16, ldx0=16, r1=xa, ldr1=C)
+                xa, xb = xb, xa
+                if taps is not None and bi == 0 and ci == 0:
+                    taps["conv0"] = xa.clone()
+            ops.esc_layernorm(xa, w["n"], *b.ln_out, npix=B * N, dtype=dt, eps=LN_EPS)
+            ops.conv(b.conv_out, w["n"], xb, **geo, dtype=dt, ldx=C, ldo=C, out_mode=O_NHWC_F32, r1=cur, ldr1=C)
+            cur = xb
+        ops.conv(self.last, cur, w["n"], **geo, dtype=dt, ldx=C, ldo=C, x_mode=X_NHWC_F32, r1=w["feat0"], ldr1=C)
+        ld = w["rows"].shape[2]
+        ops.conv(self.to_img, w["n"], w["rows"], **geo, dtype=dt, ldx=C, ldo=ld, out_mode=O_NHWC_F32, n_store=ld)
+        ops.esc_shuffle_add(w["rows"], x, w["y"], B=B, H=H, W=W, s=self.scale, ld=ld)
+        return w["y"]

@@ -13,9 +13,10 @@ import torch
 from . import _lib
 from ._lib import (ACT_GELU, ACT_LRELU, ACT_NONE, HAT_BF16, HAT_F32, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T,
                    X_NCHW_F32_MEAN, X_NHWC_F32, X_NHWC_T, HatAggrCabDesc, HatCabFoldDesc, HatConvDesc, HatFfnDesc, HatHabTailDesc, HatMlpDesc, HatNafFoldDesc,
-                   HatNafHalfDesc)
+                   HatNafHalfDesc, HatEscConvFfnDesc)
 # host-side weight packing lives in packing.py; ops.pack_* / ops.Packed* stay the names the engine, the tools and the tests use
-from .packing import (FP16_SAFE, KC, NAF_WIDTHS, TORCH_DTYPE, PackedConv, PackedFFN, PackedMlp, PackedNafBlock, choose_nt,  # noqa: F401
+from .packing import (ESC_HID_PAD, FP16_SAFE, KC, NAF_WIDTHS, TORCH_DTYPE, PackedConv, PackedEscFfn, PackedFFN, PackedMlp, PackedNafBlock, choose_nt,  # noqa: F401
+                      esc_geo_ensemble, pack_esc_convffn,
                       choose_nt_linear, naf_ffn_fold, naf_frags, pack_naf_block,
                       ffn_fp16_range_bound, pack_cab_squeeze, pack_cab_w2f, pack_conv_weight, pack_ffn, pack_ffn2, pack_ffn3,
                       pack_linear_weight, pack_ocab_mlp, pack_ocab_qkv, pack_pointwise)
@@ -297,6 +298,60 @@ def naf_fold(partials, blk: PackedNafBlock, wf, bf, *, B: int, H: int, W: int, C
     d.wf, d.bf, d.npix, d.B, d.tiles, d.C, d.dtype = _ptr(wf), _ptr(bf), H * W, B, naf_tiles(H, W), C_, dtype
     _timed(f"naf_fold_kernel<{_TNAME[dtype]}, {C_}>", 0.0, lambda: _lib.check(lib.hat_naf_fold(C.byref(d), _stream()), f"hat_naf_fold(c={C_})"),
            tag=f"naf fold c{C_} {H}x{W}")
+
+
+# ------------------------------------------------------------------------------------------------
+# ESC (hat_esc_convffn / hat_window_attention_r / hat_esc_layernorm / hat_esc_shuffle_add)
+# ------------------------------------------------------------------------------------------------
+def esc_convffn_tiles(H: int, W: int) -> int:
+    """Tiles per sample of hat_esc_convffn = slots per sample of its pool partials."""
+    n = _lib.load().hat_esc_convffn_tiles(H, W)
+    _lib.check(min(n, 0), "hat_esc_convffn_tiles")
+    return n
+
+
+def esc_convffn(pf: PackedEscFfn, x, out, *, B: int, H: int, W: int, dtype: int, ln=None, eps: float = 1e-6, r=None, partials=None,
+                ldx: int = 64, ldr: int = 64, ldo: int = 64):
+    """out = ConvFFN(ln ? LayerNorm(x; ln = (gamma, beta), eps) : x) (+ r) in one launch (hat_esc_convffn).  x, r: fp32 rows; out: fp32
+    rows when it is an fp32 tensor, else T rows; partials: the (B, esc_convffn_tiles, 16) fp32 pool partials of out[..., :16]."""
+    lib = _lib.load()
+    d = HatEscConvFfnDesc()
+    d.x, d.w1, d.b1, d.dww, d.dwb, d.w2, d.b2 = _ptr(x), _ptr(pf.w1), _ptr(pf.b1), _ptr(pf.dww), _ptr(pf.dwb), _ptr(pf.w2), _ptr(pf.b2)
+    if ln is not None:
+        d.ln_g, d.ln_b = _ptr(ln[0]), _ptr(ln[1])
+    d.ln_eps = eps
+    d.r, d.out, d.partials = _ptr(r), _ptr(out), _ptr(partials)
+    d.B, d.H, d.W, d.hid_p, d.ldx, d.ldr, d.ldo, d.dtype = B, H, W, pf.hid_p, ldx, ldr, ldo, dtype
+    d.out_f32 = int(out.dtype == torch.float32)
+    es, npx = (4 if d.out_f32 or dtype == HAT_F32 else 2), float(B * H * W)
+    _timed(f"esc_convffn_kernel<{_TNAME[dtype]}, {pf.hid_p}>", 2.0 * npx * pf.hid * (2 * 64 + 9),
+           lambda: _lib.check(lib.hat_esc_convffn(C.byref(d), _stream()), f"hat_esc_convffn(hid={pf.hid})"),
+           tag=f"convffn 64->{pf.hid}->64 {H}x{W}{' ln' if ln is not None else ''}{' r' if r is not None else ''}{' pool' if partials is not None else ''}",
+           nbytes=npx * 64 * (4 + es + (4 if r is not None else 0)))
+
+
+def window_attention_r(q, kv, bias, out, *, B: int, h: int, w: int, C_: int, heads: int, ws: int, ldq: int, ldkv: int, ldo: int, dtype: int):
+    """ESC's 32 x 32 window attention with reflected edge windows (hat_window_attention_r; esc_arch.py:205-250); q pre-scaled."""
+    lib = _lib.load()
+    nw = -(-h // ws) * -(-w // ws)
+    _timed(f"window_attention_r_kernel<{_TNAME[dtype]}>", 2.0 * 2 * (ws * ws) ** 2 * C_ * B * nw, lambda: _lib.check(
+        lib.hat_window_attention_r(_ptr(q), _ptr(kv), _ptr(bias), _ptr(out), B, h, w, C_, heads, ws, ldq, ldkv, ldo, dtype, _stream()),
+        "hat_window_attention_r"), tag=f"attn ws{ws} {h}x{w}")
+
+
+def esc_layernorm(x, y, gamma, beta, *, npix: int, dtype: int, eps: float = 1e-6, ldx: int = 64, ldy: int = 64):
+    """y (T rows) = LayerNorm over 64 channels of x (fp32 rows) with `eps` (hat_esc_layernorm)."""
+    lib = _lib.load()
+    _timed(f"esc_layernorm_kernel<{_TNAME[dtype]}>", 0.0, lambda: _lib.check(
+        lib.hat_esc_layernorm(_ptr(x), _ptr(y), _ptr(gamma), _ptr(beta), eps, npix, ldx, ldy, dtype, _stream()), "hat_esc_layernorm"),
+        tag="ln64 eps")
+
+
+def esc_shuffle_add(rows, x, y, *, B: int, H: int, W: int, s: int, ld: int):
+    """y (B,3,sH,sW) = pixel_shuffle(rows (B,H,W,ld) fp32) + repeat_interleave(x (B,3,H,W), s*s) (hat_esc_shuffle_add)."""
+    lib = _lib.load()
+    _timed("esc_shuffle_add_kernel", 0.0, lambda: _lib.check(
+        lib.hat_esc_shuffle_add(_ptr(rows), _ptr(x), _ptr(y), B, H, W, s, ld, _stream()), "hat_esc_shuffle_add"), tag=f"shuffle x{s} {H}x{W}")
 
 
 LOG2E = 1.4426950408889634

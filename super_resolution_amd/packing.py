@@ -405,3 +405,41 @@ def pack_naf_block(sd, p: str, dtype: int, device) -> PackedNafBlock:
     wf2, bf2 = naf_ffn_fold(sd[p + ".gamma"], sd[p + ".ffn2.weight"], sd[p + ".ffn2.bias"])
     b.wf2, b.bf2 = naf_frags(wf2, dtype, device), bf2.contiguous().to(device)
     return b
+
+
+# ------------------------------------------------------------------------------------------------
+# ESC: hat_esc_convffn (esc_arch.py:148-159) and the geometric re-parameterisation of the large-kernel filter (:289-298)
+# ------------------------------------------------------------------------------------------------
+ESC_HID_PAD = {80: 96, 128: 128}   # hidden widths hat_esc_convffn is instantiated for -> padded to a multiple of 32
+
+
+class PackedEscFfn:
+    """One ConvFFN in hat_esc_convffn's operand layouts (include/hat_mi355x.h "ESC"): w1 T fragments [hid_p/16][2][64][8] of the
+    (hid_p, 64) 1x1, w2 T fragments [4][hid_p/32][64][8] of the (64, hid_p) 1x1, b1 / dwb [hid_p], dww [9][hid_p], b2 [64] fp32; the
+    pad units are zero everywhere."""
+    __slots__ = ("w1", "b1", "dww", "dwb", "w2", "b2", "hid", "hid_p")
+
+
+def pack_esc_convffn(sd, p: str, dtype: int, device) -> PackedEscFfn:
+    """sd[p + '.proj.weight'] ... of one ConvFFN (state-dict names of esc_arch.py:151-153) -> PackedEscFfn."""
+    W1 = _f32(sd[p + ".proj.weight"])
+    hid, dim = W1.shape[0], W1.shape[1]
+    if dim != 64 or hid not in ESC_HID_PAD:
+        raise ValueError(f"ConvFFN {dim} -> {hid} is not supported: hat_esc_convffn is built for 64 channels and a hidden width of "
+                         f"{' or '.join(map(str, ESC_HID_PAD))} (exp_ratio 1.25 or 2)")
+    hp = ESC_HID_PAD[hid]
+    f = PackedEscFfn()
+    f.hid, f.hid_p = hid, hp
+    f.w1 = frags(_pad(W1.reshape(hid, dim), hp)).to(TORCH_DTYPE[dtype]).contiguous().to(device)
+    f.b1 = _pad(_f32(sd[p + ".proj.bias"]), hp).to(device)
+    f.dww = _pad(_f32(sd[p + ".dwc.weight"]).reshape(hid, 9), hp).t().contiguous().to(device)
+    f.dwb = _pad(_f32(sd[p + ".dwc.bias"]), hp).to(device)
+    f.w2 = frags(_pad(_f32(sd[p + ".aggr.weight"]).reshape(dim, hid), dim, hp)).to(TORCH_DTYPE[dtype]).contiguous().to(device)
+    f.b2 = _f32(sd[p + ".aggr.bias"]).contiguous().to(device)
+    return f
+
+
+def esc_geo_ensemble(k: torch.Tensor) -> torch.Tensor:
+    """The mean of the 8 flips / rotations of a (pdim, pdim, k, k) filter, in the reference's order of additions (esc_arch.py:289-298)."""
+    r = torch.rot90(k, -1, [2, 3])
+    return (k + k.flip([3]) + k.flip([2]) + k.flip([2, 3]) + r + r.flip([3]) + r.flip([2]) + r.flip([2, 3])) / 8

@@ -104,6 +104,8 @@ def export_plan(net, x_shape: Tuple[int, int, int, int], path: str) -> dict:
     """Record `net`'s forward for inputs of `x_shape` = (B, Cin, H, W) on the module's device and write the plan file."""
     eng = net.engine()
     dev = eng.dev
+    if not hasattr(eng, "pe_norm"):
+        raise NotImplementedError(f"a plan records HATEngine's call list: {type(net).__name__} cannot be exported yet (DESIGN.md §7)")
     if eng.pe_norm is None:
         raise NotImplementedError("patch_norm=False copies a tensor with a torch op, which a plan cannot record")
     B, Cin, H, W = x_shape

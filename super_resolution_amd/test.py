@@ -1,5 +1,5 @@
 """`python -m super_resolution_amd.test -opt options/test/HAT-S_SRx4.yml` — the reference's `hat/test.py` entry
-(basicsr `test_pipeline`): parse the YAML, build the test datasets and `HATModel`, validate each dataset."""
+(basicsr `test_pipeline`): parse the YAML, build the test datasets and the model harness of `model_type` (`HATModel`; ESC's `ESRModel` is the same harness), validate each dataset."""
 from __future__ import annotations
 
 import argparse
@@ -9,7 +9,7 @@ import sys
 import yaml
 
 from .data import FolderDataset
-from .models import HATModel
+from .models import HATModel, model_class
 
 
 def parse_options(path: str, u8: bool = False, metrics_on_device: bool = False, lq_on_device: bool = False, self_ensemble=None) -> dict:
@@ -50,6 +50,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     opt = parse_options(args.opt, u8=args.u8, metrics_on_device=args.metrics_on_device, lq_on_device=args.lq_on_device,
                         self_ensemble=args.self_ensemble)
+    model_class(opt.get("model_type"))   # KeyError for a model type that is not built; every one that is (HATModel, ESRModel) is this harness
     model = HATModel(opt, device=args.device)
     results = {}
     for _, dopt in sorted((opt.get("datasets") or {}).items()):

@@ -1,0 +1,182 @@
+"""An fp64 restatement of the ESC network (esc_arch.py:68-386, eval mode) from its state dict, for the tests of the device path:
+`oracle/` is frozen, and the goldens under tests/golden/esc_*.npz come from the reference itself (gen_golden_esc.py).  Plain torch
+on the CPU, one function per stage, so the kernel tests can restate exactly the operation a kernel performs."""
+from __future__ import annotations
+
+import json
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from super_resolution_amd import synth
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+W_SEED, X_SEED = 1234, 4321
+LN_EPS = 1e-6
+BASE = dict(dim=64, pdim=16, kernel_size=13, window_size=32, num_heads=4)
+CASES = {   # the whole-model goldens: constructor keywords, frame
+    "a": (dict(BASE, n_blocks=1, conv_blocks=1, exp_ratio=1.25, upscaling_factor=2), (1, 3, 40, 72)),
+    "b": (dict(BASE, n_blocks=2, conv_blocks=2, exp_ratio=2, use_ln=True, upscaling_factor=4), (1, 3, 33, 64)),
+}
+SURFACE_CFGS = {   # esc_surface.json: ESC, ESC-light (ESC/options/test/ESC_*.yaml) and ESCReal's body
+    "ESC": dict(BASE, n_blocks=5, conv_blocks=5, exp_ratio=1.25, upscaling_factor=4),
+    "ESC_light": dict(BASE, n_blocks=3, conv_blocks=5, exp_ratio=1.25, upscaling_factor=4),
+    "ESCReal_body": dict(BASE, n_blocks=10, conv_blocks=5, exp_ratio=2, use_ln=True, upscaling_factor=4),
+}
+TAPS = ("ffn0", "attn0", "conv0")   # the stream after the first ConvFFN, after the attention, after the first conv block
+N_TAP_PIXELS = 160
+
+
+def esc_state_dict(template: dict, seed: int = W_SEED) -> dict:
+    """Every parameter randomised (synth.synth_state_dict), with the two families its name rules miss set as SURVEY §8(d) sets their
+    HAT counterparts: the relative-position bias N(0, 0.5^2), so a wrong index shows, and LayerNorm weights 1 + N(0, 0.1^2)."""
+    sd = synth.synth_state_dict(template, seed)
+    for k, v in template.items():
+        if k.endswith("relative_position_bias"):
+            sd[k] = synth.normal(seed, k, tuple(v.shape), std=0.5)
+        elif k.endswith(".weight") and v.dim() == 1:
+            sd[k] = synth.normal(seed, k, tuple(v.shape), std=0.1, mean=1.0)
+    return sd
+
+
+def template_from_surface(surface) -> dict:
+    return {k: torch.zeros(shape, dtype=torch.float32) for k, shape in surface}
+
+
+def tap_pixels(h: int, w: int) -> np.ndarray:
+    """The pixels at which the goldens keep the intermediates (all 64 channels): the corners, the window seams and a seeded sample."""
+    fixed = [(0, 0), (0, w - 1), (h - 1, 0), (h - 1, w - 1), (31 % h, 31 % w), (min(32, h - 1), min(32, w - 1)), (h - 1, min(32, w - 1)),
+             (min(32, h - 1), w - 1)]
+    idx = [y * w + x for y, x in fixed]
+    rnd = (synth.uniform(X_SEED, f"taps{h}x{w}", (N_TAP_PIXELS - len(idx),)).numpy() * (h * w)).astype(np.int64)
+    return np.concatenate([np.array(idx, dtype=np.int64), np.minimum(rnd, h * w - 1)])
+
+
+def d64(sd: dict) -> dict:
+    return {k: v.detach().to(torch.float64) for k, v in sd.items()}
+
+
+def geo_ensemble(k):
+    r = torch.rot90(k, -1, [2, 3])
+    return (k + k.flip([3]) + k.flip([2]) + k.flip([2, 3]) + r + r.flip([3]) + r.flip([2]) + r.flip([2, 3])) / 8
+
+
+def layernorm(x, g, b, eps=LN_EPS):
+    """x (B,C,H,W): LayerNorm over C (esc_arch.py:68-86)."""
+    m = x.mean(1, keepdim=True)
+    v = ((x - m) ** 2).mean(1, keepdim=True)
+    return (x - m) / torch.sqrt(v + eps) * g[None, :, None, None] + b[None, :, None, None]
+
+
+def gelu(x):
+    return 0.5 * x * (1.0 + torch.erf(x * 0.7071067811865476))
+
+
+def convffn(x, sd, p):
+    """esc_arch.py:155-159; the depthwise conv zero-pads h."""
+    h = gelu(F.conv2d(x, sd[p + ".proj.weight"], sd[p + ".proj.bias"]))
+    h = gelu(F.conv2d(h, sd[p + ".dwc.weight"], sd[p + ".dwc.bias"], padding=1, groups=h.shape[1])) + h
+    return F.conv2d(h, sd[p + ".aggr.weight"], sd[p + ".aggr.bias"])
+
+
+def bias_matrix(table, ws):
+    """(heads, (2ws-1)^2) -> (heads, ws^2, ws^2): entry [q, k] = table[(kh - qh + ws - 1) * (2ws - 1) + kw - qw + ws - 1] (esc_arch.py:187-203)."""
+    n = torch.arange(ws * ws)
+    qh, qw = n // ws, n % ws
+    idx = (qh[None, :] - qh[:, None] + ws - 1) * (2 * ws - 1) + (qw[None, :] - qw[:, None] + ws - 1)
+    return table[:, idx]
+
+
+def reflect_index(n: int, npad: int) -> torch.Tensor:
+    i = torch.arange(npad)
+    return torch.where(i < n, i, 2 * n - 2 - i)
+
+
+def attention_core(qkv, table, ws, heads):
+    """qkv (B,3C,Hp,Wp) with Hp, Wp multiples of ws -> (B,C,Hp,Wp): softmax(q k^T / sqrt(d) + bias) v per window and head."""
+    B, C3, Hp, Wp = qkv.shape
+    C, d = C3 // 3, C3 // 3 // heads
+    t = qkv.reshape(B, 3, heads, d, Hp // ws, ws, Wp // ws, ws).permute(1, 0, 4, 6, 2, 5, 7, 3).reshape(3, -1, heads, ws * ws, d)
+    q, k, v = t[0], t[1], t[2]
+    s = q @ k.transpose(-2, -1) / d ** 0.5 + bias_matrix(table, ws)[None]
+    o = torch.softmax(s, dim=-1) @ v
+    return o.reshape(B, Hp // ws, Wp // ws, heads, ws, ws, d).permute(0, 3, 6, 1, 4, 2, 5).reshape(B, C, Hp, Wp)
+
+
+def window_attention(x, sd, p, ws, heads, gather=False):
+    """esc_arch.py:220-250.  gather=False: reflect-pad, then to_qkv, as the reference.  gather=True: to_qkv on the frame, then q, k, v
+    of the pad positions gathered from the reflected coordinates — what hat_window_attention_r does."""
+    B, C, h, w = x.shape
+    Hp, Wp = -(-h // ws) * ws, -(-w // ws) * ws
+    if gather:
+        qkv = F.conv2d(x, sd[p + ".to_qkv.weight"], sd[p + ".to_qkv.bias"])
+        qkv = qkv[:, :, reflect_index(h, Hp)][:, :, :, reflect_index(w, Wp)]
+    else:
+        qkv = F.conv2d(F.pad(x, (0, Wp - w, 0, Hp - h), mode="reflect"), sd[p + ".to_qkv.weight"], sd[p + ".to_qkv.bias"])
+    o = attention_core(qkv, sd[p + ".relative_position_bias"], ws, heads)[:, :, :h, :w]
+    return F.conv2d(o, sd[p + ".to_out.weight"], sd[p + ".to_out.bias"])
+
+
+def plk(z, sd, p, lk, pdim):
+    """esc_arch.py:119-123 on a copy: the first pdim channels through the large-kernel conv plus the instance-dynamic depthwise conv."""
+    z1 = z[:, :pdim]
+    pooled = z1.mean((2, 3), keepdim=True)
+    dyn = F.conv2d(gelu(F.conv2d(pooled, sd[p + ".plk.dwc_proj.1.weight"], sd[p + ".plk.dwc_proj.1.bias"])),
+                   sd[p + ".plk.dwc_proj.3.weight"], sd[p + ".plk.dwc_proj.3.bias"]).reshape(pdim, 1, 3, 3)
+    y1 = F.conv2d(z1, lk, padding=lk.shape[-1] // 2) + F.conv2d(z1, dyn, padding=1, groups=pdim)
+    return torch.cat([y1, z[:, pdim:]], 1)
+
+
+def forward(sd, cfg, x, taps=None, converted=False):
+    """The eval forward of ESC in the dtype of sd / x (pass d64(sd), x.double() for the fp64 restatement)."""
+    if x.shape[0] != 1:
+        raise RuntimeError("ESC's eval path takes one frame at a time")
+    ws, heads, pdim, s = cfg["window_size"], cfg["num_heads"], cfg["pdim"], cfg["upscaling_factor"]
+    lk = sd["plk_filter"] if converted else geo_ensemble(sd["plk_filter"])
+    feat = F.conv2d(x, sd["proj.weight"], sd["proj.bias"], padding=1)
+    feat0 = feat
+    for i in range(cfg["n_blocks"]):
+        p, skip = f"blocks.{i}", feat
+        t = convffn(layernorm(feat, sd[p + ".ln_proj.weight"], sd[p + ".ln_proj.bias"]), sd, p + ".proj")
+        if taps is not None and i == 0:
+            taps["ffn0"] = t
+        t = t + window_attention(layernorm(t, sd[p + ".ln_attn.weight"], sd[p + ".ln_attn.bias"]), sd, p + ".attn", ws, heads)
+        if taps is not None and i == 0:
+            taps["attn0"] = t
+        for j in range(cfg["conv_blocks"]):
+            n = layernorm(t, sd[f"{p}.lns.{j}.weight"], sd[f"{p}.lns.{j}.bias"]) if cfg.get("use_ln", False) else t
+            z = plk(convffn(n, sd, f"{p}.convffns.{j}"), sd, f"{p}.pconvs.{j}", lk, pdim)
+            t = t + F.conv2d(z, sd[f"{p}.pconvs.{j}.aggr.weight"], sd[f"{p}.pconvs.{j}.aggr.bias"])
+            if taps is not None and i == 0 and j == 0:
+                taps["conv0"] = t
+        feat = F.conv2d(layernorm(t, sd[p + ".ln_out.weight"], sd[p + ".ln_out.bias"]), sd[p + ".conv_out.weight"], sd[p + ".conv_out.bias"],
+                        padding=1) + skip
+    feat = F.conv2d(feat, sd["last.weight"], sd["last.bias"], padding=1) + feat0
+    y = F.conv2d(feat, sd["to_img.weight"], sd["to_img.bias"], padding=1) + torch.repeat_interleave(x, s * s, dim=1)
+    return F.pixel_shuffle(y, s)
+
+
+def convert_to_img(k, b, s_out):
+    """esc_arch.py:357-373: the sub-pixel conv of another scale, bilinear over the (rh, rw) grid."""
+    s_in = int((k.shape[0] // 3) ** 0.5)
+    _, cin, kh, kw = k.shape
+    kk = k.reshape(3, s_in, s_in, cin * kh * kw).permute(3, 0, 1, 2)
+    kk = F.interpolate(kk, size=(s_out, s_out), mode="bilinear", align_corners=False).permute(1, 2, 3, 0).reshape(3 * s_out * s_out, cin, kh, kw)
+    bb = F.interpolate(b.reshape(1, 3, s_in, s_in), size=(s_out, s_out), mode="bilinear", align_corners=False).reshape(-1)
+    return kk, bb
+
+
+def surfaces() -> dict:
+    with open(os.path.join(GOLDEN, "esc_surface.json")) as f:
+        return json.load(f)
+
+
+def load_case(name: str):
+    """-> (cfg, state dict regenerated from the seed, golden arrays, meta) of whole-model case a / b / c / d."""
+    meta = surfaces()
+    g = dict(np.load(os.path.join(GOLDEN, f"esc_{name}.npz")))
+    cfg = meta["cases"][name]["cfg"]
+    sd = esc_state_dict(template_from_surface(meta["cases"][name]["surface"]), W_SEED)
+    return cfg, sd, g, meta["cases"][name]
