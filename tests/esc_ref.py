@@ -94,15 +94,24 @@ def reflect_index(n: int, npad: int) -> torch.Tensor:
     return torch.where(i < n, i, 2 * n - 2 - i)
 
 
-def attention_core(qkv, table, ws, heads):
-    """qkv (B,3C,Hp,Wp) with Hp, Wp multiples of ws -> (B,C,Hp,Wp): softmax(q k^T / sqrt(d) + bias) v per window and head."""
+def attention_core(qkv, table, ws, heads, logits=False):
+    """qkv (B,3C,Hp,Wp) with Hp, Wp multiples of ws -> (B,C,Hp,Wp): softmax(q k^T / sqrt(d) + bias) v per window and head.
+    logits=True: -> (that, the logits (B * windows, heads, ws^2, ws^2) the softmax was taken of)."""
     B, C3, Hp, Wp = qkv.shape
     C, d = C3 // 3, C3 // 3 // heads
     t = qkv.reshape(B, 3, heads, d, Hp // ws, ws, Wp // ws, ws).permute(1, 0, 4, 6, 2, 5, 7, 3).reshape(3, -1, heads, ws * ws, d)
     q, k, v = t[0], t[1], t[2]
     s = q @ k.transpose(-2, -1) / d ** 0.5 + bias_matrix(table, ws)[None]
     o = torch.softmax(s, dim=-1) @ v
-    return o.reshape(B, Hp // ws, Wp // ws, heads, ws, ws, d).permute(0, 3, 6, 1, 4, 2, 5).reshape(B, C, Hp, Wp)
+    o = o.reshape(B, Hp // ws, Wp // ws, heads, ws, ws, d).permute(0, 3, 6, 1, 4, 2, 5).reshape(B, C, Hp, Wp)
+    return (o, s) if logits else o
+
+
+def reflect_pad(x, ws):
+    """x (B,C,h,w) -> (B,C,Hp,Wp), Hp and Wp the next multiples of ws: F.pad(..., mode="reflect") on the bottom and the right,
+    by index (position i >= n holds pixel 2n - 2 - i)."""
+    h, w = x.shape[-2:]
+    return x[:, :, reflect_index(h, -(-h // ws) * ws)][:, :, :, reflect_index(w, -(-w // ws) * ws)]
 
 
 def window_attention(x, sd, p, ws, heads, gather=False):

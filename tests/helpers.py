@@ -63,6 +63,14 @@ def to_dev(x_bhwc: torch.Tensor, ld: int, tdt, dev):
     return out
 
 
+def fill_rows(x_bhwc: torch.Tensor, ld: int, tdt, dev, fill):
+    """(B,H,W,C) float -> device (B, H*W, ld) of dtype tdt whose pad channels hold `fill` (nothing may read them)."""
+    b, h, w, c = x_bhwc.shape
+    out = torch.full((b, h * w, ld), fill, dtype=tdt, device=dev)
+    out[:, :, :c] = x_bhwc.reshape(b, h * w, c).to(dev).to(tdt)
+    return out
+
+
 def check(got: torch.Tensor, ref: torch.Tensor, dtype: str, what: str, f32_tol=2e-5):
     got, ref = got.detach().double(), ref.detach().double()
     if got.device != ref.device:      # (two tensors of one device are judged there: the multi-trip tests' maps are 0.2 Mpx)
@@ -85,6 +93,14 @@ def rnd(key, shape, std=1.0):
 def q(x, dtype):
     """Round inputs the way the kernel's storage type does, so the oracle sees the same operands."""
     return x.to(torch.bfloat16).to(torch.float32) if dtype == "bf16" else x
+
+
+def esc_ffn_sd(hid, dtype, b1_mean=0.0):
+    """Seeded ConvFFN parameters under the prefix "f" (esc_ref.convffn / ops.pack_esc_convffn), the MFMA operands rounded to dtype."""
+    k = f"ecf{hid}"
+    return {"f.proj.weight": q(rnd(k + "w1", (hid, 64, 1, 1), std=1 / 8), dtype), "f.proj.bias": rnd(k + "b1", (hid,), std=0.1) + b1_mean,
+            "f.dwc.weight": rnd(k + "dw", (hid, 1, 3, 3), std=1 / 3), "f.dwc.bias": rnd(k + "db", (hid,), std=0.1),
+            "f.aggr.weight": q(rnd(k + "w2", (64, hid, 1, 1), std=hid ** -0.5), dtype), "f.aggr.bias": rnd(k + "b2", (64,), std=0.1)}
 
 
 # ------------------------------------------------------------------------------------------------
@@ -205,6 +221,13 @@ def run_chunked(launch, rows: dict, B: int, N: int, chunk: int):
         for p0 in range(0, N, chunk):
             p1 = min(p0 + chunk, N)
             launch({key: t[b:b + 1, p0:p1] for key, t in rows.items()}, b)
+
+
+def need_trips(units: int, cap: int, depth: int, what: str):
+    """Some loops take ceil(units / cap) >= depth trips, the others exactly one fewer (and at least one)."""
+    hi, lo = -(-units // cap), units // cap
+    assert hi >= depth and lo == hi - 1 and lo >= 1, f"{what}: {units} units on a first trip of {cap}: {hi} / {lo} trips, {depth} wanted"
+    return hi, lo
 
 
 def esc_weights_case(ops, dev, dtype: str, pdim: int, ks: int, nblk: int, B: int = 2, N: int = 777):

@@ -152,3 +152,20 @@ def test_reflect_gather_identity(hw):
     b = esc_ref.window_attention(x, sd64, "blocks.0.attn", 32, 4, gather=True)
     assert torch.equal(a, b)
     assert np.array_equal(esc_ref.reflect_index(33, 64).numpy()[33:], np.arange(31, 0, -1))
+
+
+def test_reflect_pad_and_logits_of_the_restatement():
+    """What test_gpu_esc_edges.py adds to esc_ref: reflect_pad is F.pad(mode="reflect") at the smallest legal frame and at the largest
+    pad, and the logits attention_core hands back are the ones its output is the softmax of (a per-head shift leaves it unchanged)."""
+    F = torch.nn.functional
+    for h, w in [(17, 17), (33, 65), (32, 32)]:
+        x = esc_ref.synth.normal(7, f"pad{h}x{w}", (2, 5, h, w)).double()
+        assert torch.equal(esc_ref.reflect_pad(x, 32), F.pad(x, (0, (-w) % 32, 0, (-h) % 32), mode="reflect"))
+    qkv = esc_ref.synth.normal(7, "logit_qkv", (1, 96, 32, 32)).double()
+    table = esc_ref.synth.normal(7, "logit_rpb", (2, 63 * 63), std=0.5).double()
+    o, s = esc_ref.attention_core(qkv, table, 32, 2, logits=True)
+    assert s.shape == (1, 2, 1024, 1024) and torch.equal(o, esc_ref.attention_core(qkv, table, 32, 2))
+    v = qkv[0, 64:].reshape(2, 16, 1024).transpose(1, 2)
+    assert float((torch.softmax(s[0], -1) @ v - o[0].reshape(2, 16, 1024).transpose(1, 2)).abs().max()) == 0.0
+    shifted = esc_ref.attention_core(qkv, table + torch.tensor([[100.0], [-100.0]], dtype=torch.float64), 32, 2)
+    assert float((shifted - o).abs().max()) <= 1e-12

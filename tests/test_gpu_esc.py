@@ -13,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 import esc_ref as R
-from helpers import check, max_abs, q, rnd
+from helpers import check, esc_ffn_sd as _ffn_sd, max_abs, q, rnd
 from oracle import hat_oracle as O
 from super_resolution_amd import synth
 
@@ -38,13 +38,6 @@ def _rows(x_bchw, ld, tdt, dev, fill=7.0):
 
 def _maps(rows, c, h, w):
     return rows[0, :, :c].float().cpu().t().reshape(1, c, h, w)
-
-
-def _ffn_sd(hid, dtype, b1_mean=0.0):
-    k = f"ecf{hid}"
-    return {"f.proj.weight": q(rnd(k + "w1", (hid, 64, 1, 1), std=1 / 8), dtype), "f.proj.bias": rnd(k + "b1", (hid,), std=0.1) + b1_mean,
-            "f.dwc.weight": rnd(k + "dw", (hid, 1, 3, 3), std=1 / 3), "f.dwc.bias": rnd(k + "db", (hid,), std=0.1),
-            "f.aggr.weight": q(rnd(k + "w2", (64, hid, 1, 1), std=hid ** -0.5), dtype), "f.aggr.bias": rnd(k + "b2", (64,), std=0.1)}
 
 
 def _convffn(dtype, hid, full, dev, b1_mean=0.0, out_f32=False):

@@ -23,7 +23,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import _r8, check, conv_ref_banded, dev_randn, dev_rows, esc_weights_case, q, rnd, run_chunked
+from helpers import _r8, check, conv_ref_banded, dev_randn, dev_rows, esc_weights_case, need_trips, q, rnd, run_chunked
 
 pytestmark = pytest.mark.gpu
 
@@ -57,13 +57,6 @@ def conv64r_trip_tiles(nsl: int, ntiles: int):
     while m > 1 and 8 * (m - 1) >= ntiles:
         m -= 1
     return 8 * m, m
-
-
-def need_trips(units: int, cap: int, depth: int, what: str):
-    """Some loops take ceil(units / cap) >= depth trips, the others exactly one fewer (and at least one)."""
-    hi, lo = -(-units // cap), units // cap
-    assert hi >= depth and lo == hi - 1 and lo >= 1, f"{what}: {units} units on a first trip of {cap}: {hi} / {lo} trips, {depth} wanted"
-    return hi, lo
 
 
 def _dev():

@@ -14,8 +14,9 @@ from super_resolution_amd import synth
 pytestmark = pytest.mark.gpu
 
 WIDTHS = [64, 32]
-#          5x3: smaller than a tile, every pixel is border;  20x37: ragged in both axes;  33x64, B = 2: a tile row of one pixel row
-SHAPES = [(1, 5, 3), (1, 20, 37), (2, 33, 64)]
+#          5x3: smaller than a tile, every pixel is border;  20x37: ragged in both axes;  33x64, B = 2: a tile row of one pixel row;
+#          8x16 and 16x32: exactly one and 2 x 2 tiles of 8 x 16
+SHAPES = [(1, 5, 3), (1, 20, 37), (2, 33, 64), (1, 8, 16), (1, 16, 32)]
 
 
 def _dev():
@@ -42,7 +43,8 @@ def _unfrag(wf, rows, cols):
 
 
 def _half(dtype, c, form, pool, B, H, W, dev, b1=None, dw=None):
-    """Runs hat_naf_half once; returns (g (B,H,W,c) as stored, g_ref fp64, r_out / r_ref or None, partials or None, raw buffers)."""
+    """Runs hat_naf_half once; returns (g_out rows as stored, g_ref fp64, r_out or None, r_ref, partials or None).  form "p" is
+    form b without w1 (the projection that ends the stem): only r_out is written, g_ref is None."""
     from super_resolution_amd import ops
     dt = ops.DTYPE_CODE[dtype]
     tdt = ops.TORCH_DTYPE[dt]
@@ -66,11 +68,21 @@ def _half(dtype, c, form, pool, B, H, W, dev, b1=None, dw=None):
                   r_out=torch.full((B, H * W, ldr), float("nan"), device=dev))
     g_out = torch.full((B, H * W, ldo), float("nan"), dtype=tdt, device=dev)
     part = torch.full((B, ops.naf_tiles(H, W), c), float("nan"), device=dev) if pool else None
-    ops.naf_half(_rows(r, ldr, torch.float32, dev, float("nan")), g_out, ops.naf_frags(w1, dt, dev), b1.to(dev),
+    ops.naf_half(_rows(r, ldr, torch.float32, dev, float("nan")), g_out, None if form == "p" else ops.naf_frags(w1, dt, dev), b1.to(dev),
                  dw.reshape(2 * c, 9).t().contiguous().to(dev), db.to(dev), B=B, H=H, W=W, C_=c, dtype=dt, ldr=ldr, ldo=ldo, partials=part, **kw)
     torch.cuda.synchronize()
-    g_ref = R.gate_half(r_ref.permute(0, 3, 1, 2), w1, b1, dw, db).permute(0, 2, 3, 1)
+    g_ref = None if form == "p" else R.gate_half(r_ref.permute(0, 3, 1, 2), w1, b1, dw, db).permute(0, 2, 3, 1)
     return g_out, g_ref, kw.get("r_out"), r_ref, part
+
+
+def _check_r_out(r_out, r_ref, dtype, c, B, H, W, what):
+    """The stream r_in + Wf . gprev + bf as form b and the projection-only form write it."""
+    check(r_out[:, :, :c].cpu().reshape(B, H, W, c), r_ref, "f32" if dtype == "f32" else "bf16", what + " r_out")
+    assert torch.isnan(r_out[:, :, c:]).all(), what + ": pad channels of r_out were written"
+    err = max_abs(r_out[:, :, :c].cpu().reshape(B, H, W, c), r_ref)
+    print(f"NAF-EDGES {what} r_out: max-abs {err:.3e} (scale {float(r_ref.abs().max()):.3g})")
+    if dtype == "bf16":   # the stream itself is fp32: only its Wf . gprev term carries bf16 operands, exact products, fp32 sums
+        assert err <= 2e-5 * max(1.0, float(r_ref.abs().max())), what
 
 
 @pytest.mark.parametrize("pool", [True, False], ids=["pool", "nopool"])
@@ -86,10 +98,7 @@ def test_naf_half(dtype, c, form, pool):
         check(g, g_ref, dtype, what)                                   # (asserts that everything written is finite)
         assert torch.isnan(g_out[:, :, c:].float()).all(), what + ": pad channels of g_out were written"
         if form == "b":
-            check(r_out[:, :, :c].cpu().reshape(B, H, W, c), r_ref, "f32" if dtype == "f32" else "bf16", what + " r_out")
-            assert torch.isnan(r_out[:, :, c:]).all(), what + ": pad channels of r_out were written"
-            if dtype == "bf16":   # the stream itself is fp32: only its Wf . gprev term carries bf16 operands, exact products, fp32 sums
-                assert max_abs(r_out[:, :, :c].cpu().reshape(B, H, W, c), r_ref) <= 2e-5 * max(1.0, float(r_ref.abs().max())), what
+            _check_r_out(r_out, r_ref, dtype, c, B, H, W, what)
         if pool:
             assert torch.isfinite(part).all(), what + ": a partials slot was not written"
             got, stored = part.double().sum(1).cpu(), g.double().sum(dim=(1, 2))
@@ -122,11 +131,47 @@ def test_naf_half_zero_pads_u_not_x(dtype, c):
 
 @pytest.mark.parametrize("c", WIDTHS)
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
-def test_naf_fold(dtype, c):
+def test_naf_half_projection_only(dtype, c):
+    """w1 = None with gprev, wf, bf, r_out: the stream after the last block.  Nothing but r_out is written."""
+    dev = _dev()
+    for B, H, W in SHAPES:
+        g_out, _, r_out, r_ref, _ = _half(dtype, c, "p", False, B, H, W, dev)
+        what = f"naf_half {dtype} c{c} projection only {B}x{H}x{W}"
+        _check_r_out(r_out, r_ref, dtype, c, B, H, W, what)
+        assert torch.isnan(g_out.float()).all(), what + ": g_out was written"
+
+
+def test_naf_half_refusals():
+    dev = _dev()
+    from super_resolution_amd import ops
+    c, B, H, W = 64, 1, 9, 17
+    z = lambda *shape: torch.zeros(*shape, device=dev)
+    r, r2, g, gp, part = z(B, H * W, c), z(B, H * W, c), z(B, H * W, c), z(B, H * W, c), z(B, ops.naf_tiles(H, W), c)
+    w1, b1, dww, dwb, wf, bf = z(2 * c * c), z(2 * c), z(9, 2 * c), z(2 * c), z(c * c), z(c)
+    geo = dict(B=B, H=H, W=W, C_=c, dtype=ops.HAT_F32)
+    formb = dict(gprev=gp, wf=wf, bf=bf, r_out=r2)
+    ops.naf_half(r, g, w1, b1, dww, dwb, **geo, partials=part, **formb)              # form b and the projection-only form are accepted
+    ops.naf_half(r, g, None, b1, dww, dwb, **geo, **formb)
+    torch.cuda.synchronize()
+    with pytest.raises(RuntimeError, match="HAT_EINVAL"):                             # halo pixels are recomputed from r_in
+        ops.naf_half(r, g, w1, b1, dww, dwb, **geo, **dict(formb, r_out=r))
+    with pytest.raises(RuntimeError, match="HAT_EINVAL"):                             # the halo would read written rows
+        ops.naf_half(r, g, w1, b1, dww, dwb, **geo, **dict(formb, gprev=g))
+    with pytest.raises(RuntimeError, match="HAT_EINVAL"):                             # no gated map, no pool
+        ops.naf_half(r, g, None, b1, dww, dwb, **geo, partials=part, **formb)
+    with pytest.raises(RuntimeError, match="HAT_EINVAL"):                             # form a with the c -> 2c stage switched off
+        ops.naf_half(r, g, None, b1, dww, dwb, **geo)
+    with pytest.raises(RuntimeError, match="HAT_EUNSUPPORTED"):
+        ops.naf_half(r, g, w1, b1, dww, dwb, **dict(geo, C_=48))
+    with pytest.raises(RuntimeError, match="HAT_EINVAL"):                             # fp32 rows are read 4 floats at a time
+        ops.naf_half(r, g, w1, b1, dww, dwb, **geo, ldr=c + 2)
+
+
+def _fold_case(dtype, c, H, W):
     dev = _dev()
     from super_resolution_amd import ops
     dt = ops.DTYPE_CODE[dtype]
-    B, H, W = 2, 20, 37
+    B = 2
     tiles = ops.naf_tiles(H, W)
     part = rnd(f"part{c}", (B, tiles, c), std=3.0)
     blk = ops.PackedNafBlock()
@@ -139,9 +184,25 @@ def test_naf_fold(dtype, c):
     torch.cuda.synchronize()
     Wf, bfr = R.fold(part.double().sum(1) / (H * W), blk.wsca.cpu(), blk.bsca.cpu(), blk.w2.cpu(), blk.b2.cpu(), blk.beta.cpu())
     got = torch.stack([_unfrag(wf[b], c, c) for b in range(B)])
+    print(f"NAF-EDGES naf_fold {dtype} c{c} {H}x{W} ({tiles} tiles): wf max-abs {max_abs(got, Wf):.3e} (scale {float(Wf.abs().max()):.3g})")
     check(got, Wf, dtype, f"naf_fold wf {dtype} c{c}", f32_tol=2e-5)        # (bf16: the stored type's bars; fp32: the issue's 2e-5)
     check(bf.cpu(), bfr[None].expand(B, c), "f32", f"naf_fold bf c{c}", f32_tol=2e-5)
     assert torch.equal(wf, wf2) and torch.equal(bf, bf2), "two runs agree bit for bit"
+
+
+@pytest.mark.parametrize("c", WIDTHS)
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_naf_fold(dtype, c):
+    _fold_case(dtype, c, 20, 37)
+
+
+@pytest.mark.parametrize("c", WIDTHS)
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_naf_fold_one_tile(dtype, c):
+    """5 x 3: one tile, fewer tiles than the kernel has partial-sum lanes per channel (256 / c)."""
+    from super_resolution_amd import ops
+    assert ops.naf_tiles(5, 3) == 1
+    _fold_case(dtype, c, 5, 3)
 
 
 def test_naf_half_is_deterministic():

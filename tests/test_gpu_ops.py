@@ -48,6 +48,13 @@ CONV_CASES = [
     ("lk13", 1, 32, 32, 16, 16, 13, 0),
     ("lk5", 1, 16, 24, 8, 8, 5, 0),
     ("small_3x5", 1, 3, 5, 24, 24, 3, 0),
+    # ESC's shapes (esc_engine.py): `last` / conv_out, to_img at x2 / x3 / x4 (n_store = round4(Cout)), and to_qkv, which hat_linear
+    # does not instantiate (the "esc_qkv" row of LIN_CASES skips), as the k = 1 conv ESCEngine._lin falls back to
+    ("esc_last", 1, 20, 37, 64, 64, 3, 0),
+    ("esc_img_x2", 1, 20, 37, 64, 12, 3, 0),
+    ("esc_img_x3", 1, 20, 37, 64, 27, 3, 0),
+    ("esc_img_x4", 1, 20, 37, 64, 48, 3, 0),
+    ("esc_qkv_k1", 1, 20, 37, 64, 192, 1, 0),
 ]
 
 
@@ -492,7 +499,7 @@ def test_fused_ffn(dtype, geom):
 
 # ------------------------------------------------------------------------------------------------
 LIN_CASES = [("aggr144", 144, 144), ("kv288", 144, 288), ("mlp2_288", 288, 144), ("lin180", 180, 180), ("mlp360", 360, 180),
-             ("kv360", 180, 360), ("tiny24", 24, 48), ("tiny48", 48, 24)]
+             ("kv360", 180, 360), ("tiny24", 24, 48), ("tiny48", 48, 24), ("esc_qkv", 64, 192), ("esc_out", 64, 64)]
 
 
 @pytest.mark.parametrize("dtype", DT)
