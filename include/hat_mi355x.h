@@ -34,7 +34,9 @@ enum { HAT_F32 = 0, HAT_BF16 = 1 };
 enum { HAT_EINVAL = -1, HAT_ELDS = -2, HAT_EUNSUPPORTED = -3 };
 
 /* activation codes */
-enum { HAT_ACT_NONE = 0, HAT_ACT_GELU = 1 /* exact erf, nn.GELU() */, HAT_ACT_LRELU = 2 /* slope 0.01 */ };
+enum { HAT_ACT_NONE = 0, HAT_ACT_GELU = 1 /* exact erf, nn.GELU() */, HAT_ACT_LRELU = 2 /* slope 0.01 */,
+       HAT_ACT_LRELU02 = 3 /* slope 0.2 (ESCReal's to_img head): hat_conv's own kernel only; the resident-weight 3x3 kernel
+                              declines it, hat_linear and hat_conv3x3_small return HAT_EUNSUPPORTED */ };
 /* conv input modes */
 enum { HAT_X_NHWC_T = 0, HAT_X_NHWC_F32 = 1, HAT_X_NCHW_F32_MEAN = 2 };
 /* conv output modes */
@@ -1006,6 +1008,40 @@ int hat_esc_layernorm(const float* x, void* y, const float* gamma, const float* 
                       int32_t ldy, int32_t dtype, void* stream);
 int hat_esc_shuffle_add(const float* rows, const float* x, float* y, int32_t B, int32_t H, int32_t W, int32_t s, int32_t ld,
                         void* stream);
+
+/*
+ * ESCReal: what ESCReal (esc_real_arch.py:402-475) needs beyond ESC's launches.  DESIGN.md 4.15.
+ *
+ * hat_escreal_skip  out = [r +] skip(x), skip = Conv2d(3, 128, 1) -> depthwise Conv2d(128, 128, 7, padding 3, reflect) ->
+ *   LeakyReLU(0.2) -> Conv2d(128, 64, 1) (esc_real_arch.py:460-465), in one launch, 64 pixels per workgroup.
+ *   (1) A 1x1 conv commutes with reflect padding: the hidden map at a pad position is the hidden map at the mirrored pixel, so
+ *       x is gathered at (reflect(y), reflect(x)) and no padded copy exists.
+ *   (2) Reflect padding puts all 49 taps of every pixel inside, so the first two layers are one dense 7x7 conv 3 -> 128 with
+ *       weights dw[c][tap] * W0[c][ci] and the constant bias b0[c] * sum_tap dw[c][tap] + bdw[c] (packing.escreal_skip_fold).
+ *   Both GEMMs run on the MFMA units, operands rounded to T, fp32 accumulation; the 128-wide map stays in LDS.
+ *     x      (B,3,H,W) fp32 planes
+ *     w1     T fragments [8][5][64 lanes][8] of the (128, 160) matrix, column k = 3 tap + ci (tap = 7 ky + kx), k >= 147 zero:
+ *            element (t, ks, l, j) = Wf[16 t + (l & 15)][32 ks + 8 (l >> 4) + j];  b1 fp32 [128]
+ *     w3     T fragments [4][4][64][8] of the (64, 128) matrix, same element order;  b3 fp32 [64]
+ *     r      optional (B,H,W,ldr) fp32 rows added to the result, ldr >= 64, ldr % 4 == 0
+ *     out    (B,H,W,ldo) fp32 rows, ldo >= 64, ldo % 4 == 0
+ *   HAT_EINVAL, before any launch: a null or misaligned pointer (16 bytes; x: 4), bad leading dimensions, H or W < 4 (reflect
+ *   pad 3 needs a side of at least 4), B < 1 or > 65535, an unknown dtype.
+ *
+ * hat_dysample  the gather of DySample (esc_real_arch.py:361-399; groups 4, end_conv 64 -> 3) with end_conv moved in front of
+ *   the (linear) bilinear sampling.  rows (B,H,W,ld) fp32 hold per LR pixel [offset(x) 8 s^2 | scope(x) 8 s^2 | proj 12]:
+ *   offset includes its bias, scope has none, proj[3 grp + o] = sum_c end_conv.weight[o][16 grp + c] x[16 grp + c].  Entry
+ *   d 4 s^2 + grp s^2 + i s + j of offset / scope / init_pos is axis d (0: x, 1: y) of group grp at output pixel
+ *   (s y + i, s x + j): the reference's view(B, 2, -1, H, W), pixel_shuffle(s), view(B, 2, 4, sH, sW).  Per output pixel and
+ *   group: off = offset * sigmoid(scope) * 0.5 + init_pos; the grid value 2 (c + 0.5 + off) / size - 1 is un-normalised as
+ *   grid_sample(align_corners=False) does and clamped to [0, size - 1] (padding_mode='border'); the four corners are blended;
+ *   y[b][o][Y][X] = bias[o] + the sum over the groups.  y: (B,3,sH,sW) fp32 planes.  A sample may lie anywhere in the frame.
+ *   s in 2..4 (HAT_EUNSUPPORTED otherwise); HAT_EINVAL for null pointers, B, H, W < 1, ld < 16 s^2 + 12.
+ */
+int hat_escreal_skip(const float* x, const void* w1, const float* b1, const void* w3, const float* b3, const float* r, float* out,
+                     int32_t B, int32_t H, int32_t W, int32_t ldr, int32_t ldo, int32_t dtype, void* stream);
+int hat_dysample(const float* rows, const float* init_pos, const float* bias, float* y, int32_t B, int32_t H, int32_t W, int32_t s,
+                 int32_t ld, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("HAT_MI355X_LIB") or os.path.join(_HERE, "libhat_mi355
 
 ABI_VERSION = 2   # == HAT_ABI_VERSION of include/hat_mi355x.h: bump both whenever a descriptor or packing changes
 HAT_F32, HAT_BF16 = 0, 1
-ACT_NONE, ACT_GELU, ACT_LRELU = 0, 1, 2
+ACT_NONE, ACT_GELU, ACT_LRELU, ACT_LRELU02 = 0, 1, 2, 3   # LRELU: slope 0.01; LRELU02: slope 0.2, hat_conv only
 X_NHWC_T, X_NHWC_F32, X_NCHW_F32_MEAN = 0, 1, 2
 O_NHWC_T, O_NHWC_F32, O_PIXSHUF_T, O_NCHW_F32 = 0, 1, 2, 3
 METRICS_Y, METRICS_BGR, METRICS_PSNR, METRICS_SSIM = 1, 2, 4, 8   # flags of hat_u8_metrics
@@ -250,6 +250,8 @@ SIGNATURES = {
     "hat_window_attention_r": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 10 + [C.c_void_p]),
     "hat_esc_layernorm": (C.c_int, [C.c_void_p] * 4 + [C.c_float, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "hat_esc_shuffle_add": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p]),
+    "hat_escreal_skip": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 6 + [C.c_void_p]),
+    "hat_dysample": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]),
 }
 
 _lib = None

@@ -134,7 +134,6 @@ class ESC(HAT):
 
     def engine(self, device=None):
         """The packed-weight engine for the current parameters (re-packed when they change)."""
-        from ..esc_engine import ESCEngine
         device = torch.device(device) if device is not None else self._anchor().device
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
@@ -143,9 +142,13 @@ class ESC(HAT):
             if self._anchor().device != device:
                 raise RuntimeError(f"input is on {device} but the parameters are on {self._anchor().device}: "
                                    f"move the module first (net.to('{device}'))")
-            self._engine = ESCEngine(self.cfg, self.state_dict(), device, self.compute_dtype)
+            self._engine = self._make_engine(device)
             self._engine_key = key
         return self._engine
+
+    def _make_engine(self, device):
+        from ..esc_engine import ESCEngine
+        return ESCEngine(self.cfg, self.state_dict(), device, self.compute_dtype)
 
     def forward(self, x):
         if self.training:

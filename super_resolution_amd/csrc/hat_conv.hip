@@ -406,6 +406,9 @@ __global__ __launch_bounds__(WAVES * 64) void conv_kernel(const HatConvDesc d) {
                     } else if (d.act == HAT_ACT_LRELU) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = v[r] >= 0.f ? v[r] : 0.01f * v[r];
+                    } else if (d.act == HAT_ACT_LRELU02) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = v[r] >= 0.f ? v[r] : 0.2f * v[r];
                     }
                     if (has_r1) {
                         if constexpr ((TH & 1) != 0) v += h4raw_to_f32(r1v[i][pt]);
@@ -588,6 +591,7 @@ int conv_validate(const HatConvDesc& d) {
         if ((d.reserved0 & 2) && (d.out_mode != HAT_O_NHWC_F32 || d.ldo % 8 || reinterpret_cast<uintptr_t>(d.out) % 16)) return HAT_EINVAL;
     }
     if (d.B < 1 || d.H < 1 || d.W < 1 || d.Cin < 1) return HAT_EINVAL;
+    if (d.act < HAT_ACT_NONE || d.act > HAT_ACT_LRELU02) return HAT_EINVAL;
     if (d.ksize < 1 || (d.ksize & 1) == 0 || d.ksize > 17) return HAT_EINVAL;   // (17: the OCAB-ESC kernel of the HATX training config)
     if (d.dtype != HAT_F32 && d.dtype != HAT_BF16) return HAT_EINVAL;
     const int kc = (d.dtype == HAT_BF16 ? 64 : 32) * (d.nt == 1 ? 3 : (d.nt <= 4 ? 2 : 1)), vec = d.dtype == HAT_BF16 ? 8 : 4;

@@ -552,6 +552,7 @@ extern "C" int hat_linear(const HatConvDesc* dp, void* stream) {
     const HatConvDesc& d = *dp;
     if (!d.x || !d.w || !d.bias || !d.out || d.ksize != 1 || d.B < 1 || d.H < 1 || d.W < 1 || d.Cin < 4) return HAT_EINVAL;
     if (d.x_mode != HAT_X_NHWC_T || (d.out_mode != HAT_O_NHWC_T && d.out_mode != HAT_O_NHWC_F32)) return HAT_EINVAL;
+    if (d.act == HAT_ACT_LRELU02) return HAT_EUNSUPPORTED;   // (hat_conv's own kernel has it)
     if (d.n_store % 4 || d.ldo % 4 || d.n_store > d.n_slices * d.nt * 16 || d.colsum) return HAT_EINVAL;
     const int vec = d.dtype == HAT_BF16 ? 8 : 4;
     if (d.ldx % vec || d.Cin % 4 || (d.x0 && (d.ldx0 % vec || d.c_split % vec || d.c_split > d.Cin))) return HAT_EINVAL;
@@ -693,6 +694,7 @@ extern "C" int hat_conv3x3_small(const HatConvDesc* dp, void* stream) {
     if (!d.x || !d.w || !d.bias || !d.out || d.B < 1 || d.H < 1 || d.W < 1) return HAT_EINVAL;
     const int vec = d.dtype == HAT_BF16 ? 8 : 4;
     if (d.ldx % vec || d.n_store % 4 || d.ldo % 4 || d.n_store > d.nt * 16) return HAT_EINVAL;
+    if (d.act == HAT_ACT_LRELU02) return HAT_EUNSUPPORTED;
     return tap3_dispatch(d, reinterpret_cast<hipStream_t>(stream), nullptr);
 }
 

@@ -13,7 +13,7 @@ import torch
 
 from . import ops
 from .engine import _ESC
-from .ops import O_NHWC_F32, O_NHWC_T, X_NCHW_F32_MEAN, X_NHWC_F32
+from .ops import ACT_LRELU02, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T, X_NCHW_F32_MEAN, X_NHWC_F32
 
 LN_EPS = 1e-6   # esc_arch.py:69
 SUPPORTED = dict(dim=64, pdim=16, kernel_size=13, window_size=32, num_heads=4)
@@ -71,9 +71,17 @@ class ESCEngine:
             b.conv_out = ops.pack_conv_weight(sd[p + ".conv_out.weight"], sd[p + ".conv_out.bias"], dt, dev)
             self.blocks.append(b)
         self.last = ops.pack_conv_weight(sd["last.weight"], sd["last.bias"], dt, dev)
-        self.to_img = ops.pack_conv_weight(sd["to_img.weight"], sd["to_img.bias"], dt, dev)
+        self._pack_head(sd)
         self._kpad = self.blocks[0].convs[0][2].kpad if self.blocks and self.blocks[0].convs else 0
         self._ws_cache = collections.OrderedDict()
+
+    def _pack_head(self, sd):
+        self.to_img = ops.pack_conv_weight(sd["to_img.weight"], sd["to_img.bias"], self.dtype, self.dev)
+
+    def _head_buffers(self, B: int, H: int, W: int, f, t) -> dict:
+        """What the end of the network needs beside the body's buffers; f / t allocate fp32 / T tensors."""
+        s = self.scale
+        return {"rows": f(B, H * W, _r4(3 * s * s)), "y": f(B, 3, H * s, W * s)}
 
     # ------------------------------------------------------------------------------------------
     def _workspace(self, B: int, H: int, W: int):
@@ -82,12 +90,12 @@ class ESCEngine:
         if w is not None:
             self._ws_cache.move_to_end(key)
             return w
-        dev, N, C, s = self.dev, H * W, self.C, self.scale
+        dev, N, C = self.dev, H * W, self.C
         f = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
         t = lambda *shape: torch.zeros(*shape, dtype=self.tdt, device=dev)
         w = {"feat0": f(B, N, C), "s": [f(B, N, C) for _ in range(3)], "n": t(B, N, C), "qkv": t(B, N, 3 * C), "att": t(B, N, C),
-             "z": t(B, N, C), "y16": t(B, N, 16), "gap": f(B, ops.esc_convffn_tiles(H, W), 16), "weff": t(B, 16, max(self._kpad, 1)),
-             "rows": f(B, N, _r4(3 * s * s)), "y": f(B, 3, H * s, W * s)}
+             "z": t(B, N, C), "y16": t(B, N, 16), "gap": f(B, ops.esc_convffn_tiles(H, W), 16), "weff": t(B, 16, max(self._kpad, 1))}
+        w.update(self._head_buffers(B, H, W, f, t))
         self._ws_cache[key] = w
         while len(self._ws_cache) > 4:
             self._ws_cache.popitem(last=False)
@@ -111,6 +119,7 @@ class ESCEngine:
         ws = self.ws
         if (-H) % ws > H - 1 or (-W) % ws > W - 1:
             raise RuntimeError(f"a {H}x{W} frame cannot be reflect-padded to a multiple of window_size {ws}: the padding must be smaller than the frame")
+        self._check_frame(H, W)
         x = x.to(torch.float32).contiguous()
         w, C, dt, N = self._workspace(B, H, W), self.C, self.dtype, H * W
         geo = dict(B=B, H=H, W=W)
@@ -146,8 +155,85 @@ class ESCEngine:
             ops.esc_layernorm(xa, w["n"], *b.ln_out, npix=B * N, dtype=dt, eps=LN_EPS)
             ops.conv(b.conv_out, w["n"], xb, **geo, dtype=dt, ldx=C, ldo=C, out_mode=O_NHWC_F32, r1=cur, ldr1=C)
             cur = xb
+        return self._tail(x, w, cur, geo)
+
+    def _check_frame(self, H: int, W: int):
+        pass
+
+    def _tail(self, x, w, cur, geo):
+        """last (+ feat0), to_img, the pixel shuffle plus the base image                                       esc_arch.py:383-385"""
+        C, dt = self.C, self.dtype
+        B, H, W = geo["B"], geo["H"], geo["W"]
         ops.conv(self.last, cur, w["n"], **geo, dtype=dt, ldx=C, ldo=C, x_mode=X_NHWC_F32, r1=w["feat0"], ldr1=C)
         ld = w["rows"].shape[2]
         ops.conv(self.to_img, w["n"], w["rows"], **geo, dtype=dt, ldx=C, ldo=ld, out_mode=O_NHWC_F32, n_store=ld)
         ops.esc_shuffle_add(w["rows"], x, w["y"], B=B, H=H, W=W, s=self.scale, ld=ld)
+        return w["y"]
+
+
+class ESCRealEngine(ESCEngine):
+    """ESCReal (esc_real_arch.py:402-475): ESC's body with use_ln, then
+        hat_escreal_skip (feat0 + skip(x))  ->  last (+ that)  ->  the head:
+        default   to_img.1, to_img.4 folded to conv 64 -> 256 + PixelShuffle(2) (+ LeakyReLU 0.2), to_img.6 (+ LeakyReLU 0.2), to_img.8 -> planes
+        DySample  one pointwise launch [offset | scope | end_conv per group]  ->  hat_dysample
+    DESIGN.md §4.15.  The default head is x4 whatever upscaling_factor says (two hard-coded nearest x2 steps, as the reference)."""
+
+    def _pack_head(self, sd):
+        dt, dev = self.dtype, self.dev
+        self.dysample = bool(self.cfg.get("use_dysample", False))
+        self.skip = ops.pack_escreal_skip(sd, "skip", dt, dev)
+        if self.dysample:
+            s = self.scale
+            if s not in (2, 3, 4):
+                raise ValueError(f"ESCReal with use_dysample and upscaling_factor={s} is not supported: hat_dysample is built for 2, 3 and 4")
+            f32 = lambda k: sd[k].detach().to(torch.float32).cpu()
+            wd, bd = ops.dysample_fold(f32("to_img.offset.weight"), f32("to_img.offset.bias"), f32("to_img.scope.weight"),
+                                       f32("to_img.end_conv.weight"))
+            self.dys = ops.pack_pointwise(wd, bd, dt, dev)
+            self.dys_ld = wd.shape[0]
+            self.dys_init = f32("to_img.init_pos").reshape(-1).contiguous().to(dev)
+            self.dys_bias = f32("to_img.end_conv.bias").contiguous().to(dev)
+            self.out_scale = s
+            return
+        self.out_scale = 4
+        self.up1 = ops.pack_nearest_conv(sd["to_img.1.weight"], sd["to_img.1.bias"], dt, dev)
+        self.up2 = ops.pack_nearest_conv(sd["to_img.4.weight"], sd["to_img.4.bias"], dt, dev)
+        self.hr = ops.pack_conv_weight(sd["to_img.6.weight"], sd["to_img.6.bias"], dt, dev)
+        self.out = ops.pack_conv_weight(sd["to_img.8.weight"], sd["to_img.8.bias"], dt, dev)
+        self.out_sweep = None   # the row-sweep kernel for the 64 -> 3 conv at output size, where HATEngine takes it for conv_last
+        if ops.conv3x3_to_planes_supported(3, 64, 16, dt):
+            self.out_sweep = ops.pack_cab_squeeze(sd["to_img.8.weight"], sd["to_img.8.bias"], dev)
+
+    def _head_buffers(self, B, H, W, f, t):
+        s = self.out_scale
+        w = {"y": f(B, 3, H * s, W * s)}
+        if self.dysample:
+            w["rows"] = f(B, H * W, self.dys_ld)
+        else:
+            w.update(u1=t(B, 4 * H * W, 64), u2=t(B, 16 * H * W, 64), u3=t(B, 16 * H * W, 64))
+        return w
+
+    def _check_frame(self, H, W):
+        if H < 4 or W < 4:
+            raise RuntimeError(f"a {H}x{W} frame cannot be reflect-padded by 3 for the skip branch's 7x7 conv: a side of at least 4 is needed")
+
+    def _tail(self, x, w, cur, geo):
+        C, dt = self.C, self.dtype
+        B, H, W = geo["B"], geo["H"], geo["W"]
+        sk = next(s for s in w["s"] if s is not cur)
+        ops.escreal_skip(self.skip, x, sk, **geo, dtype=dt, r=w["feat0"], ldr=C, ldo=C)
+        ops.conv(self.last, cur, w["n"], **geo, dtype=dt, ldx=C, ldo=C, x_mode=X_NHWC_F32, r1=sk, ldr1=C)
+        if self.dysample:
+            self._lin(self.dys, w["n"], w["rows"], geo=geo, ldx=C, ldo=self.dys_ld, out_mode=O_NHWC_F32)
+            ops.dysample(w["rows"], self.dys_init, self.dys_bias, w["y"], **geo, s=self.scale, ld=self.dys_ld)
+            return w["y"]
+        ops.conv(self.up1, w["n"], w["u1"], **geo, dtype=dt, ldx=C, ldo=C, out_mode=O_PIXSHUF_T, ps_r=2, act=ACT_LRELU02)
+        ops.conv(self.up2, w["u1"], w["u2"], B=B, H=2 * H, W=2 * W, dtype=dt, ldx=C, ldo=C, out_mode=O_PIXSHUF_T, ps_r=2, act=ACT_LRELU02)
+        ops.conv(self.hr, w["u2"], w["u3"], B=B, H=4 * H, W=4 * W, dtype=dt, ldx=C, ldo=C, act=ACT_LRELU02)
+        if self.out_sweep is not None and (4 * W) % 16 == 0:
+            wpk, b8 = self.out_sweep
+            ops.conv3x3_to_planes(w["u3"], wpk, b8, w["y"], B=B, H=4 * H, W=4 * W, C_=C, ldx=C, n_out=3, out_scale=1.0, mean=(0.0, 0.0, 0.0, 0.0),
+                                  dtype=dt)
+        else:
+            ops.conv(self.out, w["u3"], w["y"], B=B, H=4 * H, W=4 * W, dtype=dt, ldx=C, ldo=0, out_mode=O_NCHW_F32)
         return w["y"]

@@ -11,12 +11,12 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import (ACT_GELU, ACT_LRELU, ACT_NONE, HAT_BF16, HAT_F32, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T,
+from ._lib import (ACT_GELU, ACT_LRELU, ACT_LRELU02, ACT_NONE, HAT_BF16, HAT_F32, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T,
                    X_NCHW_F32_MEAN, X_NHWC_F32, X_NHWC_T, HatAggrCabDesc, HatCabFoldDesc, HatConvDesc, HatFfnDesc, HatHabTailDesc, HatMlpDesc, HatNafFoldDesc,
                    HatNafHalfDesc, HatEscConvFfnDesc)
 # host-side weight packing lives in packing.py; ops.pack_* / ops.Packed* stay the names the engine, the tools and the tests use
 from .packing import (ESC_HID_PAD, FP16_SAFE, KC, NAF_WIDTHS, TORCH_DTYPE, PackedConv, PackedEscFfn, PackedFFN, PackedMlp, PackedNafBlock, choose_nt,  # noqa: F401
-                      esc_geo_ensemble, pack_esc_convffn,
+                      esc_geo_ensemble, pack_esc_convffn, PackedEscRealSkip, dysample_fold, pack_escreal_skip, pack_nearest_conv,
                       choose_nt_linear, naf_ffn_fold, naf_frags, pack_naf_block,
                       ffn_fp16_range_bound, pack_cab_squeeze, pack_cab_w2f, pack_conv_weight, pack_ffn, pack_ffn2, pack_ffn3,
                       pack_linear_weight, pack_ocab_mlp, pack_ocab_qkv, pack_pointwise)
@@ -352,6 +352,27 @@ def esc_shuffle_add(rows, x, y, *, B: int, H: int, W: int, s: int, ld: int):
     lib = _lib.load()
     _timed("esc_shuffle_add_kernel", 0.0, lambda: _lib.check(
         lib.hat_esc_shuffle_add(_ptr(rows), _ptr(x), _ptr(y), B, H, W, s, ld, _stream()), "hat_esc_shuffle_add"), tag=f"shuffle x{s} {H}x{W}")
+
+
+# ------------------------------------------------------------------------------------------------
+# ESCReal (hat_escreal_skip / hat_dysample)
+# ------------------------------------------------------------------------------------------------
+def escreal_skip(ps: PackedEscRealSkip, x, out, *, B: int, H: int, W: int, dtype: int, r=None, ldr: int = 64, ldo: int = 64):
+    """out (fp32 rows) = [r +] skip(x), x (B,3,H,W) fp32 planes: the reflect-padded 7x7 skip branch of ESCReal in one launch."""
+    lib = _lib.load()
+    npx = float(B * H * W)
+    _timed(f"escreal_skip_kernel<{_TNAME[dtype]}>", 2.0 * npx * 128 * (147 + 64), lambda: _lib.check(
+        lib.hat_escreal_skip(_ptr(x), _ptr(ps.w1), _ptr(ps.b1), _ptr(ps.w3), _ptr(ps.b3), _ptr(r), _ptr(out), B, H, W, ldr, ldo, dtype,
+                             _stream()), "hat_escreal_skip"),
+        tag=f"skip 3->128->64 {H}x{W}{' r' if r is not None else ''}", nbytes=npx * (12 + 256 + (256 if r is not None else 0)))
+
+
+def dysample(rows, init_pos, bias, y, *, B: int, H: int, W: int, s: int, ld: int):
+    """y (B,3,sH,sW) fp32 = DySample's gather over rows (B,H*W,ld) fp32 = [offset | scope | 12 projected values] (hat_dysample)."""
+    lib = _lib.load()
+    _timed("dysample_kernel", 0.0, lambda: _lib.check(
+        lib.hat_dysample(_ptr(rows), _ptr(init_pos), _ptr(bias), _ptr(y), B, H, W, s, ld, _stream()), "hat_dysample"),
+        tag=f"dysample x{s} {H}x{W}", nbytes=4.0 * B * H * W * (ld + 3 * s * s))
 
 
 LOG2E = 1.4426950408889634

@@ -443,3 +443,72 @@ def esc_geo_ensemble(k: torch.Tensor) -> torch.Tensor:
     """The mean of the 8 flips / rotations of a (pdim, pdim, k, k) filter, in the reference's order of additions (esc_arch.py:289-298)."""
     r = torch.rot90(k, -1, [2, 3])
     return (k + k.flip([3]) + k.flip([2]) + k.flip([2, 3]) + r + r.flip([3]) + r.flip([2]) + r.flip([2, 3])) / 8
+
+
+# ------------------------------------------------------------------------------------------------
+# ESCReal (esc_real_arch.py:402-475): the three pack-time folds.  Each fold function computes in the dtype of its arguments
+# (the packers pass fp32; the tests pass fp64 to pin the identities to round-off).
+# ------------------------------------------------------------------------------------------------
+def escreal_skip_fold(w0, b0, dw, bdw):
+    """skip.0 (1x1 3 -> 128) followed by skip.1 (depthwise 7x7, reflect padding) as ONE dense 7x7 conv 3 -> 128 on the
+    reflect-padded image: reflect padding leaves no tap outside, so Wf[c][ci][ky][kx] = dw[c][ky][kx] * W0[c][ci] and the bias is
+    the constant b0[c] * sum_tap dw[c][tap] + bdw[c].  -> (Wf (128, 3, 7, 7), bf (128,))."""
+    c = w0.shape[0]
+    d = dw.reshape(c, 1, 7, 7)
+    return d * w0.reshape(c, 3, 1, 1), b0 * d.sum((1, 2, 3)) + bdw
+
+
+def nearest_conv_fold(w, b):
+    """UpsamplingNearest2d(2) -> Conv2d(I, O, 3, 1, 1) as Conv2d(I, 4 O, 3, 1, 1) at the low size -> PixelShuffle(2): for output
+    phase (i, j) every HR tap's weight is added onto the LR tap it lands on — rows {-1 | 0, +1} for i = 0, {-1, 0 | +1} for i = 1,
+    columns alike — and the output channel is 4 c + 2 i + j.  Zero padding agrees at every border: an HR tap outside the x2 map
+    lands on an LR tap outside the map.  -> (weight (4 O, I, 3, 3), bias (4 O,))."""
+    o, i = w.shape[:2]
+    m = torch.tensor([[[1, 0, 0], [0, 1, 1], [0, 0, 0]], [[0, 0, 0], [1, 1, 0], [0, 0, 1]]], dtype=w.dtype)   # [phase][LR tap][HR tap]
+    wf = torch.einsum("iak,jbl,cnkl->cijnab", m, m, w).reshape(4 * o, i, 3, 3)
+    return wf, b.repeat_interleave(4)
+
+
+def dysample_fold(offset_w, offset_b, scope_w, end_w, groups: int = 4):
+    """DySample's three pointwise layers as one: rows [offset 8 s^2 | scope 8 s^2 (no bias) | proj 3 groups], proj[3 g + o] =
+    end_conv.weight[o] restricted to group g's channels — end_conv in front of the (linear) sampling; end_conv.bias joins after
+    it (the four bilinear weights of a group sum to 1, and the bias counts once, not once per group).
+    -> (weight (16 s^2 + 3 groups, C), bias)."""
+    c = offset_w.shape[1]
+    cg = c // groups
+    ew = end_w.reshape(end_w.shape[0], c)
+    proj = torch.zeros(groups * ew.shape[0], c, dtype=ew.dtype)
+    for g in range(groups):
+        proj[ew.shape[0] * g: ew.shape[0] * (g + 1), cg * g: cg * (g + 1)] = ew[:, cg * g: cg * (g + 1)]
+    w = torch.cat([offset_w.reshape(-1, c), scope_w.reshape(-1, c), proj], 0)
+    return w, torch.cat([offset_b, torch.zeros(w.shape[0] - offset_b.shape[0], dtype=offset_b.dtype)])
+
+
+class PackedEscRealSkip:
+    """The skip branch in hat_escreal_skip's operand layouts (include/hat_mi355x.h "ESCReal"): w1 T fragments [8][5][64][8] of the
+    folded (128, 160) matrix (column 3 tap + ci, 147.. zero), b1 [128], w3 T fragments [4][4][64][8] of the (64, 128) 1x1, b3 [64]."""
+    __slots__ = ("w1", "b1", "w3", "b3")
+
+
+def pack_escreal_skip(sd, p: str, dtype: int, device) -> PackedEscRealSkip:
+    """sd[p + '.0.weight'] ... of ESCReal.skip (esc_real_arch.py:460-465) -> PackedEscRealSkip."""
+    w0, dw, w3 = _f32(sd[p + ".0.weight"]), _f32(sd[p + ".1.weight"]), _f32(sd[p + ".3.weight"])
+    if tuple(w0.shape) != (128, 3, 1, 1) or tuple(dw.shape) != (128, 1, 7, 7) or tuple(w3.shape) != (64, 128, 1, 1):
+        raise ValueError(f"skip branch {tuple(w0.shape)} / {tuple(dw.shape)} / {tuple(w3.shape)} is not supported: hat_escreal_skip is "
+                         "built for 3 -> 128 (1x1), depthwise 7x7, 128 -> 64 (1x1)")
+    wf, bf = escreal_skip_fold(w0, _f32(sd[p + ".0.bias"]), dw, _f32(sd[p + ".1.bias"]))
+    f = PackedEscRealSkip()
+    f.w1 = frags(_pad(wf.permute(0, 2, 3, 1).reshape(128, 147), 128, 160)).to(TORCH_DTYPE[dtype]).contiguous().to(device)   # k = 3 tap + ci
+    f.b1 = bf.contiguous().to(device)
+    f.w3 = frags(w3.reshape(64, 128)).to(TORCH_DTYPE[dtype]).contiguous().to(device)
+    f.b3 = _f32(sd[p + ".3.bias"]).contiguous().to(device)
+    return f
+
+
+def pack_nearest_conv(weight, bias, dtype: int, device) -> PackedConv:
+    """nearest x2 + 3x3 conv -> the folded conv for hat_conv with HAT_O_PIXSHUF_T (ps_r = 2): output channel 4 c + ij is stored as
+    packed row ij * O + c, HATEngine's Upsample layout."""
+    wf, bf = nearest_conv_fold(_f32(weight), _f32(bias))
+    o = weight.shape[0]
+    n = torch.arange(4 * o)
+    return pack_conv_weight(wf, bf, dtype, device, out_perm=(n % o) * 4 + n // o)
