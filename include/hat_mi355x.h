@@ -1043,6 +1043,47 @@ int hat_escreal_skip(const float* x, const void* w1, const float* b1, const void
 int hat_dysample(const float* rows, const float* init_pos, const float* bias, float* y, int32_t B, int32_t H, int32_t W, int32_t s,
                  int32_t ld, void* stream);
 
+/*
+ * ESCFP: what ESCFP (esc_fp_arch.py:247-355; 48 channels, 3 heads of 16) needs beyond ESC's launches.  DESIGN.md 4.16.
+ * hat_window_attention_r, hat_esc_conv13, hat_conv and hat_linear serve it as they are.
+ *
+ * hat_escfp_convffn  hat_esc_convffn at 48 channels: the same descriptor, the same contract with 48 wherever that one says 64
+ *   (ldx, ldr, ldo >= 48; ln_g, ln_b [48]; b2 [48]; the LayerNorm divides by 48), the same 8 x 12 tiles and pool-partial slots
+ *   (hat_esc_convffn_tiles).  Channels >= 48 of a row are neither read nor written.
+ *     hid_p   the hidden width padded: 64 (int(48 * 1.25) = 60) or 96 (72 = Block.proj's int(48 * 1.5), and 96);
+ *             HAT_EUNSUPPORTED otherwise
+ *     w1      T fragments [hid_p/16][2][64 lanes][8] of the (hid_p, 64) matrix W1 zero-padded from 48 to 64 columns (48 is one
+ *             and a half k-steps: the x image in LDS is padded with zeros likewise)
+ *     w2      T fragments [3][hid_p/32][64][8] of the (48, hid_p) matrix
+ *
+ * hat_escfp_layernorm  hat_esc_layernorm over 48 channels: x (npix, ldx >= 48) fp32 -> y (npix, ldy >= 48) T, `eps` an argument.
+ *
+ * hat_escfp_weights  the per-sample weights of DecomposedConvolutionalAttention (esc_fp_arch.py:102-120), pdim 16, 13 x 13:
+ *       p = mean over the frame = (fixed-order sum of the nblk pool partials [B][nblk][16]) / npix
+ *       dyn = W2 gelu(W1 p + b1) + b2                     W1 (4,16), b1 [4], W2 (144,4) rows 9 o + 3 ky + kx, b2 [144]; erf GELU
+ *       K[o][tap] = lk_spatial[o][tap] + (dyn[o] on the central 3 x 3 taps)
+ *       w_out[b][o][16 tap + i] = T( lk_channel[o][i] * K[o][tap] )          one fp32 product, rounded once
+ *   A 1x1 conv (lk_channel, no bias) followed by a depthwise 13 x 13 with zero padding is this dense 16 -> 16 conv with zero
+ *   padding, at the border too.  w_out: (B,16,Kpad) T in the [16][Kpad] row layout hat_esc_conv13 and hat_conv (ksize 13,
+ *   w_bstride = 16 Kpad) read; K >= 169 * 16 is written as zeros.  All operands fp32; lk_channel [16][16], lk_spatial [16][169].
+ *   No atomics: two runs agree bit for bit.  HAT_EINVAL for a null pointer, B, nblk or npix < 1, Kpad < 2704.
+ *
+ * hat_escfp_shuffle_bicubic  y[b][c][s yy + i][s xx + j] = rows[b][yy][xx][c s^2 + s i + j] + bicubic_s(x)[b][c][s yy + i][s xx + j]
+ *   (esc_fp_arch.py:354): rows (B,H,W,ld) fp32, x (B,3,H,W) fp32 planes, y (B,3,sH,sW) fp32 planes.  bicubic_s is
+ *   F.interpolate(scale_factor = s, mode = 'bicubic', align_corners = False): Keys' cubic with A = -0.75 at src = (o + 0.5) / s
+ *   - 0.5, so output phase p = o % s has four fixed weights ptab[p][0..3] (fp32 [s][4], 16-byte aligned) on the source taps
+ *   o / s + first .. first + 3, first = (2 p + 1 < s) ? -2 : -1, each tap index clamped to the frame: any H, W >= 1 is legal.
+ *   No clamp of the result.  s in 2..4 (HAT_EUNSUPPORTED otherwise); HAT_EINVAL for null pointers, B, H, W < 1, ld < 3 s^2.
+ */
+int hat_escfp_convffn(const HatEscConvFfnDesc* d, void* stream);
+int hat_escfp_layernorm(const float* x, void* y, const float* gamma, const float* beta, float eps, int64_t npix, int32_t ldx,
+                        int32_t ldy, int32_t dtype, void* stream);
+int hat_escfp_weights(const float* partials, int32_t nblk, int64_t npix, const float* w1, const float* b1, const float* w2,
+                      const float* b2, const float* lk_channel, const float* lk_spatial, void* w_out, int32_t B, int32_t Kpad,
+                      int32_t dtype, void* stream);
+int hat_escfp_shuffle_bicubic(const float* rows, const float* x, const float* ptab, float* y, int32_t B, int32_t H, int32_t W,
+                              int32_t s, int32_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,49 +73,16 @@ _NOT_BUILT = ("ESC runs its float forward only: {} is not built for it (DESIGN.m
               "tile_parallel work")
 
 
-@ARCH_REGISTRY.register()
-class ESC(HAT):
-    """The ESC network on the MI355X.  It is a `HAT` from the engine up — `compute_dtype` / `set_compute_dtype`, `use_graph` and the
-    weight-change tracking are HAT's own — over a module tree and an engine of its own.
-
-    Built: dim 64, pdim 16, kernel_size 13, window_size 32, num_heads 4, exp_ratio 1.25 or 2, any n_blocks / conv_blocks,
-    use_ln either way (ESC, ESC-light, ESCReal's body); anything else is a ValueError when the engine packs.  One frame per
-    forward, as in the reference's eval path.  Extra (non-reference) keywords: `compute_dtype` ('bf16' | 'fp32') and `use_graph`."""
-
-    def __init__(self, dim: int, pdim: int, kernel_size: int, n_blocks: int, conv_blocks: int, window_size: int, num_heads: int,
-                 upscaling_factor: int, exp_ratio: int = 2, attn_type: str = 'Flex', use_ln: bool = False, compute_dtype: str = "bf16",
-                 use_graph: bool = False):
-        nn.Module.__init__(self)   # (HAT's own constructor builds HAT's tree: this class has another)
-        if attn_type not in ('Naive', 'SDPA', 'Flex'):
-            raise NotImplementedError(f'Attention type {attn_type} is not supported.')
-        self.plk_filter = nn.Parameter(torch.randn(pdim, pdim, kernel_size, kernel_size))
-        torch.nn.init.orthogonal_(self.plk_filter)
-        self.proj = nn.Conv2d(3, dim, 3, 1, 1)
-        self.blocks = nn.ModuleList([_Block(dim, pdim, conv_blocks, window_size, num_heads, exp_ratio, use_ln) for _ in range(n_blocks)])
-        self.last = nn.Conv2d(dim, dim, 3, 1, 1)
-        self.to_img = nn.Conv2d(dim, 3 * upscaling_factor ** 2, 3, 1, 1)
-        self.upscaling_factor = self.upscale = int(upscaling_factor)
-        self.window_size, self.attn_type, self.in_chans, self.img_range = int(window_size), attn_type, 3, 1.0
-        self.cfg = dict(dim=dim, pdim=pdim, kernel_size=kernel_size, n_blocks=n_blocks, conv_blocks=conv_blocks, window_size=window_size,
-                        num_heads=num_heads, upscaling_factor=int(upscaling_factor), exp_ratio=exp_ratio, use_ln=bool(use_ln), converted=False)
-        self.compute_dtype = compute_dtype
-        self._init_runtime(bool(use_graph))
+class _ESCNet(HAT):
+    """What the networks of the ESC family share above their module trees: a `HAT` from the engine up — `compute_dtype` /
+    `set_compute_dtype`, `use_graph` and the weight-change tracking are HAT's own — with the float forward as the only path, and the
+    `to_img` scale conversion of `load_state_dict`.  A subclass builds its tree, sets `cfg`, and names its engine in `_make_engine`."""
 
     def extra_repr(self) -> str:
         return ", ".join(f"{k}={v}" for k, v in self.cfg.items())
 
     def _anchor(self) -> torch.Tensor:
         return self.proj.weight
-
-    @torch.no_grad()
-    def convert(self):
-        """Bake the geometric re-parameterisation into `plk_filter` (esc_arch.py:337-340); the forward then uses it as it is."""
-        if not self.cfg["converted"]:
-            self.plk_filter = nn.Parameter(esc_geo_ensemble(self.plk_filter.detach()))
-            self.cfg["converted"] = True
-            self._plist = None
-            self.mark_weights_changed()
-        return self
 
     @torch.no_grad()
     def load_state_dict(self, state_dict, strict=True, assign=False):
@@ -137,7 +104,7 @@ class ESC(HAT):
         device = torch.device(device) if device is not None else self._anchor().device
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
-        key = self._weights_key(device) + (self.cfg["converted"],)
+        key = self._weights_key(device) + (self.cfg.get("converted", False),)
         if self._engine is None or self._engine_key != key:
             if self._anchor().device != device:
                 raise RuntimeError(f"input is on {device} but the parameters are on {self._anchor().device}: "
@@ -145,10 +112,6 @@ class ESC(HAT):
             self._engine = self._make_engine(device)
             self._engine_key = key
         return self._engine
-
-    def _make_engine(self, device):
-        from ..esc_engine import ESCEngine
-        return ESCEngine(self.cfg, self.state_dict(), device, self.compute_dtype)
 
     def forward(self, x):
         if self.training:
@@ -179,3 +142,46 @@ class ESC(HAT):
 
     def forward_band_parallel(self, x, group=None):
         raise NotImplementedError(_NOT_BUILT.format("row-band sharding"))
+
+
+@ARCH_REGISTRY.register()
+class ESC(_ESCNet):
+    """The ESC network on the MI355X.  It is a `HAT` from the engine up — `compute_dtype` / `set_compute_dtype`, `use_graph` and the
+    weight-change tracking are HAT's own — over a module tree and an engine of its own.
+
+    Built: dim 64, pdim 16, kernel_size 13, window_size 32, num_heads 4, exp_ratio 1.25 or 2, any n_blocks / conv_blocks,
+    use_ln either way (ESC, ESC-light, ESCReal's body); anything else is a ValueError when the engine packs.  One frame per
+    forward, as in the reference's eval path.  Extra (non-reference) keywords: `compute_dtype` ('bf16' | 'fp32') and `use_graph`."""
+
+    def __init__(self, dim: int, pdim: int, kernel_size: int, n_blocks: int, conv_blocks: int, window_size: int, num_heads: int,
+                 upscaling_factor: int, exp_ratio: int = 2, attn_type: str = 'Flex', use_ln: bool = False, compute_dtype: str = "bf16",
+                 use_graph: bool = False):
+        nn.Module.__init__(self)   # (HAT's own constructor builds HAT's tree: this class has another)
+        if attn_type not in ('Naive', 'SDPA', 'Flex'):
+            raise NotImplementedError(f'Attention type {attn_type} is not supported.')
+        self.plk_filter = nn.Parameter(torch.randn(pdim, pdim, kernel_size, kernel_size))
+        torch.nn.init.orthogonal_(self.plk_filter)
+        self.proj = nn.Conv2d(3, dim, 3, 1, 1)
+        self.blocks = nn.ModuleList([_Block(dim, pdim, conv_blocks, window_size, num_heads, exp_ratio, use_ln) for _ in range(n_blocks)])
+        self.last = nn.Conv2d(dim, dim, 3, 1, 1)
+        self.to_img = nn.Conv2d(dim, 3 * upscaling_factor ** 2, 3, 1, 1)
+        self.upscaling_factor = self.upscale = int(upscaling_factor)
+        self.window_size, self.attn_type, self.in_chans, self.img_range = int(window_size), attn_type, 3, 1.0
+        self.cfg = dict(dim=dim, pdim=pdim, kernel_size=kernel_size, n_blocks=n_blocks, conv_blocks=conv_blocks, window_size=window_size,
+                        num_heads=num_heads, upscaling_factor=int(upscaling_factor), exp_ratio=exp_ratio, use_ln=bool(use_ln), converted=False)
+        self.compute_dtype = compute_dtype
+        self._init_runtime(bool(use_graph))
+
+    @torch.no_grad()
+    def convert(self):
+        """Bake the geometric re-parameterisation into `plk_filter` (esc_arch.py:337-340); the forward then uses it as it is."""
+        if not self.cfg["converted"]:
+            self.plk_filter = nn.Parameter(esc_geo_ensemble(self.plk_filter.detach()))
+            self.cfg["converted"] = True
+            self._plist = None
+            self.mark_weights_changed()
+        return self
+
+    def _make_engine(self, device):
+        from ..esc_engine import ESCEngine
+        return ESCEngine(self.cfg, self.state_dict(), device, self.compute_dtype)

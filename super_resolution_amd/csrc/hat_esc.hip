@@ -8,183 +8,12 @@
 //                             with the reflect pad) and their outputs are dropped
 //   hat_esc_layernorm         LayerNorm over 64 channels with eps as an argument (esc_arch.py:68-86: 1e-6)
 //   hat_esc_shuffle_add       pixel_shuffle(to_img rows + repeat_interleave(x, s*s)) (esc_arch.py:384-385) -> fp32 planes
+// The ConvFFN and LayerNorm kernels are templates on the channel count in hat_esc_ffn.h (hat_escfp.hip instantiates them at 48);
+// their 64-channel entry points are here.
 // Contracts: include/hat_mi355x.h "ESC".  DESIGN.md 4.14.
-#include "hat_common.h"
+#include "hat_esc_ffn.h"   // the ConvFFN and LayerNorm kernels, shared with hat_escfp.hip
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------
-// ConvFFN
-// ---------------------------------------------------------------------------------------------
-constexpr int ECF_C = 64;
-constexpr int ECF_TH = 8, ECF_TW = 12;                   // own pixels of a tile
-constexpr int ECF_HH = ECF_TH + 2, ECF_HW = ECF_TW + 2;  // with the depthwise conv's halo
-constexpr int ECF_HPX = ECF_HH * ECF_HW;                 // 140 halo pixels ...
-constexpr int ECF_PT = (ECF_HPX + 15) / 16;              // ... in 9 MFMA pixel tiles
-constexpr int ECF_NPX = ECF_PT * 16;                     // 144 rows of the halo images (rows >= 140 hold zeros)
-constexpr int ECF_OPX = ECF_TH * ECF_TW;                 // 96 own pixels = 6 MFMA pixel tiles
-constexpr int ECF_OPT = ECF_OPX / 16;
-constexpr int ECF_THREADS = 256;
-constexpr int ECF_POOL = 16;                             // channels of a pool partial slot
-
-template <typename T, int HIDP> struct EcfLds {
-    static constexpr int LDX = lds_row_elems(ECF_C, sizeof(T));   // x rows, MFMA operand (T)
-    static constexpr int LDU = HIDP + 4;                          // h rows (fp32)
-    static constexpr int LDH = lds_row_elems(HIDP, sizeof(T));    // h2 rows, MFMA operand (T)
-    static constexpr size_t US = (size_t)ECF_NPX * LDU * sizeof(float);
-    static constexpr size_t XS = (size_t)ECF_NPX * LDX * sizeof(T);
-    static constexpr size_t HS = (size_t)ECF_OPX * LDH * sizeof(T);
-    static constexpr size_t BYTES = US + (XS > HS ? XS : HS);     // the h2 image takes the x image's place
-    static_assert(BYTES <= HAT_LDS_MAX, "tile does not fit in LDS");
-};
-
-// LDS: [ us: h = gelu(W1 x + b1), fp32 [144][LDU] | xs: x (after the LayerNorm) as T [144][LDX], later hs: h2 as T [96][LDH] ]
-template <typename T, int HIDP>
-__global__ __launch_bounds__(ECF_THREADS) void esc_convffn_kernel(const HatEscConvFfnDesc d, const int tiles_x) {
-    typedef EcfLds<T, HIDP> L;
-    typedef typename MT<T>::frag_t frag_t;
-    constexpr int C = ECF_C, KS1 = C / 32, KS2 = HIDP / 32, LDX = L::LDX, LDU = L::LDU, LDH = L::LDH;
-    extern __shared__ __attribute__((aligned(16))) unsigned char ecf_smem[];
-    float* us = reinterpret_cast<float*>(ecf_smem);
-    T* xs = reinterpret_cast<T*>(ecf_smem + L::US);
-    T* hs = reinterpret_cast<T*>(ecf_smem + L::US);
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
-    const int tile = blockIdx.x, b = blockIdx.y;
-    const int ty0 = (tile / tiles_x) * ECF_TH, tx0 = (tile % tiles_x) * ECF_TW;
-    const int H = d.H, W = d.W;
-    const int64_t pix0 = (int64_t)b * H * W;
-
-    // halo pixel p -> its pixel index in the sample's map, or -1 outside the image (and for the pad rows p >= 140)
-    auto pixel = [&](int p) -> int64_t {
-        const int yy = ty0 - 1 + p / ECF_HW, xx = tx0 - 1 + p % ECF_HW;
-        return (p < ECF_HPX && yy >= 0 && yy < H && xx >= 0 && xx < W) ? pix0 + (int64_t)yy * W + xx : -1;
-    };
-
-    // ---- x rows, 16 lanes (one DPP row) per pixel; the LayerNorm over the 64 channels is two row sums
-    {
-        const int v = tid & 15;
-        f32x4 gam = {1.f, 1.f, 1.f, 1.f}, bet = {0.f, 0.f, 0.f, 0.f};
-        if (d.ln_g) {
-            gam = *reinterpret_cast<const f32x4*>(d.ln_g + 4 * v);
-            bet = *reinterpret_cast<const f32x4*>(d.ln_b + 4 * v);
-        }
-        for (int p = tid >> 4; p < ECF_NPX; p += ECF_THREADS / 16) {   // 144 = 9 x 16: every lane runs every trip
-            const int64_t px = pixel(p);
-            f32x4 r = {0.f, 0.f, 0.f, 0.f};
-            if (px >= 0) r = *reinterpret_cast<const f32x4*>(d.x + px * d.ldx + 4 * v);
-            if (d.ln_g) {
-                const float mean = row_sum16((r[0] + r[1]) + (r[2] + r[3])) * (1.0f / C);
-                const f32x4 c = r - mean;
-                const float var = row_sum16((c[0] * c[0] + c[1] * c[1]) + (c[2] * c[2] + c[3] * c[3])) * (1.0f / C);
-                r = c * (1.0f / sqrtf(var + d.ln_eps)) * gam + bet;
-            }
-            Vec4<T>::store(xs + p * LDX + 4 * v, r);
-        }
-    }
-    __syncthreads();
-
-    // ---- h = gelu(W1 . x + b1) on the MFMA units; h = 0 where the pixel lies outside the image: the depthwise conv pads h
-    {
-        constexpr int OT1 = HIDP / 16;
-        const T* w1 = reinterpret_cast<const T*>(d.w1);
-        for (int ot = wave; ot < OT1; ot += 4) {
-            frag_t a[KS1];
-#pragma unroll
-            for (int ks = 0; ks < KS1; ++ks) a[ks] = MT<T>::load(w1 + ((ot * KS1 + ks) * 64 + lane) * 8);
-            const int ch = 16 * ot + 4 * g;
-            const f32x4 b1 = *reinterpret_cast<const f32x4*>(d.b1 + ch);
-            for (int pt = 0; pt < ECF_PT; ++pt) {
-                const int p = 16 * pt + l15;
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int ks = 0; ks < KS1; ++ks) acc = MT<T>::mma(a[ks], MT<T>::load(xs + p * LDX + 32 * ks + 8 * g), acc);
-                f32x4 hv = {0.f, 0.f, 0.f, 0.f};
-                if (pixel(p) >= 0) {
-                    acc += b1;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) hv[r] = gelu_act<T>(acc[r]);
-                }
-                *reinterpret_cast<f32x4*>(us + p * LDU + ch) = hv;
-            }
-        }
-    }
-    __syncthreads();   // us is complete; nobody reads xs any more
-
-    // ---- h2 = gelu(dw3x3(h) + bias) + h for the own pixels; a thread keeps one group of 4 hidden channels for all its pixels
-    {
-        constexpr int CG = HIDP / 4, ROWS = ECF_THREADS / CG, ACTIVE = ROWS * CG;
-        if (tid < ACTIVE) {
-            const int c0 = 4 * (tid % CG);
-            f32x4 wt[9];
-#pragma unroll
-            for (int t = 0; t < 9; ++t) wt[t] = *reinterpret_cast<const f32x4*>(d.dww + t * HIDP + c0);
-            const f32x4 bd = *reinterpret_cast<const f32x4*>(d.dwb + c0);
-            for (int pxi = tid / CG; pxi < ECF_OPX; pxi += ROWS) {
-                const int oy = pxi / ECF_TW, ox = pxi % ECF_TW;
-                f32x4 v = bd;
-#pragma unroll
-                for (int t = 0; t < 9; ++t) v += wt[t] * *reinterpret_cast<const f32x4*>(us + ((oy + t / 3) * ECF_HW + ox + t % 3) * LDU + c0);
-                const f32x4 h = *reinterpret_cast<const f32x4*>(us + ((oy + 1) * ECF_HW + ox + 1) * LDU + c0);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = gelu_act<T>(v[r]) + h[r];
-                Vec4<T>::store(hs + pxi * LDH + c0, v);
-            }
-        }
-    }
-    __syncthreads();
-
-    // ---- out = W2 . h2 + b2 [+ r]; wave w owns output channels 16 w .. 16 w + 15 of every own pixel
-    {
-        const int ot = wave;
-        const T* w2 = reinterpret_cast<const T*>(d.w2);
-        frag_t a[KS2];
-#pragma unroll
-        for (int ks = 0; ks < KS2; ++ks) a[ks] = MT<T>::load(w2 + ((ot * KS2 + ks) * 64 + lane) * 8);
-        const int ch = 16 * ot + 4 * g;
-        const f32x4 b2 = *reinterpret_cast<const f32x4*>(d.b2 + ch);
-        f32x4 psum = {0.f, 0.f, 0.f, 0.f};
-        for (int pt = 0; pt < ECF_OPT; ++pt) {
-            const int p = 16 * pt + l15;
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KS2; ++ks) acc = MT<T>::mma(a[ks], MT<T>::load(hs + p * LDH + 32 * ks + 8 * g), acc);
-            const int yy = ty0 + p / ECF_TW, xx = tx0 + p % ECF_TW;
-            if (yy < H && xx < W) {
-                const int64_t px = pix0 + (int64_t)yy * W + xx;
-                f32x4 v = acc + b2;
-                if (d.r) v += *reinterpret_cast<const f32x4*>(d.r + px * d.ldr + ch);
-                if (d.out_f32) {
-                    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(d.out) + px * d.ldo + ch) = v;
-                    psum += v;
-                } else {
-                    Vec4<T>::store(reinterpret_cast<T*>(d.out) + px * d.ldo + ch, v);
-                    psum += as_stored<T>(v);
-                }
-            }
-        }
-        // the pool's share of this tile: the stored values of channels 0..15, summed in a fixed order, one slot per tile
-        if (d.partials && ot == 0) {   // (wave-uniform: all 64 lanes take part in the row sums)
-            f32x4 s;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s[r] = row_sum16(psum[r]);
-            if (l15 == 0) *reinterpret_cast<f32x4*>(d.partials + ((int64_t)b * gridDim.x + tile) * ECF_POOL + ch) = s;
-        }
-    }
-}
-
-template <typename T, int HIDP>
-int esc_convffn_launch(const HatEscConvFfnDesc& d, hipStream_t s) {
-    constexpr size_t lds = EcfLds<T, HIDP>::BYTES;
-    auto kern = esc_convffn_kernel<T, HIDP>;
-    if (lds > 65536) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    const int tiles_x = (d.W + ECF_TW - 1) / ECF_TW, tiles_y = (d.H + ECF_TH - 1) / ECF_TH;
-    HAT_LAUNCH(kern, dim3(tiles_x * tiles_y, d.B), dim3(ECF_THREADS), lds, s, d, tiles_x);
-    return hat_check_launch();
-}
 
 // ---------------------------------------------------------------------------------------------
 // 32 x 32 window attention with reflected edges
@@ -299,27 +128,8 @@ int window_attention_r_launch(const WarArgs& a, int B, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// LayerNorm over 64 channels, eps as an argument; the pixel-shuffle + base-image epilogue
+// The pixel-shuffle + base-image epilogue (the LayerNorm over 64 channels is hat_esc_ffn.h's)
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void esc_layernorm_kernel(const float* __restrict__ x, T* __restrict__ y, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, float eps, int64_t npix, int ldx, int ldy) {
-    constexpr int C = ECF_C;
-    const int v = threadIdx.x & 15;
-    const f32x4 gam = *reinterpret_cast<const f32x4*>(gamma + 4 * v), bet = *reinterpret_cast<const f32x4*>(beta + 4 * v);
-    const int64_t trips = (npix + 15) / 16;   // 16 pixels per trip of a 256-thread group; every lane runs every trip of its group
-    for (int64_t t = (int64_t)blockIdx.x; t < trips; t += gridDim.x) {
-        const int64_t px = 16 * t + (threadIdx.x >> 4);
-        f32x4 r = {0.f, 0.f, 0.f, 0.f};
-        if (px < npix) r = *reinterpret_cast<const f32x4*>(x + px * ldx + 4 * v);
-        const float mean = row_sum16((r[0] + r[1]) + (r[2] + r[3])) * (1.0f / C);
-        const f32x4 c = r - mean;
-        const float var = row_sum16((c[0] * c[0] + c[1] * c[1]) + (c[2] * c[2] + c[3] * c[3])) * (1.0f / C);
-        r = c * (1.0f / sqrtf(var + eps)) * gam + bet;
-        if (px < npix) Vec4<T>::store(y + px * ldy + 4 * v, r);
-    }
-}
-
 __global__ __launch_bounds__(256) void esc_shuffle_add_kernel(const float* __restrict__ rows, const float* __restrict__ x, float* __restrict__ y,
                                                               int H, int W, int s, int ld, int64_t total) {
     const int Hs = H * s, Ws = W * s;
@@ -332,7 +142,7 @@ __global__ __launch_bounds__(256) void esc_shuffle_add_kernel(const float* __res
     }
 }
 
-bool aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+constexpr int ECF_C = 64;
 
 }  // namespace
 
@@ -347,19 +157,10 @@ extern "C" int hat_esc_convffn(const HatEscConvFfnDesc* dp, void* stream) {
     if (d.dtype != HAT_F32 && d.dtype != HAT_BF16) return HAT_EINVAL;
     if (d.B < 1 || d.B > 65535 || d.H < 1 || d.W < 1 || d.reserved0) return HAT_EINVAL;
     if (d.hid_p != 96 && d.hid_p != 128) return HAT_EUNSUPPORTED;
-    if (!d.x || !d.w1 || !d.b1 || !d.dww || !d.dwb || !d.w2 || !d.b2 || !d.out || d.out == d.x) return HAT_EINVAL;
-    if (!aligned(d.x, 16) || !aligned(d.w1, 16) || !aligned(d.b1, 16) || !aligned(d.dww, 16) || !aligned(d.dwb, 16) || !aligned(d.w2, 16)
-        || !aligned(d.b2, 16) || !aligned(d.out, 16)) return HAT_EINVAL;
-    if (d.ldx < ECF_C || d.ldx % 4) return HAT_EINVAL;
-    const int ovec = (d.dtype == HAT_BF16 && !d.out_f32) ? 8 : 4;
-    if (d.ldo < ECF_C || d.ldo % ovec) return HAT_EINVAL;
-    if ((d.ln_g == nullptr) != (d.ln_b == nullptr)) return HAT_EINVAL;
-    if (d.ln_g && (!aligned(d.ln_g, 16) || !aligned(d.ln_b, 16) || !(d.ln_eps > 0.f))) return HAT_EINVAL;
-    if (d.r && (!aligned(d.r, 16) || d.ldr < ECF_C || d.ldr % 4)) return HAT_EINVAL;
-    if (d.partials && !aligned(d.partials, 16)) return HAT_EINVAL;
+    if (const int e = esc_convffn_check(d, ECF_C)) return e;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (d.dtype == HAT_BF16) return d.hid_p == 96 ? esc_convffn_launch<bf16_t, 96>(d, s) : esc_convffn_launch<bf16_t, 128>(d, s);
-    return d.hid_p == 96 ? esc_convffn_launch<float, 96>(d, s) : esc_convffn_launch<float, 128>(d, s);
+    if (d.dtype == HAT_BF16) return d.hid_p == 96 ? esc_convffn_launch<bf16_t, ECF_C, 96>(d, s) : esc_convffn_launch<bf16_t, ECF_C, 128>(d, s);
+    return d.hid_p == 96 ? esc_convffn_launch<float, ECF_C, 96>(d, s) : esc_convffn_launch<float, ECF_C, 128>(d, s);
 }
 
 extern "C" int hat_window_attention_r(const void* q, const void* kv, const float* bias, void* out, int32_t B, int32_t h, int32_t w,
@@ -370,7 +171,7 @@ extern "C" int hat_window_attention_r(const void* q, const void* kv, const float
     if (ws != WAR_WS || heads < 1 || C != heads * WAR_D) return HAT_EUNSUPPORTED;
     const int vec = dtype == HAT_BF16 ? 8 : 4;
     if (ldq < C || ldq % vec || ldkv < 2 * C || ldkv % vec || ldo < C || ldo % vec) return HAT_EINVAL;
-    if (!aligned(q, 16) || !aligned(kv, 16) || !aligned(out, 16) || !aligned(bias, 4)) return HAT_EINVAL;
+    if (!esc_aligned(q, 16) || !esc_aligned(kv, 16) || !esc_aligned(out, 16) || !esc_aligned(bias, 4)) return HAT_EINVAL;
     const int Hp = (h + WAR_WS - 1) / WAR_WS * WAR_WS, Wp = (w + WAR_WS - 1) / WAR_WS * WAR_WS;
     if (Hp - h > h - 1 || Wp - w > w - 1) return HAT_EINVAL;   // a reflection reaches at most the first row / column
     WarArgs a{q, kv, bias, out, h, w, C, heads, Wp / WAR_WS, ldq, ldkv, ldo};
@@ -380,18 +181,7 @@ extern "C" int hat_window_attention_r(const void* q, const void* kv, const float
 
 extern "C" int hat_esc_layernorm(const float* x, void* y, const float* gamma, const float* beta, float eps, int64_t npix, int32_t ldx,
                                  int32_t ldy, int32_t dtype, void* stream) {
-    if (!x || !y || !gamma || !beta || npix < 1 || !(eps > 0.f)) return HAT_EINVAL;
-    if (dtype != HAT_F32 && dtype != HAT_BF16) return HAT_EINVAL;
-    if (ldx < ECF_C || ldx % 4 || ldy < ECF_C || ldy % 4) return HAT_EINVAL;
-    if (!aligned(x, 16) || !aligned(y, 8) || !aligned(gamma, 16) || !aligned(beta, 16)) return HAT_EINVAL;
-    const int64_t trips = (npix + 15) / 16;
-    const int grid = (int)(trips < 4096 ? trips : 4096);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == HAT_BF16)
-        HAT_LAUNCH(esc_layernorm_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, x, reinterpret_cast<bf16_t*>(y), gamma, beta, eps, npix, ldx, ldy);
-    else
-        HAT_LAUNCH(esc_layernorm_kernel<float>, dim3(grid), dim3(256), 0, s, x, reinterpret_cast<float*>(y), gamma, beta, eps, npix, ldx, ldy);
-    return hat_check_launch();
+    return esc_layernorm_run<ECF_C>(x, y, gamma, beta, eps, npix, ldx, ldy, dtype, stream);
 }
 
 extern "C" int hat_esc_shuffle_add(const float* rows, const float* x, float* y, int32_t B, int32_t H, int32_t W, int32_t s, int32_t ld,

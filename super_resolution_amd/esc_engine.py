@@ -4,6 +4,8 @@ input shape, no torch op on the hot path.  DESIGN.md §4.14 has the launch list.
 The residual stream is fp32 rows (B, H*W, 64); what a 1x1 / 3x3 / 13x13 conv reads is T rows (T = the compute dtype).  Per Block:
     hat_esc_convffn (LN + ConvFFN)  ->  hat_esc_layernorm, to_qkv, hat_window_attention_r, to_out (+ x)
     conv_blocks x [ hat_esc_convffn (+ pool partials), hat_esc_weights, 13x13 conv, aggr (+ x) ]  ->  hat_esc_layernorm, conv_out (+ skip)
+`ESCRealEngine` (§4.15) and `ESCFPEngine` (§4.16: 48 channels, its own ConvFFN / LayerNorm instantiations and weights launch) reuse
+the loop through the hooks of `ESCEngine`.
 """
 from __future__ import annotations
 
@@ -28,30 +30,34 @@ class _Block:
 
 
 class ESCEngine:
-    def __init__(self, cfg: dict, sd: dict, device, compute_dtype: str = "bf16"):
+    # what a width of the family swaps: the two kernels that are instantiated per channel count, and their packer
+    _convffn, _layernorm, _pack_ffn = staticmethod(ops.esc_convffn), staticmethod(ops.esc_layernorm), staticmethod(ops.pack_esc_convffn)
+
+    def _check_cfg(self, cfg):
         for k, v in SUPPORTED.items():
             if int(cfg[k]) != v:
                 raise ValueError(f"ESC with {k}={cfg[k]} is not supported: the device path is built for "
                                  + ", ".join(f"{a}={b}" for a, b in SUPPORTED.items()) + " (ESC, ESC-light, ESCReal's body)")
         if int(cfg["dim"] * cfg["exp_ratio"]) not in ops.ESC_HID_PAD:
             raise ValueError(f"ESC with exp_ratio={cfg['exp_ratio']} is not supported: hat_esc_convffn is built for exp_ratio 1.25 and 2")
+
+    def __init__(self, cfg: dict, sd: dict, device, compute_dtype: str = "bf16"):
+        self._check_cfg(cfg)
         if compute_dtype not in ops.DTYPE_CODE:
             raise ValueError(f"compute_dtype {compute_dtype!r}: expected 'bf16' or 'fp32'")
         self.cfg, self.dev = dict(cfg), torch.device(device)
         self.dtype = dt = ops.DTYPE_CODE[compute_dtype]
         self.tdt = ops.TORCH_DTYPE[dt]
-        self.C, self.scale, self.heads, self.ws = 64, int(cfg["upscaling_factor"]), int(cfg["num_heads"]), int(cfg["window_size"])
+        self.C, self.scale, self.heads, self.ws = int(cfg["dim"]), int(cfg["upscaling_factor"]), int(cfg["num_heads"]), int(cfg["window_size"])
         dev, C = self.dev, self.C
         vec = lambda k: sd[k].detach().to(dtype=torch.float32, device=dev).contiguous()
-        # the geometric re-parameterisation of the one large-kernel filter, once, unless convert() has baked it in already
-        plk = sd["plk_filter"].detach().to(torch.float32).cpu()
-        sd = dict(sd, _plk=plk if cfg.get("converted", False) else ops.esc_geo_ensemble(plk))
+        sd = self._shared_filter(sd)
         self.proj = ops.pack_conv_weight(sd["proj.weight"], sd["proj.bias"], dt, dev)
         self.blocks = []
         for i in range(int(cfg["n_blocks"])):
             p, b = f"blocks.{i}", _Block()
             b.ln_proj = (vec(p + ".ln_proj.weight"), vec(p + ".ln_proj.bias"))
-            b.proj = ops.pack_esc_convffn(sd, p + ".proj", dt, dev)
+            b.proj = self._pack_ffn(sd, p + ".proj", dt, dev)
             b.ln_attn = (vec(p + ".ln_attn.weight"), vec(p + ".ln_attn.bias"))
             # head_dim^-0.5 = 1/4 folded into the q rows of to_qkv: a power of two, so exact
             qs = torch.cat([torch.full((C,), (C // self.heads) ** -0.5), torch.ones(2 * C)])
@@ -63,10 +69,10 @@ class ESCEngine:
             b.convs = []
             for j in range(int(cfg["conv_blocks"])):
                 ln = (vec(f"{p}.lns.{j}.weight"), vec(f"{p}.lns.{j}.bias")) if cfg.get("use_ln", False) else None
-                esc = _ESC(sd, f"{p}.pconvs.{j}", "_plk", 16, 13, C, dt, dev)
-                esc.aggr = ops.pack_pointwise(sd[esc.aggr_keys[0]].detach().reshape(C, C), sd[esc.aggr_keys[1]], dt, dev)
+                esc = self._pack_lk(sd, f"{p}.pconvs.{j}")
+                esc.aggr = ops.pack_pointwise(sd[f"{p}.pconvs.{j}.aggr.weight"].detach().reshape(C, C), sd[f"{p}.pconvs.{j}.aggr.bias"], dt, dev)
                 esc.conv13 = ops.esc_conv13_supported(16, 13, dt)
-                b.convs.append((ln, ops.pack_esc_convffn(sd, f"{p}.convffns.{j}", dt, dev), esc))
+                b.convs.append((ln, self._pack_ffn(sd, f"{p}.convffns.{j}", dt, dev), esc))
             b.ln_out = (vec(p + ".ln_out.weight"), vec(p + ".ln_out.bias"))
             b.conv_out = ops.pack_conv_weight(sd[p + ".conv_out.weight"], sd[p + ".conv_out.bias"], dt, dev)
             self.blocks.append(b)
@@ -74,6 +80,24 @@ class ESCEngine:
         self._pack_head(sd)
         self._kpad = self.blocks[0].convs[0][2].kpad if self.blocks and self.blocks[0].convs else 0
         self._ws_cache = collections.OrderedDict()
+
+    def _shared_filter(self, sd):
+        """The geometric re-parameterisation of the one large-kernel filter, once, unless convert() has baked it in already."""
+        plk = sd["plk_filter"].detach().to(torch.float32).cpu()
+        return dict(sd, _plk=plk if self.cfg.get("converted", False) else ops.esc_geo_ensemble(plk))
+
+    def _pack_lk(self, sd, core: str):
+        return _ESC(sd, core, "_plk", 16, 13, self.C, self.dtype, self.dev)
+
+    def _lk_weights(self, esc, w, tiles: int, N: int, B: int):
+        """The per-sample weight image of the 13x13 conv, from the pool partials the ConvFFN left."""
+        ops.esc_weights(w["gap"], tiles, N, esc.w1, esc.b1, esc.w2, esc.b2, esc.plk, w["weff"], B=B, pdim=16, ksize=13, kpad=esc.kpad,
+                        dtype=self.dtype)
+
+    def _check_batch(self, B: int):
+        if B != 1:
+            raise RuntimeError("ESC's eval path takes one frame at a time (esc_arch.py:121: the dynamic kernel of a batch cannot be "
+                               f"reshaped to (pdim,1,3,3)), got a batch of {B}")
 
     def _pack_head(self, sd):
         self.to_img = ops.pack_conv_weight(sd["to_img.weight"], sd["to_img.bias"], self.dtype, self.dev)
@@ -108,14 +132,12 @@ class ESCEngine:
             ops.conv(pw, x, out, **geo, dtype=self.dtype, ldx=ldx, ldo=ldo, out_mode=out_mode, **kw)
 
     def forward(self, x: torch.Tensor, taps: dict = None) -> torch.Tensor:
-        """x (1, 3, h, w) fp32 -> (1, 3, s h, s w) fp32 (the workspace's output buffer: copy it before the next forward of the shape).
+        """x (B, 3, h, w) fp32 (B = 1 unless the network takes batches) -> (B, 3, s h, s w) fp32 (the workspace's output buffer: copy it before the next forward of the shape).
         taps: a dict that receives clones of the stream after the first ConvFFN, the attention and the first conv block."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError(f"ESC expects (B,3,h,w) input, got {tuple(x.shape)}")
         B, _, H, W = x.shape
-        if B != 1:
-            raise RuntimeError("ESC's eval path takes one frame at a time (esc_arch.py:121: the dynamic kernel of a batch cannot be "
-                               f"reshaped to (pdim,1,3,3)), got a batch of {B}")
+        self._check_batch(B)
         ws = self.ws
         if (-H) % ws > H - 1 or (-W) % ws > W - 1:
             raise RuntimeError(f"a {H}x{W} frame cannot be reflect-padded to a multiple of window_size {ws}: the padding must be smaller than the frame")
@@ -128,10 +150,10 @@ class ESCEngine:
         cur = w["feat0"]
         for bi, b in enumerate(self.blocks):
             xa, xb = [s for s in w["s"] if s is not cur][:2]
-            ops.esc_convffn(b.proj, cur, xa, **geo, dtype=dt, ln=b.ln_proj, eps=LN_EPS)
+            self._convffn(b.proj, cur, xa, **geo, dtype=dt, ln=b.ln_proj, eps=LN_EPS, ldx=C, ldo=C)
             if taps is not None and bi == 0:
                 taps["ffn0"] = xa.clone()
-            ops.esc_layernorm(xa, w["n"], *b.ln_attn, npix=B * N, dtype=dt, eps=LN_EPS)
+            self._layernorm(xa, w["n"], *b.ln_attn, npix=B * N, dtype=dt, eps=LN_EPS, ldx=C, ldy=C)
             self._lin(b.to_qkv, w["n"], w["qkv"], geo=geo, ldx=C, ldo=3 * C)
             ops.window_attention_r(w["qkv"], w["qkv"].view(-1)[C:], b.rpb, w["att"], B=B, h=H, w=W, C_=C, heads=self.heads, ws=ws,
                                    ldq=3 * C, ldkv=3 * C, ldo=C, dtype=dt)
@@ -140,9 +162,8 @@ class ESCEngine:
             if taps is not None and bi == 0:
                 taps["attn0"] = xa.clone()
             for ci, (ln, ffn, esc) in enumerate(b.convs):
-                ops.esc_convffn(ffn, xa, w["z"], **geo, dtype=dt, ln=ln, eps=LN_EPS, partials=w["gap"])
-                ops.esc_weights(w["gap"], tiles, N, esc.w1, esc.b1, esc.w2, esc.b2, esc.plk, w["weff"], B=B, pdim=16, ksize=13,
-                                kpad=esc.kpad, dtype=dt)
+                self._convffn(ffn, xa, w["z"], **geo, dtype=dt, ln=ln, eps=LN_EPS, partials=w["gap"], ldx=C, ldo=C)
+                self._lk_weights(esc, w, tiles, N, B)
                 if esc.conv13:
                     ops.esc_conv13(w["z"], w["weff"], w["y16"], **geo, ldx=C, kpad=esc.kpad, dtype=dt)
                 else:
@@ -152,7 +173,7 @@ class ESCEngine:
                 xa, xb = xb, xa
                 if taps is not None and bi == 0 and ci == 0:
                     taps["conv0"] = xa.clone()
-            ops.esc_layernorm(xa, w["n"], *b.ln_out, npix=B * N, dtype=dt, eps=LN_EPS)
+            self._layernorm(xa, w["n"], *b.ln_out, npix=B * N, dtype=dt, eps=LN_EPS, ldx=C, ldy=C)
             ops.conv(b.conv_out, w["n"], xb, **geo, dtype=dt, ldx=C, ldo=C, out_mode=O_NHWC_F32, r1=cur, ldr1=C)
             cur = xb
         return self._tail(x, w, cur, geo)
@@ -236,4 +257,57 @@ class ESCRealEngine(ESCEngine):
                                   dtype=dt)
         else:
             ops.conv(self.out, w["u3"], w["y"], B=B, H=4 * H, W=4 * W, dtype=dt, ldx=C, ldo=0, out_mode=O_NCHW_F32)
+        return w["y"]
+
+
+FP_SUPPORTED = dict(dim=48, pdim=16, kernel_size=13, window_size=32, num_heads=3)
+
+
+class ESCFPEngine(ESCEngine):
+    """ESCFP (esc_fp_arch.py:277-355): ESC's Block loop at 48 channels and 3 heads, with a LayerNorm in front of every conv block,
+    hat_escfp_weights in place of hat_esc_weights (the decomposed large-kernel branch folded to the dense rank-1 filter the 13x13
+    conv kernels read), then
+        hat_escfp_layernorm (ln_last)  ->  last (+ feat0)  ->  to_img  ->  hat_escfp_shuffle_bicubic
+    Batches are taken: workspace, pool partials and weight images are per sample.  DESIGN.md §4.16."""
+
+    _convffn, _layernorm, _pack_ffn = staticmethod(ops.escfp_convffn), staticmethod(ops.escfp_layernorm), staticmethod(ops.pack_escfp_convffn)
+
+    def _check_cfg(self, cfg):
+        for k, v in FP_SUPPORTED.items():
+            if int(cfg[k]) != v:
+                raise ValueError(f"ESCFP with {k}={cfg[k]} is not supported: the device path is built for "
+                                 + ", ".join(f"{a}={b}" for a, b in FP_SUPPORTED.items()) + " (ESC_FP_X2 / X3 / X4)")
+        if int(cfg["dim"] * cfg["exp_ratio"]) not in ops.ESCFP_HID_PAD:
+            raise ValueError(f"ESCFP with exp_ratio={cfg['exp_ratio']} is not supported: hat_escfp_convffn is built for a hidden width of "
+                             + ", ".join(map(str, ops.ESCFP_HID_PAD)) + " (exp_ratio 1.25, 1.5, 2)")
+        if int(cfg["upscaling_factor"]) not in (2, 3, 4):
+            raise ValueError(f"ESCFP with upscaling_factor={cfg['upscaling_factor']} is not supported: hat_escfp_shuffle_bicubic is built for 2, 3 and 4")
+
+    def _shared_filter(self, sd):
+        return sd   # lk_channel / lk_spatial are used as they are: no geometric ensemble, no convert()
+
+    def _pack_lk(self, sd, core: str):
+        return ops.pack_escfp_lk(sd, core, self.dtype, self.dev)
+
+    def _lk_weights(self, esc, w, tiles, N, B):
+        ops.escfp_weights(w["gap"], tiles, N, esc, w["weff"], B=B, dtype=self.dtype)
+
+    def _check_batch(self, B):
+        pass
+
+    def _pack_head(self, sd):
+        super()._pack_head(sd)
+        vec = lambda k: sd[k].detach().to(dtype=torch.float32, device=self.dev).contiguous()
+        self.ln_last = (vec("ln_last.weight"), vec("ln_last.bias"))
+        self.ptab = ops.bicubic_phase_table(self.scale).to(self.dev)
+
+    def _tail(self, x, w, cur, geo):
+        """ln_last, last (+ feat0), to_img, the pixel shuffle plus the bicubic base image                   esc_fp_arch.py:352-354"""
+        C, dt = self.C, self.dtype
+        B, H, W = geo["B"], geo["H"], geo["W"]
+        self._layernorm(cur, w["z"], *self.ln_last, npix=B * H * W, dtype=dt, eps=LN_EPS, ldx=C, ldy=C)
+        ops.conv(self.last, w["z"], w["n"], **geo, dtype=dt, ldx=C, ldo=C, r1=w["feat0"], ldr1=C)
+        ld = w["rows"].shape[2]
+        ops.conv(self.to_img, w["n"], w["rows"], **geo, dtype=dt, ldx=C, ldo=ld, out_mode=O_NHWC_F32, n_store=ld)
+        ops.escfp_shuffle_bicubic(w["rows"], x, self.ptab, w["y"], B=B, H=H, W=W, s=self.scale, ld=ld)
         return w["y"]

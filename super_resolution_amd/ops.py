@@ -16,7 +16,8 @@ from ._lib import (ACT_GELU, ACT_LRELU, ACT_LRELU02, ACT_NONE, HAT_BF16, HAT_F32
                    HatNafHalfDesc, HatEscConvFfnDesc)
 # host-side weight packing lives in packing.py; ops.pack_* / ops.Packed* stay the names the engine, the tools and the tests use
 from .packing import (ESC_HID_PAD, FP16_SAFE, KC, NAF_WIDTHS, TORCH_DTYPE, PackedConv, PackedEscFfn, PackedFFN, PackedMlp, PackedNafBlock, choose_nt,  # noqa: F401
-                      esc_geo_ensemble, pack_esc_convffn, PackedEscRealSkip, dysample_fold, pack_escreal_skip, pack_nearest_conv,
+                      esc_geo_ensemble, pack_esc_convffn, PackedEscRealSkip, ESCFP_HID_PAD, PackedEscFpLk, bicubic_phase_table, escfp_rank1_fold,
+                      pack_escfp_convffn, pack_escfp_lk, dysample_fold, pack_escreal_skip, pack_nearest_conv,
                       choose_nt_linear, naf_ffn_fold, naf_frags, pack_naf_block,
                       ffn_fp16_range_bound, pack_cab_squeeze, pack_cab_w2f, pack_conv_weight, pack_ffn, pack_ffn2, pack_ffn3,
                       pack_linear_weight, pack_ocab_mlp, pack_ocab_qkv, pack_pointwise)
@@ -324,7 +325,7 @@ def esc_convffn(pf: PackedEscFfn, x, out, *, B: int, H: int, W: int, dtype: int,
     d.B, d.H, d.W, d.hid_p, d.ldx, d.ldr, d.ldo, d.dtype = B, H, W, pf.hid_p, ldx, ldr, ldo, dtype
     d.out_f32 = int(out.dtype == torch.float32)
     es, npx = (4 if d.out_f32 or dtype == HAT_F32 else 2), float(B * H * W)
-    _timed(f"esc_convffn_kernel<{_TNAME[dtype]}, {pf.hid_p}>", 2.0 * npx * pf.hid * (2 * 64 + 9),
+    _timed(f"esc_convffn_kernel<{_TNAME[dtype]}, 64, {pf.hid_p}>", 2.0 * npx * pf.hid * (2 * 64 + 9),
            lambda: _lib.check(lib.hat_esc_convffn(C.byref(d), _stream()), f"hat_esc_convffn(hid={pf.hid})"),
            tag=f"convffn 64->{pf.hid}->64 {H}x{W}{' ln' if ln is not None else ''}{' r' if r is not None else ''}{' pool' if partials is not None else ''}",
            nbytes=npx * 64 * (4 + es + (4 if r is not None else 0)))
@@ -342,7 +343,7 @@ def window_attention_r(q, kv, bias, out, *, B: int, h: int, w: int, C_: int, hea
 def esc_layernorm(x, y, gamma, beta, *, npix: int, dtype: int, eps: float = 1e-6, ldx: int = 64, ldy: int = 64):
     """y (T rows) = LayerNorm over 64 channels of x (fp32 rows) with `eps` (hat_esc_layernorm)."""
     lib = _lib.load()
-    _timed(f"esc_layernorm_kernel<{_TNAME[dtype]}>", 0.0, lambda: _lib.check(
+    _timed(f"esc_layernorm_kernel<{_TNAME[dtype]}, 64>", 0.0, lambda: _lib.check(
         lib.hat_esc_layernorm(_ptr(x), _ptr(y), _ptr(gamma), _ptr(beta), eps, npix, ldx, ldy, dtype, _stream()), "hat_esc_layernorm"),
         tag="ln64 eps")
 
@@ -373,6 +374,52 @@ def dysample(rows, init_pos, bias, y, *, B: int, H: int, W: int, s: int, ld: int
     _timed("dysample_kernel", 0.0, lambda: _lib.check(
         lib.hat_dysample(_ptr(rows), _ptr(init_pos), _ptr(bias), _ptr(y), B, H, W, s, ld, _stream()), "hat_dysample"),
         tag=f"dysample x{s} {H}x{W}", nbytes=4.0 * B * H * W * (ld + 3 * s * s))
+
+
+# ------------------------------------------------------------------------------------------------
+# ESCFP (hat_escfp_convffn / hat_escfp_layernorm / hat_escfp_weights / hat_escfp_shuffle_bicubic)
+# ------------------------------------------------------------------------------------------------
+def escfp_convffn(pf: PackedEscFfn, x, out, *, B: int, H: int, W: int, dtype: int, ln=None, eps: float = 1e-6, r=None, partials=None,
+                  ldx: int = 48, ldr: int = 48, ldo: int = 48):
+    """esc_convffn at 48 channels (hat_escfp_convffn); pf from pack_escfp_convffn."""
+    lib = _lib.load()
+    d = HatEscConvFfnDesc()
+    d.x, d.w1, d.b1, d.dww, d.dwb, d.w2, d.b2 = _ptr(x), _ptr(pf.w1), _ptr(pf.b1), _ptr(pf.dww), _ptr(pf.dwb), _ptr(pf.w2), _ptr(pf.b2)
+    if ln is not None:
+        d.ln_g, d.ln_b = _ptr(ln[0]), _ptr(ln[1])
+    d.ln_eps = eps
+    d.r, d.out, d.partials = _ptr(r), _ptr(out), _ptr(partials)
+    d.B, d.H, d.W, d.hid_p, d.ldx, d.ldr, d.ldo, d.dtype = B, H, W, pf.hid_p, ldx, ldr, ldo, dtype
+    d.out_f32 = int(out.dtype == torch.float32)
+    es, npx = (4 if d.out_f32 or dtype == HAT_F32 else 2), float(B * H * W)
+    _timed(f"esc_convffn_kernel<{_TNAME[dtype]}, 48, {pf.hid_p}>", 2.0 * npx * pf.hid * (2 * 48 + 9),
+           lambda: _lib.check(lib.hat_escfp_convffn(C.byref(d), _stream()), f"hat_escfp_convffn(hid={pf.hid})"),
+           tag=f"convffn 48->{pf.hid}->48 {H}x{W}{' ln' if ln is not None else ''}{' r' if r is not None else ''}{' pool' if partials is not None else ''}",
+           nbytes=npx * 48 * (4 + es + (4 if r is not None else 0)))
+
+
+def escfp_layernorm(x, y, gamma, beta, *, npix: int, dtype: int, eps: float = 1e-6, ldx: int = 48, ldy: int = 48):
+    """y (T rows) = LayerNorm over 48 channels of x (fp32 rows) with `eps` (hat_escfp_layernorm)."""
+    lib = _lib.load()
+    _timed(f"esc_layernorm_kernel<{_TNAME[dtype]}, 48>", 0.0, lambda: _lib.check(
+        lib.hat_escfp_layernorm(_ptr(x), _ptr(y), _ptr(gamma), _ptr(beta), eps, npix, ldx, ldy, dtype, _stream()), "hat_escfp_layernorm"),
+        tag="ln48 eps")
+
+
+def escfp_weights(partials, nblk: int, npix: int, lk: PackedEscFpLk, w_out, *, B: int, dtype: int):
+    """w_out (B,16,lk.kpad) T = the dense rank-1 weights of the decomposed large-kernel branch from the pool partials (hat_escfp_weights)."""
+    lib = _lib.load()
+    _timed("escfp_weights_kernel", 0.0, lambda: _lib.check(
+        lib.hat_escfp_weights(_ptr(partials), nblk, npix, _ptr(lk.w1), _ptr(lk.b1), _ptr(lk.w2), _ptr(lk.b2), _ptr(lk.lk_channel),
+                              _ptr(lk.lk_spatial), _ptr(w_out), B, lk.kpad, dtype, _stream()), "hat_escfp_weights"))
+
+
+def escfp_shuffle_bicubic(rows, x, ptab, y, *, B: int, H: int, W: int, s: int, ld: int):
+    """y (B,3,sH,sW) = pixel_shuffle(rows (B,H,W,ld) fp32) + bicubic x`s` of x (B,3,H,W); ptab = bicubic_phase_table(s) on the device."""
+    lib = _lib.load()
+    _timed("escfp_shuffle_bicubic_kernel", 0.0, lambda: _lib.check(
+        lib.hat_escfp_shuffle_bicubic(_ptr(rows), _ptr(x), _ptr(ptab), _ptr(y), B, H, W, s, ld, _stream()), "hat_escfp_shuffle_bicubic"),
+        tag=f"shuffle+bicubic x{s} {H}x{W}", nbytes=4.0 * B * H * W * (ld + 3 + 3 * s * s))
 
 
 LOG2E = 1.4426950408889634

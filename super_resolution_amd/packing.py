@@ -439,6 +439,76 @@ def pack_esc_convffn(sd, p: str, dtype: int, device) -> PackedEscFfn:
     return f
 
 
+ESCFP_HID_PAD = {60: 64, 72: 96, 96: 96}   # hidden widths hat_escfp_convffn is instantiated for (48 channels) -> padded
+
+
+def pack_escfp_convffn(sd, p: str, dtype: int, device) -> PackedEscFfn:
+    """One ConvFFN of ESCFP (esc_fp_arch.py:139-150) in hat_escfp_convffn's operand layouts (include/hat_mi355x.h "ESCFP"): as
+    pack_esc_convffn at 48 channels, with W1's 48 columns zero-padded to the two k-steps (64) the kernel runs: w1 [hid_p/16][2][64][8],
+    w2 [3][hid_p/32][64][8], b2 [48]."""
+    W1 = _f32(sd[p + ".proj.weight"])
+    hid, dim = W1.shape[0], W1.shape[1]
+    if dim != 48 or hid not in ESCFP_HID_PAD:
+        raise ValueError(f"ConvFFN {dim} -> {hid} is not supported: hat_escfp_convffn is built for 48 channels and a hidden width of "
+                         f"{', '.join(map(str, ESCFP_HID_PAD))} (exp_ratio 1.25, 1.5 or 2)")
+    hp = ESCFP_HID_PAD[hid]
+    f = PackedEscFfn()
+    f.hid, f.hid_p = hid, hp
+    f.w1 = frags(_pad(W1.reshape(hid, dim), hp, 64)).to(TORCH_DTYPE[dtype]).contiguous().to(device)
+    f.b1 = _pad(_f32(sd[p + ".proj.bias"]), hp).to(device)
+    f.dww = _pad(_f32(sd[p + ".dwc.weight"]).reshape(hid, 9), hp).t().contiguous().to(device)
+    f.dwb = _pad(_f32(sd[p + ".dwc.bias"]), hp).to(device)
+    f.w2 = frags(_pad(_f32(sd[p + ".aggr.weight"]).reshape(dim, hid), dim, hp)).to(TORCH_DTYPE[dtype]).contiguous().to(device)
+    f.b2 = _f32(sd[p + ".aggr.bias"]).contiguous().to(device)
+    return f
+
+
+class PackedEscFpLk:
+    """hat_escfp_weights' operands for one DecomposedConvolutionalAttention (esc_fp_arch.py:89-120), all fp32: w1 (4,16), b1 [4],
+    w2 (144,4), b2 [144] = plk.proj.1 / plk.proj.3; lk_channel (16,16), lk_spatial (16,169) = the network's two shared filters.  kpad:
+    the row length of the weight image it writes = what hat_esc_conv13 / hat_conv (nt 1) read for a 13 x 13 conv over 16 channels."""
+    __slots__ = ("w1", "b1", "w2", "b2", "lk_channel", "lk_spatial", "kpad", "zero_bias", "aggr", "conv13")   # the last two: set by the engine
+
+
+def pack_escfp_lk(sd, p: str, dtype: int, device) -> PackedEscFpLk:
+    """sd[p + '.plk.proj.1.weight'] ..., sd['lk_channel'], sd['lk_spatial'] -> PackedEscFpLk."""
+    w1, w2 = _f32(sd[p + ".plk.proj.1.weight"]), _f32(sd[p + ".plk.proj.3.weight"])
+    lc, ls = _f32(sd["lk_channel"]), _f32(sd["lk_spatial"])
+    if tuple(w1.shape[:2]) != (4, 16) or tuple(w2.shape[:2]) != (144, 4) or tuple(lc.shape) != (16, 16, 1, 1) or tuple(ls.shape) != (16, 1, 13, 13):
+        raise ValueError(f"large-kernel branch {tuple(w1.shape)} / {tuple(w2.shape)} / {tuple(lc.shape)} / {tuple(ls.shape)} is not supported: "
+                         "hat_escfp_weights is built for pdim 16 (16 -> 4 -> 144) and a 13 x 13 kernel")
+    f = PackedEscFpLk()
+    f.w1, f.b1 = w1.reshape(4, 16).contiguous().to(device), _f32(sd[p + ".plk.proj.1.bias"]).contiguous().to(device)
+    f.w2, f.b2 = w2.reshape(144, 4).contiguous().to(device), _f32(sd[p + ".plk.proj.3.bias"]).contiguous().to(device)
+    f.lk_channel, f.lk_spatial = lc.reshape(16, 16).contiguous().to(device), ls.reshape(16, 169).contiguous().to(device)
+    kc = KC[dtype] * 3   # hat_conv's weight chunk length at nt == 1
+    f.kpad = -(-(169 * 16) // kc) * kc
+    f.zero_bias = torch.zeros(16, device=device)
+    return f
+
+
+def escfp_rank1_fold(lk_channel, k):
+    """lk_channel (16,16,1,1), k (16,1,13,13) = lk_spatial + the padded dynamic kernel -> the dense (16,16,13,13) filter
+    weff[o][i] = lk_channel[o][i] * k[o] of conv1x1(lk_channel) followed by the depthwise conv k.  lk_channel has no bias, so zero
+    padding commutes with it and the dense conv with zero padding 6 is exact at the border too."""
+    return lk_channel.reshape(16, 16, 1, 1) * k.reshape(16, 1, 13, 13)
+
+
+def bicubic_phase_table(s: int) -> torch.Tensor:
+    """(s, 4) fp32: the weights of F.interpolate(scale_factor=s, mode='bicubic', align_corners=False) per output phase p = o % s, on
+    the source taps o // s + first .. first + 3 with first = -2 if 2 p + 1 < s else -1: Keys' cubic with A = -0.75 at the exact
+    fraction t = frac((2 p + 1) / (2 s) - 1/2), computed in fp64."""
+    A = -0.75
+    inner = lambda t: ((A + 2.0) * t - (A + 3.0)) * t * t + 1.0           # |t| <= 1
+    outer = lambda t: ((A * t - 5.0 * A) * t + 8.0 * A) * t - 4.0 * A     # 1 < |t| < 2
+    rows = []
+    for p in range(s):
+        num = (2 * p + 1 - s) % (2 * s)     # t = num / (2 s), exactly
+        t = num / (2.0 * s)
+        rows.append([outer(t + 1.0), inner(t), inner(1.0 - t), outer(2.0 - t)])
+    return torch.tensor(rows, dtype=torch.float64).to(torch.float32)
+
+
 def esc_geo_ensemble(k: torch.Tensor) -> torch.Tensor:
     """The mean of the 8 flips / rotations of a (pdim, pdim, k, k) filter, in the reference's order of additions (esc_arch.py:289-298)."""
     r = torch.rot90(k, -1, [2, 3])
