@@ -9,13 +9,12 @@ the loop through the hooks of `ESCEngine`.
 """
 from __future__ import annotations
 
-import collections
-
 import torch
 
 from . import ops
-from .engine import _ESC
+from .engine_base import EngineBase
 from .ops import ACT_LRELU02, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T, X_NCHW_F32_MEAN, X_NHWC_F32
+from .packing import _ESC
 
 LN_EPS = 1e-6   # esc_arch.py:69
 SUPPORTED = dict(dim=64, pdim=16, kernel_size=13, window_size=32, num_heads=4)
@@ -29,7 +28,8 @@ class _Block:
     pass
 
 
-class ESCEngine:
+class ESCEngine(EngineBase):
+    WS_MAX = 4   # entries of the workspace LRU
     # what a width of the family swaps: the two kernels that are instantiated per channel count, and their packer
     _convffn, _layernorm, _pack_ffn = staticmethod(ops.esc_convffn), staticmethod(ops.esc_layernorm), staticmethod(ops.pack_esc_convffn)
 
@@ -45,9 +45,8 @@ class ESCEngine:
         self._check_cfg(cfg)
         if compute_dtype not in ops.DTYPE_CODE:
             raise ValueError(f"compute_dtype {compute_dtype!r}: expected 'bf16' or 'fp32'")
-        self.cfg, self.dev = dict(cfg), torch.device(device)
-        self.dtype = dt = ops.DTYPE_CODE[compute_dtype]
-        self.tdt = ops.TORCH_DTYPE[dt]
+        super().__init__(device, compute_dtype, self.WS_MAX)   # (a host device is taken: the engine then packs and never runs)
+        self.cfg, dt = dict(cfg), self.dtype
         self.C, self.scale, self.heads, self.ws = int(cfg["dim"]), int(cfg["upscaling_factor"]), int(cfg["num_heads"]), int(cfg["window_size"])
         dev, C = self.dev, self.C
         vec = lambda k: sd[k].detach().to(dtype=torch.float32, device=dev).contiguous()
@@ -79,7 +78,6 @@ class ESCEngine:
         self.last = ops.pack_conv_weight(sd["last.weight"], sd["last.bias"], dt, dev)
         self._pack_head(sd)
         self._kpad = self.blocks[0].convs[0][2].kpad if self.blocks and self.blocks[0].convs else 0
-        self._ws_cache = collections.OrderedDict()
 
     def _shared_filter(self, sd):
         """The geometric re-parameterisation of the one large-kernel filter, once, unless convert() has baked it in already."""
@@ -108,21 +106,13 @@ class ESCEngine:
         return {"rows": f(B, H * W, _r4(3 * s * s)), "y": f(B, 3, H * s, W * s)}
 
     # ------------------------------------------------------------------------------------------
-    def _workspace(self, B: int, H: int, W: int):
-        key = (B, H, W)
-        w = self._ws_cache.get(key)
-        if w is not None:
-            self._ws_cache.move_to_end(key)
-            return w
+    def _alloc_workspace(self, B: int, H: int, W: int, tag=None):
         dev, N, C = self.dev, H * W, self.C
         f = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
         t = lambda *shape: torch.zeros(*shape, dtype=self.tdt, device=dev)
         w = {"feat0": f(B, N, C), "s": [f(B, N, C) for _ in range(3)], "n": t(B, N, C), "qkv": t(B, N, 3 * C), "att": t(B, N, C),
              "z": t(B, N, C), "y16": t(B, N, 16), "gap": f(B, ops.esc_convffn_tiles(H, W), 16), "weff": t(B, 16, max(self._kpad, 1))}
         w.update(self._head_buffers(B, H, W, f, t))
-        self._ws_cache[key] = w
-        while len(self._ws_cache) > 4:
-            self._ws_cache.popitem(last=False)
         return w
 
     def _lin(self, pw, x, out, *, geo, ldx, ldo, out_mode=O_NHWC_T, **kw):
@@ -131,7 +121,7 @@ class ESCEngine:
         else:
             ops.conv(pw, x, out, **geo, dtype=self.dtype, ldx=ldx, ldo=ldo, out_mode=out_mode, **kw)
 
-    def forward(self, x: torch.Tensor, taps: dict = None) -> torch.Tensor:
+    def _forward(self, x: torch.Tensor, taps: dict = None) -> torch.Tensor:
         """x (B, 3, h, w) fp32 (B = 1 unless the network takes batches) -> (B, 3, s h, s w) fp32 (the workspace's output buffer: copy it before the next forward of the shape).
         taps: a dict that receives clones of the stream after the first ConvFFN, the attention and the first conv block."""
         if x.dim() != 4 or x.shape[1] != 3:

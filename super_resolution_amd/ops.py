@@ -311,10 +311,9 @@ def esc_convffn_tiles(H: int, W: int) -> int:
     return n
 
 
-def esc_convffn(pf: PackedEscFfn, x, out, *, B: int, H: int, W: int, dtype: int, ln=None, eps: float = 1e-6, r=None, partials=None,
-                ldx: int = 64, ldr: int = 64, ldo: int = 64):
-    """out = ConvFFN(ln ? LayerNorm(x; ln = (gamma, beta), eps) : x) (+ r) in one launch (hat_esc_convffn).  x, r: fp32 rows; out: fp32
-    rows when it is an fp32 tensor, else T rows; partials: the (B, esc_convffn_tiles, 16) fp32 pool partials of out[..., :16]."""
+def _esc_convffn(C_: int, entry: str, pf: PackedEscFfn, x, out, *, B: int, H: int, W: int, dtype: int, ldx: int, ldr: int, ldo: int, ln=None,
+             eps: float = 1e-6, r=None, partials=None):
+    """esc_convffn_kernel at C_ channels through `entry` (hat_esc_convffn: 64, hat_escfp_convffn: 48); the **kw of the public names."""
     lib = _lib.load()
     d = HatEscConvFfnDesc()
     d.x, d.w1, d.b1, d.dww, d.dwb, d.w2, d.b2 = _ptr(x), _ptr(pf.w1), _ptr(pf.b1), _ptr(pf.dww), _ptr(pf.dwb), _ptr(pf.w2), _ptr(pf.b2)
@@ -325,10 +324,16 @@ def esc_convffn(pf: PackedEscFfn, x, out, *, B: int, H: int, W: int, dtype: int,
     d.B, d.H, d.W, d.hid_p, d.ldx, d.ldr, d.ldo, d.dtype = B, H, W, pf.hid_p, ldx, ldr, ldo, dtype
     d.out_f32 = int(out.dtype == torch.float32)
     es, npx = (4 if d.out_f32 or dtype == HAT_F32 else 2), float(B * H * W)
-    _timed(f"esc_convffn_kernel<{_TNAME[dtype]}, 64, {pf.hid_p}>", 2.0 * npx * pf.hid * (2 * 64 + 9),
-           lambda: _lib.check(lib.hat_esc_convffn(C.byref(d), _stream()), f"hat_esc_convffn(hid={pf.hid})"),
-           tag=f"convffn 64->{pf.hid}->64 {H}x{W}{' ln' if ln is not None else ''}{' r' if r is not None else ''}{' pool' if partials is not None else ''}",
-           nbytes=npx * 64 * (4 + es + (4 if r is not None else 0)))
+    _timed(f"esc_convffn_kernel<{_TNAME[dtype]}, {C_}, {pf.hid_p}>", 2.0 * npx * pf.hid * (2 * C_ + 9),
+           lambda: _lib.check(getattr(lib, entry)(C.byref(d), _stream()), f"{entry}(hid={pf.hid})"),
+           tag=f"convffn {C_}->{pf.hid}->{C_} {H}x{W}{' ln' if ln is not None else ''}{' r' if r is not None else ''}{' pool' if partials is not None else ''}",
+           nbytes=npx * C_ * (4 + es + (4 if r is not None else 0)))
+
+
+def esc_convffn(pf: PackedEscFfn, x, out, *, ldx: int = 64, ldr: int = 64, ldo: int = 64, **kw):
+    """out = ConvFFN(ln ? LayerNorm(x; ln = (gamma, beta), eps) : x) (+ r) in one launch (hat_esc_convffn).  x, r: fp32 rows; out: fp32
+    rows when it is an fp32 tensor, else T rows; partials: the (B, esc_convffn_tiles, 16) fp32 pool partials of out[..., :16]."""
+    _esc_convffn(64, "hat_esc_convffn", pf, x, out, ldx=ldx, ldr=ldr, ldo=ldo, **kw)
 
 
 def window_attention_r(q, kv, bias, out, *, B: int, h: int, w: int, C_: int, heads: int, ws: int, ldq: int, ldkv: int, ldo: int, dtype: int):
@@ -340,12 +345,16 @@ def window_attention_r(q, kv, bias, out, *, B: int, h: int, w: int, C_: int, hea
         "hat_window_attention_r"), tag=f"attn ws{ws} {h}x{w}")
 
 
-def esc_layernorm(x, y, gamma, beta, *, npix: int, dtype: int, eps: float = 1e-6, ldx: int = 64, ldy: int = 64):
-    """y (T rows) = LayerNorm over 64 channels of x (fp32 rows) with `eps` (hat_esc_layernorm)."""
+def _esc_layernorm(C_: int, entry: str, x, y, gamma, beta, *, npix: int, dtype: int, ldx: int, ldy: int, eps: float = 1e-6):
     lib = _lib.load()
-    _timed(f"esc_layernorm_kernel<{_TNAME[dtype]}, 64>", 0.0, lambda: _lib.check(
-        lib.hat_esc_layernorm(_ptr(x), _ptr(y), _ptr(gamma), _ptr(beta), eps, npix, ldx, ldy, dtype, _stream()), "hat_esc_layernorm"),
-        tag="ln64 eps")
+    _timed(f"esc_layernorm_kernel<{_TNAME[dtype]}, {C_}>", 0.0, lambda: _lib.check(
+        getattr(lib, entry)(_ptr(x), _ptr(y), _ptr(gamma), _ptr(beta), eps, npix, ldx, ldy, dtype, _stream()), entry),
+        tag=f"ln{C_} eps")
+
+
+def esc_layernorm(x, y, gamma, beta, *, ldx: int = 64, ldy: int = 64, **kw):
+    """y (T rows) = LayerNorm over 64 channels of x (fp32 rows) with `eps` (hat_esc_layernorm)."""
+    _esc_layernorm(64, "hat_esc_layernorm", x, y, gamma, beta, ldx=ldx, ldy=ldy, **kw)
 
 
 def esc_shuffle_add(rows, x, y, *, B: int, H: int, W: int, s: int, ld: int):
@@ -379,31 +388,14 @@ def dysample(rows, init_pos, bias, y, *, B: int, H: int, W: int, s: int, ld: int
 # ------------------------------------------------------------------------------------------------
 # ESCFP (hat_escfp_convffn / hat_escfp_layernorm / hat_escfp_weights / hat_escfp_shuffle_bicubic)
 # ------------------------------------------------------------------------------------------------
-def escfp_convffn(pf: PackedEscFfn, x, out, *, B: int, H: int, W: int, dtype: int, ln=None, eps: float = 1e-6, r=None, partials=None,
-                  ldx: int = 48, ldr: int = 48, ldo: int = 48):
+def escfp_convffn(pf: PackedEscFfn, x, out, *, ldx: int = 48, ldr: int = 48, ldo: int = 48, **kw):
     """esc_convffn at 48 channels (hat_escfp_convffn); pf from pack_escfp_convffn."""
-    lib = _lib.load()
-    d = HatEscConvFfnDesc()
-    d.x, d.w1, d.b1, d.dww, d.dwb, d.w2, d.b2 = _ptr(x), _ptr(pf.w1), _ptr(pf.b1), _ptr(pf.dww), _ptr(pf.dwb), _ptr(pf.w2), _ptr(pf.b2)
-    if ln is not None:
-        d.ln_g, d.ln_b = _ptr(ln[0]), _ptr(ln[1])
-    d.ln_eps = eps
-    d.r, d.out, d.partials = _ptr(r), _ptr(out), _ptr(partials)
-    d.B, d.H, d.W, d.hid_p, d.ldx, d.ldr, d.ldo, d.dtype = B, H, W, pf.hid_p, ldx, ldr, ldo, dtype
-    d.out_f32 = int(out.dtype == torch.float32)
-    es, npx = (4 if d.out_f32 or dtype == HAT_F32 else 2), float(B * H * W)
-    _timed(f"esc_convffn_kernel<{_TNAME[dtype]}, 48, {pf.hid_p}>", 2.0 * npx * pf.hid * (2 * 48 + 9),
-           lambda: _lib.check(lib.hat_escfp_convffn(C.byref(d), _stream()), f"hat_escfp_convffn(hid={pf.hid})"),
-           tag=f"convffn 48->{pf.hid}->48 {H}x{W}{' ln' if ln is not None else ''}{' r' if r is not None else ''}{' pool' if partials is not None else ''}",
-           nbytes=npx * 48 * (4 + es + (4 if r is not None else 0)))
+    _esc_convffn(48, "hat_escfp_convffn", pf, x, out, ldx=ldx, ldr=ldr, ldo=ldo, **kw)
 
 
-def escfp_layernorm(x, y, gamma, beta, *, npix: int, dtype: int, eps: float = 1e-6, ldx: int = 48, ldy: int = 48):
+def escfp_layernorm(x, y, gamma, beta, *, ldx: int = 48, ldy: int = 48, **kw):
     """y (T rows) = LayerNorm over 48 channels of x (fp32 rows) with `eps` (hat_escfp_layernorm)."""
-    lib = _lib.load()
-    _timed(f"esc_layernorm_kernel<{_TNAME[dtype]}, 48>", 0.0, lambda: _lib.check(
-        lib.hat_escfp_layernorm(_ptr(x), _ptr(y), _ptr(gamma), _ptr(beta), eps, npix, ldx, ldy, dtype, _stream()), "hat_escfp_layernorm"),
-        tag="ln48 eps")
+    _esc_layernorm(48, "hat_escfp_layernorm", x, y, gamma, beta, ldx=ldx, ldy=ldy, **kw)
 
 
 def escfp_weights(partials, nblk: int, npix: int, lk: PackedEscFpLk, w_out, *, B: int, dtype: int):

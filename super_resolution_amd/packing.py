@@ -439,6 +439,31 @@ def pack_esc_convffn(sd, p: str, dtype: int, device) -> PackedEscFfn:
     return f
 
 
+class _ESC:
+    """Packed parameters of one ConvAttnWrapper (esc_arch.py:136-145) + its large-kernel filter."""
+
+    def __init__(self, sd, core: str, plk_key: str, pdim: int, ksize: int, C: int, dtype: int, dev):
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.pdim, self.ksize = pdim, ksize
+        self.w1 = sd[core + ".plk.dwc_proj.1.weight"].detach().reshape(pdim // 2, pdim).to(**f32).contiguous()
+        self.b1 = sd[core + ".plk.dwc_proj.1.bias"].detach().to(**f32).contiguous()
+        self.w2 = sd[core + ".plk.dwc_proj.3.weight"].detach().reshape(pdim * 9, pdim // 2).to(**f32).contiguous()
+        self.b2 = sd[core + ".plk.dwc_proj.3.bias"].detach().to(**f32).contiguous()
+        # static large-kernel filter packed in fp32 [16 or 32][Kpad]; hat_esc_weights adds the dynamic
+        # depthwise 3x3 on the diagonal of the central taps and casts to T per forward
+        lk = pack_conv_weight(sd[plk_key], None, HAT_F32, dev, nt=1)
+        kc = KC[dtype] * 3  # nt == 1 chunk length (hat_conv.hip)
+        self.kpad = -(-(ksize * ksize * ((pdim + 7) // 8 * 8)) // kc) * kc
+        self.npad = 16 if pdim <= 16 else 32   # weight rows / output channels of the conv (one or two 16-row slices)
+        plk = torch.zeros(self.npad, self.kpad, **f32)
+        plk[:lk.w.shape[0], :min(self.kpad, lk.kpad)] = lk.w[:self.npad, :min(self.kpad, lk.kpad)]
+        self.plk = plk.contiguous()
+        self.zero_bias = torch.zeros(self.npad, **f32)
+        self.aggr = None  # packed by the engine (hat_linear when the shape is instantiated)
+        self.aggr_keys = (core + ".aggr.weight", core + ".aggr.bias")
+        self.conv13 = False   # set by the engine: the conv runs on hat_esc_conv13 (else on hat_conv)
+
+
 ESCFP_HID_PAD = {60: 64, 72: 96, 96: 96}   # hidden widths hat_escfp_convffn is instantiated for (48 channels) -> padded
 
 

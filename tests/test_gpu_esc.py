@@ -250,6 +250,52 @@ def test_batch_and_small_frames_are_refused():
         net(torch.zeros(1, 3, 16, 40, device=dev))
 
 
+def _fresh_engine(dev):
+    """A new engine (empty workspace cache, its own lock) over case a's network: n_blocks 1, conv_blocks 1, fp32."""
+    from super_resolution_amd.esc_engine import ESCEngine
+    net, _, _ = _net("a", "fp32", dev)
+    return ESCEngine(net.cfg, net.state_dict(), dev, "fp32")
+
+
+def test_engine_refuses_host_and_other_device_tensors_before_any_launch():
+    dev = _dev()
+    eng = _fresh_engine(dev)
+    x = synth.synth_input(R.X_SEED, (1, 3, 33, 40)).to(dev)
+    with pytest.raises(RuntimeError, match="device tensor"):
+        eng.forward(x.cpu())
+    if torch.cuda.device_count() >= 2:
+        with pytest.raises(RuntimeError, match="lives on"):
+            eng.forward(x.to("cuda:1"))
+    assert len(eng._ws_cache) == 0 and eng.ws_allocations == 0
+
+
+def test_one_forward_at_a_time_per_engine():
+    """Three threads on one engine, two of them on the same shape, so on the same workspace (w["s"], w["gap"], w["weff"] and the
+    output buffer): every result, cloned under no lock of the thread's own, is the serial one bit for bit."""
+    import threading
+    dev = _dev()
+    eng = _fresh_engine(dev)
+    x33, x40 = (synth.synth_input(R.X_SEED + i, shape).to(dev) for i, shape in enumerate([(1, 3, 33, 40), (1, 3, 40, 33)]))
+    y33, y40 = eng.forward(x33).clone(), eng.forward(x40).clone()
+    got, errors = [], []
+
+    def run(x, want):
+        try:
+            for _ in range(8):
+                got.append((eng.forward(x).clone(), want))
+        except Exception as e:   # noqa: BLE001  (reported by the assert below, with the thread's traceback text)
+            errors.append(repr(e))
+
+    threads = [threading.Thread(target=run, args=a, daemon=True) for a in ((x33, y33), (x40, y40), (x33, y33))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(60)
+    assert not any(t.is_alive() for t in threads), "a forward did not come back within 60 s"
+    assert not errors, errors
+    assert len(got) == 24 and all(torch.equal(y, want) for y, want in got)
+
+
 def test_reference_style_yaml_through_the_test_entry(tmp_path):
     """An option file as the reference ships them (model_type ESRModel, network_g.type ESC) through `python -m
     super_resolution_amd.test`: the PSNR is the one metrics.py gives for the fp32 golden path's output (tests/esc_ref.py in fp32 on
