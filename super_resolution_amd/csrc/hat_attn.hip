@@ -9,7 +9,6 @@
 // cross-lane shuffles; P^T feeds the second MFMA (O^T = V^T.P^T) straight from the accumulator
 // registers — the contraction index (key) ordering inside a 32-wide k-step is permuted
 // identically for both operands, so no LDS round trip or lane movement is needed for P.
-#include <cstdlib>
 #include <type_traits>
 
 #include "hat_common.h"
@@ -849,16 +848,13 @@ static int ocab_attention_impl(const void* q, const void* kv, const float* bias_
     const bool fast30 = d == 30 && ldq % 2 == 0 && ldkv % 2 == 0 && ldo % 2 == 0 && C % 2 == 0;
     if (dtype == HAT_BF16 && ws == 16 && wse == 24 && (fast24 || fast30)) {
         const size_t lds = (size_t)576 * ((fast24 && !qlog2) ? 24 : 32) * 2 + (size_t)576 * 32 * 2 + (size_t)39 * 39 * 4;
-        static const bool w4 = getenv("HAT_ATTN_4WAVES") != nullptr;   // (A/B switch: round 1's four-wave workgroups)
         if (qlog2 && !fast24) return HAT_EUNSUPPORTED;
-        auto kern = fast24 ? (qlog2 ? ocab_attn_fast_kernel<24, 24, false, 512, true>
-                                    : (w4 ? ocab_attn_fast_kernel<24, 24, false> : ocab_attn_fast_kernel<24, 24, false, 512>))
-                           : (w4 ? ocab_attn_fast_kernel<30, 24, false> : ocab_attn_fast_kernel<30, 24, false, 512>);
-        const int nth = (w4 && !qlog2) ? 256 : 512;
+        auto kern = fast24 ? (qlog2 ? ocab_attn_fast_kernel<24, 24, false, 512, true> : ocab_attn_fast_kernel<24, 24, false, 512>)
+                           : ocab_attn_fast_kernel<30, 24, false, 512>;
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
         const int nwin = B * (W / ws) * (H / ws);
-        HAT_LAUNCH(kern, dim3((nwin + 7) / 8 * 8 * heads), dim3(nth), lds, s, reinterpret_cast<const bf16_t*>(q),
+        HAT_LAUNCH(kern, dim3((nwin + 7) / 8 * 8 * heads), dim3(512), lds, s, reinterpret_cast<const bf16_t*>(q),
                    reinterpret_cast<const bf16_t*>(kv), bias_rot, reinterpret_cast<bf16_t*>(out), B, H, W, C, heads, ldq, ldkv, ldo, 0);
         return hat_check_launch();
     }

@@ -12,7 +12,6 @@
 //   tile T2(dx): A rows 0-7  = tap (ky = 2, kx) -> output row r - 1        (rows 8-15 are zero)
 // so after input row r the lower lane half of ring slot (r-1)%3 holds the ky = 0 and ky = 2 terms of output row r - 1 and
 // the upper lane half of slot r%3 its ky = 1 terms: one cross-half add finishes the row.  No LDS, no barriers.
-#include <cstdlib>
 #include <type_traits>
 
 #include "hat_common.h"
@@ -273,9 +272,8 @@ extern "C" int hat_cab_squeeze_units(int32_t H, int32_t W, int32_t* rows_out, in
     if (H < 1 || W < 16 || W % 16 || !rows_out || !units_out) return HAT_EINVAL;
     // 256 CUs x 4 SIMDs x 2 waves.  (One wave per SIMD — which lets the 13x13 ESC conv's workgroups start beside this kernel
     // instead of after it, 240 + 2 x 128 registers — was measured: both kernels then take nearly twice as long, 128 and 92 us,
-    // and the pair finishes when it does run back to back, ~140 us after the tail.  HAT_SQUEEZE_SLOTS=1024 repeats it.)
-    static const int slots = [] { const char* e = getenv("HAT_SQUEEZE_SLOTS"); const int v = e ? atoi(e) : 0; return v >= 256 ? v : 2048; }();
-    return sweep_units(H, W, slots, rows_out, units_out);
+    // and the pair finishes when it does run back to back, ~140 us after the tail.)
+    return sweep_units(H, W, 2048, rows_out, units_out);
 }
 
 extern "C" int hat_cab_squeeze(const void* x, const void* wpk, const float* bias, void* out, float* colsum, int32_t B,

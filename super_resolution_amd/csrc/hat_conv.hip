@@ -12,7 +12,6 @@
 //   K is flat: k = tap * Cin_p + ci; a lane's 8-element k group never straddles a tap because
 //   Cin_p % 8 == 0, so each lane tracks its own (tap, ci) and reads its B fragment from the
 //   shifted pixel: no im2col buffer exists anywhere.
-#include <cstdlib>
 #include <type_traits>
 
 #include "hat_common.h"
@@ -548,8 +547,7 @@ int launch_conv(const HatConvDesc& d, size_t lds, hipStream_t stream) {
     dim3 grid((d.W + 15) / 16, (d.H + WAVES * PT - 1) / (WAVES * PT), d.B);
     HatConvDesc dd = d;
     // stagger (kernel side: see conv_kernel): only for launches that keep every CU busy for several rounds of ONE workgroup each
-    static const int stag = [] { const char* e = getenv("HAT_CONV_STAGGER"); return e ? atoi(e) : 2; }();
-    dd.reserved0 = (lds > HAT_LDS_MAX / 2 && (size_t)grid.x * grid.y * grid.z >= 1024) ? stag : 0;
+    dd.reserved0 = (lds > HAT_LDS_MAX / 2 && (size_t)grid.x * grid.y * grid.z >= 1024) ? 2 : 0;
     HAT_LAUNCH(kern, grid, dim3(WAVES * 64), lds, stream, dd);
     return hat_check_launch();
 }

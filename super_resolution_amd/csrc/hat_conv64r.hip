@@ -13,8 +13,6 @@
 //   * a wave owns two tile rows x all four channel tiles and sweeps the tap ROWS for a fixed (tap column, channel half): the
 //     input-row fragment tile row 1 uses for tap row dy is the one tile row 0 needs for dy + 1 (4 row fragments feed 6
 //     (tap row, tile row) pairs: 16 fragment reads per 24 MFMAs).
-#include <cstdlib>
-
 #include "hat_common.h"
 
 namespace {
@@ -155,8 +153,7 @@ __global__ __launch_bounds__(R_NTHR) void conv64r_kernel(const HatConvDesc d, in
 // Does hat_conv route `d` here?  bf16, 3x3, exactly 64 input channels as T rows, a whole number of 64-channel output slices,
 // every one stored, plain epilogue (bias, optional LeakyReLU), NHWC or PixelShuffle output.
 bool hat_conv64r_can_launch(const HatConvDesc& d) {
-    static const bool off = getenv("HAT_NO_CONV64R") != nullptr;
-    if (off || d.dtype != HAT_BF16 || d.ksize != 3 || d.Cin != 64 || d.x_mode != HAT_X_NHWC_T || d.x0) return false;
+    if (d.dtype != HAT_BF16 || d.ksize != 3 || d.Cin != 64 || d.x_mode != HAT_X_NHWC_T || d.x0) return false;
     const int n = d.n_slices * d.nt * 16;
     if (n % 64 || d.n_store != n || d.Kpad < 576 || d.w_bstride) return false;
     if (d.r1 || d.r2 || d.colsum || d.ln_out || d.gap_out || (d.act != HAT_ACT_NONE && d.act != HAT_ACT_LRELU)) return false;

@@ -12,10 +12,8 @@
 //     g & 1 is conflict-free for ds_read_b128) is resident too: no barrier inside the K loop;
 //   * a wave owns RW output rows x 32 columns and sweeps the tap ROWS for a fixed column pair: the input-row fragment that
 //     output row j + 1 uses for tap row dy is the one output row j needs for tap row dy + 1, so RW + 12 row fragments (x 2
-//     column tiles) and 13 weight fragments feed 13 * RW * 2 MFMAs.  RW = 2 (sixteen waves, round 2): 0.79 KB of LDS reads
-//     per MFMA, the LDS array 75 % busy at the MFMA rate; RW = 4 (eight waves, two per SIMD): 0.43 KB per MFMA.
-#include <cstdlib>
-
+//     column tiles) and 13 weight fragments feed 13 * RW * 2 MFMAs.  RW = 4 (eight waves, two per SIMD): 0.43 KB of LDS reads
+//     per MFMA; round 2's RW = 2 (sixteen waves) read 0.79 KB per MFMA and kept the LDS array 75 % busy at the MFMA rate.
 #include "hat_common.h"
 
 namespace {
@@ -23,16 +21,15 @@ namespace {
 constexpr int E_TR = 32, E_TC = 32, E_HALO = 6;
 constexpr int E_HR = E_TR + 2 * E_HALO, E_HC = E_TC + 2 * E_HALO;      // 44 x 44 haloed pixels
 constexpr int E_NFRAG = 7 * 13;
+constexpr int RW = 4, E_WAVES = E_TR / RW;                               // output rows per wave, waves per workgroup
 constexpr int E_X_OFF = E_NFRAG * 1024;                                  // 93184
 constexpr int E_LDS = E_X_OFF + E_HR * E_HC * 32 + 64;                   // 155200 bytes (one workgroup per CU)
 
 __device__ __attribute__((aligned(16))) unsigned hat_esc13_zero_page[4] = {0, 0, 0, 0};
 
-template <int RW>
-__global__ __launch_bounds__((E_TR / RW) * 64) void esc13_kernel(const bf16_t* __restrict__ x, int ldx, const bf16_t* __restrict__ wp, int Kpad,
+__global__ __launch_bounds__(E_WAVES * 64) void esc13_kernel(const bf16_t* __restrict__ x, int ldx, const bf16_t* __restrict__ wp, int Kpad,
                                                              bf16_t* __restrict__ y16, int H, int W, int tiles_x, int ntiles) {
     typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-    constexpr int E_WAVES = E_TR / RW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef __attribute__((address_space(3))) char lds_char;
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_char*)smem;
@@ -157,13 +154,9 @@ extern "C" int hat_esc_conv13(const void* x, int32_t ldx, const void* wp, int32_
     const int tiles_x = (W + E_TC - 1) / E_TC, tiles_y = (H + E_TR - 1) / E_TR, ntiles = tiles_x * tiles_y;
     int gx = 256 / (B < 2 ? 1 : (B < 4 ? 2 : 4));   // tests/test_gpu_multitrip.py: ESC13_TRIP_TILES[B] 32 x 32 tiles per sample
     if (gx > ntiles) gx = ntiles;
-    static const int rw = [] { const char* e = getenv("HAT_ESC13_RW"); return e && atoi(e) == 2 ? 2 : 4; }();   // 2: round 2's sixteen-wave shape (A/B)
-    auto launch = [&](auto kern, int waves) -> int {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, E_LDS);
-        if (e != hipSuccess) return (int)e;
-        HAT_LAUNCH(kern, dim3(gx, B), dim3(waves * 64), E_LDS, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const bf16_t*>(x), ldx,
-                   reinterpret_cast<const bf16_t*>(wp), Kpad, reinterpret_cast<bf16_t*>(y16), H, W, tiles_x, ntiles);
-        return hat_check_launch();
-    };
-    return rw == 2 ? launch(esc13_kernel<2>, 16) : launch(esc13_kernel<4>, 8);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(esc13_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, E_LDS);
+    if (e != hipSuccess) return (int)e;
+    HAT_LAUNCH(esc13_kernel, dim3(gx, B), dim3(E_WAVES * 64), E_LDS, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const bf16_t*>(x), ldx,
+               reinterpret_cast<const bf16_t*>(wp), Kpad, reinterpret_cast<bf16_t*>(y16), H, W, tiles_x, ntiles);
+    return hat_check_launch();
 }

@@ -12,7 +12,6 @@
 // 4g..4g+3 of a 16-unit tile) IS the B operand of fc2 when fc2's k-slot (g, j) is defined as unit 4g + j of tile 2kk
 // (j < 4) or of tile 2kk + 1 (j >= 4) — ops.pack_ocab_mlp orders fc2's fragments that way (the trick of the attention
 // kernel's P fragment and of hat_ffn2's gate).
-#include <cstdlib>
 #include <type_traits>
 
 #include "hat_common.h"
@@ -46,11 +45,13 @@ constexpr int ML_NREG = 4;                         // fc2 fragments kept in regi
 constexpr int ML_W2F = (ML_NT2 * ML_KK - ML_NREG) * 1024;   // 78848
 constexpr int ML_OFF_W1H = ML_W1F, ML_OFF_W2 = ML_W1F + ML_W1H, ML_OFF_B1 = ML_OFF_W2 + ML_W2F, ML_OFF_B2 = ML_OFF_B1 + ML_HID * 4;
 constexpr int ML_LDS = ML_OFF_B2 + ML_C * 4;       // 163520 <= 163840
+// Eight waves per workgroup in both kernels.  Sixteen were built and measured: the MLP kernel spilled at 128 registers and
+// ran slower, the q + kv kernel showed no difference.
+constexpr int ML_WAVES = 8, ML_NTHR = ML_WAVES * 64;
 
 // R16: r1 is FP16 rows (the 16-bit residual stream), loaded as raw bits and converted (exactly) where it is added
-template <bool OUTF32, int WAVES, bool R16 = false>
-__global__ __launch_bounds__(WAVES * 64) void ocab_mlp_kernel(const HatMlpDesc d, long npix, long tiles) {
-    constexpr int ML_NTHR = WAVES * 64, ML_WAVES = WAVES;
+template <bool OUTF32, bool R16 = false>
+__global__ __launch_bounds__(ML_NTHR) void ocab_mlp_kernel(const HatMlpDesc d, long npix, long tiles) {
     using M = MT<bf16_t>;
     typedef bf16_t T;
     typedef M::frag_t frag_t;
@@ -207,9 +208,7 @@ __global__ __launch_bounds__(WAVES * 64) void ocab_mlp_kernel(const HatMlpDesc d
 constexpr int QK_NT = 27, QK_N = QK_NT * 16;
 constexpr int QK_WF = QK_NT * 4 * 1024, QK_WH = QK_NT * 512, QK_OFF_B = QK_WF + QK_WH, QK_LDS = QK_OFF_B + QK_N * 4;   // 126144 B
 
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void ocab_qkv_kernel(const HatMlpDesc d, long npix, long tiles) {
-    constexpr int ML_NTHR = WAVES * 64, ML_WAVES = WAVES;
+__global__ __launch_bounds__(ML_NTHR) void ocab_qkv_kernel(const HatMlpDesc d, long npix, long tiles) {
     using M = MT<bf16_t>;
     typedef bf16_t T;
     typedef M::frag_t frag_t;
@@ -292,14 +291,11 @@ extern "C" int hat_ocab_qkv(const HatMlpDesc* dp, void* stream) {
     if (d.C != ML_C || d.hidden != QK_N || d.dtype != HAT_BF16) return HAT_EUNSUPPORTED;
     if (d.ldx < ML_C || d.ldx % 8 || d.ldo < QK_N || d.ldo % 8 || reinterpret_cast<uintptr_t>(d.out) % 16) return HAT_EINVAL;
     const long npix = (long)d.B * d.H * d.W, tiles = (npix + 15) / 16;
-    static const int waves = getenv("HAT_QKV_WAVES") ? atoi(getenv("HAT_QKV_WAVES")) : 8;    // (A/B switch: 8 or 16 waves per workgroup; no difference measured)
-    const int nw = waves == 8 ? 8 : 16;
-    int gx = 256;   // tests/test_gpu_multitrip.py: QKV_TRIP_TILES = 256 * nw
-    if ((long)gx * nw > tiles) gx = (int)((tiles + nw - 1) / nw);
-    auto kern = nw == 8 ? ocab_qkv_kernel<8> : ocab_qkv_kernel<16>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, QK_LDS);
+    int gx = 256;   // tests/test_gpu_multitrip.py: QKV_TRIP_TILES = 256 * ML_WAVES
+    if ((long)gx * ML_WAVES > tiles) gx = (int)((tiles + ML_WAVES - 1) / ML_WAVES);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ocab_qkv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, QK_LDS);
     if (e != hipSuccess) return (int)e;
-    HAT_LAUNCH(kern, dim3(gx), dim3(nw * 64), QK_LDS, reinterpret_cast<hipStream_t>(stream), d, npix, tiles);
+    HAT_LAUNCH(ocab_qkv_kernel, dim3(gx), dim3(ML_NTHR), QK_LDS, reinterpret_cast<hipStream_t>(stream), d, npix, tiles);
     return hat_check_launch();
 }
 
@@ -316,16 +312,12 @@ extern "C" int hat_ocab_mlp(const HatMlpDesc* dp, void* stream) {
     if (r16 && reinterpret_cast<uintptr_t>(d.r1) % 8) return HAT_EINVAL;
     if (out_f32 ? d.ldo % 4 : (d.ldo % 8 || reinterpret_cast<uintptr_t>(d.out) % 16)) return HAT_EINVAL;
     const long npix = (long)d.B * d.H * d.W, tiles = (npix + 15) / 16;
-    static const int waves = getenv("HAT_MLP_WAVES") ? atoi(getenv("HAT_MLP_WAVES")) : 8;    // (A/B switch; 16 waves spill at 128 registers and measured slower)
-    const int nw = waves == 8 ? 8 : 16;
-    int gx = 256;   // tests/test_gpu_multitrip.py: MLP_TRIP_TILES = 256 * nw
-    if ((long)gx * nw > tiles) gx = (int)((tiles + nw - 1) / nw);
+    int gx = 256;   // tests/test_gpu_multitrip.py: MLP_TRIP_TILES = 256 * ML_WAVES
+    if ((long)gx * ML_WAVES > tiles) gx = (int)((tiles + ML_WAVES - 1) / ML_WAVES);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    void (*kern)(const HatMlpDesc, long, long) = out_f32 ? (nw == 8 ? ocab_mlp_kernel<true, 8> : ocab_mlp_kernel<true, 16>)
-                                               : r16 ? (nw == 8 ? ocab_mlp_kernel<false, 8, true> : ocab_mlp_kernel<false, 16, true>)
-                                                     : (nw == 8 ? ocab_mlp_kernel<false, 8> : ocab_mlp_kernel<false, 16>);
+    void (*kern)(const HatMlpDesc, long, long) = out_f32 ? ocab_mlp_kernel<true> : r16 ? ocab_mlp_kernel<false, true> : ocab_mlp_kernel<false>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, ML_LDS);
     if (e != hipSuccess) return (int)e;
-    HAT_LAUNCH(kern, dim3(gx), dim3(nw * 64), ML_LDS, s, d, npix, tiles);
+    HAT_LAUNCH(kern, dim3(gx), dim3(ML_NTHR), ML_LDS, s, d, npix, tiles);
     return hat_check_launch();
 }

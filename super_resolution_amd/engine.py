@@ -20,7 +20,7 @@ from __future__ import annotations
 import dataclasses
 import math
 import os
-from typing import Dict, Optional
+from typing import Dict
 
 import torch
 
@@ -49,12 +49,9 @@ class Options:
       HAT_NO_N16=1           no compact 16-channel copy of the LayerNorm rows for the 13x13 ESC conv
       HAT_NO_T16=1           the residual stream in fp32 everywhere (default on the bf16 path at embed_dim 144: FP16 rows wherever
                              every reader takes them: group conv, fused HAB tails, OCAB projection / MLP)
-      HAT_EMU_T16=fp16|bf16  measurement only: round the fp32 residual stream to that type after every fused HAB tail and group
-                             conv (a torch copy, not a product path; tools/residual16_psnr.py)
       HAT_NO_FUSED_FFN=1     the FFN as fc1 -> dw + gate -> fc2 instead of hat_ffn / hat_ffn2
       HAT_FFN_V1=1           hat_ffn (bf16 hidden tensor) instead of hat_ffn2
       HAT_NO_HAB_TAIL=1      no fused HAB tail: the aggregation (hat_aggr_cab / hat_linear), then the fused FFN
-      HAT_TAIL_V2=1          round 2's hat_hab_tail instead of hat_hab_tail3 (embed_dim 180: no fused tail)
       HAT_NO_CAB_FOLD        CAB expand conv + ECA as their own launches instead of folded into the aggregation
       HAT_NO_CAB_SWEEP       CAB squeeze conv and conv_last on hat_conv instead of the row-sweep kernels
       HAT_NO_ESC13=1         the 13x13 ESC conv on hat_conv instead of hat_esc_conv13
@@ -68,11 +65,9 @@ class Options:
       HAT_NO_CONV_LN         the LayerNorm after the group conv as its own launch instead of the conv's epilogue"""
     no_n16: bool = False
     no_t16: bool = False
-    emu_t16: Optional[torch.dtype] = None
     no_fused_ffn: bool = False
     ffn_v1: bool = False
     no_hab_tail: bool = False
-    tail_v2: bool = False
     no_cab_fold: bool = False
     no_cab_sweep: bool = False
     no_esc13: bool = False
@@ -90,8 +85,7 @@ class Options:
         env = os.environ if env is None else env
         get = lambda name: env.get("HAT_" + name.upper(), "")
         any_value = ("no_cab_fold", "no_cab_sweep", "no_ocab_mlp", "no_ocab_qkv", "no_bf16_conv_in", "no_conv_ln")
-        kw = {k.name: (get(k.name) != "" if k.name in any_value else get(k.name) == "1") for k in dataclasses.fields(cls)}
-        return cls(**dict(kw, emu_t16={"fp16": torch.float16, "bf16": torch.bfloat16}.get(get("emu_t16"))))
+        return cls(**{k.name: (get(k.name) != "" if k.name in any_value else get(k.name) == "1") for k in dataclasses.fields(cls)})
 
 
 class _Packed:
@@ -107,7 +101,7 @@ class _Packed:
 class _Hab(_Packed):
     """One HAB (hat_arch.py:217-238): packed weights and the launches chosen for it at pack time.
     fold: the CAB expand conv + ECA folded into the aggregation (hat_cab_fold / hat_aggr_cab), else None (plain CAB convs).
-    tail: "fused144" (hat_hab_tail3, or hat_hab_tail under HAT_TAIL_V2) | "fused180" (hat_hab_tail3 with c2 as a map) |
+    tail: "fused144" (hat_hab_tail3 on ffn3) | "fused180" (hat_hab_tail3 with c2 as a map) |
           "aggr_cab" (after a fold) or "aggr" (hat_linear) followed by the FFN: fused (ffn) or fc1 / gate / fc2 (ffn None).
     next_ln: (gamma, beta), gap_c of the LayerNorm its consumer (the next HAB or the OCAB) starts with.
     out16: the fused tail hands the residual stream on as FP16 rows."""
@@ -196,7 +190,7 @@ class HATEngine(FrameBoundary, EngineBase):
         self.yuv_fused_calls = self.yuv_planes_calls = 0   # YCbCr forwards that ended in hat_conv3x3_to_yuv / in hat_planes_to_yuv
         self.use_n16 = not self.opt.no_n16
         # FP16 residual rows between the fused HAB tails of a residual group (bf16 path, embed_dim 144; HAT_NO_T16=1: fp32 everywhere)
-        self.t16 = not self.opt.no_t16 and self.opt.emu_t16 is None and self.dtype == ops.HAT_BF16 and self.C == 144
+        self.t16 = not self.opt.no_t16 and self.dtype == ops.HAT_BF16 and self.C == 144
         self._s1 = None
         ops._lib.load()
         # HATX (hatx_arch.py): the SGFN runs as fc1 -> hat_sgfn_gate -> fc2; odd window overlaps are padded with
@@ -336,13 +330,14 @@ class HATEngine(FrameBoundary, EngineBase):
             hb.ffn = ops.pack_ffn(*fw, dt, dev)
         hb.tail144_ok = (hb.fold is not None and hb.esc.pdim == 16 and ops.hab_tail_supported(hb.ffn, hb.esc.aggr, w2raw.shape[1], dt)
                          and not opt.no_hab_tail)
-        # third-generation tail (activation-stationary fc1, weights shared through LDS): its own packing;
-        # HAT_TAIL_V2=1 keeps hat_hab_tail for A/B runs
-        if hb.tail144_ok and hb.ffn.layout == "ffn2" and not opt.tail_v2:
+        # third-generation tail (activation-stationary fc1, weights shared through LDS): its own packing.  tail144_ok is the ONE
+        # condition of "fused144" and means ffn3 is packed: hab_tail_supported admits only hat_ffn2's packing of hb.ffn here,
+        # and ffn2_supported and tail3_supported are the same predicate at embed_dim 144
+        if hb.tail144_ok:
             hb.ffn3 = ops.pack_ffn3(*fw, *hb.n2, dev)
         # embed_dim 180 (HAT / HAT-L): hat_hab_tail3 with the CAB's c2 as a map (their squeeze is 60 wide: no fold)
         if (hb.fold is None and C == 180 and fp16_ok and ops.tail3_supported(C, hid2 // 2, dt) and hb.esc.pdim == 16
-                and hb.esc.aggr.frag and not opt.no_hab_tail and not opt.tail_v2):
+                and hb.esc.aggr.frag and not opt.no_hab_tail):
             f3 = ops.pack_ffn3(*fw, *hb.n2, dev)
             if ops.hab_tail_supported(f3, hb.esc.aggr, w2raw.shape[1], dt):
                 hb.ffn3, hb.tail180_ok = f3, True
@@ -446,7 +441,7 @@ class HATEngine(FrameBoundary, EngineBase):
         if not self.t16:
             return
         layers = self.layers
-        tail16 = lambda hb: hb.tail == "fused144" and hb.ffn3 is not None and hb.ffn3.C == 144
+        tail16 = lambda hb: hb.tail == "fused144" and hb.ffn3.C == 144
         conv16 = lambda G: bool(G.conv is not None and not G.conv.frag and G.conv.ksize > 1 and G.conv.nt == 9
                                 and G.conv.n_slices == 1 and G.conv.nout == 144)
         for G in layers:
@@ -819,12 +814,10 @@ class HATEngine(FrameBoundary, EngineBase):
         else:
             tout = w["tB"] if t is not w["tB"] else w["tC"]
         nxt, gap_c = hb.next_ln
-        ops.hab_tail(hb.ffn3 if hb.ffn3 is not None else hb.ffn, hb.esc.aggr, t, tout, hb.n2[0], hb.n2[1], n=w["n"], ldn_in=f.ldc,
+        ops.hab_tail(hb.ffn3, hb.esc.aggr, t, tout, hb.n2[0], hb.n2[1], n=w["n"], ldn_in=f.ldc,
                      y16=w["y16"], c1=w["c1"], wf=w["wf"], bias_b=w["bias_b"], B=f.B, H=f.H, W=f.W, dtype=f.dt, ln1=nxt,
                      n_out=w["n2b"], ldn=f.ldc, gap_out=w["gap"], gap_c=gap_c, n16_out=(w["n16"] if self.use_n16 else None))
         w["n"], w["n2b"] = w["n2b"], w["n"]      # the kernel reads n with a halo: its output n' is another buffer
-        if self.opt.emu_t16 is not None:   # measurement only (tools/residual16_psnr.py): what a 16-bit residual stream would cost
-            tout.copy_(tout.to(self.opt.emu_t16).to(torch.float32))
         f.t, f.have_n, f.have_n16, f.nblk = tout, True, self.use_n16, ops.ffn_tiles(hb.ffn, f.H, f.W, f.dt)
 
     def _tail_fused180(self, f: _Fwd, hb: _Hab):
@@ -985,8 +978,6 @@ class HATEngine(FrameBoundary, EngineBase):
         else:
             ops.conv(G.conv, tout, gout, **f.geo, ldx=C, ldo=C, x_mode=X_NHWC_F32, out_mode=O_NHWC_F32, r1=f.gin, ldr1=C, **lnkw)
         f.t = f.gin = gout
-        if self.opt.emu_t16 is not None:
-            tA.copy_(tA.to(self.opt.emu_t16).to(torch.float32))
 
     def _body_end(self, f: _Fwd):
         """final LN; conv_after_body + f0 ; conv_before_upsample + LeakyReLU               :844, :854-855"""

@@ -41,6 +41,15 @@ def test_library_exports_every_declared_symbol(lib_path):
     assert loaded.hat_layernorm_blocks() > 0
 
 
+def test_library_reads_no_environment(lib_path):
+    """The library is driven through its arguments alone: no launch path may depend on a process variable (DESIGN: the
+    environment rule), so the shared object has no undefined dynamic reference to getenv / secure_getenv."""
+    out = subprocess.run(["nm", "-D", "--undefined-only", lib_path], capture_output=True, text=True, check=True).stdout
+    undefined = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.strip()}
+    assert len(undefined) > 8, "nm listed no undefined symbols: the check would pass vacuously"
+    assert not undefined & {"getenv", "secure_getenv"}
+
+
 @pytest.mark.parametrize("name", ["HatConvDesc", "HatFfnDesc", "HatCabFoldDesc", "HatAggrCabDesc"])
 def test_desc_layout_matches_c(lib_path, tmp_path, name):
     """Compile a tiny C program against the header and compare sizeof/offsetof with ctypes."""

@@ -1,5 +1,5 @@
-"""Time the Upsample convs (64 -> 256 + PixelShuffle(2)) of the headline frame through hat_conv (HAT_NO_CONV64R=1: hat_conv's
-general kernel instead of the resident-weight one) and check the two against each other."""
+"""Time the Upsample convs (64 -> 256 + PixelShuffle(2)) of the headline frame through hat_conv (which routes them to the
+resident-weight kernel of hat_conv64r.hip) and print a checksum of the output."""
 import os
 import sys
 
