@@ -731,7 +731,21 @@ int hat_hab_tail3(const HatHabTailDesc* d, void* stream);
  * and scalars, every device pointer as (buffer, offset), the packed weights and constants with their bytes, and the sizes
  * of the workspace buffers.  `python -m super_resolution_amd.plan -opt x.yml --shape B H W -o net.hatplan` (or
  * `super_resolution_amd.plan.export_plan(net, shape, path)`) writes it by recording what the engine launches.
- *   hat_plan_load     reads the file, allocates (hipMalloc) and uploads; *out owns the device memory.
+ *   hat_plan_load     reads and checks the WHOLE file on the host, then allocates (hipMalloc) and uploads; *out owns the device
+ *                     memory.  The file is untrusted input: a refused file has made no device call and allocated nothing on
+ *                     the device.  HAT_EUNSUPPORTED: another HAT_ABI_VERSION, another function table size, more than 2^20
+ *                     buffers or 2^24 calls.  HAT_EINVAL: no such file, wrong magic, a file that ends early or goes on after
+ *                     the last call; B, Cin, H, W, scale or Cout < 1, a dtype other than HAT_F32 / HAT_BF16, a non-zero
+ *                     reserved word, scale*H or scale*W past int32, B*3*H*W or B*3*(scale*H)*(scale*W) floats past
+ *                     INT64_MAX / 4; a buffer kind > 3 or size > 2^38, anything but exactly one input of B*Cin*H*W*4 bytes
+ *                     and one output of B*Cout*(scale*H)*(scale*W)*4 bytes, a constant buffer whose bytes the file does not
+ *                     hold; a call whose function id is outside the table, whose argument count or any argument kind is not
+ *                     the entry point's (pointer, int32, int64, float, descriptor, host array; the stream last and only
+ *                     last), an int32 argument that does not fit, a descriptor whose size is not sizeof its struct in this
+ *                     header, a fixup whose field offset is not 8-aligned or not wholly inside the descriptor, more than 64
+ *                     fixups, a (buffer, offset) whose buffer does not exist or whose offset is past its bytes.  A positive
+ *                     value is the hipError_t of a failed hipMalloc / copy.  csrc/hat_plan_parse.h is that check (host-only
+ *                     C++); csrc/hat_plan_check.cpp runs it from the command line on machines without a GPU.
  *   hat_plan_info     dims8 = {B, Cin, H, W, scale, Cout, dtype, 0}; number of launches; device bytes held.
  *   hat_plan_forward  x: (B,Cin,H,W) fp32 NCHW in [0,1], y: (B,Cout,scale*H,scale*W) fp32, both device memory of that
  *                     shape; issues the recorded launches on `stream` (one stream; no allocation, no sync).  Results

@@ -8,9 +8,11 @@ The exporter runs ONE forward of the engine on the GPU with a recording proxy in
 offset) against the tensors the engine owns (packed weights, per-shape workspace) plus the input and the output, and the
 list is written with the weights' bytes to a file that `hat_plan_load` / `hat_plan_forward` (csrc/hat_plan.cpp,
 include/hat_mi355x.h "Forward plans") replay from C.  Whatever kernel sequence the engine chooses for the model and shape
-is what the plan contains; results are bit-identical to `net(x)`.
+is what the plan contains; results are bit-identical to `net(x)`.  `record_plan` does the recording, `plan_bytes` the writing
+(no torch, no GPU: it also builds files by hand); `hat_plan_load` checks a file in full before it allocates
+(csrc/hat_plan_parse.h).
 
-File format (little endian): "HATPLAN1", u32 version = 1, u32 n_buffers, u32 n_calls, u32 n_functions, i32 dims[8] =
+File format (little endian): "HATPLAN1", u32 version = HAT_ABI_VERSION, u32 n_buffers, u32 n_calls, u32 n_functions, i32 dims[8] =
 {B, Cin, H, W, scale, Cout, dtype, 0}; buffers {u32 kind (0 const, 1 scratch, 2 input, 3 output), u32 0, u64 bytes,
 [bytes padded to 8 if const]}; calls {u32 function id, u32 n_args, args {u32 tag, u32 0, payload}} with payloads
 int: i64 | float: f64 | pointer: u32 buffer (0xFFFFFFFF = NULL), u32 0, u64 offset | struct / host array: u32 bytes,
@@ -29,7 +31,7 @@ import torch
 
 from . import _lib
 
-# function ids = index in this list (csrc/hat_plan.cpp FN_NAMES mirrors it)
+# function ids = index in this list (csrc/hat_plan_parse.h HAT_PLAN_FUNCTIONS mirrors it)
 FN_IDS = ["hat_conv", "hat_linear", "hat_conv3x3_small", "hat_cab_fold", "hat_aggr_cab", "hat_ffn", "hat_ffn2", "hat_hab_tail",
           "hat_layernorm", "hat_esc_weights", "hat_eca_scale", "hat_dwconv_gate", "hat_sgfn_gate", "hat_ocab_attention",
           "hat_window_attention", "hat_cab_squeeze", "hat_conv3x3_to_planes", "hat_add_f32", "hat_esc_conv13", "hat_ocab_keybias", "hat_ocab_attention_kb", "hat_ocab_mlp", "hat_ocab_qkv", "hat_hab_tail3", "hat_ocab_attention_log2", "hat_naf_half",
@@ -100,8 +102,58 @@ def _tensors_of(obj, seen, out):
                 _tensors_of(getattr(obj, k, None), seen, out)
 
 
-def export_plan(net, x_shape: Tuple[int, int, int, int], path: str) -> dict:
-    """Record `net`'s forward for inputs of `x_shape` = (B, Cin, H, W) on the module's device and write the plan file."""
+def plan_bytes(dims, buffers, calls, offsets=None) -> bytes:
+    """The file of a plan (format: this module's docstring) from plain values; touches neither torch nor the GPU.
+
+    dims     the eight int32 {B, Cin, H, W, scale, Cout, dtype, 0}
+    buffers  [(kind, nbytes, data)]: data = the bytes of a BUF_CONST buffer (written as they are, padded to 8), else None
+    calls    [(name or function id, [argument ...])] with arguments ("int", v) | ("float", v) | ("ptr", buffer, offset) |
+             ("struct", image, [(field offset, buffer, offset) ...]) | ("host", image) | ("stream",); NULL_BUF = a null pointer
+    offsets  a dict to fill with where things went: "dims", "buffers" (each buffer's header: u32 kind, u32 0, u64 bytes),
+             "calls" ([{"at": the call's header (u32 function id, u32 n_args), "args": each argument's header (u32 tag, u32 0;
+             the payload follows at + 8)}]) and "end" — what a test patches a file by."""
+    pad8 = lambda data: bytes(data) + b"\0" * ((8 - len(data) % 8) % 8)
+    where = {"dims": 24, "buffers": [], "calls": []}
+    out = bytearray()
+    out += b"HATPLAN1" + struct.pack("<4I", _lib.ABI_VERSION, len(buffers), len(calls), len(FN_IDS))
+    out += struct.pack("<8i", *dims)
+    for kind, nbytes, data in buffers:
+        where["buffers"].append(len(out))
+        out += struct.pack("<IIQ", kind, 0, nbytes)
+        if data is not None:
+            out += pad8(data)
+    for fn, args in calls:
+        entry = {"at": len(out), "args": []}
+        where["calls"].append(entry)
+        out += struct.pack("<II", fn if isinstance(fn, int) else FN_IDS.index(fn), len(args))
+        for a in args:
+            entry["args"].append(len(out))
+            if a[0] == "struct":
+                _, image, fixes = a
+                out += struct.pack("<IIII", ARG_STRUCT, 0, len(image), len(fixes)) + pad8(image)
+                for off, bi, bo in fixes:
+                    out += struct.pack("<IIQ", off, bi, bo)
+            elif a[0] == "host":
+                out += struct.pack("<IIII", ARG_HOST, 0, len(a[1]), 0) + pad8(a[1])
+            elif a[0] == "stream":
+                out += struct.pack("<II", ARG_STREAM, 0)
+            elif a[0] == "ptr":
+                out += struct.pack("<IIIIQ", ARG_PTR, 0, a[1], 0, a[2])
+            elif a[0] == "float":
+                out += struct.pack("<IId", ARG_FLOAT, 0, float(a[1]))
+            elif a[0] == "int":
+                out += struct.pack("<IIq", ARG_INT, 0, int(a[1]))
+            else:
+                raise ValueError(f"plan_bytes: unknown argument form {a[0]!r}")
+    where["end"] = len(out)
+    if offsets is not None:
+        offsets.update(where)
+    return bytes(out)
+
+
+def record_plan(net, x_shape: Tuple[int, int, int, int]):
+    """Run ONE forward of `net`'s engine for inputs of `x_shape` = (B, Cin, H, W) on the module's device behind the recorder and
+    return what plan_bytes takes: (dims, buffers, calls), every device pointer resolved to (buffer, offset)."""
     eng = net.engine()
     dev = eng.dev
     if not hasattr(eng, "pe_norm"):
@@ -156,47 +208,46 @@ def export_plan(net, x_shape: Tuple[int, int, int, int], path: str) -> dict:
         raise RuntimeError(f"plan export: device pointer {p:#x} does not belong to the engine's weights, its workspace, the input "
                            f"or the output (a temporary allocated inside forward?)")
 
-    out = bytearray()
-    out += b"HATPLAN1" + struct.pack("<4I", _lib.ABI_VERSION, len(bufs), len(rec.calls), len(FN_IDS))
-    out += struct.pack("<8i", B, Cin, H, W, eng.scale, y.shape[1], eng.dtype, 0)
+    buffers = []
     for b in bufs:
-        out += struct.pack("<IIQ", b["kind"], 0, b["nbytes"])
+        data = None
         if b["kind"] == BUF_CONST:
             raw = torch.empty(b["nbytes"], dtype=torch.uint8, device="cpu")
             raw.copy_(torch.tensor([], dtype=torch.uint8, device=dev).set_(b["storage"], 0, (b["nbytes"],)))
             data = raw.numpy().tobytes()
-            out += data + b"\0" * ((8 - len(data) % 8) % 8)
+        buffers.append((b["kind"], b["nbytes"], data))
+    calls = []
     for name, args in rec.calls:
         sig = _lib.SIGNATURES[name][1]
-        out += struct.pack("<II", FN_IDS.index(name), len(args))
+        out = []
         for k, a in enumerate(args):
-            last = k == len(args) - 1
             if isinstance(a, tuple) and a[0] == "struct":
                 _, stype, image = a
-                fixes = []
-                for off in _pointer_fields(stype):
-                    (p,) = struct.unpack_from("<Q", image, off)
-                    fixes.append((off,) + resolve(p))
-                out += struct.pack("<IIII", ARG_STRUCT, 0, len(image), len(fixes)) + image + b"\0" * ((8 - len(image) % 8) % 8)
-                for off, bi, bo in fixes:
-                    out += struct.pack("<IIQ", off, bi, bo)
+                out.append(("struct", image, [(off,) + resolve(struct.unpack_from("<Q", image, off)[0]) for off in _pointer_fields(stype)]))
             elif isinstance(a, tuple) and a[0] == "host":
-                image = a[1]
-                out += struct.pack("<IIII", ARG_HOST, 0, len(image), 0) + image + b"\0" * ((8 - len(image) % 8) % 8)
-            elif last:                                   # every launch entry point ends with the stream
-                out += struct.pack("<II", ARG_STREAM, 0)
+                out.append(("host", a[1]))
+            elif k == len(args) - 1:                     # every launch entry point ends with the stream
+                out.append(("stream",))
             elif sig[k] is C.c_void_p:
-                bi, bo = resolve(a)
-                out += struct.pack("<IIIIQ", ARG_PTR, 0, bi, 0, bo)
+                out.append(("ptr",) + resolve(a))
             elif sig[k] is C.c_float:
-                out += struct.pack("<IId", ARG_FLOAT, 0, float(a))
+                out.append(("float", a))
             else:
-                out += struct.pack("<IIq", ARG_INT, 0, int(a))
+                out.append(("int", a))
+        calls.append((name, out))
+    return (B, Cin, H, W, eng.scale, y.shape[1], eng.dtype, 0), buffers, calls
+
+
+def export_plan(net, x_shape: Tuple[int, int, int, int], path: str) -> dict:
+    """Record `net`'s forward for inputs of `x_shape` = (B, Cin, H, W) on the module's device and write the plan file."""
+    dims, buffers, calls = record_plan(net, x_shape)
+    out = plan_bytes(dims, buffers, calls)
     with open(path, "wb") as f:
         f.write(out)
-    return {"path": path, "launches": len(rec.calls), "buffers": len(bufs), "file_bytes": len(out),
-            "const_bytes": sum(b["nbytes"] for b in bufs if b["kind"] == BUF_CONST),
-            "scratch_bytes": sum(b["nbytes"] for b in bufs if b["kind"] == BUF_SCRATCH)}
+    return {"path": path, "launches": len(calls), "buffers": len(buffers), "file_bytes": len(out),
+            "const_bytes": sum(n for kind, n, _ in buffers if kind == BUF_CONST),
+            "scratch_bytes": sum(n for kind, n, _ in buffers if kind == BUF_SCRATCH),
+            "functions": sorted({name for name, _ in calls})}
 
 
 class Plan:
