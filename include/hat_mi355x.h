@@ -1058,6 +1058,39 @@ int hat_dysample(const float* rows, const float* init_pos, const float* bias, fl
                  int32_t ld, void* stream);
 
 /*
+ * ESCRealM: what ESCRealM (esc_real_arch.py:478-661) needs beyond ESCReal's launches.  DESIGN.md 4.18.  The heads of UniUpsample
+ * run on hat_conv (HAT_ACT_LRELU is nn.LeakyReLU()'s 0.01, HAT_ACT_LRELU02 the 0.2; HAT_O_PIXSHUF_T with ps_r 2 or 3),
+ * hat_conv3x3_to_planes, hat_linear and hat_dysample as they are.
+ *
+ * hat_unshuffle_pad  check_img_size and PixelUnshuffle(f) of the stem (esc_real_arch.py:606-620, 645-648) in one pass:
+ *   rows[b][yb][xb][c f^2 + f i + j] = x[b][c][refl(f yb + i)][refl(f xb + j)], refl(v) = v < size ? v : 2 size - 2 - v (reflect
+ *   padding on the right and bottom up to a multiple of f).  x (B,3,h,w) fp32 planes -> rows (B, ceil(h/f), ceil(w/f), ld) fp32,
+ *   ld >= 3 f^2; columns >= 3 f^2 of a row are not written.  f is 2 or 4 (HAT_EUNSUPPORTED otherwise).  HAT_EINVAL: a null
+ *   pointer, x == rows, B, h, w < 1, ld < 3 f^2, a pad that is not smaller than the side ((f - h % f) % f > h - 1).
+ *
+ * hat_escrealm_skip  out = [r +] skip(x) for the unshuffled stem: Conv2d(cin, 128, 1) -> depthwise Conv2d(128, 128, 7, padding 3,
+ *   reflect) -> LeakyReLU(0.2) -> Conv2d(128, 64, 1), cin = 12 or 48 (HAT_EUNSUPPORTED otherwise), one launch, 8 x 8 pixels per
+ *   workgroup.  The 14 x 14 halo of x is gathered at the mirrored pixels (a 1x1 conv commutes with reflect padding); the first
+ *   1x1 and the depthwise conv run in fp32 on the halo's hidden map, which stays in LDS; the last 1x1 runs on the MFMA units
+ *   with operands rounded to T.
+ *     x      (B,H,W,ldx) fp32 rows, ldx >= cin, ldx % 4 == 0, 16-byte aligned
+ *     w0     fp32 [128][cin], b0 fp32 [128];  dw fp32 [128][49] (tap = 7 ky + kx), bdw fp32 [128]
+ *     w3     T fragments [4][4][64 lanes][8] of the (64, 128) matrix, hat_escreal_skip's w3;  b3 fp32 [64], 16-byte aligned
+ *     r      optional (B,H,W,ldr) fp32 rows added to the result;  out (B,H,W,ldo) fp32 rows; ldr, ldo >= 64, % 4 == 0
+ *   HAT_EINVAL, before any launch: a null or misaligned pointer, bad leading dimensions, H or W < 4, B < 1 or > 65535, out == x,
+ *   an unknown dtype.
+ *
+ * hat_shuffle_planes  y[b][c][s yy + i][s xx + j] = rows[b][yy][xx][c s^2 + s i + j]: PixelShuffle(s) of rows (B,H,W,ld) fp32
+ *   into (B,3,sH,sW) fp32 planes (hat_esc_shuffle_add without the base image).  HAT_EINVAL for null pointers, rows == y,
+ *   B, H, W < 1, s outside 1..8, ld < 3 s^2.
+ */
+int hat_unshuffle_pad(const float* x, float* rows, int32_t B, int32_t h, int32_t w, int32_t f, int32_t ld, void* stream);
+int hat_escrealm_skip(const float* x, const float* w0, const float* b0, const float* dw, const float* bdw, const void* w3,
+                      const float* b3, const float* r, float* out, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t ldx,
+                      int32_t ldr, int32_t ldo, int32_t dtype, void* stream);
+int hat_shuffle_planes(const float* rows, float* y, int32_t B, int32_t H, int32_t W, int32_t s, int32_t ld, void* stream);
+
+/*
  * ESCFP: what ESCFP (esc_fp_arch.py:247-355; 48 channels, 3 heads of 16) needs beyond ESC's launches.  DESIGN.md 4.16.
  * hat_window_attention_r, hat_esc_conv13, hat_conv and hat_linear serve it as they are.
  *

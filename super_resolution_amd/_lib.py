@@ -252,6 +252,9 @@ SIGNATURES = {
     "hat_esc_shuffle_add": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p]),
     "hat_escreal_skip": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 6 + [C.c_void_p]),
     "hat_dysample": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]),
+    "hat_unshuffle_pad": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_void_p]),
+    "hat_escrealm_skip": (C.c_int, [C.c_void_p] * 9 + [C.c_int32] * 8 + [C.c_void_p]),
+    "hat_shuffle_planes": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_void_p]),
     "hat_escfp_convffn": (C.c_int, [C.POINTER(HatEscConvFfnDesc), C.c_void_p]),
     "hat_escfp_layernorm": (C.c_int, [C.c_void_p] * 4 + [C.c_float, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "hat_escfp_weights": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 7 + [C.c_int32] * 3 + [C.c_void_p]),

@@ -4,7 +4,7 @@ input shape, no torch op on the hot path.  DESIGN.md §4.14 has the launch list.
 The residual stream is fp32 rows (B, H*W, 64); what a 1x1 / 3x3 / 13x13 conv reads is T rows (T = the compute dtype).  Per Block:
     hat_esc_convffn (LN + ConvFFN)  ->  hat_esc_layernorm, to_qkv, hat_window_attention_r, to_out (+ x)
     conv_blocks x [ hat_esc_convffn (+ pool partials), hat_esc_weights, 13x13 conv, aggr (+ x) ]  ->  hat_esc_layernorm, conv_out (+ skip)
-`ESCRealEngine` (§4.15) and `ESCFPEngine` (§4.16: 48 channels, its own ConvFFN / LayerNorm instantiations and weights launch) reuse
+`ESCRealEngine` (§4.15), `ESCRealMEngine` (§4.18) and `ESCFPEngine` (§4.16: 48 channels, its own ConvFFN / LayerNorm instantiations and weights launch) reuse
 the loop through the hooks of `ESCEngine`.
 """
 from __future__ import annotations
@@ -13,7 +13,7 @@ import torch
 
 from . import ops
 from .engine_base import EngineBase
-from .ops import ACT_LRELU02, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T, X_NCHW_F32_MEAN, X_NHWC_F32
+from .ops import ACT_LRELU, ACT_LRELU02, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T, X_NCHW_F32_MEAN, X_NHWC_F32
 from .packing import _ESC
 
 LN_EPS = 1e-6   # esc_arch.py:69
@@ -106,7 +106,17 @@ class ESCEngine(EngineBase):
         return {"rows": f(B, H * W, _r4(3 * s * s)), "y": f(B, 3, H * s, W * s)}
 
     # ------------------------------------------------------------------------------------------
-    def _alloc_workspace(self, B: int, H: int, W: int, tag=None):
+    def _body_size(self, h: int, w: int):
+        """The size the body runs at for an (h, w) frame: the frame's own, unless a stem shrinks it."""
+        return h, w
+
+    def _stem(self, x, w, geo):
+        """feat0 = proj(x)"""
+        ops.conv(self.proj, x, w["feat0"], **geo, dtype=self.dtype, ldx=0, ldo=self.C, x_mode=X_NCHW_F32_MEAN, out_mode=O_NHWC_F32)
+
+    def _alloc_workspace(self, B: int, h: int, w: int, tag=None):
+        """Keyed by the frame's shape (EngineBase._workspace); the buffers have the body's size."""
+        H, W = self._body_size(h, w)
         dev, N, C = self.dev, H * W, self.C
         f = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
         t = lambda *shape: torch.zeros(*shape, dtype=self.tdt, device=dev)
@@ -126,17 +136,18 @@ class ESCEngine(EngineBase):
         taps: a dict that receives clones of the stream after the first ConvFFN, the attention and the first conv block."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError(f"ESC expects (B,3,h,w) input, got {tuple(x.shape)}")
-        B, _, H, W = x.shape
+        B, _, h0, w0 = x.shape
         self._check_batch(B)
+        H, W = self._body_size(h0, w0)
         ws = self.ws
         if (-H) % ws > H - 1 or (-W) % ws > W - 1:
             raise RuntimeError(f"a {H}x{W} frame cannot be reflect-padded to a multiple of window_size {ws}: the padding must be smaller than the frame")
         self._check_frame(H, W)
         x = x.to(torch.float32).contiguous()
-        w, C, dt, N = self._workspace(B, H, W), self.C, self.dtype, H * W
+        w, C, dt, N = self._workspace(B, h0, w0), self.C, self.dtype, H * W
         geo = dict(B=B, H=H, W=W)
         tiles = w["gap"].shape[1]
-        ops.conv(self.proj, x, w["feat0"], **geo, dtype=dt, ldx=0, ldo=C, x_mode=X_NCHW_F32_MEAN, out_mode=O_NHWC_F32)
+        self._stem(x, w, geo)
         cur = w["feat0"]
         for bi, b in enumerate(self.blocks):
             xa, xb = [s for s in w["s"] if s is not cur][:2]
@@ -247,6 +258,182 @@ class ESCRealEngine(ESCEngine):
                                   dtype=dt)
         else:
             ops.conv(self.out, w["u3"], w["y"], B=B, H=4 * H, W=4 * W, dtype=dt, ldx=C, ldo=0, out_mode=O_NCHW_F32)
+        return w["y"]
+
+
+class ESCRealMEngine(ESCRealEngine):
+    """ESCRealM (esc_real_arch.py:478-661): ESCReal's body and residual, with
+        unshuffle mode   hat_unshuffle_pad (reflect pad + PixelUnshuffle(f) -> fp32 rows of 3 f^2 channels)  ->  proj on those rows,
+                         hat_escrealm_skip in place of hat_escreal_skip; the body runs at ceil(h/f) x ceil(w/f), the head is x4 and the
+                         output is the (s h, s w) corner of its buffer
+        plain mode       ESCReal's stem
+    and UniUpsample's five heads at the internal scale S (4 in unshuffle mode, else upscaling_factor):
+        conv                 to_img.0 -> planes (the row-sweep kernel where it applies)
+        pixelshuffledirect   to_img.0 -> fp32 rows, hat_shuffle_planes
+        pixelshuffle         to_img.0 (+ LeakyReLU 0.01), one or two 3x3 mid -> r^2 mid with the pixel shuffle in the store, 3x3 mid -> 3
+        nearest+conv         per step conv -> nearest x r -> LeakyReLU 0.2 as ONE conv 64 -> 64 r^2 (rows repeated) with the shuffle in
+                             the store and the activation in the epilogue; then conv (+ LeakyReLU 0.2), conv -> planes
+        dysample             [to_img.0 (+ LeakyReLU 0.01) when mid_dim != dim,] ESCReal's pointwise fold and hat_dysample
+    DESIGN.md §4.18."""
+
+    def _check_cfg(self, cfg):
+        super()._check_cfg(cfg)
+        s, up, mid = int(cfg["upscaling_factor"]), cfg["upsampler"], int(cfg["mid_dim"])
+        S = int(cfg["head_scale"])
+        if up not in ops.UNI_UPSAMPLERS:
+            raise ValueError(f"ESCRealM with upsampler={up!r} is not supported: expected one of {ops.UNI_UPSAMPLERS}")
+        if s not in (1, 2, 3, 4) or S not in (1, 2, 3, 4):
+            raise ValueError(f"ESCRealM with upscaling_factor={s} is not supported: the heads are built for 1, 2, 3 and 4")
+        if cfg["unshuffle"] and up == "conv":
+            raise ValueError("ESCRealM with upsampler='conv' behind the unshuffled stem is not supported: its output would be smaller than the frame")
+        if up == "pixelshuffle" and S > 1 and (mid < 16 or mid % 16):
+            raise ValueError(f"ESCRealM with upsampler='pixelshuffle' and mid_dim={mid} is not supported: mid_dim must be a multiple of 16")
+        if up == "dysample" and S > 1 and mid not in (48, 64):
+            raise ValueError(f"ESCRealM with upsampler='dysample' and mid_dim={mid} is not supported: built for mid_dim 48 and 64")
+
+    def __init__(self, cfg, sd, device, compute_dtype="bf16"):
+        self.f = int(cfg["unshuffle"])
+        if self.f:   # the plain-named keys the shared packing reads
+            sd = dict(sd)
+            sd["proj.weight"], sd["proj.bias"] = sd["proj.1.weight"], sd["proj.1.bias"]
+        super().__init__(cfg, sd, device, compute_dtype)
+
+    def _pack_head(self, sd):
+        dt, dev, cfg = self.dtype, self.dev, self.cfg
+        self.dysample = False   # (ESCRealEngine's flag; this class dispatches on self.head)
+        self.skip = ops.pack_escrealm_skip(sd, "skip", dt, dev) if self.f else ops.pack_escreal_skip(sd, "skip", dt, dev)
+        S = self.S = int(cfg["head_scale"])
+        self.out_scale = S
+        self.head = "conv" if S == 1 else cfg["upsampler"]
+        mid = self.mid = int(cfg["mid_dim"])
+        conv = lambda i: ops.pack_conv_weight(sd[f"to_img.{i}.weight"], sd[f"to_img.{i}.bias"], dt, dev)
+        self.out_sweep = None
+        if self.head == "conv":
+            self.out_scale = 1
+            self._pack_out(sd, 0)
+        elif self.head == "pixelshuffledirect":
+            self.direct = conv(0)
+        elif self.head == "pixelshuffle":
+            self.pre = conv(0)
+            self.steps = [(2, 3)] if S == 3 else [(2 + 2 * k, 2) for k in range(S // 2)]   # (index in the Sequential, r)
+            self.ups = [ops.pack_pixshuf_conv(sd[f"to_img.{i}.weight"], sd[f"to_img.{i}.bias"], r, dt, dev) for i, r in self.steps]
+            self.out = conv(self.steps[-1][0] + 2)
+        elif self.head == "nearest+conv":
+            self.steps = [(0, 3)] if S == 3 else [(3 * k, 2) for k in range(S // 2)]
+            self.ups = [ops.pack_conv_nearest(sd[f"to_img.{i}.weight"], sd[f"to_img.{i}.bias"], r, dt, dev) for i, r in self.steps]
+            i = self.steps[-1][0] + 3
+            self.hr = conv(i)
+            self._pack_out(sd, i + 2)
+        else:   # dysample
+            p = "to_img.0"
+            self.pre = None
+            if mid != self.C:
+                self.pre, p = conv(0), "to_img.2"
+            f32 = lambda k: sd[k].detach().to(torch.float32).cpu()
+            wd, bd = ops.dysample_fold(f32(p + ".offset.weight"), f32(p + ".offset.bias"), f32(p + ".scope.weight"), f32(p + ".end_conv.weight"))
+            self.dys = ops.pack_pointwise(wd, bd, dt, dev)
+            self.dys_ld = wd.shape[0]
+            self.dys_init = f32(p + ".init_pos").reshape(-1).contiguous().to(dev)
+            self.dys_bias = f32(p + ".end_conv.bias").contiguous().to(dev)
+
+    def _pack_out(self, sd, i: int):
+        """The 64 -> 3 conv into planes: hat_conv, and the row-sweep kernel where HATEngine takes it for conv_last."""
+        self.out = ops.pack_conv_weight(sd[f"to_img.{i}.weight"], sd[f"to_img.{i}.bias"], self.dtype, self.dev)
+        if ops.conv3x3_to_planes_supported(3, 64, 16, self.dtype):
+            self.out_sweep = ops.pack_cab_squeeze(sd[f"to_img.{i}.weight"], sd[f"to_img.{i}.bias"], self.dev)
+
+    def _body_size(self, h, w):
+        f = self.f
+        return (-(-h // f), -(-w // f)) if f else (h, w)
+
+    def _alloc_workspace(self, B, h, w, tag=None):
+        ws = super()._alloc_workspace(B, h, w, tag)
+        if self.f:
+            H, W = self._body_size(h, w)
+            ws["xr"] = torch.zeros(B, H * W, 3 * self.f ** 2, dtype=torch.float32, device=self.dev)
+        return ws
+
+    def _head_buffers(self, B, H, W, f, t):
+        S, N, hd = self.out_scale, H * W, self.head
+        w = {"y": f(B, 3, H * S, W * S)}
+        if hd == "pixelshuffledirect":
+            w["rows"] = f(B, N, _r4(3 * S * S))
+        elif hd in ("pixelshuffle", "nearest+conv"):
+            ch, npx, w["u"] = (self.mid if hd == "pixelshuffle" else 64), N, []
+            for _, r in self.steps:   # the map after each upsampling step
+                npx *= r * r
+                w["u"].append(t(B, npx, ch))
+            if hd == "pixelshuffle":
+                w["pre"] = t(B, N, ch)
+            else:
+                w["hr"] = t(B, npx, 64)
+        elif hd == "dysample":
+            if self.pre is not None:
+                w["pre"] = t(B, N, self.mid)
+            w["rows"] = f(B, N, self.dys_ld)
+        return w
+
+    def _check_frame(self, H, W):
+        if H < 4 or W < 4:
+            raise RuntimeError(f"a {H}x{W} map cannot be reflect-padded by 3 for the skip branch's 7x7 conv: a side of at least 4 is needed"
+                               + (f" behind the /{self.f} unshuffle" if self.f else ""))
+
+    def _stem(self, x, w, geo):
+        if not self.f:
+            return super()._stem(x, w, geo)
+        B, _, h, wd = x.shape
+        cin = 3 * self.f ** 2
+        ops.unshuffle_pad(x, w["xr"], B=B, h=h, w=wd, f=self.f, ld=cin)
+        ops.conv(self.proj, w["xr"], w["feat0"], **geo, dtype=self.dtype, ldx=cin, ldo=self.C, x_mode=X_NHWC_F32, out_mode=O_NHWC_F32)
+
+    def _to_planes(self, src, y, B, H, W):
+        C, dt = self.C, self.dtype
+        if self.out_sweep is not None and self.out.cin == 64 and W % 16 == 0:
+            wpk, b8 = self.out_sweep
+            ops.conv3x3_to_planes(src, wpk, b8, y, B=B, H=H, W=W, C_=C, ldx=C, n_out=3, out_scale=1.0, mean=(0.0, 0.0, 0.0, 0.0), dtype=dt)
+        else:
+            ops.conv(self.out, src, y, B=B, H=H, W=W, dtype=dt, ldx=self.out.cin, ldo=0, out_mode=O_NCHW_F32)
+
+    def _tail(self, x, w, cur, geo):
+        C, dt, S, hd = self.C, self.dtype, self.out_scale, self.head
+        B, H, W = geo["B"], geo["H"], geo["W"]
+        sk = next(s for s in w["s"] if s is not cur)
+        if self.f:
+            ops.escrealm_skip(self.skip, w["xr"], sk, **geo, dtype=dt, ldx=w["xr"].shape[2], r=w["feat0"], ldr=C, ldo=C)
+        else:
+            ops.escreal_skip(self.skip, x, sk, **geo, dtype=dt, r=w["feat0"], ldr=C, ldo=C)
+        ops.conv(self.last, cur, w["n"], **geo, dtype=dt, ldx=C, ldo=C, x_mode=X_NHWC_F32, r1=sk, ldr1=C)
+        if hd == "conv":
+            self._to_planes(w["n"], w["y"], B, H, W)
+        elif hd == "pixelshuffledirect":
+            ld = w["rows"].shape[2]
+            ops.conv(self.direct, w["n"], w["rows"], **geo, dtype=dt, ldx=C, ldo=ld, out_mode=O_NHWC_F32, n_store=ld)
+            ops.shuffle_planes(w["rows"], w["y"], **geo, s=S, ld=ld)
+        elif hd in ("pixelshuffle", "nearest+conv"):
+            src, ch, hh, ww = w["n"], C, H, W
+            if hd == "pixelshuffle":
+                ch = self.mid
+                ops.conv(self.pre, w["n"], w["pre"], **geo, dtype=dt, ldx=C, ldo=ch, act=ACT_LRELU)
+                src = w["pre"]
+            for (_, r), pw, u in zip(self.steps, self.ups, w["u"]):
+                ops.conv(pw, src, u, B=B, H=hh, W=ww, dtype=dt, ldx=ch, ldo=ch, out_mode=O_PIXSHUF_T, ps_r=r,
+                         act=ACT_LRELU02 if hd == "nearest+conv" else ops.ACT_NONE)
+                src, hh, ww = u, hh * r, ww * r
+            if hd == "nearest+conv":
+                ops.conv(self.hr, src, w["hr"], B=B, H=hh, W=ww, dtype=dt, ldx=C, ldo=C, act=ACT_LRELU02)
+                src = w["hr"]
+            self._to_planes(src, w["y"], B, hh, ww)
+        else:
+            src, ch = w["n"], C
+            if self.pre is not None:
+                ch = self.mid
+                ops.conv(self.pre, w["n"], w["pre"], **geo, dtype=dt, ldx=C, ldo=ch, act=ACT_LRELU)
+                src = w["pre"]
+            self._lin(self.dys, src, w["rows"], geo=geo, ldx=ch, ldo=self.dys_ld, out_mode=O_NHWC_F32)
+            ops.dysample(w["rows"], self.dys_init, self.dys_bias, w["y"], **geo, s=S, ld=self.dys_ld)
+        if self.f:   # the reference's crop to (s h, s w): a corner of the x4 buffer
+            s = self.scale
+            return w["y"][:, :, :s * x.shape[2], :s * x.shape[3]]
         return w["y"]
 
 

@@ -18,6 +18,7 @@ from ._lib import (ACT_GELU, ACT_LRELU, ACT_LRELU02, ACT_NONE, HAT_BF16, HAT_F32
 from .packing import (ESC_HID_PAD, FP16_SAFE, KC, NAF_WIDTHS, TORCH_DTYPE, PackedConv, PackedEscFfn, PackedFFN, PackedMlp, PackedNafBlock, choose_nt,  # noqa: F401
                       esc_geo_ensemble, pack_esc_convffn, PackedEscRealSkip, ESCFP_HID_PAD, PackedEscFpLk, bicubic_phase_table, escfp_rank1_fold,
                       pack_escfp_convffn, pack_escfp_lk, dysample_fold, pack_escreal_skip, pack_nearest_conv,
+                      UNI_UPSAMPLERS, PackedEscRealMSkip, conv_nearest_fold, pack_conv_nearest, pack_escrealm_skip, pack_pixshuf_conv, pixshuf_perm,
                       choose_nt_linear, naf_ffn_fold, naf_frags, pack_naf_block,
                       ffn_fp16_range_bound, pack_cab_squeeze, pack_cab_w2f, pack_conv_weight, pack_ffn, pack_ffn2, pack_ffn3,
                       pack_linear_weight, pack_ocab_mlp, pack_ocab_qkv, pack_pointwise)
@@ -383,6 +384,35 @@ def dysample(rows, init_pos, bias, y, *, B: int, H: int, W: int, s: int, ld: int
     _timed("dysample_kernel", 0.0, lambda: _lib.check(
         lib.hat_dysample(_ptr(rows), _ptr(init_pos), _ptr(bias), _ptr(y), B, H, W, s, ld, _stream()), "hat_dysample"),
         tag=f"dysample x{s} {H}x{W}", nbytes=4.0 * B * H * W * (ld + 3 * s * s))
+
+
+# ------------------------------------------------------------------------------------------------
+# ESCRealM (hat_unshuffle_pad / hat_escrealm_skip / hat_shuffle_planes)
+# ------------------------------------------------------------------------------------------------
+def unshuffle_pad(x, rows, *, B: int, h: int, w: int, f: int, ld: int):
+    """rows (B, ceil(h/f) * ceil(w/f), ld) fp32 = PixelUnshuffle(f) of x (B,3,h,w) reflect-padded right / bottom to a multiple of f."""
+    lib = _lib.load()
+    _timed("unshuffle_pad_kernel", 0.0, lambda: _lib.check(
+        lib.hat_unshuffle_pad(_ptr(x), _ptr(rows), B, h, w, f, ld, _stream()), "hat_unshuffle_pad"),
+        tag=f"unshuffle /{f} {h}x{w}", nbytes=4.0 * B * 3 * (h * w + f * f * (-(-h // f)) * (-(-w // f))))
+
+
+def escrealm_skip(ps: PackedEscRealMSkip, x, out, *, B: int, H: int, W: int, dtype: int, ldx: int, r=None, ldr: int = 64, ldo: int = 64):
+    """out (fp32 rows) = [r +] skip(x), x (B,H*W,ldx) fp32 rows of 12 or 48 unshuffled channels (hat_escrealm_skip)."""
+    lib = _lib.load()
+    npx = float(B * H * W)
+    _timed(f"escrealm_skip_kernel<{_TNAME[dtype]}, {ps.cin}>", 2.0 * npx * 128 * (ps.cin + 49 + 64), lambda: _lib.check(
+        lib.hat_escrealm_skip(_ptr(x), _ptr(ps.w0), _ptr(ps.b0), _ptr(ps.dw), _ptr(ps.bdw), _ptr(ps.w3), _ptr(ps.b3), _ptr(r), _ptr(out),
+                              B, H, W, ps.cin, ldx, ldr, ldo, dtype, _stream()), "hat_escrealm_skip"),
+        tag=f"skip {ps.cin}->128->64 {H}x{W}{' r' if r is not None else ''}", nbytes=npx * (4 * ps.cin + 256 + (256 if r is not None else 0)))
+
+
+def shuffle_planes(rows, y, *, B: int, H: int, W: int, s: int, ld: int):
+    """y (B,3,sH,sW) fp32 = pixel_shuffle(rows (B,H,W,ld) fp32, s) (hat_shuffle_planes)."""
+    lib = _lib.load()
+    _timed("shuffle_planes_kernel", 0.0, lambda: _lib.check(
+        lib.hat_shuffle_planes(_ptr(rows), _ptr(y), B, H, W, s, ld, _stream()), "hat_shuffle_planes"),
+        tag=f"shuffle x{s} {H}x{W}", nbytes=4.0 * B * H * W * (ld + 3 * s * s))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -607,3 +607,61 @@ def pack_nearest_conv(weight, bias, dtype: int, device) -> PackedConv:
     o = weight.shape[0]
     n = torch.arange(4 * o)
     return pack_conv_weight(wf, bf, dtype, device, out_perm=(n % o) * 4 + n // o)
+
+
+# ------------------------------------------------------------------------------------------------
+# ESCRealM (esc_real_arch.py:478-661): the unshuffled stem's skip branch and the heads of UniUpsample
+# ------------------------------------------------------------------------------------------------
+UNI_UPSAMPLERS = ("conv", "pixelshuffledirect", "pixelshuffle", "nearest+conv", "dysample")   # SampleMods, in MetaUpsample's index order
+
+
+class PackedEscRealMSkip:
+    """The skip branch over 12 or 48 unshuffled channels in hat_escrealm_skip's layouts (include/hat_mi355x.h "ESCRealM"): w0 fp32
+    [128][cin], b0 [128], dw fp32 [128][49], bdw [128], w3 T fragments [4][4][64][8] of the (64, 128) 1x1, b3 [64]."""
+    __slots__ = ("cin", "w0", "b0", "dw", "bdw", "w3", "b3")
+
+
+def pack_escrealm_skip(sd, p: str, dtype: int, device) -> PackedEscRealMSkip:
+    """sd[p + '.1.weight'] ... of ESCRealM.skip behind its PixelUnshuffle (esc_real_arch.py:613-619) -> PackedEscRealMSkip."""
+    w0, dw, w3 = _f32(sd[p + ".1.weight"]), _f32(sd[p + ".2.weight"]), _f32(sd[p + ".4.weight"])
+    cin = w0.shape[1]
+    if cin not in (12, 48) or tuple(w0.shape) != (128, cin, 1, 1) or tuple(dw.shape) != (128, 1, 7, 7) or tuple(w3.shape) != (64, 128, 1, 1):
+        raise ValueError(f"skip branch {tuple(w0.shape)} / {tuple(dw.shape)} / {tuple(w3.shape)} is not supported: hat_escrealm_skip is "
+                         "built for 12 or 48 -> 128 (1x1), depthwise 7x7, 128 -> 64 (1x1)")
+    f = PackedEscRealMSkip()
+    f.cin = cin
+    f.w0, f.b0 = w0.reshape(128, cin).contiguous().to(device), _f32(sd[p + ".1.bias"]).contiguous().to(device)
+    f.dw, f.bdw = dw.reshape(128, 49).contiguous().to(device), _f32(sd[p + ".2.bias"]).contiguous().to(device)
+    f.w3 = frags(w3.reshape(64, 128)).to(TORCH_DTYPE[dtype]).contiguous().to(device)
+    f.b3 = _f32(sd[p + ".4.bias"]).contiguous().to(device)
+    return f
+
+
+def pixshuf_perm(o: int, r: int) -> torch.Tensor:
+    """Row order of a conv whose o = r^2 c outputs feed PixelShuffle(r) through HAT_O_PIXSHUF_T: packed row ij * c + cc holds
+    nn.PixelShuffle's channel cc * r^2 + ij."""
+    n = torch.arange(o)
+    cps = o // (r * r)
+    return (n % cps) * (r * r) + n // cps
+
+
+def conv_nearest_fold(w, b, r: int):
+    """Conv2d(I, O, 3, 1, 1) -> nn.Upsample(scale_factor=r) (nearest) as Conv2d(I, r^2 O, 3, 1, 1) -> PixelShuffle(r): every one of
+    the r^2 output pixels of an LR pixel is that pixel's conv result, so output channel c r^2 + ij repeats row c.  Exact: no
+    arithmetic changes, and a pointwise activation behind the nearest step acts on the same values in the conv's epilogue.
+    (UniUpsample's "nearest+conv" puts the conv FIRST, esc_real_arch.py:514-544; ESCReal's own head upsamples first, which is
+    nearest_conv_fold.)  -> (weight (r^2 O, I, 3, 3), bias (r^2 O,))."""
+    return w.repeat_interleave(r * r, 0), b.repeat_interleave(r * r)
+
+
+def pack_conv_nearest(weight, bias, r: int, dtype: int, device) -> PackedConv:
+    """3x3 conv + nearest x r -> the folded conv for hat_conv with HAT_O_PIXSHUF_T (ps_r = r)."""
+    if r not in (2, 3):
+        raise ValueError(f"nearest x{r} is not supported: the fold is built for 2 and 3")
+    wf, bf = conv_nearest_fold(_f32(weight), _f32(bias), r)
+    return pack_conv_weight(wf, bf, dtype, device, out_perm=pixshuf_perm(wf.shape[0], r))
+
+
+def pack_pixshuf_conv(weight, bias, r: int, dtype: int, device) -> PackedConv:
+    """Conv2d(I, r^2 C, 3, 1, 1) in front of nn.PixelShuffle(r) for hat_conv with HAT_O_PIXSHUF_T (ps_r = r)."""
+    return pack_conv_weight(weight, bias, dtype, device, out_perm=pixshuf_perm(weight.shape[0], r))
