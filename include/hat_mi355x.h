@@ -1091,6 +1091,46 @@ int hat_escrealm_skip(const float* x, const float* w0, const float* b0, const fl
 int hat_shuffle_planes(const float* rows, float* y, int32_t B, int32_t H, int32_t W, int32_t s, int32_t ld, void* stream);
 
 /*
+ * ESC-LTE: the head of the arbitrary-scale model (esc_arb/models/lte.py:34-105; the encoder is ESC's launches).  DESIGN.md 4.19.
+ *
+ * hat_lte_query  one launch per query set: gather + Fourier basis + the 256 -> 256 -> 256 -> 256 -> 3 MLP + area-weighted sum +
+ *   bilinear base image.  For a query with coordinate c = (cy, cx) in [-1, 1] and cell (ky, kx) over a feature map of H x W, and for
+ *   the four shifts (vy, vx) in the order (-1,-1), (-1,1), (1,-1), (1,1):
+ *     1. c' = clamp(c + fp32(v / (H, W) + 1e-6), -1 + 1e-6, 1 - 1e-6)
+ *     2. (i, j) = the pixel grid_sample(mode='nearest', align_corners=False) picks: rint(((c' + 1) n - 1) / 2), half to even,
+ *        every product and sum rounded on its own as torch rounds them
+ *     3. q = the pixel's centre as make_coord gives it: fp32(-1 + 1/n) + fp32(2/n) * i
+ *     4. rel = (c - q) * (H, W)
+ *     5. f_k = (freq[2k] rel_y + freq[2k+1] rel_x) + (Wp[k][0] ky H + Wp[k][1] kx W),  k < 128
+ *     6. the MLP input: coef[0:128] cos(pi f) | coef[128:256] sin(pi f)
+ *     7. pred = Linear + ReLU three times, then Linear to 3
+ *     8. area = |rel_y rel_x| + 1e-9
+ *   out = sum_n pred_n area_{3-n} / sum(area)  +  grid_sample(inp, c, 'bilinear', padding_mode='border', align_corners=False),
+ *   then out * out_a + out_b.
+ *     coef, freq   fp32 rows [H*W][ldc / ldf] of the 256 coef / freq channels at each feature pixel; ldc, ldf >= 256, % 4 == 0,
+ *                  16-byte aligned (the two halves of one 512-wide row are fine)
+ *     inp          (3,H,W) fp32 planes, the network's normalised input
+ *     phase        fp32 [128][2] (phase.weight), 16-byte aligned
+ *     w1, w2, w3   T fragments [16][8][64 lanes][8] of the (256, 256) matrices imnet.layers.{0,2,4}.weight: element (t, ks, l, j) =
+ *                  W[16 t + (l & 15)][32 ks + 8 (l >> 4) + j];  b1, b2, b3 fp32 [256], 16-byte aligned
+ *     w4, b4       fp32 [3][256] and [3] (imnet.layers.6): the last layer runs in fp32 from the third layer's accumulators
+ *   Explicit mode: coord, cell fp32 (Q,2) in (y, x) order, Q >= 1; out (Q,3) fp32 rows; gh, gw, cell_y, cell_x ignored.
+ *   Grid mode: coord == cell == NULL; the queries are the pixel centres of a (gh, gw) image, coordinate of row r =
+ *     fp32(-1 + 1/gh) + fp32(2/gh) * r (make_coord's operation order), every query with the cell (cell_y, cell_x); out (3,gh,gw)
+ *     fp32 planes.  The output is tiled 4 x 8 so that the queries of a workgroup share feature pixels.
+ *   dtype HAT_F32: every step in fp32 (sincospi by the device library), the exact path.  HAT_BF16: the three 256 x 256 layers on
+ *     v_mfma_f32_16x16x32_bf16 with fp32 accumulation; the basis is computed in fp32 (sin / cos by v_sin_f32 / v_cos_f32 on the
+ *     exact fraction of f / 2) and rounded once when it becomes the first layer's operand.
+ *   32 queries (128 MLP rows) per workgroup; the last tile may be ragged.  HAT_EINVAL, before any launch: a null or misaligned
+ *   pointer, exactly one of coord / cell null, H, W, Q, gh or gw < 1, H W or gh gw > 2^31 - 1, bad leading dimensions, out == inp,
+ *   an unknown dtype.
+ */
+int hat_lte_query(const float* coef, const float* freq, int32_t ldc, int32_t ldf, const float* inp, int32_t H, int32_t W,
+                  const float* phase, const void* w1, const float* b1, const void* w2, const float* b2, const void* w3, const float* b3,
+                  const float* w4, const float* b4, const float* coord, const float* cell, int64_t Q, int32_t gh, int32_t gw,
+                  float cell_y, float cell_x, float out_a, float out_b, float* out, int32_t dtype, void* stream);
+
+/*
  * ESCFP: what ESCFP (esc_fp_arch.py:247-355; 48 channels, 3 heads of 16) needs beyond ESC's launches.  DESIGN.md 4.16.
  * hat_window_attention_r, hat_esc_conv13, hat_conv and hat_linear serve it as they are.
  *

@@ -259,6 +259,8 @@ SIGNATURES = {
     "hat_escfp_layernorm": (C.c_int, [C.c_void_p] * 4 + [C.c_float, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "hat_escfp_weights": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 7 + [C.c_int32] * 3 + [C.c_void_p]),
     "hat_escfp_shuffle_bicubic": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]),
+    "hat_lte_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 11
+                      + [C.c_int64, C.c_int32, C.c_int32] + [C.c_float] * 4 + [C.c_void_p, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

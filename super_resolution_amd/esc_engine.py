@@ -4,7 +4,8 @@ input shape, no torch op on the hot path.  DESIGN.md §4.14 has the launch list.
 The residual stream is fp32 rows (B, H*W, 64); what a 1x1 / 3x3 / 13x13 conv reads is T rows (T = the compute dtype).  Per Block:
     hat_esc_convffn (LN + ConvFFN)  ->  hat_esc_layernorm, to_qkv, hat_window_attention_r, to_out (+ x)
     conv_blocks x [ hat_esc_convffn (+ pool partials), hat_esc_weights, 13x13 conv, aggr (+ x) ]  ->  hat_esc_layernorm, conv_out (+ skip)
-`ESCRealEngine` (§4.15), `ESCRealMEngine` (§4.18) and `ESCFPEngine` (§4.16: 48 channels, its own ConvFFN / LayerNorm instantiations and weights launch) reuse
+`ESCRealEngine` (§4.15), `ESCRealMEngine` (§4.18), `ESCLTEEngine` (§4.19: the encoder of the arbitrary-scale model; its head is one
+kernel, `hat_lte_query`) and `ESCFPEngine` (§4.16: 48 channels, its own ConvFFN / LayerNorm instantiations and weights launch) reuse
 the loop through the hooks of `ESCEngine`.
 """
 from __future__ import annotations
@@ -488,3 +489,67 @@ class ESCFPEngine(ESCEngine):
         ops.conv(self.to_img, w["n"], w["rows"], **geo, dtype=dt, ldx=C, ldo=ld, out_mode=O_NHWC_F32, n_store=ld)
         ops.escfp_shuffle_bicubic(w["rows"], x, self.ptab, w["y"], B=B, H=H, W=W, s=self.scale, ld=ld)
         return w["y"]
+
+
+class ESCLTEEngine(ESCEngine):
+    """ESC-LTE (esc_arb/models/lte.py, esc.py): ESC's Block loop as the encoder (no to_img; the geometric filter ensemble on every
+    forward), then
+        last (+ feat0)  ->  hat_conv 64 -> 512 (coef | freq, fp32 rows)         gen_feat, kept in the workspace of the shape
+        hat_lte_query                                                           query / query_grid, any number of times
+    The state dict is the reference LTE's: the encoder's keys under `encoder.`, the head's beside them.  DESIGN.md §4.19."""
+
+    def __init__(self, cfg, sd, device, compute_dtype="bf16"):
+        sd = dict(sd)
+        for k in [k for k in sd if k.startswith("encoder.")]:   # the plain-named keys the shared packing reads
+            sd[k[len("encoder."):]] = sd[k]
+        self._feat_ws = None
+        super().__init__(dict(cfg, upscaling_factor=1), sd, device, compute_dtype)
+
+    def _check_cfg(self, cfg):
+        super()._check_cfg(cfg)
+        hd, hl = int(cfg.get("hidden_dim", 256)), tuple(int(v) for v in cfg.get("hidden_list", (256, 256, 256)))
+        if hd != ops.LTE_HIDDEN or hl != (ops.LTE_HIDDEN,) * 3:
+            raise ValueError(f"ESC-LTE with hidden_dim={hd}, hidden_list={hl} is not supported: hat_lte_query is built for hidden_dim "
+                             f"{ops.LTE_HIDDEN} and hidden_list {(ops.LTE_HIDDEN,) * 3}")
+
+    def _pack_head(self, sd):
+        self.lte = ops.pack_lte(sd, self.dtype, self.dev)
+
+    def _head_buffers(self, B, H, W, f, t):
+        return {"cf": f(B, H * W, 2 * ops.LTE_HIDDEN), "x": f(B, 3, H, W)}
+
+    def _tail(self, x, w, cur, geo):
+        """last (+ feat0); coef | freq as one 512-wide conv into fp32 rows; the input kept for the bilinear base      lte.py:23-32"""
+        C, dt = self.C, self.dtype
+        ops.conv(self.last, cur, w["n"], **geo, dtype=dt, ldx=C, ldo=C, x_mode=X_NHWC_F32, r1=w["feat0"], ldr1=C)
+        ld = w["cf"].shape[2]
+        ops.conv(self.lte.taps, w["n"], w["cf"], **geo, dtype=dt, ldx=C, ldo=ld, out_mode=O_NHWC_F32, n_store=ld)
+        w["x"].copy_(x)
+        self._feat_ws = (w, geo["H"], geo["W"])
+        return w["n"]
+
+    def _query(self, out, **kw):
+        if self._feat_ws is None:
+            raise RuntimeError("ESC-LTE: query before gen_feat: there are no features to query")
+        w, H, W = self._feat_ws
+        hd = ops.LTE_HIDDEN
+        with self._lock, torch.cuda.device(self.dev):
+            ops.lte_query(self.lte, w["cf"], w["cf"].view(-1)[hd:], w["x"], out, H=H, W=W, ldc=2 * hd, ldf=2 * hd, dtype=self.dtype, **kw)
+        return out
+
+    def query(self, coord: torch.Tensor, cell: torch.Tensor) -> torch.Tensor:
+        """coord, cell (Q,2) fp32 on the engine's device -> (Q,3) fp32 (a fresh tensor) against the last gen_feat."""
+        for name, t in (("coord", coord), ("cell", cell)):
+            if t.device != self.dev or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 2:
+                raise RuntimeError(f"ESC-LTE: {name} must be a (Q,2) fp32 tensor on {self.dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        if coord.shape != cell.shape:
+            raise RuntimeError(f"ESC-LTE: coord {tuple(coord.shape)} and cell {tuple(cell.shape)} differ in shape")
+        out = torch.empty(coord.shape[0], 3, dtype=torch.float32, device=self.dev)
+        if coord.shape[0] == 0:
+            return out
+        return self._query(out, coord=coord.contiguous(), cell=cell.contiguous())
+
+    def query_grid(self, h: int, w: int, cell_yx, out_affine=(1.0, 0.0)) -> torch.Tensor:
+        """The make_coord grid of an (h, w) image, every query with the cell cell_yx -> (3,h,w) fp32 planes * a + b (a fresh tensor)."""
+        out = torch.empty(3, h, w, dtype=torch.float32, device=self.dev)
+        return self._query(out, grid=(h, w), cell_yx=cell_yx, out_affine=out_affine)

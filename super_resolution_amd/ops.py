@@ -18,6 +18,7 @@ from ._lib import (ACT_GELU, ACT_LRELU, ACT_LRELU02, ACT_NONE, HAT_BF16, HAT_F32
 from .packing import (ESC_HID_PAD, FP16_SAFE, KC, NAF_WIDTHS, TORCH_DTYPE, PackedConv, PackedEscFfn, PackedFFN, PackedMlp, PackedNafBlock, choose_nt,  # noqa: F401
                       esc_geo_ensemble, pack_esc_convffn, PackedEscRealSkip, ESCFP_HID_PAD, PackedEscFpLk, bicubic_phase_table, escfp_rank1_fold,
                       pack_escfp_convffn, pack_escfp_lk, dysample_fold, pack_escreal_skip, pack_nearest_conv,
+                      LTE_HIDDEN, PackedLte, pack_lte,
                       UNI_UPSAMPLERS, PackedEscRealMSkip, conv_nearest_fold, pack_conv_nearest, pack_escrealm_skip, pack_pixshuf_conv, pixshuf_perm,
                       choose_nt_linear, naf_ffn_fold, naf_frags, pack_naf_block,
                       ffn_fp16_range_bound, pack_cab_squeeze, pack_cab_w2f, pack_conv_weight, pack_ffn, pack_ffn2, pack_ffn3,
@@ -442,6 +443,46 @@ def escfp_shuffle_bicubic(rows, x, ptab, y, *, B: int, H: int, W: int, s: int, l
     _timed("escfp_shuffle_bicubic_kernel", 0.0, lambda: _lib.check(
         lib.hat_escfp_shuffle_bicubic(_ptr(rows), _ptr(x), _ptr(ptab), _ptr(y), B, H, W, s, ld, _stream()), "hat_escfp_shuffle_bicubic"),
         tag=f"shuffle+bicubic x{s} {H}x{W}", nbytes=4.0 * B * H * W * (ld + 3 + 3 * s * s))
+
+
+# ------------------------------------------------------------------------------------------------
+# ESC-LTE (hat_lte_query)
+# ------------------------------------------------------------------------------------------------
+LTE_TILE = 32   # queries per workgroup of hat_lte_query
+
+
+def lte_query(pl: PackedLte, coef, freq, inp, out, *, H: int, W: int, ldc: int, ldf: int, dtype: int, coord=None, cell=None,
+              grid=None, cell_yx=(0.0, 0.0), out_affine=(1.0, 0.0)):
+    """The LTE head on the rows coef / freq (H*W, ld) fp32 of a feature map and the normalised input inp (3,H,W) (hat_lte_query).
+    Explicit mode: coord, cell (Q,2) fp32 -> out (Q,3).  Grid mode: grid=(h, w), cell_yx the one cell -> out (3,h,w) planes.
+    out_affine=(a, b): out * a + b."""
+    lib = _lib.load()
+    if (coord is None) == (grid is None) or (coord is None) != (cell is None):
+        raise ValueError("lte_query takes either coord and cell or grid")
+    if coord is not None:
+        Q, gh, gw = int(coord.shape[0]), 0, 0
+        if tuple(coord.shape) != (Q, 2) or tuple(cell.shape) != (Q, 2) or coord.dtype != torch.float32 or cell.dtype != torch.float32:
+            raise ValueError(f"lte_query expects coord and cell as (Q,2) fp32, got {tuple(coord.shape)} {coord.dtype} and {tuple(cell.shape)} {cell.dtype}")
+        if out.numel() != 3 * Q:
+            raise ValueError(f"lte_query: out holds {out.numel()} values, {Q} queries need {3 * Q}")
+    else:
+        gh, gw = int(grid[0]), int(grid[1])
+        Q = gh * gw
+        if out.numel() != 3 * Q:
+            raise ValueError(f"lte_query: out holds {out.numel()} values, a {gh}x{gw} grid needs {3 * Q}")
+    if out.dtype != torch.float32 or coef.dtype != torch.float32 or freq.dtype != torch.float32 or inp.dtype != torch.float32:
+        raise ValueError("lte_query expects fp32 coef / freq rows, fp32 input planes and an fp32 output")
+    if coef.numel() < (H * W - 1) * ldc + LTE_HIDDEN or freq.numel() < (H * W - 1) * ldf + LTE_HIDDEN or inp.numel() != 3 * H * W:
+        raise ValueError(f"lte_query: coef / freq / inp do not hold a {H}x{W} map")
+    hd = float(LTE_HIDDEN)
+    flops = Q * (4.0 * (2.0 * hd * hd * 3 + 2.0 * hd * 3 + 5.0 * hd) + 30.0)
+    wbytes = 3 * hd * hd * (2 if dtype == HAT_BF16 else 4)
+    nbytes = 4.0 * (min(4 * Q, H * W) * 2 * hd + 3 * H * W + 3 * Q + (4 * Q if coord is not None else 0)) + wbytes
+    _timed(f"lte_query_kernel<{_TNAME[dtype]}>", flops, lambda: _lib.check(
+        lib.hat_lte_query(_ptr(coef), _ptr(freq), ldc, ldf, _ptr(inp), H, W, _ptr(pl.phase), _ptr(pl.w[0]), _ptr(pl.b[0]), _ptr(pl.w[1]),
+                          _ptr(pl.b[1]), _ptr(pl.w[2]), _ptr(pl.b[2]), _ptr(pl.w4), _ptr(pl.b4), _ptr(coord), _ptr(cell), Q, gh, gw,
+                          float(cell_yx[0]), float(cell_yx[1]), float(out_affine[0]), float(out_affine[1]), _ptr(out), dtype, _stream()),
+        "hat_lte_query"), tag=f"lte {'grid ' + str(gh) + 'x' + str(gw) if coord is None else 'Q=' + str(Q)} on {H}x{W}", nbytes=nbytes)
 
 
 LOG2E = 1.4426950408889634

@@ -665,3 +665,35 @@ def pack_conv_nearest(weight, bias, r: int, dtype: int, device) -> PackedConv:
 def pack_pixshuf_conv(weight, bias, r: int, dtype: int, device) -> PackedConv:
     """Conv2d(I, r^2 C, 3, 1, 1) in front of nn.PixelShuffle(r) for hat_conv with HAT_O_PIXSHUF_T (ps_r = r)."""
     return pack_conv_weight(weight, bias, dtype, device, out_perm=pixshuf_perm(weight.shape[0], r))
+
+
+# ------------------------------------------------------------------------------------------------
+# hat_lte_query (ESC-LTE's head)
+# ------------------------------------------------------------------------------------------------
+LTE_HIDDEN = 256   # hidden_dim and every entry of hidden_list hat_lte_query is built for
+
+
+class PackedLte:
+    """The LTE head for hat_lte_query: `taps` the coef | freq 3x3 convs as ONE hat_conv layer of 512 outputs (fp32 rows out),
+    `phase` fp32 [128][2], `w` / `b` the three hidden layers (T fragments [16][8][64][8], fp32 [256]), `w4` / `b4` the last layer in fp32."""
+    __slots__ = ("taps", "phase", "w", "b", "w4", "b4")
+
+
+def pack_lte(sd, dtype: int, device) -> PackedLte:
+    """sd: coef.*, freq.*, phase.weight, imnet.layers.{0,2,4,6}.* of the reference's LTE (esc_arb/models/lte.py:14-21)."""
+    hd = LTE_HIDDEN
+    if tuple(sd["coef.weight"].shape[:1]) != (hd,) or tuple(sd["freq.weight"].shape[:1]) != (hd,) or tuple(sd["phase.weight"].shape) != (hd // 2, 2):
+        raise ValueError(f"ESC-LTE with hidden_dim={sd['coef.weight'].shape[0]} is not supported: hat_lte_query is built for hidden_dim {hd}")
+    shapes = [tuple(sd[f"imnet.layers.{i}.weight"].shape) for i in (0, 2, 4, 6) if f"imnet.layers.{i}.weight" in sd]
+    if shapes != [(hd, hd)] * 3 + [(3, hd)] or "imnet.layers.8.weight" in sd:
+        raise ValueError(f"ESC-LTE with an imnet of layer shapes {shapes} is not supported: hat_lte_query is built for hidden_list "
+                         f"({hd}, {hd}, {hd}) and out_dim 3")
+    p = PackedLte()
+    p.taps = pack_conv_weight(torch.cat([_f32(sd["coef.weight"]), _f32(sd["freq.weight"])]),
+                              torch.cat([_f32(sd["coef.bias"]), _f32(sd["freq.bias"])]), dtype, device)
+    p.phase = _f32(sd["phase.weight"]).contiguous().to(device)
+    p.w = [frags(_f32(sd[f"imnet.layers.{i}.weight"])).to(TORCH_DTYPE[dtype]).contiguous().to(device) for i in (0, 2, 4)]
+    p.b = [_f32(sd[f"imnet.layers.{i}.bias"]).contiguous().to(device) for i in (0, 2, 4)]
+    p.w4 = _f32(sd["imnet.layers.6.weight"]).contiguous().to(device)
+    p.b4 = _f32(sd["imnet.layers.6.bias"]).contiguous().to(device)
+    return p
