@@ -144,6 +144,7 @@ extern "C" int hat_escfp_shuffle_bicubic(const float* rows, const float* x, cons
     if (s < 2 || s > 4) return HAT_EUNSUPPORTED;
     const int64_t total = (int64_t)B * 3 * H * s * W * s;
     const int64_t blocks = (total + 255) / 256;
+    // tests/test_gpu_escreal_edges.py: BICUBIC_TRIP_OUTPUTS = 8192 * 256 output values per trip
     HAT_LAUNCH(escfp_shuffle_bicubic_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                rows, x, ptab, y, H, W, s, ld, total);
     return hat_check_launch();

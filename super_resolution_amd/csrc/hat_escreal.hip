@@ -217,6 +217,7 @@ extern "C" int hat_dysample(const float* rows, const float* init_pos, const floa
     const int64_t total = (int64_t)B * H * s * W * s;
     const int64_t blocks = (total + 255) / 256;
     const DysArgs a{rows, init_pos, bias, y, H, W, s, ld, total};
+    // tests/test_gpu_escreal_edges.py: DYS_TRIP_PIXELS = 16384 * 256 output pixels per trip
     HAT_LAUNCH(dysample_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     return hat_check_launch();
 }

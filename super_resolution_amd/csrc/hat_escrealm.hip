@@ -177,6 +177,7 @@ extern "C" int hat_unshuffle_pad(const float* x, float* rows, int32_t B, int32_t
     const int Hb = (h + f - 1) / f, Wb = (w + f - 1) / f;
     const int64_t total = (int64_t)B * Hb * Wb * 3 * f * f;
     const int64_t blocks = (total + 255) / 256;
+    // tests/test_gpu_escreal_edges.py: UNSHUF_TRIP_VALUES = 8192 * 256 row values per trip
     HAT_LAUNCH(unshuffle_pad_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, rows,
                h, w, f, Hb, Wb, ld, total);
     return hat_check_launch();
@@ -188,6 +189,7 @@ extern "C" int hat_shuffle_planes(const float* rows, float* y, int32_t B, int32_
     if ((int64_t)H * s > 0x7fffffff / ((int64_t)W * s)) return HAT_EINVAL;   // a plane's pixel count fits an int
     const int64_t total = (int64_t)B * 3 * H * s * W * s;
     const int64_t blocks = (total + 255) / 256;
+    // tests/test_gpu_escreal_edges.py: SHUFP_TRIP_OUTPUTS = 8192 * 256 output values per trip
     HAT_LAUNCH(shuffle_planes_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), rows, y,
                H, W, s, ld, total);
     return hat_check_launch();

@@ -109,14 +109,51 @@ def coef_freq(sd, feat):
     return (F.conv2d(feat, sd["coef.weight"], sd["coef.bias"], padding=1), F.conv2d(feat, sd["freq.weight"], sd["freq.bias"], padding=1))
 
 
-def imnet(sd, x):
+def imnet(sd, x, act_round=None):
+    """act_round: applied to the input and to the output of the first two hidden layers, the three places where hat_lte_query
+    stores activations as T (the last hidden layer feeds the 256 -> 3 layer from the fp32 accumulators)."""
+    rd = act_round or (lambda t: t)
+    x = rd(x)
     for i in (0, 2, 4):
         x = F.relu(F.linear(x, sd[f"imnet.layers.{i}.weight"], sd[f"imnet.layers.{i}.bias"]))
+        x = rd(x) if i != 4 else x
     return F.linear(x, sd["imnet.layers.6.weight"], sd["imnet.layers.6.bias"])
 
 
-def head(sd, coef, freq, inp, coord, cell):
-    """lte.py:34-105, statement for statement.  coef, freq (1,256,H,W); inp (1,3,H,W); coord, cell (1,Q,2) -> (1,Q,3)."""
+def bf16_round(t):
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+def mfma_weights_as_bf16(sd):
+    """The head's parameters with the three 256 x 256 layers (hat_lte_query's MFMA operands) rounded to bf16; everything else as is."""
+    return {k: (bf16_round(v) if k in ("imnet.layers.0.weight", "imnet.layers.2.weight", "imnet.layers.4.weight") else v) for k, v in sd.items()}
+
+
+def without_hidden_group(sd, g):
+    """The head with channels 16 g .. 16 g + 15 of the last hidden layer dropped: their columns of the 256 -> 3 layer are zero."""
+    sd = dict(sd)
+    w = sd["imnet.layers.6.weight"].clone()
+    w[:, 16 * g: 16 * g + 16] = 0
+    sd["imnet.layers.6.weight"] = w
+    return sd
+
+
+def bilinear_base(inp, coord):
+    """The bilinear base image of the head (lte.py:102-104) by explicit indexing, in fp64: inp (1,3,H,W), coord (1,Q,2) as (y, x) in
+    [-1, 1], align_corners=False, border padding -> (1,Q,3)."""
+    H, W = inp.shape[-2:]
+    m, c = inp[0].double(), coord[0].double()
+    iy, ix = (((c[:, 0] + 1) * H - 1) / 2).clamp(0, H - 1), (((c[:, 1] + 1) * W - 1) / 2).clamp(0, W - 1)
+    y0, x0 = iy.floor().long(), ix.floor().long()
+    y1, x1 = (y0 + 1).clamp(max=H - 1), (x0 + 1).clamp(max=W - 1)
+    ty, tx = iy - y0, ix - x0
+    v = m[:, y0, x0] * (1 - tx) * (1 - ty) + m[:, y0, x1] * tx * (1 - ty) + m[:, y1, x0] * (1 - tx) * ty + m[:, y1, x1] * tx * ty
+    return v.t()[None]
+
+
+def head(sd, coef, freq, inp, coord, cell, act_round=None):
+    """lte.py:34-105, statement for statement.  coef, freq (1,256,H,W); inp (1,3,H,W); coord, cell (1,Q,2) -> (1,Q,3).
+    act_round: see imnet (None: the reference)."""
     dt = coef.dtype
     coord, cell = coord.to(dt), cell.to(dt)
     H, W = coef.shape[-2:]
@@ -142,7 +179,7 @@ def head(sd, coef, freq, inp, coord, cell):
             q_freq = torch.sum(torch.mul(q_freq, rel.unsqueeze(-1)), dim=-2)
             q_freq = q_freq + F.linear(rel_cell.view(bs * q, -1), sd["phase.weight"]).view(bs, q, -1)
             q_freq = torch.cat((torch.cos(math.pi * q_freq), torch.sin(math.pi * q_freq)), dim=-1)
-            preds.append(imnet(sd, torch.mul(q_coef, q_freq).contiguous().view(bs * q, -1)).view(bs, q, -1))
+            preds.append(imnet(sd, torch.mul(q_coef, q_freq).contiguous().view(bs * q, -1), act_round).view(bs, q, -1))
             areas.append(torch.abs(rel[:, :, 0] * rel[:, :, 1]) + 1e-9)
     tot = torch.stack(areas).sum(dim=0)
     areas = areas[::-1]   # the diagonal swap (lte.py:96-97)

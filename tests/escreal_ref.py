@@ -1,6 +1,7 @@
 """An fp64 restatement of ESCReal (esc_real_arch.py:312-475, eval mode) from its state dict, built on esc_ref's functions, for the
 tests of the device path: `oracle/` is frozen, and the goldens under tests/golden/escreal_*.npz come from the reference itself
-(gen_golden_escreal.py).  Plain torch on the CPU; DySample is restated by explicit indexing, not by grid_sample."""
+(gen_golden_escreal.py).  Plain torch on the CPU; DySample is restated by explicit indexing, not by grid_sample.
+dysample_from_rows restates hat_dysample on the kernel's own rows and runs on the rows' device (the multi-trip test's frame)."""
 from __future__ import annotations
 
 import json
@@ -109,6 +110,40 @@ def head_dysample(feat, sd, s, offset_scale=1.0, project_first=False, groups=4):
         return y[None]
     up = torch.cat([bilinear_border(feat[0, cg * g: cg * (g + 1)], px[g], py[g]) for g in range(groups)], 0)
     return F.conv2d(up[None], sd["to_img.end_conv.weight"], be)
+
+
+def dysample_from_rows(rows, init_pos, bias, H, W, s, band=None, groups=4):
+    """hat_dysample restated in fp64 on the kernel's own operands, on the rows' device.  rows (B, H*W, ld) = [offset 8 s^2 | scope
+    8 s^2 | groups x 3 projected values | pad], entry d * 4 s^2 + grp * s^2 + i * s + j of offset / scope / init_pos being axis d
+    (0: x, 1: y) of group grp at output pixel (s y + i, s x + j); init_pos (8 s^2,); bias (3,) -> (B, 3, sH, sW) fp64.
+    `band`: LR rows handled at a time (None: all); only a band's positions and gathers exist next to the result."""
+    B, ss, dev = rows.shape[0], s * s, rows.device
+    m = rows.reshape(B, H, W, rows.shape[-1])
+    proj = m[..., 16 * ss: 16 * ss + 3 * groups].double().reshape(B, H * W, groups, 3)
+    ip = init_pos.double().reshape(2, groups, s, s).to(dev)
+    out = torch.empty(B, 3, s * H, s * W, dtype=torch.float64, device=dev)
+    xs = torch.arange(W, dtype=torch.float64, device=dev)[None, None, :, None, None, None]
+    band = H if band is None else band
+    for r0 in range(0, H, band):
+        r1 = min(r0 + band, H)
+        n = r1 - r0
+        blk = m[:, r0:r1, :, :16 * ss].double()
+        off = blk[..., :8 * ss].reshape(B, n, W, 2, groups, s, s)
+        scope = blk[..., 8 * ss:].reshape(B, n, W, 2, groups, s, s)
+        pos = off * torch.sigmoid(scope) * 0.5 + ip
+        ys = torch.arange(r0, r1, dtype=torch.float64, device=dev)[None, :, None, None, None, None]
+        px, py = (pos[:, :, :, 0] + xs).clamp(0, W - 1), (pos[:, :, :, 1] + ys).clamp(0, H - 1)     # (B, n, W, groups, s, s)
+        x0, y0 = px.floor().long(), py.floor().long()
+        x1, y1 = (x0 + 1).clamp(max=W - 1), (y0 + 1).clamp(max=H - 1)
+        tx, ty = px - x0, py - y0
+        acc = bias.double().to(dev).reshape(1, 1, 1, 1, 1, 3).expand(B, n, W, s, s, 3).clone()
+        for g in range(groups):
+            pg = proj[:, :, g]
+            take = lambda yy, xx: torch.gather(pg, 1, (yy[:, :, :, g] * W + xx[:, :, :, g]).reshape(B, -1, 1).expand(-1, -1, 3)).reshape(B, n, W, s, s, 3)
+            wx, wy = tx[:, :, :, g, :, :, None], ty[:, :, :, g, :, :, None]
+            acc += take(y0, x0) * (1 - wx) * (1 - wy) + take(y0, x1) * wx * (1 - wy) + take(y1, x0) * (1 - wx) * wy + take(y1, x1) * wx * wy
+        out[:, :, s * r0: s * r1] = acc.permute(0, 5, 1, 3, 2, 4).reshape(B, 3, n * s, W * s)
+    return out
 
 
 def trunk(sd, cfg, x):

@@ -33,6 +33,29 @@ def test_restatement_matches_the_reference(name):
     assert max_abs(y64, g["y"]) <= 1e-5
 
 
+@pytest.mark.parametrize("hw", [(1, 1), (3, 1)], ids=lambda m: f"{m[0]}x{m[1]}")
+def test_head_restatement_on_one_pixel_and_one_column_maps(hw):
+    """The maps tests/test_gpu_escreal_edges.py adds, at its queries: the fp64 head agrees with the fp32 head in the reference's
+    operation order (no query sits on a nearest-pixel tie the two would resolve differently), and on the 1 x 1 map with the closed
+    form: all four shifts read the one pixel, rel = coord, the four areas are equal, the base is the pixel itself."""
+    from test_gpu_esclte import head_case, head_ref
+    from test_gpu_escreal_edges import LTE_EXPLICIT_Q, LTE_SMALL_MAPS
+    H, W = hw
+    coef, freq, inp = head_case(H, W)
+    sd = R.head_state_dict()
+    for key in (("scatter", LTE_EXPLICIT_Q), ("grid", LTE_SMALL_MAPS[hw])):
+        coord, cell, y64 = head_ref(H, W, key)
+        for ax in (0, 1):
+            assert key[0] == "grid" or ((coord[:, ax] == -1).any() and (coord[:, ax] == 1).any())
+        y32 = R.head(sd, coef, freq, inp, coord[None], cell[None])[0]
+        assert tuple(y64.shape) == (coord.shape[0], 3) and max_abs(y32, y64) <= 2e-5
+        if hw == (1, 1):
+            c, k, fq = coord.double(), cell.double(), freq.double()[0, :, 0, 0]
+            f = fq[0::2] * c[:, :1] + fq[1::2] * c[:, 1:] + k @ sd["phase.weight"].double().t()
+            basis = coef.double()[0, :, 0, 0] * torch.cat([torch.cos(torch.pi * f), torch.sin(torch.pi * f)], -1)
+            assert max_abs(R.imnet(R.d64(sd), basis) + inp.double()[0, :, 0, 0], y64) <= 1e-12
+
+
 def test_golden_cases_are_what_the_issue_names():
     g = {n: R.load_case(n)[2] for n in R.CASES}
     assert g["a"]["coord"].shape[0] == 30 * 41 and g["b"]["coord"].shape[0] == 20 * 24 and g["c"]["coord"].shape[0] == 100 * 120

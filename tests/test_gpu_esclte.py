@@ -4,7 +4,10 @@ the halves of the coordinates, and upscale against the reference's goldens (test
 
 Bars, in image units (y * 0.5 + 0.5), README "Parity": fp32 max-abs <= 1e-4; bf16 >= 40 dB and max-abs <= 0.08.  At kernel level the
 fp32 path is held to helpers.check's 2e-5 * max(scale, 1) against fp64 (what test_gpu_ops.py asks of hat_linear), and the two
-addressing modes agree to it."""
+addressing modes agree to it.  The bf16 instantiation is also judged on the MLP term alone (mlp_bar): got - base against the fp64
+head with the MFMA weights rounded to bf16, minus base, where base is the fp64 bilinear base image — in the image bar the base of
+an input with std 0.5 carries most of the signal.  Its bar is helpers.check's bf16 bar (relative L2 <= 1.2e-2); the measured
+figures and the head with one 16-channel group dropped (tests/test_escreal_edges_ref_cpu.py) are in DESIGN 4.19."""
 import functools
 
 import pytest
@@ -58,6 +61,27 @@ def head_ref(H, W, key):
     return coord, cell, y
 
 
+@functools.lru_cache(maxsize=None)
+def mlp_ref(H, W, key):
+    """-> (the MLP term of the fp64 head whose three 256 x 256 layers are rounded to bf16, the fp64 base image), each (Q,3)."""
+    coef, freq, inp = head_case(H, W)
+    coord, cell, _ = head_ref(H, W, key)
+    sd = R.d64(R.mfma_weights_as_bf16(R.head_state_dict()))
+    base = R.bilinear_base(inp.double(), coord[None].double())[0]
+    y = R.head(sd, coef.double(), freq.double(), inp.double(), coord[None].double(), cell[None].double())[0]
+    return y - base, base
+
+
+def mlp_bar(got, H, W, key, what):
+    """The bf16 kernel's MLP term on its own: (got - base) against (ref - base) at helpers.check's bf16 bar."""
+    ref, base = mlp_ref(H, W, key)
+    term = got.detach().double().cpu() - base
+    rel = float((term - ref).norm() / ref.norm())
+    print(f"{what} [bf16] MLP term: rel {rel:.3e}, max-abs {float((term - ref).abs().max()):.3e} (scale {float(ref.abs().max()):.3g}, "
+          f"base scale {float(base.abs().max()):.3g})")
+    check(term, ref, "bf16", what + ", MLP term")
+
+
 def device_head(dtype, H, W):
     from super_resolution_amd import ops
     dev = _dev()
@@ -92,6 +116,8 @@ def test_query_explicit(hw, dtype):
         ops.lte_query(pl, coef, freq, inp, out, coord=coord.to(coef.device), cell=cell.to(coef.device), **kw)
         torch.cuda.synchronize()
         kernel_bar(out, y, dtype, f"lte_query explicit Q={Q} on {H}x{W}")
+        if dtype == "bf16":
+            mlp_bar(out, H, W, ("scatter", Q), f"lte_query explicit Q={Q} on {H}x{W}")
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -110,6 +136,8 @@ def test_query_grid_equals_explicit(hw, dtype):
         torch.cuda.synchronize()
         got = (planes.permute(1, 2, 0).reshape(-1, 3) - 0.5) / 0.5
         kernel_bar(got, y, dtype, f"lte_query grid {h}x{w} on {H}x{W}")
+        if dtype == "bf16":
+            mlp_bar(got, H, W, ("grid", (h, w)), f"lte_query grid {h}x{w} on {H}x{W}")
         check(got, rows, "f32", f"grid mode vs explicit mode {h}x{w} on {H}x{W} [{dtype}]")
 
 
