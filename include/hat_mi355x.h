@@ -1131,6 +1131,30 @@ int hat_lte_query(const float* coef, const float* freq, int32_t ldc, int32_t ldf
                   float cell_y, float cell_x, float out_a, float out_b, float* out, int32_t dtype, void* stream);
 
 /*
+ * hat_lte_query_u8, hat_lte_query_yuv  hat_lte_query's grid mode with another sink: the same queries, the same fp32
+ *   image value v * out_a + out_b per channel, but no fp32 image is written.  A workgroup's 4 x 8 tile of output pixels is held by 32
+ *   lanes of one wave, which convert and store it.  Arguments up to b4, gh, gw, cell_y, cell_x, out_a, out_b and dtype: hat_lte_query's,
+ *   with its refusals.
+ *     hat_lte_query_u8   dst (gh, gw, 3) interleaved bytes, rows dst_pitch >= 3 gw bytes apart: hat_planes_to_u8's conversion (clamp to
+ *                        [0, 1], x255 in fp32, round half to even); bgr != 0 swaps bytes 0 and 2.  No alignment is asked of dst.
+ *     hat_lte_query_yuv  dst one HatYuvSurface of a (gh, gw) frame (B = 1), any subsampling or grey, 8 / 10 / 12 / 16 bits, msb either
+ *                        way, centre-sited, checked as hat_planes_to_yuv checks it; from_rgb12 as there.  Per pixel and per chroma
+ *                        sample the conversion is hat_planes_to_yuv's, bit for bit: the pair and block sums are taken between lanes
+ *                        (lane ^ 1, lane ^ 8; a tile's origin is even in both axes).  A co-sited output needs a halo a tile does not
+ *                        have: write planes with hat_lte_query and convert with hat_planes_to_yuv_sited.
+ *   HAT_EINVAL, before any launch: what hat_lte_query refuses; a null dst (or dst->y) or from_rgb12; a pitch below the row; gw odd where
+ *   the surface subsamples horizontally, gh odd where vertically; a destination plane that overlaps inp.
+ */
+int hat_lte_query_u8(const float* coef, const float* freq, int32_t ldc, int32_t ldf, const float* inp, int32_t H, int32_t W,
+                     const float* phase, const void* w1, const float* b1, const void* w2, const float* b2, const void* w3, const float* b3,
+                     const float* w4, const float* b4, int32_t gh, int32_t gw, float cell_y, float cell_x, float out_a, float out_b,
+                     uint8_t* dst, int64_t dst_pitch, int32_t bgr, int32_t dtype, void* stream);
+int hat_lte_query_yuv(const float* coef, const float* freq, int32_t ldc, int32_t ldf, const float* inp, int32_t H, int32_t W,
+                      const float* phase, const void* w1, const float* b1, const void* w2, const float* b2, const void* w3, const float* b3,
+                      const float* w4, const float* b4, int32_t gh, int32_t gw, float cell_y, float cell_x, float out_a, float out_b,
+                      const HatYuvSurface* dst, const float* from_rgb12, int32_t dtype, void* stream);
+
+/*
  * ESCFP: what ESCFP (esc_fp_arch.py:247-355; 48 channels, 3 heads of 16) needs beyond ESC's launches.  DESIGN.md 4.16.
  * hat_window_attention_r, hat_esc_conv13, hat_conv and hat_linear serve it as they are.
  *

@@ -261,6 +261,11 @@ SIGNATURES = {
     "hat_escfp_shuffle_bicubic": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]),
     "hat_lte_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 11
                       + [C.c_int64, C.c_int32, C.c_int32] + [C.c_float] * 4 + [C.c_void_p, C.c_int32, C.c_void_p]),
+    # grid mode into bytes / a YCbCr surface: hat_lte_query's arguments up to b4, then the grid, the cell, the affine and the sink
+    "hat_lte_query_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 9
+                         + [C.c_int32, C.c_int32] + [C.c_float] * 4 + [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "hat_lte_query_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 9
+                          + [C.c_int32, C.c_int32] + [C.c_float] * 4 + [C.POINTER(HatYuvSurface), C.c_void_p, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

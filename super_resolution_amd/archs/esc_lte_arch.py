@@ -51,7 +51,11 @@ class ESCLTE(_ESCNet):
 
     Built: the encoder of train_esc-lte.yaml (dim 64, pdim 16, kernel_size 13, window_size 32, num_heads 4, exp_ratio 1.25 or 2,
     any n_blocks / conv_blocks), hidden_dim 256, hidden_list (256, 256, 256); anything else is a ValueError when the engine packs.
-    One frame per call.  `forward_ensemble`, the byte and YCbCr paths, row bands and plans raise NotImplementedError, as for `ESC`."""
+      upscale_u8(frame, size= | scale=)           an (h,w,3) uint8 device frame -> (1,H',W',3) uint8: tensor2img's bytes of `upscale`
+      upscale_yuv(frame, size= | scale=, fmt=)    a YCbCr device frame of any layout and depth -> the resized frame in any layout
+    `query_rgb` and the three `upscale` calls run eagerly also with `use_graph=True`.
+    One frame per call.  `forward_ensemble`, the fixed-scale byte and YCbCr entry points (`forward_u8`, `forward_yuv`, ...), row bands
+    and plans raise NotImplementedError, as for `ESC`: this network's frame paths are `upscale_u8` and `upscale_yuv`."""
 
     def __init__(self, dim: int = 64, pdim: int = 16, kernel_size: int = 13, n_blocks: int = 5, conv_blocks: int = 5, window_size: int = 32,
                  num_heads: int = 4, exp_ratio: float = 1.25, hidden_dim: int = 256, hidden_list=(256, 256, 256), compute_dtype: str = "bf16",
@@ -159,3 +163,113 @@ class ESCLTE(_ESCNet):
             factor = max((h / H) / scale_max, 1)   # inference.py:64, 70: the cell of the largest trained scale
             cy, cx = (float(torch.tensor(2 / n, dtype=torch.float32) * factor) for n in (h, w))   # rounded as the reference rounds them
             return eng.query_grid(h, w, (cy, cx), out_affine=(0.5, 0.5))[None]
+
+    # ---- frames in, frames out: any output size.  New names: the fixed-scale entry points above keep refusing.
+    def _out_size(self, what, H, W, size, scale):
+        if (size is None) == (scale is None):
+            raise ValueError(f"ESCLTE.{what} takes exactly one of size=(h, w) and scale=")
+        h, w = (int(H * scale), int(W * scale)) if size is None else (int(size[0]), int(size[1]))
+        if h < 1 or w < 1:
+            raise ValueError(f"ESCLTE.{what}: an output of {h}x{w} is empty")
+        return h, w
+
+    @staticmethod
+    def _cells(H, W, h, w, scale_max):
+        factor = max((h / H) / scale_max, 1)   # upscale's cell rule (inference.py:64, 70)
+        return tuple(float(torch.tensor(2 / n, dtype=torch.float32) * factor) for n in (h, w))
+
+    def upscale_u8(self, frame, size=None, scale=None, *, bgr: bool = False, out=None, scale_max=4):
+        """An 8-bit frame in, an 8-bit frame of any size out, all on the device: `frame` (h,w,3) or (1,h,w,3) uint8 -> (1,H',W',3)
+        uint8 with (H', W') = size or (int(h scale), int(w scale)).  Equal, bit for bit, to float32(u8) / 255 -> `upscale` ->
+        tensor2img (clamp to [0, 1], x255 in fp32, round half to even): hat_u8_to_planes into the workspace (no padding: ESC reflects
+        its own window edges), the encoder, and one hat_lte_query_u8, which stores the bytes itself; no fp32 image is written.
+        bgr: the bytes are B, G, R on both sides.  out: a (1,H',W',3) uint8 device tensor to fill (rows may be pitched); with it the
+        call allocates nothing after the first call of a shape."""
+        if not isinstance(frame, torch.Tensor) or frame.dtype != torch.uint8 or frame.dim() not in (3, 4) or frame.shape[-1] != 3:
+            raise RuntimeError(f"ESCLTE.upscale_u8 expects an (h,w,3) or (1,h,w,3) uint8 frame, got {tuple(getattr(frame, 'shape', ()))} "
+                               f"{getattr(frame, 'dtype', type(frame).__name__)}")
+        if frame.dim() == 3:
+            frame = frame.unsqueeze(0)
+        if frame.shape[0] != 1:
+            raise RuntimeError(f"ESCLTE.upscale_u8 takes one frame per call, got a batch of {frame.shape[0]}")
+        H, W = int(frame.shape[1]), int(frame.shape[2])
+        h, w = self._out_size("upscale_u8", H, W, size, scale)
+        self._check_call(frame)
+        from .. import ops
+        with torch.no_grad():
+            eng = self.engine(frame.device)
+            dst = out
+            if dst is None:
+                dst = torch.empty((1, h, w, 3), dtype=torch.uint8, device=eng.dev)
+            elif not isinstance(dst, torch.Tensor) or dst.dtype != torch.uint8 or tuple(dst.shape) != (1, h, w, 3) or dst.device != eng.dev \
+                    or dst.stride(3) != 1 or dst.stride(2) != 3:
+                raise RuntimeError(f"out must be a {(1, h, w, 3)} uint8 tensor on {eng.dev} with interleaved pixels, got "
+                                   f"{tuple(getattr(dst, 'shape', ()))} {getattr(dst, 'dtype', type(dst).__name__)} on {getattr(dst, 'device', None)}")
+            if frame.stride(3) != 1 or frame.stride(2) != 3:
+                frame = frame.contiguous()
+            eng.gen_feat_frame(H, W, lambda x: ops.u8_to_planes(frame, x, bgr=bgr))
+            self._feat_engine = eng
+            return eng.query_grid_u8(dst, self._cells(H, W, h, w, scale_max), bgr)
+
+    def upscale_yuv(self, frame, size=None, scale=None, *, fmt: str, out_fmt=None, matrix: str = "bt601", full_range: bool = False, depth: int = 8,
+                    out_depth=None, msb=None, out_msb=None, out=None, siting: str = "center", out_siting=None, scale_max=4):
+        """A YCbCr frame in, a YCbCr frame of any size out, all on the device: `frame` is a (rows, w) or (1, rows, w) uint8 (uint16
+        with depth 10 / 12 / 16) device tensor in the standard layout of `fmt` (yuv.LAYOUTS); the result is the (H', W') frame in the
+        layout `out_fmt` (default: fmt), (H', W') = size or (int(h scale), int(w scale)), W' even where out_fmt subsamples horizontally
+        and H' where vertically (ValueError otherwise).  fmt, out_fmt, matrix, full_range, depth, out_depth, msb, out_msb, siting,
+        out_siting and out: as `HAT.forward_yuv` takes them.  Equal, bit for bit, to yuv.yuv_to_planes -> `upscale` ->
+        yuv.planes_to_yuv.  A centre-sited output is stored by hat_lte_query_yuv and no fp32 image is written (with out= the call then
+        allocates nothing after the first call of a shape); an output with a co-sited axis ('left' / 'topleft' on a subsampled axis)
+        is the plane query into the workspace, then hat_planes_to_yuv_sited."""
+        if not isinstance(frame, torch.Tensor):
+            raise TypeError(f"upscale_yuv needs a uint8 device tensor, got {type(frame).__name__}")
+        if frame.dtype not in (torch.uint8, torch.uint16):
+            raise TypeError(f"upscale_yuv needs a uint8 tensor (uint16 with depth 10, 12 or 16), got {frame.dtype}")
+        from .. import ops, yuv
+        yuv.check_layout(fmt)
+        out_fmt = fmt if out_fmt is None else out_fmt
+        yuv.check_layout(out_fmt)
+        yuv.check_siting(siting)
+        out_siting = siting if out_siting is None else yuv.check_siting(out_siting)
+        out_depth = depth if out_depth is None else out_depth
+        to_rgb, from_rgb = yuv.csc(matrix, full_range, depth)[0], yuv.csc(matrix, full_range, out_depth)[1]
+        in_msb, out_msb = bool(yuv.container(depth, fmt, msb)[3]), bool(yuv.container(out_depth, out_fmt, out_msb)[3])
+        in_dt, out_dt = (torch.uint8 if d == 8 else torch.uint16 for d in (depth, out_depth))
+        if frame.dtype != in_dt:
+            raise TypeError(f"upscale_yuv: depth={depth} needs a {'uint8' if depth == 8 else 'uint16'} tensor, got {frame.dtype}")
+        if frame.dim() == 2:
+            frame = frame.unsqueeze(0)
+        if frame.dim() != 3:
+            raise RuntimeError(f"expected (1,rows,w) {fmt} frames, got {tuple(frame.shape)}")
+        if frame.shape[0] != 1:
+            raise RuntimeError(f"ESCLTE.upscale_yuv takes one frame per call, got a batch of {frame.shape[0]}")
+        H, W = yuv.frame_size_fmt(frame.shape, fmt)
+        h, w = self._out_size("upscale_yuv", H, W, size, scale)
+        sub = lambda f: None if yuv.LAYOUTS[f][0] is None else yuv.LAYOUTS[f][:2]
+        so = sub(out_fmt)
+        if so is not None and ((so[0] and w % 2) or (so[1] and h % 2)):
+            raise ValueError(f"ESCLTE.upscale_yuv: an output of {h}x{w} is no {out_fmt} frame: the layout needs an even "
+                             + " and an even ".join(n for n, odd in (("width", so[0] and w % 2), ("height", so[1] and h % 2)) if odd))
+        self._check_call(frame)
+        with torch.no_grad():
+            eng = self.engine(frame.device)
+            shape, dst = (1,) + yuv.frame_shape_fmt(h, w, out_fmt), out
+            if dst is None:
+                dst = torch.empty(shape, dtype=out_dt, device=eng.dev)
+            elif not isinstance(dst, torch.Tensor) or dst.dtype != out_dt or tuple(dst.shape) != shape or dst.device != eng.dev \
+                    or dst.stride(2) != 1 or dst.stride(1) != w:
+                raise RuntimeError(f"out must be a {shape} {str(out_dt)[6:]} tensor on {eng.dev} with packed rows, got "
+                                   f"{tuple(dst.shape)} {dst.dtype} on {dst.device}")
+            f = frame
+            if f.stride(2) != 1 or f.stride(1) != W:
+                f = f.contiguous() if in_dt is torch.uint8 else f.view(torch.int16).contiguous().view(torch.uint16)
+            eng.gen_feat_frame(H, W, lambda x: ops.yuv_to_planes(*ops.yuv_views(f, fmt), x, to_rgb, sub=sub(fmt), depth=depth, msb=in_msb,
+                                                                 siting=siting))
+            self._feat_engine = eng
+            cells, views = self._cells(H, W, h, w, scale_max), ops.yuv_views(dst, out_fmt)
+            if ops._siting(so, out_siting)[0] == "center":
+                eng.query_grid_yuv(views, cells, from_rgb, so, out_depth, out_msb)
+            else:   # the 2-tap filter of a co-sited axis needs a halo a 4 x 8 tile does not have
+                planes = eng.query_grid_planes(eng.planes_buffer(H, W, h, w), cells, out_affine=(0.5, 0.5))
+                ops.planes_to_yuv(planes, *views, from_rgb, sub=so, depth=out_depth, msb=out_msb, siting=out_siting)
+            return dst

@@ -4,6 +4,8 @@
 //
 //   hat_lte_query   explicit mode: coord / cell (Q,2) -> out (Q,3);  grid mode: the make_coord grid of a (gh, gw) image, computed in
 //                   the kernel, -> out (3,gh,gw) planes.  Both with the affine out * a + b.
+//   hat_lte_query_u8 / hat_lte_query_yuv   grid mode with another sink: the same fp32 image value, stored as interleaved bytes
+//                   (hat_unit_to_u8) or as a YCbCr surface of any layout and depth (hat_planes_to_yuv's conversion); no fp32 image.
 //
 // A workgroup (256 threads, 4 waves) owns 32 queries = 128 MLP rows (row = 32 shift + query).  The rows live in LDS as T
 // ([128][LD], the MFMA B operand; T = bf16 or fp32) from the basis to the last hidden layer; a layer's 256 x 256 weights stream
@@ -11,8 +13,10 @@
 // 64 w .. 64 w + 63 of all 128 rows (4 x 8 accumulator tiles), and the layer's output replaces its input in place once every
 // wave has finished reading.  The last layer (256 -> 3) is folded into the third layer's epilogue from the fp32 accumulators.
 // Grid mode tiles the output 4 x 8 so that the queries of a tile share feature pixels.
-// Contract: include/hat_mi355x.h "ESC-LTE".  DESIGN.md 4.19.
+// Contract: include/hat_mi355x.h "ESC-LTE".  DESIGN.md 4.19, 4.20.
 #include "hat_common.h"
+#include "hat_yuv_check.h"
+#include "hat_yuv_sample.h"
 
 namespace {
 
@@ -102,8 +106,106 @@ __device__ __forceinline__ void lte_layer(const T* __restrict__ wf, const T* act
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(LTE_THREADS) void lte_query_kernel(const LteArgs a) {
+// Where the last phase stores a query's three values.  LtePlanes: a.out, planes (grid mode) or rows (explicit mode), the store the
+// kernel always had.  The other two are grid mode only: the 32 lanes of a 4 x 8 tile hold the fp32 image value v * out_a + out_b of
+// their pixel (lte_pixel) and convert it.
+struct LtePlanes {};
+
+// (gh, gw, 3) interleaved bytes, rows `pitch` bytes apart: hat_unit_to_u8 of each value, bytes 0 and 2 swapped with bgr
+struct LteU8 {
+    uint8_t* dst;
+    long long pitch;
+    int bgr;
+    __device__ __forceinline__ void store(const float (&rgb)[3], bool valid, int oy, int ox) const {
+        if (!valid) return;
+        uint8_t* o = dst + (size_t)oy * pitch + (size_t)ox * 3;
+        o[bgr ? 2 : 0] = (uint8_t)hat_unit_to_u8(rgb[0]);
+        o[1] = (uint8_t)hat_unit_to_u8(rgb[1]);
+        o[bgr ? 0 : 2] = (uint8_t)hat_unit_to_u8(rgb[2]);
+    }
+};
+
+// A YCbCr surface, centre-sited: planes_to_yuv420_kernel's conversion per pixel and per chroma sample (hat_yuv.hip).  The tile origin
+// is even in both axes, so lane q's horizontal partner is q ^ 1 and its vertical partner q ^ 8, and the lane with even ox (and even
+// oy where SUB_Y) stores the chroma sample of its pair / block.  store() is called by every lane of the wave, valid or not: the
+// exchanges are outside every branch; a lane without a pixel converts zeros and stores nothing.  The subsampled axes of the image
+// have even extent (the host checks it), so the partner of a lane that stores is a pixel of the image.
+template <typename S, int SUB_X, int SUB_Y, bool GREY> struct LteYuv {
+    S* yp;
+    S* cbp;
+    S* crp;
+    long long y_pitch, c_pitch;
+    int c_step;
+    HatCsc k;
+    HatSample<S> q;
+    __device__ __forceinline__ void store(const float (&rgb)[3], bool valid, int oy, int ox) const {
+        float Y, cb, cr;
+        hat_rgb_to_ycc(k, rgb[0], rgb[1], rgb[2], Y, cb, cr);
+        if (valid) sample_at(yp, (size_t)oy * y_pitch + (size_t)ox * sizeof(S)) = (S)q.luma(Y);
+        if constexpr (!GREY) {
+            const size_t co = (size_t)(oy >> SUB_Y) * c_pitch + (size_t)(ox >> SUB_X) * c_step;
+            if constexpr (SUB_X == 1) {
+                // the pair sum left + right, in that order, on the even lane
+                const float sb = hat_add_rn(cb, __shfl_xor(cb, 1)), sr = hat_add_rn(cr, __shfl_xor(cr, 1));
+                if constexpr (SUB_Y == 1) {
+                    const float bb = __shfl_xor(sb, 8), br = __shfl_xor(sr, 8);   // the bottom row's pair sums, on the top row's lanes
+                    if (valid && !(ox & 1) && !(oy & 1)) {
+                        sample_at(cbp, co) = (S)q.chroma(sb, bb, k.m[7]);
+                        sample_at(crp, co) = (S)q.chroma(sr, br, k.m[11]);
+                    }
+                } else {
+                    if (valid && !(ox & 1)) {
+                        sample_at(cbp, co) = (S)q.luma(hat_chroma_value_h(sb, k.m[7]));
+                        sample_at(crp, co) = (S)q.luma(hat_chroma_value_h(sr, k.m[11]));
+                    }
+                }
+            } else {
+                if (valid) {
+                    sample_at(cbp, co) = (S)q.luma(hat_add_rn(cb, k.m[7]));
+                    sample_at(crp, co) = (S)q.luma(hat_add_rn(cr, k.m[11]));
+                }
+            }
+        }
+    }
+};
+
+// One query's three values for the byte and YCbCr sinks: the area-weighted sum with the diagonal swap, plus the bilinear base image
+// (border padding), then the affine.                                                                             lte.py:95-104
+// The plane store below states this as plain expressions and leaves the fusing of its products and sums to the compiler, and how
+// those fuse may differ from one instantiation to the next.  A sink's bytes must be those of the planes, so here the operation
+// order the plane store compiles to is written out — contraction off, every fused multiply-add explicit:
+//   base = fma(p11, wse, fma(p10, wsw, fma(p00, wnw, p01 * wne))),  v = fma(P3, w3, fma(P2, w2, fma(P0, w0, P1 * w1))),
+//   value = fma(v + base, out_a, out_b).
+// tests/test_gpu_esclte_frames.py holds the two equal bit for bit; DESIGN.md 4.20.
+__device__ __forceinline__ void lte_pixel(const LteArgs& a, int q, const float* m_area, const float* m_cy, const float* m_cx, const float* part,
+                                          float (&rgb)[3]) {
+#pragma clang fp contract(off)
+    const int H = a.H, W = a.W;
+    const float a0 = m_area[q], a1 = m_area[LTE_TQ + q], a2 = m_area[2 * LTE_TQ + q], a3 = m_area[3 * LTE_TQ + q];
+    const float tot = ((a0 + a1) + a2) + a3;
+    const float w0 = a3 / tot, w1 = a2 / tot, w2 = a1 / tot, w3 = a0 / tot;
+    const float cy = m_cy[q], cx = m_cx[q];
+    float iy = fminf(fmaxf(lte_unnormalize(cy, (float)H), 0.f), (float)(H - 1));
+    float ix = fminf(fmaxf(lte_unnormalize(cx, (float)W), 0.f), (float)(W - 1));
+    const float fy = floorf(iy), fx = floorf(ix);
+    const int y0 = min(max((int)fy, 0), H - 1), x0 = min(max((int)fx, 0), W - 1);
+    const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
+    const float ty = iy - fy, tx = ix - fx;
+    const float wnw = (1.f - tx) * (1.f - ty), wne = tx * (1.f - ty), wsw = (1.f - tx) * ty, wse = tx * ty;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float* pl = a.inp + (int64_t)c * H * W;
+        const float p00 = pl[(int64_t)y0 * W + x0], p01 = pl[(int64_t)y0 * W + x1], p10 = pl[(int64_t)y1 * W + x0], p11 = pl[(int64_t)y1 * W + x1];
+        const float base = __builtin_fmaf(p11, wse, __builtin_fmaf(p10, wsw, __builtin_fmaf(p00, wnw, p01 * wne)));
+        const float v = __builtin_fmaf(part[(3 * LTE_TQ + q) * 3 + c], w3,
+                                       __builtin_fmaf(part[(2 * LTE_TQ + q) * 3 + c], w2,
+                                                      __builtin_fmaf(part[q * 3 + c], w0, part[(LTE_TQ + q) * 3 + c] * w1)));
+        rgb[c] = __builtin_fmaf(v + base, a.out_a, a.out_b);
+    }
+}
+
+template <typename T, typename Sink>
+__global__ __launch_bounds__(LTE_THREADS) void lte_query_kernel(const LteArgs a, const Sink sink) {
     typedef LteLds<T> L;
     constexpr int LD = L::LD;
     extern __shared__ __attribute__((aligned(16))) unsigned char lte_smem[];
@@ -249,76 +351,87 @@ __global__ __launch_bounds__(LTE_THREADS) void lte_query_kernel(const LteArgs a)
     __syncthreads();
 
     // ---- the area-weighted sum with the diagonal swap, plus the bilinear base image (border padding)         lte.py:95-104
-    if (tid < LTE_TQ) {
-        const int q = tid;
-        bool valid;
-        int64_t o0, ostride;
-        if (grid) {
-            const int oy = ty0 + q / LTE_TX, ox = tx0 + q % LTE_TX;
-            valid = oy < a.gh && ox < a.gw;
-            o0 = (int64_t)oy * a.gw + ox;
-            ostride = (int64_t)a.gh * a.gw;
-        } else {
-            valid = q0 + q < a.Q;
-            o0 = 3 * (q0 + q);
-            ostride = 1;
-        }
-        if (valid) {
-            const float a0 = m_area[q], a1 = m_area[LTE_TQ + q], a2 = m_area[2 * LTE_TQ + q], a3 = m_area[3 * LTE_TQ + q];
-            const float tot = ((a0 + a1) + a2) + a3;
-            const float w0 = a3 / tot, w1 = a2 / tot, w2 = a1 / tot, w3 = a0 / tot;
-            const float cy = m_cy[q], cx = m_cx[q];
-            float iy = fminf(fmaxf(lte_unnormalize(cy, (float)H), 0.f), (float)(H - 1));
-            float ix = fminf(fmaxf(lte_unnormalize(cx, (float)W), 0.f), (float)(W - 1));
-            const float fy = floorf(iy), fx = floorf(ix);
-            const int y0 = min(max((int)fy, 0), H - 1), x0 = min(max((int)fx, 0), W - 1);
-            const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
-            const float ty = iy - fy, tx = ix - fx;
-            const float wnw = (1.f - tx) * (1.f - ty), wne = tx * (1.f - ty), wsw = (1.f - tx) * ty, wse = tx * ty;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float* pl = a.inp + (int64_t)c * H * W;
-                const float base = pl[(int64_t)y0 * W + x0] * wnw + pl[(int64_t)y0 * W + x1] * wne + pl[(int64_t)y1 * W + x0] * wsw +
-                                   pl[(int64_t)y1 * W + x1] * wse;
-                float v = part[q * 3 + c] * w0 + part[(LTE_TQ + q) * 3 + c] * w1 + part[(2 * LTE_TQ + q) * 3 + c] * w2 +
-                          part[(3 * LTE_TQ + q) * 3 + c] * w3;
-                v += base;
-                a.out[o0 + c * ostride] = v * a.out_a + a.out_b;
+    if constexpr (std::is_same<Sink, LtePlanes>::value) {
+        if (tid < LTE_TQ) {
+            const int q = tid;
+            bool valid;
+            int64_t o0, ostride;
+            if (grid) {
+                const int oy = ty0 + q / LTE_TX, ox = tx0 + q % LTE_TX;
+                valid = oy < a.gh && ox < a.gw;
+                o0 = (int64_t)oy * a.gw + ox;
+                ostride = (int64_t)a.gh * a.gw;
+            } else {
+                valid = q0 + q < a.Q;
+                o0 = 3 * (q0 + q);
+                ostride = 1;
             }
+            if (valid) {
+                const float a0 = m_area[q], a1 = m_area[LTE_TQ + q], a2 = m_area[2 * LTE_TQ + q], a3 = m_area[3 * LTE_TQ + q];
+                const float tot = ((a0 + a1) + a2) + a3;
+                const float w0 = a3 / tot, w1 = a2 / tot, w2 = a1 / tot, w3 = a0 / tot;
+                const float cy = m_cy[q], cx = m_cx[q];
+                float iy = fminf(fmaxf(lte_unnormalize(cy, (float)H), 0.f), (float)(H - 1));
+                float ix = fminf(fmaxf(lte_unnormalize(cx, (float)W), 0.f), (float)(W - 1));
+                const float fy = floorf(iy), fx = floorf(ix);
+                const int y0 = min(max((int)fy, 0), H - 1), x0 = min(max((int)fx, 0), W - 1);
+                const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
+                const float ty = iy - fy, tx = ix - fx;
+                const float wnw = (1.f - tx) * (1.f - ty), wne = tx * (1.f - ty), wsw = (1.f - tx) * ty, wse = tx * ty;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float* pl = a.inp + (int64_t)c * H * W;
+                    const float base = pl[(int64_t)y0 * W + x0] * wnw + pl[(int64_t)y0 * W + x1] * wne + pl[(int64_t)y1 * W + x0] * wsw +
+                                       pl[(int64_t)y1 * W + x1] * wse;
+                    float v = part[q * 3 + c] * w0 + part[(LTE_TQ + q) * 3 + c] * w1 + part[(2 * LTE_TQ + q) * 3 + c] * w2 +
+                              part[(3 * LTE_TQ + q) * 3 + c] * w3;
+                    v += base;
+                    a.out[o0 + c * ostride] = v * a.out_a + a.out_b;
+                }
+            }
+        }
+    } else {
+        // grid mode only.  The whole first wave enters: the YCbCr sink exchanges values between lanes, so no lane may be missing
+        // from it; lanes 32 .. 63 and lanes past gh / gw hold zeros.
+        if (wave == 0) {
+            const int q = lane & (LTE_TQ - 1);
+            const int oy = ty0 + q / LTE_TX, ox = tx0 + q % LTE_TX;
+            const bool valid = lane < LTE_TQ && oy < a.gh && ox < a.gw;
+            float rgb[3] = {0.f, 0.f, 0.f};
+            if (valid) lte_pixel(a, q, m_area, m_cy, m_cx, part, rgb);
+            sink.store(rgb, valid, oy, ox);
         }
     }
 }
 
-template <typename T> int lte_launch(const LteArgs& a, int64_t tiles, hipStream_t s) {
+template <typename T, typename Sink> int lte_launch(const LteArgs& a, const Sink& sink, int64_t tiles, hipStream_t s) {
     constexpr size_t lds = LteLds<T>::BYTES;
-    auto kern = lte_query_kernel<T>;
+    auto kern = lte_query_kernel<T, Sink>;
     if (lds > 65536) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
-    HAT_LAUNCH(kern, dim3((unsigned)tiles), dim3(LTE_THREADS), lds, s, a);
+    HAT_LAUNCH(kern, dim3((unsigned)tiles), dim3(LTE_THREADS), lds, s, a, sink);
     return hat_check_launch();
 }
 
 bool aligned(const void* p, uintptr_t al) { return reinterpret_cast<uintptr_t>(p) % al == 0; }
 
-}  // namespace
-
-extern "C" int hat_lte_query(const float* coef, const float* freq, int32_t ldc, int32_t ldf, const float* inp, int32_t H, int32_t W,
-                             const float* phase, const void* w1, const float* b1, const void* w2, const float* b2, const void* w3,
-                             const float* b3, const float* w4, const float* b4, const float* coord, const float* cell, int64_t Q,
-                             int32_t gh, int32_t gw, float cell_y, float cell_x, float out_a, float out_b, float* out, int32_t dtype,
-                             void* stream) {
+// What every entry checks and fills, from the arguments alone; `out`: where the result goes first (it must not be inp).  Grid mode
+// when coord is null.  Returns 0 or HAT_EINVAL.
+int lte_args(LteArgs& a, int64_t& tiles, const float* coef, const float* freq, int32_t ldc, int32_t ldf, const float* inp, int32_t H, int32_t W,
+             const float* phase, const void* w1, const float* b1, const void* w2, const float* b2, const void* w3, const float* b3,
+             const float* w4, const float* b4, const float* coord, const float* cell, int64_t Q, int32_t gh, int32_t gw, float cell_y,
+             float cell_x, float out_a, float out_b, const void* out, int32_t dtype) {
     if (!coef || !freq || !inp || !phase || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4 || !out) return HAT_EINVAL;
     if (dtype != HAT_F32 && dtype != HAT_BF16) return HAT_EINVAL;
     if (H < 1 || W < 1 || (int64_t)H * W > 0x7fffffff) return HAT_EINVAL;
     if (ldc < LTE_HID || ldc % 4 || ldf < LTE_HID || ldf % 4) return HAT_EINVAL;
     if (!aligned(coef, 16) || !aligned(freq, 16) || !aligned(phase, 16) || !aligned(w1, 16) || !aligned(w2, 16) || !aligned(w3, 16) ||
-        !aligned(b1, 16) || !aligned(b2, 16) || !aligned(b3, 16) || !aligned(w4, 16) || !aligned(b4, 4) || !aligned(inp, 4) || !aligned(out, 4))
+        !aligned(b1, 16) || !aligned(b2, 16) || !aligned(b3, 16) || !aligned(w4, 16) || !aligned(b4, 4) || !aligned(inp, 4))
         return HAT_EINVAL;
     if ((coord == nullptr) != (cell == nullptr)) return HAT_EINVAL;
-    LteArgs a{};
-    int64_t tiles;
+    a = LteArgs{};
     if (coord) {
         if (Q < 1 || !aligned(coord, 4) || !aligned(cell, 4)) return HAT_EINVAL;
         tiles = (Q + LTE_TQ - 1) / LTE_TQ;
@@ -331,10 +444,10 @@ extern "C" int hat_lte_query(const float* coef, const float* freq, int32_t ldc, 
         a.gy0 = (float)(-1.0 + 1.0 / gh), a.gys = (float)(2.0 / gh), a.gx0 = (float)(-1.0 + 1.0 / gw), a.gxs = (float)(2.0 / gw);
     }
     if (tiles > 0x7fffffff) return HAT_EINVAL;
-    if (reinterpret_cast<const void*>(out) == reinterpret_cast<const void*>(inp)) return HAT_EINVAL;
+    if (out == reinterpret_cast<const void*>(inp)) return HAT_EINVAL;
     a.coef = coef, a.freq = freq, a.inp = inp, a.phase = phase;
     a.w[0] = w1, a.w[1] = w2, a.w[2] = w3, a.b[0] = b1, a.b[1] = b2, a.b[2] = b3, a.w4 = w4, a.b4 = b4;
-    a.coord = coord, a.cell = cell, a.out = out, a.Q = Q;
+    a.coord = coord, a.cell = cell, a.Q = Q;
     a.H = H, a.W = W, a.ldc = ldc, a.ldf = ldf, a.gh = gh, a.gw = gw;
     a.cell_y = cell_y, a.cell_x = cell_x;
     a.fy0 = (float)(-1.0 + 1.0 / H), a.fys = (float)(2.0 / H), a.fx0 = (float)(-1.0 + 1.0 / W), a.fxs = (float)(2.0 / W);
@@ -343,6 +456,81 @@ extern "C" int hat_lte_query(const float* coef, const float* freq, int32_t ldc, 
         a.sx[v] = (float)((2 * v - 1) * (2.0 / W / 2) + 1e-6);
     }
     a.out_a = out_a, a.out_b = out_b;
+    return 0;
+}
+
+// the bytes [p, p + n) and the input planes share a byte
+bool overlaps_inp(const void* p, int64_t n, const float* inp, int32_t H, int32_t W) {
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(p), ilo = reinterpret_cast<uintptr_t>(inp);
+    return lo < ilo + (uintptr_t)12 * H * W && ilo < lo + (uintptr_t)n;
+}
+
+template <typename Sink> int lte_launch_dtype(const LteArgs& a, const Sink& sink, int64_t tiles, int32_t dtype, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return dtype == HAT_BF16 ? lte_launch<bf16_t>(a, tiles, s) : lte_launch<float>(a, tiles, s);
+    return dtype == HAT_BF16 ? lte_launch<bf16_t>(a, sink, tiles, s) : lte_launch<float>(a, sink, tiles, s);
+}
+
+template <typename S> int lte_launch_yuv(const LteArgs& a, const HatYuvSurface& d, const HatCsc& k, HatSample<S> q, int64_t tiles, int32_t dtype,
+                                         void* stream) {
+    S* y = reinterpret_cast<S*>(d.y);
+    S* cb = reinterpret_cast<S*>(d.cb);
+    S* cr = reinterpret_cast<S*>(d.cr);
+    if (!d.cb) return lte_launch_dtype(a, LteYuv<S, 0, 0, true>{y, nullptr, nullptr, (long long)d.y_pitch, 0, 0, k, q}, tiles, dtype, stream);
+    const long long yp = d.y_pitch, cp = d.c_pitch;
+    if (d.sub_y) return lte_launch_dtype(a, LteYuv<S, 1, 1, false>{y, cb, cr, yp, cp, (int)d.c_step, k, q}, tiles, dtype, stream);
+    if (d.sub_x) return lte_launch_dtype(a, LteYuv<S, 1, 0, false>{y, cb, cr, yp, cp, (int)d.c_step, k, q}, tiles, dtype, stream);
+    return lte_launch_dtype(a, LteYuv<S, 0, 0, false>{y, cb, cr, yp, cp, (int)d.c_step, k, q}, tiles, dtype, stream);
+}
+
+}  // namespace
+
+extern "C" int hat_lte_query(const float* coef, const float* freq, int32_t ldc, int32_t ldf, const float* inp, int32_t H, int32_t W,
+                             const float* phase, const void* w1, const float* b1, const void* w2, const float* b2, const void* w3,
+                             const float* b3, const float* w4, const float* b4, const float* coord, const float* cell, int64_t Q,
+                             int32_t gh, int32_t gw, float cell_y, float cell_x, float out_a, float out_b, float* out, int32_t dtype,
+                             void* stream) {
+    LteArgs a;
+    int64_t tiles;
+    if (!aligned(out, 4)) return HAT_EINVAL;
+    if (int rc = lte_args(a, tiles, coef, freq, ldc, ldf, inp, H, W, phase, w1, b1, w2, b2, w3, b3, w4, b4, coord, cell, Q, gh, gw, cell_y, cell_x,
+                          out_a, out_b, out, dtype))
+        return rc;
+    a.out = out;
+    return lte_launch_dtype(a, LtePlanes{}, tiles, dtype, stream);
+}
+
+extern "C" int hat_lte_query_u8(const float* coef, const float* freq, int32_t ldc, int32_t ldf, const float* inp, int32_t H, int32_t W,
+                                const float* phase, const void* w1, const float* b1, const void* w2, const float* b2, const void* w3,
+                                const float* b3, const float* w4, const float* b4, int32_t gh, int32_t gw, float cell_y, float cell_x,
+                                float out_a, float out_b, uint8_t* dst, int64_t dst_pitch, int32_t bgr, int32_t dtype, void* stream) {
+    LteArgs a;
+    int64_t tiles;
+    if (int rc = lte_args(a, tiles, coef, freq, ldc, ldf, inp, H, W, phase, w1, b1, w2, b2, w3, b3, w4, b4, nullptr, nullptr, 0, gh, gw, cell_y,
+                          cell_x, out_a, out_b, dst, dtype))
+        return rc;
+    if (dst_pitch < (int64_t)3 * gw || overlaps_inp(dst, dst_pitch * (gh - 1) + (int64_t)3 * gw, inp, H, W)) return HAT_EINVAL;
+    return lte_launch_dtype(a, LteU8{dst, (long long)dst_pitch, bgr ? 1 : 0}, tiles, dtype, stream);
+}
+
+extern "C" int hat_lte_query_yuv(const float* coef, const float* freq, int32_t ldc, int32_t ldf, const float* inp, int32_t H, int32_t W,
+                                 const float* phase, const void* w1, const float* b1, const void* w2, const float* b2, const void* w3,
+                                 const float* b3, const float* w4, const float* b4, int32_t gh, int32_t gw, float cell_y, float cell_x,
+                                 float out_a, float out_b, const HatYuvSurface* dst, const float* from_rgb12, int32_t dtype, void* stream) {
+    LteArgs a;
+    int64_t tiles;
+    if (!dst || !from_rgb12) return HAT_EINVAL;
+    if (int rc = lte_args(a, tiles, coef, freq, ldc, ldf, inp, H, W, phase, w1, b1, w2, b2, w3, b3, w4, b4, nullptr, nullptr, 0, gh, gw, cell_y,
+                          cell_x, out_a, out_b, dst->y, dtype))
+        return rc;
+    if (!hat_yuv_surface_ok(dst, 1, gh, gw)) return HAT_EINVAL;
+    const int64_t bps = dst->depth == 8 ? 1 : 2;
+    if (overlaps_inp(dst->y, dst->y_pitch * (gh - 1) + bps * gw, inp, H, W)) return HAT_EINVAL;
+    if (dst->cb) {
+        const int64_t ch = gh >> dst->sub_y, crow = (int64_t)dst->c_step * ((gw >> dst->sub_x) - 1) + bps;
+        if (overlaps_inp(dst->cb, dst->c_pitch * (ch - 1) + crow, inp, H, W) || overlaps_inp(dst->cr, dst->c_pitch * (ch - 1) + crow, inp, H, W))
+            return HAT_EINVAL;
+    }
+    const HatCsc k = load_csc(from_rgb12);
+    if (dst->depth == 8) return lte_launch_yuv<uint8_t>(a, *dst, k, HatSample<uint8_t>{}, tiles, dtype, stream);
+    return lte_launch_yuv<uint16_t>(a, *dst, k, deep_sample(dst->depth, dst->msb), tiles, dtype, stream);
 }

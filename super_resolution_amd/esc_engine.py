@@ -553,3 +553,51 @@ class ESCLTEEngine(ESCEngine):
         """The make_coord grid of an (h, w) image, every query with the cell cell_yx -> (3,h,w) fp32 planes * a + b (a fresh tensor)."""
         out = torch.empty(3, h, w, dtype=torch.float32, device=self.dev)
         return self._query(out, grid=(h, w), cell_yx=cell_yx, out_affine=out_affine)
+
+    # ---- frames: 8-bit and YCbCr in, any size out (DESIGN.md §4.20).  The sinks are hat_lte_query's own, so nothing of FrameBoundary
+    # (reflect-padding, conv_last's epilogues, the ensemble) applies: ESC's window attention reflects its own edges.
+    def _ws_f32(self, H: int, W: int, key: str, shape) -> torch.Tensor:
+        """An fp32 buffer in the workspace of the (1, H, W) frame shape, allocated with its first use (FrameBoundary._ws_buffer's rule)."""
+        ws = self._workspace(1, H, W)
+        t = ws.get(key)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = ws[key] = torch.zeros(shape, dtype=torch.float32, device=self.dev)
+            ws["bytes"] += t.numel() * 4
+        return t
+
+    def gen_feat_frame(self, H: int, W: int, fill) -> None:
+        """gen_feat of a frame that arrives as bytes: fill(x) writes its [0, 1] planes into x (1,3,H,W), the staging buffer of the
+        shape's workspace; the normalisation (x - 0.5) / 0.5 runs in place; then the encoder."""
+        with self._lock, torch.cuda.device(self.dev):
+            x = self._ws_f32(H, W, "x_frame", (1, 3, H, W))
+            fill(x)
+            x.sub_(0.5).div_(0.5)
+            self._forward(x)
+
+    def planes_buffer(self, H: int, W: int, h: int, w: int) -> torch.Tensor:
+        """The (1,3,h,w) fp32 image a co-sited YCbCr output is converted from, in the workspace of the (H, W) frame."""
+        with self._lock, torch.cuda.device(self.dev):
+            return self._ws_f32(H, W, "y_frame", (1, 3, h, w))
+
+    def _query_sink(self, fn, *dst, **kw):
+        if self._feat_ws is None:
+            raise RuntimeError("ESC-LTE: query before gen_feat: there are no features to query")
+        w, H, W = self._feat_ws
+        hd = ops.LTE_HIDDEN
+        with self._lock, torch.cuda.device(self.dev):
+            fn(self.lte, w["cf"], w["cf"].view(-1)[hd:], w["x"], *dst, H=H, W=W, ldc=2 * hd, ldf=2 * hd, dtype=self.dtype, **kw)
+
+    def query_grid_planes(self, out: torch.Tensor, cell_yx, out_affine=(1.0, 0.0)) -> torch.Tensor:
+        """query_grid into the caller's (3,h,w) or (1,3,h,w) contiguous fp32 tensor."""
+        return self._query(out, grid=tuple(out.shape[-2:]), cell_yx=cell_yx, out_affine=out_affine)
+
+    def query_grid_u8(self, out: torch.Tensor, cell_yx, bgr: bool = False, out_affine=(0.5, 0.5)) -> torch.Tensor:
+        """The grid of out's (h, w) -> out (1,h,w,3) uint8 (rows may be pitched): tensor2img's bytes of the image * a + b."""
+        self._query_sink(ops.lte_query_u8, out, grid=tuple(out.shape[-3:-1]), cell_yx=cell_yx, out_affine=out_affine, bgr=bgr)
+        return out
+
+    def query_grid_yuv(self, out_views, cell_yx, from_rgb, sub, depth: int = 8, msb=False, out_affine=(0.5, 0.5)) -> None:
+        """The grid of the Y view's (h, w) -> the views (y, cb, cr) of a centre-sited frame (ops.yuv_views) of the image * a + b."""
+        y, cb, cr = out_views
+        self._query_sink(ops.lte_query_yuv, y, cb, cr, from_rgb, grid=tuple(y.shape[-2:]), cell_yx=cell_yx, out_affine=out_affine, sub=sub,
+                         depth=depth, msb=msb)

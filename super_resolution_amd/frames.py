@@ -23,7 +23,8 @@ def _raw(t):
 
 
 def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", matrix: str = "bt601", full_range: bool = False, depth: int = 8,
-                   out_depth=None, msb=None, ensemble: int = 1, out_pixfmt=None, out_msb=None, siting: str = "center", out_siting=None):
+                   out_depth=None, msb=None, ensemble: int = 1, out_pixfmt=None, out_msb=None, siting: str = "center", out_siting=None,
+                   size=None, scale=None):
     """Generator: for every (h,w,3) uint8 array of `frames` (all of one size) yield the (s*h,s*w,3) uint8 array that
     `net.forward_u8` computes for it, in order.  `net`: a HAT / HATX module on a GPU, in eval mode.  The yielded array is
     the caller's own (copied out of the pinned buffer).  An empty sequence yields nothing.
@@ -36,7 +37,10 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
     subsampling in, any out; out_msb: the output words' alignment), in the same two-slot pipeline.
     ensemble 2 / 4 / 8: every frame through the geometric self-ensemble (HAT.forward_ensemble) of that many members.
     siting / out_siting (YCbCr pixel formats; yuv.SITINGS): the chroma siting of the frames and of the yielded frames (default:
-    the input's), as HAT.forward_yuv takes them; 'center' is the sequence as it always was."""
+    the input's), as HAT.forward_yuv takes them; 'center' is the sequence as it always was.
+    size=(h, w) or scale= (one of them): `net` is an arbitrary-scale network (ESCLTE) and every frame goes through `net.upscale_u8`
+    (rgb24) or `net.upscale_yuv` (every YCbCr pixfmt) to that size, in the same two-slot pipeline; the yielded arrays have the
+    resolved size's shape.  ensemble is then refused, and so is a network without `upscale_u8`.  Without either, nothing changes."""
     from .ops import ensemble_members
     ensemble = ensemble_members(ensemble)
     if pixfmt not in PIXFMTS:
@@ -50,7 +54,16 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
     skw = {} if (siting, out_siting) == ("center", "center") else {"siting": siting, "out_siting": out_siting}
     if skw and pixfmt == "rgb24":
         raise RuntimeError("siting and out_siting belong to the YCbCr pixel formats")
-    general = pixfmt != "rgb24" and (pixfmt not in PIXFMTS[1:4] or out_pixfmt not in (None, pixfmt) or out_msb is not None)
+    arb = size is not None or scale is not None
+    if arb:
+        if not hasattr(net, "upscale_u8"):
+            raise RuntimeError(f"upscale_frames: size= / scale= need an arbitrary-scale network with upscale_u8 / upscale_yuv (ESCLTE); "
+                               f"{type(net).__name__} has a fixed scale")
+        if (size is None) == (scale is None):
+            raise ValueError("upscale_frames takes exactly one of size=(h, w) and scale=, or neither")
+        if ensemble != 1:
+            raise RuntimeError("upscale_frames: the self-ensemble is not built for size= / scale= (ESCLTE's frame paths)")
+    general = pixfmt != "rgb24" and (arb or pixfmt not in PIXFMTS[1:4] or out_pixfmt not in (None, pixfmt) or out_msb is not None)
     yuv420 = pixfmt != "rgb24" and not general
     dev = next(net.parameters()).device
     if dev.type != "cuda":
@@ -60,7 +73,14 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
     if first is None:
         return
     first = np.ascontiguousarray(first)
-    s = net.upscale
+    s = None if arb else net.upscale
+
+    def out_hw(h, w):
+        """The output size of an (h, w) frame: the network's scale, or the resolved size= / scale= (ESCLTE.upscale's rule)."""
+        if not arb:
+            return s * h, s * w
+        return (int(h * scale), int(w * scale)) if size is None else (int(size[0]), int(size[1]))
+
     in_np, in_dt, out_dt = np.uint8, torch.uint8, torch.uint8
     if general:
         from . import yuv as _yuv
@@ -72,9 +92,20 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
         if first.ndim != 2 or first.dtype != in_np:
             raise RuntimeError(f"expected (rows,w) {np.dtype(in_np).name} {pixfmt} frames, got {first.shape} {first.dtype}")
         h, w = _yuv.frame_size_fmt(first.shape, pixfmt)
-        in_shape, out_shape, shape_text = first.shape, _yuv.frame_shape_fmt(s * h, s * w, out_pixfmt), str(tuple(first.shape)).replace(" ", "")
-        forward = lambda src, dst: net.forward_yuv(src, fmt=pixfmt, out_fmt=out_pixfmt, matrix=matrix, full_range=full_range, out=dst,
-                                                   depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, ensemble=ensemble, **skw)
+        in_shape, shape_text = first.shape, str(tuple(first.shape)).replace(" ", "")
+        if arb:
+            oh, ow = out_hw(h, w)
+            so = _yuv.LAYOUTS[out_pixfmt]
+            if oh < 1 or ow < 1 or (so[0] is not None and ((so[0] and ow % 2) or (so[1] and oh % 2))):
+                raise ValueError(f"upscale_frames: an output of {oh}x{ow} is no {out_pixfmt} frame")
+        out_shape = _yuv.frame_shape_fmt(*out_hw(h, w), out_pixfmt)
+        if arb:
+            forward = lambda src, dst: net.upscale_yuv(src, size=out_hw(h, w), fmt=pixfmt, out_fmt=out_pixfmt, matrix=matrix, full_range=full_range,
+                                                       out=dst, depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, siting=siting,
+                                                       out_siting=out_siting)
+        else:
+            forward = lambda src, dst: net.forward_yuv(src, fmt=pixfmt, out_fmt=out_pixfmt, matrix=matrix, full_range=full_range, out=dst,
+                                                       depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, ensemble=ensemble, **skw)
     elif yuv420:
         from . import yuv as _yuv
         out_depth = depth if out_depth is None else out_depth
@@ -93,8 +124,13 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
         if first.ndim != 3 or first.shape[2] != 3 or first.dtype != np.uint8:
             raise RuntimeError(f"expected (h,w,3) uint8 frames, got {first.shape} {first.dtype}")
         h, w, _ = first.shape
-        in_shape, out_shape, shape_text = (h, w, 3), (s * h, s * w, 3), f"({h},{w},3)"
-        forward = lambda src, dst: net.forward_u8(src, bgr=bgr, out=dst, ensemble=ensemble)
+        in_shape, out_shape, shape_text = (h, w, 3), out_hw(h, w) + (3,), f"({h},{w},3)"
+        if arb and min(out_shape) < 1:
+            raise ValueError(f"upscale_frames: an output of {out_shape[0]}x{out_shape[1]} is empty")
+        if arb:
+            forward = lambda src, dst: net.upscale_u8(src, size=out_shape[:2], bgr=bgr, out=dst)
+        else:
+            forward = lambda src, dst: net.forward_u8(src, bgr=bgr, out=dst, ensemble=ensemble)
     # Nothing of the device state stays entered across a yield: the buffers and the copy stream are made once, and every step
     # enters the device and takes the stream that is current THEN, so a caller may switch device or stream between frames.
     with torch.cuda.device(dev):

@@ -485,6 +485,54 @@ def lte_query(pl: PackedLte, coef, freq, inp, out, *, H: int, W: int, ldc: int, 
         "hat_lte_query"), tag=f"lte {'grid ' + str(gh) + 'x' + str(gw) if coord is None else 'Q=' + str(Q)} on {H}x{W}", nbytes=nbytes)
 
 
+def _lte_grid_args(what: str, pl: PackedLte, coef, freq, inp, H: int, W: int, ldc: int, ldf: int, grid, cell_yx, out_affine):
+    """What lte_query_u8 / lte_query_yuv pass ahead of their sink: the checks of lte_query's grid mode, then (the C arguments up to
+    out_b, the flops and the bytes of the launch without its stores)."""
+    gh, gw = int(grid[0]), int(grid[1])
+    if coef.dtype != torch.float32 or freq.dtype != torch.float32 or inp.dtype != torch.float32:
+        raise ValueError(f"{what} expects fp32 coef / freq rows and fp32 input planes")
+    if coef.numel() < (H * W - 1) * ldc + LTE_HIDDEN or freq.numel() < (H * W - 1) * ldf + LTE_HIDDEN or inp.numel() != 3 * H * W:
+        raise ValueError(f"{what}: coef / freq / inp do not hold a {H}x{W} map")
+    Q, hd = gh * gw, float(LTE_HIDDEN)
+    flops = Q * (4.0 * (2.0 * hd * hd * 3 + 2.0 * hd * 3 + 5.0 * hd) + 30.0)
+    nbytes = 4.0 * (min(4 * Q, H * W) * 2 * hd + 3 * H * W) + 3 * hd * hd * (2 if pl.w[0].element_size() == 2 else 4)
+    args = (_ptr(coef), _ptr(freq), ldc, ldf, _ptr(inp), H, W, _ptr(pl.phase), _ptr(pl.w[0]), _ptr(pl.b[0]), _ptr(pl.w[1]), _ptr(pl.b[1]),
+            _ptr(pl.w[2]), _ptr(pl.b[2]), _ptr(pl.w4), _ptr(pl.b4), gh, gw, float(cell_yx[0]), float(cell_yx[1]), float(out_affine[0]),
+            float(out_affine[1]))
+    return args, flops, nbytes
+
+
+def lte_query_u8(pl: PackedLte, coef, freq, inp, out, *, H: int, W: int, ldc: int, ldf: int, dtype: int, grid, cell_yx=(0.0, 0.0),
+                 out_affine=(1.0, 0.0), bgr: bool = False):
+    """lte_query's grid mode ending in bytes: out (h, w, 3) or (1, h, w, 3) uint8 with interleaved pixels (rows may be pitched) =
+    planes_to_u8 of what lte_query would write; no fp32 image is written (hat_lte_query_u8)."""
+    lib = _lib.load()
+    gh, gw = int(grid[0]), int(grid[1])
+    o = out[0] if out.dim() == 4 and out.shape[0] == 1 else out
+    if o.dtype != torch.uint8 or not o.is_cuda or tuple(o.shape) != (gh, gw, 3) or o.stride(2) != 1 or o.stride(1) != 3:
+        raise RuntimeError(f"lte_query_u8 needs a ({gh},{gw},3) uint8 device destination with interleaved pixels, got {tuple(out.shape)} {out.dtype}")
+    args, flops, nbytes = _lte_grid_args("lte_query_u8", pl, coef, freq, inp, H, W, ldc, ldf, grid, cell_yx, out_affine)
+    _timed(f"lte_query_kernel<{_TNAME[dtype]}, u8>", flops, lambda: _lib.check(
+        lib.hat_lte_query_u8(*args, o.data_ptr(), o.stride(0), int(bool(bgr)), dtype, _stream()), "hat_lte_query_u8"),
+        tag=f"lte grid {gh}x{gw} on {H}x{W} -> u8", nbytes=nbytes + 3.0 * gh * gw)
+
+
+def lte_query_yuv(pl: PackedLte, coef, freq, inp, y, cb, cr, from_rgb, *, H: int, W: int, ldc: int, ldf: int, dtype: int, grid,
+                  cell_yx=(0.0, 0.0), out_affine=(1.0, 0.0), sub, depth: int = 8, msb=False):
+    """lte_query's grid mode ending in a YCbCr frame: the views Y (1,h,w), Cb, Cr of any subsampling (None, None and sub=None: grey),
+    centre-sited = planes_to_yuv of what lte_query would write; no fp32 image is written (hat_lte_query_yuv)."""
+    lib = _lib.load()
+    gh, gw = int(grid[0]), int(grid[1])
+    surf = yuv_surface(y, cb, cr, sub=sub, depth=depth, msb=msb, what="lte_query_yuv")
+    if tuple(y.shape) != (1, gh, gw):
+        raise RuntimeError(f"lte_query_yuv: a {gh}x{gw} grid needs a (1,{gh},{gw}) Y view, got {tuple(y.shape)}")
+    args, flops, nbytes = _lte_grid_args("lte_query_yuv", pl, coef, freq, inp, H, W, ldc, ldf, grid, cell_yx, out_affine)
+    m, name = _f12(from_rgb), _sub_name(sub, depth)
+    _timed(f"lte_query_kernel<{_TNAME[dtype]}, {name}>", flops, lambda: _lib.check(
+        lib.hat_lte_query_yuv(*args, C.byref(surf), m, dtype, _stream()), "hat_lte_query_yuv"),
+        tag=f"lte grid {gh}x{gw} on {H}x{W} -> {name}", nbytes=nbytes + 3.0 * gh * gw)
+
+
 LOG2E = 1.4426950408889634
 
 

@@ -3,6 +3,7 @@
     python -m super_resolution_amd.video -opt options/test/HAT-S_SRx4.yml -i in.y4m -o out.y4m [--matrix bt709] [--full-range]
                                          [--out-depth 10] [--out-chroma 444] [--self-ensemble [N]]
                                          [--chroma-loc auto|center|left|topleft] [--out-chroma-loc ...]
+    python -m super_resolution_amd.video --lte-model esc-lte.pth --size 1080 1920 -i 720p.y4m -o 1080p.y4m [the flags above]
 
 y4m.Reader -> frames.upscale_frames(pixfmt='i420') -> y4m.Writer.  W and H of the header are multiplied by the network's
 scale; every other header token (frame rate, interlacing, aspect, colour space, X comments) is copied.  Decoding and
@@ -18,6 +19,10 @@ every stream as this tool always did.  auto takes it from the header (y4m.siting
 4:2:2 header cannot say, so ask for left).  --out-chroma-loc sets the output's (default: the input's), and the written header
 says what was written.
 --self-ensemble [N] runs every frame through the geometric self-ensemble of N = 2, 4 or 8 (the default) members.
+--lte-model ckpt.pth, in place of -opt, loads the arbitrary-scale network (ESCLTE.from_checkpoint, the reference's esc_arb checkpoint)
+and needs --size H W or --scale S: the output stream has exactly that size (int(h S), int(w S) with --scale), even where the output's
+chroma is subsampled; W and H of the header are set to it and every other token is copied (y4m.sized_header).  --self-ensemble does
+not go with it.
 """
 from __future__ import annotations
 
@@ -27,14 +32,16 @@ from . import y4m
 
 
 def upscale_file(net, src: str, dst: str, *, matrix: str = "bt601", full_range: bool = False, out_depth=None, ensemble: int = 1,
-                 out_chroma=None, chroma_loc: str = "center", out_chroma_loc=None) -> dict:
+                 out_chroma=None, chroma_loc: str = "center", out_chroma_loc=None, size=None, scale=None) -> dict:
     """Every frame of the .y4m file `src` through `net` into `dst`; returns {'frames', 'in', 'out'} (sizes as (w, h)), and for
     streams that are not 8-bit on both sides also 'depth' and 'out_depth'; with ensemble 2 / 4 / 8 (the self-ensemble of every
     frame, frames.upscale_frames) also 'ensemble'; for streams that are not 4:2:0 on both sides also 'chroma' and 'out_chroma'
     (out_chroma '420' / '422' / '444' / 'mono'; default: the input's).  chroma_loc 'auto' / 'center' / 'left' / 'topleft': the
     input's chroma siting ('auto': y4m.siting_of the header); out_chroma_loc: the output's (default: the input's).  Unless both
     are 'center' — then the header is copied as always — the result also holds 'chroma_loc' and 'out_chroma_loc' and the output
-    header names the output's siting (y4m.with_siting)."""
+    header names the output's siting (y4m.with_siting).
+    size=(h, w) or scale=: `net` is an arbitrary-scale network (ESCLTE; frames.upscale_frames' size= / scale=) and the output stream
+    has that size."""
     from . import frames
     from .ops import ensemble_members
     ensemble = ensemble_members(ensemble)
@@ -44,7 +51,14 @@ def upscale_file(net, src: str, dst: str, *, matrix: str = "bt601", full_range: 
         out_depth = depth if out_depth is None else out_depth
         chroma = y4m.chroma(rd.header)
         out_chroma = chroma if out_chroma is None else out_chroma
-        hdr = y4m.with_chroma(y4m.with_depth(y4m.scaled_header(rd.header, net.upscale), out_depth), out_chroma)
+        if size is None and scale is None:
+            sized, akw = y4m.scaled_header(rd.header, net.upscale), {}
+        else:
+            if (size is None) == (scale is None):
+                raise ValueError("upscale_file takes exactly one of size=(h, w) and scale=, or neither")
+            oh, ow = (int(rd.h * scale), int(rd.w * scale)) if size is None else (int(size[0]), int(size[1]))
+            sized, akw = y4m.sized_header(rd.header, ow, oh), {"size": (oh, ow)}
+        hdr = y4m.with_chroma(y4m.with_depth(sized, out_depth), out_chroma)
         siting, out_siting = resolve_chroma_loc(rd.header, chroma_loc, out_chroma_loc)
         skw = {} if (siting, out_siting) == ("center", "center") else {"siting": siting, "out_siting": out_siting}
         if skw:
@@ -55,7 +69,7 @@ def upscale_file(net, src: str, dst: str, *, matrix: str = "bt601", full_range: 
         info = {} if chroma == "420" and out_chroma == "420" else {"chroma": chroma, "out_chroma": out_chroma}
         fkw = {"out_pixfmt": y4m.CHROMAS[out_chroma]} if info else {}
         with y4m.Writer(dst, hdr, chroma=True) as wr:
-            for out in frames.upscale_frames(net, rd, pixfmt=rd.fmt, matrix=matrix, full_range=full_range, **kw, **fkw, **skw):
+            for out in frames.upscale_frames(net, rd, pixfmt=rd.fmt, matrix=matrix, full_range=full_range, **kw, **fkw, **skw, **akw):
                 wr.write(out)
                 n += 1
     loc = {"chroma_loc": siting, "out_chroma_loc": out_siting} if skw else {}
@@ -75,9 +89,35 @@ def resolve_chroma_loc(header: dict, chroma_loc: str = "center", out_chroma_loc=
     return siting, out_siting
 
 
+class _Parser(argparse.ArgumentParser):
+    """The flags that depend on each other are checked where the others are: parse_args exits on them as on a bad choice."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if (ns.opt is None) == (ns.lte_model is None):
+            self.error("one of -opt (a fixed-scale network) and --lte-model (the arbitrary-scale network) is required")
+        if ns.lte_model is not None:
+            if (ns.size is None) == (ns.scale is None):
+                self.error("--lte-model needs exactly one of --size H W and --scale S")
+            if ns.self_ensemble is not None:
+                self.error("--self-ensemble is not built for --lte-model")
+            if ns.scale is not None and not ns.scale > 0:
+                self.error("--scale must be positive")
+            if ns.size is not None and min(ns.size) < 1:
+                self.error("--size must be positive")
+        elif ns.size is not None or ns.scale is not None:
+            self.error("--size and --scale belong to --lte-model: a network loaded with -opt has a fixed scale")
+        return ns
+
+
 def parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(description="upscale a YUV4MPEG2 (.y4m) file of 4:2:0 video (8, 10, 12 or 16 bits) on the device")
-    ap.add_argument("-opt", required=True, help="test YAML (network_g, path.pretrain_network_g ...), as for super_resolution_amd.test")
+    ap = _Parser(description="upscale a YUV4MPEG2 (.y4m) file of 4:2:0 video (8, 10, 12 or 16 bits) on the device")
+    ap.add_argument("-opt", default=None, help="test YAML (network_g, path.pretrain_network_g ...), as for super_resolution_amd.test")
+    ap.add_argument("--lte-model", default=None, metavar="CKPT",
+                    help="in place of -opt: a checkpoint of the arbitrary-scale ESC-LTE (the reference's esc_arb format); needs --size or --scale")
+    ap.add_argument("--size", type=int, nargs=2, default=None, metavar=("H", "W"), help="with --lte-model: the output size")
+    ap.add_argument("--scale", type=float, default=None, metavar="S", help="with --lte-model: the output is int(h S) x int(w S)")
+    ap.add_argument("--compute-dtype", default="bf16", choices=["bf16", "fp32"], help="with --lte-model: the compute dtype (default: bf16)")
     ap.add_argument("-i", "--input", required=True)
     ap.add_argument("-o", "--output", required=True)
     ap.add_argument("--matrix", default="bt601", choices=["bt601", "bt709", "bt2020nc"],
@@ -100,12 +140,18 @@ def parser() -> argparse.ArgumentParser:
 
 def main(argv=None):
     args = parser().parse_args(argv)
-    from .models import HATModel
-    from .test import parse_options
-    model = HATModel(parse_options(args.opt), device=args.device)
-    info = upscale_file(model.get_bare_model(model.net_g), args.input, args.output, matrix=args.matrix, full_range=args.full_range,
+    if args.lte_model is not None:
+        import torch
+        from .archs.esc_lte_arch import ESCLTE
+        net = ESCLTE.from_checkpoint(torch.load(args.lte_model, map_location="cpu", weights_only=True), compute_dtype=args.compute_dtype).to(args.device)
+    else:
+        from .models import HATModel
+        from .test import parse_options
+        model = HATModel(parse_options(args.opt), device=args.device)
+        net = model.get_bare_model(model.net_g)
+    info = upscale_file(net, args.input, args.output, matrix=args.matrix, full_range=args.full_range,
                         out_depth=args.out_depth, ensemble=args.self_ensemble or 1, out_chroma=args.out_chroma, chroma_loc=args.chroma_loc,
-                        out_chroma_loc=args.out_chroma_loc)
+                        out_chroma_loc=args.out_chroma_loc, size=args.size, scale=args.scale)
     print(info)
     return info
 

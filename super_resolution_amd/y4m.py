@@ -171,6 +171,16 @@ def scaled_header(hdr: dict, scale: int) -> dict:
     return dict(hdr, W=hdr["W"] * scale, H=hdr["H"] * scale, X=list(hdr.get("X", [])))
 
 
+def sized_header(hdr: dict, w: int, h: int) -> dict:
+    """The header of a stream resized to w x h (an arbitrary-scale network's output): W and H set, every other token copied.  The
+    pixel aspect ratio `A` is copied as it is even where the two axes are scaled by different factors: the caller chose the size,
+    and whether the pixels or the picture keep their shape is the caller's to say."""
+    w, h = int(w), int(h)
+    if w < 1 or h < 1:
+        raise Y4MError(f"a stream of {w}x{h} is empty")
+    return dict(hdr, W=w, H=h, X=list(hdr.get("X", [])))
+
+
 def _readline(f, limit: int = 4096) -> bytes:
     line = f.readline(limit)
     if len(line) == limit and not line.endswith(b"\n"):
