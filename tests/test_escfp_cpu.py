@@ -209,7 +209,7 @@ def test_engine_packs_on_the_host_and_esc_keeps_refusing_dim_48():
     cfg, sd, _, _ = R.load_case("a")
     net = build_network(dict(cfg, type="ESCFP"))
     e = ESCFPEngine(net.cfg, sd, "cpu", "bf16")
-    assert e.C == 48 and e.heads == 3 and e._kpad == 2880 and e.ptab.shape == (2, 4) and e.blocks[0].convs[0][0] is not None
+    assert e.C == 48 and e.heads == 3 and e._kpad == 2880 and e.head.ptab.shape == (2, 4) and e.blocks[0].convs[0][0] is not None
     with pytest.raises(ValueError, match="compute_dtype"):
         ESCFPEngine(net.cfg, sd, "cpu", "fp16")
     with pytest.raises(ValueError, match="upscaling_factor=5"):
