@@ -1195,6 +1195,30 @@ int hat_escfp_weights(const float* partials, int32_t nblk, int64_t npix, const f
 int hat_escfp_shuffle_bicubic(const float* rows, const float* x, const float* ptab, float* y, int32_t B, int32_t H, int32_t W,
                               int32_t s, int32_t ld, void* stream);
 
+/*
+ * The shuffle heads of the ESC family into a frame: PixelShuffle(s) of fp32 rows, plus a base image, stored as
+ * bytes or as a YCbCr surface.  No fp32 image is written.  The value of output pixel (b, c, Y, X), Y < s H, X < s W, is
+ *     rows[b][Y / s][X / s][c s^2 + (Y % s) s + X % s]  (+ base[b][c][Y / s][X / s] when base is not NULL: one rounded fp32 add)
+ * which is what hat_esc_shuffle_add (with base) and hat_shuffle_planes (without) store, and the top-left (h_out, w_out) pixels are
+ * converted as hat_planes_to_u8 / hat_planes_to_yuv convert them: the results are those of the two-step composition bit for bit.
+ *     rows     (B,H,W,ld) fp32 rows, ld >= 3 s^2;  base  NULL or (B,3,H,W) fp32 planes;  s in 1..8
+ *     h_out, w_out   the crop, 1 <= h_out <= s H, 1 <= w_out <= s W
+ *
+ * hat_shuffle_to_u8   dst (B,h_out,w_out,3) interleaved bytes, rows dst_pitch >= 3 w_out bytes apart, samples dst_bstride bytes apart
+ *   (ignored for B == 1); bgr != 0 swaps bytes 0 and 2.  No alignment is asked of dst.
+ * hat_shuffle_to_yuv  dst one HatYuvSurface of (B, h_out, w_out) frames, any subsampling or grey, 8 / 10 / 12 / 16 bits, msb either
+ *   way, centre-sited, checked as hat_planes_to_yuv checks it; from_rgb12 as there.  A co-sited output is written from planes
+ *   (hat_planes_to_yuv_sited).
+ * HAT_EINVAL, before any launch: a null rows, dst (or dst->y) or from_rgb12; rows or base not 4-byte aligned; B, H, W, s, h_out or
+ *   w_out < 1; B or h_out > 65535; H W > 2^31 - 1; ld < 3 s^2; a crop beyond (s H, s W); a pitch below the row, overlapping samples of a batch, odd
+ *   pitches of 16-bit words; w_out odd where the surface subsamples horizontally, h_out odd where vertically.
+ * HAT_EUNSUPPORTED: s > 8.
+ */
+int hat_shuffle_to_u8(const float* rows, int32_t ld, const float* base, int32_t B, int32_t H, int32_t W, int32_t s, uint8_t* dst,
+                      int64_t dst_pitch, int64_t dst_bstride, int32_t h_out, int32_t w_out, int32_t bgr, void* stream);
+int hat_shuffle_to_yuv(const float* rows, int32_t ld, const float* base, int32_t B, int32_t H, int32_t W, int32_t s,
+                       const HatYuvSurface* dst, int32_t h_out, int32_t w_out, const float* from_rgb12, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

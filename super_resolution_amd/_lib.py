@@ -266,6 +266,11 @@ SIGNATURES = {
                          + [C.c_int32, C.c_int32] + [C.c_float] * 4 + [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "hat_lte_query_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 9
                           + [C.c_int32, C.c_int32] + [C.c_float] * 4 + [C.POINTER(HatYuvSurface), C.c_void_p, C.c_int32, C.c_void_p]),
+    # the shuffle heads into a frame: rows, ld, base, B, H, W, s, then the sink, the crop and the stream
+    "hat_shuffle_to_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 3
+                          + [C.c_void_p]),
+    "hat_shuffle_to_yuv": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(HatYuvSurface), C.c_int32, C.c_int32,
+                                                                                              C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -71,12 +71,15 @@ class _Block(_Holder):  # esc_arch.py:256-274
 
 _NOT_BUILT = ("ESC runs its float forward only: {} is not built for it (DESIGN.md §7); `forward` and, through it, "
               "tile_parallel work")
+_NEW_NAME = ("ESC runs its float forward only under HAT's forward_* names: {} is `{}` in this family (upscale_u8, upscale_gt_u8, "
+             "upscale_to_u8, upscale_yuv, upscale_ensemble; DESIGN.md §4.21)")
 
 
 class _ESCNet(HAT):
     """What the networks of the ESC family share above their module trees: a `HAT` from the engine up — `compute_dtype` /
     `set_compute_dtype`, `use_graph` and the weight-change tracking are HAT's own — with the float forward as the only path, and the
     `to_img` scale conversion of `load_state_dict`.  A subclass builds its tree, sets `cfg`, and names its engine in `_make_engine`."""
+    arbitrary_scale = False   # True: the network has no fixed scale and its frame paths take size= / scale= (ESCLTE)
 
     def extra_repr(self) -> str:
         return ", ".join(f"{k}={v}" for k, v in self.cfg.items())
@@ -144,8 +147,71 @@ class _ESCNet(HAT):
         raise NotImplementedError(_NOT_BUILT.format("row-band sharding"))
 
 
+class _FixedScaleNet(_ESCNet):
+    """The fixed-scale networks of the family (ESC, ESCReal, ESCRealM, ESCFP): frames in, frames out under the `upscale_*` names, as
+    ESCLTE has them.  Semantics, errors and `out=` rules are those of HAT's `forward_*` namesakes, whose module-level wrappers (they
+    resolve matrices, devices and batch axes) these calls go through; the engine side is frame_boundary.FrameBoundary on ESCEngine.
+    A frame of any size is taken as it is, nothing is padded, and the network's own refusals apply (a reflection larger than the
+    frame; a side below 4 for the skip branch; a batch where the network takes one frame).  The result is `upscale` times the frame:
+    what the network really applies (ESCReal's default head: 4).  All run eagerly also with use_graph=True.  HAT's own names for
+    these calls keep raising NotImplementedError, and say which call took their place.  DESIGN.md §4.21."""
+
+    def _check_u8_input(self, t):   # (HAT's, without in_chans: the family's networks are three-channel)
+        if self.training:
+            raise RuntimeError("this ESC implements the inference forward pass only: call .eval() first (training is out of scope)")
+        if not t.is_cuda:
+            raise RuntimeError("ESC needs a GPU tensor: the MI355X HIP path is the only path (no CPU fallback)")
+
+    def forward_ensemble(self, x, n: int = 8):
+        raise NotImplementedError(_NEW_NAME.format("the self-ensemble", "upscale_ensemble"))
+
+    def forward_to_u8(self, *a, **k):
+        raise NotImplementedError(_NEW_NAME.format("the byte frame path", "upscale_u8 / upscale_gt_u8 / upscale_to_u8"))
+
+    forward_u8 = forward_gt_u8 = forward_to_u8
+
+    def forward_yuv420(self, *a, **k):
+        raise NotImplementedError(_NEW_NAME.format("the YCbCr frame path", "upscale_yuv"))
+
+    forward_yuv = forward_yuv420
+
+    def upscale_u8(self, frame, *, bgr: bool = False, out=None, ensemble: int = 1):
+        """(h,w,3) or (B,h,w,3) uint8 device frames -> (B,S h,S w,3) uint8: HAT.forward_u8's contract.  Equal to hat_u8_to_planes ->
+        `forward` -> hat_planes_to_u8; where the head ends in a fused sink (ESCEngine.u8_fused_calls counts them) no fp32 image is
+        written."""
+        return HAT.forward_u8(self, frame, bgr=bgr, out=out, ensemble=ensemble)
+
+    def upscale_gt_u8(self, gt, *, bgr: bool = False, out=None, ensemble: int = 1):
+        """Ground-truth frames in, the super-resolution of their own bicubic low-resolution image out: HAT.forward_gt_u8's contract
+        (a result factor of 2, 3 or 4)."""
+        return HAT.forward_gt_u8(self, gt, bgr=bgr, out=out, ensemble=ensemble)
+
+    def upscale_to_u8(self, x, *, crop=None, bgr: bool = False, out=None, ensemble: int = 1):
+        """`forward(x)` handed over as bytes: (B,3,H,W) float planes in -> (B,h_out,w_out,3) uint8, crop = (h_out, w_out) the top-left
+        pixels kept (default: all of (S H, S W)): HAT.forward_to_u8's contract."""
+        self._check_u8_input(x)
+        with torch.no_grad():
+            return self.engine(x.device).forward_to_u8(x, crop=crop, bgr=bgr, out=out, ensemble=ensemble)
+
+    def upscale_yuv(self, frame, *, fmt: str, out_fmt=None, matrix: str = "bt601", full_range: bool = False, depth: int = 8, out_depth=None,
+                    msb=None, out_msb=None, siting: str = "center", out_siting=None, out=None, ensemble: int = 1):
+        """YCbCr frames of any layout of yuv.LAYOUTS in, any out: HAT.forward_yuv's contract.  A centre-sited output of a shuffle or
+        conv head is stored by the head's fused sink; a co-sited one is converted from planes (hat_planes_to_yuv_sited)."""
+        return HAT.forward_yuv(self, frame, fmt=fmt, out_fmt=out_fmt, matrix=matrix, full_range=full_range, depth=depth, out_depth=out_depth,
+                               msb=msb, out_msb=out_msb, out=out, ensemble=ensemble, siting=siting, out_siting=out_siting)
+
+    def upscale_ensemble(self, x, n: int = 8):
+        """The geometric self-ensemble of `forward`: HAT.forward_ensemble's contract (n in 1, 2, 4, 8; the transposed members run
+        the transposed frame)."""
+        from .. import ops
+        n = ops.ensemble_members(n)
+        self._check_u8_input(x)
+        with torch.no_grad():
+            return self.engine(x.device).forward_ensemble(x, n).to(x.dtype, copy=n == 1)   # (n = 1: the workspace's buffer)
+
+
 @ARCH_REGISTRY.register()
-class ESC(_ESCNet):
+class ESC(_FixedScaleNet):
     """The ESC network on the MI355X.  It is a `HAT` from the engine up — `compute_dtype` / `set_compute_dtype`, `use_graph` and the
     weight-change tracking are HAT's own — over a module tree and an engine of its own.
 

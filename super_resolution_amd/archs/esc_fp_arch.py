@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from ..registry import ARCH_REGISTRY
-from .esc_arch import _ConvFFN, _ESCNet, _LayerNorm, _WindowAttention
+from .esc_arch import _ConvFFN, _FixedScaleNet, _LayerNorm, _WindowAttention
 from .hat_arch import _Holder
 
 
@@ -49,14 +49,15 @@ class _Block(_Holder):  # esc_fp_arch.py:247-264
 
 
 @ARCH_REGISTRY.register()
-class ESCFP(_ESCNet):
+class ESCFP(_FixedScaleNet):
     """ESCFP on the MI355X.  Everything from the engine up is shared with `ESC` (and through it `HAT`'s): `compute_dtype`,
     `use_graph`, the weight-change tracking, `tile_parallel`, the `ESRModel` harness.
 
     Built: dim 48, pdim 16, kernel_size 13, window_size 32, num_heads 3, int(48 exp_ratio) in {60, 72, 96} (exp_ratio 1.25, 1.5, 2),
     upscaling_factor 2, 3 or 4, any n_blocks / conv_blocks; anything else is a ValueError when the engine packs.  Any batch size.
     `attn_type` selects an implementation in the reference, not a function: all three values run hat_window_attention_r.
-    `forward_ensemble`, the byte and YCbCr paths, row bands and plans raise NotImplementedError, as for `ESC`.
+    Frames go in and out under the `upscale_*` names (`upscale_u8`, `upscale_gt_u8`, `upscale_to_u8`, `upscale_yuv`, `upscale_ensemble`: DESIGN.md §4.21);
+    HAT's `forward_ensemble` / `forward_u8` / `forward_yuv` names, row bands and plans raise NotImplementedError, as for `ESC`.
     Extra (non-reference) keywords: `compute_dtype` ('bf16' | 'fp32') and `use_graph`."""
 
     def __init__(self, dim: int, pdim: int, kernel_size: int, n_blocks: int, conv_blocks: int, window_size: int, num_heads: int,

@@ -56,6 +56,7 @@ class ESCLTE(_ESCNet):
     `query_rgb` and the three `upscale` calls run eagerly also with `use_graph=True`.
     One frame per call.  `forward_ensemble`, the fixed-scale byte and YCbCr entry points (`forward_u8`, `forward_yuv`, ...), row bands
     and plans raise NotImplementedError, as for `ESC`: this network's frame paths are `upscale_u8` and `upscale_yuv`."""
+    arbitrary_scale = True   # frames.upscale_frames: size= / scale= go to upscale_u8 / upscale_yuv; nothing else does
 
     def __init__(self, dim: int = 64, pdim: int = 16, kernel_size: int = 13, n_blocks: int = 5, conv_blocks: int = 5, window_size: int = 32,
                  num_heads: int = 4, exp_ratio: float = 1.25, hidden_dim: int = 256, hidden_list=(256, 256, 256), compute_dtype: str = "bf16",

@@ -49,7 +49,8 @@ class ESCReal(ESC):
     Built: ESC's limits (dim 64, pdim 16, kernel_size 13, window_size 32, num_heads 4, exp_ratio 1.25 or 2, any n_blocks /
     conv_blocks), checked when the engine packs; one frame per forward; frames with a side below 4 are refused (the skip branch's
     reflect pad of 3).  The default head outputs x4 whatever `upscaling_factor`; DySample outputs x`upscaling_factor` (2, 3, 4).
-    `forward_ensemble`, the byte and YCbCr paths, row bands and plans raise NotImplementedError, as for `ESC`."""
+    Frames go in and out under the `upscale_*` names (`upscale_u8`, `upscale_gt_u8`, `upscale_to_u8`, `upscale_yuv`, `upscale_ensemble`: DESIGN.md §4.21);
+    HAT's `forward_ensemble` / `forward_u8` / `forward_yuv` names, row bands and plans raise NotImplementedError, as for `ESC`."""
 
     def __init__(self, dim: int, pdim: int, kernel_size: int, n_blocks: int, conv_blocks: int, window_size: int, num_heads: int,
                  upscaling_factor: int, exp_ratio: int = 2, attn_type: str = 'Flex', use_dysample: bool = False,

@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from ..packing import UNI_UPSAMPLERS
 from ..registry import ARCH_REGISTRY
-from .esc_arch import _Block, _ESCNet
+from .esc_arch import _Block, _FixedScaleNet
 from .esc_real_arch import _DySample
 from .hat_arch import HAT
 
@@ -65,14 +65,15 @@ class _UniUpsample(nn.Sequential):  # esc_real_arch.py:478-574
 
 
 @ARCH_REGISTRY.register()
-class ESCRealM(_ESCNet):
+class ESCRealM(_FixedScaleNet):
     """ESCRealM on the MI355X.  Everything from the engine up is the ESC family's (and through it `HAT`'s): `compute_dtype`,
     `use_graph`, the weight-change tracking, `tile_parallel`, the `ESRModel` harness.
 
     Built: ESC's limits (dim 64, pdim 16, kernel_size 13, window_size 32, num_heads 4, exp_ratio 1.25 or 2, any n_blocks /
     conv_blocks); upscaling_factor 1..4; `mid_dim` a multiple of 16 for "pixelshuffle", 48 or 64 for "dysample"; "conv" only on the
     plain stem; all checked when the engine packs.  One frame per forward; the body's frame needs sides of at least 4.
-    `forward_ensemble`, the byte and YCbCr paths, row bands and plans raise NotImplementedError, as for `ESC`."""
+    Frames go in and out under the `upscale_*` names (`upscale_u8`, `upscale_gt_u8`, `upscale_to_u8`, `upscale_yuv`, `upscale_ensemble`: DESIGN.md §4.21);
+    HAT's `forward_ensemble` / `forward_u8` / `forward_yuv` names, row bands and plans raise NotImplementedError, as for `ESC`."""
 
     def __init__(self, dim: int, pdim: int, kernel_size: int, n_blocks: int, conv_blocks: int, window_size: int, num_heads: int,
                  upscaling_factor: int, exp_ratio: int = 2, attn_type: str = 'Flex', mid_dim: int = 48, upsampler: str = "nearest+conv",

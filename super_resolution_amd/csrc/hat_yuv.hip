@@ -69,21 +69,6 @@ __global__ __launch_bounds__(256) void yuv_to_planes_sited_kernel(const T* __res
     for (int c = 0; c < 3; ++c) o[c * plane] = rgb[c];
 }
 
-// four samples of one row from o: one store (a dword of bytes, 8 bytes of words) where all four are there and o is aligned to
-// that store, single samples otherwise
-template <typename T> __device__ __forceinline__ void store_row4(T* o, const unsigned (&v)[4], int n) {
-    if (n == 4 && (reinterpret_cast<uintptr_t>(o) & (4 * sizeof(T) - 1)) == 0) {
-        if constexpr (sizeof(T) == 1) {
-            *reinterpret_cast<unsigned*>(o) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
-        } else {
-            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-            *reinterpret_cast<u32x2*>(o) = u32x2{v[0] | (v[1] << 16), v[2] | (v[3] << 16)};
-        }
-    } else {
-        for (int i = 0; i < n; ++i) o[i] = (T)v[i];
-    }
-}
-
 // one thread = (1 + SUB_Y) rows x four columns (4:2:0: two 2 x 2 blocks, rows are not independent there).  Per row and plane 16
 // contiguous bytes are loaded; the four Y samples of a row go out through store_row4.  4:2:0 and 4:2:2: the two Cb and two Cr
 // samples are single stores (planar or interleaved: the step decides); 4:4:4: four samples a row, through store_row4 when planar.

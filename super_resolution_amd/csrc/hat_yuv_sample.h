@@ -1,6 +1,7 @@
 // hat_yuv_sample.h — what the kernels that read or write YCbCr samples share beyond hat_common.h's arithmetic: the sample types
 // (bytes, n-bit codes in 16-bit words), byte addressing of a sample, and the host side's matrix and deep-sample arguments.
-// Included by hat_yuv.hip (the frame boundary) and hat_lte.hip (the YCbCr sink of hat_lte_query).  HIP sources only.
+// Included by hat_yuv.hip (the frame boundary), hat_lte.hip (the YCbCr sink of hat_lte_query) and hat_esc_sink.hip (the shuffle
+// heads' sinks).  HIP sources only.
 #pragma once
 #include <type_traits>
 
@@ -38,6 +39,21 @@ template <> struct HatSample<uint16_t> {
 template <typename T> __device__ __forceinline__ T& sample_at(T* base, size_t bytes) {
     using byte_t = typename std::conditional<std::is_const<T>::value, const char, char>::type;
     return *reinterpret_cast<T*>(reinterpret_cast<byte_t*>(base) + bytes);
+}
+
+// four samples of one row from o: one store (a dword of bytes, 8 bytes of words) where all four are there and o is aligned to
+// that store, single samples otherwise
+template <typename T> __device__ __forceinline__ void store_row4(T* o, const unsigned (&v)[4], int n) {
+    if (n == 4 && (reinterpret_cast<uintptr_t>(o) & (4 * sizeof(T) - 1)) == 0) {
+        if constexpr (sizeof(T) == 1) {
+            *reinterpret_cast<unsigned*>(o) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+        } else {
+            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+            *reinterpret_cast<u32x2*>(o) = u32x2{v[0] | (v[1] << 16), v[2] | (v[3] << 16)};
+        }
+    } else {
+        for (int i = 0; i < n; ++i) o[i] = (T)v[i];
+    }
 }
 
 HatCsc load_csc(const float* m12) {

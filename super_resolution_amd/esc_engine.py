@@ -19,6 +19,7 @@ from . import ops
 from .engine_base import EngineBase
 from .esc_parts import (LN_EPS, ConvHead, DySampleHead, Feat0Residual, LTEHead, NearestX4Head, PlainStem, ShuffleAddHead, ShuffleBicubicHead,
                         ShufflePlanesHead, SkipResidual, StepsHead, UnshuffledSkipResidual, UnshuffledStem)
+from .frame_boundary import FrameBoundary
 from .ops import O_NHWC_F32, O_NHWC_T
 from .packing import _ESC
 
@@ -63,7 +64,10 @@ def _check_esc(cfg):
         raise ValueError(f"ESC with exp_ratio={cfg['exp_ratio']} is not supported: hat_esc_convffn is built for exp_ratio 1.25 and 2")
 
 
-class ESCEngine(EngineBase):
+class ESCEngine(FrameBoundary, EngineBase):
+    """The frame boundary (frame_boundary.FrameBoundary: bytes, ground truth, YCbCr, the self-ensemble) is mixed in with two hooks
+    of its own: a frame is not padded (the window attention reflects its own edges, the unshuffled stem pads itself), and the
+    factor between a frame and its result is the one the stem and the head really apply.  DESIGN.md §4.21."""
     WS_MAX = 4   # entries of the workspace LRU
 
     def __init__(self, cfg: dict, sd: dict, device, compute_dtype: str = "bf16"):
@@ -75,7 +79,9 @@ class ESCEngine(EngineBase):
         if compute_dtype not in ops.DTYPE_CODE:
             raise ValueError(f"compute_dtype {compute_dtype!r}: expected 'bf16' or 'fp32'")
         super().__init__(device, compute_dtype, self.WS_MAX)   # (a host device is taken: the engine then packs and never runs)
-        self.cfg, dt, self.batches = dict(cfg), self.dtype, batches
+        self.cfg, dt, self.batches = dict(cfg, in_chans=3), self.dtype, batches
+        self.u8_fused_calls = self.u8_planes_calls = 0   # 8-bit forwards that ended in a fused sink / in hat_planes_to_u8
+        self.yuv_fused_calls = self.yuv_planes_calls = 0   # YCbCr forwards that ended in a fused sink / in hat_planes_to_yuv
         self.C, self.scale, self.heads, self.ws = int(cfg["dim"]), int(cfg["upscaling_factor"]), int(cfg["num_heads"]), int(cfg["window_size"])
         dev, C = self.dev, self.C
         wd = self.width = WIDTH[C]
@@ -137,18 +143,34 @@ class ESCEngine(EngineBase):
         else:
             ops.conv(pw, x, out, **geo, dtype=self.dtype, ldx=ldx, ldo=ldo, out_mode=out_mode, **kw)
 
-    def _forward(self, x: torch.Tensor, taps: dict = None) -> torch.Tensor:
-        """x (B, 3, h, w) fp32 (B = 1 unless the network takes batches) -> (B, 3, s h, s w) fp32 (the workspace's output buffer: copy it before the next forward of the shape).
-        taps: a dict that receives clones of the stream after the first ConvFFN, the attention and the first conv block."""
+    def _pad_multiple(self) -> int:
+        return 1   # any frame size is taken as it is; _check_input refuses what the reflections cannot serve
+
+    def _out_factor(self) -> int:
+        """What the network applies to a frame: behind an unshuffled stem the x4 head runs on a smaller body and the result is the
+        (s h, s w) corner of its buffer; else the head's own factor where it has one (ESCReal's default head: 4)."""
+        return self.scale if self.stem.f else (self.head.out_scale or self.scale)
+
+    def _check_input(self, x):
+        """The shapes every forward refuses (_forward calls it; an ensemble calls it before it allocates or launches)."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError(f"ESC expects (B,3,h,w) input, got {tuple(x.shape)}")
-        B, _, h0, w0 = x.shape
-        self._check_batch(B)
-        H, W = self._body_size(h0, w0)
+        self._check_batch(x.shape[0])
+        H, W = self._body_size(x.shape[2], x.shape[3])
         ws = self.ws
         if (-H) % ws > H - 1 or (-W) % ws > W - 1:
             raise RuntimeError(f"a {H}x{W} frame cannot be reflect-padded to a multiple of window_size {ws}: the padding must be smaller than the frame")
         self._check_frame(H, W)
+
+    def _forward(self, x: torch.Tensor, one_stream=None, sink=None, taps: dict = None) -> torch.Tensor:
+        """x (B, 3, h, w) fp32 (B = 1 unless the network takes batches) -> (B, 3, s h, s w) fp32 (the workspace's output buffer: copy it before the next forward of the shape).
+        one_stream: accepted and ignored (there is no side stream).  sink (a frame_boundary._Sink): the head fills and returns
+        sink.out, bytes, instead of fp32 planes.
+        taps: a dict that receives clones of the stream after the first ConvFFN, the attention and the first conv block."""
+        self._check_input(x)
+        B, _, h0, w0 = x.shape
+        H, W = self._body_size(h0, w0)
+        ws = self.ws
         x = x.to(torch.float32).contiguous()
         w, C, dt, N = self._workspace(B, h0, w0), self.C, self.dtype, H * W
         geo = dict(B=B, H=H, W=W)
@@ -185,7 +207,7 @@ class ESCEngine(EngineBase):
             ops.conv(b.conv_out, w["n"], xb, **geo, dtype=dt, ldx=C, ldo=C, out_mode=O_NHWC_F32, r1=cur, ldr1=C)
             cur = xb
         res = self.residual.run(x, w, cur, geo)
-        return self.head.run(x, w, cur, res, geo)
+        return self.head.run(x, w, cur, res, geo, sink=sink)
 
 
 class ESCRealEngine(ESCEngine):
@@ -239,9 +261,9 @@ class ESCRealMEngine(ESCEngine):
         self._build(cfg, sd, device, compute_dtype, part(UnshuffledStem, f=f) if f else PlainStem,
                     part(UnshuffledSkipResidual, what="map", behind=f" behind the /{f} unshuffle") if f else part(SkipResidual, what="map"), head)
 
-    def _forward(self, x, taps=None):
-        y = super()._forward(x, taps)
-        if self.f:   # the reference's crop to (s h, s w): a corner of the x4 buffer
+    def _forward(self, x, one_stream=None, sink=None, taps=None):
+        y = super()._forward(x, sink=sink, taps=taps)
+        if self.f and sink is None:   # the reference's crop to (s h, s w): a corner of the x4 buffer (a sink's size is that crop)
             s = self.scale
             return y[:, :, :s * x.shape[2], :s * x.shape[3]]
         return y
@@ -286,6 +308,12 @@ class ESCLTEEngine(ESCEngine):
         self._feat_ws = None
         self._build(dict(cfg, upscaling_factor=1), sd, device, compute_dtype, PlainStem, Feat0Residual, LTEHead)
         self.lte = self.head.lte
+
+    def _no_frame_boundary(self, *a, **k):
+        raise RuntimeError("ESC-LTE's forward returns feature rows, not an image: the fixed-scale frame boundary does not apply; its frame "
+                           "paths are gen_feat_frame with query_grid_u8 / query_grid_yuv (ESCLTE.upscale_u8 / upscale_yuv)")
+
+    forward_ensemble = forward_to_u8 = forward_u8 = forward_gt_u8 = forward_yuv420 = forward_yuv = _no_frame_boundary
 
     def _query(self, out, *dst, fn=ops.lte_query, **kw):
         """One launch of hat_lte_query, or of the sink `fn` of its family, on what the last gen_feat left."""

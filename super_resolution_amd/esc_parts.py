@@ -43,6 +43,7 @@ class Part:
 # ---- stems: run(x, w, geo) writes w["feat0"] ----------------------------------------------------------------------------------
 class PlainStem(Part):
     """feat0 = proj(x - mean) on the NCHW frame"""
+    f = 0   # no unshuffle: the body runs at the frame's size
 
     def pack(self, sd):
         self.proj = self.conv(sd, "proj")
@@ -116,7 +117,9 @@ class UnshuffledSkipResidual(SkipResidual):
         ops.escrealm_skip(self.skip, w["xr"], sk, **geo, dtype=self.e.dtype, ldx=w["xr"].shape[2], r=w["feat0"], ldr=self.e.C, ldo=self.e.C)
 
 
-# ---- heads: run(x, w, cur, res, geo) -> the forward's result --------------------------------------------------------------------
+# ---- heads: run(x, w, cur, res, geo, sink=None) -> the forward's result: the planes w["y"], or with a sink (frame_boundary._Sink)
+# sink.out, filled by one of three routes: the conv route (ToPlanes: the row sweep's byte / YCbCr epilogue, else planes), the
+# shuffle route (hat_shuffle_to_u8 / hat_shuffle_to_yuv where the sink is fusable, else planes), planes only (Head.end) -----------
 class ToPlanes:
     """A 3x3 conv to 3 channels stored as fp32 NCHW planes: hat_conv, or (sweep=True) the row-sweep kernel where HATEngine takes it
     for conv_last: 64 input channels, T rows it is built for, a width that is a multiple of 16.
@@ -132,13 +135,19 @@ class ToPlanes:
         if sweep and ops.conv3x3_to_planes_supported(3, 64, 16, self.e.dtype):
             self.sweep = ops.pack_cab_squeeze(sd[name + ".weight"], sd[name + ".bias"], self.e.dev)
 
-    def run(self, src, y, B, H, W):
-        """H, W: the size the conv runs at."""
+    def run(self, src, y, B, H, W, sink=None):
+        """H, W: the size the conv runs at.  With a sink the row sweep converts in its epilogue where it runs and the sink can take
+        it (hat_conv3x3_to_u8 / hat_conv3x3_to_yuv; y is not written); else the planes y are written as always and the sink
+        converts them.  -> the result: y, or sink.out."""
         C, dt = self.out.cin, self.e.dtype
+        if sink is not None and self.sweep is not None and W % 16 == 0 and sink.fusable:
+            sink.fused(src, *self.sweep, B=B, H=H, W=W, C_=C, ldx=C, out_scale=1.0, mean=(0.0, 0.0, 0.0, 0.0), dtype=dt)
+            return sink.out
         if self.sweep is not None and W % 16 == 0:
             ops.conv3x3_to_planes(src, *self.sweep, y, B=B, H=H, W=W, C_=C, ldx=C, n_out=3, out_scale=1.0, mean=(0.0, 0.0, 0.0, 0.0), dtype=dt)
         else:
             ops.conv(self.out, src, y, B=B, H=H, W=W, dtype=dt, ldx=C, ldo=0, out_mode=O_NCHW_F32)
+        return Head.end(y, sink)
 
 
 class Head(Part):
@@ -152,6 +161,14 @@ class Head(Part):
     def y(self, B, H, W, f):
         s = self.out_scale or self.e.scale
         return f(B, 3, H * s, W * s)
+
+    @staticmethod
+    def end(y, sink):
+        """The result of a head that wrote the planes y: y itself, or the sink's, converted from them (the sink's size is the crop)."""
+        if sink is None:
+            return y
+        sink.from_planes(y)
+        return sink.out
 
     def rows_conv(self, pw, w, geo):
         """A conv from n into all of the fp32 rows w["rows"] -> their width."""
@@ -169,11 +186,14 @@ class ShuffleAddHead(Head):
     def buffers(self, B, H, W, f, t):
         return {"rows": f(B, H * W, _r4(3 * self.e.scale ** 2)), "y": self.y(B, H, W, f)}
 
-    def run(self, x, w, cur, res, geo):
+    def run(self, x, w, cur, res, geo, sink=None):
         self.last(w, cur, res, geo)
         ld = self.rows_conv(self.to_img, w, geo)
+        if sink is not None and sink.fusable:   # rows + base image straight to the frame: w["y"] is not written
+            sink.shuffled(w["rows"], x, **geo, s=self.e.scale, ld=ld)
+            return sink.out
         ops.esc_shuffle_add(w["rows"], x, w["y"], **geo, s=self.e.scale, ld=ld)
-        return w["y"]
+        return self.end(w["y"], sink)
 
 
 class ShuffleBicubicHead(ShuffleAddHead):
@@ -184,13 +204,13 @@ class ShuffleBicubicHead(ShuffleAddHead):
         self.ln_last = tuple(sd[k].detach().to(dtype=torch.float32, device=self.e.dev).contiguous() for k in ("ln_last.weight", "ln_last.bias"))
         self.ptab = ops.bicubic_phase_table(self.e.scale).to(self.e.dev)
 
-    def run(self, x, w, cur, res, geo):
+    def run(self, x, w, cur, res, geo, sink=None):   # (a sink always converts the planes: DESIGN.md §4.21)
         e = self.e
         e.width.layernorm(cur, w["z"], *self.ln_last, npix=geo["B"] * geo["H"] * geo["W"], dtype=e.dtype, eps=LN_EPS, ldx=e.C, ldy=e.C)
         self.last(w, w["z"], res, geo, x_mode=X_NHWC_T)
         ld = self.rows_conv(self.to_img, w, geo)
         ops.escfp_shuffle_bicubic(w["rows"], x, self.ptab, w["y"], **geo, s=e.scale, ld=ld)
-        return w["y"]
+        return self.end(w["y"], sink)
 
 
 class NearestX4Head(Head):
@@ -206,15 +226,14 @@ class NearestX4Head(Head):
     def buffers(self, B, H, W, f, t):
         return {"y": self.y(B, H, W, f), "u1": t(B, 4 * H * W, 64), "u2": t(B, 16 * H * W, 64), "u3": t(B, 16 * H * W, 64)}
 
-    def run(self, x, w, cur, res, geo):
+    def run(self, x, w, cur, res, geo, sink=None):
         C, dt = self.e.C, self.e.dtype
         B, H, W = geo["B"], geo["H"], geo["W"]
         self.last(w, cur, res, geo)
         ops.conv(self.ups[0], w["n"], w["u1"], **geo, dtype=dt, ldx=C, ldo=C, out_mode=O_PIXSHUF_T, ps_r=2, act=ACT_LRELU02)
         ops.conv(self.ups[1], w["u1"], w["u2"], B=B, H=2 * H, W=2 * W, dtype=dt, ldx=C, ldo=C, out_mode=O_PIXSHUF_T, ps_r=2, act=ACT_LRELU02)
         ops.conv(self.hr, w["u2"], w["u3"], B=B, H=4 * H, W=4 * W, dtype=dt, ldx=C, ldo=C, act=ACT_LRELU02)
-        self.out.run(w["u3"], w["y"], B, 4 * H, 4 * W)
-        return w["y"]
+        return self.out.run(w["u3"], w["y"], B, 4 * H, 4 * W, sink)
 
 
 class DySampleHead(Head):
@@ -236,7 +255,7 @@ class DySampleHead(Head):
             w["pre"] = t(B, H * W, self.pre)
         return w
 
-    def run(self, x, w, cur, res, geo):
+    def run(self, x, w, cur, res, geo, sink=None):   # (a sink always converts the planes: DESIGN.md §4.21)
         e = self.e
         self.last(w, cur, res, geo)
         src, ch = w["n"], e.C
@@ -245,7 +264,7 @@ class DySampleHead(Head):
             ops.conv(self.pre_conv, w["n"], src, **geo, dtype=e.dtype, ldx=e.C, ldo=ch, act=ACT_LRELU)
         e._lin(self.dys, src, w["rows"], geo=geo, ldx=ch, ldo=self.ld, out_mode=O_NHWC_F32)
         ops.dysample(w["rows"], self.init, self.bias, w["y"], **geo, s=self.out_scale, ld=self.ld)
-        return w["y"]
+        return self.end(w["y"], sink)
 
 
 class ConvHead(Head):
@@ -258,10 +277,9 @@ class ConvHead(Head):
     def buffers(self, B, H, W, f, t):
         return {"y": self.y(B, H, W, f)}
 
-    def run(self, x, w, cur, res, geo):
+    def run(self, x, w, cur, res, geo, sink=None):
         self.last(w, cur, res, geo)
-        self.out.run(w["n"], w["y"], **geo)
-        return w["y"]
+        return self.out.run(w["n"], w["y"], **geo, sink=sink)
 
 
 class ShufflePlanesHead(Head):
@@ -273,11 +291,14 @@ class ShufflePlanesHead(Head):
     def buffers(self, B, H, W, f, t):
         return {"y": self.y(B, H, W, f), "rows": f(B, H * W, _r4(3 * self.out_scale ** 2))}
 
-    def run(self, x, w, cur, res, geo):
+    def run(self, x, w, cur, res, geo, sink=None):
         self.last(w, cur, res, geo)
         ld = self.rows_conv(self.direct, w, geo)
+        if sink is not None and sink.fusable:   # rows straight to the frame: w["y"] is not written
+            sink.shuffled(w["rows"], None, **geo, s=self.out_scale, ld=ld)
+            return sink.out
         ops.shuffle_planes(w["rows"], w["y"], **geo, s=self.out_scale, ld=ld)
-        return w["y"]
+        return self.end(w["y"], sink)
 
 
 class StepsHead(Head):
@@ -308,7 +329,7 @@ class StepsHead(Head):
             w["pre"] = t(B, H * W, self.ch)
         return w
 
-    def run(self, x, w, cur, res, geo):
+    def run(self, x, w, cur, res, geo, sink=None):
         C, dt, ch = self.e.C, self.e.dtype, self.ch
         B, hh, ww = geo["B"], geo["H"], geo["W"]
         self.last(w, cur, res, geo)
@@ -322,8 +343,7 @@ class StepsHead(Head):
         if self.nearest:
             ops.conv(self.ends, src, w["hr"], B=B, H=hh, W=ww, dtype=dt, ldx=C, ldo=C, act=ACT_LRELU02)
             src = w["hr"]
-        self.out.run(src, w["y"], B, hh, ww)
-        return w["y"]
+        return self.out.run(src, w["y"], B, hh, ww, sink)
 
 
 class LTEHead(Head):
@@ -336,7 +356,7 @@ class LTEHead(Head):
     def buffers(self, B, H, W, f, t):
         return {"cf": f(B, H * W, 2 * ops.LTE_HIDDEN), "x": f(B, 3, H, W)}
 
-    def run(self, x, w, cur, res, geo):
+    def run(self, x, w, cur, res, geo, sink=None):
         self.last(w, cur, res, geo)
         ld = w["cf"].shape[2]
         ops.conv(self.lte.taps, w["n"], w["cf"], **geo, dtype=self.e.dtype, ldx=self.e.C, ldo=ld, out_mode=O_NHWC_F32, n_store=ld)

@@ -11,11 +11,12 @@ from . import ops
 
 class _Sink:
     """Where a byte-frame forward ends instead of in fp32 planes: `out`, the caller's result tensor of the (h_out, w_out) top-left
-    pixels, and the two ways to fill it — fused(src, wpk, b8, conv_last's geometry ...), conv_last's row sweep with the conversion
-    as its epilogue (no fp32 image exists), or from_planes(y) of an fp32 image.  Each bumps its engine counter, `kind`_fused_calls
-    or `kind`_planes_calls.  band_refusal: why a row band, which hands its rows over as fp32, cannot end in this sink."""
+    pixels, and the ways to fill it — fused(src, wpk, b8, conv_last's geometry ...), conv_last's row sweep with the conversion
+    as its epilogue (no fp32 image exists); shuffled(rows, base, B, H, W, s, ld), the same for a head that ends in a pixel shuffle of
+    fp32 rows (hat_shuffle_to_u8 / hat_shuffle_to_yuv; base: the image added, or None); or from_planes(y) of an fp32 image, which
+    may be larger than `out`: the sink's size is the crop.  Each bumps its engine counter, `kind`_fused_calls or `kind`_planes_calls.  band_refusal: why a row band, which hands its rows over as fp32, cannot end in this sink."""
     kind = band_refusal = None
-    fusable = True   # False: conv_last has no epilogue for this sink; it always ends in from_planes
+    fusable = True   # False: neither conv_last nor the shuffle has an epilogue for this sink; it always ends in from_planes
 
     def __init__(self, eng, out, size):
         self.eng, self.out, self.size = eng, out, size
@@ -35,6 +36,10 @@ class _U8Sink(_Sink):
 
     def fused(self, src, wpk, b8, **conv):
         ops.conv3x3_to_u8(src, wpk, b8, self.out, h_out=self.size[0], w_out=self.size[1], bgr=self.bgr, **conv)
+        self._count("fused")
+
+    def shuffled(self, rows, base, **geo):
+        ops.shuffle_to_u8(rows, base, self.out, bgr=self.bgr, **geo)
         self._count("fused")
 
     def from_planes(self, y):
@@ -59,6 +64,10 @@ class _YuvSink(_Sink):
         ops.conv3x3_to_yuv(src, wpk, b8, *self.views, from_rgb=self.from_rgb, **self.surface, **conv)
         self._count("fused")
 
+    def shuffled(self, rows, base, **geo):
+        ops.shuffle_to_yuv(rows, base, *self.views, self.from_rgb, **self.surface, **geo)
+        self._count("fused")
+
     def from_planes(self, y):
         ops.planes_to_yuv(y, *self.views, self.from_rgb, siting=self.siting, **self.surface)
         self._count("planes")
@@ -67,7 +76,15 @@ class _YuvSink(_Sink):
 class FrameBoundary:
     """Requires of its host engine: `_forward(x, one_stream=, sink=)` and `_check_input(x)`; `_workspace`, `scale`, `ws`, `dev`,
     `_lock` and `cfg["in_chans"]`; and the four counters `u8_fused_calls`, `u8_planes_calls`, `yuv_fused_calls`, `yuv_planes_calls`,
-    which stay attributes of the engine (the sinks bump them there)."""
+    which stay attributes of the engine (the sinks bump them there).  Two hooks say what a frame is to the network; their defaults
+    are HAT's: `_pad_multiple()`, the multiple a frame is reflect-padded to before the forward (the window size; 1: the network
+    takes any size and refuses in its own words), and `_out_factor()`, the factor between a frame and its result (`scale`)."""
+
+    def _pad_multiple(self) -> int:
+        return self.ws
+
+    def _out_factor(self) -> int:
+        return self.scale
 
     def forward_ensemble(self, x: torch.Tensor, n: int = 8, *, one_stream: Optional[bool] = None) -> torch.Tensor:
         """The geometric self-ensemble ("+" mode; basicsr models/sr_model.py:132-178): the mean over the first n of the eight flips /
@@ -87,7 +104,8 @@ class FrameBoundary:
             self._check_input(x)
             # the result is the caller's, as forward's is: it is the accumulator (the byte paths, whose fp32 image never leaves
             # the engine, keep theirs in the workspace: _ens_acc)
-            acc = torch.empty(x.shape[0], x.shape[1], x.shape[2] * self.scale, x.shape[3] * self.scale, dtype=torch.float32, device=self.dev)
+            s = self._out_factor()
+            acc = torch.empty(x.shape[0], x.shape[1], x.shape[2] * s, x.shape[3] * s, dtype=torch.float32, device=self.dev)
             return self._ensemble(x, n, acc, one_stream=one_stream)
 
     def _ws_buffer(self, ws, key, shape):
@@ -100,7 +118,7 @@ class FrameBoundary:
 
     def _ens_acc(self, ws, B, Hp, Wp):
         """The byte paths' fp32 accumulator of the (B, Hp, Wp) workspace: the ensembled image before the crop and the conversion."""
-        return self._ws_buffer(ws, "ens_acc", (B, 3, Hp * self.scale, Wp * self.scale))
+        return self._ws_buffer(ws, "ens_acc", (B, 3, Hp * self._out_factor(), Wp * self._out_factor()))
 
     def _ensemble(self, x, n, acc, one_stream=None):
         """acc (B, C, sH, sW) fp32 = sum over i < n of (1 / n) * T_i^-1(forward(T_i x)), in member order; returns acc.  Called under
@@ -115,6 +133,9 @@ class FrameBoundary:
                 xi = self._ws_buffer(self._workspace(B, Hi, Wi), "ens_x", (B, C_, Hi, Wi))
                 ops.dihedral(x, xi, op=i)
             y = self._forward(xi, one_stream=one_stream)
+            if not y.is_contiguous():   # a corner of a larger buffer (ESCRealM behind its unshuffled stem): into the member's workspace
+                Hi, Wi = xi.shape[2:]
+                y = self._ws_buffer(self._workspace(B, Hi, Wi), "ens_y", tuple(y.shape)).copy_(y)
             ops.dihedral(y, acc, op=i, inverse=True, alpha=1.0 / n, accumulate=i > 0)
         return acc
 
@@ -145,7 +166,8 @@ class FrameBoundary:
         """What the frame entry points share: (B, h, w) frames reflect-pad to the next window multiple (Hp, Wp) or are refused;
         fill(x) writes the padded fp32 planes x = ws["x_u8"], the one staging buffer of this shape's workspace; make_sink() checks
         the caller's `out` and returns the sink; then the forward (or its ensemble) into it."""
-        Hp, Wp = -(-h // self.ws) * self.ws, -(-w // self.ws) * self.ws
+        m = self._pad_multiple()
+        Hp, Wp = -(-h // m) * m, -(-w // m) * m
         if Hp - h >= h or Wp - w >= w:
             raise RuntimeError(f"{what or f'a {h}x{w} frame'} cannot be reflect-padded to {Hp}x{Wp} (window_size {self.ws}): the padding must be "
                                f"smaller than the {of}")
@@ -166,9 +188,10 @@ class FrameBoundary:
         ensemble = ops.ensemble_members(ensemble)
         if not x.is_cuda or x.device != self.dev:
             raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
-        ho, wo = (x.shape[2] * self.scale, x.shape[3] * self.scale) if crop is None else (int(crop[0]), int(crop[1]))
-        if not (1 <= ho <= x.shape[2] * self.scale and 1 <= wo <= x.shape[3] * self.scale):
-            raise RuntimeError(f"crop {(ho, wo)} does not lie inside the output {(x.shape[2] * self.scale, x.shape[3] * self.scale)}")
+        s = self._out_factor()
+        ho, wo = (x.shape[2] * s, x.shape[3] * s) if crop is None else (int(crop[0]), int(crop[1]))
+        if not (1 <= ho <= x.shape[2] * s and 1 <= wo <= x.shape[3] * s):
+            raise RuntimeError(f"crop {(ho, wo)} does not lie inside the output {(x.shape[2] * s, x.shape[3] * s)}")
         with self._lock, torch.cuda.device(self.dev):
             if ensemble > 1:
                 self._check_input(x)
@@ -190,7 +213,7 @@ class FrameBoundary:
         if frame.stride(3) != 1 or frame.stride(2) != 3:
             frame = frame.contiguous()
         return self._frame_forward(B, h, w, lambda x: ops.u8_to_planes(frame, x, bgr=bgr),
-                                   lambda: _U8Sink(self, self._u8_out(out, (B, h * self.scale, w * self.scale, 3)), bgr), ensemble)
+                                   lambda: _U8Sink(self, self._u8_out(out, (B, h * self._out_factor(), w * self._out_factor(), 3)), bgr), ensemble)
 
     def forward_gt_u8(self, gt: torch.Tensor, *, bgr: bool = False, out=None, ensemble: int = 1) -> torch.Tensor:
         """(B,H,W,3) uint8 device GROUND-TRUTH frames -> the (B, H - H % s, W - W % s, 3) uint8 super-resolution of their own
@@ -204,7 +227,7 @@ class FrameBoundary:
             raise RuntimeError(f"expected (B,H,W,3) uint8 ground-truth frames, got {tuple(getattr(gt, 'shape', ()))} {getattr(gt, 'dtype', type(gt))}")
         if not gt.is_cuda or gt.device != self.dev:
             raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
-        s = self.scale
+        s = self._out_factor()
         if s not in (2, 3, 4):
             raise RuntimeError(f"forward_gt_u8 makes the low-resolution image at 1/2, 1/3 or 1/4: upscale {s} has no such path")
         B, H, W, _ = gt.shape
@@ -269,7 +292,7 @@ class FrameBoundary:
         if not frame.is_cuda or frame.device != self.dev:
             raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
         h, w = _yuv.frame_size_fmt(frame.shape, fmt)
-        B, s = frame.shape[0], self.scale
+        B, s = frame.shape[0], self._out_factor()
         sub = lambda f: None if _yuv.LAYOUTS[f][0] is None else _yuv.LAYOUTS[f][:2]
 
         def fill(x):

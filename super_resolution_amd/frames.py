@@ -22,6 +22,25 @@ def _raw(t):
     return t.view(torch.int16) if t.dtype == torch.uint16 else t
 
 
+def fixed_scale_family(net) -> bool:
+    """`net` is a fixed-scale network of the ESC family (ESC, ESCReal, ESCRealM, ESCFP): its frame paths are `upscale_*` and it is
+    not marked `arbitrary_scale` (ESCLTE, whose `upscale_*` calls take size= / scale=)."""
+    return hasattr(net, "upscale_u8") and not getattr(net, "arbitrary_scale", False)
+
+
+def entry_points(net, arb: bool = False):
+    """The names of (byte call, YCbCr call, 4:2:0 call or None) of `net` for upscale_frames: HAT's forward_u8 / forward_yuv / forward_yuv420; for a
+    fixed-scale network of the ESC family (it has `upscale_u8` and is not marked `arbitrary_scale`) its upscale_u8 / upscale_yuv, the
+    4:2:0 layouts through upscale_yuv too; with arb (size= / scale=) the network must be marked `arbitrary_scale` (ESCLTE)."""
+    marked = bool(getattr(net, "arbitrary_scale", False))
+    if arb and not marked:
+        raise RuntimeError(f"upscale_frames: size= / scale= need an arbitrary-scale network with upscale_u8 / upscale_yuv (ESCLTE); "
+                           f"{type(net).__name__} has a fixed scale")
+    if arb or fixed_scale_family(net):
+        return "upscale_u8", "upscale_yuv", None
+    return "forward_u8", "forward_yuv", "forward_yuv420"
+
+
 def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", matrix: str = "bt601", full_range: bool = False, depth: int = 8,
                    out_depth=None, msb=None, ensemble: int = 1, out_pixfmt=None, out_msb=None, siting: str = "center", out_siting=None,
                    size=None, scale=None):
@@ -40,7 +59,10 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
     the input's), as HAT.forward_yuv takes them; 'center' is the sequence as it always was.
     size=(h, w) or scale= (one of them): `net` is an arbitrary-scale network (ESCLTE) and every frame goes through `net.upscale_u8`
     (rgb24) or `net.upscale_yuv` (every YCbCr pixfmt) to that size, in the same two-slot pipeline; the yielded arrays have the
-    resolved size's shape.  ensemble is then refused, and so is a network without `upscale_u8`.  Without either, nothing changes."""
+    resolved size's shape.  ensemble is then refused, and so is a network that is not marked `arbitrary_scale`.
+    A fixed-scale network of the ESC family (ESC, ESCReal, ESCRealM, ESCFP: it has `upscale_u8` and is not `arbitrary_scale`) goes,
+    without size= / scale=, through `net.upscale_u8` (rgb24) or `net.upscale_yuv` (every YCbCr pixfmt, the 4:2:0 ones included) with
+    every keyword above, ensemble too, in the same two-slot pipeline; the yielded frames are `net.upscale` times the input's."""
     from .ops import ensemble_members
     ensemble = ensemble_members(ensemble)
     if pixfmt not in PIXFMTS:
@@ -56,14 +78,14 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
         raise RuntimeError("siting and out_siting belong to the YCbCr pixel formats")
     arb = size is not None or scale is not None
     if arb:
-        if not hasattr(net, "upscale_u8"):
-            raise RuntimeError(f"upscale_frames: size= / scale= need an arbitrary-scale network with upscale_u8 / upscale_yuv (ESCLTE); "
-                               f"{type(net).__name__} has a fixed scale")
+        entry_points(net, arb=True)
         if (size is None) == (scale is None):
             raise ValueError("upscale_frames takes exactly one of size=(h, w) and scale=, or neither")
         if ensemble != 1:
             raise RuntimeError("upscale_frames: the self-ensemble is not built for size= / scale= (ESCLTE's frame paths)")
-    general = pixfmt != "rgb24" and (arb or pixfmt not in PIXFMTS[1:4] or out_pixfmt not in (None, pixfmt) or out_msb is not None)
+    name_u8, name_yuv, name_yuv420 = entry_points(net, arb)
+    family = not arb and name_yuv420 is None   # a fixed-scale network of the ESC family
+    general = pixfmt != "rgb24" and (arb or family or pixfmt not in PIXFMTS[1:4] or out_pixfmt not in (None, pixfmt) or out_msb is not None)
     yuv420 = pixfmt != "rgb24" and not general
     dev = next(net.parameters()).device
     if dev.type != "cuda":
@@ -84,6 +106,8 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
     in_np, in_dt, out_dt = np.uint8, torch.uint8, torch.uint8
     if general:
         from . import yuv as _yuv
+        if family and pixfmt in PIXFMTS[1:4] and out_pixfmt in (None, pixfmt) and out_msb is None:
+            out_msb = msb   # (what forward_yuv420 makes of msb: the alignment of both sides)
         out_pixfmt = pixfmt if out_pixfmt is None else out_pixfmt
         out_depth = depth if out_depth is None else out_depth
         in_np = _yuv.container(depth, pixfmt, msb)[0]
@@ -100,11 +124,11 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
                 raise ValueError(f"upscale_frames: an output of {oh}x{ow} is no {out_pixfmt} frame")
         out_shape = _yuv.frame_shape_fmt(*out_hw(h, w), out_pixfmt)
         if arb:
-            forward = lambda src, dst: net.upscale_yuv(src, size=out_hw(h, w), fmt=pixfmt, out_fmt=out_pixfmt, matrix=matrix, full_range=full_range,
+            forward = lambda src, dst: getattr(net, name_yuv)(src, size=out_hw(h, w), fmt=pixfmt, out_fmt=out_pixfmt, matrix=matrix, full_range=full_range,
                                                        out=dst, depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, siting=siting,
                                                        out_siting=out_siting)
         else:
-            forward = lambda src, dst: net.forward_yuv(src, fmt=pixfmt, out_fmt=out_pixfmt, matrix=matrix, full_range=full_range, out=dst,
+            forward = lambda src, dst: getattr(net, name_yuv)(src, fmt=pixfmt, out_fmt=out_pixfmt, matrix=matrix, full_range=full_range, out=dst,
                                                        depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, ensemble=ensemble, **skw)
     elif yuv420:
         from . import yuv as _yuv
@@ -116,7 +140,7 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
             raise RuntimeError(f"expected (3h/2,w) {np.dtype(in_np).name} {pixfmt} frames, got {first.shape} {first.dtype}")
         h, w = _yuv.frame_size(first.shape)
         in_shape, out_shape, shape_text = first.shape, _yuv.frame_shape(s * h, s * w), f"({3 * h // 2},{w})"
-        forward = lambda src, dst: net.forward_yuv420(src, fmt=pixfmt, matrix=matrix, full_range=full_range, out=dst, depth=depth,
+        forward = lambda src, dst: getattr(net, name_yuv420)(src, fmt=pixfmt, matrix=matrix, full_range=full_range, out=dst, depth=depth,
                                                       out_depth=out_depth, msb=msb, ensemble=ensemble, **skw)
     else:
         if depth != 8 or out_depth not in (None, 8):
@@ -128,9 +152,9 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
         if arb and min(out_shape) < 1:
             raise ValueError(f"upscale_frames: an output of {out_shape[0]}x{out_shape[1]} is empty")
         if arb:
-            forward = lambda src, dst: net.upscale_u8(src, size=out_shape[:2], bgr=bgr, out=dst)
+            forward = lambda src, dst: getattr(net, name_u8)(src, size=out_shape[:2], bgr=bgr, out=dst)
         else:
-            forward = lambda src, dst: net.forward_u8(src, bgr=bgr, out=dst, ensemble=ensemble)
+            forward = lambda src, dst: getattr(net, name_u8)(src, bgr=bgr, out=dst, ensemble=ensemble)
     # Nothing of the device state stays entered across a yield: the buffers and the copy stream are made once, and every step
     # enters the device and takes the stream that is current THEN, so a caller may switch device or stream between frames.
     with torch.cuda.device(dev):

@@ -62,7 +62,17 @@ class HATModel:
         if n == 1:
             return self.net_g
         bare = self.get_bare_model(self.net_g)
-        return lambda t: bare.forward_ensemble(t, n)
+        ens = bare.forward_ensemble if self._family() is None else bare.upscale_ensemble   # (the ESC family's name for it)
+        return lambda t: ens(t, n)
+
+    def _family(self):
+        """The bare network where it is a fixed-scale network of the ESC family, whose frame paths are `upscale_*`; else None.
+        Such a network takes a frame of any size as it is, but this harness pads to a window multiple first (ESRModel.test does,
+        as HATModel.pre_process): its byte branches therefore build the padded planes themselves (hat_u8_to_planes / ops.imresize)
+        and hand them to `upscale_to_u8` with the crop, so the bytes are those of the float branch."""
+        from ..frames import fixed_scale_family
+        bare = self.get_bare_model(self.net_g)
+        return bare if fixed_scale_family(bare) else None
 
     def model_to_device(self, net):
         """basicsr BaseModel.model_to_device (base_model.py:91-104): `num_gpu > 1` wraps the network in nn.DataParallel, as the
@@ -136,7 +146,8 @@ class HATModel:
 
     def test_u8(self, lq: torch.Tensor, on_device: bool = False):
         """`val.u8_on_device`: the same result as test() + tensor2img, with the conversions on the device.  The LQ image goes up
-        as uint8 and only the uint8 result comes back: without `tile`, HAT.forward_u8 pads, runs, crops and converts; with
+        as uint8 and only the uint8 result comes back: without `tile`, HAT.forward_u8 pads, runs, crops and converts (a network of
+        the ESC family: hat_u8_to_planes pads and `upscale_to_u8` runs, crops and converts: _family); with
         `tile`, hat_u8_to_planes builds the padded input (pre_process_u8), tile_process runs as always and hat_planes_to_u8
         crops and converts the assembled fp32 output.  lq: the
         dataset's (1,3,h,w) float image, which must hold 8-bit values (v / 255, what data.read_image produces).
@@ -144,9 +155,16 @@ class HATModel:
         `val.self_ensemble`: forward_u8(ensemble=n) without `tile`; with `tile`, tile_process ensembles every tile."""
         from .. import ops
         frame = self._u8_frame(lq, "val.u8_on_device", "input")
-        if "tile" not in self.opt:
+        fam = self._family()
+        if "tile" not in self.opt and fam is None:
             with torch.no_grad():
                 out = self.get_bare_model(self.net_g).forward_u8(frame, **self._ensemble_kw())
+        elif "tile" not in self.opt:
+            self.pre_process_u8(frame)
+            _, _, h, w = self.img.shape
+            with torch.no_grad():
+                out = fam.upscale_to_u8(self.img, crop=((h - self.mod_pad_h) * self.scale, (w - self.mod_pad_w) * self.scale), **self._ensemble_kw())
+            del self.img
         else:
             self.pre_process_u8(frame)
             self.tile_process()
@@ -221,10 +239,12 @@ class HATModel:
     def test_gt_u8(self, gt: torch.Tensor):
         """`val.lq_on_device`: the (1,H,W,3) uint8 device ground truth -> the (h,w,3) uint8 device result of its own bicubic
         low-resolution image (resize.py's imresize at 1 / scale, made on the device: the float LQ never exists on the host).
-        Without `tile`, HAT.forward_gt_u8 does it all; with `tile`, ops.imresize writes the padded planes, tile_process runs
+        Without `tile`, HAT.forward_gt_u8 does it all (a network of the ESC family: ops.imresize writes the padded planes and
+        `upscale_to_u8` runs, crops and converts: _family); with `tile`, ops.imresize writes the padded planes, tile_process runs
         as always and hat_planes_to_u8 crops and converts, as test_u8 does.  `val.self_ensemble`: as in test_u8."""
         from .. import ops
-        if "tile" not in self.opt:
+        fam = self._family()
+        if "tile" not in self.opt and fam is None:
             with torch.no_grad():
                 return self.get_bare_model(self.net_g).forward_gt_u8(gt, **self._ensemble_kw())[0]
         window_size = self.opt["network_g"]["window_size"]
@@ -238,6 +258,11 @@ class HATModel:
             raise RuntimeError(f"a {h}x{w} image cannot be reflect-padded to a multiple of window_size {window_size}")
         with torch.cuda.device(self.device):
             self.img = ops.imresize(gt, 1.0 / s, pad_to=(h + self.mod_pad_h, w + self.mod_pad_w))
+        if "tile" not in self.opt:   # (the ESC family, whole frame: the padded planes into bytes with the crop)
+            with torch.no_grad():
+                out = fam.upscale_to_u8(self.img, crop=(h * s, w * s), **self._ensemble_kw())
+            del self.img
+            return out[0]
         self.tile_process()
         out = torch.empty(b, h * s, w * s, 3, dtype=torch.uint8, device=self.device)
         ops.planes_to_u8(self.output.to(torch.float32).contiguous(), out)

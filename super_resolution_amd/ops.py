@@ -416,6 +416,50 @@ def shuffle_planes(rows, y, *, B: int, H: int, W: int, s: int, ld: int):
         tag=f"shuffle x{s} {H}x{W}", nbytes=4.0 * B * H * W * (ld + 3 * s * s))
 
 
+def _shuffle_src(what: str, rows, base, B: int, H: int, W: int, s: int, ld: int):
+    """The checks shuffle_to_u8 / shuffle_to_yuv make of their source: rows (B,H,W,ld) fp32, base None or (B,3,H,W) fp32 planes."""
+    if not isinstance(s, int) or isinstance(s, bool) or not 1 <= s <= 8:
+        raise RuntimeError(f"{what}: the shuffle factor is 1..8, got {s!r}")
+    if rows.dtype != torch.float32 or not rows.is_cuda or not rows.is_contiguous() or ld < 3 * s * s or rows.numel() != B * H * W * ld:
+        raise RuntimeError(f"{what} needs contiguous ({B},{H},{W},ld >= {3 * s * s}) fp32 device rows, got {tuple(rows.shape)} {rows.dtype} for ld {ld}")
+    if base is not None and (base.dtype != torch.float32 or tuple(base.shape) != (B, 3, H, W) or not base.is_contiguous() or base.device != rows.device):
+        raise RuntimeError(f"{what} needs a contiguous ({B},3,{H},{W}) fp32 base image on {rows.device}, got {tuple(base.shape)} {base.dtype} "
+                           f"on {base.device}")
+
+
+def shuffle_to_u8(rows, base, dst, *, B: int, H: int, W: int, s: int, ld: int, bgr: bool = False):
+    """dst (B,h_out,w_out,3) uint8 (rows may be pitched) = planes_to_u8 of what esc_shuffle_add (base (B,3,H,W)) or shuffle_planes
+    (base None) writes for rows (B,H,W,ld) fp32, cropped to the top-left h_out x w_out pixels; no fp32 image is written
+    (hat_shuffle_to_u8)."""
+    lib = _lib.load()
+    _shuffle_src("shuffle_to_u8", rows, base, B, H, W, s, ld)
+    if dst.dtype != torch.uint8 or not dst.is_cuda or dst.dim() != 4 or dst.shape[0] != B or dst.shape[3] != 3 or dst.stride(-1) != 1 \
+            or dst.stride(-2) != 3 or dst.shape[1] > s * H or dst.shape[2] > s * W or dst.device != rows.device:
+        raise RuntimeError(f"shuffle_to_u8 needs a ({B},h_out <= {s * H},w_out <= {s * W},3) uint8 destination on {rows.device} with interleaved "
+                           f"pixels, got {tuple(dst.shape)} {dst.dtype} on {dst.device}")
+    _timed("shuffle_to_u8_kernel", 0.0, lambda: _lib.check(
+        lib.hat_shuffle_to_u8(_ptr(rows), ld, _ptr(base), B, H, W, s, dst.data_ptr(), dst.stride(1), dst.stride(0), dst.shape[1], dst.shape[2],
+                              int(bool(bgr)), _stream()), "hat_shuffle_to_u8"),
+        tag=f"shuffle x{s} {H}x{W} -> u8 {dst.shape[1]}x{dst.shape[2]}", nbytes=B * (4.0 * H * W * (ld + (3 if base is not None else 0))
+                                                                                   + 3.0 * dst.shape[1] * dst.shape[2]))
+
+
+def shuffle_to_yuv(rows, base, y, cb, cr, from_rgb, *, B: int, H: int, W: int, s: int, ld: int, sub, depth: int = 8, msb=False):
+    """The views Y (B,h_out,w_out), Cb, Cr of any subsampling (None, None and sub=None: grey), centre-sited = planes_to_yuv of what
+    esc_shuffle_add / shuffle_planes writes for rows (and base), cropped to the views' size; no fp32 image is written
+    (hat_shuffle_to_yuv)."""
+    lib = _lib.load()
+    _shuffle_src("shuffle_to_yuv", rows, base, B, H, W, s, ld)
+    surf = yuv_surface(y, cb, cr, sub=sub, depth=depth, msb=msb, what="shuffle_to_yuv")
+    if y.shape[0] != B or y.shape[1] > s * H or y.shape[2] > s * W or y.device != rows.device:
+        raise RuntimeError(f"shuffle_to_yuv needs a ({B},h_out <= {s * H},w_out <= {s * W}) Y view on {rows.device}, got {tuple(y.shape)} on {y.device}")
+    m, name = _f12(from_rgb), _sub_name(sub, depth)
+    _timed(f"shuffle_to_yuv_kernel<{name}>", 0.0, lambda: _lib.check(
+        lib.hat_shuffle_to_yuv(_ptr(rows), ld, _ptr(base), B, H, W, s, C.byref(surf), y.shape[1], y.shape[2], m, _stream()), "hat_shuffle_to_yuv"),
+        tag=f"shuffle x{s} {H}x{W} -> {name} {y.shape[1]}x{y.shape[2]}", nbytes=B * (4.0 * H * W * (ld + (3 if base is not None else 0))
+                                                                                    + 3.0 * y.shape[1] * y.shape[2]))
+
+
 # ------------------------------------------------------------------------------------------------
 # ESCFP (hat_escfp_convffn / hat_escfp_layernorm / hat_escfp_weights / hat_escfp_shuffle_bicubic)
 # ------------------------------------------------------------------------------------------------
