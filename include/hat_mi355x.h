@@ -596,6 +596,42 @@ int hat_u8_metrics(const uint8_t* a, int64_t a_pitch, int64_t a_bstride, const u
                    int32_t B, int32_t h, int32_t w, int32_t crop_border, int32_t flags, double* sums, void* workspace, void* stream);
 
 /*
+ * The ESC-LTE benchmark loop's two device pieces (ESC/esc_arb/test.py eval_psnr; csrc/hat_pil_resize.hip).
+ *
+ * hat_pil_resize_u8: Pillow's 8-bit bicubic Image.resize (libImaging/Resample.c), which the reference's dataset wrappers make
+ * their LR images with (esc_arb/datasets/wrappers.py:149-152).  src: one (h,w,3) uint8 frame with src_pitch >= 3 w bytes per
+ * row; dst: (oh,ow,3) uint8 with dst_pitch >= 3 ow (bytes past 3 ow of a row are not touched); mid: 3 ow h bytes of the
+ * caller's workspace, the uint8 image between the passes.  Any sizes >= 1, shrinking or enlarging, each axis on its own.
+ * Tables.  The CALLER builds them on the host (resize.pil_tables: Pillow's float64 arithmetic) and passes DEVICE pointers,
+ * per axis coef[out_len][K] int32 (22-bit fixed point) and bounds[out_len][2] int32 = (first tap, tap count <= K); K = 2
+ * ceil(2 max(in / out, 1)) + 1, any size.  Arithmetic.  out = clip8((2^21 + sum_k coef[k] * pixel[first + k]) >> 22) in
+ * int32, the horizontal pass (w -> ow) into mid first, then the vertical pass (h -> oh): Pillow's order, and the rounding
+ * of mid to bytes is part of the definition.  The result equals PIL.Image.resize((ow, oh), BICUBIC) bit for bit.  The
+ * library cannot look into device tables: an entry whose taps leave the source contributes nothing (no read outside src or
+ * mid follows from a wrong table), and tables shorter than out_len rows are the caller's error.  HAT_EINVAL for null
+ * pointers, a size or K below 1 and a pitch below the row.  Two launches; nothing allocates or synchronises.
+ *
+ * hat_arb_psnr: utils.py:132-149 (calc_psnr) of an fp32 prediction against an 8-bit ground truth.  pred: (3,ph,pw) contiguous
+ * fp32 planes, ph >= h, pw >= w: the top-left (h, w) is scored (test.py:112).  gt: (h,w,3) uint8 with gt_pitch >= 3 w, value
+ * float(byte) / 255.0f exactly.  Per pixel d_c = min(max(pred_c, 0), 1) - gt_c in fp32; gray != 0 ('benchmark'): v = (d_0 k_0 +
+ * d_1 k_1) + d_2 k_2 with k = float32(65.738, 129.057, 25.064) / 256, every product and sum rounded to fp32 on its own, one
+ * term v^2 per pixel; gray == 0 ('div2k', or no eval_type): three terms d_c^2.  shave pixels come off every side (the caller
+ * passes S for 'benchmark-S', S + 6 for 'div2k-S').  The squares are formed and added in fp64.  sums: two doubles in device
+ * memory, sums[0] = the sum, sums[1] = the number of terms; PSNR = -10 log10(sums[0] / sums[1]) is the caller's.  One partial
+ * per workgroup in `workspace`, added in a fixed order by a second small launch: reproducible bit for bit, no atomics.
+ * hat_arb_psnr_workspace_bytes is a pure host query of the workspace's size (8-byte aligned device memory).  Both return
+ * HAT_EINVAL for h or w < 1, a negative shave and 2 shave >= h or w; hat_arb_psnr also for null pointers, ph < h, pw < w and a
+ * pitch below 3 w.  The checks come before anything touches the device; neither function allocates or synchronises.
+ * No plan records these calls.
+ */
+int hat_pil_resize_u8(const uint8_t* src, int64_t src_pitch, int32_t h, int32_t w, uint8_t* mid, uint8_t* dst, int64_t dst_pitch, int32_t oh,
+                      int32_t ow, const int32_t* coef_w, const int32_t* bounds_w, int32_t K_w, const int32_t* coef_h,
+                      const int32_t* bounds_h, int32_t K_h, void* stream);
+int hat_arb_psnr_workspace_bytes(int32_t h, int32_t w, int32_t shave, int64_t* bytes);
+int hat_arb_psnr(const float* pred, int32_t ph, int32_t pw, const uint8_t* gt, int64_t gt_pitch, int32_t h, int32_t w, int32_t gray,
+                 int32_t shave, double* sums, void* workspace, void* stream);
+
+/*
  * (Shifted-)window self-attention, (S)W-MSA — SURVEY §8 row f2.  Replaces, for one attention branch of a Swin / upstream-HAT
  * block, ESC/basicsr/archs/swinir_arch.py:291-317 (torch.roll by -shift, window_partition, WindowAttention core :147-168
  * with the relative-position bias :153-156 and the shift mask of calculate_mask :262-280, window_reverse, torch.roll by

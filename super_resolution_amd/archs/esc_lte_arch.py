@@ -53,7 +53,9 @@ class ESCLTE(_ESCNet):
     any n_blocks / conv_blocks), hidden_dim 256, hidden_list (256, 256, 256); anything else is a ValueError when the engine packs.
       upscale_u8(frame, size= | scale=)           an (h,w,3) uint8 device frame -> (1,H',W',3) uint8: tensor2img's bytes of `upscale`
       upscale_yuv(frame, size= | scale=, fmt=)    a YCbCr device frame of any layout and depth -> the resized frame in any layout
-    `query_rgb` and the three `upscale` calls run eagerly also with `use_graph=True`.
+      score_u8(lr, gt, eval_type=)                a paired LR / GT frame -> the PSNR of the reference's test.py (`benchmark-S`, `div2k-S`)
+      score_gt_u8(gt, scale, eval_type=)          a GT frame: the LR frame by Pillow's 8-bit bicubic resize on the device, then the same
+    `query_rgb`, the three `upscale` calls and the two `score` calls run eagerly also with `use_graph=True`.
     One frame per call.  `forward_ensemble`, the fixed-scale byte and YCbCr entry points (`forward_u8`, `forward_yuv`, ...), row bands
     and plans raise NotImplementedError, as for `ESC`: this network's frame paths are `upscale_u8` and `upscale_yuv`."""
     arbitrary_scale = True   # frames.upscale_frames: size= / scale= go to upscale_u8 / upscale_yuv; nothing else does
@@ -211,6 +213,55 @@ class ESCLTE(_ESCNet):
             eng.gen_feat_frame(H, W, lambda x: ops.u8_to_planes(frame, x, bgr=bgr))
             self._feat_engine = eng
             return eng.query_grid_u8(dst, self._cells(H, W, h, w, scale_max), bgr)
+
+    # ---- the reference's benchmark loop (esc_arb/test.py eval_psnr over the configs/test files): bytes in, a score
+    # out.  New names; the arithmetic of sizes, crops and cells is arb_test's, where it runs without a device.
+    def _u8_frame(self, what, name, frame):
+        if not isinstance(frame, torch.Tensor) or frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3:
+            raise RuntimeError(f"ESCLTE.{what} expects {name} as an (h,w,3) uint8 frame, got {tuple(getattr(frame, 'shape', ()))} "
+                               f"{getattr(frame, 'dtype', type(frame).__name__)}")
+        self._check_call(frame)
+        return frame if frame.stride(2) == 1 and frame.stride(1) == 3 else frame.contiguous()
+
+    def _score(self, what, eng, lr, gt, eval_type, scale_max):
+        from .. import arb_test, ops
+        mode, shave, S = arb_test.parse_eval_type(eval_type)
+        H, W = int(lr.shape[0]), int(lr.shape[1])
+        h, w = int(gt.shape[0]), int(gt.shape[1])
+        arb_test.check_lr_size(H, W)
+        if 2 * shave >= min(h, w):
+            raise ValueError(f"ESCLTE.{what}: eval_type {eval_type!r} shaves {shave} pixels off every side, which leaves nothing of a {h}x{w} ground truth")
+        eng.gen_feat_frame(H, W, lambda x: ops.u8_to_planes(lr.unsqueeze(0), x))
+        self._feat_engine = eng
+        total, terms = eng.score_grid(gt, arb_test.eval_cells(h, w, S, scale_max), mode, shave)
+        return arb_test.psnr_of(total, terms)
+
+    def score_u8(self, lr_u8, gt_u8, *, eval_type, scale_max=4):
+        """One image of a paired test set (`sr-implicit-paired[-fast]`, esc_arb/datasets/wrappers.py:27-34) scored on the device:
+        lr_u8 (h,w,3) and gt_u8 (H,W,3) uint8 device frames -> the reference's PSNR as a Python float.  s = H // h; the ground truth
+        is cropped to (h s, w s), which is also the queried grid; the cells are 2 / (h s), 2 / (w s) rounded to fp32, times
+        max(S / scale_max, 1) with S the integer of `eval_type` ('benchmark-S': the weighted channel sum, S pixels shaved;
+        'div2k-S': all of RGB, S + 6 shaved; None: all of RGB, no shave, the cell as it is; anything else: NotImplementedError).
+        hat_u8_to_planes, the encoder, hat_lte_query into the workspace, hat_arb_psnr: only the score leaves the device."""
+        from .. import arb_test
+        lr, gt = self._u8_frame("score_u8", "lr_u8", lr_u8), self._u8_frame("score_u8", "gt_u8", gt_u8)
+        _, (h, w) = arb_test.paired_sizes(lr.shape[0], lr.shape[1], gt.shape[0], gt.shape[1])
+        with torch.no_grad():
+            return self._score("score_u8", self.engine(lr.device), lr, gt[:h, :w], eval_type, scale_max)
+
+    def score_gt_u8(self, gt_u8, scale, *, eval_type, scale_max=4):
+        """One image of a ground-truth-only test set (`sr-implicit-downsampled[-fast]` with inp_size unset, wrappers.py:172-181):
+        per axis h_lr = floor(H / scale + 1e-9), the ground truth cropped to round(h_lr scale), the LR frame made from it by Pillow's
+        8-bit bicubic resize on the device (hat_pil_resize_u8: the bytes of the reference's `resize_fn`); then as `score_u8`."""
+        from .. import arb_test
+        gt = self._u8_frame("score_gt_u8", "gt_u8", gt_u8)
+        arb_test.parse_eval_type(eval_type)   # refuse before the resize runs
+        (h_lr, w_lr), (h, w) = arb_test.downsampled_sizes(gt.shape[0], gt.shape[1], scale)
+        arb_test.check_lr_size(h_lr, w_lr)
+        with torch.no_grad():
+            eng = self.engine(gt.device)
+            gt = gt[:h, :w]
+            return self._score("score_gt_u8", eng, eng.pil_lr_frame(gt, h_lr, w_lr), gt, eval_type, scale_max)
 
     def upscale_yuv(self, frame, size=None, scale=None, *, fmt: str, out_fmt=None, matrix: str = "bt601", full_range: bool = False, depth: int = 8,
                     out_depth=None, msb=None, out_msb=None, out=None, siting: str = "center", out_siting=None, scale_max=4):

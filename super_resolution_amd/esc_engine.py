@@ -344,13 +344,14 @@ class ESCLTEEngine(ESCEngine):
 
     # ---- frames: 8-bit and YCbCr in, any size out.  The sinks are hat_lte_query's own, so nothing of FrameBoundary
     # (reflect-padding, conv_last's epilogues, the ensemble) applies: ESC's window attention reflects its own edges.
-    def _ws_f32(self, H: int, W: int, key: str, shape) -> torch.Tensor:
-        """An fp32 buffer in the workspace of the (1, H, W) frame shape, allocated with its first use (FrameBoundary._ws_buffer's rule)."""
+    def _ws_f32(self, H: int, W: int, key: str, shape, dtype=torch.float32) -> torch.Tensor:
+        """An fp32 buffer (or one of `dtype`) in the workspace of the (1, H, W) frame shape, allocated with its first use
+        (FrameBoundary._ws_buffer's rule)."""
         ws = self._workspace(1, H, W)
         t = ws.get(key)
         if t is None or tuple(t.shape) != tuple(shape):
-            t = ws[key] = torch.zeros(shape, dtype=torch.float32, device=self.dev)
-            ws["bytes"] += t.numel() * 4
+            t = ws[key] = torch.zeros(shape, dtype=dtype, device=self.dev)
+            ws["bytes"] += t.numel() * t.element_size()
         return t
 
     def gen_feat_frame(self, H: int, W: int, fill) -> None:
@@ -370,6 +371,25 @@ class ESCLTEEngine(ESCEngine):
     def query_grid_planes(self, out: torch.Tensor, cell_yx, out_affine=(1.0, 0.0)) -> torch.Tensor:
         """query_grid into the caller's (3,h,w) or (1,3,h,w) contiguous fp32 tensor."""
         return self._query(out, grid=tuple(out.shape[-2:]), cell_yx=cell_yx, out_affine=out_affine)
+
+    # ---- the benchmark loop (esc_arb/test.py eval_psnr; DESIGN.md §4.22): the LR frame and the score are made on the device
+    def pil_lr_frame(self, gt: torch.Tensor, h_lr: int, w_lr: int) -> torch.Tensor:
+        """Pillow's 8-bit bicubic resize of the (h,w,3) uint8 ground truth (rows may be pitched) to (h_lr, w_lr), into the workspace
+        of the (h_lr, w_lr) frame (hat_pil_resize_u8)."""
+        with self._lock, torch.cuda.device(self.dev):
+            return ops.pil_resize_u8(gt, (h_lr, w_lr), dst=self._ws_f32(h_lr, w_lr, "lr_frame", (h_lr, w_lr, 3), torch.uint8))
+
+    def score_grid(self, gt: torch.Tensor, cell_yx, mode, shave: int):
+        """The grid of gt's (h, w) against the last gen_feat, image * 0.5 + 0.5, into the workspace; then hat_arb_psnr against gt
+        (h,w,3) uint8 -> (sum of squares, number of terms) as Python numbers: sixteen bytes leave the device."""
+        if self._feat_ws is None:
+            raise RuntimeError("ESC-LTE: score_grid before gen_feat: there are no features to query")
+        _, H, W = self._feat_ws
+        h, w = int(gt.shape[0]), int(gt.shape[1])
+        planes = self.query_grid_planes(self.planes_buffer(H, W, h, w), cell_yx, out_affine=(0.5, 0.5))
+        with self._lock, torch.cuda.device(self.dev):
+            s = ops.arb_psnr(planes, gt, mode=mode, shave=shave).cpu()
+        return float(s[0]), int(s[1])
 
     def query_grid_u8(self, out: torch.Tensor, cell_yx, bgr: bool = False, out_affine=(0.5, 0.5)) -> torch.Tensor:
         """The grid of out's (h, w) -> out (1,h,w,3) uint8 (rows may be pitched): tensor2img's bytes of the image * a + b."""

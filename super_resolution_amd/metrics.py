@@ -88,6 +88,45 @@ def calculate_niqe(img, crop_border, input_order="HWC", convert_to="y", **kw):
     return fn(img, crop_border, input_order=input_order, convert_to=convert_to, **kw)
 
 
+ARB_GRAY = (65.738, 129.057, 25.064)   # esc_arb/utils.py:138: divided by 256, on the DIFFERENCE image
+
+
+def arb_psnr_sums(pred, gt_u8, mode, shave: int):
+    """(sum of squares, number of terms) of the ESC-LTE benchmark's PSNR (esc_arb/utils.py:132-149 calc_psnr after test.py:95,
+    :112): the definition of what hat_arb_psnr sums.  pred: float32 (3,ph,pw), any range, at least as large as gt_u8 (h,w,3) uint8:
+    its top-left (h, w) is taken, clamped to [0, 1], and d = pred - float32(gt) / 255 formed in fp32.  mode 'benchmark': one term
+    per pixel, ((d_0 k_0 + d_1 k_1) + d_2 k_2)^2 with k = float32(ARB_GRAY) / 256, products and sums rounded to fp32 one by one;
+    'div2k' or None: three terms d_c^2.  `shave` pixels come off every side first.  The squares and their sum are fp64 (the
+    reference's fp32 `.pow(2).mean()` is the one step this does not restate: DESIGN.md §4.22)."""
+    if mode not in (None, "benchmark", "div2k"):
+        raise NotImplementedError(f"arb_psnr: mode {mode!r} is not one of None, 'benchmark', 'div2k'")
+    p = pred.detach().cpu().numpy() if isinstance(pred, torch.Tensor) else np.asarray(pred)
+    g = gt_u8.detach().cpu().numpy() if isinstance(gt_u8, torch.Tensor) else np.asarray(gt_u8)
+    if p.ndim == 4 and p.shape[0] == 1:
+        p = p[0]
+    if p.dtype != np.float32 or p.ndim != 3 or p.shape[0] != 3 or g.dtype != np.uint8 or g.ndim != 3 or g.shape[2] != 3:
+        raise ValueError(f"arb_psnr takes float32 (3,ph,pw) planes and an (h,w,3) uint8 ground truth, got {p.shape} {p.dtype}, {g.shape} {g.dtype}")
+    h, w, shave = g.shape[0], g.shape[1], int(shave)
+    if p.shape[1] < h or p.shape[2] < w:
+        raise ValueError(f"arb_psnr: the prediction {p.shape[1]}x{p.shape[2]} is smaller than the ground truth {h}x{w}")
+    if shave < 0 or 2 * shave >= h or 2 * shave >= w:
+        raise ValueError(f"arb_psnr: shaving {shave} pixels off every side of {h}x{w} leaves nothing")
+    d = np.clip(p[:, :h, :w], np.float32(0), np.float32(1)) - (g.astype(np.float32) / np.float32(255.0)).transpose(2, 0, 1)
+    d = d[:, shave:h - shave, shave:w - shave]
+    if mode == "benchmark":
+        k = np.asarray(ARB_GRAY, dtype=np.float32) / np.float32(256.0)
+        d = ((d[0] * k[0] + d[1] * k[1]) + d[2] * k[2])
+    d = d.astype(np.float64)
+    return float((d * d).sum()), int(d.size)
+
+
+def arb_psnr(pred, gt_u8, mode, shave: int) -> float:
+    """-10 log10(sum / terms) of arb_psnr_sums: 'benchmark-S' is (mode 'benchmark', shave S), 'div2k-S' is ('div2k', S + 6), no
+    eval_type is (None, 0)."""
+    s, n = arb_psnr_sums(pred, gt_u8, mode, shave)
+    return float("inf") if s == 0 else -10.0 * math.log10(s / n)
+
+
 METRICS = {"calculate_psnr": calculate_psnr, "calculate_ssim": calculate_ssim, "calculate_niqe": calculate_niqe}
 NO_REFERENCE = ("calculate_niqe",)   # the types that score `img` alone
 

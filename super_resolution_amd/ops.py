@@ -787,6 +787,111 @@ def imresize(src, scale: float, *, antialiasing: bool = True, dst=None, to: str 
     return dst
 
 
+# ---- Pillow's 8-bit bicubic resize and the ESC-LTE benchmark's PSNR (definitions: resize.pil_bicubic_u8, metrics.arb_psnr; kernels:
+# csrc/hat_pil_resize.hip) ----
+_pil_mid = {}               # (device, stream) -> ONE flat uint8 buffer, the image between the two passes: it only grows
+_arb_psnr_ws = {}           # (device, stream) -> (the partials' workspace, the (2,) float64 result)
+
+
+def _pil_axis(dev, in_len: int, out_len: int) -> dict:
+    """One axis' Pillow tables on `dev` (resize.pil_tables), cached beside the MATLAB ones: coef, bounds (device tensors), K."""
+    from . import resize as _rz
+    key = (str(dev), "pil", int(in_len), int(out_len))
+    t = _resize_tables.get(key)
+    if t is not None:
+        _resize_tables.move_to_end(key)
+    else:
+        coef, bounds = _rz.pil_tables(in_len, out_len)
+        t = {"coef": torch.from_numpy(coef).to(dev).contiguous(), "bounds": torch.from_numpy(bounds).to(dev).contiguous(), "K": coef.shape[1]}
+        _resize_tables[key] = t
+        while len(_resize_tables) > _RESIZE_TABLES_KEPT:
+            _resize_tables.popitem(last=False)
+    return t
+
+
+def pil_resize_u8(src, size, *, dst=None):
+    """resize.pil_bicubic_u8 on the device, bit for bit: src (h,w,3) uint8 (rows may be pitched) -> (size[0], size[1], 3) uint8,
+    PIL.Image.resize's 8-bit bicubic (hat_pil_resize_u8: the horizontal pass into a uint8 intermediate, then the vertical pass).
+    dst: the caller's destination (rows may be pitched; bytes past a row's width stay as they are); default: a fresh tensor."""
+    lib = _lib.load()
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 3 or src.stride(2) != 1 \
+            or src.stride(1) != 3:
+        raise RuntimeError(f"pil_resize_u8 needs an (h,w,3) uint8 frame with interleaved pixels, got {tuple(getattr(src, 'shape', ()))} "
+                           f"{getattr(src, 'dtype', type(src).__name__)}")
+    if not src.is_cuda:
+        raise RuntimeError("HAT HIP ops need device tensors (no CPU path exists: resize.pil_bicubic_u8 is the host definition)")
+    h, w = int(src.shape[0]), int(src.shape[1])
+    oh, ow = int(size[0]), int(size[1])
+    if min(h, w, oh, ow) < 1:
+        raise RuntimeError(f"pil_resize_u8: a resize of {h}x{w} to {oh}x{ow} has an empty side")
+    dev = src.device
+    if dst is None:
+        dst = torch.empty((oh, ow, 3), dtype=torch.uint8, device=dev)
+    elif not isinstance(dst, torch.Tensor) or tuple(dst.shape) != (oh, ow, 3) or dst.dtype != torch.uint8 or dst.device != dev \
+            or dst.stride(2) != 1 or dst.stride(1) != 3:
+        raise RuntimeError(f"pil_resize_u8: dst must be a {(oh, ow, 3)} uint8 tensor on {dev} with interleaved pixels, got "
+                           f"{tuple(getattr(dst, 'shape', ()))} {getattr(dst, 'dtype', type(dst).__name__)}")
+    tw, th = _pil_axis(dev, w, ow), _pil_axis(dev, h, oh)
+    key, n = (str(dev), _stream()), 3 * ow * h
+    mid = _pil_mid.get(key)
+    if mid is None or mid.numel() < n:
+        _pil_mid.pop(key, None)
+        mid = _pil_mid[key] = torch.empty(n, dtype=torch.uint8, device=dev)
+    src_pitch = src.stride(0) if h > 1 else 3 * w
+    dst_pitch = dst.stride(0) if oh > 1 else 3 * ow
+    _timed("pil_resize_h_kernel+pil_resize_v_kernel", 2.0 * 3 * ow * (h * tw["K"] + oh * th["K"]), lambda: _lib.check(
+        lib.hat_pil_resize_u8(src.data_ptr(), src_pitch, h, w, _ptr(mid), dst.data_ptr(), dst_pitch, oh, ow, _ptr(tw["coef"]),
+                              _ptr(tw["bounds"]), tw["K"], _ptr(th["coef"]), _ptr(th["bounds"]), th["K"], _stream()), "hat_pil_resize_u8"),
+        tag=f"pil bicubic {h}x{w} -> {oh}x{ow}", nbytes=3.0 * (h * w + 2 * h * ow + oh * ow))
+    return dst
+
+
+ARB_PSNR_MODES = (None, "benchmark", "div2k")   # utils.py:132-149: no eval_type, the weighted channel sum, all of RGB
+
+
+def arb_psnr_workspace_bytes(h: int, w: int, shave: int) -> int:
+    """Bytes of workspace hat_arb_psnr needs for an (h,w) ground truth; raises for what it refuses (a pure host query)."""
+    lib = _lib.load()
+    n = C.c_int64(0)
+    _lib.check(lib.hat_arb_psnr_workspace_bytes(int(h), int(w), int(shave), C.byref(n)), "hat_arb_psnr_workspace_bytes")
+    return n.value
+
+
+def arb_psnr(pred, gt, *, mode, shave: int, sums=None):
+    """metrics.arb_psnr's sum on the device: pred (3,ph,pw) or (1,3,ph,pw) contiguous fp32 planes, gt (h,w,3) uint8 (rows may be
+    pitched), h <= ph, w <= pw: the top-left (h, w) of pred is scored.  mode: None | 'benchmark' | 'div2k' (ARB_PSNR_MODES); shave
+    pixels off every side.  -> sums, a (2,) float64 device tensor (the caller's, or the device's and stream's own): the sum of
+    squares and the number of terms (hat_arb_psnr).  The same inputs give the same bits."""
+    lib = _lib.load()
+    if mode not in ARB_PSNR_MODES:
+        raise RuntimeError(f"arb_psnr: mode is one of {ARB_PSNR_MODES}, got {mode!r}")
+    if not isinstance(pred, torch.Tensor) or pred.dtype != torch.float32 or not pred.is_contiguous() \
+            or tuple(pred.shape[:-2]) not in ((3,), (1, 3)):
+        raise RuntimeError(f"arb_psnr needs contiguous (3,h,w) fp32 planes, got {tuple(getattr(pred, 'shape', ()))} "
+                           f"{getattr(pred, 'dtype', type(pred).__name__)}")
+    if not isinstance(gt, torch.Tensor) or gt.dtype != torch.uint8 or gt.dim() != 3 or gt.shape[2] != 3 or gt.stride(2) != 1 or gt.stride(1) != 3:
+        raise RuntimeError(f"arb_psnr needs an (h,w,3) uint8 ground truth with interleaved pixels, got {tuple(getattr(gt, 'shape', ()))}")
+    if not pred.is_cuda or gt.device != pred.device:
+        raise RuntimeError("HAT HIP ops need device tensors on one device (no CPU path exists: metrics.arb_psnr is the host definition)")
+    ph, pw = int(pred.shape[-2]), int(pred.shape[-1])
+    h, w = int(gt.shape[0]), int(gt.shape[1])
+    dev = pred.device
+    need = arb_psnr_workspace_bytes(h, w, shave)
+    key = (str(dev), _stream())
+    ws = _arb_psnr_ws.get(key)
+    if ws is None or ws[0].numel() < need:
+        ws = _arb_psnr_ws[key] = (torch.empty(max(need, 8192), dtype=torch.uint8, device=dev), torch.zeros(2, dtype=torch.float64, device=dev))
+    if sums is None:
+        sums = ws[1]
+    elif sums.dtype != torch.float64 or tuple(sums.shape) != (2,) or sums.device != dev:
+        raise RuntimeError(f"arb_psnr: sums must be a (2,) float64 tensor on {dev}")
+    _timed("arb_psnr_kernel", 0.0, lambda: _lib.check(
+        lib.hat_arb_psnr(_ptr(pred), ph, pw, gt.data_ptr(), gt.stride(0) if h > 1 else 3 * w, h, w, int(mode == "benchmark"), int(shave),
+                         _ptr(sums), _ptr(ws[0]), _stream()), "hat_arb_psnr"),
+        tag=f"arb psnr {h}x{w} shave {shave} {mode}", nbytes=15.0 * (h - 2 * shave) * (w - 2 * shave))
+    return sums
+
+
 def yuv420_views(frame, fmt: str = "nv12"):
     """yuv_views for the three 4:2:0 layouts of yuv.FORMATS: frame (B, 3h/2, w) -> views y (B,h,w), cb, cr (B,h/2,w/2), the torch
     twin of yuv.split.  The chroma views step 2 samples for nv12 / nv21 and 1 for i420."""

@@ -161,6 +161,76 @@ def error_bound(h: int, w: int, scale: float, antialiasing: bool = True, max_abs
     return (w_h.shape[1] * s_h + w_w.shape[1] * s_w * s_h) * 2.0 ** -24 * float(max_abs)
 
 
+# ---- Pillow's 8-bit bicubic `Image.resize` (libImaging/Resample.c): the DEFINITION of what csrc/hat_pil_resize.hip computes.
+# A sibling of the MATLAB tables above, not a mode of them: the scale is per axis (in / out), nothing is mirrored (the window is
+# cut at the image's edge and renormalised), the coefficients are 22-bit fixed point and the image between the two passes is
+# uint8.  The ESC-LTE benchmark's LR images are made with it (esc_arb/datasets/wrappers.py:149-152).
+PIL_PRECISION_BITS = 32 - 8 - 2   # Resample.c: PRECISION_BITS
+
+
+def _pil_bicubic(x: float) -> float:   # Resample.c: bicubic_filter, a = -0.5
+    a = -0.5
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def pil_tables(in_len: int, out_len: int):
+    """One axis of Pillow's 8-bit bicubic resize: (coef int32 (out_len, K), bounds int32 (out_len, 2) = (first tap, tap count)),
+    K = 2 ceil(2 max(in / out, 1)) + 1; output i is clip8((2^21 + sum_k coef[i,k] * pixel[first + k]) >> 22) over its tap count.
+    Float64 arithmetic in Pillow's order of operations (precompute_coeffs, normalize_coeffs_8bpc)."""
+    in_len, out_len = int(in_len), int(out_len)
+    if in_len < 1 or out_len < 1:
+        raise ValueError(f"a resize needs positive lengths, got {in_len} -> {out_len}")
+    scale = in_len / out_len
+    filterscale = max(scale, 1.0)
+    support = 2.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    coef = np.zeros((out_len, ksize), dtype=np.int32)
+    bounds = np.zeros((out_len, 2), dtype=np.int32)
+    ss = 1.0 / filterscale
+    for xx in range(out_len):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_len) - xmin
+        k = [_pil_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for v in k:
+            ww += v
+        if ww != 0.0:
+            k = [v / ww for v in k]
+        coef[xx, :xmax] = [int(-0.5 + v * (1 << PIL_PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PIL_PRECISION_BITS)) for v in k]
+        bounds[xx] = (xmin, xmax)
+    return coef, bounds
+
+
+def _pil_pass(img: np.ndarray, coef: np.ndarray, bounds: np.ndarray) -> np.ndarray:
+    """One pass along axis 0 of a (n, ...) uint8 array -> (out_len, ...) uint8, in integers."""
+    out = np.empty((coef.shape[0],) + img.shape[1:], dtype=np.uint8)
+    src = img.astype(np.int64)
+    tail = (1,) * (img.ndim - 1)
+    for i in range(coef.shape[0]):
+        first, n = int(bounds[i, 0]), int(bounds[i, 1])
+        acc = (coef[i, :n].astype(np.int64).reshape((n,) + tail) * src[first:first + n]).sum(0) + (1 << (PIL_PRECISION_BITS - 1))
+        out[i] = np.clip(acc >> PIL_PRECISION_BITS, 0, 255)
+    return out
+
+
+def pil_bicubic_u8(img_u8: np.ndarray, size) -> np.ndarray:
+    """(h,w,3) uint8 -> (size[0], size[1], 3) uint8, equal bit for bit to PIL.Image.resize((size[1], size[0]), BICUBIC) of the RGB
+    image: the horizontal pass into a uint8 image first, then the vertical pass."""
+    img = np.asarray(img_u8)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"expected an (h,w,3) uint8 frame, got {img.shape} {img.dtype}")
+    oh, ow = int(size[0]), int(size[1])
+    mid = _pil_pass(np.ascontiguousarray(img.transpose(1, 0, 2)), *pil_tables(img.shape[1], ow)).transpose(1, 0, 2)
+    return np.ascontiguousarray(_pil_pass(np.ascontiguousarray(mid), *pil_tables(img.shape[0], oh)))
+
+
 def mod_crop(h: int, w: int, n: int):
     return h - h % n, w - w % n
 
