@@ -14,8 +14,7 @@
 // the upper lane half of slot r%3 its ky = 1 terms: one cross-half add finishes the row.  No LDS, no barriers.
 #include <type_traits>
 
-#include "hat_common.h"
-#include "hat_yuv_check.h"
+#include "hat_frame_sink.h"
 
 __device__ __attribute__((aligned(16))) unsigned hat_cabsq_zero_page[80] = {};   // 160 bf16 channels of zeros
 
@@ -25,30 +24,20 @@ namespace {
 // NCHW = true: (acc + bias) * out_scale + mean[ch] -> (B,nst,H,W) fp32 planes (conv_last, hat_arch.py:856-858).
 // Epi = SweepEpiU8 (with NCHW): that same fp32 value, by the same expression, converted as tensor2img converts it and
 // stored as interleaved bytes (B,h_out,w_out,3) with a row pitch; rows and columns outside the crop are not stored.
-// Epi = SweepEpiYUV (with NCHW): that same fp32 value converted to 4:2:0 YCbCr (hat_rgb_to_ycc): a Y byte per pixel into outv,
-// a Cb and a Cr byte per 2 x 2 block into cb / cr.  The bands of this instantiation start on even rows.
-// Epi = SweepEpiYUV16 (with NCHW): SweepEpiYUV with 16-bit words for bytes: the n-bit code hat_ycc_code(., scale, maxcode) << shift.
-// Both carry the chroma subsampling of the destination as template parameters (SX, SY; GREY: no chroma): (1,1) is 4:2:0 as
-// described; (1,0) 4:2:2 stores chroma on every row from the even column's lane (the same row_shl:1 move, no carry between
-// rows); (0,0) 4:4:4 stores per lane with no move; GREY stores Y only.  Only (1,1) needs bands that start on even rows.
+// Epi = SweepEpiYuv<T, SX, SY, GREY> (with NCHW): that same fp32 value converted to YCbCr (hat_rgb_to_ycc) and stored into the
+// surface d as samples of type T (bytes, or n-bit codes in 16-bit words) by the one-pixel stores of hat_frame_sink.h.  The chroma
+// subsampling of the destination is (SX, SY; GREY: no chroma): (1,1) is 4:2:0, a Y sample per pixel and a Cb and a Cr sample per
+// 2 x 2 block, stored on odd rows from the even column's lane (the bands of this instantiation start on even rows); (1,0) 4:2:2
+// stores chroma on every row from the even column's lane (the same row_shl:1 move, no carry between rows); (0,0) 4:4:4 stores
+// per lane with no move; GREY stores Y only.
 struct SweepEpi { float out_scale; float mean[4]; int nst; };
 struct SweepEpiU8 { float out_scale; float mean[4]; int h_out, w_out, bgr; long long pitch, bstride; };
-template <int SX, int SY, bool GREY> struct SweepEpiYUVT {
-    float out_scale; float mean[4]; int h_out, w_out, c_step; long long pitch, bstride, c_pitch, c_bstride;
-    uint8_t* cb; uint8_t* cr; HatCsc k;
+template <typename T, int SX, int SY, bool GREY> struct SweepEpiYuv {
+    float out_scale; float mean[4]; int h_out, w_out; HatCsc k; HatSample<T> q; HatYuvDst<T> d;
 };
-template <int SX, int SY, bool GREY> struct SweepEpiYUV16T {   // pitches, strides and c_step in bytes, as everywhere
-    float out_scale; float mean[4]; int h_out, w_out, c_step; long long pitch, bstride, c_pitch, c_bstride;
-    uint8_t* cb; uint8_t* cr; HatCsc k; int shift; float scale, maxcode;
-};
-using SweepEpiYUV = SweepEpiYUVT<1, 1, false>;
-using SweepEpiYUV16 = SweepEpiYUV16T<1, 1, false>;
-template <typename E> struct SweepYuvTraits { static constexpr bool yuv = false, deep = false, grey = false; static constexpr int sx = 1, sy = 1; };
-template <int SX, int SY, bool G> struct SweepYuvTraits<SweepEpiYUVT<SX, SY, G>> {
-    static constexpr bool yuv = true, deep = false, grey = G; static constexpr int sx = SX, sy = SY;
-};
-template <int SX, int SY, bool G> struct SweepYuvTraits<SweepEpiYUV16T<SX, SY, G>> {
-    static constexpr bool yuv = true, deep = true, grey = G; static constexpr int sx = SX, sy = SY;
+template <typename E> struct SweepYuvTraits { static constexpr bool yuv = false, grey = false; static constexpr int sx = 1, sy = 1; };
+template <typename T, int SX, int SY, bool G> struct SweepYuvTraits<SweepEpiYuv<T, SX, SY, G>> {
+    static constexpr bool yuv = true, grey = G; static constexpr int sx = SX, sy = SY;
 };
 
 template <int KS, bool NCHW, typename Epi = SweepEpi>
@@ -58,7 +47,7 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
                                                              int rows, int strips, int units, Epi epi) {
     constexpr bool U8 = std::is_same<Epi, SweepEpiU8>::value;
     using YT = SweepYuvTraits<Epi>;
-    constexpr bool YUV16 = YT::deep, YUV = YT::yuv;
+    constexpr bool YUV = YT::yuv;
     constexpr bool C420 = YUV && !YT::grey && YT::sx == 1 && YT::sy == 1, C422 = YUV && !YT::grey && YT::sx == 1 && YT::sy == 0;
     constexpr bool C444 = YUV && !YT::grey && YT::sx == 0;
     static_assert((!U8 && !YUV) || NCHW, "the byte epilogues convert the conv_last value");
@@ -74,8 +63,8 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
     bf16_t* ob = reinterpret_cast<bf16_t*>(outv) + (size_t)b * H * W * 8;
     float* of = nullptr;
     uint8_t* o8 = nullptr;
-    if constexpr (U8 || YUV) o8 = reinterpret_cast<uint8_t*>(outv) + (size_t)b * epi.bstride;
-    else of = reinterpret_cast<float*>(outv) + (size_t)b * epi.nst * H * W;
+    if constexpr (U8) o8 = reinterpret_cast<uint8_t*>(outv) + (size_t)b * epi.bstride;
+    else if constexpr (!YUV) of = reinterpret_cast<float*>(outv) + (size_t)b * epi.nst * H * W;
     // yuv epilogue: cb00 + cb01 and cr00 + cr01 of the even row wait here for the odd row (the lane of the even column)
     [[maybe_unused]] float ctop_b = 0.f, ctop_r = 0.f;
 
@@ -150,8 +139,8 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
             // Lane group g = 0 holds R, G, B of pixel (y, xx).  A strip starts at the even column 14 strip = lane c16 = 1, so the
             // pixels of a 2 x 2 block's row sit in lanes (c16, c16 + 1), c16 odd: one row_shl:1 move per chroma component brings
             // the right pixel's term to the left pixel's lane.  Every lane runs the arithmetic (the move is not under the store's
-            // condition); only lanes that own a pixel inside the crop store.  Y: one byte per lane and row, a 14-byte span per
-            // strip; Cb, Cr: on odd rows, the lane of the even column, 7 samples per strip.
+            // condition); only lanes that own a pixel inside the crop store.  Y: one sample per lane and row, 14 per strip; 4:2:0
+            // Cb, Cr: on odd rows, the lane of the even column, 7 samples per strip.
             const f32x4 vb = v + bs;
             float Yv, cbv, crv;
             hat_rgb_to_ycc(epi.k, vb[0] * epi.out_scale + epi.mean[0], vb[1] * epi.out_scale + epi.mean[1], vb[2] * epi.out_scale + epi.mean[2],
@@ -164,45 +153,13 @@ __global__ __launch_bounds__(256, KS > 2 ? 2 : 3) void cab_squeeze_kernel(const 
                 crs = hat_add_rn(crv, crn);
             }
             if (y >= y0 && y < y1 && g == 0 && oin && y < epi.h_out && xx < epi.w_out) {
-                if constexpr (YUV16) {
-                    // the same lanes, 16-bit stores: a 28-byte Y span per strip and row, 7 + 7 chroma words on odd rows
-                    *reinterpret_cast<uint16_t*>(o8 + (size_t)y * epi.pitch + 2 * (size_t)xx) = (uint16_t)(hat_ycc_code(Yv, epi.scale, epi.maxcode) << epi.shift);
-                    if constexpr (C420) {
-                        if ((y & 1) && !(xx & 1)) {
-                            const size_t co = (size_t)b * epi.c_bstride + (size_t)(y >> 1) * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
-                            *reinterpret_cast<uint16_t*>(epi.cb + co) = (uint16_t)(hat_ycc_code(hat_chroma_value(ctop_b, cbs, epi.k.m[7]), epi.scale, epi.maxcode) << epi.shift);
-                            *reinterpret_cast<uint16_t*>(epi.cr + co) = (uint16_t)(hat_ycc_code(hat_chroma_value(ctop_r, crs, epi.k.m[11]), epi.scale, epi.maxcode) << epi.shift);
-                        }
-                    } else if constexpr (C422) {   // every row, the lane of the even column: 7 + 7 chroma words per strip and row
-                        if (!(xx & 1)) {
-                            const size_t co = (size_t)b * epi.c_bstride + (size_t)y * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
-                            *reinterpret_cast<uint16_t*>(epi.cb + co) = (uint16_t)(hat_ycc_code(hat_chroma_value_h(cbs, epi.k.m[7]), epi.scale, epi.maxcode) << epi.shift);
-                            *reinterpret_cast<uint16_t*>(epi.cr + co) = (uint16_t)(hat_ycc_code(hat_chroma_value_h(crs, epi.k.m[11]), epi.scale, epi.maxcode) << epi.shift);
-                        }
-                    } else if constexpr (C444) {   // every lane: 14 + 14 chroma words per strip and row
-                        const size_t co = (size_t)b * epi.c_bstride + (size_t)y * epi.c_pitch + (size_t)xx * epi.c_step;
-                        *reinterpret_cast<uint16_t*>(epi.cb + co) = (uint16_t)(hat_ycc_code(hat_add_rn(cbv, epi.k.m[7]), epi.scale, epi.maxcode) << epi.shift);
-                        *reinterpret_cast<uint16_t*>(epi.cr + co) = (uint16_t)(hat_ycc_code(hat_add_rn(crv, epi.k.m[11]), epi.scale, epi.maxcode) << epi.shift);
-                    }
-                } else {
-                    o8[(size_t)y * epi.pitch + xx] = (uint8_t)hat_ycc_byte(Yv);
-                    if constexpr (C420) {
-                        if ((y & 1) && !(xx & 1)) {
-                            const size_t co = (size_t)b * epi.c_bstride + (size_t)(y >> 1) * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
-                            epi.cb[co] = (uint8_t)hat_chroma_byte(ctop_b, cbs, epi.k.m[7]);
-                            epi.cr[co] = (uint8_t)hat_chroma_byte(ctop_r, crs, epi.k.m[11]);
-                        }
-                    } else if constexpr (C422) {
-                        if (!(xx & 1)) {
-                            const size_t co = (size_t)b * epi.c_bstride + (size_t)y * epi.c_pitch + (size_t)(xx >> 1) * epi.c_step;
-                            epi.cb[co] = (uint8_t)hat_ycc_byte(hat_chroma_value_h(cbs, epi.k.m[7]));
-                            epi.cr[co] = (uint8_t)hat_ycc_byte(hat_chroma_value_h(crs, epi.k.m[11]));
-                        }
-                    } else if constexpr (C444) {
-                        const size_t co = (size_t)b * epi.c_bstride + (size_t)y * epi.c_pitch + (size_t)xx * epi.c_step;
-                        epi.cb[co] = (uint8_t)hat_ycc_byte(hat_add_rn(cbv, epi.k.m[7]));
-                        epi.cr[co] = (uint8_t)hat_ycc_byte(hat_add_rn(crv, epi.k.m[11]));
-                    }
+                yuv_store_luma(epi.d, epi.q, b, y, xx, Yv);
+                if constexpr (C420) {
+                    if ((y & 1) && !(xx & 1)) yuv_store_chroma420(epi.d, epi.q, epi.k, b, y >> 1, xx >> 1, ctop_b, cbs, ctop_r, crs);
+                } else if constexpr (C422) {   // every row, the lane of the even column
+                    if (!(xx & 1)) yuv_store_chroma422(epi.d, epi.q, epi.k, b, y, xx >> 1, cbs, crs);
+                } else if constexpr (C444) {   // every lane
+                    yuv_store_chroma444(epi.d, epi.q, epi.k, b, y, xx, cbv, crv);
                 }
             }
             if constexpr (C420) {
@@ -333,25 +290,18 @@ int sweep_conv_last_ok(const void* x, const void* wpk, int C, int ldx, int dtype
     return (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpk)) % 16 ? HAT_EINVAL : 0;
 }
 
-template <typename Epi>
-void launch_sweep_yuv(const void* x, const void* wpk, const float* bias, const HatYuvSurface& d, int B, int H, int W, int C, int ldx, int h_out,
-                      int w_out, float out_scale, const float* mean4, const float* from_rgb12, bool even_rows, hipStream_t st) {
-    int rows = 0, units = 0;
-    sweep_units(H, W, 3072, &rows, &units, even_rows);      // hat_conv3x3_to_planes' geometry; even band heights for 4:2:0 only
-    Epi epi{};
-    epi.out_scale = out_scale;
-    for (int i = 0; i < 4; ++i) epi.mean[i] = mean4[i];
-    epi.h_out = h_out, epi.w_out = w_out, epi.c_step = d.c_step;
-    epi.pitch = d.y_pitch, epi.bstride = d.y_bstride, epi.c_pitch = d.c_pitch, epi.c_bstride = d.c_bstride;
-    epi.cb = reinterpret_cast<uint8_t*>(d.cb), epi.cr = reinterpret_cast<uint8_t*>(d.cr);
-    for (int i = 0; i < 12; ++i) epi.k.m[i] = from_rgb12[i];
-    if constexpr (SweepYuvTraits<Epi>::deep) {
-        epi.shift = d.msb ? 16 - d.depth : 0;
-        epi.scale = (float)(1 << (d.depth - 8));
-        epi.maxcode = (float)((1u << d.depth) - 1u);
-    }
-    HAT_LAUNCH((cab_squeeze_kernel<2, true, Epi>), dim3((units + 3) / 4, B), dim3(256), 0, st, reinterpret_cast<const bf16_t*>(x),
-               reinterpret_cast<const bf16_t*>(wpk), bias, d.y, nullptr, H, W, C, ldx, rows, (W + 13) / 14, units, epi);
+int launch_sweep_yuv(const void* x, const void* wpk, const float* bias, const HatYuvSurface& d, int B, int H, int W, int C, int ldx, int h_out,
+                     int w_out, float out_scale, const float* mean4, const float* from_rgb12, void* stream) {
+    yuv_dispatch(d, [&](auto L, auto q) {
+        using T = typename decltype(L)::sample_t;
+        using Epi = SweepEpiYuv<T, L.sx, L.sy, L.grey>;
+        int rows = 0, units = 0;
+        sweep_units(H, W, 3072, &rows, &units, L.sy == 1);   // hat_conv3x3_to_planes' geometry; even band heights for 4:2:0 only
+        const Epi epi{out_scale, {mean4[0], mean4[1], mean4[2], mean4[3]}, h_out, w_out, load_csc(from_rgb12), q, yuv_dst<T>(d)};
+        HAT_LAUNCH((cab_squeeze_kernel<2, true, Epi>), dim3((units + 3) / 4, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                   reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(wpk), bias, d.y, nullptr, H, W, C, ldx, rows, (W + 13) / 14, units, epi);
+    });
+    return hat_check_launch();
 }
 }  // namespace
 
@@ -363,9 +313,8 @@ extern "C" int hat_conv3x3_to_yuv420(const void* x, const void* wpk, const float
     if (!x || !wpk || !bias || !y || !cb || !cr || !mean4 || !from_rgb12 || H < 1 || W < 16 || W % 16 || h_out > H || w_out > W) return HAT_EINVAL;
     if (!hat_yuv_block_ok(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out)) return HAT_EINVAL;
     if (const int rc = sweep_conv_last_ok(x, wpk, C, ldx, dtype)) return rc;
-    launch_sweep_yuv<SweepEpiYUV>(x, wpk, bias, hat_yuv420_surface(y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride, 8, 0), B, H, W, C, ldx,
-                                  h_out, w_out, out_scale, mean4, from_rgb12, true, reinterpret_cast<hipStream_t>(stream));
-    return hat_check_launch();
+    return launch_sweep_yuv(x, wpk, bias, hat_yuv420_surface(y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride, 8, 0), B, H, W, C, ldx, h_out,
+                            w_out, out_scale, mean4, from_rgb12, stream);
 }
 
 extern "C" int hat_conv3x3_to_yuv420p16(const void* x, const void* wpk, const float* bias, uint16_t* y, int64_t y_pitch, int64_t y_bstride,
@@ -376,9 +325,8 @@ extern "C" int hat_conv3x3_to_yuv420p16(const void* x, const void* wpk, const fl
     if (!hat_yuv_depth_ok(depth, msb) || ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(cb) | reinterpret_cast<uintptr_t>(cr)) & 1)) return HAT_EINVAL;
     if (!hat_yuv_block_ok_n(y_pitch, y_bstride, c_pitch, c_step, c_bstride, B, h_out, w_out, 2)) return HAT_EINVAL;
     if (const int rc = sweep_conv_last_ok(x, wpk, C, ldx, dtype)) return rc;
-    launch_sweep_yuv<SweepEpiYUV16>(x, wpk, bias, hat_yuv420_surface(y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride, depth, msb), B, H, W, C,
-                                    ldx, h_out, w_out, out_scale, mean4, from_rgb12, true, reinterpret_cast<hipStream_t>(stream));
-    return hat_check_launch();
+    return launch_sweep_yuv(x, wpk, bias, hat_yuv420_surface(y, y_pitch, y_bstride, cb, cr, c_pitch, c_step, c_bstride, depth, msb), B, H, W, C, ldx,
+                            h_out, w_out, out_scale, mean4, from_rgb12, stream);
 }
 
 // the destination described once: the instance by the surface's depth and subsampling
@@ -388,19 +336,5 @@ extern "C" int hat_conv3x3_to_yuv(const void* x, const void* wpk, const float* b
     if (!x || !wpk || !bias || !mean4 || !from_rgb12 || H < 1 || W < 16 || W % 16 || h_out > H || w_out > W) return HAT_EINVAL;
     if (!hat_yuv_surface_ok(dst, B, h_out, w_out)) return HAT_EINVAL;
     if (const int rc = sweep_conv_last_ok(x, wpk, C, ldx, dtype)) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define HAT_SWEEP_YUV(E, even) launch_sweep_yuv<E>(x, wpk, bias, *dst, B, H, W, C, ldx, h_out, w_out, out_scale, mean4, from_rgb12, even, st)
-    using Grey8 = SweepEpiYUVT<0, 0, true>;
-    using Grey16 = SweepEpiYUV16T<0, 0, true>;
-    using C422x8 = SweepEpiYUVT<1, 0, false>;
-    using C422x16 = SweepEpiYUV16T<1, 0, false>;
-    using C444x8 = SweepEpiYUVT<0, 0, false>;
-    using C444x16 = SweepEpiYUV16T<0, 0, false>;
-    const bool deep = dst->depth != 8;
-    if (!dst->cb) { if (deep) HAT_SWEEP_YUV(Grey16, false); else HAT_SWEEP_YUV(Grey8, false); }
-    else if (dst->sub_y) { if (deep) HAT_SWEEP_YUV(SweepEpiYUV16, true); else HAT_SWEEP_YUV(SweepEpiYUV, true); }
-    else if (dst->sub_x) { if (deep) HAT_SWEEP_YUV(C422x16, false); else HAT_SWEEP_YUV(C422x8, false); }
-    else { if (deep) HAT_SWEEP_YUV(C444x16, false); else HAT_SWEEP_YUV(C444x8, false); }
-#undef HAT_SWEEP_YUV
-    return hat_check_launch();
+    return launch_sweep_yuv(x, wpk, bias, *dst, B, H, W, C, ldx, h_out, w_out, out_scale, mean4, from_rgb12, stream);
 }

@@ -2,14 +2,12 @@
 // fp32 rows `to_img` left (plus ESC's base image) stored as interleaved bytes or as a YCbCr surface; no fp32 image is written.
 // Contract: include/hat_mi355x.h (hat_shuffle_to_u8, hat_shuffle_to_yuv); DESIGN.md 4.21.
 // The value of output pixel (b, c, Y, X) is rows[b][Y / s][X / s][c s^2 + (Y % s) s + X % s] (+ base[b][c][Y / s][X / s], one
-// rounded fp32 add: what esc_shuffle_add_kernel stores), and it is converted by the device functions planes_to_u8_kernel
-// (hat_u8.hip) and planes_to_yuv420_kernel (hat_yuv.hip) call, in their order and with their thread shapes, so the bytes are
-// those of hat_esc_shuffle_add / hat_shuffle_planes followed by hat_planes_to_u8 / hat_planes_to_yuv by construction.
+// rounded fp32 add: what esc_shuffle_add_kernel stores).  It is converted and stored by rgb4_store_u8 and yuv_store_tile
+// (hat_frame_sink.h), the functions planes_to_u8_kernel (hat_u8.hip) and planes_to_yuv420_kernel (hat_yuv.hip) end in, with their
+// thread shapes: the bytes are those of hat_esc_shuffle_add / hat_shuffle_planes followed by hat_planes_to_u8 / hat_planes_to_yuv.
 // Bound: the rows read (4 r4(3 s^2) bytes per LR pixel; every 64-byte line of it is fetched from HBM once and again from L2 by
 // the s output rows that share it) and the byte store.  No LDS, no MFMA.
-#include "hat_common.h"
-#include "hat_yuv_check.h"
-#include "hat_yuv_sample.h"
+#include "hat_frame_sink.h"
 
 namespace {
 
@@ -58,107 +56,25 @@ template <int R> __device__ __forceinline__ void shuffle_tile(const ShuffleSrc& 
     }
 }
 
-// planes_to_u8_kernel's thread: four consecutive pixels of an output row = 12 bytes, three dword stores when the row segment is
-// 4-byte aligned and whole, single bytes otherwise
+// one thread = four consecutive pixels of an output row, stored by rgb4_store_u8
 __global__ __launch_bounds__(256) void shuffle_to_u8_kernel(const ShuffleSrc a, uint8_t* __restrict__ dst, long long pitch, long long dbstride,
                                                             int w_out, int bgr) {
     const int x = (blockIdx.x * 256 + threadIdx.x) * 4, y = blockIdx.y, b = blockIdx.z;
     if (x >= w_out) return;
-    uint8_t* o = dst + (size_t)b * dbstride + (size_t)y * pitch + (size_t)x * 3;
     const int n = min(4, w_out - x);
     float v[1][4][3];
     shuffle_tile<1>(a, b, y, x, n, v);
-    unsigned q[12];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) q[3 * i + c] = i < n ? hat_unit_to_u8(bgr ? v[0][i][2 - c] : v[0][i][c]) : 0u;
-    if (n == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            reinterpret_cast<unsigned*>(o)[k] = q[4 * k] | (q[4 * k + 1] << 8) | (q[4 * k + 2] << 16) | (q[4 * k + 3] << 24);
-    } else {
-        for (int k = 0; k < 3 * n; ++k) o[k] = (uint8_t)q[k];
-    }
+    rgb4_store_u8(dst + (size_t)b * dbstride + (size_t)y * pitch + (size_t)x * 3, v[0], n, bgr);
 }
 
-// planes_to_yuv420_kernel's thread: (1 + SUB_Y) rows x four columns, the Y samples of a row through store_row4, the chroma pair
-// sums left + right, then top + bottom; a tail of n = 1, 2 or 3 columns (odd only without horizontal subsampling)
+// one thread = (1 + SUB_Y) rows x four columns, converted and stored by yuv_store_tile
 template <typename T, int SUB_X, int SUB_Y, bool GREY>
-__global__ __launch_bounds__(256) void shuffle_to_yuv_kernel(const ShuffleSrc a, T* __restrict__ yp, long long y_pitch, long long y_bstride,
-                                                             T* __restrict__ cbp, T* __restrict__ crp, long long c_pitch, int c_step,
-                                                             long long c_bstride, int w_out, HatCsc k, HatSample<T> q) {
+__global__ __launch_bounds__(256) void shuffle_to_yuv_kernel(const ShuffleSrc a, const HatYuvDst<T> d, int w_out, HatCsc k, HatSample<T> q) {
     constexpr int R = 1 + SUB_Y;
     const int x = (blockIdx.x * 256 + threadIdx.x) * 4, y = blockIdx.y * R, b = blockIdx.z;
     if (x >= w_out) return;
     const int n = min(4, w_out - x);
-    float rgb[R][4][3];
-    shuffle_tile<R>(a, b, y, x, n, rgb);
-    float cb[R][4], cr[R][4];
-    unsigned v[R][4];
-#pragma unroll
-    for (int j = 0; j < R; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float Y = 0.f;
-            cb[j][i] = cr[j][i] = 0.f;
-            if (i < n) hat_rgb_to_ycc(k, rgb[j][i][0], rgb[j][i][1], rgb[j][i][2], Y, cb[j][i], cr[j][i]);
-            v[j][i] = q.luma(Y);
-        }
-#pragma unroll
-    for (int j = 0; j < R; ++j)
-        store_row4(&sample_at(yp, (size_t)b * y_bstride + (size_t)(y + j) * y_pitch + (size_t)x * sizeof(T)), v[j], n);
-    if constexpr (!GREY) {
-        const size_t co = (size_t)b * c_bstride + (size_t)(y >> SUB_Y) * c_pitch + (size_t)(x >> SUB_X) * c_step;
-        if constexpr (SUB_X == 1 && SUB_Y == 1) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                if (2 * i < n) {
-                    sample_at(cbp, co + (size_t)i * c_step) = (T)q.chroma(hat_add_rn(cb[0][2 * i], cb[0][2 * i + 1]), hat_add_rn(cb[1][2 * i], cb[1][2 * i + 1]), k.m[7]);
-                    sample_at(crp, co + (size_t)i * c_step) = (T)q.chroma(hat_add_rn(cr[0][2 * i], cr[0][2 * i + 1]), hat_add_rn(cr[1][2 * i], cr[1][2 * i + 1]), k.m[11]);
-                }
-            }
-        } else if constexpr (SUB_X == 1) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                if (2 * i < n) {
-                    sample_at(cbp, co + (size_t)i * c_step) = (T)q.luma(hat_chroma_value_h(hat_add_rn(cb[0][2 * i], cb[0][2 * i + 1]), k.m[7]));
-                    sample_at(crp, co + (size_t)i * c_step) = (T)q.luma(hat_chroma_value_h(hat_add_rn(cr[0][2 * i], cr[0][2 * i + 1]), k.m[11]));
-                }
-            }
-        } else {
-            unsigned vb[4], vr[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                vb[i] = q.luma(hat_add_rn(cb[0][i], k.m[7]));
-                vr[i] = q.luma(hat_add_rn(cr[0][i], k.m[11]));
-            }
-            if (c_step == (int)sizeof(T)) {
-                store_row4(&sample_at(cbp, co), vb, n);
-                store_row4(&sample_at(crp, co), vr, n);
-            } else {
-                for (int i = 0; i < n; ++i) {
-                    sample_at(cbp, co + (size_t)i * c_step) = (T)vb[i];
-                    sample_at(crp, co + (size_t)i * c_step) = (T)vr[i];
-                }
-            }
-        }
-    }
-}
-
-template <typename T, int SX, int SY, bool GREY>
-void launch_yuv(const ShuffleSrc& a, int B, const HatYuvSurface& d, int h_out, int w_out, const HatCsc& k, HatSample<T> q, hipStream_t st) {
-    HAT_LAUNCH((shuffle_to_yuv_kernel<T, SX, SY, GREY>), dim3((w_out + 1023) / 1024, h_out >> SY, B), dim3(256), 0, st, a, reinterpret_cast<T*>(d.y),
-               (long long)d.y_pitch, (long long)d.y_bstride, reinterpret_cast<T*>(d.cb), reinterpret_cast<T*>(d.cr), (long long)d.c_pitch,
-               (int)d.c_step, (long long)d.c_bstride, w_out, k, q);
-}
-
-template <typename T>
-void surface_yuv(const ShuffleSrc& a, int B, const HatYuvSurface& d, int h_out, int w_out, const HatCsc& k, HatSample<T> q, hipStream_t st) {
-    if (!d.cb) launch_yuv<T, 0, 0, true>(a, B, d, h_out, w_out, k, q, st);
-    else if (d.sub_y) launch_yuv<T, 1, 1, false>(a, B, d, h_out, w_out, k, q, st);
-    else if (d.sub_x) launch_yuv<T, 1, 0, false>(a, B, d, h_out, w_out, k, q, st);
-    else launch_yuv<T, 0, 0, false>(a, B, d, h_out, w_out, k, q, st);
+    yuv_store_tile<T, SUB_X, SUB_Y, GREY>(d, k, q, b, y, x, n, [&](float (&rgb)[R][4][3]) { shuffle_tile<R>(a, b, y, x, n, rgb); });
 }
 
 // what both entries ask of the source and the crop; 0 when they hold
@@ -187,9 +103,10 @@ extern "C" int hat_shuffle_to_yuv(const float* rows, int32_t ld, const float* ba
     if (!dst || !from_rgb12 || (reinterpret_cast<uintptr_t>(base) & 3)) return HAT_EINVAL;
     if (const int rc = shuffle_check(rows, ld, B, H, W, s, h_out, w_out)) return rc;
     if (!hat_yuv_surface_ok(dst, B, h_out, w_out)) return HAT_EINVAL;   // (odd crops on subsampled axes, short or odd pitches)
-    const ShuffleSrc a{rows, base, H, W, s, ld};
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dst->depth == 8) surface_yuv<uint8_t>(a, B, *dst, h_out, w_out, load_csc(from_rgb12), HatSample<uint8_t>{}, st);
-    else surface_yuv<uint16_t>(a, B, *dst, h_out, w_out, load_csc(from_rgb12), deep_sample(dst->depth, dst->msb), st);
+    yuv_dispatch(*dst, [&](auto L, auto q) {
+        using T = typename decltype(L)::sample_t;
+        HAT_LAUNCH((shuffle_to_yuv_kernel<T, L.sx, L.sy, L.grey>), dim3((w_out + 1023) / 1024, h_out >> L.sy, B), dim3(256), 0,
+                   reinterpret_cast<hipStream_t>(stream), ShuffleSrc{rows, base, H, W, s, ld}, yuv_dst<T>(*dst), w_out, load_csc(from_rgb12), q);
+    });
     return hat_check_launch();
 }

@@ -14,9 +14,7 @@
 // wave has finished reading.  The last layer (256 -> 3) is folded into the third layer's epilogue from the fp32 accumulators.
 // Grid mode tiles the output 4 x 8 so that the queries of a tile share feature pixels.
 // Contract: include/hat_mi355x.h "ESC-LTE".  DESIGN.md 4.19, 4.20.
-#include "hat_common.h"
-#include "hat_yuv_check.h"
-#include "hat_yuv_sample.h"
+#include "hat_frame_sink.h"
 
 namespace {
 
@@ -125,45 +123,31 @@ struct LteU8 {
     }
 };
 
-// A YCbCr surface, centre-sited: planes_to_yuv420_kernel's conversion per pixel and per chroma sample (hat_yuv.hip).  The tile origin
-// is even in both axes, so lane q's horizontal partner is q ^ 1 and its vertical partner q ^ 8, and the lane with even ox (and even
-// oy where SUB_Y) stores the chroma sample of its pair / block.  store() is called by every lane of the wave, valid or not: the
+// A YCbCr surface, centre-sited: hat_rgb_to_ycc per pixel, then the one-pixel stores of hat_frame_sink.h (yuv_store_luma,
+// yuv_store_chroma420 / 422 / 444), which yuv_store_tile of the planes route shares.  The tile origin is even in both axes, so lane
+// q's horizontal partner is q ^ 1 and its vertical partner q ^ 8, and the lane with even ox (and even oy where SUB_Y) stores the chroma sample of its pair / block.  store() is called by every lane of the wave, valid or not: the
 // exchanges are outside every branch; a lane without a pixel converts zeros and stores nothing.  The subsampled axes of the image
 // have even extent (the host checks it), so the partner of a lane that stores is a pixel of the image.
 template <typename S, int SUB_X, int SUB_Y, bool GREY> struct LteYuv {
-    S* yp;
-    S* cbp;
-    S* crp;
-    long long y_pitch, c_pitch;
-    int c_step;
+    HatYuvDst<S> d;   // (one image: sample 0)
     HatCsc k;
     HatSample<S> q;
     __device__ __forceinline__ void store(const float (&rgb)[3], bool valid, int oy, int ox) const {
         float Y, cb, cr;
         hat_rgb_to_ycc(k, rgb[0], rgb[1], rgb[2], Y, cb, cr);
-        if (valid) sample_at(yp, (size_t)oy * y_pitch + (size_t)ox * sizeof(S)) = (S)q.luma(Y);
+        if (valid) yuv_store_luma(d, q, 0, oy, ox, Y);
         if constexpr (!GREY) {
-            const size_t co = (size_t)(oy >> SUB_Y) * c_pitch + (size_t)(ox >> SUB_X) * c_step;
             if constexpr (SUB_X == 1) {
                 // the pair sum left + right, in that order, on the even lane
                 const float sb = hat_add_rn(cb, __shfl_xor(cb, 1)), sr = hat_add_rn(cr, __shfl_xor(cr, 1));
                 if constexpr (SUB_Y == 1) {
                     const float bb = __shfl_xor(sb, 8), br = __shfl_xor(sr, 8);   // the bottom row's pair sums, on the top row's lanes
-                    if (valid && !(ox & 1) && !(oy & 1)) {
-                        sample_at(cbp, co) = (S)q.chroma(sb, bb, k.m[7]);
-                        sample_at(crp, co) = (S)q.chroma(sr, br, k.m[11]);
-                    }
+                    if (valid && !(ox & 1) && !(oy & 1)) yuv_store_chroma420(d, q, k, 0, oy >> 1, ox >> 1, sb, bb, sr, br);
                 } else {
-                    if (valid && !(ox & 1)) {
-                        sample_at(cbp, co) = (S)q.luma(hat_chroma_value_h(sb, k.m[7]));
-                        sample_at(crp, co) = (S)q.luma(hat_chroma_value_h(sr, k.m[11]));
-                    }
+                    if (valid && !(ox & 1)) yuv_store_chroma422(d, q, k, 0, oy, ox >> 1, sb, sr);
                 }
             } else {
-                if (valid) {
-                    sample_at(cbp, co) = (S)q.luma(hat_add_rn(cb, k.m[7]));
-                    sample_at(crp, co) = (S)q.luma(hat_add_rn(cr, k.m[11]));
-                }
+                if (valid) yuv_store_chroma444(d, q, k, 0, oy, ox, cb, cr);
             }
         }
     }
@@ -470,18 +454,6 @@ template <typename Sink> int lte_launch_dtype(const LteArgs& a, const Sink& sink
     return dtype == HAT_BF16 ? lte_launch<bf16_t>(a, sink, tiles, s) : lte_launch<float>(a, sink, tiles, s);
 }
 
-template <typename S> int lte_launch_yuv(const LteArgs& a, const HatYuvSurface& d, const HatCsc& k, HatSample<S> q, int64_t tiles, int32_t dtype,
-                                         void* stream) {
-    S* y = reinterpret_cast<S*>(d.y);
-    S* cb = reinterpret_cast<S*>(d.cb);
-    S* cr = reinterpret_cast<S*>(d.cr);
-    if (!d.cb) return lte_launch_dtype(a, LteYuv<S, 0, 0, true>{y, nullptr, nullptr, (long long)d.y_pitch, 0, 0, k, q}, tiles, dtype, stream);
-    const long long yp = d.y_pitch, cp = d.c_pitch;
-    if (d.sub_y) return lte_launch_dtype(a, LteYuv<S, 1, 1, false>{y, cb, cr, yp, cp, (int)d.c_step, k, q}, tiles, dtype, stream);
-    if (d.sub_x) return lte_launch_dtype(a, LteYuv<S, 1, 0, false>{y, cb, cr, yp, cp, (int)d.c_step, k, q}, tiles, dtype, stream);
-    return lte_launch_dtype(a, LteYuv<S, 0, 0, false>{y, cb, cr, yp, cp, (int)d.c_step, k, q}, tiles, dtype, stream);
-}
-
 }  // namespace
 
 extern "C" int hat_lte_query(const float* coef, const float* freq, int32_t ldc, int32_t ldf, const float* inp, int32_t H, int32_t W,
@@ -530,7 +502,8 @@ extern "C" int hat_lte_query_yuv(const float* coef, const float* freq, int32_t l
         if (overlaps_inp(dst->cb, dst->c_pitch * (ch - 1) + crow, inp, H, W) || overlaps_inp(dst->cr, dst->c_pitch * (ch - 1) + crow, inp, H, W))
             return HAT_EINVAL;
     }
-    const HatCsc k = load_csc(from_rgb12);
-    if (dst->depth == 8) return lte_launch_yuv<uint8_t>(a, *dst, k, HatSample<uint8_t>{}, tiles, dtype, stream);
-    return lte_launch_yuv<uint16_t>(a, *dst, k, deep_sample(dst->depth, dst->msb), tiles, dtype, stream);
+    return yuv_dispatch(*dst, [&](auto L, auto q) {
+        using S = typename decltype(L)::sample_t;
+        return lte_launch_dtype(a, LteYuv<S, L.sx, L.sy, L.grey>{yuv_dst<S>(*dst), load_csc(from_rgb12), q}, tiles, dtype, stream);
+    });
 }

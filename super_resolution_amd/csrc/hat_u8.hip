@@ -2,7 +2,7 @@
 // Contract: include/hat_mi355x.h (hat_u8_to_planes, hat_planes_to_u8); reference: basicsr utils/img_util.py:9-35, :131
 // (float32(u8) / 255, HWC -> CHW, BGR -> RGB), hat/models/hat_model.py:16-26 (reflect-pad bottom / right to a window
 // multiple), :110-112 (crop) and img_util.py:66-91 (tensor2img: clamp, x255, round half to even, CHW -> HWC).
-#include "hat_common.h"
+#include "hat_frame_sink.h"
 
 namespace {
 
@@ -21,29 +21,21 @@ __global__ __launch_bounds__(256) void u8_to_planes_kernel(const uint8_t* __rest
     for (int c = 0; c < 3; ++c) o[c * plane] = hat_u8_unit.v[p[bgr ? 2 - c : c]];
 }
 
-// one thread = four consecutive pixels of an output row = 12 bytes: three dword stores when the row segment is 4-byte
-// aligned and whole, single bytes otherwise (the last segment of a row, odd pitches).  The plane loads of a lane are 16
-// contiguous bytes per plane; a wave covers 1 KB of each plane row.
+// one thread = four consecutive pixels of an output row = 12 bytes, stored by rgb4_store_u8 (hat_frame_sink.h).  The plane loads
+// of a lane are 16 contiguous bytes per plane; a wave covers 1 KB of each plane row.
 __global__ __launch_bounds__(256) void planes_to_u8_kernel(const float* __restrict__ src, int Hs, int Ws, uint8_t* __restrict__ dst,
                                                            long long pitch, long long dbstride, int h_out, int w_out, int bgr) {
     const int x = (blockIdx.x * 256 + threadIdx.x) * 4, y = blockIdx.y, b = blockIdx.z;
     if (x >= w_out) return;
     const size_t plane = (size_t)Hs * Ws;
     const float* s = src + (size_t)b * 3 * plane + (size_t)y * Ws + x;
-    uint8_t* o = dst + (size_t)b * dbstride + (size_t)y * pitch + (size_t)x * 3;
     const int n = min(4, w_out - x);
-    unsigned q[12];
+    float rgb[4][3];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) q[3 * i + c] = i < n ? hat_unit_to_u8(s[(bgr ? 2 - c : c) * plane + i]) : 0u;
-    if (n == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            reinterpret_cast<unsigned*>(o)[k] = q[4 * k] | (q[4 * k + 1] << 8) | (q[4 * k + 2] << 16) | (q[4 * k + 3] << 24);
-    } else {
-        for (int k = 0; k < 3 * n; ++k) o[k] = (uint8_t)q[k];
-    }
+        for (int c = 0; c < 3; ++c) rgb[i][c] = i < n ? s[c * plane + i] : 0.f;
+    rgb4_store_u8(dst + (size_t)b * dbstride + (size_t)y * pitch + (size_t)x * 3, rgb, n, bgr);
 }
 
 }  // namespace

@@ -1,7 +1,6 @@
 // hat_yuv_sample.h — what the kernels that read or write YCbCr samples share beyond hat_common.h's arithmetic: the sample types
 // (bytes, n-bit codes in 16-bit words), byte addressing of a sample, and the host side's matrix and deep-sample arguments.
-// Included by hat_yuv.hip (the frame boundary), hat_lte.hip (the YCbCr sink of hat_lte_query) and hat_esc_sink.hip (the shuffle
-// heads' sinks).  HIP sources only.
+// Included through hat_frame_sink.h, which holds the stores built on these.  HIP sources only.
 #pragma once
 #include <type_traits>
 
@@ -13,6 +12,7 @@ namespace {
 // shift = 16 - n for MSB-aligned words (else 0), maxcode = 2^n - 1, inv = 2^(8 - n), scale = 2^(n - 8).
 template <typename T> struct HatSample;
 template <> struct HatSample<uint8_t> {
+    using sample_t = uint8_t;
     __device__ __forceinline__ void to_rgb(const HatCsc& k, unsigned Y, unsigned Cb, unsigned Cr, float (&rgb)[3]) const { hat_ycc_to_rgb(k, Y, Cb, Cr, rgb); }
     __device__ __forceinline__ unsigned luma(float v) const { return hat_ycc_byte(v); }
     __device__ __forceinline__ unsigned chroma(float top, float bottom, float offset) const { return hat_chroma_byte(top, bottom, offset); }
@@ -20,6 +20,7 @@ template <> struct HatSample<uint8_t> {
     __device__ __forceinline__ float value(unsigned word) const { return (float)word; }   // the sample in byte units (sited kernels)
 };
 template <> struct HatSample<uint16_t> {
+    using sample_t = uint16_t;
     int shift;
     unsigned maxcode;
     float inv, scale;
