@@ -40,7 +40,11 @@ enum { HAT_ACT_NONE = 0, HAT_ACT_GELU = 1 /* exact erf, nn.GELU() */, HAT_ACT_LR
 /* conv input modes */
 enum { HAT_X_NHWC_T = 0, HAT_X_NHWC_F32 = 1, HAT_X_NCHW_F32_MEAN = 2 };
 /* conv output modes */
-enum { HAT_O_NHWC_T = 0, HAT_O_NHWC_F32 = 1, HAT_O_PIXSHUF_T = 2, HAT_O_NCHW_F32 = 3 };
+enum { HAT_O_NHWC_T = 0, HAT_O_NHWC_F32 = 1, HAT_O_PIXSHUF_T = 2, HAT_O_NCHW_F32 = 3,
+       HAT_O_FOLD2_NCHW_F32 = 4 /* the folded ending as a conv: ksize 5, Cin 64, x_mode HAT_X_NHWC_T, w / bias packing.pack_upfold's
+                                   variants, out (B,3,2H,2W) fp32 = v*out_scale + mean[colour]; hat_conv hands the launch to
+                                   hat_upfold_to_planes (below) and takes no residual, activation, colsum or LayerNorm with it.
+                                   This is the form a forward plan records the folded ending in. */ };
 
 /*
  * Implicit-GEMM convolution / pointwise linear on channel-last data with a fused epilogue:
@@ -493,6 +497,31 @@ int hat_planes_to_yuv(const float* src, int32_t B, int32_t Hs, int32_t Ws, const
 int hat_conv3x3_to_yuv(const void* x, const void* wpk, const float* bias, const HatYuvSurface* dst, int32_t B, int32_t H, int32_t W, int32_t C,
                        int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, const float* mean4, const float* from_rgb12,
                        int32_t dtype, void* stream);
+
+/*
+ * The folded ending of the network: the last Upsample conv (3x3, 64 -> 256), its PixelShuffle(2) and conv_last (3x3, 64 -> 3) as one
+ * 5x5 conv on x, the (B,H,W,ldx) bf16 input of that Upsample conv; the results are 2H x 2W.  No 64-channel map at output size is
+ * written or read.  wpk / bias: packing.pack_upfold's twelve weight variants, bf16 [12][50][64][8] fragments and fp32 [12][16]
+ * (variant 3 rs + cs: which neighbour rows / columns of a pixel lie outside the image; a shift of the shuffled map that falls
+ * outside is absent as a whole, so every pixel, corners included, is the composition's in exact arithmetic), both 16-byte aligned.
+ * The fp32 value of every entry is (conv + bias) * out_scale + mean of the colour, by one expression:
+ *   hat_upfold_to_planes  (B,3,2H,2W) fp32 planes, what hat_conv3x3_to_planes writes after hat_conv's PixelShuffle stage;
+ *   hat_upfold_to_u8      the bytes hat_planes_to_u8 makes of those planes (top-left h_out x w_out, h_out <= 2H, w_out <= 2W);
+ *   hat_upfold_to_yuv     the samples hat_planes_to_yuv makes of them (centre-sited chroma; any subsampling, depth, grey).
+ * W % 16 == 0, W >= 16, H >= 1, ldx >= 64, ldx % 8 == 0; dtype must be HAT_BF16 (HAT_EUNSUPPORTED otherwise).  Arguments are
+ * checked before anything touches the device; none allocates or synchronises.  hat_conv with out_mode HAT_O_FOLD2_NCHW_F32 is
+ * hat_upfold_to_planes behind a HatConvDesc: the engine launches the planes form that way, so a forward plan records it as a
+ * hat_conv call (the plan's function table is unchanged and plans written before still load), and hat_plan_forward_u8 / _yuv*
+ * replay such a last call as hat_upfold_to_u8 / hat_upfold_to_yuv.
+ */
+int hat_upfold_to_planes(const void* x, const void* wpk, const float* bias, float* out, int32_t B, int32_t H, int32_t W, int32_t ldx,
+                         float out_scale, float mean_r, float mean_g, float mean_b, int32_t dtype, void* stream);
+int hat_upfold_to_u8(const void* x, const void* wpk, const float* bias, uint8_t* dst, int64_t dst_pitch, int64_t dst_bstride, int32_t B,
+                     int32_t H, int32_t W, int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, float mean_r, float mean_g,
+                     float mean_b, int32_t bgr, int32_t dtype, void* stream);
+int hat_upfold_to_yuv(const void* x, const void* wpk, const float* bias, const HatYuvSurface* dst, int32_t B, int32_t H, int32_t W,
+                      int32_t ldx, int32_t h_out, int32_t w_out, float out_scale, float mean_r, float mean_g, float mean_b,
+                      const float* from_rgb12, int32_t dtype, void* stream);
 
 /*
  * Chroma siting.  HatYuvSurface keeps its layout (HAT_ABI_VERSION stays 2): the siting travels beside the surface, as a code

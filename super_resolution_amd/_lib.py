@@ -16,7 +16,7 @@ ABI_VERSION = 2   # == HAT_ABI_VERSION of include/hat_mi355x.h: bump both whenev
 HAT_F32, HAT_BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_LRELU, ACT_LRELU02 = 0, 1, 2, 3   # LRELU: slope 0.01; LRELU02: slope 0.2, hat_conv only
 X_NHWC_T, X_NHWC_F32, X_NCHW_F32_MEAN = 0, 1, 2
-O_NHWC_T, O_NHWC_F32, O_PIXSHUF_T, O_NCHW_F32 = 0, 1, 2, 3
+O_NHWC_T, O_NHWC_F32, O_PIXSHUF_T, O_NCHW_F32, O_FOLD2_NCHW_F32 = 0, 1, 2, 3, 4
 METRICS_Y, METRICS_BGR, METRICS_PSNR, METRICS_SSIM = 1, 2, 4, 8   # flags of hat_u8_metrics
 
 _ERRORS = {-1: "HAT_EINVAL (bad argument)", -2: "HAT_ELDS (tile does not fit in 160 KiB LDS)",
@@ -210,6 +210,11 @@ SIGNATURES = {
                                     C.c_void_p]),
     "hat_conv3x3_to_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HatYuvSurface)] + [C.c_int32] * 7 + [C.c_float, C.c_void_p,
                                                                                                         C.c_void_p, C.c_int32, C.c_void_p]),
+    # the folded network ending (hat_upfold.hip): x, wpk, bias, destination, B, H, W, ldx, ..., out_scale, the RGB mean as three floats
+    "hat_upfold_to_planes": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_float] * 4 + [C.c_int32, C.c_void_p]),
+    "hat_upfold_to_u8": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64] + [C.c_int32] * 6 + [C.c_float] * 4 + [C.c_int32, C.c_int32, C.c_void_p]),
+    "hat_upfold_to_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HatYuvSurface)] + [C.c_int32] * 6 + [C.c_float] * 4
+                          + [C.c_void_p, C.c_int32, C.c_void_p]),
     "hat_plan_forward_yuv": (C.c_int, [C.c_void_p, C.POINTER(HatYuvSurface), C.POINTER(HatYuvSurface), C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     # chroma siting: the surface entries with a siting code (0 centre, 1 left, 2 top-left) beside each surface

@@ -19,6 +19,7 @@
 // hat_conv64r.hip: resident-weight kernel for the 3x3 convs of a 64-channel map (the Upsample convs)
 bool hat_conv64r_can_launch(const HatConvDesc& d);
 int hat_conv64r_launch(const HatConvDesc& d, hipStream_t s);
+int hat_upfold_launch_desc(const HatConvDesc& d, hipStream_t s);   // hat_upfold.hip: out_mode HAT_O_FOLD2_NCHW_F32
 
 #ifndef HAT_CONV_PIPE
 #define HAT_CONV_PIPE 1   // 0: round 2's K loop (operand reads left to the scheduler), for A/B builds
@@ -665,10 +666,11 @@ extern "C" int hat_conv_occupancy(const HatConvDesc* dp, int32_t* wgs_per_cu) {
 extern "C" int hat_conv(const HatConvDesc* dp, void* stream) {
     if (!dp) return HAT_EINVAL;
     const HatConvDesc& d = *dp;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (d.out_mode == HAT_O_FOLD2_NCHW_F32) return hat_upfold_launch_desc(d, s);   // the folded ending: its own kernel and checks
     int rc = conv_validate(d);
     if (rc) return rc;
     TileCfg tc; size_t lds;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (hat_conv64r_can_launch(d)) return hat_conv64r_launch(d, s);
     if (!conv_pick(d, &tc, &lds)) return HAT_ELDS;
     if (d.dtype == HAT_BF16) return dispatch_tile<bf16_t>(d, tc, lds, s);

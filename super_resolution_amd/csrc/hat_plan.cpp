@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stddef.h>
 #include <string.h>
 
 #include <string>
@@ -192,29 +193,50 @@ bool addresses_output(const hat_plan* p, const Call& c) {
     return false;
 }
 
-// The recorded forward ends with hat_conv3x3_to_planes writing three planes to the start of the output buffer and no earlier
-// launch touches that buffer: the fp32 image can be skipped (the earlier launches are then replayed without an output).
-bool ends_in_planes(const hat_plan* p) {
-    if (p->calls.empty()) return false;
+// The recorded forward ends with a launch that writes three planes to the start of the output buffer and no earlier launch
+// touches that buffer: the fp32 image can be skipped (the earlier launches are then replayed without an output).  That launch is
+// hat_conv3x3_to_planes (ENDS_CONV_LAST) or the folded ending, a hat_conv call whose descriptor has out_mode
+// HAT_O_FOLD2_NCHW_F32 (ENDS_FOLDED: hat_upfold_to_planes behind a HatConvDesc).  ENDS_OTHER: neither.
+enum Ending { ENDS_OTHER = 0, ENDS_CONV_LAST, ENDS_FOLDED };
+Ending ending_of(const hat_plan* p) {
+    if (p->calls.empty()) return ENDS_OTHER;
     const Call& c = p->calls.back();
-    if (c.fn != FN_hat_conv3x3_to_planes || c.args.size() != 14 || c.args[3].tag != ARG_PTR || c.args[3].buf >= p->bufs.size()) return false;
-    if (p->bufs[c.args[3].buf].kind != BUF_OUTPUT || c.args[3].off != 0 || c.args[9].i != 3) return false;
+    Ending e = ENDS_OTHER;
+    if (c.fn == FN_hat_conv3x3_to_planes) {
+        if (c.args.size() != 14 || c.args[3].tag != ARG_PTR || c.args[3].buf >= p->bufs.size()) return ENDS_OTHER;
+        if (p->bufs[c.args[3].buf].kind != BUF_OUTPUT || c.args[3].off != 0 || c.args[9].i != 3) return ENDS_OTHER;
+        e = ENDS_CONV_LAST;
+    } else if (c.fn == FN_hat_conv) {
+        if (c.args.size() != 2 || c.args[0].tag != ARG_STRUCT || c.args[0].blob.size() != sizeof(HatConvDesc)) return ENDS_OTHER;
+        HatConvDesc d;
+        memcpy(&d, c.args[0].blob.data(), sizeof(d));
+        if (d.out_mode != HAT_O_FOLD2_NCHW_F32) return ENDS_OTHER;
+        bool out_ok = false;
+        for (const Fix& fx : c.args[0].fix)
+            if (fx.field_off == offsetof(HatConvDesc, out))
+                out_ok = fx.buf != NULL_BUF && fx.buf < p->bufs.size() && p->bufs[fx.buf].kind == BUF_OUTPUT && fx.off == 0;
+        if (!out_ok) return ENDS_OTHER;
+        e = ENDS_FOLDED;
+    } else {
+        return ENDS_OTHER;
+    }
     for (size_t k = 0; k + 1 < p->calls.size(); ++k)
-        if (addresses_output(p, p->calls[k])) return false;
-    return true;
+        if (addresses_output(p, p->calls[k])) return ENDS_OTHER;
+    return e;
 }
 
 // What the frame entries share once their own checks have passed: the device check, the fp32 staging (allocated by the first
-// call), source(stage_in), the replay of all but a final hat_conv3x3_to_planes, and the ending: fused(r), the conv_last
-// epilogue on the recorded arguments r of that last call, or planes(stage_out, Hs, Ws) after a replay of every call.
-// may_fuse = false: the ending has no epilogue form (a co-sited YCbCr destination), so a final hat_conv3x3_to_planes is replayed
+// call), source(stage_in), the replay of all but a final planes launch (ending_of), and the ending: fused(r, ending), that
+// launch's sink form on the recorded arguments r of the last call, or planes(stage_out, Hs, Ws) after a replay of every call.
+// may_fuse = false: the ending has no epilogue form (a co-sited YCbCr destination), so the final planes launch is replayed
 // like every other call, into the output staging image.
 template <typename Source, typename Fused, typename Planes>
 int forward_frames(const hat_plan* p, void* stream, Source source, Fused fused_sink, Planes planes_sink, bool may_fuse = true) {
     const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4];
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != p->device) return HAT_EINVAL;
-    const bool fused = may_fuse && ends_in_planes(p);
+    const Ending ending = may_fuse ? ending_of(p) : ENDS_OTHER;
+    const bool fused = ending != ENDS_OTHER;
     if (!p->stage_in) {
         const hipError_t e = hipMalloc((void**)&p->stage_in, (size_t)B * 3 * H * W * sizeof(float));
         if (e != hipSuccess) { p->stage_in = nullptr; return (int)e; }
@@ -233,7 +255,7 @@ int forward_frames(const hat_plan* p, void* stream, Source source, Fused fused_s
     }
     if (!fused) return planes_sink(p->stage_out, s * H, s * W);
     Resolved r{p, &p->calls.back(), p->stage_in, nullptr, stream, {}};
-    return fused_sink(r);
+    return fused_sink(r, ending);
 }
 
 // a three-channel plan whose (H, W) the (h, w) frame reflect-pads to
@@ -261,7 +283,12 @@ int forward_yuv(const hat_plan* p, const HatYuvSurface* src, const HatYuvSurface
             if (hat_siting_of(src, src_siting) == HAT_SITING_CENTER) return hat_yuv_to_planes(src, in, B, h, w, H, W, to_rgb12, stream);
             return hat_yuv_to_planes_sited(src, src_siting, in, B, h, w, H, W, to_rgb12, stream);
         },
-        [&](Resolved& r) {
+        [&](Resolved& r, Ending ending) {
+            if (ending == ENDS_FOLDED) {
+                const HatConvDesc* d = (const HatConvDesc*)r.P(0);
+                return hat_upfold_to_yuv(d->x, d->w, d->bias, dst, d->B, d->H, d->W, d->ldx, ho, wo, d->out_scale, d->mean[0], d->mean[1], d->mean[2],
+                                         from_rgb12, d->dtype, stream);
+            }
             return hat_conv3x3_to_yuv(r.P(0), r.P(1), (const float*)r.P(2), dst, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10),
                                       (const float*)r.P(11), from_rgb12, r.I(12), stream);
         },
@@ -288,7 +315,12 @@ extern "C" int hat_plan_forward_u8(const hat_plan* p, const uint8_t* src, int64_
     const int bgr = flags & 1, ho = s * h, wo = s * w;
     return forward_frames(
         p, stream, [&](float* in) { return hat_u8_to_planes(src, src_pitch, src_pitch * h, in, B, h, w, H, W, bgr, stream); },
-        [&](Resolved& r) {
+        [&](Resolved& r, Ending ending) {
+            if (ending == ENDS_FOLDED) {
+                const HatConvDesc* d = (const HatConvDesc*)r.P(0);
+                return hat_upfold_to_u8(d->x, d->w, d->bias, dst, dst_pitch, dst_pitch * ho, d->B, d->H, d->W, d->ldx, ho, wo, d->out_scale, d->mean[0],
+                                        d->mean[1], d->mean[2], bgr, d->dtype, stream);
+            }
             return hat_conv3x3_to_u8(r.P(0), r.P(1), (const float*)r.P(2), dst, dst_pitch, dst_pitch * ho, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8),
                                      ho, wo, r.F(10), (const float*)r.P(11), bgr, r.I(12), stream);
         },

@@ -62,7 +62,8 @@ class Options:
       HAT_NO_OCAB_MLP        the OCAB MLP as two hat_linear launches instead of hat_ocab_mlp
       HAT_NO_OCAB_QKV        the OCAB q and kv projections as two hat_linear launches on two streams instead of hat_ocab_qkv
       HAT_NO_BF16_CONV_IN    fp32 rows into the group conv instead of the OCAB MLP's bf16 rows
-      HAT_NO_CONV_LN         the LayerNorm after the group conv as its own launch instead of the conv's epilogue"""
+      HAT_NO_CONV_LN         the LayerNorm after the group conv as its own launch instead of the conv's epilogue
+      HAT_NO_UPFOLD=1        the last Upsample conv and conv_last as their two launches instead of hat_upfold_*"""
     no_n16: bool = False
     no_t16: bool = False
     no_fused_ffn: bool = False
@@ -78,6 +79,7 @@ class Options:
     no_ocab_qkv: bool = False
     no_bf16_conv_in: bool = False
     no_conv_ln: bool = False
+    no_upfold: bool = False
 
     @classmethod
     def from_env(cls, env=None) -> "Options":
@@ -276,6 +278,15 @@ class HATEngine(FrameBoundary, EngineBase):
         self.conv_last_sweep = None   # row-sweep kernel (no LDS) for the 64 -> 3 conv at output resolution
         if ops.conv3x3_to_planes_supported(wl.shape[0], wl.shape[1], 16, self.dtype) and not self.opt.no_cab_sweep:
             self.conv_last_sweep = ops.pack_cab_squeeze(wl, sd["conv_last.bias"], dev) + (wl.shape[0],)
+        # The folded ending (hat_upfold_*): the last PixelShuffle(2) conv and conv_last as one 5x5 conv on that stage's input, where
+        # conv_last's row sweep is packed for three colours (so u8_fused says the same of both endings).  x4: the first stage is
+        # unchanged; x2: the only stage.  x3, fp32 and other widths keep the two launches; _folded adds the per-shape width rule.
+        self.upfold = None
+        if self.ups and self.ups[-1][1] == 2 and self.conv_last_sweep is not None and not self.opt.no_upfold:   # (x1 has no stage)
+            key = f"upsample.{2 * (len(self.ups) - 1)}"
+            wu = sd[key + ".weight"]
+            if ops.upfold_supported(wu.shape[1], wl.shape[0], 2, 16, self.dtype) and wl.shape[1] * 4 == wu.shape[0]:
+                self.upfold = ops.pack_upfold(wu, sd[key + ".bias"], wl, sd["conv_last.bias"], dev)
 
     def _pack_naf(self, sd):
         """cfg["naf"] = {width, blocks}: the stem in front of the network, parameters under "naf." (the rest of sd is HATX's own
@@ -516,10 +527,20 @@ class HATEngine(FrameBoundary, EngineBase):
             w["x_naf"] = z(B, self.cfg["in_chans"], H, W, dtype=f)
         h, wd = H, W
         w["ups"] = []
-        for _, r in self.ups:
+        for i, (_, r) in enumerate(self.ups):
             h, wd = h * r, wd * r
-            w["ups"].append(z(B, h * wd, 64))
+            # (the folded ending writes no shuffled map of its last stage)
+            w["ups"].append(None if i + 1 == len(self.ups) and self._folded(W) else z(B, h * wd, 64))
         return w
+
+    def _folded(self, W: int) -> bool:
+        """Whether the forward of a W-wide input ends in hat_upfold_* (packed, and the last stage's input width is one the kernel
+        takes): the ONE condition of _upsample's plain and sink branches and of the workspace."""
+        if self.upfold is None:
+            return False
+        for _, r in self.ups[:-1]:
+            W *= r
+        return ops.upfold_supported(64, 3, 2, W, self.dtype)
 
     # ------------------------------------------------------------------------------------------
     def _esc_w(self, esc: _ESC, w, B, H, W, nblk, gap=None):
@@ -1003,14 +1024,27 @@ class HATEngine(FrameBoundary, EngineBase):
 
     def _upsample(self, f: _Fwd, y, sink=None):
         """conv + PixelShuffle per stage; conv_last ; / img_range + mean                     :593-605, :856-858
+        Where the network ends folded (_folded) the last stage and conv_last are hat_upfold_*, with the same three ways out.
         Without a sink conv_last writes the fp32 planes y.  With one (then y is sink.out) it converts in its epilogue, sink.fused,
         where the row-sweep kernel runs with three output channels; else it writes fp32 planes of its own as always and
         sink.from_planes converts and crops them."""
         src, h, wd, dt = f.w["fb"], f.H, f.W, f.dt
-        for (pw, rr), dst in zip(self.ups, f.w["ups"]):
+        fold = self._folded(f.W)
+        for (pw, rr), dst in list(zip(self.ups, f.w["ups"]))[:len(self.ups) - int(fold)]:
             ops.conv(pw, src, dst, B=f.B, H=h, W=wd, dtype=dt, ldx=64, ldo=64, out_mode=O_PIXSHUF_T, ps_r=rr)
             src, h, wd = dst, h * rr, wd * rr
         r = float(self.cfg.get("img_range", 1.0))
+        if fold:   # the last stage and conv_last in one launch on the stage's input: the same epilogue choice as below
+            kw = dict(B=f.B, H=h, W=wd, ldx=64, out_scale=1.0 / r, mean=self._mean(), dtype=dt)
+            if sink is not None and sink.fusable:
+                sink.folded(src, self.upfold, **kw)
+                return
+            if sink is not None:
+                y = torch.empty(f.B, 3, 2 * h, 2 * wd, dtype=torch.float32, device=self.dev)
+            ops.upfold_to_planes(src, self.upfold, y, **kw)
+            if sink is not None:
+                sink.from_planes(y)
+            return
         if sink is not None:
             if self.u8_fused and wd % 16 == 0 and sink.fusable:
                 wpk, b8, _ = self.conv_last_sweep

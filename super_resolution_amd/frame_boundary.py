@@ -12,7 +12,7 @@ from . import ops
 class _Sink:
     """Where a byte-frame forward ends instead of in fp32 planes: `out`, the caller's result tensor of the (h_out, w_out) top-left
     pixels, and the ways to fill it — fused(src, wpk, b8, conv_last's geometry ...), conv_last's row sweep with the conversion
-    as its epilogue (no fp32 image exists); shuffled(rows, base, B, H, W, s, ld), the same for a head that ends in a pixel shuffle of
+    as its epilogue (no fp32 image exists); folded(src, pf, the folded ending's geometry ...), the same for hat_upfold_*; shuffled(rows, base, B, H, W, s, ld), the same for a head that ends in a pixel shuffle of
     fp32 rows (hat_shuffle_to_u8 / hat_shuffle_to_yuv; base: the image added, or None); or from_planes(y) of an fp32 image, which
     may be larger than `out`: the sink's size is the crop.  Each bumps its engine counter, `kind`_fused_calls or `kind`_planes_calls.  band_refusal: why a row band, which hands its rows over as fp32, cannot end in this sink."""
     kind = band_refusal = None
@@ -36,6 +36,10 @@ class _U8Sink(_Sink):
 
     def fused(self, src, wpk, b8, **conv):
         ops.conv3x3_to_u8(src, wpk, b8, self.out, h_out=self.size[0], w_out=self.size[1], bgr=self.bgr, **conv)
+        self._count("fused")
+
+    def folded(self, src, pf, **conv):
+        ops.upfold_to_u8(src, pf, self.out, h_out=self.size[0], w_out=self.size[1], bgr=self.bgr, **conv)
         self._count("fused")
 
     def shuffled(self, rows, base, **geo):
@@ -62,6 +66,10 @@ class _YuvSink(_Sink):
 
     def fused(self, src, wpk, b8, **conv):
         ops.conv3x3_to_yuv(src, wpk, b8, *self.views, from_rgb=self.from_rgb, **self.surface, **conv)
+        self._count("fused")
+
+    def folded(self, src, pf, **conv):
+        ops.upfold_to_yuv(src, pf, *self.views, from_rgb=self.from_rgb, **self.surface, **conv)
         self._count("fused")
 
     def shuffled(self, rows, base, **geo):

@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import (ACT_GELU, ACT_LRELU, ACT_LRELU02, ACT_NONE, HAT_BF16, HAT_F32, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T,
+from ._lib import (ACT_GELU, ACT_LRELU, ACT_LRELU02, ACT_NONE, HAT_BF16, HAT_F32, O_FOLD2_NCHW_F32, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T,
                    X_NCHW_F32_MEAN, X_NHWC_F32, X_NHWC_T, HatAggrCabDesc, HatCabFoldDesc, HatConvDesc, HatFfnDesc, HatHabTailDesc, HatMlpDesc, HatNafFoldDesc,
                    HatNafHalfDesc, HatEscConvFfnDesc)
 # host-side weight packing lives in packing.py; ops.pack_* / ops.Packed* stay the names the engine, the tools and the tests use
@@ -21,7 +21,7 @@ from .packing import (ESC_HID_PAD, FP16_SAFE, KC, NAF_WIDTHS, TORCH_DTYPE, Packe
                       LTE_HIDDEN, PackedLte, pack_lte,
                       UNI_UPSAMPLERS, PackedEscRealMSkip, conv_nearest_fold, pack_conv_nearest, pack_escrealm_skip, pack_pixshuf_conv, pixshuf_perm,
                       choose_nt_linear, naf_ffn_fold, naf_frags, pack_naf_block,
-                      ffn_fp16_range_bound, pack_cab_squeeze, pack_cab_w2f, pack_conv_weight, pack_ffn, pack_ffn2, pack_ffn3,
+                      ffn_fp16_range_bound, pack_upfold, pack_cab_squeeze, pack_cab_w2f, pack_conv_weight, pack_ffn, pack_ffn2, pack_ffn3,
                       pack_linear_weight, pack_ocab_mlp, pack_ocab_qkv, pack_pointwise)
 
 DTYPE_CODE = {"f32": HAT_F32, "fp32": HAT_F32, "float32": HAT_F32, "bf16": HAT_BF16, "bfloat16": HAT_BF16}
@@ -628,6 +628,50 @@ def conv3x3_to_u8(x, wpk, bias8, out, *, B: int, H: int, W: int, C_: int, ldx: i
                               out_scale, m4, int(bgr), dtype, _stream()), "hat_conv3x3_to_u8"), tag=f"k3 {C_}->3 {H}x{W} row sweep u8")
 
 
+def upfold_supported(cin: int, nout: int, r: int, W: int, dtype: int) -> bool:
+    """The folded ending (hat_upfold_*): a 64-channel PixelShuffle(2) stage into a 64 -> 3 conv_last, bf16, W (of the stage's
+    input) a multiple of 16."""
+    return dtype == HAT_BF16 and cin == 64 and nout == 3 and r == 2 and W >= 16 and W % 16 == 0
+
+
+def _upfold_flops(B, H, W):
+    return 2.0 * B * H * W * 25 * 64 * 12
+
+
+def _upfold_bytes(B, H, W, out_bytes):
+    return float(B * H * W * 64 * 2 + out_bytes)
+
+
+def upfold_to_planes(x, pf, out, *, B: int, H: int, W: int, ldx: int, out_scale: float, mean, dtype: int):
+    """The last PixelShuffle(2) conv and conv_last as one 5x5 conv: x (B,H,W,ldx) bf16 -> (conv_last + bias) * out_scale + mean as
+    (B, 3, 2H, 2W) fp32 planes.  pf: packing.PackedUpfold."""
+    lib = _lib.load()
+    if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (B, 3, 2 * H, 2 * W):
+        raise RuntimeError(f"upfold_to_planes needs a contiguous (B,3,2H,2W) fp32 device destination, got {tuple(out.shape)} {out.dtype}")
+    # through hat_conv's out_mode O_FOLD2_NCHW_F32 (hat_upfold_to_planes behind a HatConvDesc): the form a forward plan records
+    d = HatConvDesc()
+    d.x, d.w, d.bias, d.out = _ptr(x), _ptr(pf.w), _ptr(pf.bias), _ptr(out)
+    d.B, d.H, d.W, d.Cin, d.ldx, d.x_mode = B, H, W, 64, ldx, X_NHWC_T
+    d.ksize, d.Kpad, d.nt, d.n_slices, d.n_store = 5, 25 * 64, 1, 1, 12
+    d.out_mode, d.act, d.in_scale, d.out_scale, d.dtype = O_FOLD2_NCHW_F32, ACT_NONE, 1.0, out_scale, dtype
+    for i in range(3):
+        d.mean[i] = float(mean[i])
+    _timed("upfold_kernel<planes>", _upfold_flops(B, H, W), lambda: _lib.check(lib.hat_conv(C.byref(d), _stream()), "hat_conv (folded ending)"),
+        tag=f"k5 64->2x2x3 {H}x{W} folded planes", nbytes=_upfold_bytes(B, H, W, B * 12 * H * W * 4))
+
+
+def upfold_to_u8(x, pf, out, *, B: int, H: int, W: int, ldx: int, h_out: int, w_out: int, out_scale: float, mean, bgr: bool, dtype: int):
+    """The folded ending with the 8-bit conversion as its epilogue: out (B, h_out, w_out, 3) uint8 = planes_to_u8 of what
+    upfold_to_planes writes, cropped to the top-left h_out x w_out pixels; no fp32 image is written."""
+    lib = _lib.load()
+    if out.dtype != torch.uint8 or not out.is_cuda or tuple(out.shape) != (B, h_out, w_out, 3) or out.stride(-1) != 1 or out.stride(-2) != 3:
+        raise RuntimeError("upfold_to_u8 needs a (B,h_out,w_out,3) uint8 device destination with interleaved pixels")
+    _timed("upfold_kernel<u8>", _upfold_flops(B, H, W), lambda: _lib.check(
+        lib.hat_upfold_to_u8(_ptr(x), _ptr(pf.w), _ptr(pf.bias), out.data_ptr(), out.stride(1), out.stride(0), B, H, W, ldx, h_out, w_out,
+                             out_scale, float(mean[0]), float(mean[1]), float(mean[2]), int(bgr), dtype, _stream()), "hat_upfold_to_u8"),
+        tag=f"k5 64->2x2x3 {H}x{W} folded u8", nbytes=_upfold_bytes(B, H, W, B * h_out * w_out * 3))
+
+
 def u8_to_planes(src, dst, *, bgr: bool = False):
     """src (B, h, w, 3) uint8 (rows may be pitched: stride(-3) >= 3 w) -> dst (B, 3, Hp, Wp) fp32 = float(src) / 255 as
     planes, the rows and columns past (h, w) filled by reflection (hat_u8_to_planes)."""
@@ -1111,6 +1155,21 @@ def conv3x3_to_yuv(x, wpk, bias8, y, cb, cr, *, sub, B: int, H: int, W: int, C_:
     _timed(f"cab_squeeze_kernel<2, {name}>", 2.0 * B * H * W * 9 * C_ * 3, lambda: _lib.check(
         lib.hat_conv3x3_to_yuv(_ptr(x), _ptr(wpk), _ptr(bias8), C.byref(surf), B, H, W, C_, ldx, y.shape[1], y.shape[2], out_scale, m4, m, dtype,
                                _stream()), "hat_conv3x3_to_yuv"), tag=f"k3 {C_}->3 {H}x{W} row sweep {name}")
+
+
+def upfold_to_yuv(x, pf, y, cb, cr, *, sub, B: int, H: int, W: int, ldx: int, out_scale: float, mean, from_rgb, dtype: int, depth: int = 8,
+                  msb=False):
+    """The folded ending with the YCbCr conversion of any subsampling (or grey) as its epilogue: planes_to_yuv of what
+    upfold_to_planes writes, cropped to the top-left h x w pixels of the views; no fp32 image is written (hat_upfold_to_yuv)."""
+    lib = _lib.load()
+    surf = yuv_surface(y, cb, cr, sub=sub, depth=depth, msb=msb, what="upfold_to_yuv")
+    if y.shape[0] != B:
+        raise RuntimeError(f"upfold_to_yuv: destination batch {y.shape[0]} != {B}")
+    m, name = _f12(from_rgb), _sub_name(sub, depth)
+    _timed(f"upfold_kernel<{name}>", _upfold_flops(B, H, W), lambda: _lib.check(
+        lib.hat_upfold_to_yuv(_ptr(x), _ptr(pf.w), _ptr(pf.bias), C.byref(surf), B, H, W, ldx, y.shape[1], y.shape[2], out_scale, float(mean[0]),
+                              float(mean[1]), float(mean[2]), m, dtype, _stream()), "hat_upfold_to_yuv"),
+        tag=f"k5 64->2x2x3 {H}x{W} folded {name}", nbytes=_upfold_bytes(B, H, W, B * y.shape[1] * y.shape[2] * 2))
 
 
 def u8_metrics_flags(*, y_channel: bool, bgr: bool, psnr: bool, ssim: bool) -> int:

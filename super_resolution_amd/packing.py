@@ -697,3 +697,92 @@ def pack_lte(sd, dtype: int, device) -> PackedLte:
     p.w4 = _f32(sd["imnet.layers.6.weight"]).contiguous().to(device)
     p.b4 = _f32(sd["imnet.layers.6.bias"]).contiguous().to(device)
     return p
+
+
+# ------------------------------------------------------------------------------------------------
+# hat_upfold_* (the last PixelShuffle(2) conv and conv_last as one 5x5 conv at the shuffle's input size)
+# ------------------------------------------------------------------------------------------------
+class PackedUpfold:
+    """`w` T fragments [12 variants][50][64][8], `bias` fp32 [12][16]; variant 3 rs + cs (upfold_variant), fragment 2 t + ks of tap
+    t = 5 (ty + 2) + (tx + 2), A row 4 (2 a + b) + m (m < 3; row 4 (2 a + b) + 3 is zero): lane group g of the MFMA result holds
+    R, G, B of output pixel 2 p + (g >> 1, g & 1)."""
+    __slots__ = ("w", "bias")
+
+
+def upfold_pieces(wu, bu, wl, bl):
+    """Conv2d(C, 4 K, 3, 1, 1) -> PixelShuffle(2) -> Conv2d(K, M, 3, 1, 1) as per-shift pieces, in fp64.  Tap d of the last conv
+    at output pixel 2 p + (a, b) reads shuffled pixel 2 (p + delta) + (a', b'), delta = floor((a + d) / 2), a' = (a + d) mod 2:
+      y[m, 2 p + (a, b)] = bl[m] + sum_delta [p + delta inside] (B[delta][m, a, b] + sum_e sum_c G[delta][m, a, b, c, e] x[c, p + delta + e])
+    -> G (3, 3, M, 2, 2, C, 3, 3) indexed [delta_y + 1, delta_x + 1, m, a, b, c, e_y + 1, e_x + 1], B (3, 3, M, 2, 2), bl (M,)."""
+    wu, bu, wl, bl = (t.detach().to(torch.float64).cpu() for t in (wu, bu, wl, bl))
+    m, k = wl.shape[:2]
+    if wu.shape[0] != 4 * k or tuple(wu.shape[2:]) != (3, 3) or tuple(wl.shape[2:]) != (3, 3):
+        raise ValueError(f"upfold: a {tuple(wu.shape)} conv does not feed PixelShuffle(2) and a {tuple(wl.shape)} conv")
+    c = wu.shape[1]
+    wu4, bu4 = wu.reshape(k, 4, c, 3, 3), bu.reshape(k, 4)
+    G, Bd = torch.zeros(3, 3, m, 2, 2, c, 3, 3, dtype=torch.float64), torch.zeros(3, 3, m, 2, 2, dtype=torch.float64)
+    for a in range(2):
+        for b in range(2):
+            for dy in (-1, 0, 1):
+                for dx in (-1, 0, 1):
+                    iy, ix, sub = (a + dy) // 2 + 1, (b + dx) // 2 + 1, 2 * ((a + dy) % 2) + (b + dx) % 2
+                    G[iy, ix, :, a, b] += torch.einsum("mk,kcef->mcef", wl[:, :, dy + 1, dx + 1], wu4[:, sub])
+                    Bd[iy, ix, :, a, b] += wl[:, :, dy + 1, dx + 1] @ bu4[:, sub]
+    return G, Bd, bl
+
+
+def upfold_variant(G, Bd, bl, rs: int, cs: int):
+    """The merged 5x5 weights F (M, 2, 2, C, 5, 5) = sum over the shifts delta present of G[delta] placed at delta + e, and the bias
+    (M, 2, 2) = bl + their B[delta], for a pixel p whose neighbour rows / columns are partly outside the image: rs bit 0: row
+    p_y - 1 is outside (the first row), bit 1: row p_y + 1 is (the last row); cs likewise for columns.  (0, 0) is the interior."""
+    m, c = G.shape[2], G.shape[5]
+    F = torch.zeros(m, 2, 2, c, 5, 5, dtype=torch.float64)
+    bias = bl[:, None, None].expand(m, 2, 2).clone()
+    for iy in range(3):
+        for ix in range(3):
+            if (iy == 0 and rs & 1) or (iy == 2 and rs & 2) or (ix == 0 and cs & 1) or (ix == 2 and cs & 2):
+                continue
+            F[..., iy:iy + 3, ix:ix + 3] += G[iy, ix]
+            bias += Bd[iy, ix]
+    return F, bias
+
+
+def upfold_apply(x, wu, bu, wl, bl):
+    """The fold applied on the host in fp64, every pixel by its variant: x (B, C, H, W) -> (B, M, 2 H, 2 W).  What hat_upfold_*
+    computes, for the tests."""
+    x = x.detach().to(torch.float64).cpu()
+    G, Bd, b0 = upfold_pieces(wu, bu, wl, bl)
+    Bn, _, H, W = x.shape
+    m = G.shape[2]
+    py, px = torch.arange(H)[:, None], torch.arange(W)[None, :]
+    rs, cs = (py == 0) * 1 + (py == H - 1) * 2, (px == 0) * 1 + (px == W - 1) * 2
+    out = torch.zeros(Bn, m * 4, H, W, dtype=torch.float64)
+    for r in range(4):
+        for s in range(4):
+            mask = (rs == r) & (cs == s)
+            if mask.any():
+                F, bias = upfold_variant(G, Bd, b0, r, s)
+                y = torch.nn.functional.conv2d(x, F.reshape(m * 4, -1, 5, 5), bias.reshape(-1), padding=2)
+                out = torch.where(mask, y, out)
+    return torch.nn.functional.pixel_shuffle(out, 2)
+
+
+def pack_upfold(wu, bu, wl, bl, device) -> PackedUpfold:
+    """The twelve variants (rs 0..3 x cs 0..2; hat_upfold_* takes W >= 16, so no column is first and last) as bf16 fragments."""
+    G, Bd, b0 = upfold_pieces(wu, bu, wl, bl)
+    if G.shape[2] != 3 or G.shape[5] != 64:
+        raise ValueError(f"hat_upfold is built for 64 -> 3 channels, got {G.shape[5]} -> {G.shape[2]}")
+    ws, bs = [], []
+    for rs in range(4):
+        for cs in range(3):
+            F, bias = upfold_variant(G, Bd, b0, rs, cs)
+            A = torch.zeros(2, 2, 4, 25, 64, dtype=torch.float64)          # [a][b][m (3: zero)][tap][c]
+            A[:, :, :3] = F.permute(1, 2, 0, 4, 5, 3).reshape(2, 2, 3, 25, 64)
+            ws.append(frags(A.reshape(16, 25 * 64).to(torch.float32))[0])
+            bb = torch.zeros(2, 2, 4, dtype=torch.float64)
+            bb[:, :, :3] = bias.permute(1, 2, 0)
+            bs.append(bb.reshape(16))
+    p = PackedUpfold()
+    p.w = torch.stack(ws).to(torch.bfloat16).contiguous().to(device)
+    p.bias = torch.stack(bs).to(torch.float32).contiguous().to(device)
+    return p
