@@ -63,11 +63,14 @@ def to_dev(x_bhwc: torch.Tensor, ld: int, tdt, dev):
     return out
 
 
-def fill_rows(x_bhwc: torch.Tensor, ld: int, tdt, dev, fill):
-    """(B,H,W,C) float -> device (B, H*W, ld) of dtype tdt whose pad channels hold `fill` (nothing may read them)."""
+def fill_rows(x_bhwc: torch.Tensor, ld: int, tdt, dev, fill, c_zero=None):
+    """(B,H,W,C) float -> device (B, H*W, ld) of dtype tdt whose pad channels hold `fill` (nothing may read them).  c_zero: channels
+    [C, c_zero) are zero instead (hat_conv's documented zero pad up to Cin_p, which it may read under zero weights)."""
     b, h, w, c = x_bhwc.shape
     out = torch.full((b, h * w, ld), fill, dtype=tdt, device=dev)
     out[:, :, :c] = x_bhwc.reshape(b, h * w, c).to(dev).to(tdt)
+    if c_zero is not None and c_zero > c:
+        out[:, :, c:c_zero] = 0
     return out
 
 
