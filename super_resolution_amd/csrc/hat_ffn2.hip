@@ -18,14 +18,11 @@
 // Ms rows are exactly 144 bf16 = 18 sixteen-byte slots (18 = 2 mod 4: conflict-free ds_read_b128 operand reads,
 // hat_common.h lds_row_elems) — the fc1 bias left the K dimension, so the image is 51.8 KB instead of 57.6 KB and the
 // depthwise weights (1.3 KB per chunk) fit beside it.
-#include "hat_common.h"
+// The fp16 helpers, the depthwise accumulators' start, the SiLU gate and the host-side argument check and launch are shared
+// with the third generation (hat_tail3.hip, hat_tail3l.hip): hat_gated_ffn.h.
+#include "hat_gated_ffn.h"
 
 namespace {
-
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 
 constexpr int F2_C = 144, F2_NT = 9, F2_KS = 5, F2_WAVES = 4, F2_ROWS = 8, F2_HW = 18;
 constexpr int F2_NPH = (F2_ROWS + 2) * F2_HW;      // 180 haloed pixels
@@ -48,12 +45,6 @@ constexpr int F2_US_OFF = F2_WD_OFF + F2_WD_BYTES;  // 53120
 constexpr int F2_US_ROWB = 160;
 constexpr int F2_LDS = F2_US_OFF + F2_NPH * F2_US_ROWB;   // 81920
 
-typedef __attribute__((address_space(3))) char lds_char;
-
-__device__ __forceinline__ u32x4 lds_read16(unsigned addr) { return *(__attribute__((address_space(3))) const u32x4*)(uintptr_t)addr; }
-__device__ __forceinline__ h2 as_h2(unsigned v) { return __builtin_bit_cast(h2, v); }
-__device__ __forceinline__ unsigned as_u(h2 v) { return __builtin_bit_cast(unsigned, v); }
-
 // Inputs of the fused aggregation stage (hat_hab_tail): stage 0 then computes tB = t + W_aggr . [y16 | n[16:]] +
 // wf . im2col3x3(c1) + bias_b itself (what hat_aggr_cab writes to HBM as fp32 and hat_ffn reads back with a halo) and
 // t_in is the residual stream BEFORE the aggregation.
@@ -66,7 +57,6 @@ struct F2Aggr {
     const float* bias_b;   // per-sample bias [B][144]
     int ldn;
 };
-__device__ __attribute__((aligned(16))) unsigned hat_ffn2_zero_page[4] = {0, 0, 0, 0};
 
 // DBG: timing-ablation mask for tools/ubench_ffn2.hip (the library instantiates 0):
 //   1 skip LN stage, 2 skip fc1 MFMAs, 4 skip the depthwise FMAs, 8 skip gate math, 16 skip fc2 MFMAs, 32 skip weight loads,
@@ -147,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void ffn2_kernel(const HatFfnDesc d, const 
                 const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
                 const int yy = yc + dy, xx = xc + dx;
                 const bool inb = tap < 9 && yy >= 0 && yy < H && xx >= 0 && xx < W;
-                bfr[t][5 + kc] = MT<bf16_t>::load(inb ? cb + ((size_t)yy * W + xx) * 8 : reinterpret_cast<const bf16_t*>(hat_ffn2_zero_page));
+                bfr[t][5 + kc] = MT<bf16_t>::load(inb ? cb + ((size_t)yy * W + xx) * 8 : reinterpret_cast<const bf16_t*>(hat_gffn_zero_page));
             }
         }
         // The accumulators START as residual + bias (t and the per-sample bias, loaded straight into them in the MFMA D
@@ -171,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void ffn2_kernel(const HatFfnDesc d, const 
         for (int nt = 0; nt < NT; ++nt) {
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks) {
-                const bf8 a = __builtin_bit_cast(bf8, lds_read16(lds0 + (unsigned)((nt * 8 + ks) * 1024) + (unsigned)lane * 16u));
+                const bf8 a = __builtin_bit_cast(bf8, lds_rd16(lds0 + (unsigned)((nt * 8 + ks) * 1024) + (unsigned)lane * 16u));
                 acc2[nt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr[0][ks], acc2[nt][0], 0, 0, 0);
                 acc2[nt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr[1][ks], acc2[nt][1], 0, 0, 0);
                 accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr[2][ks], accx[nt], 0, 0, 0);
@@ -314,7 +304,7 @@ __global__ __launch_bounds__(256, 2) void ffn2_kernel(const HatFfnDesc d, const 
     auto load_b = [&](int i, bf8 (&bf)[KS]) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
-            bf[ks] = __builtin_bit_cast(bf8, lds_read16(mbase + (unsigned)(i * 32 * F2_MS_ROWB + ks * 64)));
+            bf[ks] = __builtin_bit_cast(bf8, lds_rd16(mbase + (unsigned)(i * 32 * F2_MS_ROWB + ks * 64)));
     };
     // this lane's Us store position of its first pixel tile (tile i is 32 rows further): ONE 16-byte store holds the
     // lane's 4 + 4 results of n-tiles 2*nt2 and 2*nt2+1, so fc1's output row (tile ii, 4g + r) is hidden unit
@@ -406,14 +396,8 @@ __global__ __launch_bounds__(256, 2) void ffn2_kernel(const HatFfnDesc d, const 
                 a2[nt] = (DBG & 32) ? (h8)(_Float16)0 : *reinterpret_cast<const h8*>(w2f + (((size_t)chunk * NT + nt) * 64 + lane) * 8);
         };
         if constexpr (DBG & 4) load_a2();
-        h2 da[2][4], dg[2][4];   // [tile row][dword]: a-units / gate-units 8g..8g+7, two per dword
-        {
-            const u32x4 ba = lds_read16(wdad + 9 * 32), bg = lds_read16(wdad + 9 * 32 + 16);   // "tap 9" = depthwise bias
-#pragma unroll
-            for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { da[pt][k] = as_h2(ba[k]); dg[pt][k] = as_h2(bg[k]); }
-        }
+        h2 da[2][4], dg[2][4];
+        dw_init(wdad, da, dg);
         if constexpr (!(DBG & 4)) {
             // 12 positions (haloed row hr = 0..3, column offset dx = 0..2), software-pipelined by hand one position ahead:
             // left to itself the scheduler hoists all 44 LDS reads (176 registers) above the first FMA and spills.
@@ -422,13 +406,13 @@ __global__ __launch_bounds__(256, 2) void ffn2_kernel(const HatFfnDesc d, const 
             constexpr int PD = 3;   // U operands in flight: a whole haloed row ahead of the FMAs that consume them
             u32x4 wa[2][3], wg[2][3], ua[PD + 1], ug[PD + 1];
             auto rd_w = [&](int tr, int dx) {
-                wa[tr & 1][dx] = lds_read16(wdad + (unsigned)((tr * 3 + dx) * 32));
-                wg[tr & 1][dx] = lds_read16(wdad + (unsigned)((tr * 3 + dx) * 32 + 16));
+                wa[tr & 1][dx] = lds_rd16(wdad + (unsigned)((tr * 3 + dx) * 32));
+                wg[tr & 1][dx] = lds_rd16(wdad + (unsigned)((tr * 3 + dx) * 32 + 16));
             };
             auto rd_u = [&](int pos) {
                 const int hr = pos / 3, dx = pos - 3 * hr;
-                ua[pos % (PD + 1)] = lds_read16(ubase + (unsigned)((hr * HALO_W + dx) * F2_US_ROWB));
-                ug[pos % (PD + 1)] = lds_read16(ubase + (unsigned)((hr * HALO_W + dx) * F2_US_ROWB + 64));
+                ua[pos % (PD + 1)] = lds_rd16(ubase + (unsigned)((hr * HALO_W + dx) * F2_US_ROWB));
+                ug[pos % (PD + 1)] = lds_rd16(ubase + (unsigned)((hr * HALO_W + dx) * F2_US_ROWB + 64));
             };
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx) rd_w(0, dx);
@@ -469,21 +453,10 @@ __global__ __launch_bounds__(256, 2) void ffn2_kernel(const HatFfnDesc d, const 
         load_a1(min(chunk + 1, d.chunks - 1));
 #pragma unroll
         for (int pt = 0; pt < 2; ++pt) {
-            u32x4 gu;
+            u32x4 au;   // (DBG & 8: the a half alone)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                h2 v = da[pt][k];
-                if constexpr (!(DBG & 8)) {
-                    const h2 x = dg[pt][k];
-                    const h2 t = x * (h2){(_Float16)-1.4426950408889634f, (_Float16)-1.4426950408889634f};
-                    h2 e = {(_Float16)__builtin_exp2f16(t[0]), (_Float16)__builtin_exp2f16(t[1])};
-                    e = e + (h2){(_Float16)1.0f, (_Float16)1.0f};
-                    const h2 r = {(_Float16)__builtin_amdgcn_rcph(e[0]), (_Float16)__builtin_amdgcn_rcph(e[1])};
-                    v = v * (x * r);                  // a * g * sigmoid(g)
-                }
-                gu[k] = as_u(v);
-            }
-            const h8 gf = __builtin_bit_cast(h8, gu);
+            for (int k = 0; k < 4; ++k) au[k] = as_u(da[pt][k]);
+            const h8 gf = (DBG & 8) ? __builtin_bit_cast(h8, au) : gate_silu(da[pt], dg[pt]);
             if constexpr (!(DBG & 16)) {
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) acc2[nt][pt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[nt], gf, acc2[nt][pt], 0, 0, 0);
@@ -578,23 +551,14 @@ int ffn2_check(const HatFfnDesc& d) {
     if (!d.t_in || !d.t_out || d.t_in == d.t_out || !d.ln_g || !d.ln_b || !d.w1f || !d.b1 || !d.dww || !d.w2f || !d.b2) return HAT_EINVAL;
     if (d.B < 1 || d.H < 1 || d.W < 1 || d.chunks < 1 || d.m_in) return HAT_EINVAL;
     if (d.C != F2_C || d.dtype != HAT_BF16) return HAT_EUNSUPPORTED;
-    if (d.ln1_g && (!d.ln1_b || !d.n_out || d.ldn < d.C || d.ldn % 4 || d.gap_c < 0 || d.gap_c > 16 || d.gap_c % 4)) return HAT_EINVAL;
-    return 0;
-}
-template <bool AGGR> int ffn2_launch(const HatFfnDesc& d, const F2Aggr& ag, void* stream) {
-    auto kern = ffn2_kernel<0, AGGR>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, F2_LDS);
-    if (e != hipSuccess) return (int)e;
-    dim3 grid((d.W + 15) / 16, (d.H + F2_ROWS - 1) / F2_ROWS, d.B);
-    HAT_LAUNCH(kern, grid, dim3(256), F2_LDS, reinterpret_cast<hipStream_t>(stream), d, ag);
-    return hat_check_launch();
+    return hat_ln1_args_ok(d) ? 0 : HAT_EINVAL;
 }
 }  // namespace
 
 extern "C" int hat_ffn2(const HatFfnDesc* dp, void* stream) {
     if (!dp) return HAT_EINVAL;
     if (int rc = ffn2_check(*dp)) return rc;
-    return ffn2_launch<false>(*dp, F2Aggr{}, stream);
+    return hat_tail_launch(ffn2_kernel<0, false>, F2_LDS, F2_ROWS, *dp, F2Aggr{}, stream);
 }
 
 extern "C" int hat_hab_tail(const HatHabTailDesc* dp, void* stream) {
@@ -604,6 +568,6 @@ extern "C" int hat_hab_tail(const HatHabTailDesc* dp, void* stream) {
     if (!h.n || !h.y16 || !h.c1 || !h.w_aggr || !h.wf || !h.bias_b || h.ldn_in < F2_C || h.ldn_in % 8) return HAT_EINVAL;
     const F2Aggr ag{reinterpret_cast<const bf16_t*>(h.n), reinterpret_cast<const bf16_t*>(h.y16), reinterpret_cast<const bf16_t*>(h.c1),
                     reinterpret_cast<const char*>(h.w_aggr), reinterpret_cast<const char*>(h.wf), h.bias_b, h.ldn_in};
-    return ffn2_launch<true>(h.ffn, ag, stream);
+    return hat_tail_launch(ffn2_kernel<0, true>, F2_LDS, F2_ROWS, h.ffn, ag, stream);
 }
 #endif

@@ -21,8 +21,10 @@
 //     depthwise conv's zero padding needs (hat_arch.py:112-114 pads u AFTER the bias) — without the 32 selects per chunk
 //     that forced U to zero, and without a bias operand.
 // Everything downstream of U (packed-fp16 depthwise conv, gate, fp16 fc2 MFMA, epilogue with the next LayerNorm, its GAP
-// partials and compact 16-channel copy) is the second generation's.
-#include "hat_common.h"
+// partials and compact 16-channel copy) is the second generation's.  hat_gated_ffn.h holds what the three tail kernels
+// (this one, hat_ffn2.hip, hat_tail3l.hip) share of it: the fp16 / LDS helpers, dw_init, gate_fc2 and the host-side argument
+// check and launch.  The depthwise loop, the epilogue and the GAP reduction stay here as text: DESIGN.md 4.0d.
+#include "hat_gated_ffn.h"
 
 // compile-time experiment switches (tools/ubench_tail3.hip builds the variants; the library builds the defaults)
 #ifndef T3_ISSUE_ALL
@@ -46,10 +48,6 @@
 
 namespace {
 
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-
 constexpr int T3_C = 144, T3_NT = 9, T3_KS = 5, T3_WAVES = 4, T3_ROWS = 8, T3_HW = 18;
 constexpr int T3_NPH = (T3_ROWS + 2) * T3_HW;        // 180 haloed pixels
 // LDS map of the chunk loop (81 024 B, two workgroups per CU):
@@ -69,17 +67,6 @@ constexpr int T3_WD_REC = 2048;                       // bytes per chunk of the 
 constexpr int T3_LDS = T3_WD_OFF + T3_WD_REC;         // 81024
 constexpr int T3_B2_OFF = 73728;                      // stage 0 only: 1 KiB record of the fc2 bias behind the 72 KiB of A operands
 
-typedef __attribute__((address_space(3))) char lds_char;
-
-__device__ __forceinline__ u32x4 lds_rd16(unsigned addr) { return *(__attribute__((address_space(3))) const u32x4*)(uintptr_t)addr; }
-__device__ __forceinline__ h2 as_h2(unsigned v) { return __builtin_bit_cast(h2, v); }
-__device__ __forceinline__ unsigned as_u(h2 v) { return __builtin_bit_cast(unsigned, v); }
-// one LDS-DMA piece: 64 lanes x 16 B from src (wave-uniform) + lane_off -> 1 KiB at dst (wave-uniform)
-__device__ __forceinline__ void dma1k(const char* src, unsigned lane_off, char* dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + lane_off),
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-
 struct T3Aggr {
     const bf16_t* n;       // (B,H,W,ldn) LayerNorm1 output
     const bf16_t* y16;     // (B,H,W,16)  ESC large-kernel conv output: replaces channels [0, 16) of n
@@ -89,7 +76,6 @@ struct T3Aggr {
     const float* bias_b;   // per-sample bias [B][144]
     int ldn;
 };
-__device__ __attribute__((aligned(16))) unsigned hat_tail3_zero_page[4] = {0, 0, 0, 0};
 __device__ __attribute__((aligned(16))) unsigned hat_tail3_ones_page[4] = {0x3F803F80u, 0, 0, 0};   // bf16 {1, 1, 0 ...}
 
 // DBG 64: per-phase s_memtime totals of every wave -> gap_out[wg][wave][12] (tools/ubench_tail3.hip; the library builds 0)
@@ -205,7 +191,7 @@ __global__ __launch_bounds__(256, 2) void tail3_kernel(const HatFfnDesc d, const
                 const int yy = yc + dy, xx = xc + dx;
                 const bool inb = tap < 9 && yy >= 0 && yy < H && xx >= 0 && xx < W;
                 // "tap 9" (k = 72..79): 1.0 in the two slots that hold the bias head and remainder
-                const bf16_t* cst = reinterpret_cast<const bf16_t*>(tap == 9 ? hat_tail3_ones_page : hat_tail3_zero_page);
+                const bf16_t* cst = reinterpret_cast<const bf16_t*>(tap == 9 ? hat_tail3_ones_page : hat_gffn_zero_page);
                 bfr[t][5 + kc] = MT<bf16_t>::load(inb ? cb + ((size_t)yy * W + xx) * 8 : cst);
             }
 #pragma unroll
@@ -394,14 +380,8 @@ __global__ __launch_bounds__(256, 2) void tail3_kernel(const HatFfnDesc d, const
         if constexpr ((T3_ABL & 32) != 0) { dma_rest(chunk); dma_fc1(min(chunk + 1, d.chunks - 1), (chunk + 1) & 1); }
 
         // ====================== phase B: depthwise 3x3 in packed fp16 (this wave's two rows) ======================
-        h2 da[2][4], dg[2][4];   // [tile row][dword]: a-units / gate-units 8g..8g+7, two per dword
-        {
-            const u32x4 ba = lds_rd16(wdad + 9 * 32), bg = lds_rd16(wdad + 9 * 32 + 16);   // "tap 9" = depthwise bias
-#pragma unroll
-            for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { da[pt][k] = as_h2(ba[k]); dg[pt][k] = as_h2(bg[k]); }
-        }
+        h2 da[2][4], dg[2][4];
+        dw_init(wdad, da, dg);
         {
             // 12 positions (haloed row hr = 0..3, column offset dx = 0..2), software-pipelined by hand one row ahead: left to
             // itself the scheduler hoists all 44 LDS reads (176 registers) above the first FMA and spills.  Position (hr, dx)
@@ -450,25 +430,7 @@ __global__ __launch_bounds__(256, 2) void tail3_kernel(const HatFfnDesc d, const
         }
         stamp(4);
         // ================================ phase C: gate + fc2 ===================================
-        h8 a2[NT];  // fc2 fragments of the chunk: requested now, consumed after the gate math
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) a2[nt] = __builtin_bit_cast(h8, lds_rd16(w2ad + (unsigned)(nt * 1024)));
-#pragma unroll
-        for (int pt = 0; pt < 2; ++pt) {
-            u32x4 gu;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const h2 x = dg[pt][k];
-                const h2 tt = x * (h2){(_Float16)-1.4426950408889634f, (_Float16)-1.4426950408889634f};
-                h2 e = {(_Float16)__builtin_exp2f16(tt[0]), (_Float16)__builtin_exp2f16(tt[1])};
-                e = e + (h2){(_Float16)1.0f, (_Float16)1.0f};
-                const h2 r = {(_Float16)__builtin_amdgcn_rcph(e[0]), (_Float16)__builtin_amdgcn_rcph(e[1])};
-                gu[k] = as_u(da[pt][k] * (x * r));                  // a * g * sigmoid(g)
-            }
-            const h8 gf = __builtin_bit_cast(h8, gu);
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc2[nt][pt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[nt], gf, acc2[nt][pt], 0, 0, 0);
-        }
+        gate_fc2<NT>(w2ad, da, dg, acc2);
         stamp(5);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the next chunk's fc1 fragments has landed
         lds_barrier();  // every wave is done reading Us / W2 / Wd before the next chunk overwrites them
@@ -591,7 +553,7 @@ extern "C" int hat_hab_tail3(const HatHabTailDesc* dp, void* stream) {
     if (d.dtype != HAT_BF16) return HAT_EUNSUPPORTED;
     if (d.C == 180) return (d.chunks == 12 && h.reserved1 == 0) ? hat_tail3_launch_c180(h, stream) : HAT_EINVAL;
     if (d.C != T3_C) return HAT_EUNSUPPORTED;
-    if (d.ln1_g && (!d.ln1_b || !d.n_out || d.ldn < d.C || d.ldn % 4 || d.gap_c < 0 || d.gap_c > 16 || d.gap_c % 4)) return HAT_EINVAL;
+    if (!hat_ln1_args_ok(d)) return HAT_EINVAL;
     if (!h.n || !h.y16 || !h.c1 || !h.w_aggr || !h.wf || !h.bias_b || h.ldn_in < T3_C || h.ldn_in % 8) return HAT_EINVAL;
     const T3Aggr ag{reinterpret_cast<const bf16_t*>(h.n), reinterpret_cast<const bf16_t*>(h.y16), reinterpret_cast<const bf16_t*>(h.c1),
                     reinterpret_cast<const char*>(h.w_aggr), reinterpret_cast<const char*>(h.wf), h.bias_b, h.ldn_in};
@@ -601,10 +563,6 @@ extern "C" int hat_hab_tail3(const HatHabTailDesc* dp, void* stream) {
     if ((th & 1) && reinterpret_cast<uintptr_t>(d.t_in) % 8) return HAT_EINVAL;
     if ((th & 2) && reinterpret_cast<uintptr_t>(d.t_out) % 16) return HAT_EINVAL;
     void (*kern)(const HatFfnDesc, const T3Aggr) = th == 0 ? tail3_kernel<0, 0> : th == 1 ? tail3_kernel<0, 1> : th == 2 ? tail3_kernel<0, 2> : tail3_kernel<0, 3>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, T3_LDS);
-    if (e != hipSuccess) return (int)e;
-    dim3 grid((d.W + 15) / 16, (d.H + T3_ROWS - 1) / T3_ROWS, d.B);
-    HAT_LAUNCH(kern, grid, dim3(256), T3_LDS, reinterpret_cast<hipStream_t>(stream), d, ag);
-    return hat_check_launch();
+    return hat_tail_launch(kern, T3_LDS, T3_ROWS, d, ag, stream);
 }
 #endif

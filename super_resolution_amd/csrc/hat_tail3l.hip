@@ -14,14 +14,12 @@
 //   * registers: 96 fc2 accumulators + 72 B-fragment registers persist (144: 72 + 60), so the fc1 fragments of a chunk are
 //     single-buffered in LDS (the next chunk's are copied in after the barrier that ends phase A: 66 KB instead of 91) and
 //     the depthwise phase walks the 3x3 window column by column (3 tap rows of weights and 2 of U live instead of 6 and 4).
-#include "hat_common.h"
+// What it shares with hat_ffn2.hip and hat_tail3.hip lives in hat_gated_ffn.h: the fp16 / LDS helpers, dw_init, gate_fc2 and the
+// host-side argument check and launch.  The depthwise walk, the epilogue (dead lanes, gamma / beta per tile) and the GAP
+// reduction stay here: DESIGN.md 4.0d.
+#include "hat_gated_ffn.h"
 
 namespace {
-
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int L_C = 180, L_NT = 12, L_KS = 6, L_WAVES = 4, L_ROWS = 8, L_HW = 18;
 constexpr int L_NPH = (L_ROWS + 2) * L_HW;            // 180 haloed pixels
@@ -35,15 +33,6 @@ constexpr int L_WD_OFF = L_W2_OFF + L_NT * 1024;      // 65664
 constexpr int L_WD_REC = 2048;
 constexpr int L_B2_OFF = 73728, L_BIAS_OFF = 74752, L_SCALE_OFF = 75776;
 constexpr int L_LDS = 76800;
-
-typedef __attribute__((address_space(3))) char lds_char;
-__device__ __forceinline__ u32x4 lds_rd16(unsigned addr) { return *(__attribute__((address_space(3))) const u32x4*)(uintptr_t)addr; }
-__device__ __forceinline__ h2 as_h2(unsigned v) { return __builtin_bit_cast(h2, v); }
-__device__ __forceinline__ unsigned as_u(h2 v) { return __builtin_bit_cast(unsigned, v); }
-__device__ __forceinline__ void dma1k(const char* src, unsigned lane_off, char* dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + lane_off),
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
 
 struct LAggr {
     const bf16_t* n;        // (B,H,W,ldn) LayerNorm1 output
@@ -290,13 +279,7 @@ __global__ __launch_bounds__(256, 2) void tail3l_kernel(const HatFfnDesc d, cons
 
         // ====================== phase B: depthwise 3x3 in packed fp16, one window column at a time ======================
         h2 da[2][4], dg[2][4];
-        {
-            const u32x4 ba = lds_rd16(wdad + 9 * 32), bg = lds_rd16(wdad + 9 * 32 + 16);   // "tap 9" = depthwise bias
-#pragma unroll
-            for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { da[pt][k] = as_h2(ba[k]); dg[pt][k] = as_h2(bg[k]); }
-        }
+        dw_init(wdad, da, dg);
 #pragma unroll
         for (int dx = 0; dx < 3; ++dx) {
             u32x4 wa[3], wg[3], ua[2], ug[2];
@@ -333,25 +316,7 @@ __global__ __launch_bounds__(256, 2) void tail3l_kernel(const HatFfnDesc d, cons
             }
         }
         // ================================ phase C: gate + fc2 ===================================
-        h8 a2[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) a2[nt] = __builtin_bit_cast(h8, lds_rd16(w2ad + (unsigned)(nt * 1024)));
-#pragma unroll
-        for (int pt = 0; pt < 2; ++pt) {
-            u32x4 gu;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const h2 x = dg[pt][k];
-                const h2 tt = x * (h2){(_Float16)-1.4426950408889634f, (_Float16)-1.4426950408889634f};
-                h2 e = {(_Float16)__builtin_exp2f16(tt[0]), (_Float16)__builtin_exp2f16(tt[1])};
-                e = e + (h2){(_Float16)1.0f, (_Float16)1.0f};
-                const h2 r = {(_Float16)__builtin_amdgcn_rcph(e[0]), (_Float16)__builtin_amdgcn_rcph(e[1])};
-                gu[k] = as_u(da[pt][k] * (x * r));
-            }
-            const h8 gf = __builtin_bit_cast(h8, gu);
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc2[nt][pt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[nt], gf, acc2[nt][pt], 0, 0, 0);
-        }
+        gate_fc2<NT>(w2ad, da, dg, acc2);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the next chunk's fc1 fragments has landed
         lds_barrier();
     }
@@ -426,13 +391,8 @@ int hat_tail3_launch_c180(const HatHabTailDesc& h, void* stream) {
     if (!h.n || !h.y16 || !h.r2 || !h.r2scale || !h.w_aggr || !h.bias_b || h.ldn_in < L_C || h.ldn_in % 8 || h.ldr2 < L_C || h.ldr2 % 4 ||
         h.r2scale_bstride < 192)
         return HAT_EINVAL;
-    if (d.ln1_g && (!d.ln1_b || !d.n_out || d.ldn < d.C || d.ldn % 4 || d.gap_c < 0 || d.gap_c > 16 || d.gap_c % 4)) return HAT_EINVAL;
+    if (!hat_ln1_args_ok(d)) return HAT_EINVAL;
     const LAggr ag{reinterpret_cast<const bf16_t*>(h.n), reinterpret_cast<const bf16_t*>(h.y16), reinterpret_cast<const bf16_t*>(h.r2),
                    reinterpret_cast<const char*>(h.w_aggr), h.bias_b, h.r2scale, h.ldn_in, h.ldr2, h.r2scale_bstride};
-    auto kern = tail3l_kernel<0>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L_LDS);
-    if (e != hipSuccess) return (int)e;
-    dim3 grid((d.W + 15) / 16, (d.H + L_ROWS - 1) / L_ROWS, d.B);
-    HAT_LAUNCH(kern, grid, dim3(256), L_LDS, reinterpret_cast<hipStream_t>(stream), d, ag);
-    return hat_check_launch();
+    return hat_tail_launch(tail3l_kernel<0>, L_LDS, L_ROWS, d, ag, stream);
 }
