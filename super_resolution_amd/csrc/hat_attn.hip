@@ -21,6 +21,215 @@ template <typename T> __device__ __forceinline__ float exp_t(float x);
 template <> __device__ __forceinline__ float exp_t<float>(float x) { return expf(x); }
 template <> __device__ __forceinline__ float exp_t<bf16_t>(float x) { return __expf(x); }
 
+// The LDS image of `nkeys` keys of one head: K [nkeys][ldk] (channels d..dk8 are zeros), V^T [dv][ldv] and, 16-byte aligned
+// behind them at byte `tab`, the head's (Mr x Mr) bias table.  The kernels carve their LDS up with it and launch_attn sizes
+// the launch with it, so the two cannot drift apart.
+struct AttnLds { int dk8, dv, ldk, ldv; size_t tab, bytes; };
+__host__ __device__ constexpr AttnLds attn_lds(int nkeys, int d, int Mr, int es) {
+    const int dk8 = (d + 7) & ~7;                      // K channels kept in LDS (zero padded d..dk8)
+    const int dv = (d + 1) & ~1;                        // V^T rows kept in LDS
+    const int ldk = lds_row_elems(dk8, es), ldv = lds_row_elems(nkeys, es);
+    const size_t tab = (((size_t)nkeys * ldk + (size_t)dv * ldv) * es + 15) / 16 * 16;
+    return {dk8, dv, ldk, ldv, tab, tab + (size_t)Mr * Mr * 4};
+}
+
+// What ocab_attn_kernel and ocab_attn_stream_kernel share: one workgroup's view of its (window, head) and every step of the
+// attention on it.  The two kernels are two loop orders around these steps; the tuned
+// ocab_attn_fast_kernel below shares nothing with them.
+// SELF / ODD: see ocab_attn_kernel.
+template <typename T>
+struct Attn {
+    using M = MT<T>;
+    struct Query { typename M::frag_t qf; int qy, qx, rid; size_t qpix; };   // one query tile: this lane's query c16 of it
+    struct Softmax {                                                         // online-softmax state of one query tile
+        f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+        float mrun = -3.0e38f, l = 0.f;   // l: per-lane partial; reduced across the 4 lane groups in finish()
+        int kh = 0, kw = 0;               // !ODD: key row / column of the lane's 4 keys of the next key tile
+    };
+    const T* q; const T* kv; T* out;
+    const int H, W, C, ws, wse, ldq, ldkv, ldo, shift, pad, d, Mr;
+    const AttnLds L;
+    T* Ks; T* Vt; float* tab;
+    const int tid, g, c16, wave, wx, wy, b, h;
+    const size_t img;
+    const float* kbw;   // HATX key bias / prune mask of this window (hat_ocab_keybias): nkb floats, -inf = pruned key
+
+    // nkeys: keys resident in LDS at a time; nkb: keys of a window's kb row (the whole padded key window)
+    __device__ __forceinline__ Attn(char* smem, int nkeys, int nkb, const T* q, const T* kv, T* out, const float* kb, int H, int W,
+                                    int C, int heads, int ws, int wse, int ldq, int ldkv, int ldo, int shift, int pad)
+        : q(q), kv(kv), out(out), H(H), W(W), C(C), ws(ws), wse(wse), ldq(ldq), ldkv(ldkv), ldo(ldo), shift(shift), pad(pad),
+          d(C / heads), Mr(ws + wse - 1), L(attn_lds(nkeys, d, Mr, sizeof(T))), Ks(reinterpret_cast<T*>(smem)),
+          Vt(Ks + (size_t)nkeys * L.ldk), tab(reinterpret_cast<float*>(smem + L.tab)), tid(threadIdx.x), g((tid & 63) >> 4),
+          c16(tid & 15), wave(tid >> 6), wx(blockIdx.x), wy(blockIdx.y), b(blockIdx.z / heads), h(blockIdx.z - b * heads),
+          img((size_t)b * H * W), kbw(kb ? kb + (((size_t)b * gridDim.y + wy) * gridDim.x + wx) * nkb : nullptr) {}
+
+    __device__ __forceinline__ int band(int v, int n) const { return v < n - ws ? 0 : (v < n - shift ? 1 : 2); }   // of the shift mask
+
+    __device__ __forceinline__ void load_table(const float* __restrict__ bias_rot) const {
+        for (int i = tid; i < Mr * Mr; i += 256) tab[i] = bias_rot[(size_t)h * Mr * Mr + i];
+    }
+
+    // ---- stage keys [key0, key0 + n) as K [key][32] and V^T [32][key], LDS rows / columns 0 .. n; 2 channels per work item
+    template <bool SELF, bool ODD>
+    __device__ __forceinline__ void stage(int key0, int n) const {
+        const int cpk = L.dk8 / 2;  // channel pairs per key
+        for (int i = tid; i < n * cpk; i += 256) {
+            const int kl = i / cpk, c = (i - kl * cpk) * 2, key = key0 + kl;
+            const int kh = key / wse, kw = key - kh * wse;
+            int y = wy * ws - pad + kh, x = wx * ws - pad + kw;
+            if (SELF) {
+                y += shift; if (y >= H) y -= H;
+                x += shift; if (x >= W) x -= W;
+            }
+            T k0 = to_T<T>(0.f), k1 = k0, v0 = k0, v1 = k0;
+            if (c < d && (!ODD || key < wse * wse) && y >= 0 && y < H && x >= 0 && x < W) {
+                const T* p = kv + (img + (size_t)y * W + x) * ldkv + h * d + c;
+                k0 = p[0]; k1 = p[1];
+                v0 = p[C]; v1 = p[C + 1];
+            }
+            Ks[kl * L.ldk + c] = k0; Ks[kl * L.ldk + c + 1] = k1;
+            if (c < L.dv) { Vt[c * L.ldv + kl] = v0; Vt[(c + 1) * L.ldv + kl] = v1; }
+        }
+    }
+
+    // ---- Q fragment (B operand) of query tile qt: this lane's query, channels 8g..8g+7
+    template <bool SELF>
+    __device__ __forceinline__ Query load_query(int qt) const {
+        Query r;
+        const int qi = qt * 16 + c16;
+        r.qy = qi / ws; r.qx = qi - r.qy * ws;
+        int qyo = wy * ws + r.qy, qxo = wx * ws + r.qx;   // position on the (shifted) frame -> pixel of the map
+        r.rid = SELF ? 3 * band(qyo, H) + band(qxo, W) : 0;
+        if (SELF) {
+            qyo += shift; if (qyo >= H) qyo -= H;
+            qxo += shift; if (qxo >= W) qxo -= W;
+        }
+        r.qpix = img + (size_t)qyo * W + qxo;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = 8 * g + j;
+            r.qf[j] = c < d ? q[r.qpix * ldq + h * d + c] : to_T<T>(0.f);
+        }
+        return r;
+    }
+
+    // The chunk step — S^T tiles, softmax update, O^T update for KCH key tiles — is three calls, and the loops over the
+    // key tiles stay in the kernels: a helper that held them would be unrolled on its own before it is inlined, the K / V
+    // reads of the stream kernel's four query tiles would then be merged and held in registers, and that kernel spills.
+
+    // ---- S^T tile of the key tile at LDS tile kl: s[r] = S[key = 16 kl + 4g + r][query c16]
+    __device__ __forceinline__ f32x4 qk(const Query& qr, int kl) const {
+        // channel groups beyond dk8 are clamped: they meet a zero Q fragment, so contribute 0
+        const typename M::frag_t kf = M::load(Ks + (kl * 16 + c16) * L.ldk + (8 * g < L.dk8 ? 8 * g : L.dk8 - 8));
+        return M::mma(kf, qr.qf, f32x4{0.f, 0.f, 0.f, 0.f});
+    }
+
+    // ---- one online-softmax step over the S^T tiles of key tiles kt0 .. kt0 + KCH of the window: s becomes P^T (O is only
+    //      d <= 32 wide, so the rescale is 8 registers; this keeps the live S tile set at KCH*4 registers)
+    template <int KCH, bool SELF, bool ODD>
+    __device__ __forceinline__ void softmax(f32x4 (&s)[KCH], const Query& qr, Softmax& st, int kt0) const {
+        if (kbw != nullptr) {   // hatx_arch.py:421-449: + focus bias per key; a pruned key's logit is REPLACED by -1e4
+#pragma unroll
+            for (int t = 0; t < KCH; ++t) {
+                const f32x4 k4 = *reinterpret_cast<const f32x4*>(kbw + (kt0 + t) * 16 + 4 * g);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s[t][r] = k4[r] == -INFINITY ? -1.0e4f : s[t][r] + k4[r];
+            }
+        }
+        float mx = -3.0e38f;
+#pragma unroll
+        for (int t = 0; t < KCH; ++t) {
+            const float* tb = tab + (st.kh - qr.qy + ws - 1) * Mr + (st.kw - qr.qx + ws - 1);
+            // the lane's 4 keys share a mask band: shift % 4 == 0 and kw % 4 == 0
+            const float madd = (SELF && shift > 0 && 3 * band(wy * ws + st.kh, H) + band(wx * ws + st.kw, W) != qr.rid) ? -100.0f : 0.0f;
+            if constexpr (ODD) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int key = (kt0 + t) * 16 + 4 * g + r;
+                    const int khr = key / wse, kwr = key - khr * wse;
+                    const int ti = min((khr - qr.qy + ws - 1) * Mr + (kwr - qr.qx + ws - 1), Mr * Mr - 1);
+                    s[t][r] = key < wse * wse ? s[t][r] + tab[ti] : -3.0e38f;
+                    mx = fmaxf(mx, s[t][r]);
+                }
+                continue;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                s[t][r] += tb[r];
+                if (SELF) s[t][r] += madd;
+                mx = fmaxf(mx, s[t][r]);
+            }
+            st.kw += 16;
+            while (st.kw >= wse) { st.kw -= wse; ++st.kh; }
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float mnew = fmaxf(st.mrun, mx);
+        const float alpha = exp_t<T>(st.mrun - mnew);
+        st.mrun = mnew;
+        float lsum = 0.f;
+#pragma unroll
+        for (int t = 0; t < KCH; ++t) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p = exp_t<T>(s[t][r] - mnew);
+                s[t][r] = p;
+                lsum += p;
+            }
+        }
+        st.l = st.l * alpha + lsum;
+        st.o[0] *= alpha;
+        st.o[1] *= alpha;
+    }
+
+    // ---- O^T += V^T . P^T for the chunk's key tiles 2 kk and (but for the last of an odd KCH) 2 kk + 1, which sit in LDS from key
+    //      tile kl0 on: k-slot (g, j) = key 32 kk + 4g + j (j<4) | 32 kk + 16 + 4g + (j-4)
+    template <int KCH>
+    __device__ __forceinline__ void pv(const f32x4 (&s)[KCH], int kk, int kl0, Softmax& st) const {
+        const bool has_b = (2 * kk + 1 < KCH);
+        const int kb = has_b ? 2 * kk + 1 : 2 * kk;
+        typename M::frag_t pf;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            pf[j] = to_T<T>(s[2 * kk][j]);
+            pf[j + 4] = has_b ? to_T<T>(s[kb][j]) : to_T<T>(0.f);
+        }
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+            // rows >= d are clamped: their outputs are never stored
+            const int vrow = (ct * 16 + c16 < L.dv) ? ct * 16 + c16 : L.dv - 1;
+            const T* vr = Vt + (size_t)vrow * L.ldv + (kl0 + 2 * kk) * 16 + 4 * g;
+            const Q4<T> va = *reinterpret_cast<const Q4<T>*>(vr);
+            const Q4<T> vb = *reinterpret_cast<const Q4<T>*>(vr + (has_b ? 16 : 0));
+            typename M::frag_t vf;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                vf[j] = va.v[j];
+                vf[j + 4] = has_b ? vb.v[j] : to_T<T>(0.f);
+            }
+            st.o[ct] = M::mma(vf, pf, st.o[ct]);
+        }
+    }
+
+    // ---- store: lane holds channels ct*16 + 4g + r of query c16
+    __device__ __forceinline__ void finish(const Query& qr, const Softmax& st) const {
+        float l = st.l;
+        l += __shfl_xor(l, 16);
+        l += __shfl_xor(l, 32);
+        const float inv = 1.0f / l;
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int c = ct * 16 + 4 * g + r;
+                if (c < d) out[qr.qpix * ldo + h * d + c] = to_T<T>(st.o[ct][r] * inv);
+            }
+        }
+    }
+};
+
+// One workgroup (4 waves) per (window, head), the whole key window resident in LDS; every wave finishes one query tile after
+// the other.
 // SELF = true turns the same kernel into (shifted-)window self-attention, (S)W-MSA of swinir_arch.py:140-172, 291-317:
 // the key window is the query window (wse == ws), window coordinates live on the cyclically shifted frame (pixel
 // (Y, X) of the shifted frame is pixel ((Y + shift) % H, (X + shift) % W) of the map, so the two torch.roll calls become
@@ -34,177 +243,30 @@ __global__ __launch_bounds__(256) void ocab_attn_kernel(const T* __restrict__ q,
                                                         const float* __restrict__ bias_rot, T* __restrict__ out, int H, int W,
                                                         int C, int heads, int ws, int wse, int ldq, int ldkv, int ldo,
                                                         int shift, const float* __restrict__ kb, int pad) {
-    using M = MT<T>;
     constexpr int NK = NKT * 16;
     static_assert(NKT % KCH == 0, "key tiles must split evenly into chunks");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int d = C / heads;
-    const int dk8 = (d + 7) & ~7;                      // K channels kept in LDS (zero padded d..dk8)
-    const int dv = (d + 1) & ~1;                        // V^T rows kept in LDS
-    const int ldk = lds_row_elems(dk8, sizeof(T));
-    const int ldv = lds_row_elems(NK, sizeof(T));
-    T* Ks = reinterpret_cast<T*>(smem);
-    T* Vt = Ks + (size_t)NK * ldk;
-    float* tab = reinterpret_cast<float*>(smem + (((size_t)NK * ldk + (size_t)dv * ldv) * sizeof(T) + 15) / 16 * 16);
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c16 = lane & 15;
-    const int wx = blockIdx.x, wy = blockIdx.y;
-    const int b = blockIdx.z / heads, h = blockIdx.z - b * heads;
-    const int Mr = ws + wse - 1;
-    const size_t img = (size_t)b * H * W;
-    // HATX key bias / prune mask of this window (hat_ocab_keybias): NK floats, -inf = pruned key
-    const float* kbw = kb ? kb + (((size_t)b * gridDim.y + wy) * gridDim.x + wx) * NK : nullptr;
-
-    for (int i = tid; i < Mr * Mr; i += 256) tab[i] = bias_rot[(size_t)h * Mr * Mr + i];
-
-    // ---- stage K [key][32] and V^T [32][key]; 2 channels per work item -----------------------
-    const int cpk = dk8 / 2;  // channel pairs per key
-    for (int i = tid; i < NK * cpk; i += 256) {
-        const int key = i / cpk, c = (i - key * cpk) * 2;
-        const int kh = key / wse, kw = key - kh * wse;
-        int y = wy * ws - pad + kh, x = wx * ws - pad + kw;
-        if (SELF) {
-            y += shift; if (y >= H) y -= H;
-            x += shift; if (x >= W) x -= W;
-        }
-        T k0 = to_T<T>(0.f), k1 = k0, v0 = k0, v1 = k0;
-        if (c < d && (!ODD || key < wse * wse) && y >= 0 && y < H && x >= 0 && x < W) {
-            const T* p = kv + (img + (size_t)y * W + x) * ldkv + h * d + c;
-            k0 = p[0]; k1 = p[1];
-            v0 = p[C]; v1 = p[C + 1];
-        }
-        Ks[key * ldk + c] = k0; Ks[key * ldk + c + 1] = k1;
-        if (c < dv) { Vt[c * ldv + key] = v0; Vt[(c + 1) * ldv + key] = v1; }
-    }
+    const Attn<T> a(smem, NK, NK, q, kv, out, kb, H, W, C, heads, ws, wse, ldq, ldkv, ldo, shift, pad);
+    a.load_table(bias_rot);
+    a.template stage<SELF, ODD>(0, NK);
     __syncthreads();
 
     const int nqt = (ws * ws) / 16;
-    for (int qt = wave; qt < nqt; qt += 4) {
-        // ---- Q fragment (B operand): this lane's query, channels 8g..8g+7 --------------------
-        const int qi = qt * 16 + c16;
-        const int qy = qi / ws, qx = qi - qy * ws;
-        int qyo = wy * ws + qy, qxo = wx * ws + qx;   // position on the (shifted) frame -> pixel of the map
-        auto band = [&](int v, int n) { return v < n - ws ? 0 : (v < n - shift ? 1 : 2); };
-        const int rid_q = SELF ? 3 * band(qyo, H) + band(qxo, W) : 0;
-        if (SELF) {
-            qyo += shift; if (qyo >= H) qyo -= H;
-            qxo += shift; if (qxo >= W) qxo -= W;
-        }
-        const size_t qpix = img + (size_t)qyo * W + qxo;
-        typename M::frag_t qf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int c = 8 * g + j;
-            qf[j] = c < d ? q[qpix * ldq + h * d + c] : to_T<T>(0.f);
-        }
-        // ---- online softmax over chunks of KCH key tiles (O is only d <= 32 wide, so the rescale
-        //      is 8 registers; this keeps the live S tile set at KCH*4 registers) ------------------
-        f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-        float mrun = -3.0e38f, l = 0.f;
-        int kh = (4 * g) / wse, kw = 4 * g - kh * wse;  // the lane's 4 keys of a tile share one key row (wse % 4 == 0)
+    for (int qt = a.wave; qt < nqt; qt += 4) {
+        const typename Attn<T>::Query qr = a.template load_query<SELF>(qt);
+        typename Attn<T>::Softmax st;
+        st.kh = (4 * a.g) / wse; st.kw = 4 * a.g - st.kh * wse;  // the lane's 4 keys of a tile share one key row (wse % 4 == 0)
 #pragma unroll 1
         for (int ch = 0; ch < NKT / KCH; ++ch) {
             const int kt0 = ch * KCH;
-            // S^T tiles: s[t][r] = S[key = 16 (kt0+t) + 4g + r][query c16]
             f32x4 s[KCH];
 #pragma unroll
-            for (int t = 0; t < KCH; ++t) {
-                // channel groups beyond dk8 are clamped: they meet a zero Q fragment, so contribute 0
-                const typename M::frag_t kf = M::load(Ks + ((kt0 + t) * 16 + c16) * ldk + (8 * g < dk8 ? 8 * g : dk8 - 8));
-                s[t] = M::mma(kf, qf, f32x4{0.f, 0.f, 0.f, 0.f});
-            }
-            if (kbw != nullptr) {   // hatx_arch.py:421-449: + focus bias per key; a pruned key's logit is REPLACED by -1e4
+            for (int t = 0; t < KCH; ++t) s[t] = a.qk(qr, kt0 + t);
+            a.template softmax<KCH, SELF, ODD>(s, qr, st, kt0);
 #pragma unroll
-                for (int t = 0; t < KCH; ++t) {
-                    const f32x4 k4 = *reinterpret_cast<const f32x4*>(kbw + (kt0 + t) * 16 + 4 * g);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) s[t][r] = k4[r] == -INFINITY ? -1.0e4f : s[t][r] + k4[r];
-                }
-            }
-            float mx = -3.0e38f;
-#pragma unroll
-            for (int t = 0; t < KCH; ++t) {
-                const float* tb = tab + (kh - qy + ws - 1) * Mr + (kw - qx + ws - 1);
-                // the lane's 4 keys share a mask band: shift % 4 == 0 and kw % 4 == 0
-                const float madd = (SELF && shift > 0 && 3 * band(wy * ws + kh, H) + band(wx * ws + kw, W) != rid_q) ? -100.0f : 0.0f;
-                if constexpr (ODD) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int key = (kt0 + t) * 16 + 4 * g + r;
-                        const int khr = key / wse, kwr = key - khr * wse;
-                        const int ti = min((khr - qy + ws - 1) * Mr + (kwr - qx + ws - 1), Mr * Mr - 1);
-                        s[t][r] = key < wse * wse ? s[t][r] + tab[ti] : -3.0e38f;
-                        mx = fmaxf(mx, s[t][r]);
-                    }
-                    continue;
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    s[t][r] += tb[r];
-                    if (SELF) s[t][r] += madd;
-                    mx = fmaxf(mx, s[t][r]);
-                }
-                kw += 16;
-                while (kw >= wse) { kw -= wse; ++kh; }
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 16));
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float mnew = fmaxf(mrun, mx);
-            const float alpha = exp_t<T>(mrun - mnew);
-            mrun = mnew;
-            float lsum = 0.f;
-#pragma unroll
-            for (int t = 0; t < KCH; ++t) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float p = exp_t<T>(s[t][r] - mnew);
-                    s[t][r] = p;
-                    lsum += p;
-                }
-            }
-            l = l * alpha + lsum;  // per-lane partial; reduced across the 4 lane groups after the loop
-            o[0] *= alpha;
-            o[1] *= alpha;
-            // O^T += V^T . P^T : k-slot (g, j) = key 32 kk + 4g + j (j<4) | 32 kk + 16 + 4g + (j-4)
-#pragma unroll
-            for (int kk = 0; kk < (KCH + 1) / 2; ++kk) {
-                const bool has_b = (2 * kk + 1 < KCH);
-                const int kb = has_b ? 2 * kk + 1 : 2 * kk;
-                typename M::frag_t pf;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    pf[j] = to_T<T>(s[2 * kk][j]);
-                    pf[j + 4] = has_b ? to_T<T>(s[kb][j]) : to_T<T>(0.f);
-                }
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct) {
-                    // rows >= d are clamped: their outputs are never stored
-                    const int vrow = (ct * 16 + c16 < dv) ? ct * 16 + c16 : dv - 1;
-                    const T* vr = Vt + (size_t)vrow * ldv + (kt0 + 2 * kk) * 16 + 4 * g;
-                    const Q4<T> va = *reinterpret_cast<const Q4<T>*>(vr);
-                    const Q4<T> vb = *reinterpret_cast<const Q4<T>*>(vr + (has_b ? 16 : 0));
-                    typename M::frag_t vf;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        vf[j] = va.v[j];
-                        vf[j + 4] = has_b ? vb.v[j] : to_T<T>(0.f);
-                    }
-                    o[ct] = M::mma(vf, pf, o[ct]);
-                }
-            }
+            for (int kk = 0; kk < (KCH + 1) / 2; ++kk) a.template pv<KCH>(s, kk, kt0, st);
         }
-        l += __shfl_xor(l, 16);
-        l += __shfl_xor(l, 32);
-        // ---- store: lane holds channels ct*16 + 4g + r of query c16 -----------------------------
-        const float inv = 1.0f / l;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int c = ct * 16 + 4 * g + r;
-                if (c < d) out[qpix * ldo + h * d + c] = to_T<T>(o[ct][r] * inv);
-            }
-        }
+        a.finish(qr, st);
     }
 }
 
@@ -214,156 +276,40 @@ __global__ __launch_bounds__(256) void ocab_attn_kernel(const T* __restrict__ q,
 // fp32 = 169 KB).  The online softmax already consumed the keys in chunks of KCH tiles; here only ONE chunk of K and V^T is
 // resident (KCH = 10: 43 KB), staged by the whole workgroup between two barriers, and every wave carries the softmax state
 // (O, running max, partial denominator) of ALL its NQW query tiles across the chunks instead of finishing one query tile
-// after the other.  Same arithmetic, same order of the key chunks, same ODD handling (dead keys past wse^2, per-key bias
-// lookup) and the same optional HATX key bias as ocab_attn_kernel.
+// after the other.  The steps are ocab_attn_kernel's own (Attn<T>, with its ODD handling: dead keys past wse^2, per-key bias
+// lookup), on the key chunks in the same order.  Instantiated only where a window can fail to fit (attn_may_stream).
 // ---------------------------------------------------------------------------------------------------------
 template <typename T, int NKT, int KCH, int NQW>
 __global__ __launch_bounds__(256) void ocab_attn_stream_kernel(const T* __restrict__ q, const T* __restrict__ kv,
                                                                const float* __restrict__ bias_rot, T* __restrict__ out, int H, int W,
                                                                int C, int heads, int ws, int wse, int ldq, int ldkv, int ldo,
                                                                const float* __restrict__ kb, int pad) {
-    using M = MT<T>;
     constexpr int NK = NKT * 16, CK = KCH * 16;
     static_assert(NKT % KCH == 0, "key tiles must split evenly into chunks");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int d = C / heads;
-    const int dk8 = (d + 7) & ~7, dv = (d + 1) & ~1;
-    const int ldk = lds_row_elems(dk8, sizeof(T)), ldv = lds_row_elems(CK, sizeof(T));
-    T* Ks = reinterpret_cast<T*>(smem);                       // [CK][ldk]   one chunk of keys
-    T* Vt = Ks + (size_t)CK * ldk;                            // [dv][ldv]   the same chunk of V, transposed
-    float* tab = reinterpret_cast<float*>(smem + (((size_t)CK * ldk + (size_t)dv * ldv) * sizeof(T) + 15) / 16 * 16);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c16 = lane & 15;
-    const int wx = blockIdx.x, wy = blockIdx.y;
-    const int b = blockIdx.z / heads, h = blockIdx.z - b * heads;
-    const int Mr = ws + wse - 1;
-    const size_t img = (size_t)b * H * W;
-    const float* kbw = kb ? kb + (((size_t)b * gridDim.y + wy) * gridDim.x + wx) * NK : nullptr;
-    for (int i = tid; i < Mr * Mr; i += 256) tab[i] = bias_rot[(size_t)h * Mr * Mr + i];
-
-    typename M::frag_t qf[NQW];
-    f32x4 o[NQW][2];
-    float mrun[NQW], l[NQW];
-    int qy[NQW], qx[NQW];
-    size_t qpix[NQW];
+    const Attn<T> a(smem, CK, NK, q, kv, out, kb, H, W, C, heads, ws, wse, ldq, ldkv, ldo, 0, pad);
+    a.load_table(bias_rot);
+    typename Attn<T>::Query qr[NQW];
+    typename Attn<T>::Softmax st[NQW];
 #pragma unroll
-    for (int i = 0; i < NQW; ++i) {
-        const int qi = (wave + 4 * i) * 16 + c16;
-        qy[i] = qi / ws; qx[i] = qi - qy[i] * ws;
-        qpix[i] = img + (size_t)(wy * ws + qy[i]) * W + wx * ws + qx[i];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int c = 8 * g + j;
-            qf[i][j] = c < d ? q[qpix[i] * ldq + h * d + c] : to_T<T>(0.f);
-        }
-        o[i][0] = o[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-        mrun[i] = -3.0e38f; l[i] = 0.f;
-    }
-    const int cpk = dk8 / 2;
+    for (int i = 0; i < NQW; ++i) qr[i] = a.template load_query<false>(a.wave + 4 * i);
 #pragma unroll 1
     for (int ch = 0; ch < NKT / KCH; ++ch) {
-        const int kt0 = ch * KCH;
         __syncthreads();   // every wave is done with the previous chunk (first pass: the bias table is complete)
-        for (int i = tid; i < CK * cpk; i += 256) {
-            const int kl = i / cpk, c = (i - kl * cpk) * 2, key = kt0 * 16 + kl;
-            const int kh = key / wse, kw = key - kh * wse;
-            const int y = wy * ws - pad + kh, x = wx * ws - pad + kw;
-            T k0 = to_T<T>(0.f), k1 = k0, v0 = k0, v1 = k0;
-            if (c < d && key < wse * wse && y >= 0 && y < H && x >= 0 && x < W) {
-                const T* p = kv + (img + (size_t)y * W + x) * ldkv + h * d + c;
-                k0 = p[0]; k1 = p[1];
-                v0 = p[C]; v1 = p[C + 1];
-            }
-            Ks[kl * ldk + c] = k0; Ks[kl * ldk + c + 1] = k1;
-            if (c < dv) { Vt[c * ldv + kl] = v0; Vt[(c + 1) * ldv + kl] = v1; }
-        }
+        a.template stage<false, true>(ch * CK, CK);
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < NQW; ++i) {
             f32x4 s[KCH];
 #pragma unroll
-            for (int t = 0; t < KCH; ++t) {
-                const typename M::frag_t kf = M::load(Ks + (t * 16 + c16) * ldk + (8 * g < dk8 ? 8 * g : dk8 - 8));
-                s[t] = M::mma(kf, qf[i], f32x4{0.f, 0.f, 0.f, 0.f});
-            }
-            if (kbw != nullptr) {   // hatx_arch.py:421-449: + focus bias per key; a pruned key's logit is REPLACED by -1e4
+            for (int t = 0; t < KCH; ++t) s[t] = a.qk(qr[i], t);
+            a.template softmax<KCH, false, true>(s, qr[i], st[i], ch * KCH);
 #pragma unroll
-                for (int t = 0; t < KCH; ++t) {
-                    const f32x4 k4 = *reinterpret_cast<const f32x4*>(kbw + (kt0 + t) * 16 + 4 * g);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) s[t][r] = k4[r] == -INFINITY ? -1.0e4f : s[t][r] + k4[r];
-                }
-            }
-            float mx = -3.0e38f;
-#pragma unroll
-            for (int t = 0; t < KCH; ++t) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int key = (kt0 + t) * 16 + 4 * g + r;
-                    const int khr = key / wse, kwr = key - khr * wse;
-                    const int ti = min((khr - qy[i] + ws - 1) * Mr + (kwr - qx[i] + ws - 1), Mr * Mr - 1);
-                    s[t][r] = key < wse * wse ? s[t][r] + tab[ti] : -3.0e38f;
-                    mx = fmaxf(mx, s[t][r]);
-                }
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 16));
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float mnew = fmaxf(mrun[i], mx);
-            const float alpha = exp_t<T>(mrun[i] - mnew);
-            mrun[i] = mnew;
-            float lsum = 0.f;
-#pragma unroll
-            for (int t = 0; t < KCH; ++t) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float pe = exp_t<T>(s[t][r] - mnew);
-                    s[t][r] = pe;
-                    lsum += pe;
-                }
-            }
-            l[i] = l[i] * alpha + lsum;
-            o[i][0] *= alpha;
-            o[i][1] *= alpha;
-#pragma unroll
-            for (int kk = 0; kk < (KCH + 1) / 2; ++kk) {
-                const bool has_b = (2 * kk + 1 < KCH);
-                const int kb2 = has_b ? 2 * kk + 1 : 2 * kk;
-                typename M::frag_t pf;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    pf[j] = to_T<T>(s[2 * kk][j]);
-                    pf[j + 4] = has_b ? to_T<T>(s[kb2][j]) : to_T<T>(0.f);
-                }
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct) {
-                    const int vrow = (ct * 16 + c16 < dv) ? ct * 16 + c16 : dv - 1;
-                    const T* vr = Vt + (size_t)vrow * ldv + (2 * kk) * 16 + 4 * g;
-                    const Q4<T> va = *reinterpret_cast<const Q4<T>*>(vr);
-                    const Q4<T> vb = *reinterpret_cast<const Q4<T>*>(vr + (has_b ? 16 : 0));
-                    typename M::frag_t vf;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        vf[j] = va.v[j];
-                        vf[j + 4] = has_b ? vb.v[j] : to_T<T>(0.f);
-                    }
-                    o[i][ct] = M::mma(vf, pf, o[i][ct]);
-                }
-            }
+            for (int kk = 0; kk < (KCH + 1) / 2; ++kk) a.template pv<KCH>(s, kk, 0, st[i]);
         }
     }
 #pragma unroll
-    for (int i = 0; i < NQW; ++i) {
-        float ls = l[i];
-        ls += __shfl_xor(ls, 16);
-        ls += __shfl_xor(ls, 32);
-        const float inv = 1.0f / ls;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int c = ct * 16 + 4 * g + r;
-                if (c < d) out[qpix[i] * ldo + h * d + c] = to_T<T>(o[i][ct][r] * inv);
-            }
-    }
+    for (int i = 0; i < NQW; ++i) a.finish(qr[i], st[i]);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -731,43 +677,6 @@ __global__ __launch_bounds__(NTH, WSE == 24 ? 2 : 4) void ocab_attn_fast_kernel(
     }
 }
 
-template <typename T, int NKT, int KCH, bool SELF = false, bool ODD = false>
-int launch_attn(const void* q, const void* kv, const float* bias_rot, void* out, int B, int H, int W, int C, int heads,
-                int ws, int wse, int ldq, int ldkv, int ldo, hipStream_t s, int shift = 0, const float* kb = nullptr, int pad = -1) {
-    if (pad < 0) pad = (wse - ws + 1) / 2;   // (HATX pads odd overlaps with the ceiling, hatx_arch.py:303-305)
-    const int es = sizeof(T);
-    const int Mr = ws + wse - 1;
-    const int d = C / heads, dk8 = (d + 7) & ~7, dv = (d + 1) & ~1;
-    const size_t kvb = ((size_t)NKT * 16 * lds_row_elems(dk8, es) + (size_t)dv * lds_row_elems(NKT * 16, es)) * es;
-    const size_t lds = (kvb + 15) / 16 * 16 + (size_t)Mr * Mr * 4;
-    if (lds > HAT_LDS_MAX) {
-        // the key window does not fit: stream it through LDS chunk by chunk (instantiated for 16 x 16 query windows)
-        if constexpr (!SELF) {
-            if (ws != 16) return HAT_ELDS;
-            const size_t cb = ((size_t)KCH * 16 * lds_row_elems(dk8, es) + (size_t)dv * lds_row_elems(KCH * 16, es)) * es;
-            const size_t lds2 = (cb + 15) / 16 * 16 + (size_t)Mr * Mr * 4;
-            if (lds2 > HAT_LDS_MAX) return HAT_ELDS;
-            auto ks = ocab_attn_stream_kernel<T, NKT, KCH, 4>;
-            if (lds2 > 65536) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-                if (e != hipSuccess) return (int)e;
-            }
-            HAT_LAUNCH(ks, dim3(W / ws, H / ws, B * heads), dim3(256), lds2, s, reinterpret_cast<const T*>(q), reinterpret_cast<const T*>(kv),
-                       bias_rot, reinterpret_cast<T*>(out), H, W, C, heads, ws, wse, ldq, ldkv, ldo, kb, pad);
-            return hat_check_launch();
-        }
-        return HAT_ELDS;
-    }
-    auto kern = ocab_attn_kernel<T, NKT, KCH, SELF, ODD>;
-    if (lds > 65536) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    dim3 grid(W / ws, H / ws, B * heads);
-    HAT_LAUNCH(kern, grid, dim3(256), lds, s, reinterpret_cast<const T*>(q), reinterpret_cast<const T*>(kv), bias_rot,
-                       reinterpret_cast<T*>(out), H, W, C, heads, ws, wse, ldq, ldkv, ldo, shift, kb, pad);
-    return hat_check_launch();
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // HATX key bias / prune mask (hatx_arch.py:421-449): one workgroup per key window, one thread per key.
@@ -811,55 +720,121 @@ __global__ __launch_bounds__(1024) void keybias_kernel(const ST* __restrict__ sa
         kb[(((size_t)b * gridDim.y + wy) * gridDim.x + wx) * nkp + key] = 0.f;
     }
 }
-}  // namespace
 
-namespace {
-// The generic kernel's instantiations by key-window size: 24 / 12 (HAT: window 16 / 8, overlap 0.5), 25 (HATX training
-// config: window 16, overlap 0.6; 625 keys in 40 tiles) and 13 (window 8, overlap 0.7: the small model of the goldens).
-int attn_dispatch(const void* q, const void* kv, const float* bias_rot, void* out, int B, int H, int W, int C, int heads, int ws, int wse,
-                  int ldq, int ldkv, int ldo, int dtype, hipStream_t s, const float* kb, int pad) {
-#define HAT_ATTN_CASE(TT, N, K, ODD_) return launch_attn<TT, N, K, false, ODD_>(q, kv, bias_rot, out, B, H, W, C, heads, ws, wse, ldq, ldkv, ldo, s, 0, kb, pad)
-    if (dtype != HAT_BF16 && dtype != HAT_F32) return HAT_EINVAL;
-    if (dtype == HAT_BF16) {
-        if (wse == 24) HAT_ATTN_CASE(bf16_t, 36, 12, false);
-        if (wse == 12) HAT_ATTN_CASE(bf16_t, 9, 9, false);
-        if (wse == 25) HAT_ATTN_CASE(bf16_t, 40, 10, true);
-        if (wse == 13) HAT_ATTN_CASE(bf16_t, 11, 11, true);
-    } else {
-        if (wse == 24) HAT_ATTN_CASE(float, 36, 12, false);
-        if (wse == 12) HAT_ATTN_CASE(float, 9, 9, false);
-        if (wse == 25) HAT_ATTN_CASE(float, 40, 10, true);
-        if (wse == 13) HAT_ATTN_CASE(float, 11, 11, true);
+// ---------------------------------------------------------------------------------------------------------
+// Host side
+// ---------------------------------------------------------------------------------------------------------
+// What hat_ocab_attention, hat_ocab_attention_kb and hat_window_attention all refuse, in the order they always tested it;
+// `window_ok` holds the entry's own conditions on the windows and runs between the two shared lines.
+template <typename F>
+int attn_check(bool ptrs, int B, int C, int heads, int ldq, int ldkv, int ldo, F window_ok) {
+    if (!ptrs || B < 1 || heads < 1 || C % heads) return HAT_EINVAL;
+    if (!window_ok()) return HAT_EINVAL;
+    const int d = C / heads;
+    if (d > 32 || d % 2 || ldq < C || ldkv < 2 * C || ldo < C) return HAT_EINVAL;
+    return 0;
+}
+
+// Raise the dynamic-LDS limit where the launch needs more than the default 64 KiB, launch, report.
+template <typename K, typename... A>
+int attn_launch(K kern, dim3 grid, int threads, size_t lds, hipStream_t s, A... args) {
+    if (lds > 65536) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
     }
-#undef HAT_ATTN_CASE
-    return HAT_EUNSUPPORTED;  // other key-window sizes are not instantiated
+    HAT_LAUNCH(kern, grid, dim3(threads), lds, s, args...);
+    return hat_check_launch();
+}
+
+struct AttnArgs {   // one call of a generic kernel; pad < 0: the ceiling (HATX pads odd overlaps with it, hatx_arch.py:303-305)
+    const void* q; const void* kv; const float* bias; void* out;
+    int B, H, W, C, heads, ws, wse, ldq, ldkv, ldo;
+    hipStream_t s;
+    int shift; const float* kb; int pad;
+};
+
+// Whether a key window of nkt tiles may have to be streamed: not when its resident image fits in LDS for every call that
+// reaches ocab_attn_stream_kernel.  The stream kernel takes ws == 16 only, the entries admit d <= 32 and attn_lds grows
+// with d, and nkt tiles hold wse * wse <= 16 nkt keys, which bounds the table.  Where this is false, a call whose image does
+// not fit has ws != 16, which the streaming branch refuses with HAT_ELDS as well — so launch_attn returns the same code
+// with the stream kernel never instantiated.  True for fp32 with 40 key tiles alone (25 x 25 keys: 92 160 B of K + 82 432 B
+// of V^T at d = 32); fp32 with 36 tiles is 163 268 B and bf16 with 40 tiles 109 824 B.
+constexpr bool attn_may_stream(int nkt, int es) {
+    int wse = 0;
+    while ((wse + 1) * (wse + 1) <= 16 * nkt) ++wse;
+    return attn_lds(16 * nkt, 32, 16 + wse - 1, es).bytes > HAT_LDS_MAX;
+}
+
+template <typename T, int NKT, int KCH, bool SELF, bool ODD>
+int launch_attn(const AttnArgs& a) {
+    const int pad = a.pad < 0 ? (a.wse - a.ws + 1) / 2 : a.pad;
+    const int Mr = a.ws + a.wse - 1, d = a.C / a.heads;
+    const dim3 grid(a.W / a.ws, a.H / a.ws, a.B * a.heads);
+    const T* q = reinterpret_cast<const T*>(a.q);
+    const T* kv = reinterpret_cast<const T*>(a.kv);
+    T* out = reinterpret_cast<T*>(a.out);
+    const size_t lds = attn_lds(NKT * 16, d, Mr, sizeof(T)).bytes;
+    if (lds <= HAT_LDS_MAX)
+        return attn_launch(ocab_attn_kernel<T, NKT, KCH, SELF, ODD>, grid, 256, lds, a.s, q, kv, a.bias, out, a.H, a.W, a.C, a.heads, a.ws,
+                           a.wse, a.ldq, a.ldkv, a.ldo, a.shift, a.kb, pad);
+    // the key window does not fit: stream it through LDS chunk by chunk (instantiated for 16 x 16 query windows)
+    if constexpr (!SELF && attn_may_stream(NKT, sizeof(T))) {
+        const size_t lds2 = attn_lds(KCH * 16, d, Mr, sizeof(T)).bytes;
+        if (a.ws == 16 && lds2 <= HAT_LDS_MAX)
+            return attn_launch(ocab_attn_stream_kernel<T, NKT, KCH, 4>, grid, 256, lds2, a.s, q, kv, a.bias, out, a.H, a.W, a.C, a.heads,
+                               a.ws, a.wse, a.ldq, a.ldkv, a.ldo, a.kb, pad);
+    }
+    return HAT_ELDS;
+}
+
+// The generic kernels' instantiations by key-window size.  OCAB: 24 / 12 (HAT: window 16 / 8, overlap 0.5), 25 (HATX training
+// config: window 16, overlap 0.6; 625 keys in 40 tiles) and 13 (window 8, overlap 0.7: the small model of the goldens).
+// SELF: the key window is the query window, 16 or 8.
+template <typename T, bool SELF>
+int attn_by_window(const AttnArgs& a) {
+    if constexpr (SELF) {
+        if (a.wse == 16) return launch_attn<T, 16, 8, true, false>(a);
+        if (a.wse == 8) return launch_attn<T, 4, 4, true, false>(a);
+    } else {
+        if (a.wse == 24) return launch_attn<T, 36, 12, false, false>(a);
+        if (a.wse == 12) return launch_attn<T, 9, 9, false, false>(a);
+        if (a.wse == 25) return launch_attn<T, 40, 10, false, true>(a);
+        if (a.wse == 13) return launch_attn<T, 11, 11, false, true>(a);
+    }
+    return HAT_EUNSUPPORTED;  // other window sizes are not instantiated
+}
+
+template <bool SELF>
+int attn_dispatch(const AttnArgs& a, int dtype) {
+    if (dtype == HAT_BF16) return attn_by_window<bf16_t, SELF>(a);
+    if (dtype == HAT_F32) return attn_by_window<float, SELF>(a);
+    return HAT_EINVAL;
 }
 }  // namespace
+
 
 static int ocab_attention_impl(const void* q, const void* kv, const float* bias_rot, void* out, int32_t B, int32_t H,
                                int32_t W, int32_t C, int32_t heads, int32_t ws, int32_t wse, int32_t ldq,
                                int32_t ldkv, int32_t ldo, int32_t dtype, void* stream, bool qlog2) {
-    if (!q || !kv || !bias_rot || !out || B < 1 || heads < 1 || C % heads) return HAT_EINVAL;
-    if (ws < 4 || H % ws || W % ws || wse < ws || (ws * ws) % 16) return HAT_EINVAL;
+    if (const int rc = attn_check(q && kv && bias_rot && out, B, C, heads, ldq, ldkv, ldo,
+                                  [&] { return !(ws < 4 || H % ws || W % ws || wse < ws || (ws * ws) % 16); }))
+        return rc;
     const int d = C / heads;
-    if (d > 32 || d % 2 || ldq < C || ldkv < 2 * C || ldo < C) return HAT_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool fast24 = d == 24 && ldq % 8 == 0 && ldkv % 8 == 0 && ldo % 4 == 0 && C % 8 == 0;
     const bool fast30 = d == 30 && ldq % 2 == 0 && ldkv % 2 == 0 && ldo % 2 == 0 && C % 2 == 0;
     if (dtype == HAT_BF16 && ws == 16 && wse == 24 && (fast24 || fast30)) {
+        // (always above 64 KiB: the limit is raised on every call)
         const size_t lds = (size_t)576 * ((fast24 && !qlog2) ? 24 : 32) * 2 + (size_t)576 * 32 * 2 + (size_t)39 * 39 * 4;
         if (qlog2 && !fast24) return HAT_EUNSUPPORTED;
         auto kern = fast24 ? (qlog2 ? ocab_attn_fast_kernel<24, 24, false, 512, true> : ocab_attn_fast_kernel<24, 24, false, 512>)
                            : ocab_attn_fast_kernel<30, 24, false, 512>;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
         const int nwin = B * (W / ws) * (H / ws);
-        HAT_LAUNCH(kern, dim3((nwin + 7) / 8 * 8 * heads), dim3(512), lds, s, reinterpret_cast<const bf16_t*>(q),
-                   reinterpret_cast<const bf16_t*>(kv), bias_rot, reinterpret_cast<bf16_t*>(out), B, H, W, C, heads, ldq, ldkv, ldo, 0);
-        return hat_check_launch();
+        return attn_launch(kern, dim3((nwin + 7) / 8 * 8 * heads), 512, lds, s, reinterpret_cast<const bf16_t*>(q),
+                           reinterpret_cast<const bf16_t*>(kv), bias_rot, reinterpret_cast<bf16_t*>(out), B, H, W, C, heads, ldq, ldkv, ldo, 0);
     }
     if (qlog2) return HAT_EUNSUPPORTED;   // only the tuned kernel takes log2-domain queries
-    return attn_dispatch(q, kv, bias_rot, out, B, H, W, C, heads, ws, wse, ldq, ldkv, ldo, dtype, s, nullptr, -1);
+    return attn_dispatch<false>(AttnArgs{q, kv, bias_rot, out, B, H, W, C, heads, ws, wse, ldq, ldkv, ldo, s, 0, nullptr, -1}, dtype);
 }
 
 extern "C" int hat_ocab_attention(const void* q, const void* kv, const float* bias_rot, void* out, int32_t B, int32_t H,
@@ -897,43 +872,33 @@ extern "C" int hat_ocab_keybias(const void* sal, int32_t ldsal, const void* kv, 
 extern "C" int hat_ocab_attention_kb(const void* q, const void* kv, const float* bias_rot, const float* kb, void* out, int32_t B, int32_t H,
                                      int32_t W, int32_t C, int32_t heads, int32_t ws, int32_t wse, int32_t pad, int32_t ldq, int32_t ldkv,
                                      int32_t ldo, int32_t dtype, void* stream) {
-    if (!q || !kv || !bias_rot || !kb || !out || B < 1 || heads < 1 || C % heads) return HAT_EINVAL;
-    if (ws < 4 || H % ws || W % ws || wse < ws || (ws * ws) % 16 || pad != (wse - ws + 1) / 2) return HAT_EINVAL;
-    const int d = C / heads;
-    if (d > 32 || d % 2 || ldq < C || ldkv < 2 * C || ldo < C) return HAT_EINVAL;
-    return attn_dispatch(q, kv, bias_rot, out, B, H, W, C, heads, ws, wse, ldq, ldkv, ldo, dtype, reinterpret_cast<hipStream_t>(stream), kb, pad);
+    if (const int rc = attn_check(q && kv && bias_rot && kb && out, B, C, heads, ldq, ldkv, ldo, [&] {
+            return !(ws < 4 || H % ws || W % ws || wse < ws || (ws * ws) % 16 || pad != (wse - ws + 1) / 2);
+        }))
+        return rc;
+    return attn_dispatch<false>(
+        AttnArgs{q, kv, bias_rot, out, B, H, W, C, heads, ws, wse, ldq, ldkv, ldo, reinterpret_cast<hipStream_t>(stream), 0, kb, pad}, dtype);
 }
 
 extern "C" int hat_window_attention(const void* q, const void* kv, const float* bias_flip, void* out, int32_t B, int32_t H,
                                     int32_t W, int32_t C, int32_t heads, int32_t ws, int32_t shift, int32_t ldq,
                                     int32_t ldkv, int32_t ldo, int32_t dtype, void* stream) {
-    if (!q || !kv || !bias_flip || !out || B < 1 || heads < 1 || C % heads) return HAT_EINVAL;
-    if (ws < 4 || ws % 4 || H % ws || W % ws || shift < 0 || shift >= ws || shift % 4) return HAT_EINVAL;
+    if (const int rc = attn_check(q && kv && bias_flip && out, B, C, heads, ldq, ldkv, ldo,
+                                  [&] { return !(ws < 4 || ws % 4 || H % ws || W % ws || shift < 0 || shift >= ws || shift % 4); }))
+        return rc;
     const int d = C / heads;
-    if (d > 32 || d % 2 || ldq < C || ldkv < 2 * C || ldo < C) return HAT_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool fast24 = d == 24 && ldq % 8 == 0 && ldkv % 8 == 0 && ldo % 4 == 0 && C % 8 == 0 &&
                         (reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kv)) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0;
     const bool fast30 = d == 30 && ldq % 2 == 0 && ldkv % 2 == 0 && ldo % 2 == 0 && C % 2 == 0;
     if (dtype == HAT_BF16 && ws == 16 && (fast24 || fast30)) {
+        // (36 612 B at most: the limit is never raised)
         const size_t lds = (size_t)256 * (fast24 ? 24 : 32) * 2 + (size_t)256 * 32 * 2 + (size_t)31 * 31 * 4;
         auto kern = fast24 ? ocab_attn_fast_kernel<24, 16, true> : ocab_attn_fast_kernel<30, 16, true>;
         const int nwin = B * (W / ws) * (H / ws);
-        HAT_LAUNCH(kern, dim3((nwin + 7) / 8 * 8 * heads), dim3(256), lds, s, reinterpret_cast<const bf16_t*>(q),
-                   reinterpret_cast<const bf16_t*>(kv), bias_flip, reinterpret_cast<bf16_t*>(out), B, H, W, C, heads, ldq, ldkv,
-                   ldo, shift);
-        return hat_check_launch();
+        return attn_launch(kern, dim3((nwin + 7) / 8 * 8 * heads), 256, lds, s, reinterpret_cast<const bf16_t*>(q),
+                           reinterpret_cast<const bf16_t*>(kv), bias_flip, reinterpret_cast<bf16_t*>(out), B, H, W, C, heads, ldq, ldkv,
+                           ldo, shift);
     }
-#define HAT_WATTN_CASE(TT, N, K) return launch_attn<TT, N, K, true>(q, kv, bias_flip, out, B, H, W, C, heads, ws, ws, ldq, ldkv, ldo, s, shift)
-    if (dtype == HAT_BF16) {
-        if (ws == 16) HAT_WATTN_CASE(bf16_t, 16, 8);
-        if (ws == 8) HAT_WATTN_CASE(bf16_t, 4, 4);
-    } else if (dtype == HAT_F32) {
-        if (ws == 16) HAT_WATTN_CASE(float, 16, 8);
-        if (ws == 8) HAT_WATTN_CASE(float, 4, 4);
-    } else {
-        return HAT_EINVAL;
-    }
-#undef HAT_WATTN_CASE
-    return HAT_EUNSUPPORTED;  // window sizes other than 16 and 8 are not instantiated
+    return attn_dispatch<true>(AttnArgs{q, kv, bias_flip, out, B, H, W, C, heads, ws, ws, ldq, ldkv, ldo, s, shift, nullptr, -1}, dtype);
 }

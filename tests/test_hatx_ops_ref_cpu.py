@@ -119,6 +119,20 @@ def test_attention_kb_refuses_a_pad_that_is_not_the_ceiling(lib):
                 assert call(ws, wse, pad, dt) == EINVAL
 
 
+def test_attention_refuses_a_key_window_that_neither_fits_nor_streams(lib):
+    """fp32, 24 x 24 queries and keys, d = 32: K + V^T take 82 944 + 74 240 B and the 47 x 47 table 8 836 B, 166 020 B in all
+    against 163 840 B of LDS, and only 16 x 16 query windows stream: HAT_ELDS.  A 17 x 17 key window has no instantiation."""
+    lib, L = lib
+    ELDS, EUNSUPPORTED = -2, -3   # include/hat_mi355x.h
+    plain = lambda ws, wse, dt: lib.hat_ocab_attention(P[0], P[1], P[2], P[4], 1, 48, 48, 64, 2, ws, wse, 64, 128, 64, dt, None)
+    kb = lambda ws, wse, dt: lib.hat_ocab_attention_kb(P[0], P[1], P[2], P[3], P[4], 1, 48, 48, 64, 2, ws, wse, (wse - ws + 1) // 2,
+                                                       64, 128, 64, dt, None)
+    for call in (plain, kb):
+        assert call(24, 24, L.HAT_F32) == ELDS
+        for dt in (L.HAT_F32, L.HAT_BF16):
+            assert call(16, 17, dt) == EUNSUPPORTED
+
+
 def test_sgfn_gate_refuses_bad_arguments(lib):
     lib, L = lib
     call = lambda u, out, half, ldu, ldo, dt: lib.hat_sgfn_gate(u, P[1], P[2], out, 1, 8, 8, half, ldu, ldo, dt, None)
