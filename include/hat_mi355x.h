@@ -120,6 +120,17 @@ int hat_conv_tiles(const HatConvDesc* d, int32_t* tiles_out);
  * LDS bytes.  The kernel instantiation is conv_kernel<T, waves, rows_per_wave, nt> (used to label profiles). */
 int hat_conv_plan(const HatConvDesc* d, int32_t* waves, int32_t* rows_per_wave, int32_t* tiles, int64_t* lds_bytes);
 int hat_conv(const HatConvDesc* d, void* stream);
+/*
+ * hat_conv with the FP16-range guard of the residual stream.  A launch that stores FP16 rows (reserved0 bit 1) clamps what lies
+ * beyond +-65504 and, by itself, records nothing.  The guarded launch stores the same bytes into every output and also watches
+ * the fp32 values it converts, before the clamp, at the pixels it stores (not at the pixels of a ragged tile beyond H or W):
+ * if one has a magnitude above 65504, or is an infinity or a NaN, *sat is raised (atomic maximum, as an unsigned integer) to the
+ * fp32 bit pattern of its magnitude.  The caller zeroes *sat; a word that is still 0 after the launches of a forward says that
+ * no FP16 store of that forward clipped, any other word is the largest offending magnitude (a NaN's pattern above all).
+ * sat: device memory, 4-byte aligned.  sat == NULL: hat_conv.  With sat set, a descriptor that stores no FP16 rows (reserved0
+ * bit 1 clear) or a misaligned sat returns HAT_EINVAL.  Forward plans record hat_conv, never this entry.
+ */
+int hat_conv_guarded(const HatConvDesc* d, uint32_t* sat, void* stream);
 
 /*
  * Pointwise linear layer (ksize == 1, channel-last T input, HAT_O_NHWC_T / HAT_O_NHWC_F32 output, same epilogue
@@ -130,6 +141,12 @@ int hat_conv(const HatConvDesc* d, void* stream);
  * Returns HAT_EUNSUPPORTED for (nt, Cin) pairs that are not instantiated: call hat_conv instead.
  */
 int hat_linear(const HatConvDesc* d, void* stream);
+/*
+ * hat_linear with the FP16-range guard: hat_conv_guarded's contract for the launch that stores FP16 rows (reserved0 bit 1: the
+ * OCAB projection).  Lanes beyond the last pixel re-store the last pixel and count its values again; nothing else is counted.
+ * sat == NULL: hat_linear.  reserved0 bit 1 clear with sat set, or a misaligned sat: HAT_EINVAL.
+ */
+int hat_linear_guarded(const HatConvDesc* d, uint32_t* sat, void* stream);
 
 /*
  * 3x3 convolution (zero padding 1) whose whole weight slice fits in LDS — the two CAB convolutions
@@ -789,6 +806,13 @@ int hat_hab_tail(const HatHabTailDesc* d, void* stream);
  * w_aggr fragment packed [12][6][64][8], bias_b a 1 KiB record [256] (zero padded), r2 / r2scale as below; c1 and wf are ignored.
  */
 int hat_hab_tail3(const HatHabTailDesc* d, void* stream);
+/*
+ * hat_hab_tail3 with the FP16-range guard: hat_conv_guarded's contract for an FP16 t_out (reserved1 bit 1, embed_dim 144).  The
+ * values watched are the fp32 t_out of the pixels inside the image, before the clamp; the LayerNorm rows, the compact copy and
+ * the pool partials are not part of it (they are computed from the unclamped values anyway).  sat == NULL: hat_hab_tail3.
+ * With sat set: reserved1 bit 1 clear, embed_dim 180 (which has no FP16 stream) or a misaligned sat return HAT_EINVAL.
+ */
+int hat_hab_tail3_guarded(const HatHabTailDesc* d, uint32_t* sat, void* stream);
 
 /*
  * Forward plans — the whole network behind three calls, for hosts without Python (SURVEY §8b's hat_forward(handle ...)).

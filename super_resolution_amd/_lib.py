@@ -140,6 +140,10 @@ SIGNATURES = {
                                 C.POINTER(C.c_int64)]),
     "hat_conv": (C.c_int, [C.POINTER(HatConvDesc), C.c_void_p]),
     "hat_linear": (C.c_int, [C.POINTER(HatConvDesc), C.c_void_p]),
+    # the FP16-range guard: the launch, then the uint32 device slot, then the stream
+    "hat_conv_guarded": (C.c_int, [C.POINTER(HatConvDesc), C.c_void_p, C.c_void_p]),
+    "hat_linear_guarded": (C.c_int, [C.POINTER(HatConvDesc), C.c_void_p, C.c_void_p]),
+    "hat_hab_tail3_guarded": (C.c_int, [C.POINTER(HatHabTailDesc), C.c_void_p, C.c_void_p]),
     "hat_conv3x3_small_groups": (C.c_int, [C.POINTER(HatConvDesc), C.POINTER(C.c_int32)]),
     "hat_conv3x3_small": (C.c_int, [C.POINTER(HatConvDesc), C.c_void_p]),
     "hat_cab_fold": (C.c_int, [C.POINTER(HatCabFoldDesc), C.c_void_p]),

@@ -527,12 +527,23 @@ class HAT(nn.Module):
     def _forward_graph(self, x):
         """Replay the whole forward (about 290 launches on two streams) as one HIP graph: captured once per input
         shape after two eager warm-up passes, input copied into the graph's static buffer, output copied out of it.
-        Removes the host launch path and most inter-kernel gaps; matters most for small frames / tiles."""
+        Removes the host launch path and most inter-kernel gaps; matters most for small frames / tiles.
+        The FP16-range guard of HATEngine's residual stream: the guarded launches and the copy of the guard's word
+        are part of the graph; the engine zeroes the word before a replay and looks at it behind one, as around an eager
+        forward.  Whether the stream is FP16 is part of the cache key: after a fallback the shape is captured again on the fp32
+        plan, and the graphs of the old plan are dropped."""
         eng = self.engine(x.device)
         if self._graph_engine is not eng:
             self._graphs, self._graph_engine = collections.OrderedDict(), eng
-        key = (tuple(x.shape), x.dtype)
+        guarded = getattr(eng, "_guard", None) is not None
         with torch.cuda.device(x.device):
+            if guarded:
+                with eng._lock:
+                    eng._guard_begin()          # (may find that an earlier frame clipped, and leave the FP16 stream)
+            t16 = bool(getattr(eng, "t16", False))
+            key = (tuple(x.shape), x.dtype, t16, guarded and eng.t16_guard != "off")   # (a graph holds guarded launches or it does not)
+            for k in [k for k in self._graphs if k[2] != t16]:
+                del self._graphs[k]
             ent = self._graphs.get(key)
             if ent is None:
                 sx = x.detach().clone()
@@ -543,6 +554,8 @@ class HAT(nn.Module):
                     for _ in range(2):
                         eng.forward(sx)
                 cur.wait_stream(side)
+                if bool(getattr(eng, "t16", False)) != t16:   # (a warm-up pass fell back: capture the new plan)
+                    return self._forward_graph(x)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     sy = eng.forward(sx)
@@ -551,12 +564,23 @@ class HAT(nn.Module):
                 ent = self._graphs[key] = (g, sx, sy, eng._workspace(*x.shape[:1], *x.shape[2:]))
                 while len(self._graphs) > self._graph_max:
                     self._graphs.popitem(last=False)
+                if guarded:
+                    with eng._lock:
+                        eng._guard_begin()      # (the warm-up passes ended their own brackets)
+                    if bool(getattr(eng, "t16", False)) != t16:   # (their word was looked at here and the engine fell back: the
+                        return self._forward_graph(x)             # graph just captured is of the old plan — capture the new one)
             else:
                 self._graphs.move_to_end(key)
             g, sx, sy, _ = ent
             sx.copy_(x)
             g.replay()
-            return sy.to(x.dtype, copy=True)
+            y = sy.to(x.dtype, copy=True)
+            if guarded:
+                with eng._lock:
+                    again = eng._guard_end()    # "sync": waits; True: this frame clipped and the engine has fallen back
+                if again:
+                    return self._forward_graph(x)
+            return y
 
 
 @ARCH_REGISTRY.register()

@@ -180,8 +180,13 @@ def forward_bands_local(engine, x: torch.Tensor, n: int) -> torch.Tensor:
 
     with engine._lock, torch.cuda.device(engine.dev):
         x = x.to(torch.float32)
+        # the FP16-range guard (HATEngine): every band raises the engine's one word; "defer" whatever the mode — the
+        # word is looked at by the next forward or by resolve_t16_guard
+        guard = getattr(engine, "_guard_begin", None) is not None and engine._guard_begin()
         gens = [engine._forward_gen(x[:, :, b.e0:b.e1].contiguous(), band=b) for b in bands]
         ys = run_lockstep(gens, bands, B, add)
+        if guard:
+            engine._guard_end(defer=True)
         out = torch.empty(B, x.shape[1], H * s, W * s, dtype=torch.float32, device=x.device)
         for b, y in zip(bands, ys):
             out[:, :, b.r0 * s:b.r1 * s] = y[:, :, b.lo * s:(b.lo + b.own) * s]
@@ -261,6 +266,7 @@ def forward_band_distributed(engine, x: torch.Tensor, group=None, stage_on_host:
     bands = make_bands(H, world, engine.ws, halo=engine.band_halo())
     band, s = bands[rank], engine.scale
     with engine._lock, torch.cuda.device(engine.dev):
+        # (no FP16-range guard here: ranks that fell back one by one would exchange halo rows of two types)
         gen = engine._forward_gen(x.to(torch.float32)[:, :, band.e0:band.e1].contiguous(), band=band)
         y = run_distributed(gen, band, bands, B, group, stage_on_host)
         mh = max(b.own for b in bands) * s

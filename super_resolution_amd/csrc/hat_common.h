@@ -192,6 +192,33 @@ __device__ __forceinline__ void store_h4(_Float16* p, f32x4 v) {
     *reinterpret_cast<v4*>(p) = v4{c(v[0]), c(v[1]), c(v[2]), c(v[3])};
 }
 
+// ---- the FP16-range guard of the residual stream (hat_hab_tail3_guarded, hat_conv_guarded, hat_linear_guarded) ----
+// The guarded form of a kernel that stores FP16 rows takes one more argument, `unsigned* sat`, as a template parameter pack
+// beside TH: the pack is empty in the unguarded instantiations, whose signature, arguments and code are what they were.
+template <typename... S> __device__ __forceinline__ unsigned* sat_arg(S... s) {
+    static_assert(sizeof...(S) <= 1, "at most one guard slot");
+    if constexpr (sizeof...(S) == 1) return (s, ...);
+    else return nullptr;
+}
+// Running maximum of |v| over the fp32 values a lane is about to convert: two v_maximum3_f32 with abs modifiers per four
+// values.  The IEEE-754-2019 maximum, not fmax: a NaN stays a NaN.
+__device__ __forceinline__ float sat_max4(float m, f32x4 v) {
+    m = __builtin_elementwise_maximum(__builtin_elementwise_maximum(m, __builtin_fabsf(v[0])), __builtin_fabsf(v[1]));
+    return __builtin_elementwise_maximum(__builtin_elementwise_maximum(m, __builtin_fabsf(v[2])), __builtin_fabsf(v[3]));
+}
+// After the stores: m = the lane's maximum (>= 0, or a NaN).  !(m <= 65504) holds for a larger magnitude, an infinity and a
+// NaN.  In range — no lane of the wave trips — this is one compare and one branch.  Otherwise the wave reduces the bit patterns
+// (as unsigned they order like the magnitudes, a NaN above the infinity) and ONE lane raises *sat to the largest with a global
+// atomic; *sat keeps the largest over all waves and launches since it was last zeroed.  All 64 lanes must be active.
+__device__ __forceinline__ void sat_report(unsigned* sat, float m, int lane) {
+    if (__builtin_amdgcn_ballot_w64(!(m <= 65504.0f)) != 0) {
+        unsigned u = __float_as_uint(m) & 0x7fffffffu;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, off));
+        if (lane == 0) atomicMax(sat, u);
+    }
+}
+
 // LDS row stride (in elements) for rows of `n` elements of size `es`, for MFMA operand images read by ds_read_b128
 // with lane (c16, g) -> row base + c16, 16-byte slot k0 + g (bf16) or k0 + 2g (+1) (f32).  The instruction is serviced
 // in the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, {32-35,...}: rows 0-3 and 12-15 of lane group g together

@@ -63,8 +63,12 @@ __host__ inline bool conv_pick(const HatConvDesc& d, TileCfg* out, size_t* lds) 
 
 // TH: the residual stream's type in the epilogue (hat_conv's reserved0 flags; bf16 group conv only) — bit 0: r1 is FP16 rows,
 // bit 1: the HAT_O_NHWC_F32 output is stored as FP16 rows (round to nearest, clamped to +-65504).  Else fp32.
-template <typename T, int WAVES, int PT, int NT, int TH = 0>
-__global__ __launch_bounds__(WAVES * 64) void conv_kernel(const HatConvDesc d) {
+// SAT: empty, or `unsigned*` — the guarded form (TH & 2 only; hat_conv_guarded): the FP16 stores also keep the maximum of |v| over the
+// values of the pixels they store and report a value beyond the FP16 range to that slot (sat_report, hat_common.h).
+template <typename T, int WAVES, int PT, int NT, int TH = 0, typename... SAT>
+__global__ __launch_bounds__(WAVES * 64) void conv_kernel(const HatConvDesc d, SAT... sat) {
+    constexpr bool GUARD = sizeof...(SAT) == 1;
+    static_assert(!GUARD || (TH & 2) != 0, "the guard watches FP16 stores");
     using M = MT<T>;
     constexpr int NTHR = WAVES * 64;
     constexpr int TROWS = WAVES * PT;
@@ -429,6 +433,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_kernel(const HatConvDesc d) {
             // FP16 rows (host checks: one slice, every channel stored, no column sums, 16-byte rows): n-tile pairs leave as one
             // 16-byte store per lane, the odd last tile as an 8-byte one.  The fused LayerNorm below reads the unrounded fp32
             // values, as hat_hab_tail3 does with its FP16 t_out.
+            float smax = 0.f;   // GUARD: the largest |v| this lane stores (pixels inside the image only)
 #pragma unroll
             for (int pt = 0; pt < PT; ++pt) {
                 const int y = y0 + wave * PT + pt, x = x0 + c16;
@@ -439,7 +444,14 @@ __global__ __launch_bounds__(WAVES * 64) void conv_kernel(const HatConvDesc d) {
                 if constexpr ((NT & 1) != 0) {
                     if (valid) store_h4(orow + (NT - 1) * 16 + 4 * g, acc[NT - 1][pt]);
                 }
+                if constexpr (GUARD) {
+                    float mp = 0.f;
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) mp = sat_max4(mp, acc[nt][pt]);
+                    smax = __builtin_elementwise_maximum(smax, valid ? mp : 0.f);
+                }
             }
+            if constexpr (GUARD) sat_report(sat_arg(sat...), smax, lane);
         } else if constexpr (TWO_PASS) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
@@ -534,9 +546,10 @@ __global__ __launch_bounds__(WAVES * 64) void conv_kernel(const HatConvDesc d) {
 
 int* g_occ_query = nullptr;   // hat_conv_occupancy: when set, launch_conv reports workgroups per CU instead of launching
 
-template <typename T, int WAVES, int PT, int NT, int TH = 0>
-int launch_conv(const HatConvDesc& d, size_t lds, hipStream_t stream) {
-    auto kern = conv_kernel<T, WAVES, PT, NT, TH>;
+// More: the guarded form's slot (conv_kernel<.., TH, unsigned*>)
+template <typename T, int WAVES, int PT, int NT, int TH = 0, typename... More>
+int launch_conv(const HatConvDesc& d, size_t lds, hipStream_t stream, More... more) {
+    auto kern = conv_kernel<T, WAVES, PT, NT, TH, More...>;
     if (g_occ_query != nullptr) {
         if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(g_occ_query, kern, WAVES * 64, lds);
@@ -549,12 +562,19 @@ int launch_conv(const HatConvDesc& d, size_t lds, hipStream_t stream) {
     HatConvDesc dd = d;
     // stagger (kernel side: see conv_kernel): only for launches that keep every CU busy for several rounds of ONE workgroup each
     dd.reserved0 = (lds > HAT_LDS_MAX / 2 && (size_t)grid.x * grid.y * grid.z >= 1024) ? 2 : 0;
-    HAT_LAUNCH(kern, grid, dim3(WAVES * 64), lds, stream, dd);
+    HAT_LAUNCH(kern, grid, dim3(WAVES * 64), lds, stream, dd, more...);
     return hat_check_launch();
 }
 
 template <typename T, int WAVES, int PT>
-int dispatch_nt(const HatConvDesc& d, size_t lds, hipStream_t s) {
+int dispatch_nt(const HatConvDesc& d, size_t lds, hipStream_t s, unsigned* sat) {
+    if (sat != nullptr) {   // hat_conv_guarded checked: reserved0 bit 1, so (conv_validate) the bf16 group conv of nine n-tiles
+        if constexpr (sizeof(T) == 2) {
+            if (d.nt == 9 && d.reserved0 == 2) return launch_conv<T, WAVES, PT, 9, 2>(d, lds, s, sat);
+            if (d.nt == 9 && d.reserved0 == 3) return launch_conv<T, WAVES, PT, 9, 3>(d, lds, s, sat);
+        }
+        return HAT_EINVAL;
+    }
     switch (d.nt) {
         case 1: return launch_conv<T, WAVES, PT, 1>(d, lds, s);
         case 4: return launch_conv<T, WAVES, PT, 4>(d, lds, s);
@@ -575,10 +595,10 @@ int dispatch_nt(const HatConvDesc& d, size_t lds, hipStream_t s) {
 }
 
 template <typename T>
-int dispatch_tile(const HatConvDesc& d, TileCfg tc, size_t lds, hipStream_t s) {
-    if (tc.waves == 8 && tc.pt == 2) return dispatch_nt<T, 8, 2>(d, lds, s);
-    if (tc.waves == 4 && tc.pt == 2) return dispatch_nt<T, 4, 2>(d, lds, s);
-    return dispatch_nt<T, 4, 1>(d, lds, s);
+int dispatch_tile(const HatConvDesc& d, TileCfg tc, size_t lds, hipStream_t s, unsigned* sat = nullptr) {
+    if (tc.waves == 8 && tc.pt == 2) return dispatch_nt<T, 8, 2>(d, lds, s, sat);
+    if (tc.waves == 4 && tc.pt == 2) return dispatch_nt<T, 4, 2>(d, lds, s, sat);
+    return dispatch_nt<T, 4, 1>(d, lds, s, sat);
 }
 
 int conv_validate(const HatConvDesc& d) {
@@ -663,16 +683,21 @@ extern "C" int hat_conv_occupancy(const HatConvDesc* dp, int32_t* wgs_per_cu) {
     return rc;
 }
 
-extern "C" int hat_conv(const HatConvDesc* dp, void* stream) {
+// hat_conv (sat == nullptr) and hat_conv_guarded
+static int conv_entry(const HatConvDesc* dp, unsigned* sat, void* stream) {
     if (!dp) return HAT_EINVAL;
     const HatConvDesc& d = *dp;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (sat && (reinterpret_cast<uintptr_t>(sat) % 4 || !(d.reserved0 & 2) || d.out_mode != HAT_O_NHWC_F32)) return HAT_EINVAL;   // FP16 rows only
     if (d.out_mode == HAT_O_FOLD2_NCHW_F32) return hat_upfold_launch_desc(d, s);   // the folded ending: its own kernel and checks
     int rc = conv_validate(d);
     if (rc) return rc;
     TileCfg tc; size_t lds;
-    if (hat_conv64r_can_launch(d)) return hat_conv64r_launch(d, s);
+    if (!sat && hat_conv64r_can_launch(d)) return hat_conv64r_launch(d, s);
     if (!conv_pick(d, &tc, &lds)) return HAT_ELDS;
-    if (d.dtype == HAT_BF16) return dispatch_tile<bf16_t>(d, tc, lds, s);
-    return dispatch_tile<float>(d, tc, lds, s);
+    if (d.dtype == HAT_BF16) return dispatch_tile<bf16_t>(d, tc, lds, s, sat);
+    return dispatch_tile<float>(d, tc, lds, s, sat);
 }
+
+extern "C" int hat_conv(const HatConvDesc* dp, void* stream) { return conv_entry(dp, nullptr, stream); }
+extern "C" int hat_conv_guarded(const HatConvDesc* dp, uint32_t* sat, void* stream) { return conv_entry(dp, sat, stream); }

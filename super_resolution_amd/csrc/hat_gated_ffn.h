@@ -72,12 +72,14 @@ inline bool hat_ln1_args_ok(const HatFfnDesc& d) {
     return !d.ln1_g || (d.ln1_b && d.n_out && d.ldn >= d.C && d.ldn % 4 == 0 && d.gap_c >= 0 && d.gap_c <= 16 && d.gap_c % 4 == 0);
 }
 // one 256-thread workgroup per 16 x `rows` pixel tile and sample, `lds` bytes of dynamic LDS
-template <typename Aggr>
-int hat_tail_launch(void (*kern)(const HatFfnDesc, const Aggr), int lds, int rows, const HatFfnDesc& d, const Aggr& ag, void* stream) {
+// (more...: the guarded form's slot, hat_tail3.hip)
+template <typename Aggr, typename... More>
+int hat_tail_launch(void (*kern)(const HatFfnDesc, const Aggr, More...), int lds, int rows, const HatFfnDesc& d, const Aggr& ag, void* stream,
+                    More... more) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
     dim3 grid((d.W + 15) / 16, (d.H + rows - 1) / rows, d.B);
-    HAT_LAUNCH(kern, grid, dim3(256), lds, reinterpret_cast<hipStream_t>(stream), d, ag);
+    HAT_LAUNCH(kern, grid, dim3(256), lds, reinterpret_cast<hipStream_t>(stream), d, ag, more...);
     return hat_check_launch();
 }
 

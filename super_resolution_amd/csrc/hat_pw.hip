@@ -27,8 +27,13 @@ template <bool SPEC_, bool R1_, bool R2_, bool OUTF32_, bool LN_, bool PAIR_ = f
 // TH (RES only; hat_linear's reserved0 flags): bit 0 — r1 is FP16 rows, bit 1 — the HAT_O_NHWC_F32 output is stored as FP16
 // rows (round to nearest, clamped to +-65504; the fused LayerNorm reads the unrounded fp32 values, like hat_hab_tail3).  Only
 // the specialised copies of an fp32-output, r1-only launch (the OCAB projection) are instantiated with TH != 0.
-template <typename T, int NT, int KS, int WAVES, int MINW, bool RES, int TH = 0>
-__global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc d, long npix_total, int tiles, int scale_in_lds) {
+// SAT: empty, or `unsigned*` — the guarded form (TH & 2 only; hat_linear_guarded): a wave keeps the maximum of |v| over the values it
+// stores as FP16 rows, over all its tiles, and reports a value beyond the FP16 range to that slot when its tile loop ends (sat_report,
+// hat_common.h).  A lane past the last pixel re-stores the last pixel: it counts that pixel's values again.
+template <typename T, int NT, int KS, int WAVES, int MINW, bool RES, int TH = 0, typename... SAT>
+__global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc d, long npix_total, int tiles, int scale_in_lds, SAT... sat) {
+    constexpr bool GUARD = sizeof...(SAT) == 1;
+    static_assert(!GUARD || (TH & 2) != 0, "the guard watches FP16 stores");
     using M = MT<T>;
     using frag_t = typename M::frag_t;
     constexpr int KSMAX = KS;
@@ -154,6 +159,7 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc 
         load_b(tile + stride, bnxt);
         if constexpr (DEEP) load_b(tile + 2 * stride, bnx2);
         load_r(tile, r1v, r2v);
+        float smax = 0.f;   // GUARD: the largest |v| this lane has stored as FP16
         for (; tile < tiles; tile += stride) {
             const long p = tile * 16 + c16;
             const long pc = p < npix_total ? p : npix_total - 1;
@@ -216,6 +222,10 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc 
 #pragma unroll
                 for (int nt = 0; nt + 1 < NT; nt += 2) store_pair_f16_if(orow, nt * 16, g, acc[nt], acc[nt + 1], true);
                 if constexpr (NT & 1) store_h4(orow + (NT - 1) * 16 + 4 * g, acc[NT - 1]);
+                if constexpr (GUARD) {
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) smax = sat_max4(smax, acc[nt]);
+                }
             } else if (SPEC || p < npix_total) {
                 const long ps = SPEC ? pc : p;
 #pragma unroll
@@ -231,7 +241,10 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc 
                     }
                     if (SPEC || n < d.n_store) {
                         if (!out_f32) Vec4<T>::store(reinterpret_cast<T*>(d.out) + ps * d.ldo + n, v);
-                        else if constexpr ((TH & 2) != 0) store_h4(reinterpret_cast<_Float16*>(d.out) + ps * d.ldo + n, v);
+                        else if constexpr ((TH & 2) != 0) {
+                            store_h4(reinterpret_cast<_Float16*>(d.out) + ps * d.ldo + n, v);
+                            if constexpr (GUARD) smax = sat_max4(smax, v);   // (v: what is stored, also for a partial last tile)
+                        }
                         else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(d.out) + ps * d.ldo + n) = v;
                     }
                 }
@@ -312,6 +325,7 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc 
             else load_b(tile + 2 * stride, bnxt);
             load_r(tile + stride, r1v, r2v);
         }
+        if constexpr (GUARD) sat_report(sat_arg(sat...), smax, lane);
     };
 
     // specialised copies need: one slice that stores all NT*16 channels, no split source oddities beyond load_b's, and
@@ -341,23 +355,24 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void pw_kernel(const HatConvDesc 
     }
 }
 
-template <typename T, int NT, int KS, int WAVES, int MINW, bool RES, int TH = 0>
-int launch_pw_cfg(const HatConvDesc& d, hipStream_t s, size_t lds, int wgs_per_cu, int scale_in_lds) {
+// More: the guarded form's slot (pw_kernel<.., TH, unsigned*>)
+template <typename T, int NT, int KS, int WAVES, int MINW, bool RES, int TH = 0, typename... More>
+int launch_pw_cfg(const HatConvDesc& d, hipStream_t s, size_t lds, int wgs_per_cu, int scale_in_lds, More... more) {
     const long npix = (long)d.B * d.H * d.W;
     const int tiles = (int)((npix + 15) / 16);
     int gx = 256 * wgs_per_cu;   // tests/test_gpu_multitrip.py: PW_TRIP_TILES = 256 * wgs_per_cu * WAVES (2048 or 3072)
     if (gx > (tiles + WAVES - 1) / WAVES) gx = (tiles + WAVES - 1) / WAVES;
-    auto kern = pw_kernel<T, NT, KS, WAVES, MINW, RES, TH>;
+    auto kern = pw_kernel<T, NT, KS, WAVES, MINW, RES, TH, More...>;
     if (lds > 65536) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
-    HAT_LAUNCH(kern, dim3(gx, d.n_slices, 1), dim3(WAVES * 64), lds, s, d, npix, tiles, scale_in_lds);
+    HAT_LAUNCH(kern, dim3(gx, d.n_slices, 1), dim3(WAVES * 64), lds, s, d, npix, tiles, scale_in_lds, more...);
     return hat_check_launch();
 }
 
 template <typename T, int NT, int KS>
-int launch_pw(const HatConvDesc& d, hipStream_t s) {
+int launch_pw(const HatConvDesc& d, hipStream_t s, unsigned* sat) {
     size_t lds = (size_t)NT * KS * 64 * 8 * sizeof(T) + (size_t)NT * 16 * sizeof(float);  // fragments (64 lanes x 8) + bias
     if (lds > HAT_LDS_MAX) return HAT_EUNSUPPORTED;
     const bool res = d.r1 != nullptr || d.r2 != nullptr;
@@ -376,6 +391,10 @@ int launch_pw(const HatConvDesc& d, hipStream_t s) {
     // residual variant keeps a tile's residual operands in registers and is sized for 2
     wgs_per_cu = wgs_per_cu > (res ? 2 : 3) ? (res ? 2 : 3) : wgs_per_cu;
     if constexpr (NT == 9 && KS == 5 && sizeof(T) == 2) {   // FP16 residual stream (reserved0; the OCAB projection at C = 144)
+        if (sat != nullptr && wgs_per_cu == 2) {   // (hat_linear_guarded checked: reserved0 bit 1)
+            if (d.reserved0 == 2) return launch_pw_cfg<T, NT, KS, 4, 2, true, 2>(d, s, lds, 2, scale_in_lds, sat);
+            return launch_pw_cfg<T, NT, KS, 4, 2, true, 3>(d, s, lds, 2, scale_in_lds, sat);
+        }
         if (d.reserved0 != 0 && wgs_per_cu == 2) {
             switch (d.reserved0) {
                 case 1: return launch_pw_cfg<T, NT, KS, 4, 2, true, 1>(d, s, lds, 2, scale_in_lds);
@@ -385,7 +404,7 @@ int launch_pw(const HatConvDesc& d, hipStream_t s) {
             }
         }
     }
-    if (d.reserved0 != 0) return HAT_EINVAL;
+    if (d.reserved0 != 0 || sat != nullptr) return HAT_EINVAL;
     if (wgs_per_cu < 2) return res ? launch_pw_cfg<T, NT, KS, 8, 2, true>(d, s, lds, 1, scale_in_lds) : launch_pw_cfg<T, NT, KS, 8, 2, false>(d, s, lds, 1, 0);
     if (wgs_per_cu == 2) return res ? launch_pw_cfg<T, NT, KS, 4, 2, true>(d, s, lds, 2, scale_in_lds) : launch_pw_cfg<T, NT, KS, 4, 2, false>(d, s, lds, 2, 0);
     return launch_pw_cfg<T, NT, KS, 4, 3, false>(d, s, lds, 3, 0);
@@ -547,9 +566,11 @@ int tap3_dispatch(const HatConvDesc& d, hipStream_t s, int32_t* groups_out) {
 
 }  // namespace
 
-extern "C" int hat_linear(const HatConvDesc* dp, void* stream) {
+// hat_linear (sat == nullptr) and hat_linear_guarded
+static int linear_entry(const HatConvDesc* dp, unsigned* sat, void* stream) {
     if (!dp) return HAT_EINVAL;
     const HatConvDesc& d = *dp;
+    if (sat && (reinterpret_cast<uintptr_t>(sat) % 4 || !(d.reserved0 & 2))) return HAT_EINVAL;   // FP16 rows only
     if (!d.x || !d.w || !d.bias || !d.out || d.ksize != 1 || d.B < 1 || d.H < 1 || d.W < 1 || d.Cin < 4) return HAT_EINVAL;
     if (d.x_mode != HAT_X_NHWC_T || (d.out_mode != HAT_O_NHWC_T && d.out_mode != HAT_O_NHWC_F32)) return HAT_EINVAL;
     if (d.act == HAT_ACT_LRELU02) return HAT_EUNSUPPORTED;   // (hat_conv's own kernel has it)
@@ -568,20 +589,23 @@ extern "C" int hat_linear(const HatConvDesc* dp, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int ks = (d.Cin + 31) / 32;
 #define HAT_PW_CASE(TT)                                                   \
-    if (d.nt == 9 && ks == 5) return launch_pw<TT, 9, 5>(d, s);           \
-    if (d.nt == 18 && ks == 5) return launch_pw<TT, 18, 5>(d, s);         \
-    if (d.nt == 23 && ks == 6) { if constexpr (sizeof(TT) == 2) return launch_pw<TT, 23, 6>(d, s); }  /* 180 -> 360, one slice */ \
-    if (d.nt == 9 && ks == 9) return launch_pw<TT, 9, 9>(d, s);           \
-    if (d.nt == 12 && ks == 6) return launch_pw<TT, 12, 6>(d, s);         \
-    if (d.nt == 12 && ks == 12) return launch_pw<TT, 12, 12>(d, s);       \
-    if (d.nt == 4 && ks == 1) return launch_pw<TT, 4, 1>(d, s);           \
-    if (d.nt == 4 && ks == 2) return launch_pw<TT, 4, 2>(d, s);
+    if (d.nt == 9 && ks == 5) return launch_pw<TT, 9, 5>(d, s, sat);           \
+    if (d.nt == 18 && ks == 5) return launch_pw<TT, 18, 5>(d, s, sat);         \
+    if (d.nt == 23 && ks == 6) { if constexpr (sizeof(TT) == 2) return launch_pw<TT, 23, 6>(d, s, sat); }  /* 180 -> 360, one slice */ \
+    if (d.nt == 9 && ks == 9) return launch_pw<TT, 9, 9>(d, s, sat);           \
+    if (d.nt == 12 && ks == 6) return launch_pw<TT, 12, 6>(d, s, sat);         \
+    if (d.nt == 12 && ks == 12) return launch_pw<TT, 12, 12>(d, s, sat);       \
+    if (d.nt == 4 && ks == 1) return launch_pw<TT, 4, 1>(d, s, sat);           \
+    if (d.nt == 4 && ks == 2) return launch_pw<TT, 4, 2>(d, s, sat);
     if (d.dtype == HAT_BF16) { HAT_PW_CASE(bf16_t) }
     else if (d.dtype == HAT_F32) { HAT_PW_CASE(float) }
     else return HAT_EINVAL;
 #undef HAT_PW_CASE
     return HAT_EUNSUPPORTED;  // shapes not instantiated here: use hat_conv (ksize 1)
 }
+
+extern "C" int hat_linear(const HatConvDesc* dp, void* stream) { return linear_entry(dp, nullptr, stream); }
+extern "C" int hat_linear_guarded(const HatConvDesc* dp, uint32_t* sat, void* stream) { return linear_entry(dp, sat, stream); }
 
 // ---------------------------------------------------------------------------------------------------------
 // hat_aggr_cab (include/hat_mi355x.h): the ESC aggregation 1x1 with the CAB expand conv folded in as three more

@@ -82,8 +82,12 @@ __device__ __attribute__((aligned(16))) unsigned hat_tail3_ones_page[4] = {0x3F8
 // TH: the residual stream's type — bit 0: t_in is FP16 rows, bit 1: t_out is FP16 rows (else fp32).  Between two HABs of a group
 // the stream is read and written by this kernel only; 16 bits there take 4C of a pixel's 12.3C bytes away at 0.1 dB
 // (profiles/r03_residual16_emulation.txt).  FP16, not bf16 (2.9 dB); values are clamped to the finite FP16 range on the way out.
-template <int DBG, int TH = 0>
-__global__ __launch_bounds__(256, 2) void tail3_kernel(const HatFfnDesc d, const T3Aggr ag) {
+// SAT: empty, or `unsigned*` — the guarded form (TH & 2 only; hat_hab_tail3_guarded): the epilogue also keeps the maximum of |v| over
+// the values it stores as FP16 rows and reports a value beyond the FP16 range to that slot (sat_report, hat_common.h).
+template <int DBG, int TH = 0, typename... SAT>
+__global__ __launch_bounds__(256, 2) void tail3_kernel(const HatFfnDesc d, const T3Aggr ag, SAT... sat) {
+    constexpr bool GUARD = sizeof...(SAT) == 1;
+    static_assert(!GUARD || (TH & 2) != 0, "the guard watches FP16 stores");
     constexpr int C = T3_C, NT = T3_NT, KS = T3_KS, NPH = T3_NPH, HALO_W = T3_HW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_char*)smem;
@@ -441,6 +445,7 @@ __global__ __launch_bounds__(256, 2) void tail3_kernel(const HatFfnDesc d, const
     float* tout = d.t_out + (size_t)b * H * W * C;
     const bool do_ln = d.ln1_g != nullptr;
     f32x4 gapv = {0.f, 0.f, 0.f, 0.f};
+    float smax = 0.f;   // GUARD: the largest |v| this lane stores as FP16 (pixels inside the image only)
     f32x4 g1v[NT], bt1v[NT];
     if (do_ln) {
 #pragma unroll
@@ -454,13 +459,15 @@ __global__ __launch_bounds__(256, 2) void tail3_kernel(const HatFfnDesc d, const
         const int y = y0 + 2 * wave + pt, x = x0 + c16;
         const bool valid = y < H && x < W;
         const size_t pix = (size_t)y * W + x;
-        float s = 0.f;
+        float s = 0.f, mp = 0.f;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const f32x4 v = acc2[nt][pt];
             if constexpr (!(TH & 2)) { if (valid) *reinterpret_cast<f32x4*>(tout + pix * C + nt * 16 + 4 * g) = v; }
             s += (v[0] + v[1]) + (v[2] + v[3]);
+            if constexpr (GUARD) mp = sat_max4(mp, v);
         }
+        if constexpr (GUARD) smax = __builtin_elementwise_maximum(smax, valid ? mp : 0.f);
         if constexpr ((TH & 2) != 0) {   // FP16 rows: n-tile pairs as 16-byte stores, the last tile as an 8-byte one
             _Float16* trow = reinterpret_cast<_Float16*>(d.t_out) + ((size_t)b * H * W + pix) * C;
 #pragma unroll
@@ -512,6 +519,7 @@ __global__ __launch_bounds__(256, 2) void tail3_kernel(const HatFfnDesc d, const
             }
         }
     }
+    if constexpr (GUARD) sat_report(sat_arg(sat...), smax, lane);
     if constexpr (DBG & 64) {
         stamp(7);
         if (lane == 0) {
@@ -544,8 +552,10 @@ __global__ __launch_bounds__(256, 2) void tail3_kernel(const HatFfnDesc d, const
 #ifndef HAT_TAIL3_NO_ENTRY
 int hat_tail3_launch_c180(const HatHabTailDesc& h, void* stream);   // hat_tail3l.hip
 
-extern "C" int hat_hab_tail3(const HatHabTailDesc* dp, void* stream) {
+// hat_hab_tail3 (sat == nullptr) and hat_hab_tail3_guarded
+static int tail3_entry(const HatHabTailDesc* dp, unsigned* sat, void* stream) {
     if (!dp) return HAT_EINVAL;
+    if (sat && (reinterpret_cast<uintptr_t>(sat) % 4 || dp->ffn.C != T3_C || !(dp->reserved1 & 2))) return HAT_EINVAL;   // FP16 t_out at 144 only
     const HatHabTailDesc& h = *dp;
     const HatFfnDesc& d = h.ffn;
     if (!d.t_in || !d.t_out || d.t_in == d.t_out || !d.w1f || !d.dww || !d.w2f || !d.b2) return HAT_EINVAL;
@@ -562,7 +572,14 @@ extern "C" int hat_hab_tail3(const HatHabTailDesc* dp, void* stream) {
     if ((h.reserved1 & ~3) != 0) return HAT_EINVAL;
     if ((th & 1) && reinterpret_cast<uintptr_t>(d.t_in) % 8) return HAT_EINVAL;
     if ((th & 2) && reinterpret_cast<uintptr_t>(d.t_out) % 16) return HAT_EINVAL;
+    if (sat) {
+        void (*gk)(const HatFfnDesc, const T3Aggr, unsigned*) = th == 2 ? tail3_kernel<0, 2, unsigned*> : tail3_kernel<0, 3, unsigned*>;
+        return hat_tail_launch(gk, T3_LDS, T3_ROWS, d, ag, stream, sat);
+    }
     void (*kern)(const HatFfnDesc, const T3Aggr) = th == 0 ? tail3_kernel<0, 0> : th == 1 ? tail3_kernel<0, 1> : th == 2 ? tail3_kernel<0, 2> : tail3_kernel<0, 3>;
     return hat_tail_launch(kern, T3_LDS, T3_ROWS, d, ag, stream);
 }
+
+extern "C" int hat_hab_tail3(const HatHabTailDesc* dp, void* stream) { return tail3_entry(dp, nullptr, stream); }
+extern "C" int hat_hab_tail3_guarded(const HatHabTailDesc* dp, uint32_t* sat, void* stream) { return tail3_entry(dp, sat, stream); }
 #endif

@@ -17,10 +17,12 @@ T = bf16 (performance path) or fp32 (exact-fp32 parity path).
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import math
 import os
-from typing import Dict
+import warnings
+from typing import Dict, Optional
 
 import torch
 
@@ -39,6 +41,9 @@ def _r8(x: int) -> int:
 
 def _r4(x: int) -> int:
     return (x + 3) // 4 * 4
+
+
+T16_GUARD_MODES = ("defer", "sync", "off")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -63,7 +68,11 @@ class Options:
       HAT_NO_OCAB_QKV        the OCAB q and kv projections as two hat_linear launches on two streams instead of hat_ocab_qkv
       HAT_NO_BF16_CONV_IN    fp32 rows into the group conv instead of the OCAB MLP's bf16 rows
       HAT_NO_CONV_LN         the LayerNorm after the group conv as its own launch instead of the conv's epilogue
-      HAT_NO_UPFOLD=1        the last Upsample conv and conv_last as their two launches instead of hat_upfold_*"""
+      HAT_NO_UPFOLD=1        the last Upsample conv and conv_last as their two launches instead of hat_upfold_*
+    One switch is not an A/B switch and takes a word:
+      HAT_T16_GUARD          defer (default) | sync | off — what happens when the FP16 residual stream leaves the FP16 range
+                             (_T16Guard below): off launches the unguarded entries and clips in silence; any other
+                             word raises"""
     no_n16: bool = False
     no_t16: bool = False
     no_fused_ffn: bool = False
@@ -80,6 +89,11 @@ class Options:
     no_bf16_conv_in: bool = False
     no_conv_ln: bool = False
     no_upfold: bool = False
+    t16_guard: str = "defer"
+
+    def __post_init__(self):
+        if self.t16_guard not in T16_GUARD_MODES:
+            raise ValueError(f"t16_guard / HAT_T16_GUARD is one of {', '.join(T16_GUARD_MODES)}, got {self.t16_guard!r}")
 
     @classmethod
     def from_env(cls, env=None) -> "Options":
@@ -87,7 +101,26 @@ class Options:
         env = os.environ if env is None else env
         get = lambda name: env.get("HAT_" + name.upper(), "")
         any_value = ("no_cab_fold", "no_cab_sweep", "no_ocab_mlp", "no_ocab_qkv", "no_bf16_conv_in", "no_conv_ln")
-        return cls(**{k.name: (get(k.name) != "" if k.name in any_value else get(k.name) == "1") for k in dataclasses.fields(cls)})
+        kw = {k.name: (get(k.name) != "" if k.name in any_value else get(k.name) == "1") for k in dataclasses.fields(cls) if k.type == "bool"}
+        return cls(t16_guard=(get("t16_guard") or "defer"), **kw)
+
+
+class _T16Guard:
+    """The FP16-range guard of the residual stream: `slot`, one word on the device that the guarded launches of a
+    forward raise to the bit pattern of the largest magnitude their FP16 stores clipped (0: none did); `host`, the pinned word
+    it is copied to behind the last launch, and `event`, recorded behind that copy; `pending`, the forwards handed to the
+    caller whose word nobody has looked at yet.  The slot is zeroed only while nothing is pending, so a word that is looked
+    at late still holds the largest magnitude of every forward since the last look.  One per engine, not per workspace: every
+    shape and every band of a frame raises the same word."""
+
+    def __init__(self, dev):
+        self.slot = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self.event = torch.cuda.Event()
+        self.pending = 0
+
+    def word(self) -> int:
+        return int(self.host[0]) & 0xFFFFFFFF
 
 
 class _Packed:
@@ -172,13 +205,14 @@ class _Fwd:
 
 
 class HATEngine(FrameBoundary, EngineBase):
-    def __init__(self, cfg: dict, state_dict: Dict[str, torch.Tensor], device, dtype: str = "bf16"):
+    def __init__(self, cfg: dict, state_dict: Dict[str, torch.Tensor], device, dtype: str = "bf16", options: Optional[Options] = None):
+        """options: the switches (default: Options.from_env(), the environment's)."""
         if cfg.get("upsampler") != "pixelshuffle":
             raise NotImplementedError("only upsampler='pixelshuffle' is on the hot path (all shipped test YAMLs)")
         if cfg.get("resi_connection", "1conv") not in ("1conv", "identity"):
             raise ValueError(f"Unknown resi_connection: {cfg.get('resi_connection')}")   # hat_arch.py:547-548, :750-751
         self.cfg = cfg
-        self.opt = Options.from_env()
+        self.opt = Options.from_env() if options is None else options
         self.identity = cfg.get("resi_connection", "1conv") == "identity"
         if torch.device(device).type != "cuda":
             raise RuntimeError("HATEngine needs a GPU device: there is no CPU path")
@@ -193,6 +227,12 @@ class HATEngine(FrameBoundary, EngineBase):
         self.use_n16 = not self.opt.no_n16
         # FP16 residual rows between the fused HAB tails of a residual group (bf16 path, embed_dim 144; HAT_NO_T16=1: fp32 everywhere)
         self.t16 = not self.opt.no_t16 and self.dtype == ops.HAT_BF16 and self.C == 144
+        # the guard of that stream (_T16Guard): the mode, what it has seen, and its state; no FP16 stream, no guard
+        self.t16_guard = self.opt.t16_guard
+        self.t16_fallbacks = self.t16_clipped_frames = 0   # switches to the fp32 stream; clipped frames that were already handed out
+        self.t16_peak = 0.0                                # the magnitude the stream peaked at when it fell back
+        self._guard = _T16Guard(self.dev) if self.t16 else None
+        self._armed = False                                # this forward launches the guarded entries
         self._s1 = None
         ops._lib.load()
         # HATX (hatx_arch.py): the SGFN runs as fc1 -> hat_sgfn_gate -> fc2; odd window overlaps are padded with
@@ -432,7 +472,7 @@ class HATEngine(FrameBoundary, EngineBase):
                 else:
                     nxt, gap_c = (self.norm, 0) if self.conv_after_body is not None else (None, 0)
                 G.conv_ln = (nxt, gap_c) if nxt is not None and gap_c in (0, 4, 8, 12, 16) else None
-        self._resolve_stream16()
+        self._plan_t16()
         # 8-bit output (forward_to_u8 / forward_u8): conv_last's row-sweep kernel converts in its epilogue when it is packed for
         # three output channels (the width condition, W % 16, is the one _upsample already checks per shape); otherwise
         # conv_last writes fp32 planes and hat_planes_to_u8 converts them
@@ -443,15 +483,22 @@ class HATEngine(FrameBoundary, EngineBase):
         self._yw = max([16] + [e.npad for e in escs])      # channels of the ESC conv output / floats per GAP partial block
         self._kpad = max([hab0.esc.kpad if hab0 else 0] + [G.ocab.esc.kpad for G in layers if G.ocab.esc is not None])
 
-    def _resolve_stream16(self):
-        """Where the residual stream is handed over as FP16 rows (bf16 path at embed_dim 144, HAT_NO_T16=1: nowhere).
+    def _plan_t16(self):
+        """Where the residual stream is handed over as FP16 rows (bf16 path at embed_dim 144, HAT_NO_T16=1: nowhere; called again
+        when the guard switches the stream to fp32).
         A hand-over is FP16 only when EVERY reader of that buffer takes FP16 rows: hat_hab_tail3 (t_in / t_out), the OCAB
         projection (hat_linear: r1 and its output, in place), hat_ocab_mlp (r1) and the group conv (hat_conv: r1 and its
         output, in place).  hat_layernorm, hat_add_f32, the unfused OCAB / conv-LN fallbacks and the embed_dim-180 tail read
-        fp32.  Sets G.ocab16, G.out16 (group input of the next group, or the stream after the last group) and hb.out16."""
+        fp32.  Sets G.ocab16, G.out16 (group input of the next group, or the stream after the last group) and hb.out16: the
+        three kinds of launch that STORE FP16 rows, and so the three the guard replaces by their guarded entries
+        (guarded_launches): the tail of a block with out16, the projection of a group with ocab16, the conv of one with out16."""
+        layers = self.layers
+        for G in layers:
+            G.ocab16 = G.out16 = False
+            for hb in G.habs:
+                hb.out16 = False
         if not self.t16:
             return
-        layers = self.layers
         tail16 = lambda hb: hb.tail == "fused144" and hb.ffn3.C == 144
         conv16 = lambda G: bool(G.conv is not None and not G.conv.frag and G.conv.ksize > 1 and G.conv.nt == 9
                                 and G.conv.n_slices == 1 and G.conv.nout == 144)
@@ -472,6 +519,102 @@ class HATEngine(FrameBoundary, EngineBase):
             else:
                 G.out16 = self.conv_after_body is not None     # (the stream itself is not read after the last group)
 
+    def guarded_launches(self):
+        """The launches that go through a *_guarded entry while the guard is on, in launch order: ("tail", group, block),
+        ("proj", group), ("conv", group).  Exactly the FP16 stores of _plan_t16; none with t16_guard "off" or without the stream."""
+        if not self.t16 or self.t16_guard == "off":
+            return []
+        out = []
+        for gi, G in enumerate(self.layers):
+            out += [("tail", gi, i) for i, hb in enumerate(G.habs) if hb.out16]
+            out += [("proj", gi)] if G.ocab16 else []
+            out += [("conv", gi)] if G.out16 else []
+        return out
+
+    # ------------------------------------------------------------------------------------------ the FP16-range guard
+    @contextlib.contextmanager
+    def guard_mode(self, mode: str):
+        """The guard's mode for the forwards inside the block: callers that wait for every frame anyway take "sync", the plan
+        recorder "off".  A fallback that happens inside outlives the block."""
+        if mode not in T16_GUARD_MODES:
+            raise ValueError(f"t16_guard is one of {', '.join(T16_GUARD_MODES)}, got {mode!r}")
+        with self._lock:      # (not across the block: the forwards inside take the lock themselves)
+            old, self.t16_guard = self.t16_guard, mode
+        try:
+            yield self
+        finally:
+            with self._lock:
+                self.t16_guard = old
+
+    def _sat(self, stores16: bool):
+        """The slot a launch that stores FP16 rows reports to, or None: the unguarded entry."""
+        return self._guard.slot if stores16 and self._armed else None
+
+    def _guard_begin(self) -> bool:
+        """Before the first launch of a forward (under the lock, not while a graph is being captured): look at the word of
+        earlier forwards if their event has passed — never waiting — then arm this one and zero the slot."""
+        g = self._guard
+        if g is None:
+            return False
+        if g.pending and g.event.query():
+            self._guard_look()
+        self._armed = self.t16 and self.t16_guard != "off"
+        if self._armed and not g.pending:
+            g.slot.zero_()
+        return self._armed
+
+    def _guard_look(self):
+        """The pending word: clean, or the frames it covers were handed out clipped — count them, warn once, leave the FP16 stream."""
+        g = self._guard
+        word, n, g.pending = g.word(), g.pending, 0
+        if word and self.t16:
+            self.t16_clipped_frames += n
+            self._t16_fall_back(word)
+            warnings.warn(f"the FP16 residual stream left the FP16 range (peaked at {self.t16_peak:.4g}, limit 65504): {n} frame"
+                          f"{'s' if n != 1 else ''} already returned {'were' if n != 1 else 'was'} clipped; this engine carries "
+                          f"the stream in fp32 from now on (t16_guard='sync' re-runs such a frame before it is returned)", RuntimeWarning, stacklevel=3)
+
+    def _t16_fall_back(self, word: int):
+        """Switch to the fp32 stream for the life of the engine: what HAT_NO_T16=1 runs.  Workspaces of the old plan are dropped
+        (a HIP graph captured on one keeps it alive and is dropped by its owner, whose cache key holds t16)."""
+        self.t16, self._armed = False, False
+        self.t16_fallbacks += 1
+        self.t16_peak = ops.read_sat(word)
+        self._plan_t16()
+        self._ws_cache.clear()
+
+    def _guard_end(self, defer: bool = False) -> bool:
+        """Behind the last launch of an armed forward (not while capturing: a graph's owner calls it behind the replay): record
+        the copy of the slot to the host word and the event behind it (defer=True: "defer" whatever the mode).  "sync": wait for it; True when the stream clipped and the engine has fallen back —
+        the caller runs the frame again.  "defer": leave the word to the next forward or to resolve_t16_guard."""
+        g = self._guard
+        if g is None or not self._armed:
+            return False
+        self._armed = False
+        g.host.copy_(g.slot, non_blocking=True)
+        g.event.record()
+        if defer or self.t16_guard != "sync":
+            g.pending += 1
+            return False
+        g.event.synchronize()
+        word, earlier, g.pending = g.word(), g.pending, 0
+        if not word:
+            return False
+        self.t16_clipped_frames += earlier   # (forwards deferred before this one share the word: counted as handed out clipped)
+        self._t16_fall_back(word)
+        return True
+
+    def resolve_t16_guard(self) -> bool:
+        """Wait for the forwards handed out so far and look at their word.  True: they stayed in the FP16 range (or there is no
+        FP16 stream).  False: the engine is, or has just gone, on the fp32 stream; t16_clipped_frames, t16_fallbacks and
+        t16_peak say what happened."""
+        with self._lock:
+            g = self._guard
+            if g is not None and g.pending:
+                g.event.synchronize()
+                self._guard_look()
+            return self.t16_fallbacks == 0
+
     # ------------------------------------------------------------------------------------------
     def _alloc_workspace(self, B, H, W, tag):
         """The buffers of one (B, H, W) input; a row band's (tag, EngineBase._workspace) also holds its pooled sums."""
@@ -484,7 +627,7 @@ class HATEngine(FrameBoundary, EngineBase):
         w = {
             "f0": z(B, N, C, dtype=f), "tA": z(B, N, C, dtype=f), "tB": z(B, N, C, dtype=f), "tC": z(B, N, C, dtype=f),
             # the residual stream as FP16 rows: hA = a group's input (written by the previous group conv), hB / hC = between its
-            # fused tails and through its OCAB (see _resolve_stream16)
+            # fused tails and through its OCAB (see _plan_t16)
             "hA": (z(B, N, C, dtype=torch.float16) if self.t16 else None),
             "hB": (z(B, N, C, dtype=torch.float16) if self.t16 else None), "hC": (z(B, N, C, dtype=torch.float16) if self.t16 else None),
             "n": z(B, N, _r8(C)), "n2b": z(B, N, _r8(C)), "c1": z(B, N, _r8(mid)), "c2": z(B, N, _r8(C)), "m2": z(B, N, ops.ffn_m_ld(C)),
@@ -608,7 +751,25 @@ class HATEngine(FrameBoundary, EngineBase):
             return self._forward(x, only_ocab=(t.to(self.dev, torch.float32).contiguous(), group))
 
     def _forward(self, x: torch.Tensor, only_ocab=None, one_stream=None, sink=None) -> torch.Tensor:
-        """one_stream: overrides HAT_ONE_STREAM for this call (plan export records the one-stream order)."""
+        """one_stream: overrides HAT_ONE_STREAM for this call (plan export records the one-stream order).
+        The guard brackets the launches: zero the slot, launch (guarded entries where FP16 rows are stored), copy the slot to
+        the host word, record the event.  While a HIP graph is captured only the launches and the copy are recorded; the
+        graph's owner zeroes before a replay and records behind it (archs/hat_arch.py)."""
+        capturing = self._guard is not None and torch.cuda.is_current_stream_capturing()
+        if capturing:
+            self._armed = self.t16 and self.t16_guard != "off"
+        else:
+            self._guard_begin()
+        y = self._launches(x, only_ocab=only_ocab, one_stream=one_stream, sink=sink)
+        if self._armed:
+            if capturing:
+                self._guard.host.copy_(self._guard.slot, non_blocking=True)
+                self._armed = False
+            elif self._guard_end():   # "sync" and the stream clipped: the same frame on the fp32 stream
+                y = self._launches(x, only_ocab=only_ocab, one_stream=one_stream, sink=sink)
+        return y
+
+    def _launches(self, x: torch.Tensor, only_ocab=None, one_stream=None, sink=None) -> torch.Tensor:
         gen = self._forward_gen(x, only_ocab=only_ocab, one_stream=one_stream, sink=sink)
         try:
             req = next(gen)
@@ -837,7 +998,8 @@ class HATEngine(FrameBoundary, EngineBase):
         nxt, gap_c = hb.next_ln
         ops.hab_tail(hb.ffn3, hb.esc.aggr, t, tout, hb.n2[0], hb.n2[1], n=w["n"], ldn_in=f.ldc,
                      y16=w["y16"], c1=w["c1"], wf=w["wf"], bias_b=w["bias_b"], B=f.B, H=f.H, W=f.W, dtype=f.dt, ln1=nxt,
-                     n_out=w["n2b"], ldn=f.ldc, gap_out=w["gap"], gap_c=gap_c, n16_out=(w["n16"] if self.use_n16 else None))
+                     n_out=w["n2b"], ldn=f.ldc, gap_out=w["gap"], gap_c=gap_c, n16_out=(w["n16"] if self.use_n16 else None),
+                     sat=self._sat(hb.out16))
         w["n"], w["n2b"] = w["n2b"], w["n"]      # the kernel reads n with a halo: its output n' is another buffer
         f.t, f.have_n, f.have_n16, f.nblk = tout, True, self.use_n16, ops.ffn_tiles(hb.ffn, f.H, f.W, f.dt)
 
@@ -941,7 +1103,7 @@ class HATEngine(FrameBoundary, EngineBase):
         tout = w["tB"] if t is w["tA"] else t  # never write the RHAG input buffer (an FP16 t is hB / hC: proj and MLP take it in place)
         if oc.proj.frag:  # norm2 (:306) rides on the projection's epilogue
             self._run_lin(oc.proj, w["ao"], tout, **geo, ldx=ldc, ldo=C, out_mode=O_NHWC_F32, r1=t, ldr1=C,
-                          ln=oc.n2, ln_out=w["n"], ld_ln=ldc)
+                          ln=oc.n2, ln_out=w["n"], ld_ln=ldc, **({"sat": self._sat(True)} if tout.dtype == torch.float16 and self._armed else {}))
         else:
             self._run_lin(oc.proj, w["ao"], tout, **geo, ldx=ldc, ldo=C, out_mode=O_NHWC_F32, r1=t, ldr1=C)
             f.ln(tout, w["n"], oc.n2)
@@ -995,7 +1157,8 @@ class HATEngine(FrameBoundary, EngineBase):
         f.have_n16 = bool(f.have_n and self.use_n16 and G.conv_ln[1])
         gout = w["hA"] if G.out16 else tA   # written over the group input when both have the same type, else into hA
         if G.to_conv:
-            ops.conv(G.conv, tout, gout, **f.geo, ldx=f.ldc, ldo=C, x_mode=X_NHWC_T, out_mode=O_NHWC_F32, r1=f.gin, ldr1=C, **lnkw)
+            ops.conv(G.conv, tout, gout, **f.geo, ldx=f.ldc, ldo=C, x_mode=X_NHWC_T, out_mode=O_NHWC_F32, r1=f.gin, ldr1=C,
+                     sat=self._sat(G.out16), **lnkw)
         else:
             ops.conv(G.conv, tout, gout, **f.geo, ldx=C, ldo=C, x_mode=X_NHWC_F32, out_mode=O_NHWC_F32, r1=f.gin, ldr1=C, **lnkw)
         f.t = f.gin = gout
@@ -1004,7 +1167,7 @@ class HATEngine(FrameBoundary, EngineBase):
         """final LN; conv_after_body + f0 ; conv_before_upsample + LeakyReLU               :844, :854-855"""
         w, tA, C, ldc = f.w, f.w["tA"], self.C, f.ldc
         if f.gin is not tA and not (f.have_n and self.conv_after_body is not None):
-            raise RuntimeError("the FP16 residual stream reached a reader that takes fp32 only")   # (_resolve_stream16 rules it out)
+            raise RuntimeError("the FP16 residual stream reached a reader that takes fp32 only")   # (_plan_t16 rules it out)
         if self.conv_after_body is None:   # nn.Identity: LN(t) + f0 in fp32, read as such by the next conv      :748
             if f.band is not None:   # the same one refresh as below: LN + f0 and the four 3x3 convs that end the network read < 4 rows
                 yield ("halo", [(tA, 8)])

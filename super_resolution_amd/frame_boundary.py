@@ -133,7 +133,9 @@ class FrameBoundary:
         the lock.  x must not be the buffer a member's input is written to (it is not: that is ens_x, this method's own)."""
         x = x.to(torch.float32).contiguous()
         B, C_, H, W = x.shape
-        for i in range(n):
+        plan = getattr(self, "t16_fallbacks", 0)   # (HATEngine's FP16-range guard: a member that switches the engine to the fp32 stream ...)
+        i = 0
+        while i < n:
             if i == 0:
                 xi = x
             else:
@@ -144,7 +146,13 @@ class FrameBoundary:
             if not y.is_contiguous():   # a corner of a larger buffer (ESCRealM behind its unshuffled stem): into the member's workspace
                 Hi, Wi = xi.shape[2:]
                 y = self._ws_buffer(self._workspace(B, Hi, Wi), "ens_y", tuple(y.shape)).copy_(y)
+            if getattr(self, "t16_fallbacks", 0) != plan:   # (... starts the ensemble again: no member of it stays clipped)
+                plan, again = self.t16_fallbacks, i > 0
+                if again:
+                    i = 0
+                    continue
             ops.dihedral(y, acc, op=i, inverse=True, alpha=1.0 / n, accumulate=i > 0)
+            i += 1
         return acc
 
     def _check_u8(self):

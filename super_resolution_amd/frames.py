@@ -10,6 +10,8 @@ uses three streams, within the four hardware queues a process gets by default.
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 import torch
 
@@ -20,6 +22,16 @@ PIXFMTS = ("rgb24", "nv12", "nv21", "i420", "i422", "nv16", "i444", "nv24", "gra
 def _raw(t):
     """A uint16 tensor as int16 (the same words): torch's copy kernels are complete for the signed type."""
     return t.view(torch.int16) if t.dtype == torch.uint16 else t
+
+
+def sync_guard(net):
+    """The context in which `net`'s forwards run the FP16-range guard of the residual stream in "sync" mode (HATEngine.guard_mode;
+    DESIGN 4.0c): for callers that bring every frame to the host anyway, so a frame whose stream left the FP16 range is run
+    again on the fp32 stream before it is delivered.  Nothing for an engine without the guard, or with the guard "off"."""
+    eng = net.engine()
+    if getattr(eng, "_guard", None) is None or eng.t16_guard == "off":
+        return contextlib.nullcontext()
+    return eng.guard_mode("sync")
 
 
 def fixed_scale_family(net) -> bool:
@@ -185,7 +197,8 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
             comp.wait_event(up[k])
             comp.wait_event(down[k])           # dout[k] was last read by the download of frame n-2
             comp.wait_event(done[k ^ 1])       # the engine's workspace is shared: after frame n-1's forward, whatever stream it ran on
-            forward(din[k], dout[k])
+            with sync_guard(net):              # (the frame goes to the host: a clipped one is run again first)
+                forward(din[k], dout[k])
             done[k].record(comp)               # din[k] is free again and dout[k] is complete
             with torch.cuda.stream(copy):
                 copy.wait_event(done[k])

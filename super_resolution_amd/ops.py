@@ -92,6 +92,19 @@ def _stream16(r1, out, out_mode: int) -> int:
     return h
 
 
+def _sat_ptr(sat: torch.Tensor) -> int:
+    """The guard slot of the *_guarded entries: one uint32 (or int32) word of device memory."""
+    if sat.dtype not in (torch.uint32, torch.int32) or sat.numel() < 1:
+        raise RuntimeError(f"the guard slot is one 32-bit integer word on the device, got {tuple(sat.shape)} {sat.dtype}")
+    return _ptr(sat)
+
+
+def read_sat(word) -> float:
+    """The magnitude a guard slot's word stands for: 0.0 for a clean word, else the fp32 value of its bit pattern (inf, nan)."""
+    import struct
+    return struct.unpack("<f", struct.pack("<I", int(word) & 0xFFFFFFFF))[0]
+
+
 def conv(pw: PackedConv, x: torch.Tensor, out: torch.Tensor, *, B: int, H: int, W: int, dtype: int, ldx: int, ldo: int,
          x_mode: int = X_NHWC_T, out_mode: int = O_NHWC_T, act: int = ACT_NONE, n_store: Optional[int] = None,
          x0: Optional[torch.Tensor] = None, c_split: int = 0, ldx0: int = 0,
@@ -99,10 +112,11 @@ def conv(pw: PackedConv, x: torch.Tensor, out: torch.Tensor, *, B: int, H: int, 
          r2scale: Optional[torch.Tensor] = None, r2scale_bstride: int = 0, colsum: Optional[torch.Tensor] = None,
          ps_r: int = 0, in_scale: float = 1.0, out_scale: float = 1.0, mean=(0.0, 0.0, 0.0, 0.0), cin: Optional[int] = None,
          ln=None, ln_out: Optional[torch.Tensor] = None, ld_ln: int = 0, gap_out: Optional[torch.Tensor] = None, gap_c: int = 0,
-         n16_out: Optional[torch.Tensor] = None):
+         n16_out: Optional[torch.Tensor] = None, sat: Optional[torch.Tensor] = None):
     """ln=(gamma, beta), ln_out, ld_ln: also emit LayerNorm(result) as T rows from the conv's epilogue (one slice that stores
     every channel), with the per-tile sums of its first gap_c channels (gap_out, conv_tiles blocks) and a compact copy of
-    its first 16 channels (n16_out) for the ESC path of the block that consumes it."""
+    its first 16 channels (n16_out) for the ESC path of the block that consumes it.
+    sat: the FP16-range guard's slot (one uint32 on the device): hat_conv_guarded instead of hat_conv, for FP16 output rows only."""
     lib = _lib.load()
     d = HatConvDesc()
     if ln is not None:
@@ -131,8 +145,8 @@ def conv(pw: PackedConv, x: torch.Tensor, out: torch.Tensor, *, B: int, H: int, 
         # algorithmic FLOPs (2*MAC, unpadded).  The 13x13 ESC conv also carries the
         # dynamic depthwise 3x3 that is folded into its weights (2*9*pdim per pixel).
         flops = 2.0 * B * H * W * (pw.ksize ** 2) * d.Cin * pw.nout + (2.0 * 9 * pw.nout * B * H * W if pw.w_bstride else 0.0)
-    _timed(name, flops, lambda: _lib.check(lib.hat_conv(C.byref(d), _stream()),
-                                           f"hat_conv(k={pw.ksize}, Cin={d.Cin}, N={pw.nout})"),
+    launch = (lambda: lib.hat_conv(C.byref(d), _stream())) if sat is None else (lambda: lib.hat_conv_guarded(C.byref(d), _sat_ptr(sat), _stream()))
+    _timed(name, flops, lambda: _lib.check(launch(), f"hat_conv{'' if sat is None else '_guarded'}(k={pw.ksize}, Cin={d.Cin}, N={pw.nout})"),
            tag=f"k{pw.ksize} {d.Cin}->{pw.nout} {H}x{W} x{x_mode} o{out_mode}{' r1' if r1 is not None else ''}{' r2' if r2 is not None else ''}")
 
 
@@ -1392,9 +1406,10 @@ def hab_tail_supported(pf: PackedFFN, aggr: PackedConv, mid: int, dtype: int) ->
 
 def hab_tail(pf: PackedFFN, aggr: PackedConv, t_in, t_out, ln_g, ln_b, *, n, ldn_in: int, y16, c1=None, wf=None, bias_b, B: int, H: int,
              W: int, dtype: int, ln1=None, n_out=None, ldn: int = 0, gap_out=None, gap_c: int = 0, n16_out=None,
-             r2=None, ldr2: int = 0, r2scale=None, r2scale_bstride: int = 0):
+             r2=None, ldr2: int = 0, r2scale=None, r2scale_bstride: int = 0, sat=None):
     """hat_hab_tail: aggregation + folded CAB + residuals + the whole gated FFN in one launch (t_in = the residual stream
-    BEFORE the aggregation).  hat_hab_tail3 at embed_dim 144 takes t_in / t_out as fp32 or FP16 rows (by the tensors' dtype)."""
+    BEFORE the aggregation).  hat_hab_tail3 at embed_dim 144 takes t_in / t_out as fp32 or FP16 rows (by the tensors' dtype).
+    sat: the FP16-range guard's slot: hat_hab_tail3_guarded instead of hat_hab_tail3, for an FP16 t_out only."""
     lib = _lib.load()
     h = HatHabTailDesc()
     d = h.ffn
@@ -1408,17 +1423,21 @@ def hab_tail(pf: PackedFFN, aggr: PackedConv, t_in, t_out, ln_g, ln_b, *, n, ldn
     if (not in_half and t_in.dtype != torch.float32) or (not out_half and t_out.dtype != torch.float32):
         raise RuntimeError("hab_tail: t_in / t_out must be fp32 or FP16 rows")
     h.reserved1 = (1 if in_half else 0) | (2 if out_half else 0)
+    if sat is not None and not (pf.layout == "tail3"):
+        raise RuntimeError("the FP16-range guard is hat_hab_tail3's")
+    tail3 = (lambda: lib.hat_hab_tail3(C.byref(h), _stream())) if sat is None else (lambda: lib.hat_hab_tail3_guarded(C.byref(h), _sat_ptr(sat), _stream()))
+    what = "hat_hab_tail3" if sat is None else "hat_hab_tail3_guarded"
     if pf.C == 180:   # aggregation + c2 term + FFN; n, y16, c2 (T), t read once, t_out and the next LayerNorm written
         flops = B * H * W * (2.0 * pf.C * pf.C + 2.0 * pf.C * 2 * pf.hid + 2.0 * 9 * 2 * pf.hid + 2.0 * pf.hid * pf.C)
         nbytes = B * H * W * (2.0 * ldn_in + 32 + 2.0 * ldr2 + 4.0 * pf.C + 4.0 * pf.C + (2 * ldn if ln1 is not None else 0))
-        _timed("tail3l_kernel", flops, lambda: _lib.check(lib.hat_hab_tail3(C.byref(h), _stream()), "hat_hab_tail3"), nbytes=nbytes)
+        _timed("tail3l_kernel", flops, lambda: _lib.check(tail3(), what), nbytes=nbytes)
         return
     flops = B * H * W * (2.0 * pf.C * (pf.C + 72) + 2.0 * pf.C * 2 * pf.hid + 2.0 * 9 * 2 * pf.hid + 2.0 * pf.hid * pf.C)
     # algorithmic HBM bytes per pixel: n (T), y16 (T x 16), c1 (T x 8), t (fp32) read once; t_out (fp32) and the next
     # block's LayerNorm output (T) written
     nbytes = B * H * W * (2.0 * ldn_in + 32 + 16 + (2.0 if in_half else 4.0) * pf.C + (2.0 if out_half else 4.0) * pf.C + (2 * ldn if ln1 is not None else 0))
     if pf.layout == "tail3":
-        _timed("tail3_kernel", flops, lambda: _lib.check(lib.hat_hab_tail3(C.byref(h), _stream()), "hat_hab_tail3"), nbytes=nbytes)
+        _timed("tail3_kernel", flops, lambda: _lib.check(tail3(), what), nbytes=nbytes)
         return
     _timed("ffn2_kernel<aggr>", flops, lambda: _lib.check(lib.hat_hab_tail(C.byref(h), _stream()), "hat_hab_tail"), nbytes=nbytes)
 
@@ -1440,9 +1459,10 @@ def linear(pw: PackedConv, x: torch.Tensor, out: torch.Tensor, *, B: int, H: int
            out_mode: int = O_NHWC_T, act: int = ACT_NONE, n_store: Optional[int] = None, x0: Optional[torch.Tensor] = None,
            c_split: int = 0, ldx0: int = 0, r1: Optional[torch.Tensor] = None, ldr1: int = 0, r2: Optional[torch.Tensor] = None,
            ldr2: int = 0, r2scale: Optional[torch.Tensor] = None, r2scale_bstride: int = 0, ln=None,
-           ln_out: Optional[torch.Tensor] = None, ld_ln: int = 0, ln_ones: bool = False):
+           ln_out: Optional[torch.Tensor] = None, ld_ln: int = 0, ln_ones: bool = False, sat: Optional[torch.Tensor] = None):
     """ln=(gamma, beta), ln_out, ld_ln: also emit LayerNorm(result) as T rows (hat_linear's fused LayerNorm; needs a
-    residual operand); ln_ones appends the [1.0, 0...] tail that hat_ffn's m_in expects."""
+    residual operand); ln_ones appends the [1.0, 0...] tail that hat_ffn's m_in expects.
+    sat: the FP16-range guard's slot: hat_linear_guarded instead of hat_linear, for FP16 output rows only."""
     lib = _lib.load()
     d = HatConvDesc()
     d.x, d.x0, d.w, d.bias, d.out = _ptr(x), _ptr(x0), _ptr(pw.w), _ptr(pw.bias), _ptr(out)
@@ -1456,7 +1476,8 @@ def linear(pw: PackedConv, x: torch.Tensor, out: torch.Tensor, *, B: int, H: int
     d.reserved0 = _stream16(r1, out, out_mode)
     flops = 2.0 * B * H * W * pw.cin * pw.nout
     _timed(f"pw_kernel<{_TNAME[dtype]}, {pw.nt}, {pw.kpad // 32}>", flops,
-           lambda: _lib.check(lib.hat_linear(C.byref(d), _stream()), f"hat_linear(Cin={pw.cin}, N={pw.nout})"),
+           lambda: _lib.check(lib.hat_linear(C.byref(d), _stream()) if sat is None else lib.hat_linear_guarded(C.byref(d), _sat_ptr(sat), _stream()),
+                              f"hat_linear{'' if sat is None else '_guarded'}(Cin={pw.cin}, N={pw.nout})"),
            tag=f"lin {pw.cin}->{pw.nout} {H}x{W} o{out_mode}{' r1' if r1 is not None else ''}{' r2' if r2 is not None else ''}")
 
 

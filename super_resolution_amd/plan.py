@@ -167,14 +167,14 @@ def record_plan(net, x_shape: Tuple[int, int, int, int]):
     with _EXPORT_LOCK:                         # one export at a time: the recorder stands in for the process-wide library handle
         _lib._lib = rec
         try:
-            with torch.no_grad():
+            with torch.no_grad(), eng.guard_mode("off"):   # a plan holds the unguarded entries: a C host has no guard
                 y = eng.forward(x, one_stream=True)   # the plan replays on one stream: record the launches in that order
             torch.cuda.synchronize(dev)
         finally:
             _lib._lib = real
     ws = eng._workspace(B, H, W)
     consts, scratch = [], []
-    _tensors_of({k: v for k, v in eng.__dict__.items() if k != "_ws_cache"}, set(), consts)
+    _tensors_of({k: v for k, v in eng.__dict__.items() if k not in ("_ws_cache", "_guard")}, set(), consts)
     _tensors_of(ws, set(), scratch)
 
     # buffers = distinct storages; kind by where the tensor came from

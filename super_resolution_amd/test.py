@@ -9,6 +9,7 @@ import sys
 import yaml
 
 from .data import FolderDataset
+from .frames import sync_guard
 from .models import HATModel, model_class
 
 
@@ -56,7 +57,8 @@ def main(argv=None):
     for _, dopt in sorted((opt.get("datasets") or {}).items()):
         ds = FolderDataset(dopt)
         print(f"Testing {dopt['name']} ({len(ds)} images)...", file=sys.stderr)
-        mean, rows = model.nondist_validation(ds, save_img=(opt.get("val") or {}).get("save_img", True))
+        with sync_guard(model.net_g):   # every image comes to the host: one whose FP16 stream clipped is run again on fp32 first
+            mean, rows = model.nondist_validation(ds, save_img=(opt.get("val") or {}).get("save_img", True))
         results[dopt["name"]] = {"mean": mean, "images": rows}
         print(f"Validation {dopt['name']}: " + "  ".join(f"# {k}: {v:.4f}" for k, v in mean.items()), file=sys.stderr)
     print(json.dumps(results))
