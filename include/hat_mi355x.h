@@ -500,8 +500,8 @@ int hat_conv3x3_to_yuv420p16(const void* x, const void* wpk, const float* bias, 
  * and write the same samples.  hat_conv3x3_to_yuv takes hat_conv3x3_to_yuv420's conv arguments.  A bad surface (odd w with
  * sub_x = 1, one chroma pointer NULL, c_step not bps / 2 bps, an odd pitch for words, overlapping batch strides, sub_y >
  * sub_x ...) returns HAT_EINVAL before anything touches the device; none allocates or synchronises.  Packed 4:2:2 (YUY2 / UYVY /
- * Y210 / v210), 4:1:1, 4:4:0, alpha planes and tone mapping are out of scope.  These entries are centre-sited chroma; see
- * "Chroma siting" below for the rest.
+ * Y210 / v210) has a descriptor of its own: "Packed 4:2:2" below.  4:1:1, 4:4:0, alpha planes and tone mapping are out of
+ * scope.  These entries are centre-sited chroma; see "Chroma siting" below for the rest.
  */
 typedef struct {
     void* y; int64_t y_pitch, y_bstride; void* cb; void* cr; int64_t c_pitch; int32_t c_step; int64_t c_bstride;
@@ -563,7 +563,7 @@ int hat_upfold_to_yuv(const void* x, const void* wpk, const float* bias, const H
  * touches the device.  Where the surface makes the siting 0 they forward to the unsited entry: the same launch, the same
  * samples.  conv_last's fused epilogue (hat_conv3x3_to_yuv) has no sited form — its bands and lanes would need a halo column and
  * row — so a sited output is hat_conv3x3_to_planes followed by hat_planes_to_yuv_sited.  Other filters (Lanczos, 3/4 - 1/4
- * vertical linear for centred axes), PAL-DV's alternating-line siting, packed 4:2:2 and transfer functions are out of scope.
+ * vertical linear for centred axes), PAL-DV's alternating-line siting and transfer functions are out of scope.
  */
 #define HAT_SITING_CENTER 0
 #define HAT_SITING_LEFT 1
@@ -571,6 +571,45 @@ int hat_upfold_to_yuv(const void* x, const void* wpk, const float* bias, const H
 int hat_yuv_to_planes_sited(const HatYuvSurface* src, int32_t siting, float* dst, int32_t B, int32_t h, int32_t w, int32_t Hp, int32_t Wp,
                             const float* to_rgb12, void* stream);
 int hat_planes_to_yuv_sited(const float* src, int32_t B, int32_t Hs, int32_t Ws, const HatYuvSurface* dst, int32_t siting, int32_t h_out,
+                            int32_t w_out, const float* from_rgb12, void* stream);
+
+/*
+ * Packed 4:2:2: what SDI capture cards (UYVY, v210), cameras and UVC devices (YUY2) and 10-bit 4:2:2 decoders (Y210 / Y216)
+ * deliver.  One array per frame, luma and chroma interleaved, which no HatYuvSurface describes (there is no luma step, and v210
+ * is not byte-addressable), so a packed frame has a descriptor of its own.  Per row of w pixels, w even and >= 2, any h >= 1:
+ *     HAT_PACKED_UYVY 0   bytes Cb0 Y0 Cr0 Y1 per pixel pair; depth 8; a row is 2 w bytes
+ *     HAT_PACKED_YUY2 1   bytes Y0 Cb0 Y1 Cr0; depth 8; 2 w bytes
+ *     HAT_PACKED_Y210 2   little-endian 16-bit words Y0 Cb0 Y1 Cr0; depth 10 / 12 / 16 (16: Y216), msb as in the deep entries
+ *                         (Y210 proper is msb = 1); 4 w bytes
+ *     HAT_PACKED_V210 3   six pixels in four little-endian 32-bit words, three 10-bit codes each at bits 0-9, 10-19, 20-29:
+ *                         Cb0 Y0 Cr0 | Y1 Cb1 Y2 | Cr1 Y3 Cb2 | Y4 Cr2 Y5; depth 10, msb 0 or 1 and not used; a row is
+ *                         128 ceil(w / 48) bytes.  Out: bits 30-31 of every word, the codes of the last group past w and every
+ *                         byte from the last group to the end of the row are zero.  In: none of them is read for its value.
+ *     base, pitch, bstride   the first byte, the bytes between rows and between the frames of a batch (ignored for B == 1);
+ *                         base, pitch and bstride are multiples of the unit's word: 4 bytes, 2 for Y210.  reserved is not read.
+ * A packed sample means what the sample of a (sub_x, sub_y) = (1, 0) surface means: the definition is super_resolution_amd/yuv.py
+ * (packed_to_planes / planes_to_packed, which ARE the 'i422' functions on the unpacked samples), the arithmetic is the shared
+ * code of the planar kernels, and the results equal hat_yuv_to_planes_sited / hat_planes_to_yuv_sited on an I422 surface bit for
+ * bit.  siting: HAT_SITING_CENTER or HAT_SITING_LEFT (standard 4:2:2 video is LEFT-sited); HAT_SITING_TOPLEFT means LEFT, as on
+ * every 4:2:2 surface.  hat_packed422_to_planes reflect-pads to (Hp, Wp); hat_planes_to_packed422 keeps the top-left h_out x
+ * w_out pixels.  The destination is written in whole units (a dword for two 8-bit pixels, 8 bytes for two Y210 pixels, 16 bytes
+ * for six v210 pixels), one lane a unit; bytes of a pitched row past the layout's row length are never written.
+ * HAT_EINVAL, before anything touches the device (none allocates or synchronises): a null pointer; w or w_out odd or < 2; h < 1;
+ * a layout outside 0..3; a depth the layout does not take; msb not 0 / 1; a siting outside {0, 1, 2}; a pitch below the row
+ * length; base, pitch or (B > 1) bstride not aligned as above; a bstride that makes the frames of a batch overlap; Hp - h >= h or
+ * Wp - w >= w (no reflection), Hp < h, Wp < w, h_out > Hs, w_out > Ws; B, Hp or h_out > 65535.
+ * There is NO fused packed epilogue (conv_last, the folded ending, the shuffle heads, hat_lte_query): a packed output is fp32
+ * planes followed by hat_planes_to_packed422, like a co-sited output.  Packed 4:4:4 and alpha (AYUV / Y410 / RGBA), 4:1:1, 4:4:0
+ * and big-endian words are out of scope.
+ */
+#define HAT_PACKED_UYVY 0
+#define HAT_PACKED_YUY2 1
+#define HAT_PACKED_Y210 2
+#define HAT_PACKED_V210 3
+typedef struct { void* base; int64_t pitch, bstride; int32_t layout, depth, msb, reserved; } HatPackedSurface;
+int hat_packed422_to_planes(const HatPackedSurface* src, int32_t siting, float* dst, int32_t B, int32_t h, int32_t w, int32_t Hp, int32_t Wp,
+                            const float* to_rgb12, void* stream);
+int hat_planes_to_packed422(const float* src, int32_t B, int32_t Hs, int32_t Ws, const HatPackedSurface* dst, int32_t siting, int32_t h_out,
                             int32_t w_out, const float* from_rgb12, void* stream);
 
 /*
@@ -898,6 +937,13 @@ int hat_plan_forward_yuv(const hat_plan* plan, const HatYuvSurface* src, const H
                          const float* to_rgb12, const float* from_rgb12, void* stream);
 int hat_plan_forward_yuv_sited(const hat_plan* plan, const HatYuvSurface* src, int32_t src_siting, const HatYuvSurface* dst,
                                int32_t dst_siting, int32_t h, int32_t w, const float* to_rgb12, const float* from_rgb12, void* stream);
+/* hat_plan_forward_packed422: the same forward with a packed 4:2:2 surface ("Packed 4:2:2") on either side or on both.  Exactly one
+ * of the two pointers of a side is non-NULL (both or neither: HAT_EINVAL), so UYVY -> UYVY, NV12 -> v210 and v210 -> I420 all work.
+ * Both surfaces are checked in full before anything is enqueued.  A planar destination keeps its fused ending where
+ * hat_plan_forward_yuv_sited has one; a packed destination ends in the fp32 image and hat_planes_to_packed422. */
+int hat_plan_forward_packed422(const hat_plan* plan, const HatPackedSurface* src_packed, const HatYuvSurface* src_planar, int32_t src_siting,
+                               const HatPackedSurface* dst_packed, const HatYuvSurface* dst_planar, int32_t dst_siting, int32_t h, int32_t w,
+                               const float* to_rgb12, const float* from_rgb12, void* stream);
 
 /*
  * Per-channel sums of a channel-last map over the pixel rectangle rows [r0, r1) x columns [c0, c1):

@@ -101,6 +101,12 @@ class HatYuvSurface(C.Structure):
                 ("sub_x", C.c_int32), ("sub_y", C.c_int32), ("depth", C.c_int32), ("msb", C.c_int32)]
 
 
+class HatPackedSurface(C.Structure):
+    """Mirror of `HatPackedSurface` (include/hat_mi355x.h): one packed 4:2:2 surface; bytes everywhere, layout: the index in yuv.PACKED_FORMATS."""
+    _fields_ = [("base", C.c_void_p), ("pitch", C.c_int64), ("bstride", C.c_int64), ("layout", C.c_int32), ("depth", C.c_int32),
+                ("msb", C.c_int32), ("reserved", C.c_int32)]
+
+
 class HatNafHalfDesc(C.Structure):
     """Mirror of `struct HatNafHalfDesc` (include/hat_mi355x.h)."""
     _fields_ = [("r_in", C.c_void_p), ("gprev", C.c_void_p), ("wf", C.c_void_p), ("bf", C.c_void_p), ("r_out", C.c_void_p),
@@ -227,6 +233,12 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p]),
     "hat_plan_forward_yuv_sited": (C.c_int, [C.c_void_p, C.POINTER(HatYuvSurface), C.c_int32, C.POINTER(HatYuvSurface), C.c_int32, C.c_int32,
                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # packed 4:2:2: one HatPackedSurface per side, the siting beside it; the plan entry takes a packed and a planar pointer a side
+    "hat_packed422_to_planes": (C.c_int, [C.POINTER(HatPackedSurface), C.c_int32, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
+    "hat_planes_to_packed422": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HatPackedSurface), C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p]),
+    "hat_plan_forward_packed422": (C.c_int, [C.c_void_p, C.POINTER(HatPackedSurface), C.POINTER(HatYuvSurface), C.c_int32, C.POINTER(HatPackedSurface),
+                                             C.POINTER(HatYuvSurface), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hat_imresize_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     "hat_imresize_cols_to_planes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,

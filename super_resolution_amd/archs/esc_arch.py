@@ -194,11 +194,12 @@ class _FixedScaleNet(_ESCNet):
             return self.engine(x.device).forward_to_u8(x, crop=crop, bgr=bgr, out=out, ensemble=ensemble)
 
     def upscale_yuv(self, frame, *, fmt: str, out_fmt=None, matrix: str = "bt601", full_range: bool = False, depth: int = 8, out_depth=None,
-                    msb=None, out_msb=None, siting: str = "center", out_siting=None, out=None, ensemble: int = 1):
-        """YCbCr frames of any layout of yuv.LAYOUTS in, any out: HAT.forward_yuv's contract.  A centre-sited output of a shuffle or
-        conv head is stored by the head's fused sink; a co-sited one is converted from planes (hat_planes_to_yuv_sited)."""
+                    msb=None, out_msb=None, siting: str = "center", out_siting=None, out=None, ensemble: int = 1, width=None):
+        """YCbCr frames of any layout of yuv.LAYOUTS or yuv.PACKED_FORMATS in, any out: HAT.forward_yuv's contract.  A centre-sited
+        output of a shuffle or conv head is stored by the head's fused sink; a co-sited or packed one is converted from planes
+        (hat_planes_to_yuv_sited / hat_planes_to_packed422)."""
         return HAT.forward_yuv(self, frame, fmt=fmt, out_fmt=out_fmt, matrix=matrix, full_range=full_range, depth=depth, out_depth=out_depth,
-                               msb=msb, out_msb=out_msb, out=out, ensemble=ensemble, siting=siting, out_siting=out_siting)
+                               msb=msb, out_msb=out_msb, out=out, ensemble=ensemble, siting=siting, out_siting=out_siting, width=width)
 
     def upscale_ensemble(self, x, n: int = 8):
         """The geometric self-ensemble of `forward`: HAT.forward_ensemble's contract (n in 1, 2, 4, 8; the transposed members run

@@ -264,64 +264,50 @@ class ESCLTE(_ESCNet):
             return self._score("score_gt_u8", eng, eng.pil_lr_frame(gt, h_lr, w_lr), gt, eval_type, scale_max)
 
     def upscale_yuv(self, frame, size=None, scale=None, *, fmt: str, out_fmt=None, matrix: str = "bt601", full_range: bool = False, depth: int = 8,
-                    out_depth=None, msb=None, out_msb=None, out=None, siting: str = "center", out_siting=None, scale_max=4):
+                    out_depth=None, msb=None, out_msb=None, out=None, siting: str = "center", out_siting=None, scale_max=4, width=None):
         """A YCbCr frame in, a YCbCr frame of any size out, all on the device: `frame` is a (rows, w) or (1, rows, w) uint8 (uint16
-        with depth 10 / 12 / 16) device tensor in the standard layout of `fmt` (yuv.LAYOUTS); the result is the (H', W') frame in the
-        layout `out_fmt` (default: fmt), (H', W') = size or (int(h scale), int(w scale)), W' even where out_fmt subsamples horizontally
-        and H' where vertically (ValueError otherwise).  fmt, out_fmt, matrix, full_range, depth, out_depth, msb, out_msb, siting,
-        out_siting and out: as `HAT.forward_yuv` takes them.  Equal, bit for bit, to yuv.yuv_to_planes -> `upscale` ->
-        yuv.planes_to_yuv.  A centre-sited output is stored by hat_lte_query_yuv and no fp32 image is written (with out= the call then
-        allocates nothing after the first call of a shape); an output with a co-sited axis ('left' / 'topleft' on a subsampled axis)
-        is the plane query into the workspace, then hat_planes_to_yuv_sited."""
+        with depth 10 / 12 / 16) device tensor in the standard layout of `fmt` (yuv.LAYOUTS or yuv.PACKED_FORMATS); the result is the
+        (H', W') frame in the layout `out_fmt` (default: fmt), (H', W') = size or (int(h scale), int(w scale)), W' even where out_fmt
+        subsamples horizontally and H' where vertically (ValueError otherwise).  fmt, out_fmt, matrix, full_range, depth, out_depth, msb,
+        out_msb, siting, out_siting, width and out: as `HAT.forward_yuv` takes them.  Equal, bit for bit, to yuv.yuv_to_planes ->
+        `upscale` -> yuv.planes_to_yuv (yuv.packed_to_planes / planes_to_packed for a packed side).  A centre-sited planar output is
+        stored by hat_lte_query_yuv and no fp32 image is written (with out= the call then allocates nothing after the first call of a
+        shape); an output with a co-sited axis ('left' / 'topleft' on a subsampled axis) or a packed one is the plane query into the
+        workspace, then hat_planes_to_yuv_sited / hat_planes_to_packed422."""
         if not isinstance(frame, torch.Tensor):
             raise TypeError(f"upscale_yuv needs a uint8 device tensor, got {type(frame).__name__}")
         if frame.dtype not in (torch.uint8, torch.uint16):
             raise TypeError(f"upscale_yuv needs a uint8 tensor (uint16 with depth 10, 12 or 16), got {frame.dtype}")
         from .. import ops, yuv
-        yuv.check_layout(fmt)
         out_fmt = fmt if out_fmt is None else out_fmt
-        yuv.check_layout(out_fmt)
-        yuv.check_siting(siting)
-        out_siting = siting if out_siting is None else yuv.check_siting(out_siting)
+        out_siting = siting if out_siting is None else out_siting
         out_depth = depth if out_depth is None else out_depth
+        src = ops.FrameSide(fmt, depth=depth, msb=msb, siting=siting)   # (refuses what is no layout, depth or siting)
+        dst_side = ops.FrameSide(out_fmt, depth=out_depth, msb=out_msb, siting=out_siting)
         to_rgb, from_rgb = yuv.csc(matrix, full_range, depth)[0], yuv.csc(matrix, full_range, out_depth)[1]
-        in_msb, out_msb = bool(yuv.container(depth, fmt, msb)[3]), bool(yuv.container(out_depth, out_fmt, out_msb)[3])
-        in_dt, out_dt = (torch.uint8 if d == 8 else torch.uint16 for d in (depth, out_depth))
-        if frame.dtype != in_dt:
-            raise TypeError(f"upscale_yuv: depth={depth} needs a {'uint8' if depth == 8 else 'uint16'} tensor, got {frame.dtype}")
+        if frame.dtype != src.dtype:
+            raise TypeError(f"upscale_yuv: depth={depth} {fmt} needs a {str(src.dtype)[6:]} tensor, got {frame.dtype}")
         if frame.dim() == 2:
             frame = frame.unsqueeze(0)
         if frame.dim() != 3:
             raise RuntimeError(f"expected (1,rows,w) {fmt} frames, got {tuple(frame.shape)}")
         if frame.shape[0] != 1:
             raise RuntimeError(f"ESCLTE.upscale_yuv takes one frame per call, got a batch of {frame.shape[0]}")
-        H, W = yuv.frame_size_fmt(frame.shape, fmt)
+        H, W = src.size(frame.shape, width)
         h, w = self._out_size("upscale_yuv", H, W, size, scale)
-        sub = lambda f: None if yuv.LAYOUTS[f][0] is None else yuv.LAYOUTS[f][:2]
-        so = sub(out_fmt)
-        if so is not None and ((so[0] and w % 2) or (so[1] and h % 2)):
-            raise ValueError(f"ESCLTE.upscale_yuv: an output of {h}x{w} is no {out_fmt} frame: the layout needs an even "
-                             + " and an even ".join(n for n, odd in (("width", so[0] and w % 2), ("height", so[1] and h % 2)) if odd))
+        odd = dst_side.size_refusal(h, w)
+        if odd:
+            raise ValueError(f"ESCLTE.upscale_yuv: an output of {h}x{w} is no {out_fmt} frame: the layout needs an even {odd}")
         self._check_call(frame)
         with torch.no_grad():
             eng = self.engine(frame.device)
-            shape, dst = (1,) + yuv.frame_shape_fmt(h, w, out_fmt), out
-            if dst is None:
-                dst = torch.empty(shape, dtype=out_dt, device=eng.dev)
-            elif not isinstance(dst, torch.Tensor) or dst.dtype != out_dt or tuple(dst.shape) != shape or dst.device != eng.dev \
-                    or dst.stride(2) != 1 or dst.stride(1) != w:
-                raise RuntimeError(f"out must be a {shape} {str(out_dt)[6:]} tensor on {eng.dev} with packed rows, got "
-                                   f"{tuple(dst.shape)} {dst.dtype} on {dst.device}")
-            f = frame
-            if f.stride(2) != 1 or f.stride(1) != W:
-                f = f.contiguous() if in_dt is torch.uint8 else f.view(torch.int16).contiguous().view(torch.uint16)
-            eng.gen_feat_frame(H, W, lambda x: ops.yuv_to_planes(*ops.yuv_views(f, fmt), x, to_rgb, sub=sub(fmt), depth=depth, msb=in_msb,
-                                                                 siting=siting))
+            dst = dst_side.out(out, (1,) + dst_side.shape(h, w), eng.dev)
+            eng.gen_feat_frame(H, W, lambda x: src.to_planes(frame, x, to_rgb, width=W))
             self._feat_engine = eng
-            cells, views = self._cells(H, W, h, w, scale_max), ops.yuv_views(dst, out_fmt)
-            if ops._siting(so, out_siting)[0] == "center":
-                eng.query_grid_yuv(views, cells, from_rgb, so, out_depth, out_msb)
-            else:   # the 2-tap filter of a co-sited axis needs a halo a 4 x 8 tile does not have
+            cells = self._cells(H, W, h, w, scale_max)
+            if dst_side.fusable:
+                eng.query_grid_yuv(dst_side.views(dst), cells, from_rgb, dst_side.sub, out_depth, dst_side.msb)
+            else:   # the 2-tap filter of a co-sited axis needs a halo a 4 x 8 tile does not have; a packed unit spans tiles
                 planes = eng.query_grid_planes(eng.planes_buffer(H, W, h, w), cells, out_affine=(0.5, 0.5))
-                ops.planes_to_yuv(planes, *views, from_rgb, sub=so, depth=out_depth, msb=out_msb, siting=out_siting)
+                dst_side.from_planes(planes, dst, from_rgb, width=w)
             return dst

@@ -459,7 +459,7 @@ class HAT(nn.Module):
                                 out_msb=msb, out=out, ensemble=ensemble, siting=siting, out_siting=out_siting)
 
     def forward_yuv(self, frame, *, fmt: str, out_fmt=None, matrix: str = "bt601", full_range: bool = False, depth: int = 8, out_depth=None,
-                    msb=None, out_msb=None, out=None, ensemble: int = 1, siting: str = "center", out_siting=None):
+                    msb=None, out_msb=None, out=None, ensemble: int = 1, siting: str = "center", out_siting=None, width=None):
         """YCbCr frames of any chroma subsampling in, any out, all on the device: `frame` is a (rows, w) or (B, rows, w) uint8
         (uint16 with depth 10 / 12 / 16) device tensor in the standard contiguous layout of `fmt`, one of yuv.ALL_FORMATS —
         'nv12' 'nv21' 'i420' (4:2:0), 'i422' 'nv16' (4:2:2), 'i444' 'nv24' (4:4:4), 'gray' — and the result is the s-times larger
@@ -473,27 +473,33 @@ class HAT(nn.Module):
         box down: the call as it always was), 'left' (MPEG-2, H.264, HEVC, AV1 4:2:0 and all standard 4:2:2) or 'topleft'
         (BT.2020); out_siting: the result's (None: the input's).  A siting applies to the subsampled axes only, so it is
         ignored by 4:4:4 and grey.  The call stays bit-equal to the composition with the same siting= on both yuv.py functions;
-        an output with a co-sited axis is written from fp32 planes (hat_planes_to_yuv_sited), not in conv_last's epilogue."""
+        an output with a co-sited axis is written from fp32 planes (hat_planes_to_yuv_sited), not in conv_last's epilogue.
+        Packed 4:2:2: fmt and out_fmt also take yuv.PACKED_FORMATS, in any combination with the layouts above — 'uyvy' and 'yuy2'
+        (depth 8, (h, 2w) uint8), 'y210' (depth 10 / 12 / 16, (h, 2w) uint16, MSB-aligned by default) and 'v210' (depth 10, (h, 128
+        ceil(w / 48)) uint8; width= is required, ValueError without it: the array does not give it).  The samples mean what 'i422'
+        samples mean (yuv.packed_to_planes / planes_to_packed) and the result equals the 'i422' call on the unpacked frame, repacked.
+        A packed output is written from fp32 planes (hat_planes_to_packed422).  Standard 4:2:2 video is siting='left'."""
         if not isinstance(frame, torch.Tensor):
             raise TypeError(f"forward_yuv needs a uint8 device tensor, got {type(frame).__name__}")
         if frame.dtype not in (torch.uint8, torch.uint16):
             raise TypeError(f"forward_yuv needs a uint8 tensor (uint16 with depth 10, 12 or 16), got {frame.dtype}")
         self._check_u8_input(frame)
-        from .. import yuv
-        yuv.check_layout(fmt)
-        yuv.check_layout(fmt if out_fmt is None else out_fmt)
-        yuv.check_siting(siting)
-        out_siting = siting if out_siting is None else yuv.check_siting(out_siting)
+        from .. import ops, yuv
+        out_siting = siting if out_siting is None else out_siting
         out_depth = depth if out_depth is None else out_depth
+        src = ops.FrameSide(fmt, depth=depth, msb=msb, siting=siting)   # (refuses what is no layout, depth or siting)
+        ops.FrameSide(fmt if out_fmt is None else out_fmt, depth=out_depth, msb=out_msb, siting=out_siting)
         to_rgb, from_rgb = yuv.csc(matrix, full_range, depth)[0], yuv.csc(matrix, full_range, out_depth)[1]
-        if frame.dtype != (torch.uint8 if depth == 8 else torch.uint16):
-            raise TypeError(f"forward_yuv: depth={depth} needs a {'uint8' if depth == 8 else 'uint16'} tensor, got {frame.dtype}")
+        if frame.dtype != src.dtype:
+            raise TypeError(f"forward_yuv: depth={depth} {fmt} needs a {str(src.dtype)[6:]} tensor, got {frame.dtype}")
+        if fmt == "v210" and width is None:
+            raise ValueError("forward_yuv: a v210 frame does not give its width (a row is 128 ceil(w / 48) bytes): pass width=")
         if frame.dim() == 2:
             frame = frame.unsqueeze(0)
         with torch.no_grad():
             return self.engine(frame.device).forward_yuv(frame, fmt=fmt, out_fmt=out_fmt, to_rgb=to_rgb, from_rgb=from_rgb, out=out,
                                                          depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, ensemble=ensemble,
-                                                         siting=siting, out_siting=out_siting)
+                                                         siting=siting, out_siting=out_siting, width=width)
 
     # ---- exact full-frame sharding into row bands (SURVEY §8 f4; no counterpart in the reference, whose tile loop
     # hat_model.py:40-108 gives a DIFFERENT result than the full frame: SURVEY F6) ----

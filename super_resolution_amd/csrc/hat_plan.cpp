@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/hat_mi355x.h"
+#include "hat_packed_check.h"
 #include "hat_plan_parse.h"
 #include "hat_yuv_check.h"
 
@@ -265,37 +266,48 @@ int frame_fits(const hat_plan* p, int32_t h, int32_t w) {
     return h > H || w > W || H - h >= h || W - w >= w ? HAT_EINVAL : 0;
 }
 
+// One side of a YCbCr frame forward: a planar / semi-planar surface or a packed 4:2:2 one (exactly one is set), and its siting.
+struct FrameSide {
+    const HatYuvSurface* planar;
+    const HatPackedSurface* packed;
+    int32_t siting;
+    bool ok(int32_t B, int64_t h, int64_t w) const { return packed ? hat_packed_surface_ok(packed, B, h, w) : hat_yuv_surface_ok(planar, B, h, w); }
+    bool centre() const { return !packed && hat_siting_of(planar, siting) == HAT_SITING_CENTER; }   // (of a checked surface)
+};
+
 // hat_plan_forward_yuv after its NULL checks.  The 4:2:0 entries come here with the (1,1) surfaces of their blocks and their own
-// from-planes entry (planes420: its grid takes frames twice as tall as hat_planes_to_yuv's).
-int forward_yuv(const hat_plan* p, const HatYuvSurface* src, const HatYuvSurface* dst, int32_t h, int32_t w, const float* to_rgb12,
-                const float* from_rgb12, void* stream, bool planes420, int32_t src_siting = HAT_SITING_CENTER,
-                int32_t dst_siting = HAT_SITING_CENTER) {
+// from-planes entry (planes420: its grid takes frames twice as tall as hat_planes_to_yuv's).  A packed side (hat_plan_forward_packed422)
+// has no fused ending, like a co-sited one.
+int forward_yuv(const hat_plan* p, const FrameSide& src, const FrameSide& dst, int32_t h, int32_t w, const float* to_rgb12,
+                const float* from_rgb12, void* stream, bool planes420) {
     // what needs no plan first (a B of 1 stands in: the batch strides are checked against the plan's B below)
-    if (!hat_yuv_surface_ok(src, 1, h, w)) return HAT_EINVAL;
+    if (!src.ok(1, h, w)) return HAT_EINVAL;
     if (const int rc = frame_fits(p, h, w)) return rc;
     const int32_t B = p->dims[0], H = p->dims[2], W = p->dims[3], s = p->dims[4], ho = s * h, wo = s * w;
     // both surfaces in full before anything is enqueued (the kernels' own checks would refuse the destination only after the replay)
-    if (!hat_yuv_surface_ok(src, B, h, w) || !hat_yuv_surface_ok(dst, B, (int64_t)s * h, (int64_t)s * w)) return HAT_EINVAL;
-    const bool sited_out = hat_siting_of(dst, dst_siting) != HAT_SITING_CENTER;   // (a sited entry: never planes420)
+    if (!src.ok(B, h, w) || !dst.ok(B, (int64_t)s * h, (int64_t)s * w)) return HAT_EINVAL;
+    const bool sited_out = !dst.centre();   // (a sited or packed entry: never planes420)
     return forward_frames(
         p, stream,
         [&](float* in) {
-            if (hat_siting_of(src, src_siting) == HAT_SITING_CENTER) return hat_yuv_to_planes(src, in, B, h, w, H, W, to_rgb12, stream);
-            return hat_yuv_to_planes_sited(src, src_siting, in, B, h, w, H, W, to_rgb12, stream);
+            if (src.packed) return hat_packed422_to_planes(src.packed, src.siting, in, B, h, w, H, W, to_rgb12, stream);
+            if (src.centre()) return hat_yuv_to_planes(src.planar, in, B, h, w, H, W, to_rgb12, stream);
+            return hat_yuv_to_planes_sited(src.planar, src.siting, in, B, h, w, H, W, to_rgb12, stream);
         },
         [&](Resolved& r, Ending ending) {
             if (ending == ENDS_FOLDED) {
                 const HatConvDesc* d = (const HatConvDesc*)r.P(0);
-                return hat_upfold_to_yuv(d->x, d->w, d->bias, dst, d->B, d->H, d->W, d->ldx, ho, wo, d->out_scale, d->mean[0], d->mean[1], d->mean[2],
-                                         from_rgb12, d->dtype, stream);
+                return hat_upfold_to_yuv(d->x, d->w, d->bias, dst.planar, d->B, d->H, d->W, d->ldx, ho, wo, d->out_scale, d->mean[0], d->mean[1],
+                                         d->mean[2], from_rgb12, d->dtype, stream);
             }
-            return hat_conv3x3_to_yuv(r.P(0), r.P(1), (const float*)r.P(2), dst, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10),
+            return hat_conv3x3_to_yuv(r.P(0), r.P(1), (const float*)r.P(2), dst.planar, r.I(4), r.I(5), r.I(6), r.I(7), r.I(8), ho, wo, r.F(10),
                                       (const float*)r.P(11), from_rgb12, r.I(12), stream);
         },
         [&](const float* out, int32_t Hs, int32_t Ws) {
-            const HatYuvSurface& d = *dst;
-            if (sited_out) return hat_planes_to_yuv_sited(out, B, Hs, Ws, dst, dst_siting, ho, wo, from_rgb12, stream);
-            if (!planes420) return hat_planes_to_yuv(out, B, Hs, Ws, dst, ho, wo, from_rgb12, stream);
+            if (dst.packed) return hat_planes_to_packed422(out, B, Hs, Ws, dst.packed, dst.siting, ho, wo, from_rgb12, stream);
+            const HatYuvSurface& d = *dst.planar;
+            if (sited_out) return hat_planes_to_yuv_sited(out, B, Hs, Ws, dst.planar, dst.siting, ho, wo, from_rgb12, stream);
+            if (!planes420) return hat_planes_to_yuv(out, B, Hs, Ws, dst.planar, ho, wo, from_rgb12, stream);
             if (d.depth == 8)
                 return hat_planes_to_yuv420(out, B, Hs, Ws, (uint8_t*)d.y, d.y_pitch, d.y_bstride, (uint8_t*)d.cb, (uint8_t*)d.cr, d.c_pitch, d.c_step,
                                             d.c_bstride, ho, wo, from_rgb12, stream);
@@ -303,6 +315,13 @@ int forward_yuv(const hat_plan* p, const HatYuvSurface* src, const HatYuvSurface
                                            d.c_bstride, ho, wo, from_rgb12, d.depth, d.msb, stream);
         },
         !sited_out);
+}
+
+// the planar sides of the entries that know no packed surface
+int forward_yuv(const hat_plan* p, const HatYuvSurface* src, const HatYuvSurface* dst, int32_t h, int32_t w, const float* to_rgb12,
+                const float* from_rgb12, void* stream, bool planes420, int32_t src_siting = HAT_SITING_CENTER,
+                int32_t dst_siting = HAT_SITING_CENTER) {
+    return forward_yuv(p, FrameSide{src, nullptr, src_siting}, FrameSide{dst, nullptr, dst_siting}, h, w, to_rgb12, from_rgb12, stream, planes420);
 }
 }  // namespace
 
@@ -369,4 +388,14 @@ extern "C" int hat_plan_forward_yuv_sited(const hat_plan* p, const HatYuvSurface
     if (!p || !src || !dst || !to_rgb12 || !from_rgb12 || h < 1 || w < 1 || !hat_siting_ok(src_siting) || !hat_siting_ok(dst_siting))
         return HAT_EINVAL;
     return forward_yuv(p, src, dst, h, w, to_rgb12, from_rgb12, stream, false, src_siting, dst_siting);
+}
+
+// The same forward with a packed 4:2:2 surface on either side or on both: exactly one of the two pointers of a side is set.
+extern "C" int hat_plan_forward_packed422(const hat_plan* p, const HatPackedSurface* src_packed, const HatYuvSurface* src_planar,
+                                          int32_t src_siting, const HatPackedSurface* dst_packed, const HatYuvSurface* dst_planar,
+                                          int32_t dst_siting, int32_t h, int32_t w, const float* to_rgb12, const float* from_rgb12, void* stream) {
+    if (!p || !to_rgb12 || !from_rgb12 || h < 1 || w < 1 || !hat_siting_ok(src_siting) || !hat_siting_ok(dst_siting)) return HAT_EINVAL;
+    if (!src_packed == !src_planar || !dst_packed == !dst_planar) return HAT_EINVAL;
+    return forward_yuv(p, FrameSide{src_planar, src_packed, src_siting}, FrameSide{dst_planar, dst_packed, dst_siting}, h, w, to_rgb12, from_rgb12,
+                       stream, false);
 }

@@ -81,6 +81,28 @@ class _YuvSink(_Sink):
         self._count("planes")
 
 
+class _PackedSink(_Sink):
+    """out in a packed 4:2:2 layout of yuv.PACKED_FORMATS (side: its ops.FrameSide).  No kernel that ends a network has a packed
+    epilogue, so the sink is never fusable: it ends in fp32 planes and hat_planes_to_packed422, and counts under yuv_planes_calls."""
+    kind, band_refusal, fusable = "yuv", _YuvSink.band_refusal, False
+
+    def __init__(self, eng, out, side, from_rgb, width):
+        super().__init__(eng, out, (out.shape[1], width))
+        self.side, self.from_rgb, self.width = side, from_rgb, width
+
+    def from_planes(self, y):
+        self.side.from_planes(y, self.out, self.from_rgb, width=self.width)
+        self._count("planes")
+
+
+def yuv_sink(eng, out, side, from_rgb, width):
+    """The sink of a YCbCr result `out` (already checked: side.out) whose layout, depth and siting are the ops.FrameSide `side`;
+    width: the result's width in pixels (a v210 array does not give it)."""
+    if side.packed:
+        return _PackedSink(eng, out, side, from_rgb, width)
+    return _YuvSink(eng, out, side.views(out), from_rgb, sub=side.sub, depth=side.depth, msb=side.msb, siting=side.siting)
+
+
 class FrameBoundary:
     """Requires of its host engine: `_forward(x, one_stream=, sink=)` and `_check_input(x)`; `_workspace`, `scale`, `ws`, `dev`,
     `_lock` and `cfg["in_chans"]`; and the four counters `u8_fused_calls`, `u8_planes_calls`, `yuv_fused_calls`, `yuv_planes_calls`,
@@ -280,51 +302,33 @@ class FrameBoundary:
                                 msb=msb, out_msb=msb, ensemble=ensemble, siting=siting, out_siting=out_siting)
 
     def forward_yuv(self, frame: torch.Tensor, *, fmt: str, out_fmt=None, to_rgb, from_rgb, out=None, depth: int = 8, out_depth=None,
-                    msb=None, out_msb=None, ensemble: int = 1, siting: str = "center", out_siting=None) -> torch.Tensor:
-        """(B,rows,w) device frames in the layout `fmt` of yuv.LAYOUTS, any size the layout and the reflection allow -> the frames
-        of the s-times larger image in the layout `out_fmt` (default: fmt), any subsampling or grey to any other:
-        hat_yuv_to_planes into this shape's workspace, the forward, the crop and the conversion back (in conv_last's epilogue,
-        hat_conv3x3_to_yuv, or hat_planes_to_yuv).  to_rgb / from_rgb: yuv.csc's matrices (of `depth` / `out_depth`).  out: the
-        caller's result tensor.  depth / out_depth 10, 12, 16: uint16 frames on that side (yuv.py, "Deep samples"; out_depth
-        defaults to depth); msb / out_msb: MSB-aligned words on that side (default: by the layout).  ensemble 2 / 4 / 8: the
-        padded RGB planes go through forward_ensemble, then hat_planes_to_yuv with the crop.  siting / out_siting (yuv.SITINGS;
-        out_siting defaults to siting): the chroma siting of each side; a co-sited output ends in hat_conv3x3_to_planes and
-        hat_planes_to_yuv_sited (yuv_planes_calls counts it), never in conv_last's epilogue."""
+                    msb=None, out_msb=None, ensemble: int = 1, siting: str = "center", out_siting=None, width=None) -> torch.Tensor:
+        """(B,rows,w) device frames in the layout `fmt` of yuv.LAYOUTS or yuv.PACKED_FORMATS, any size the layout and the reflection
+        allow -> the frames of the s-times larger image in the layout `out_fmt` (default: fmt), any subsampling, grey or packed
+        4:2:2 to any other: hat_yuv_to_planes (hat_packed422_to_planes) into this shape's workspace, the forward, the crop and the
+        conversion back (in conv_last's epilogue, hat_conv3x3_to_yuv, or hat_planes_to_yuv / hat_planes_to_packed422).  to_rgb /
+        from_rgb: yuv.csc's matrices (of `depth` / `out_depth`).  out: the caller's result tensor.  depth / out_depth 10, 12, 16:
+        uint16 frames on that side (yuv.py, "Deep samples"; out_depth defaults to depth; a v210 side has depth 10 and uint8 frames);
+        msb / out_msb: MSB-aligned words on that side (default: by the layout).  ensemble 2 / 4 / 8: the padded RGB planes go through
+        forward_ensemble, then the from-planes kernel with the crop.  siting / out_siting (yuv.SITINGS; out_siting defaults to
+        siting): the chroma siting of each side; a co-sited or packed output ends in hat_conv3x3_to_planes and the from-planes kernel
+        (yuv_planes_calls counts it), never in conv_last's epilogue.  width: the source's width in pixels, required where fmt is
+        'v210' (ValueError without it) and checked for every other layout."""
         self._check_u8()
         ensemble = ops.ensemble_members(ensemble)
-        from . import yuv as _yuv
-        siting = _yuv.check_siting(siting)
-        out_siting = siting if out_siting is None else _yuv.check_siting(out_siting)
-        out_fmt = fmt if out_fmt is None else out_fmt
-        out_depth = depth if out_depth is None else out_depth
-        in_msb, out_msb = bool(_yuv.container(depth, fmt, msb)[3]), bool(_yuv.container(out_depth, out_fmt, out_msb)[3])
-        in_dt, out_dt = (torch.uint8 if d == 8 else torch.uint16 for d in (depth, out_depth))
+        out_siting = siting if out_siting is None else out_siting
+        src = ops.FrameSide(fmt, depth=depth, msb=msb, siting=siting)
+        dst = ops.FrameSide(fmt if out_fmt is None else out_fmt, depth=depth if out_depth is None else out_depth, msb=out_msb, siting=out_siting)
         if not isinstance(frame, torch.Tensor) or frame.dtype not in (torch.uint8, torch.uint16):
             raise TypeError(f"expected (B,rows,w) uint8 frames, got {getattr(frame, 'dtype', type(frame))}")
-        if frame.dtype != in_dt:
-            raise TypeError(f"{depth}-bit frames are {in_dt} tensors (uint8 holds 8-bit samples, uint16 deeper ones), got {frame.dtype}")
+        if frame.dtype != src.dtype:
+            raise TypeError(f"{src.depth}-bit {fmt} frames are {src.dtype} tensors (uint8 holds 8-bit samples and v210 rows, uint16 deeper ones), "
+                            f"got {frame.dtype}")
         if frame.dim() != 3:
             raise RuntimeError(f"expected (B,rows,w) {fmt} frames, got {tuple(frame.shape)}")
         if not frame.is_cuda or frame.device != self.dev:
             raise RuntimeError(f"HAT forward needs a tensor on {self.dev}: the HIP path is the only path")
-        h, w = _yuv.frame_size_fmt(frame.shape, fmt)
+        h, w = src.size(frame.shape, width)
         B, s = frame.shape[0], self._out_factor()
-        sub = lambda f: None if _yuv.LAYOUTS[f][0] is None else _yuv.LAYOUTS[f][:2]
-
-        def fill(x):
-            f = frame
-            if f.stride(2) != 1 or f.stride(1) != w:
-                f = f.contiguous() if in_dt is torch.uint8 else f.view(torch.int16).contiguous().view(torch.uint16)
-            ops.yuv_to_planes(*ops.yuv_views(f, fmt), x, to_rgb, sub=sub(fmt), depth=depth, msb=in_msb, siting=siting)
-
-        def make_sink():
-            shape, dst = (B,) + _yuv.frame_shape_fmt(s * h, s * w, out_fmt), out
-            if dst is None:
-                dst = torch.empty(shape, dtype=out_dt, device=self.dev)
-            elif not isinstance(dst, torch.Tensor) or dst.dtype != out_dt or tuple(dst.shape) != shape or dst.device != self.dev \
-                    or dst.stride(2) != 1 or dst.stride(1) != s * w:
-                raise RuntimeError(f"out must be a {shape} {str(out_dt)[6:]} tensor on {self.dev} with packed rows, got "
-                                   f"{tuple(dst.shape)} {dst.dtype} on {dst.device}")
-            return _YuvSink(self, dst, ops.yuv_views(dst, out_fmt), from_rgb, sub=sub(out_fmt), depth=out_depth, msb=out_msb, siting=out_siting)
-
-        return self._frame_forward(B, h, w, fill, make_sink, ensemble)
+        return self._frame_forward(B, h, w, lambda x: src.to_planes(frame, x, to_rgb, width=w),
+                                   lambda: yuv_sink(self, dst.out(out, (B,) + dst.shape(s * h, s * w), self.dev), dst, from_rgb, s * w), ensemble)

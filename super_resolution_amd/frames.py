@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 
-PIXFMTS = ("rgb24", "nv12", "nv21", "i420", "i422", "nv16", "i444", "nv24", "gray")
+PIXFMTS = ("rgb24", "nv12", "nv21", "i420", "i422", "nv16", "i444", "nv24", "gray", "uyvy", "yuy2", "y210", "v210")
 
 
 def _raw(t):
@@ -55,7 +55,7 @@ def entry_points(net, arb: bool = False):
 
 def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", matrix: str = "bt601", full_range: bool = False, depth: int = 8,
                    out_depth=None, msb=None, ensemble: int = 1, out_pixfmt=None, out_msb=None, siting: str = "center", out_siting=None,
-                   size=None, scale=None):
+                   size=None, scale=None, width=None):
     """Generator: for every (h,w,3) uint8 array of `frames` (all of one size) yield the (s*h,s*w,3) uint8 array that
     `net.forward_u8` computes for it, in order.  `net`: a HAT / HATX module on a GPU, in eval mode.  The yielded array is
     the caller's own (copied out of the pinned buffer).  An empty sequence yields nothing.
@@ -66,6 +66,9 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
     pixfmt 'i422' / 'nv16' / 'i444' / 'nv24' / 'gray', or out_pixfmt (any layout of yuv.LAYOUTS; default: pixfmt) different from
     pixfmt: the frames are arrays of yuv.frame_shape_fmt in that layout and every frame goes through `net.forward_yuv` (any
     subsampling in, any out; out_msb: the output words' alignment), in the same two-slot pipeline.
+    pixfmt / out_pixfmt 'uyvy' / 'yuy2' / 'y210' / 'v210' (yuv.PACKED_FORMATS; depth 8, 8, 10 / 12 / 16, 10 on that side): packed 4:2:2
+    frames, arrays of yuv.packed_shape, through `net.forward_yuv` in the same pipeline; width=: the frames' width in pixels, required
+    for 'v210' frames (the array does not give it) and checked for every other YCbCr pixfmt.
     ensemble 2 / 4 / 8: every frame through the geometric self-ensemble (HAT.forward_ensemble) of that many members.
     siting / out_siting (YCbCr pixel formats; yuv.SITINGS): the chroma siting of the frames and of the yielded frames (default:
     the input's), as HAT.forward_yuv takes them; 'center' is the sequence as it always was.
@@ -88,6 +91,8 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
     skw = {} if (siting, out_siting) == ("center", "center") else {"siting": siting, "out_siting": out_siting}
     if skw and pixfmt == "rgb24":
         raise RuntimeError("siting and out_siting belong to the YCbCr pixel formats")
+    if width is not None and pixfmt == "rgb24":
+        raise RuntimeError("width belongs to the YCbCr pixel formats (a v210 frame does not give its own)")
     arb = size is not None or scale is not None
     if arb:
         entry_points(net, arb=True)
@@ -122,23 +127,25 @@ def upscale_frames(net, frames, *, bgr: bool = False, pixfmt: str = "rgb24", mat
             out_msb = msb   # (what forward_yuv420 makes of msb: the alignment of both sides)
         out_pixfmt = pixfmt if out_pixfmt is None else out_pixfmt
         out_depth = depth if out_depth is None else out_depth
-        in_np = _yuv.container(depth, pixfmt, msb)[0]
-        _yuv.container(out_depth, out_pixfmt, out_msb)
-        in_dt, out_dt = (torch.uint8 if d == 8 else torch.uint16 for d in (depth, out_depth))
+        from .ops import FrameSide
+        a, b = FrameSide(pixfmt, depth=depth, msb=msb, siting=siting), FrameSide(out_pixfmt, depth=out_depth, msb=out_msb, siting=out_siting)
+        in_dt, out_dt = a.dtype, b.dtype
+        in_np = np.uint8 if in_dt is torch.uint8 else np.uint16
         if first.ndim != 2 or first.dtype != in_np:
             raise RuntimeError(f"expected (rows,w) {np.dtype(in_np).name} {pixfmt} frames, got {first.shape} {first.dtype}")
-        h, w = _yuv.frame_size_fmt(first.shape, pixfmt)
+        h, w = a.size(first.shape, width)
         in_shape, shape_text = first.shape, str(tuple(first.shape)).replace(" ", "")
         if arb:
             oh, ow = out_hw(h, w)
-            so = _yuv.LAYOUTS[out_pixfmt]
-            if oh < 1 or ow < 1 or (so[0] is not None and ((so[0] and ow % 2) or (so[1] and oh % 2))):
+            if oh < 1 or ow < 1 or b.size_refusal(oh, ow):
                 raise ValueError(f"upscale_frames: an output of {oh}x{ow} is no {out_pixfmt} frame")
-        out_shape = _yuv.frame_shape_fmt(*out_hw(h, w), out_pixfmt)
+        out_shape = b.shape(*out_hw(h, w))
+        if width is not None:
+            skw = dict(skw, width=w)
         if arb:
             forward = lambda src, dst: getattr(net, name_yuv)(src, size=out_hw(h, w), fmt=pixfmt, out_fmt=out_pixfmt, matrix=matrix, full_range=full_range,
                                                        out=dst, depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, siting=siting,
-                                                       out_siting=out_siting)
+                                                       out_siting=out_siting, **({} if width is None else {"width": w}))
         else:
             forward = lambda src, dst: getattr(net, name_yuv)(src, fmt=pixfmt, out_fmt=out_pixfmt, matrix=matrix, full_range=full_range, out=dst,
                                                        depth=depth, out_depth=out_depth, msb=msb, out_msb=out_msb, ensemble=ensemble, **skw)

@@ -8,6 +8,7 @@ import collections
 import ctypes as C
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1184,6 +1185,134 @@ def upfold_to_yuv(x, pf, y, cb, cr, *, sub, B: int, H: int, W: int, ldx: int, ou
         lib.hat_upfold_to_yuv(_ptr(x), _ptr(pf.w), _ptr(pf.bias), C.byref(surf), B, H, W, ldx, y.shape[1], y.shape[2], out_scale, float(mean[0]),
                               float(mean[1]), float(mean[2]), m, dtype, _stream()), "hat_upfold_to_yuv"),
         tag=f"k5 64->2x2x3 {H}x{W} folded {name}", nbytes=_upfold_bytes(B, H, W, B * y.shape[1] * y.shape[2] * 2))
+
+
+def packed_surface(frame, fmt: str, *, width=None, depth=None, msb=None, what: str = "packed_surface"):
+    """(HatPackedSurface, h, w) of frame (B, h, row): device frames in the packed 4:2:2 layout `fmt` of yuv.PACKED_FORMATS, uint8
+    (uyvy, yuy2, v210) or uint16 (y210) with unit-step rows of yuv.packed_shape's length; rows and frames may be pitched (a view of a
+    larger tensor).  width: required for v210, checked otherwise.  The struct holds a raw pointer: keep `frame` alive while it is used."""
+    from . import yuv as _yuv
+    dt, depth, msb = _yuv.packed_container(fmt, depth, msb)
+    tdt = torch.uint8 if dt is np.uint8 else torch.uint16
+    if not isinstance(frame, torch.Tensor) or frame.dim() != 3 or frame.dtype != tdt:
+        raise TypeError(f"{what} needs (B,h,row) {str(tdt)[6:]} {fmt} frames, got {getattr(frame, 'dtype', type(frame))} {tuple(getattr(frame, 'shape', ()))}")
+    if not frame.is_cuda or frame.stride(2) != 1:
+        raise RuntimeError("HAT HIP ops need device tensors with unit-step rows (no CPU path exists)")
+    h, w = _yuv.packed_size(frame.shape, fmt, width)
+    n = frame.element_size()
+    s = _lib.HatPackedSurface(base=frame.data_ptr(), pitch=n * frame.stride(1), bstride=n * frame.stride(0), layout=_yuv.PACKED_FORMATS.index(fmt),
+                              depth=depth, msb=int(msb))
+    return s, h, w
+
+
+def packed422_to_planes(frame, dst, to_rgb, *, fmt: str, width=None, depth=None, msb=None, siting: str = "center"):
+    """frame (B,h,row) in the packed 4:2:2 layout `fmt` (packed_surface) -> dst (B,3,Hp,Wp) fp32 RGB planes, rows and columns past
+    (h, w) filled by reflection: yuv.packed_to_planes' conversion (hat_packed422_to_planes)."""
+    lib = _lib.load()
+    eff, code = _siting((1, 0), siting)
+    surf, h, w = packed_surface(frame, fmt, width=width, depth=depth, msb=msb, what="packed422_to_planes")
+    B = frame.shape[0]
+    if dst.dtype != torch.float32 or dst.dim() != 4 or dst.shape[0] != B or dst.shape[1] != 3 or dst.shape[2] < h or dst.shape[3] < w \
+            or dst.device != frame.device or not dst.is_contiguous():
+        raise RuntimeError(f"packed422_to_planes needs a contiguous (B,3,Hp>=h,Wp>=w) fp32 destination on {frame.device}, got "
+                           f"{tuple(dst.shape)} {dst.dtype} on {dst.device} for {B} frames of {h}x{w}")
+    m = _f12(to_rgb)
+    _timed(f"packed422_to_planes_kernel<{fmt}, {eff}>", 0.0, lambda: _lib.check(
+        lib.hat_packed422_to_planes(C.byref(surf), code, _ptr(dst), B, h, w, dst.shape[2], dst.shape[3], m, _stream()), "hat_packed422_to_planes"),
+        tag=f"{fmt} {eff} {h}x{w} -> planes {dst.shape[2]}x{dst.shape[3]}")
+
+
+def planes_to_packed422(src, frame, from_rgb, *, fmt: str, width=None, depth=None, msb=None, siting: str = "center"):
+    """src (B,3,Hs,Ws) fp32 planes -> the top-left h x w pixels as frame (B,h,row) in the packed 4:2:2 layout `fmt` (packed_surface),
+    converted as yuv.planes_to_packed converts (hat_planes_to_packed422).  Bytes of a pitched row past the layout's row are not written."""
+    lib = _lib.load()
+    eff, code = _siting((1, 0), siting)
+    surf, h, w = packed_surface(frame, fmt, width=width, depth=depth, msb=msb, what="planes_to_packed422")
+    B = frame.shape[0]
+    if src.dim() != 4 or src.shape[0] != B or src.shape[1] != 3 or src.dtype != torch.float32 or src.device != frame.device or not src.is_contiguous():
+        raise RuntimeError(f"planes_to_packed422 needs contiguous (B,3,Hs,Ws) fp32 planes on {frame.device}, got {tuple(src.shape)} "
+                           f"{src.dtype} on {src.device}")
+    m = _f12(from_rgb)
+    _timed(f"planes_to_packed422_kernel<{fmt}, {eff}>", 0.0, lambda: _lib.check(
+        lib.hat_planes_to_packed422(_ptr(src), B, src.shape[2], src.shape[3], C.byref(surf), code, h, w, m, _stream()), "hat_planes_to_packed422"),
+        tag=f"planes {src.shape[2]}x{src.shape[3]} -> {fmt} {eff} {h}x{w}")
+
+
+class FrameSide:
+    """One side of a YCbCr frame call, resolved once: the layout `fmt` (yuv.LAYOUTS: planes and semi-planes; yuv.PACKED_FORMATS: packed
+    4:2:2), its sample depth, word alignment and chroma siting.  The ONE place that tells the two kinds of layout apart: frame entry
+    points ask it for the frame's dtype, size and shape, have it fill the planes from a frame (to_planes) and write a frame from
+    planes (from_planes); `fusable` says whether the kernels that end a network have an epilogue for it (views: their destination)."""
+
+    def __init__(self, fmt: str, *, depth: int = 8, msb=None, siting: str = "center"):
+        from . import yuv as _yuv
+        self.fmt, self.packed = fmt, fmt in _yuv.PACKED_FORMATS
+        _yuv.check_siting(siting)
+        if self.packed:
+            dt, self.depth, self.msb = _yuv.packed_container(fmt, depth, msb)
+            self.sub = (1, 0)
+        else:
+            sub_x, sub_y, _ = _yuv.check_layout(fmt)
+            dt, _, _, shift = _yuv.container(depth, fmt, msb)
+            self.depth, self.msb, self.sub = int(depth), bool(shift), None if sub_x is None else (sub_x, sub_y)
+        self.dtype = torch.uint8 if dt is np.uint8 else torch.uint16
+        self.siting = _siting(self.sub, siting)[0]
+        self.fusable = not self.packed and self.siting == "center"
+
+    def size(self, shape, width=None):
+        """(h, w) of a frame array of this layout; width: required for v210, checked for every other layout."""
+        from . import yuv as _yuv
+        if self.packed:
+            return _yuv.packed_size(shape, self.fmt, width)
+        h, w = _yuv.frame_size_fmt(shape, self.fmt)
+        if width is not None and int(width) != w:
+            raise ValueError(f"width={width} does not agree with a {self.fmt} frame of {tuple(shape)}: its rows hold {w} pixels")
+        return h, w
+
+    def shape(self, h: int, w: int):
+        from . import yuv as _yuv
+        return _yuv.packed_shape(h, w, self.fmt) if self.packed else _yuv.frame_shape_fmt(h, w, self.fmt)
+
+    def size_refusal(self, h: int, w: int):
+        """None if an h x w frame exists in this layout, else the axes that would have to be even, as words."""
+        sx, sy = (0, 0) if self.sub is None else self.sub
+        odd = [n for n, bad in (("width", sx and w % 2), ("height", sy and h % 2)) if bad]
+        return " and an even ".join(odd) if odd else None
+
+    def rows_packed(self, t) -> bool:
+        """t (B, rows, cols) lies in the standard contiguous layout (rows one row apart)."""
+        return t.stride(2) == 1 and t.stride(1) == t.shape[2]
+
+    def contiguous(self, frame):
+        if self.rows_packed(frame):
+            return frame
+        return frame.contiguous() if frame.dtype is torch.uint8 else frame.view(torch.int16).contiguous().view(torch.uint16)
+
+    def out(self, out, shape, dev):
+        """The result tensor of `shape`: the caller's `out` (checked) or a fresh one."""
+        if out is None:
+            return torch.empty(shape, dtype=self.dtype, device=dev)
+        if not isinstance(out, torch.Tensor) or out.dtype != self.dtype or tuple(out.shape) != tuple(shape) or out.device != dev \
+                or not self.rows_packed(out):
+            raise RuntimeError(f"out must be a {tuple(shape)} {str(self.dtype)[6:]} tensor on {dev} with packed rows, got "
+                               f"{tuple(getattr(out, 'shape', ()))} {getattr(out, 'dtype', type(out))} on {getattr(out, 'device', None)}")
+        return out
+
+    def views(self, frame):
+        return yuv_views(frame, self.fmt)
+
+    def to_planes(self, frame, x, to_rgb, *, width=None):
+        """x (B,3,Hp,Wp) fp32 = the reflect-padded RGB planes of `frame`."""
+        frame = self.contiguous(frame)
+        if self.packed:
+            return packed422_to_planes(frame, x, to_rgb, fmt=self.fmt, width=width, depth=self.depth, msb=self.msb, siting=self.siting)
+        yuv_to_planes(*self.views(frame), x, to_rgb, sub=self.sub, depth=self.depth, msb=self.msb, siting=self.siting)
+
+    def from_planes(self, planes, frame, from_rgb, *, width=None):
+        """frame = the top-left pixels of the fp32 planes, as many as `frame` holds."""
+        if self.packed:
+            return planes_to_packed422(planes, frame, from_rgb, fmt=self.fmt, width=width, depth=self.depth, msb=self.msb, siting=self.siting)
+        planes_to_yuv(planes, *self.views(frame), from_rgb, sub=self.sub, depth=self.depth, msb=self.msb, siting=self.siting)
 
 
 def u8_metrics_flags(*, y_channel: bool, bgr: bool, psnr: bool, ssim: bool) -> int:

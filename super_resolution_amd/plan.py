@@ -320,20 +320,36 @@ class Plan:
                    "hat_plan_forward_yuv420_deep")
 
     def forward_yuv(self, src: torch.Tensor, dst: torch.Tensor, *, fmt: str, out_fmt=None, matrix: str = "bt601", full_range: bool = False,
-                    depth: int = 8, out_depth=None, msb=None, out_msb=None, stream: int = 0, siting: str = "center", out_siting=None):
+                    depth: int = 8, out_depth=None, msb=None, out_msb=None, stream: int = 0, siting: str = "center", out_siting=None, width=None):
         """hat_plan_forward_yuv: src (B,rows,w) device frames in any layout `fmt` of yuv.LAYOUTS with h <= H, w <= W of the plan ->
         dst, the frames of the s-times larger image in the layout `out_fmt` (default: fmt).  Keywords as HAT.forward_yuv takes them;
-        a siting or out_siting other than 'center' goes through hat_plan_forward_yuv_sited."""
+        a siting or out_siting other than 'center' goes through hat_plan_forward_yuv_sited, and a fmt or out_fmt of
+        yuv.PACKED_FORMATS (width= for 'v210') through hat_plan_forward_packed422."""
         from . import ops, yuv
         out_siting = yuv.check_siting(siting) if out_siting is None else yuv.check_siting(out_siting)
         out_fmt = fmt if out_fmt is None else out_fmt
         out_depth = depth if out_depth is None else out_depth
-        h, w, to_rgb, from_rgb = self._yuv_args("forward_yuv", src, dst, lambda shape: yuv.frame_size_fmt(shape, fmt),
-                                                lambda ho, wo: yuv.frame_shape_fmt(ho, wo, out_fmt), matrix, full_range, depth, out_depth)
-        sub = lambda f: None if yuv.LAYOUTS[f][0] is None else yuv.LAYOUTS[f][:2]
-        sv, dv = ops.yuv_views(src, fmt), ops.yuv_views(dst, out_fmt)     # (kept alive: the surfaces hold raw pointers)
-        ss = ops.yuv_surface(*sv, sub=sub(fmt), depth=depth, msb=yuv.container(depth, fmt, msb)[3], what="forward_yuv")
-        ds = ops.yuv_surface(*dv, sub=sub(out_fmt), depth=out_depth, msb=yuv.container(out_depth, out_fmt, out_msb)[3], what="forward_yuv")
+        a = ops.FrameSide(fmt, depth=depth, msb=msb, siting=siting)
+        b = ops.FrameSide(out_fmt, depth=out_depth, msb=out_msb, siting=out_siting)
+        h, w, to_rgb, from_rgb = self._yuv_args("forward_yuv", src, dst, lambda shape: a.size(shape, width), b.shape, matrix, full_range, depth,
+                                                out_depth)
+
+        def surface(side, t, wd):   # (the packed surface, the planar one, what keeps their pointers alive)
+            if side.packed:
+                if not side.rows_packed(t):
+                    raise RuntimeError(f"forward_yuv needs {side.fmt} frames with packed rows, got strides {t.stride()}")
+                return ops.packed_surface(t, side.fmt, width=wd, depth=side.depth, msb=side.msb, what="forward_yuv")[0], None, t
+            v = side.views(t)
+            return None, ops.yuv_surface(*v, sub=side.sub, depth=side.depth, msb=side.msb, what="forward_yuv"), v
+
+        sp, ss, _keep_s = surface(a, src, w)
+        dp, ds, _keep_d = surface(b, dst, self.dims[4] * w)
+        ref = lambda x: None if x is None else C.byref(x)
+        if a.packed or b.packed:
+            _lib.check(self._lib.hat_plan_forward_packed422(self._h, ref(sp), ref(ss), yuv.SITINGS.index(siting), ref(dp), ref(ds),
+                                                            yuv.SITINGS.index(out_siting), h, w, to_rgb, from_rgb, stream),
+                       "hat_plan_forward_packed422")
+            return
         if (siting, out_siting) != ("center", "center"):
             _lib.check(self._lib.hat_plan_forward_yuv_sited(self._h, C.byref(ss), yuv.SITINGS.index(siting), C.byref(ds),
                                                             yuv.SITINGS.index(out_siting), h, w, to_rgb, from_rgb, stream),

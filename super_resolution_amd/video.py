@@ -23,6 +23,14 @@ says what was written.
 and needs --size H W or --scale S: the output stream has exactly that size (int(h S), int(w S) with --scale), even where the output's
 chroma is subsampled; W and H of the header are set to it and every other token is copied (y4m.sized_header).  --self-ensemble does
 not go with it.
+Packed 4:2:2 (uyvy, yuy2, y210, v210: yuv.py, "Packed 4:2:2") does not fit a Y4M file, so either side can be a HEADERLESS file instead
+(rawvideo.py; `ffmpeg -f rawvideo -pix_fmt uyvy422 | yuyv422 | y210le | v210`): --pixfmt F --raw-size H W [--raw-depth N] says what the
+input holds, --out-pixfmt F makes the output headerless.  A side is Y4M when its flag is absent, so `--out-pixfmt v210` on a .y4m file
+writes v210, and `--pixfmt uyvy --raw-size 1080 1920` with a .y4m output writes a C422 stream (whose header then names W, H and C
+only).  uyvy / yuy2 are 8-bit, v210 is 10-bit, y210 takes --raw-depth / --out-depth 10 (the default), 12 or 16.
+
+    python -m super_resolution_amd.video -opt options/test/HAT-S_SRx4.yml --pixfmt uyvy --raw-size 720 1280 -i in.uyvy --out-pixfmt uyvy \
+                                         -o out.uyvy --chroma-loc left
 """
 from __future__ import annotations
 
@@ -32,7 +40,8 @@ from . import y4m
 
 
 def upscale_file(net, src: str, dst: str, *, matrix: str = "bt601", full_range: bool = False, out_depth=None, ensemble: int = 1,
-                 out_chroma=None, chroma_loc: str = "center", out_chroma_loc=None, size=None, scale=None) -> dict:
+                 out_chroma=None, chroma_loc: str = "center", out_chroma_loc=None, size=None, scale=None, pixfmt=None, raw_size=None,
+                 raw_depth=None, out_pixfmt=None) -> dict:
     """Every frame of the .y4m file `src` through `net` into `dst`; returns {'frames', 'in', 'out'} (sizes as (w, h)), and for
     streams that are not 8-bit on both sides also 'depth' and 'out_depth'; with ensemble 2 / 4 / 8 (the self-ensemble of every
     frame, frames.upscale_frames) also 'ensemble'; for streams that are not 4:2:0 on both sides also 'chroma' and 'out_chroma'
@@ -41,10 +50,16 @@ def upscale_file(net, src: str, dst: str, *, matrix: str = "bt601", full_range: 
     are 'center' — then the header is copied as always — the result also holds 'chroma_loc' and 'out_chroma_loc' and the output
     header names the output's siting (y4m.with_siting).
     size=(h, w) or scale=: `net` is an arbitrary-scale network (ESCLTE; frames.upscale_frames' size= / scale=) and the output stream
-    has that size."""
+    has that size.
+    pixfmt (yuv.PACKED_FORMATS) with raw_size=(h, w) and raw_depth: `src` is a headerless file of packed 4:2:2 frames (rawvideo.Reader);
+    out_pixfmt: `dst` is one (rawvideo.Writer).  A side without its keyword is Y4M: upscale_packed_file."""
     from . import frames
     from .ops import ensemble_members
     ensemble = ensemble_members(ensemble)
+    if pixfmt is not None or out_pixfmt is not None:
+        return upscale_packed_file(net, src, dst, matrix=matrix, full_range=full_range, out_depth=out_depth, ensemble=ensemble,
+                                   out_chroma=out_chroma, chroma_loc=chroma_loc, out_chroma_loc=out_chroma_loc, size=size, scale=scale,
+                                   pixfmt=pixfmt, raw_size=raw_size, raw_depth=raw_depth, out_pixfmt=out_pixfmt)
     n = 0
     with y4m.Reader(src, chroma=True) as rd:
         depth = rd.depth
@@ -74,6 +89,67 @@ def upscale_file(net, src: str, dst: str, *, matrix: str = "bt601", full_range: 
                 n += 1
     loc = {"chroma_loc": siting, "out_chroma_loc": out_siting} if skw else {}
     return dict({"frames": n, "in": (rd.w, rd.h), "out": (hdr["W"], hdr["H"])}, **kw, **info, **loc)
+
+
+def check_raw_args(pixfmt, raw_size, raw_depth, out_pixfmt, out_depth):
+    """The headerless sides' arguments, refused in words (RuntimeError): -> (depth of a headerless input or None, depth of a headerless
+    output or None: the caller's default)."""
+    from . import yuv
+    if pixfmt is None:
+        if raw_size is not None or raw_depth is not None:
+            raise RuntimeError("--raw-size and --raw-depth describe a headerless input: they need --pixfmt")
+        depth = None
+    else:
+        if raw_size is None:
+            raise RuntimeError(f"a headerless {pixfmt} file does not say its size: --pixfmt needs --raw-size H W")
+        depth = yuv.packed_container(pixfmt, raw_depth)[1]
+        yuv.packed_shape(raw_size[0], raw_size[1], pixfmt)
+    if out_pixfmt is not None and out_depth is not None:
+        yuv.packed_container(out_pixfmt, out_depth)
+    return depth
+
+
+def upscale_packed_file(net, src: str, dst: str, *, matrix="bt601", full_range=False, out_depth=None, ensemble=1, out_chroma=None,
+                        chroma_loc="center", out_chroma_loc=None, size=None, scale=None, pixfmt=None, raw_size=None, raw_depth=None,
+                        out_pixfmt=None) -> dict:
+    """upscale_file with a headerless packed 4:2:2 file (rawvideo.py) on the input side (pixfmt, raw_size, raw_depth), the output side
+    (out_pixfmt) or both; the other side, if any, is Y4M.  Returns {'frames', 'in', 'out', 'pixfmt', 'out_pixfmt', 'depth', 'out_depth'}."""
+    from . import frames, rawvideo, yuv
+    depth = check_raw_args(pixfmt, raw_size, raw_depth, out_pixfmt, out_depth)
+    if out_pixfmt is not None and out_chroma is not None:
+        raise RuntimeError("--out-chroma names the subsampling of a Y4M output: a packed output is 4:2:2")
+    if (size is not None) and (scale is not None):
+        raise ValueError("upscale_file takes exactly one of size=(h, w) and scale=, or neither")
+    n = 0
+    rd = rawvideo.Reader(src, pixfmt, raw_size[0], raw_size[1], depth) if pixfmt is not None else y4m.Reader(src, chroma=True)
+    with rd:
+        in_fmt, depth = rd.fmt, rd.depth
+        header = {"W": rd.w, "H": rd.h, "X": []} if pixfmt is not None else rd.header
+        if size is None and scale is None:
+            oh, ow, akw = rd.h * net.upscale, rd.w * net.upscale, {}
+        else:
+            oh, ow = (int(rd.h * scale), int(rd.w * scale)) if size is None else (int(size[0]), int(size[1]))
+            akw = {"size": (oh, ow)}
+        siting, out_siting = resolve_chroma_loc(header, chroma_loc, out_chroma_loc)
+        if out_pixfmt is not None:
+            if out_depth is None:   # the input's where the layout takes it, else the layout's own
+                out_depth = depth if out_pixfmt == "y210" and depth in (10, 12, 16) else yuv.packed_container(out_pixfmt)[1]
+            wr, out_fmt = rawvideo.Writer(dst, out_pixfmt, oh, ow, out_depth), out_pixfmt
+        else:
+            out_depth = depth if out_depth is None else out_depth
+            out_chroma = ("422" if pixfmt is not None else y4m.chroma(header)) if out_chroma is None else out_chroma
+            hdr = y4m.with_chroma(y4m.with_depth(y4m.sized_header(header, ow, oh), out_depth), out_chroma)
+            if (siting, out_siting) != ("center", "center"):
+                hdr = y4m.with_siting(hdr, out_siting)
+            wr, out_fmt = y4m.Writer(dst, hdr, chroma=True), y4m.CHROMAS[out_chroma]
+        kw = {"ensemble": ensemble} if ensemble > 1 else {}
+        wkw = {"width": rd.w} if pixfmt is not None else {}
+        with wr:
+            for out in frames.upscale_frames(net, rd, pixfmt=in_fmt, out_pixfmt=out_fmt, matrix=matrix, full_range=full_range, depth=depth,
+                                             out_depth=out_depth, siting=siting, out_siting=out_siting, **kw, **wkw, **akw):
+                wr.write(out)
+                n += 1
+    return {"frames": n, "in": (rd.w, rd.h), "out": (ow, oh), "pixfmt": in_fmt, "out_pixfmt": out_fmt, "depth": depth, "out_depth": out_depth}
 
 
 CHROMA_LOCS = ("auto", "center", "left", "topleft")
@@ -107,6 +183,10 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--size must be positive")
         elif ns.size is not None or ns.scale is not None:
             self.error("--size and --scale belong to --lte-model: a network loaded with -opt has a fixed scale")
+        try:
+            check_raw_args(ns.pixfmt, ns.raw_size, ns.raw_depth, ns.out_pixfmt, ns.out_depth)
+        except RuntimeError as e:
+            self.error(str(e))
         return ns
 
 
@@ -131,6 +211,13 @@ def parser() -> argparse.ArgumentParser:
                          "AV1; all 4:2:2), topleft (BT.2020), or auto: what the header says (C420mpeg2 left, C420paldv topleft)")
     ap.add_argument("--out-chroma-loc", default=None, choices=list(CHROMA_LOCS),
                     help="chroma siting of the output stream (default: the input's); the output header names it")
+    ap.add_argument("--pixfmt", default=None, choices=["uyvy", "yuy2", "y210", "v210"],
+                    help="the input is a HEADERLESS file of packed 4:2:2 frames in this layout (needs --raw-size); absent: a .y4m file")
+    ap.add_argument("--raw-size", type=int, nargs=2, default=None, metavar=("H", "W"), help="with --pixfmt: the size of the input's frames")
+    ap.add_argument("--raw-depth", type=int, default=None, choices=[8, 10, 12, 16],
+                    help="with --pixfmt: bits per sample (uyvy / yuy2: 8; v210: 10; y210: 10, 12 or 16, default 10)")
+    ap.add_argument("--out-pixfmt", default=None, choices=["uyvy", "yuy2", "y210", "v210"],
+                    help="write a HEADERLESS file of packed 4:2:2 frames in this layout; absent: a .y4m file")
     ap.add_argument("--full-range", action="store_true", help="the stream is full range (0-255) instead of 16-235 / 16-240")
     ap.add_argument("--self-ensemble", nargs="?", type=int, const=8, default=None, choices=[2, 4, 8], metavar="N",
                     help="geometric self-ensemble of every frame over the first N = 2, 4 or 8 (default when N is left out) flips / transposes")
@@ -151,7 +238,8 @@ def main(argv=None):
         net = model.get_bare_model(model.net_g)
     info = upscale_file(net, args.input, args.output, matrix=args.matrix, full_range=args.full_range,
                         out_depth=args.out_depth, ensemble=args.self_ensemble or 1, out_chroma=args.out_chroma, chroma_loc=args.chroma_loc,
-                        out_chroma_loc=args.out_chroma_loc, size=args.size, scale=args.scale)
+                        out_chroma_loc=args.out_chroma_loc, size=args.size, scale=args.scale, pixfmt=args.pixfmt, raw_size=args.raw_size,
+                        raw_depth=args.raw_depth, out_pixfmt=args.out_pixfmt)
     print(info)
     return info
 

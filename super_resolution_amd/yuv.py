@@ -67,7 +67,22 @@ Depths, container, decode / encode and csc apply unchanged.  In: as above with t
 exactly and the same expression follows.  Out: Y and the per-pixel cb, cr terms as above, then
     4:2:0  as above        4:2:2  C = (c0 + c1) * 0.5 + k[c][3], left + right        4:4:4  C = c + k[c][3]        gray  Y only
 and the byte / code rule is unchanged.  For nv12 / nv21 / i420 the general functions return what the 4:2:0 pair returns.
-Packed 4:2:2 (YUY2 / UYVY / Y210 / v210), 4:1:1, 4:4:0, alpha planes and tone mapping are out of scope.
+4:1:1, 4:4:0, alpha planes and tone mapping are out of scope; packed 4:2:2 is "Packed 4:2:2" below.
+
+Packed 4:2:2 (PACKED_FORMATS; packed_shape, packed_size, unpack422, pack422, packed_to_planes, planes_to_packed).  What capture
+cards, cameras and 4:2:2 decoders deliver: one array per frame, luma and chroma interleaved, w even and >= 2, any h >= 1.
+  uyvy   bytes Cb0 Y0 Cr0 Y1 per pixel pair, 8 bit; (h, 2w) uint8                                     (ffmpeg uyvy422)
+  yuy2   bytes Y0 Cb0 Y1 Cr0, 8 bit; (h, 2w) uint8                                                   (ffmpeg yuyv422)
+  y210   little-endian 16-bit words Y0 Cb0 Y1 Cr0, depth 10 / 12 / 16 (16: Y216), MSB-aligned by default; (h, 2w) uint16
+  v210   10 bit only.  Six pixels in four little-endian 32-bit words, three codes each at bits 0-9, 10-19, 20-29:
+         word 0 Cb0 Y0 Cr0, word 1 Y1 Cb1 Y2, word 2 Cr1 Y3 Cb2, word 3 Y4 Cr2 Y5.  A row is 128 ceil(w / 48) bytes; (h, that) uint8.
+         Out: bits 30-31 of every word, every code of the last group past w and every byte from the last group to the end of the
+         row are zero.  In: none of them is read for its value.  The shape does not give the width: width= is required.
+The samples mean what the samples of a (sub_x, sub_y) = (1, 0) surface mean, so the two directions are DEFINED through 'i422':
+  packed_to_planes(frame)  = yuv_to_planes(join_fmt(*unpack422(frame), "i422"), fmt="i422")
+  planes_to_packed(planes) = pack422(*split_fmt(planes_to_yuv(planes, fmt="i422"), "i422"))
+with the word alignment of the packed side (v210's codes are LSB-aligned words in between).  Sitings: 'center' (the default, as for
+every other call) and 'left'; 'topleft' means 'left', as on every 4:2:2 surface.  Standard 4:2:2 video is LEFT-sited.
 
 Chroma siting (siting= / out_siting=; SITINGS = 'center', 'left', 'topleft', C codes 0, 1, 2).  An axis is CO-SITED when it is
 subsampled and the siting puts the chroma sample on the even luma sample: x where sub_x = 1 and the siting is 'left' or 'topleft',
@@ -99,6 +114,7 @@ FORMATS = ("nv12", "nv21", "i420")
 LAYOUTS = {"nv12": (1, 1, "semi"), "nv21": (1, 1, "semi_vu"), "i420": (1, 1, "planar"), "i422": (1, 0, "planar"), "nv16": (1, 0, "semi"),
            "i444": (0, 0, "planar"), "nv24": (0, 0, "semi"), "gray": (None, None, "gray")}
 ALL_FORMATS = tuple(LAYOUTS)
+PACKED_FORMATS = ("uyvy", "yuy2", "y210", "v210")   # the index is the C code (include/hat_mi355x.h, HAT_PACKED_*)
 MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020nc": (0.2627, 0.0593)}   # Kr, Kb
 DEPTHS = (8, 10, 12, 16)
 SITINGS = ("center", "left", "topleft")   # the index is the C code (include/hat_mi355x.h, HAT_SITING_*)
@@ -528,3 +544,139 @@ def planes_to_yuv(planes: np.ndarray, *, fmt: str, matrix: str = "bt601", full_r
     if kind == "gray":
         return join_fmt(q(Y), None, None, fmt, out_depth, msb)
     return join_fmt(q(Y), q(down(cb, k[7])), q(down(cr, k[11])), fmt, out_depth, msb)
+
+
+# ------------------------------------------------------------------------------------------------ packed 4:2:2
+def check_packed(fmt: str) -> str:
+    if fmt not in PACKED_FORMATS:
+        raise RuntimeError(f"unknown packed 4:2:2 format {fmt!r}: one of {PACKED_FORMATS}")
+    return fmt
+
+
+def packed_container(fmt: str, depth=None, msb=None):
+    """(dtype of the frame array, depth, msb) of packed layout `fmt`: uyvy / yuy2 take depth 8, y210 10 / 12 / 16 (default 10;
+    MSB-aligned unless msb=False), v210 10 (its codes are neither: msb is False)."""
+    check_packed(fmt)
+    if fmt in ("uyvy", "yuy2"):
+        want, dt = (8,), np.uint8
+    elif fmt == "y210":
+        want, dt = (10, 12, 16), np.uint16
+    else:
+        want, dt = (10,), np.uint8
+    depth = want[0] if depth is None else depth
+    if isinstance(depth, bool) or depth not in want:
+        raise RuntimeError(f"{fmt} frames hold {' / '.join(map(str, want))}-bit samples, not depth {depth!r}")
+    return dt, int(depth), (True if msb is None else bool(msb)) if fmt == "y210" else False
+
+
+def _check_packed_size(h, w, fmt):
+    h, w = int(h), int(w)
+    if h < 1 or w < 2 or w % 2:
+        raise RuntimeError(f"{fmt} frames (packed 4:2:2) need an even width >= 2 and at least one row, got {h}x{w}")
+    return h, w
+
+
+def packed_shape(h: int, w: int, fmt: str):
+    """Shape of the array that holds one h x w frame in packed layout `fmt`."""
+    check_packed(fmt)
+    h, w = _check_packed_size(h, w, fmt)
+    return (h, 128 * -(-w // 48)) if fmt == "v210" else (h, 2 * w)
+
+
+def packed_size(shape, fmt: str, width=None):
+    """(h, w) of a packed frame array; width is required for v210 (the row length does not give it), optional and checked otherwise."""
+    check_packed(fmt)
+    h, cols = int(shape[-2]), int(shape[-1])
+    if fmt == "v210":
+        if width is None:
+            raise ValueError("a v210 frame does not give its width (a row is 128 ceil(w / 48) bytes): pass width=")
+        w = int(width)
+    else:
+        w = cols // 2
+        if width is not None and int(width) != w:
+            raise ValueError(f"width={width} does not agree with a {fmt} frame of {tuple(shape)}: its rows hold {w} pixels")
+    if cols < 1 or packed_shape(h, w, fmt) != (h, cols):
+        raise RuntimeError(f"a {h}x{w} {fmt} frame is a {packed_shape(h, w, fmt) if w >= 2 and not w % 2 and h >= 1 else '(h, row)'} array, got {tuple(shape)}")
+    return h, w
+
+
+_V210_WORD = np.arange(12) // 3           # component n of a group (Cb0 Y0 Cr0 Y1 Cb1 Y2 Cr1 Y3 Cb2 Y4 Cr2 Y5) lies in this word
+_V210_SHIFT = 10 * (np.arange(12) % 3)    # at this bit
+
+
+def unpack422(frame: np.ndarray, fmt: str, w: int, depth=None, msb=None):
+    """frame (..., h, row) in packed layout `fmt` -> Y (..., h, w), Cb, Cr (..., h, w / 2): the samples AS STORED (bytes; y210: words
+    in their alignment, what decode reads with the same depth and msb; v210: the 10-bit codes as uint16)."""
+    dt, depth, msb = packed_container(fmt, depth, msb)
+    frame = np.asarray(frame)
+    if frame.dtype != dt or frame.ndim < 2:
+        raise RuntimeError(f"a {fmt} frame is a (h, row) {np.dtype(dt).name} array, got {frame.shape} {frame.dtype}")
+    h, w = packed_size(frame.shape, fmt, w)
+    if fmt != "v210":
+        q = frame.reshape(frame.shape[:-1] + (w // 2, 4))
+        iy0, icb, iy1, icr = (1, 0, 3, 2) if fmt == "uyvy" else (0, 1, 2, 3)
+        Y = np.stack([q[..., iy0], q[..., iy1]], axis=-1).reshape(frame.shape[:-1] + (w,))
+        return Y, q[..., icb].copy(), q[..., icr].copy()
+    g = -(-w // 6)
+    words = np.ascontiguousarray(frame[..., :16 * g]).view("<u4").reshape(frame.shape[:-1] + (g, 4))
+    comp = ((words[..., _V210_WORD] >> _V210_SHIFT.astype(np.uint32)) & np.uint32(1023)).astype(np.uint16)   # (..., g, 12)
+    lead = frame.shape[:-1]
+    Y = comp[..., 1::2].reshape(lead + (6 * g,))[..., :w]
+    Cb = comp[..., 0::4].reshape(lead + (3 * g,))[..., :w // 2]
+    Cr = comp[..., 2::4].reshape(lead + (3 * g,))[..., :w // 2]
+    return np.ascontiguousarray(Y), np.ascontiguousarray(Cb), np.ascontiguousarray(Cr)
+
+
+def pack422(Y: np.ndarray, Cb: np.ndarray, Cr: np.ndarray, fmt: str, depth=None, msb=None) -> np.ndarray:
+    """The packed frame of the stored samples Y (..., h, w), Cb, Cr (..., h, w / 2): the inverse of unpack422 (v210: of 10-bit codes;
+    the top bits, the codes past w and the row tail are zero)."""
+    dt, depth, msb = packed_container(fmt, depth, msb)
+    Y, Cb, Cr = np.asarray(Y), np.asarray(Cb), np.asarray(Cr)
+    h, w = Y.shape[-2:]
+    lead = Y.shape[:-2]
+    shape = packed_shape(h, w, fmt)
+    if Cb.shape != lead + (h, w // 2) or Cr.shape != Cb.shape:
+        raise RuntimeError(f"a {h}x{w} 4:2:2 frame has ({h}, {w // 2}) chroma samples a plane, got {Cb.shape[-2:]} / {Cr.shape[-2:]}")
+    if fmt != "v210":
+        out = np.empty(lead + (h, w // 2, 4), dtype=dt)
+        iy0, icb, iy1, icr = (1, 0, 3, 2) if fmt == "uyvy" else (0, 1, 2, 3)
+        out[..., iy0], out[..., iy1], out[..., icb], out[..., icr] = Y[..., 0::2], Y[..., 1::2], Cb, Cr
+        return out.reshape(lead + shape)
+    g = -(-w // 6)
+    comp = np.zeros(lead + (h, g, 12), dtype=np.uint32)
+    fill = lambda a, n: np.concatenate([a.astype(np.uint32) & np.uint32(1023), np.zeros(lead + (h, n - a.shape[-1]), np.uint32)], axis=-1)
+    comp[..., 1::2] = fill(Y, 6 * g).reshape(lead + (h, g, 6))
+    comp[..., 0::4] = fill(Cb, 3 * g).reshape(lead + (h, g, 3))
+    comp[..., 2::4] = fill(Cr, 3 * g).reshape(lead + (h, g, 3))
+    words = np.zeros(lead + (h, g, 4), dtype=np.uint32)
+    for n in range(12):
+        words[..., _V210_WORD[n]] |= comp[..., n] << np.uint32(_V210_SHIFT[n])
+    out = np.zeros(lead + shape, dtype=np.uint8)
+    out[..., :16 * g] = words.astype("<u4").reshape(lead + (h, 4 * g)).view(np.uint8)
+    return out
+
+
+def packed_to_planes(frame: np.ndarray, *, fmt: str, width=None, matrix: str = "bt601", full_range: bool = False, pad=(0, 0), depth=None,
+                     msb=None, siting: str = "center") -> np.ndarray:
+    """frame (h, row) or (B, h, row) in packed 4:2:2 layout `fmt` -> (B, 3, h + pad[0], w + pad[1]) float32 RGB planes: yuv_to_planes of
+    the 'i422' frame with the same samples ("Packed 4:2:2" of the module docstring).  siting 'center' (the default) or 'left' ('topleft'
+    means 'left'); standard 4:2:2 video is left-sited."""
+    _, depth, msb = packed_container(fmt, depth, msb)
+    frame = np.asarray(frame)
+    if frame.ndim not in (2, 3):
+        raise RuntimeError(f"expected a (h, row) or (B, h, row) {fmt} frame, got {frame.shape}")
+    w = packed_size(frame.shape, fmt, width)[1]
+    planar = join_fmt(*unpack422(frame, fmt, w, depth, msb), "i422", depth, msb)
+    return yuv_to_planes(planar, fmt="i422", matrix=matrix, full_range=full_range, pad=pad, depth=depth, msb=msb, siting=siting)
+
+
+def planes_to_packed(planes: np.ndarray, *, fmt: str, matrix: str = "bt601", full_range: bool = False, crop=None, out_depth=None, msb=None,
+                     siting: str = "center") -> np.ndarray:
+    """planes (B, 3, Hs, Ws) float32 -> (B,) + packed_shape(h_out, w_out, fmt) frames in packed 4:2:2 layout `fmt`: pack422 of the samples
+    of planes_to_yuv(fmt='i422'); crop = (h_out, w_out), w_out even (default: all).  siting: as packed_to_planes."""
+    _, depth, msb = packed_container(fmt, out_depth, msb)
+    planes = np.asarray(planes, dtype=_F)
+    if planes.ndim == 4:
+        _check_packed_size(*((planes.shape[2], planes.shape[3]) if crop is None else crop), fmt)
+    planar = planes_to_yuv(planes, fmt="i422", matrix=matrix, full_range=full_range, crop=crop, out_depth=depth, msb=msb, siting=siting)
+    return pack422(*split_fmt(planar, "i422"), fmt, depth, msb)
