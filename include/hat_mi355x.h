@@ -336,6 +336,8 @@ int hat_sgfn_gate(const void* u, const float* wdw, const float* bdw, void* out, 
  * (HATX: overlap 0.6 / 0.7, padding ceil((wse - ws) / 2), hatx_arch.py:303-305); HAT_EUNSUPPORTED for others.  When
  * K and V of one key window do not fit the LDS (fp32, wse 25, head_dim 30) a 16 x 16 window streams its keys through the LDS
  * in chunks (same arithmetic, same key order); HAT_ELDS for other window sizes in that case.
+ * Nothing beyond element alignment is required of q, kv and out: the tuned bf16 kernels (ws 16, wse 24, head_dim 24 / 30) are taken
+ * only when strides AND pointers allow their 16- / 8-byte (head_dim 24) or 4-byte (head_dim 30) accesses, the generic kernel otherwise.
  */
 int hat_ocab_attention(const void* q, const void* kv, const float* bias_rot, void* out, int32_t B, int32_t H,
                        int32_t W, int32_t C, int32_t heads, int32_t ws, int32_t wse, int32_t ldq,
@@ -729,6 +731,8 @@ int hat_arb_psnr(const float* pred, int32_t ph, int32_t pw, const uint8_t* gt, i
  * shift: 0 (W-MSA) or a multiple of 4 below ws (SW-MSA; the reference uses ws/2): windows are taken on the cyclically
  * shifted frame and pairs in different mask bands get -100 added to the logit (not -inf), as in the reference.
  * out: (B,H,W,ldo) T at the un-shifted pixel positions.  ws in {8, 16}; H, W multiples of ws.
+ * Pad channels (>= C of q, >= 2C of kv) are never read and those of out never written; q, kv and out need element alignment only
+ * (the tuned bf16 kernels for head_dim 24 / 30 at ws 16 are taken when strides and pointers allow their wider accesses).
  */
 int hat_window_attention(const void* q, const void* kv, const float* bias_flip, void* out, int32_t B, int32_t H,
                          int32_t W, int32_t C, int32_t heads, int32_t ws, int32_t shift, int32_t ldq, int32_t ldkv,

@@ -821,8 +821,12 @@ static int ocab_attention_impl(const void* q, const void* kv, const float* bias_
         return rc;
     const int d = C / heads;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool fast24 = d == 24 && ldq % 8 == 0 && ldkv % 8 == 0 && ldo % 4 == 0 && C % 8 == 0;
-    const bool fast30 = d == 30 && ldq % 2 == 0 && ldkv % 2 == 0 && ldo % 2 == 0 && C % 2 == 0;
+    // (the pointer term as in hat_window_attention: the D = 24 kernel stages q / k / v in 16-byte pieces and stores 8-byte ones, so
+    // the strides alone do not make its accesses aligned; a call that misses it takes the generic kernel — the log2 entry refuses)
+    const bool fast24 = d == 24 && ldq % 8 == 0 && ldkv % 8 == 0 && ldo % 4 == 0 && C % 8 == 0 &&
+                        (reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kv)) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0;
+    const bool fast30 = d == 30 && ldq % 2 == 0 && ldkv % 2 == 0 && ldo % 2 == 0 && C % 2 == 0 &&   // (4-byte accesses throughout)
+                        (reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kv) | reinterpret_cast<uintptr_t>(out)) % 4 == 0;
     if (dtype == HAT_BF16 && ws == 16 && wse == 24 && (fast24 || fast30)) {
         // (always above 64 KiB: the limit is raised on every call)
         const size_t lds = (size_t)576 * ((fast24 && !qlog2) ? 24 : 32) * 2 + (size_t)576 * 32 * 2 + (size_t)39 * 39 * 4;
@@ -890,7 +894,8 @@ extern "C" int hat_window_attention(const void* q, const void* kv, const float* 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool fast24 = d == 24 && ldq % 8 == 0 && ldkv % 8 == 0 && ldo % 4 == 0 && C % 8 == 0 &&
                         (reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kv)) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0;
-    const bool fast30 = d == 30 && ldq % 2 == 0 && ldkv % 2 == 0 && ldo % 2 == 0 && C % 2 == 0;
+    const bool fast30 = d == 30 && ldq % 2 == 0 && ldkv % 2 == 0 && ldo % 2 == 0 && C % 2 == 0 &&   // (4-byte accesses throughout)
+                        (reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kv) | reinterpret_cast<uintptr_t>(out)) % 4 == 0;
     if (dtype == HAT_BF16 && ws == 16 && (fast24 || fast30)) {
         // (36 612 B at most: the limit is never raised)
         const size_t lds = (size_t)256 * (fast24 ? 24 : 32) * 2 + (size_t)256 * 32 * 2 + (size_t)31 * 31 * 4;

@@ -1,7 +1,7 @@
 """Shared helpers for the tests: golden loading, oracle nets with synthetic weights, the per-kernel GPU tests' input / tolerance
 helpers, plain fp64 restatements of the HATX attention options and the SGFN gate that take the kernels' own inputs, and the
 builders / references of the multi-trip tests (test_gpu_multitrip.py): device-drawn activations, a banded fp64 convolution,
-the chunked re-run of a pointwise launch."""
+the chunked re-run of a pointwise launch.  (The hat_window_attention cases and their restatement are in wmsa_cases.py.)"""
 import json
 import os
 
@@ -72,6 +72,12 @@ def fill_rows(x_bhwc: torch.Tensor, ld: int, tdt, dev, fill, c_zero=None):
     if c_zero is not None and c_zero > c:
         out[:, :, c:c_zero] = 0
     return out
+
+
+def pads_keep(rows: torch.Tensor, c: int, fill: float, what: str):
+    """The pad channels [c, ld) of (B, N, ld) rows pre-filled with `fill` still hold it, bit for bit: the launch wrote live columns only."""
+    assert rows.shape[-1] > c, what + ": no pad channels"
+    assert torch.equal(rows[..., c:], torch.full_like(rows[..., c:], fill)), what + ": pad channels written"
 
 
 def check(got: torch.Tensor, ref: torch.Tensor, dtype: str, what: str, f32_tol=2e-5):

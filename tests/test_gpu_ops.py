@@ -864,6 +864,18 @@ def test_window_attention_rejects_bad_arguments():
     for bad in (dict(shift=3), dict(shift=16), dict(H=24), dict(ws=12)):
         with pytest.raises(RuntimeError):
             ops.window_attention(t, t.view(-1)[48:], bias, o, **{**kw, "shift": 0, **bad})
+    # odd head size; head size 34; strides below the live columns; a shift past the window; no such dtype; and in bf16 a window size
+    # no kernel is instantiated for, on a frame it divides and buffers that would hold it (every refusal comes before a launch)
+    for bad in (dict(C_=6), dict(C_=68, ldq=204, ldkv=204, ldo=68), dict(ldq=47), dict(ldkv=95), dict(ldo=47), dict(shift=20),
+                dict(dtype=7)):
+        with pytest.raises(RuntimeError):
+            ops.window_attention(t, t.view(-1)[48:], bias, o, **{**kw, "shift": 0, **bad})
+    big = torch.zeros(1, 24, 24, 3 * 48, dtype=torch.bfloat16, device=dev)
+    with pytest.raises(RuntimeError):
+        ops.window_attention(big, big.view(-1)[48:], torch.zeros(2, 23 * 23, device=dev), torch.zeros(1, 24, 24, 48, dtype=torch.bfloat16, device=dev),
+                             **{**kw, "shift": 0, "H": 24, "W": 24, "ws": 12, "dtype": ops.HAT_BF16})
+    ops.window_attention(t, t.view(-1)[48:], bias, o, **{**kw, "shift": 0})       # what is left when nothing is wrong is accepted
+    torch.cuda.synchronize()
 
 
 # ------------------------------------------------------------------------------------------------
