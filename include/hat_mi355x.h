@@ -1358,6 +1358,40 @@ int hat_shuffle_to_u8(const float* rows, int32_t ld, const float* base, int32_t 
 int hat_shuffle_to_yuv(const float* rows, int32_t ld, const float* base, int32_t B, int32_t H, int32_t W, int32_t s,
                        const HatYuvSurface* dst, int32_t h_out, int32_t w_out, const float* from_rgb12, void* stream);
 
+/*
+ * SRVGGNetCompact (srvgg_arch.py:6-69): one conv + activation layer of the compact VGG-style generator.
+ *     out[b][y][x][n] = f_n( sum over tap, ci of X[b][y + ty - 1][x + tx - 1][ci] * W[n][ci][ty][tx] + bias[n] ),  n < 64,
+ *     f_n(v) = v >= 0 ? v : slope[n] * v
+ * a 3x3 conv, zero padding 1, stride 1, to 64 channels.  slope (fp32[64]) is always read: the PReLU weight, zeros for ReLU, 0.1
+ * for the reference's LeakyReLU.  fp32 accumulation; bias, slope and activation in fp32; one rounding to T at the store.
+ *     frame == 0   x (B,H,W,ldx) T rows of 64 channels, ldx >= 64 and rows of whole 16 bytes; K = 9 * 64
+ *     frame != 0   x (B,3,H,W) fp32 planes, used as they are (no mean, no scale; converted to T before the MFMA); ldx is ignored;
+ *                  K = 27, k = 9 ci + 3 ty + tx, padded to one 32-deep k-step
+ *     out          (B,H,W,ldo) T rows, ldo >= 64 and rows of whole 16 bytes; columns >= 64 are not written; out != x
+ *     w            packing.pack_vgg_conv's image: MFMA A fragments [slices][k-steps][n-tiles per slice][64 lanes][8] of T, where
+ *                  a workgroup owns `slices`' share of the 64 outputs with its weights resident in LDS: bf16 1 slice of 4
+ *                  n-tiles (72 KB), fp32 2 slices of 2 (72 KB each; the fp32 tile is 86 KB).  k-step = 2 tap + half for rows.
+ *     dtype        HAT_BF16 (the product path) or HAT_F32 (hat_conv's fp32 products: chains of v_mfma_f32_16x16x4_f32)
+ * Persistent workgroups of 8 waves walk the 16 x 16 tiles of all samples: tile t of ceil(W/16) ceil(H/16) B goes to workgroup
+ * t % wgs of its slice; hat_vgg_conv_tiles reports tiles, wgs (per slice) and slices for a shape, so workgroup i < min(wgs, tiles)
+ * takes ceil((tiles - i) / wgs) trips.  HAT_EINVAL, before any launch: a null pointer; x (rows), w, bias, slope or out not 16-byte
+ * aligned (x as planes: 4); B, H or W < 1; more than 2^30 tiles; a bad leading dimension; out == x; another dtype.
+ */
+typedef struct HatVggConvDesc {
+    const void* x;
+    const void* w;
+    const float* bias;
+    const float* slope;
+    void* out;
+    int32_t B, H, W;
+    int32_t ldx, ldo;
+    int32_t frame;
+    int32_t dtype;
+    int32_t reserved0;
+} HatVggConvDesc;
+int hat_vgg_conv(const HatVggConvDesc* d, void* stream);
+int hat_vgg_conv_tiles(int32_t B, int32_t H, int32_t W, int32_t dtype, int32_t* tiles, int32_t* wgs, int32_t* slices);
+
 #ifdef __cplusplus
 }
 #endif

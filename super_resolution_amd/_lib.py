@@ -132,6 +132,13 @@ class HatEscConvFfnDesc(C.Structure):
                 ("ldo", C.c_int32), ("out_f32", C.c_int32), ("dtype", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class HatVggConvDesc(C.Structure):
+    """Mirror of `struct HatVggConvDesc` (include/hat_mi355x.h)."""
+    _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("slope", C.c_void_p), ("out", C.c_void_p),
+                ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("ldx", C.c_int32), ("ldo", C.c_int32), ("frame", C.c_int32),
+                ("dtype", C.c_int32), ("reserved0", C.c_int32)]
+
+
 _YUV_BLOCK = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]   # a 4:2:0 frame block
 
 # name -> (restype, argtypes); every symbol declared in include/hat_mi355x.h
@@ -297,6 +304,8 @@ SIGNATURES = {
                           + [C.c_void_p]),
     "hat_shuffle_to_yuv": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(HatYuvSurface), C.c_int32, C.c_int32,
                                                                                               C.c_void_p, C.c_void_p]),
+    "hat_vgg_conv": (C.c_int, [C.POINTER(HatVggConvDesc), C.c_void_p]),
+    "hat_vgg_conv_tiles": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_int32)] * 3),
 }
 
 _lib = None

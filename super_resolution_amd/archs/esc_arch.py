@@ -69,9 +69,10 @@ class _Block(_Holder):  # esc_arch.py:256-274
         self.conv_out = nn.Conv2d(dim, dim, 3, 1, 1)
 
 
-_NOT_BUILT = ("ESC runs its float forward only: {} is not built for it (DESIGN.md §7); `forward` and, through it, "
+# {0}: the network's name in messages (_ESCNet._NAME)
+_NOT_BUILT = ("{0} runs its float forward only: {1} is not built for it (DESIGN.md §7); `forward` and, through it, "
               "tile_parallel work")
-_NEW_NAME = ("ESC runs its float forward only under HAT's forward_* names: {} is `{}` in this family (upscale_u8, upscale_gt_u8, "
+_NEW_NAME = ("{0} runs its float forward only under HAT's forward_* names: {1} is `{2}` in this family (upscale_u8, upscale_gt_u8, "
              "upscale_to_u8, upscale_yuv, upscale_ensemble; DESIGN.md §4.21)")
 
 
@@ -80,6 +81,7 @@ class _ESCNet(HAT):
     `set_compute_dtype`, `use_graph` and the weight-change tracking are HAT's own — with the float forward as the only path, and the
     `to_img` scale conversion of `load_state_dict`.  A subclass builds its tree, sets `cfg`, and names its engine in `_make_engine`."""
     arbitrary_scale = False   # True: the network has no fixed scale and its frame paths take size= / scale= (ESCLTE)
+    _NAME = "ESC"             # what the refusals call the network (the family says ESC; SRVGGNetCompact names itself)
 
     def extra_repr(self) -> str:
         return ", ".join(f"{k}={v}" for k, v in self.cfg.items())
@@ -118,9 +120,9 @@ class _ESCNet(HAT):
 
     def forward(self, x):
         if self.training:
-            raise RuntimeError("this ESC implements the inference forward pass only: call .eval() first (training is out of scope)")
+            raise RuntimeError(f"this {self._NAME} implements the inference forward pass only: call .eval() first (training is out of scope)")
         if not x.is_cuda:
-            raise RuntimeError("ESC.forward needs a GPU tensor: the MI355X HIP path is the only path (no CPU fallback)")
+            raise RuntimeError(f"{self._NAME}.forward needs a GPU tensor: the MI355X HIP path is the only path (no CPU fallback)")
         with torch.no_grad():
             from .. import ops
             if self.use_graph and not ops.profiling():
@@ -128,23 +130,23 @@ class _ESCNet(HAT):
             return self.engine(x.device).forward(x).to(x.dtype, copy=True)
 
     def forward_ensemble(self, x, n: int = 8):
-        raise NotImplementedError(_NOT_BUILT.format("forward_ensemble"))
+        raise NotImplementedError(_NOT_BUILT.format(self._NAME, "forward_ensemble"))
 
     def forward_to_u8(self, *a, **k):
-        raise NotImplementedError(_NOT_BUILT.format("the byte frame path"))
+        raise NotImplementedError(_NOT_BUILT.format(self._NAME, "the byte frame path"))
 
     forward_u8 = forward_gt_u8 = forward_to_u8
 
     def forward_yuv420(self, *a, **k):
-        raise NotImplementedError(_NOT_BUILT.format("the YCbCr frame path"))
+        raise NotImplementedError(_NOT_BUILT.format(self._NAME, "the YCbCr frame path"))
 
     forward_yuv = forward_yuv420
 
     def forward_bands(self, x, n_bands: int):
-        raise NotImplementedError(_NOT_BUILT.format("row-band sharding"))
+        raise NotImplementedError(_NOT_BUILT.format(self._NAME, "row-band sharding"))
 
     def forward_band_parallel(self, x, group=None):
-        raise NotImplementedError(_NOT_BUILT.format("row-band sharding"))
+        raise NotImplementedError(_NOT_BUILT.format(self._NAME, "row-band sharding"))
 
 
 class _FixedScaleNet(_ESCNet):
@@ -158,20 +160,20 @@ class _FixedScaleNet(_ESCNet):
 
     def _check_u8_input(self, t):   # (HAT's, without in_chans: the family's networks are three-channel)
         if self.training:
-            raise RuntimeError("this ESC implements the inference forward pass only: call .eval() first (training is out of scope)")
+            raise RuntimeError(f"this {self._NAME} implements the inference forward pass only: call .eval() first (training is out of scope)")
         if not t.is_cuda:
-            raise RuntimeError("ESC needs a GPU tensor: the MI355X HIP path is the only path (no CPU fallback)")
+            raise RuntimeError(f"{self._NAME} needs a GPU tensor: the MI355X HIP path is the only path (no CPU fallback)")
 
     def forward_ensemble(self, x, n: int = 8):
-        raise NotImplementedError(_NEW_NAME.format("the self-ensemble", "upscale_ensemble"))
+        raise NotImplementedError(_NEW_NAME.format(self._NAME, "the self-ensemble", "upscale_ensemble"))
 
     def forward_to_u8(self, *a, **k):
-        raise NotImplementedError(_NEW_NAME.format("the byte frame path", "upscale_u8 / upscale_gt_u8 / upscale_to_u8"))
+        raise NotImplementedError(_NEW_NAME.format(self._NAME, "the byte frame path", "upscale_u8 / upscale_gt_u8 / upscale_to_u8"))
 
     forward_u8 = forward_gt_u8 = forward_to_u8
 
     def forward_yuv420(self, *a, **k):
-        raise NotImplementedError(_NEW_NAME.format("the YCbCr frame path", "upscale_yuv"))
+        raise NotImplementedError(_NEW_NAME.format(self._NAME, "the YCbCr frame path", "upscale_yuv"))
 
     forward_yuv = forward_yuv420
 

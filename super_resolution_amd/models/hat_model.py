@@ -106,8 +106,13 @@ class HATModel:
         if "gt" in data:
             self.gt = data["gt"].to(self.device)
 
+    def _window_size(self) -> int:
+        """The multiple a frame is reflect-padded to: network_g.window_size, or 1 for a network without windows (SRVGGNetCompact,
+        whose option files carry no such key)."""
+        return self.opt["network_g"].get("window_size", 1)
+
     def pre_process(self):  # hat_model.py:16-26
-        window_size = self.opt["network_g"]["window_size"]
+        window_size = self._window_size()
         self.scale = self.opt.get("scale", 1)
         _, _, h, w = self.lq.size()
         self.mod_pad_h = (window_size - h % window_size) % window_size
@@ -184,7 +189,7 @@ class HATModel:
         what pre_process makes of data.read_image's tensor.  hat_u8_to_planes divides exactly and pads; a torch division on the
         device would not do (it multiplies by the reciprocal, which is off by an ulp for about half of the byte values)."""
         from .. import ops
-        window_size = self.opt["network_g"]["window_size"]
+        window_size = self._window_size()
         self.scale = self.opt.get("scale", 1)
         b, h, w, _ = frame.shape
         self.mod_pad_h = (window_size - h % window_size) % window_size
@@ -247,7 +252,7 @@ class HATModel:
         if "tile" not in self.opt and fam is None:
             with torch.no_grad():
                 return self.get_bare_model(self.net_g).forward_gt_u8(gt, **self._ensemble_kw())[0]
-        window_size = self.opt["network_g"]["window_size"]
+        window_size = self._window_size()
         s = self.scale = self.opt.get("scale", 1)
         b, H, W, _ = gt.shape
         gt = gt[:, :H - H % s, :W - W % s]

@@ -14,12 +14,13 @@ import torch
 from . import _lib
 from ._lib import (ACT_GELU, ACT_LRELU, ACT_LRELU02, ACT_NONE, HAT_BF16, HAT_F32, O_FOLD2_NCHW_F32, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T,
                    X_NCHW_F32_MEAN, X_NHWC_F32, X_NHWC_T, HatAggrCabDesc, HatCabFoldDesc, HatConvDesc, HatFfnDesc, HatHabTailDesc, HatMlpDesc, HatNafFoldDesc,
-                   HatNafHalfDesc, HatEscConvFfnDesc)
+                   HatNafHalfDesc, HatEscConvFfnDesc, HatVggConvDesc)
 # host-side weight packing lives in packing.py; ops.pack_* / ops.Packed* stay the names the engine, the tools and the tests use
 from .packing import (ESC_HID_PAD, FP16_SAFE, KC, NAF_WIDTHS, TORCH_DTYPE, PackedConv, PackedEscFfn, PackedFFN, PackedMlp, PackedNafBlock, choose_nt,  # noqa: F401
                       esc_geo_ensemble, pack_esc_convffn, PackedEscRealSkip, ESCFP_HID_PAD, PackedEscFpLk, bicubic_phase_table, escfp_rank1_fold,
                       pack_escfp_convffn, pack_escfp_lk, dysample_fold, pack_escreal_skip, pack_nearest_conv,
                       LTE_HIDDEN, PackedLte, pack_lte,
+                      PackedVggConv, pack_vgg_conv,
                       UNI_UPSAMPLERS, PackedEscRealMSkip, conv_nearest_fold, pack_conv_nearest, pack_escrealm_skip, pack_pixshuf_conv, pixshuf_perm,
                       choose_nt_linear, naf_ffn_fold, naf_frags, pack_naf_block,
                       ffn_fp16_range_bound, pack_upfold, pack_cab_squeeze, pack_cab_w2f, pack_conv_weight, pack_ffn, pack_ffn2, pack_ffn3,
@@ -473,6 +474,33 @@ def shuffle_to_yuv(rows, base, y, cb, cr, from_rgb, *, B: int, H: int, W: int, s
         lib.hat_shuffle_to_yuv(_ptr(rows), ld, _ptr(base), B, H, W, s, C.byref(surf), y.shape[1], y.shape[2], m, _stream()), "hat_shuffle_to_yuv"),
         tag=f"shuffle x{s} {H}x{W} -> {name} {y.shape[1]}x{y.shape[2]}", nbytes=B * (4.0 * H * W * (ld + (3 if base is not None else 0))
                                                                                     + 3.0 * y.shape[1] * y.shape[2]))
+
+
+# ------------------------------------------------------------------------------------------------
+# SRVGGNetCompact (hat_vgg_conv)
+# ------------------------------------------------------------------------------------------------
+def vgg_conv(pv: PackedVggConv, x, out, *, B: int, H: int, W: int, dtype: int, ldx: int = 64, ldo: int = 64):
+    """out (B,H,W,ldo) T rows = PReLU-like(conv3x3(x) + bias) with pv.slope on the negative side (hat_vgg_conv): x (B,H,W,ldx) T rows
+    of 64 channels, or, for a layer packed from a 3-channel weight, the (B,3,H,W) fp32 frame."""
+    lib = _lib.load()
+    if pv.dtype != dtype:
+        raise RuntimeError(f"vgg_conv: the layer is packed for dtype {pv.dtype}, the launch asks for {dtype}")
+    d = HatVggConvDesc()
+    d.x, d.w, d.bias, d.slope, d.out = _ptr(x), _ptr(pv.w), _ptr(pv.bias), _ptr(pv.slope), _ptr(out)
+    d.B, d.H, d.W, d.ldx, d.ldo, d.frame, d.dtype = B, H, W, (0 if pv.frame else ldx), ldo, int(pv.frame), dtype
+    npx, es, cin = float(B * H * W), (2 if dtype == HAT_BF16 else 4), (3 if pv.frame else 64)
+    _timed(f"vgg_conv_kernel<{_TNAME[dtype]}, {'true' if pv.frame else 'false'}>", 2.0 * npx * 9 * cin * 64,
+           lambda: _lib.check(lib.hat_vgg_conv(C.byref(d), _stream()), "hat_vgg_conv"),
+           tag=f"vgg {cin}->64 {H}x{W}", nbytes=npx * ((12 if pv.frame else 64 * es) + 64 * es))
+
+
+def vgg_conv_tiles(B: int, H: int, W: int, dtype: int):
+    """-> (tiles, workgroups per slice, slices) of a hat_vgg_conv launch: workgroup i < min(workgroups, tiles) of a slice takes the
+    tiles i, i + workgroups, ... (hat_vgg_conv_tiles)."""
+    lib = _lib.load()
+    t, g, s = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _lib.check(lib.hat_vgg_conv_tiles(B, H, W, dtype, C.byref(t), C.byref(g), C.byref(s)), "hat_vgg_conv_tiles")
+    return t.value, g.value, s.value
 
 
 # ------------------------------------------------------------------------------------------------

@@ -786,3 +786,32 @@ def pack_upfold(wu, bu, wl, bl, device) -> PackedUpfold:
     p.w = torch.stack(ws).to(torch.bfloat16).contiguous().to(device)
     p.bias = torch.stack(bs).to(torch.float32).contiguous().to(device)
     return p
+
+
+# ------------------------------------------------------------------------------------------------
+# hat_vgg_conv (SRVGGNetCompact)
+# ------------------------------------------------------------------------------------------------
+VGG_NTL = {HAT_BF16: 4, HAT_F32: 2}   # n-tiles of the 64 outputs a workgroup of hat_vgg_conv keeps resident
+
+
+class PackedVggConv:
+    """One conv + activation layer of SRVGGNetCompact for hat_vgg_conv: w [slices][k-steps][n-tiles][64][8] of T, bias and slope fp32[64];
+    frame: the layer reads the 3-channel fp32 frame (k = 9 ci + tap) instead of 64-channel rows (k = 64 tap + ci)."""
+    __slots__ = ("w", "bias", "slope", "frame", "dtype")
+
+
+def pack_vgg_conv(weight: torch.Tensor, bias: torch.Tensor, slope: torch.Tensor, dtype: int, device) -> PackedVggConv:
+    """weight (64, 64, 3, 3) or (64, 3, 3, 3), bias (64,), slope (64,): the factor on the negative side, per output channel."""
+    w = _f32(weight)
+    if tuple(w.shape) not in ((64, 64, 3, 3), (64, 3, 3, 3)) or tuple(bias.shape) != (64,) or tuple(slope.shape) != (64,):
+        raise ValueError(f"hat_vgg_conv is built for a 3x3 conv of 64 or 3 channels to 64 with 64 slopes, got weight {tuple(w.shape)}, "
+                         f"bias {tuple(bias.shape)}, slope {tuple(slope.shape)}")
+    p = PackedVggConv()
+    p.frame, p.dtype = w.shape[1] == 3, dtype
+    m = _pad(w.reshape(64, 27), 64, 32) if p.frame else _tap_major(w)
+    ntl = VGG_NTL[dtype]
+    f = frags(m)                                                            # [4 n-tiles][k-steps][64][8]
+    f = f.reshape(4 // ntl, ntl, f.shape[1], 64, 8).permute(0, 2, 1, 3, 4)   # [slices][k-steps][n-tiles of the slice][64][8]
+    p.w = f.to(TORCH_DTYPE[dtype]).contiguous().to(device)
+    p.bias, p.slope = _f32(bias).contiguous().to(device), _f32(slope).contiguous().to(device)
+    return p
