@@ -1392,6 +1392,52 @@ typedef struct HatVggConvDesc {
 int hat_vgg_conv(const HatVggConvDesc* d, void* stream);
 int hat_vgg_conv_tiles(int32_t B, int32_t H, int32_t W, int32_t dtype, int32_t* tiles, int32_t* wgs, int32_t* slices);
 
+/*
+ * RRDBNet (rrdbnet_arch.py:9-119): one 3x3 conv (zero padding 1, stride 1) of a residual dense block on DENSE ROWS.
+ * A block's input and its grown maps share one row buffer (B,H,W,ld) of T, ld >= 192: channels [0,64) hold the block's input x,
+ * [64 + 32 (k - 1), 64 + 32 k) hold x_k.  No concatenation is ever made.
+ *     cin 64, 96, 128, 160 (convs 1-4), cout 32:
+ *         out[p][out_off + n] = f(acc[p][n] + bias[n]),  f(v) = v >= 0 ? v : slope * v,  rounded once to T
+ *         out may be x itself (the block's own buffer, out_off = cin): the kernel reads channels [0, cin) only, with 16-byte loads
+ *         none of which reaches channel cin, and stores channels [out_off, out_off + 32) only, so reads and writes of a launch never
+ *         share a byte although other workgroups store while a workgroup still reads its halo.  out == x requires out_off >= cin and
+ *         ldo == ldx.  Two DIFFERENT pointers into one buffer are the caller's to keep apart.  r1, r2, s_out must be NULL.
+ *     cin 192 (conv 5), cout 64, no activation, the residual arithmetic of :39 and :62 on an fp32 stream:
+ *         v = beta1 * (acc + bias) + r1[p][n]             (r1 == NULL: + 0)
+ *         v = beta2 * v + r2[p][n]                        (r2 given; needs r1)
+ *         s_out[p][n] = v (fp32), out[p][out_off + n] = v rounded once to T
+ *         r1, r2, s_out are fp32 rows (B,H,W,64) without padding; s_out may be r1 or r2 (every element is read, then written, by
+ *         one lane).  out is the NEXT block's dense buffer (out_off 0), never x.
+ *     w      packing.pack_rdb_conv's image: MFMA A fragments [slices][k-steps][2 n-tiles][64 lanes][8] of bf16 with
+ *            k-step = 9 (channel / 32) + 3 ty + tx, element (lane l, j) = W[32 slice + 16 t + (l & 15)][32 (channel / 32) + 8 (l >> 4) + j][ty][tx];
+ *            1 slice for convs 1-4, 2 for conv 5.  bias fp32[cout].
+ *     slope, beta1, beta2   fp32, applied in fp32 after the fp32 accumulation whose initial value is the bias.
+ *     dtype  HAT_BF16 (v_mfma_f32_16x16x32_bf16).  HAT_F32 passes the argument checks and returns HAT_EUNSUPPORTED: the fp32
+ *            compute path runs these layers on hat_conv.
+ * Persistent workgroups of 8 waves keep their 32 outputs' weights in LDS and walk the 16 x 16 tiles of all samples in 64-channel
+ * chunks of the haloed tile: tile t of ceil(W/16) ceil(H/16) B goes to workgroup t % wgs of its slice; hat_rdb_conv_tiles reports
+ * tiles, wgs (per slice) and slices.  HAT_EINVAL, before any launch: a null pointer; x, w, bias, out, r1, r2 or s_out not 16-byte
+ * aligned; cin not in {64, 96, 128, 160, 192}; cout not 32 (64 for cin 192); ldx < cin; ldo < out_off + cout; ldx, ldo or out_off
+ * not giving whole 16 bytes; B, H or W < 1; more than 2^30 tiles; r2 without r1; s_out missing at cin 192; a stream pointer at
+ * another cin; out == x with out_off < cin or ldo != ldx; another dtype.
+ */
+typedef struct HatRdbConvDesc {
+    const void* x;
+    const void* w;
+    const float* bias;
+    void* out;
+    const float* r1;
+    const float* r2;
+    float* s_out;
+    int32_t B, H, W;
+    int32_t cin, cout;
+    int32_t ldx, ldo, out_off;
+    float slope, beta1, beta2;
+    int32_t dtype;
+} HatRdbConvDesc;
+int hat_rdb_conv(const HatRdbConvDesc* d, void* stream);
+int hat_rdb_conv_tiles(int32_t B, int32_t H, int32_t W, int32_t cin, int32_t* tiles, int32_t* wgs, int32_t* slices);
+
 #ifdef __cplusplus
 }
 #endif

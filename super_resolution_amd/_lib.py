@@ -139,6 +139,14 @@ class HatVggConvDesc(C.Structure):
                 ("dtype", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class HatRdbConvDesc(C.Structure):
+    """Mirror of `struct HatRdbConvDesc` (include/hat_mi355x.h)."""
+    _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p), ("r1", C.c_void_p), ("r2", C.c_void_p),
+                ("s_out", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32),
+                ("ldx", C.c_int32), ("ldo", C.c_int32), ("out_off", C.c_int32), ("slope", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("dtype", C.c_int32)]
+
+
 _YUV_BLOCK = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]   # a 4:2:0 frame block
 
 # name -> (restype, argtypes); every symbol declared in include/hat_mi355x.h
@@ -306,6 +314,8 @@ SIGNATURES = {
                                                                                               C.c_void_p, C.c_void_p]),
     "hat_vgg_conv": (C.c_int, [C.POINTER(HatVggConvDesc), C.c_void_p]),
     "hat_vgg_conv_tiles": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_int32)] * 3),
+    "hat_rdb_conv": (C.c_int, [C.POINTER(HatRdbConvDesc), C.c_void_p]),
+    "hat_rdb_conv_tiles": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_int32)] * 3),
 }
 
 _lib = None

@@ -2,7 +2,9 @@ from .hat_model import HATModel  # noqa: F401
 
 # `model_type` of an option file -> the test-time harness.  ESC's ESRModel.test (ESC/esc/models/esr_model.py:269-310) is HATModel's:
 # reflect-pad to network_g.window_size, run, crop — the test branch is all that is built (training is out of scope).
-MODEL_TYPES = {"HATModel": HATModel, "ESRModel": HATModel, "SRModel": HATModel, "RealESRNetModel": HATModel}
+# ESRGANModel / SRGANModel / RealESRGANModel validate as SRModel does (esrgan_model.py, realesrgan_model.py): their own parts are training.
+MODEL_TYPES = {"HATModel": HATModel, "ESRModel": HATModel, "SRModel": HATModel, "RealESRNetModel": HATModel,
+               "ESRGANModel": HATModel, "SRGANModel": HATModel, "RealESRGANModel": HATModel}
 
 
 def model_class(model_type):

@@ -108,8 +108,12 @@ class HATModel:
 
     def _window_size(self) -> int:
         """The multiple a frame is reflect-padded to: network_g.window_size, or 1 for a network without windows (SRVGGNetCompact,
-        whose option files carry no such key)."""
-        return self.opt["network_g"].get("window_size", 1)
+        whose option files carry no such key); for RRDBNet the factor it unshuffles the frame by at scale 2 / 1 (2 / 4), as
+        Real-ESRGAN's inference wrapper pads."""
+        net = self.opt["network_g"]
+        if net.get("type") == "RRDBNet" and net.get("scale", 4) in (1, 2):
+            return 4 // net["scale"]
+        return net.get("window_size", 1)
 
     def pre_process(self):  # hat_model.py:16-26
         window_size = self._window_size()

@@ -14,13 +14,14 @@ import torch
 from . import _lib
 from ._lib import (ACT_GELU, ACT_LRELU, ACT_LRELU02, ACT_NONE, HAT_BF16, HAT_F32, O_FOLD2_NCHW_F32, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T,
                    X_NCHW_F32_MEAN, X_NHWC_F32, X_NHWC_T, HatAggrCabDesc, HatCabFoldDesc, HatConvDesc, HatFfnDesc, HatHabTailDesc, HatMlpDesc, HatNafFoldDesc,
-                   HatNafHalfDesc, HatEscConvFfnDesc, HatVggConvDesc)
+                   HatNafHalfDesc, HatEscConvFfnDesc, HatVggConvDesc, HatRdbConvDesc)
 # host-side weight packing lives in packing.py; ops.pack_* / ops.Packed* stay the names the engine, the tools and the tests use
 from .packing import (ESC_HID_PAD, FP16_SAFE, KC, NAF_WIDTHS, TORCH_DTYPE, PackedConv, PackedEscFfn, PackedFFN, PackedMlp, PackedNafBlock, choose_nt,  # noqa: F401
                       esc_geo_ensemble, pack_esc_convffn, PackedEscRealSkip, ESCFP_HID_PAD, PackedEscFpLk, bicubic_phase_table, escfp_rank1_fold,
                       pack_escfp_convffn, pack_escfp_lk, dysample_fold, pack_escreal_skip, pack_nearest_conv,
                       LTE_HIDDEN, PackedLte, pack_lte,
                       PackedVggConv, pack_vgg_conv,
+                      RDB_CIN, PackedRdbConv, pack_rdb_conv,
                       UNI_UPSAMPLERS, PackedEscRealMSkip, conv_nearest_fold, pack_conv_nearest, pack_escrealm_skip, pack_pixshuf_conv, pixshuf_perm,
                       choose_nt_linear, naf_ffn_fold, naf_frags, pack_naf_block,
                       ffn_fp16_range_bound, pack_upfold, pack_cab_squeeze, pack_cab_w2f, pack_conv_weight, pack_ffn, pack_ffn2, pack_ffn3,
@@ -500,6 +501,36 @@ def vgg_conv_tiles(B: int, H: int, W: int, dtype: int):
     lib = _lib.load()
     t, g, s = C.c_int32(0), C.c_int32(0), C.c_int32(0)
     _lib.check(lib.hat_vgg_conv_tiles(B, H, W, dtype, C.byref(t), C.byref(g), C.byref(s)), "hat_vgg_conv_tiles")
+    return t.value, g.value, s.value
+
+
+# ------------------------------------------------------------------------------------------------
+# RRDBNet (hat_rdb_conv)
+# ------------------------------------------------------------------------------------------------
+def rdb_conv(pr: PackedRdbConv, x, out, *, B: int, H: int, W: int, dtype: int, ldx: int, ldo: int, out_off: int, slope: float = 0.2,
+             beta1: float = 1.0, beta2: float = 1.0, r1=None, r2=None, s_out=None):
+    """One conv of a residual dense block on dense rows (hat_rdb_conv).  Convs 1-4: out[..., out_off : out_off + 32] = lrelu_slope(conv(x[...,
+    :cin]) + bias), out may be x (out_off = cin).  Conv 5 (cin 192): v = beta1 (conv + bias) + r1, then beta2 v + r2 when r2 is given; s_out
+    (B, H W, 64) fp32 = v and out[..., out_off : out_off + 64] = v rounded to T.  r1, r2: fp32 rows of 64."""
+    lib = _lib.load()
+    if pr.dtype != dtype:
+        raise RuntimeError(f"rdb_conv: the layer is packed for dtype {pr.dtype}, the launch asks for {dtype}")
+    d = HatRdbConvDesc()
+    d.x, d.w, d.bias, d.out, d.r1, d.r2, d.s_out = _ptr(x), _ptr(pr.w), _ptr(pr.bias), _ptr(out), _ptr(r1), _ptr(r2), _ptr(s_out)
+    d.B, d.H, d.W, d.cin, d.cout, d.ldx, d.ldo, d.out_off = B, H, W, pr.cin, pr.cout, ldx, ldo, out_off
+    d.slope, d.beta1, d.beta2, d.dtype = slope, beta1, beta2, dtype
+    npx, es = float(B * H * W), (2 if dtype == HAT_BF16 else 4)
+    nres = (r1 is not None) + (r2 is not None) + (s_out is not None)
+    _timed(f"rdb_conv_kernel<{pr.cin}>", 2.0 * npx * 9 * pr.cin * pr.cout, lambda: _lib.check(lib.hat_rdb_conv(C.byref(d), _stream()), "hat_rdb_conv"),
+           tag=f"rdb {pr.cin}->{pr.cout} {H}x{W}", nbytes=npx * ((pr.cin + pr.cout) * es + 256.0 * nres))
+
+
+def rdb_conv_tiles(B: int, H: int, W: int, cin: int):
+    """-> (tiles, workgroups per slice, slices) of a hat_rdb_conv launch: workgroup i < min(workgroups, tiles) of a slice takes the
+    tiles i, i + workgroups, ... (hat_rdb_conv_tiles)."""
+    lib = _lib.load()
+    t, g, s = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _lib.check(lib.hat_rdb_conv_tiles(B, H, W, cin, C.byref(t), C.byref(g), C.byref(s)), "hat_rdb_conv_tiles")
     return t.value, g.value, s.value
 
 

@@ -815,3 +815,32 @@ def pack_vgg_conv(weight: torch.Tensor, bias: torch.Tensor, slope: torch.Tensor,
     p.w = f.to(TORCH_DTYPE[dtype]).contiguous().to(device)
     p.bias, p.slope = _f32(bias).contiguous().to(device), _f32(slope).contiguous().to(device)
     return p
+
+
+# ------------------------------------------------------------------------------------------------
+# hat_rdb_conv (RRDBNet)
+# ------------------------------------------------------------------------------------------------
+RDB_CIN = (64, 96, 128, 160, 192)   # the five convs of a residual dense block: 32 outputs each, 64 for the last
+
+
+class PackedRdbConv:
+    """One conv of a residual dense block for hat_rdb_conv: w [slices][k-steps][2 n-tiles][64][8] of T with k-step = 9 (channel / 32)
+    + tap (1 slice of 32 outputs for convs 1-4, 2 for conv 5), bias fp32[cout]."""
+    __slots__ = ("w", "bias", "cin", "cout", "dtype")
+
+
+def pack_rdb_conv(weight: torch.Tensor, bias: torch.Tensor, dtype: int, device) -> PackedRdbConv:
+    """weight (32, cin, 3, 3) with cin in 64, 96, 128, 160, or (64, 192, 3, 3); bias (cout,)."""
+    w = _f32(weight)
+    cout, cin = (w.shape[0], w.shape[1]) if w.dim() == 4 else (0, 0)
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or cin not in RDB_CIN or cout != (64 if cin == 192 else 32) or tuple(bias.shape) != (cout,):
+        raise ValueError(f"hat_rdb_conv is built for the 3x3 convs of a residual dense block (64 + 32 k channels to 32, 192 to 64), got weight "
+                         f"{tuple(w.shape)}, bias {tuple(bias.shape)}")
+    p = PackedRdbConv()
+    p.cin, p.cout, p.dtype = cin, cout, dtype
+    m = w.reshape(cout, cin // 32, 32, 9).permute(0, 1, 3, 2).reshape(cout, 9 * cin)   # K = (9 (channel / 32) + tap) 32 + channel % 32
+    f = frags(m)                                                                      # [cout / 16][k-steps][64][8]
+    f = f.reshape(cout // 32, 2, f.shape[1], 64, 8).permute(0, 2, 1, 3, 4)            # [slices][k-steps][2 n-tiles][64][8]
+    p.w = f.to(TORCH_DTYPE[dtype]).contiguous().to(device)
+    p.bias = _f32(bias).contiguous().to(device)
+    return p
