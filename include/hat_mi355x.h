@@ -216,6 +216,44 @@ int hat_layernorm(const float* x, void* y, const float* gamma, const float* beta
                   int32_t dtype, void* stream);
 
 /*
+ * The head of the network in ONE launch (embed_dim 144, in_chans 3, bf16; hat_arch.py:836-837, :849-850 and the first
+ * block's norm1 :209): what hat_conv (conv_first, HAT_X_NCHW_F32_MEAN -> HAT_O_NHWC_F32), hat_layernorm (patch-embed norm,
+ * fp32 -> fp32) and hat_layernorm (norm1, fp32 -> bf16 rows with GAP partials) compute in three, bit for bit:
+ *     f0 = conv3x3((x - mean) * in_scale) + bias;  t = LayerNorm(f0; ln0);  n = bf16(LayerNorm(t; ln1))
+ * The conv runs on hat_conv's packed weights with hat_conv's k order (k = tap * 8 + ci, three 32-deep MFMA steps, the bias
+ * added in fp32 behind them), both LayerNorms on the accumulators with hat_layernorm's formula and summation tree, so
+ * every output equals the three-launch result.  A wave owns block `blk` of hat_layernorm's pixel partition (16 consecutive
+ * pixels every hat_layernorm_blocks() * 16), which makes gap_partial hat_layernorm's, block for block.
+ *   x (B,3,H,W) fp32 planes;  w [144][Kpad] bf16, bias [144] fp32: hat_conv's packing of conv_first (nt = 9, one slice);
+ *   f0, t (B,H*W,144) fp32 (f0 NULL: not stored);  n (B,H*W,ldn) bf16, ldn >= 144, % 8;  n16 (B,H*W,16) bf16 or NULL: a
+ *   compact copy of n's first 16 channels;  gap_partial (B, hat_layernorm_blocks(), 16) fp32, sums of the STORED n over the
+ *   first gap_c in {0, 4, 8, 12, 16} channels (NULL with gap_c = 0).
+ * HAT_EUNSUPPORTED: dtype != HAT_BF16 or C != 144.  HAT_EINVAL: anything else out of range, H * W >= 2^31 - 2^15, a pointer
+ * that is not 16-byte aligned (x: 4).
+ */
+typedef struct HatHeadDesc {
+    const float* x;
+    const void* w;
+    const float* bias;
+    const float* ln0_g;      /* patch-embed norm, [144] each */
+    const float* ln0_b;
+    const float* ln1_g;      /* the first block's norm1 */
+    const float* ln1_b;
+    float* f0;
+    float* t;
+    void* n;
+    void* n16;
+    float* gap_partial;
+    int32_t B, H, W, C;
+    int32_t Kpad;            /* row stride of w in elements: >= 96, % 32 */
+    int32_t ldn, gap_c, dtype;
+    float in_scale;
+    float mean[4];           /* per input channel; [3] unused */
+    int32_t reserved0;       /* 0 */
+} HatHeadDesc;
+int hat_head_fused(const HatHeadDesc* d, void* stream);
+
+/*
  * out[b][i] = a[b][i] + c[b * c_bstride + i], i < n (fp32, n % 4 == 0; out may alias a).  The plain adds of the
  * reference that no producing kernel can absorb: the absolute position embedding (hat_arch.py:837-838,
  * c_bstride = 0: broadcast over the batch) and the residuals around nn.Identity when

@@ -147,6 +147,15 @@ class HatRdbConvDesc(C.Structure):
                 ("beta2", C.c_float), ("dtype", C.c_int32)]
 
 
+class HatHeadDesc(C.Structure):
+    """Mirror of `struct HatHeadDesc` (include/hat_mi355x.h)."""
+    _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("ln0_g", C.c_void_p), ("ln0_b", C.c_void_p),
+                ("ln1_g", C.c_void_p), ("ln1_b", C.c_void_p), ("f0", C.c_void_p), ("t", C.c_void_p), ("n", C.c_void_p),
+                ("n16", C.c_void_p), ("gap_partial", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+                ("Kpad", C.c_int32), ("ldn", C.c_int32), ("gap_c", C.c_int32), ("dtype", C.c_int32), ("in_scale", C.c_float),
+                ("mean", C.c_float * 4), ("reserved0", C.c_int32)]
+
+
 _YUV_BLOCK = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]   # a 4:2:0 frame block
 
 # name -> (restype, argtypes); every symbol declared in include/hat_mi355x.h
@@ -316,6 +325,7 @@ SIGNATURES = {
     "hat_vgg_conv_tiles": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_int32)] * 3),
     "hat_rdb_conv": (C.c_int, [C.POINTER(HatRdbConvDesc), C.c_void_p]),
     "hat_rdb_conv_tiles": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_int32)] * 3),
+    "hat_head_fused": (C.c_int, [C.POINTER(HatHeadDesc), C.c_void_p]),
 }
 
 _lib = None

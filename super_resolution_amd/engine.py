@@ -69,6 +69,7 @@ class Options:
       HAT_NO_BF16_CONV_IN    fp32 rows into the group conv instead of the OCAB MLP's bf16 rows
       HAT_NO_CONV_LN         the LayerNorm after the group conv as its own launch instead of the conv's epilogue
       HAT_NO_UPFOLD=1        the last Upsample conv and conv_last as their two launches instead of hat_upfold_*
+      HAT_NO_HEAD_FUSED=1    conv_first, the patch-embed LayerNorm and the first norm1 as their three launches instead of hat_head_fused
     One switch is not an A/B switch and takes a word:
       HAT_T16_GUARD          defer (default) | sync | off — what happens when the FP16 residual stream leaves the FP16 range
                              (_T16Guard below): off launches the unguarded entries and clips in silence; any other
@@ -89,6 +90,7 @@ class Options:
     no_bf16_conv_in: bool = False
     no_conv_ln: bool = False
     no_upfold: bool = False
+    no_head_fused: bool = False
     t16_guard: str = "defer"
 
     def __post_init__(self):
@@ -472,6 +474,11 @@ class HATEngine(FrameBoundary, EngineBase):
                 else:
                     nxt, gap_c = (self.norm, 0) if self.conv_after_body is not None else (None, 0)
                 G.conv_ln = (nxt, gap_c) if nxt is not None and gap_c in (0, 4, 8, 12, 16) else None
+        # the head in one launch (hat_head_fused) when the first block takes what it emits: the fused tail's prologue reads n, its
+        # compact copy and hat_layernorm's GAP partials.  The absolute position embedding sits between the two LayerNorms: not fused.
+        hb0 = layers[0].habs[0] if layers and layers[0].habs else None
+        self.head_fused = bool(not self.opt.no_head_fused and hb0 is not None and hb0.tail == "fused144" and self.pe_norm is not None
+                               and self.ape is None and ops.head_fused_supported(self.conv_first, C, hb0.esc.pdim, dt))
         self._plan_t16()
         # 8-bit output (forward_to_u8 / forward_u8): conv_last's row-sweep kernel converts in its epilogue when it is packed for
         # three output channels (the width condition, W % 16, is the one _upsample already checks per shape); otherwise
@@ -545,6 +552,18 @@ class HATEngine(FrameBoundary, EngineBase):
         finally:
             with self._lock:
                 self.t16_guard = old
+
+    @contextlib.contextmanager
+    def head_route(self, fused: bool):
+        """The head's route for the forwards inside the block: hat_head_fused where _resolve chose it (fused=True), or the three
+        launches it equals bit for bit (the plan recorder: hat_head_fused is not in the plan format's function table)."""
+        with self._lock:
+            old, self.head_fused = self.head_fused, bool(fused and self.head_fused)
+        try:
+            yield self
+        finally:
+            with self._lock:
+                self.head_fused = old
 
     def _sat(self, stores16: bool):
         """The slot a launch that stores FP16 rows reports to, or None: the unguarded entry."""
@@ -856,6 +875,12 @@ class HATEngine(FrameBoundary, EngineBase):
         """(x - mean) * img_range ; conv_first ; patch_embed LN ; + absolute_pos_embed     :836-838, :849-853"""
         w, tA, C = f.w, f.w["tA"], self.C
         r = float(self.cfg.get("img_range", 1.0))
+        if self.head_fused:   # ... and the first block's norm1 with its compact copy and GAP partials: one launch
+            hb0 = self._hab0
+            ops.head_fused(self.conv_first, x, w["f0"], tA, w["n"], self.pe_norm, hb0.n1, B=f.B, H=f.H, W=f.W, ldn=f.ldc, dtype=f.dt,
+                           in_scale=r, mean=self._mean(), n16=(w["n16"] if self.use_n16 else None), gap=w["gap"], gap_c=hb0.esc.pdim)
+            f.have_n, f.have_n16, f.nblk = True, self.use_n16, ops.layernorm_blocks()
+            return
         ops.conv(self.conv_first, x, w["f0"], **f.geo, ldx=0, ldo=C, x_mode=X_NCHW_F32_MEAN, out_mode=O_NHWC_F32,
                  in_scale=r, mean=self._mean())
         if self.pe_norm is not None:

@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from ._lib import (ACT_GELU, ACT_LRELU, ACT_LRELU02, ACT_NONE, HAT_BF16, HAT_F32, O_FOLD2_NCHW_F32, O_NCHW_F32, O_NHWC_F32, O_NHWC_T, O_PIXSHUF_T,
                    X_NCHW_F32_MEAN, X_NHWC_F32, X_NHWC_T, HatAggrCabDesc, HatCabFoldDesc, HatConvDesc, HatFfnDesc, HatHabTailDesc, HatMlpDesc, HatNafFoldDesc,
-                   HatNafHalfDesc, HatEscConvFfnDesc, HatVggConvDesc, HatRdbConvDesc)
+                   HatNafHalfDesc, HatEscConvFfnDesc, HatVggConvDesc, HatRdbConvDesc, HatHeadDesc)
 # host-side weight packing lives in packing.py; ops.pack_* / ops.Packed* stay the names the engine, the tools and the tests use
 from .packing import (ESC_HID_PAD, FP16_SAFE, KC, NAF_WIDTHS, TORCH_DTYPE, PackedConv, PackedEscFfn, PackedFFN, PackedMlp, PackedNafBlock, choose_nt,  # noqa: F401
                       esc_geo_ensemble, pack_esc_convffn, PackedEscRealSkip, ESCFP_HID_PAD, PackedEscFpLk, bicubic_phase_table, escfp_rank1_fold,
@@ -172,6 +172,30 @@ def layernorm(x: torch.Tensor, y: torch.Tensor, gamma: torch.Tensor, beta: torch
     _timed("ln_kernel", 0.0, lambda: _lib.check(
         lib.hat_layernorm(_ptr(x), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(gap), B, npix, C_, ldy, int(out_f32), gap_c, dtype,
                           _stream()), "hat_layernorm"))
+
+
+def head_fused_supported(pw: PackedConv, C_: int, gap_c: int, dtype: int) -> bool:
+    """hat_head_fused takes conv_first as hat_conv packs it for 3 -> 144 channels (bf16) and pools at most 16 channels."""
+    return bool(dtype == HAT_BF16 and C_ == 144 and not pw.frag and pw.ksize == 3 and pw.cin == 3 and pw.nout == 144 and pw.nt == 9
+                and pw.n_slices == 1 and pw.kpad >= 96 and gap_c in (0, 4, 8, 12, 16))
+
+
+def head_fused(pw: PackedConv, x: torch.Tensor, f0: Optional[torch.Tensor], t: torch.Tensor, n: torch.Tensor, ln0, ln1, *, B: int, H: int,
+               W: int, ldn: int, dtype: int, in_scale: float = 1.0, mean=(0.0, 0.0, 0.0, 0.0), n16: Optional[torch.Tensor] = None,
+               gap: Optional[torch.Tensor] = None, gap_c: int = 0):
+    """conv_first + LayerNorm(ln0) + LayerNorm(ln1) in one launch (hat_head_fused): x (B,3,H,W) fp32 -> f0, t (B,H*W,144) fp32,
+    n (B,H*W,ldn) bf16, n16 its compact 16-channel copy, gap hat_layernorm's GAP partials of n's first gap_c channels."""
+    lib = _lib.load()
+    d = HatHeadDesc()
+    d.x, d.w, d.bias, d.f0, d.t, d.n, d.n16 = _ptr(x), _ptr(pw.w), _ptr(pw.bias), _ptr(f0), _ptr(t), _ptr(n), _ptr(n16)
+    d.ln0_g, d.ln0_b, d.ln1_g, d.ln1_b = _ptr(ln0[0]), _ptr(ln0[1]), _ptr(ln1[0]), _ptr(ln1[1])
+    d.gap_partial = _ptr(gap) if gap_c else None
+    d.B, d.H, d.W, d.C, d.Kpad, d.ldn, d.gap_c, d.dtype = B, H, W, pw.nout, pw.kpad, ldn, gap_c, dtype
+    d.in_scale, d.mean = in_scale, _mean4(mean)
+    px = float(B) * H * W
+    # bytes: the planes read once; f0 and t (fp32), n (bf16) and its compact copy written once
+    _timed("head_fused_kernel", px * (2.0 * 27 * 144 + 2 * 8.0 * 144), lambda: _lib.check(lib.hat_head_fused(C.byref(d), _stream()), "hat_head_fused"),
+           tag=f"3->144 {H}x{W} gap{gap_c}", nbytes=px * (12 + (576 if f0 is not None else 0) + 576 + 288 + (32 if n16 is not None else 0)))
 
 
 def add_f32(a: torch.Tensor, c: torch.Tensor, out: torch.Tensor, *, B: int, n: int, c_bstride: Optional[int] = None):

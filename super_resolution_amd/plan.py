@@ -167,7 +167,9 @@ def record_plan(net, x_shape: Tuple[int, int, int, int]):
     with _EXPORT_LOCK:                         # one export at a time: the recorder stands in for the process-wide library handle
         _lib._lib = rec
         try:
-            with torch.no_grad(), eng.guard_mode("off"):   # a plan holds the unguarded entries: a C host has no guard
+            # a plan holds the unguarded entries: a C host has no guard; and the head as its three launches: the
+            # function table's size is the file format, and hat_head_fused writes what they write, bit for bit
+            with torch.no_grad(), eng.guard_mode("off"), eng.head_route(fused=False):
                 y = eng.forward(x, one_stream=True)   # the plan replays on one stream: record the launches in that order
             torch.cuda.synchronize(dev)
         finally:
