@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhat_mi355x.so")
 SOURCES = ["hat_conv.hip", "hat_conv64r.hip", "hat_attn.hip", "hat_misc.hip", "hat_ffn.hip", "hat_ffn2.hip", "hat_tail3.hip", "hat_tail3l.hip", "hat_pw.hip", "hat_mlp.hip", "hat_cabsq.hip", "hat_esc13.hip", "hat_upfold.hip", "hat_u8.hip", "hat_yuv.hip", "hat_packed422.hip", "hat_resize.hip", "hat_pil_resize.hip", "hat_metrics.hip", "hat_dihedral.hip", "hat_niqe.hip", "hat_naf.hip", "hat_esc.hip", "hat_escreal.hip", "hat_escrealm.hip", "hat_escfp.hip", "hat_lte.hip", "hat_esc_sink.hip", "hat_vgg.hip", "hat_rrdb.hip", "hat_head.hip", "hat_plan.cpp"]
-HEADERS = [os.path.join(CSRC, "hat_common.h"), os.path.join(CSRC, "hat_yuv_check.h"), os.path.join(CSRC, "hat_packed_check.h"), os.path.join(CSRC, "hat_yuv_sample.h"), os.path.join(CSRC, "hat_frame_sink.h"), os.path.join(CSRC, "hat_esc_ffn.h"), os.path.join(CSRC, "hat_gated_ffn.h"), os.path.join(CSRC, "hat_plan_parse.h"), os.path.join(os.path.dirname(HERE), "include", "hat_mi355x.h")]
+HEADERS = [os.path.join(CSRC, "hat_common.h"), os.path.join(CSRC, "hat_yuv_check.h"), os.path.join(CSRC, "hat_packed_check.h"), os.path.join(CSRC, "hat_yuv_sample.h"), os.path.join(CSRC, "hat_frame_sink.h"), os.path.join(CSRC, "hat_esc_ffn.h"), os.path.join(CSRC, "hat_gated_ffn.h"), os.path.join(CSRC, "hat_conv3_tile.h"), os.path.join(CSRC, "hat_plan_parse.h"), os.path.join(os.path.dirname(HERE), "include", "hat_mi355x.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 

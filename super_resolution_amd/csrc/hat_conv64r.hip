@@ -5,25 +5,22 @@
 // hat_conv's kernel streams the weight slice through LDS in chunks behind two barriers each and reaches 23 % of the MFMA
 // peak on this layer (1.9 ms for 1.09 TFLOP at 1440 x 2560); the round-2 experiments on the wider group conv
 // (tools/experiments/hat_conv3_slab.hip.txt) showed why: per-chunk fixed costs and the weight stream from L2, not the
-// MFMAs.  With 64 input channels the weights of 64 output channels are 72 KB: they fit.  So, as hat_esc13.hip does:
-//   * a persistent workgroup owns ONE 64-channel output slice, copies its 72 A fragments (4 channel tiles x 18 k-steps) into
-//     LDS once — LDS-DMA, a gather of 16-byte pieces out of hat_conv's row-major weights — and walks the 16 x 16 tiles;
-//   * the haloed input tile (18 x 18 pixels x 64 channels, rows of 10 sixteen-byte slots: conflict-free fragment reads) is
-//     resident too, the next tile's is fetched into registers during the K loop: NO barrier inside the K loop;
-//   * a wave owns two tile rows x all four channel tiles and sweeps the tap ROWS for a fixed (tap column, channel half): the
-//     input-row fragment tile row 1 uses for tap row dy is the one tile row 0 needs for dy + 1 (4 row fragments feed 6
-//     (tap row, tile row) pairs: 16 fragment reads per 24 MFMAs).
-#include "hat_common.h"
+// MFMAs.  With 64 input channels the weights of 64 output channels are 72 KB: they fit.  So this is the resident-weight conv whose
+// structure hat_conv3_tile.h describes, one 64-channel output slice per workgroup; the schedule, launcher, block mapping and tile
+// decode are that header's.  The fetch, put and K sweep are written out here: as helpers shared with the other two kernels they compiled
+// to another schedule and the 64 -> 64 layer ran 4.5 % slower.  Its own besides: the 72 A fragments (4
+// channel tiles x 18 k-steps) arrive by LDS-DMA, a gather of 16-byte pieces out of hat_conv's row-major weights; the fragment reads go
+// through address-space-3 pointers with immediate offsets; the epilogue is hat_conv's plain one.
+#include "hat_conv3_tile.h"
 
 namespace {
 
-constexpr int R_T = 16, R_WAVES = 8, R_HW = R_T + 2, R_NPH = R_HW * R_HW;   // 16 x 16 tile, 18 x 18 haloed pixels
-constexpr int R_ROWB = 160;                                                  // bytes per haloed pixel in LDS (64 channels + pad)
-constexpr int R_NFRAG = 4 * 18, R_X_OFF = R_NFRAG * 1024;                    // 72 KB of weights, then the input tile
-constexpr int R_LDS = R_X_OFF + R_NPH * R_ROWB;                              // 125568 bytes: one workgroup per CU
-constexpr int R_NTHR = R_WAVES * 64;
+constexpr int R_ROWB = lds_row_elems(64, 2) * 2;            // bytes per haloed pixel in LDS (64 channels + pad): 160
+constexpr int R_NFRAG = 4 * 18, R_X_OFF = R_NFRAG * 1024;   // 72 KB of weights, then the input tile
+constexpr int R_LDS = R_X_OFF + C3_NPH * R_ROWB;            // one workgroup per CU
+static_assert(R_ROWB == 160 && R_LDS == 125568, "LDS budget");
 
-__global__ __launch_bounds__(R_NTHR) void conv64r_kernel(const HatConvDesc d, int nsl, int nwps, int tiles_x, int tiles_y) {
+__global__ __launch_bounds__(C3_NTHR) void conv64r_kernel(const HatConvDesc d, int nwps, int tiles_x, int tiles_y, int nsl) {
     typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
     typedef bf16_t T;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -31,10 +28,7 @@ __global__ __launch_bounds__(R_NTHR) void conv64r_kernel(const HatConvDesc d, in
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_char*)smem;
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c16 = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // workgroups are dealt round-robin to the 8 XCDs: the nsl slice-workgroups that walk the same tiles sit on one XCD
-    // (consecutive values of blockIdx.x >> 3), so the input tile comes from HBM once and from that XCD's L2 nsl - 1 times
-    const int slice = ((int)blockIdx.x >> 3) % nsl;
-    const int wgi = (((int)blockIdx.x >> 3) / nsl) * 8 + ((int)blockIdx.x & 7);
+    const int slice = conv3_slice(nsl), wgi = conv3_wgi(nsl);
     const int H = d.H, W = d.W;
     const int ntiles = tiles_x * tiles_y * d.B;
     if (wgi >= ntiles) return;   // (whole workgroup, before the weight copy is issued)
@@ -43,7 +37,7 @@ __global__ __launch_bounds__(R_NTHR) void conv64r_kernel(const HatConvDesc d, in
     // ---- weights -> LDS, once: fragment f = ks * 4 + nt = rows 64 slice + 16 nt + c16, k = 32 ks + 8 g of the [N][Kpad] rows ----
     {
         const T* wrow = reinterpret_cast<const T*>(d.w) + (size_t)(slice * 64 + c16) * d.Kpad + 8 * g;
-        for (int f = wave; f < R_NFRAG; f += R_WAVES) {
+        for (int f = wave; f < R_NFRAG; f += C3_WAVES) {
             const int ks = f >> 2, nt = f & 3;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wrow + (size_t)nt * 16 * d.Kpad + 32 * ks),
                                              (__attribute__((address_space(3))) void*)(smem + f * 1024), 16, 0, 0);
@@ -51,22 +45,20 @@ __global__ __launch_bounds__(R_NTHR) void conv64r_kernel(const HatConvDesc d, in
     }
     const int r0 = 2 * wave;
     // B fragment of (haloed row r0 + rr, tap column dx, channel half): lane (c16, g) -> pixel column c16 + dx, channels 32 half + 8 g
-    const unsigned xbase = lds0 + R_X_OFF + (unsigned)((r0 * R_HW + c16) * R_ROWB + g * 16);
+    const unsigned xbase = lds0 + R_X_OFF + (unsigned)((r0 * C3_HW + c16) * R_ROWB + g * 16);
     const unsigned abase = lds0 + (unsigned)lane * 16u;
 
     // The next tile's haloed input is fetched into registers BEFORE this tile's K loop and written to LDS after it.
-    constexpr int NPIECE = R_NPH * 8, NIT = (NPIECE + R_NTHR - 1) / R_NTHR;
+    constexpr int NPIECE = C3_NPH * 8, NIT = (NPIECE + C3_NTHR - 1) / C3_NTHR;
     u32x4 pv[NIT];
     auto fetch = [&](int t) {
-        const int tc = min(t, ntiles - 1);
-        const int bb = tc / (tiles_x * tiles_y), tr = tc - bb * tiles_x * tiles_y;
-        const int ty0 = (tr / tiles_x) * R_T, tx0 = (tr - (tr / tiles_x) * tiles_x) * R_T;
+        const auto [bb, ty0, tx0] = conv3_tile(min(t, ntiles - 1), tiles_x, tiles_y);
         const T* xb = xg + (size_t)bb * H * W * d.ldx;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
-            const int i = min(tid + it * R_NTHR, NPIECE - 1);
+            const int i = min(tid + it * C3_NTHR, NPIECE - 1);
             const int hp = i >> 3, piece = i & 7;
-            const int hy = hp / R_HW, hx = hp - hy * R_HW;
+            const int hy = hp / C3_HW, hx = hp - hy * C3_HW;
             const int y = ty0 - 1 + hy, xx = tx0 - 1 + hx;
             const bool in = y >= 0 && y < H && xx >= 0 && xx < W;
             const u32x4 v = *reinterpret_cast<const u32x4*>(xb + ((size_t)min(max(y, 0), H - 1) * W + min(max(xx, 0), W - 1)) * d.ldx + piece * 8);
@@ -79,11 +71,10 @@ __global__ __launch_bounds__(R_NTHR) void conv64r_kernel(const HatConvDesc d, in
 
     fetch(wgi);
     for (int t = wgi; t < ntiles; t += nwps) {
-        const int bb = t / (tiles_x * tiles_y), tr = t - bb * tiles_x * tiles_y;
-        const int ty0 = (tr / tiles_x) * R_T, tx0 = (tr - (tr / tiles_x) * tiles_x) * R_T;
+        const auto [bb, ty0, tx0] = conv3_tile(t, tiles_x, tiles_y);
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
-            const int i = tid + it * R_NTHR;
+            const int i = tid + it * C3_NTHR;
             if (i < NPIECE) *reinterpret_cast<u32x4*>(smem + R_X_OFF + (i >> 3) * R_ROWB + (i & 7) * 16) = pv[it];
         }
         __syncthreads();   // (first tile: also drains the weight copy)
@@ -95,7 +86,7 @@ __global__ __launch_bounds__(R_NTHR) void conv64r_kernel(const HatConvDesc d, in
 #pragma unroll
             for (int pt = 0; pt < 2; ++pt) acc[nt][pt] = biasv[nt];
         auto ldb = [&](int rr, int dx, int half) {
-            return __builtin_bit_cast(bf8, *(__attribute__((address_space(3))) const u32x4*)(uintptr_t)(xbase + (unsigned)((rr * R_HW + dx) * R_ROWB + half * 64)));
+            return __builtin_bit_cast(bf8, *(__attribute__((address_space(3))) const u32x4*)(uintptr_t)(xbase + (unsigned)((rr * C3_HW + dx) * R_ROWB + half * 64)));
         };
         auto lda = [&](int ks, int nt) {
             return __builtin_bit_cast(bf8, *(__attribute__((address_space(3))) const u32x4*)(uintptr_t)(abase + (unsigned)((ks * 4 + nt) * 1024)));
@@ -162,15 +153,6 @@ bool hat_conv64r_can_launch(const HatConvDesc& d) {
 }
 
 int hat_conv64r_launch(const HatConvDesc& d, hipStream_t s) {
-    auto kern = conv64r_kernel;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, R_LDS);
-    if (e != hipSuccess) return (int)e;
-    const int nsl = d.n_slices * d.nt * 16 / 64;
-    const int tiles_x = (d.W + R_T - 1) / R_T, tiles_y = (d.H + R_T - 1) / R_T, ntiles = tiles_x * tiles_y * d.B;
-    int m = 32 / nsl;                       // groups of 8 workgroups per slice: 256 workgroups for 4 slices
-    if (m < 1) m = 1;
-    while (m > 1 && 8 * (m - 1) >= ntiles) --m;   // (small frames: no idle workgroups)
-    const int nwps = 8 * m;   // tests/test_gpu_multitrip.py: conv64r_trip_tiles(nsl, ntiles) restates m and nwps
-    HAT_LAUNCH(kern, dim3(8 * nsl * m), dim3(R_NTHR), R_LDS, s, d, nsl, nwps, tiles_x, tiles_y);
-    return hat_check_launch();
+    const int nsl = d.n_slices * d.nt * 16 / 64;   // 256 workgroups for 4 slices
+    return conv3_launch(conv64r_kernel, R_LDS, nsl, d, s, nsl);
 }

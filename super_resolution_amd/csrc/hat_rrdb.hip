@@ -3,10 +3,10 @@
 // buffer, so torch.cat is never made.  Conv 5 (Cin 192, 64 outputs) carries the residual arithmetic of :39 and :62 on an fp32 stream.
 // Contract: include/hat_mi355x.h "RRDBNet".  DESIGN.md 4.26.
 //
-// The structure is hat_vgg.hip's: a persistent workgroup of 8 waves keeps the MFMA A fragments of its 32 outputs in LDS for its whole
-// life, walks 16 x 16 tiles, a wave owns two tile rows and sweeps the tap rows for a fixed (tap column, channel half) so that four
-// row fragments feed six (tap row, tile row) pairs.  What differs is the depth.  Weights and a full-depth haloed tile never fit
-// together (table below), so the weights stay and the INPUT is walked in channel chunks of 64 (the last one 32 wide where Cin is no
+// A resident-weight conv with the structure hat_conv3_tile.h describes (its schedule, launcher, block mapping and tile decode are that
+// header's): the workgroup's slice is the A fragments of 32 outputs.  The fetch, put and K sweep are written out here: as helpers
+// shared with the other two kernels they compiled to other schedules and the layers ran up to 9 % slower.
+// Its own besides is the depth.  Weights and a full-depth haloed tile never fit together (table below), so the weights stay and the INPUT is walked in channel chunks of 64 (the last one 32 wide where Cin is no
 // multiple of 64): one chunk of the haloed tile is resident (324 px x 160 B), the next chunk (of this tile, or the first of the next
 // tile) is fetched into registers before the chunk's MFMAs and written after them.  There is no barrier inside a chunk's K loop; two
 // per chunk around the LDS write.  Conv 5 runs as two 32-output slices whose workgroups share an XCD, as hat_vgg_conv's fp32 slices do.
@@ -20,16 +20,14 @@
 //
 // Reads and writes of one launch never share a byte: every 16-byte load covers 8 channels below Cin (a chunk ends at Cin, a multiple
 // of 32), every store covers channels at or above the output offset, which hat_rdb_conv requires to be >= Cin when out == x.
-#include "hat_common.h"
+#include "hat_conv3_tile.h"
 
 namespace {
 
-constexpr int R_T = 16, R_WAVES = 8, R_HW = R_T + 2, R_NPH = R_HW * R_HW, R_NTHR = R_WAVES * 64;
-constexpr long long R_MAX_TILES = 1LL << 30;   // the kernel walks tiles with int arithmetic: t + nwps (nwps <= 256) must not overflow
 constexpr int R_NTL = 2;                       // n-tiles a workgroup owns: 32 outputs
 constexpr int R_FRAGB = 64 * 8 * 2;            // bytes of one bf16 A fragment
 constexpr int R_ROWB = lds_row_elems(64, 2) * 2;   // bytes per haloed pixel of a chunk in LDS: 160
-constexpr int R_CHUNKB = R_NPH * R_ROWB;       // 51,840
+constexpr int R_CHUNKB = C3_NPH * R_ROWB;       // 51,840
 
 constexpr int rdb_wb(int cin) { return 9 * (cin / 32) * R_NTL * R_FRAGB; }   // resident weight bytes of a workgroup
 constexpr int rdb_lds(int cin) { return rdb_wb(cin) + R_CHUNKB; }
@@ -37,28 +35,19 @@ static_assert(R_ROWB == 160 && R_CHUNKB == 51840, "chunk image");
 static_assert(rdb_lds(64) == 88704 && rdb_lds(96) == 107136 && rdb_lds(128) == 125568 && rdb_lds(160) == 144000 && rdb_lds(192) == 162432, "LDS budget per layer");
 static_assert(rdb_lds(192) <= HAT_LDS_MAX, "conv 5: one 32-output slice and one 64-channel chunk");
 static_assert(2 * rdb_wb(192) > HAT_LDS_MAX, "conv 5's 64 outputs cannot be resident in one workgroup: two slices");
-static_assert(rdb_wb(128) + R_NPH * lds_row_elems(128, 2) * 2 > HAT_LDS_MAX, "convs 3-5: no full-depth tile beside the weights");
-
-// groups of 8 workgroups per slice (hat_vgg_conv's rule): 256 workgroups on a large frame, no idle ones on a small
-inline int rdb_groups(int nsl, long long ntiles) {
-    int m = 32 / nsl;
-    while (m > 1 && 8LL * (m - 1) >= ntiles) --m;
-    return m;
-}
+static_assert(rdb_wb(128) + C3_NPH * lds_row_elems(128, 2) * 2 > HAT_LDS_MAX, "convs 3-5: no full-depth tile beside the weights");
 
 template <int CIN>
-__global__ __launch_bounds__(R_NTHR) void rdb_conv_kernel(const HatRdbConvDesc d, int nwps, int tiles_x, int tiles_y) {
+__global__ __launch_bounds__(C3_NTHR) void rdb_conv_kernel(const HatRdbConvDesc d, int nwps, int tiles_x, int tiles_y) {
     using M = MT<bf16_t>;
     using frag_t = typename M::frag_t;
     constexpr bool LAST = CIN == 192;
     constexpr int NSL = LAST ? 2 : 1, WB = rdb_wb(CIN), NCH = (CIN + 63) / 64;
-    constexpr int NIT = (R_NPH * 8 + R_NTHR - 1) / R_NTHR;   // 16-byte pieces of a 64-channel chunk per thread: 6
+    constexpr int NIT = (C3_NPH * 8 + C3_NTHR - 1) / C3_NTHR;   // 16-byte pieces of a 64-channel chunk per thread: 6
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c16 = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // as in vgg_conv_kernel: the NSL slice-workgroups that walk the same tiles sit on one XCD
-    const int slice = ((int)blockIdx.x >> 3) % NSL;
-    const int wgi = (((int)blockIdx.x >> 3) / NSL) * 8 + ((int)blockIdx.x & 7);
+    const int slice = conv3_slice(NSL), wgi = conv3_wgi(NSL);
     const int H = d.H, W = d.W;
     const int ntiles = tiles_x * tiles_y * d.B;
     if (wgi >= ntiles) return;
@@ -66,7 +55,7 @@ __global__ __launch_bounds__(R_NTHR) void rdb_conv_kernel(const HatRdbConvDesc d
     // ---- this slice's fragments -> LDS, once: [k-step = 9 (channel / 32) + tap][n-tile][lane][8], already in that order ----
     {
         const u32x4* wsrc = reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(d.w) + (size_t)slice * WB);
-        for (int i = tid; i < WB / 16; i += R_NTHR) reinterpret_cast<u32x4*>(smem)[i] = wsrc[i];
+        for (int i = tid; i < WB / 16; i += C3_NTHR) reinterpret_cast<u32x4*>(smem)[i] = wsrc[i];
     }
     char* const xs = smem + WB;
     const int r0 = 2 * wave;
@@ -76,17 +65,15 @@ __global__ __launch_bounds__(R_NTHR) void rdb_conv_kernel(const HatRdbConvDesc d
     // reaches channel CIN or beyond.
     u32x4 pv[NIT];
     auto fetch = [&](int t, int c) {
-        const int ppp = (c == NCH - 1 && CIN % 64) ? 4 : 8, npiece = R_NPH * ppp;
-        const int tc = min(t, ntiles - 1);
-        const int bb = tc / (tiles_x * tiles_y), tr = tc - bb * tiles_x * tiles_y;
-        const int ty0 = (tr / tiles_x) * R_T, tx0 = (tr - (tr / tiles_x) * tiles_x) * R_T;
+        const int ppp = (c == NCH - 1 && CIN % 64) ? 4 : 8, npiece = C3_NPH * ppp;
+        const auto [bb, ty0, tx0] = conv3_tile(min(t, ntiles - 1), tiles_x, tiles_y);
         const bf16_t* xb = xg + (size_t)bb * H * W * d.ldx + c * 64;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
-            if (it * R_NTHR >= npiece) break;
-            const int i = min(tid + it * R_NTHR, npiece - 1);
+            if (it * C3_NTHR >= npiece) break;
+            const int i = min(tid + it * C3_NTHR, npiece - 1);
             const int hp = i / ppp, piece = i - hp * ppp;
-            const int hy = hp / R_HW, hx = hp - hy * R_HW;
+            const int hy = hp / C3_HW, hx = hp - hy * C3_HW;
             const int y = ty0 - 1 + hy, xx = tx0 - 1 + hx;
             const bool in = y >= 0 && y < H && xx >= 0 && xx < W;
             const u32x4 v = *reinterpret_cast<const u32x4*>(xb + ((size_t)min(max(y, 0), H - 1) * W + min(max(xx, 0), W - 1)) * d.ldx + piece * 8);
@@ -94,10 +81,10 @@ __global__ __launch_bounds__(R_NTHR) void rdb_conv_kernel(const HatRdbConvDesc d
         }
     };
     auto put = [&](int c) {
-        const int ppp = (c == NCH - 1 && CIN % 64) ? 4 : 8, npiece = R_NPH * ppp;
+        const int ppp = (c == NCH - 1 && CIN % 64) ? 4 : 8, npiece = C3_NPH * ppp;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
-            const int i = tid + it * R_NTHR;
+            const int i = tid + it * C3_NTHR;
             if (i < npiece) *reinterpret_cast<u32x4*>(xs + (i / ppp) * R_ROWB + (i % ppp) * 16) = pv[it];
         }
     };
@@ -108,8 +95,7 @@ __global__ __launch_bounds__(R_NTHR) void rdb_conv_kernel(const HatRdbConvDesc d
 
     fetch(wgi, 0);
     for (int t = wgi; t < ntiles; t += nwps) {
-        const int bb = t / (tiles_x * tiles_y), tr = t - bb * tiles_x * tiles_y;
-        const int ty0 = (tr / tiles_x) * R_T, tx0 = (tr - (tr / tiles_x) * tiles_x) * R_T;
+        const auto [bb, ty0, tx0] = conv3_tile(t, tiles_x, tiles_y);
         f32x4 acc[R_NTL][2];
 #pragma unroll
         for (int nt = 0; nt < R_NTL; ++nt)
@@ -126,7 +112,7 @@ __global__ __launch_bounds__(R_NTHR) void rdb_conv_kernel(const HatRdbConvDesc d
             auto lda = [&](int ks, int nt) { return M::load(reinterpret_cast<const bf16_t*>(smem + (ks * R_NTL + nt) * R_FRAGB) + lane * 8); };
             // B fragment of (haloed row r0 + rr, tap column dx, half): lane (c16, g) -> pixel column c16 + dx, channels 32 half + 8 g
             auto ldb = [&](int rr, int dx, int half) {
-                return M::load(reinterpret_cast<const bf16_t*>(xs + ((r0 + rr) * R_HW + c16 + dx) * R_ROWB) + half * 32 + 8 * g);
+                return M::load(reinterpret_cast<const bf16_t*>(xs + ((r0 + rr) * C3_HW + c16 + dx) * R_ROWB) + half * 32 + 8 * g);
             };
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx) {
@@ -184,30 +170,16 @@ __global__ __launch_bounds__(R_NTHR) void rdb_conv_kernel(const HatRdbConvDesc d
 }
 
 template <int CIN>
-int rdb_launch(const HatRdbConvDesc& d, int tiles_x, int tiles_y, hipStream_t s) {
-    auto kern = rdb_conv_kernel<CIN>;
-    constexpr int lds = rdb_lds(CIN), nsl = CIN == 192 ? 2 : 1;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    const int m = rdb_groups(nsl, (long long)tiles_x * tiles_y * d.B);
-    HAT_LAUNCH(kern, dim3(8 * nsl * m), dim3(R_NTHR), lds, s, d, 8 * m, tiles_x, tiles_y);
-    return hat_check_launch();
+int rdb_launch(const HatRdbConvDesc& d, hipStream_t s) {
+    return conv3_launch(rdb_conv_kernel<CIN>, rdb_lds(CIN), CIN == 192 ? 2 : 1, d, s);
 }
-
-inline bool misaligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 inline bool rdb_cin_ok(int cin) { return cin >= 64 && cin <= 192 && cin % 32 == 0; }
 
 }  // namespace
 
 extern "C" int hat_rdb_conv_tiles(int32_t B, int32_t H, int32_t W, int32_t cin, int32_t* tiles, int32_t* wgs, int32_t* slices) {
     if (!tiles || !wgs || !slices || B < 1 || H < 1 || W < 1 || !rdb_cin_ok(cin)) return HAT_EINVAL;
-    const long long nt = (long long)((W + R_T - 1) / R_T) * ((H + R_T - 1) / R_T) * B;
-    if (nt > R_MAX_TILES) return HAT_EINVAL;
-    const int nsl = cin == 192 ? 2 : 1;
-    *tiles = (int32_t)nt;
-    *wgs = 8 * rdb_groups(nsl, nt);
-    *slices = nsl;
-    return 0;
+    return conv3_tiles_query(B, H, W, cin == 192 ? 2 : 1, tiles, wgs, slices);
 }
 
 extern "C" int hat_rdb_conv(const HatRdbConvDesc* dp, void* stream) {
@@ -227,15 +199,14 @@ extern "C" int hat_rdb_conv(const HatRdbConvDesc* dp, void* stream) {
     } else if (d.r1 || d.r2 || d.s_out) {
         return HAT_EINVAL;   // the fp32 stream belongs to conv 5
     }
-    const int tiles_x = (d.W + R_T - 1) / R_T, tiles_y = (d.H + R_T - 1) / R_T;
-    if ((long long)tiles_x * tiles_y * d.B > R_MAX_TILES) return HAT_EINVAL;
+    if (conv3_ntiles(d.B, d.H, d.W) > C3_MAX_TILES) return HAT_EINVAL;
     if (d.dtype != HAT_BF16) return HAT_EUNSUPPORTED;   // the fp32 compute path runs these layers on hat_conv
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (d.cin) {
-        case 64: return rdb_launch<64>(d, tiles_x, tiles_y, s);
-        case 96: return rdb_launch<96>(d, tiles_x, tiles_y, s);
-        case 128: return rdb_launch<128>(d, tiles_x, tiles_y, s);
-        case 160: return rdb_launch<160>(d, tiles_x, tiles_y, s);
-        default: return rdb_launch<192>(d, tiles_x, tiles_y, s);
+        case 64: return rdb_launch<64>(d, s);
+        case 96: return rdb_launch<96>(d, s);
+        case 128: return rdb_launch<128>(d, s);
+        case 160: return rdb_launch<160>(d, s);
+        default: return rdb_launch<192>(d, s);
     }
 }

@@ -2,22 +2,18 @@
 // side (PReLU; ReLU and LeakyReLU 0.1 as slope vectors), from 64-channel T rows (the body) or from the 3-channel fp32 frame (the
 // first conv).  Contract: include/hat_mi355x.h "SRVGGNetCompact".  DESIGN.md 4.25.
 //
-// The structure is hat_conv64r.hip's: a persistent workgroup of 8 waves keeps the MFMA A fragments of its output slice in LDS (72 KB:
-// all 64 outputs in bf16, 32 of them in fp32, whose 86 KB tile leaves no room for more), the 18 x 18 haloed input tile is resident
-// beside them, the next tile's is fetched into registers before the K loop and written after it (no barrier inside the K loop), a wave
-// owns two tile rows and sweeps the tap rows for a fixed (tap column, channel half) so that four row fragments feed six (tap row,
-// tile row) pairs.  What differs: the weights arrive in fragment order (packing.pack_vgg_conv), so their copy is linear; the epilogue
-// applies slope[n]; bf16 rows leave as 16-byte stores (store_pair_bf16_if); the fp32 instantiation exists (hat_conv's products).
+// A resident-weight conv with the structure hat_conv3_tile.h describes (its schedule, launcher, block mapping and tile decode are that
+// header's): the workgroup's slice is 72 KB of A fragments, all 64 outputs in bf16, 32 of them in fp32, whose 86 KB tile leaves no room
+// for more.  Its own: the weights arrive in fragment order
+// (packing.pack_vgg_conv), so their copy is linear; the epilogue applies slope[n]; bf16 rows leave as 16-byte stores
+// (store_pair_bf16_if); the fp32 instantiation exists (hat_conv's products).
 // Frame mode stages the three fp32 planes of the haloed tile (3.9 KB) and builds its one B fragment per tile row from them: lane
 // (c16, g) holds k = 8 g + j = 9 ci + 3 ty + tx, a per-lane table of eight LDS offsets made once.
 #include <type_traits>
 
-#include "hat_common.h"
+#include "hat_conv3_tile.h"
 
 namespace {
-
-constexpr int V_T = 16, V_WAVES = 8, V_HW = V_T + 2, V_NPH = V_HW * V_HW, V_NTHR = V_WAVES * 64;
-constexpr long long V_MAX_TILES = 1LL << 30;   // the kernel walks tiles with int arithmetic: t + nwps (nwps <= 256) must not overflow
 
 template <typename T> struct VggCfg {
     static constexpr int ES = (int)sizeof(T);
@@ -27,19 +23,12 @@ template <typename T> struct VggCfg {
     static constexpr int ROWB = lds_row_elems(64, ES) * ES;      // bytes per haloed pixel in LDS: 160 / 272
     static constexpr int PPP = 64 * ES / 16;                     // 16-byte pieces per pixel row
     static constexpr int VEC = 16 / ES;
-    static constexpr int lds(bool frame) { return (frame ? 1 : 18) * NTL * FRAGB + (frame ? 3 * V_NPH * 4 : V_NPH * ROWB); }
+    static constexpr int lds(bool frame) { return (frame ? 1 : 18) * NTL * FRAGB + (frame ? 3 * C3_NPH * 4 : C3_NPH * ROWB); }
 };
 static_assert(VggCfg<bf16_t>::lds(false) == 125568 && VggCfg<float>::lds(false) == 161856 && VggCfg<float>::lds(false) <= HAT_LDS_MAX, "LDS budget");
 
-// groups of 8 workgroups per slice (hat_conv64r_launch's rule): 256 workgroups on a large frame, no idle ones on a small
-inline int vgg_groups(int nsl, long long ntiles) {
-    int m = 32 / nsl;
-    while (m > 1 && 8LL * (m - 1) >= ntiles) --m;
-    return m;
-}
-
 template <typename T, bool FRAME>
-__global__ __launch_bounds__(V_NTHR) void vgg_conv_kernel(const HatVggConvDesc d, int nwps, int tiles_x, int tiles_y) {
+__global__ __launch_bounds__(C3_NTHR) void vgg_conv_kernel(const HatVggConvDesc d, int nwps, int tiles_x, int tiles_y) {
     using M = MT<T>;
     using Cf = VggCfg<T>;
     using frag_t = typename M::frag_t;
@@ -47,9 +36,7 @@ __global__ __launch_bounds__(V_NTHR) void vgg_conv_kernel(const HatVggConvDesc d
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c16 = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // as in conv64r_kernel: the NSL slice-workgroups that walk the same tiles sit on one XCD
-    const int slice = ((int)blockIdx.x >> 3) % NSL;
-    const int wgi = (((int)blockIdx.x >> 3) / NSL) * 8 + ((int)blockIdx.x & 7);
+    const int slice = conv3_slice(NSL), wgi = conv3_wgi(NSL);
     const int H = d.H, W = d.W;
     const int ntiles = tiles_x * tiles_y * d.B;
     if (wgi >= ntiles) return;
@@ -57,32 +44,30 @@ __global__ __launch_bounds__(V_NTHR) void vgg_conv_kernel(const HatVggConvDesc d
     // ---- this slice's fragments -> LDS, once: [k-step][n-tile][lane][8], already in that order ----
     {
         const u32x4* wsrc = reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(d.w) + (size_t)slice * WB);
-        for (int i = tid; i < WB / 16; i += V_NTHR) reinterpret_cast<u32x4*>(smem)[i] = wsrc[i];
+        for (int i = tid; i < WB / 16; i += C3_NTHR) reinterpret_cast<u32x4*>(smem)[i] = wsrc[i];
     }
     char* const xs = smem + WB;
     const int r0 = 2 * wave;
 
     // The next tile's haloed input is fetched into registers BEFORE this tile's K loop and written to LDS after it.
-    constexpr int NPIECE = FRAME ? 3 * V_NPH : V_NPH * Cf::PPP, NIT = (NPIECE + V_NTHR - 1) / V_NTHR;
+    constexpr int NPIECE = FRAME ? 3 * C3_NPH : C3_NPH * Cf::PPP, NIT = (NPIECE + C3_NTHR - 1) / C3_NTHR;
     using piece_t = std::conditional_t<FRAME, float, u32x4>;
     piece_t pv[NIT];
     auto fetch = [&](int t) {
-        const int tc = min(t, ntiles - 1);
-        const int bb = tc / (tiles_x * tiles_y), tr = tc - bb * tiles_x * tiles_y;
-        const int ty0 = (tr / tiles_x) * V_T, tx0 = (tr - (tr / tiles_x) * tiles_x) * V_T;
+        const auto [bb, ty0, tx0] = conv3_tile(min(t, ntiles - 1), tiles_x, tiles_y);
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
-            const int i = min(tid + it * V_NTHR, NPIECE - 1);
+            const int i = min(tid + it * C3_NTHR, NPIECE - 1);
             if constexpr (FRAME) {
-                const int c = i / V_NPH, hp = i - c * V_NPH;
-                const int hy = hp / V_HW, hx = hp - hy * V_HW;
+                const int c = i / C3_NPH, hp = i - c * C3_NPH;
+                const int hy = hp / C3_HW, hx = hp - hy * C3_HW;
                 const int y = ty0 - 1 + hy, xx = tx0 - 1 + hx;
                 const bool in = y >= 0 && y < H && xx >= 0 && xx < W;
                 const float v = reinterpret_cast<const float*>(d.x)[(((size_t)bb * 3 + c) * H + min(max(y, 0), H - 1)) * W + min(max(xx, 0), W - 1)];
                 pv[it] = in ? v : 0.f;
             } else {
                 const int hp = i / Cf::PPP, piece = i - hp * Cf::PPP;
-                const int hy = hp / V_HW, hx = hp - hy * V_HW;
+                const int hy = hp / C3_HW, hx = hp - hy * C3_HW;
                 const int y = ty0 - 1 + hy, xx = tx0 - 1 + hx;
                 const bool in = y >= 0 && y < H && xx >= 0 && xx < W;
                 const T* xb = reinterpret_cast<const T*>(d.x) + (size_t)bb * H * W * d.ldx;
@@ -102,16 +87,15 @@ __global__ __launch_bounds__(V_NTHR) void vgg_conv_kernel(const HatVggConvDesc d
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int k = 8 * g + j, ci = k / 9, tap = k - 9 * ci;
-        koff[j] = k < 27 ? ci * V_NPH + (tap / 3) * V_HW + tap % 3 : -1;
+        koff[j] = k < 27 ? ci * C3_NPH + (tap / 3) * C3_HW + tap % 3 : -1;
     }
 
     fetch(wgi);
     for (int t = wgi; t < ntiles; t += nwps) {
-        const int bb = t / (tiles_x * tiles_y), tr = t - bb * tiles_x * tiles_y;
-        const int ty0 = (tr / tiles_x) * V_T, tx0 = (tr - (tr / tiles_x) * tiles_x) * V_T;
+        const auto [bb, ty0, tx0] = conv3_tile(t, tiles_x, tiles_y);
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
-            const int i = tid + it * V_NTHR;
+            const int i = tid + it * C3_NTHR;
             if (i < NPIECE) {
                 if constexpr (FRAME) reinterpret_cast<float*>(xs)[i] = pv[it];
                 else *reinterpret_cast<u32x4*>(xs + (i / Cf::PPP) * Cf::ROWB + (i % Cf::PPP) * 16) = pv[it];
@@ -133,7 +117,7 @@ __global__ __launch_bounds__(V_NTHR) void vgg_conv_kernel(const HatVggConvDesc d
             for (int pt = 0; pt < 2; ++pt)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const float v = koff[j] >= 0 ? xp[max(koff[j], 0) + (r0 + pt) * V_HW + c16] : 0.f;
+                    const float v = koff[j] >= 0 ? xp[max(koff[j], 0) + (r0 + pt) * C3_HW + c16] : 0.f;
                     b[pt][j] = to_T<T>(v);
                 }
 #pragma unroll
@@ -145,7 +129,7 @@ __global__ __launch_bounds__(V_NTHR) void vgg_conv_kernel(const HatVggConvDesc d
         } else {
             // B fragment of (haloed row r0 + rr, tap column dx, channel half): lane (c16, g) -> pixel column c16 + dx, channels 32 half + 8 g
             auto ldb = [&](int rr, int dx, int half) {
-                return M::load(reinterpret_cast<const T*>(xs + ((r0 + rr) * V_HW + c16 + dx) * Cf::ROWB) + half * 32 + 8 * g);
+                return M::load(reinterpret_cast<const T*>(xs + ((r0 + rr) * C3_HW + c16 + dx) * Cf::ROWB) + half * 32 + 8 * g);
             };
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx) {
@@ -195,32 +179,15 @@ __global__ __launch_bounds__(V_NTHR) void vgg_conv_kernel(const HatVggConvDesc d
 }
 
 template <typename T, bool FRAME>
-int vgg_launch(const HatVggConvDesc& d, int tiles_x, int tiles_y, hipStream_t s) {
-    using Cf = VggCfg<T>;
-    auto kern = vgg_conv_kernel<T, FRAME>;
-    constexpr int lds = Cf::lds(FRAME);
-    if (lds > 65536) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    const int m = vgg_groups(Cf::NSL, (long long)tiles_x * tiles_y * d.B);
-    HAT_LAUNCH(kern, dim3(8 * Cf::NSL * m), dim3(V_NTHR), lds, s, d, 8 * m, tiles_x, tiles_y);
-    return hat_check_launch();
+int vgg_launch(const HatVggConvDesc& d, hipStream_t s) {
+    return conv3_launch(vgg_conv_kernel<T, FRAME>, VggCfg<T>::lds(FRAME), VggCfg<T>::NSL, d, s);
 }
-
-inline bool misaligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 }  // namespace
 
 extern "C" int hat_vgg_conv_tiles(int32_t B, int32_t H, int32_t W, int32_t dtype, int32_t* tiles, int32_t* wgs, int32_t* slices) {
     if (!tiles || !wgs || !slices || B < 1 || H < 1 || W < 1 || (dtype != HAT_BF16 && dtype != HAT_F32)) return HAT_EINVAL;
-    const long long nt = (long long)((W + V_T - 1) / V_T) * ((H + V_T - 1) / V_T) * B;
-    if (nt > V_MAX_TILES) return HAT_EINVAL;
-    const int nsl = dtype == HAT_BF16 ? VggCfg<bf16_t>::NSL : VggCfg<float>::NSL;
-    *tiles = (int32_t)nt;
-    *wgs = 8 * vgg_groups(nsl, nt);
-    *slices = nsl;
-    return 0;
+    return conv3_tiles_query(B, H, W, dtype == HAT_BF16 ? VggCfg<bf16_t>::NSL : VggCfg<float>::NSL, tiles, wgs, slices);
 }
 
 extern "C" int hat_vgg_conv(const HatVggConvDesc* dp, void* stream) {
@@ -234,9 +201,8 @@ extern "C" int hat_vgg_conv(const HatVggConvDesc* dp, void* stream) {
     if (misaligned(d.x, d.frame ? 4 : 16)) return HAT_EINVAL;
     if (d.ldo < 64 || d.ldo % vec) return HAT_EINVAL;
     if (!d.frame && (d.ldx < 64 || d.ldx % vec)) return HAT_EINVAL;
-    const int tiles_x = (d.W + V_T - 1) / V_T, tiles_y = (d.H + V_T - 1) / V_T;
-    if ((long long)tiles_x * tiles_y * d.B > V_MAX_TILES) return HAT_EINVAL;
+    if (conv3_ntiles(d.B, d.H, d.W) > C3_MAX_TILES) return HAT_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (d.dtype == HAT_BF16) return d.frame ? vgg_launch<bf16_t, true>(d, tiles_x, tiles_y, s) : vgg_launch<bf16_t, false>(d, tiles_x, tiles_y, s);
-    return d.frame ? vgg_launch<float, true>(d, tiles_x, tiles_y, s) : vgg_launch<float, false>(d, tiles_x, tiles_y, s);
+    if (d.dtype == HAT_BF16) return d.frame ? vgg_launch<bf16_t, true>(d, s) : vgg_launch<bf16_t, false>(d, s);
+    return d.frame ? vgg_launch<float, true>(d, s) : vgg_launch<float, false>(d, s);
 }

@@ -248,6 +248,17 @@ def resident_kernel_takes(dtype: str, k: int, cin: int, cout: int, opt) -> bool:
             and not o["colsum"] and not o["ln"] and o["act"] in (0, 2) and o["out"] in ("T", "ps"))
 
 
+def conv64r_trip_tiles(nsl: int, ntiles: int):
+    """csrc/hat_conv3_tile.h conv3_groups, which hat_conv64r_launch has no query for: `int m = 32 / nsl; if (m < 1) m = 1;
+    while (m > 1 && 8LL * (m - 1) >= ntiles) --m;`, launched as nwps = 8 * m workgroups per slice
+    -> (nwps: 16 x 16 tiles over B that the workgroups of one 64-channel slice cover per trip, m).
+    test_srvgg_cpu.py holds it against the queries of the kernels that share the rule (hat_vgg_conv_tiles, hat_rdb_conv_tiles)."""
+    m = max(32 // nsl, 1)
+    while m > 1 and 8 * (m - 1) >= ntiles:
+        m -= 1
+    return 8 * m, m
+
+
 def lin_dtypes(cin: int, cout: int):
     """The instantiations hat_linear has for a shape (the fp32 image of the widest weights does not fit the LDS)."""
     from super_resolution_amd import ops

@@ -24,6 +24,7 @@ import torch
 import torch.nn.functional as F
 
 from helpers import _r8, check, conv_ref_banded, dev_randn, dev_rows, esc_weights_case, need_trips, q, rnd, run_chunked
+from lattice import conv64r_trip_tiles
 
 pytestmark = pytest.mark.gpu
 
@@ -48,15 +49,6 @@ LN_BLOCK_PIXELS = 16
 # hat_misc.hip esc_weights_kernel: `for (int k0 = pp; k0 < nblk; k0 += np * 8 * 4)`, np = 1024 / (16 or 32 floats per GAP block)
 ESCW_TRIP_BLOCKS = {16: 64 * 32, 32: 32 * 32}
 CONV64R_TILE = 16
-
-
-def conv64r_trip_tiles(nsl: int, ntiles: int):
-    """hat_conv64r.hip hat_conv64r_launch: `int m = 32 / nsl; ... while (m > 1 && 8 * (m - 1) >= ntiles) --m; nwps = 8 * m;`
-    -> (nwps: 16 x 16 tiles over B that the workgroups of one 64-channel slice cover per trip, m)."""
-    m = max(32 // nsl, 1)
-    while m > 1 and 8 * (m - 1) >= ntiles:
-        m -= 1
-    return 8 * m, m
 
 
 def _dev():

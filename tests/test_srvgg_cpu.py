@@ -196,6 +196,22 @@ def test_vgg_conv_rejects_bad_arguments_without_gpu(lib):
     assert q(1, 1, 1, _lib.HAT_F32) == 0 and (t.value, g.value, s.value) == (1, 8, 2)
 
 
+def test_resident_convs_share_one_schedule(lib):
+    """conv3_groups (csrc/hat_conv3_tile.h) through its two queries and the Python restatement the conv64r tests use: the same
+    workgroups per slice for the same (slices, tiles), whole groups of eight, at most 256 workgroups in all, no idle group."""
+    from lattice import conv64r_trip_tiles
+    from super_resolution_amd import ops
+    queries = {1: [lambda g: ops.vgg_conv_tiles(*g, ops.HAT_BF16), lambda g: ops.rdb_conv_tiles(*g, 64)],
+               2: [lambda g: ops.vgg_conv_tiles(*g, ops.HAT_F32), lambda g: ops.rdb_conv_tiles(*g, 192)]}
+    for tiles in list(range(1, 301)) + [2047, 2048, 2049, (1 << 20) + 1, (1 << 30) - 1, 1 << 30]:
+        geoms = [(tiles, 1, 1)] + ([(1, 1, 16 * tiles)] if tiles <= 300 else [])
+        for nsl, qs in queries.items():
+            got = {q(g) for q in qs for g in geoms}
+            wgs = conv64r_trip_tiles(nsl, tiles)[0]
+            assert got == {(tiles, wgs, nsl)}, (tiles, nsl, got, wgs)
+            assert wgs % 8 == 0 and wgs <= 256 // nsl and (wgs <= 8 or wgs - 8 < tiles), (tiles, nsl, wgs)
+
+
 # ---- the harness --------------------------------------------------------------------------------------------------------------
 def test_harness_parses_the_fixture_option_file():
     import yaml
